@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 n=${1:-8}
 for i in $(seq 1 $n); do
-  timeout 300 python bench.py --no-extras --steps 30 --warmup 6 2>/dev/null | tail -n 1 | python3 -c "
+  timeout 300 python bench.py --full --no-extras --steps 30 --warmup 6 2>/dev/null | tail -n 1 | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read()); k={t['kernel'].split(' ')[0][:22]: t.get('ms_per_client') for t in j['kernels']['top']}
 b=j.get('breakdown_ms_per_client') or {}

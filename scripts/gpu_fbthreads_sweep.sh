@@ -1,8 +1,9 @@
 #!/bin/bash
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-extras --steps 8 --warmup 2 > gpurun_out/fbt_$tag.json 2>/dev/null; python3 - <<PY
+T=$(mktemp -d)
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-extras --steps 8 --warmup 2 > $T/fbt_$tag.json 2>/dev/null; python3 - <<PY
 import json
-j=json.load(open("gpurun_out/fbt_$tag.json"))
+j=json.load(open("$T/fbt_$tag.json"))
 k={r["kernel"][:18]:round(r["ms_per_client"],2) for r in j["kernels"]["top"]}
 print("$tag", round(j["median_ms_per_step"],2), k)
 PY

@@ -16,8 +16,8 @@ timeout 600 bash scripts/gpu_c_host_bench.sh > $P/c_host.log 2>&1; cp gpurun_out
 # ONE client over several devices / ranks on the one GPU of the box: rehearsals of the control flow, NOT scaling numbers
 timeout 600 python bench.py --one-process --gpus 2 --steps 8 --warmup 3 --compact-tables 2>$P/op2.err | tail -1 > profiles/r06_rehearsal_split_one_process_2dev.json
 timeout 600 python bench.py --one-process --gpus 4 --n-partition 64 --steps 8 --warmup 3 --compact-tables 2>$P/op4.err | tail -1 > profiles/r06_rehearsal_split_one_process_4dev_p64.json
-ROFL_BENCH_BACKEND=gloo ROFL_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --gpus 2 --split-chunks --steps 8 --warmup 3 --compact-tables 2>$P/ranks2.err | tail -1 > profiles/r06_rehearsal_split_ranks2.json
-ROFL_BENCH_BACKEND=gloo ROFL_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 8 --warmup 3 --compact-tables 2>$P/ranks2w.err | tail -1 > profiles/r06_rehearsal_ranks2_weak_with_split_extra.json
+ROFL_BENCH_BACKEND=gloo ROFL_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --split-chunks --steps 8 --warmup 3 --compact-tables 2>$P/ranks2.err | tail -1 > profiles/r06_rehearsal_split_ranks2.json
+ROFL_BENCH_BACKEND=gloo ROFL_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --steps 8 --warmup 3 --compact-tables 2>$P/ranks2w.err | tail -1 > profiles/r06_rehearsal_ranks2_weak_with_split_extra.json
 ( cd scripts && ./ubench_fe9 ) > profiles/r06_fe9.txt 2>&1
 mkdir -p $P/profiles; cp profiles/r06_* $P/profiles/ 2>/dev/null
 ls $P $P/profiles

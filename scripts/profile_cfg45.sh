@@ -11,9 +11,9 @@ for c in 4 5; do
   cp $(find $OUT/stats$c -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_cfg${c}_kernel_stats.csv
   rm -rf $OUT/stats$c
 done
-timeout 900 python3 bench.py --config 4 --steps 8 --warmup 3 2>$OUT/b4.err | tail -1 > $OUT/${TAG}_bench_cfg4.json
-timeout 900 python3 bench.py --config 4 --n-partition 64 --steps 8 --warmup 3 2>$OUT/b4p64.err | tail -1 > $OUT/${TAG}_bench_cfg4_p64.json
-timeout 900 python3 bench.py --config 5 --steps 8 --warmup 3 2>$OUT/b5.err | tail -1 > $OUT/${TAG}_bench_cfg5.json
+timeout 900 python3 bench.py --full --config 4 --steps 8 --warmup 3 2>$OUT/b4.err | tail -1 > $OUT/${TAG}_bench_cfg4.json
+timeout 900 python3 bench.py --full --config 4 --n-partition 64 --steps 8 --warmup 3 2>$OUT/b4p64.err | tail -1 > $OUT/${TAG}_bench_cfg4_p64.json
+timeout 900 python3 bench.py --full --config 5 --steps 8 --warmup 3 2>$OUT/b5.err | tail -1 > $OUT/${TAG}_bench_cfg5.json
 timeout 900 python3 bench.py --config 4 --one-process --gpus 2 --steps 8 --warmup 3 2>$OUT/b4op.err | tail -1 > $OUT/${TAG}_bench_cfg4_one_process_2dev.json
 cp $OUT/${TAG}_*.json $OUT/${TAG}_*.csv profiles/ 2>/dev/null
 for f in $OUT/${TAG}_bench_*.json; do python3 -c "

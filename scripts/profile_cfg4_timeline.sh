@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 for mi in 1 3; do
   rm -rf $OUT/kt$mi
-  timeout 900 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt$mi -- python3 bench.py --config 4 --steps 1 --warmup 1 --multi-inflight $mi --no-cpu-baseline --hip-runtime process > $OUT/bench_mi$mi.json 2> $OUT/kt$mi.err
+  timeout 900 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt$mi -- python3 bench.py --full --config 4 --steps 1 --warmup 1 --multi-inflight $mi --no-cpu-baseline --hip-runtime process > $OUT/bench_mi$mi.json 2> $OUT/kt$mi.err
   python3 scripts/kt_overlap.py $OUT/kt$mi 0.45 > $OUT/${TAG}_cfg4_timeline_inflight$mi.txt 2>&1
   rm -rf $OUT/kt$mi
 done

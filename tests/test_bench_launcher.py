@@ -32,3 +32,22 @@ def test_world_size_mismatch_is_an_error():
     e = dict(os.environ); e.update(env); e.update({"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29999"})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], env=e, capture_output=True, text=True, timeout=120)
     assert r.returncode == 2
+
+
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path):
+    """--dump-outputs: byte arrays come back as exact float32; one too large for its share of the budget is a fixed, seeded sample of its
+    elements with their flat indices, the same from call to call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.arange(4 * 1440, dtype=np.int64).reshape(4, 1440) % 256
+    big = np.resize(np.arange(251, dtype=np.uint8), bench.DUMP_BUDGET // 2)      # 4 x that in float32: over its half of the budget
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"proofs": small.astype(np.uint8), "commitments": big, "verified": np.ones(1, np.float32)})
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("proofs", "commitments", "commitments_index", "verified")}
+    assert got["proofs"].dtype == np.float32 and got["proofs"].shape == (4, 1440) and (got["proofs"] == small).all()
+    idx = got["commitments_index"].astype(np.int64)
+    assert got["commitments"].dtype == np.float32 and got["commitments"].size == idx.size > 1000 and (np.diff(idx) > 0).all()
+    assert (got["commitments"] == big[idx]).all() and got["verified"].tolist() == [1.0]
+    assert sum(os.path.getsize(str(p)) for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    assert all((np.load(str(tmp_path / "b" / f.name)) == np.load(str(f))).all() for f in (tmp_path / "a").iterdir())

@@ -79,9 +79,9 @@ def test_two_ranks_hip_product_cross_verify():
 
 
 def test_bench_two_ranks_report_the_one_client_split():
-    """Every N > 1 line of the headline config carries, beside its weak-scaling value, ONE client split by chunks over the ranks,
+    """Every N > 1 line of the headline config with --full carries, beside its weak-scaling value, ONE client split by chunks over the ranks,
     and `--split-chunks` makes that the timed workload (strong scaling).  Two ranks on GPU 0 over gloo here."""
-    line = _bench_two_ranks("--steps", "2", "--warmup", "1", "--no-cpu-baseline")      # bench.py --gpus 2 (no torchrun): the launcher starts the two ranks itself
+    line = _bench_two_ranks("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full")      # bench.py --gpus 2 (no torchrun): the launcher starts the two ranks itself
     assert line["n_gpus"] == 2 and line["rccl_world_size"] == 2 and line["steps"] == 2
     assert line["value"] > 0 and "cfg 2" in line["config"]["workload"]
     sp = line["one_client_split_over_ranks"]
@@ -182,6 +182,27 @@ def test_headline_runs_on_the_system_hip_runtime_and_falls_back():
     assert "repeating on the process's runtime" in r.stderr
     j = json.loads(r.stdout.strip().splitlines()[-1])
     assert not any(x.startswith("/opt/rocm") for x in j["config"]["hip_runtime"]) and j["value"] > 0
+
+
+def test_headline_dumps_what_its_last_step_returned(tmp_path):
+    """bench.py --dump-outputs DIR: the proofs, commitments and verdict of the LAST timed step as float32 arrays.  Two plain runs whose last
+    step is the same seeded client (warm-up + steps - 1 = 2) write the same arrays, and the proofs verify against the commitments (oracle)."""
+    import orc
+    lines, outs = [], []
+    for k, w in ((2, 1), (1, 2)):
+        d = tmp_path / ("k%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(k), "--warmup", str(w), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        outs.append({n: np.load(str(d / (n + ".npy"))) for n in ("proofs", "commitments", "verified")})
+    for j, k in zip(lines, (2, 1)):
+        assert j["steps"] == k and j["ms_per_step"] > 0 and len(j["step_ms"]) == k
+        assert not any(x in j for x in ("kernels", "roofline", "cpu_baseline", "baseline_configs"))      # a plain run: the headline only
+    a, b = outs
+    assert a["proofs"].dtype == np.float32 and a["proofs"].shape == (4, 1440) and a["commitments"].shape == (25000, 32) and a["verified"].tolist() == [1.0]
+    assert all((a[n] == b[n]).all() for n in a)
+    assert orc.verify_rangeproof(a["proofs"].astype(np.uint8), a["commitments"].astype(np.uint8), 32, 32, 7) == (0, True)
 
 
 _LIB_RCCL_WORLD1 = r"""

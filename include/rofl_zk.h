@@ -254,6 +254,32 @@ int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, fl
  * either direction returns 11 (the reference unwraps None). */
 int rofl_discrete_log_vec(const uint8_t *points32, size_t d, size_t table_size, unsigned bsgs_bits, uint8_t *scalars_out32);
 
+/* ---- server-side aggregation on the device (params.rs:74-147 EncModelParamsAccumulator, server.rs:504-507, 696-714) ----
+ * A round's running sum of d ElGamal pairs kept on the device: every record is decoded once and added in extended coordinates, nothing
+ * is encoded until export or extraction.  A handle names an accumulator in the library's registry (it is not a pointer): an unknown or
+ * destroyed handle returns 11, so does a second destroy.  Parameter checks (11) come before the device is touched.  The accumulator lives
+ * on the device of the thread that created it and every later call runs there, whatever the calling thread is bound to.  Calls on one
+ * accumulator are serialised; calls on different accumulators run side by side on the device's lanes.
+ *   init 0: identity pairs, unity check R == identity (the sums EncModelParamsAccumulator of the Python package returns: the true sum);
+ *   init 1: ElGamalPair::unity() = (B, B), unity check R == B (params.rs:173, 176; el_gamal.rs:83-88, 101-103) -- the reference's bytes,
+ *           whose aggregate is the sum plus one raw fixed-point unit per coordinate. */
+int rofl_acc_create(size_t d, int init, uint64_t *handle_out);
+/* Adds n_clients updates: client c's records are read every `stride` >= 64 bytes from records[c] (64: ElGamalPair; 96:
+ * SquareRandProofCommitments, whose ElGamal pair c is the first 64 bytes), host (pageable or pinned) or device memory, in place.  Client c
+ * adds records 0 .. min(d_each[c], d) (d_each NULL: d each) -- the zip truncation of gamal_accumulate (params.rs:81-90).  All or nothing:
+ * if any record of the call does not decode (invalid or non-canonical encoding) the call returns 5 and the accumulator is unchanged. */
+int rofl_acc_add(uint64_t h, size_t n_clients, const uint8_t *const *records, const size_t *d_each, size_t stride);
+/* d x 64 bytes: the encodings of the current sums.  The exports of init-0 accumulators are ordinary records: partial sums of several
+ * devices or ranks merge by adding them to one accumulator with rofl_acc_add (create partials with init 0: an init-1 partial counts B twice). */
+int rofl_acc_export(uint64_t h, uint8_t *pairs_out);
+/* EncModelParamsAccumulator::extract: the unity check of every R on the device (failed: *ok_out = 0, return 0 -- the reference's None),
+ * else every L is encoded and solved on the device with the baby-step table of table_size (the cache of rofl_discrete_log_vec), and the
+ * logs are converted to f32 (conversion32.rs:24-39).  The same values and errors as rofl_discrete_log_vec + rofl_scalar_to_f32_vec over the
+ * exported L, 11 for a log that is not found included. */
+int rofl_acc_extract(uint64_t h, size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac, float *out, int *ok_out);
+int rofl_acc_reset(uint64_t h);      /* back to the initial state of its init */
+int rofl_acc_destroy(uint64_t h);    /* frees the device memory; the handle is invalid afterwards (after a HIP error only destroy accepts it again) */
+
 /* ---- wire formats of the encrypted update containers ----
  * proto3 messages of rofl_service/proto/roflservice/flservice.proto:75-100, length-delimited as written by
  * EncParamsRange::serialize (params.rs:513-527; EncParamsRangeCompressed :745-759 uses the same message with the 128-byte

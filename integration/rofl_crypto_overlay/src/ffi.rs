@@ -72,6 +72,15 @@ extern "C" {
     pub fn rofl_add_points_vec(a32: *const u8, b32: *const u8, d: usize, out32: *mut u8) -> c_int;
     pub fn rofl_shift_points(a32: *const u8, d: usize, offset32: *const u8, out32: *mut u8) -> c_int;
     pub fn rofl_discrete_log_vec(points32: *const u8, d: usize, table_size: usize, bsgs_bits: c_uint, scalars_out32: *mut u8) -> c_int;
+    /// server-side aggregation on the device (EncModelParamsAccumulator, params.rs:74-147): a handle from the library's registry;
+    /// init 1 = ElGamalPair::unity() = (B, B), the reference's bytes
+    pub fn rofl_acc_create(d: usize, init: c_int, handle_out: *mut u64) -> c_int;
+    pub fn rofl_acc_add(h: u64, n_clients: usize, records: *const *const u8, d_each: *const usize, stride: usize) -> c_int;
+    pub fn rofl_acc_export(h: u64, pairs_out: *mut u8) -> c_int;
+    pub fn rofl_acc_extract(h: u64, table_size: usize, bsgs_bits: c_uint, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float,
+        ok_out: *mut c_int) -> c_int;
+    pub fn rofl_acc_reset(h: u64) -> c_int;
+    pub fn rofl_acc_destroy(h: u64) -> c_int;
 
     // ---- the rest of include/rofl_zk.h (scripts/check_ffi.py keeps this block and the header in step: names and arity)
     pub fn rofl_bp_gens_export(n_bits: usize, m: usize, g_out: *mut u8, h_out: *mut u8) -> c_int;

@@ -804,9 +804,8 @@ class pedersen_ops:
     @staticmethod
     def default_discrete_log_vec(points, fp=None):
         """pedersen_ops.rs:27-35: BSGSTable::default() = 2^(BSGS_N_BITS/2 + PRECOMP_BIAS) entries (fp.rs)."""
-        fb = _fp(fp)[0]
-        bits, bias = {8: (8, 3), 16: (16, 7), 32: (16, 7), 64: (16, 0)}[fb]
-        return pedersen_ops.discrete_log_vec(points, 1 << (bits // 2 + bias), bits)
+        table_size, bits = default_bsgs(fp)
+        return pedersen_ops.discrete_log_vec(points, table_size, bits)
 
     @staticmethod
     def compute_shifted_values_rp(points, offset):
@@ -815,6 +814,51 @@ class pedersen_ops:
         out = np.zeros_like(p)
         _check(lib().rofl_shift_points(_ptr(p), _sz(p.shape[0]), _ptr(o), _ptr(out)))
         return out
+
+
+class accumulator:
+    """rofl_acc_*: a round's running sum of ElGamal pairs resident on the device (params.rs:74-147).  Handles are registry ids; records are
+    host arrays or GPU tensors (read in place, every `stride` bytes)."""
+    @staticmethod
+    def create(d, init=0):
+        h = ctypes.c_uint64()
+        _check(lib().rofl_acc_create(_sz(d), int(init), ctypes.byref(h)))
+        return h.value
+
+    @staticmethod
+    def add(h, records, counts, stride):
+        """records: one pointer (int / c_void_p) per client; counts: records of each client (truncated to d by the library)"""
+        n = len(records)
+        rp = (ctypes.c_void_p * max(n, 1))(*records)
+        cp = (_sz * max(n, 1))(*[int(c) for c in counts])
+        _check(lib().rofl_acc_add(ctypes.c_uint64(h), _sz(n), rp, cp, _sz(stride)))
+
+    @staticmethod
+    def export(h, d):
+        out = np.zeros((d, 64), dtype=np.uint8)
+        _check(lib().rofl_acc_export(ctypes.c_uint64(h), _ptr(out)))
+        return out
+
+    @staticmethod
+    def extract(h, d, table_size, bsgs_bits, fp):
+        out = np.zeros(d, dtype=np.float32)
+        ok = ctypes.c_int()
+        _check(lib().rofl_acc_extract(ctypes.c_uint64(h), _sz(table_size), int(bsgs_bits), *fp, _ptr(out), ctypes.byref(ok)))
+        return out if ok.value else None
+
+    @staticmethod
+    def reset(h):
+        _check(lib().rofl_acc_reset(ctypes.c_uint64(h)))
+
+    @staticmethod
+    def destroy(h):
+        _check(lib().rofl_acc_destroy(ctypes.c_uint64(h)))
+
+
+def default_bsgs(fp=None):
+    """(table_size, bsgs_bits) of BSGSTable::default() for the fixed-point type (fp.rs; pedersen_ops.rs:27-35)"""
+    bits, bias = {8: (8, 3), 16: (16, 7), 32: (16, 7), 64: (16, 0)}[_fp(fp)[0]]
+    return 1 << (bits // 2 + bias), bits
 
 
 class conversion32:

@@ -2675,6 +2675,59 @@ __global__ void __launch_bounds__(TPB) k_decode_pairs(u32 d, const uint8_t *pair
 }
 #endif
 
+// ================================================================ server-side aggregation on the device (params.rs:74-147 gamal_accumulate / extract)
+// The round's running sum of ElGamal pairs stays resident in HBM as extended points (ge; pair j = sum[2j] L, sum[2j + 1] R).  An add of
+// a group of clients decodes every record once (k_acc_decode_partial), one thread per (point, L or R, client slice); the S slice partials
+// are added into the sum by k_acc_fold.  Nothing is encoded until export / extraction (k_acc_finish).
+//
+// One tile of points [j0, j0 + tn) of a group of nc clients: client k's records of the tile are packed 64-byte ElGamal pairs at
+// rec + 64 * off[k], cnt[k] of them (zip truncation: a client shorter than the tile covers a prefix).  Thread t = (s, j, which) sums the
+// records of clients s, s + S, s + 2S, ... into part[t] = part[(s * tn + j) * 2 + which]; a record that does not decode sets bit 4 of *status.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_acc_decode_partial(u32 tn, u32 S, u32 nc, const u64 *off, const u32 *cnt, const uint8_t *rec, ge *part, u32 *status) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)2 * tn * S) return;
+    const u32 s = (u32)(t / (2 * (size_t)tn)), r = (u32)(t % (2 * (size_t)tn)), j = r >> 1, which = r & 1;
+    gd acc = gd_identity();
+    for (u32 k = s; k < nc; k += S) {
+        if (j >= cnt[k]) continue;
+        const uint8_t *src = rec + (off[k] + j) * 64 + 32 * which;
+        __align__(16) uint8_t b[32];
+        reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
+        gd p;
+        if (!gd_ristretto_decode(p, b)) { atomicOr(status, 4u); continue; }
+        acc = gd_add(acc, p);
+    }
+    store_gd(&part[t], acc);
+}
+#endif
+// dst[t] = (src ? src[t] : init) + sum_s part[s * n + t], t < n (n = 2 x points).  Returns at once when *status says a decode of this call
+// failed: the accumulator is left as it was (all or nothing) without a host round trip.  S = 0 with src = null: reset to the initial state.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_acc_fold(u32 n, u32 S, const ge *part, const ge *src, ge init, ge *dst, const u32 *status) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    if (status && (*(volatile const u32 *)status & 4u)) return;
+    gd acc = src ? load_gd(&src[t]) : gd_unpack(init);
+    for (u32 s = 0; s < S; s++) acc = gd_add(acc, load_gd(&part[(size_t)s * n + t]));
+    store_gd(&dst[t], acc);
+}
+#endif
+// mode 0 (extract): one thread per pair -- the unity check of R (Ristretto equality with (bx, by): identity (0, 1) for init 0, the basepoint
+// for init 1 -- X1 Y2 == Y1 X2 or Y1 Y2 == X1 X2; a sum of decoded points may be any representative of its coset), a failure ORs 1 into
+// *flag; then L is encoded into out[j] (d x 32, the input of k_bsgs_solve).  mode 1 (export): one thread per point, out = d x 64 pairs.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_acc_finish(u32 d, int mode, const ge *sum, fe bx, fe by, uint8_t *out, u32 *flag) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (mode ? 2 * d : d)) return;
+    if (mode) { gd_ristretto_encode(out + (size_t)32 * t, load_gd(&sum[t])); return; }
+    gd R = load_gd(&sum[2 * (size_t)t + 1]);
+    fd X = fd_unpack(bx), Y = fd_unpack(by);
+    if (!(fd_eq(fd_mul(R.X, Y), fd_mul(R.Y, X)) || fd_eq(fd_mul(R.Y, Y), fd_mul(R.X, X)))) atomicOr(flag, 1u);
+    gd_ristretto_encode(out + (size_t)32 * t, load_gd(&sum[2 * (size_t)t]));
+}
+#endif
+
 // ================================================================ BSGS discrete log (bsgs32.rs:14-73, pedersen_ops.rs:27-53)
 // Baby-step table: keys[x] = compress(x B), x = 0..m, indexed by an open-addressing hash table (slot = first 8 key
 // bytes, linear probing) that lives in HBM; one thread per point walks the giant steps.

@@ -116,6 +116,26 @@ void timing_end(Ctx &C) {
 }
 
 
+// BSGSTable::new(table_size) on the device, built once per table_size and cached on the device's primary lane (callers hold it: acquire_lane(true)),
+// then one k_bsgs_solve over the d compressed points at dp (device) -> canonical scalars at dout; status bit 8: a log that was not found
+void bsgs_solve_launch(Ctx &C, size_t d, const uint8_t *dp, size_t table_size, unsigned bsgs_bits, uint8_t *dout, u32 *status) {
+    auto it = C.bsgs.find(table_size);
+    if (it == C.bsgs.end()) {
+        Ctx::Bsgs b; u32 nslots = 1; while (nslots < 2 * (table_size + 1)) nslots <<= 1;
+        b.mask = nslots - 1;
+        HIPCHK(hipMalloc(&b.keys, 32 * (table_size + 1))); HIPCHK(hipMalloc(&b.slots, sizeof(u32) * nslots));
+        HIPCHK(hipMemsetAsync(b.slots, 0, sizeof(u32) * nslots, C.stream));
+        ROFL_LAUNCH(k_bsgs_build, dim3((unsigned)((table_size + 1 + 63) / 64)), dim3(64), 0, C.stream, (u32)table_size, C.d_tabB, b.keys, b.slots, b.mask);
+        it = C.bsgs.emplace(table_size, b).first;
+    }
+    const Ctx::Bsgs &B = it->second;
+    u64 mask = bsgs_bits >= 32 ? 0xffffffffULL : ((1ULL << bsgs_bits) - 1);
+    // mG = B * Scalar::from(m as BSGS_URawFix)  (bsgs32.rs:18): the multiplier wraps to bsgs_bits bits
+    niels neg_mG = h51::to_niels32(h_fixed_mul(C.ht.B5, sc_neg(sc_from_u64((u64)table_size & mask))));
+    u64 max_it = (1ULL << bsgs_bits) / table_size;
+    ROFL_LAUNCH(k_bsgs_solve, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, C.stream, (u32)d, dp, (u32)table_size, bsgs_bits, max_it, neg_mG, B.keys, B.slots, B.mask, dout, status);
+}
+
 constexpr size_t kMaxBatchMembers = 65535;      // gridDim.y: what a batch entry point accepts in one call (the launches themselves are checked too, ROFL_LAUNCH)
 
 template <class F> int guarded(F f) {
@@ -559,6 +579,119 @@ int verify_split(const std::vector<int> &devs, const uint8_t *proofs, size_t pro
 }
 // can this (d, n_proofs) set be split?  Only the regular case: the proofs cover the padded vector exactly
 bool verify_splittable(size_t d, size_t n_proofs) { if (!d || n_proofs < 2) return false; size_t dp = next_pow2(d); return n_proofs <= dp && (dp / n_proofs) * n_proofs == dp; }
+
+// ---------------------------------------------------------------- server-side aggregation on the device (rofl_acc_*; params.rs:74-147)
+// An accumulator is a resident d x 2 array of extended points on the device of the thread that created it, named by a handle from this
+// registry (never a pointer: an unknown or destroyed handle is a bad parameter, not a crash).  Calls on one accumulator are serialised by
+// its lock; calls on different accumulators take different lanes of their device.
+struct Acc {
+    int device = 0, init = 0; size_t d = 0;
+    ge *sum = nullptr;      // [d][2]: L, R of every pair
+    ge *work = nullptr;     // a copy of sum for an add that takes several passes (all or nothing: committed by the last fold); allocated on first use
+    std::mutex mu; bool dead = false, released = false;      // dead: being or been destroyed (every call but destroy refuses it); released: memory freed
+};
+std::mutex g_acc_mu;
+std::map<uint64_t, std::shared_ptr<Acc>> g_accs;
+uint64_t g_acc_next = 1;
+std::shared_ptr<Acc> acc_find(uint64_t h) { std::lock_guard<std::mutex> lk(g_acc_mu); auto it = g_accs.find(h); return it == g_accs.end() ? nullptr : it->second; }
+// the initial state of every pair and the R of the unity check: init 0 the identity, init 1 ElGamalPair::unity() = (B, B) (el_gamal.rs:83-88)
+ge acc_init_point(int init) {
+    if (!init) return ge_identity();
+    static const uint8_t kB[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
+                                   0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};      // RISTRETTO_BASEPOINT_COMPRESSED
+    ge b; ristretto_decode(b, kB); return b;
+}
+void acc_reset_launch(Ctx &C, Acc &A) {
+    ROFL_LAUNCH(k_acc_fold, grid1(2 * A.d), dim3(TPB), 0, C.stream, (u32)(2 * A.d), 0u, (const ge *)nullptr, (const ge *)nullptr, acc_init_point(A.init), A.sum, (const u32 *)nullptr);
+}
+// Points are taken in tiles of kAccTile; the clients of a tile in groups of at most kAccGroupRecords records (the device copy of a group's
+// records and the S x tile partials are the only scratch, whatever the round's size).  Per group: the records are packed into 64-byte
+// pairs (host memory: one parallel gather into pinned staging + one upload; device memory: a strided device-to-device copy), one
+// k_acc_decode_partial with S client slices, one k_acc_fold.  S is chosen so that the decode launch has ~4 waves per SIMD (256 CUs x 4
+// SIMDs; the decode chain runs at one wave per SIMD).  A group holds at most 1.5 M records (96 MB of packed pairs): the two staging buffers
+// of a call with several groups and its small per-group arrays stay inside the 256 MB of pinned memory a lane keeps between calls
+// (Stage::finish, ROFL_STAGE_KEEP_MB) -- larger buffers would be released and pinned again by every add.
+constexpr size_t kAccTile = (size_t)1 << 17, kAccGroupRecords = (size_t)3 << 19, kAccThreads = (size_t)256 * 4 * 4 * 64;
+int acc_add_impl(Ctx &C, Acc &A, const std::vector<size_t> &cl, const std::vector<size_t> &nrec, const uint8_t *const *records, size_t stride) {
+    const size_t d = A.d;
+    size_t max_n = 0; for (size_t n : nrec) max_n = std::max(max_n, n);
+    const size_t tile = std::min(max_n, kAccTile), ntiles = (max_n + tile - 1) / tile;
+    size_t first_tile = 0; for (size_t n : nrec) first_tile += std::min(n, tile);
+    const size_t rec_cap = std::min(first_tile, kAccGroupRecords);      // no group of any tile holds more records than the first tile's clients
+    const size_t S_max = std::max<size_t>(1, std::min(cl.size(), (kAccThreads + 2 * tile - 1) / (2 * tile)));
+    const bool multi = ntiles > 1 || first_tile > kAccGroupRecords;
+    C.init();
+    uint8_t *rec = C.tmp_in.as<uint8_t>(rec_cap * 64);
+    ge *part = C.partial2.as<ge>(S_max * tile * 2);
+    u64 *d_off = C.tmp_in2.as<u64>(cl.size()); u32 *d_cnt = C.tmp_out.as<u32>(cl.size());
+    u32 *status = C.status.as<u32>(4);
+    HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
+    ge *tgt = A.sum;
+    if (multi) {
+        if (!A.work) HIPCHK(hipMalloc(&A.work, sizeof(ge) * 2 * d));
+        HIPCHK(hipMemcpyAsync(A.work, A.sum, sizeof(ge) * 2 * d, hipMemcpyDeviceToDevice, C.stream));
+        tgt = A.work;
+    }
+    // (host work per call is O(clients): one pointer query per client here and, per group, one strided copy per device-resident client --
+    //  ~1-2 us each, nothing at a round's 48 clients, about a second per add of 10^6 single-record clients)
+    std::vector<char> on_dev(cl.size());
+    for (size_t k = 0; k < cl.size(); k++) on_dev[k] = is_device_ptr(records[cl[k]]);
+    const ge init = acc_init_point(A.init);
+    uint8_t *stb[2] = {nullptr, nullptr}; size_t gi = 0;
+    for (size_t t = 0; t < ntiles; t++) {
+        const size_t j0 = t * tile;
+        size_t k = 0;
+        while (k < cl.size()) {
+            // the next group: clients k.. that reach into this tile, up to kAccGroupRecords records
+            std::vector<size_t> gk; std::vector<u64> off; std::vector<u32> cnt; size_t nr = 0, tn = 0;
+            for (; k < cl.size(); k++) {
+                if (nrec[k] <= j0) continue;
+                size_t c = std::min(nrec[k] - j0, tile);
+                if (nr + c > kAccGroupRecords && !gk.empty()) break;
+                gk.push_back(k); off.push_back(nr); cnt.push_back((u32)c); nr += c; tn = std::max(tn, c);
+            }
+            if (gk.empty()) break;
+            const size_t gc = gk.size();
+            // host clients: gathered into pinned staging on the pool (the gather is the packing: the first 64 bytes of every record)
+            bool any_host = false; for (size_t q : gk) any_host |= !on_dev[q];
+            if (any_host) {
+                // two staging buffers: the gather of group g + 1 runs while the device works on group g (a buffer is reused once its upload is done)
+                const int b = (int)(gi & 1);
+                if (!stb[b]) stb[b] = (uint8_t *)C.stg.alloc(rec_cap * 64);
+                else C.wait_event(C.pool_event(b));
+                uint8_t *st = stb[b];
+                const size_t per = (size_t)1 << 12;      // records per task (256 KB)
+                std::vector<std::pair<size_t, size_t>> tasks;      // (group member, first record)
+                for (size_t g = 0; g < gc; g++) if (!on_dev[gk[g]]) for (size_t e = 0; e < cnt[g]; e += per) tasks.push_back({g, e});
+                C.pool->run(tasks.size(), [&](size_t ti) {
+                    const size_t g = tasks[ti].first, e0 = tasks[ti].second, e1 = std::min<size_t>(cnt[g], e0 + per);
+                    const uint8_t *src = records[cl[gk[g]]] + (j0 + e0) * stride; uint8_t *dst = st + (off[g] + e0) * 64;
+                    if (stride == 64) stage_copy(dst, src, (e1 - e0) * 64);
+                    else for (size_t e = e0; e < e1; e++) memcpy(dst + (e - e0) * 64, src + (e - e0) * stride, 64);
+                });
+                HIPCHK(hipMemcpyAsync(rec, st, nr * 64, hipMemcpyHostToDevice, C.stream));
+                HIPCHK(hipEventRecord(C.pool_event(b), C.stream));
+            }
+            gi++;
+            for (size_t g = 0; g < gc; g++)      // device clients: after the upload, which carries no bytes of theirs
+                if (on_dev[gk[g]]) HIPCHK(hipMemcpy2DAsync(rec + off[g] * 64, 64, records[cl[gk[g]]] + j0 * stride, stride, 64, cnt[g], hipMemcpyDeviceToDevice, C.stream));
+            u64 *h_off = (u64 *)C.stg.alloc(gc * 8); u32 *h_cnt = (u32 *)C.stg.alloc(gc * 4);
+            memcpy(h_off, off.data(), gc * 8); memcpy(h_cnt, cnt.data(), gc * 4);
+            HIPCHK(hipMemcpyAsync(d_off, h_off, gc * 8, hipMemcpyHostToDevice, C.stream));
+            HIPCHK(hipMemcpyAsync(d_cnt, h_cnt, gc * 4, hipMemcpyHostToDevice, C.stream));
+            const size_t S = std::min(S_max, gc);
+            ROFL_LAUNCH(k_acc_decode_partial, grid1(2 * tn * S), dim3(TPB), 0, C.stream, (u32)tn, (u32)S, (u32)gc, (const u64 *)d_off, (const u32 *)d_cnt, (const uint8_t *)rec, part, status);
+            ROFL_LAUNCH(k_acc_fold, grid1(2 * tn), dim3(TPB), 0, C.stream, (u32)(2 * tn), (u32)S, (const ge *)part, (const ge *)(tgt + 2 * j0), init, tgt + 2 * j0, (const u32 *)status);
+        }
+    }
+    if (multi)      // commit: sum <- work, unless a decode of the call failed
+        ROFL_LAUNCH(k_acc_fold, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)(2 * d), 0u, (const ge *)nullptr, (const ge *)A.work, init, A.sum, (const u32 *)status);
+    u32 st = 0;
+    HIPCHK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    if (st & 4u) return fail(ROFL_FORMAT_ERROR, "FormatError: a record is not a valid Ristretto encoding (the accumulator is unchanged)");
+    return ROFL_OK;
+}
 }  // namespace
 
 // ================================================================ C ABI
@@ -1576,25 +1709,11 @@ int rofl_discrete_log_vec(const uint8_t *points32, size_t d, size_t table_size, 
         if (d == 0) return ROFL_OK;
         C.init();
         timing_begin(C);
-        auto it = C.bsgs.find(table_size);
-        if (it == C.bsgs.end()) {
-            Ctx::Bsgs b; u32 nslots = 1; while (nslots < 2 * (table_size + 1)) nslots <<= 1;
-            b.mask = nslots - 1;
-            HIPCHK(hipMalloc(&b.keys, 32 * (table_size + 1))); HIPCHK(hipMalloc(&b.slots, sizeof(u32) * nslots));
-            HIPCHK(hipMemsetAsync(b.slots, 0, sizeof(u32) * nslots, C.stream));
-            ROFL_LAUNCH(k_bsgs_build, dim3((unsigned)((table_size + 1 + 63) / 64)), dim3(64), 0, C.stream, (u32)table_size, C.d_tabB, b.keys, b.slots, b.mask);
-            it = C.bsgs.emplace(table_size, b).first;
-        }
-        const Ctx::Bsgs &B = it->second;
-        u64 mask = bsgs_bits >= 32 ? 0xffffffffULL : ((1ULL << bsgs_bits) - 1);
-        // mG = B * Scalar::from(m as BSGS_URawFix)  (bsgs32.rs:18): the multiplier wraps to bsgs_bits bits
-        niels neg_mG = h51::to_niels32(h_fixed_mul(C.ht.B5, sc_neg(sc_from_u64((u64)table_size & mask))));
-        u64 max_it = (1ULL << bsgs_bits) / table_size;
         uint8_t *dp = C.tmp_in.as<uint8_t>(d * 32), *dout = C.Cbytes.as<uint8_t>(d * 32);
         u32 *status = C.status.as<u32>(4);
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
         C.up(dp, points32, 32 * d, C.stream);
-        ROFL_LAUNCH(k_bsgs_solve, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, C.stream, (u32)d, dp, (u32)table_size, bsgs_bits, max_it, neg_mG, B.keys, B.slots, B.mask, dout, status);
+        bsgs_solve_launch(C, d, dp, table_size, bsgs_bits, dout, status);
         u32 st = 0;
         C.down(scalars_out32, dout, 32 * d, C.stream);
         HIPCHK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, C.stream));
@@ -1604,6 +1723,129 @@ int rofl_discrete_log_vec(const uint8_t *points32, size_t d, size_t table_size, 
         if (st & 8u) return fail(ROFL_BAD_PARAM, "discrete log not found (the reference unwraps None)");
         return ROFL_OK;
     });
+}
+// ---- server-side aggregation on the device (params.rs:74-147, server.rs:504-507, 696-714) ----
+int rofl_acc_create(size_t d, int init, uint64_t *handle_out) {
+    if (!handle_out || d == 0 || (init != 0 && init != 1)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (d >= ((size_t)1 << 31)) return fail(ROFL_BAD_PARAM, "accumulator too large");
+    auto A = std::make_shared<Acc>();
+    A->d = d; A->init = init; A->device = current_device();
+    DeviceBinding bind(A->device);
+    int rc = guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        HIPCHK(hipMalloc(&A->sum, sizeof(ge) * 2 * d));
+        acc_reset_launch(C, *A);
+        C.sync();
+        return ROFL_OK;
+    });
+    if (rc) { if (A->sum) (void)hipFree(A->sum); return rc; }
+    std::lock_guard<std::mutex> lk(g_acc_mu);
+    uint64_t h = g_acc_next++;
+    g_accs.emplace(h, A);
+    *handle_out = h;
+    return ROFL_OK;
+}
+int rofl_acc_add(uint64_t h, size_t n_clients, const uint8_t *const *records, const size_t *d_each, size_t stride) {
+    if (stride < 64 || (n_clients && !records)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::shared_ptr<Acc> A = acc_find(h);
+    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    size_t bytes;
+    if (__builtin_mul_overflow(n_clients, A->d, &bytes) || __builtin_mul_overflow(bytes, stride, &bytes)) return fail(ROFL_BAD_PARAM, "batch too large");
+    std::vector<size_t> cl, nrec;      // the clients that add anything: zip truncation to the accumulator's length (params.rs:81-90)
+    for (size_t c = 0; c < n_clients; c++) {
+        size_t n = std::min(d_each ? d_each[c] : A->d, A->d);
+        if (!n) continue;
+        if (!records[c]) return fail(ROFL_BAD_PARAM, "bad parameter");
+        cl.push_back(c); nrec.push_back(n);
+    }
+    std::lock_guard<std::mutex> lk(A->mu);
+    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    if (cl.empty()) return ROFL_OK;
+    DeviceBinding bind(A->device);
+    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); return acc_add_impl(*lane_lock.c, *A, cl, nrec, records, stride); });
+}
+int rofl_acc_export(uint64_t h, uint8_t *pairs_out) {
+    if (!pairs_out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::shared_ptr<Acc> A = acc_find(h);
+    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    std::lock_guard<std::mutex> lk(A->mu);
+    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    DeviceBinding bind(A->device);
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        const size_t d = A->d;
+        uint8_t *o = C.Cbytes.as<uint8_t>(d * 64);
+        const ge b = acc_init_point(A->init);
+        ROFL_LAUNCH(k_acc_finish, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)d, 1, (const ge *)A->sum, b.X, b.Y, o, (u32 *)nullptr);
+        C.down(pairs_out, o, d * 64, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
+int rofl_acc_extract(uint64_t h, size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac, float *out, int *ok_out) {
+    if (!out || !ok_out || table_size == 0 || table_size >= (1u << 30) || !(bsgs_bits == 8 || bsgs_bits == 16 || bsgs_bits == 32) || !valid_fp(fp_bits, fp_frac))
+        return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::shared_ptr<Acc> A = acc_find(h);
+    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    std::lock_guard<std::mutex> lk(A->mu);
+    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    DeviceBinding bind(A->device);
+    std::vector<uint8_t> hv;      // (outlives the lane: its release delivers the staged scalars here)
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(true); Ctx &C = *lane_lock.c;      // the primary lane: the baby-step tables rofl_discrete_log_vec caches
+        C.init();
+        const size_t d = A->d;
+        uint8_t *enc = C.tmp_in.as<uint8_t>(d * 32), *dout = C.Cbytes.as<uint8_t>(d * 32);
+        u32 *status = C.status.as<u32>(4);
+        HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
+        const ge b = acc_init_point(A->init);
+        ROFL_LAUNCH(k_acc_finish, grid1(d), dim3(TPB), 0, C.stream, (u32)d, 0, (const ge *)A->sum, b.X, b.Y, enc, status + 1);
+        u32 st[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(st, status, 8, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        if (st[1]) { *ok_out = 0; return ROFL_OK; }      // some R is not the initial one: the blindings did not cancel (the reference's None)
+        bsgs_solve_launch(C, d, enc, table_size, bsgs_bits, dout, status);
+        hv.resize(d * 32);
+        const uint8_t *hs = (const uint8_t *)C.down(hv.data(), dout, d * 32, C.stream);
+        HIPCHK(hipMemcpyAsync(st, status, 4, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        if (st[0] & 4u) return fail(ROFL_FORMAT_ERROR, "invalid Ristretto encoding");
+        if (st[0] & 8u) return fail(ROFL_BAD_PARAM, "discrete log not found (the reference unwraps None)");
+        for (size_t i = 0; i < d; i++) out[i] = sc_to_f32(sc_frombytes(hs + 32 * i), fp_bits, fp_frac);
+        *ok_out = 1;
+        return ROFL_OK;
+    });
+}
+int rofl_acc_reset(uint64_t h) {
+    std::shared_ptr<Acc> A = acc_find(h);
+    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    std::lock_guard<std::mutex> lk(A->mu);
+    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    DeviceBinding bind(A->device);
+    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c; C.init(); acc_reset_launch(C, *A); C.sync(); return ROFL_OK; });
+}
+int rofl_acc_destroy(uint64_t h) {
+    std::shared_ptr<Acc> A = acc_find(h);
+    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    std::lock_guard<std::mutex> lk(A->mu);
+    if (A->released) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");      // destroyed by another thread meanwhile
+    A->dead = true;      // from here on only a destroy may use the handle (a failed one leaves it in the registry for another try)
+    DeviceBinding bind(A->device);
+    int rc = guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane();
+        if (A->sum) HIPCHK(hipFree(A->sum));
+        A->sum = nullptr;
+        if (A->work) HIPCHK(hipFree(A->work));
+        A->work = nullptr;
+        return ROFL_OK;
+    });
+    if (rc) return rc;      // the handle stays in the registry: a later destroy frees what is left
+    A->released = true;      // a destroy that found the handle before it leaves the registry waits for the lock and then sees this
+    std::lock_guard<std::mutex> g(g_acc_mu);
+    g_accs.erase(h);
+    return ROFL_OK;
 }
 size_t rofl_wire_encoded_size(const rofl_wire_msg_t *m) { return m ? wire::encoded_size(*m) : 0; }
 int rofl_wire_encode(const rofl_wire_msg_t *m, uint8_t *out, size_t cap, size_t *len_out) {

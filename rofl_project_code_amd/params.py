@@ -525,7 +525,9 @@ class EncModelParamsAccumulator:
     """params.rs:74-138 (Enc variant): element-wise sum of ElGamal pairs, then unity check + BSGS extraction."""
 
     def __init__(self, size):
-        self.acc = np.zeros((size, 64), dtype=np.uint8)        # ElGamalPair::unity() = (identity, identity) = 64 zero bytes
+        # (identity, identity) = 64 zero bytes, unity check R == identity: extract() returns the true sum.  The reference starts from
+        # ElGamalPair::unity() = (B, B) instead (el_gamal.rs:83-88, params.rs:173) and checks R == B: DeviceAccumulator(reference_unity=True)
+        self.acc = np.zeros((size, 64), dtype=np.uint8)
 
     @classmethod
     def unity(cls, size):
@@ -546,3 +548,106 @@ class EncModelParamsAccumulator:
         pts = np.ascontiguousarray(self.acc[:, :32])
         sc = pedersen_ops.default_discrete_log_vec(pts, fp=fp) if table_size is None else pedersen_ops.discrete_log_vec(pts, table_size, bsgs_bits)
         return conversion32.scalar_to_f32_vec(sc, fp=fp)
+
+
+class DeviceAccumulator:
+    """EncModelParamsAccumulator with the round's running sum kept on the device (rofl_acc_*): every update is decoded once and added in
+    extended coordinates; nothing is encoded until export() / extract(), and extraction (unity check, BSGS) runs on the device too.
+
+    reference_unity=False: starts from (identity, identity) and checks R == identity -- the same bytes and values as EncModelParamsAccumulator.
+    reference_unity=True: starts from ElGamalPair::unity() = (B, B) and checks R == B, as the reference does (params.rs:173, 176;
+    el_gamal.rs:83-88, 101-103): its aggregate is the sum plus one raw fixed-point unit per coordinate.
+    The accumulator lives on the device of the calling thread; partial sums of several devices merge by accumulate_pairs(other.export())
+    (partials created with reference_unity=False: a (B, B) partial would count B twice)."""
+
+    def __init__(self, size, reference_unity=False):
+        self.size, self.reference_unity = int(size), bool(reference_unity)
+        self._open = False
+        self._h = api.accumulator.create(self.size, 1 if self.reference_unity else 0)
+        self._open = True
+
+    @classmethod
+    def unity(cls, size, reference_unity=False):
+        return cls(size, reference_unity)
+
+    @staticmethod
+    def _records(update):
+        """(array, stride) of an update's ElGamal pairs as they are held: L2 containers keep SquareRandProofCommitments (96 B, the pair c
+        first), read in place without a copy"""
+        if isinstance(update, EncParamsL2):
+            return update.enc_values, 96
+        return np.ascontiguousarray(update.pedersen_part(), dtype=np.uint8).reshape(-1, 64), 64
+
+    def _add(self, arrays, stride):
+        ptrs, counts = [], []
+        for a in arrays:
+            if api._is_dev(a):
+                p, nbytes = api._dev_arg(a, 1)
+                ptrs.append(p.value); counts.append(nbytes // stride)
+            else:
+                if not (a.flags.c_contiguous and a.dtype == np.uint8 and a.ndim == 2 and a.shape[1] == stride):
+                    raise ValueError("records must be a contiguous uint8 array of shape (n, stride)")
+                ptrs.append(a.ctypes.data); counts.append(a.shape[0])
+        api.accumulator.add(self._h, ptrs, counts, stride)
+        return arrays      # (kept alive by the caller until here)
+
+    def accumulate_other(self, other):
+        """gamal_accumulate / l2_vec_accumulate of one update (params.rs:81-104): zip() truncates to the accumulator's length"""
+        a, stride = self._records(other)
+        self._add([a], stride)
+        return True
+
+    def accumulate_batch(self, updates):
+        """all updates of a round (or a part of it) in ONE rofl_acc_add: all or nothing -- a record that does not decode raises FormatError
+        and leaves the sum as it was"""
+        recs = [self._records(u) for u in updates]
+        if not recs:
+            return True
+        strides = {st for _, st in recs}
+        if len(strides) == 1:
+            self._add([a for a, _ in recs], strides.pop())
+        else:      # mixed containers: the pairs of the 96-byte records packed (one call keeps the batch all or nothing)
+            self._add([a if st == 64 else np.ascontiguousarray(a[:, :64]) for a, st in recs], 64)
+        return True
+
+    def accumulate_pairs(self, pairs, stride=64):
+        """one client's records: a (n, stride) uint8 array, or a contiguous uint8 GPU tensor of n * stride bytes (read on the device)"""
+        if api._is_dev(pairs):
+            self._add([pairs], int(stride))
+        else:
+            self._add([np.ascontiguousarray(pairs, dtype=np.uint8).reshape(-1, int(stride))], int(stride))
+        return True
+
+    def export(self):
+        """(size, 64) encodings of the current sums (EncModelParamsAccumulator.acc for reference_unity=False)"""
+        return api.accumulator.export(self._h, self.size)
+
+    def extract(self, table_size=None, bsgs_bits=16, fp=None):
+        """None when some R is not the initial one (the blindings did not cancel), else the f32 aggregate -- as
+        EncModelParamsAccumulator.extract (table_size None: BSGSTable::default() of the fixed-point type)"""
+        fp = api._fp(fp)
+        if table_size is None:
+            table_size, bsgs_bits = api.default_bsgs(fp)
+        return api.accumulator.extract(self._h, self.size, table_size, bsgs_bits, fp)
+
+    def reset(self):
+        api.accumulator.reset(self._h)
+
+    def close(self):
+        """frees the device memory (once); later calls on the accumulator raise RoflError 11"""
+        if getattr(self, "_open", False):
+            self._open = False
+            api.accumulator.destroy(self._h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

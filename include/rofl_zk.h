@@ -228,6 +228,15 @@ int rofl_create_compressed_randproof(const float *values, size_t d, const uint8_
                                      unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonce, uint8_t proof_out[128],
                                      uint8_t *pairs_out /* d*64 */);
 int rofl_verify_compressed_randproof(const uint8_t proof[128], const uint8_t *pairs, size_t d, int *ok_out);
+/* server side: the compressed randomness proofs of n_clients clients (proofs[i]: 128 bytes, pairs[i]: d * 64 bytes in host memory) in one
+ * launch sequence.  Per client the check stays the two exact group equations of compressed_rand_proof/mod.rs:76-101 (no random weights), so
+ * ok_out[i] is exactly what rofl_verify_compressed_randproof gives client i.  A member with a non-canonical Z_m / Z_r, an undecodable C' or
+ * an undecodable pair gets ok = 0 (the single call's FormatError) and the others are still verified.  n_clients = 0 returns 0; d = 0 gives
+ * every well-formed member commit(Z_m, Z_r) == C'.  11 (bad parameter), before any device work: d >= 900 000, a null pointer with
+ * n_clients > 0, more than 32 767 clients (a fixed cap per call; the clients are verified in groups of at most sixteen, one MSM of two
+ * problems per client each).  With rofl_set_option("devices", mask) the clients are dealt
+ * round-robin to the listed devices. */
+int rofl_verify_compressed_randproof_batch(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out);
 
 /* ---- pedersen_ops (pedersen_ops.rs) ---- */
 int rofl_commit_vec(const uint8_t *values32, const uint8_t *blindings32 /* NULL: commit_no_blinding_vec */,

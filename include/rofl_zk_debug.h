@@ -100,6 +100,11 @@ int rofl_dbg_host_encode8_selftest(unsigned batches, double *us_simd, double *us
  * `lanes` transcripts, `count` commitments each, `skew` extra prefix bytes (moves the records across the rate block): 0 = states and the
  * next challenge agree, 1 = mismatch, -1 = no AVX-512 on this CPU */
 int rofl_dbg_host_merlin8_selftest(int lanes, unsigned count, unsigned skew, double *us_simd, double *us_scalar);
+/* the same for the labelled pairs of a CompressedRandProof transcript (k8::append_lbl3_run_x8: eight transcripts of count x
+ * append_lbl({3i, 3i + 1, 3i + 2}, pair_i, 64) per AVX-512 stream) against the scalar Merlin::append_lbl loop: `lanes` transcripts,
+ * `count` pairs each, `skew` (<= 400) extra prefix bytes; 0 = states, positions and the challenge drawn after C' agree, 1 = mismatch,
+ * -1 = no AVX-512 on this CPU */
+int rofl_dbg_host_merlin8_lbl3_selftest(int lanes, unsigned count, unsigned skew, double *us_simd, double *us_scalar);
 /* Merlin::append32_run (the run of m commitment appends of a chunk, records assembled in registers and split at the end of the rate block)
  * against `count` plain appends after `skew` (<= 400) extra prefix bytes: 0 = state, positions and next challenge equal, 1 = mismatch */
 int rofl_dbg_host_merlin_run_selftest(unsigned count, unsigned skew);

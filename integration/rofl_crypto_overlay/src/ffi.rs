@@ -106,6 +106,10 @@ extern "C" {
     pub fn rofl_create_compressed_randproof(values: *const c_float, d: usize, r32: *const u8, d_r: usize, existing32: *const u8,
         fp_bits: c_uint, fp_frac: c_uint, nonce: *const RoflNonce, proof_out: *mut u8, pairs_out: *mut u8) -> c_int;
     pub fn rofl_verify_compressed_randproof(proof: *const u8, pairs: *const u8, d: usize, ok_out: *mut c_int) -> c_int;
+    /// the compressed randomness proofs of a round's clients (d pairs each) in one launch sequence; ok_out[i] = client i's verdict,
+    /// exactly the single call's (a malformed member is 0, the others are still verified)
+    pub fn rofl_verify_compressed_randproof_batch(n_clients: usize, proofs: *const *const u8, pairs: *const *const u8, d: usize,
+        ok_out: *mut c_int) -> c_int;
     pub fn rofl_sum_points(points: *const u8, d: usize, stride: usize, out32: *mut u8) -> c_int;
     pub fn rofl_f32_to_scalar_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out32: *mut u8) -> c_int;
     pub fn rofl_scalar_to_f32_vec(in32: *const u8, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;

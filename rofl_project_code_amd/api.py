@@ -704,6 +704,31 @@ class compressed_rand_proof:
         _check(lib().rofl_verify_compressed_randproof(_ptr(p), _ptr(c), _sz(c.shape[0]), ctypes.byref(ok)))
         return bool(ok.value)
 
+    @staticmethod
+    def helper_verify_batch(proofs, pairs_list):
+        """rofl_verify_compressed_randproof_batch: the proofs of a round's clients, one call per vector length d.  One verdict per client,
+        what helper_verify gives it -- a member that helper_verify rejects with FormatError is False.  A member whose arrays are malformed
+        (a proof that is not 128 bytes, pairs that are not a (d, 64) array) is False without reaching the library."""
+        n = len(proofs)
+        if n != len(pairs_list):
+            raise ValueError("one pair vector per proof")
+        ps, cs, by_d = [None] * n, [None] * n, {}
+        for i, (p, c) in enumerate(zip(proofs, pairs_list)):
+            p = np.ascontiguousarray(p, dtype=np.uint8).reshape(-1)
+            c = np.ascontiguousarray(c, dtype=np.uint8)
+            if p.size == 128 and c.ndim == 2 and c.shape[1] == 64:
+                ps[i], cs[i] = p, c
+                by_d.setdefault(c.shape[0], []).append(i)
+        res = [False] * n
+        for d, idx in by_d.items():
+            pp = (ctypes.c_void_p * len(idx))(*[ps[i].ctypes.data for i in idx])
+            cp = (ctypes.c_void_p * len(idx))(*[cs[i].ctypes.data for i in idx])
+            ok = (ctypes.c_int * len(idx))()
+            _check(lib().rofl_verify_compressed_randproof_batch(_sz(len(idx)), pp, cp, _sz(d), ok))
+            for k, i in enumerate(idx):
+                res[i] = bool(ok[k])
+        return res
+
 
 class pedersen_ops:
     @staticmethod

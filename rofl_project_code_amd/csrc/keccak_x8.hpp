@@ -122,6 +122,38 @@ struct Run8 {
             }
         }
     }
+    // count x append_lbl({3i, 3i + 1, 3i + 2}, msg[l] + 64 j, 64), i = i0 + j (label bytes mod 256), on every lane -- the labelled
+    // ElGamal pairs of a CompressedRandProof transcript.  A record is 75 transcript bytes: {pos_begin, META_AD} label(3) len(4)
+    // {pos_begin', AD} pair(64).  A record that reaches the end of the rate block is split there, as Merlin::append32_run splits its
+    // records: the second header sits at record byte 9, so a block that ends within bytes 0..8 (k <= 9 bytes left) permutes with
+    // pos_begin = start + 1 and the second operation begins in the new block with pos_begin 0; otherwise the permutation sees start + 10.
+    ROFL_K8 void append_lbl3(size_t i0, const uint8_t *const msg[8], size_t count) {
+        for (size_t j = 0; j < count; j++) {
+            const size_t i = i0 + j, off = 64 * j;
+            const unsigned k = (unsigned)R - pos;      // bytes left in the rate block, 1..166
+            const uint8_t hdr[11] = {pos_begin, 16 | 2, (uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2), 64, 0, 0, 0,
+                                     (uint8_t)(k <= 9 ? 0 : pos + 1), 2};
+            if (k > 75) {                              // the whole record stays inside the rate block
+                u64 h0; memcpy(&h0, hdr, 8);
+                for (int l = 0; l < 8; l++) {
+                    uint8_t *b = reinterpret_cast<uint8_t *>(blk[l]) + pos;
+                    u64 x; memcpy(&x, b, 8); x ^= h0; memcpy(b, &x, 8);
+                    b[9] ^= hdr[9]; b[10] ^= hdr[10];
+                    Merlin::xor_bytes(b + 11, msg[l] + off, 64);
+                }
+                pos_begin = (uint8_t)(pos + 10); pos = (uint8_t)(pos + 75);
+            } else {
+                uint8_t rec[8][80];
+                for (int l = 0; l < 8; l++) { memcpy(rec[l], hdr, 11); memcpy(rec[l] + 11, msg[l] + off, 64); Merlin::xor_bytes(reinterpret_cast<uint8_t *>(blk[l]) + pos, rec[l], k); }
+                const uint8_t mark = (uint8_t)(pos + (k <= 9 ? 1 : 10));
+                for (int l = 0; l < 8; l++) { uint8_t *b = reinterpret_cast<uint8_t *>(blk[l]); b[R] ^= mark; b[R + 1] ^= 0x04 ^ 0x80; }
+                flush_block();
+                keccak_f1600_x8(S);
+                for (int l = 0; l < 8; l++) Merlin::xor_bytes(reinterpret_cast<uint8_t *>(blk[l]), rec[l] + k, 75 - k);
+                pos = (uint8_t)(75 - k); pos_begin = (uint8_t)(k <= 9 ? 10 - k : 0);
+            }
+        }
+    }
 };
 
 // Merlin::append32_run for up to eight transcripts at once.  All of them must be in the same position (same label, same appends so far).
@@ -129,6 +161,14 @@ ROFL_K8 void append32_run_x8(Merlin *const t[8], int lanes, char label, const ui
     Run8 r; r.load(t, lanes);
     const uint8_t *m[8]; for (int l = 0; l < 8; l++) m[l] = msg[l < lanes ? l : 0];
     r.append32(label, m, count);
+    r.store(t);
+}
+// count x Merlin::append_lbl({3i, 3i + 1, 3i + 2}, msg[l] + 64 j, 64), i = i0 + j, for up to eight transcripts in the same position
+// (the d ElGamal pairs of a CompressedRandProof transcript, compressed_challenges in rofl_zk.hip).
+ROFL_K8 void append_lbl3_run_x8(Merlin *const t[8], int lanes, size_t i0, const uint8_t *const msg[8], size_t count) {
+    Run8 r; r.load(t, lanes);
+    const uint8_t *m[8]; for (int l = 0; l < 8; l++) m[l] = msg[l < lanes ? l : 0];
+    r.append_lbl3(i0, m, count);
     r.store(t);
 }
 

@@ -2674,6 +2674,29 @@ __global__ void __launch_bounds__(TPB) k_decode_pairs(u32 d, const uint8_t *pair
     store_niels(which ? &Rs[i] : &Ls[i], gd_to_niels(p));
 }
 #endif
+// The same for a group of clients (blockIdx.y = client y, its pairs at pairs + 64 (y d + i)): L of client y at pts[2y d + i], R at
+// pts[(2y + 1) d + i] -- the two problems of the client's MSM.  An undecodable point sets bit 4 of ITS client's status word (one bad client
+// must not sink the round) and is stored as the identity.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_decode_pairs_batch(u32 d, const uint8_t *pairs, niels *pts, u32 *status /* [gridDim.y] */) {
+    const size_t y = blockIdx.y;
+    u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * d) return;
+    u32 i = t >> 1, which = t & 1;
+    gd p;
+    if (!gd_ristretto_decode(p, pairs + (y * d + i) * 64 + 32 * which)) { atomicOr(status + y, 4u); p = gd_identity(); }
+    store_niels(&pts[(2 * y + which) * d + i], gd_to_niels(p));
+}
+#endif
+// c_y^(i + 1) (canonical) of client y = blockIdx.y, i < d, from its table sq[y * MAX_LG + b] = c_y^(2^b) (Montgomery) in device memory
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_cpow_scalars_batch(u32 d, const sc *sq, sc *out_canon) {
+    const size_t y = blockIdx.y;
+    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d) return;
+    store_sc(&out_canon[y * d + i], sc_from_mont(sc_pow_tab(sq + y * MAX_LG, i + 1)));
+}
+#endif
 
 // ================================================================ server-side aggregation on the device (params.rs:74-147 gamal_accumulate / extract)
 // The round's running sum of ElGamal pairs stays resident in HBM as extended points (ge; pair j = sum[2j] L, sum[2j + 1] R).  An add of

@@ -1363,6 +1363,107 @@ int compressed_verify(const uint8_t *proof, const uint8_t *pairs, size_t d, int 
     timing_end(C);
     return ROFL_OK;
 }
+// The challenges c of nc CompressedRandProof transcripts of d pairs each (compressed_challenge) on the lane's host pool.  Having absorbed
+// messages of the same lengths, the transcripts' STROBE bookkeeping is identical at every step: eight of them share one AVX-512 instruction
+// stream (keccak_x8.hpp); groups of fewer than five, and CPUs without AVX-512, keep the scalar transcript, one client per task.
+void compressed_challenges(Ctx &C, size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, sc *out) {
+    static const bool x8_on = k8::available();
+    std::vector<std::pair<size_t, size_t>> tasks;      // (first client, count)
+    for (size_t j0 = 0; j0 < nc; j0 += 8) {
+        const size_t cnt = std::min<size_t>(8, nc - j0);
+        if (x8_on && cnt >= 5) tasks.emplace_back(j0, cnt);
+        else for (size_t l = 0; l < cnt; l++) tasks.emplace_back(j0 + l, 1);
+    }
+    C.pool->run(tasks.size(), [&](size_t k) {
+        const size_t j0 = tasks[k].first, cnt = tasks[k].second;
+        if (cnt == 1) { out[j0] = compressed_challenge(pairs[j0], d, proofs[j0]); return; }
+        std::vector<Merlin> t;
+        t.reserve(cnt);
+        for (size_t l = 0; l < cnt; l++) { t.emplace_back("CompressedRandProof", 19); t[l].append("dom-sep", (const uint8_t *)"randomness proof v1", 19); }
+        Merlin *tp[8]; const uint8_t *msg[8];
+        for (size_t l = 0; l < cnt; l++) { tp[l] = &t[l]; msg[l] = pairs[j0 + l]; }
+        if (d) k8::append_lbl3_run_x8(tp, (int)cnt, 0, msg, d);
+        for (size_t l = 0; l < cnt; l++) { t[l].append("C_prime_eg", proofs[j0 + l], 64); out[j0 + l] = t[l].challenge_scalar("c"); }
+    });
+}
+// compressed_verify for the clients of a round (the server checks every RangeCompressed update, server.rs:656-687, params.rs:235-256): per
+// client the same two exact group equations (no random weights), so ok_out[i] is what compressed_verify gives client i; a member whose proof
+// or pairs do not decode gets 0 and the others go on.  Clients go in groups of at most sixteen (device buffers for sixteen clients, two
+// pinned staging buffers of a group each, whatever the size of the round): a group's pairs are staged on the host pool, uploaded and decoded
+// one thread per point (k_decode_pairs_batch, one status word per client).  The pairs do not depend on the challenges: the first group is
+// enqueued before every client's transcript is hashed on the host pool, so the device decodes while the host hashes.  Then per group
+// k_cpow_scalars_batch and ONE multi-problem MSM -- two problems per client, sum_i c^(i+1) L_i and sum_i c^(i+1) R_i over the client's one
+// scalar array -- while the host stages the next group's pairs.  The final equalities (three fixed-base multiplications per client) run on
+// the host pool.
+int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out) {
+    LaneLock lane_lock = acquire_lane(false, nc == 1); Ctx &C = *lane_lock.c;
+    for (size_t i = 0; i < nc; i++) ok_out[i] = 0;
+    if (nc == 0) return ROFL_OK;
+    C.init();
+    C.batch_mode = nc > 1;
+    timing_begin(C);
+    std::vector<ge5> sumL(nc, h51::identity()), sumR(nc, h51::identity());
+    std::vector<u32> st(nc, 0);
+    if (d) {
+        const size_t G = std::min<size_t>(nc, 16);
+        u32 *status = C.status.as<u32>(nc + 4);
+        HIPCHK(hipMemsetAsync(status, 0, 4 * (nc + 4), C.stream));
+        uint8_t *dpairs = C.tmp_in.as<uint8_t>(G * d * 64);
+        niels *pts = C.aux_pts.as<niels>(2 * G * d);
+        sc *scal = C.aux_scal.as<sc>(G * d);
+        sc *dtab = C.tmp_out.as<sc>(G * MAX_LG), *htab = C.h_cp.as<sc>(G * MAX_LG);
+        // two pinned staging buffers alternate: group g + 2 is staged into group g's buffer while group g + 1 runs, and by then group g's
+        // upload has completed (msm_run waits for the lane's stream after every group)
+        uint8_t *stg_buf[2] = {(uint8_t *)C.stg.alloc(G * d * 64), nc > G ? (uint8_t *)C.stg.alloc(G * d * 64) : nullptr};
+        auto stage = [&](size_t g0) -> const uint8_t * {      // caller memory -> pinned staging, one pool task per client
+            const size_t gc = std::min(G, nc - g0);
+            uint8_t *sp = stg_buf[(g0 / G) & 1];
+            C.pool->run(gc, [&](size_t i) { stage_copy(sp + i * d * 64, pairs[g0 + i], d * 64); });
+            return sp;
+        };
+        auto decode = [&](size_t g0, const uint8_t *sp) {
+            const size_t gc = std::min(G, nc - g0);
+            HIPCHK(hipMemcpyAsync(dpairs, sp, gc * d * 64, hipMemcpyHostToDevice, C.stream));
+            ROFL_LAUNCH(k_decode_pairs_batch, grid1(2 * d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const uint8_t *)dpairs, pts, status + g0);
+        };
+        decode(0, stage(0));
+        std::vector<sc> c(nc);
+        compressed_challenges(C, nc, proofs, pairs, d, c.data());      // (the device decodes the first group meanwhile)
+        const uint8_t *next = nullptr;
+        for (size_t g0 = 0; g0 < nc; g0 += G) {
+            const size_t gc = std::min(G, nc - g0);
+            if (g0) decode(g0, next);      // (the previous group's MSM has finished: msm_run waited for it)
+            for (size_t j = 0; j < gc; j++) fill_pow2(htab + j * MAX_LG, h_mont(c[g0 + j]), MAX_LG);
+            HIPCHK(hipMemcpyAsync(dtab, htab, sizeof(sc) * MAX_LG * gc, hipMemcpyHostToDevice, C.stream));
+            ROFL_LAUNCH(k_cpow_scalars_batch, grid1(d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const sc *)dtab, scal);
+            std::vector<MsmProb> pr(2 * gc);
+            for (size_t j = 0; j < gc; j++) { pr[2 * j] = MsmProb{pts + 2 * j * d, scal + j * d}; pr[2 * j + 1] = MsmProb{pts + (2 * j + 1) * d, scal + j * d}; }
+            C.tm.t.msm_terms += 2 * gc * d;
+            MsmOpt opt;
+            if (g0 + gc < nc) opt.overlap = [&] { next = stage(g0 + gc); };
+            std::vector<ge5> res;
+            msm_run(C, pr, d, res, opt);
+            for (size_t j = 0; j < gc; j++) { sumL[g0 + j] = res[2 * j]; sumR[g0 + j] = res[2 * j + 1]; }
+        }
+        u32 *h_st = C.h_misc.as<u32>(nc + 4);
+        HIPCHK(hipMemcpyAsync(h_st, status, 4 * nc, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        for (size_t i = 0; i < nc; i++) st[i] = h_st[i];
+    }
+    auto neg5 = [](const ge5 &p) { ge5 r = p; r.X = h51::neg(p.X); r.T = h51::neg(p.T); return r; };
+    C.pool->run(nc, [&](size_t i) {
+        const uint8_t *proof = proofs[i];
+        ge Lp32, Rp32;      // the proof's own encodings: compressed_verify's FormatError
+        if ((st[i] & 4u) || !ristretto_decode(Lp32, proof) || !ristretto_decode(Rp32, proof + 32) || !sc_is_canonical_bytes(proof + 64) || !sc_is_canonical_bytes(proof + 96))
+            return;
+        sc zm = sc_frombytes(proof + 64), zr = sc_frombytes(proof + 96);
+        ge5 e1 = h51::gadd(h51::gadd(h_fixed_mul(C.ht.B5, zm), h_fixed_mul(C.ht.Bb5, zr)), neg5(h51::gadd(h51::from_ge(Lp32), sumL[i])));
+        ge5 e2 = h51::gadd(h_fixed_mul(C.ht.B5, zr), neg5(h51::gadd(h51::from_ge(Rp32), sumR[i])));
+        ok_out[i] = h51::is_identity_ristretto(e1) && h51::is_identity_ristretto(e2);
+    });
+    timing_end(C);
+    return ROFL_OK;
+}
 }  // namespace
 
 namespace {
@@ -1439,6 +1540,24 @@ int rofl_create_compressed_randproof(const float *values, size_t d, const uint8_
 }
 int rofl_verify_compressed_randproof(const uint8_t proof[128], const uint8_t *pairs, size_t d, int *ok_out) {
     return guarded([&]() -> int { return compressed_verify(proof, pairs, d, ok_out); });
+}
+int rofl_verify_compressed_randproof_batch(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out) {
+    // (a fixed cap on the round, half of kMaxBatchMembers as for the other batch entries; the clients themselves run in groups of sixteen)
+    if (!ok_out || (n_clients && (!proofs || !pairs)) || d >= 900000 || n_clients > kMaxBatchMembers / 2) return fail(ROFL_BAD_PARAM, "bad parameter");
+    for (size_t i = 0; i < n_clients; i++) if (!proofs[i] || (d && !pairs[i])) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_clients == 0) return ROFL_OK;
+    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
+    if (devs.empty() || n_clients < 2)
+        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
+            return compressed_verify_batch(n_clients, proofs, pairs, d, ok_out); });
+    for (size_t i = 0; i < n_clients; i++) ok_out[i] = 0;
+    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
+        const size_t k = idx.size();
+        std::vector<const uint8_t *> p(k), c(k); std::vector<int> ok(k, 0);
+        for (size_t j = 0; j < k; j++) { p[j] = proofs[idx[j]]; c[j] = pairs[idx[j]]; }
+        int r = compressed_verify_batch(k, p.data(), c.data(), d, ok.data());
+        for (size_t j = 0; j < k; j++) ok_out[idx[j]] = ok[j];
+        return r; }); });
 }
 int rofl_create_randproof_vec(const float *values, size_t d, const uint8_t *r32, size_t d_r, const uint8_t *existing32, unsigned fp_bits, unsigned fp_frac,
                               const rofl_nonce_t *nonce, uint8_t *proofs_out, uint8_t *commits_out) {
@@ -2286,6 +2405,42 @@ int rofl_dbg_host_merlin8_selftest(int lanes, unsigned count, unsigned skew, dou
     for (int l = 0; l < lanes; l++) {
         bad |= a[l].pos != b[l].pos || a[l].pos_begin != b[l].pos_begin || a[l].cur_flags != b[l].cur_flags || memcmp(a[l].stw, b[l].stw, 200) != 0;
         uint8_t ca[64], cb[64]; a[l].challenge_bytes("y", ca, 64); b[l].challenge_bytes("y", cb, 64); bad |= memcmp(ca, cb, 64) != 0;
+    }
+    if (us_simd) *us_simd = (t2 - t1) * 1e3;
+    if (us_scalar) *us_scalar = (t1 - t0) * 1e3;
+    return bad;
+}
+// k8::append_lbl3_run_x8 against `count` Merlin::append_lbl calls per transcript (the labelled pairs of compressed_challenge): `lanes`
+// CompressedRandProof transcripts, `skew` extra prefix bytes, then the pairs, C' and the challenge.  0 = equal, 1 = mismatch, -1 = no AVX-512.
+int rofl_dbg_host_merlin8_lbl3_selftest(int lanes, unsigned count, unsigned skew, double *us_simd, double *us_scalar) {
+    if (!k8::available()) return -1;
+    if (lanes < 1 || lanes > 8 || skew > 400) return ROFL_BAD_PARAM;
+    std::vector<uint8_t> data((size_t)8 * count * 64 + 64);
+    for (size_t i = 0; i < data.size(); i++) data[i] = (uint8_t)((i * 2654435761u) >> 13);
+    std::vector<uint8_t> pre(skew, 0x5a);
+    std::vector<Merlin> a, b;
+    for (int l = 0; l < lanes; l++) { a.emplace_back("CompressedRandProof", 19); b.emplace_back("CompressedRandProof", 19); }
+    for (int l = 0; l < lanes; l++) {
+        a[l].append("dom-sep", (const uint8_t *)"randomness proof v1", 19); b[l].append("dom-sep", (const uint8_t *)"randomness proof v1", 19);
+        if (skew) { a[l].append("skew", pre.data(), skew); b[l].append("skew", pre.data(), skew); }
+    }
+    double t0 = now_ms();
+    for (int l = 0; l < lanes; l++)
+        for (size_t i = 0; i < count; i++) {
+            uint8_t lbl[3] = {(uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2)};
+            a[l].append_lbl(lbl, 3, data.data() + ((size_t)l * count + i) * 64, 64);
+        }
+    double t1 = now_ms();
+    Merlin *t[8]; const uint8_t *msg[8];
+    for (int l = 0; l < lanes; l++) { t[l] = &b[l]; msg[l] = data.data() + (size_t)l * count * 64; }
+    k8::append_lbl3_run_x8(t, lanes, 0, msg, count);
+    double t2 = now_ms();
+    int bad = 0;
+    for (int l = 0; l < lanes; l++) {
+        bad |= a[l].pos != b[l].pos || a[l].pos_begin != b[l].pos_begin || a[l].cur_flags != b[l].cur_flags || memcmp(a[l].stw, b[l].stw, 200) != 0;
+        const uint8_t *cp = data.data() + data.size() - 64;
+        a[l].append("C_prime_eg", cp, 64); b[l].append("C_prime_eg", cp, 64);
+        uint8_t ca[64], cb[64]; a[l].challenge_bytes("c", ca, 64); b[l].challenge_bytes("c", cb, 64); bad |= memcmp(ca, cb, 64) != 0;
     }
     if (us_simd) *us_simd = (t2 - t1) * 1e3;
     if (us_scalar) *us_scalar = (t1 - t0) * 1e3;

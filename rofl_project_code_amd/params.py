@@ -230,6 +230,64 @@ class EncParamsRange:
             return False
         return bool(ok and ok_range)
 
+    def _rand_key(self):      # the randomness proof's part of the shape key: the number of RandProofs (one per pair when well-formed)
+        return self.rand_proofs.shape[0]
+
+    @staticmethod
+    def _rand_key_ok(key, d):
+        return key == d
+
+    @staticmethod
+    def _rand_batch(us):
+        return rand_proof_vec.verify_randproof_vec_batch([u.rand_proofs for u in us], [u.enc_values for u in us])
+
+    @classmethod
+    def verify_batch(cls, updates, verifier_seed=None, fp=None):
+        """The server's side of a round (server.rs:656-687 hands every client's update to the verification pool; :474-484 rejects the round
+        when one fails): EncModelParams::verify, EncRange / EncRangeCompressed arms (params.rs:185-203, 235-256), for ALL clients of the round as two
+        batched calls that run side by side -- the randomness proofs of every client in one launch sequence (_rand_batch) and the L-inf legs
+        through rofl_verify_rangeproof_batch_strided over the first k pairs of every client, read in place from the 64-byte records.  One
+        verdict per update, the same as update.verify() gives it; updates whose shape (d, the randomness proof's count or size, the range
+        proofs' shape, prove_range, k) differs from the majority's are verified on their own."""
+        fp = api._fp(fp)
+        n = len(updates)
+        res = [False] * n
+        if n == 0:
+            return res
+
+        def shape(u):
+            try:
+                d = u.enc_values.shape[0]
+                return (d, u._rand_key(), u.range_proofs.shape if u.range_proofs.ndim == 2 else None, u.prove_range, _num_checked(d, u.check_percentage))
+            except (AttributeError, RoflError):
+                return None
+        shapes = [shape(u) for u in updates]
+        ok_shape = [sh for sh in shapes if sh is not None and sh[0] > 0 and cls._rand_key_ok(sh[1], sh[0]) and sh[2] is not None and sh[2][0] > 0 and sh[4] > 0]
+        major = max(set(ok_shape), key=ok_shape.count) if ok_shape else None
+        idx = [i for i, sh in enumerate(shapes) if major is not None and sh == major]
+        for i, sh in enumerate(shapes):
+            if major is None or sh != major:
+                res[i] = bool(updates[i].verify(verifier_seed=verifier_seed, fp=fp))
+        if not idx:
+            return res
+        us = [updates[i] for i in idx]
+        k = major[4]
+        try:
+            ok_rand, ok_range = _concurrently(
+                lambda: cls._rand_batch(us),
+                lambda: range_proof_vec.verify_rangeproof_batch([u.range_proofs for u in us], [u.enc_values[:k] for u in us], major[3], verifier_seed=_sub_seed(verifier_seed, b"v"), fp=fp, commit_stride=64))
+        except (RoflError, ValueError, OverflowError, IndexError) as e:
+            if not _is_message_error(e):
+                raise      # the verifier itself failed (HIP / RCCL runtime error): not a verdict about any client
+            # a parameter of a batched call (a batch that has to be split, code 11) or a field of the majority shape that no proof can have:
+            # client by client, which gives every member the verdict its own verify() gives
+            for i in idx:
+                res[i] = bool(updates[i].verify(verifier_seed=verifier_seed, fp=fp))
+            return res
+        for j, i in enumerate(idx):
+            res[i] = bool(ok_rand[j] and ok_range[j])
+        return res
+
     def serialize(self, as_array=False):
         return wire.encode(self.kind, enc_values=self.enc_values, rand_proof=self.rand_proofs, range_proofs=self.range_proofs,
                            range_bits=self.prove_range, check_percentage=self.check_percentage, as_array=as_array)
@@ -288,6 +346,17 @@ class EncParamsRangeCompressed(EncParamsRange):
                 raise      # a fault of the verifier, not a verdict (see _MESSAGE_ERRORS)
             return False
         return bool(ok and ok_range)
+
+    def _rand_key(self):      # the size of the one CompressedRandProof
+        return self.rand_proof.size
+
+    @staticmethod
+    def _rand_key_ok(key, d):
+        return key == 128
+
+    @staticmethod
+    def _rand_batch(us):
+        return compressed_rand_proof.helper_verify_batch([u.rand_proof for u in us], [u.enc_values for u in us])
 
     def serialize(self, as_array=False):
         return wire.encode(self.kind, enc_values=self.enc_values, rand_proof=self.rand_proof, range_proofs=self.range_proofs,

@@ -289,6 +289,40 @@ int rofl_acc_extract(uint64_t h, size_t table_size, unsigned bsgs_bits, unsigned
 int rofl_acc_reset(uint64_t h);      /* back to the initial state of its init */
 int rofl_acc_destroy(uint64_t h);    /* frees the device memory; the handle is invalid afterwards (after a HIP error only destroy accepts it again) */
 
+/* ---- a round resident on the device: every update uploaded once and decoded once (server.rs:474-521, 656-714; params.rs:181-291) ----
+ * The server's part of a round -- check every client's proofs, add the accepted updates into the round's sum -- over ONE device copy of
+ * the clients' records: ingest uploads a client's records and decodes every point of them once (as the messages arrive), the
+ * verification legs take their commitments from the round (bytes for the transcripts, decoded points for the checks) and accumulate adds
+ * the cached (L, R) of the accepted clients into a rofl_acc_* accumulator without an upload or a decode.  Handles as for rofl_acc_*: from
+ * the library's registry, unknown or destroyed = 11, parameter checks (11) before the device is touched, the round lives on the device of
+ * the thread that created it and every later call runs there (the `devices` option does not apply: one round per device, partial sums
+ * merge through rofl_acc_export / rofl_acc_add).  Calls on one round are serialised, except that one verify_sigma and one verify_range
+ * may run side by side.
+ *   record_len 64: ElGamalPair (L | R); 96: SquareRandProofCommitments (L | R | c_sq).  create allocates what max_clients clients need
+ *   (record bytes and decoded points: max_clients * d * (record_len + 6 * record_len) bytes); nothing is allocated per round afterwards. */
+int rofl_round_create(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out);
+/* Appends n_clients clients (records[i]: d * record_len bytes, host or device memory) as clients first .. first + n_clients of the round
+ * (*first_index_out, may be NULL).  More clients than max_clients leaves room for: 11, nothing ingested.  A point that does not decode
+ * never fails the call: it is remembered per client and component and fails exactly the legs that read it (below). */
+int rofl_round_ingest(uint64_t h, size_t n_clients, const uint8_t *const *records, size_t *first_index_out);
+/* The batched Sigma-proof check of every ingested client (the random-linear-combination form of rofl_verify_*_vec_batch), commitments
+ * from the round; kind 0: RandProof (128 B per element, 64-byte records), 1: SquareRandProof (192 B, 96-byte records), 2: SquareProof
+ * (160 B) over L and c_sq of 96-byte records (the EncL2Compressed arm, params.rs:257-267: R is never read); a kind that does not fit the
+ * records is 11.  proofs[i]: client i's d proofs, or NULL to leave the client out (ok_out[i] = 0).  ok_out[i] is what the existing batched
+ * call returns for client i on the same bytes; csq_sum_out32 (kinds 1, 2; may be NULL) as in rofl_verify_squarerandproof_vec_batch. */
+int rofl_round_verify_sigma(uint64_t h, int kind, const uint8_t *const *proofs, int *ok_out, uint8_t *csq_sum_out32);
+/* rofl_verify_rangeproof_batch_strided over the first k_checked L of every ingested client (verify_batch and verify_zip_truncate apply
+ * as they do there); the L are not decoded again.  An undecodable L fails a client only at an index < k_checked.  proofs[i] NULL as above. */
+int rofl_round_verify_range(uint64_t h, const uint8_t *const *proofs, size_t proof_len, size_t n_proofs, size_t k_checked,
+                            size_t prove_range, unsigned fp_bits, unsigned fp_frac, const uint8_t verifier_seed[32], int *ok_out);
+/* Adds the (L, R) of the clients with accept[i] != 0 (accept NULL: every ingested client) to accumulator `acc` (same device, same d, else
+ * 11).  All or nothing as rofl_acc_add: an accepted client with an undecodable L or R -> 5, the accumulator unchanged (decided before
+ * anything is launched; d past one point tile of 131 072 goes through the accumulator's work copy, committed by a last fold).  The
+ * accumulator's export afterwards is byte-equal to rofl_acc_add of the accepted clients' records. */
+int rofl_round_accumulate(uint64_t h, uint64_t acc, const int *accept);
+int rofl_round_reset(uint64_t h);      /* no clients; the memory is kept for the next round */
+int rofl_round_destroy(uint64_t h);    /* frees the device memory; the handle is invalid afterwards */
+
 /* ---- wire formats of the encrypted update containers ----
  * proto3 messages of rofl_service/proto/roflservice/flservice.proto:75-100, length-delimited as written by
  * EncParamsRange::serialize (params.rs:513-527; EncParamsRangeCompressed :745-759 uses the same message with the 128-byte

@@ -59,6 +59,10 @@ int rofl_dbg_verify_labelled(const uint8_t *label, size_t label_len, size_t gens
  * overflow of the fused small launch, out[2] repeats on the slot path after a coarse bin of the two-level sort overflowed (scalars built to
  * collide), out[3] repeats after the slot path's overflow list ran out.  The server-path tests use them to show which path a scenario took. */
 int rofl_dbg_msm_retries(uint64_t out[4]);
+/* process-wide: the number of compressed points handed to the device's Ristretto decoder so far, added up on the host where the decoding
+ * kernels are launched (padding entries that are not decoded do not count).  The round tests use it to show, without a clock, that a
+ * rofl_round_* round decodes every record point once. */
+int rofl_dbg_point_decodes(uint64_t *count_out);
 /* field-multiply micro-benchmark: returns GF(2^255-19) multiplications per second on the device */
 int rofl_bench_femul(unsigned iters, double *fe_mul_per_sec_out);
 /* self-test of the quad-parallel point arithmetic (csrc/quad26.hpp): pair i = (P, Q) -> 2^doublings P + Q, one thread per pair and one quad of lanes per pair */

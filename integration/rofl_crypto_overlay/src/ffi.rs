@@ -81,6 +81,16 @@ extern "C" {
         ok_out: *mut c_int) -> c_int;
     pub fn rofl_acc_reset(h: u64) -> c_int;
     pub fn rofl_acc_destroy(h: u64) -> c_int;
+    /// a round resident on the device (server.rs:474-521, 656-714): records ingested once (one upload, one decode per point), both
+    /// verification legs and the accumulation read the decoded points; handles as for rofl_acc_*
+    pub fn rofl_round_create(d: usize, record_len: usize, max_clients: usize, handle_out: *mut u64) -> c_int;
+    pub fn rofl_round_ingest(h: u64, n_clients: usize, records: *const *const u8, first_index_out: *mut usize) -> c_int;
+    pub fn rofl_round_verify_sigma(h: u64, kind: c_int, proofs: *const *const u8, ok_out: *mut c_int, csq_sum_out32: *mut u8) -> c_int;
+    pub fn rofl_round_verify_range(h: u64, proofs: *const *const u8, proof_len: usize, n_proofs: usize, k_checked: usize,
+        prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, verifier_seed: *const u8, ok_out: *mut c_int) -> c_int;
+    pub fn rofl_round_accumulate(h: u64, acc: u64, accept: *const c_int) -> c_int;
+    pub fn rofl_round_reset(h: u64) -> c_int;
+    pub fn rofl_round_destroy(h: u64) -> c_int;
 
     // ---- the rest of include/rofl_zk.h (scripts/check_ffi.py keeps this block and the header in step: names and arity)
     pub fn rofl_bp_gens_export(n_bits: usize, m: usize, g_out: *mut u8, h_out: *mut u8) -> c_int;

@@ -880,6 +880,63 @@ class accumulator:
         _check(lib().rofl_acc_destroy(ctypes.c_uint64(h)))
 
 
+class device_round:
+    """rofl_round_*: a round's records resident on the device -- uploaded and decoded once by ingest, read by both verification legs and by
+    the accumulation.  Handles are registry ids; records / proofs are pointers (int / c_void_p; a proof pointer may be None: client left out)."""
+    @staticmethod
+    def create(d, record_len, max_clients):
+        h = ctypes.c_uint64()
+        _check(lib().rofl_round_create(_sz(d), _sz(record_len), _sz(max_clients), ctypes.byref(h)))
+        return h.value
+
+    @staticmethod
+    def ingest(h, records):
+        n = len(records)
+        rp = (ctypes.c_void_p * max(n, 1))(*records)
+        first = _sz()
+        _check(lib().rofl_round_ingest(ctypes.c_uint64(h), _sz(n), rp, ctypes.byref(first)))
+        return first.value
+
+    @staticmethod
+    def verify_sigma(h, kind, proofs, want_csq=False):
+        """(verdicts, csq sums or None), one per ingested client"""
+        n = len(proofs)
+        pp = (ctypes.c_void_p * max(n, 1))(*proofs)
+        ok = (ctypes.c_int * max(n, 1))()
+        sums = np.zeros((n, 32), dtype=np.uint8) if want_csq else None
+        _check(lib().rofl_round_verify_sigma(ctypes.c_uint64(h), int(kind), pp, ok, _ptr(sums) if want_csq and n else None))
+        return [bool(ok[i]) for i in range(n)], sums
+
+    @staticmethod
+    def verify_range(h, proofs, proof_len, n_proofs, k_checked, prove_range, verifier_seed=None, fp=None):
+        n = len(proofs)
+        pp = (ctypes.c_void_p * max(n, 1))(*proofs)
+        ok = (ctypes.c_int * max(n, 1))()
+        seed = bytes(verifier_seed) if verifier_seed is not None else os.urandom(32)
+        _check(lib().rofl_round_verify_range(ctypes.c_uint64(h), pp, _sz(proof_len), _sz(n_proofs), _sz(k_checked), _sz(prove_range), *_fp(fp), seed, ok))
+        return [bool(ok[i]) for i in range(n)]
+
+    @staticmethod
+    def accumulate(h, acc, accept=None):
+        a = None if accept is None else (ctypes.c_int * max(len(accept), 1))(*[1 if x else 0 for x in accept])
+        _check(lib().rofl_round_accumulate(ctypes.c_uint64(h), ctypes.c_uint64(acc), a))
+
+    @staticmethod
+    def reset(h):
+        _check(lib().rofl_round_reset(ctypes.c_uint64(h)))
+
+    @staticmethod
+    def destroy(h):
+        _check(lib().rofl_round_destroy(ctypes.c_uint64(h)))
+
+
+def point_decodes():
+    """test hook (include/rofl_zk_debug.h): compressed points handed to the device's Ristretto decoder so far, process-wide"""
+    out = ctypes.c_uint64()
+    _check(lib().rofl_dbg_point_decodes(ctypes.byref(out)))
+    return int(out.value)
+
+
 def default_bsgs(fp=None):
     """(table_size, bsgs_bits) of BSGSTable::default() for the fixed-point type (fp.rs; pedersen_ops.rs:27-35)"""
     bits, bias = {8: (8, 3), 16: (16, 7), 32: (16, 7), 64: (16, 0)}[_fp(fp)[0]]

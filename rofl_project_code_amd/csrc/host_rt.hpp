@@ -98,6 +98,10 @@ static const bool g_keccak_knob_applied = [] { if (const char *e = knob("ROFL_KE
 // ---------------------------------------------------------------- error plumbing
 thread_local std::string g_err;
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
+// rofl_dbg_point_decodes: compressed points handed to the device's Ristretto decoder, added up at the launch sites (padding entries that
+// are not decoded do not count).  Process-wide, like the MSM retry counters.
+std::atomic<uint64_t> g_point_decodes{0};
+inline void count_decodes(size_t n) { g_point_decodes.fetch_add((uint64_t)n, std::memory_order_relaxed); }
 struct HipErr { hipError_t e; const char *what; };
 #define HIPCHK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) throw HipErr{e__, #x}; } while (0)
 // Every kernel launch is checked where it is made: a launch the runtime refuses (a grid dimension past 65 535, too much LDS) would otherwise

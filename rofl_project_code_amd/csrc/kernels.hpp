@@ -2751,6 +2751,91 @@ __global__ void __launch_bounds__(TPB) k_acc_finish(u32 d, int mode, const ge *s
 }
 #endif
 
+// ================================================================ one round, decoded once (rofl_round_*)
+// A round keeps the decoded points of its clients' records in HBM in the layout the batched Sigma-proof check reads:
+// pts[(client * 2 npts + slot) * d + i], affine niels, the record's points (L, R, [c_sq]) in the EVEN slots; the odd slots are left for the
+// proof's primed points (k_sigma_vdecode_proofs).  Every verification leg and the accumulation read these; nothing decodes a record twice.
+//
+// Ingest: ONE THREAD PER POINT of the records of gridDim.y clients (npts = 2: 64-byte ElGamal pairs, 3: 96-byte
+// SquareRandProofCommitments).  A point that does not decode is stored as the identity and recorded as bad[client][slot] = the smallest such
+// index (the caller clears bad[] to 0xffffffff): which leg it fails is decided by the leg (the range leg reads only the first k L).
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_round_ingest(u32 d, u32 npts, const uint8_t *rec, niels *pts, u32 *bad /* [gridDim.y][3] */) {
+    const size_t y = blockIdx.y;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)npts * d) return;
+    u32 slot = (u32)(t / d), i = (u32)(t % d);
+    const uint8_t *src = rec + ((y * d + i) * npts + slot) * 32;
+    __align__(16) uint8_t b[32];
+    reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
+    gd p;
+    if (!gd_ristretto_decode(p, b)) { atomicMin(&bad[y * 3 + slot], i); p = gd_identity(); }
+    store_niels(&pts[((y * npts + slot) * 2) * d + i], sg_affine_niels(p));
+}
+#endif
+// The proof-points-only form of k_sigma_vdecode: the commitments' points are already in the even slots of pts (a round's cache, or a copy of
+// its L / c_sq slots for kind 2); one thread per primed point of the proofs, into the odd slots.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_sigma_vdecode_proofs(int kind, u32 d, const uint8_t *proofs, niels *pts, u32 *status /* [gridDim.y] */) {
+    bool has_R = kind != 2, has_sq = kind != 0;
+    u32 npts = 1 + (has_R ? 1 : 0) + (has_sq ? 1 : 0), nn = has_sq ? 3 : 2, plen = 32 * (npts + nn), nslots = 2 * npts;
+    const size_t y = blockIdx.y;
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)npts * d) return;
+    u32 k = (u32)(t / d), i = (u32)(t % d);
+    const uint8_t *src = proofs + (y * d + i) * plen + 32 * k;
+    __align__(16) uint8_t b[32];
+    reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
+    gd p;
+    if (!gd_ristretto_decode(p, b)) { atomicOr(status + y, 4u); p = gd_identity(); }
+    store_niels(&pts[(y * nslots + 2 * k + 1) * d + i], sg_affine_niels(p));
+}
+#endif
+// SquareProofCommitments { c_l: c.L, c_sq } (params.rs:262-266) of n 96-byte records, packed for the kind-2 transcripts: out[t] = L | c_sq
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_round_pack_lcsq(u32 n, const uint8_t *rec, uint8_t *out) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint4 *s = reinterpret_cast<const uint4 *>(rec + (size_t)t * 96);
+    uint4 *o = reinterpret_cast<uint4 *>(out + (size_t)t * 64);
+    o[0] = s[0]; o[1] = s[1]; o[2] = s[4]; o[3] = s[5];
+}
+#endif
+// The range leg's inputs from the cache (what k_decode makes from bytes): client y's first k cached L (at cache + y * cstride) -> out_niels
+// (a copy: the verifier's MSM reads one packed array) and the encoding of L + shift for the transcripts; entries k .. count are padding
+// (identity, zero bytes).  The encode's inversion chain remains, the decode's is gone.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_round_shift_encode(u32 count, u32 k, const niels *cache, size_t cstride, const niels *shift, niels *out_niels, uint8_t *out_enc) {
+    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const size_t y = blockIdx.y;
+    out_niels += y * count; out_enc += y * count * 32;
+    if (i >= k) {
+        store_niels(&out_niels[i], niels_identity());
+        uint4 z = make_uint4(0, 0, 0, 0); reinterpret_cast<uint4 *>(out_enc + (size_t)i * 32)[0] = z; reinterpret_cast<uint4 *>(out_enc + (size_t)i * 32)[1] = z;
+        return;
+    }
+    niels n = load_niels(&cache[y * cstride + i]);
+    store_niels(&out_niels[i], n);
+    gd p = gd_madd(gd_madd(gd_identity(), nd_unpack(n), false), load_nd(shift), false);
+    gd_ristretto_encode(out_enc + (size_t)i * 32, p);
+}
+#endif
+// The accumulation from the cache: thread (s, which, j) adds the cached L (which = 0) or R (1) of point j0 + j of the accepted clients
+// idx[s], idx[s + S], ... (mixed additions, no decode) into part[(s * tn + j) * 2 + which], the layout k_acc_fold folds into the sum.
+// Consecutive threads read consecutive 96-byte entries of one slot with 16-byte loads.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_round_sum(u32 tn, u32 j0, u32 S, u32 na, const u32 *idx, const niels *pts, u32 d, u32 nslots, ge *part) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)2 * tn * S) return;
+    const u32 s = (u32)(t / (2 * (size_t)tn)), r = (u32)(t % (2 * (size_t)tn)), which = r / tn, j = r % tn;
+    gd acc = gd_identity();
+    for (u32 q = s; q < na; q += S)
+        acc = gd_madd(acc, load_nd(&pts[((size_t)idx[q] * nslots + 2 * which) * d + j0 + j]), false);
+    store_gd(&part[((size_t)s * tn + j) * 2 + which], acc);
+}
+#endif
+
 // ================================================================ BSGS discrete log (bsgs32.rs:14-73, pedersen_ops.rs:27-53)
 // Baby-step table: keys[x] = compress(x B), x = 0..m, indexed by an open-addressing hash table (slot = first 8 key
 // bytes, linear probing) that lives in HBM; one thread per point walks the giant steps.

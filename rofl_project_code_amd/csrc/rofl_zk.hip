@@ -26,6 +26,7 @@
 #include <exception>
 #include <functional>
 #include <mutex>
+#include <shared_mutex>
 #include <thread>
 #include <string>
 #include <vector>
@@ -135,6 +136,15 @@ void bsgs_solve_launch(Ctx &C, size_t d, const uint8_t *dp, size_t table_size, u
     u64 max_it = (1ULL << bsgs_bits) / table_size;
     ROFL_LAUNCH(k_bsgs_solve, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, C.stream, (u32)d, dp, (u32)table_size, bsgs_bits, max_it, neg_mG, B.keys, B.slots, B.mask, dout, status);
 }
+
+// The commitments of a batched verification leg that come from a round (rofl_round_*) instead of caller memory: the records' bytes and
+// their decoded points are on the device already (k_round_ingest), and what did not decode is known per client and slot.
+struct RoundSrc {
+    size_t d, npts;            // the records: d per client, npts points each (2: ElGamal pair, 3: SquareRandProofCommitments)
+    const uint8_t *rec;        // device: [client][d][32 npts], as ingested
+    niels *pts;                // device: [client][2 npts][d], record points in the even slots (see k_round_ingest)
+    const u32 *bad;            // host: [client][3] -- smallest index of an undecodable L / R / c_sq, 0xffffffff: none
+};
 
 constexpr size_t kMaxBatchMembers = 65535;      // gridDim.y: what a batch entry point accepts in one call (the launches themselves are checked too, ROFL_LAUNCH)
 
@@ -278,7 +288,9 @@ int create_impl(Ctx &C, size_t nc, const float *const *values, size_t d, const u
 // SquareRandProofCommitments as they arrive on the wire, params.rs:197, 215: `enc_values.iter().map(|x| x.c.L)`).
 int verify_impl(Ctx &C, size_t n_clients, const uint8_t *const *proofs, size_t proof_len, size_t n_proofs, const uint8_t *const *commits,
                 size_t d, size_t prove_range, unsigned fp_bits, unsigned fp_frac, const uint8_t seed[32], int *ok_out, bool single,
-                const size_t *gid = nullptr, size_t cstride = 32, size_t chunk_first = 0, size_t chunk_count = 0) {
+                const size_t *gid = nullptr, size_t cstride = 32, size_t chunk_first = 0, size_t chunk_count = 0, const RoundSrc *rs = nullptr) {
+    // rs: the commitments are the first d cached L of the round's clients (`commits` is not read); a client without proofs (proofs[i] null)
+    // is left out: it takes part as a malformed member and gets ok = 0.
     // [chunk_first, chunk_first + chunk_count) (count 0: all): the proofs of every client that THIS call checks -- the reference verifies a
     // client's proofs independently of each other and ANDs the bits (range_proof_vec/mod.rs:168-181), so a device or a rank can take any run
     // of them.  n_proofs and d stay the client's (they fix the chunk length); proofs[i] points at the run's first proof, commits[i] at the
@@ -314,6 +326,7 @@ int verify_impl(Ctx &C, size_t n_clients, const uint8_t *const *proofs, size_t p
     if (P + 2 * nv * (size_t)std::ceil(std::sqrt((double)n_clients)) > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "batch too large (split it)");
     std::vector<uint8_t> pf(P * proof_len);
     for (size_t i = 0; i < n_clients; i++) {      // host or device memory; caller memory is not handed to the HIP runtime
+        if (rs && !proofs[i]) continue;      // (zero bytes: a proof that fails on its own)
         if (is_device_ptr(proofs[i])) HIPCHK(hipMemcpy(&pf[i * nv * proof_len], proofs[i], nv * proof_len, hipMemcpyDeviceToHost));
         else memcpy(&pf[i * nv * proof_len], proofs[i], nv * proof_len);
     }
@@ -322,6 +335,7 @@ int verify_impl(Ctx &C, size_t n_clients, const uint8_t *const *proofs, size_t p
     // offender gets ok = 0 and the others are still verified -- its scalars are zeroed in the local copy so that the shared launch
     // sequence stays well-formed (its check then fails on its own; clients never share a check).
     std::vector<char> bad_format(n_clients, 0);
+    if (rs) for (size_t i = 0; i < n_clients; i++) bad_format[i] = !proofs[i];
     for (size_t q = 0; q < P; q++) {
         uint8_t *pb = &pf[q * proof_len];
         const size_t offs[5] = {128, 160, 192, 7 * 32 + 64 * lg, 7 * 32 + 64 * lg + 32};
@@ -341,7 +355,7 @@ int verify_impl(Ctx &C, size_t n_clients, const uint8_t *const *proofs, size_t p
     niels *d_shift = C.tmp_out.as<niels>(1);
     HIPCHK(hipMemcpyAsync(d_shift, &h_shift, sizeof(niels), hipMemcpyHostToDevice, C.stream));
     size_t tot = n_clients * dp;
-    uint8_t *d_in = C.Cbytes.as<uint8_t>(tot * 32);
+    uint8_t *d_in = rs ? nullptr : C.Cbytes.as<uint8_t>(tot * 32);      // (a round brings no commitment bytes in)
     uint8_t *d_enc = C.Vbytes.as<uint8_t>(tot * 32);
     niels *d_vn = C.gbuf[0].as<niels>(tot);
     u32 *status = C.status.as<u32>(n_clients + 4);       // one status word per client: an undecodable commitment fails that client only
@@ -355,10 +369,11 @@ int verify_impl(Ctx &C, size_t n_clients, const uint8_t *const *proofs, size_t p
     std::vector<VerifyReady> ready;
     bool used_up = false;
     struct JoinUp { Ctx &c; bool &used; ~JoinUp() { if (used && c.stream_up) (void)hipStreamSynchronize(c.stream_up); } } join_up{C, used_up};      // nothing of the upload stream outlives the call
-    bool all_host = true; for (size_t i = 0; i < n_clients; i++) all_host &= !is_device_ptr(commits[i]);
+    bool all_host = true; for (size_t i = 0; i < n_clients && !rs; i++) all_host &= !is_device_ptr(commits[i]);
+    if (rs) for (size_t i = 0; i < n_clients; i++) h_st[i] = rs->bad[3 * i] < d ? 4u : 0u;      // an undecodable L fails the leg only where the leg reads it
     for (size_t i0 = 0; i0 < n_clients; i0 += GC) {
         const size_t gc = std::min(GC, n_clients - i0);
-        if (d == 0) {      // a run of padding chunks: nothing to bring in, the decode kernel writes identities
+        if (rs || d == 0) {      // the round's cache, or a run of padding chunks: nothing to bring in (the decode kernel writes identities)
         } else if (all_host && (d * 32 >= Stage::kMin || cstride != 32)) {
             uint8_t *st = (uint8_t *)C.stg.alloc(gc * d * 32);
             const size_t slices = std::max<size_t>(1, (d * 32) >> 18);      // ~256 KB per task
@@ -383,10 +398,14 @@ int verify_impl(Ctx &C, size_t n_clients, const uint8_t *const *proofs, size_t p
                 else { uint8_t *st = (uint8_t *)C.stg.alloc(d * 32); for (size_t e = 0; e < d; e++) memcpy(st + e * 32, commits[i] + e * cstride, 32);
                        HIPCHK(hipMemcpyAsync(d_in + i * dp * 32, st, d * 32, hipMemcpyHostToDevice, C.stream)); }
             }
-        { KSpan ks(C.tm, C.stream, ROFL_TK_CODEC, (uint64_t)gc * d * (2 * 265 + 7), (uint64_t)gc * d * 64);
+        if (rs) { KSpan ks(C.tm, C.stream, ROFL_TK_CODEC, (uint64_t)gc * d * (265 + 14), (uint64_t)gc * d * (96 + 96 + 32));      // no decode: shift + encode from the cached point
+          ROFL_LAUNCH(k_round_shift_encode, grid1(dp, (u32)gc), dim3(TPB), 0, C.stream, (u32)dp, (u32)d, (const niels *)(rs->pts + i0 * 2 * rs->npts * rs->d), 2 * rs->npts * rs->d,
+                      (const niels *)d_shift, d_vn + i0 * dp, d_enc + i0 * dp * 32); }
+        else { KSpan ks(C.tm, C.stream, ROFL_TK_CODEC, (uint64_t)gc * d * (2 * 265 + 7), (uint64_t)gc * d * 64);
+          count_decodes(gc * d);
           ROFL_LAUNCH(k_decode, grid1(dp, (u32)gc), dim3(TPB), 0, C.stream, (u32)dp, (u32)d, d_in + i0 * dp * 32, d_shift, d_vn + i0 * dp, d_enc + i0 * dp * 32, status + i0); }
         HIPCHK(hipMemcpyAsync(hV + i0 * dp * 32, d_enc + i0 * dp * 32, gc * dp * 32, hipMemcpyDeviceToHost, C.stream));
-        HIPCHK(hipMemcpyAsync(h_st + i0, status + i0, 4 * gc, hipMemcpyDeviceToHost, C.stream));
+        if (!rs) HIPCHK(hipMemcpyAsync(h_st + i0, status + i0, 4 * gc, hipMemcpyDeviceToHost, C.stream));
         ready.push_back(VerifyReady{(i0 + gc) * nv, C.pool_event(3 + ready.size())});      // (events 0..2 of the call: the upload stream's)
         HIPCHK(hipEventRecord(ready.back().ev, C.stream));
     }
@@ -680,6 +699,7 @@ int acc_add_impl(Ctx &C, Acc &A, const std::vector<size_t> &cl, const std::vecto
             HIPCHK(hipMemcpyAsync(d_off, h_off, gc * 8, hipMemcpyHostToDevice, C.stream));
             HIPCHK(hipMemcpyAsync(d_cnt, h_cnt, gc * 4, hipMemcpyHostToDevice, C.stream));
             const size_t S = std::min(S_max, gc);
+            count_decodes(2 * nr);
             ROFL_LAUNCH(k_acc_decode_partial, grid1(2 * tn * S), dim3(TPB), 0, C.stream, (u32)tn, (u32)S, (u32)gc, (const u64 *)d_off, (const u32 *)d_cnt, (const uint8_t *)rec, part, status);
             ROFL_LAUNCH(k_acc_fold, grid1(2 * tn), dim3(TPB), 0, C.stream, (u32)(2 * tn), (u32)S, (const ge *)part, (const ge *)(tgt + 2 * j0), init, tgt + 2 * j0, (const u32 *)status);
         }
@@ -690,6 +710,98 @@ int acc_add_impl(Ctx &C, Acc &A, const std::vector<size_t> &cl, const std::vecto
     HIPCHK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, C.stream));
     C.sync();
     if (st & 4u) return fail(ROFL_FORMAT_ERROR, "FormatError: a record is not a valid Ristretto encoding (the accumulator is unchanged)");
+    return ROFL_OK;
+}
+
+// ---------------------------------------------------------------- a round resident on the device (rofl_round_*; server.rs:474-521, 656-714)
+// The clients' records as ingested and their decoded points (RoundSrc's layout), allocated once for max_clients by create.  Ingest,
+// accumulate, reset and destroy hold the round exclusively; the two verification legs hold it shared (they only read the record points --
+// the Sigma leg also writes the odd slots, which no other call reads) and may run side by side on two lanes, one leg of each kind at a time.
+struct Round {
+    int device = 0; size_t d = 0, rec_len = 0, npts = 0, max_clients = 0, n = 0;
+    uint8_t *rec = nullptr; niels *pts = nullptr; u32 *d_bad = nullptr;
+    std::vector<u32> bad;      // host copy of d_bad: [client][3]
+    std::shared_mutex rw; std::mutex sigma_mu, range_mu;
+    bool dead = false, released = false;
+    RoundSrc src() const { return RoundSrc{d, npts, rec, pts, bad.data()}; }
+};
+std::mutex g_round_mu;
+std::map<uint64_t, std::shared_ptr<Round>> g_rounds;
+uint64_t g_round_next = 1;
+std::shared_ptr<Round> round_find(uint64_t h) { std::lock_guard<std::mutex> lk(g_round_mu); auto it = g_rounds.find(h); return it == g_rounds.end() ? nullptr : it->second; }
+
+// clients [R.n, R.n + n): the records go up in groups of ~64 MB through two pinned staging buffers (the pool copies group g + 1 while group g
+// is on its way and being decoded; device-resident records are copied on the device), one k_round_ingest per group: every point decoded once
+int round_ingest_impl(Ctx &C, Round &R, size_t n, const uint8_t *const *records) {
+    const size_t d = R.d, per = d * R.rec_len, first = R.n;
+    C.init();
+    HIPCHK(hipMemsetAsync(R.d_bad + 3 * first, 0xff, 12 * n, C.stream));
+    const size_t G = std::max<size_t>(1, std::min<size_t>(n, ((size_t)64 << 20) / per));
+    std::vector<char> on_dev(n);
+    for (size_t i = 0; i < n; i++) on_dev[i] = is_device_ptr(records[i]);
+    uint8_t *stb[2] = {nullptr, nullptr};
+    for (size_t g0 = 0, gi = 0; g0 < n; g0 += G, gi++) {
+        const size_t gc = std::min(G, n - g0);
+        uint8_t *dst = R.rec + (first + g0) * per;
+        bool any_host = false; for (size_t i = g0; i < g0 + gc; i++) any_host |= !on_dev[i];
+        if (any_host) {
+            const int b = (int)(gi & 1);
+            if (!stb[b]) stb[b] = (uint8_t *)C.stg.alloc(G * per); else C.wait_event(C.pool_event(b));
+            uint8_t *st = stb[b];
+            const size_t slices = std::max<size_t>(1, per >> 18);      // ~256 KB per task
+            C.pool->run(gc * slices, [&](size_t t) { size_t i = t / slices, k = t % slices; if (on_dev[g0 + i]) return;
+                                                     size_t lo = per * k / slices, hi = per * (k + 1) / slices; stage_copy(st + i * per + lo, records[g0 + i] + lo, hi - lo); });
+            for (size_t i = 0; i < gc; ) {      // one upload per run of host clients
+                if (on_dev[g0 + i]) { i++; continue; }
+                size_t j = i; while (j < gc && !on_dev[g0 + j]) j++;
+                HIPCHK(hipMemcpyAsync(dst + i * per, st + i * per, (j - i) * per, hipMemcpyHostToDevice, C.stream));
+                i = j;
+            }
+            HIPCHK(hipEventRecord(C.pool_event(b), C.stream));
+        }
+        for (size_t i = 0; i < gc; i++) if (on_dev[g0 + i]) HIPCHK(hipMemcpyAsync(dst + i * per, records[g0 + i], per, hipMemcpyDeviceToDevice, C.stream));
+        count_decodes(gc * R.npts * d);
+        ROFL_LAUNCH(k_round_ingest, dim3((unsigned)((R.npts * d + TPB - 1) / TPB), (unsigned)gc), dim3(TPB), 0, C.stream, (u32)d, (u32)R.npts, (const uint8_t *)dst,
+                    R.pts + (first + g0) * 2 * R.npts * d, R.d_bad + 3 * (first + g0));
+    }
+    u32 *hb = C.h_misc.as<u32>(3 * n);
+    HIPCHK(hipMemcpyAsync(hb, R.d_bad + 3 * first, 12 * n, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    memcpy(&R.bad[3 * first], hb, 12 * n);
+    R.n = first + n;
+    return ROFL_OK;
+}
+// sum += the cached (L, R) of the clients in `cl`: mixed additions from the cache in tiles of kAccTile points, S client slices per tile
+// folded into the sum by k_acc_fold.  All or nothing is decided before anything is launched: what did not decode is known since ingest.
+int round_accumulate_impl(Ctx &C, Round &R, Acc &A, const std::vector<u32> &cl) {
+    for (u32 c : cl) if (R.bad[3 * c] != ~0u || R.bad[3 * c + 1] != ~0u)
+        return fail(ROFL_FORMAT_ERROR, "FormatError: a record is not a valid Ristretto encoding (the accumulator is unchanged)");
+    if (cl.empty()) return ROFL_OK;
+    const size_t d = R.d, tile = std::min(d, kAccTile), na = cl.size();
+    const size_t S = std::max<size_t>(1, std::min(na, (kAccThreads + 2 * tile - 1) / (2 * tile)));
+    C.init();
+    ge *part = C.partial2.as<ge>(S * tile * 2);
+    u32 *d_idx = C.tmp_out.as<u32>(na);
+    u32 *h_idx = (u32 *)C.stg.alloc(na * 4); memcpy(h_idx, cl.data(), na * 4);
+    HIPCHK(hipMemcpyAsync(d_idx, h_idx, na * 4, hipMemcpyHostToDevice, C.stream));
+    const ge init = acc_init_point(A.init);
+    ge *tgt = A.sum;
+    const bool multi = d > tile;      // several tiles: into a copy of the sum that a last fold commits, as acc_add_impl (a runtime error on the way leaves the sum as it was)
+    if (multi) {
+        if (!A.work) HIPCHK(hipMalloc(&A.work, sizeof(ge) * 2 * d));
+        HIPCHK(hipMemcpyAsync(A.work, A.sum, sizeof(ge) * 2 * d, hipMemcpyDeviceToDevice, C.stream));
+        tgt = A.work;
+    }
+    for (size_t j0 = 0; j0 < d; j0 += tile) {
+        const size_t tn = std::min(tile, d - j0);
+        ROFL_LAUNCH(k_round_sum, grid1(2 * tn * S), dim3(TPB), 0, C.stream, (u32)tn, (u32)j0, (u32)S, (u32)na, (const u32 *)d_idx, (const niels *)R.pts, (u32)d, (u32)(2 * R.npts), part);
+        ROFL_LAUNCH(k_acc_fold, grid1(2 * tn), dim3(TPB), 0, C.stream, (u32)(2 * tn), (u32)S, (const ge *)part, (const ge *)(tgt + 2 * j0), init, tgt + 2 * j0, (const u32 *)nullptr);
+    }
+    if (multi) {
+        C.sync();      // every tile is in the copy: only now does the sum change
+        ROFL_LAUNCH(k_acc_fold, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)(2 * d), 0u, (const ge *)nullptr, (const ge *)A.work, init, A.sum, (const u32 *)nullptr);
+    }
+    C.sync();
     return ROFL_OK;
 }
 }  // namespace
@@ -937,6 +1049,7 @@ int rofl_verify_rangeproof_l2(const uint8_t *proof, size_t proof_len, const uint
         u32 *status = C.status.as<u32>(4);
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
         HIPCHK(hipMemcpyAsync(d_in, commit, 32, hipMemcpyHostToDevice, C.stream));
+        count_decodes(1);
         ROFL_LAUNCH(k_decode, grid1(1), dim3(TPB), 0, C.stream, 1u, 1u, d_in, (const niels *)nullptr, d_vn, d_enc, status);
         uint8_t hV[32]; u32 st = 0;
         HIPCHK(hipMemcpyAsync(hV, d_enc, 32, hipMemcpyDeviceToHost, C.stream));
@@ -987,6 +1100,7 @@ int rofl_verify_rangeproof_l2_batch(size_t n_clients, const uint8_t *const *proo
         u32 *status = C.status.as<u32>(nc + 4);
         HIPCHK(hipMemsetAsync(status, 0, 4 * (nc + 4), C.stream));
         C.up(d_in, commits32, nc * 32, C.stream);
+        count_decodes(nc);
         ROFL_LAUNCH(k_decode, grid1(1, (u32)nc), dim3(TPB), 0, C.stream, 1u, 1u, d_in, (const niels *)nullptr, d_vn, d_enc, status);
         uint8_t *hV = C.h_V.as<uint8_t>(nc * 32); u32 *h_st = C.h_misc.as<u32>(nc + 4);
         HIPCHK(hipMemcpyAsync(hV, d_enc, nc * 32, hipMemcpyDeviceToHost, C.stream));
@@ -1095,7 +1209,11 @@ int sigma_create(int kind, const float *values, size_t d, const uint8_t *r1, siz
 // csq_sum_out (kinds 1, 2; may be null): sum_i c_sq_i of every client, compressed (params.rs:220, 277) -- the points are decoded here anyway.
 // `single`: the call is one of the rofl_verify_*_vec entry points (a malformed vector is the call's FormatError); batch calls give the
 // offender ok = 0 and go on.
-int sigma_verify_batch(int kind, size_t nc, const uint8_t *const *proofs, const uint8_t *const *commits, size_t d, int *ok_out, uint8_t *csq_sum_out, bool single) {
+// rs: the commitments are the round's (`commits` is not read): their bytes are on the device for the transcripts, their points decoded in
+// the even slots of the round's point array, which IS the MSM's input for kinds 0 / 1 (kind 2 reads L and c_sq of 96-byte records: a
+// packing kernel for the bytes, two strided device copies for the points); only the proofs' own points are decoded here.  A client without proofs (proofs[i] null) is left out (ok = 0).
+int sigma_verify_batch(int kind, size_t nc, const uint8_t *const *proofs, const uint8_t *const *commits, size_t d, int *ok_out, uint8_t *csq_sum_out, bool single,
+                       const RoundSrc *rs = nullptr) {
     LaneLock lane_lock = acquire_lane(false, nc == 1); Ctx &C = *lane_lock.c;
     for (size_t i = 0; i < nc; i++) ok_out[i] = 0;
     const bool has_R = kind != 2, has_sq = kind != 0;
@@ -1109,13 +1227,14 @@ int sigma_verify_batch(int kind, size_t nc, const uint8_t *const *proofs, const 
     C.init();
     C.batch_mode = nc > 1;
     timing_begin(C);
-    if (!opts().sigma_batch.load()) {      // rofl_set_option("sigma_batch", 0): one check per element (the reference's form), client by client
+    if (!rs && !opts().sigma_batch.load()) {      // rofl_set_option("sigma_batch", 0): one check per element (the reference's form), client by client
         int rc_all = ROFL_OK;
         for (size_t i = 0; i < nc; i++) {
             uint8_t *dp = C.aux_pts.as<uint8_t>(d * plen), *dc = C.aux_scal.as<uint8_t>(d * clen);
             u32 *status = C.status.as<u32>(4);
             HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
             C.up(dp, proofs[i], d * plen, C.stream); C.up(dc, commits[i], d * clen, C.stream);
+            count_decodes(nslots * d + (csq_sum_out && has_sq ? d : 0));
             { KSpan ks_sigma(C.tm, C.stream, ROFL_TK_SIGMA, (uint64_t)d * (2 * npts * 265 + (kind ? 3 : 2) * 2 * 325 * 8), (uint64_t)d * (clen + plen));
               ROFL_LAUNCH(k_sigma_verify, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, C.stream, kind, (u32)d, dp, dc, sigma_init_state(kind), C.d_tabB, C.d_tabBb, status + 1, status); }
             u32 *st = C.h_misc.as<u32>(4);
@@ -1138,13 +1257,22 @@ int sigma_verify_batch(int kind, size_t nc, const uint8_t *const *proofs, const 
     static const bool strace = knob("ROFL_TRACE") && atoi(knob("ROFL_TRACE")) >= 2;
     double st0 = now_ms(), stl = st0;
     auto smark = [&](const char *what) { if (!strace) return; double t = now_ms(); fprintf(stderr, "[rofl-trace sigma-verify] %-18s +%.3f ms  (t=%.3f)\n", what, t - stl, t - st0); stl = t; };
-    uint8_t *dp = C.aux_pts.as<uint8_t>(nc * d * plen), *dc = C.aux_scal.as<uint8_t>(nc * d * clen);
+    const bool rs_direct = rs && clen == 32 * rs->npts;      // kinds 0 / 1: the records are the leg's commitments as they lie
+    uint8_t *dp = C.aux_pts.as<uint8_t>(nc * d * plen);
+    const uint8_t *dc = rs_direct ? rs->rec : C.aux_scal.as<uint8_t>(nc * d * clen);
     u32 *status = C.status.as<u32>(nc + 4);
     HIPCHK(hipMemsetAsync(status, 0, 4 * (nc + 4), C.stream));
     NonceSeed ws{};
     { FILE *f = fopen("/dev/urandom", "rb"); bool got = f && fread(ws.w, 1, 32, f) == 32; if (f) fclose(f);
       if (!got) return fail(ROFL_HIP_ERROR, "no randomness for the batched Sigma-proof check"); }
-    niels *pts = C.gbuf[0].as<niels>(nc * nslots * d);
+    niels *pts = rs_direct ? rs->pts : C.gbuf[0].as<niels>(nc * nslots * d);
+    if (rs && !rs_direct) {      // kind 2 over 96-byte records: (L, c_sq) of every record packed for the transcripts, their cached points into slots 0 / 2
+        uint8_t *pk = const_cast<uint8_t *>(dc);
+        ROFL_LAUNCH(k_round_pack_lcsq, grid1(nc * d), dim3(TPB), 0, C.stream, (u32)(nc * d), rs->rec, pk);
+        HIPCHK(hipMemcpy2DAsync(pts, 4 * d * sizeof(niels), rs->pts, 6 * d * sizeof(niels), d * sizeof(niels), nc, hipMemcpyDeviceToDevice, C.stream));
+        HIPCHK(hipMemcpy2DAsync(pts + 2 * d, 4 * d * sizeof(niels), rs->pts + 4 * d, 6 * d * sizeof(niels), d * sizeof(niels), nc, hipMemcpyDeviceToDevice, C.stream));
+    }
+    const size_t cup = rs ? 0 : clen;      // commitment bytes per element that this call brings in
     sc *scal = C.SL.as<sc>(nc * nslots * d);
     sc *d_fixed = C.tmp_out.as<sc>(nc * nblk * 2);
     const DMerlin init = sigma_init_state(kind);
@@ -1157,9 +1285,9 @@ int sigma_verify_batch(int kind, size_t nc, const uint8_t *const *proofs, const 
         }
         return 96u; }();
     // groups of clients: ~64 MB of caller bytes each, through two staging buffers
-    const size_t per = d * (plen + clen);
+    const size_t per = d * (plen + cup);
     const size_t G = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nc, 16), ((size_t)64 << 20) / per));      // (at most sixteen: a group is also a row count of gridDim.y and part of one Pippenger launch)
-    bool all_host = true; for (size_t i = 0; i < nc; i++) all_host &= !is_device_ptr(proofs[i]) && !is_device_ptr(commits[i]);
+    bool all_host = true; for (size_t i = 0; i < nc; i++) all_host &= !is_device_ptr(proofs[i]) && (rs || !is_device_ptr(commits[i]));
     // three staging buffers; the uploads run on a stream of their own (the copy of group g + 1 beside the kernels of group g: on one stream they
     // alternated, and the "staging" time of the first version was the host waiting for that stream)
     constexpr size_t NST = 3;
@@ -1201,19 +1329,26 @@ int sigma_verify_batch(int kind, size_t nc, const uint8_t *const *proofs, const 
         if (stage[0]) {
             if (used[b]) C.wait_event(C.pool_event(b));      // the upload that read this buffer three groups ago
             uint8_t *sp = stage[b], *sq = stage[b] + gc * d * plen;
-            const size_t sl_p = std::max<size_t>(1, (d * plen) >> 18), sl_c = std::max<size_t>(1, (d * clen) >> 18);      // ~256 KB per task
+            const size_t sl_p = std::max<size_t>(1, (d * plen) >> 18), sl_c = cup ? std::max<size_t>(1, (d * clen) >> 18) : 0;      // ~256 KB per task
             C.pool->run(gc * (sl_p + sl_c), [&](size_t t) {
                 size_t i = t / (sl_p + sl_c), k = t % (sl_p + sl_c);
-                if (k < sl_p) { size_t lo = d * plen * k / sl_p, hi = d * plen * (k + 1) / sl_p; stage_copy(sp + i * d * plen + lo, proofs[g0 + i] + lo, hi - lo); }
+                if (k < sl_p) { size_t lo = d * plen * k / sl_p, hi = d * plen * (k + 1) / sl_p;
+                                if (proofs[g0 + i]) stage_copy(sp + i * d * plen + lo, proofs[g0 + i] + lo, hi - lo); else memset(sp + i * d * plen + lo, 0, hi - lo); }
                 else { k -= sl_p; size_t lo = d * clen * k / sl_c, hi = d * clen * (k + 1) / sl_c; stage_copy(sq + i * d * clen + lo, commits[g0 + i] + lo, hi - lo); }
             });
             HIPCHK(hipMemcpyAsync(dp + g0 * d * plen, sp, gc * d * plen, hipMemcpyHostToDevice, C.stream_up));
-            HIPCHK(hipMemcpyAsync(dc + g0 * d * clen, sq, gc * d * clen, hipMemcpyHostToDevice, C.stream_up));
+            if (cup) HIPCHK(hipMemcpyAsync(const_cast<uint8_t *>(dc) + g0 * d * clen, sq, gc * d * clen, hipMemcpyHostToDevice, C.stream_up));
             HIPCHK(hipEventRecord(C.pool_event(b), C.stream_up)); used[b] = true;
             HIPCHK(hipStreamWaitEvent(C.stream, C.pool_event(b), 0));      // this group's kernels wait for its bytes
         } else
-            for (size_t i = g0; i < g0 + gc; i++) { C.up(dp + i * d * plen, proofs[i], d * plen, C.stream); C.up(dc + i * d * clen, commits[i], d * clen, C.stream); }
-        {   KSpan ks_sigma(C.tm, C.stream, ROFL_TK_SIGMA, (uint64_t)gc * d * (2 * npts * 265), (uint64_t)gc * d * (clen + plen));      // decoding of 2 npts points per element
+            for (size_t i = g0; i < g0 + gc; i++) {
+                if (proofs[i]) C.up(dp + i * d * plen, proofs[i], d * plen, C.stream); else HIPCHK(hipMemsetAsync(dp + i * d * plen, 0, d * plen, C.stream));
+                if (cup) C.up(const_cast<uint8_t *>(dc) + i * d * clen, commits[i], d * clen, C.stream); }
+        {   KSpan ks_sigma(C.tm, C.stream, ROFL_TK_SIGMA, (uint64_t)gc * d * ((rs ? 1 : 2) * npts * 265), (uint64_t)gc * d * (cup + plen));      // decoding of 2 npts points per element (a round: the proofs' npts)
+            count_decodes(gc * (rs ? npts : nslots) * d);
+            if (rs) ROFL_LAUNCH(k_sigma_vdecode_proofs, dim3((unsigned)((npts * d + TPB - 1) / TPB), (unsigned)gc), dim3(TPB), 0, C.stream, kind, (u32)d, (const uint8_t *)(dp + g0 * d * plen),
+                               pts + g0 * nslots * d, status + g0);
+            else
             ROFL_LAUNCH(k_sigma_vdecode, dim3((unsigned)((nslots * d + TPB - 1) / TPB), (unsigned)gc), dim3(TPB), 0, C.stream, kind, (u32)d, dp + g0 * d * plen, dc + g0 * d * clen,
                                pts + g0 * nslots * d, status + g0);
             ROFL_LAUNCH(k_sigma_vprep, dim3((unsigned)nblk, (unsigned)gc), dim3(TPB), 0, C.stream, kind, (u32)d, dp + g0 * d * plen, dc + g0 * d * clen, init, ws, (u64)(g0 * d), wbits,
@@ -1241,7 +1376,9 @@ int sigma_verify_batch(int kind, size_t nc, const uint8_t *const *proofs, const 
     std::vector<size_t> good;
     std::vector<char> is_bad(nc, 0);
     for (size_t i = 0; i < nc; i++) {
-        if (h_st[i] & 4u) { is_bad[i] = 1; if (single) { timing_end(C); return fail(ROFL_FORMAT_ERROR, "FormatError: non-canonical scalar or invalid point"); } }
+        bool bad = (h_st[i] & 4u) != 0;
+        if (rs) bad |= !proofs[i] || rs->bad[3 * i] != ~0u || (has_R && rs->bad[3 * i + 1] != ~0u) || (has_sq && rs->bad[3 * i + 2] != ~0u);      // the slots this kind reads
+        if (bad) { is_bad[i] = 1; if (single) { timing_end(C); return fail(ROFL_FORMAT_ERROR, "FormatError: non-canonical scalar or invalid point"); } }
         else good.push_back(i);
     }
     for (auto &jb : jobs)
@@ -1344,6 +1481,7 @@ int compressed_verify(const uint8_t *proof, const uint8_t *pairs, size_t d, int 
         u32 *status = C.status.as<u32>(4);
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
         C.up(dpairs, pairs, 64 * d, C.stream);
+        count_decodes(2 * d);
         ROFL_LAUNCH(k_decode_pairs, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)d, dpairs, pts, pts + d, status);
         CPow cp; fill_pow2(cp.sq, h_mont(c), MAX_LG);
         ROFL_LAUNCH(k_cpow_scalars, grid1(d), dim3(TPB), 0, C.stream, (u32)d, cp, scal);
@@ -1424,6 +1562,7 @@ int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8
         auto decode = [&](size_t g0, const uint8_t *sp) {
             const size_t gc = std::min(G, nc - g0);
             HIPCHK(hipMemcpyAsync(dpairs, sp, gc * d * 64, hipMemcpyHostToDevice, C.stream));
+            count_decodes(2 * d * gc);
             ROFL_LAUNCH(k_decode_pairs_batch, grid1(2 * d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const uint8_t *)dpairs, pts, status + g0);
         };
         decode(0, stage(0));
@@ -1625,6 +1764,7 @@ int rofl_add_points_vec(const uint8_t *a32, const uint8_t *b32, size_t d, uint8_
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
         C.up(da, a32, 32 * d, C.stream);
         C.up(db, b32, 32 * d, C.stream);
+        count_decodes(2 * d);
         ROFL_LAUNCH(k_add_points, grid1(d), dim3(TPB), 0, C.stream, (u32)d, da, db, o, status);
         u32 st = 0;
         C.down(out32, o, 32 * d, C.stream);
@@ -1646,6 +1786,7 @@ int rofl_sum_points(const uint8_t *points, size_t d, size_t stride, uint8_t out3
         u32 *status = C.status.as<u32>(4);
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
         C.up(da, points, stride * d, C.stream);
+        count_decodes(d);
         ROFL_LAUNCH(k_decode_sum, dim3(nblk), dim3(TPB), TPB * sizeof(ge), C.stream, da, (u32)d, (u32)stride, part, status);
         std::vector<ge> hp(nblk); u32 st = 0;
         HIPCHK(hipMemcpyAsync(hp.data(), part, sizeof(ge) * nblk, hipMemcpyDeviceToHost, C.stream));
@@ -1671,6 +1812,7 @@ int rofl_shift_points(const uint8_t *a32, size_t d, const uint8_t offset32[32], 
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
         HIPCHK(hipMemcpyAsync(ds, &hs, sizeof hs, hipMemcpyHostToDevice, C.stream));
         C.up(da, a32, 32 * d, C.stream);
+        count_decodes(d);
         ROFL_LAUNCH(k_decode, grid1(d), dim3(TPB), 0, C.stream, (u32)d, (u32)d, da, ds, (niels *)nullptr, o, status);
         u32 st = 0;
         C.down(out32, o, 32 * d, C.stream);
@@ -1755,6 +1897,7 @@ int rofl_dbg_msm(const uint8_t *scalars32, const uint8_t *points32, size_t n, ui
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
         C.up(dp, points32, n * 32, C.stream);
         C.up(ds, hs.data(), n * 32, C.stream);
+        count_decodes(n);
         ROFL_LAUNCH(k_decode, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (u32)n, dp, (const niels *)nullptr, dn, (uint8_t *)nullptr, status);
         u32 st = 0;
         HIPCHK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, C.stream));
@@ -1785,6 +1928,7 @@ int rofl_dbg_verify_labelled(const uint8_t *label, size_t label_len, size_t gens
         u32 *status = C.status.as<u32>(4);
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
         C.up(d_in, commits32, m * 32, C.stream);
+        count_decodes(m);
         ROFL_LAUNCH(k_decode, grid1(m), dim3(TPB), 0, C.stream, (u32)m, (u32)m, d_in, (const niels *)nullptr, d_vn, d_enc, status);
         std::vector<uint8_t> hV(m * 32); u32 *h_st = C.h_misc.as<u32>(4);
         uint8_t *hp = C.h_V.as<uint8_t>(m * 32);
@@ -1966,6 +2110,120 @@ int rofl_acc_destroy(uint64_t h) {
     g_accs.erase(h);
     return ROFL_OK;
 }
+// ---- a round resident on the device: ingested once, verified and accumulated from the decoded points ----
+int rofl_round_create(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out) {
+    if (!handle_out || d == 0 || max_clients == 0 || (record_len != 64 && record_len != 96)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    const size_t npts = record_len / 32;
+    size_t bytes;      // the larger array: max_clients * 2 npts * d decoded points
+    if (__builtin_mul_overflow(max_clients, d, &bytes) || __builtin_mul_overflow(bytes, 2 * npts * sizeof(niels), &bytes)) return fail(ROFL_BAD_PARAM, "round too large");
+    if (max_clients > kMaxBatchMembers || max_clients * 2 * npts * d >= ((size_t)1 << 31)) return fail(ROFL_BAD_PARAM, "round too large (split it)");      // what the Sigma leg's kernels index
+    auto R = std::make_shared<Round>();
+    R->d = d; R->rec_len = record_len; R->npts = npts; R->max_clients = max_clients; R->device = current_device();
+    DeviceBinding bind(R->device);
+    int rc = guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        R->bad.assign(3 * max_clients, ~0u);
+        HIPCHK(hipMalloc(&R->rec, max_clients * d * record_len));
+        HIPCHK(hipMalloc(&R->pts, max_clients * 2 * npts * d * sizeof(niels)));
+        HIPCHK(hipMalloc(&R->d_bad, 12 * max_clients));
+        return ROFL_OK;
+    });
+    if (rc) { if (R->rec) (void)hipFree(R->rec); if (R->pts) (void)hipFree(R->pts); if (R->d_bad) (void)hipFree(R->d_bad); return rc; }
+    std::lock_guard<std::mutex> lk(g_round_mu);
+    uint64_t h = g_round_next++;
+    g_rounds.emplace(h, R);
+    *handle_out = h;
+    return ROFL_OK;
+}
+int rofl_round_ingest(uint64_t h, size_t n_clients, const uint8_t *const *records, size_t *first_index_out) {
+    if (n_clients && !records) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::shared_ptr<Round> R = round_find(h);
+    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    for (size_t i = 0; i < n_clients; i++) if (!records[i]) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::unique_lock<std::shared_mutex> lk(R->rw);
+    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    if (n_clients > R->max_clients - R->n) return fail(ROFL_BAD_PARAM, "the round is full (nothing ingested)");
+    if (first_index_out) *first_index_out = R->n;
+    if (!n_clients) return ROFL_OK;
+    DeviceBinding bind(R->device);
+    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); return round_ingest_impl(*lane_lock.c, *R, n_clients, records); });
+}
+int rofl_round_verify_sigma(uint64_t h, int kind, const uint8_t *const *proofs, int *ok_out, uint8_t *csq_sum_out32) {
+    if (!ok_out || !proofs || kind < 0 || kind > 2) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::shared_ptr<Round> R = round_find(h);
+    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    if ((kind == 0) != (R->rec_len == 64)) return fail(ROFL_BAD_PARAM, "the proof kind does not fit the round's records");
+    std::shared_lock<std::shared_mutex> lk(R->rw);
+    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    std::lock_guard<std::mutex> leg(R->sigma_mu);
+    DeviceBinding bind(R->device);
+    const RoundSrc rs = R->src();
+    return guarded([&]() -> int { return sigma_verify_batch(kind, R->n, proofs, nullptr, R->d, ok_out, csq_sum_out32, false, &rs); });
+}
+int rofl_round_verify_range(uint64_t h, const uint8_t *const *proofs, size_t proof_len, size_t n_proofs, size_t k_checked, size_t prove_range,
+                            unsigned fp_bits, unsigned fp_frac, const uint8_t verifier_seed[32], int *ok_out) {
+    if (!ok_out || !proofs || !verifier_seed) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::shared_ptr<Round> R = round_find(h);
+    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    if (k_checked == 0 || k_checked > R->d) return fail(ROFL_BAD_PARAM, "k_checked outside the round's records");
+    std::shared_lock<std::shared_mutex> lk(R->rw);
+    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    if (R->n == 0) return ROFL_OK;
+    std::lock_guard<std::mutex> leg(R->range_mu);
+    DeviceBinding bind(R->device);
+    const RoundSrc rs = R->src();
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        return verify_impl(C, R->n, proofs, proof_len, n_proofs, nullptr, k_checked, prove_range, fp_bits, fp_frac, verifier_seed, ok_out, false, nullptr, 32, 0, 0, &rs); });
+}
+int rofl_round_accumulate(uint64_t h, uint64_t acc, const int *accept) {
+    std::shared_ptr<Round> R = round_find(h);
+    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    std::shared_ptr<Acc> A = acc_find(acc);
+    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    std::unique_lock<std::shared_mutex> lk(R->rw);
+    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    std::lock_guard<std::mutex> la(A->mu);
+    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
+    if (A->d != R->d || A->device != R->device) return fail(ROFL_BAD_PARAM, "the accumulator does not fit the round (length or device)");
+    std::vector<u32> cl;
+    for (size_t i = 0; i < R->n; i++) if (!accept || accept[i]) cl.push_back((u32)i);
+    DeviceBinding bind(R->device);
+    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); return round_accumulate_impl(*lane_lock.c, *R, *A, cl); });
+}
+int rofl_round_reset(uint64_t h) {
+    std::shared_ptr<Round> R = round_find(h);
+    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    std::unique_lock<std::shared_mutex> lk(R->rw);
+    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    R->n = 0;
+    return ROFL_OK;
+}
+int rofl_round_destroy(uint64_t h) {
+    std::shared_ptr<Round> R = round_find(h);
+    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    std::unique_lock<std::shared_mutex> lk(R->rw);
+    if (R->released) return fail(ROFL_BAD_PARAM, "unknown round handle");      // destroyed by another thread meanwhile
+    R->dead = true;
+    DeviceBinding bind(R->device);
+    int rc = guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane();
+        if (R->rec) HIPCHK(hipFree(R->rec));
+        R->rec = nullptr;
+        if (R->pts) HIPCHK(hipFree(R->pts));
+        R->pts = nullptr;
+        if (R->d_bad) HIPCHK(hipFree(R->d_bad));
+        R->d_bad = nullptr;
+        return ROFL_OK;
+    });
+    if (rc) return rc;      // the handle stays in the registry: a later destroy frees what is left
+    R->released = true;
+    std::lock_guard<std::mutex> g(g_round_mu);
+    g_rounds.erase(h);
+    return ROFL_OK;
+}
+int rofl_dbg_point_decodes(uint64_t *count_out) { if (!count_out) return ROFL_BAD_PARAM; *count_out = g_point_decodes.load(); return ROFL_OK; }
 size_t rofl_wire_encoded_size(const rofl_wire_msg_t *m) { return m ? wire::encoded_size(*m) : 0; }
 int rofl_wire_encode(const rofl_wire_msg_t *m, uint8_t *out, size_t cap, size_t *len_out) {
     if (!m || !out) return fail(ROFL_BAD_PARAM, "bad parameter");

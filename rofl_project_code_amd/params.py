@@ -184,6 +184,24 @@ def _num_checked(d, check_percentage):
     return min(int(d), int(np.floor(np.float64(x) + 0.5)))
 
 
+class _HostLegs:
+    """Where verify_batch takes the batched legs of the majority-shape members from: caller memory, through the existing batch entry points.
+    DeviceRound supplies the same three legs over the commitments it holds on the device (us = the members, idx = their positions in the
+    list verify_batch was given)."""
+
+    @staticmethod
+    def rand(cls, us, idx):
+        return cls._rand_batch(us)
+
+    @staticmethod
+    def square(cls, us, idx):
+        return cls._square_batch(us)
+
+    @staticmethod
+    def range(us, idx, k, prove_range, seed, fp, stride):
+        return range_proof_vec.verify_rangeproof_batch([u.range_proofs for u in us], [u.enc_values[:k] for u in us], prove_range, verifier_seed=seed, fp=fp, commit_stride=stride)
+
+
 class EncParamsRange:
     """params.rs:456-541."""
     kind = WIRE_ENC_RANGE
@@ -242,13 +260,14 @@ class EncParamsRange:
         return rand_proof_vec.verify_randproof_vec_batch([u.rand_proofs for u in us], [u.enc_values for u in us])
 
     @classmethod
-    def verify_batch(cls, updates, verifier_seed=None, fp=None):
+    def verify_batch(cls, updates, verifier_seed=None, fp=None, _legs=_HostLegs):
         """The server's side of a round (server.rs:656-687 hands every client's update to the verification pool; :474-484 rejects the round
         when one fails): EncModelParams::verify, EncRange / EncRangeCompressed arms (params.rs:185-203, 235-256), for ALL clients of the round as two
         batched calls that run side by side -- the randomness proofs of every client in one launch sequence (_rand_batch) and the L-inf legs
         through rofl_verify_rangeproof_batch_strided over the first k pairs of every client, read in place from the 64-byte records.  One
         verdict per update, the same as update.verify() gives it; updates whose shape (d, the randomness proof's count or size, the range
-        proofs' shape, prove_range, k) differs from the majority's are verified on their own."""
+        proofs' shape, prove_range, k) differs from the majority's are verified on their own.
+        `_legs` is internal (not part of the interface): where the batched legs take the commitments from -- DeviceRound passes itself."""
         fp = api._fp(fp)
         n = len(updates)
         res = [False] * n
@@ -274,8 +293,8 @@ class EncParamsRange:
         k = major[4]
         try:
             ok_rand, ok_range = _concurrently(
-                lambda: cls._rand_batch(us),
-                lambda: range_proof_vec.verify_rangeproof_batch([u.range_proofs for u in us], [u.enc_values[:k] for u in us], major[3], verifier_seed=_sub_seed(verifier_seed, b"v"), fp=fp, commit_stride=64))
+                lambda: _legs.rand(cls, us, idx),
+                lambda: _legs.range(us, idx, k, major[3], _sub_seed(verifier_seed, b"v"), fp, 64))
         except (RoflError, ValueError, OverflowError, IndexError) as e:
             if not _is_message_error(e):
                 raise      # the verifier itself failed (HIP / RCCL runtime error): not a verdict about any client
@@ -461,14 +480,15 @@ class EncParamsL2:
         return square_rand_proof_vec.verify_l2rangeproof_vec_batch([u.square_proofs for u in us], [u.enc_values for u in us], with_csq_sums=True)
 
     @classmethod
-    def verify_batch(cls, updates, verifier_seed=None, fp=None):
+    def verify_batch(cls, updates, verifier_seed=None, fp=None, _legs=_HostLegs):
         """The server's side of a round (server.rs:656-687 hands every client's update to the verification pool; :474-484 rejects the round
         when one fails): EncModelParams::verify, EncL2 arm (params.rs:204-232), for ALL clients of the round as three batched calls that run
         side by side -- the square proofs of every client in one launch sequence (rofl_verify_squarerandproof_vec_batch, which also hands
         back every client's sum of c_sq), the L-inf legs through rofl_verify_rangeproof_batch_strided (commitments read in place from the
         96-byte SquareRandProofCommitments; one random-weighted equation per batch with verify_batch = 2) and, once the sums are there, the
         L2 sum proofs through rofl_verify_rangeproof_l2_batch.  One verdict per client, the same as update.verify() gives each of them;
-        clients whose shapes differ from the majority's are verified on their own."""
+        clients whose shapes differ from the majority's are verified on their own.
+        `_legs` is internal (not part of the interface): where the batched legs take the commitments from -- DeviceRound passes itself."""
         fp = api._fp(fp)
         n = len(updates)
         res = [False] * n
@@ -490,7 +510,7 @@ class EncParamsL2:
                 res[i] = bool(sh is not None and updates[i].verify(verifier_seed=verifier_seed, fp=fp))
         us = [updates[i] for i in idx]
         def sigma_then_sum():
-            ok_sq, sums = cls._square_batch(us)
+            ok_sq, sums = _legs.square(cls, us, idx)
             if kernel_time_sink is not None:
                 kernel_time_sink(api.last_kernel_times())      # (this thread makes two calls; _timed reports the second)
             ok_sum = l2_range_proof_vec.verify_rangeproof_l2_batch([u.square_range_proof for u in us], sums, major[5], verifier_seed=_sub_seed(verifier_seed, b"s"), fp=fp)
@@ -498,7 +518,7 @@ class EncParamsL2:
         try:
             (ok_sq, ok_sum), ok_range = _concurrently(
                 sigma_then_sum,
-                lambda: range_proof_vec.verify_rangeproof_batch([u.range_proofs for u in us], [u.enc_values for u in us], major[4], verifier_seed=_sub_seed(verifier_seed, b"v"), fp=fp, commit_stride=96))
+                lambda: _legs.range(us, idx, major[0], major[4], _sub_seed(verifier_seed, b"v"), fp, 96))
         except (RoflError, ValueError, OverflowError, IndexError) as e:
             if not _is_message_error(e):
                 raise      # the verifier itself failed (HIP / RCCL runtime error): not a verdict about any client
@@ -707,6 +727,164 @@ class DeviceAccumulator:
         if getattr(self, "_open", False):
             self._open = False
             api.accumulator.destroy(self._h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceRound:
+    """One round of updates of container class `cls`, resident on the device (rofl_round_*): every update is uploaded once and every point
+    of its enc_values decoded once, as it is ingested; verify() runs the legs of cls.verify_batch over the decoded points and
+    accumulate_into() adds the accepted updates to a DeviceAccumulator from the same points -- no second upload, no second decode.
+
+        with DeviceRound(EncParamsL2, d, max_clients=48) as rnd:
+            rnd.ingest(updates[:20]); rnd.ingest(updates[20:])      # as the messages arrive (enc_values read in place)
+            ok = rnd.verify()                                       # == EncParamsL2.verify_batch(updates)
+            rnd.accumulate_into(acc, accept=ok)                     # acc.export() == acc.accumulate_batch(accepted updates)
+
+    Updates whose enc_values are not `size` records cannot sit in the cache: they are kept in the list, verified on their own and
+    accumulated through acc.accumulate_batch (zip truncation included), as are members whose proofs are off the round's majority shape.
+    The records are a snapshot: enc_values are copied to the device at ingest() and never read again, while the proofs are read from the
+    update objects at verify() -- an update changed in place after it was ingested must be ingested again (reset()).
+    EncParamsRangeCompressed keeps its randomness leg on rofl_verify_compressed_randproof_batch (host bytes); its range leg and the
+    accumulation come from the round.  The round lives on the device of the thread that created it."""
+
+    def __init__(self, cls, size, max_clients):
+        if cls not in (EncParamsRange, EncParamsRangeCompressed, EncParamsL2, EncParamsL2Compressed):
+            raise ValueError("cls must be one of the four encrypted-update containers")
+        self.cls, self.size, self.max_clients = cls, int(size), int(max_clients)
+        self.record_len = 96 if issubclass(cls, EncParamsL2) else 64
+        self.updates, self._slot, self._n_cached = [], [], 0
+        self._open = False
+        self._h = api.device_round.create(self.size, self.record_len, self.max_clients)
+        self._open = True
+
+    def __len__(self):
+        return len(self.updates)
+
+    def _check_open(self):
+        if not self._open:
+            raise RoflError(11, "unknown round handle")
+
+    def ingest(self, updates, device_records=None):
+        """Appends updates (instances of cls) to the round; more than max_clients in all raises RoflError 11 and ingests nothing.
+        device_records[i] (optional): a contiguous uint8 GPU tensor holding update i's enc_values bytes, read on the device instead."""
+        self._check_open()
+        updates = list(updates)
+        if len(self.updates) + len(updates) > self.max_clients:
+            raise RoflError(11, "the round is full (nothing ingested)")
+        ptrs, slots = [], []
+        for j, u in enumerate(updates):
+            if not isinstance(u, self.cls):
+                raise ValueError("the updates of a round are of its container class")
+            ev = u.enc_values
+            fits = ev.ndim == 2 and ev.shape == (self.size, self.record_len) and ev.dtype == np.uint8 and ev.flags.c_contiguous
+            dv = device_records[j] if device_records is not None else None
+            if fits and dv is not None:
+                p, nbytes = api._dev_arg(dv, 1)
+                if nbytes != ev.size:
+                    raise ValueError("device_records[i] holds the bytes of update i's enc_values")
+                ptrs.append(p.value)
+            elif fits:
+                ptrs.append(ev.ctypes.data)
+            slots.append(len(ptrs) - 1 if fits else None)
+        first = api.device_round.ingest(self._h, ptrs) if ptrs else self._n_cached
+        assert first == self._n_cached
+        self.updates.extend(updates)
+        self._slot.extend(None if sl is None else first + sl for sl in slots)
+        self._n_cached += len(ptrs)
+        return True
+
+    # ---- the legs of cls.verify_batch over the round (the interface of _HostLegs) ----
+    def _on_round(self, idx):
+        """the majority members sit in the cache (their d is the round's): the legs can run there"""
+        return all(self._slot[i] is not None for i in idx)
+
+    def _ptrs(self, us, idx, arr):
+        p = [None] * self._n_cached      # clients of the cache that are not among `us` are left out of the leg
+        for u, i in zip(us, idx):
+            p[self._slot[i]] = arr(u).ctypes.data
+        return p
+
+    def rand(self, cls, us, idx):
+        if cls is EncParamsRangeCompressed or not self._on_round(idx):
+            return _HostLegs.rand(cls, us, idx)
+        ok, _ = api.device_round.verify_sigma(self._h, 0, self._ptrs(us, idx, lambda u: u.rand_proofs))
+        return [ok[self._slot[i]] for i in idx]
+
+    def square(self, cls, us, idx):
+        if not self._on_round(idx):
+            return _HostLegs.square(cls, us, idx)
+        ok, sums = api.device_round.verify_sigma(self._h, 2 if cls is EncParamsL2Compressed else 1, self._ptrs(us, idx, lambda u: u.square_proofs), want_csq=True)
+        sl = [self._slot[i] for i in idx]
+        return [ok[s] for s in sl], sums[sl]
+
+    def range(self, us, idx, k, prove_range, seed, fp, stride):
+        if not self._on_round(idx):
+            return _HostLegs.range(us, idx, k, prove_range, seed, fp, stride)
+        n_proofs, proof_len = us[0].range_proofs.shape
+        ok = api.device_round.verify_range(self._h, self._ptrs(us, idx, lambda u: u.range_proofs), proof_len, n_proofs, k, prove_range, verifier_seed=seed, fp=fp)
+        return [ok[self._slot[i]] for i in idx]
+
+    def verify(self, verifier_seed=None, fp=None):
+        """list[bool], one per ingested update, in order: exactly cls.verify_batch(updates) -- the same majority-shape rule, the legs side by
+        side on the round's device, the same error policy (a HIP error is raised, never a verdict)"""
+        self._check_open()
+        return self.cls.verify_batch(self.updates, verifier_seed=verifier_seed, fp=fp, _legs=self)
+
+    def accumulate_into(self, acc, accept=None):
+        """Adds the updates with accept[i] true (None: all) to the DeviceAccumulator `acc`: the cached ones from the decoded points
+        (rofl_round_accumulate), the others through accumulate_batch.  acc.export() afterwards ==
+        acc.accumulate_batch([u for u, a in zip(updates, accept) if a]), and like that call it is all or nothing: RoflError 5 when an accepted
+        update has an undecodable L or R, `acc` unchanged.  For that the members outside the cache are summed into a partial accumulator of
+        their own first (nothing of `acc` is touched if one of them fails), the cached ones are added next (refused before anything is
+        launched if one of them has a bad point), and the partial -- valid points by then -- is merged last."""
+        self._check_open()
+        n = len(self.updates)
+        accept = [True] * n if accept is None else [bool(a) for a in accept]
+        if len(accept) != n:
+            raise ValueError("one accept flag per ingested update")
+        flags = [0] * self._n_cached
+        others = []
+        for u, sl, a in zip(self.updates, self._slot, accept):
+            if a and sl is not None:
+                flags[sl] = 1
+            elif a:
+                others.append(u)
+        part = DeviceAccumulator(acc.size) if others else None
+        try:
+            if others:
+                part.accumulate_batch(others)
+            if self._n_cached:
+                api.device_round.accumulate(self._h, acc._h, flags)
+            if others:
+                acc.accumulate_pairs(part.export())
+        finally:
+            if part is not None:
+                part.close()
+        return True
+
+    def reset(self):
+        """no updates; the device memory is kept for the next round"""
+        self._check_open()
+        api.device_round.reset(self._h)
+        self.updates, self._slot, self._n_cached = [], [], 0
+
+    def close(self):
+        """frees the device memory (once); later calls on the round raise RoflError 11"""
+        if getattr(self, "_open", False):
+            self._open = False
+            api.device_round.destroy(self._h)
 
     def __enter__(self):
         return self

@@ -296,11 +296,17 @@ int rofl_acc_destroy(uint64_t h);    /* frees the device memory; the handle is i
  * the cached (L, R) of the accepted clients into a rofl_acc_* accumulator without an upload or a decode.  Handles as for rofl_acc_*: from
  * the library's registry, unknown or destroyed = 11, parameter checks (11) before the device is touched, the round lives on the device of
  * the thread that created it and every later call runs there (the `devices` option does not apply: one round per device, partial sums
- * merge through rofl_acc_export / rofl_acc_add).  Calls on one round are serialised, except that one verify_sigma and one verify_range
- * may run side by side.
+ * merge through rofl_acc_export / rofl_acc_add).  Calls on one round are serialised, except that the verification legs only read the
+ * round: one verify_sigma, one verify_range and one verify_compressed may run side by side.
  *   record_len 64: ElGamalPair (L | R); 96: SquareRandProofCommitments (L | R | c_sq).  create allocates what max_clients clients need
  *   (record bytes and decoded points: max_clients * d * (record_len + 6 * record_len) bytes); nothing is allocated per round afterwards. */
-int rofl_round_create(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out);
+int rofl_round_create(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out);      /* = rofl_round_create_ex with flags 0 */
+/* flags: ROFL_ROUND_COMPRESSED -- a round of EncParamsRangeCompressed updates: ingest also keeps, per client, the CompressedRandProof
+ * transcript as it stands after the client's d labelled pairs (a few hundred bytes; hashed on the host from the very bytes that go to the
+ * device and are decoded there), which rofl_round_verify_compressed continues.  Needs record_len 64 and d < 900000 (the limit of
+ * rofl_verify_compressed_randproof), else 11; unknown flag bits: 11.  A round without the flag ingests exactly as before. */
+#define ROFL_ROUND_COMPRESSED 1u
+int rofl_round_create_ex(size_t d, size_t record_len, size_t max_clients, unsigned flags, uint64_t *handle_out);
 /* Appends n_clients clients (records[i]: d * record_len bytes, host or device memory) as clients first .. first + n_clients of the round
  * (*first_index_out, may be NULL).  More clients than max_clients leaves room for: 11, nothing ingested.  A point that does not decode
  * never fails the call: it is remembered per client and component and fails exactly the legs that read it (below). */
@@ -315,6 +321,13 @@ int rofl_round_verify_sigma(uint64_t h, int kind, const uint8_t *const *proofs, 
  * as they do there); the L are not decoded again.  An undecodable L fails a client only at an index < k_checked.  proofs[i] NULL as above. */
 int rofl_round_verify_range(uint64_t h, const uint8_t *const *proofs, size_t proof_len, size_t n_proofs, size_t k_checked,
                             size_t prove_range, unsigned fp_bits, unsigned fp_frac, const uint8_t verifier_seed[32], int *ok_out);
+/* The CompressedRandProofs (params.rs:235-256) of every ingested client of a ROFL_ROUND_COMPRESSED round (any other round: 11): proofs[i]
+ * is client i's 128-byte proof, or NULL to leave the client out (ok_out[i] = 0).  ok_out[i] is exactly what
+ * rofl_verify_compressed_randproof_batch returns for client i on (proofs[i], the bytes ingested for client i): the same two exact group
+ * equations, no random weights; an undecodable C', a non-canonical Z_m / Z_r or an undecodable L or R at any index fails that member alone.
+ * The call reads the round only -- the transcript state and the decoded L and R of ingest: no record is uploaded, decoded or hashed again,
+ * and what the caller's memory holds by now does not matter.  A round with no clients: 0. */
+int rofl_round_verify_compressed(uint64_t h, const uint8_t *const *proofs, int *ok_out);
 /* Adds the (L, R) of the clients with accept[i] != 0 (accept NULL: every ingested client) to accumulator `acc` (same device, same d, else
  * 11).  All or nothing as rofl_acc_add: an accepted client with an undecodable L or R -> 5, the accumulator unchanged (decided before
  * anything is launched; d past one point tile of 131 072 goes through the accumulator's work copy, committed by a last fold).  The

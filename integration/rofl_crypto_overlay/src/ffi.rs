@@ -84,10 +84,13 @@ extern "C" {
     /// a round resident on the device (server.rs:474-521, 656-714): records ingested once (one upload, one decode per point), both
     /// verification legs and the accumulation read the decoded points; handles as for rofl_acc_*
     pub fn rofl_round_create(d: usize, record_len: usize, max_clients: usize, handle_out: *mut u64) -> c_int;
+    /// flags = ROFL_ROUND_COMPRESSED (1): the round keeps each client's CompressedRandProof transcript prefix for rofl_round_verify_compressed
+    pub fn rofl_round_create_ex(d: usize, record_len: usize, max_clients: usize, flags: c_uint, handle_out: *mut u64) -> c_int;
     pub fn rofl_round_ingest(h: u64, n_clients: usize, records: *const *const u8, first_index_out: *mut usize) -> c_int;
     pub fn rofl_round_verify_sigma(h: u64, kind: c_int, proofs: *const *const u8, ok_out: *mut c_int, csq_sum_out32: *mut u8) -> c_int;
     pub fn rofl_round_verify_range(h: u64, proofs: *const *const u8, proof_len: usize, n_proofs: usize, k_checked: usize,
         prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, verifier_seed: *const u8, ok_out: *mut c_int) -> c_int;
+    pub fn rofl_round_verify_compressed(h: u64, proofs: *const *const u8, ok_out: *mut c_int) -> c_int;
     pub fn rofl_round_accumulate(h: u64, acc: u64, accept: *const c_int) -> c_int;
     pub fn rofl_round_reset(h: u64) -> c_int;
     pub fn rofl_round_destroy(h: u64) -> c_int;

@@ -883,10 +883,12 @@ class accumulator:
 class device_round:
     """rofl_round_*: a round's records resident on the device -- uploaded and decoded once by ingest, read by both verification legs and by
     the accumulation.  Handles are registry ids; records / proofs are pointers (int / c_void_p; a proof pointer may be None: client left out)."""
+    COMPRESSED = 1      # ROFL_ROUND_COMPRESSED: ingest keeps every client's CompressedRandProof transcript prefix (verify_compressed)
+
     @staticmethod
-    def create(d, record_len, max_clients):
+    def create(d, record_len, max_clients, flags=0):
         h = ctypes.c_uint64()
-        _check(lib().rofl_round_create(_sz(d), _sz(record_len), _sz(max_clients), ctypes.byref(h)))
+        _check(lib().rofl_round_create_ex(_sz(d), _sz(record_len), _sz(max_clients), ctypes.c_uint(int(flags)), ctypes.byref(h)))
         return h.value
 
     @staticmethod
@@ -914,6 +916,15 @@ class device_round:
         ok = (ctypes.c_int * max(n, 1))()
         seed = bytes(verifier_seed) if verifier_seed is not None else os.urandom(32)
         _check(lib().rofl_round_verify_range(ctypes.c_uint64(h), pp, _sz(proof_len), _sz(n_proofs), _sz(k_checked), _sz(prove_range), *_fp(fp), seed, ok))
+        return [bool(ok[i]) for i in range(n)]
+
+    @staticmethod
+    def verify_compressed(h, proofs):
+        """the 128-byte CompressedRandProofs of a round created with COMPRESSED, one pointer (or None) per ingested client -> list[bool]"""
+        n = len(proofs)
+        pp = (ctypes.c_void_p * max(n, 1))(*proofs)
+        ok = (ctypes.c_int * max(n, 1))()
+        _check(lib().rofl_round_verify_compressed(ctypes.c_uint64(h), pp, ok))
         return [bool(ok[i]) for i in range(n)]
 
     @staticmethod

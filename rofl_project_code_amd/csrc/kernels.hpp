@@ -2835,6 +2835,28 @@ __global__ void __launch_bounds__(TPB) k_round_sum(u32 tn, u32 j0, u32 S, u32 na
     store_gd(&part[((size_t)s * tn + j) * 2 + which], acc);
 }
 #endif
+// The scalars of the compressed randomness leg for a selection of the round's clients: y = blockIdx.y is the y-th selected client, sel[y]
+// its index in the round, sq[sel[y] * MAX_LG + b] = c^(2^b) (Montgomery) its table -- the tables lie by client as the cache does (one upload
+// per call, whatever the groups), out_canon[y * d + i] = c^(i + 1) is packed by selection (the scalar array of the client's two MSM
+// problems).  A thread takes kRoundCpowRun consecutive exponents: one walk of the table for the first (popcount(i + 1) multiplications,
+// what k_cpow_scalars_batch spends on every element), one multiplication by c for each of the others; its stores are one 128-byte line.
+constexpr u32 kRoundCpowRun = 4;
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_round_cpow_scalars(u32 d, const sc *sq, const u32 *sel, sc *out_canon) {
+    const size_t y = blockIdx.y;
+    const size_t i0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kRoundCpowRun;
+    if (i0 >= d) return;
+    const sc *tab = sq + (size_t)sel[y] * MAX_LG;
+    const sc c = load_sc(&tab[0]);
+    sc p = sc_pow_tab(tab, (u32)i0 + 1);
+    sc *o = out_canon + y * d + i0;
+    const u32 cnt = (u32)(d - i0 < kRoundCpowRun ? d - i0 : kRoundCpowRun);
+    for (u32 k = 0; k < cnt; k++) {
+        store_sc(&o[k], sc_from_mont(p));
+        if (k + 1 < cnt) p = sc_montmul(p, c);
+    }
+}
+#endif
 
 // ================================================================ BSGS discrete log (bsgs32.rs:14-73, pedersen_ops.rs:27-53)
 // Baby-step table: keys[x] = compress(x B), x = 0..m, indexed by an open-addressing hash table (slot = first 8 key

@@ -717,11 +717,15 @@ int acc_add_impl(Ctx &C, Acc &A, const std::vector<size_t> &cl, const std::vecto
 // The clients' records as ingested and their decoded points (RoundSrc's layout), allocated once for max_clients by create.  Ingest,
 // accumulate, reset and destroy hold the round exclusively; the two verification legs hold it shared (they only read the record points --
 // the Sigma leg also writes the odd slots, which no other call reads) and may run side by side on two lanes, one leg of each kind at a time.
+// A round created with ROFL_ROUND_COMPRESSED also keeps, per client, the CompressedRandProof transcript as it stands after the client's d
+// labelled pairs (everything the transcript absorbs before C' depends on the records alone): hashed at ingest from the bytes that are
+// decoded, so that the compressed leg's verdict is about the snapshot the accumulation adds, whatever became of the caller's memory since.
 struct Round {
-    int device = 0; size_t d = 0, rec_len = 0, npts = 0, max_clients = 0, n = 0;
+    int device = 0; size_t d = 0, rec_len = 0, npts = 0, max_clients = 0, n = 0; unsigned flags = 0;
     uint8_t *rec = nullptr; niels *pts = nullptr; u32 *d_bad = nullptr;
     std::vector<u32> bad;      // host copy of d_bad: [client][3]
-    std::shared_mutex rw; std::mutex sigma_mu, range_mu;
+    std::vector<Merlin> prefix;      // ROFL_ROUND_COMPRESSED: [client], the Merlin state after the last pair (n of them)
+    std::shared_mutex rw; std::mutex sigma_mu, range_mu, comp_mu;
     bool dead = false, released = false;
     RoundSrc src() const { return RoundSrc{d, npts, rec, pts, bad.data()}; }
 };
@@ -730,24 +734,56 @@ std::map<uint64_t, std::shared_ptr<Round>> g_rounds;
 uint64_t g_round_next = 1;
 std::shared_ptr<Round> round_find(uint64_t h) { std::lock_guard<std::mutex> lk(g_round_mu); auto it = g_rounds.find(h); return it == g_rounds.end() ? nullptr : it->second; }
 
+// The Merlin states of nc CompressedRandProof transcripts after their d labelled pairs (compressed_challenge up to, not including, C'), on
+// the lane's host pool: eight transcripts per AVX-512 stream, the scalar transcript for groups of fewer than five and CPUs without AVX-512
+// (the split compressed_challenges makes).  pairs[j]: d x 64 bytes in host memory.
+void compressed_prefixes(Ctx &C, size_t nc, const uint8_t *const *pairs, size_t d, Merlin *out) {
+    static const bool x8_on = k8::available();
+    const Merlin start = [] { Merlin t("CompressedRandProof", 19); t.append("dom-sep", (const uint8_t *)"randomness proof v1", 19); return t; }();
+    std::vector<std::pair<size_t, size_t>> tasks;      // (first client, count)
+    for (size_t j0 = 0; j0 < nc; j0 += 8) {
+        const size_t cnt = std::min<size_t>(8, nc - j0);
+        if (x8_on && cnt >= 5) tasks.emplace_back(j0, cnt);
+        else for (size_t l = 0; l < cnt; l++) tasks.emplace_back(j0 + l, 1);
+    }
+    C.pool->run(tasks.size(), [&](size_t k) {
+        const size_t j0 = tasks[k].first, cnt = tasks[k].second;
+        for (size_t l = 0; l < cnt; l++) out[j0 + l] = start;
+        if (cnt == 1) {
+            for (size_t i = 0; i < d; i++) { uint8_t lbl[3] = {(uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2)}; out[j0].append_lbl(lbl, 3, pairs[j0] + 64 * i, 64); }
+            return;
+        }
+        Merlin *tp[8]; const uint8_t *msg[8];
+        for (size_t l = 0; l < cnt; l++) { tp[l] = &out[j0 + l]; msg[l] = pairs[j0 + l]; }
+        k8::append_lbl3_run_x8(tp, (int)cnt, 0, msg, d);
+    });
+}
 // clients [R.n, R.n + n): the records go up in groups of ~64 MB through two pinned staging buffers (the pool copies group g + 1 while group g
-// is on its way and being decoded; device-resident records are copied on the device), one k_round_ingest per group: every point decoded once
+// is on its way and being decoded; device-resident records are copied on the device), one k_round_ingest per group: every point decoded once.
+// A ROFL_ROUND_COMPRESSED round hashes each group's transcript prefixes on the pool while the device uploads and decodes the group: host
+// records from the pinned staging copy that is being uploaded (the bytes that are decoded, not the caller's memory), device records from
+// one copy back of what was copied into the round.  The states join the round with its client count, after the last synchronisation.
 int round_ingest_impl(Ctx &C, Round &R, size_t n, const uint8_t *const *records) {
     const size_t d = R.d, per = d * R.rec_len, first = R.n;
+    const bool comp = (R.flags & ROFL_ROUND_COMPRESSED) != 0;
     C.init();
     HIPCHK(hipMemsetAsync(R.d_bad + 3 * first, 0xff, 12 * n, C.stream));
     const size_t G = std::max<size_t>(1, std::min<size_t>(n, ((size_t)64 << 20) / per));
     std::vector<char> on_dev(n);
     for (size_t i = 0; i < n; i++) on_dev[i] = is_device_ptr(records[i]);
-    uint8_t *stb[2] = {nullptr, nullptr};
+    std::vector<Merlin> prefix;
+    if (comp) prefix.assign(n, Merlin("CompressedRandProof", 19));
+    uint8_t *stb[2] = {nullptr, nullptr}; bool uploaded[2] = {false, false};
     for (size_t g0 = 0, gi = 0; g0 < n; g0 += G, gi++) {
         const size_t gc = std::min(G, n - g0);
         uint8_t *dst = R.rec + (first + g0) * per;
-        bool any_host = false; for (size_t i = g0; i < g0 + gc; i++) any_host |= !on_dev[i];
+        bool any_host = false, any_dev = false; for (size_t i = g0; i < g0 + gc; i++) { any_host |= !on_dev[i]; any_dev |= (bool)on_dev[i]; }
+        const int b = (int)(gi & 1);
+        if (any_host || (comp && any_dev)) {      // (without the flag: only a group with host records touches the staging buffers)
+            if (!stb[b]) stb[b] = (uint8_t *)C.stg.alloc(G * per); else if (uploaded[b]) C.wait_event(C.pool_event(b));
+        }
+        uint8_t *st = stb[b];
         if (any_host) {
-            const int b = (int)(gi & 1);
-            if (!stb[b]) stb[b] = (uint8_t *)C.stg.alloc(G * per); else C.wait_event(C.pool_event(b));
-            uint8_t *st = stb[b];
             const size_t slices = std::max<size_t>(1, per >> 18);      // ~256 KB per task
             C.pool->run(gc * slices, [&](size_t t) { size_t i = t / slices, k = t % slices; if (on_dev[g0 + i]) return;
                                                      size_t lo = per * k / slices, hi = per * (k + 1) / slices; stage_copy(st + i * per + lo, records[g0 + i] + lo, hi - lo); });
@@ -757,17 +793,28 @@ int round_ingest_impl(Ctx &C, Round &R, size_t n, const uint8_t *const *records)
                 HIPCHK(hipMemcpyAsync(dst + i * per, st + i * per, (j - i) * per, hipMemcpyHostToDevice, C.stream));
                 i = j;
             }
-            HIPCHK(hipEventRecord(C.pool_event(b), C.stream));
+            HIPCHK(hipEventRecord(C.pool_event(b), C.stream)); uploaded[b] = true;
         }
         for (size_t i = 0; i < gc; i++) if (on_dev[g0 + i]) HIPCHK(hipMemcpyAsync(dst + i * per, records[g0 + i], per, hipMemcpyDeviceToDevice, C.stream));
+        if (comp && any_dev) {      // the round's copy of the device records comes back once, for the transcripts (before the decode is queued: the wait below covers copies only)
+            for (size_t i = 0; i < gc; i++) if (on_dev[g0 + i]) HIPCHK(hipMemcpyAsync(st + i * per, dst + i * per, per, hipMemcpyDeviceToHost, C.stream));
+            HIPCHK(hipEventRecord(C.pool_event(2), C.stream));
+        }
         count_decodes(gc * R.npts * d);
         ROFL_LAUNCH(k_round_ingest, dim3((unsigned)((R.npts * d + TPB - 1) / TPB), (unsigned)gc), dim3(TPB), 0, C.stream, (u32)d, (u32)R.npts, (const uint8_t *)dst,
                     R.pts + (first + g0) * 2 * R.npts * d, R.d_bad + 3 * (first + g0));
+        if (comp) {      // beside the upload and the decode of this group
+            if (any_dev) C.wait_event(C.pool_event(2));
+            std::vector<const uint8_t *> src(gc);
+            for (size_t i = 0; i < gc; i++) src[i] = st + i * per;
+            compressed_prefixes(C, gc, src.data(), d, prefix.data() + g0);
+        }
     }
     u32 *hb = C.h_misc.as<u32>(3 * n);
     HIPCHK(hipMemcpyAsync(hb, R.d_bad + 3 * first, 12 * n, hipMemcpyDeviceToHost, C.stream));
     C.sync();
     memcpy(&R.bad[3 * first], hb, 12 * n);
+    if (comp) { R.prefix.resize(first, Merlin("CompressedRandProof", 19)); R.prefix.insert(R.prefix.end(), prefix.begin(), prefix.end()); }
     R.n = first + n;
     return ROFL_OK;
 }
@@ -1603,6 +1650,74 @@ int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8
     timing_end(C);
     return ROFL_OK;
 }
+// compressed_verify_batch for the clients of a ROFL_ROUND_COMPRESSED round, from what ingest left on the device and in the round: nothing is
+// uploaded but the power tables, nothing is decoded and no pair is hashed.  Per client with a proof and without a bad L or R (known since
+// ingest): the stored transcript state is copied, C' appended and c drawn, on the host pool with the decoding of C' and the canonical checks
+// of Z_m, Z_r -- a proof that fails those is out before anything is launched, as is a client left out or with a bad point (verdict 0 either
+// way, as compressed_verify_batch gives them after its MSM).  The others are the selection: their tables go up once, by client;
+// then in groups of at most sixteen (the host-bytes call's group: one scalar array of sixteen clients, whatever the round)
+// k_round_cpow_scalars and ONE multi-problem MSM over slots 0 (L) and 2 (R) of the cache as they lie, two problems per client sharing the
+// client's scalars.  The final equalities run on the host pool.
+int round_verify_compressed_impl(Ctx &C, Round &R, const uint8_t *const *proofs, int *ok_out) {
+    const size_t n = R.n, d = R.d;
+    for (size_t i = 0; i < n; i++) ok_out[i] = 0;
+    std::vector<u32> cand;
+    for (size_t i = 0; i < n; i++) if (proofs[i] && R.bad[3 * i] == ~0u && R.bad[3 * i + 1] == ~0u) cand.push_back((u32)i);
+    if (cand.empty()) return ROFL_OK;
+    C.init();
+    C.batch_mode = n > 1;
+    timing_begin(C);
+    struct Item { ge Lp, Rp; sc c; bool ok; };
+    std::vector<Item> it(cand.size());
+    C.pool->run(cand.size(), [&](size_t k) {
+        const uint8_t *proof = proofs[cand[k]];
+        Item &q = it[k];      // the proof's own encodings: compressed_verify's FormatError
+        q.ok = ristretto_decode(q.Lp, proof) && ristretto_decode(q.Rp, proof + 32) && sc_is_canonical_bytes(proof + 64) && sc_is_canonical_bytes(proof + 96);
+        if (!q.ok) return;
+        Merlin t = R.prefix[cand[k]];
+        t.append("C_prime_eg", proof, 64);
+        q.c = t.challenge_scalar("c");
+    });
+    std::vector<u32> sel; std::vector<size_t> item_of;
+    for (size_t k = 0; k < cand.size(); k++) if (it[k].ok) { sel.push_back(cand[k]); item_of.push_back(k); }
+    const size_t ns = sel.size();
+    if (!ns) { timing_end(C); return ROFL_OK; }
+    const size_t G = std::min<size_t>(ns, 16);
+    sc *scal = C.aux_scal.as<sc>(G * d);
+    sc *dtab = C.tmp_out.as<sc>(n * MAX_LG), *htab = C.h_cp.as<sc>(n * MAX_LG);
+    u32 *dsel = C.tmp_in2.as<u32>(ns), *hsel = C.h_misc.as<u32>(ns);
+    // the tables lie by client; only the selected clients' rows are written and read
+    const size_t lo = sel.front(), hi = sel.back() + 1;
+    for (size_t j = 0; j < ns; j++) fill_pow2(htab + (size_t)sel[j] * MAX_LG, h_mont(it[item_of[j]].c), MAX_LG);
+    memcpy(hsel, sel.data(), 4 * ns);
+    HIPCHK(hipMemcpyAsync(dtab + lo * MAX_LG, htab + lo * MAX_LG, sizeof(sc) * MAX_LG * (hi - lo), hipMemcpyHostToDevice, C.stream));
+    HIPCHK(hipMemcpyAsync(dsel, hsel, 4 * ns, hipMemcpyHostToDevice, C.stream));
+    std::vector<ge5> sumL(ns), sumR(ns);
+    const size_t cstride = 2 * R.npts * d;      // a client's slots in the cache
+    for (size_t g0 = 0; g0 < ns; g0 += G) {
+        const size_t gc = std::min(G, ns - g0);      // (gridDim.y = gc <= 16)
+        ROFL_LAUNCH(k_round_cpow_scalars, grid1((d + kRoundCpowRun - 1) / kRoundCpowRun, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const sc *)dtab, (const u32 *)(dsel + g0), scal);
+        std::vector<MsmProb> pr(2 * gc);
+        for (size_t j = 0; j < gc; j++) {
+            const niels *base = R.pts + (size_t)sel[g0 + j] * cstride;
+            pr[2 * j] = MsmProb{base, scal + j * d}; pr[2 * j + 1] = MsmProb{base + 2 * d, scal + j * d};
+        }
+        C.tm.t.msm_terms += 2 * gc * d;
+        std::vector<ge5> res;
+        msm_run(C, pr, d, res);      // (returns after the lane's stream has been waited for: the next group may overwrite the scalars)
+        for (size_t j = 0; j < gc; j++) { sumL[g0 + j] = res[2 * j]; sumR[g0 + j] = res[2 * j + 1]; }
+    }
+    auto neg5 = [](const ge5 &p) { ge5 r = p; r.X = h51::neg(p.X); r.T = h51::neg(p.T); return r; };
+    C.pool->run(ns, [&](size_t j) {
+        const uint8_t *proof = proofs[sel[j]]; const Item &q = it[item_of[j]];
+        sc zm = sc_frombytes(proof + 64), zr = sc_frombytes(proof + 96);
+        ge5 e1 = h51::gadd(h51::gadd(h_fixed_mul(C.ht.B5, zm), h_fixed_mul(C.ht.Bb5, zr)), neg5(h51::gadd(h51::from_ge(q.Lp), sumL[j])));
+        ge5 e2 = h51::gadd(h_fixed_mul(C.ht.B5, zr), neg5(h51::gadd(h51::from_ge(q.Rp), sumR[j])));
+        ok_out[sel[j]] = h51::is_identity_ristretto(e1) && h51::is_identity_ristretto(e2);
+    });
+    timing_end(C);
+    return ROFL_OK;
+}
 }  // namespace
 
 namespace {
@@ -2110,20 +2225,26 @@ int rofl_acc_destroy(uint64_t h) {
     g_accs.erase(h);
     return ROFL_OK;
 }
-// ---- a round resident on the device: ingested once, verified and accumulated from the decoded points ----
-int rofl_round_create(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out) {
+// ---- a round resident on the device: ingested once, verified and accumulated from the decoded points; a ROFL_ROUND_COMPRESSED round also
+// ---- hashes its CompressedRandProof transcript prefixes at ingest, and its compressed leg reads nothing but the round ----
+int rofl_round_create(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out) { return rofl_round_create_ex(d, record_len, max_clients, 0, handle_out); }
+int rofl_round_create_ex(size_t d, size_t record_len, size_t max_clients, unsigned flags, uint64_t *handle_out) {
     if (!handle_out || d == 0 || max_clients == 0 || (record_len != 64 && record_len != 96)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (flags & ~(unsigned)ROFL_ROUND_COMPRESSED) return fail(ROFL_BAD_PARAM, "unknown round flag");
+    if ((flags & ROFL_ROUND_COMPRESSED) && (record_len != 64 || d >= 900000))      // (the label table of the reference's transcript ends there, as in rofl_verify_compressed_randproof)
+        return fail(ROFL_BAD_PARAM, "a compressed round holds 64-byte records of d < 900000");
     const size_t npts = record_len / 32;
     size_t bytes;      // the larger array: max_clients * 2 npts * d decoded points
     if (__builtin_mul_overflow(max_clients, d, &bytes) || __builtin_mul_overflow(bytes, 2 * npts * sizeof(niels), &bytes)) return fail(ROFL_BAD_PARAM, "round too large");
     if (max_clients > kMaxBatchMembers || max_clients * 2 * npts * d >= ((size_t)1 << 31)) return fail(ROFL_BAD_PARAM, "round too large (split it)");      // what the Sigma leg's kernels index
     auto R = std::make_shared<Round>();
-    R->d = d; R->rec_len = record_len; R->npts = npts; R->max_clients = max_clients; R->device = current_device();
+    R->d = d; R->rec_len = record_len; R->npts = npts; R->max_clients = max_clients; R->flags = flags; R->device = current_device();
     DeviceBinding bind(R->device);
     int rc = guarded([&]() -> int {
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
         C.init();
         R->bad.assign(3 * max_clients, ~0u);
+        if (flags & ROFL_ROUND_COMPRESSED) R->prefix.reserve(max_clients);
         HIPCHK(hipMalloc(&R->rec, max_clients * d * record_len));
         HIPCHK(hipMalloc(&R->pts, max_clients * 2 * npts * d * sizeof(niels)));
         HIPCHK(hipMalloc(&R->d_bad, 12 * max_clients));
@@ -2177,6 +2298,18 @@ int rofl_round_verify_range(uint64_t h, const uint8_t *const *proofs, size_t pro
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
         return verify_impl(C, R->n, proofs, proof_len, n_proofs, nullptr, k_checked, prove_range, fp_bits, fp_frac, verifier_seed, ok_out, false, nullptr, 32, 0, 0, &rs); });
 }
+int rofl_round_verify_compressed(uint64_t h, const uint8_t *const *proofs, int *ok_out) {
+    if (!ok_out || !proofs) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::shared_ptr<Round> R = round_find(h);
+    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    if (!(R->flags & ROFL_ROUND_COMPRESSED)) return fail(ROFL_BAD_PARAM, "the round was not created with ROFL_ROUND_COMPRESSED");
+    std::shared_lock<std::shared_mutex> lk(R->rw);
+    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
+    if (R->n == 0) return ROFL_OK;
+    std::lock_guard<std::mutex> leg(R->comp_mu);
+    DeviceBinding bind(R->device);
+    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); return round_verify_compressed_impl(*lane_lock.c, *R, proofs, ok_out); });
+}
 int rofl_round_accumulate(uint64_t h, uint64_t acc, const int *accept) {
     std::shared_ptr<Round> R = round_find(h);
     if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
@@ -2198,6 +2331,7 @@ int rofl_round_reset(uint64_t h) {
     std::unique_lock<std::shared_mutex> lk(R->rw);
     if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
     R->n = 0;
+    R->prefix.clear();
     return ROFL_OK;
 }
 int rofl_round_destroy(uint64_t h) {

@@ -756,8 +756,10 @@ class DeviceRound:
     accumulated through acc.accumulate_batch (zip truncation included), as are members whose proofs are off the round's majority shape.
     The records are a snapshot: enc_values are copied to the device at ingest() and never read again, while the proofs are read from the
     update objects at verify() -- an update changed in place after it was ingested must be ingested again (reset()).
-    EncParamsRangeCompressed keeps its randomness leg on rofl_verify_compressed_randproof_batch (host bytes); its range leg and the
-    accumulation come from the round.  The round lives on the device of the thread that created it."""
+    A round of EncParamsRangeCompressed also hashes, at ingest, each update's CompressedRandProof transcript up to the proof's C' from the
+    bytes that go to the device (rofl_round_create_ex, ROFL_ROUND_COMPRESSED): its randomness leg continues those transcripts over the
+    decoded points (rofl_round_verify_compressed) and, like every other leg, gives its verdict about the snapshot that accumulate_into
+    adds.  The round lives on the device of the thread that created it."""
 
     def __init__(self, cls, size, max_clients):
         if cls not in (EncParamsRange, EncParamsRangeCompressed, EncParamsL2, EncParamsL2Compressed):
@@ -766,7 +768,9 @@ class DeviceRound:
         self.record_len = 96 if issubclass(cls, EncParamsL2) else 64
         self.updates, self._slot, self._n_cached = [], [], 0
         self._open = False
-        self._h = api.device_round.create(self.size, self.record_len, self.max_clients)
+        # (d >= 900 000 is past what a CompressedRandProof can have: such a round keeps the host call, which refuses it member by member)
+        self._compressed = cls is EncParamsRangeCompressed and self.size < 900000
+        self._h = api.device_round.create(self.size, self.record_len, self.max_clients, api.device_round.COMPRESSED if self._compressed else 0)
         self._open = True
 
     def __len__(self):
@@ -817,8 +821,11 @@ class DeviceRound:
         return p
 
     def rand(self, cls, us, idx):
-        if cls is EncParamsRangeCompressed or not self._on_round(idx):
+        if not self._on_round(idx) or (cls is EncParamsRangeCompressed and not self._compressed):
             return _HostLegs.rand(cls, us, idx)
+        if cls is EncParamsRangeCompressed:
+            ok = api.device_round.verify_compressed(self._h, self._ptrs(us, idx, lambda u: u.rand_proof))
+            return [ok[self._slot[i]] for i in idx]
         ok, _ = api.device_round.verify_sigma(self._h, 0, self._ptrs(us, idx, lambda u: u.rand_proofs))
         return [ok[self._slot[i]] for i in idx]
 

@@ -12,10 +12,12 @@ round verifies AND extracts.  rofl_set_option("verify_batch", 2).
 Shapes:
   range_cfg4  EncParamsRange, d = 55 000, fp 32/7, range 32, n_partition 4, check_percentage 1.0 (BASELINE cfg 4)
   l2_cfg5     EncParamsL2, d = 55 000, fp 32/7, 8-bit L-inf legs, 32-bit sum proof, n_partition 4 (BASELINE cfg 5)
+  range_compressed_e2e  EncParamsRangeCompressed, d = 40 000, fp 16/7, range 8, n_partition 64, check_percentage 0.013 (the shape of the
+              reference's end-to-end experiments; --check 1.0 for every element range-checked).  Not among the default shapes.
 Way (a) uses nothing that the commit before the device-resident round lacks: the same file with --ways a runs on a checkout of that commit
 (same box, same job) and gives the figure (b) is compared with.
 
-  python scripts/gpu_round_session.py [--clients 48] [--reps 5] [--shapes range_cfg4,l2_cfg5] [--ways a,b] [--warmup 1]
+  python scripts/gpu_round_session.py [--clients 48] [--reps 5] [--shapes range_cfg4,l2_cfg5] [--ways a,b] [--warmup 1] [--check P]
                                       [--out profiles/r08_round_session.json] [--rounds DIR]"""
 import argparse
 import json
@@ -32,6 +34,7 @@ import rofl_project_code_amd as R  # noqa: E402
 SHAPES = {
     "range_cfg4": dict(cls="EncParamsRange", d=55000, fp=(32, 7), nb=32, P=4, check=1.0),
     "l2_cfg5": dict(cls="EncParamsL2", d=55000, fp=(32, 7), nb=8, P=4, l2n=32),
+    "range_compressed_e2e": dict(cls="EncParamsRangeCompressed", d=40000, fp=(16, 7), nb=8, P=64, check=0.013),
 }
 SEED = b"\x5e" * 32
 
@@ -70,7 +73,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clients", type=int, default=48)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--shapes", default="range_cfg4,l2_cfg5")
+    ap.add_argument("--check", type=float, default=None, help="check_percentage of the Range shapes instead of the shape's own")
     ap.add_argument("--ways", default="a,b")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_round_session.json"), help="'' = print only")
@@ -82,7 +86,10 @@ def main():
     decodes = getattr(R.api, "point_decodes", None)
     res = {"clients": a.clients, "reps": a.reps, "ways": ways, "verify_batch_option": 2, "host_clock": "perf_counter around each way", "shapes": {}}
     for name in a.shapes.split(","):
-        sh = SHAPES[name]
+        sh = dict(SHAPES[name])
+        if a.check is not None and "check" in sh:
+            sh["check"] = a.check
+            name = "%s_check%g" % (name, a.check)
         cls, d, fp = getattr(R, sh["cls"]), sh["d"], sh["fp"]
         R.api.set_fp(*fp)
         t = time.perf_counter()

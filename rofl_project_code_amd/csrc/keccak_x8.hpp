@@ -164,7 +164,7 @@ ROFL_K8 void append32_run_x8(Merlin *const t[8], int lanes, char label, const ui
     r.store(t);
 }
 // count x Merlin::append_lbl({3i, 3i + 1, 3i + 2}, msg[l] + 64 j, 64), i = i0 + j, for up to eight transcripts in the same position
-// (the d ElGamal pairs of a CompressedRandProof transcript, compressed_challenges in rofl_zk.hip).
+// (the d ElGamal pairs of a CompressedRandProof transcript, compressed_prefixes in rofl_zk.hip).
 ROFL_K8 void append_lbl3_run_x8(Merlin *const t[8], int lanes, size_t i0, const uint8_t *const msg[8], size_t count) {
     Run8 r; r.load(t, lanes);
     const uint8_t *m[8]; for (int l = 0; l < 8; l++) m[l] = msg[l < lanes ? l : 0];

@@ -2656,27 +2656,9 @@ __global__ void __launch_bounds__(TPB) k_cpow_dot(u32 d, const float *vals, u32 
     if (threadIdx.x == 0) { store_sc(&out[blockIdx.x * 2], v[0]); store_sc(&out[blockIdx.x * 2 + 1], v[1]); }
 }
 #endif
-#if ROFL_KG(3)
-__global__ void __launch_bounds__(TPB) k_cpow_scalars(u32 d, CPow cp, sc *out_canon) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d) return;
-    store_sc(&out_canon[i], sc_from_mont(sc_pow_tab(cp.sq, i + 1)));
-}
-#endif
-// de-interleave and decode d ElGamal pairs into two niels arrays
-#if ROFL_KG(3)
-__global__ void __launch_bounds__(TPB) k_decode_pairs(u32 d, const uint8_t *pairs, niels *Ls, niels *Rs, u32 *status) {
-    u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 2 * d) return;
-    u32 i = t >> 1, which = t & 1;
-    gd p;
-    if (!gd_ristretto_decode(p, pairs + (size_t)64 * i + 32 * which)) { atomicOr(status, 4u); p = gd_identity(); }
-    store_niels(which ? &Rs[i] : &Ls[i], gd_to_niels(p));
-}
-#endif
-// The same for a group of clients (blockIdx.y = client y, its pairs at pairs + 64 (y d + i)): L of client y at pts[2y d + i], R at
-// pts[(2y + 1) d + i] -- the two problems of the client's MSM.  An undecodable point sets bit 4 of ITS client's status word (one bad client
-// must not sink the round) and is stored as the identity.
+// de-interleave and decode the d ElGamal pairs of each client of a group (blockIdx.y = client y, its pairs at pairs + 64 (y d + i)) into
+// two niels arrays: L of client y at pts[2y d + i], R at pts[(2y + 1) d + i] -- the two problems of the client's MSM.  An undecodable point
+// sets bit 4 of ITS client's status word (one bad client must not sink the round) and is stored as the identity.
 #if ROFL_KG(3)
 __global__ void __launch_bounds__(TPB) k_decode_pairs_batch(u32 d, const uint8_t *pairs, niels *pts, u32 *status /* [gridDim.y] */) {
     const size_t y = blockIdx.y;
@@ -2688,13 +2670,25 @@ __global__ void __launch_bounds__(TPB) k_decode_pairs_batch(u32 d, const uint8_t
     store_niels(&pts[(2 * y + which) * d + i], gd_to_niels(p));
 }
 #endif
-// c_y^(i + 1) (canonical) of client y = blockIdx.y, i < d, from its table sq[y * MAX_LG + b] = c_y^(2^b) (Montgomery) in device memory
+// The scalars of the CompressedRandProof equations for a group of clients: row y = blockIdx.y has its table sq[y * MAX_LG + b] = c_y^(2^b)
+// (Montgomery) in device memory and gets out_canon[y * d + i] = c_y^(i + 1) (canonical), i < d -- the scalar array of the client's two MSM
+// problems.  A thread takes kCpowRun consecutive exponents: one walk of the table for the first (popcount(i + 1) multiplications), one
+// multiplication by c for each of the others; its stores are one 128-byte line.
+constexpr u32 kCpowRun = 4;
 #if ROFL_KG(3)
-__global__ void __launch_bounds__(TPB) k_cpow_scalars_batch(u32 d, const sc *sq, sc *out_canon) {
+__global__ void __launch_bounds__(TPB) k_cpow_rows(u32 d, const sc *sq, sc *out_canon) {
     const size_t y = blockIdx.y;
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d) return;
-    store_sc(&out_canon[y * d + i], sc_from_mont(sc_pow_tab(sq + y * MAX_LG, i + 1)));
+    const size_t i0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kCpowRun;
+    if (i0 >= d) return;
+    const sc *tab = sq + y * MAX_LG;
+    const sc c = load_sc(&tab[0]);
+    sc p = sc_pow_tab(tab, (u32)i0 + 1);
+    sc *o = out_canon + y * d + i0;
+    const u32 cnt = (u32)(d - i0 < kCpowRun ? d - i0 : kCpowRun);
+    for (u32 k = 0; k < cnt; k++) {
+        store_sc(&o[k], sc_from_mont(p));
+        if (k + 1 < cnt) p = sc_montmul(p, c);
+    }
 }
 #endif
 
@@ -2833,28 +2827,6 @@ __global__ void __launch_bounds__(TPB) k_round_sum(u32 tn, u32 j0, u32 S, u32 na
     for (u32 q = s; q < na; q += S)
         acc = gd_madd(acc, load_nd(&pts[((size_t)idx[q] * nslots + 2 * which) * d + j0 + j]), false);
     store_gd(&part[((size_t)s * tn + j) * 2 + which], acc);
-}
-#endif
-// The scalars of the compressed randomness leg for a selection of the round's clients: y = blockIdx.y is the y-th selected client, sel[y]
-// its index in the round, sq[sel[y] * MAX_LG + b] = c^(2^b) (Montgomery) its table -- the tables lie by client as the cache does (one upload
-// per call, whatever the groups), out_canon[y * d + i] = c^(i + 1) is packed by selection (the scalar array of the client's two MSM
-// problems).  A thread takes kRoundCpowRun consecutive exponents: one walk of the table for the first (popcount(i + 1) multiplications,
-// what k_cpow_scalars_batch spends on every element), one multiplication by c for each of the others; its stores are one 128-byte line.
-constexpr u32 kRoundCpowRun = 4;
-#if ROFL_KG(3)
-__global__ void __launch_bounds__(TPB) k_round_cpow_scalars(u32 d, const sc *sq, const u32 *sel, sc *out_canon) {
-    const size_t y = blockIdx.y;
-    const size_t i0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kRoundCpowRun;
-    if (i0 >= d) return;
-    const sc *tab = sq + (size_t)sel[y] * MAX_LG;
-    const sc c = load_sc(&tab[0]);
-    sc p = sc_pow_tab(tab, (u32)i0 + 1);
-    sc *o = out_canon + y * d + i0;
-    const u32 cnt = (u32)(d - i0 < kRoundCpowRun ? d - i0 : kRoundCpowRun);
-    for (u32 k = 0; k < cnt; k++) {
-        store_sc(&o[k], sc_from_mont(p));
-        if (k + 1 < cnt) p = sc_montmul(p, c);
-    }
 }
 #endif
 

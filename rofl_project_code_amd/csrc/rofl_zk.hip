@@ -603,16 +603,19 @@ bool verify_splittable(size_t d, size_t n_proofs) { if (!d || n_proofs < 2) retu
 // An accumulator is a resident d x 2 array of extended points on the device of the thread that created it, named by a handle from this
 // registry (never a pointer: an unknown or destroyed handle is a bad parameter, not a crash).  Calls on one accumulator are serialised by
 // its lock; calls on different accumulators take different lanes of their device.
+template <class T> struct Registry {
+    std::mutex mu; std::map<uint64_t, std::shared_ptr<T>> m; uint64_t next = 1;
+    std::shared_ptr<T> find(uint64_t h) { std::lock_guard<std::mutex> lk(mu); auto it = m.find(h); return it == m.end() ? nullptr : it->second; }
+    uint64_t add(std::shared_ptr<T> p) { std::lock_guard<std::mutex> lk(mu); m.emplace(next, std::move(p)); return next++; }
+    void erase(uint64_t h) { std::lock_guard<std::mutex> lk(mu); m.erase(h); }
+};
 struct Acc {
     int device = 0, init = 0; size_t d = 0;
     ge *sum = nullptr;      // [d][2]: L, R of every pair
     ge *work = nullptr;     // a copy of sum for an add that takes several passes (all or nothing: committed by the last fold); allocated on first use
     std::mutex mu; bool dead = false, released = false;      // dead: being or been destroyed (every call but destroy refuses it); released: memory freed
 };
-std::mutex g_acc_mu;
-std::map<uint64_t, std::shared_ptr<Acc>> g_accs;
-uint64_t g_acc_next = 1;
-std::shared_ptr<Acc> acc_find(uint64_t h) { std::lock_guard<std::mutex> lk(g_acc_mu); auto it = g_accs.find(h); return it == g_accs.end() ? nullptr : it->second; }
+Registry<Acc> g_accs;
 // the initial state of every pair and the R of the unity check: init 0 the identity, init 1 ElGamalPair::unity() = (B, B) (el_gamal.rs:83-88)
 ge acc_init_point(int init) {
     if (!init) return ge_identity();
@@ -622,6 +625,18 @@ ge acc_init_point(int init) {
 }
 void acc_reset_launch(Ctx &C, Acc &A) {
     ROFL_LAUNCH(k_acc_fold, grid1(2 * A.d), dim3(TPB), 0, C.stream, (u32)(2 * A.d), 0u, (const ge *)nullptr, (const ge *)nullptr, acc_init_point(A.init), A.sum, (const u32 *)nullptr);
+}
+// An addition that takes several passes is all or nothing: its passes fold into a copy of the sum (acc_work_begin returns where they fold:
+// the copy, or the sum itself for a single pass), and one last fold makes the copy the sum (acc_work_commit) -- unless bit 4 of the device
+// word *status says that a decode of the call failed (nullptr: unconditionally).
+ge *acc_work_begin(Ctx &C, Acc &A, bool multi) {
+    if (!multi) return A.sum;
+    if (!A.work) HIPCHK(hipMalloc(&A.work, sizeof(ge) * 2 * A.d));
+    HIPCHK(hipMemcpyAsync(A.work, A.sum, sizeof(ge) * 2 * A.d, hipMemcpyDeviceToDevice, C.stream));
+    return A.work;
+}
+void acc_work_commit(Ctx &C, Acc &A, const u32 *status) {
+    ROFL_LAUNCH(k_acc_fold, grid1(2 * A.d), dim3(TPB), 0, C.stream, (u32)(2 * A.d), 0u, (const ge *)nullptr, (const ge *)A.work, acc_init_point(A.init), A.sum, status);
 }
 // Points are taken in tiles of kAccTile; the clients of a tile in groups of at most kAccGroupRecords records (the device copy of a group's
 // records and the S x tile partials are the only scratch, whatever the round's size).  Per group: the records are packed into 64-byte
@@ -645,12 +660,7 @@ int acc_add_impl(Ctx &C, Acc &A, const std::vector<size_t> &cl, const std::vecto
     u64 *d_off = C.tmp_in2.as<u64>(cl.size()); u32 *d_cnt = C.tmp_out.as<u32>(cl.size());
     u32 *status = C.status.as<u32>(4);
     HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
-    ge *tgt = A.sum;
-    if (multi) {
-        if (!A.work) HIPCHK(hipMalloc(&A.work, sizeof(ge) * 2 * d));
-        HIPCHK(hipMemcpyAsync(A.work, A.sum, sizeof(ge) * 2 * d, hipMemcpyDeviceToDevice, C.stream));
-        tgt = A.work;
-    }
+    ge *tgt = acc_work_begin(C, A, multi);
     // (host work per call is O(clients): one pointer query per client here and, per group, one strided copy per device-resident client --
     //  ~1-2 us each, nothing at a round's 48 clients, about a second per add of 10^6 single-record clients)
     std::vector<char> on_dev(cl.size());
@@ -704,8 +714,7 @@ int acc_add_impl(Ctx &C, Acc &A, const std::vector<size_t> &cl, const std::vecto
             ROFL_LAUNCH(k_acc_fold, grid1(2 * tn), dim3(TPB), 0, C.stream, (u32)(2 * tn), (u32)S, (const ge *)part, (const ge *)(tgt + 2 * j0), init, tgt + 2 * j0, (const u32 *)status);
         }
     }
-    if (multi)      // commit: sum <- work, unless a decode of the call failed
-        ROFL_LAUNCH(k_acc_fold, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)(2 * d), 0u, (const ge *)nullptr, (const ge *)A.work, init, A.sum, (const u32 *)status);
+    if (multi) acc_work_commit(C, A, status);      // sum <- work, unless a decode of the call failed (the kernel reads the status word)
     u32 st = 0;
     HIPCHK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, C.stream));
     C.sync();
@@ -729,14 +738,12 @@ struct Round {
     bool dead = false, released = false;
     RoundSrc src() const { return RoundSrc{d, npts, rec, pts, bad.data()}; }
 };
-std::mutex g_round_mu;
-std::map<uint64_t, std::shared_ptr<Round>> g_rounds;
-uint64_t g_round_next = 1;
-std::shared_ptr<Round> round_find(uint64_t h) { std::lock_guard<std::mutex> lk(g_round_mu); auto it = g_rounds.find(h); return it == g_rounds.end() ? nullptr : it->second; }
+Registry<Round> g_rounds;
 
-// The Merlin states of nc CompressedRandProof transcripts after their d labelled pairs (compressed_challenge up to, not including, C'), on
-// the lane's host pool: eight transcripts per AVX-512 stream, the scalar transcript for groups of fewer than five and CPUs without AVX-512
-// (the split compressed_challenges makes).  pairs[j]: d x 64 bytes in host memory.
+// The Merlin states of nc CompressedRandProof transcripts after their d labelled pairs (everything they absorb before C'), on the lane's
+// host pool.  Having absorbed messages of the same lengths, the transcripts' STROBE bookkeeping is identical at every step: eight of them
+// share one AVX-512 instruction stream (keccak_x8.hpp); groups of fewer than five, and CPUs without AVX-512, keep the scalar transcript, one
+// client per task.  pairs[j]: d x 64 bytes in host memory.
 void compressed_prefixes(Ctx &C, size_t nc, const uint8_t *const *pairs, size_t d, Merlin *out) {
     static const bool x8_on = k8::available();
     const Merlin start = [] { Merlin t("CompressedRandProof", 19); t.append("dom-sep", (const uint8_t *)"randomness proof v1", 19); return t; }();
@@ -749,14 +756,22 @@ void compressed_prefixes(Ctx &C, size_t nc, const uint8_t *const *pairs, size_t 
     C.pool->run(tasks.size(), [&](size_t k) {
         const size_t j0 = tasks[k].first, cnt = tasks[k].second;
         for (size_t l = 0; l < cnt; l++) out[j0 + l] = start;
-        if (cnt == 1) {
+        if (cnt == 1) {      // label = UNIQUE_U8_TRIPLETS[i] (generate_unique_u8_triplets.py:8-13)
             for (size_t i = 0; i < d; i++) { uint8_t lbl[3] = {(uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2)}; out[j0].append_lbl(lbl, 3, pairs[j0] + 64 * i, 64); }
             return;
         }
         Merlin *tp[8]; const uint8_t *msg[8];
         for (size_t l = 0; l < cnt; l++) { tp[l] = &out[j0 + l]; msg[l] = pairs[j0 + l]; }
-        k8::append_lbl3_run_x8(tp, (int)cnt, 0, msg, d);
+        if (d) k8::append_lbl3_run_x8(tp, (int)cnt, 0, msg, d);
     });
+}
+// the challenge c of a transcript that stands after its pairs: C' absorbed, c drawn (the state is a copy: a round keeps its prefixes)
+sc compressed_challenge(Merlin t, const uint8_t cprime[64]) { t.append("C_prime_eg", cprime, 64); return t.challenge_scalar("c"); }
+// the challenges of nc proofs over host pairs
+void compressed_challenges(Ctx &C, size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, sc *out) {
+    std::vector<Merlin> t(nc, Merlin("CompressedRandProof", 19));
+    compressed_prefixes(C, nc, pairs, d, t.data());
+    for (size_t j = 0; j < nc; j++) out[j] = compressed_challenge(t[j], proofs[j]);
 }
 // clients [R.n, R.n + n): the records go up in groups of ~64 MB through two pinned staging buffers (the pool copies group g + 1 while group g
 // is on its way and being decoded; device-resident records are copied on the device), one k_round_ingest per group: every point decoded once.
@@ -832,13 +847,8 @@ int round_accumulate_impl(Ctx &C, Round &R, Acc &A, const std::vector<u32> &cl) 
     u32 *h_idx = (u32 *)C.stg.alloc(na * 4); memcpy(h_idx, cl.data(), na * 4);
     HIPCHK(hipMemcpyAsync(d_idx, h_idx, na * 4, hipMemcpyHostToDevice, C.stream));
     const ge init = acc_init_point(A.init);
-    ge *tgt = A.sum;
     const bool multi = d > tile;      // several tiles: into a copy of the sum that a last fold commits, as acc_add_impl (a runtime error on the way leaves the sum as it was)
-    if (multi) {
-        if (!A.work) HIPCHK(hipMalloc(&A.work, sizeof(ge) * 2 * d));
-        HIPCHK(hipMemcpyAsync(A.work, A.sum, sizeof(ge) * 2 * d, hipMemcpyDeviceToDevice, C.stream));
-        tgt = A.work;
-    }
+    ge *tgt = acc_work_begin(C, A, multi);
     for (size_t j0 = 0; j0 < d; j0 += tile) {
         const size_t tn = std::min(tile, d - j0);
         ROFL_LAUNCH(k_round_sum, grid1(2 * tn * S), dim3(TPB), 0, C.stream, (u32)tn, (u32)j0, (u32)S, (u32)na, (const u32 *)d_idx, (const niels *)R.pts, (u32)d, (u32)(2 * R.npts), part);
@@ -846,11 +856,47 @@ int round_accumulate_impl(Ctx &C, Round &R, Acc &A, const std::vector<u32> &cl) 
     }
     if (multi) {
         C.sync();      // every tile is in the copy: only now does the sum change
-        ROFL_LAUNCH(k_acc_fold, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)(2 * d), 0u, (const ge *)nullptr, (const ge *)A.work, init, A.sum, (const u32 *)nullptr);
+        acc_work_commit(C, A, nullptr);
     }
     C.sync();
     return ROFL_OK;
 }
+// What every rofl_acc_* / rofl_round_* entry does before its own work, f(object), which runs bound to the object's device with the object
+// locked (Lock on its mutex; then `leg`, if any) and alive: the handle is looked up, pre(object) checks the arguments against what create
+// fixed (before the lock, as ever), a handle that is being or has been destroyed is as unknown as one that never was.
+template <class Lock, class T, class M, class Pre, class F>
+int with_handle(Registry<T> &reg, uint64_t h, M T::*mu, const char *unknown, std::mutex T::*leg, Pre pre, F f) {
+    std::shared_ptr<T> p = reg.find(h);
+    if (!p) return fail(ROFL_BAD_PARAM, unknown);
+    if (int rc = pre(*p)) return rc;
+    Lock lk((*p).*mu);
+    if (p->dead) return fail(ROFL_BAD_PARAM, unknown);
+    std::unique_lock<std::mutex> leg_lk;
+    if (leg) leg_lk = std::unique_lock<std::mutex>((*p).*leg);
+    DeviceBinding bind(p->device);
+    return guarded([&]() -> int { return f(*p); });
+}
+constexpr const char *kNoAcc = "unknown accumulator handle", *kNoRound = "unknown round handle";
+template <class Pre, class F> int with_acc(uint64_t h, Pre pre, F f) { return with_handle<std::lock_guard<std::mutex>>(g_accs, h, &Acc::mu, kNoAcc, (std::mutex Acc::*)nullptr, pre, f); }
+template <class Lock, class Pre, class F> int with_round(uint64_t h, std::mutex Round::*leg, Pre pre, F f) { return with_handle<Lock>(g_rounds, h, &Round::rw, kNoRound, leg, pre, f); }
+using RoundShared = std::shared_lock<std::shared_mutex>; using RoundExclusive = std::unique_lock<std::shared_mutex>;
+// destroy: the object is marked dead (from here on only a destroy may use the handle), what it holds on the device is freed, and only then
+// does the handle leave the registry -- a free that fails leaves it there for another try, which frees what is left.  `released` is for a
+// destroy that found the handle before it left the registry: it waits for the lock and then sees that another thread was first.
+template <class T, class M, class F> int destroy_handle(Registry<T> &reg, uint64_t h, M T::*mu, const char *unknown, F free_all) {
+    std::shared_ptr<T> p = reg.find(h);
+    if (!p) return fail(ROFL_BAD_PARAM, unknown);
+    std::unique_lock<M> lk((*p).*mu);
+    if (p->released) return fail(ROFL_BAD_PARAM, unknown);
+    p->dead = true;
+    DeviceBinding bind(p->device);
+    if (int rc = guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); free_all(*p); return ROFL_OK; })) return rc;
+    p->released = true;
+    reg.erase(h);
+    return ROFL_OK;
+}
+template <class T> void dev_free(T *&p) { if (p) HIPCHK(hipFree(p)); p = nullptr; }
+const auto no_check = [](auto &) { return ROFL_OK; };
 }  // namespace
 
 // ================================================================ C ABI
@@ -1448,16 +1494,6 @@ int sigma_verify(int kind, const uint8_t *proofs, const uint8_t *commits, size_t
     return sigma_verify_batch(kind, 1, &proofs, &commits, d, ok_out, nullptr, true);
 }
 // ---- compressed_rand_proof
-sc compressed_challenge(const uint8_t *pairs, size_t d, const uint8_t cprime[64]) {
-    Merlin t("CompressedRandProof", 19);
-    t.append("dom-sep", (const uint8_t *)"randomness proof v1", 19);
-    for (size_t i = 0; i < d; i++) {      // label = UNIQUE_U8_TRIPLETS[i] (generate_unique_u8_triplets.py:8-13)
-        uint8_t lbl[3] = {(uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2)};
-        t.append_lbl(lbl, 3, pairs + 64 * i, 64);
-    }
-    t.append("C_prime_eg", cprime, 64);
-    return t.challenge_scalar("c");
-}
 int compressed_create(const float *values, size_t d, const uint8_t *r32, size_t d_r, const uint8_t *existing, unsigned fp_bits, unsigned fp_frac,
                       const rofl_nonce_t *nonce, uint8_t *proof_out, uint8_t *pairs_out) {
     LaneLock lane_lock = acquire_lane(false, true); Ctx &C = *lane_lock.c;
@@ -1495,7 +1531,8 @@ int compressed_create(const float *values, size_t d, const uint8_t *r32, size_t 
     }
     h51::encode(proof_out, h51::gadd(h_fixed_mul(C.ht.B5, nc[0]), h_fixed_mul(C.ht.Bb5, nc[1])));
     h51::encode(proof_out + 32, h_fixed_mul(C.ht.B5, nc[1]));
-    sc c = compressed_challenge(pairs_host, d, proof_out);
+    sc c; const uint8_t *proof = proof_out;
+    compressed_challenges(C, 1, &proof, &pairs_host, d, &c);
     sc zm = nc[0], zr = nc[1];
     if (d) {
         CPow cp; fill_pow2(cp.sq, h_mont(c), MAX_LG);
@@ -1511,153 +1548,116 @@ int compressed_create(const float *values, size_t d, const uint8_t *r32, size_t 
     timing_end(C);
     return ROFL_OK;
 }
-int compressed_verify(const uint8_t *proof, const uint8_t *pairs, size_t d, int *ok_out) {
-    LaneLock lane_lock = acquire_lane(false, true); Ctx &C = *lane_lock.c;
-    *ok_out = 0;
-    ge Lp32, Rp32;
-    if (!ristretto_decode(Lp32, proof) || !ristretto_decode(Rp32, proof + 32) || !sc_is_canonical_bytes(proof + 64) || !sc_is_canonical_bytes(proof + 96))
-        return fail(ROFL_FORMAT_ERROR, "FormatError");
-    if (d >= 900000) return fail(ROFL_BAD_PARAM, "bad parameter");
-    C.init();
-    timing_begin(C);
-    ge5 sumL = h51::identity(), sumR = h51::identity();
-    sc c = compressed_challenge(pairs, d, proof);
-    if (d) {
-        uint8_t *dpairs = C.tmp_in.as<uint8_t>(d * 64);
-        niels *pts = C.aux_pts.as<niels>(2 * d); sc *scal = C.aux_scal.as<sc>(d);
-        u32 *status = C.status.as<u32>(4);
-        HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
-        C.up(dpairs, pairs, 64 * d, C.stream);
-        count_decodes(2 * d);
-        ROFL_LAUNCH(k_decode_pairs, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)d, dpairs, pts, pts + d, status);
-        CPow cp; fill_pow2(cp.sq, h_mont(c), MAX_LG);
-        ROFL_LAUNCH(k_cpow_scalars, grid1(d), dim3(TPB), 0, C.stream, (u32)d, cp, scal);
-        u32 st = 0;
-        HIPCHK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        if (st & 4u) return fail(ROFL_FORMAT_ERROR, "FormatError: invalid ElGamal pair");
-        std::vector<MsmProb> pr = {MsmProb{pts, scal}, MsmProb{pts + d, scal}}; std::vector<ge5> res;
-        msm_run(C, pr, d, res);          // sum_i c^(i+1) L_i and sum_i c^(i+1) R_i share the scalars
-        sumL = res[0]; sumR = res[1];
-    }
-    sc zm = sc_frombytes(proof + 64), zr = sc_frombytes(proof + 96);
+// What every CompressedRandProof verifier does with the proof's 128 bytes: L', R' decoded, Z_m, Z_r canonical (the reference's FormatError
+// otherwise), and, given sumL = sum_i c^(i+1) L_i and sumR = sum_i c^(i+1) R_i, the two exact group equations (params.rs:235-256)
+//   z_m B + z_r B~ - (L' + sumL) == 0  and  z_r B - (R' + sumR) == 0   on the Ristretto coset.
+struct CompProof { ge Lp, Rp; sc zm, zr; bool ok = false; };
+CompProof compressed_parse(const uint8_t *proof) {
+    CompProof q;
+    q.ok = ristretto_decode(q.Lp, proof) && ristretto_decode(q.Rp, proof + 32) && sc_is_canonical_bytes(proof + 64) && sc_is_canonical_bytes(proof + 96);
+    if (q.ok) { q.zm = sc_frombytes(proof + 64); q.zr = sc_frombytes(proof + 96); }
+    return q;
+}
+bool compressed_equations(const Ctx &C, const CompProof &q, const ge5 &sumL, const ge5 &sumR) {
     auto neg5 = [](const ge5 &p) { ge5 r = p; r.X = h51::neg(p.X); r.T = h51::neg(p.T); return r; };
-    ge5 e1 = h51::gadd(h51::gadd(h_fixed_mul(C.ht.B5, zm), h_fixed_mul(C.ht.Bb5, zr)), neg5(h51::gadd(h51::from_ge(Lp32), sumL)));
-    ge5 e2 = h51::gadd(h_fixed_mul(C.ht.B5, zr), neg5(h51::gadd(h51::from_ge(Rp32), sumR)));
-    *ok_out = h51::is_identity_ristretto(e1) && h51::is_identity_ristretto(e2);
-    timing_end(C);
-    return ROFL_OK;
+    ge5 e1 = h51::gadd(h51::gadd(h_fixed_mul(C.ht.B5, q.zm), h_fixed_mul(C.ht.Bb5, q.zr)), neg5(h51::gadd(h51::from_ge(q.Lp), sumL)));
+    ge5 e2 = h51::gadd(h_fixed_mul(C.ht.B5, q.zr), neg5(h51::gadd(h51::from_ge(q.Rp), sumR)));
+    return h51::is_identity_ristretto(e1) && h51::is_identity_ristretto(e2);
 }
-// The challenges c of nc CompressedRandProof transcripts of d pairs each (compressed_challenge) on the lane's host pool.  Having absorbed
-// messages of the same lengths, the transcripts' STROBE bookkeeping is identical at every step: eight of them share one AVX-512 instruction
-// stream (keccak_x8.hpp); groups of fewer than five, and CPUs without AVX-512, keep the scalar transcript, one client per task.
-void compressed_challenges(Ctx &C, size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, sc *out) {
-    static const bool x8_on = k8::available();
-    std::vector<std::pair<size_t, size_t>> tasks;      // (first client, count)
-    for (size_t j0 = 0; j0 < nc; j0 += 8) {
-        const size_t cnt = std::min<size_t>(8, nc - j0);
-        if (x8_on && cnt >= 5) tasks.emplace_back(j0, cnt);
-        else for (size_t l = 0; l < cnt; l++) tasks.emplace_back(j0 + l, 1);
+// The device half of every verifier.  A client is its challenge c and the device addresses of its d decoded L and its d decoded R; the
+// clients go in groups of at most sixteen (one scalar array of sixteen clients, whatever their number): per group the power tables c^(2^b)
+// go up, k_cpow_rows writes c^(i+1), and ONE multi-problem MSM -- two problems per client, naming the client's one scalar array -- gives
+// sumL and sumR.  enqueue(g0), if any, runs before the launches of every group but the first (the group's points may be made then:
+// msm_run has waited for the lane's stream, the previous group's MSM has finished); stage(g0), if any, runs on the host inside the MSM
+// of the group before g0.
+struct CompClient { sc c; const niels *L, *R; };
+constexpr size_t kCompGroup = 16;
+void compressed_sums(Ctx &C, size_t d, const std::vector<CompClient> &cl, std::vector<ge5> &sumL, std::vector<ge5> &sumR,
+                     const std::function<void(size_t)> &enqueue = nullptr, const std::function<void(size_t)> &stage = nullptr) {
+    const size_t ns = cl.size(), G = std::min<size_t>(ns, kCompGroup);
+    sumL.assign(ns, h51::identity()); sumR.assign(ns, h51::identity());
+    if (!ns || !d) return;
+    sc *scal = C.aux_scal.as<sc>(G * d);
+    sc *dtab = C.tmp_out.as<sc>(G * MAX_LG), *htab = C.h_cp.as<sc>(G * MAX_LG);
+    for (size_t g0 = 0; g0 < ns; g0 += G) {
+        const size_t gc = std::min(G, ns - g0);      // (gridDim.y = gc <= 16)
+        if (g0 && enqueue) enqueue(g0);
+        for (size_t j = 0; j < gc; j++) fill_pow2(htab + j * MAX_LG, h_mont(cl[g0 + j].c), MAX_LG);
+        HIPCHK(hipMemcpyAsync(dtab, htab, sizeof(sc) * MAX_LG * gc, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_cpow_rows, grid1((d + kCpowRun - 1) / kCpowRun, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const sc *)dtab, scal);
+        std::vector<MsmProb> pr(2 * gc);
+        for (size_t j = 0; j < gc; j++) { pr[2 * j] = MsmProb{cl[g0 + j].L, scal + j * d}; pr[2 * j + 1] = MsmProb{cl[g0 + j].R, scal + j * d}; }
+        C.tm.t.msm_terms += 2 * gc * d;
+        MsmOpt opt;
+        if (stage && g0 + gc < ns) opt.overlap = [&] { stage(g0 + gc); };
+        std::vector<ge5> res;
+        msm_run(C, pr, d, res, opt);      // (returns after the lane's stream has been waited for: the next group may overwrite the tables and the scalars)
+        for (size_t j = 0; j < gc; j++) { sumL[g0 + j] = res[2 * j]; sumR[g0 + j] = res[2 * j + 1]; }
     }
-    C.pool->run(tasks.size(), [&](size_t k) {
-        const size_t j0 = tasks[k].first, cnt = tasks[k].second;
-        if (cnt == 1) { out[j0] = compressed_challenge(pairs[j0], d, proofs[j0]); return; }
-        std::vector<Merlin> t;
-        t.reserve(cnt);
-        for (size_t l = 0; l < cnt; l++) { t.emplace_back("CompressedRandProof", 19); t[l].append("dom-sep", (const uint8_t *)"randomness proof v1", 19); }
-        Merlin *tp[8]; const uint8_t *msg[8];
-        for (size_t l = 0; l < cnt; l++) { tp[l] = &t[l]; msg[l] = pairs[j0 + l]; }
-        if (d) k8::append_lbl3_run_x8(tp, (int)cnt, 0, msg, d);
-        for (size_t l = 0; l < cnt; l++) { t[l].append("C_prime_eg", proofs[j0 + l], 64); out[j0 + l] = t[l].challenge_scalar("c"); }
-    });
 }
-// compressed_verify for the clients of a round (the server checks every RangeCompressed update, server.rs:656-687, params.rs:235-256): per
-// client the same two exact group equations (no random weights), so ok_out[i] is what compressed_verify gives client i; a member whose proof
-// or pairs do not decode gets 0 and the others go on.  Clients go in groups of at most sixteen (device buffers for sixteen clients, two
-// pinned staging buffers of a group each, whatever the size of the round): a group's pairs are staged on the host pool, uploaded and decoded
-// one thread per point (k_decode_pairs_batch, one status word per client).  The pairs do not depend on the challenges: the first group is
-// enqueued before every client's transcript is hashed on the host pool, so the device decodes while the host hashes.  Then per group
-// k_cpow_scalars_batch and ONE multi-problem MSM -- two problems per client, sum_i c^(i+1) L_i and sum_i c^(i+1) R_i over the client's one
-// scalar array -- while the host stages the next group's pairs.  The final equalities (three fixed-base multiplications per client) run on
-// the host pool.
-int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out) {
+// The server's check of the CompressedRandProofs of a round's clients on host bytes (it checks every RangeCompressed update,
+// server.rs:656-687, params.rs:235-256): ok_out[i] is client i's own two equations (no random weights); a member whose proof or pairs do not
+// decode gets 0 and the others go on -- every member is computed, the bad ones are ignored afterwards.  A group's pairs are staged on the
+// host pool, uploaded and decoded one thread per point (k_decode_pairs_batch, one status word per client) into the device buffers of one
+// group; two pinned staging buffers of a group alternate.  The pairs do not depend on the challenges: the first group is enqueued before
+// the transcripts are hashed on the host pool, so the device decodes while the host hashes; the host stages group g + 1 inside the MSM of
+// group g.  The final equalities (three fixed-base multiplications per client) run on the host pool.
+// single: the one-client call (rofl_verify_compressed_randproof), which reports a malformed member as the reference does -- a FormatError,
+// the proof's before anything else, the pairs' after their decode -- instead of the verdict 0.
+int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out, bool single = false) {
     LaneLock lane_lock = acquire_lane(false, nc == 1); Ctx &C = *lane_lock.c;
     for (size_t i = 0; i < nc; i++) ok_out[i] = 0;
     if (nc == 0) return ROFL_OK;
+    std::vector<CompProof> q(nc);
+    if (single) {
+        q[0] = compressed_parse(proofs[0]);
+        if (!q[0].ok) return fail(ROFL_FORMAT_ERROR, "FormatError");
+        if (d >= 900000) return fail(ROFL_BAD_PARAM, "bad parameter");
+    }
     C.init();
     C.batch_mode = nc > 1;
     timing_begin(C);
-    std::vector<ge5> sumL(nc, h51::identity()), sumR(nc, h51::identity());
-    std::vector<u32> st(nc, 0);
-    if (d) {
-        const size_t G = std::min<size_t>(nc, 16);
-        u32 *status = C.status.as<u32>(nc + 4);
-        HIPCHK(hipMemsetAsync(status, 0, 4 * (nc + 4), C.stream));
-        uint8_t *dpairs = C.tmp_in.as<uint8_t>(G * d * 64);
-        niels *pts = C.aux_pts.as<niels>(2 * G * d);
-        sc *scal = C.aux_scal.as<sc>(G * d);
-        sc *dtab = C.tmp_out.as<sc>(G * MAX_LG), *htab = C.h_cp.as<sc>(G * MAX_LG);
-        // two pinned staging buffers alternate: group g + 2 is staged into group g's buffer while group g + 1 runs, and by then group g's
-        // upload has completed (msm_run waits for the lane's stream after every group)
-        uint8_t *stg_buf[2] = {(uint8_t *)C.stg.alloc(G * d * 64), nc > G ? (uint8_t *)C.stg.alloc(G * d * 64) : nullptr};
-        auto stage = [&](size_t g0) -> const uint8_t * {      // caller memory -> pinned staging, one pool task per client
-            const size_t gc = std::min(G, nc - g0);
-            uint8_t *sp = stg_buf[(g0 / G) & 1];
-            C.pool->run(gc, [&](size_t i) { stage_copy(sp + i * d * 64, pairs[g0 + i], d * 64); });
-            return sp;
-        };
-        auto decode = [&](size_t g0, const uint8_t *sp) {
-            const size_t gc = std::min(G, nc - g0);
-            HIPCHK(hipMemcpyAsync(dpairs, sp, gc * d * 64, hipMemcpyHostToDevice, C.stream));
-            count_decodes(2 * d * gc);
-            ROFL_LAUNCH(k_decode_pairs_batch, grid1(2 * d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const uint8_t *)dpairs, pts, status + g0);
-        };
-        decode(0, stage(0));
-        std::vector<sc> c(nc);
-        compressed_challenges(C, nc, proofs, pairs, d, c.data());      // (the device decodes the first group meanwhile)
-        const uint8_t *next = nullptr;
-        for (size_t g0 = 0; g0 < nc; g0 += G) {
-            const size_t gc = std::min(G, nc - g0);
-            if (g0) decode(g0, next);      // (the previous group's MSM has finished: msm_run waited for it)
-            for (size_t j = 0; j < gc; j++) fill_pow2(htab + j * MAX_LG, h_mont(c[g0 + j]), MAX_LG);
-            HIPCHK(hipMemcpyAsync(dtab, htab, sizeof(sc) * MAX_LG * gc, hipMemcpyHostToDevice, C.stream));
-            ROFL_LAUNCH(k_cpow_scalars_batch, grid1(d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const sc *)dtab, scal);
-            std::vector<MsmProb> pr(2 * gc);
-            for (size_t j = 0; j < gc; j++) { pr[2 * j] = MsmProb{pts + 2 * j * d, scal + j * d}; pr[2 * j + 1] = MsmProb{pts + (2 * j + 1) * d, scal + j * d}; }
-            C.tm.t.msm_terms += 2 * gc * d;
-            MsmOpt opt;
-            if (g0 + gc < nc) opt.overlap = [&] { next = stage(g0 + gc); };
-            std::vector<ge5> res;
-            msm_run(C, pr, d, res, opt);
-            for (size_t j = 0; j < gc; j++) { sumL[g0 + j] = res[2 * j]; sumR[g0 + j] = res[2 * j + 1]; }
-        }
-        u32 *h_st = C.h_misc.as<u32>(nc + 4);
-        HIPCHK(hipMemcpyAsync(h_st, status, 4 * nc, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        for (size_t i = 0; i < nc; i++) st[i] = h_st[i];
-    }
-    auto neg5 = [](const ge5 &p) { ge5 r = p; r.X = h51::neg(p.X); r.T = h51::neg(p.T); return r; };
+    const size_t G = std::min<size_t>(nc, kCompGroup);
+    u32 *status = C.status.as<u32>(nc + 4);
+    HIPCHK(hipMemsetAsync(status, 0, 4 * (nc + 4), C.stream));
+    uint8_t *dpairs = C.tmp_in.as<uint8_t>(G * d * 64);
+    niels *pts = C.aux_pts.as<niels>(2 * G * d);
+    // group g + 2 is staged into group g's buffer while group g + 1 runs, and by then group g's upload has completed
+    uint8_t *stg_buf[2] = {d ? (uint8_t *)C.stg.alloc(G * d * 64) : nullptr, d && nc > G ? (uint8_t *)C.stg.alloc(G * d * 64) : nullptr};
+    auto stage = [&](size_t g0) {      // caller memory -> pinned staging, one pool task per client
+        uint8_t *sp = stg_buf[(g0 / G) & 1];
+        C.pool->run(std::min(G, nc - g0), [&](size_t i) { stage_copy(sp + i * d * 64, pairs[g0 + i], d * 64); });
+    };
+    auto decode = [&](size_t g0) {
+        const size_t gc = std::min(G, nc - g0);
+        HIPCHK(hipMemcpyAsync(dpairs, stg_buf[(g0 / G) & 1], gc * d * 64, hipMemcpyHostToDevice, C.stream));
+        count_decodes(2 * d * gc);
+        ROFL_LAUNCH(k_decode_pairs_batch, grid1(2 * d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const uint8_t *)dpairs, pts, status + g0);
+    };
+    if (d) { stage(0); decode(0); }
+    std::vector<sc> c(nc);
+    compressed_challenges(C, nc, proofs, pairs, d, c.data());      // (the device decodes the first group meanwhile)
+    std::vector<CompClient> cl(nc);
+    for (size_t i = 0; i < nc; i++) cl[i] = CompClient{c[i], pts + 2 * (i % G) * d, pts + (2 * (i % G) + 1) * d};
+    std::vector<ge5> sumL, sumR;
+    compressed_sums(C, d, cl, sumL, sumR, decode, stage);
+    u32 *h_st = C.h_misc.as<u32>(nc + 4);
+    HIPCHK(hipMemcpyAsync(h_st, status, 4 * nc, hipMemcpyDeviceToHost, C.stream));
+    C.sync();
+    if (single && (h_st[0] & 4u)) return fail(ROFL_FORMAT_ERROR, "FormatError: invalid ElGamal pair");
     C.pool->run(nc, [&](size_t i) {
-        const uint8_t *proof = proofs[i];
-        ge Lp32, Rp32;      // the proof's own encodings: compressed_verify's FormatError
-        if ((st[i] & 4u) || !ristretto_decode(Lp32, proof) || !ristretto_decode(Rp32, proof + 32) || !sc_is_canonical_bytes(proof + 64) || !sc_is_canonical_bytes(proof + 96))
-            return;
-        sc zm = sc_frombytes(proof + 64), zr = sc_frombytes(proof + 96);
-        ge5 e1 = h51::gadd(h51::gadd(h_fixed_mul(C.ht.B5, zm), h_fixed_mul(C.ht.Bb5, zr)), neg5(h51::gadd(h51::from_ge(Lp32), sumL[i])));
-        ge5 e2 = h51::gadd(h_fixed_mul(C.ht.B5, zr), neg5(h51::gadd(h51::from_ge(Rp32), sumR[i])));
-        ok_out[i] = h51::is_identity_ristretto(e1) && h51::is_identity_ristretto(e2);
+        if (!single) q[i] = compressed_parse(proofs[i]);      // (the single call has parsed its proof before anything else)
+        ok_out[i] = !(h_st[i] & 4u) && q[i].ok && compressed_equations(C, q[i], sumL[i], sumR[i]);
     });
     timing_end(C);
     return ROFL_OK;
 }
 // compressed_verify_batch for the clients of a ROFL_ROUND_COMPRESSED round, from what ingest left on the device and in the round: nothing is
 // uploaded but the power tables, nothing is decoded and no pair is hashed.  Per client with a proof and without a bad L or R (known since
-// ingest): the stored transcript state is copied, C' appended and c drawn, on the host pool with the decoding of C' and the canonical checks
-// of Z_m, Z_r -- a proof that fails those is out before anything is launched, as is a client left out or with a bad point (verdict 0 either
-// way, as compressed_verify_batch gives them after its MSM).  The others are the selection: their tables go up once, by client;
-// then in groups of at most sixteen (the host-bytes call's group: one scalar array of sixteen clients, whatever the round)
-// k_round_cpow_scalars and ONE multi-problem MSM over slots 0 (L) and 2 (R) of the cache as they lie, two problems per client sharing the
-// client's scalars.  The final equalities run on the host pool.
+// ingest): the proof is parsed and, from a copy of the stored transcript state, c drawn, on the host pool -- a proof that does not parse is
+// out before anything is launched, as is a client left out or with a bad point (verdict 0 either way, as compressed_verify_batch gives them
+// after its MSM).  The others are the selection: compressed_sums over slots 0 (L) and 2 (R) of the cache as they lie.  The final equalities
+// run on the host pool.
 int round_verify_compressed_impl(Ctx &C, Round &R, const uint8_t *const *proofs, int *ok_out) {
     const size_t n = R.n, d = R.d;
     for (size_t i = 0; i < n; i++) ok_out[i] = 0;
@@ -1667,54 +1667,20 @@ int round_verify_compressed_impl(Ctx &C, Round &R, const uint8_t *const *proofs,
     C.init();
     C.batch_mode = n > 1;
     timing_begin(C);
-    struct Item { ge Lp, Rp; sc c; bool ok; };
-    std::vector<Item> it(cand.size());
+    std::vector<CompProof> q(cand.size()); std::vector<sc> c(cand.size());
     C.pool->run(cand.size(), [&](size_t k) {
-        const uint8_t *proof = proofs[cand[k]];
-        Item &q = it[k];      // the proof's own encodings: compressed_verify's FormatError
-        q.ok = ristretto_decode(q.Lp, proof) && ristretto_decode(q.Rp, proof + 32) && sc_is_canonical_bytes(proof + 64) && sc_is_canonical_bytes(proof + 96);
-        if (!q.ok) return;
-        Merlin t = R.prefix[cand[k]];
-        t.append("C_prime_eg", proof, 64);
-        q.c = t.challenge_scalar("c");
+        q[k] = compressed_parse(proofs[cand[k]]);
+        if (q[k].ok) c[k] = compressed_challenge(R.prefix[cand[k]], proofs[cand[k]]);
     });
-    std::vector<u32> sel; std::vector<size_t> item_of;
-    for (size_t k = 0; k < cand.size(); k++) if (it[k].ok) { sel.push_back(cand[k]); item_of.push_back(k); }
-    const size_t ns = sel.size();
-    if (!ns) { timing_end(C); return ROFL_OK; }
-    const size_t G = std::min<size_t>(ns, 16);
-    sc *scal = C.aux_scal.as<sc>(G * d);
-    sc *dtab = C.tmp_out.as<sc>(n * MAX_LG), *htab = C.h_cp.as<sc>(n * MAX_LG);
-    u32 *dsel = C.tmp_in2.as<u32>(ns), *hsel = C.h_misc.as<u32>(ns);
-    // the tables lie by client; only the selected clients' rows are written and read
-    const size_t lo = sel.front(), hi = sel.back() + 1;
-    for (size_t j = 0; j < ns; j++) fill_pow2(htab + (size_t)sel[j] * MAX_LG, h_mont(it[item_of[j]].c), MAX_LG);
-    memcpy(hsel, sel.data(), 4 * ns);
-    HIPCHK(hipMemcpyAsync(dtab + lo * MAX_LG, htab + lo * MAX_LG, sizeof(sc) * MAX_LG * (hi - lo), hipMemcpyHostToDevice, C.stream));
-    HIPCHK(hipMemcpyAsync(dsel, hsel, 4 * ns, hipMemcpyHostToDevice, C.stream));
-    std::vector<ge5> sumL(ns), sumR(ns);
+    std::vector<size_t> sel; std::vector<CompClient> cl;      // sel: the selected among the candidates
     const size_t cstride = 2 * R.npts * d;      // a client's slots in the cache
-    for (size_t g0 = 0; g0 < ns; g0 += G) {
-        const size_t gc = std::min(G, ns - g0);      // (gridDim.y = gc <= 16)
-        ROFL_LAUNCH(k_round_cpow_scalars, grid1((d + kRoundCpowRun - 1) / kRoundCpowRun, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const sc *)dtab, (const u32 *)(dsel + g0), scal);
-        std::vector<MsmProb> pr(2 * gc);
-        for (size_t j = 0; j < gc; j++) {
-            const niels *base = R.pts + (size_t)sel[g0 + j] * cstride;
-            pr[2 * j] = MsmProb{base, scal + j * d}; pr[2 * j + 1] = MsmProb{base + 2 * d, scal + j * d};
-        }
-        C.tm.t.msm_terms += 2 * gc * d;
-        std::vector<ge5> res;
-        msm_run(C, pr, d, res);      // (returns after the lane's stream has been waited for: the next group may overwrite the scalars)
-        for (size_t j = 0; j < gc; j++) { sumL[g0 + j] = res[2 * j]; sumR[g0 + j] = res[2 * j + 1]; }
+    for (size_t k = 0; k < cand.size(); k++) if (q[k].ok) {
+        const niels *base = R.pts + (size_t)cand[k] * cstride;
+        sel.push_back(k); cl.push_back(CompClient{c[k], base, base + 2 * d});
     }
-    auto neg5 = [](const ge5 &p) { ge5 r = p; r.X = h51::neg(p.X); r.T = h51::neg(p.T); return r; };
-    C.pool->run(ns, [&](size_t j) {
-        const uint8_t *proof = proofs[sel[j]]; const Item &q = it[item_of[j]];
-        sc zm = sc_frombytes(proof + 64), zr = sc_frombytes(proof + 96);
-        ge5 e1 = h51::gadd(h51::gadd(h_fixed_mul(C.ht.B5, zm), h_fixed_mul(C.ht.Bb5, zr)), neg5(h51::gadd(h51::from_ge(q.Lp), sumL[j])));
-        ge5 e2 = h51::gadd(h_fixed_mul(C.ht.B5, zr), neg5(h51::gadd(h51::from_ge(q.Rp), sumR[j])));
-        ok_out[sel[j]] = h51::is_identity_ristretto(e1) && h51::is_identity_ristretto(e2);
-    });
+    std::vector<ge5> sumL, sumR;
+    compressed_sums(C, d, cl, sumL, sumR);
+    C.pool->run(sel.size(), [&](size_t j) { ok_out[cand[sel[j]]] = compressed_equations(C, q[sel[j]], sumL[j], sumR[j]); });
     timing_end(C);
     return ROFL_OK;
 }
@@ -1793,7 +1759,7 @@ int rofl_create_compressed_randproof(const float *values, size_t d, const uint8_
     return guarded([&]() -> int { return compressed_create(values, d, r32, d_r, existing32, fp_bits, fp_frac, nonce, proof_out, pairs_out); });
 }
 int rofl_verify_compressed_randproof(const uint8_t proof[128], const uint8_t *pairs, size_t d, int *ok_out) {
-    return guarded([&]() -> int { return compressed_verify(proof, pairs, d, ok_out); });
+    return guarded([&]() -> int { return compressed_verify_batch(1, &proof, &pairs, d, ok_out, true); });
 }
 int rofl_verify_compressed_randproof_batch(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out) {
     // (a fixed cap on the round, half of kMaxBatchMembers as for the other batch entries; the clients themselves run in groups of sixteen)
@@ -2118,45 +2084,35 @@ int rofl_acc_create(size_t d, int init, uint64_t *handle_out) {
         return ROFL_OK;
     });
     if (rc) { if (A->sum) (void)hipFree(A->sum); return rc; }
-    std::lock_guard<std::mutex> lk(g_acc_mu);
-    uint64_t h = g_acc_next++;
-    g_accs.emplace(h, A);
-    *handle_out = h;
+    *handle_out = g_accs.add(A);
     return ROFL_OK;
 }
 int rofl_acc_add(uint64_t h, size_t n_clients, const uint8_t *const *records, const size_t *d_each, size_t stride) {
     if (stride < 64 || (n_clients && !records)) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::shared_ptr<Acc> A = acc_find(h);
-    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    size_t bytes;
-    if (__builtin_mul_overflow(n_clients, A->d, &bytes) || __builtin_mul_overflow(bytes, stride, &bytes)) return fail(ROFL_BAD_PARAM, "batch too large");
     std::vector<size_t> cl, nrec;      // the clients that add anything: zip truncation to the accumulator's length (params.rs:81-90)
-    for (size_t c = 0; c < n_clients; c++) {
-        size_t n = std::min(d_each ? d_each[c] : A->d, A->d);
-        if (!n) continue;
-        if (!records[c]) return fail(ROFL_BAD_PARAM, "bad parameter");
-        cl.push_back(c); nrec.push_back(n);
-    }
-    std::lock_guard<std::mutex> lk(A->mu);
-    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    if (cl.empty()) return ROFL_OK;
-    DeviceBinding bind(A->device);
-    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); return acc_add_impl(*lane_lock.c, *A, cl, nrec, records, stride); });
+    return with_acc(h, [&](Acc &A) -> int {
+        size_t bytes;
+        if (__builtin_mul_overflow(n_clients, A.d, &bytes) || __builtin_mul_overflow(bytes, stride, &bytes)) return fail(ROFL_BAD_PARAM, "batch too large");
+        for (size_t c = 0; c < n_clients; c++) {
+            size_t n = std::min(d_each ? d_each[c] : A.d, A.d);
+            if (!n) continue;
+            if (!records[c]) return fail(ROFL_BAD_PARAM, "bad parameter");
+            cl.push_back(c); nrec.push_back(n);
+        }
+        return ROFL_OK;
+    }, [&](Acc &A) -> int {
+        if (cl.empty()) return ROFL_OK;
+        LaneLock lane_lock = acquire_lane(); return acc_add_impl(*lane_lock.c, A, cl, nrec, records, stride); });
 }
 int rofl_acc_export(uint64_t h, uint8_t *pairs_out) {
     if (!pairs_out) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::shared_ptr<Acc> A = acc_find(h);
-    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    std::lock_guard<std::mutex> lk(A->mu);
-    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    DeviceBinding bind(A->device);
-    return guarded([&]() -> int {
+    return with_acc(h, no_check, [&](Acc &A) -> int {
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
         C.init();
-        const size_t d = A->d;
+        const size_t d = A.d;
         uint8_t *o = C.Cbytes.as<uint8_t>(d * 64);
-        const ge b = acc_init_point(A->init);
-        ROFL_LAUNCH(k_acc_finish, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)d, 1, (const ge *)A->sum, b.X, b.Y, o, (u32 *)nullptr);
+        const ge b = acc_init_point(A.init);
+        ROFL_LAUNCH(k_acc_finish, grid1(2 * d), dim3(TPB), 0, C.stream, (u32)d, 1, (const ge *)A.sum, b.X, b.Y, o, (u32 *)nullptr);
         C.down(pairs_out, o, d * 64, C.stream);
         C.sync();
         return ROFL_OK;
@@ -2165,21 +2121,16 @@ int rofl_acc_export(uint64_t h, uint8_t *pairs_out) {
 int rofl_acc_extract(uint64_t h, size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac, float *out, int *ok_out) {
     if (!out || !ok_out || table_size == 0 || table_size >= (1u << 30) || !(bsgs_bits == 8 || bsgs_bits == 16 || bsgs_bits == 32) || !valid_fp(fp_bits, fp_frac))
         return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::shared_ptr<Acc> A = acc_find(h);
-    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    std::lock_guard<std::mutex> lk(A->mu);
-    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    DeviceBinding bind(A->device);
     std::vector<uint8_t> hv;      // (outlives the lane: its release delivers the staged scalars here)
-    return guarded([&]() -> int {
+    return with_acc(h, no_check, [&](Acc &A) -> int {
         LaneLock lane_lock = acquire_lane(true); Ctx &C = *lane_lock.c;      // the primary lane: the baby-step tables rofl_discrete_log_vec caches
         C.init();
-        const size_t d = A->d;
+        const size_t d = A.d;
         uint8_t *enc = C.tmp_in.as<uint8_t>(d * 32), *dout = C.Cbytes.as<uint8_t>(d * 32);
         u32 *status = C.status.as<u32>(4);
         HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
-        const ge b = acc_init_point(A->init);
-        ROFL_LAUNCH(k_acc_finish, grid1(d), dim3(TPB), 0, C.stream, (u32)d, 0, (const ge *)A->sum, b.X, b.Y, enc, status + 1);
+        const ge b = acc_init_point(A.init);
+        ROFL_LAUNCH(k_acc_finish, grid1(d), dim3(TPB), 0, C.stream, (u32)d, 0, (const ge *)A.sum, b.X, b.Y, enc, status + 1);
         u32 st[2] = {0, 0};
         HIPCHK(hipMemcpyAsync(st, status, 8, hipMemcpyDeviceToHost, C.stream));
         C.sync();
@@ -2197,33 +2148,10 @@ int rofl_acc_extract(uint64_t h, size_t table_size, unsigned bsgs_bits, unsigned
     });
 }
 int rofl_acc_reset(uint64_t h) {
-    std::shared_ptr<Acc> A = acc_find(h);
-    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    std::lock_guard<std::mutex> lk(A->mu);
-    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    DeviceBinding bind(A->device);
-    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c; C.init(); acc_reset_launch(C, *A); C.sync(); return ROFL_OK; });
+    return with_acc(h, no_check, [&](Acc &A) -> int { LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c; C.init(); acc_reset_launch(C, A); C.sync(); return ROFL_OK; });
 }
 int rofl_acc_destroy(uint64_t h) {
-    std::shared_ptr<Acc> A = acc_find(h);
-    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    std::lock_guard<std::mutex> lk(A->mu);
-    if (A->released) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");      // destroyed by another thread meanwhile
-    A->dead = true;      // from here on only a destroy may use the handle (a failed one leaves it in the registry for another try)
-    DeviceBinding bind(A->device);
-    int rc = guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane();
-        if (A->sum) HIPCHK(hipFree(A->sum));
-        A->sum = nullptr;
-        if (A->work) HIPCHK(hipFree(A->work));
-        A->work = nullptr;
-        return ROFL_OK;
-    });
-    if (rc) return rc;      // the handle stays in the registry: a later destroy frees what is left
-    A->released = true;      // a destroy that found the handle before it leaves the registry waits for the lock and then sees this
-    std::lock_guard<std::mutex> g(g_acc_mu);
-    g_accs.erase(h);
-    return ROFL_OK;
+    return destroy_handle(g_accs, h, &Acc::mu, kNoAcc, [](Acc &A) { dev_free(A.sum); dev_free(A.work); });
 }
 // ---- a round resident on the device: ingested once, verified and accumulated from the decoded points; a ROFL_ROUND_COMPRESSED round also
 // ---- hashes its CompressedRandProof transcript prefixes at ingest, and its compressed leg reads nothing but the round ----
@@ -2251,111 +2179,65 @@ int rofl_round_create_ex(size_t d, size_t record_len, size_t max_clients, unsign
         return ROFL_OK;
     });
     if (rc) { if (R->rec) (void)hipFree(R->rec); if (R->pts) (void)hipFree(R->pts); if (R->d_bad) (void)hipFree(R->d_bad); return rc; }
-    std::lock_guard<std::mutex> lk(g_round_mu);
-    uint64_t h = g_round_next++;
-    g_rounds.emplace(h, R);
-    *handle_out = h;
+    *handle_out = g_rounds.add(R);
     return ROFL_OK;
 }
 int rofl_round_ingest(uint64_t h, size_t n_clients, const uint8_t *const *records, size_t *first_index_out) {
     if (n_clients && !records) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::shared_ptr<Round> R = round_find(h);
-    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    for (size_t i = 0; i < n_clients; i++) if (!records[i]) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::unique_lock<std::shared_mutex> lk(R->rw);
-    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    if (n_clients > R->max_clients - R->n) return fail(ROFL_BAD_PARAM, "the round is full (nothing ingested)");
-    if (first_index_out) *first_index_out = R->n;
-    if (!n_clients) return ROFL_OK;
-    DeviceBinding bind(R->device);
-    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); return round_ingest_impl(*lane_lock.c, *R, n_clients, records); });
+    return with_round<RoundExclusive>(h, nullptr, [&](Round &) -> int {
+        for (size_t i = 0; i < n_clients; i++) if (!records[i]) return fail(ROFL_BAD_PARAM, "bad parameter");
+        return ROFL_OK;
+    }, [&](Round &R) -> int {
+        if (n_clients > R.max_clients - R.n) return fail(ROFL_BAD_PARAM, "the round is full (nothing ingested)");
+        if (first_index_out) *first_index_out = R.n;
+        if (!n_clients) return ROFL_OK;
+        LaneLock lane_lock = acquire_lane(); return round_ingest_impl(*lane_lock.c, R, n_clients, records); });
 }
 int rofl_round_verify_sigma(uint64_t h, int kind, const uint8_t *const *proofs, int *ok_out, uint8_t *csq_sum_out32) {
     if (!ok_out || !proofs || kind < 0 || kind > 2) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::shared_ptr<Round> R = round_find(h);
-    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    if ((kind == 0) != (R->rec_len == 64)) return fail(ROFL_BAD_PARAM, "the proof kind does not fit the round's records");
-    std::shared_lock<std::shared_mutex> lk(R->rw);
-    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    std::lock_guard<std::mutex> leg(R->sigma_mu);
-    DeviceBinding bind(R->device);
-    const RoundSrc rs = R->src();
-    return guarded([&]() -> int { return sigma_verify_batch(kind, R->n, proofs, nullptr, R->d, ok_out, csq_sum_out32, false, &rs); });
+    return with_round<RoundShared>(h, &Round::sigma_mu, [&](Round &R) -> int {
+        return (kind == 0) != (R.rec_len == 64) ? fail(ROFL_BAD_PARAM, "the proof kind does not fit the round's records") : ROFL_OK;
+    }, [&](Round &R) -> int {
+        const RoundSrc rs = R.src();
+        return sigma_verify_batch(kind, R.n, proofs, nullptr, R.d, ok_out, csq_sum_out32, false, &rs); });
 }
 int rofl_round_verify_range(uint64_t h, const uint8_t *const *proofs, size_t proof_len, size_t n_proofs, size_t k_checked, size_t prove_range,
                             unsigned fp_bits, unsigned fp_frac, const uint8_t verifier_seed[32], int *ok_out) {
     if (!ok_out || !proofs || !verifier_seed) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::shared_ptr<Round> R = round_find(h);
-    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    if (k_checked == 0 || k_checked > R->d) return fail(ROFL_BAD_PARAM, "k_checked outside the round's records");
-    std::shared_lock<std::shared_mutex> lk(R->rw);
-    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    if (R->n == 0) return ROFL_OK;
-    std::lock_guard<std::mutex> leg(R->range_mu);
-    DeviceBinding bind(R->device);
-    const RoundSrc rs = R->src();
-    return guarded([&]() -> int {
+    return with_round<RoundShared>(h, &Round::range_mu, [&](Round &R) -> int {
+        return k_checked == 0 || k_checked > R.d ? fail(ROFL_BAD_PARAM, "k_checked outside the round's records") : ROFL_OK;
+    }, [&](Round &R) -> int {
+        if (R.n == 0) return ROFL_OK;
+        const RoundSrc rs = R.src();
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        return verify_impl(C, R->n, proofs, proof_len, n_proofs, nullptr, k_checked, prove_range, fp_bits, fp_frac, verifier_seed, ok_out, false, nullptr, 32, 0, 0, &rs); });
+        return verify_impl(C, R.n, proofs, proof_len, n_proofs, nullptr, k_checked, prove_range, fp_bits, fp_frac, verifier_seed, ok_out, false, nullptr, 32, 0, 0, &rs); });
 }
 int rofl_round_verify_compressed(uint64_t h, const uint8_t *const *proofs, int *ok_out) {
     if (!ok_out || !proofs) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::shared_ptr<Round> R = round_find(h);
-    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    if (!(R->flags & ROFL_ROUND_COMPRESSED)) return fail(ROFL_BAD_PARAM, "the round was not created with ROFL_ROUND_COMPRESSED");
-    std::shared_lock<std::shared_mutex> lk(R->rw);
-    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    if (R->n == 0) return ROFL_OK;
-    std::lock_guard<std::mutex> leg(R->comp_mu);
-    DeviceBinding bind(R->device);
-    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); return round_verify_compressed_impl(*lane_lock.c, *R, proofs, ok_out); });
+    return with_round<RoundShared>(h, &Round::comp_mu, [&](Round &R) -> int {
+        return !(R.flags & ROFL_ROUND_COMPRESSED) ? fail(ROFL_BAD_PARAM, "the round was not created with ROFL_ROUND_COMPRESSED") : ROFL_OK;
+    }, [&](Round &R) -> int {
+        if (R.n == 0) return ROFL_OK;
+        LaneLock lane_lock = acquire_lane(); return round_verify_compressed_impl(*lane_lock.c, R, proofs, ok_out); });
 }
 int rofl_round_accumulate(uint64_t h, uint64_t acc, const int *accept) {
-    std::shared_ptr<Round> R = round_find(h);
-    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    std::shared_ptr<Acc> A = acc_find(acc);
-    if (!A) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    std::unique_lock<std::shared_mutex> lk(R->rw);
-    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    std::lock_guard<std::mutex> la(A->mu);
-    if (A->dead) return fail(ROFL_BAD_PARAM, "unknown accumulator handle");
-    if (A->d != R->d || A->device != R->device) return fail(ROFL_BAD_PARAM, "the accumulator does not fit the round (length or device)");
-    std::vector<u32> cl;
-    for (size_t i = 0; i < R->n; i++) if (!accept || accept[i]) cl.push_back((u32)i);
-    DeviceBinding bind(R->device);
-    return guarded([&]() -> int { LaneLock lane_lock = acquire_lane(); return round_accumulate_impl(*lane_lock.c, *R, *A, cl); });
+    std::shared_ptr<Acc> A;
+    return with_round<RoundExclusive>(h, nullptr, [&](Round &) -> int {
+        A = g_accs.find(acc);
+        return A ? ROFL_OK : fail(ROFL_BAD_PARAM, kNoAcc);
+    }, [&](Round &R) -> int {
+        std::lock_guard<std::mutex> la(A->mu);
+        if (A->dead) return fail(ROFL_BAD_PARAM, kNoAcc);
+        if (A->d != R.d || A->device != R.device) return fail(ROFL_BAD_PARAM, "the accumulator does not fit the round (length or device)");
+        std::vector<u32> cl;
+        for (size_t i = 0; i < R.n; i++) if (!accept || accept[i]) cl.push_back((u32)i);
+        LaneLock lane_lock = acquire_lane(); return round_accumulate_impl(*lane_lock.c, R, *A, cl); });
 }
 int rofl_round_reset(uint64_t h) {
-    std::shared_ptr<Round> R = round_find(h);
-    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    std::unique_lock<std::shared_mutex> lk(R->rw);
-    if (R->dead) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    R->n = 0;
-    R->prefix.clear();
-    return ROFL_OK;
+    return with_round<RoundExclusive>(h, nullptr, no_check, [&](Round &R) -> int { R.n = 0; R.prefix.clear(); return ROFL_OK; });
 }
 int rofl_round_destroy(uint64_t h) {
-    std::shared_ptr<Round> R = round_find(h);
-    if (!R) return fail(ROFL_BAD_PARAM, "unknown round handle");
-    std::unique_lock<std::shared_mutex> lk(R->rw);
-    if (R->released) return fail(ROFL_BAD_PARAM, "unknown round handle");      // destroyed by another thread meanwhile
-    R->dead = true;
-    DeviceBinding bind(R->device);
-    int rc = guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane();
-        if (R->rec) HIPCHK(hipFree(R->rec));
-        R->rec = nullptr;
-        if (R->pts) HIPCHK(hipFree(R->pts));
-        R->pts = nullptr;
-        if (R->d_bad) HIPCHK(hipFree(R->d_bad));
-        R->d_bad = nullptr;
-        return ROFL_OK;
-    });
-    if (rc) return rc;      // the handle stays in the registry: a later destroy frees what is left
-    R->released = true;
-    std::lock_guard<std::mutex> g(g_round_mu);
-    g_rounds.erase(h);
-    return ROFL_OK;
+    return destroy_handle(g_rounds, h, &Round::rw, kNoRound, [](Round &R) { dev_free(R.rec); dev_free(R.pts); dev_free(R.d_bad); });
 }
 int rofl_dbg_point_decodes(uint64_t *count_out) { if (!count_out) return ROFL_BAD_PARAM; *count_out = g_point_decodes.load(); return ROFL_OK; }
 size_t rofl_wire_encoded_size(const rofl_wire_msg_t *m) { return m ? wire::encoded_size(*m) : 0; }
@@ -2802,7 +2684,7 @@ int rofl_dbg_host_merlin8_selftest(int lanes, unsigned count, unsigned skew, dou
     if (us_scalar) *us_scalar = (t1 - t0) * 1e3;
     return bad;
 }
-// k8::append_lbl3_run_x8 against `count` Merlin::append_lbl calls per transcript (the labelled pairs of compressed_challenge): `lanes`
+// k8::append_lbl3_run_x8 against `count` Merlin::append_lbl calls per transcript (the labelled pairs of compressed_prefixes): `lanes`
 // CompressedRandProof transcripts, `skew` extra prefix bytes, then the pairs, C' and the challenge.  0 = equal, 1 = mismatch, -1 = no AVX-512.
 int rofl_dbg_host_merlin8_lbl3_selftest(int lanes, unsigned count, unsigned skew, double *us_simd, double *us_scalar) {
     if (!k8::available()) return -1;

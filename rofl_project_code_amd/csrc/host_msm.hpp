@@ -80,9 +80,8 @@ bool msm_plan_job(Ctx &C, MsmJob &J, const MsmOpt &opt, const MsmAllow &al, MsmM
             if (J.P.W % sdiv == 0 && (size_t)nq * (lr ? 2 : 1) * sdiv * J.P.B >= want) { sets = sdiv; break; }      // many problems (n_partition = 64): one set each is plenty
         // ... but the two-level sort needs a coarse bin to fit a block's LDS: with many problems of many terms (a batched call of cfg-4 clients:
         // 48 problems of 2^19 terms a side) one set per problem means 16 windows per array and bins of 131 KB -- the launch fell back to the slot
-        // sort (a 6.4 GB slot array, 3x the sort time).  More sets per problem until the bins fit (ROFL_MSM_FB_FITSETS=0: as before).
-        static const bool fitsets = !(knob("ROFL_MSM_FB_FITSETS") && atoi(knob("ROFL_MSM_FB_FITSETS")) == 0);
-        if (fitsets && al.two && C.msm_two_level && (J.P.B == 32768 || J.P.B == 16384) && per_side >= 8192)
+        // sort (a 6.4 GB slot array, 3x the sort time).  More sets per problem until the bins fit.
+        if (al.two && C.msm_two_level && (J.P.B == 32768 || J.P.B == 16384) && per_side >= 8192)
             while (sets < J.P.W && (size_t)msm_bin_cap(per_side * (J.P.W / sets) / 512) * 4 + 1024 > 96 * 1024) {
                 u32 nx = sets + 1; while (nx < J.P.W && J.P.W % nx) nx++;
                 sets = nx;
@@ -140,8 +139,6 @@ bool msm_plan_job(Ctx &C, MsmJob &J, const MsmOpt &opt, const MsmAllow &al, MsmM
 MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n, const MsmOpt &opt, MsmAllow &al, hipStream_t st = nullptr) {
     if (!st) st = C.stream;
     static const u32 acc_balance = knob("ROFL_ACC_BALANCE") ? (atoi(knob("ROFL_ACC_BALANCE")) ? 1u : 0u) : 1u;   // equal-work blocks in k_msm_accumulate (0 = plain descending order)
-    static const u32 dbg_mask = knob("ROFL_DBG_IDX_MASK") ? (u32)strtoul(knob("ROFL_DBG_IDX_MASK"), nullptr, 0) : 0x7fffffffu;   // timing experiments only (wrong results): gathers confined to a cache-resident prefix
-    static const u32 dbg_scatter = knob("ROFL_DBG_SCATTER") ? (u32)atoi(knob("ROFL_DBG_SCATTER")) : 0u;   // timing experiments only: 1 = no range reservation, 2 = no slot stores
     MsmJob J; J.ws = &W; J.np = probs.size(); J.n = n; J.lr = opt.lr_nh != 0; J.nq = J.lr ? J.np / 2 : J.np;
     const size_t np = J.np, nq = J.nq; const bool lr = J.lr;
     MsmMap mm{}; u32 small_cap = 0; Msm2L tl{};
@@ -224,11 +221,10 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
         u32 *bcur = W.cur.as<u32>(PW * tl.nbins * 2);
         u32 *btail = W.tail.as<u32>(PW * tl.nbins * (size_t)MSM_BIN_TAIL);
         HIPCHK(hipMemsetAsync(bcur, 0, sizeof(u32) * PW * tl.nbins * 2, st));
-        // window-ordered bucket lists + set-major block order of the accumulation (ROFL_MSM_WINDOW_ORDER; r06_experiments.txt item 14): when the index of
-        // an entry says which window slot it belongs to by a shift (stride and sets powers of two) and there is more than one slot per array
-        static const bool worder_on = !(knob("ROFL_MSM_WINDOW_ORDER") && atoi(knob("ROFL_MSM_WINDOW_ORDER")) == 0);
+        // window-ordered bucket lists + set-major block order of the accumulation (r06_experiments.txt item 14): when the index of an entry
+        // says which window slot it belongs to by a shift (stride and sets powers of two) and there is more than one slot per array
         const u64 wdiv = (u64)mm.fb_stride * mm.fb_sets;
-        const bool worder = worder_on && mm.fb_wps > 1 && mm.fb_wps <= 16 && wdiv && (wdiv & (wdiv - 1)) == 0 && wdiv < ((u64)1 << tl.ebits);
+        const bool worder = mm.fb_wps > 1 && mm.fb_wps <= 16 && wdiv && (wdiv & (wdiv - 1)) == 0 && wdiv < ((u64)1 << tl.ebits);
         const u32 worder_wps = worder ? mm.fb_wps : 1u, worder_shift = worder ? (u32)lg2u((size_t)wdiv) : 0u;
         u32 iter_pts = (tl.stage >= 144 ? 16384u : 12288u) / mm.fb_wps; if (iter_pts < 1024) iter_pts = 1024;      // ~ 64 (48) new items per bin and iteration against a row of 144 (72)
         u32 tile = iter_pts;
@@ -237,21 +233,18 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
             // arrays (a batch of clients: PW = 96) the doubling above lands on e.g. 3 tiles x 96 arrays = 288 blocks -- a full pass and a second one for 32
             // blocks: 5.1 ms where 2.6 were due (profiles/r06_cfg4_timeline_inflight1.txt).  Look for a tile (any multiple of an iteration) whose passes
             // x tile length is shorter; the power-of-two choice stays unless another is clearly better (a lone client's 512 blocks are two exact passes).
-            static const bool tile_search = !(knob("ROFL_MSM_BIN_TILE_SEARCH") && atoi(knob("ROFL_MSM_BIN_TILE_SEARCH")) == 0);
             const size_t kCU = 256;
             auto cost = [&](u32 t) { const size_t tiles = (n_side + t - 1) / t; return (double)((tiles * PW + kCU - 1) / kCU) * ((double)std::min<u32>(t, n_side) + 0.25 * iter_pts); };      // (+ a block's fixed part: counters, the flush of its rows)
-            if (tile_search) {
-                u32 best = tile; double best_cost = cost(tile);
-                for (u32 t = iter_pts; t < n_side + iter_pts; t += iter_pts) {
-                    const size_t tiles = (n_side + t - 1) / t;
-                    if (tiles > 48 || tiles * PW > 4096) continue;
-                    const double c = cost(t);
-                    if (c < best_cost * 0.999) { best = t; best_cost = c; }
-                }
-                if (knob("ROFL_TRACE")) fprintf(stderr, "[rofl] bin_l1 tiling: n_side=%u PW=%zu iter=%u: tile %u (%zu blocks, cost %.0f) -> best %u (%zu blocks, cost %.0f)\n", n_side, PW, iter_pts, tile,
-                                                (size_t)((n_side + tile - 1) / tile) * PW, cost(tile), best, (size_t)((n_side + best - 1) / best) * PW, best_cost);
-                if (best_cost < 0.85 * cost(tile)) tile = best;
+            u32 best = tile; double best_cost = cost(tile);
+            for (u32 t = iter_pts; t < n_side + iter_pts; t += iter_pts) {
+                const size_t tiles = (n_side + t - 1) / t;
+                if (tiles > 48 || tiles * PW > 4096) continue;
+                const double c = cost(t);
+                if (c < best_cost * 0.999) { best = t; best_cost = c; }
             }
+            if (knob("ROFL_TRACE")) fprintf(stderr, "[rofl] bin_l1 tiling: n_side=%u PW=%zu iter=%u: tile %u (%zu blocks, cost %.0f) -> best %u (%zu blocks, cost %.0f)\n", n_side, PW, iter_pts, tile,
+                                            (size_t)((n_side + tile - 1) / tile) * PW, cost(tile), best, (size_t)((n_side + best - 1) / best) * PW, best_cost);
+            if (best_cost < 0.85 * cost(tile)) tile = best;
         }
         dim3 grid((n_side + tile - 1) / tile, (u32)PW);
         { KSpan ks(C.tm, st, ROFL_TK_MSM_SCATTER, 0, terms * 32 + terms * P.W * 4);
@@ -261,20 +254,19 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
         ROFL_LAUNCH(k_msm_scan, dim3((unsigned)PW), dim3(P.B >= 1024 ? 1024 : 256), 0, st, P.B, cnt, off, (u32 *)nullptr, perm);
         if (C.tm.enabled) { e0 = C.tm.get(); e1 = C.tm.get(); HIPCHK(hipEventRecord(e0, st)); }
         {
-            HeavyScope heavy(C, st); hipStream_t hst = heavy.run;      // (the debug timeline variant below stays on st)
-            KSpan ks_acc(C.tm, hst, ROFL_TK_MSM_ACCUMULATE_FB, terms * P.W * 7, terms * 32);
+            KSpan ks_acc(C.tm, st, ROFL_TK_MSM_ACCUMULATE_FB, terms * P.W * 7, terms * 32);
             static const char *timeline = knob("ROFL_DBG_ACC_TIMELINE");      // debugging: per-wave start / end / placement of every launch, appended to this file
             if (timeline) {
                 dim3 g = grid1((size_t)Wb * P.B, (u32)nq);
                 size_t waves = (size_t)g.x * g.y * (TPB / 64);
                 unsigned long long *rec; HIPCHK(hipMalloc(&rec, waves * 32)); HIPCHK(hipMemsetAsync(rec, 0, waves * 32, st));
-                ROFL_LAUNCH(k_msm_accumulate_fb_dbg, g, dim3(TPB), 0, st, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, bins, perm, buckets, MSM_LIST_ABS, dbg_mask, acc_balance, rec);
+                ROFL_LAUNCH(k_msm_accumulate_fb_dbg, g, dim3(TPB), 0, st, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, bins, perm, buckets, MSM_LIST_ABS, acc_balance, rec);
                 std::vector<unsigned long long> h(waves * 4);
                 HIPCHK(hipMemcpyAsync(h.data(), rec, waves * 32, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
                 if (FILE *f = fopen(timeline, "ab")) { unsigned long long hdr[4] = {0x54494d45ull, waves, g.x, g.y}; fwrite(hdr, 8, 4, f); fwrite(h.data(), 8, h.size(), f); fclose(f); }
                 HIPCHK(hipFree(rec));
             } else
-            ROFL_LAUNCH(k_msm_accumulate_fb, grid1((size_t)Wb * P.B, (u32)nq), dim3(TPB), 0, hst, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, bins, perm, buckets, MSM_LIST_ABS, dbg_mask,
+            ROFL_LAUNCH(k_msm_accumulate_fb, grid1((size_t)Wb * P.B, (u32)nq), dim3(TPB), 0, st, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, bins, perm, buckets, MSM_LIST_ABS,
                         acc_balance | ((worder && nq > 1 && Wb > 1) ? 2u : 0u));
         }
         if (C.tm.enabled) HIPCHK(hipEventRecord(e1, st));
@@ -293,7 +285,7 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
             dim3 grid((n_side + tile - 1) / tile, (u32)(nq * (lr ? 2 : 1) * per_q));
             uint64_t items = terms * P.W;
             KSpan ks(C.tm, st, ROFL_TK_MSM_SCATTER, 0, terms * 32 + items * 4);
-            ROFL_LAUNCH(k_msm_scatter_lds, grid, dim3(1024), (size_t)P.B * 4, st, n_side, tile, mw, mm, d_probs, cnt, slots, cap, ovf_count, ovf, MSM_OVF_MAX, dbg_scatter);
+            ROFL_LAUNCH(k_msm_scatter_lds, grid, dim3(1024), (size_t)P.B * 4, st, n_side, tile, mw, mm, d_probs, cnt, slots, cap, ovf_count, ovf, MSM_OVF_MAX);
         } else
             ROFL_LAUNCH(k_msm_scatter_slots, grid1(n, (u32)(nq * P.W)), dim3(TPB), 0, st, (u32)n, mw, mm, d_probs, cnt, slots, cap, ovf_count, ovf, MSM_OVF_MAX);
         ROFL_LAUNCH(k_msm_scan, dim3((unsigned)PW), dim3(P.B >= 1024 ? 1024 : 256), 0, st, P.B, cnt, off, (u32 *)nullptr, perm);
@@ -301,11 +293,9 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
         if (C.tm.enabled) { e0 = C.tm.get(); e1 = C.tm.get(); HIPCHK(hipEventRecord(e0, st)); }
         {
             uint64_t acc_adds = terms * P.W;
-            const bool big = acc_adds >= ((uint64_t)1 << 22);      // (a launch of a few hundred microseconds is not worth two events)
-            HeavyScope heavy(C, st, big); hipStream_t hst = heavy.run;
-            KSpan ks_acc(C.tm, hst, fb ? ROFL_TK_MSM_ACCUMULATE_FB : ROFL_TK_MSM_ACCUMULATE_GEN, acc_adds * 7, terms * 32);
-            if (fb) ROFL_LAUNCH(k_msm_accumulate_fb, grid1((size_t)Wb * P.B, (u32)nq), dim3(TPB), 0, hst, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, slots, perm, buckets, cap, dbg_mask, acc_balance);
-            else ROFL_LAUNCH(k_msm_accumulate_gen, grid1((size_t)Wb * P.B, (u32)nq), dim3(TPB), 0, hst, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, slots, perm, buckets, cap, dbg_mask, acc_balance);
+            KSpan ks_acc(C.tm, st, fb ? ROFL_TK_MSM_ACCUMULATE_FB : ROFL_TK_MSM_ACCUMULATE_GEN, acc_adds * 7, terms * 32);
+            if (fb) ROFL_LAUNCH(k_msm_accumulate_fb, grid1((size_t)Wb * P.B, (u32)nq), dim3(TPB), 0, st, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, slots, perm, buckets, cap, acc_balance);
+            else ROFL_LAUNCH(k_msm_accumulate_gen, grid1((size_t)Wb * P.B, (u32)nq), dim3(TPB), 0, st, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, slots, perm, buckets, cap, acc_balance);
         }
         if (C.tm.enabled) HIPCHK(hipEventRecord(e1, st));
         ROFL_LAUNCH(k_msm_overflow, dim3(1), dim3(64), 0, st, Wb, P.B, (u32)(np / nq), d_probs, ovf_count, ovf, MSM_OVF_MAX, buckets, fb ? 1 : 0);
@@ -318,7 +308,7 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
         ROFL_LAUNCH(k_msm_scatter, grid1(n, (u32)(nq * P.W)), dim3(TPB), 0, st, (u32)n, mw, mm, d_probs, cur, sorted);
         if (opt.pts_ready) HIPCHK(hipStreamWaitEvent(st, opt.pts_ready, 0));
         if (C.tm.enabled) { e0 = C.tm.get(); e1 = C.tm.get(); HIPCHK(hipEventRecord(e0, st)); }
-        ROFL_LAUNCH(k_msm_accumulate_gen, grid1((size_t)Wb * P.B, (u32)nq), dim3(TPB), 0, st, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, sorted, perm, buckets, 0u, dbg_mask, acc_balance);
+        ROFL_LAUNCH(k_msm_accumulate_gen, grid1((size_t)Wb * P.B, (u32)nq), dim3(TPB), 0, st, (u32)n, P.c, Wb, (u32)(np / nq), d_probs, cnt, off, sorted, perm, buckets, 0u, acc_balance);
         if (C.tm.enabled) HIPCHK(hipEventRecord(e1, st));
     }
     if (C.tm.enabled) {
@@ -335,35 +325,22 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
     ge *C_fin = J.dev_horner ? W.Cacc[1].as<ge>(PW * (size_t)nb_final) : hres_dev + PW;
     {
         KSpan ks_red(C.tm, st, ROFL_TK_MSM_REDUCE, red_adds * PW * 9, (uint64_t)PW * P.B * 128);
-        if (C.msm_group_reduce && P.B >= 1024) {
-            // every run of 512 buckets reduced by its own block, then one block per array combines the groups (two launches, the
-            // first at full occupancy, instead of a chain of three whose last one ran on PW blocks)
-            u32 G = P.B / 512, gbits = P.c - 1 - 9;
-            ge *GS = W.S[0].as<ge>(PW * G);
-            ge *GC = W.Cacc[0].as<ge>(PW * (size_t)G * 9);
-            size_t lds_a = ((size_t)64 * 4 + (size_t)32 * 5 + 1) * sizeof(ge);
-            ROFL_LAUNCH(k_msm_reduce_fused, dim3((unsigned)(PW * G)), dim3(256), lds_a, st, 512u, 0u, (const ge *)buckets, (const ge *)nullptr, GS, GC, 9u);
-            u32 half = G / 2 ? G / 2 : 1, nout = 10 + gbits;
-            ROFL_LAUNCH(k_msm_reduce_groups, dim3((unsigned)PW), dim3(half, nout), (size_t)nout * half * sizeof(ge), st, G, gbits, (const ge *)GS, (const ge *)GC, S_fin, C_fin, nb_final);
-        } else {
-            while (E > 512) {
-                u32 E8 = E / 8;
-                ge *S_out = W.S[lv & 1].as<ge>(PW * E8);
-                ge *C_out = W.Cacc[lv & 1].as<ge>(PW * (size_t)(nb + 3) * E8);
-                static const int red_split = knob("ROFL_RED_SPLIT") ? atoi(knob("ROFL_RED_SPLIT")) : 0;
-                ROFL_LAUNCH(k_msm_reduce_level, grid1((size_t)E8 * ((red_split ? 4 : 1) + nb), (u32)PW), dim3(TPB), 0, st, E, nb, S_in, C_in, S_out, C_out, red_split);
-                S_in = S_out; C_in = C_out; E = E8; nb += 3; lv++;
-            }
-            if (J.dev_horner) { S_fin = W.S[lv & 1].as<ge>(PW); C_fin = W.Cacc[lv & 1].as<ge>(PW * (size_t)nb_final); }
-            // block size = first-level work items (small bucket arrays, c = 7: 32 items -- a 256-thread block would idle 7 of its 8
-            // waves and, at 163 VGPRs, hold a whole CU: thousands of such blocks (n_partition = 64) ran 18 deep per CU)
-            static const u32 red_fused_max = knob("ROFL_RED_FUSED_T") ? (u32)atoi(knob("ROFL_RED_FUSED_T")) : 768u;
-            // (a fixed-base array enters with E = 512, nb = 6: 640 first-level items -- on 512 threads that was two passes of a seven-addition chain)
-            u32 fused_items = (E / 8) * (4 + nb), fused_threads = fused_items > 512 ? (fused_items > 640 ? 768 : 640) : fused_items > 256 ? 512 : fused_items > 128 ? 256 : fused_items > 64 ? 128 : 64;
-            if (fused_threads > red_fused_max) fused_threads = red_fused_max;
-            size_t lds = ((size_t)(E / 8) * (1 + nb + 3) + (size_t)(E / 16) * (1 + nb + 4) + 1) * sizeof(ge);
-            ROFL_LAUNCH(k_msm_reduce_fused, dim3((unsigned)PW), dim3(fused_threads), lds, st, E, nb, S_in, C_in, S_fin, C_fin, nb_final);
+        while (E > 512) {
+            u32 E8 = E / 8;
+            ge *S_out = W.S[lv & 1].as<ge>(PW * E8);
+            ge *C_out = W.Cacc[lv & 1].as<ge>(PW * (size_t)(nb + 3) * E8);
+            ROFL_LAUNCH(k_msm_reduce_level, grid1((size_t)E8 * (1 + nb), (u32)PW), dim3(TPB), 0, st, E, nb, S_in, C_in, S_out, C_out);
+            S_in = S_out; C_in = C_out; E = E8; nb += 3; lv++;
         }
+        if (J.dev_horner) { S_fin = W.S[lv & 1].as<ge>(PW); C_fin = W.Cacc[lv & 1].as<ge>(PW * (size_t)nb_final); }
+        // block size = first-level work items (small bucket arrays, c = 7: 32 items -- a 256-thread block would idle 7 of its 8
+        // waves and, at 163 VGPRs, hold a whole CU: thousands of such blocks (n_partition = 64) ran 18 deep per CU)
+        static const u32 red_fused_max = knob("ROFL_RED_FUSED_T") ? (u32)atoi(knob("ROFL_RED_FUSED_T")) : 768u;
+        // (a fixed-base array enters with E = 512, nb = 6: 640 first-level items -- on 512 threads that was two passes of a seven-addition chain)
+        u32 fused_items = (E / 8) * (4 + nb), fused_threads = fused_items > 512 ? (fused_items > 640 ? 768 : 640) : fused_items > 256 ? 512 : fused_items > 128 ? 256 : fused_items > 64 ? 128 : 64;
+        if (fused_threads > red_fused_max) fused_threads = red_fused_max;
+        size_t lds = ((size_t)(E / 8) * (1 + nb + 3) + (size_t)(E / 16) * (1 + nb + 4) + 1) * sizeof(ge);
+        ROFL_LAUNCH(k_msm_reduce_fused, dim3((unsigned)PW), dim3(fused_threads), lds, st, E, nb, S_in, C_in, S_fin, C_fin, nb_final);
     }
     if (J.host8)           // many problems, AVX-512 IFMA host: the device adds up each window's bit-sums, the chains across the windows go to the host
         ROFL_LAUNCH(k_msm_wsum, grid1(PW * 4), dim3(TPB), 0, st, (u32)PW, (const ge *)S_fin, (const ge *)C_fin, nb_final, hres_dev);

@@ -19,12 +19,7 @@ static const Knob KNOBS[] = {
     {"ROFL_VERIFY_ZIP_TRUNCATE", "0", "option verify_zip_truncate: 1 = the reference's zip-truncating verify_rangeproof"},
     {"ROFL_VERIFY_BATCH", "1", "option verify_batch: 0 = one check per proof, 1 = one per client, 2 = one per batch of clients (bisecting down to per-client checks on failure)"},
     {"ROFL_SIGMA_BATCH", "1", "option sigma_batch: 0 = one check per element in the Sigma-proof verifiers"},
-    {"ROFL_STAGE_COHERENT", "0", "1 = the staging arenas are coherent (hipHostMallocDefault) pinned memory as in rounds 3-4 instead of non-coherent (the DMA engine reads 32 instead of 57 GB/s out of it)"},
     {"ROFL_STAGE_KEEP_MB", "256", "pinned staging memory a lane keeps between calls (a call that needed more frees it when it ends)"},
-    {"ROFL_MSM_WINDOW_ORDER", "1", "0 = the bucket lists of the fixed-base two-level sort stay in arrival order and the accumulation's blocks in (problem, array) order (default: lists ordered by window slot, blocks array-major, so that the gathers of a launch stay within a few window slices of the table at a time)"},
-    {"ROFL_SIGMA_SPLIT", "1", "0 = the per-element Sigma-proof prover runs as one thread per element (k_sigma_prove) instead of one thread per output point + a finishing kernel (k_sigma_points, k_sigma_finish); same bytes"},
-    {"ROFL_MSM_BIN_TILE_SEARCH", "1", "0 = the coarse-bin pass of the two-level bucket sort keeps its power-of-two tile also when another tile length fills the CUs in fewer, shorter passes (batched rounds)"},
-    {"ROFL_HEAVY_LO", "0", "1 = while several calls share the device, the chip-filling launches (bucket accumulation, generator folds) go to a lowest-priority stream of their lane so that other calls' short kernels are dispatched between their blocks (measured: neutral for rounds of range proofs, slower for rounds of L2 updates -- profiles/r06_experiments.txt item 2; off)"},
     {"ROFL_GENS_LAZY", "1", "0 = the first call of a shape waits for its full fold table (otherwise it is served from the compact table while a background thread builds the full one)"},
     {"ROFL_GENS_LAZY_IDLE_MS", "20", "the background build of a full fold table starts when no call has been in flight for this long (its allocation stalls every HIP call of the process)"},
     {"ROFL_GENS_LAZY_MAX_WAIT_MS", "3000", "... or after this long, whichever comes first (a host that never pauses still gets its full table)"},
@@ -33,23 +28,13 @@ static const Knob KNOBS[] = {
     {"ROFL_FOLD_T1", "3", "IPP rounds before the first generator fold (1..6)"},
     {"ROFL_FOLD_T", "2", "IPP rounds between later folds (1..6)"},
     {"ROFL_FOLD_MIN", "1024", "no fold once fewer generators per chunk would remain (launches with many chunks fold down to 64)"},
-    {"ROFL_MSM_FB_FITSETS", "1", "0 = do not add bucket sets to a fixed-base launch whose coarse bins would not fit the two-level sort"},
     {"ROFL_MSM_BIN_SIGMA", "8", "room of a coarse bin of the two-level sort above twice its mean load, in standard deviations of that load (0 = the fixed 256 entries of rounds 2-3)"},
-    {"ROFL_POOL_NAP", "1", "0 = pool workers do not nap through a wait whose length the caller announced (they poll for ROFL_POOL_SPIN_US, then sleep until woken)"},
-    {"ROFL_SYNC_POLL", "0", "1 = wait for the lane's stream with hipStreamQuery in a pause loop instead of hipStreamSynchronize"},
     {"ROFL_FOLD_TAB", "1", "0 = first fold without the precomputed odd-multiple slices"},
     {"ROFL_FOLD_PB", "32", "piece width of the fold table in bits (16, 32, 64)"},
     {"ROFL_FOLD_W", "10", "NAF width of the fold table (3..10: 2^(w-2) odd multiples per 32-bit piece, 1/(w+1) of the digits non-zero; narrowed until the table fits ROFL_FOLD_TAB_MB)"},
     {"ROFL_FOLD_TAB_MB", "106496", "HBM budget of one (n, m) fold table (cfg 2 at width 10 and cfg 4 at width 9: 102.4 GB of the 288; 57344 = one width less, half the memory, +0.25 ms per cfg-2 proof)"},
-    {"ROFL_FOLD_WNAF", "0", "later folds: NAF width over odd multiples of the sources built on a side stream during the preceding rounds (3..6; 0 = plain NAF over the sources alone: the build disturbs the rounds it runs beside by what the shorter fold chains save -- measured neutral, off by default)"},
-    {"ROFL_FOLD_TAB_EV", "1", "0 = the first (table) fold scans digit arrays (k_fold_gens_tab) instead of walking an event list with operand prefetch (k_fold_gens_w)"},
-    {"ROFL_FOLD_UNIT", "1", "0 = do not keep the common factor s_0 of a fold in gscale / hscale"},
     {"ROFL_FOLD_K", "0", "digit-position segments per fold output (1, 2, 4; 0 = by launch size)"},
     {"ROFL_FOLD_THREADS", "131072", "fold launches with fewer threads split their chains into segments"},
-    {"ROFL_FOLD_DEFER", "1", "0 = the first fold converts every output to affine form itself (one inversion per output) instead of leaving that to k_niels_batch on the side stream"},
-    {"ROFL_FOLD_REGS", "1", "0 = the generic fold kernel instead of the three-sources-in-registers one"},
-    {"ROFL_IPP_FUSED", "1", "0 = k_ipp_fold_ab + k_ipp_scalars + k_ipp_inner instead of one k_ipp_round per round"},
-    {"ROFL_MSM_LR", "1", "0 = separate L and R scalar arrays (with zeros) instead of the merged layout"},
     {"ROFL_MSM_FB", "1", "0 = no window tables (every MSM generic)"},
     {"ROFL_MSM_FB_MIN", "4096", "generator sets smaller than this get no window table"},
     {"ROFL_MSM_FB_C", "0", "one window width (13, 15, 16) for every window table; 0 = 16-bit tables, plus a 15-bit one for generator sets below 2^17 that launches with many problems and the verifier use"},
@@ -66,19 +51,13 @@ static const Knob KNOBS[] = {
     {"ROFL_MSM_HOST8_MIN", "8", "launches with at least this many problems run their window chains eight per AVX-512 IFMA stream on the host (when the CPU has it)"},
     {"ROFL_MSM_FB_HOST8_MIN", "8", "fixed-base launches with at least this many problems finish eight problems per AVX-512 IFMA task (32 = as in rounds 3-4: one scalar chain per pool task below 32 problems)"},
     {"ROFL_KECCAK_ZMM", "", "host transcripts: 1 = Keccak-f[1600] with one state across five AVX-512 registers, 0 = the scalar rounds; unset = whichever a 50 us measurement at first use finds faster (Intel: the registers, 1.27x; Zen 5: scalar)"},
-    {"ROFL_LR_FIRST", "1", "0 = l(x), r(x), the first round's MSM scalars and its inner products in three launches (k_lr_vec, k_ipp_scalars, k_ipp_inner) instead of one (k_lr_first)"},
-    {"ROFL_HOP_CQ", "1", "0 = the <a,b> w B terms of a round are computed on the hop (after the wait) instead of on the pool while the round's MSM runs"},
     {"ROFL_MSM_DEV_HORNER_MIN", "32", "launches with at least this many problems combine their windows on the device"},
     {"ROFL_MSM_T13", "8192", "generic MSMs from this many terms on use 13-bit windows"},
     {"ROFL_MSM_T10", "512 / 2048", "generic MSMs from this many terms on use 10-bit windows (7-bit below, 4-bit below 64); default 2048 for launches with >= 32 problems"},
     {"ROFL_MSM_C", "0", "window width of every generic MSM (4, 7, 10, 13, 16; 0 = by size)"},
-    {"ROFL_MSM_GROUP_REDUCE", "0", "1 = two-launch bucket reduction by groups of 512 (measured slower)"},
-    {"ROFL_RED_SPLIT", "0", "1 = four threads per 8-group in k_msm_reduce_level (measured slower)"},
     {"ROFL_RED_FUSED_T", "768", "largest block of k_msm_reduce_fused"},
     {"ROFL_ACC_BALANCE", "1", "0 = accumulate blocks in plain descending-load order instead of equal-work blocks"},
     {"ROFL_TRACE", "0", "1 = one line per MSM on stderr, 2 = per-phase host timeline of every proof / verification"},
-    {"ROFL_DBG_IDX_MASK", "0x7fffffff", "timing experiments only (WRONG results): confines the table gathers to a prefix"},
-    {"ROFL_DBG_SCATTER", "0", "timing experiments only (WRONG results): 1 = no range reservation, 2 = no slot stores"},
     {"ROFL_DBG_SMALL_TIMELINE", "", "set: per-phase block timings of every fused small-MSM launch on stderr (synchronises; debugging)"},
     {"ROFL_DBG_ACC_TIMELINE", "", "file to append per-wave start / end / placement records of every fixed-base accumulate launch to"},
     {"ROFL_FEMUL_LDS", "0", "rofl_bench_femul: dynamic LDS per block (pins the micro-benchmark's occupancy)"},
@@ -121,26 +100,6 @@ sc h_mul(const sc &a, const sc &b) { return sc_mul_plain(a, b); }          // ca
 sc h_inv(const sc &canon) { return h_canon(h51::sc_invert_mont_fast(h_mont(canon))); }
 bool sc_is_canonical_bytes(const uint8_t *b) { sc s = sc_frombytes(b); return !sc_geq_l(s.v); }
 
-// width-w NAF (3 <= w <= 8) of a canonical scalar: odd digits |d| < 2^(w-1), at most one non-zero among w consecutive positions, density
-// 1 / (w + 1); returns the index of the highest non-zero digit (-1 if zero)
-int sc_wnaf(int8_t out[256], const sc &k, unsigned w) {
-    u32 x[9]; for (int i = 0; i < 8; i++) x[i] = k.v[i]; x[8] = 0;
-    const int full = 1 << w, half = 1 << (w - 1);
-    int top = -1;
-    for (int pos = 0; pos < 256; pos++) {
-        int d = 0;
-        if (x[0] & 1) {
-            d = (int)(x[0] & (u32)(full - 1)); if (d >= half) d -= full;
-            if (d > 0) { x[0] -= (u32)d; }        // (the low w bits are d: no borrow)
-            else { u64 c = (u64)(-d); for (int i = 0; i < 9 && c; i++) { c += x[i]; x[i] = (u32)c; c >>= 32; } }
-            top = pos;
-        }
-        out[pos] = (int8_t)d;
-        for (int i = 0; i < 8; i++) x[i] = (x[i] >> 1) | (x[i + 1] << 31);
-        x[8] >>= 1;
-    }
-    return top;
-}
 // width-2 NAF (digits -1,0,1) of a canonical scalar; returns index of the highest non-zero digit (-1 if zero)
 int sc_naf(int8_t out[256], const sc &k) {
     u32 x[9]; for (int i = 0; i < 8; i++) x[i] = k.v[i]; x[8] = 0;
@@ -160,7 +119,6 @@ int sc_naf(int8_t out[256], const sc &k) {
     return top;
 }
 
-// width-4 NAF (digits in +-{1,3,5,7}) of a 64-bit piece; returns the highest non-zero position (-1 if zero)
 // width-w NAF of a piece of at most 64 bits: odd digits |d| < 2^(w-1), at most one non-zero among w consecutive positions
 int wnaf_u64(int16_t out[FOLD_TAB_DIGITS], u64 piece, unsigned w) {
     unsigned __int128 k = piece; int top = -1;
@@ -313,15 +271,13 @@ class HostPool {
 public:
     explicit HostPool(int nthreads, const std::atomic<int> *in_flight = nullptr) : calls_in_flight(in_flight) {
         if (const char *e = knob("ROFL_POOL_SPIN_US")) spin_us = atof(e);
-        if (const char *e = knob("ROFL_POOL_NAP")) nap = atoi(e) != 0;
         asleep.reset(new std::atomic<uint32_t>[nthreads > 0 ? nthreads : 1]);
         for (int i = 0; i < nthreads; i++) asleep[i].store(0);
         for (int i = 1; i < nthreads; i++) workers.emplace_back([this, i] { loop(i); });
     }
     ~HostPool() { stop.store(true, std::memory_order_seq_cst); for (size_t w = 1; w <= workers.size(); w++) wake((int)w); for (auto &t : workers) t.join(); }
     // called right before the caller starts a wait it expects to last `us` microseconds (0 = unknown): polling workers nap through it
-    void expect_gap(double us) { if (!nap) return; gap_us.store(us, std::memory_order_relaxed); hint_seq.fetch_add(1, std::memory_order_release); }
-    bool nap = true;      // ROFL_POOL_NAP=0: workers only poll / sleep on the condition variable, as before
+    void expect_gap(double us) { gap_us.store(us, std::memory_order_relaxed); hint_seq.fetch_add(1, std::memory_order_release); }
     void run(size_t n, std::function<void(size_t)> f) {
         if (n <= 1 || workers.empty()) { for (size_t i = 0; i < n; i++) f(i); return; }
         spin_until([&] { return active.load() == 0; });     // no straggler of the previous job may still look at fn
@@ -385,12 +341,11 @@ struct Stage {
     static constexpr size_t kMin = 32 << 10;      // below this the runtime's own bounce buffers do the same job
     // The arena is only ever the source or destination of copies (no kernel reads it): non-coherent pinned memory.  The DMA engine moves
     // 57 GB/s out of it against 32 GB/s out of the default (coherent, fine-grained) flavour on this platform (scripts/stage_bw.hip).
-    static unsigned flags() { static const unsigned f = (knob("ROFL_STAGE_COHERENT") && atoi(knob("ROFL_STAGE_COHERENT")) != 0) ? hipHostMallocDefault : hipHostMallocNonCoherent; return f; }
     void *alloc(size_t n) {
         n = (n + 255) & ~(size_t)255; dirty = true;
         for (auto &c : chunks) if (c.cap - c.used >= n) { void *r = (char *)c.p + c.used; c.used += n; return r; }
         Chunk c; c.cap = std::max<size_t>(n, (size_t)4 << 20);      // never moves or frees a chunk that copies in flight may still use
-        HIPCHK(hipHostMalloc(&c.p, c.cap, flags()));
+        HIPCHK(hipHostMalloc(&c.p, c.cap, hipHostMallocNonCoherent));
         c.used = n; chunks.push_back(c); return c.p;
     }
     // after the call's last synchronisation: hand the results over, recycle the arena (several chunks -> one of their total size next time)
@@ -404,7 +359,7 @@ struct Stage {
         if (tot > keep || chunks.size() > 1) {
             for (auto &c : chunks) (void)hipHostFree(c.p);
             chunks.clear();
-            if (tot <= keep) { Chunk c; c.cap = tot; if (hipHostMalloc(&c.p, c.cap, flags()) == hipSuccess) chunks.push_back(c); }
+            if (tot <= keep) { Chunk c; c.cap = tot; if (hipHostMalloc(&c.p, c.cap, hipHostMallocNonCoherent) == hipSuccess) chunks.push_back(c); }
         }
         for (auto &c : chunks) c.used = 0;
         dirty = false;
@@ -551,10 +506,7 @@ struct Ctx {
     std::atomic<int> active_calls{0};  // primary lane only: calls currently holding a lane
     std::atomic<unsigned> rr{0};
     hipStream_t stream = nullptr, stream2 = nullptr;      // stream2: side stream for work that may run beside the main one (created on first use)
-    hipStream_t stream3 = nullptr;                        // the odd-multiple tables of the later folds are built here, beside the rounds that precede the fold
     hipStream_t stream_up = nullptr;                      // uploads of a pipelined batch call: the copy of group g + 1 runs beside the kernels of group g (created on first use)
-    hipStream_t stream_lo = nullptr;                      // LOWEST priority: the VALU-saturating launches (bucket accumulation, generator folds) of calls that share the device (HeavyScope)
-    std::vector<hipEvent_t> heavy_ev; size_t heavy_k = 0;  // ring of fork / join events of the heavy launches
     std::mutex mu;
     HostTables ht;
     niels *d_tabB = nullptr, *d_tabBb = nullptr, *d_tabB8 = nullptr, *d_tabBb8 = nullptr;      // radix-16 (64 x 8) and radix-256 (32 x 128) fixed-base tables of B and B~
@@ -565,30 +517,21 @@ struct Ctx {
     std::map<std::pair<size_t, size_t>, int> gens_pending;                 // shapes whose full table is still being built (rofl_bp_gens_prepare waits for them)
     u64 gens_tick = 0; size_t gens_budget = (size_t)128 << 30;   // ROFL_GENS_BUDGET_MB: evict least recently used (unpinned) tables beyond this
     u32 fold_pb = 32, fold_w = 10; size_t fold_tab_budget = (size_t)104 << 30;   // widest NAF whose table fits the per-(n, m) budget (ROFL_FOLD_W, ROFL_FOLD_TAB_MB)
-    int msm_lds = 1, msm_two_level = 1, msm_group_reduce = 0; size_t msm_lds_min = 8192, msm_lds_tile = 131072;
+    int msm_lds = 1, msm_two_level = 1; size_t msm_lds_min = 8192, msm_lds_tile = 131072;
     size_t msm_fb_threads = (size_t)1 << 19;
-    int msm_fb = 1; size_t msm_fb_min = (size_t)1 << 12; int msm_lr = 1;   // window tables for every (n, m) with 2N >= 4096: many small chunks (n_partition = 64) share them
+    int msm_fb = 1; size_t msm_fb_min = (size_t)1 << 12;   // window tables for every (n, m) with 2N >= 4096: many small chunks (n_partition = 64) share them
     bool crowded() const { const Ctx *P = parent ? parent : this; return P->active_calls.load() > 1; }   // other calls in flight on this device
     // Waiting for the lane's stream.  hipStreamSynchronize spins (lowest latency: right for a call that is alone on the device); with
     // more than three calls in flight -- or when the host asked for it (ROFL_BLOCKING_SYNC=1) -- the thread sleeps between queries instead, so
     // a server that keeps several clients in flight does not burn one host core per client on busy-waiting (ROFL_BLOCKING_SYNC=0: always spin).
-    hipEvent_t ev_block = nullptr, ev_v = nullptr, ev_fork = nullptr, ev_a = nullptr, ev_a0 = nullptr, ev_m2 = nullptr, ev_m2j = nullptr, ev_norm = nullptr, ev_norm0 = nullptr, ev_ip = nullptr, ev_mult = nullptr, ev_mult0 = nullptr; bool batch_mode = false;
+    hipEvent_t ev_block = nullptr, ev_v = nullptr, ev_fork = nullptr, ev_a = nullptr, ev_a0 = nullptr, ev_m2 = nullptr, ev_m2j = nullptr, ev_norm = nullptr, ev_norm0 = nullptr, ev_ip = nullptr; bool batch_mode = false;
     void sync() {
         const Ctx *P = parent ? parent : this;
         // (up to three calls in flight still spin: the three proofs of ONE client's L2 update run side by side -- EncParamsL2::encrypt --
         //  and that is a latency case; a server with more clients in flight is a throughput case)
         const int bs = opts().blocking_sync.load(std::memory_order_relaxed);
         bool block = bs == 1 || (bs < 0 && (P->active_calls.load() > 3 || batch_mode));
-        if (!block) {
-            static const bool poll = knob("ROFL_SYNC_POLL") && atoi(knob("ROFL_SYNC_POLL")) != 0;
-            if (!poll) { HIPCHK(hipStreamSynchronize(stream)); return; }
-            for (;;) {      // hipStreamQuery in a pause loop: never gives the CPU away
-                hipError_t q = hipStreamQuery(stream);
-                if (q == hipSuccess) return;
-                if (q != hipErrorNotReady) throw HipErr{q, "hipStreamQuery"};
-                for (int i = 0; i < 16; i++) __builtin_ia32_pause();
-            }
-        }
+        if (!block) { HIPCHK(hipStreamSynchronize(stream)); return; }
         // (hipEventSynchronize on a hipEventBlockingSync event still keeps the calling thread runnable on this runtime -- measured: 100 %
         //  of a core either way -- so the wait is a query loop with short sleeps: ~50 us of extra latency per wait, no CPU)
         if (!ev_block) HIPCHK(hipEventCreateWithFlags(&ev_block, hipEventDisableTiming));
@@ -620,13 +563,13 @@ struct Ctx {
     size_t msm_small_max = 8192;      // ROFL_MSM_SMALL_MAX: generic MSMs with at most this many terms per problem side run as one fused launch (0 = off)
     size_t msm_dev_horner_min = 32;   // ROFL_MSM_DEV_HORNER_MIN: launches with at least this many problems finish their Horner chains on the device
     bool msm_slots = true;
-    int fold_t = 2, fold_t1 = 3, fold_k = 0, fold_tab = 1, fold_unit = 1, fold_wnaf = 0; long fold_threads = 131072;
+    int fold_t = 2, fold_t1 = 3, fold_k = 0, fold_tab = 1; long fold_threads = 131072;
     Timing tm;
     struct HopStats { double enqueue = 0, sync = 0, horner_wall = 0, horner_cpu = 0, host_wall = 0, host_cpu = 0, max_enqueue = 0, max_sync = 0, max_horner = 0, max_task = 0; int n = 0; } hs;      // where the host hops of the current call go (ROFL_TRACE, rofl_dbg_last_hops)
     // workspace
     DevBuf cp, sL, sR, party, Scanon, vshift, blind, Vbytes, Cbytes, status, partial, partial2, scpart, a, b, a2, b2, ptab[2], yinv,
-        SL, SR, powtabs, foldprobs, naf,
-        gbuf[2], aux_pts, aux_scal, vscal, tmp_in, tmp_in2, tmp_out, vals, uni, stream_buf, vgroups, vtabs, ipdev, qpts, vspart, foldext, fmul_ext, fmul_tab, fold_ev;
+        SL, powtabs, foldprobs, naf,
+        gbuf[2], aux_pts, aux_scal, vscal, tmp_in, tmp_in2, tmp_out, vals, uni, stream_buf, vgroups, vtabs, ipdev, qpts, vspart, foldext, fold_ev;
     PinBuf h_cp, h_part, h_misc, h_misc2, h_auxc, h_auxs, h_V, h_ip, h_round, h_fdig, h_fprob, h_abfin, h_vgrp, h_q, h_fev;
     MsmWs mws[2];
     std::map<uint64_t, double> wait_ms;      // how long the wait of a tagged hop took the last times (hint for the pool workers' naps)
@@ -653,7 +596,6 @@ struct Ctx {
         HIPCHK(hipFuncSetAttribute((const void *)k_msm_reduce_fused, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void *)k_msm_small, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));      // + 2.5 KB of static LDS (bucket order)
         HIPCHK(hipFuncSetAttribute((const void *)k_msm_scatter_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *)k_msm_reduce_groups, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         HIPCHK(hipFuncSetAttribute((const void *)k_msm_bin_l1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void *)k_msm_bin_l2, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         HIPCHK(hipMalloc(&d_tabB, sizeof(niels) * 512));
@@ -675,10 +617,8 @@ struct Ctx {
         if (const char *e = knob("ROFL_MSM_FB_THREADS")) { long v = atol(e); if (v >= 1) msm_fb_threads = (size_t)v; }
         if (const char *e = knob("ROFL_MSM_LDS")) msm_lds = atoi(e);
         if (const char *e = knob("ROFL_MSM_TWO_LEVEL")) msm_two_level = atoi(e);
-        if (const char *e = knob("ROFL_MSM_GROUP_REDUCE")) msm_group_reduce = atoi(e);
         if (const char *e = knob("ROFL_MSM_LDS_MIN")) { long v = atol(e); if (v >= 1) msm_lds_min = (size_t)v; }
         if (const char *e = knob("ROFL_MSM_LDS_TILE")) { long v = atol(e); if (v >= 1024) msm_lds_tile = (size_t)v; }
-        if (const char *e = knob("ROFL_MSM_LR")) msm_lr = atoi(e);
         if (const char *e = knob("ROFL_MSM_FB_MIN")) { long v = atol(e); if (v >= 1) msm_fb_min = (size_t)v; }
         if (const char *e = knob("ROFL_FOLD_MIN")) { long v = atol(e); if (v >= 1) fold_min = (size_t)v; }
         if (const char *e = knob("ROFL_MSM_DEV_HORNER_MIN")) { long v = atol(e); if (v >= 1) msm_dev_horner_min = (size_t)v; }
@@ -696,8 +636,6 @@ struct Ctx {
         if (const char *e = knob("ROFL_FOLD_PB")) { int v = atoi(e); if (v == 16 || v == 32 || v == 64) fold_pb = (u32)v; }
         if (const char *e = knob("ROFL_FOLD_W")) { int v = atoi(e); if (v >= 3 && v <= 10) fold_w = (u32)v; }
         if (const char *e = knob("ROFL_FOLD_TAB_MB")) { long v = atol(e); if (v >= 1) fold_tab_budget = (size_t)v << 20; }
-        if (const char *e = knob("ROFL_FOLD_UNIT")) fold_unit = atoi(e) != 0;
-        if (const char *e = knob("ROFL_FOLD_WNAF")) { int v = atoi(e); if (v == 0 || (v >= 3 && v <= 6)) fold_wnaf = v; }
         if (const char *e = knob("ROFL_FOLD_K")) { int v = atoi(e); if (v == 1 || v == 2 || v == 4) fold_k = v; }
         if (const char *e = knob("ROFL_FOLD_THREADS")) { long v = atol(e); if (v > 0) fold_threads = v; }
         if (const char *e = knob("ROFL_LANES")) {      // out-of-range values are clamped, not ignored: the caller sized its thread pool by them
@@ -714,11 +652,11 @@ struct Ctx {
         HIPCHK(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));      // (with the main stream: see init)
         HIPCHK(hipStreamCreateWithFlags(&stream_up, hipStreamNonBlocking));
         ht = p.ht; d_tabB = p.d_tabB; d_tabBb = p.d_tabBb; d_tabB8 = p.d_tabB8; d_tabBb8 = p.d_tabBb8; d_two_pow = p.d_two_pow;
-        msm_lds = p.msm_lds; msm_two_level = p.msm_two_level; msm_group_reduce = p.msm_group_reduce; msm_lds_min = p.msm_lds_min; msm_lds_tile = p.msm_lds_tile;
+        msm_lds = p.msm_lds; msm_two_level = p.msm_two_level; msm_lds_min = p.msm_lds_min; msm_lds_tile = p.msm_lds_tile;
         msm_fb_threads = p.msm_fb_threads;
-        msm_fb = p.msm_fb; msm_fb_min = p.msm_fb_min; msm_lr = p.msm_lr;
+        msm_fb = p.msm_fb; msm_fb_min = p.msm_fb_min;
         fold_min = p.fold_min; msm_dev_horner_min = p.msm_dev_horner_min; msm_small_max = p.msm_small_max; msm_slots = p.msm_slots; fold_t = p.fold_t; fold_t1 = p.fold_t1; fold_k = p.fold_k; fold_tab = p.fold_tab;
-        fold_unit = p.fold_unit; fold_wnaf = p.fold_wnaf; fold_threads = p.fold_threads; nlanes = 1;
+        fold_threads = p.fold_threads; nlanes = 1;
         // (the other lanes: up to twelve -- a batched server call that lands on a sibling lane stages hundreds of MB through its pool, and which of two
         //  concurrent batch calls finds the primary lane free is a race; idle workers sleep on their futex words and cost nothing)
         { int nt = std::min(12, std::max(6, usable_cores())); if (const char *e = knob("ROFL_HOST_THREADS")) nt = atoi(e); if (nt < 1) nt = 1; pool.reset(new HostPool(nt, &g_calls_in_flight)); }
@@ -760,38 +698,6 @@ Ctx &ctx_of(int dev) {
 }
 Ctx &ctx() { return ctx_of(current_device()); }
 // binds the calling thread for the lifetime of the object (the worker threads of a sharded batch call)
-// EXPERIMENT (ROFL_HEAVY_LO=1; off): the launches that fill the chip for milliseconds -- k_msm_accumulate_*, k_fold_gens* -- at the LOWEST
-// stream priority while several calls share the device (batched rounds, calls in flight on other lanes).  The idea: at equal priority a foreign
-// lane's sort / reduce / scalar kernels (no field arithmetic, a few hundred blocks) get their workgroups dispatched only as the heavy launch
-// drains -- profiles/r06_cfg4_timeline_inflight3.txt: k_msm_bin_l2 1.6 ms alone, 23 ms beside another lane's accumulation; k_msm_reduce_level
-// 0.7 -> 11.5 ms -- so the short kernels should cut in as blocks retire.  Measured (profiles/r06_experiments.txt item 2): a cfg-4 round 1 368 /
-// 1 364 ms against 1 370 / 1 360 (neutral: with three calls in flight the device is saturated either way -- the stretched kernels wait, the
-// chip does not), a cfg-5 round 810 + 153 ms against 540 + 64 (the Sigma-proof legs' Pippenger launches wait behind everything).  Kept as a knob.
-struct HeavyScope {
-    Ctx &C; hipStream_t st, run; bool forked = false;
-    static bool enabled() { static const bool on = knob("ROFL_HEAVY_LO") && atoi(knob("ROFL_HEAVY_LO")) != 0; return on; }
-    HeavyScope(Ctx &c, hipStream_t s, bool want = true) : C(c), st(s), run(s) {      // want = false: a launch too short to be worth two events
-        if (!want || !enabled() || !(C.batch_mode || C.crowded())) return;
-        if (!C.stream_lo) {
-            int least = 0, greatest = 0;
-            if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); return; }
-            if (hipStreamCreateWithPriority(&C.stream_lo, hipStreamNonBlocking, least) != hipSuccess) { (void)hipGetLastError(); C.stream_lo = nullptr; return; }
-        }
-        while (C.heavy_ev.size() < 16) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); C.heavy_ev.push_back(e); }
-        hipEvent_t e0 = C.heavy_ev[(C.heavy_k++) & 15];
-        HIPCHK(hipEventRecord(e0, st)); HIPCHK(hipStreamWaitEvent(C.stream_lo, e0, 0));
-        run = C.stream_lo; forked = true;
-    }
-    void end() {
-        if (!forked) return;
-        forked = false;
-        hipEvent_t e1 = C.heavy_ev[(C.heavy_k++) & 15];
-        HIPCHK(hipEventRecord(e1, run)); HIPCHK(hipStreamWaitEvent(st, e1, 0));
-    }
-    ~HeavyScope() { if (forked) { hipEvent_t e1 = C.heavy_ev[(C.heavy_k++) & 15]; (void)hipEventRecord(e1, run); (void)hipStreamWaitEvent(st, e1, 0); } }
-    HeavyScope(const HeavyScope &) = delete; HeavyScope &operator=(const HeavyScope &) = delete;
-};
-
 struct DeviceBinding { int saved; explicit DeviceBinding(int dev) : saved(t_device) { t_device = dev; } ~DeviceBinding() { t_device = saved; } };
 
 // A lane held for the duration of one API call.
@@ -1003,11 +909,18 @@ bool gens_upgrade(Ctx &P0, GensEntry *raw, std::pair<size_t, size_t> key, FoldTa
     }
     return true;
 }
-// the fold-table layout a prover wants for N = n * m generators per side: the widest NAF whose table fits the per-shape budget
-FoldTabCfg gens_full_cfg(const Ctx &P0, size_t N) {
+// ROFL_FOLD_PB / ROFL_FOLD_W narrowed to the widest NAF whose table for N generators per side fits the per-shape budget and the event format
+FoldTabCfg fold_cfg_narrowed(const Ctx &P0, size_t N) {
     FoldTabCfg fc{P0.fold_pb, P0.fold_w, 256 / P0.fold_pb, 1u << (P0.fold_w - 2)};
     // HBM capacity for VALU work: a width-w NAF needs 2^(w-2) odd multiples per piece and leaves 1/(w+1) of the digits non-zero
     while (fc.w > 6 && sizeof(niels) * 2 * N * fc.np * fc.e > P0.fold_tab_budget) { fc.w--; fc.e = 1u << (fc.w - 2); }
+    // an event of the table fold numbers its slice in 12 bits (FOLD_EV; 0 = the source itself): np * e <= 4095 (16-bit pieces stop at width 9)
+    while ((size_t)fc.np * fc.e > 4095) { fc.w--; fc.e = 1u << (fc.w - 2); }
+    return fc;
+}
+// the fold-table layout a prover wants for N = n * m generators per side
+FoldTabCfg gens_full_cfg(const Ctx &P0, size_t N) {
+    FoldTabCfg fc = fold_cfg_narrowed(P0, N);
     if (sizeof(niels) * 2 * N * fc.np * fc.e > std::max(P0.fold_tab_budget, (size_t)40 << 30)) fc = FoldTabCfg{64, 4, 4, 4};     // very large tables: the compact layout
     return fc;
 }
@@ -1129,8 +1042,7 @@ bool gens_wait_full(Ctx &C, size_t n, size_t m) {
                 if (it == P0.gens.end() || it->second->full_state == 0) return true;
                 if (it->second->full_state < 0) {      // the build failed earlier: once more, on this thread
                     retry = it->second.get(); retry->users++; retry->full_state = 1; P0.gens_pending[key] = 2;
-                    fc_full = FoldTabCfg{P0.fold_pb, P0.fold_w, 256 / P0.fold_pb, 1u << (P0.fold_w - 2)};
-                    while (fc_full.w > 6 && sizeof(niels) * 2 * n * m * fc_full.np * fc_full.e > P0.fold_tab_budget) { fc_full.w--; fc_full.e = 1u << (fc_full.w - 2); }
+                    fc_full = fold_cfg_narrowed(P0, n * m);
                 }
             }
         }

@@ -80,9 +80,6 @@ __device__ __forceinline__ nd gload_nd(const niels *p) { return nd_unpack(gload_
 // Window-table entry of the fixed-base MSM: the affine niels triple already in the register radix (3 x 10 limbs + 2 words
 // of padding = 128 B, one cache line per gather; the 96-byte packed form straddles two 64-byte sectors just the same and
 // costs 66 VALU instructions per addition to unpack).
-#ifndef ROFL_ACC_LIST_CHUNK
-#define ROFL_ACC_LIST_CHUNK 0
-#endif
 struct ndm { u32 v[32]; };
 __device__ __forceinline__ nd gload_ndm(const ndm *p) {
     v4u w[8];
@@ -249,7 +246,7 @@ __global__ void __launch_bounds__(TPB) k_gens_map(u32 total, const uint8_t *uni,
 }
 #endif
 
-// Fold tables (see k_fold_gens_tab): slice (q * E + e) = (2e + 1) * 2^(PB q) * P for the NP = 256 / PB pieces of a
+// Fold tables (see k_fold_gens_w): slice (q * E + e) = (2e + 1) * 2^(PB q) * P for the NP = 256 / PB pieces of a
 // scalar and the E = 2^(w-2) odd multiples of a width-w NAF; slice 0 is the plain generator table.
 // One thread per (generator, piece); the E conversions to affine share one inversion.
 struct FoldTabCfg { u32 pb, w, np, e; };
@@ -556,25 +553,9 @@ __global__ void __launch_bounds__(TPB) k_poly_t(u32 n, u32 m, const ChunkParams 
     }
 }
 #endif
-// a = l(x), b = r(x); also yinv^k table
-#if ROFL_KG(4)
-__global__ void __launch_bounds__(TPB) k_lr_vec(u32 n, u32 m, const ChunkParams *cp, const PowTabs *pt, const u64 *vshift, const sc *sL, const sc *sR,
-                         const sc *two_pow, sc *a, sc *b, sc *yinvpow) {
-    u32 c = blockIdx.y;
-    size_t N = (size_t)n * m;
-    u32 k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= N) return;
-    sc l0, r0, r1;
-    sc l1 = load_sc(&sL[c * N + k]);
-    slot_vectors(cp[c], pt[c], n, k, vshift[(size_t)c * m + k / n], load_sc(&sR[c * N + k]), l0, r0, r1, two_pow);
-    store_sc(&a[c * N + k], sc_add(l0, sc_montmul(l1, cp[c].x)));
-    store_sc(&b[c * N + k], sc_add(r0, sc_montmul(r1, cp[c].x)));
-    store_sc(&yinvpow[c * N + k], pt_pow(pt[c].yinv, cp[c].yinvpow2, k));
-}
-#endif
 
-// k_lr_vec + the first round's k_ipp_scalars (merged form) + k_ipp_inner in one pass: a thread owns the pairs (i, N/2 + i) of its chunk and
-// writes a, b, y^-j, the round's MSM scalars (no pending challenges yet: s_G = gscale, s_H = hscale y^-j; generator j of the low half takes
+// a = l(x), b = r(x), the y^-j table, and with them the first round's MSM scalars and inner products in one pass: a thread owns the pairs
+// (i, N/2 + i) of its chunk and writes a, b, y^-j, the round's MSM scalars (no pending challenges yet: s_G = gscale, s_H = hscale y^-j; generator j of the low half takes
 // the vectors' high half and vice versa) and the partial inner products <a_L, b_R>, <a_R, b_L> of its block -> ip_out[chunk][block][2].
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(TPB, 3) k_lr_first(u32 n, u32 m, const ChunkParams *cp, const PowTabs *pt, const u64 *vshift, const sc *sL, const sc *sR,
@@ -620,83 +601,10 @@ __global__ void __launch_bounds__(TPB, 3) k_lr_first(u32 n, u32 m, const ChunkPa
 // ================================================================ K7: inner-product argument
 // Lazily folded generators: the materialised arrays Gc/Hc have n_g entries; the logical vectors have
 // n_k = n_g >> r entries; true G[i] = sum_h s_G(h) Gc[h*n_k+i], true H[i] = sum_h s_H(h) y^-j Hc[j].
-// Writes canonical MSM scalars for L (SL) and R (SR) over [Gc | Hc].
-#if ROFL_KG(4)
-__global__ void __launch_bounds__(TPB) k_ipp_scalars(u32 n_g, u32 n_k, u32 r, const ChunkParams *cp, const sc *a, const sc *b, size_t ab_stride,
-                              const sc *yinvpow, size_t y_stride, sc *SL, sc *SR, int merged) {
-    u32 c = blockIdx.y;
-    u32 j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_g) return;
-    u32 h = j / n_k, i = j % n_k, nh = n_k / 2;
-    const sc *ac = a + c * ab_stride, *bc = b + c * ab_stride;
-    // s_G(h) = gscale * prod_q (bit_q(h) ? u_q : u_q^-1), s_H(h) with u and u^-1 swapped; challenge q <-> bit r-1-q of h
-    sc sG = load_sc(&cp[c].gscale), sH = load_sc(&cp[c].hscale);
-    for (u32 q = 0; q < r; q++) {
-        bool bit = (h >> (r - 1 - q)) & 1;
-        sc up = load_sc(&cp[c].pend_u[q]), ui = load_sc(&cp[c].pend_ui[q]);
-        sG = sc_montmul(sG, bit ? up : ui);
-        sH = sc_montmul(sH, bit ? ui : up);
-    }
-    sH = sc_montmul(sH, load_sc(&yinvpow[c * y_stride + j]));
-    sc *sl = SL + (size_t)c * 2 * n_g, *sr = SR + (size_t)c * 2 * n_g;
-    if (merged) {      // one array, every term non-zero; the side of a term is a function of its index (MsmMap)
-        bool lo = i < nh; u32 ii = lo ? nh + i : i - nh;
-        store_sc(&sl[j], sc_from_mont(sc_montmul(load_sc(&ac[ii]), sG)));
-        store_sc(&sl[n_g + j], sc_from_mont(sc_montmul(load_sc(&bc[ii]), sH)));
-        return;
-    }
-    sc zero = sc_zero();
-    if (i < nh) {
-        // G_L / H_L halves: R gets a_R * G_L ; L gets b_R * H_L
-        store_sc(&sr[j], sc_from_mont(sc_montmul(load_sc(&ac[nh + i]), sG)));
-        store_sc(&sl[j], zero);
-        store_sc(&sl[n_g + j], sc_from_mont(sc_montmul(load_sc(&bc[nh + i]), sH)));
-        store_sc(&sr[n_g + j], zero);
-    } else {
-        u32 ii = i - nh;
-        store_sc(&sl[j], sc_from_mont(sc_montmul(load_sc(&ac[ii]), sG)));
-        store_sc(&sr[j], zero);
-        store_sc(&sr[n_g + j], sc_from_mont(sc_montmul(load_sc(&bc[ii]), sH)));
-        store_sc(&sl[n_g + j], zero);
-    }
-}
-#endif
-// c_L = <a_L, b_R>, c_R = <a_R, b_L>  -> out[chunk][blk][2]
-#if ROFL_KG(4)
-__global__ void __launch_bounds__(TPB) k_ipp_inner(u32 nh, const sc *a, const sc *b, size_t ab_stride, sc *out) {
-    __shared__ sc lds[TPB * 2];
-    u32 c = blockIdx.y;
-    const sc *ac = a + c * ab_stride, *bc = b + c * ab_stride;
-    sc v[2] = {sc_zero(), sc_zero()};
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nh; i += gridDim.x * blockDim.x) {
-        v[0] = sc_add(v[0], sc_montmul(load_sc(&ac[i]), load_sc(&bc[nh + i])));
-        v[1] = sc_add(v[1], sc_montmul(load_sc(&ac[nh + i]), load_sc(&bc[i])));
-    }
-    block_sum_sc<2>(v, lds);
-    if (threadIdx.x == 0) {
-        store_sc(&out[((size_t)c * gridDim.x + blockIdx.x) * 2 + 0], v[0]);
-        store_sc(&out[((size_t)c * gridDim.x + blockIdx.x) * 2 + 1], v[1]);
-    }
-}
-#endif
-// a_L = a_L u + u^-1 a_R ; b_L = b_L u^-1 + u b_R.  This round's challenge (u, u^-1; Montgomery) is read from `round_ch`
-// [chunk][2] -- mapped host memory the host wrote after the transcript step, so no H2D copy sits on the hop -- and recorded as
-// pending challenge number `pend_idx` of the chunk (k_ipp_scalars of the next rounds reads the pending list from device memory).
-#if ROFL_KG(4)
-__global__ void __launch_bounds__(TPB) k_ipp_fold_ab(u32 nh, ChunkParams *cp, const sc *round_ch, u32 pend_idx, sc *a, sc *b, size_t ab_stride) {
-    u32 c = blockIdx.y;
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    sc u = load_sc(&round_ch[2 * c]), ui = load_sc(&round_ch[2 * c + 1]);
-    if (i == 0) { store_sc(&cp[c].pend_u[pend_idx], u); store_sc(&cp[c].pend_ui[pend_idx], ui); }
-    if (i >= nh) return;
-    sc *ac = a + c * ab_stride, *bc = b + c * ab_stride;
-    store_sc(&ac[i], sc_add(sc_montmul(load_sc(&ac[i]), u), sc_montmul(load_sc(&ac[nh + i]), ui)));
-    store_sc(&bc[i], sc_add(sc_montmul(load_sc(&bc[i]), ui), sc_montmul(load_sc(&bc[nh + i]), u)));
-}
-#endif
 
-// One launch per IPP round (rounds >= 1, merged L/R layout) instead of k_ipp_fold_ab + k_ipp_scalars + k_ipp_inner and an H2D copy
-// of the challenge:  (1) fold a, b with the previous round's challenge u -- read from mapped host memory, once per block -- into the
+// One launch per IPP round (rounds >= 1, merged L/R layout: one scalar array over [Gc | Hc] serves L and R, see MsmMap) and no H2D copy
+// of the challenge:  (1) fold a, b with the previous round's challenge u (a_L = a_L u + u^-1 a_R, b_L = b_L u^-1 + u b_R) -- u, u^-1
+// (Montgomery) read from mapped host memory the host wrote after the transcript step, once per block -- into the
 // other ping-pong buffer; (2) the MSM scalars of THIS round over the materialised generators, i.e. the folded values times the
 // products of the pending challenges (those already on the device plus, unless the generators were re-materialised in between, u);
 // (3) the partial sums of c_L = <a_L, b_R>, c_R = <a_R, b_L> -> ip_out [chunk][gridDim.x][2] (mapped host memory).
@@ -773,7 +681,8 @@ __global__ void __launch_bounds__(TPB) k_ipp_round(u32 n_g, u32 n_k, u32 r_prev,
 #endif
 
 // Materialise folded generators: dst[i] = sum_{h < nsrc} s_h * src[h*n_new + i], all outputs of a problem
-// share the scalars s_h (given as NAF digits, wave-uniform control flow => no divergence).
+// share the scalars s_h (given as NAF digits, wave-uniform control flow => no divergence).  The prover keeps the common factor of a
+// fold's scalars aside in gscale / hscale, so source 0 has scalar 1 (unit_first: one addition, no digits).
 struct FoldProb { const niels *src; niels *dst; };
 #define FOLD_MAXSRC 64
 #define FOLD_MAXSEG 4
@@ -856,24 +765,12 @@ __global__ void __launch_bounds__(256, 2) k_fold_gens4(u32 n_new, FoldSeg seg, c
 }
 #endif
 
-// Later folds with odd multiples of their sources.  The sources of a later fold are the previous fold's outputs -- proof-specific, so nothing
-// can be precomputed across proofs; but they exist two rounds before the fold needs them.  k_odd_multiples builds (2e+1) P for e = 1 .. E-1 of
-// every materialised point on the SIDE stream while those rounds run (extended coordinates; k_niels_batch turns them into affine niels, eight
-// per inversion), and the fold walks width-w NAF digits (one non-zero in w + 1 positions instead of one in three): its chain -- the critical
-// path of the phase, at two waves per SIMD -- loses a third of its additions for work that was done off the path.
-#if ROFL_KG(2)
-__global__ void __launch_bounds__(TPB) k_odd_multiples(u32 count, u32 E, const niels *src, ge *ext /* [E-1][count] */) {
-    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= count) return;
-    const gd p = gd_unpack(ge_from_niels(load_niels(&src[j])));
-    const gd p2 = gd_double(p);
-    gd cur = p;
-    for (u32 e = 1; e < E; e++) { cur = gd_add(cur, p2); store_gd(&ext[(size_t)(e - 1) * count + j], cur); }
-}
-#endif
-// The fold itself: an EVENT list per problem instead of digit arrays -- (bit, source, multiple, sign), highest bit first, wave-uniform -- so
-// that the operand of the next addition is fetched while the doublings in front of it run (the table is in HBM: gathered inside the chain,
-// as the generic kernel does with its sources, every addition waited ~1.7 us for its operand).  Segments as in k_fold_gens.
+// First materialisation: the sources are the FIXED generators, for which get_gens precomputed the odd multiples of every piece of a scalar
+// (FoldTabCfg, k_gens_tables): the pieces go in width-w NAF, pb doublings per output instead of 253 and 1 / (w + 1) of the digits non-zero.
+// HBM capacity traded for VALU work.  The fold walks an EVENT list per problem -- (bit, source, table slice, sign), highest bit first,
+// wave-uniform -- so that the operand of the next addition is fetched while the doublings in front of it run (the table is in HBM: gathered
+// inside the chain, as the generic kernel does with its sources, every addition waited ~1.7 us for its operand).  Segments as in k_fold_gens.
+#define FOLD_TAB_DIGITS 72      /* digit positions of one piece on the host: 64 bits + the NAF's carry */
 struct FoldWProb { const niels *src; niels *dst; u32 tab_off, ev_off, n_ev, seg_start[FOLD_MAXSEG]; };
 #define FOLD_EV(bit, h, e, neg) ((u32)(bit) | ((u32)(h) << 9) | ((u32)(e) << 15) | ((u32)(neg) << 27))      /* e: table slice, 0 = the source itself (12 bits) */
 #if ROFL_KG(2)
@@ -930,55 +827,6 @@ __global__ void __launch_bounds__(256, 2) k_fold_gens_w(u32 n_new, FoldSeg seg, 
 }
 #endif
 
-// First materialisation: the sources are the FIXED generators, for which get_gens precomputed
-//   tbl16[(q*4+e)*stride + g] = (2e+1) * 2^(64q) * G_g      (q < 4, e < 4; affine niels)
-// so a 253-bit scalar becomes four 64-bit pieces in width-4 NAF: 64 doublings per output instead of 253 and
-// ~51 instead of ~84 mixed additions per source.  HBM capacity (16 x 50 MB at N = 262144) traded for VALU work.
-#define FOLD_TAB_DIGITS 72
-struct FoldTabProb { u32 src_off; niels *dst; };
-#if ROFL_KG(2)
-__global__ void __launch_bounds__(256, 4) k_fold_gens_tab(u32 n_new, u32 nsrc, FoldSeg seg, FoldTabCfg cfg, const niels *tbl16, size_t stride,
-                                                       const FoldTabProb *probs, const int16_t *dig /* [prob][nsrc][np][72] */, int unit_first, ge *ext_out) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    ge *lds = reinterpret_cast<ge *>(smem);
-    u32 q = blockIdx.y;
-    u32 i = blockIdx.x * 64 + threadIdx.x;
-    u32 k = threadIdx.y, K = blockDim.y;
-    bool active = i < n_new;
-    const niels *src = tbl16 + probs[q].src_off;
-    const int16_t *dg = dig + (size_t)q * nsrc * cfg.np * FOLD_TAB_DIGITS;
-    gd acc = gd_identity();
-    if (active) {
-        int lo = seg.lo[k], hi = seg.lo[k + 1] - 1;
-        for (int bit = hi; bit >= lo; bit--) {
-            acc = gd_double(acc);
-            for (u32 h = unit_first ? 1 : 0; h < nsrc; h++) {
-                for (u32 pc = 0; pc < cfg.np; pc++) {
-                    int d = dg[(h * cfg.np + pc) * FOLD_TAB_DIGITS + bit];
-                    if (d != 0) {
-                        u32 e = (u32)((d < 0 ? -d : d) - 1) >> 1;
-                        acc = gd_madd(acc, gload_nd(&src[(size_t)(pc * cfg.e + e) * stride + (size_t)h * n_new + i]), d < 0);
-                    }
-                }
-            }
-        }
-        for (int t = 0; t < lo; t++) acc = gd_double(acc);
-    }
-    if (K > 1) {
-        if (k > 0) lds[(k - 1) * 64 + threadIdx.x] = gd_pack(acc);
-        __syncthreads();
-        if (k == 0)
-            for (u32 s2 = 1; s2 < K; s2++) acc = gd_add(acc, gd_unpack(lds[(s2 - 1) * 64 + threadIdx.x]));
-    }
-    if (active && k == 0) {
-        if (unit_first) acc = gd_madd(acc, gload_nd(&src[i]), false);
-        // ext_out: leave the point in extended coordinates; k_niels_batch converts eight of them behind one inversion (the inversion chain
-        // was 14 % of this kernel's multiplications) on the side stream, while the next round's scalar and sort kernels run
-        if (ext_out) store_gd(&ext_out[(size_t)q * n_new + i], acc);
-        else gstore_niels(&probs[q].dst[i], gd_to_niels(acc));
-    }
-}
-#endif
 // out[i] = affine niels form of ext[i], NB_BATCH points per thread behind ONE field inversion (Montgomery's trick: prefix products, invert,
 // walk back): 36 multiplications per point instead of 265.
 #define NB_BATCH 8
@@ -1076,7 +924,7 @@ struct MsmProb { const niels *pts; const sc *scal; };   // per problem: points a
 // How the (term, window) grid maps to bucket arrays.
 //  * lr_nh != 0: "L/R merged" IPP round.  The grid runs over chunks; chunk q owns problems 2q (L) and 2q+1 (R), which
 //    share one scalar array over [Gc | Hc] in which every term is non-zero and belongs to exactly one side
-//    (k_ipp_scalars, merged): G-side term j is L iff (j mod n_k) >= nh, H-side the other way round.
+//    (k_lr_first, k_ipp_round): G-side term j is L iff (j mod n_k) >= nh, H-side the other way round.
 //  * fb_sets != 0: fixed-base mode.  pts is the window table T[w][i] = 2^(pos_w) P_i (stride fb_stride; the c = 16
 //    window layout of msm_window), and windows [s*wps, (s+1)*wps) of a problem share bucket set s: no doublings are
 //    left between windows, and the bucket reduction runs over fb_sets sets instead of 16 windows.  With lr each side
@@ -1214,7 +1062,7 @@ __device__ __forceinline__ u32 msm_side_term(const MsmMap &mm, u32 side, u32 k) 
 }
 #if ROFL_KG(1)
 __global__ void __launch_bounds__(1024) k_msm_scatter_lds(u32 n_side, u32 tile_pts, MsmWin mw, MsmMap mm, const MsmProb *probs, u32 *cursor, u32 *slots,
-                                                          u32 cap, u32 *ovf_count, MsmOvf *ovf, u32 ovf_max, u32 dbg) {
+                                                          u32 cap, u32 *ovf_count, MsmOvf *ovf, u32 ovf_max) {
     extern __shared__ u32 lcnt[];
     const u32 B = 1u << (mw.c - 1);
     u32 nside = mm.lr_nh ? 2u : 1u;
@@ -1243,7 +1091,7 @@ __global__ void __launch_bounds__(1024) k_msm_scatter_lds(u32 n_side, u32 tile_p
     __syncthreads();
     for (u32 b = threadIdx.x; b < B; b += 1024) {
         u32 c = lcnt[b];
-        lcnt[b] = (c && !(dbg & 1)) ? atomicAdd(&cursor[(size_t)pw * B + b], c) : 0u;
+        lcnt[b] = c ? atomicAdd(&cursor[(size_t)pw * B + b], c) : 0u;
     }
     __syncthreads();
     for (u32 k = k0 + threadIdx.x; k < k1; k += 1024) {
@@ -1260,7 +1108,6 @@ __global__ void __launch_bounds__(1024) k_msm_scatter_lds(u32 n_side, u32 tile_p
                 if (!a1) continue;
                 u32 pos = atomicAdd(&lcnt[a1 - 1], 1u);
                 u32 bi = pw * B + a1 - 1;
-                if (dbg & 2) { if (pos == 0xffffffffu) slots[0] = entry; continue; }
                 if (pos < cap) slots[(size_t)bi * cap + pos] = entry;
                 else { u32 o = atomicAdd(ovf_count, 1u); if (o < ovf_max) { ovf[o].bucket = bi; ovf[o].entry = entry; } }
             }
@@ -1446,7 +1293,7 @@ __global__ void k_msm_overflow(u32 W, u32 B, u32 pstep, const MsmProb *probs, co
 // one thread per bucket: sum its points.  buckets [prob][W][B] extended.
 // blockIdx.y = grid problem q owning W bucket arrays; its points are probs[q * pstep].pts (pstep = 2 for merged L/R pairs)
 template <bool FB> __device__ __forceinline__ void msm_accumulate_body(u32 n, u32 c, u32 W, u32 pstep, const MsmProb *probs, const u32 *cnt, const u32 *off,
-                                 const u32 *sorted, const u32 *perm, ge *buckets, u32 cap, u32 idx_mask, u32 balance) {
+                                 const u32 *sorted, const u32 *perm, ge *buckets, u32 cap, u32 balance) {
     u32 p = blockIdx.y, B = 1u << (c - 1);
     u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if ((balance & 2u) && B >= TPB) {
@@ -1483,61 +1330,27 @@ template <bool FB> __device__ __forceinline__ void msm_accumulate_body(u32 n, u3
     //  forcing 5 waves/SIMD -- 96 VGPRs, 136 B/lane of scratch -- takes 1.65x as long)
     // the list entry of the NEXT addition is fetched one iteration ahead (one register): the entry -> point gather chain is two
     // dependent memory latencies per addition otherwise
-#if ROFL_ACC_LIST_CHUNK
-    // The 64 lanes of a wave stream 64 different lists; with 16 waves per CU that is 128 KB of live list lines against a 32 KB L1 and this
-    // CU's share of L2, and a 128-byte line read four bytes at a time is evicted between two of its 32 reads about every other time
-    // (PMC, profiles/r04_experiments.txt: 5.8 GB per launch against the 3.8 GB that the table records and list entries amount to; the gather
-    // micro-benchmark, which has no lists, fetches exactly its 128 bytes per record).  This variant takes the entries two (ROFL_ACC_LIST_CHUNK
-    // = 2) or four (= 4) at a time from the aligned chunk that holds them (a chunk may start before the list and end after it: both lie inside
-    // the sort's own arrays) and requests the next chunk when the last entry of the current one has been taken, one addition ahead.
-    // MEASURED: four at a time 5.79 -> 4.99 GB per launch and 1.225 -> 1.312 ms (the selects and the branch cost more than the re-fetches);
-    // not the default.
-    const uintptr_t la = reinterpret_cast<uintptr_t>(lst);
-#if ROFL_ACC_LIST_CHUNK == 2
-    const uint2 *ch = reinterpret_cast<const uint2 *>(la & ~(uintptr_t)7);
-    u32 k = (u32)(la >> 2) & 1u;
-    uint2 cur = num ? *ch : make_uint2(0, 0);
-    for (u32 e = 0; e < num; e++) {
-        const u32 v = k ? cur.y : cur.x;
-        if (k) { if (e + 1 < num) cur = *++ch; }
-        k ^= 1u;
-        u32 idx = v & idx_mask;
-        acc = gd_madd(acc, FB ? gload_ndm(reinterpret_cast<const ndm *>(pts) + idx) : gload_nd(&pts[idx]), (v >> 31) != 0);
-    }
-#else
-    const uint4 *ch = reinterpret_cast<const uint4 *>(la & ~(uintptr_t)15);
-    u32 k = (u32)(la >> 2) & 3u;
-    uint4 cur = num ? *ch : make_uint4(0, 0, 0, 0);
-    for (u32 e = 0; e < num; e++) {
-        const u32 v = k == 0 ? cur.x : k == 1 ? cur.y : k == 2 ? cur.z : cur.w;
-        if (k == 3) { if (e + 1 < num) cur = *++ch; k = 0; } else k++;
-        u32 idx = v & idx_mask;
-        acc = gd_madd(acc, FB ? gload_ndm(reinterpret_cast<const ndm *>(pts) + idx) : gload_nd(&pts[idx]), (v >> 31) != 0);
-    }
-#endif
-#else
     u32 vnext = num ? lst[0] : 0u;
     for (u32 e = 0; e < num; e++) {
         u32 v = vnext;
         if (e + 1 < num) vnext = lst[e + 1];
-        u32 idx = v & idx_mask;
+        u32 idx = v & 0x7fffffffu;
         acc = gd_madd(acc, FB ? gload_ndm(reinterpret_cast<const ndm *>(pts) + idx) : gload_nd(&pts[idx]), (v >> 31) != 0);
     }
-#endif
     store_gd(&buckets[bi], acc);
 }
 #if ROFL_KG(1)
 __global__ void __launch_bounds__(TPB) k_msm_accumulate_fb(u32 n, u32 c, u32 W, u32 pstep, const MsmProb *probs, const u32 *cnt, const u32 *off,
-                                 const u32 *sorted, const u32 *perm, ge *buckets, u32 cap, u32 idx_mask, u32 balance) {
-    msm_accumulate_body<true>(n, c, W, pstep, probs, cnt, off, sorted, perm, buckets, cap, idx_mask, balance);
+                                 const u32 *sorted, const u32 *perm, ge *buckets, u32 cap, u32 balance) {
+    msm_accumulate_body<true>(n, c, W, pstep, probs, cnt, off, sorted, perm, buckets, cap, balance);
 }
 #endif
 // debugging aid (ROFL_DBG_ACC_TIMELINE): the same launch with one record per wave -- start / end on the 100 MHz wall clock, HW_ID, XCC_ID
 #if ROFL_KG(1)
 __global__ void __launch_bounds__(TPB) k_msm_accumulate_fb_dbg(u32 n, u32 c, u32 W, u32 pstep, const MsmProb *probs, const u32 *cnt, const u32 *off,
-                                 const u32 *sorted, const u32 *perm, ge *buckets, u32 cap, u32 idx_mask, u32 balance, unsigned long long *rec) {
+                                 const u32 *sorted, const u32 *perm, ge *buckets, u32 cap, u32 balance, unsigned long long *rec) {
     unsigned long long t0 = wall_clock64();
-    msm_accumulate_body<true>(n, c, W, pstep, probs, cnt, off, sorted, perm, buckets, cap, idx_mask, balance);
+    msm_accumulate_body<true>(n, c, W, pstep, probs, cnt, off, sorted, perm, buckets, cap, balance);
     unsigned long long t1 = wall_clock64();
     if ((threadIdx.x & 63) == 0) {
         u32 hw, xcc;
@@ -1550,8 +1363,8 @@ __global__ void __launch_bounds__(TPB) k_msm_accumulate_fb_dbg(u32 n, u32 c, u32
 #endif
 #if ROFL_KG(1)
 __global__ void __launch_bounds__(TPB) k_msm_accumulate_gen(u32 n, u32 c, u32 W, u32 pstep, const MsmProb *probs, const u32 *cnt, const u32 *off,
-                                 const u32 *sorted, const u32 *perm, ge *buckets, u32 cap, u32 idx_mask, u32 balance) {
-    msm_accumulate_body<false>(n, c, W, pstep, probs, cnt, off, sorted, perm, buckets, cap, idx_mask, balance);
+                                 const u32 *sorted, const u32 *perm, ge *buckets, u32 cap, u32 balance) {
+    msm_accumulate_body<false>(n, c, W, pstep, probs, cnt, off, sorted, perm, buckets, cap, balance);
 }
 #endif
 // Bucket reduction without doublings: sum_b (b+1) B_b = S + sum_l 2^l D_l, D_l = sum of buckets whose
@@ -1617,14 +1430,9 @@ __device__ __forceinline__ void msm_reduce_item_split(u32 E, u32 nb, const ge *S
     }
 }
 #if ROFL_KG(1)
-__global__ void __launch_bounds__(TPB) k_msm_reduce_level(u32 E, u32 nb, const ge *S_in, const ge *C_in, ge *S_out, ge *C_out, int split) {
+__global__ void __launch_bounds__(TPB) k_msm_reduce_level(u32 E, u32 nb, const ge *S_in, const ge *C_in, ge *S_out, ge *C_out) {
     u32 pw = blockIdx.y, E8 = E / 8;
     u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (split) {      // the four outputs of an 8-group on four threads: 7 / 3 / 3 / 3 additions deep instead of 11 on one thread
-        if (t >= E8 * (4 + nb)) return;
-        msm_reduce_item_split(E, nb, S_in + (size_t)pw * E, C_in + (size_t)pw * nb * E, S_out + (size_t)pw * E8, C_out + (size_t)pw * (nb + 3) * E8, t);
-        return;
-    }
     if (t >= E8 * (1 + nb)) return;
     msm_reduce_item(E, nb, S_in + (size_t)pw * E, C_in + (size_t)pw * nb * E, S_out + (size_t)pw * E8, C_out + (size_t)pw * (nb + 3) * E8, t);
 }
@@ -1691,35 +1499,6 @@ __global__ void __launch_bounds__(768) k_msm_reduce_fused(u32 E, u32 nb, const g
     extern __shared__ __align__(16) unsigned char smem[];
     u32 pw = blockIdx.x;
     msm_reduce_fused_body(E, nb, S_in + (size_t)pw * E, C_in + (size_t)pw * nb * E, S_fin + pw, C_fin + (size_t)pw * nb_final, smem);
-}
-#endif
-// Two-launch bucket reduction (round 2) for arrays of B = 512 * G buckets: k_msm_reduce_fused treats every run of 512 buckets as an
-// array of its own (E = 512, nb = 0: one block each, 64 x 16 blocks at B = 32768 instead of the 16 blocks that used to finish the
-// tree), then this kernel combines the G groups of an array: S = sum_g S_g; bit-sums 0..8 = sum_g D_(l,g); bit-sum 9 + t = sum of
-// the S_g of the groups whose index has bit t set (a bucket's 0-based index is g * 512 + low bits).  One block per array, one
-// output per threadIdx.y, G / 2 lanes per output + LDS tree.
-#if ROFL_KG(1)
-__global__ void __launch_bounds__(512) k_msm_reduce_groups(u32 G, u32 gbits, const ge *GS /* [PW][G] */, const ge *GC /* [PW][G][9] */, ge *S_fin, ge *C_fin, u32 nb_final) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    ge *lds = reinterpret_cast<ge *>(smem);                  // [nout][half]
-    u32 pw = blockIdx.x, o = threadIdx.y, t = threadIdx.x, half = blockDim.x;      // half = max(G / 2, 1)
-    const ge *gs = GS + (size_t)pw * G, *gc = GC + (size_t)pw * G * 9;
-    gd acc = gd_identity();
-    for (u32 g = t; g < G; g += half) {
-        if (o == 0) acc = gd_add(acc, load_gd(&gs[g]));
-        else if (o <= 9) acc = gd_add(acc, load_gd(&gc[(size_t)g * 9 + (o - 1)]));
-        else if ((g >> (o - 10)) & 1) acc = gd_add(acc, load_gd(&gs[g]));
-    }
-    lds[o * half + t] = gd_pack(acc);
-    __syncthreads();
-    for (u32 s2 = half / 2; s2 >= 1; s2 >>= 1) {
-        if (t < s2) lds[o * half + t] = gd_pack(gd_add(gd_unpack(lds[o * half + t]), gd_unpack(lds[o * half + t + s2])));
-        __syncthreads();
-    }
-    if (t == 0) {
-        if (o == 0) store_ge(&S_fin[pw], lds[0]);
-        else store_ge(&C_fin[(size_t)pw * nb_final + (o - 1)], lds[o * half]);
-    }
 }
 #endif
 // The same reduction as msm_reduce_fused_body with binary levels from the start (first level global -> LDS): log2(E) levels of ONE
@@ -2365,41 +2144,7 @@ __device__ inline sc sg_nonce(int mode, const NonceSeed &seed, const uint8_t *st
     } else { lo = sc_zero(); hi = sc_zero(); }
     return sc_from_wide(lo, hi);
 }
-#if ROFL_KG(3)
-__global__ void __launch_bounds__(64) k_sigma_prove(int kind, u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *r1c, const sc *r2c,
-                                                    const uint8_t *existing, int mode, NonceSeed seed, const uint8_t *stream, u64 stream_scalars, u64 nonce_base,
-                                                    DMerlin init, const niels *tabB, const niels *tabBb, uint8_t *proofs, uint8_t *commits, u32 *status) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d) return;
-    bool has_R = kind != 2, has_sq = kind != 0;
-    u32 npts = 1 + (has_R ? 1 : 0) + (has_sq ? 1 : 0), nn = has_sq ? 3 : 2, clen = 32 * npts, plen = 32 * (npts + nn), sq_off = has_R ? 64 : 32;
-    float v = vals[i];
-    if (v != v) { atomicOr(status, 2u); return; }
-    sc m = sg_f32_to_sc(v, fp_bits, fp_frac);
-    sc r1 = load_sc_reduced(&r1c[i]), r2 = has_sq ? load_sc_reduced(&r2c[i]) : sc_zero();
-    sc nc[3];
-    SgNonceCache ncache; ncache.blk = ~0ULL;
-    for (u32 j = 0; j < nn; j++) nc[j] = sg_nonce(mode, seed, stream, stream_scalars, nonce_base + (u64)nn * i + j, ncache);   // m', r1' (, r2')
-    uint8_t *cm = commits + (size_t)clen * i, *pf = proofs + (size_t)plen * i;
-    gd L;
-    if (existing) { if (!sg_decode(L, existing + (size_t)32 * i)) { atomicOr(status, 4u); return; } for (int q = 0; q < 32; q++) cm[q] = existing[(size_t)32 * i + q]; }
-    else { L = gd_add(sg_fixed_mul(tabB, m), sg_fixed_mul(tabBb, r1)); sg_encode(cm, L); }
-    if (has_R) sg_encode(cm + 32, sg_fixed_mul(tabB, r1));
-    if (has_sq) { sc msq = sc_mul_plain(m, m); sg_encode(cm + sq_off, gd_add(sg_fixed_mul(tabB, msq), sg_fixed_mul(tabBb, r2))); }
-    sg_encode(pf, gd_add(sg_fixed_mul(tabB, nc[0]), sg_fixed_mul(tabBb, nc[1])));
-    if (has_R) sg_encode(pf + 32, sg_fixed_mul(tabB, nc[1]));
-    if (has_sq) sg_encode(pf + sq_off, gd_add(sg_var_mul(nc[0], L), sg_fixed_mul(tabBb, nc[2])));
-    DMerlin t = init;
-    sg_transcript(kind, t, cm, pf, has_R);
-    sc c = dm_challenge_scalar(t, "c", 1);
-    uint8_t *z = pf + clen;
-    sc_tobytes(z, sc_add(nc[0], sc_mul_plain(m, c)));
-    sc_tobytes(z + 32, sc_add(nc[1], sc_mul_plain(r1, c)));
-    if (has_sq) sc_tobytes(z + 64, sc_add(nc[2], sc_mul_plain(sc_sub(r2, sc_mul_plain(m, r1)), c)));
-}
-#endif
-
-// The same prover with ONE THREAD PER POINT instead of one per element (ROFL_SIGMA_SPLIT, the default): an element's 4-6 output points --
+// The per-element Sigma-proof prover with ONE THREAD PER POINT instead of one per element: an element's 4-6 output points --
 // R, c_sq, L', R', c_sq' (and L when no commitment is handed in) -- are independent of each other; each costs one or two fixed-base
 // multiplications and one encoding (a 254-step square-root chain), c_sq' a variable-base multiplication on top.  One thread doing all of them
 // is a chain of ~7 300 field multiplications in 256 VGPRs + 60 AGPRs + 1.8 KB of scratch at one wave per SIMD (3.3 ms for a vector of

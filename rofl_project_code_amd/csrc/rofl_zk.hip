@@ -1257,32 +1257,27 @@ int sigma_create(int kind, const float *values, size_t d, const uint8_t *r1, siz
         uint8_t *sb = C.stream_buf.as<uint8_t>(run_bytes + 64); C.up(sb, nonce->stream + run_off, run_bytes, C.stream);
         d_stream = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(sb) - run_off); ss = nonce_base + nn * d; }
     // algorithmic work per element AS BUILT: fixed-base multiplications of 32 mixed additions (radix-256 tables) -- L, L' and c_sq, c_sq' two each,
-    // R, R' one each -- and 2 * npts encodings (the one-thread-per-element form: 7 multiplications of 64 additions + a variable-base one of
-    // ~325 point operations); bytes as SURVEY 8(d): value + randomness in, commitments + proof out
-    static const bool split = !(knob("ROFL_SIGMA_SPLIT") && atoi(knob("ROFL_SIGMA_SPLIT")) == 0);
-    const uint64_t sg_muls = split ? (uint64_t)(4 + (kind != 2 ? 2 : 0) + (has_sq ? 4 : 0)) * 32 * 7 + 2 * npts * 265 : (uint64_t)7 * 64 * 7 + 325 * 8 + 2 * npts * 265;
+    // R, R' one each -- and 2 * npts encodings; bytes as SURVEY 8(d): value + randomness in, commitments + proof out
+    const uint64_t sg_muls = (uint64_t)(4 + (kind != 2 ? 2 : 0) + (has_sq ? 4 : 0)) * 32 * 7 + 2 * npts * 265;
     { KSpan ks_sigma(C.tm, C.stream, ROFL_TK_SIGMA, (uint64_t)d * sg_muls, (uint64_t)d * (4 + 32 * (has_sq ? 2 : 1) + clen + plen));
-      if (split) {      // one thread per point (blockIdx.y = slot), then transcripts + responses per element
-          SgSlots sl{}; auto add = [&](int id) { sl.id[sl.n++] = id; };
-          // c_sq' in its fixed-base form (SG_CSQP_F: the prover knows the opening of L); a commitment handed in is compared with m B + r1 Bb first
-          // (SG_LCMP) and the elements where it differs -- none, unless the caller's commitments are not the values' -- are redone by
-          // k_sigma_point_var exactly as the reference computes them
-          uint8_t *marks = nullptr;
-          if (has_sq && dex) marks = C.vspart.as<uint8_t>(d);      // (written for every element by the SG_LCMP slot: no clearing)
-          if (!dex) add(SG_L); else add(has_sq ? SG_LCMP : SG_LCHK);
-          if (has_sq) { add(SG_CSQP_F); add(SG_CSQ); }
-          add(SG_LP);
-          if (kind != 2) { add(SG_R); add(SG_RP); }
-          ROFL_LAUNCH(k_sigma_points, dim3((unsigned)((d + 63) / 64), (unsigned)sl.n), dim3(64), 0, C.stream, kind, sl, (u32)d, dv, fp_bits, fp_frac, dr1, dr2, dex,
-                      nonce->mode, seed, d_stream, ss, nonce_base, C.d_tabB8, C.d_tabBb8, dp, dc, status, marks);
-          if (marks)
-              ROFL_LAUNCH(k_sigma_point_var, dim3((unsigned)std::min<size_t>((d + 63) / 64, 256)), dim3(64), 0, C.stream, kind, (u32)d, dv, fp_bits, fp_frac, dr1, dr2, dex,      // (walks the marks: one block per CU at most)
-                          nonce->mode, seed, d_stream, ss, nonce_base, C.d_tabB, C.d_tabBb, dp, dc, status, marks);
-          ROFL_LAUNCH(k_sigma_finish, grid1(d), dim3(TPB), 0, C.stream, kind, (u32)d, dv, fp_bits, fp_frac, dr1, dr2, dex, nonce->mode, seed, d_stream, ss, nonce_base,
-                      sigma_init_state(kind), dp, dc, status);
-      } else
-      ROFL_LAUNCH(k_sigma_prove, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, C.stream, kind, (u32)d, dv, fp_bits, fp_frac, dr1, dr2, dex,
-                         nonce->mode, seed, d_stream, ss, nonce_base, sigma_init_state(kind), C.d_tabB, C.d_tabBb, dp, dc, status); }
+      // one thread per point (blockIdx.y = slot), then transcripts + responses per element
+      SgSlots sl{}; auto add = [&](int id) { sl.id[sl.n++] = id; };
+      // c_sq' in its fixed-base form (SG_CSQP_F: the prover knows the opening of L); a commitment handed in is compared with m B + r1 Bb first
+      // (SG_LCMP) and the elements where it differs -- none, unless the caller's commitments are not the values' -- are redone by
+      // k_sigma_point_var exactly as the reference computes them
+      uint8_t *marks = nullptr;
+      if (has_sq && dex) marks = C.vspart.as<uint8_t>(d);      // (written for every element by the SG_LCMP slot: no clearing)
+      if (!dex) add(SG_L); else add(has_sq ? SG_LCMP : SG_LCHK);
+      if (has_sq) { add(SG_CSQP_F); add(SG_CSQ); }
+      add(SG_LP);
+      if (kind != 2) { add(SG_R); add(SG_RP); }
+      ROFL_LAUNCH(k_sigma_points, dim3((unsigned)((d + 63) / 64), (unsigned)sl.n), dim3(64), 0, C.stream, kind, sl, (u32)d, dv, fp_bits, fp_frac, dr1, dr2, dex,
+                  nonce->mode, seed, d_stream, ss, nonce_base, C.d_tabB8, C.d_tabBb8, dp, dc, status, marks);
+      if (marks)
+          ROFL_LAUNCH(k_sigma_point_var, dim3((unsigned)std::min<size_t>((d + 63) / 64, 256)), dim3(64), 0, C.stream, kind, (u32)d, dv, fp_bits, fp_frac, dr1, dr2, dex,      // (walks the marks: one block per CU at most)
+                      nonce->mode, seed, d_stream, ss, nonce_base, C.d_tabB, C.d_tabBb, dp, dc, status, marks);
+      ROFL_LAUNCH(k_sigma_finish, grid1(d), dim3(TPB), 0, C.stream, kind, (u32)d, dv, fp_bits, fp_frac, dr1, dr2, dex, nonce->mode, seed, d_stream, ss, nonce_base,
+                  sigma_init_state(kind), dp, dc, status); }
     u32 st = 0;
     C.down(proofs_out, dp, d * plen, C.stream);
     C.down(commits_out, dc, d * clen, C.stream);
@@ -1711,7 +1706,7 @@ int sigma_create_any(int kind, const float *values, size_t d, const uint8_t *r1,
             return sigma_create(kind, values + e0, cnt, r1 + 32 * e0, cnt, r2 ? r2 + 32 * e0 : nullptr, existing ? existing + 32 * e0 : nullptr, fp_bits, fp_frac, nonce,
                                 proofs_out + e0 * plen, commits_out + e0 * clen, e0, d); }))
         return rc;
-    // the unsplit call's outcome: the NaN check comes before anything is decoded (k_sigma_finish / k_sigma_prove report 2 before 4 per element; across
+    // the unsplit call's outcome: the NaN check comes before anything is decoded (k_sigma_finish reports 2 before 4 per element; across
     // elements the call reports NON_FINITE first, sigma_create)
     for (size_t k = 0; k < rcs.size(); k++) if (rcs[k] >= ROFL_HIP_ERROR || rcs[k] == ROFL_BAD_PARAM || rcs[k] == ROFL_NONCE_SHORT) return fail(rcs[k], errs[k]);
     for (size_t k = 0; k < rcs.size(); k++) if (rcs[k] == ROFL_NON_FINITE) return fail(rcs[k], errs[k]);

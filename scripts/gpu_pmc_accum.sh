@@ -13,7 +13,7 @@ acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = colle
 for f in glob.glob("gpurun_out/pmc_$tag/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"].split("(")[0].replace("rofl::", "")
-        if k not in ("k_msm_accumulate", "k_fold_gens_tab", "k_fold_gens", "k_msm_scatter_lds"): continue
+        if k not in ("k_msm_accumulate", "k_fold_gens_w", "k_fold_gens", "k_msm_scatter_lds"): continue
         acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
 for k, v in acc.items(): print(k, {c: "%.4g" % x for c, x in v.items()})
 PY

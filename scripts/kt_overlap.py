@@ -15,7 +15,7 @@ name = lambda r: r["Kernel_Name"].split("(")[0].replace("rofl::", "")
 ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name(r), r.get("Queue_Id", "?"), int(r.get("Grid_Size_X") or 0) * int(r.get("Grid_Size_Y") or 1)) for r in rows), key=lambda e: e[0])
 t_lo = ev[0][0] + skip * (ev[-1][1] - ev[0][0])
 ev = [e for e in ev if e[0] >= t_lo]
-heavy = [e for e in ev if e[2] in ("k_msm_accumulate_fb", "k_fold_gens_w", "k_fold_gens4", "k_fold_gens", "k_msm_accumulate_gen", "k_fold_gens_tab")]
+heavy = [e for e in ev if e[2] in ("k_msm_accumulate_fb", "k_fold_gens_w", "k_fold_gens4", "k_fold_gens", "k_msm_accumulate_gen")]
 hs = [e[0] for e in heavy]
 
 

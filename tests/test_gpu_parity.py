@@ -623,17 +623,18 @@ def test_bsgs_discrete_log(R):
     {"ROFL_MSM_FB_MIN": "64", "ROFL_MSM_LDS_MIN": "32"},                 # fixed-base tables + LDS scatter at every size
     {"ROFL_MSM_FB": "0", "ROFL_MSM_LDS_MIN": "32"},                      # generic windows through the LDS scatter
     {"ROFL_MSM_FB_MIN": "64", "ROFL_MSM_LDS": "0"},                      # fixed-base through the per-item slot scatter
-    {"ROFL_MSM_SLOTS": "0", "ROFL_MSM_LR": "0"},                         # two-pass counting sort, separate L / R arrays
+    {"ROFL_MSM_SLOTS": "0"},                                             # two-pass counting sort
     {"ROFL_VERIFY_BATCH": "0", "ROFL_FOLD_PB": "64", "ROFL_FOLD_W": "4", "ROFL_LANES": "1"},
     {"ROFL_FOLD_PB": "16", "ROFL_FOLD_W": "5", "ROFL_FOLD_T1": "2", "ROFL_FOLD_MIN": "16"},
     {"ROFL_GENS_BUDGET_MB": "1", "ROFL_LANES": "2"},                      # every new (n, m) evicts the previous tables
-    {"ROFL_FOLD_WNAF": "4", "ROFL_FOLD_MIN": "16"},                        # later folds over odd multiples of their sources (event-list kernel, side-stream table build)
-    {"ROFL_FOLD_WNAF": "5", "ROFL_FOLD_T": "1", "ROFL_FOLD_MIN": "16"},
-    {"ROFL_FOLD_TAB_EV": "0"},                                            # the first fold through the digit-scanning kernel (k_fold_gens_tab) instead of the event list
+    {"ROFL_FOLD_MIN": "16"},                                              # folds down to 16 generators per chunk
+    {"ROFL_FOLD_T": "1", "ROFL_FOLD_MIN": "16"},                          # a fold after every round: two sources, the generic fold kernel (k_fold_gens)
+    {"ROFL_FOLD_PB": "16", "ROFL_FOLD_W": "10", "ROFL_FOLD_MIN": "16"},    # 16-bit pieces at the widest NAF: the table is capped at width 9 (an event numbers its slice in 12 bits)
     {"ROFL_GENS_RESERVE_MB": "400000"},                                   # no big table may be allocated (reserve > HBM): fold tables of 4 GB and more are narrowed until they fit
     {"ROFL_MSM_DEV_HORNER_MIN": "1", "ROFL_MSM_FB": "0"},                 # every MSM finishes its Horner chains on the device
     {"ROFL_MSM_DEV_HORNER_MIN": "1", "ROFL_MSM_FB_MIN": "64"},
     {"ROFL_MSM_SMALL_MAX": "0"},                                          # the general pipeline at the sizes the fused small-MSM launch normally takes
+    {"ROFL_DBG_IDX_MASK": "0xff", "ROFL_DBG_SCATTER": "2", "ROFL_MSM_LR": "0", "ROFL_IPP_FUSED": "0", "ROFL_FOLD_TAB_EV": "0", "ROFL_FOLD_WNAF": "4"},      # retired names at their old non-default values: no longer read
 ])
 def test_msm_variants_small_sizes(R, env):
     import subprocess, sys

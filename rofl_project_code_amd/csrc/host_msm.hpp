@@ -43,6 +43,7 @@ struct MsmJob {
     MsmWs *ws = nullptr; size_t np = 0, nq = 0, n = 0, PW = 0; MsmPlan P{}; MsmKind kind = MsmKind::CountSort; bool lr = false, two = false, dev_horner = false;
     bool host8 = false;      // dev_horner launches whose chains come back to the host, eight per SIMD stream (k_msm_wsum + h8::horner8)
     u32 sets = 0, cap = 0;
+    u32 cap_bin = 0, tile = 0, fused_t = 0, acc_bal = 0;      // for the ROFL_TRACE line only: coarse-bin capacity (two-level sort), LDS scatter tile, block of k_msm_reduce_fused, ROFL_ACC_BALANCE
     u32 small_group = 1;     // fused small launch: windows of a problem per block (4 at c = 7 with thousands of bucket arrays: n_partition = 64)
     bool fb() const { return kind == MsmKind::FixedBase; }
 };
@@ -105,7 +106,7 @@ bool msm_plan_job(Ctx &C, MsmJob &J, const MsmOpt &opt, const MsmAllow &al, MsmM
             if (!fits) { tl = Msm2L{512, fb0 - 1, 24, 0, 72}; fits = size_bins(); }
             if (!fits || per_side < 8192) two = false;
         }
-        J.two = two;
+        J.two = two; J.cap_bin = two ? tl.cap_bin : 0u;
         if (!two && (size_t)J.PW * J.P.B * J.cap * 4 > ((size_t)8 << 30)) return false;      // slot array too large: next variant
         return true;
     }
@@ -141,6 +142,7 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
     static const u32 acc_balance = knob("ROFL_ACC_BALANCE") ? (atoi(knob("ROFL_ACC_BALANCE")) ? 1u : 0u) : 1u;   // equal-work blocks in k_msm_accumulate (0 = plain descending order)
     MsmJob J; J.ws = &W; J.np = probs.size(); J.n = n; J.lr = opt.lr_nh != 0; J.nq = J.lr ? J.np / 2 : J.np;
     const size_t np = J.np, nq = J.nq; const bool lr = J.lr;
+    J.acc_bal = acc_balance;
     MsmMap mm{}; u32 small_cap = 0; Msm2L tl{};
     while (!msm_plan_job(C, J, opt, al, mm, small_cap, tl)) {      // a variant whose structures would not fit: the next one
         if (al.fb && opt.fb_wtab && C.msm_slots) al.fb = false; else al.slots = false;
@@ -283,6 +285,7 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
             u32 wps = fb ? mm.fb_wps : 1;
             while (tile > 1024 && ((size_t)tile * wps > (size_t)C.msm_lds_tile || (size_t)((n_side + tile - 1) / tile) * nq * (lr ? 2 : 1) * per_q < 256)) tile /= 2;
             dim3 grid((n_side + tile - 1) / tile, (u32)(nq * (lr ? 2 : 1) * per_q));
+            J.tile = tile;
             uint64_t items = terms * P.W;
             KSpan ks(C.tm, st, ROFL_TK_MSM_SCATTER, 0, terms * 32 + items * 4);
             ROFL_LAUNCH(k_msm_scatter_lds, grid, dim3(1024), (size_t)P.B * 4, st, n_side, tile, mw, mm, d_probs, cnt, slots, cap, ovf_count, ovf, MSM_OVF_MAX);
@@ -335,10 +338,11 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
         if (J.dev_horner) { S_fin = W.S[lv & 1].as<ge>(PW); C_fin = W.Cacc[lv & 1].as<ge>(PW * (size_t)nb_final); }
         // block size = first-level work items (small bucket arrays, c = 7: 32 items -- a 256-thread block would idle 7 of its 8
         // waves and, at 163 VGPRs, hold a whole CU: thousands of such blocks (n_partition = 64) ran 18 deep per CU)
-        static const u32 red_fused_max = knob("ROFL_RED_FUSED_T") ? (u32)atoi(knob("ROFL_RED_FUSED_T")) : 768u;
+        static const u32 red_fused_max = knob("ROFL_RED_FUSED_T") ? (u32)std::max(64, atoi(knob("ROFL_RED_FUSED_T"))) : 768u;      // (below one wave -- 0, a typo -- the launch would have no threads)
         // (a fixed-base array enters with E = 512, nb = 6: 640 first-level items -- on 512 threads that was two passes of a seven-addition chain)
         u32 fused_items = (E / 8) * (4 + nb), fused_threads = fused_items > 512 ? (fused_items > 640 ? 768 : 640) : fused_items > 256 ? 512 : fused_items > 128 ? 256 : fused_items > 64 ? 128 : 64;
         if (fused_threads > red_fused_max) fused_threads = red_fused_max;
+        J.fused_t = fused_threads;
         size_t lds = ((size_t)(E / 8) * (1 + nb + 3) + (size_t)(E / 16) * (1 + nb + 4) + 1) * sizeof(ge);
         ROFL_LAUNCH(k_msm_reduce_fused, dim3((unsigned)PW), dim3(fused_threads), lds, st, E, nb, S_in, C_in, S_fin, C_fin, nb_final);
     }
@@ -363,7 +367,9 @@ bool msm_retry(const MsmJob &J, MsmAllow &al) {
 }
 bool msm_retry_inner(const MsmJob &J, MsmAllow &al) {
     u32 flag = *J.ws->h_ovf.as<u32>(4);
-    if (knob("ROFL_TRACE") && J.kind != MsmKind::CountSort) fprintf(stderr, "[rofl] msm np=%zu n=%zu c=%u cap=%u fb=%u lr=%d overflow=%u\n", J.np, J.n, J.P.c, J.cap, J.fb() ? J.sets : 0u, (int)J.lr, flag);
+    if (knob("ROFL_TRACE") && J.kind != MsmKind::CountSort)
+        fprintf(stderr, "[rofl] msm np=%zu n=%zu c=%u cap=%u fb=%u lr=%d overflow=%u kind=%s two=%d bin=%u tile=%u group=%u fused_t=%u bal=%u horner=%s\n", J.np, J.n, J.P.c, J.cap, J.fb() ? J.sets : 0u, (int)J.lr, flag,
+                J.fb() ? "fb" : J.kind == MsmKind::Small ? "small" : "slots", (int)J.two, J.cap_bin, J.tile, J.kind == MsmKind::Small ? J.small_group : 0u, J.fused_t, J.acc_bal, J.host8 ? "host8" : J.dev_horner ? "dev" : "host");
     if (J.kind == MsmKind::Small) { if (flag) { al.small = false; return true; } return false; }      // a bucket list overflowed: repeat through the general pipeline
     if (J.two) { if (flag) { al.two = false; return true; } return false; }                              // a coarse bin overflowed (skewed scalars): repeat on the slot path
     if (J.kind == MsmKind::CountSort) return false;
@@ -379,7 +385,9 @@ void msm_finish(Ctx &C, const MsmJob &J, std::vector<ge5> &results, const MsmOpt
     double t0 = now_ms();
     results.resize(np);
     std::vector<double> cpu_each(np, 0.0);
+    const char *fin = "host";      // (ROFL_TRACE: which of the finishers below ran)
     if (J.host8) {
+        fin = "host8";
         // h holds one point per (problem, window): eight problems per task run their 253-step chains in the lanes of one AVX-512 stream
         u32 pos[64];
         for (u32 w = 0; w < P.W; w++) pos[w] = w + 1 == P.W ? 253 - P.c : (w < P.wide ? w * P.c : P.wide * P.c + (w - P.wide) * (P.c - 1));      // msm_window's layout
@@ -394,6 +402,7 @@ void msm_finish(Ctx &C, const MsmJob &J, std::vector<ge5> &results, const MsmOpt
             cpu_each[p0] = now_ms() - tc0;
         });
     } else if (J.dev_horner) {
+        fin = "dev";
         if (opt.post) C.pool->run(np, [&](size_t p) { results[p] = h51::from_ge_loose(h[p]); opt.post(p); });
         else for (size_t p = 0; p < np; p++) results[p] = h51::from_ge_loose(h[p]);
     } else if (J.fb()) {
@@ -415,6 +424,7 @@ void msm_finish(Ctx &C, const MsmJob &J, std::vector<ge5> &results, const MsmOpt
             // "windows" that share positions: sum_l 2^l sum_s D[s][l] + sum_s S[s]), eight encodings per stream and the four challenge inversions
             // of the task's chunks behind one inversion, as the generic launches do.  (Rounds 3-4 ran eight scalar chains on eight pool threads
             // here below 32 problems: ~0.1 ms per hop against ~0.05.)
+            fin = "fb8";
             const int Wn = (int)(sets * (nb + 1));
             u32 pos[64];
             for (u32 s = 0; s < sets; s++) pos[s] = 0;
@@ -433,11 +443,13 @@ void msm_finish(Ctx &C, const MsmJob &J, std::vector<ge5> &results, const MsmOpt
                 opt.post8(p0, cnt);
                 cpu_each[p0] = now_ms() - tc0;
             });
-        } else
-        C.pool->run(np, [&](size_t p) {
-            double tc0 = now_ms();
-            fb_one(p); if (opt.post) opt.post(p); cpu_each[p] = now_ms() - tc0;
-        });
+        } else {
+            fin = "fb";
+            C.pool->run(np, [&](size_t p) {
+                double tc0 = now_ms();
+                fb_one(p); if (opt.post) opt.post(p); cpu_each[p] = now_ms() - tc0;
+            });
+        }
     } else {
         // One 253-step chain per problem: sum_w 2^(pos_w) (S_w + sum_l 2^l D_(w,l)).  With few problems (the IPP rounds of a client with four
         // chunks: eight) the chain is split over TWO pool threads: the upper windows (about three eighths of them: that part also carries the
@@ -460,6 +472,7 @@ void msm_finish(Ctx &C, const MsmJob &J, std::vector<ge5> &results, const MsmOpt
             return acc;
         };
         const bool split = np * 2 <= 32 && P.W >= 8;
+        if (split) fin = "split";
         if (!split) {
             C.pool->run(np, [&](size_t p) {
                 double tc0 = now_ms();
@@ -479,6 +492,7 @@ void msm_finish(Ctx &C, const MsmJob &J, std::vector<ge5> &results, const MsmOpt
             });
         }
     }
+    if (knob("ROFL_TRACE")) fprintf(stderr, "[rofl] msm-finish np=%zu c=%u finish=%s\n", np, P.c, fin);
     C.tm.t.host_ms += now_ms() - t0;
     { double w = now_ms() - t0; C.hs.horner_wall += w; C.hs.max_horner = std::max(C.hs.max_horner, w); double mx = 0; for (double v : cpu_each) mx = std::max(mx, v); C.hs.horner_cpu += mx; C.hs.max_task = std::max(C.hs.max_task, mx); } C.hs.n++;
 }

@@ -375,6 +375,7 @@ void prove_chunks(Ctx &C, const char *label, size_t P, size_t n, size_t m, const
                 for (u32 k = 1; k <= K; k++) if (bounds[k] < bounds[k - 1]) bounds[k] = bounds[k - 1];
                 for (u32 k = 0; k <= FOLD_MAXSEG; k++) seg.lo[k] = bounds[k <= K ? k : K];
                 dim3 grid((unsigned)((n_new + 63) / 64), (u32)(2 * P)), block(64, K);
+                if (knob("ROFL_TRACE")) fprintf(stderr, "[rofl] fold chunks=%zu n_g=%zu n_new=%zu nsrc=%u tab=%d pb=%u w=%u K=%u top=%d\n", P, n_g, n_new, nsrc, (int)use_tab, fc.pb, fc.w, K, top);
                 uint64_t nz = 0;
                 if (C.tm.enabled) { size_t tot_d = 2 * P * nsrc * dstride; for (size_t q = 0; q < tot_d; q++) nz += use_tab ? h_dig16[q] != 0 : h_dig[q] != 0; }
                 // algorithmic work per output: the non-zero digits of its problem (mixed additions) and ONE chain of top+1 doublings

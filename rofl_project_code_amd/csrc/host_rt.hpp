@@ -55,9 +55,9 @@ static const Knob KNOBS[] = {
     {"ROFL_MSM_T13", "8192", "generic MSMs from this many terms on use 13-bit windows"},
     {"ROFL_MSM_T10", "512 / 2048", "generic MSMs from this many terms on use 10-bit windows (7-bit below, 4-bit below 64); default 2048 for launches with >= 32 problems"},
     {"ROFL_MSM_C", "0", "window width of every generic MSM (4, 7, 10, 13, 16; 0 = by size)"},
-    {"ROFL_RED_FUSED_T", "768", "largest block of k_msm_reduce_fused"},
+    {"ROFL_RED_FUSED_T", "768", "largest block of k_msm_reduce_fused (64 at least: smaller values are raised to one wave)"},
     {"ROFL_ACC_BALANCE", "1", "0 = accumulate blocks in plain descending-load order instead of equal-work blocks"},
-    {"ROFL_TRACE", "0", "1 = one line per MSM on stderr, 2 = per-phase host timeline of every proof / verification"},
+    {"ROFL_TRACE", "0", "1 = one line per MSM, window combination, generator fold, table eviction and verifier hashing pass on stderr (which variant ran), 2 = per-phase host timeline of every proof / verification"},
     {"ROFL_DBG_SMALL_TIMELINE", "", "set: per-phase block timings of every fused small-MSM launch on stderr (synchronises; debugging)"},
     {"ROFL_DBG_ACC_TIMELINE", "", "file to append per-wave start / end / placement records of every fixed-base accumulate launch to"},
     {"ROFL_FEMUL_LDS", "0", "rofl_bench_femul: dynamic LDS per block (pins the micro-benchmark's occupancy)"},
@@ -276,6 +276,7 @@ public:
         for (int i = 1; i < nthreads; i++) workers.emplace_back([this, i] { loop(i); });
     }
     ~HostPool() { stop.store(true, std::memory_order_seq_cst); for (size_t w = 1; w <= workers.size(); w++) wake((int)w); for (auto &t : workers) t.join(); }
+    double spin() const { return spin_us; }
     // called right before the caller starts a wait it expects to last `us` microseconds (0 = unknown): polling workers nap through it
     void expect_gap(double us) { gap_us.store(us, std::memory_order_relaxed); hint_seq.fetch_add(1, std::memory_order_release); }
     void run(size_t n, std::function<void(size_t)> f) {
@@ -501,6 +502,7 @@ struct Ctx {
     Ctx *parent = nullptr;
     std::vector<Ctx *> sibs;      // additional lanes
     static constexpr int kMaxLanes = 16;
+    int host_threads = 0;      // threads of this lane's pool (for the ROFL_TRACE line)
     int nlanes = 3;      // ROFL_LANES: number of calls that can be in flight on this device (1..kMaxLanes)
     std::mutex init_mu, gens_mu;      // primary lane only: one-time initialisation; generator-table cache
     std::atomic<int> active_calls{0};  // primary lane only: calls currently holding a lane
@@ -629,7 +631,8 @@ struct Ctx {
             int nt = std::min(16, std::max(2, usable_cores()));
             if (const char *e = knob("ROFL_HOST_THREADS")) nt = atoi(e);
             if (nt < 1) nt = 1; if (nt > 64) nt = 64;
-            pool.reset(new HostPool(nt, &g_calls_in_flight)); }
+            pool.reset(new HostPool(nt, &g_calls_in_flight));
+            host_threads = nt; }
         if (const char *e = knob("ROFL_FOLD_T1")) { int v = atoi(e); if (v >= 1 && v <= 6) fold_t1 = v; }
         if (const char *e = knob("ROFL_FOLD_TAB")) fold_tab = atoi(e) != 0;
         if (const char *e = knob("ROFL_GENS_BUDGET_MB")) { long v = atol(e); if (v >= 1) gens_budget = (size_t)v << 20; }
@@ -643,6 +646,7 @@ struct Ctx {
             if (w != v) fprintf(stderr, "librofl_zk: ROFL_LANES=%d is outside 1..%d, using %d\n", v, kMaxLanes, w);
             nlanes = w;
         }
+        if (knob("ROFL_TRACE")) fprintf(stderr, "[rofl] host threads=%d spin_us=%g keccak_zmm=%d lanes=%d\n", host_threads, pool->spin(), (int)keccak_zmm_flag(), nlanes);
         inited = true;
         for (int i = 1; i < nlanes; i++) { Ctx *s = new Ctx(); s->init_lane(*this); sibs.push_back(s); }
     }
@@ -781,6 +785,7 @@ void gens_evict(Ctx &P0, size_t keep_bytes, const GensEntry *spare) {
         for (auto it = P0.gens.begin(); it != P0.gens.end(); ++it)
             if (it->second.get() != spare && it->second->users == 0 && (victim == P0.gens.end() || it->second->tick < victim->second->tick)) victim = it;
         if (victim == P0.gens.end()) return;       // everything left is in use
+        if (knob("ROFL_TRACE")) fprintf(stderr, "[rofl] gens-evict n=%zu m=%zu mb=%zu keep_mb=%zu\n", victim->first.first, victim->first.second, victim->second->bytes >> 20, keep_bytes >> 20);
         gens_free_entry(victim->second.get());
         P0.gens.erase(victim);
     }

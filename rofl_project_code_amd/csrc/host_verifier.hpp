@@ -174,6 +174,7 @@ int verify_chunks(Ctx &C, const char *label, size_t gens_capacity, size_t P, siz
     auto hash_range = [&](size_t c0, size_t c1) {
         if (c1 <= c0) return;
         const size_t cnt = c1 - c0, per = (x8_on && cnt >= 32) ? 8 : 1;
+        if (knob("ROFL_TRACE")) fprintf(stderr, "[rofl] verify-hash chunks=%zu per=%zu\n", cnt, per);
         C.pool->run((cnt + per - 1) / per, [&](size_t b) {
             Merlin tr[8] = {Merlin(label, strlen(label)), Merlin(label, strlen(label)), Merlin(label, strlen(label)), Merlin(label, strlen(label)),
                             Merlin(label, strlen(label)), Merlin(label, strlen(label)), Merlin(label, strlen(label)), Merlin(label, strlen(label))};

@@ -189,6 +189,22 @@ def msm(scalars32, points32):
     return out
 
 
+def extreme_scalar_cases(rng, n):
+    """{family: n scalars} the proof path never produces, for the Pippenger pipeline: random, heavy bucket skew (all equal; all l - 1),
+    scalars in [2^252, l) (the split top-window digit), and small ones including zero.  (Draws from `rng`: random first, then all_equal.)"""
+    L = L_ORDER
+    def sc(v):
+        return np.frombuffer((v % L).to_bytes(32, "little"), np.uint8)
+    return {
+        "random": rand_scalars(rng, n),
+        "all_equal": np.tile(sc(int.from_bytes(rng.integers(0, 256, 32, dtype=np.uint8).tobytes(), "little")), (n, 1)),
+        "top_range": np.stack([sc(L - 1 - i) for i in range(n)]),                    # >= 2^252
+        "two_pow_252": np.stack([sc((1 << 252) + i * 12345) for i in range(n)]),
+        "small": np.stack([sc(i) for i in range(n)]),                                 # includes 0
+        "minus_one": np.tile(sc(L - 1), (n, 1)),
+    }
+
+
 def sigma_create(kind, values, r1, r2, fp_bits, fp_frac, seed=None, stream=None, existing=None):
     v = np.ascontiguousarray(values, dtype=np.float32)
     r1 = np.ascontiguousarray(r1, dtype=np.uint8).reshape(-1, 32)

@@ -340,17 +340,7 @@ def test_msm_extreme_scalars(R, n):
     two-pass fallback), scalars in [2^252, l) (split top-window digit), zeros, small and all-ones scalars."""
     rng = np.random.default_rng(n)
     pts = orc.commit_vec(orc.rand_scalars(rng, n), None)            # n random valid points
-    L = orc.L_ORDER
-    def sc(v):
-        return np.frombuffer((v % L).to_bytes(32, "little"), np.uint8)
-    cases = {
-        "random": orc.rand_scalars(rng, n),
-        "all_equal": np.tile(sc(int.from_bytes(rng.integers(0, 256, 32, dtype=np.uint8).tobytes(), "little")), (n, 1)),
-        "top_range": np.stack([sc(L - 1 - i) for i in range(n)]),                    # >= 2^252
-        "two_pow_252": np.stack([sc((1 << 252) + i * 12345) for i in range(n)]),
-        "small": np.stack([sc(i) for i in range(n)]),                                 # includes 0
-        "minus_one": np.tile(sc(L - 1), (n, 1)),
-    }
+    cases = orc.extreme_scalar_cases(rng, n)
     for name, k in cases.items():
         k = np.ascontiguousarray(k)
         assert (_gpu_msm(R, k, pts) == orc.msm(k, pts)).all(), name

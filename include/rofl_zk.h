@@ -237,6 +237,24 @@ int rofl_verify_compressed_randproof(const uint8_t proof[128], const uint8_t *pa
  * problems per client each).  With rofl_set_option("devices", mask) the clients are dealt
  * round-robin to the listed devices. */
 int rofl_verify_compressed_randproof_batch(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out);
+/* client side: the compressed randomness proofs of n_clients clients of one process (client.rs:265-266 hosts its clients as tasks of one
+ * process) in one launch sequence -- groups of at most sixteen clients, two host waits per group instead of two per client.
+ * proofs_out[i] (128 bytes) and pairs_out[i] (d * 64 bytes, host memory) are byte for byte what rofl_create_compressed_randproof returns
+ * for (values[i], r32[i], existing32[i], nonces[i]); the nonces m', r' sit at index 0 and 1 of client i's own stream or seed.
+ * values[i] (d floats), r32[i] (d scalars) and existing32[i] (d commitments to complete; the array or any entry may be NULL) are host or
+ * device memory, as in the single call.  rc_out[i] is client i's own outcome: 0, 10 (a non-finite value), 5 (an existing32[i] entry that
+ * does not decode; a client with both reports 10, as the single call does) or 12 (a mode-0 stream of fewer than 2 scalars, decided before
+ * any device work) -- a client that fails is left out, its outputs are unspecified, and the others are still proved.  The return value is
+ * non-zero only for errors of the whole call: a HIP error, or 11 (bad parameter) before the device is touched -- d >= 900 000, invalid
+ * (fp_bits, fp_frac), more than 65 535 clients, with n_clients > 0 a null nonces, proofs_out or rc_out or a null proofs_out[i], and with
+ * d > 0 as well a null values, r32 or pairs_out or a null entry of one of them.  n_clients = 0 returns 0; d = 0 gives every client
+ * C' = commit(m', r'), Z = (m', r') as the single call does.  With rofl_set_option("devices", mask) the clients are dealt round-robin to
+ * the listed devices. */
+int rofl_create_compressed_randproof_batch(size_t n_clients, const float *const *values, size_t d,
+                                           const uint8_t *const *r32, const uint8_t *const *existing32 /* NULL, or entries NULL */,
+                                           unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonces /* [n_clients] */,
+                                           uint8_t *const *proofs_out /* 128 B each */, uint8_t *const *pairs_out /* d*64 B each */,
+                                           int *rc_out /* [n_clients] */);
 
 /* ---- pedersen_ops (pedersen_ops.rs) ---- */
 int rofl_commit_vec(const uint8_t *values32, const uint8_t *blindings32 /* NULL: commit_no_blinding_vec */,

@@ -37,6 +37,43 @@ impl CompressedRandProof {
         -> Result<(CompressedRandProof, CompressedRandProofCommitments), ProofError> {
         prove(m_vec, Some(&m_com), &r_vec)
     }
+    /// `helper_prove` / `helper_prove_existing` for the clients of one process (client.rs:265-266 runs them as tasks of one process):
+    /// ONE rofl_create_compressed_randproof_batch call, every client's result what its own helper call returns.  m_com[i] = None: no
+    /// commitments to complete for client i.  A client whose inputs the library refuses (a non-finite value, an undecodable commitment)
+    /// panics as in the single helper.
+    pub fn helper_prove_batch(m_vecs: &[&Vec<f32>], m_coms: &[Option<&Vec<RistrettoPoint>>], r_vecs: &[&Vec<Scalar>])
+        -> Result<Vec<(CompressedRandProof, CompressedRandProofCommitments)>, ProofError> {
+        let n = m_vecs.len();
+        if n == 0 { return Ok(Vec::new()); }
+        let d = m_vecs[0].len();
+        if r_vecs.len() != n || m_coms.len() != n { return Err(ProofError::WrongNumBlindingFactors); }
+        for i in 0..n {
+            if m_vecs[i].len() != d || r_vecs[i].len() != d || m_coms[i].map_or(false, |c| c.len() != d) { return Err(ProofError::WrongNumBlindingFactors); }
+        }
+        let r: Vec<Vec<u8>> = r_vecs.iter().map(|v| scalars_to_bytes(v)).collect();
+        let ex: Vec<Option<Vec<u8>>> = m_coms.iter().map(|c| c.map(|v| points_to_bytes(v))).collect();
+        let mut proofs: Vec<Vec<u8>> = (0..n).map(|_| vec![0u8; CompressedRandProof::serialized_size()]).collect();
+        let mut pairs: Vec<Vec<u8>> = (0..n).map(|_| vec![0u8; d * PAIR_LEN]).collect();
+        let nonces: Vec<RoflNonce> = (0..n).map(|_| fresh_nonce()).collect();
+        let vp: Vec<*const f32> = m_vecs.iter().map(|v| v.as_ptr()).collect();
+        let rp: Vec<*const u8> = r.iter().map(|v| v.as_ptr()).collect();
+        let ep: Vec<*const u8> = ex.iter().map(|e| e.as_ref().map_or(std::ptr::null(), |v| v.as_ptr())).collect();
+        let pp: Vec<*mut u8> = proofs.iter_mut().map(|v| v.as_mut_ptr()).collect();
+        let cp: Vec<*mut u8> = pairs.iter_mut().map(|v| v.as_mut_ptr()).collect();
+        let mut rcs: Vec<std::os::raw::c_int> = vec![0; n];
+        let rc = unsafe {
+            rofl_create_compressed_randproof_batch(n, vp.as_ptr(), d, rp.as_ptr(), ep.as_ptr(), fp_bits(), fp_frac(), nonces.as_ptr(),
+                                                   pp.as_ptr(), cp.as_ptr(), rcs.as_mut_ptr())
+        };
+        if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+        let mut out = Vec::with_capacity(n);
+        for i in 0..n {
+            if rcs[i] != ROFL_OK { panic!("rofl_zk: client {} of the batch: error {}", i, rcs[i]); }
+            let c_vec: Vec<ElGamalPair> = pairs[i].chunks(PAIR_LEN).map(|c| ElGamalPair::from_bytes(c).unwrap()).collect();
+            out.push((CompressedRandProof::from_bytes(&proofs[i])?, CompressedRandProofCommitments { c_vec }));
+        }
+        Ok(out)
+    }
     pub fn helper_verify(&self, c_vec: Vec<ElGamalPair>) -> Result<(), ProofError> {
         let pairs: Vec<u8> = c_vec.iter().flat_map(|c| c.to_bytes()).collect();
         let proof = self.to_bytes();

@@ -123,6 +123,12 @@ extern "C" {
     /// exactly the single call's (a malformed member is 0, the others are still verified)
     pub fn rofl_verify_compressed_randproof_batch(n_clients: usize, proofs: *const *const u8, pairs: *const *const u8, d: usize,
         ok_out: *mut c_int) -> c_int;
+    /// the compressed randomness proofs of the clients of one process in one launch sequence; proofs_out[i] / pairs_out[i] are the single
+    /// call's bytes for client i, rc_out[i] its own outcome (0, 10, 5, 12: it is left out, the others are still proved); existing32 or any
+    /// of its entries may be null
+    pub fn rofl_create_compressed_randproof_batch(n_clients: usize, values: *const *const c_float, d: usize, r32: *const *const u8,
+        existing32: *const *const u8, fp_bits: c_uint, fp_frac: c_uint, nonces: *const RoflNonce, proofs_out: *const *mut u8,
+        pairs_out: *const *mut u8, rc_out: *mut c_int) -> c_int;
     pub fn rofl_sum_points(points: *const u8, d: usize, stride: usize, out32: *mut u8) -> c_int;
     pub fn rofl_f32_to_scalar_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out32: *mut u8) -> c_int;
     pub fn rofl_scalar_to_f32_vec(in32: *const u8, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;

@@ -697,6 +697,49 @@ class compressed_rand_proof:
         return compressed_rand_proof.helper_prove(values, r_vec, nonce=nonce, existing=m_com, fp=fp)
 
     @staticmethod
+    def helper_prove_batch(values_list, r_list, nonces=None, existing_list=None, fp=None):
+        """rofl_create_compressed_randproof_batch: helper_prove / helper_prove_existing for several clients (same d) of one process as one
+        launch sequence.  existing_list (optional) holds per client the commitments to complete, or None.  -> list of (proof, pairs) per
+        client, byte-identical to the per-client call with the same nonce; a client whose own inputs are rejected (NaN, an undecodable
+        commitment, a short nonce stream) gets a RoflError instance in its place, the others are proved.  values / r / existing of a
+        client may be numpy arrays or torch tensors on the library's GPU."""
+        nc = len(values_list)
+        if nc == 0:
+            return []
+        if existing_list is None:
+            existing_list = [None] * nc
+        if len(r_list) != nc or len(existing_list) != nc or (nonces is not None and len(nonces) != nc):
+            raise ValueError("values_list, r_list, existing_list and nonces must have one entry per client")
+        keep, vptrs, rptrs, eptrs = [], [], [], []
+        d = None
+
+        def arg(x, dtype, row):      # (pointer, rows) of one array of a client, wherever it lives
+            if _is_dev(x):
+                p, n = _dev_arg(x, np.dtype(dtype).itemsize, row)
+                return p.value, n
+            a = np.ascontiguousarray(x, dtype=np.float32) if dtype == np.float32 else _u8(x)
+            keep.append(a)
+            return a.ctypes.data, (a.size if dtype == np.float32 else (a.shape[0] if a.size else 0))
+        for v, r, ex in zip(values_list, r_list, existing_list):
+            (vp, dv), (rp, dr) = arg(v, np.float32, 1), arg(r, np.uint8, 32)
+            ep, de = (None, dv) if ex is None else arg(ex, np.uint8, 32)
+            if dv != dr or de != dv:
+                raise RoflError(1, "WrongNumBlindingFactors")
+            if d is not None and dv != d:
+                raise ValueError("the clients of a batch have the same number of values")
+            d = dv
+            vptrs.append(vp); rptrs.append(rp); eptrs.append(ep)
+        nonces = nonces or [Nonce.random() for _ in range(nc)]
+        ns = (_NonceStruct * nc)(*[n._struct() for n in nonces])
+        proofs = [np.zeros(128, dtype=np.uint8) for _ in range(nc)]
+        pairs = [np.zeros((max(d, 1), 64), dtype=np.uint8) for _ in range(nc)]
+        vp = (ctypes.c_void_p * nc)(*vptrs); rp = (ctypes.c_void_p * nc)(*rptrs); ep = (ctypes.c_void_p * nc)(*eptrs)
+        pp = (ctypes.c_void_p * nc)(*[p.ctypes.data for p in proofs]); cp = (ctypes.c_void_p * nc)(*[c.ctypes.data for c in pairs])
+        rcs = (ctypes.c_int * nc)()
+        _check(lib().rofl_create_compressed_randproof_batch(_sz(nc), vp, _sz(d), rp, ep, *_fp(fp), ns, pp, cp, rcs))
+        return [(proofs[i], pairs[i][:d]) if rcs[i] == 0 else RoflError(rcs[i], "client %d of the batch" % i) for i in range(nc)]
+
+    @staticmethod
     def helper_verify(proof, pairs):
         p = np.ascontiguousarray(proof, dtype=np.uint8).reshape(128)
         c = np.ascontiguousarray(pairs, dtype=np.uint8).reshape(-1, 64)

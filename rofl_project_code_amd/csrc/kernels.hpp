@@ -2401,6 +2401,49 @@ __global__ void __launch_bounds__(TPB) k_cpow_dot(u32 d, const float *vals, u32 
     if (threadIdx.x == 0) { store_sc(&out[blockIdx.x * 2], v[0]); store_sc(&out[blockIdx.x * 2 + 1], v[1]); }
 }
 #endif
+// The prover's two kernels for a GROUP of clients (rofl_create_compressed_randproof_batch): client y = blockIdx.y, its d values at
+// vals + y d, its d blindings at rc + y d, its commitments to complete (bit y of ex_mask) at existing + 32 y d, its pairs at
+// pairs + 64 y d, its status word at status + y -- a NaN or an undecodable commitment marks ITS client only.
+// k_eg_pairs_batch: ONE THREAD PER POINT, as k_sigma_points has it: blockIdx.z = 0 computes L_i = m_i B + r_i B~ (or checks and copies
+// the commitment handed in), blockIdx.z = 1 computes R_i = r_i B, so that a block runs one formula and a pair's two encodings (a 254-step
+// chain each) run side by side instead of one after the other.  Same formulas as k_eg_pairs, same bytes.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(64) k_eg_pairs_batch(u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *rc, const uint8_t *existing, u32 ex_mask,
+                                                       const niels *tabB, const niels *tabBb, uint8_t *pairs, u32 *status /* [gridDim.y] */) {
+    const size_t y = blockIdx.y;
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x, which = blockIdx.z;
+    if (i >= d) return;
+    const float v = vals[y * d + i];
+    if (v != v) { atomicOr(status + y, 2u); return; }
+    uint8_t *o = pairs + (y * d + i) * 64 + 32 * which;
+    const sc r = load_sc_reduced(&rc[y * d + i]);
+    if (which) { sg_encode(o, sg_fixed_mul8(tabB, r)); return; }
+    if ((ex_mask >> y) & 1u) {
+        const uint8_t *e = existing + (y * d + i) * 32;
+        gd L; if (!sg_decode(L, e)) { atomicOr(status + y, 4u); return; }
+        for (int q = 0; q < 32; q++) o[q] = e[q];
+    } else sg_encode(o, gd_add(sg_fixed_mul8(tabB, sg_f32_to_sc(v, fp_bits, fp_frac)), sg_fixed_mul8(tabBb, r)));
+}
+#endif
+// k_cpow_dot for a group: client y's table sq[y * MAX_LG + b] = c_y^(2^b) (Montgomery) is read from device memory as k_cpow_rows reads
+// it; partial sums of m_i c_y^(i+1) and r_i c_y^(i+1) -> out[(y * gridDim.x + blk) * 2 + {0, 1}] (Montgomery).  Scalar sums are exact:
+// any block count gives the same totals.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_cpow_dot_batch(u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *rc, const sc *sq, sc *out) {
+    __shared__ sc lds[TPB * 2];
+    const size_t y = blockIdx.y;
+    const sc *tab = sq + y * MAX_LG;
+    vals += y * d; rc += y * d;
+    sc v[2] = {sc_zero(), sc_zero()};
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < d; i += gridDim.x * blockDim.x) {
+        sc p = sc_pow_tab(tab, i + 1);
+        sc m = sc_to_mont(sg_f32_to_sc(vals[i], fp_bits, fp_frac)), r = sc_to_mont(load_sc(&rc[i]));
+        v[0] = sc_add(v[0], sc_montmul(m, p)); v[1] = sc_add(v[1], sc_montmul(r, p));
+    }
+    block_sum_sc<2>(v, lds);
+    if (threadIdx.x == 0) { sc *o = out + (y * gridDim.x + blockIdx.x) * 2; store_sc(&o[0], v[0]); store_sc(&o[1], v[1]); }
+}
+#endif
 // de-interleave and decode the d ElGamal pairs of each client of a group (blockIdx.y = client y, its pairs at pairs + 64 (y d + i)) into
 // two niels arrays: L of client y at pts[2y d + i], R at pts[(2y + 1) d + i] -- the two problems of the client's MSM.  An undecodable point
 // sets bit 4 of ITS client's status word (one bad client must not sink the round) and is stored as the identity.

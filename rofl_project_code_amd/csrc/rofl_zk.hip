@@ -1543,6 +1543,138 @@ int compressed_create(const float *values, size_t d, const uint8_t *r32, size_t 
     timing_end(C);
     return ROFL_OK;
 }
+// compressed_create for the clients of one process (the reference's client binary runs its clients as tasks of one process,
+// client.rs:265-266): client i's proof and pairs are byte for byte what compressed_create gives it; rcs[i] is its own outcome (NaN 10,
+// an undecodable commitment 5, a mode-0 stream of fewer than two scalars 12 -- that one before any device work) and a client that fails is
+// left out from there on.  d alone is less than one wave per SIMD for the pairs and a handful of blocks for the dot products; the clients
+// go in GROUPS of at most sixteen (gridDim.y, one bit of the pairs kernel's `existing` mask each) and at most ~64 MB of staged bytes.
+// Per group: the inputs are staged on the host pool and uploaded (device-resident inputs are copied on the device), k_eg_pairs_batch
+// computes every pair one thread per point, and the pairs come back into pinned memory -- they are the output and the transcripts'
+// input.  While that runs the pool computes the group's nonces and C'.  WAIT 1 (the event after the download).  Then the pairs are handed
+// to the callers' arrays and the transcripts of the group's good clients hashed (compressed_challenges, eight per AVX-512 stream), the
+// tables c^(2^b) go up, k_cpow_dot_batch sums every client's two dot products in kCompDotBlocks blocks, the partials come down: WAIT 2.
+// The upload and the pairs launch of group g + 1 are enqueued BEFORE the host turns to group g (two sets of device and staging buffers
+// alternate), so the device computes the next group's pairs while the host hashes: two waits per group instead of two per client.
+constexpr size_t kCompCreateGroup = 16;      // clients per launch: a row of gridDim.y and a bit of the pairs kernel's `existing` mask each
+constexpr u32 kCompDotBlocks = 64;      // per client, as k_cpow_dot: a group of sixteen is 1 024 blocks of four waves, four waves on every SIMD of 256 CUs
+int compressed_create_batch(size_t nc, const float *const *values, size_t d, const uint8_t *const *r32, const uint8_t *const *existing, unsigned fp_bits,
+                            unsigned fp_frac, const rofl_nonce_t *nonces, uint8_t *const *proofs_out, uint8_t *const *pairs_out, int *rcs) {
+    std::vector<size_t> act;      // the clients that reach the device
+    for (size_t i = 0; i < nc; i++) {
+        rcs[i] = nonces[i].mode == 0 && nonces[i].stream_scalars < 2 ? ROFL_NONCE_SHORT : ROFL_OK;
+        if (!rcs[i]) act.push_back(i);
+    }
+    if (act.empty()) return ROFL_OK;
+    LaneLock lane_lock = acquire_lane(false, nc == 1); Ctx &C = *lane_lock.c;
+    C.init();
+    C.batch_mode = nc > 1;
+    timing_begin(C);
+    const size_t na = act.size();
+    // nonces m', r' at index 0, 1 of the client's own stream or seed (party.rs:66-67), C' = commit(m', r')
+    std::vector<sc> nz(2 * na);
+    auto nonces_and_cprime = [&](size_t a0, size_t cnt) {
+        C.pool->run(cnt, [&](size_t k) {
+            const size_t i = act[a0 + k]; const rofl_nonce_t &nn = nonces[i];
+            for (int j = 0; j < 2; j++) {
+                uint8_t b[32];
+                if (nn.mode == 1) rofl_dbg_host_nonce(nn.seed, (uint64_t)j, b);
+                else { sc w = sc_from_wide(sc_frombytes(nn.stream + 64 * j), sc_frombytes(nn.stream + 64 * j + 32)); sc_tobytes(b, w); }
+                nz[2 * (a0 + k) + j] = sc_frombytes(b);
+            }
+            h51::encode(proofs_out[i], h51::gadd(h_fixed_mul(C.ht.B5, nz[2 * (a0 + k)]), h_fixed_mul(C.ht.Bb5, nz[2 * (a0 + k) + 1])));
+            h51::encode(proofs_out[i] + 32, h_fixed_mul(C.ht.B5, nz[2 * (a0 + k) + 1]));
+        });
+    };
+    if (d == 0) {      // Z = (m', r'): no device work
+        nonces_and_cprime(0, na);
+        for (size_t a = 0; a < na; a++) { sc_tobytes(proofs_out[act[a]] + 64, nz[2 * a]); sc_tobytes(proofs_out[act[a]] + 96, nz[2 * a + 1]); }
+        timing_end(C);
+        return ROFL_OK;
+    }
+    const size_t in_per = d * 68, out_per = d * 64;      // staged bytes of a client: values | blindings | commitments, and its pairs
+    const size_t G = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(na, kCompCreateGroup), ((size_t)64 << 20) / (in_per + out_per)));
+    const size_t ngroups = (na + G - 1) / G, nbuf = ngroups > 1 ? 2 : 1;
+    std::vector<char> dev_v(na), dev_r(na), dev_e(na), has_e(na);
+    bool any_host = false;
+    for (size_t a = 0; a < na; a++) {
+        const size_t i = act[a];
+        has_e[a] = existing && existing[i];
+        dev_v[a] = is_device_ptr(values[i]); dev_r[a] = is_device_ptr(r32[i]); dev_e[a] = has_e[a] && is_device_ptr(existing[i]);
+        any_host |= !dev_v[a] || !dev_r[a] || (has_e[a] && !dev_e[a]);
+    }
+    float *dv = C.vals.as<float>(nbuf * G * d); sc *dr = C.tmp_in.as<sc>(nbuf * G * d);
+    uint8_t *dex = C.Cbytes.as<uint8_t>(nbuf * G * d * 32), *dpairs = C.aux_scal.as<uint8_t>(nbuf * G * out_per);
+    u32 *status = C.status.as<u32>(na + 4), *h_st = C.h_misc.as<u32>(na + 4);
+    HIPCHK(hipMemsetAsync(status, 0, 4 * (na + 4), C.stream));
+    sc *dtab = C.tmp_out.as<sc>(G * (MAX_LG + 2 * kCompDotBlocks)), *dpart = dtab + G * MAX_LG;
+    sc *htab = C.h_cp.as<sc>(G * MAX_LG), *hpart = C.h_part.as<sc>(G * 2 * kCompDotBlocks);
+    uint8_t *stg_in[2] = {nullptr, nullptr}, *stg_out[2] = {nullptr, nullptr};
+    for (size_t b = 0; b < nbuf; b++) { if (any_host) stg_in[b] = (uint8_t *)C.stg.alloc(G * in_per); stg_out[b] = (uint8_t *)C.stg.alloc(G * out_per); }
+    // one array of a group: host clients staged on the pool (~256 KB per task) and uploaded run by run, device clients copied on the device
+    auto bring = [&](size_t a0, size_t gc, uint8_t *dst, uint8_t *stg, size_t per, const std::vector<char> &on_dev, const std::vector<char> *present,
+                     const std::function<const uint8_t *(size_t)> &src) {
+        const size_t slices = std::max<size_t>(1, per >> 18);
+        auto host = [&](size_t j) { return (!present || (*present)[a0 + j]) && !on_dev[a0 + j]; };
+        bool any = false; for (size_t j = 0; j < gc; j++) any |= host(j);
+        if (any) C.pool->run(gc * slices, [&](size_t t) { const size_t j = t / slices, k = t % slices; if (!host(j)) return;
+                                                 const size_t lo = per * k / slices, hi = per * (k + 1) / slices; stage_copy(stg + j * per + lo, src(a0 + j) + lo, hi - lo); });
+        for (size_t j = 0; j < gc; ) {
+            if (!host(j)) { if ((!present || (*present)[a0 + j])) HIPCHK(hipMemcpyAsync(dst + j * per, src(a0 + j), per, hipMemcpyDeviceToDevice, C.stream)); j++; continue; }
+            size_t e = j; while (e < gc && host(e)) e++;
+            HIPCHK(hipMemcpyAsync(dst + j * per, stg + j * per, (e - j) * per, hipMemcpyHostToDevice, C.stream));
+            j = e;
+        }
+    };
+    auto enqueue = [&](size_t g) {      // upload, pairs, download of group g into buffer set g & 1; event g & 1 marks the end
+        const size_t a0 = g * G, gc = std::min(G, na - a0), b = g & (nbuf - 1);
+        uint8_t *si = stg_in[b];
+        bring(a0, gc, (uint8_t *)(dv + b * G * d), si, 4 * d, dev_v, nullptr, [&](size_t a) { return (const uint8_t *)values[act[a]]; });
+        bring(a0, gc, (uint8_t *)(dr + b * G * d), si ? si + G * 4 * d : nullptr, 32 * d, dev_r, nullptr, [&](size_t a) { return r32[act[a]]; });
+        bring(a0, gc, dex + b * G * d * 32, si ? si + G * 36 * d : nullptr, 32 * d, dev_e, &has_e, [&](size_t a) { return existing[act[a]]; });
+        u32 ex_mask = 0; for (size_t j = 0; j < gc; j++) if (has_e[a0 + j]) ex_mask |= 1u << j;
+        ROFL_LAUNCH(k_eg_pairs_batch, dim3((unsigned)((d + 63) / 64), (unsigned)gc, 2), dim3(64), 0, C.stream, (u32)d, (const float *)(dv + b * G * d), fp_bits, fp_frac,
+                    (const sc *)(dr + b * G * d), (const uint8_t *)(dex + b * G * d * 32), ex_mask, C.d_tabB8, C.d_tabBb8, dpairs + b * G * out_per, status + a0);
+        HIPCHK(hipMemcpyAsync(stg_out[b], dpairs + b * G * out_per, gc * out_per, hipMemcpyDeviceToHost, C.stream));
+        HIPCHK(hipMemcpyAsync(h_st + a0, status + a0, 4 * gc, hipMemcpyDeviceToHost, C.stream));
+        HIPCHK(hipEventRecord(C.pool_event(b), C.stream));
+    };
+    enqueue(0);
+    for (size_t g = 0; g < ngroups; g++) {
+        const size_t a0 = g * G, gc = std::min(G, na - a0), b = g & (nbuf - 1);
+        if (g + 1 < ngroups) enqueue(g + 1);      // (its buffers are those of group g - 1, which is finished)
+        nonces_and_cprime(a0, gc);
+        C.wait_event(C.pool_event(b));           // wait 1: the group's pairs and status words are on the host
+        std::vector<size_t> good;                // positions in the group
+        for (size_t j = 0; j < gc; j++) {
+            const u32 st = h_st[a0 + j];
+            rcs[act[a0 + j]] = (st & 2u) ? ROFL_NON_FINITE : (st & 4u) ? ROFL_FORMAT_ERROR : ROFL_OK;      // (the single call's order)
+            if (!(st & 6u)) good.push_back(j);
+        }
+        if (good.empty()) continue;
+        const uint8_t *hp = stg_out[b];
+        const size_t slices = std::max<size_t>(1, out_per >> 18);
+        C.pool->run(good.size() * slices, [&](size_t t) { const size_t j = good[t / slices], k = t % slices, lo = out_per * k / slices, hi = out_per * (k + 1) / slices;
+                                                          memcpy(pairs_out[act[a0 + j]] + lo, hp + j * out_per + lo, hi - lo); });
+        std::vector<const uint8_t *> pf(good.size()), pr(good.size()); std::vector<sc> c(good.size());
+        for (size_t q = 0; q < good.size(); q++) { pf[q] = proofs_out[act[a0 + good[q]]]; pr[q] = hp + good[q] * out_per; }
+        compressed_challenges(C, good.size(), pf.data(), pr.data(), d, c.data());
+        memset(htab, 0, sizeof(sc) * MAX_LG * gc);      // (a client that failed keeps its row of the launch; its sums are not read)
+        for (size_t q = 0; q < good.size(); q++) fill_pow2(htab + good[q] * MAX_LG, h_mont(c[q]), MAX_LG);
+        const u32 nblk = (u32)std::min<size_t>(kCompDotBlocks, (d + TPB - 1) / TPB);
+        HIPCHK(hipMemcpyAsync(dtab, htab, sizeof(sc) * MAX_LG * gc, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_cpow_dot_batch, dim3(nblk, (unsigned)gc), dim3(TPB), 0, C.stream, (u32)d, (const float *)(dv + b * G * d), fp_bits, fp_frac, (const sc *)(dr + b * G * d),
+                    (const sc *)dtab, dpart);
+        HIPCHK(hipMemcpyAsync(hpart, dpart, sizeof(sc) * gc * nblk * 2, hipMemcpyDeviceToHost, C.stream));
+        C.sync();                                // wait 2
+        for (size_t j : good) {
+            const sc *p = hpart + j * nblk * 2; uint8_t *po = proofs_out[act[a0 + j]];
+            sc_tobytes(po + 64, sc_add(nz[2 * (a0 + j)], h_canon(sum_partials(p, nblk, 2, 0))));
+            sc_tobytes(po + 96, sc_add(nz[2 * (a0 + j) + 1], h_canon(sum_partials(p, nblk, 2, 1))));
+        }
+    }
+    timing_end(C);
+    return ROFL_OK;
+}
 // What every CompressedRandProof verifier does with the proof's 128 bytes: L', R' decoded, Z_m, Z_r canonical (the reference's FormatError
 // otherwise), and, given sumL = sum_i c^(i+1) L_i and sumR = sum_i c^(i+1) R_i, the two exact group equations (params.rs:235-256)
 //   z_m B + z_r B~ - (L' + sumL) == 0  and  z_r B - (R' + sumR) == 0   on the Ristretto coset.
@@ -1773,6 +1905,27 @@ int rofl_verify_compressed_randproof_batch(size_t n_clients, const uint8_t *cons
         int r = compressed_verify_batch(k, p.data(), c.data(), d, ok.data());
         for (size_t j = 0; j < k; j++) ok_out[idx[j]] = ok[j];
         return r; }); });
+}
+int rofl_create_compressed_randproof_batch(size_t n_clients, const float *const *values, size_t d, const uint8_t *const *r32, const uint8_t *const *existing32,
+                                           unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonces, uint8_t *const *proofs_out, uint8_t *const *pairs_out, int *rc_out) {
+    // (everything here is decided before a device is touched)
+    if (d >= 900000 || !valid_fp(fp_bits, fp_frac) || n_clients > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_clients == 0) return ROFL_OK;
+    if (!nonces || !proofs_out || !rc_out || (d && (!values || !r32 || !pairs_out))) return fail(ROFL_BAD_PARAM, "bad parameter");
+    for (size_t i = 0; i < n_clients; i++)
+        if (!proofs_out[i] || (nonces[i].mode == 0 && nonces[i].stream_scalars && !nonces[i].stream) || (d && (!values[i] || !r32[i] || !pairs_out[i]))) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
+    if (devs.empty() || n_clients < 2)
+        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
+            return compressed_create_batch(n_clients, values, d, r32, existing32, fp_bits, fp_frac, nonces, proofs_out, pairs_out, rc_out); });
+    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
+        const size_t k = idx.size();
+        std::vector<const float *> v(k); std::vector<const uint8_t *> r(k), e(k, nullptr); std::vector<rofl_nonce_t> nn(k); std::vector<uint8_t *> po(k), co(k); std::vector<int> rc(k, ROFL_OK);
+        for (size_t j = 0; j < k; j++) { v[j] = d ? values[idx[j]] : nullptr; r[j] = d ? r32[idx[j]] : nullptr; if (existing32) e[j] = existing32[idx[j]]; nn[j] = nonces[idx[j]];
+                                         po[j] = proofs_out[idx[j]]; co[j] = d ? pairs_out[idx[j]] : nullptr; }
+        int rcode = compressed_create_batch(k, v.data(), d, r.data(), e.data(), fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
+        for (size_t j = 0; j < k; j++) rc_out[idx[j]] = rc[j];
+        return rcode; }); });
 }
 int rofl_create_randproof_vec(const float *values, size_t d, const uint8_t *r32, size_t d_r, const uint8_t *existing32, unsigned fp_bits, unsigned fp_frac,
                               const rofl_nonce_t *nonce, uint8_t *proofs_out, uint8_t *commits_out) {

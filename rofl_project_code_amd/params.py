@@ -233,6 +233,65 @@ class EncParamsRange:
                 lambda: rand_proof_vec.create_randproof_vec(x, bl, nonce=_sub_nonce(nonce_seed, b"rand", wd), fp=fp))
         return cls(pairs, proofs, rp, prove_range, check_percentage)
 
+    @staticmethod
+    def _rand_create_batch(xs, bls, enc_coms, nonces, fp):
+        """The randomness leg of encrypt_batch: (thunks, collect) -- the thunks run beside the range proofs (_concurrently), collect(their
+        results) is the list of (rand proofs, pairs) per client.  enc_coms[i]: the commitments to complete, or None.  Here: one
+        create_randproof_vec(_existing) per client on the lanes."""
+        def one(i):
+            if enc_coms[i] is None:
+                return rand_proof_vec.create_randproof_vec(xs[i], bls[i], nonce=nonces[i], fp=fp)
+            return rand_proof_vec.create_randproof_vec_existing(xs[i], enc_coms[i], bls[i], nonce=nonces[i], fp=fp)
+        return [lambda i=i: one(i) for i in range(len(xs))], list
+
+    @classmethod
+    def encrypt_batch(cls, clients, prove_range, n_partition, check_percentage, nonce_seeds=None, fp=None):
+        """encrypt() for several clients of one process (rofl_service's client binary hosts its clients as tasks of one process,
+        client.rs:265-266): clients = [(plaintext_vec, blinding_vec), ...] of one length.  The L-inf legs of all of them are ONE
+        rofl_create_rangeproof_batch call -- over the first k values of every client when check_percentage < 1 -- and the randomness leg
+        (_rand_create_batch: one call per client here, ONE rofl_create_compressed_randproof_batch for EncParamsRangeCompressed) runs beside
+        it.  Every container is byte-identical to what encrypt() returns for that client with the same nonce seed; a client that fails
+        raises."""
+        fp = api._fp(fp)
+        n = len(clients)
+        if n == 0:
+            return []
+        seeds = list(nonce_seeds) if nonce_seeds is not None else [None] * n
+        xs, bls, clipped = [], [], []
+        for (x, bl) in clients:
+            x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
+            xs.append(x); bls.append(bl)
+            clipped.append(range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp))
+        d = xs[0].size
+        if any(x.size != d for x in xs):
+            raise ValueError("the clients of a batch have one vector length")
+        wds = [witness_digest(x, bl) if sd is not None else b"" for x, bl, sd in zip(xs, bls, seeds)]
+        range_nonces = [_sub_nonce(sd, b"range", wd) for sd, wd in zip(seeds, wds)]
+        rand_nonces = [_sub_nonce(sd, b"rand", wd) for sd, wd in zip(seeds, wds)]
+        if check_percentage >= 1.0:
+            # the range proofs' commitments, computed first (one call for all clients) so that the randomness proofs can complete them while the range proofs run
+            enc_all = pedersen_ops.commit_vec(np.concatenate([conversion32.f32_to_scalar_vec(c, fp=fp) for c in clipped]), np.concatenate(bls))
+            enc_coms = [enc_all[i * d:(i + 1) * d] for i in range(n)]
+            rv, rb = clipped, bls
+        else:
+            k = _num_checked(d, check_percentage)
+            enc_coms = [None] * n
+            rv, rb = [c[:k] for c in clipped], [bl[:k] for bl in bls]
+        # NB the reference passes the un-clipped plaintext to the randomness proof (params.rs:499)
+        thunks, collect = cls._rand_create_batch(xs, bls, enc_coms, rand_nonces, fp)
+        res = _concurrently(lambda: range_proof_vec.create_rangeproof_batch(rv, rb, prove_range, n_partition, nonces=range_nonces, fp=fp), *thunks)
+        rand = collect(res[1:])
+        out = []
+        for i in range(n):
+            for r in (res[0][i], rand[i]):
+                if isinstance(r, Exception):
+                    raise r
+            rp, rp_com = res[0][i]
+            assert enc_coms[i] is None or (rp_com == enc_coms[i]).all()
+            proofs, pairs = rand[i]
+            out.append(cls(pairs, proofs, rp, prove_range, check_percentage))
+        return out
+
     def verify(self, verifier_seed=None, fp=None):
         """EncModelParams::verify, EncRange arm (params.rs:185-203): any Err counts as false (and so does anything else a
         crafted message can provoke while it is parsed)."""
@@ -350,6 +409,10 @@ class EncParamsRangeCompressed(EncParamsRange):
                 lambda: range_proof_vec.create_rangeproof(clipped[:k], bl[:k], prove_range, n_partition, nonce=_sub_nonce(nonce_seed, b"range", wd), fp=fp),
                 lambda: compressed_rand_proof.helper_prove(x, bl, nonce=_sub_nonce(nonce_seed, b"rand", wd), fp=fp))
         return cls(pairs, proof, rp, prove_range, check_percentage)
+
+    @staticmethod
+    def _rand_create_batch(xs, bls, enc_coms, nonces, fp):      # ONE rofl_create_compressed_randproof_batch for all clients
+        return [lambda: compressed_rand_proof.helper_prove_batch(xs, bls, nonces=nonces, existing_list=enc_coms, fp=fp)], lambda res: res[0]
 
     def verify(self, verifier_seed=None, fp=None):
         fp = api._fp(fp)
@@ -576,6 +639,48 @@ class EncParamsL2Compressed(EncParamsL2):
         sq_proofs, sq_commits = square_proof_vec.create_l2rangeproof_vec_existing(clipped, enc_com, bl, r2, nonce=_sub_nonce(nonce_seed, b"sq", wd), fp=fp)
         merged = np.concatenate([pairs, sq_commits[:, 32:64]], axis=1)        # merge(): c = ElGamal pair, c_sq from the square proof (params.rs:777-787)
         return cls(merged, sq_proofs, rand_proof, rp, sum_proof, prove_range, l2_range)
+
+    @classmethod
+    def encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None):
+        """encrypt() for several clients of one process: clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one
+        length.  The 8-bit legs of all of them are ONE rofl_create_rangeproof_batch call, their compressed randomness proofs ONE
+        rofl_create_compressed_randproof_batch over the range proofs' commitments; the sum proofs and the SquareProofs run per client
+        beside them on other lanes.  Every container is byte-identical to what encrypt() returns for that client with the same nonce
+        seed; a client that fails raises."""
+        fp = api._fp(fp)
+        n = len(clients)
+        if n == 0:
+            return []
+        seeds = list(nonce_seeds) if nonce_seeds is not None else [None] * n
+        xs, bls, r2s, clipped = [], [], [], []
+        for (x, bl, r2) in clients:
+            x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
+            r2 = pedersen_ops.rnd_scalar_vec(x.size) if r2 is None else api._u8(r2)
+            xs.append(x); bls.append(bl); r2s.append(r2)
+            clipped.append(range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp))
+        d = xs[0].size
+        if any(x.size != d for x in xs):
+            raise ValueError("the clients of a batch have one vector length")
+        wds = [witness_digest(x, bl, r2) if sd is not None else b"" for x, bl, r2, sd in zip(xs, bls, r2s, seeds)]
+        enc_all = pedersen_ops.commit_vec(np.concatenate([conversion32.f32_to_scalar_vec(c, fp=fp) for c in clipped]), np.concatenate(bls))
+        enc_com = [enc_all[i * d:(i + 1) * d] for i in range(n)]
+        thunks = [lambda: range_proof_vec.create_rangeproof_batch(clipped, bls, prove_range, n_partition, nonces=[_sub_nonce(sd, b"range", wd) for sd, wd in zip(seeds, wds)], fp=fp),
+                  lambda: compressed_rand_proof.helper_prove_batch(clipped, bls, nonces=[_sub_nonce(sd, b"rand", wd) for sd, wd in zip(seeds, wds)], existing_list=enc_com, fp=fp)]
+        for i in range(n):
+            thunks.append(lambda i=i: l2_range_proof_vec.create_rangeproof_l2(clipped[i], r2s[i], l2_range, n_partition, nonce=_sub_nonce(seeds[i], b"l2", wds[i]), fp=fp))
+            thunks.append(lambda i=i: square_proof_vec.create_l2rangeproof_vec_existing(clipped[i], enc_com[i], bls[i], r2s[i], nonce=_sub_nonce(seeds[i], b"sq", wds[i]), fp=fp))
+        res = _concurrently(*thunks)
+        out = []
+        for i in range(n):
+            for r in (res[0][i], res[1][i]):
+                if isinstance(r, Exception):
+                    raise r
+            (rp, rp_com), (rand_proof, pairs) = res[0][i], res[1][i]
+            assert (rp_com == enc_com[i]).all()
+            (sum_proof, _), (sq_proofs, sq_commits) = res[2 + 2 * i], res[3 + 2 * i]
+            merged = np.concatenate([pairs, sq_commits[:, 32:64]], axis=1)        # merge(), as in encrypt()
+            out.append(cls(merged, sq_proofs, rand_proof, rp, sum_proof, prove_range, l2_range))
+        return out
 
     @staticmethod
     def _square_batch(us):      # SquareProofCommitments { c_l: c.L, c_sq } (params.rs:262-266); as in verify(), the compressed randomness proof is not re-checked

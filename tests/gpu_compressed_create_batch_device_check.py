@@ -1,0 +1,32 @@
+"""Helper for test_gpu_compressed_create_batch.py::test_device_resident_inputs: device pointers in, same bytes out."""
+import os, sys
+import numpy as np
+import torch
+torch.cuda.init()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+import rofl_project_code_amd as R
+R.set_device(0)
+FP = (16, 7)
+d, n = 65, 3
+xs, bls, coms, nonces = [], [], [], []
+for i in range(n):
+    rng = np.random.default_rng(77 + i)
+    x = (rng.integers(-100, 100, size=d) / 128.0).astype(np.float32)
+    bl = rng.integers(0, 256, size=(d, 32), dtype=np.uint8); bl[:, 31] &= 0x0F
+    xs.append(x); bls.append(bl); coms.append(R.pedersen_ops.commit_vec(R.conversion32.f32_to_scalar_vec(x, fp=FP), bl))
+seeds = [bytes([0x60 + i]) * 32 for i in range(n)]
+want = [R.compressed_rand_proof.helper_prove(xs[i], bls[i], nonce=R.Nonce.seeded(seeds[i]), existing=coms[i], fp=FP) for i in range(n)]
+# client 1 lives on the device, its neighbours in host memory
+vl, rl, el = list(xs), list(bls), list(coms)
+vl[1], rl[1], el[1] = torch.from_numpy(xs[1]).cuda(), torch.from_numpy(bls[1]).cuda(), torch.from_numpy(np.ascontiguousarray(coms[1])).cuda()
+got = R.compressed_rand_proof.helper_prove_batch(vl, rl, nonces=[R.Nonce.seeded(s) for s in seeds], existing_list=el, fp=FP)
+for i in range(n):
+    assert not isinstance(got[i], Exception), (i, got[i])
+    assert (got[i][0] == want[i][0]).all() and (got[i][1] == want[i][1]).all(), i
+# every client on the device, without commitments to complete
+want2 = [R.compressed_rand_proof.helper_prove(xs[i], bls[i], nonce=R.Nonce.seeded(seeds[i]), fp=FP) for i in range(n)]
+got2 = R.compressed_rand_proof.helper_prove_batch([torch.from_numpy(x).cuda() for x in xs], [torch.from_numpy(b).cuda() for b in bls],
+                                                  nonces=[R.Nonce.seeded(s) for s in seeds], fp=FP)
+for i in range(n):
+    assert (got2[i][0] == want2[i][0]).all() and (got2[i][1] == want2[i][1]).all(), i
+print("DEVICE_INPUTS PASS")

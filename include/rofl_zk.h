@@ -237,6 +237,16 @@ int rofl_verify_compressed_randproof(const uint8_t proof[128], const uint8_t *pa
  * problems per client each).  With rofl_set_option("devices", mask) the clients are dealt
  * round-robin to the listed devices. */
 int rofl_verify_compressed_randproof_batch(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out);
+/* The same over records read in place: records[i] is d * stride bytes of host memory, stride 64 (ElGamalPair: this IS the call above, same
+ * code, same launches) or 96 (SquareRandProofCommitments L | R | c_sq: the pair is the first 64 bytes of a record and the call reads
+ * nothing else of it -- undecodable bytes in c_sq do not matter here).  This is the check the reference's EncL2Compressed arm leaves out
+ * (params.rs:257-289 never reads the update's rand_proof, so nothing there constrains R).  ok_out[i] is exactly what
+ * rofl_verify_compressed_randproof_batch gives client i on the packed pairs: the same two exact group equations, no random weights; a
+ * member with a non-canonical Z_m / Z_r, an undecodable C' or an undecodable L / R gets 0 and the others are still verified.
+ * n_clients = 0 returns 0.  11 (bad parameter), before any device work: a stride other than 64 or 96, d >= 900 000, a null pointer with
+ * n_clients > 0, more than 32 767 clients.  The `devices` option deals the clients round-robin as it does for the dense call. */
+int rofl_verify_compressed_randproof_batch_strided(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *records,
+                                                   size_t stride, size_t d, int *ok_out);
 /* client side: the compressed randomness proofs of n_clients clients of one process (client.rs:265-266 hosts its clients as tasks of one
  * process) in one launch sequence -- groups of at most sixteen clients, two host waits per group instead of two per client.
  * proofs_out[i] (128 bytes) and pairs_out[i] (d * 64 bytes, host memory) are byte for byte what rofl_create_compressed_randproof returns
@@ -325,6 +335,13 @@ int rofl_round_create(size_t d, size_t record_len, size_t max_clients, uint64_t 
  * rofl_verify_compressed_randproof), else 11; unknown flag bits: 11.  A round without the flag ingests exactly as before. */
 #define ROFL_ROUND_COMPRESSED 1u
 int rofl_round_create_ex(size_t d, size_t record_len, size_t max_clients, unsigned flags, uint64_t *handle_out);
+/* A round whose ingest keeps, per client, the CompressedRandProof transcript after the client's d labelled pairs, for records of either
+ * length: the transcript is hashed from the first 64 bytes of every record (L | R), from the very bytes that go to the device.
+ * record_len 64 is the round rofl_round_create_ex(..., ROFL_ROUND_COMPRESSED) creates; record_len 96 is a round of EncL2Compressed updates
+ * whose CompressedRandProof is to be CHECKED by rofl_round_verify_compressed (the reference's arm skips it, params.rs:257-289) beside
+ * rofl_round_verify_sigma kind 2 and rofl_round_verify_range.  Parameter checks and limits as rofl_round_create_ex with the flag:
+ * d = 0, d >= 900000, max_clients = 0, a record_len other than 64 or 96, a null handle_out, a round too large: 11. */
+int rofl_round_create_rand(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out);
 /* Appends n_clients clients (records[i]: d * record_len bytes, host or device memory) as clients first .. first + n_clients of the round
  * (*first_index_out, may be NULL).  More clients than max_clients leaves room for: 11, nothing ingested.  A point that does not decode
  * never fails the call: it is remembered per client and component and fails exactly the legs that read it (below). */
@@ -339,7 +356,9 @@ int rofl_round_verify_sigma(uint64_t h, int kind, const uint8_t *const *proofs, 
  * as they do there); the L are not decoded again.  An undecodable L fails a client only at an index < k_checked.  proofs[i] NULL as above. */
 int rofl_round_verify_range(uint64_t h, const uint8_t *const *proofs, size_t proof_len, size_t n_proofs, size_t k_checked,
                             size_t prove_range, unsigned fp_bits, unsigned fp_frac, const uint8_t verifier_seed[32], int *ok_out);
-/* The CompressedRandProofs (params.rs:235-256) of every ingested client of a ROFL_ROUND_COMPRESSED round (any other round: 11): proofs[i]
+/* The CompressedRandProofs (params.rs:235-256) of every ingested client of a round that keeps the transcript prefixes -- created with
+ * ROFL_ROUND_COMPRESSED or by rofl_round_create_rand (any other round: 11; in a round of 96-byte records an undecodable c_sq fails the
+ * client's Sigma leg, not this one): proofs[i]
  * is client i's 128-byte proof, or NULL to leave the client out (ok_out[i] = 0).  ok_out[i] is exactly what
  * rofl_verify_compressed_randproof_batch returns for client i on (proofs[i], the bytes ingested for client i): the same two exact group
  * equations, no random weights; an undecodable C', a non-canonical Z_m / Z_r or an undecodable L or R at any index fails that member alone.

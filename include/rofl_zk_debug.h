@@ -109,6 +109,11 @@ int rofl_dbg_host_merlin8_selftest(int lanes, unsigned count, unsigned skew, dou
  * `count` pairs each, `skew` (<= 400) extra prefix bytes; 0 = states, positions and the challenge drawn after C' agree, 1 = mismatch,
  * -1 = no AVX-512 on this CPU */
 int rofl_dbg_host_merlin8_lbl3_selftest(int lanes, unsigned count, unsigned skew, double *us_simd, double *us_scalar);
+/* the same with the pairs read every `stride` bytes (64 .. 256; 96: the pairs inside SquareRandProofCommitments records, as a strict
+ * EncL2Compressed check hashes them): bytes 64 .. stride of every record are filler that differs per lane and per record, and the scalar
+ * side hashes a packed copy of the first 64 bytes of each record -- 0 = states, positions and the challenge drawn after C' agree (no
+ * filler byte reached a transcript), 1 = mismatch, -1 = no AVX-512 on this CPU, 11 = bad parameter.  CPU-only. */
+int rofl_dbg_host_merlin8_lbl3_strided_selftest(int lanes, unsigned count, unsigned skew, unsigned stride, double *us_simd, double *us_scalar);
 /* Merlin::append32_run (the run of m commitment appends of a chunk, records assembled in registers and split at the end of the rate block)
  * against `count` plain appends after `skew` (<= 400) extra prefix bytes: 0 = state, positions and next challenge equal, 1 = mismatch */
 int rofl_dbg_host_merlin_run_selftest(unsigned count, unsigned skew);

@@ -83,4 +83,22 @@ impl CompressedRandProof {
         if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
         if ok != 0 { Ok(()) } else { Err(ProofError::VerificationError) }
     }
+    /// The proofs of a round's clients over records read in place: records[i] is client i's d records of `stride` bytes as they came off
+    /// the wire -- 64 (ElGamalPair::to_bytes) or 96 (SquareRandProofCommitments::to_bytes: c.L | c.R | c_sq, of which only the pair is
+    /// read).  ONE rofl_verify_compressed_randproof_batch_strided call; verdict i is what proofs[i].helper_verify gives on client i's
+    /// pairs, a malformed member (FormatError there) is false and the others are still verified.  With stride 96 this is the check the
+    /// EncL2Compressed arm of EncModelParams::verify (params.rs:257-289) leaves out: call it there, beside the square proofs and the
+    /// range proofs, so that a client cannot send arbitrary R and cost the round its aggregate.
+    pub fn helper_verify_batch_strided(proofs: &[&CompressedRandProof], records: &[&[u8]], stride: usize, d: usize) -> Vec<bool> {
+        let n = proofs.len();
+        assert!(records.len() == n && records.iter().all(|r| r.len() == d * stride));
+        if n == 0 { return Vec::new(); }
+        let pb: Vec<Vec<u8>> = proofs.iter().map(|p| p.to_bytes()).collect();
+        let pp: Vec<*const u8> = pb.iter().map(|v| v.as_ptr()).collect();
+        let rp: Vec<*const u8> = records.iter().map(|r| r.as_ptr()).collect();
+        let mut ok: Vec<std::os::raw::c_int> = vec![0; n];
+        let rc = unsafe { rofl_verify_compressed_randproof_batch_strided(n, pp.as_ptr(), rp.as_ptr(), stride, d, ok.as_mut_ptr()) };
+        if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+        ok.iter().map(|&o| o != 0).collect()
+    }
 }

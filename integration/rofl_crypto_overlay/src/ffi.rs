@@ -86,6 +86,8 @@ extern "C" {
     pub fn rofl_round_create(d: usize, record_len: usize, max_clients: usize, handle_out: *mut u64) -> c_int;
     /// flags = ROFL_ROUND_COMPRESSED (1): the round keeps each client's CompressedRandProof transcript prefix for rofl_round_verify_compressed
     pub fn rofl_round_create_ex(d: usize, record_len: usize, max_clients: usize, flags: c_uint, handle_out: *mut u64) -> c_int;
+    /// a round that keeps the CompressedRandProof transcript prefixes for records of either length (96: the strict check of EncL2Compressed)
+    pub fn rofl_round_create_rand(d: usize, record_len: usize, max_clients: usize, handle_out: *mut u64) -> c_int;
     pub fn rofl_round_ingest(h: u64, n_clients: usize, records: *const *const u8, first_index_out: *mut usize) -> c_int;
     pub fn rofl_round_verify_sigma(h: u64, kind: c_int, proofs: *const *const u8, ok_out: *mut c_int, csq_sum_out32: *mut u8) -> c_int;
     pub fn rofl_round_verify_range(h: u64, proofs: *const *const u8, proof_len: usize, n_proofs: usize, k_checked: usize,
@@ -123,6 +125,9 @@ extern "C" {
     /// exactly the single call's (a malformed member is 0, the others are still verified)
     pub fn rofl_verify_compressed_randproof_batch(n_clients: usize, proofs: *const *const u8, pairs: *const *const u8, d: usize,
         ok_out: *mut c_int) -> c_int;
+    /// the same over records read in place every `stride` bytes (64, or 96: SquareRandProofCommitments, the pair is the first 64 bytes)
+    pub fn rofl_verify_compressed_randproof_batch_strided(n_clients: usize, proofs: *const *const u8, records: *const *const u8,
+        stride: usize, d: usize, ok_out: *mut c_int) -> c_int;
     /// the compressed randomness proofs of the clients of one process in one launch sequence; proofs_out[i] / pairs_out[i] are the single
     /// call's bytes for client i, rc_out[i] its own outcome (0, 10, 5, 12: it is left out, the others are still proved); existing32 or any
     /// of its entries may be null

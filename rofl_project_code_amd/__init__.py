@@ -11,4 +11,4 @@ from .api import (  # noqa: F401
     set_device, get_device, last_timing, last_kernel_times, set_timing, bench_femul, set_fp, get_fp, set_option, get_option,
 )
 from . import params  # noqa: F401,E402
-from .params import EncParamsRange, EncParamsRangeCompressed, EncParamsL2, EncParamsL2Compressed, EncModelParamsAccumulator, DeviceAccumulator, DeviceRound, wire  # noqa: F401,E402
+from .params import EncParamsRange, EncParamsRangeCompressed, EncParamsL2, EncParamsL2Compressed, EncParamsL2CompressedStrict, EncModelParamsAccumulator, DeviceAccumulator, DeviceRound, wire  # noqa: F401,E402

@@ -772,6 +772,35 @@ class compressed_rand_proof:
                 res[i] = bool(ok[k])
         return res
 
+    @staticmethod
+    def helper_verify_batch_strided(proofs_list, records_list, stride):
+        """rofl_verify_compressed_randproof_batch_strided: helper_verify_batch over records read in place -- records_list[i] is a (d, stride)
+        array, stride 64 (ElGamal pairs) or 96 (SquareRandProofCommitments: the pair is the first 64 bytes, c_sq is never read).  One
+        verdict per client, what helper_verify_batch gives it on the packed pairs; a member whose arrays are malformed (a proof that is
+        not 128 bytes, records that are not a contiguous (d, stride) array) is False without reaching the library."""
+        stride = int(stride)
+        if stride not in (64, 96):
+            raise RoflError(11, "stride must be 64 or 96")
+        n = len(proofs_list)
+        if n != len(records_list):
+            raise ValueError("one record vector per proof")
+        ps, cs, by_d = [None] * n, [None] * n, {}
+        for i, (p, c) in enumerate(zip(proofs_list, records_list)):
+            p = np.ascontiguousarray(p, dtype=np.uint8).reshape(-1)
+            c = np.ascontiguousarray(c, dtype=np.uint8)
+            if p.size == 128 and c.ndim == 2 and c.shape[1] == stride:
+                ps[i], cs[i] = p, c
+                by_d.setdefault(c.shape[0], []).append(i)
+        res = [False] * n
+        for d, idx in by_d.items():
+            pp = (ctypes.c_void_p * len(idx))(*[ps[i].ctypes.data for i in idx])
+            cp = (ctypes.c_void_p * len(idx))(*[cs[i].ctypes.data for i in idx])
+            ok = (ctypes.c_int * len(idx))()
+            _check(lib().rofl_verify_compressed_randproof_batch_strided(_sz(len(idx)), pp, cp, _sz(stride), _sz(d), ok))
+            for k, i in enumerate(idx):
+                res[i] = bool(ok[k])
+        return res
+
 
 class pedersen_ops:
     @staticmethod
@@ -935,6 +964,14 @@ class device_round:
         return h.value
 
     @staticmethod
+    def create_rand(d, record_len, max_clients):
+        """rofl_round_create_rand: a round that keeps every client's CompressedRandProof transcript prefix (verify_compressed) for records
+        of either length -- 64 is create(..., COMPRESSED); 96 is a round of EncL2Compressed updates whose randomness proof is checked"""
+        h = ctypes.c_uint64()
+        _check(lib().rofl_round_create_rand(_sz(d), _sz(record_len), _sz(max_clients), ctypes.byref(h)))
+        return h.value
+
+    @staticmethod
     def ingest(h, records):
         n = len(records)
         rp = (ctypes.c_void_p * max(n, 1))(*records)
@@ -963,7 +1000,7 @@ class device_round:
 
     @staticmethod
     def verify_compressed(h, proofs):
-        """the 128-byte CompressedRandProofs of a round created with COMPRESSED, one pointer (or None) per ingested client -> list[bool]"""
+        """the 128-byte CompressedRandProofs of a round created with COMPRESSED or create_rand, one pointer (or None) per ingested client -> list[bool]"""
         n = len(proofs)
         pp = (ctypes.c_void_p * max(n, 1))(*proofs)
         ok = (ctypes.c_int * max(n, 1))()

@@ -122,14 +122,15 @@ struct Run8 {
             }
         }
     }
-    // count x append_lbl({3i, 3i + 1, 3i + 2}, msg[l] + 64 j, 64), i = i0 + j (label bytes mod 256), on every lane -- the labelled
-    // ElGamal pairs of a CompressedRandProof transcript.  A record is 75 transcript bytes: {pos_begin, META_AD} label(3) len(4)
+    // count x append_lbl({3i, 3i + 1, 3i + 2}, msg[l] + stride j, 64), i = i0 + j (label bytes mod 256), on every lane -- the labelled
+    // ElGamal pairs of a CompressedRandProof transcript, read every `stride` bytes (64: packed pairs; 96: the first 64 bytes of
+    // SquareRandProofCommitments -- nothing else of a record is read).  A record is 75 transcript bytes: {pos_begin, META_AD} label(3) len(4)
     // {pos_begin', AD} pair(64).  A record that reaches the end of the rate block is split there, as Merlin::append32_run splits its
     // records: the second header sits at record byte 9, so a block that ends within bytes 0..8 (k <= 9 bytes left) permutes with
     // pos_begin = start + 1 and the second operation begins in the new block with pos_begin 0; otherwise the permutation sees start + 10.
-    ROFL_K8 void append_lbl3(size_t i0, const uint8_t *const msg[8], size_t count) {
+    ROFL_K8 void append_lbl3(size_t i0, const uint8_t *const msg[8], size_t count, size_t stride) {
         for (size_t j = 0; j < count; j++) {
-            const size_t i = i0 + j, off = 64 * j;
+            const size_t i = i0 + j, off = stride * j;
             const unsigned k = (unsigned)R - pos;      // bytes left in the rate block, 1..166
             const uint8_t hdr[11] = {pos_begin, 16 | 2, (uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2), 64, 0, 0, 0,
                                      (uint8_t)(k <= 9 ? 0 : pos + 1), 2};
@@ -163,12 +164,13 @@ ROFL_K8 void append32_run_x8(Merlin *const t[8], int lanes, char label, const ui
     r.append32(label, m, count);
     r.store(t);
 }
-// count x Merlin::append_lbl({3i, 3i + 1, 3i + 2}, msg[l] + 64 j, 64), i = i0 + j, for up to eight transcripts in the same position
-// (the d ElGamal pairs of a CompressedRandProof transcript, compressed_prefixes in rofl_zk.hip).
-ROFL_K8 void append_lbl3_run_x8(Merlin *const t[8], int lanes, size_t i0, const uint8_t *const msg[8], size_t count) {
+// count x Merlin::append_lbl({3i, 3i + 1, 3i + 2}, msg[l] + stride j, 64), i = i0 + j, for up to eight transcripts in the same position
+// (the d ElGamal pairs of a CompressedRandProof transcript, compressed_prefixes in rofl_zk.hip; stride 96: the pairs inside
+// SquareRandProofCommitments records, hashed where they lie).
+ROFL_K8 void append_lbl3_run_x8(Merlin *const t[8], int lanes, size_t i0, const uint8_t *const msg[8], size_t count, size_t stride = 64) {
     Run8 r; r.load(t, lanes);
     const uint8_t *m[8]; for (int l = 0; l < 8; l++) m[l] = msg[l < lanes ? l : 0];
-    r.append_lbl3(i0, m, count);
+    r.append_lbl3(i0, m, count, stride);
     r.store(t);
 }
 

@@ -2458,6 +2458,23 @@ __global__ void __launch_bounds__(TPB) k_decode_pairs_batch(u32 d, const uint8_t
     store_niels(&pts[(2 * y + which) * d + i], gd_to_niels(p));
 }
 #endif
+// k_decode_pairs_batch over records that lie rec_len bytes apart (96: SquareRandProofCommitments, whose ElGamal pair is the first 64 bytes;
+// rec_len a multiple of 16, rec 16-byte aligned): L / R of element i of client y at rec + (y d + i) rec_len + 32 which, two 16-byte loads
+// as k_round_ingest reads its points; nothing past byte 64 of a record is read.  Same output layout, same per-client status word.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_decode_pairs_strided_batch(u32 d, u32 rec_len, const uint8_t *rec, niels *pts, u32 *status /* [gridDim.y] */) {
+    const size_t y = blockIdx.y;
+    u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * d) return;
+    u32 i = t >> 1, which = t & 1;
+    const uint8_t *src = rec + (y * d + i) * rec_len + 32 * which;
+    __align__(16) uint8_t b[32];
+    reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
+    gd p;
+    if (!gd_ristretto_decode(p, b)) { atomicOr(status + y, 4u); p = gd_identity(); }
+    store_niels(&pts[(2 * y + which) * d + i], gd_to_niels(p));
+}
+#endif
 // The scalars of the CompressedRandProof equations for a group of clients: row y = blockIdx.y has its table sq[y * MAX_LG + b] = c_y^(2^b)
 // (Montgomery) in device memory and gets out_canon[y * d + i] = c_y^(i + 1) (canonical), i < d -- the scalar array of the client's two MSM
 // problems.  A thread takes kCpowRun consecutive exponents: one walk of the table for the first (popcount(i + 1) multiplications), one

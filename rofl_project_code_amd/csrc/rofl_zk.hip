@@ -726,8 +726,9 @@ int acc_add_impl(Ctx &C, Acc &A, const std::vector<size_t> &cl, const std::vecto
 // The clients' records as ingested and their decoded points (RoundSrc's layout), allocated once for max_clients by create.  Ingest,
 // accumulate, reset and destroy hold the round exclusively; the two verification legs hold it shared (they only read the record points --
 // the Sigma leg also writes the odd slots, which no other call reads) and may run side by side on two lanes, one leg of each kind at a time.
-// A round created with ROFL_ROUND_COMPRESSED also keeps, per client, the CompressedRandProof transcript as it stands after the client's d
-// labelled pairs (everything the transcript absorbs before C' depends on the records alone): hashed at ingest from the bytes that are
+// A round created with ROFL_ROUND_COMPRESSED (or by rofl_round_create_rand, which also allows 96-byte records: the pair is the first 64 bytes
+// of each) also keeps, per client, the CompressedRandProof transcript as it stands after the client's d labelled pairs (everything the
+// transcript absorbs before C' depends on the records alone): hashed at ingest from the bytes that are
 // decoded, so that the compressed leg's verdict is about the snapshot the accumulation adds, whatever became of the caller's memory since.
 struct Round {
     int device = 0; size_t d = 0, rec_len = 0, npts = 0, max_clients = 0, n = 0; unsigned flags = 0;
@@ -743,8 +744,9 @@ Registry<Round> g_rounds;
 // The Merlin states of nc CompressedRandProof transcripts after their d labelled pairs (everything they absorb before C'), on the lane's
 // host pool.  Having absorbed messages of the same lengths, the transcripts' STROBE bookkeeping is identical at every step: eight of them
 // share one AVX-512 instruction stream (keccak_x8.hpp); groups of fewer than five, and CPUs without AVX-512, keep the scalar transcript, one
-// client per task.  pairs[j]: d x 64 bytes in host memory.
-void compressed_prefixes(Ctx &C, size_t nc, const uint8_t *const *pairs, size_t d, Merlin *out) {
+// client per task.  pairs[j]: d records of `stride` bytes in host memory, the ElGamal pair in the first 64 of each (64: packed pairs; 96:
+// SquareRandProofCommitments, hashed where they lie -- c_sq is not part of the transcript).
+void compressed_prefixes(Ctx &C, size_t nc, const uint8_t *const *pairs, size_t d, Merlin *out, size_t stride = 64) {
     static const bool x8_on = k8::available();
     const Merlin start = [] { Merlin t("CompressedRandProof", 19); t.append("dom-sep", (const uint8_t *)"randomness proof v1", 19); return t; }();
     std::vector<std::pair<size_t, size_t>> tasks;      // (first client, count)
@@ -757,20 +759,20 @@ void compressed_prefixes(Ctx &C, size_t nc, const uint8_t *const *pairs, size_t 
         const size_t j0 = tasks[k].first, cnt = tasks[k].second;
         for (size_t l = 0; l < cnt; l++) out[j0 + l] = start;
         if (cnt == 1) {      // label = UNIQUE_U8_TRIPLETS[i] (generate_unique_u8_triplets.py:8-13)
-            for (size_t i = 0; i < d; i++) { uint8_t lbl[3] = {(uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2)}; out[j0].append_lbl(lbl, 3, pairs[j0] + 64 * i, 64); }
+            for (size_t i = 0; i < d; i++) { uint8_t lbl[3] = {(uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2)}; out[j0].append_lbl(lbl, 3, pairs[j0] + stride * i, 64); }
             return;
         }
         Merlin *tp[8]; const uint8_t *msg[8];
         for (size_t l = 0; l < cnt; l++) { tp[l] = &out[j0 + l]; msg[l] = pairs[j0 + l]; }
-        if (d) k8::append_lbl3_run_x8(tp, (int)cnt, 0, msg, d);
+        if (d) k8::append_lbl3_run_x8(tp, (int)cnt, 0, msg, d, stride);
     });
 }
 // the challenge c of a transcript that stands after its pairs: C' absorbed, c drawn (the state is a copy: a round keeps its prefixes)
 sc compressed_challenge(Merlin t, const uint8_t cprime[64]) { t.append("C_prime_eg", cprime, 64); return t.challenge_scalar("c"); }
-// the challenges of nc proofs over host pairs
-void compressed_challenges(Ctx &C, size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, sc *out) {
+// the challenges of nc proofs over host pairs (records of `stride` bytes, as compressed_prefixes reads them)
+void compressed_challenges(Ctx &C, size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, sc *out, size_t stride = 64) {
     std::vector<Merlin> t(nc, Merlin("CompressedRandProof", 19));
-    compressed_prefixes(C, nc, pairs, d, t.data());
+    compressed_prefixes(C, nc, pairs, d, t.data(), stride);
     for (size_t j = 0; j < nc; j++) out[j] = compressed_challenge(t[j], proofs[j]);
 }
 // clients [R.n, R.n + n): the records go up in groups of ~64 MB through two pinned staging buffers (the pool copies group g + 1 while group g
@@ -822,7 +824,7 @@ int round_ingest_impl(Ctx &C, Round &R, size_t n, const uint8_t *const *records)
             if (any_dev) C.wait_event(C.pool_event(2));
             std::vector<const uint8_t *> src(gc);
             for (size_t i = 0; i < gc; i++) src[i] = st + i * per;
-            compressed_prefixes(C, gc, src.data(), d, prefix.data() + g0);
+            compressed_prefixes(C, gc, src.data(), d, prefix.data() + g0, R.rec_len);
         }
     }
     u32 *hb = C.h_misc.as<u32>(3 * n);
@@ -1731,7 +1733,10 @@ void compressed_sums(Ctx &C, size_t d, const std::vector<CompClient> &cl, std::v
 // group g.  The final equalities (three fixed-base multiplications per client) run on the host pool.
 // single: the one-client call (rofl_verify_compressed_randproof), which reports a malformed member as the reference does -- a FormatError,
 // the proof's before anything else, the pairs' after their decode -- instead of the verdict 0.
-int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out, bool single = false) {
+// stride 96: pairs[i] are SquareRandProofCommitments records, verified in place -- staged as they lie (one contiguous copy per client, as
+// ingest stages them), uploaded whole, hashed every 96 bytes and decoded by k_decode_pairs_strided_batch, which reads L | R of every
+// record and never c_sq.  Everything after the decode is the same.
+int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out, bool single = false, size_t stride = 64) {
     LaneLock lane_lock = acquire_lane(false, nc == 1); Ctx &C = *lane_lock.c;
     for (size_t i = 0; i < nc; i++) ok_out[i] = 0;
     if (nc == 0) return ROFL_OK;
@@ -1747,23 +1752,25 @@ int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8
     const size_t G = std::min<size_t>(nc, kCompGroup);
     u32 *status = C.status.as<u32>(nc + 4);
     HIPCHK(hipMemsetAsync(status, 0, 4 * (nc + 4), C.stream));
-    uint8_t *dpairs = C.tmp_in.as<uint8_t>(G * d * 64);
+    const size_t per = d * stride;      // a client's records
+    uint8_t *dpairs = C.tmp_in.as<uint8_t>(G * per);
     niels *pts = C.aux_pts.as<niels>(2 * G * d);
     // group g + 2 is staged into group g's buffer while group g + 1 runs, and by then group g's upload has completed
-    uint8_t *stg_buf[2] = {d ? (uint8_t *)C.stg.alloc(G * d * 64) : nullptr, d && nc > G ? (uint8_t *)C.stg.alloc(G * d * 64) : nullptr};
+    uint8_t *stg_buf[2] = {d ? (uint8_t *)C.stg.alloc(G * per) : nullptr, d && nc > G ? (uint8_t *)C.stg.alloc(G * per) : nullptr};
     auto stage = [&](size_t g0) {      // caller memory -> pinned staging, one pool task per client
         uint8_t *sp = stg_buf[(g0 / G) & 1];
-        C.pool->run(std::min(G, nc - g0), [&](size_t i) { stage_copy(sp + i * d * 64, pairs[g0 + i], d * 64); });
+        C.pool->run(std::min(G, nc - g0), [&](size_t i) { stage_copy(sp + i * per, pairs[g0 + i], per); });
     };
     auto decode = [&](size_t g0) {
         const size_t gc = std::min(G, nc - g0);
-        HIPCHK(hipMemcpyAsync(dpairs, stg_buf[(g0 / G) & 1], gc * d * 64, hipMemcpyHostToDevice, C.stream));
+        HIPCHK(hipMemcpyAsync(dpairs, stg_buf[(g0 / G) & 1], gc * per, hipMemcpyHostToDevice, C.stream));
         count_decodes(2 * d * gc);
-        ROFL_LAUNCH(k_decode_pairs_batch, grid1(2 * d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const uint8_t *)dpairs, pts, status + g0);
+        if (stride == 64) ROFL_LAUNCH(k_decode_pairs_batch, grid1(2 * d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (const uint8_t *)dpairs, pts, status + g0);
+        else ROFL_LAUNCH(k_decode_pairs_strided_batch, grid1(2 * d, (u32)gc), dim3(TPB), 0, C.stream, (u32)d, (u32)stride, (const uint8_t *)dpairs, pts, status + g0);
     };
     if (d) { stage(0); decode(0); }
     std::vector<sc> c(nc);
-    compressed_challenges(C, nc, proofs, pairs, d, c.data());      // (the device decodes the first group meanwhile)
+    compressed_challenges(C, nc, proofs, pairs, d, c.data(), stride);      // (the device decodes the first group meanwhile)
     std::vector<CompClient> cl(nc);
     for (size_t i = 0; i < nc; i++) cl[i] = CompClient{c[i], pts + 2 * (i % G) * d, pts + (2 * (i % G) + 1) * d};
     std::vector<ge5> sumL, sumR;
@@ -1779,7 +1786,8 @@ int compressed_verify_batch(size_t nc, const uint8_t *const *proofs, const uint8
     timing_end(C);
     return ROFL_OK;
 }
-// compressed_verify_batch for the clients of a ROFL_ROUND_COMPRESSED round, from what ingest left on the device and in the round: nothing is
+// compressed_verify_batch for the clients of a round that keeps prefixes (ROFL_ROUND_COMPRESSED or rofl_round_create_rand; 64- or 96-byte
+// records, the slot arithmetic below holds for both), from what ingest left on the device and in the round: nothing is
 // uploaded but the power tables, nothing is decoded and no pair is hashed.  Per client with a proof and without a bad L or R (known since
 // ingest): the proof is parsed and, from a copy of the stored transcript state, c drawn, on the host pool -- a proof that does not parse is
 // out before anything is launched, as is a client left out or with a bad point (verdict 0 either way, as compressed_verify_batch gives them
@@ -1889,20 +1897,24 @@ int rofl_verify_compressed_randproof(const uint8_t proof[128], const uint8_t *pa
     return guarded([&]() -> int { return compressed_verify_batch(1, &proof, &pairs, d, ok_out, true); });
 }
 int rofl_verify_compressed_randproof_batch(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t d, int *ok_out) {
+    return rofl_verify_compressed_randproof_batch_strided(n_clients, proofs, pairs, 64, d, ok_out);
+}
+int rofl_verify_compressed_randproof_batch_strided(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *pairs, size_t stride, size_t d, int *ok_out) {
     // (a fixed cap on the round, half of kMaxBatchMembers as for the other batch entries; the clients themselves run in groups of sixteen)
+    if (stride != 64 && stride != 96) return fail(ROFL_BAD_PARAM, "bad parameter");
     if (!ok_out || (n_clients && (!proofs || !pairs)) || d >= 900000 || n_clients > kMaxBatchMembers / 2) return fail(ROFL_BAD_PARAM, "bad parameter");
     for (size_t i = 0; i < n_clients; i++) if (!proofs[i] || (d && !pairs[i])) return fail(ROFL_BAD_PARAM, "bad parameter");
     if (n_clients == 0) return ROFL_OK;
     std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
     if (devs.empty() || n_clients < 2)
         return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
-            return compressed_verify_batch(n_clients, proofs, pairs, d, ok_out); });
+            return compressed_verify_batch(n_clients, proofs, pairs, d, ok_out, false, stride); });
     for (size_t i = 0; i < n_clients; i++) ok_out[i] = 0;
     return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
         const size_t k = idx.size();
         std::vector<const uint8_t *> p(k), c(k); std::vector<int> ok(k, 0);
         for (size_t j = 0; j < k; j++) { p[j] = proofs[idx[j]]; c[j] = pairs[idx[j]]; }
-        int r = compressed_verify_batch(k, p.data(), c.data(), d, ok.data());
+        int r = compressed_verify_batch(k, p.data(), c.data(), d, ok.data(), false, stride);
         for (size_t j = 0; j < k; j++) ok_out[idx[j]] = ok[j];
         return r; }); });
 }
@@ -2304,11 +2316,14 @@ int rofl_acc_destroy(uint64_t h) {
 // ---- a round resident on the device: ingested once, verified and accumulated from the decoded points; a ROFL_ROUND_COMPRESSED round also
 // ---- hashes its CompressedRandProof transcript prefixes at ingest, and its compressed leg reads nothing but the round ----
 int rofl_round_create(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out) { return rofl_round_create_ex(d, record_len, max_clients, 0, handle_out); }
-int rofl_round_create_ex(size_t d, size_t record_len, size_t max_clients, unsigned flags, uint64_t *handle_out) {
+namespace {
+// what rofl_round_create_ex and rofl_round_create_rand share, after their own checks of (record_len, flags); keep_prefixes: ingest hashes
+// and keeps the CompressedRandProof transcript prefixes (Round::flags carries ROFL_ROUND_COMPRESSED for it, whatever the record length)
+int round_create(size_t d, size_t record_len, size_t max_clients, bool keep_prefixes, uint64_t *handle_out) {
     if (!handle_out || d == 0 || max_clients == 0 || (record_len != 64 && record_len != 96)) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (flags & ~(unsigned)ROFL_ROUND_COMPRESSED) return fail(ROFL_BAD_PARAM, "unknown round flag");
-    if ((flags & ROFL_ROUND_COMPRESSED) && (record_len != 64 || d >= 900000))      // (the label table of the reference's transcript ends there, as in rofl_verify_compressed_randproof)
-        return fail(ROFL_BAD_PARAM, "a compressed round holds 64-byte records of d < 900000");
+    if (keep_prefixes && d >= 900000)      // (the label table of the reference's transcript ends there, as in rofl_verify_compressed_randproof)
+        return fail(ROFL_BAD_PARAM, "a round that keeps CompressedRandProof transcripts holds records of d < 900000");
+    const unsigned flags = keep_prefixes ? ROFL_ROUND_COMPRESSED : 0u;
     const size_t npts = record_len / 32;
     size_t bytes;      // the larger array: max_clients * 2 npts * d decoded points
     if (__builtin_mul_overflow(max_clients, d, &bytes) || __builtin_mul_overflow(bytes, 2 * npts * sizeof(niels), &bytes)) return fail(ROFL_BAD_PARAM, "round too large");
@@ -2330,6 +2345,14 @@ int rofl_round_create_ex(size_t d, size_t record_len, size_t max_clients, unsign
     *handle_out = g_rounds.add(R);
     return ROFL_OK;
 }
+}  // namespace
+int rofl_round_create_ex(size_t d, size_t record_len, size_t max_clients, unsigned flags, uint64_t *handle_out) {
+    if (!handle_out || d == 0 || max_clients == 0 || (record_len != 64 && record_len != 96)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (flags & ~(unsigned)ROFL_ROUND_COMPRESSED) return fail(ROFL_BAD_PARAM, "unknown round flag");
+    if ((flags & ROFL_ROUND_COMPRESSED) && record_len != 64) return fail(ROFL_BAD_PARAM, "a compressed round holds 64-byte records of d < 900000 (96-byte records: rofl_round_create_rand)");
+    return round_create(d, record_len, max_clients, (flags & ROFL_ROUND_COMPRESSED) != 0, handle_out);
+}
+int rofl_round_create_rand(size_t d, size_t record_len, size_t max_clients, uint64_t *handle_out) { return round_create(d, record_len, max_clients, true, handle_out); }
 int rofl_round_ingest(uint64_t h, size_t n_clients, const uint8_t *const *records, size_t *first_index_out) {
     if (n_clients && !records) return fail(ROFL_BAD_PARAM, "bad parameter");
     return with_round<RoundExclusive>(h, nullptr, [&](Round &) -> int {
@@ -2363,7 +2386,7 @@ int rofl_round_verify_range(uint64_t h, const uint8_t *const *proofs, size_t pro
 int rofl_round_verify_compressed(uint64_t h, const uint8_t *const *proofs, int *ok_out) {
     if (!ok_out || !proofs) return fail(ROFL_BAD_PARAM, "bad parameter");
     return with_round<RoundShared>(h, &Round::comp_mu, [&](Round &R) -> int {
-        return !(R.flags & ROFL_ROUND_COMPRESSED) ? fail(ROFL_BAD_PARAM, "the round was not created with ROFL_ROUND_COMPRESSED") : ROFL_OK;
+        return !(R.flags & ROFL_ROUND_COMPRESSED) ? fail(ROFL_BAD_PARAM, "the round keeps no transcript prefixes (create it with ROFL_ROUND_COMPRESSED or rofl_round_create_rand)") : ROFL_OK;
     }, [&](Round &R) -> int {
         if (R.n == 0) return ROFL_OK;
         LaneLock lane_lock = acquire_lane(); return round_verify_compressed_impl(*lane_lock.c, R, proofs, ok_out); });
@@ -2856,6 +2879,46 @@ int rofl_dbg_host_merlin8_lbl3_selftest(int lanes, unsigned count, unsigned skew
     Merlin *t[8]; const uint8_t *msg[8];
     for (int l = 0; l < lanes; l++) { t[l] = &b[l]; msg[l] = data.data() + (size_t)l * count * 64; }
     k8::append_lbl3_run_x8(t, lanes, 0, msg, count);
+    double t2 = now_ms();
+    int bad = 0;
+    for (int l = 0; l < lanes; l++) {
+        bad |= a[l].pos != b[l].pos || a[l].pos_begin != b[l].pos_begin || a[l].cur_flags != b[l].cur_flags || memcmp(a[l].stw, b[l].stw, 200) != 0;
+        const uint8_t *cp = data.data() + data.size() - 64;
+        a[l].append("C_prime_eg", cp, 64); b[l].append("C_prime_eg", cp, 64);
+        uint8_t ca[64], cb[64]; a[l].challenge_bytes("c", ca, 64); b[l].challenge_bytes("c", cb, 64); bad |= memcmp(ca, cb, 64) != 0;
+    }
+    if (us_simd) *us_simd = (t2 - t1) * 1e3;
+    if (us_scalar) *us_scalar = (t1 - t0) * 1e3;
+    return bad;
+}
+// the same over records `stride` bytes apart (64 <= stride <= 256; bytes 64 .. stride of every record are filler that differs per lane and per
+// record): the strided x8 path against Merlin::append_lbl over the first 64 bytes of each record -- nothing of the filler may reach a state
+int rofl_dbg_host_merlin8_lbl3_strided_selftest(int lanes, unsigned count, unsigned skew, unsigned stride, double *us_simd, double *us_scalar) {
+    if (!k8::available()) return -1;
+    if (lanes < 1 || lanes > 8 || skew > 400 || stride < 64 || stride > 256) return ROFL_BAD_PARAM;
+    std::vector<uint8_t> data((size_t)8 * count * stride + 64);
+    for (size_t i = 0; i < data.size(); i++) data[i] = (uint8_t)((i * 2654435761u) >> 13);
+    for (int l = 0; l < 8; l++)
+        for (size_t i = 0; i < count; i++)
+            for (size_t b = 64; b < stride; b++) data[((size_t)l * count + i) * stride + b] = (uint8_t)(0xA5 ^ (37 * l + 11 * i + b));
+    std::vector<uint8_t> pre(skew, 0x5a);
+    std::vector<Merlin> a, b;
+    for (int l = 0; l < lanes; l++) { a.emplace_back("CompressedRandProof", 19); b.emplace_back("CompressedRandProof", 19); }
+    for (int l = 0; l < lanes; l++) {
+        a[l].append("dom-sep", (const uint8_t *)"randomness proof v1", 19); b[l].append("dom-sep", (const uint8_t *)"randomness proof v1", 19);
+        if (skew) { a[l].append("skew", pre.data(), skew); b[l].append("skew", pre.data(), skew); }
+    }
+    double t0 = now_ms();
+    for (int l = 0; l < lanes; l++)
+        for (size_t i = 0; i < count; i++) {
+            uint8_t lbl[3] = {(uint8_t)(3 * i), (uint8_t)(3 * i + 1), (uint8_t)(3 * i + 2)}, pair[64];
+            memcpy(pair, data.data() + ((size_t)l * count + i) * stride, 64);      // (the packed pair: the scalar side never sees the filler)
+            a[l].append_lbl(lbl, 3, pair, 64);
+        }
+    double t1 = now_ms();
+    Merlin *t[8]; const uint8_t *msg[8];
+    for (int l = 0; l < lanes; l++) { t[l] = &b[l]; msg[l] = data.data() + (size_t)l * count * stride; }
+    k8::append_lbl3_run_x8(t, lanes, 0, msg, count, stride);
     double t2 = now_ms();
     int bad = 0;
     for (int l = 0; l < lanes; l++) {

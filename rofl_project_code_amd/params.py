@@ -2,6 +2,7 @@
 
     EncParamsRange / EncParamsRangeCompressed / EncParamsL2 / EncParamsL2Compressed
         .encrypt(...)  .verify()  .serialize()  .deserialize(data)        rofl_service/src/flserver/params.rs:462-541, 683-775, 544-681, 790-885
+    EncParamsL2CompressedStrict: EncParamsL2Compressed whose verify() also checks the update's CompressedRandProof (the reference's arm skips it)
     EncModelParamsAccumulator (.unity, .accumulate_other, .extract)         params.rs:74-138
 
 Same names, argument meaning and composition as the reference; every group operation runs through the C ABI
@@ -542,6 +543,11 @@ class EncParamsL2:
     def _square_batch(us):
         return square_rand_proof_vec.verify_l2rangeproof_vec_batch([u.square_proofs for u in us], [u.enc_values for u in us], with_csq_sums=True)
 
+    _checks_rand = False      # a randomness leg of its own beside the square proofs (EncParamsL2CompressedStrict; here the SquareRandProofs bind R)
+
+    def _rand_key(self):      # the randomness leg's part of the shape key
+        return ()
+
     @classmethod
     def verify_batch(cls, updates, verifier_seed=None, fp=None, _legs=_HostLegs):
         """The server's side of a round (server.rs:656-687 hands every client's update to the verification pool; :474-484 rejects the round
@@ -559,11 +565,11 @@ class EncParamsL2:
             return res
         def shape(u):
             try:
-                return (u.enc_values.shape[0], u.square_proofs.shape[0], u.range_proofs.shape if u.range_proofs.ndim == 2 else None, u.square_range_proof.size, u.prove_range, u.l2_prove_range)
+                return (u.enc_values.shape[0], u.square_proofs.shape[0], u.range_proofs.shape if u.range_proofs.ndim == 2 else None, u.square_range_proof.size, u.prove_range, u.l2_prove_range) + u._rand_key()
             except AttributeError:
                 return None
         shapes = [shape(u) for u in updates]
-        ok_shape = [sh for sh in shapes if sh is not None and sh[0] == sh[1] and sh[0] > 0 and sh[2] is not None and sh[2][0] > 0]
+        ok_shape = [sh for sh in shapes if sh is not None and sh[0] == sh[1] and sh[0] > 0 and sh[2] is not None and sh[2][0] > 0 and all(sh[6:])]
         if not ok_shape:
             return [u.verify(verifier_seed=verifier_seed, fp=fp) if sh is not None else False for u, sh in zip(updates, shapes)]
         major = max(set(ok_shape), key=ok_shape.count)
@@ -579,9 +585,10 @@ class EncParamsL2:
             ok_sum = l2_range_proof_vec.verify_rangeproof_l2_batch([u.square_range_proof for u in us], sums, major[5], verifier_seed=_sub_seed(verifier_seed, b"s"), fp=fp)
             return ok_sq, ok_sum
         try:
-            (ok_sq, ok_sum), ok_range = _concurrently(
+            (ok_sq, ok_sum), ok_range, *ok_rand = _concurrently(
                 sigma_then_sum,
-                lambda: _legs.range(us, idx, major[0], major[4], _sub_seed(verifier_seed, b"v"), fp, 96))
+                lambda: _legs.range(us, idx, major[0], major[4], _sub_seed(verifier_seed, b"v"), fp, 96),
+                *([lambda: _legs.rand(cls, us, idx)] if cls._checks_rand else []))
         except (RoflError, ValueError, OverflowError, IndexError) as e:
             if not _is_message_error(e):
                 raise      # the verifier itself failed (HIP / RCCL runtime error): not a verdict about any client
@@ -592,7 +599,7 @@ class EncParamsL2:
             # (a call-level error -- a proof length no proof can have, a bit size outside 8 / 16 / 32 / 64: every member of this shape is malformed the same way)
             return [bool(r) for r in res]
         for k, i in enumerate(idx):
-            res[i] = bool(ok_sq[k] and ok_range[k] and ok_sum[k])
+            res[i] = bool(ok_sq[k] and ok_range[k] and ok_sum[k] and all(r[k] for r in ok_rand))
         return res
 
     def serialize(self, as_array=False):
@@ -683,24 +690,28 @@ class EncParamsL2Compressed(EncParamsL2):
         return out
 
     @staticmethod
-    def _square_batch(us):      # SquareProofCommitments { c_l: c.L, c_sq } (params.rs:262-266); as in verify(), the compressed randomness proof is not re-checked
+    def _square_batch(us):      # SquareProofCommitments { c_l: c.L, c_sq } (params.rs:262-266); the reference's arm skips the compressed randomness proof, as verify() does -- EncParamsL2CompressedStrict checks it
         return square_proof_vec.verify_l2rangeproof_vec_batch([u.square_proofs for u in us], [np.concatenate([u.enc_values[:, :32], u.enc_values[:, 64:96]], axis=1) for u in us], with_csq_sums=True)
 
     def verify(self, verifier_seed=None, fp=None):
-        """EncModelParams::verify, EncL2Compressed arm (params.rs:255-289).  NB: as in the reference, the compressed
-        randomness proof itself is not re-checked here (the arm only verifies the square proofs, the range proofs and the sum)."""
+        """EncModelParams::verify, EncL2Compressed arm (params.rs:255-289).  NB: the reference's arm skips the compressed randomness
+        proof (it only verifies the square proofs, the range proofs and the sum, none of which reads R), and so does this class, verdict
+        for verdict.  EncParamsL2CompressedStrict is the class that checks it."""
         fp = api._fp(fp)
         try:
-            sqc = np.concatenate([self.enc_values[:, :32], self.enc_values[:, 64:96]], axis=1)      # SquareProofCommitments { c_l: c.L, c_sq }
-            ok, ok_range, ok_sum = _concurrently(
-                lambda: square_proof_vec.verify_l2rangeproof_vec(self.square_proofs, sqc),
-                lambda: range_proof_vec.verify_rangeproof(self.range_proofs, self.enc_values[:, :32], self.prove_range, verifier_seed=_sub_seed(verifier_seed, b"v"), fp=fp),
-                lambda: l2_range_proof_vec.verify_rangeproof_l2(self.square_range_proof, self._sum_c_sq(), self.l2_prove_range, verifier_seed=_sub_seed(verifier_seed, b"s"), fp=fp))
+            oks = _concurrently(*self._verify_legs(verifier_seed, fp))
         except (RoflError, ValueError, OverflowError, IndexError) as e:
             if not _is_message_error(e):
                 raise      # a fault of the verifier, not a verdict (see _MESSAGE_ERRORS)
             return False
-        return bool(ok and ok_range and ok_sum)
+        return all(bool(ok) for ok in oks)
+
+    def _verify_legs(self, verifier_seed, fp):
+        """the legs of verify() as thunks that run side by side: the SquareProofs, the L-inf range proofs, the L2 sum proof"""
+        sqc = np.concatenate([self.enc_values[:, :32], self.enc_values[:, 64:96]], axis=1)      # SquareProofCommitments { c_l: c.L, c_sq }
+        return [lambda: square_proof_vec.verify_l2rangeproof_vec(self.square_proofs, sqc),
+                lambda: range_proof_vec.verify_rangeproof(self.range_proofs, self.enc_values[:, :32], self.prove_range, verifier_seed=_sub_seed(verifier_seed, b"v"), fp=fp),
+                lambda: l2_range_proof_vec.verify_rangeproof_l2(self.square_range_proof, self._sum_c_sq(), self.l2_prove_range, verifier_seed=_sub_seed(verifier_seed, b"s"), fp=fp)]
 
     def serialize(self, as_array=False):
         return wire.encode(self.kind, enc_values=self.enc_values, square_proof=self.square_proofs, rand_proof=self.rand_proof,
@@ -713,6 +724,30 @@ class EncParamsL2Compressed(EncParamsL2):
         if m["enc_values"].size % 96 or m["square_proof"].size % 160 or m["rand_proof"].size != 128:
             raise RoflError(5, "FormatError")
         return cls(m["enc_values"], m["square_proof"], m["rand_proof"], m["range_proofs"], m["square_range_proof"], m["range_bits"], m["l2_range_bits"])
+
+
+class EncParamsL2CompressedStrict(EncParamsL2Compressed):
+    """EncParamsL2Compressed -- same wire kind, same bytes, same encrypt / encrypt_batch / serialize / deserialize -- whose verify() and
+    verify_batch() also check the update's CompressedRandProof, over enc_values in place (the pair is the first 64 bytes of every 96-byte
+    record).  The reference's EncL2Compressed arm (params.rs:257-289) never reads rand_proof: the SquareProofs and the range proofs read
+    only L and c_sq, so ANY valid points pass as R, the round's aggregate R is then not the identity, extract() returns None and the
+    server cannot tell which client did it.  This class is the opt-in that closes the hole; a verdict is True only if the three legs of
+    EncParamsL2Compressed and the randomness proof all hold."""
+    _checks_rand = True
+
+    def _rand_key(self):      # the size of the one CompressedRandProof (128 when well-formed: anything else is off the majority shape)
+        return (self.rand_proof.size == 128,)
+
+    @staticmethod
+    def _rand_batch(us):
+        return compressed_rand_proof.helper_verify_batch_strided([u.rand_proof for u in us], [u.enc_values for u in us], 96)
+
+    def _verify_legs(self, verifier_seed, fp):
+        """verify() runs four legs side by side and is true only if all four are: the three of EncParamsL2Compressed and the
+        CompressedRandProof (params.rs:235-256, the check of the EncRangeCompressed arm) over (L, R) of enc_values in place.  A proof
+        that is not 128 bytes is False there without reaching the library."""
+        return EncParamsL2Compressed._verify_legs(self, verifier_seed, fp) + [
+            lambda: compressed_rand_proof.helper_verify_batch_strided([self.rand_proof], [self.enc_values], 96)[0]]
 
 
 class EncModelParamsAccumulator:
@@ -864,18 +899,23 @@ class DeviceRound:
     A round of EncParamsRangeCompressed also hashes, at ingest, each update's CompressedRandProof transcript up to the proof's C' from the
     bytes that go to the device (rofl_round_create_ex, ROFL_ROUND_COMPRESSED): its randomness leg continues those transcripts over the
     decoded points (rofl_round_verify_compressed) and, like every other leg, gives its verdict about the snapshot that accumulate_into
-    adds.  The round lives on the device of the thread that created it."""
+    adds.  A round of EncParamsL2CompressedStrict does the same over its 96-byte records (rofl_round_create_rand: the pair is the first 64
+    bytes of each); a round of EncParamsL2Compressed hashes nothing at ingest and checks no randomness proof, as the reference's arm.
+    The round lives on the device of the thread that created it."""
 
     def __init__(self, cls, size, max_clients):
-        if cls not in (EncParamsRange, EncParamsRangeCompressed, EncParamsL2, EncParamsL2Compressed):
-            raise ValueError("cls must be one of the four encrypted-update containers")
+        if cls not in (EncParamsRange, EncParamsRangeCompressed, EncParamsL2, EncParamsL2Compressed, EncParamsL2CompressedStrict):
+            raise ValueError("cls must be one of the encrypted-update containers")
         self.cls, self.size, self.max_clients = cls, int(size), int(max_clients)
         self.record_len = 96 if issubclass(cls, EncParamsL2) else 64
         self.updates, self._slot, self._n_cached = [], [], 0
         self._open = False
         # (d >= 900 000 is past what a CompressedRandProof can have: such a round keeps the host call, which refuses it member by member)
-        self._compressed = cls is EncParamsRangeCompressed and self.size < 900000
-        self._h = api.device_round.create(self.size, self.record_len, self.max_clients, api.device_round.COMPRESSED if self._compressed else 0)
+        self._compressed = cls in (EncParamsRangeCompressed, EncParamsL2CompressedStrict) and self.size < 900000
+        if self._compressed and cls is EncParamsL2CompressedStrict:
+            self._h = api.device_round.create_rand(self.size, self.record_len, self.max_clients)
+        else:
+            self._h = api.device_round.create(self.size, self.record_len, self.max_clients, api.device_round.COMPRESSED if self._compressed else 0)
         self._open = True
 
     def __len__(self):
@@ -926,9 +966,10 @@ class DeviceRound:
         return p
 
     def rand(self, cls, us, idx):
-        if not self._on_round(idx) or (cls is EncParamsRangeCompressed and not self._compressed):
+        comp = cls in (EncParamsRangeCompressed, EncParamsL2CompressedStrict)      # one CompressedRandProof per update
+        if not self._on_round(idx) or (comp and not self._compressed):
             return _HostLegs.rand(cls, us, idx)
-        if cls is EncParamsRangeCompressed:
+        if comp:
             ok = api.device_round.verify_compressed(self._h, self._ptrs(us, idx, lambda u: u.rand_proof))
             return [ok[self._slot[i]] for i in idx]
         ok, _ = api.device_round.verify_sigma(self._h, 0, self._ptrs(us, idx, lambda u: u.rand_proofs))
@@ -937,7 +978,7 @@ class DeviceRound:
     def square(self, cls, us, idx):
         if not self._on_round(idx):
             return _HostLegs.square(cls, us, idx)
-        ok, sums = api.device_round.verify_sigma(self._h, 2 if cls is EncParamsL2Compressed else 1, self._ptrs(us, idx, lambda u: u.square_proofs), want_csq=True)
+        ok, sums = api.device_round.verify_sigma(self._h, 2 if issubclass(cls, EncParamsL2Compressed) else 1, self._ptrs(us, idx, lambda u: u.square_proofs), want_csq=True)
         sl = [self._slot[i] for i in idx]
         return [ok[s] for s in sl], sums[sl]
 

@@ -1835,6 +1835,13 @@ __global__ void __launch_bounds__(TPB) k_dbg_quad(u32 pairs, u32 doublings, cons
 #endif
 
 // ================================================================ K8/K9: verification
+// How the one-thread-per-point decoders read a compressed point from global memory (src 16-byte aligned): two 16-byte loads into a private
+// copy, then the decoder.  What a kernel does with a point that does not decode -- a status bit, an index, skip it, the identity -- is its own.
+__device__ __forceinline__ bool gd_load_decode(gd &p, const uint8_t *src) {
+    __align__(16) uint8_t b[32];
+    reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
+    return gd_ristretto_decode(p, b);
+}
 // decode compressed points into affine niels (+ validity); optional re-encode of the point shifted by `shift`
 // (verify_rangeproof: range_proof_vec/mod.rs:155-167).  out_niels is the UNSHIFTED point.
 #if ROFL_KG(4)
@@ -1853,11 +1860,8 @@ __global__ void __launch_bounds__(TPB) k_decode(u32 count, u32 valid_count, cons
         if (out_enc) { uint4 z = make_uint4(0, 0, 0, 0); reinterpret_cast<uint4 *>(out_enc + (size_t)i * 32)[0] = z; reinterpret_cast<uint4 *>(out_enc + (size_t)i * 32)[1] = z; }
         return;
     }
-    __align__(16) uint8_t b[32];
-    const uint4 *s = reinterpret_cast<const uint4 *>(in + (size_t)i * 32);
-    reinterpret_cast<uint4 *>(b)[0] = s[0]; reinterpret_cast<uint4 *>(b)[1] = s[1];
     gd p;
-    if (!gd_ristretto_decode(p, b)) { atomicOr(status, 4u); p = gd_identity(); }
+    if (!gd_load_decode(p, in + (size_t)i * 32)) { atomicOr(status, 4u); p = gd_identity(); }
     // the niels form is that of the DECODED point (Z = 1: no inversion chain); a caller that wants sum_j s_j (P_j + shift) from an MSM
     // over these points adds (sum_j s_j) * shift itself (verify_chunks does: the shift is a multiple of B)
     if (out_niels) { niels r; r.ypx = fd_pack(fd_add(p.Y, p.X)); r.ymx = fd_pack(fd_sub(p.Y, p.X)); r.t2d = fd_pack(fd_mul(p.T, fd_d2())); store_niels(&out_niels[i], r); }
@@ -2364,49 +2368,18 @@ __global__ void __launch_bounds__(TPB) k_sigma_vdecode(int kind, u32 d, const ui
     if (t >= (size_t)nslots * d) return;
     u32 slot = (u32)(t / d), i = (u32)(t % d);
     const uint8_t *src = (slot & 1) ? proofs + (y * d + i) * plen + 32 * (slot >> 1) : commits + (y * d + i) * clen + 32 * (slot >> 1);
-    __align__(16) uint8_t b[32];
-    reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
     gd p;
-    if (!gd_ristretto_decode(p, b)) { atomicOr(status + y, 4u); p = gd_identity(); }
+    if (!gd_load_decode(p, src)) { atomicOr(status + y, 4u); p = gd_identity(); }
     store_niels(&pts[(y * nslots + slot) * d + i], sg_affine_niels(p));
 }
 #endif
 // ---- compressed_rand_proof: the d ElGamal pairs, the challenge-power dot products, the verification scalars
-#if ROFL_KG(3)
-__global__ void __launch_bounds__(64) k_eg_pairs(u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *rc, const uint8_t *existing,
-                                                 const niels *tabB, const niels *tabBb, uint8_t *pairs, u32 *status) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d) return;
-    float v = vals[i];
-    if (v != v) { atomicOr(status, 2u); return; }
-    sc m = sg_f32_to_sc(v, fp_bits, fp_frac), r = load_sc_reduced(&rc[i]);
-    uint8_t *o = pairs + (size_t)64 * i;
-    if (existing) { gd L; if (!sg_decode(L, existing + (size_t)32 * i)) { atomicOr(status, 4u); return; } for (int q = 0; q < 32; q++) o[q] = existing[(size_t)32 * i + q]; }
-    else sg_encode(o, gd_add(sg_fixed_mul8(tabB, m), sg_fixed_mul8(tabBb, r)));      // (radix-256 tables)
-    sg_encode(o + 32, sg_fixed_mul8(tabB, r));
-}
-#endif
-// partial sums of m_i c^(i+1) and r_i c^(i+1)  -> out[blk][2] (Montgomery);  cpow2[b] = c^(2^b) (Montgomery)
-struct CPow { sc sq[MAX_LG]; };
-#if ROFL_KG(3)
-__global__ void __launch_bounds__(TPB) k_cpow_dot(u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *rc, CPow cp, sc *out) {
-    __shared__ sc lds[TPB * 2];
-    sc v[2] = {sc_zero(), sc_zero()};
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < d; i += gridDim.x * blockDim.x) {
-        sc p = sc_pow_tab(cp.sq, i + 1);
-        sc m = sc_to_mont(sg_f32_to_sc(vals[i], fp_bits, fp_frac)), r = sc_to_mont(load_sc(&rc[i]));
-        v[0] = sc_add(v[0], sc_montmul(m, p)); v[1] = sc_add(v[1], sc_montmul(r, p));
-    }
-    block_sum_sc<2>(v, lds);
-    if (threadIdx.x == 0) { store_sc(&out[blockIdx.x * 2], v[0]); store_sc(&out[blockIdx.x * 2 + 1], v[1]); }
-}
-#endif
-// The prover's two kernels for a GROUP of clients (rofl_create_compressed_randproof_batch): client y = blockIdx.y, its d values at
-// vals + y d, its d blindings at rc + y d, its commitments to complete (bit y of ex_mask) at existing + 32 y d, its pairs at
-// pairs + 64 y d, its status word at status + y -- a NaN or an undecodable commitment marks ITS client only.
-// k_eg_pairs_batch: ONE THREAD PER POINT, as k_sigma_points has it: blockIdx.z = 0 computes L_i = m_i B + r_i B~ (or checks and copies
-// the commitment handed in), blockIdx.z = 1 computes R_i = r_i B, so that a block runs one formula and a pair's two encodings (a 254-step
-// chain each) run side by side instead of one after the other.  Same formulas as k_eg_pairs, same bytes.
+// The prover's two kernels for a GROUP of clients (rofl_create_compressed_randproof_batch; rofl_create_compressed_randproof is a group of
+// one): client y = blockIdx.y, its d values at vals + y d, its d blindings at rc + y d, its commitments to complete (bit y of ex_mask) at
+// existing + 32 y d, its pairs at pairs + 64 y d, its status word at status + y -- a NaN or an undecodable commitment marks ITS client only.
+// k_eg_pairs_batch: ONE THREAD PER POINT, as k_sigma_points has it: blockIdx.z = 0 computes L_i = m_i B + r_i B~ (radix-256 tables; or
+// checks and copies the commitment handed in), blockIdx.z = 1 computes R_i = r_i B, so that a block runs one formula and a pair's two
+// encodings (a 254-step chain each) run side by side instead of one after the other.
 #if ROFL_KG(3)
 __global__ void __launch_bounds__(64) k_eg_pairs_batch(u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *rc, const uint8_t *existing, u32 ex_mask,
                                                        const niels *tabB, const niels *tabBb, uint8_t *pairs, u32 *status /* [gridDim.y] */) {
@@ -2425,9 +2398,9 @@ __global__ void __launch_bounds__(64) k_eg_pairs_batch(u32 d, const float *vals,
     } else sg_encode(o, gd_add(sg_fixed_mul8(tabB, sg_f32_to_sc(v, fp_bits, fp_frac)), sg_fixed_mul8(tabBb, r)));
 }
 #endif
-// k_cpow_dot for a group: client y's table sq[y * MAX_LG + b] = c_y^(2^b) (Montgomery) is read from device memory as k_cpow_rows reads
-// it; partial sums of m_i c_y^(i+1) and r_i c_y^(i+1) -> out[(y * gridDim.x + blk) * 2 + {0, 1}] (Montgomery).  Scalar sums are exact:
-// any block count gives the same totals.
+// k_cpow_dot_batch: client y's table sq[y * MAX_LG + b] = c_y^(2^b) (Montgomery) is read from device memory as k_cpow_rows reads it;
+// partial sums of m_i c_y^(i+1) and r_i c_y^(i+1) -> out[(y * gridDim.x + blk) * 2 + {0, 1}] (Montgomery).  Scalar sums are exact: any
+// block count gives the same totals.
 #if ROFL_KG(3)
 __global__ void __launch_bounds__(TPB) k_cpow_dot_batch(u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *rc, const sc *sq, sc *out) {
     __shared__ sc lds[TPB * 2];
@@ -2468,10 +2441,8 @@ __global__ void __launch_bounds__(TPB) k_decode_pairs_strided_batch(u32 d, u32 r
     if (t >= 2 * d) return;
     u32 i = t >> 1, which = t & 1;
     const uint8_t *src = rec + (y * d + i) * rec_len + 32 * which;
-    __align__(16) uint8_t b[32];
-    reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
     gd p;
-    if (!gd_ristretto_decode(p, b)) { atomicOr(status + y, 4u); p = gd_identity(); }
+    if (!gd_load_decode(p, src)) { atomicOr(status + y, 4u); p = gd_identity(); }
     store_niels(&pts[(2 * y + which) * d + i], gd_to_niels(p));
 }
 #endif
@@ -2514,10 +2485,8 @@ __global__ void __launch_bounds__(TPB) k_acc_decode_partial(u32 tn, u32 S, u32 n
     for (u32 k = s; k < nc; k += S) {
         if (j >= cnt[k]) continue;
         const uint8_t *src = rec + (off[k] + j) * 64 + 32 * which;
-        __align__(16) uint8_t b[32];
-        reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
         gd p;
-        if (!gd_ristretto_decode(p, b)) { atomicOr(status, 4u); continue; }
+        if (!gd_load_decode(p, src)) { atomicOr(status, 4u); continue; }
         acc = gd_add(acc, p);
     }
     store_gd(&part[t], acc);
@@ -2565,10 +2534,8 @@ __global__ void __launch_bounds__(TPB) k_round_ingest(u32 d, u32 npts, const uin
     if (t >= (size_t)npts * d) return;
     u32 slot = (u32)(t / d), i = (u32)(t % d);
     const uint8_t *src = rec + ((y * d + i) * npts + slot) * 32;
-    __align__(16) uint8_t b[32];
-    reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
     gd p;
-    if (!gd_ristretto_decode(p, b)) { atomicMin(&bad[y * 3 + slot], i); p = gd_identity(); }
+    if (!gd_load_decode(p, src)) { atomicMin(&bad[y * 3 + slot], i); p = gd_identity(); }
     store_niels(&pts[((y * npts + slot) * 2) * d + i], sg_affine_niels(p));
 }
 #endif
@@ -2583,10 +2550,8 @@ __global__ void __launch_bounds__(TPB) k_sigma_vdecode_proofs(int kind, u32 d, c
     if (t >= (size_t)npts * d) return;
     u32 k = (u32)(t / d), i = (u32)(t % d);
     const uint8_t *src = proofs + (y * d + i) * plen + 32 * k;
-    __align__(16) uint8_t b[32];
-    reinterpret_cast<uint4 *>(b)[0] = reinterpret_cast<const uint4 *>(src)[0]; reinterpret_cast<uint4 *>(b)[1] = reinterpret_cast<const uint4 *>(src)[1];
     gd p;
-    if (!gd_ristretto_decode(p, b)) { atomicOr(status + y, 4u); p = gd_identity(); }
+    if (!gd_load_decode(p, src)) { atomicOr(status + y, 4u); p = gd_identity(); }
     store_niels(&pts[(y * nslots + 2 * k + 1) * d + i], sg_affine_niels(p));
 }
 #endif

@@ -775,6 +775,26 @@ void compressed_challenges(Ctx &C, size_t nc, const uint8_t *const *proofs, cons
     compressed_prefixes(C, nc, pairs, d, t.data(), stride);
     for (size_t j = 0; j < nc; j++) out[j] = compressed_challenge(t[j], proofs[j]);
 }
+// One array of a group of gc clients onto the device, on the lane's stream: client j's `per` bytes src(j) (null: the client has none, its
+// slot is left alone) go to dst + j per.  Host clients are staged on the pool (~256 KB per task) into the pinned stg + j per and uploaded
+// run by run; then the clients that on_dev(j) names are copied on the device.  True if anything was uploaded from stg (the caller records
+// the event that guards its reuse).
+template <class Src, class OnDev>
+bool bring_group(Ctx &C, size_t gc, uint8_t *dst, uint8_t *stg, size_t per, Src src, OnDev on_dev) {
+    const size_t slices = std::max<size_t>(1, per >> 18);
+    auto host = [&](size_t j) { return src(j) && !on_dev(j); };
+    bool any = false; for (size_t j = 0; j < gc; j++) any |= host(j);
+    if (any) C.pool->run(gc * slices, [&](size_t t) { const size_t j = t / slices, k = t % slices; if (!host(j)) return;
+                                             const size_t lo = per * k / slices, hi = per * (k + 1) / slices; stage_copy(stg + j * per + lo, src(j) + lo, hi - lo); });
+    for (size_t j = 0; j < gc; ) {      // one upload per run of host clients
+        if (!host(j)) { j++; continue; }
+        size_t e = j; while (e < gc && host(e)) e++;
+        HIPCHK(hipMemcpyAsync(dst + j * per, stg + j * per, (e - j) * per, hipMemcpyHostToDevice, C.stream));
+        j = e;
+    }
+    for (size_t j = 0; j < gc; j++) if (src(j) && on_dev(j)) HIPCHK(hipMemcpyAsync(dst + j * per, src(j), per, hipMemcpyDeviceToDevice, C.stream));
+    return any;
+}
 // clients [R.n, R.n + n): the records go up in groups of ~64 MB through two pinned staging buffers (the pool copies group g + 1 while group g
 // is on its way and being decoded; device-resident records are copied on the device), one k_round_ingest per group: every point decoded once.
 // A ROFL_ROUND_COMPRESSED round hashes each group's transcript prefixes on the pool while the device uploads and decodes the group: host
@@ -800,19 +820,9 @@ int round_ingest_impl(Ctx &C, Round &R, size_t n, const uint8_t *const *records)
             if (!stb[b]) stb[b] = (uint8_t *)C.stg.alloc(G * per); else if (uploaded[b]) C.wait_event(C.pool_event(b));
         }
         uint8_t *st = stb[b];
-        if (any_host) {
-            const size_t slices = std::max<size_t>(1, per >> 18);      // ~256 KB per task
-            C.pool->run(gc * slices, [&](size_t t) { size_t i = t / slices, k = t % slices; if (on_dev[g0 + i]) return;
-                                                     size_t lo = per * k / slices, hi = per * (k + 1) / slices; stage_copy(st + i * per + lo, records[g0 + i] + lo, hi - lo); });
-            for (size_t i = 0; i < gc; ) {      // one upload per run of host clients
-                if (on_dev[g0 + i]) { i++; continue; }
-                size_t j = i; while (j < gc && !on_dev[g0 + j]) j++;
-                HIPCHK(hipMemcpyAsync(dst + i * per, st + i * per, (j - i) * per, hipMemcpyHostToDevice, C.stream));
-                i = j;
-            }
-            HIPCHK(hipEventRecord(C.pool_event(b), C.stream)); uploaded[b] = true;
-        }
-        for (size_t i = 0; i < gc; i++) if (on_dev[g0 + i]) HIPCHK(hipMemcpyAsync(dst + i * per, records[g0 + i], per, hipMemcpyDeviceToDevice, C.stream));
+        // (the event marks the end of the uploads from st -- and of the device copies queued behind them, which cost nothing to wait for)
+        if (bring_group(C, gc, dst, st, per, [&](size_t i) { return records[g0 + i]; }, [&](size_t i) { return (bool)on_dev[g0 + i]; })) {
+            HIPCHK(hipEventRecord(C.pool_event(b), C.stream)); uploaded[b] = true; }
         if (comp && any_dev) {      // the round's copy of the device records comes back once, for the transcripts (before the decode is queued: the wait below covers copies only)
             for (size_t i = 0; i < gc; i++) if (on_dev[g0 + i]) HIPCHK(hipMemcpyAsync(st + i * per, dst + i * per, per, hipMemcpyDeviceToHost, C.stream));
             HIPCHK(hipEventRecord(C.pool_event(2), C.stream));
@@ -1491,64 +1501,10 @@ int sigma_verify(int kind, const uint8_t *proofs, const uint8_t *commits, size_t
     return sigma_verify_batch(kind, 1, &proofs, &commits, d, ok_out, nullptr, true);
 }
 // ---- compressed_rand_proof
-int compressed_create(const float *values, size_t d, const uint8_t *r32, size_t d_r, const uint8_t *existing, unsigned fp_bits, unsigned fp_frac,
-                      const rofl_nonce_t *nonce, uint8_t *proof_out, uint8_t *pairs_out) {
-    LaneLock lane_lock = acquire_lane(false, true); Ctx &C = *lane_lock.c;
-    if (d != d_r) return fail(ROFL_WRONG_NUM_BLINDING, "WrongNumBlindingFactors");
-    if (!valid_fp(fp_bits, fp_frac) || !nonce || d >= 900000) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (nonce->mode == 0 && nonce->stream_scalars < 2) return fail(ROFL_NONCE_SHORT, "nonce stream too short");
-    C.init();
-    timing_begin(C);
-    size_t dd = d ? d : 1;
-    float *dv = C.vals.as<float>(dd); sc *dr = C.tmp_in.as<sc>(dd);
-    uint8_t *dex = existing ? C.Cbytes.as<uint8_t>(dd * 32) : nullptr;
-    uint8_t *dpairs = C.aux_scal.as<uint8_t>(dd * 64);
-    u32 *status = C.status.as<u32>(4);
-    HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
-    const uint8_t *pairs_host = pairs_out;      // where the pairs can be read on the host after the wait (the staging copy of a large transfer)
-    if (d) {
-        C.up(dv, values, 4 * d, C.stream);
-        C.up(dr, r32, 32 * d, C.stream);
-        if (dex) C.up(dex, existing, 32 * d, C.stream);
-        ROFL_LAUNCH(k_eg_pairs, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, C.stream, (u32)d, dv, fp_bits, fp_frac, dr, dex, C.d_tabB8, C.d_tabBb8, dpairs, status);
-        pairs_host = (const uint8_t *)C.down(pairs_out, dpairs, 64 * d, C.stream);
-    }
-    u32 st = 0;
-    HIPCHK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, C.stream));
-    C.sync();
-    if (st & 2u) return fail(ROFL_NON_FINITE, "non-finite value (the reference panics in fixed::saturating_from_float)");
-    if (st & 4u) return fail(ROFL_FORMAT_ERROR, "invalid Ristretto encoding");
-    // nonces m', r' (party.rs:66-67), C' = commit(m', r')
-    sc nc[2];
-    for (int j = 0; j < 2; j++) {
-        uint8_t b[32];
-        if (nonce->mode == 1) rofl_dbg_host_nonce(nonce->seed, (uint64_t)j, b);
-        else { sc w = sc_from_wide(sc_frombytes(nonce->stream + 64 * j), sc_frombytes(nonce->stream + 64 * j + 32)); sc_tobytes(b, w); }
-        nc[j] = sc_frombytes(b);
-    }
-    h51::encode(proof_out, h51::gadd(h_fixed_mul(C.ht.B5, nc[0]), h_fixed_mul(C.ht.Bb5, nc[1])));
-    h51::encode(proof_out + 32, h_fixed_mul(C.ht.B5, nc[1]));
-    sc c; const uint8_t *proof = proof_out;
-    compressed_challenges(C, 1, &proof, &pairs_host, d, &c);
-    sc zm = nc[0], zr = nc[1];
-    if (d) {
-        CPow cp; fill_pow2(cp.sq, h_mont(c), MAX_LG);
-        u32 nblk = (u32)std::min<size_t>(64, (d + TPB - 1) / TPB);
-        sc *part = C.tmp_out.as<sc>(64 * 2);
-        ROFL_LAUNCH(k_cpow_dot, dim3(nblk), dim3(TPB), 0, C.stream, (u32)d, dv, fp_bits, fp_frac, dr, cp, part);
-        sc hp[128];
-        HIPCHK(hipMemcpyAsync(hp, part, sizeof(sc) * nblk * 2, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        zm = sc_add(zm, h_canon(sum_partials(hp, nblk, 2, 0))); zr = sc_add(zr, h_canon(sum_partials(hp, nblk, 2, 1)));
-    }
-    sc_tobytes(proof_out + 64, zm); sc_tobytes(proof_out + 96, zr);
-    timing_end(C);
-    return ROFL_OK;
-}
-// compressed_create for the clients of one process (the reference's client binary runs its clients as tasks of one process,
-// client.rs:265-266): client i's proof and pairs are byte for byte what compressed_create gives it; rcs[i] is its own outcome (NaN 10,
-// an undecodable commitment 5, a mode-0 stream of fewer than two scalars 12 -- that one before any device work) and a client that fails is
-// left out from there on.  d alone is less than one wave per SIMD for the pairs and a handful of blocks for the dot products; the clients
+// The CompressedRandProofs of the clients of one process (the reference's client binary runs its clients as tasks of one process,
+// client.rs:265-266); the one-client call is a group of one.  rcs[i] is client i's own outcome (NaN 10 before an undecodable commitment 5; a
+// mode-0 stream of fewer than two scalars 12 -- that one before any device work) and a client that fails is left out from there on.
+// d alone is less than one wave per SIMD for the pairs and a handful of blocks for the dot products; the clients
 // go in GROUPS of at most sixteen (gridDim.y, one bit of the pairs kernel's `existing` mask each) and at most ~64 MB of staged bytes.
 // Per group: the inputs are staged on the host pool and uploaded (device-resident inputs are copied on the device), k_eg_pairs_batch
 // computes every pair one thread per point, and the pairs come back into pinned memory -- they are the output and the transcripts'
@@ -1558,7 +1514,7 @@ int compressed_create(const float *values, size_t d, const uint8_t *r32, size_t 
 // The upload and the pairs launch of group g + 1 are enqueued BEFORE the host turns to group g (two sets of device and staging buffers
 // alternate), so the device computes the next group's pairs while the host hashes: two waits per group instead of two per client.
 constexpr size_t kCompCreateGroup = 16;      // clients per launch: a row of gridDim.y and a bit of the pairs kernel's `existing` mask each
-constexpr u32 kCompDotBlocks = 64;      // per client, as k_cpow_dot: a group of sixteen is 1 024 blocks of four waves, four waves on every SIMD of 256 CUs
+constexpr u32 kCompDotBlocks = 64;      // per client: a group of sixteen is 1 024 blocks of four waves, four waves on every SIMD of 256 CUs
 int compressed_create_batch(size_t nc, const float *const *values, size_t d, const uint8_t *const *r32, const uint8_t *const *existing, unsigned fp_bits,
                             unsigned fp_frac, const rofl_nonce_t *nonces, uint8_t *const *proofs_out, uint8_t *const *pairs_out, int *rcs) {
     std::vector<size_t> act;      // the clients that reach the device
@@ -1612,27 +1568,13 @@ int compressed_create_batch(size_t nc, const float *const *values, size_t d, con
     sc *htab = C.h_cp.as<sc>(G * MAX_LG), *hpart = C.h_part.as<sc>(G * 2 * kCompDotBlocks);
     uint8_t *stg_in[2] = {nullptr, nullptr}, *stg_out[2] = {nullptr, nullptr};
     for (size_t b = 0; b < nbuf; b++) { if (any_host) stg_in[b] = (uint8_t *)C.stg.alloc(G * in_per); stg_out[b] = (uint8_t *)C.stg.alloc(G * out_per); }
-    // one array of a group: host clients staged on the pool (~256 KB per task) and uploaded run by run, device clients copied on the device
-    auto bring = [&](size_t a0, size_t gc, uint8_t *dst, uint8_t *stg, size_t per, const std::vector<char> &on_dev, const std::vector<char> *present,
-                     const std::function<const uint8_t *(size_t)> &src) {
-        const size_t slices = std::max<size_t>(1, per >> 18);
-        auto host = [&](size_t j) { return (!present || (*present)[a0 + j]) && !on_dev[a0 + j]; };
-        bool any = false; for (size_t j = 0; j < gc; j++) any |= host(j);
-        if (any) C.pool->run(gc * slices, [&](size_t t) { const size_t j = t / slices, k = t % slices; if (!host(j)) return;
-                                                 const size_t lo = per * k / slices, hi = per * (k + 1) / slices; stage_copy(stg + j * per + lo, src(a0 + j) + lo, hi - lo); });
-        for (size_t j = 0; j < gc; ) {
-            if (!host(j)) { if ((!present || (*present)[a0 + j])) HIPCHK(hipMemcpyAsync(dst + j * per, src(a0 + j), per, hipMemcpyDeviceToDevice, C.stream)); j++; continue; }
-            size_t e = j; while (e < gc && host(e)) e++;
-            HIPCHK(hipMemcpyAsync(dst + j * per, stg + j * per, (e - j) * per, hipMemcpyHostToDevice, C.stream));
-            j = e;
-        }
-    };
     auto enqueue = [&](size_t g) {      // upload, pairs, download of group g into buffer set g & 1; event g & 1 marks the end
         const size_t a0 = g * G, gc = std::min(G, na - a0), b = g & (nbuf - 1);
         uint8_t *si = stg_in[b];
-        bring(a0, gc, (uint8_t *)(dv + b * G * d), si, 4 * d, dev_v, nullptr, [&](size_t a) { return (const uint8_t *)values[act[a]]; });
-        bring(a0, gc, (uint8_t *)(dr + b * G * d), si ? si + G * 4 * d : nullptr, 32 * d, dev_r, nullptr, [&](size_t a) { return r32[act[a]]; });
-        bring(a0, gc, dex + b * G * d * 32, si ? si + G * 36 * d : nullptr, 32 * d, dev_e, &has_e, [&](size_t a) { return existing[act[a]]; });
+        bring_group(C, gc, (uint8_t *)(dv + b * G * d), si, 4 * d, [&](size_t j) { return (const uint8_t *)values[act[a0 + j]]; }, [&](size_t j) { return (bool)dev_v[a0 + j]; });
+        bring_group(C, gc, (uint8_t *)(dr + b * G * d), si ? si + G * 4 * d : nullptr, 32 * d, [&](size_t j) { return r32[act[a0 + j]]; }, [&](size_t j) { return (bool)dev_r[a0 + j]; });
+        bring_group(C, gc, dex + b * G * d * 32, si ? si + G * 36 * d : nullptr, 32 * d, [&](size_t j) { return has_e[a0 + j] ? existing[act[a0 + j]] : nullptr; },
+                    [&](size_t j) { return (bool)dev_e[a0 + j]; });
         u32 ex_mask = 0; for (size_t j = 0; j < gc; j++) if (has_e[a0 + j]) ex_mask |= 1u << j;
         ROFL_LAUNCH(k_eg_pairs_batch, dim3((unsigned)((d + 63) / 64), (unsigned)gc, 2), dim3(64), 0, C.stream, (u32)d, (const float *)(dv + b * G * d), fp_bits, fp_frac,
                     (const sc *)(dr + b * G * d), (const uint8_t *)(dex + b * G * d * 32), ex_mask, C.d_tabB8, C.d_tabBb8, dpairs + b * G * out_per, status + a0);
@@ -1649,7 +1591,7 @@ int compressed_create_batch(size_t nc, const float *const *values, size_t d, con
         std::vector<size_t> good;                // positions in the group
         for (size_t j = 0; j < gc; j++) {
             const u32 st = h_st[a0 + j];
-            rcs[act[a0 + j]] = (st & 2u) ? ROFL_NON_FINITE : (st & 4u) ? ROFL_FORMAT_ERROR : ROFL_OK;      // (the single call's order)
+            rcs[act[a0 + j]] = (st & 2u) ? ROFL_NON_FINITE : (st & 4u) ? ROFL_FORMAT_ERROR : ROFL_OK;
             if (!(st & 6u)) good.push_back(j);
         }
         if (good.empty()) continue;
@@ -1891,7 +1833,18 @@ int rofl_verify_squareproof_vec(const uint8_t *proofs, const uint8_t *commits, s
 }
 int rofl_create_compressed_randproof(const float *values, size_t d, const uint8_t *r32, size_t d_r, const uint8_t *existing32, unsigned fp_bits, unsigned fp_frac,
                                      const rofl_nonce_t *nonce, uint8_t proof_out[128], uint8_t *pairs_out) {
-    return guarded([&]() -> int { return compressed_create(values, d, r32, d_r, existing32, fp_bits, fp_frac, nonce, proof_out, pairs_out); });
+    return guarded([&]() -> int {      // a batch of one on the caller's device (the batch entry would bind the first of the `devices` option)
+        if (d != d_r) return fail(ROFL_WRONG_NUM_BLINDING, "WrongNumBlindingFactors");
+        if (!valid_fp(fp_bits, fp_frac) || !nonce || d >= 900000) return fail(ROFL_BAD_PARAM, "bad parameter");
+        int rc = ROFL_OK;
+        int r = compressed_create_batch(1, &values, d, &r32, &existing32, fp_bits, fp_frac, nonce, &proof_out, &pairs_out, &rc);
+        if (r != ROFL_OK) return r;
+        switch (rc) {
+            case ROFL_NONCE_SHORT: return fail(rc, "nonce stream too short");
+            case ROFL_NON_FINITE: return fail(rc, "non-finite value (the reference panics in fixed::saturating_from_float)");
+            case ROFL_FORMAT_ERROR: return fail(rc, "invalid Ristretto encoding");
+        }
+        return rc; });
 }
 int rofl_verify_compressed_randproof(const uint8_t proof[128], const uint8_t *pairs, size_t d, int *ok_out) {
     return guarded([&]() -> int { return compressed_verify_batch(1, &proof, &pairs, d, ok_out, true); });

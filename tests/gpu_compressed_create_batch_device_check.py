@@ -29,4 +29,16 @@ got2 = R.compressed_rand_proof.helper_prove_batch([torch.from_numpy(x).cuda() fo
                                                   nonces=[R.Nonce.seeded(s) for s in seeds], fp=FP)
 for i in range(n):
     assert (got2[i][0] == want2[i][0]).all() and (got2[i][1] == want2[i][1]).all(), i
+# the single call (the C entry itself: helper_prove takes host arrays) on device-resident values, r and existing: the host-input bytes
+import ctypes
+from rofl_project_code_amd import api
+for i, with_ex in ((0, True), (2, False)):
+    tv, tr, te = torch.from_numpy(xs[i]).cuda(), torch.from_numpy(bls[i]).cuda(), torch.from_numpy(np.ascontiguousarray(coms[i])).cuda()
+    ns = R.Nonce.seeded(seeds[i])._struct()
+    proof, pairs = np.zeros(128, np.uint8), np.zeros((d, 64), np.uint8)
+    rc = api.lib().rofl_create_compressed_randproof(ctypes.c_void_p(tv.data_ptr()), ctypes.c_size_t(d), ctypes.c_void_p(tr.data_ptr()), ctypes.c_size_t(d),
+                                                    ctypes.c_void_p(te.data_ptr()) if with_ex else None, FP[0], FP[1], ctypes.byref(ns),
+                                                    proof.ctypes.data_as(ctypes.c_void_p), pairs.ctypes.data_as(ctypes.c_void_p))
+    w = want[i] if with_ex else want2[i]
+    assert rc == 0 and (proof == w[0]).all() and (pairs == w[1]).all(), ("single call, device inputs", i, rc)
 print("DEVICE_INPUTS PASS")

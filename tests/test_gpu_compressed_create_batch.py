@@ -2,6 +2,10 @@
 process in one launch sequence -- groups of sixteen clients, k_eg_pairs_batch (one thread per point, blocks of 64 elements) and
 k_cpow_dot_batch (64 blocks of 256 per client, grid-stride).  Every client's proof and pairs must be the bytes of its own single call
 (helper_prove / helper_prove_existing) and of the CPU oracle (orc.compressed_create), whatever its neighbours in the batch are.
+The single call (rofl_create_compressed_randproof) runs the same code as a group of one: "batch equals single" says that a client's
+neighbours do not matter, and the oracle -- or, at the one shape where its create is too slow, another kernel and the verifiers -- anchors
+the bytes of both.  The single call's own promises are here too: its error order and texts, device-resident inputs, the caller's device
+under the `devices` option.
 
 Shapes: d around the pairs kernel's block (63, 64, 65) and the dot kernel's block (255, 256, 257), 0 and 1; n = 1, 2 and 17 (a second
 group, of one); d = 64 * 256 + 1, where the dot kernel's grid-stride loop wraps for exactly one thread."""
@@ -61,12 +65,17 @@ def _one(R, d, i, mode, existing=False):
     return _single[key]
 
 
-def _orc(R, d, i, mode):
-    key = (d, i, mode)
+def _orc(R, d, i, mode, existing=False):
+    key = (d, i, mode, existing)
     if key not in _oracle:
-        x, bl, _ = _client(R, d, i)
-        _oracle[key] = orc.compressed_create(x, bl, FP[0], FP[1], **_nonce(R, i, mode)[1])
+        x, bl, com = _client(R, d, i)
+        _oracle[key] = orc.compressed_create(x, bl, FP[0], FP[1], existing=com if existing else None, **_nonce(R, i, mode)[1])
     return _oracle[key]
+
+
+def _is_oracle(got, want):
+    """got = (proof, pairs) against the oracle's (rc, proof, pairs)"""
+    return want[0] == 0 and _same(got, want[1:])
 
 
 def _same(got, want):
@@ -81,20 +90,51 @@ def test_bytes_equal_the_single_call_and_the_oracle(R, n, d, mode):
     assert len(got) == n
     for i in range(n):
         assert _same(got[i], _one(R, d, i, mode)), ("single call", i)
+        assert _is_oracle(_one(R, d, i, mode), _orc(R, d, i, mode)), ("single call against the oracle", i)
         rc, oproof, opairs = _orc(R, d, i, mode)
         assert rc == 0 and _same(got[i], (oproof, opairs)), ("oracle", i)
         assert R.compressed_rand_proof.helper_verify(got[i][0], got[i][1]) is True
         assert orc.compressed_verify(got[i][0], got[i][1]) == (0, True)
 
 
+@pytest.mark.parametrize("mode", ["seed", "stream"])
+@pytest.mark.parametrize("d", DS)
+def test_the_single_call_equals_the_oracle(R, d, mode):
+    """helper_prove alone against orc.compressed_create: the single call is a group of one, so "batch equals single" compares two group
+    compositions and the oracle is the anchor of the bytes."""
+    got = _one(R, d, 0, mode)
+    assert _is_oracle(got, _orc(R, d, 0, mode))
+    assert R.compressed_rand_proof.helper_verify(got[0], got[1]) is True
+
+
+@pytest.mark.parametrize("mode", ["seed", "stream"])
+def test_the_single_call_with_existing_equals_the_oracle(R, mode):
+    d = 65
+    x, bl, com = _client(R, d, 0)
+    got = R.compressed_rand_proof.helper_prove_existing(x, com, bl, nonce=_nonce(R, 0, mode)[0], fp=FP)
+    assert _is_oracle(got, _orc(R, d, 0, mode, existing=True))
+    assert _same(got, _one(R, d, 0, mode, existing=True))
+    assert (got[1][:, :32] == com).all()
+
+
 def test_the_dot_products_grid_stride_wraps(R):
-    """d = 64 * 256 + 1: thread 0 of block 0 of every client takes a second element.  Against the single call only (the oracle at this size
-    takes too long, and the single call is pinned to it elsewhere)."""
+    """d = 64 * 256 + 1: thread 0 of block 0 of every client takes a second element.  The oracle's create at this size takes too long, so
+    the bytes of the single call and of the batch of two are anchored without it: the pairs' L are pedersen_ops.commit_vec's (another
+    kernel), C' (the proof's first 64 bytes, which do not depend on d) is that of the oracle's proof at d = 1 under the same nonce, and
+    the library's and the oracle's verifiers accept.  Given the pairs, C' and the challenge, the two equations fix Z_m, Z_r: all 128
+    bytes are pinned."""
     d, n = DOT_BLOCKS * 256 + 1, 2
     cl = [_client(R, d, i) for i in range(n)]
     got = R.compressed_rand_proof.helper_prove_batch([c[0] for c in cl], [c[1] for c in cl], nonces=[_nonce(R, i, "seed")[0] for i in range(n)], fp=FP)
     for i in range(n):
-        assert _same(got[i], _one(R, d, i, "seed")), i
+        one = _one(R, d, i, "seed")
+        assert _same(got[i], one), i
+        for proof, pairs in (one, got[i]):
+            assert (pairs[:, :32] == cl[i][2]).all(), i
+            rc1, proof1, _ = _orc(R, 1, i, "seed")
+            assert rc1 == 0 and (proof[:64] == proof1[:64]).all(), i
+            assert R.compressed_rand_proof.helper_verify(proof, pairs) is True
+        assert orc.compressed_verify(one[0], one[1]) == (0, True)
 
 
 @pytest.mark.parametrize("with_existing", [(False, True, False), (True, False, True)], ids=["middle", "outer"])
@@ -105,6 +145,7 @@ def test_mixed_existing(R, with_existing):
                                                       existing_list=[c[2] if e else None for c, e in zip(cl, with_existing)], fp=FP)
     for i in range(n):
         assert _same(got[i], _one(R, d, i, "seed", existing=with_existing[i])), i
+        assert _is_oracle(got[i], _orc(R, d, i, "seed", existing=with_existing[i])), ("oracle", i)
 
 
 def test_a_failing_member_does_not_sink_the_call(R):
@@ -129,6 +170,36 @@ def test_a_failing_member_does_not_sink_the_call(R):
     assert e.value.code == 10
 
 
+def _raises(R, code, text, *args, **kw):
+    """the single call fails with `code` and rofl_last_error's text `text`"""
+    with pytest.raises(R.RoflError) as e:
+        R.compressed_rand_proof.helper_prove(*args, **kw)
+    assert e.value.code == code and str(e.value) == "%s (%d): %s" % (e.value.name, code, text), str(e.value)
+
+
+def test_the_single_calls_error_order_and_texts(R):
+    """WrongNumBlindingFactors (1) before a bad parameter (11) before a short stream (12), all before any device work; then a non-finite
+    value (10) before an undecodable commitment (5).  Codes as rofl_zk.h numbers them, texts as rofl_last_error gives them."""
+    d = 65
+    x, bl, com = _client(R, d, 0)
+    nonce = _nonce(R, 0, "seed")[0]
+    short = R.Nonce.stream(bytes(range(64)))      # one wide scalar: m' without r'
+    xnan = x.copy(); xnan[40] = np.nan
+    bad = com.copy(); bad[64] = 0xFF
+    NAN = "non-finite value (the reference panics in fixed::saturating_from_float)"
+    _raises(R, 1, "WrongNumBlindingFactors", x, bl[:-1], nonce=nonce, fp=FP)
+    _raises(R, 1, "WrongNumBlindingFactors", xnan, bl[:-1], nonce=short, existing=bad, fp=(16, 16))      # before everything else
+    _raises(R, 11, "bad parameter", x, bl, nonce=nonce, fp=(16, 16))
+    _raises(R, 11, "bad parameter", x, bl, nonce=nonce, fp=(12, 7))
+    _raises(R, 11, "bad parameter", xnan, bl, nonce=short, existing=bad, fp=(16, 16))                    # before the stream's length
+    _raises(R, 12, "nonce stream too short", x, bl, nonce=short, fp=FP)
+    _raises(R, 12, "nonce stream too short", xnan, bl, nonce=short, existing=bad, fp=FP)                 # before the device sees the values
+    _raises(R, 10, NAN, xnan, bl, nonce=nonce, fp=FP)
+    _raises(R, 10, NAN, xnan, bl, nonce=nonce, existing=bad, fp=FP)                                      # before the commitment
+    _raises(R, 5, "invalid Ristretto encoding", x, bl, nonce=nonce, existing=bad, fp=FP)
+    assert _same(R.compressed_rand_proof.helper_prove(x, bl, nonce=nonce, fp=FP), _one(R, d, 0, "seed"))      # (and the next call is sound)
+
+
 def test_device_resident_inputs():
     """One client's values, r and existing as device pointers (torch tensors on the GPU), its neighbours' in host memory: same bytes.
     (Own process: torch has to bring up its HIP runtime before the library's is loaded.)"""
@@ -146,7 +217,9 @@ def test_devices_option(R):
     try:
         R.set_option("devices", 0b11)
         got = R.compressed_rand_proof.helper_prove_batch([c[0] for c in cl], [c[1] for c in cl], nonces=[_nonce(R, i, "seed")[0] for i in range(n)], existing_list=ex, fp=FP)
+        one = [R.compressed_rand_proof.helper_prove(cl[i][0], cl[i][1], nonce=_nonce(R, i, "seed")[0], existing=ex[i], fp=FP) for i in (0, 3)]      # the single call under the option
     finally:
         R.set_option("devices", 0)
     for i in range(n):
         assert _same(got[i], _one(R, d, i, "seed", existing=i == 3)), i
+    assert _is_oracle(one[0], _orc(R, d, 0, "seed")) and _is_oracle(one[1], _orc(R, d, 3, "seed", existing=True))

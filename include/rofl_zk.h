@@ -168,6 +168,23 @@ int rofl_create_rangeproof_l2(const float *values, size_t d, const uint8_t *blin
                               size_t prove_range, size_t n_partition, unsigned fp_bits, unsigned fp_frac,
                               const rofl_nonce_t *nonce, uint8_t *proof_out, size_t *proof_len_out,
                               uint8_t commit_out[32]);
+/* client side: create_rangeproof_l2 for n_clients clients of one process (client.rs:265-266) in one launch sequence: one kernel sums every
+ * client's squares and blindings, the host adds each client's f32 shadow terms in the reference's serial order and decides, and the
+ * one-value Bulletproofs of all surviving clients are ONE prove_multiple launch sequence with one set of host hops.  proofs_out[i]
+ * (*proof_len_out = 32 * (9 + 2 lg prove_range) bytes each) and commits_out32 + 32 i are byte for byte what rofl_create_rangeproof_l2
+ * returns for (values[i], blindings32[i], nonces[i]); client i's nonces sit at index 0 of its own stream or seed.  values[i] (d floats) and
+ * blindings32[i] (d scalars) are host or device memory (the single call reads its values on the host).  rc_out[i] is exactly the code the
+ * single call returns for client i, decided in its order: 2 ValueOutOfRangeError (it wins over a NaN wherever the two sit: the range loop
+ * runs to its end first), 10 non-finite, 8 OverflowError, 7 NormOutOfRangeError, 3 InvalidBitsize, 12 nonce stream too short -- a client
+ * that fails is left out, its outputs are unspecified, and the others are still proved.  The return value is non-zero only for errors of
+ * the whole call: a HIP error, or 11 (bad parameter) before the device is touched -- invalid (fp_bits, fp_frac), d = 0 or d >= 2^28,
+ * n_partition = 0, prove_range = 0 or > 128, 2 * n_clients > 65 535, a null pointer or a null values[i], blindings32[i] or proofs_out[i].
+ * n_clients = 0 returns 0.  With rofl_set_option("devices", mask) the clients are dealt round-robin to the listed devices. */
+int rofl_create_rangeproof_l2_batch(size_t n_clients, const float *const *values, size_t d, const uint8_t *const *blindings32,
+                                    size_t prove_range, size_t n_partition, unsigned fp_bits, unsigned fp_frac,
+                                    const rofl_nonce_t *nonces /* [n_clients] */,
+                                    uint8_t *const *proofs_out /* 32 * (9 + 2 lg prove_range) bytes each */, size_t *proof_len_out,
+                                    uint8_t *commits_out32 /* n_clients * 32 */, int *rc_out);
 /* verify_rangeproof_l2 :185-253 */
 int rofl_verify_rangeproof_l2(const uint8_t *proof, size_t proof_len, const uint8_t commit[32],
                               size_t prove_range, unsigned fp_bits, unsigned fp_frac,
@@ -221,6 +238,27 @@ int rofl_create_squareproof_vec(const float *values, size_t d, const uint8_t *r1
 int rofl_verify_squareproof_vec(const uint8_t *proofs, const uint8_t *commits, size_t d, int *ok_out);
 int rofl_verify_squareproof_vec_batch(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *commits, size_t d,
                                       int *ok_out, uint8_t *csq_sum_out32);
+/* client side: the per-element Sigma-proof vectors of n_clients clients of one process (client.rs:265-266 hosts its clients as tasks of one
+ * process) in one launch sequence -- groups of at most sixteen clients, each group three kernel launches with the client on a grid
+ * dimension of its own, one host wait per group instead of one per client.  kind 0: RandProof, 1: SquareRandProof, 2: SquareProof.
+ * proofs_out[i] and commits_out[i] (host memory; d * 128 / 192 / 160 and d * 64 / 96 / 64 bytes) are byte for byte what
+ * rofl_create_randproof_vec / rofl_create_squarerandproof_vec / rofl_create_squareproof_vec returns for (values[i], r1_32[i], r2_32[i],
+ * existing32[i], nonces[i]); client i's nonce index space is its own: element e draws at nn * e of nonces[i] (nn = 2 for kind 0, else 3).
+ * values[i] (d floats), r1_32[i], r2_32[i] (d scalars; r2_32 may be NULL for kind 0) and existing32[i] (d commitments to complete; the
+ * array or any entry may be NULL) are host or device memory.  rc_out[i] is client i's own outcome: 0, 10 (a non-finite value), 5 (an
+ * existing32[i] entry that does not decode; a client with both reports 10, as the single calls do) or 12 (a mode-0 stream of fewer than
+ * nn * d scalars, decided before any device work) -- a client that fails is left out, its outputs are not written, and the others are still
+ * proved.  The return value is non-zero only for errors of the whole call: a HIP error, or 11 (bad parameter) before the device is touched --
+ * a kind outside 0..2, invalid (fp_bits, fp_frac), d >= 2^28, more than 65 535 clients, with n_clients > 0 a null nonces or rc_out or, for
+ * kind != 0, a null r2_32, and with d > 0 as well a null values, r1_32, proofs_out or commits_out or a null entry of one of them (of r2_32
+ * too for kind != 0).  n_clients = 0 returns 0; d = 0 returns 0 with every rc_out[i] = 0 and writes nothing else.  With
+ * rofl_set_option("devices", mask) the clients are dealt round-robin to the listed devices. */
+int rofl_create_sigmaproof_vec_batch(int kind /* 0 RandProof, 1 SquareRandProof, 2 SquareProof */, size_t n_clients,
+                                     const float *const *values, size_t d, const uint8_t *const *r1_32,
+                                     const uint8_t *const *r2_32 /* NULL for kind 0 */,
+                                     const uint8_t *const *existing32 /* NULL, or entries NULL */, unsigned fp_bits, unsigned fp_frac,
+                                     const rofl_nonce_t *nonces /* [n_clients] */, uint8_t *const *proofs_out,
+                                     uint8_t *const *commits_out, int *rc_out);
 /* compressed_rand_proof/mod.rs:43-102, 134-160 (helper_prove, helper_prove_existing, helper_verify): ONE 128-byte proof
  * C'.L|C'.R|Z_m|Z_r for all d ElGamal pairs (d*64 B), z = nonce + sum_i x_i c^(i+1); nonces m', r' at index 0, 1.
  * d < 900 000 (size of the reference's label table UNIQUE_U8_TRIPLETS). */

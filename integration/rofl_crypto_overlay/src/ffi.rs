@@ -134,6 +134,17 @@ extern "C" {
     pub fn rofl_create_compressed_randproof_batch(n_clients: usize, values: *const *const c_float, d: usize, r32: *const *const u8,
         existing32: *const *const u8, fp_bits: c_uint, fp_frac: c_uint, nonces: *const RoflNonce, proofs_out: *const *mut u8,
         pairs_out: *const *mut u8, rc_out: *mut c_int) -> c_int;
+    /// the per-element Sigma-proof vectors (kind 0 RandProof, 1 SquareRandProof, 2 SquareProof) of the clients of one process in one launch
+    /// sequence; proofs_out[i] / commits_out[i] are the single call's bytes for client i, rc_out[i] its own outcome (0, 10, 5, 12: it is
+    /// left out, the others are still proved); r2_32 is null for kind 0, existing32 or any of its entries may be null
+    pub fn rofl_create_sigmaproof_vec_batch(kind: c_int, n_clients: usize, values: *const *const c_float, d: usize, r1_32: *const *const u8,
+        r2_32: *const *const u8, existing32: *const *const u8, fp_bits: c_uint, fp_frac: c_uint, nonces: *const RoflNonce,
+        proofs_out: *const *mut u8, commits_out: *const *mut u8, rc_out: *mut c_int) -> c_int;
+    /// the L2 sum proofs of the clients of one process in one launch sequence; proofs_out[i] / commits_out32 + 32 i are the single call's
+    /// bytes for client i, rc_out[i] the code the single call returns for it (it is left out, the others are still proved)
+    pub fn rofl_create_rangeproof_l2_batch(n_clients: usize, values: *const *const c_float, d: usize, blindings32: *const *const u8,
+        prove_range: usize, n_partition: usize, fp_bits: c_uint, fp_frac: c_uint, nonces: *const RoflNonce, proofs_out: *const *mut u8,
+        proof_len_out: *mut usize, commits_out32: *mut u8, rc_out: *mut c_int) -> c_int;
     pub fn rofl_sum_points(points: *const u8, d: usize, stride: usize, out32: *mut u8) -> c_int;
     pub fn rofl_f32_to_scalar_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out32: *mut u8) -> c_int;
     pub fn rofl_scalar_to_f32_vec(in32: *const u8, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
@@ -222,6 +233,35 @@ pub fn bytes_to_points(b: &[u8]) -> Vec<RistrettoPoint> {
 }
 pub fn bytes_to_scalars(b: &[u8]) -> Vec<Scalar> {
     b.chunks(32).map(|c| { let mut a = [0u8; 32]; a.copy_from_slice(c); Scalar::from_canonical_bytes(a).expect("canonical") }).collect()
+}
+/// rofl_create_sigmaproof_vec_batch over typed inputs: the bytes (proofs, commitments) of every client, for the `*_batch` wrappers of
+/// rand_proof_vec, square_rand_proof_vec and square_proof_vec.  All vectors have the length of values[0]; r2 is None for kind 0.  A
+/// client whose inputs the library refuses (a non-finite value, an undecodable commitment) panics as in the single calls.
+pub fn sigma_create_batch_bytes(kind: c_int, proof_len: usize, commit_len: usize, values: &[&Vec<f32>], existing: &[Option<&Vec<RistrettoPoint>>],
+                                r1: &[&Vec<Scalar>], r2: Option<&[&Vec<Scalar>]>) -> Vec<(Vec<u8>, Vec<u8>)> {
+    let n = values.len();
+    if n == 0 { return Vec::new(); }
+    let d = values[0].len();
+    let a: Vec<Vec<u8>> = r1.iter().map(|v| scalars_to_bytes(v)).collect();
+    let b: Option<Vec<Vec<u8>>> = r2.map(|r| r.iter().map(|v| scalars_to_bytes(v)).collect());
+    let ex: Vec<Option<Vec<u8>>> = existing.iter().map(|c| c.map(|v| points_to_bytes(v))).collect();
+    let mut proofs: Vec<Vec<u8>> = (0..n).map(|_| vec![0u8; d * proof_len]).collect();
+    let mut commits: Vec<Vec<u8>> = (0..n).map(|_| vec![0u8; d * commit_len]).collect();
+    let nonces: Vec<RoflNonce> = (0..n).map(|_| fresh_nonce()).collect();
+    let vp: Vec<*const f32> = values.iter().map(|v| v.as_ptr()).collect();
+    let ap: Vec<*const u8> = a.iter().map(|v| v.as_ptr()).collect();
+    let bp: Option<Vec<*const u8>> = b.as_ref().map(|b| b.iter().map(|v| v.as_ptr()).collect());
+    let ep: Vec<*const u8> = ex.iter().map(|e| e.as_ref().map_or(std::ptr::null(), |v| v.as_ptr())).collect();
+    let pp: Vec<*mut u8> = proofs.iter_mut().map(|v| v.as_mut_ptr()).collect();
+    let cp: Vec<*mut u8> = commits.iter_mut().map(|v| v.as_mut_ptr()).collect();
+    let mut rcs: Vec<c_int> = vec![0; n];
+    let rc = unsafe {
+        rofl_create_sigmaproof_vec_batch(kind, n, vp.as_ptr(), d, ap.as_ptr(), bp.as_ref().map_or(std::ptr::null(), |v| v.as_ptr()), ep.as_ptr(),
+                                         fp_bits(), fp_frac(), nonces.as_ptr(), pp.as_ptr(), cp.as_ptr(), rcs.as_mut_ptr())
+    };
+    if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+    for i in 0..n { if rcs[i] != ROFL_OK { panic!("rofl_zk: client {} of the batch: error {}", i, rcs[i]); } }
+    proofs.into_iter().zip(commits.into_iter()).collect()
 }
 pub fn last_error() -> String {
     let mut buf = vec![0 as c_char; 512];

@@ -49,3 +49,38 @@ pub fn verify_rangeproof_l2(range_proof: &RangeProof, commit: &RistrettoPoint, p
         _ => panic!("rofl_zk: {}", last_error()),
     }
 }
+
+/// `create_rangeproof_l2` for the clients of one process (client.rs:265-266 runs them as tasks of one process): ONE
+/// rofl_create_rangeproof_l2_batch call -- one kernel for every client's sums, one Bulletproof launch sequence for all sum proofs.  Entry i
+/// is what `create_rangeproof_l2` returns for client i, its error included.
+pub fn create_rangeproof_l2_batch(value_vecs: &[&Vec<f32>], blinding_vecs: &[&Vec<Scalar>], prove_range: usize, n_partition: usize)
+    -> Vec<Result<(RangeProof, RistrettoPoint), L2RangeProofError>> {
+    let n = value_vecs.len();
+    if n == 0 { return Vec::new(); }
+    let d = value_vecs[0].len();
+    if blinding_vecs.len() != n || (0..n).any(|i| value_vecs[i].len() != d || blinding_vecs[i].len() != d) {
+        return (0..n).map(|_| Err(ProofError::WrongNumBlindingFactors.into())).collect();
+    }
+    let bl: Vec<Vec<u8>> = blinding_vecs.iter().map(|v| scalars_to_bytes(v)).collect();
+    let mut proofs: Vec<Vec<u8>> = (0..n).map(|_| vec![0u8; 32 * (9 + 2 * 7)]).collect();
+    let mut commits = vec![0u8; 32 * n];
+    let mut plen = 0usize;
+    let nonces: Vec<RoflNonce> = (0..n).map(|_| fresh_nonce()).collect();
+    let vp: Vec<*const f32> = value_vecs.iter().map(|v| v.as_ptr()).collect();
+    let bp: Vec<*const u8> = bl.iter().map(|v| v.as_ptr()).collect();
+    let pp: Vec<*mut u8> = proofs.iter_mut().map(|v| v.as_mut_ptr()).collect();
+    let mut rcs: Vec<std::os::raw::c_int> = vec![0; n];
+    let rc = unsafe {
+        rofl_create_rangeproof_l2_batch(n, vp.as_ptr(), d, bp.as_ptr(), prove_range, n_partition, fp_bits(), fp_frac(), nonces.as_ptr(),
+                                        pp.as_ptr(), &mut plen, commits.as_mut_ptr(), rcs.as_mut_ptr())
+    };
+    if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+    (0..n).map(|i| match rcs[i] {
+        ROFL_OK => Ok((RangeProof::from_bytes(&proofs[i][..plen]).expect("librofl_zk proof layout"),
+                       CompressedRistretto::from_slice(&commits[32 * i..32 * i + 32]).decompress().expect("valid encoding"))),
+        ROFL_NORM_OUT_OF_RANGE => Err(L2RangeProofError::NormOutOfRangeError(format!("client {} of the batch", i))),
+        ROFL_OVERFLOW => Err(L2RangeProofError::OverflowError(format!("client {} of the batch", i), String::new())),
+        ROFL_INVALID_BITSIZE => Err(ProofError::InvalidBitsize.into()),
+        code => panic!("Should not get here: client {} of the batch: error {}", i, code),
+    }).collect()
+}

@@ -41,3 +41,17 @@ pub fn verify_randproof_vec(randproof_vec: &Vec<RandProof>, commit_vec: &Vec<ElG
     if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
     Ok(ok != 0)
 }
+/// `create_randproof_vec` / `create_randproof_vec_existing` for the clients of one process (client.rs:265-266 runs them as tasks of one
+/// process): ONE rofl_create_sigmaproof_vec_batch call, every client's result what its own call returns.  existing[i] = None: no
+/// commitments to complete for client i.
+pub fn create_randproof_vec_batch(value_vecs: &[&Vec<f32>], existing: &[Option<&Vec<RistrettoPoint>>], random_vecs: &[&Vec<Scalar>])
+    -> Result<Vec<(Vec<RandProof>, Vec<ElGamalPair>)>, RandProofError> {
+    let n = value_vecs.len();
+    if random_vecs.len() != n || existing.len() != n { return Err(RandProofError::WrongNumBlindingFactors); }
+    for i in 0..n {
+        if value_vecs[i].len() != value_vecs[0].len() || random_vecs[i].len() != value_vecs[0].len() { return Err(RandProofError::WrongNumBlindingFactors); }
+    }
+    Ok(sigma_create_batch_bytes(0, PROOF_LEN, PAIR_LEN, value_vecs, existing, random_vecs, None).into_iter().map(|(p, c)| {
+        (p.chunks(PROOF_LEN).map(|x| RandProof::from_bytes(x).unwrap()).collect(), c.chunks(PAIR_LEN).map(|x| ElGamalPair::from_bytes(x).unwrap()).collect())
+    }).collect())
+}

@@ -71,3 +71,19 @@ pub fn verify_l2rangeproof_vec_batch(proofs: &[&Vec<SquareProof>], commits: &[&V
     if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
     Ok((ok.iter().map(|&x| x != 0).collect(), bytes_to_points(&sums)))
 }
+/// `create_l2rangeproof_vec` / `create_l2rangeproof_vec_existing` for the clients of one process (client.rs:265-266 runs them as tasks of
+/// one process): ONE rofl_create_sigmaproof_vec_batch call, every client's result what its own call returns.  existing[i] = None: no
+/// commitments to complete for client i.
+pub fn create_l2rangeproof_vec_batch(value_vecs: &[&Vec<f32>], existing: &[Option<&Vec<RistrettoPoint>>], random_vecs: &[&Vec<Scalar>],
+                                     random_vecs_2: &[&Vec<Scalar>])
+    -> Result<Vec<(Vec<SquareProof>, Vec<SquareProofCommitments>)>, L2RangeProofError> {
+    let n = value_vecs.len();
+    if random_vecs.len() != n || random_vecs_2.len() != n || existing.len() != n { return Err(L2RangeProofError::WrongNumBlindingFactors); }
+    for i in 0..n {
+        let d = value_vecs[0].len();
+        if value_vecs[i].len() != d || random_vecs[i].len() != d || random_vecs_2[i].len() != d { return Err(L2RangeProofError::WrongNumBlindingFactors); }
+    }
+    Ok(sigma_create_batch_bytes(2, PROOF_LEN, COMMIT_LEN, value_vecs, existing, random_vecs, Some(random_vecs_2)).into_iter().map(|(p, c)| {
+        (p.chunks(PROOF_LEN).map(|x| SquareProof::from_bytes(x).unwrap()).collect(), c.chunks(COMMIT_LEN).map(|x| SquareProofCommitments::from_bytes(x).unwrap()).collect())
+    }).collect())
+}

@@ -485,6 +485,39 @@ class l2_range_proof_vec:
         return proof[:plen.value].copy(), commit
 
     @staticmethod
+    def create_rangeproof_l2_batch(values_list, blindings_list, prove_range, n_partition, nonces=None, fp=None):
+        """rofl_create_rangeproof_l2_batch: create_rangeproof_l2 for several clients (same d) of one process as one launch sequence.
+        -> list of (proof, commit) per client, byte-identical to the per-client call with the same nonce; a client whose own inputs are
+        rejected gets a RoflError instance with the per-client call's code in its place, the others are proved.  values / blindings of a
+        client may be numpy arrays or torch tensors on the library's GPU."""
+        nc = len(values_list)
+        if nc == 0:
+            return []
+        if len(blindings_list) != nc or (nonces is not None and len(nonces) != nc):
+            raise ValueError("values_list, blindings_list and nonces must have one entry per client")
+        keep, vptrs, bptrs = [], [], []
+        d = None
+        for v, b in zip(values_list, blindings_list):
+            (vp, dv), (bp, db) = _client_arg(v, np.float32, 1, keep), _client_arg(b, np.uint8, 32, keep)
+            if dv != db:
+                raise RoflError(1, "WrongNumBlindingFactors")
+            if d is not None and dv != d:
+                raise ValueError("the clients of a batch have the same number of values")
+            d = dv
+            vptrs.append(vp); bptrs.append(bp)
+        nonces = nonces or [Nonce.random() for _ in range(nc)]
+        ns = (_NonceStruct * nc)(*[n._struct() for n in nonces])
+        proofs = [np.zeros(32 * (9 + 2 * 7), dtype=np.uint8) for _ in range(nc)]
+        commits = np.zeros((nc, 32), dtype=np.uint8)
+        vp = (ctypes.c_void_p * nc)(*vptrs); bp = (ctypes.c_void_p * nc)(*bptrs)
+        pp = (ctypes.c_void_p * nc)(*[p.ctypes.data for p in proofs])
+        rcs = (ctypes.c_int * nc)()
+        plen = _sz()
+        _check(lib().rofl_create_rangeproof_l2_batch(_sz(nc), vp, _sz(d), bp, _sz(prove_range), _sz(n_partition), *_fp(fp), ns, pp, ctypes.byref(plen),
+                                                     _ptr(commits), rcs))
+        return [(proofs[i][:plen.value].copy(), commits[i].copy()) if rcs[i] == 0 else RoflError(rcs[i], "client %d of the batch" % i) for i in range(nc)]
+
+    @staticmethod
     def verify_rangeproof_l2(proof, commit, prove_range, verifier_seed=None, fp=None):
         p = np.ascontiguousarray(proof, dtype=np.uint8)
         c = np.ascontiguousarray(commit, dtype=np.uint8)
@@ -538,6 +571,56 @@ def _sigma_verify_batch(fn, plen, clen, proofs_list, commits_list, want_csq):
 SIGMA_KINDS = {0: (128, 64), 1: (192, 96), 2: (160, 64)}      # kind -> (proof bytes, commitment bytes) per element: RandProof, SquareRandProof, SquareProof
 
 
+def _client_arg(x, dtype, row, keep):
+    """(pointer, rows) of one array of a batch's client, wherever it lives: a numpy array (kept alive in `keep`) or a torch tensor on the library's GPU"""
+    if _is_dev(x):
+        p, n = _dev_arg(x, np.dtype(dtype).itemsize, row)
+        return p.value, n
+    a = np.ascontiguousarray(x, dtype=np.float32) if dtype == np.float32 else _u8(x)
+    keep.append(a)
+    return a.ctypes.data, (a.size if dtype == np.float32 else (a.shape[0] if a.size else 0))
+
+
+def _sigma_create_batch(kind, values_list, r1_list, r2_list, nonces, existing_list, fp):
+    """rofl_create_sigmaproof_vec_batch: the per-element Sigma-proof vectors (kind 0 RandProof, 1 SquareRandProof, 2 SquareProof) of several
+    clients (same d) of one process as one launch sequence.  -> list of (proofs, commitments) per client, byte-identical to the per-client
+    create_*_vec call with the same nonce; a client whose own inputs are rejected (NaN, an undecodable commitment, a short nonce stream)
+    gets a RoflError instance in its place, the others are proved.  The arrays of a client may be numpy arrays or torch tensors on the
+    library's GPU."""
+    plen, clen = SIGMA_KINDS[int(kind)]
+    nc = len(values_list)
+    if nc == 0:
+        return []
+    if existing_list is None:
+        existing_list = [None] * nc
+    if r2_list is None:
+        r2_list = [None] * nc
+    if len(r1_list) != nc or len(r2_list) != nc or len(existing_list) != nc or (nonces is not None and len(nonces) != nc):
+        raise ValueError("every list of a batch must have one entry per client")
+    keep, vptrs, aptrs, bptrs, eptrs = [], [], [], [], []
+    d = None
+    for v, r1, r2, ex in zip(values_list, r1_list, r2_list, existing_list):
+        (vp, dv), (ap, da) = _client_arg(v, np.float32, 1, keep), _client_arg(r1, np.uint8, 32, keep)
+        bp, db = (None, dv) if kind == 0 else _client_arg(r2, np.uint8, 32, keep)
+        ep, de = (None, dv) if ex is None else _client_arg(ex, np.uint8, 32, keep)
+        if dv != da or db != dv or de != dv:
+            raise RoflError(1, "WrongNumBlindingFactors")
+        if d is not None and dv != d:
+            raise ValueError("the clients of a batch have the same number of values")
+        d = dv
+        vptrs.append(vp); aptrs.append(ap); bptrs.append(bp); eptrs.append(ep)
+    nonces = nonces or [Nonce.random() for _ in range(nc)]
+    ns = (_NonceStruct * nc)(*[n._struct() for n in nonces])
+    proofs = [np.zeros((max(d, 1), plen), dtype=np.uint8) for _ in range(nc)]
+    commits = [np.zeros((max(d, 1), clen), dtype=np.uint8) for _ in range(nc)]
+    vp = (ctypes.c_void_p * nc)(*vptrs); ap = (ctypes.c_void_p * nc)(*aptrs); ep = (ctypes.c_void_p * nc)(*eptrs)
+    bp = None if kind == 0 else (ctypes.c_void_p * nc)(*bptrs)
+    pp = (ctypes.c_void_p * nc)(*[p.ctypes.data for p in proofs]); cp = (ctypes.c_void_p * nc)(*[c.ctypes.data for c in commits])
+    rcs = (ctypes.c_int * nc)()
+    _check(lib().rofl_create_sigmaproof_vec_batch(int(kind), _sz(nc), vp, _sz(d), ap, bp, ep, *_fp(fp), ns, pp, cp, rcs))
+    return [(proofs[i][:d], commits[i][:d]) if rcs[i] == 0 else RoflError(rcs[i], "client %d of the batch" % i) for i in range(nc)]
+
+
 def create_sigmaproof_vec_range(kind, values, random_vec, random_vec_2, elem_first, elem_count, nonce=None, existing=None, fp=None):
     """rofl_create_sigmaproof_vec_range: the proofs of elements [elem_first, elem_first + elem_count) of ONE vector -- the unit a rank takes when a
     client's per-element Sigma-proofs are split over GPUs (the reference proves the elements independently on its rayon pool,
@@ -582,6 +665,11 @@ class rand_proof_vec:
         return proofs[:d], pairs[:d]
 
     @staticmethod
+    def create_randproof_vec_batch(values_list, random_list, nonces=None, existing_list=None, fp=None):
+        """create_randproof_vec(_existing) for several clients (same d) of one process as one call; see _sigma_create_batch"""
+        return _sigma_create_batch(0, values_list, random_list, None, nonces, existing_list, fp)
+
+    @staticmethod
     def create_randproof_vec_existing(values, existing, random_vec, nonce=None, fp=None):
         return rand_proof_vec.create_randproof_vec(values, random_vec, nonce=nonce, existing=existing, fp=fp)
 
@@ -613,6 +701,11 @@ class square_rand_proof_vec:
                                                      None if ex is None else _ptr(ex), *_fp(fp),
                                                      ctypes.byref(ns), _ptr(proofs), _ptr(commits)))
         return proofs[:d], commits[:d]
+
+    @staticmethod
+    def create_l2rangeproof_vec_batch(values_list, random_list, random2_list, nonces=None, existing_list=None, fp=None):
+        """create_l2rangeproof_vec(_existing) for several clients (same d) of one process as one call; see _sigma_create_batch"""
+        return _sigma_create_batch(1, values_list, random_list, random2_list, nonces, existing_list, fp)
 
     @staticmethod
     def create_l2rangeproof_vec_existing(values, existing, random_vec, random_vec_2, nonce=None, fp=None):
@@ -658,6 +751,11 @@ class square_proof_vec:
                                                  None if ex is None else _ptr(ex), *_fp(fp),
                                                  ctypes.byref(ns), _ptr(proofs), _ptr(commits)))
         return proofs[:d], commits[:d]
+
+    @staticmethod
+    def create_l2rangeproof_vec_batch(values_list, random_list, random2_list, nonces=None, existing_list=None, fp=None):
+        """create_l2rangeproof_vec(_existing) for several clients (same d) of one process as one call; see _sigma_create_batch"""
+        return _sigma_create_batch(2, values_list, random_list, random2_list, nonces, existing_list, fp)
 
     @staticmethod
     def create_l2rangeproof_vec_existing(values, existing, random_vec, random_vec_2, nonce=None, fp=None):

@@ -367,6 +367,62 @@ __global__ void __launch_bounds__(TPB) k_quantize_shift(const float *vals, u32 d
 }
 #endif
 
+// The sums of the L2 sum proof (l2_range_proof_vec/mod.rs:37-79) for the clients of a batch, one client per grid row, a fixed number of
+// blocks per client striding over its d values.  Per client: the status bits (1 = a value outside the clip range, 2 = NaN, as
+// k_quantize_shift has them); sum_i s_i^2 -- s_i is k_i or l - k_i with k_i < 2^64, so s_i^2 = k_i^2 mod l and the sum is the plain integer
+// sum of k_i^2 < d 2^128 < l: a 192-bit accumulator, exact in any order, never reduced; the blinding sum mod l (inputs >= l reduced first,
+// exact in any order); and, per ELEMENT, the term q q 2^frac of the reference's f32 shadow sum, q = (float)k / 2^frac -- the shadow sum
+// itself is serial by definition and stays on the host.  Block partials go to memory; k_l2_sumsq_combine adds them.
+__device__ __forceinline__ void u192_add(u64 *a, u64 b0, u64 b1, u64 b2) {
+    u64 t = a[0] + b0, c = t < b0; a[0] = t;
+    t = a[1] + b1; u64 c1 = t < b1; t += c; c1 += t < c; a[1] = t;
+    a[2] += b2 + c1;
+}
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(TPB) k_l2_sumsq_batch(u32 d, u32 fp_bits, u32 fp_frac, float clip_min, float clip_max, const float *vals /* [client][d] */,
+                                                        const sc *blind /* [client][d] */, float *terms /* [client][d] */, u64 *part_sq /* [client][gridDim.x][3] */,
+                                                        sc *part_bl /* [client][gridDim.x] */, u32 *status /* [client] */) {
+    __shared__ u64 s_sq[TPB][3];
+    __shared__ sc s_bl[TPB];
+    vals += (size_t)blockIdx.y * d; blind += (size_t)blockIdx.y * d; terms += (size_t)blockIdx.y * d;
+    const u64 maxbits = fp_bits >= 64 ? ~0ULL : ((1ULL << fp_bits) - 1);
+    const double lim = ldexp(1.0, (int)fp_bits);
+    const float inv = 1.0f / (float)(1u << fp_frac), shift = (float)(1u << fp_frac);      // (exact powers of two)
+    u64 acc[3] = {0, 0, 0}; sc bl = sc_zero(); u32 st = 0;
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < d; i += gridDim.x * blockDim.x) {
+        float v = vals[i];
+        if (clip_min > v || v > clip_max) st |= 1;
+        if (v != v) st |= 2;
+        u64 k = 0;
+        if (!(v != v)) { double x = fabs((double)v) * (double)(1ULL << fp_frac); if (x >= lim) k = maxbits; else { double r = rint(x); k = (r >= lim) ? maxbits : (u64)r; } }
+        u192_add(acc, k * k, __umul64hi(k, k), 0);
+        float q = __fmul_rn(__ull2float_rn(k), inv);
+        terms[i] = __fmul_rn(__fmul_rn(q, q), shift);
+        bl = sc_add(bl, load_sc_reduced(&blind[i]));
+    }
+    if (st) atomicOr(status + blockIdx.y, st);
+    const u32 t = threadIdx.x;
+    s_sq[t][0] = acc[0]; s_sq[t][1] = acc[1]; s_sq[t][2] = acc[2]; s_bl[t] = bl;
+    __syncthreads();
+    for (u32 w = TPB / 2; w; w >>= 1) {
+        if (t < w) { u64 a[3] = {s_sq[t][0], s_sq[t][1], s_sq[t][2]}; u192_add(a, s_sq[t + w][0], s_sq[t + w][1], s_sq[t + w][2]);
+                     s_sq[t][0] = a[0]; s_sq[t][1] = a[1]; s_sq[t][2] = a[2]; s_bl[t] = sc_add(s_bl[t], s_bl[t + w]); }
+        __syncthreads();
+    }
+    if (t == 0) { const size_t o = (size_t)blockIdx.y * gridDim.x + blockIdx.x; part_sq[3 * o] = s_sq[0][0]; part_sq[3 * o + 1] = s_sq[0][1]; part_sq[3 * o + 2] = s_sq[0][2]; part_bl[o] = s_bl[0]; }
+}
+// one thread per client: out[2 c] = the sum of squares as a scalar (canonical: it is below 2^192), out[2 c + 1] = the blinding sum
+__global__ void __launch_bounds__(64) k_l2_sumsq_combine(u32 n_clients, u32 nblk, const u64 *part_sq, const sc *part_bl, sc *out /* [client][2] */) {
+    u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_clients) return;
+    u64 a[3] = {0, 0, 0}; sc bl = sc_zero();
+    for (u32 b = 0; b < nblk; b++) { const size_t o = (size_t)c * nblk + b; u192_add(a, part_sq[3 * o], part_sq[3 * o + 1], part_sq[3 * o + 2]); bl = sc_add(bl, part_bl[o]); }
+    sc v = sc_zero();
+    for (int q = 0; q < 3; q++) { v.v[2 * q] = (u32)a[q]; v.v[2 * q + 1] = (u32)(a[q] >> 32); }
+    out[2 * c] = v; out[2 * c + 1] = bl;
+}
+#endif
+
 // ================================================================ K3: Pedersen commit (fixed-base)
 // tables: radix-256 signed digits, tab[w][e] = (e+1) * 256^w * P, w < 32, e < 128  (affine niels; built by k_fixed_tab8 from the radix-16
 // table the per-element chains started with: half the mixed additions, the 393 KB of a base stay in L2)
@@ -2228,11 +2284,10 @@ __global__ void __launch_bounds__(64) k_sigma_point_var(int kind, u32 d, const f
     sigma_point_body<true>(kind, SG_CSQP, d, vals, fp_bits, fp_frac, r1c, r2c, existing, mode, seed, stream, stream_scalars, nonce_base, tabB, tabBb, proofs, commits, status, slow_mark);
 }
 #endif
-#if ROFL_KG(4)
-__global__ void __launch_bounds__(TPB) k_sigma_finish(int kind, u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *r1c, const sc *r2c,
-                                                      const uint8_t *existing, int mode, NonceSeed seed, const uint8_t *stream, u64 stream_scalars, u64 nonce_base,
-                                                      DMerlin init, uint8_t *proofs, uint8_t *commits, u32 *status) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+// (the body of k_sigma_finish and k_sigma_finish_batch: element i of one vector)
+__device__ __forceinline__ void sigma_finish_elem(u32 i, int kind, u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *r1c, const sc *r2c,
+                                                  const uint8_t *existing, int mode, const NonceSeed &seed, const uint8_t *stream, u64 stream_scalars, u64 nonce_base,
+                                                  const DMerlin &init, uint8_t *proofs, uint8_t *commits, u32 *status) {
     if (i >= d) return;
     bool has_R = kind != 2, has_sq = kind != 0;
     u32 npts = 1 + (has_R ? 1 : 0) + (has_sq ? 1 : 0), nn = has_sq ? 3 : 2, clen = 32 * npts, plen = 32 * (npts + nn);
@@ -2252,6 +2307,45 @@ __global__ void __launch_bounds__(TPB) k_sigma_finish(int kind, u32 d, const flo
     sc_tobytes(z, sc_add(nc[0], sc_mul_plain(m, c)));
     sc_tobytes(z + 32, sc_add(nc[1], sc_mul_plain(r1, c)));
     if (has_sq) sc_tobytes(z + 64, sc_add(nc[2], sc_mul_plain(sc_sub(r2, sc_mul_plain(m, r1)), c)));
+}
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(TPB) k_sigma_finish(int kind, u32 d, const float *vals, u32 fp_bits, u32 fp_frac, const sc *r1c, const sc *r2c,
+                                                      const uint8_t *existing, int mode, NonceSeed seed, const uint8_t *stream, u64 stream_scalars, u64 nonce_base,
+                                                      DMerlin init, uint8_t *proofs, uint8_t *commits, u32 *status) {
+    sigma_finish_elem(blockIdx.x * blockDim.x + threadIdx.x, kind, d, vals, fp_bits, fp_frac, r1c, r2c, existing, mode, seed, stream, stream_scalars, nonce_base, init, proofs, commits, status);
+}
+#endif
+// The vectors of SEVERAL clients (one process hosts them: sigma_create_batch) in the same three launches: the client is a grid dimension of
+// its own and what varies by client -- where its nonces come from, whether a commitment is handed in, where its arrays lie -- is read from a
+// descriptor in device memory indexed by it (sixteen seeds by value would not fit the kernel arguments); one status word per client.  The
+// per-element bodies are those of the single-client kernels, so are nonce indices and bytes.  A client with a commitment handed in runs
+// SG_LCMP / SG_LCHK where the others run SG_L (the slot list is the one of a client without), and only such clients walk their marks.
+struct SgClient { int mode; u32 has_existing; NonceSeed seed; const uint8_t *stream; u64 stream_scalars;
+                  const float *vals; const sc *r1c, *r2c; const uint8_t *existing; uint8_t *proofs, *commits, *slow_mark; };
+#if ROFL_KG(2)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_sigma_points_batch(int kind, SgSlots slots, u32 d, u32 fp_bits, u32 fp_frac, const SgClient *cl,
+                                                     const niels *tabB, const niels *tabBb, u32 *status /* [gridDim.z] */) {
+    const SgClient &c = cl[blockIdx.z];
+    int slot = slots.id[blockIdx.y];
+    const uint8_t *ex = c.has_existing ? c.existing : nullptr;
+    if (slot == SG_L && ex) slot = kind != 0 ? SG_LCMP : SG_LCHK;
+    sigma_point_body<false>(kind, slot, d, c.vals, fp_bits, fp_frac, c.r1c, c.r2c, ex, c.mode, c.seed, c.stream, c.stream_scalars, 0, tabB, tabBb, c.proofs, c.commits, status + blockIdx.z,
+                            ex ? c.slow_mark : nullptr);
+}
+#endif
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(64) k_sigma_point_var_batch(int kind, u32 d, u32 fp_bits, u32 fp_frac, const SgClient *cl, const niels *tabB, const niels *tabBb, u32 *status /* [gridDim.y] */) {
+    const SgClient &c = cl[blockIdx.y];
+    if (!c.has_existing) return;      // (no commitment handed in: nothing was compared, no marks)
+    sigma_point_body<true>(kind, SG_CSQP, d, c.vals, fp_bits, fp_frac, c.r1c, c.r2c, c.existing, c.mode, c.seed, c.stream, c.stream_scalars, 0, tabB, tabBb, c.proofs, c.commits, status + blockIdx.y,
+                           c.slow_mark);
+}
+#endif
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(TPB) k_sigma_finish_batch(int kind, u32 d, u32 fp_bits, u32 fp_frac, const SgClient *cl, DMerlin init, u32 *status /* [gridDim.y] */) {
+    const SgClient &c = cl[blockIdx.y];
+    sigma_finish_elem(blockIdx.x * blockDim.x + threadIdx.x, kind, d, c.vals, fp_bits, fp_frac, c.r1c, c.r2c, c.has_existing ? c.existing : nullptr, c.mode, c.seed, c.stream, c.stream_scalars, 0,
+                      init, c.proofs, c.commits, status + blockIdx.y);
 }
 #endif
 

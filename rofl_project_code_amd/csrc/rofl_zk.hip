@@ -1091,6 +1091,108 @@ int rofl_clip_f32(const float *in, size_t d, size_t prove_range, unsigned fp_bit
     return ROFL_OK;
 }
 
+namespace {
+// What create_rangeproof_l2 decides on the host once a client's sums are known (l2_range_proof_vec/mod.rs:62-79, then the upstream errors), in
+// the reference's order: the f32 shadow sum against the scalar sum (OverflowError), the norm bound, the bit size, the nonce stream.  The
+// single call and the batch both ask here.  *v_out: the value the sum proof commits to.
+int l2_sum_outcome(const sc &val, float val_float, size_t prove_range, unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonce, u64 *v_out) {
+    float val_f = sc_to_f32(val, fp_bits, fp_frac);
+    volatile float diff = val_f - val_float;
+    if (std::fabs(diff) > 1.1920929e-07f) return ROFL_OVERFLOW;
+    if (val_f > l2_clip_bound(prove_range, fp_bits, fp_frac)) return ROFL_NORM_OUT_OF_RANGE;
+    if (!(prove_range == 8 || prove_range == 16 || prove_range == 32 || prove_range == 64)) return ROFL_INVALID_BITSIZE;
+    if (nonce->mode == 0 && nonce->stream_scalars < 2 * prove_range + 4) return ROFL_NONCE_SHORT;
+    *v_out = read_from_bytes(val, fp_bits);
+    return ROFL_OK;
+}
+const char *l2_outcome_text(int rc) {
+    switch (rc) {
+        case ROFL_VALUE_OUT_OF_RANGE: return "ValueOutOfRangeError";
+        case ROFL_NON_FINITE: return "non-finite value";
+        case ROFL_OVERFLOW: return "OverflowError";
+        case ROFL_NORM_OUT_OF_RANGE: return "NormOutOfRangeError";
+        case ROFL_INVALID_BITSIZE: return "InvalidBitsize";
+        case ROFL_NONCE_SHORT: return "nonce stream too short";
+    }
+    return "";
+}
+// create_rangeproof_l2 for the clients of one process (the one-value sum proofs of a round's L2 updates) as ONE launch sequence.
+// k_l2_sumsq_batch (client = grid row, kL2SumBlocks blocks striding over the d values) leaves per client the status bits, the block
+// partials of sum k^2 (192-bit integers) and of the blinding sum, and per element the f32 term of the reference's shadow sum;
+// k_l2_sumsq_combine adds the partials.  WAIT 1: status words, sums and terms are on the host (4 d bytes per client: the shadow sum is
+// serial left to right by definition, so the pool adds every client's terms in order and decides with l2_sum_outcome what the single call
+// would have returned).  The surviving clients are compacted densely: one k_commit over them (WAIT 2: their V bytes, for the
+// transcripts) and one prove_chunks over na chunks of one value -- the host hops of the Bulletproof are paid once per batch.
+constexpr u32 kL2SumBlocks = 8;      // per client: 2 048 threads stride over d; 48 clients are 384 blocks on 256 CUs
+int l2_create_batch(size_t nc, const float *const *values, size_t d, const uint8_t *const *blind, size_t prove_range, unsigned fp_bits, unsigned fp_frac,
+                    const rofl_nonce_t *nonces, uint8_t *const *proofs_out, uint8_t *commits_out32, int *rcs) {
+    LaneLock lane_lock = acquire_lane(false, nc == 1); Ctx &C = *lane_lock.c;
+    for (size_t i = 0; i < nc; i++) rcs[i] = ROFL_OK;
+    C.init();
+    C.batch_mode = nc > 1;
+    timing_begin(C);
+    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+    std::vector<char> dev_v(nc), dev_b(nc); bool any_host = false;
+    for (size_t i = 0; i < nc; i++) { dev_v[i] = is_device_ptr(values[i]); dev_b[i] = is_device_ptr(blind[i]); any_host |= !dev_v[i] || !dev_b[i]; }
+    const u32 nblk = (u32)std::min<size_t>(kL2SumBlocks, (d + TPB - 1) / TPB);
+    float *dv = C.vals.as<float>(nc * d), *dterms = C.tmp_out.as<float>(nc * d);
+    sc *dbl = C.blind.as<sc>(std::max<size_t>(nc * d, nc)), *part_bl = C.tmp_in2.as<sc>(nc * nblk), *dsums = C.aux_scal.as<sc>(2 * nc);
+    u64 *part_sq = C.tmp_in.as<u64>(nc * nblk * 3);
+    u32 *status = C.status.as<u32>(nc + 4), *h_st = C.h_misc.as<u32>(nc + 4);
+    HIPCHK(hipMemsetAsync(status, 0, 4 * (nc + 4), C.stream));
+    uint8_t *stg = any_host ? (uint8_t *)C.stg.alloc(nc * d * 36) : nullptr;
+    bring_group(C, nc, (uint8_t *)dv, stg, 4 * d, [&](size_t j) { return (const uint8_t *)values[j]; }, [&](size_t j) { return (bool)dev_v[j]; });
+    bring_group(C, nc, (uint8_t *)dbl, stg ? stg + nc * d * 4 : nullptr, 32 * d, [&](size_t j) { return blind[j]; }, [&](size_t j) { return (bool)dev_b[j]; });
+    ROFL_LAUNCH(k_l2_sumsq_batch, dim3(nblk, (unsigned)nc), dim3(TPB), 0, C.stream, (u32)d, fp_bits, fp_frac, mn, mx, (const float *)dv, (const sc *)dbl, dterms, part_sq, part_bl, status);
+    ROFL_LAUNCH(k_l2_sumsq_combine, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, C.stream, (u32)nc, nblk, (const u64 *)part_sq, (const sc *)part_bl, dsums);
+    float *h_terms = (float *)C.stg.alloc(nc * d * 4); sc *h_sums = C.h_misc2.as<sc>(2 * nc);
+    HIPCHK(hipMemcpyAsync(h_terms, dterms, nc * d * 4, hipMemcpyDeviceToHost, C.stream));
+    HIPCHK(hipMemcpyAsync(h_sums, dsums, sizeof(sc) * 2 * nc, hipMemcpyDeviceToHost, C.stream));
+    HIPCHK(hipMemcpyAsync(h_st, status, 4 * nc, hipMemcpyDeviceToHost, C.stream));
+    C.sync();                                    // wait 1
+    std::vector<u64> v64(nc, 0);
+    C.pool->run(nc, [&](size_t i) {
+        if (h_st[i] & 1u) { rcs[i] = ROFL_VALUE_OUT_OF_RANGE; return; }      // (the range loop runs to its end before anything is converted)
+        if (h_st[i] & 2u) { rcs[i] = ROFL_NON_FINITE; return; }
+        const float *t = h_terms + i * d;
+        volatile float val_float = 0.0f;
+        for (size_t e = 0; e < d; e++) { volatile float term = t[e]; val_float = (e == 0) ? term : val_float + term; }
+        rcs[i] = l2_sum_outcome(h_sums[2 * i], val_float, prove_range, fp_bits, fp_frac, &nonces[i], &v64[i]);
+    });
+    std::vector<size_t> act;
+    for (size_t i = 0; i < nc; i++) if (rcs[i] == ROFL_OK) act.push_back(i);
+    if (act.empty()) { timing_end(C); return ROFL_OK; }
+    const size_t na = act.size();
+    // the survivors, densely (the proof kernels index chunks densely): value and blinding sum of each
+    u64 *h_v = C.h_auxc.as<u64>(na); sc *h_b = C.h_auxs.as<sc>(na);
+    for (size_t k = 0; k < na; k++) { h_v[k] = v64[act[k]]; h_b[k] = h_sums[2 * act[k] + 1]; }
+    u64 *vshift = C.vshift.as<u64>(na); sc *d_bl = dbl;      // (the blindings themselves have been read)
+    HIPCHK(hipMemcpyAsync(vshift, h_v, 8 * na, hipMemcpyHostToDevice, C.stream));
+    HIPCHK(hipMemcpyAsync(d_bl, h_b, sizeof(sc) * na, hipMemcpyHostToDevice, C.stream));
+    uint8_t *Vb = C.Vbytes.as<uint8_t>(na * 32), *hV = C.h_V.as<uint8_t>(na * 32);
+    ROFL_LAUNCH(k_commit, grid1(na), dim3(TPB), 0, C.stream, (u32)na, vshift, (const sc *)nullptr, d_bl, C.d_tabB8, C.d_tabBb8, (const niels *)nullptr, Vb, (uint8_t *)nullptr, 0u, 1u);
+    HIPCHK(hipMemcpyAsync(hV, Vb, na * 32, hipMemcpyDeviceToHost, C.stream));
+    // explicit nonce streams: the 2 n + 4 scalars a one-value proof draws, every client's at index 0 of its own stream
+    const size_t per = 2 * prove_range + 4;
+    size_t n_streams = 0; for (size_t k = 0; k < na; k++) n_streams += nonces[act[k]].mode == 0;
+    uint8_t *sb = n_streams ? C.stream_buf.as<uint8_t>(n_streams * per * 64 + 64) : nullptr; size_t off = 0;
+    std::vector<ChunkNonce> cn(na);
+    for (size_t k = 0; k < na; k++) {
+        const rofl_nonce_t &nn = nonces[act[k]];
+        cn[k] = ChunkNonce{}; cn[k].mode = nn.mode;
+        if (nn.mode == 1) memcpy(cn[k].seed.w, nn.seed, 32);
+        else { C.up(sb + off, nn.stream, per * 64, C.stream); cn[k].d_stream = sb + off; cn[k].stream_scalars = per; off += per * 64; }
+    }
+    C.sync();                                    // wait 2
+    std::vector<uint8_t *> pout(na);
+    for (size_t k = 0; k < na; k++) pout[k] = proofs_out[act[k]];
+    // BulletproofGens::new(64, 1), label "L2RangeProof" (l2_range_proof_vec/mod.rs:156-171), one chunk of one value per client
+    prove_chunks(C, "L2RangeProof", na, prove_range, 1, vshift, d_bl, cn, hV, pout.data());
+    for (size_t k = 0; k < na; k++) memcpy(commits_out32 + 32 * act[k], hV + 32 * k, 32);
+    timing_end(C);
+    return ROFL_OK;
+}
+}  // namespace
 int rofl_create_rangeproof_l2(const float *values, size_t d, const uint8_t *blindings32, size_t d_blindings, size_t prove_range, size_t n_partition,
                               unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonce, uint8_t *proof_out, size_t *proof_len_out, uint8_t commit_out[32]) {
     return guarded([&]() -> int {
@@ -1111,15 +1213,10 @@ int rofl_create_rangeproof_l2(const float *values, size_t d, const uint8_t *blin
             sc bl = sc_frombytes(blindings32 + 32 * i); if (sc_geq_l(bl.v)) bl = sc_from_mont(sc_to_mont(bl));
             bsum = sc_add(bsum, bl);
         }
-        float val_f = sc_to_f32(val, fp_bits, fp_frac);
-        volatile float diff = val_f - val_float;
-        if (std::fabs(diff) > 1.1920929e-07f) return fail(ROFL_OVERFLOW, "OverflowError");
-        if (val_f > l2_clip_bound(prove_range, fp_bits, fp_frac)) return fail(ROFL_NORM_OUT_OF_RANGE, "NormOutOfRangeError");
-        if (!(prove_range == 8 || prove_range == 16 || prove_range == 32 || prove_range == 64)) return fail(ROFL_INVALID_BITSIZE, "InvalidBitsize");
-        if (nonce->mode == 0 && nonce->stream_scalars < 2 * prove_range + 4) return fail(ROFL_NONCE_SHORT, "nonce stream too short");
+        u64 v = 0;
+        if (int rc = l2_sum_outcome(val, val_float, prove_range, fp_bits, fp_frac, nonce, &v)) return fail(rc, l2_outcome_text(rc));
         C.init();
         timing_begin(C);
-        u64 v = read_from_bytes(val, fp_bits);
         u64 *vshift = C.vshift.as<u64>(1); sc *d_bl = C.blind.as<sc>(1);
         HIPCHK(hipMemcpyAsync(vshift, &v, 8, hipMemcpyHostToDevice, C.stream));
         HIPCHK(hipMemcpyAsync(d_bl, &bsum, 32, hipMemcpyHostToDevice, C.stream));
@@ -1140,6 +1237,28 @@ int rofl_create_rangeproof_l2(const float *values, size_t d, const uint8_t *blin
         *proof_len_out = 32 * (9 + 2 * (size_t)lg2u(prove_range));
         return ROFL_OK;
     });
+}
+int rofl_create_rangeproof_l2_batch(size_t n_clients, const float *const *values, size_t d, const uint8_t *const *blindings32, size_t prove_range, size_t n_partition,
+                                    unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonces, uint8_t *const *proofs_out, size_t *proof_len_out, uint8_t *commits_out32, int *rc_out) {
+    // (everything here is decided before a device is touched)
+    if (!valid_fp(fp_bits, fp_frac) || d == 0 || d >= ((size_t)1 << 28) || n_partition == 0 || prove_range == 0 || prove_range > 128 || 2 * n_clients > kMaxBatchMembers)
+        return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (!values || !blindings32 || !nonces || !proofs_out || !proof_len_out || !commits_out32 || !rc_out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    for (size_t i = 0; i < n_clients; i++)
+        if (!values[i] || !blindings32[i] || !proofs_out[i] || (nonces[i].mode == 0 && nonces[i].stream_scalars && !nonces[i].stream)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    *proof_len_out = 32 * (9 + 2 * (size_t)lg2u(prove_range));
+    if (n_clients == 0) return ROFL_OK;
+    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
+    if (devs.empty() || n_clients < 2)
+        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
+            return l2_create_batch(n_clients, values, d, blindings32, prove_range, fp_bits, fp_frac, nonces, proofs_out, commits_out32, rc_out); });
+    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
+        const size_t k = idx.size();
+        std::vector<const float *> v(k); std::vector<const uint8_t *> b(k); std::vector<rofl_nonce_t> nn(k); std::vector<uint8_t *> po(k); std::vector<uint8_t> co(32 * k); std::vector<int> rc(k, ROFL_OK);
+        for (size_t j = 0; j < k; j++) { v[j] = values[idx[j]]; b[j] = blindings32[idx[j]]; nn[j] = nonces[idx[j]]; po[j] = proofs_out[idx[j]]; }
+        int rcode = l2_create_batch(k, v.data(), d, b.data(), prove_range, fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
+        for (size_t j = 0; j < k; j++) { rc_out[idx[j]] = rc[j]; if (rc[j] == ROFL_OK && rcode == ROFL_OK) memcpy(commits_out32 + 32 * idx[j], &co[32 * j], 32); }
+        return rcode; }); });
 }
 int rofl_verify_rangeproof_l2(const uint8_t *proof, size_t proof_len, const uint8_t commit[32], size_t prove_range, unsigned fp_bits, unsigned fp_frac,
                               const uint8_t verifier_seed[32], int *ok_out) {
@@ -1298,6 +1417,121 @@ int sigma_create(int kind, const float *values, size_t d, const uint8_t *r1, siz
     timing_end(C);
     if (st & 2u) return fail(ROFL_NON_FINITE, "non-finite value (the reference panics in fixed::saturating_from_float)");
     if (st & 4u) return fail(ROFL_FORMAT_ERROR, "invalid Ristretto encoding");
+    return ROFL_OK;
+}
+// sigma_create for the clients of one process (the reference's client binary runs its clients as tasks of one process, client.rs:265-266):
+// the vectors of a GROUP of clients are one launch of each of the three kernels, the client on a grid dimension of its own
+// (k_sigma_points_batch and its companions read what varies by client from an SgClient descriptor on the device).  5 000 elements alone
+// are 79 waves per slot on 1 024 SIMDs; a group fills the chip and pays the launches, the status hop and the wait once.  rcs[i] is client i's
+// own outcome as sigma_create reports it (NaN 10 before an undecodable commitment 5; a mode-0 stream shorter than nn d scalars 12 -- that
+// one before any device work) and a client that fails is left out: its output arrays are not written.
+// Groups: at most sixteen clients and ~64 MB of staged bytes (kind 1: 100 d in, 288 d out per client -- three clients at d = 55 000; explicit
+// nonce streams count too).  Per group: every input array is staged on the host pool and goes up with one copy per run of host clients
+// (device-resident arrays are copied on the device), the descriptors go up, the three launches run, proofs, commitments and status words
+// come down into pinned memory.  ONE WAIT per group (the event after its download); the pool then hands the group's bytes to the callers'
+// arrays.  Two sets of device and staging buffers alternate: group g + 1 is staged, uploaded and launched BEFORE the host waits for group g,
+// so the device computes it while group g comes down and is handed over.
+constexpr size_t kSigmaCreateGroup = 16;
+int sigma_create_batch(int kind, size_t nc, const float *const *values, size_t d, const uint8_t *const *r1, const uint8_t *const *r2, const uint8_t *const *existing,
+                       unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonces, uint8_t *const *proofs_out, uint8_t *const *commits_out, int *rcs) {
+    const bool has_sq = kind != 0;
+    const size_t npts = 1 + (kind != 2) + (has_sq ? 1 : 0), nn = has_sq ? 3 : 2, clen = 32 * npts, plen = 32 * (npts + nn);
+    std::vector<size_t> act;      // the clients that reach the device
+    for (size_t i = 0; i < nc; i++) {
+        rcs[i] = nonces[i].mode == 0 && nonces[i].stream_scalars < nn * d ? ROFL_NONCE_SHORT : ROFL_OK;
+        if (!rcs[i]) act.push_back(i);
+    }
+    if (act.empty() || d == 0) return ROFL_OK;
+    LaneLock lane_lock = acquire_lane(false, nc == 1); Ctx &C = *lane_lock.c;
+    C.init();
+    C.batch_mode = nc > 1;
+    timing_begin(C);
+    const size_t na = act.size();
+    std::vector<char> dev_v(na), dev_r1(na), dev_r2(na), dev_e(na), dev_s(na), has_e(na), has_s(na);
+    bool any_host = false, any_e = false, any_s = false;
+    for (size_t a = 0; a < na; a++) {
+        const size_t i = act[a];
+        has_e[a] = existing && existing[i]; has_s[a] = nonces[i].mode == 0;
+        dev_v[a] = is_device_ptr(values[i]); dev_r1[a] = is_device_ptr(r1[i]); dev_r2[a] = has_sq && is_device_ptr(r2[i]);
+        dev_e[a] = has_e[a] && is_device_ptr(existing[i]); dev_s[a] = has_s[a] && is_device_ptr(nonces[i].stream);
+        any_host |= !dev_v[a] || !dev_r1[a] || (has_sq && !dev_r2[a]) || (has_e[a] && !dev_e[a]) || (has_s[a] && !dev_s[a]);
+        any_e |= (bool)has_e[a]; any_s |= (bool)has_s[a];
+    }
+    // staged bytes of a client: values | r1 | r2 | commitments handed in | nonce stream, and its proofs | commitments
+    const size_t o_r1 = 4 * d, o_r2 = o_r1 + 32 * d, o_ex = o_r2 + (has_sq ? 32 * d : 0), o_st = o_ex + 32 * d, per_s = any_s ? nn * d * 64 : 0;
+    const size_t in_per = o_st + per_s, out_per = d * (plen + clen);
+    const size_t G = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(na, kSigmaCreateGroup), ((size_t)64 << 20) / (in_per + out_per)));
+    const size_t ngroups = (na + G - 1) / G, nbuf = ngroups > 1 ? 2 : 1;
+    float *dv = C.vals.as<float>(nbuf * G * d); sc *dr1 = C.tmp_in.as<sc>(nbuf * G * d); sc *dr2 = has_sq ? C.tmp_in2.as<sc>(nbuf * G * d) : nullptr;
+    uint8_t *dex = any_e ? C.Cbytes.as<uint8_t>(nbuf * G * d * 32) : nullptr, *dst = any_s ? C.stream_buf.as<uint8_t>(nbuf * G * per_s + 64) : nullptr;
+    uint8_t *dout = C.aux_pts.as<uint8_t>(nbuf * G * out_per);      // per buffer set: [G][d] proofs | [G][d] commitments
+    uint8_t *marks = has_sq && any_e ? C.vspart.as<uint8_t>(nbuf * G * d) : nullptr;      // (written for every element by the SG_LCMP slot: no clearing)
+    SgClient *dcl = C.tmp_out.as<SgClient>(nbuf * G), *hcl = C.h_misc2.as<SgClient>(nbuf * G);
+    u32 *status = C.status.as<u32>(na + 4), *h_st = C.h_misc.as<u32>(na + 4);
+    HIPCHK(hipMemsetAsync(status, 0, 4 * (na + 4), C.stream));
+    uint8_t *stg_in[2] = {nullptr, nullptr}, *stg_out[2] = {nullptr, nullptr};
+    for (size_t b = 0; b < nbuf; b++) { if (any_host) stg_in[b] = (uint8_t *)C.stg.alloc(G * in_per); stg_out[b] = (uint8_t *)C.stg.alloc(G * out_per); }
+    SgSlots sl{}; auto add = [&](int id) { sl.id[sl.n++] = id; };      // the slots of a client WITHOUT a commitment handed in; with one, SG_L becomes SG_LCMP / SG_LCHK in the kernel
+    add(SG_L);
+    if (has_sq) { add(SG_CSQP_F); add(SG_CSQ); }
+    add(SG_LP);
+    if (kind != 2) { add(SG_R); add(SG_RP); }
+    const DMerlin init = sigma_init_state(kind);
+    const uint64_t sg_muls = (uint64_t)(4 + (kind != 2 ? 2 : 0) + (has_sq ? 4 : 0)) * 32 * 7 + 2 * npts * 265;
+    auto enqueue = [&](size_t g) {      // upload, the three launches, download of group g in buffer set g & 1; event g & 1 marks the end
+        const size_t a0 = g * G, gc = std::min(G, na - a0), b = g & (nbuf - 1);
+        uint8_t *si = stg_in[b];
+        auto sub = [&](size_t o) { return si ? si + G * o : nullptr; };      // (array by array: [G] values, [G] r1, ...)
+        float *gv = dv + b * G * d; sc *gr1 = dr1 + b * G * d, *gr2 = dr2 ? dr2 + b * G * d : nullptr;
+        uint8_t *gex = dex ? dex + b * G * d * 32 : nullptr, *gst = dst ? dst + b * G * per_s : nullptr, *gp = dout + b * G * out_per, *gc_ = gp + G * d * plen;
+        uint8_t *gm = marks ? marks + b * G * d : nullptr;
+        bring_group(C, gc, (uint8_t *)gv, sub(0), 4 * d, [&](size_t j) { return (const uint8_t *)values[act[a0 + j]]; }, [&](size_t j) { return (bool)dev_v[a0 + j]; });
+        bring_group(C, gc, (uint8_t *)gr1, sub(o_r1), 32 * d, [&](size_t j) { return r1[act[a0 + j]]; }, [&](size_t j) { return (bool)dev_r1[a0 + j]; });
+        if (has_sq) bring_group(C, gc, (uint8_t *)gr2, sub(o_r2), 32 * d, [&](size_t j) { return r2[act[a0 + j]]; }, [&](size_t j) { return (bool)dev_r2[a0 + j]; });
+        if (gex) bring_group(C, gc, gex, sub(o_ex), 32 * d, [&](size_t j) { return has_e[a0 + j] ? existing[act[a0 + j]] : nullptr; }, [&](size_t j) { return (bool)dev_e[a0 + j]; });
+        if (gst) bring_group(C, gc, gst, sub(o_st), per_s, [&](size_t j) { return has_s[a0 + j] ? nonces[act[a0 + j]].stream : nullptr; }, [&](size_t j) { return (bool)dev_s[a0 + j]; });
+        bool var = false;
+        for (size_t j = 0; j < gc; j++) {
+            const rofl_nonce_t &nz = nonces[act[a0 + j]];
+            SgClient c{}; c.mode = nz.mode; c.has_existing = has_e[a0 + j] ? 1u : 0u;
+            if (nz.mode == 1) memcpy(c.seed.w, nz.seed, 32); else { c.stream = gst + j * per_s; c.stream_scalars = nn * d; }
+            c.vals = gv + j * d; c.r1c = gr1 + j * d; c.r2c = gr2 ? gr2 + j * d : nullptr; c.existing = gex ? gex + j * d * 32 : nullptr;
+            c.proofs = gp + j * d * plen; c.commits = gc_ + j * d * clen; c.slow_mark = gm ? gm + j * d : nullptr;
+            hcl[b * G + j] = c; var |= has_sq && has_e[a0 + j];
+        }
+        HIPCHK(hipMemcpyAsync(dcl + b * G, hcl + b * G, sizeof(SgClient) * gc, hipMemcpyHostToDevice, C.stream));
+        { KSpan ks_sigma(C.tm, C.stream, ROFL_TK_SIGMA, (uint64_t)gc * d * sg_muls, (uint64_t)gc * d * (4 + 32 * (has_sq ? 2 : 1) + clen + plen));
+          ROFL_LAUNCH(k_sigma_points_batch, dim3((unsigned)((d + 63) / 64), (unsigned)sl.n, (unsigned)gc), dim3(64), 0, C.stream, kind, sl, (u32)d, fp_bits, fp_frac, (const SgClient *)(dcl + b * G),
+                      C.d_tabB8, C.d_tabBb8, status + a0);
+          if (var)
+              ROFL_LAUNCH(k_sigma_point_var_batch, dim3((unsigned)std::min<size_t>((d + 63) / 64, 256), (unsigned)gc), dim3(64), 0, C.stream, kind, (u32)d, fp_bits, fp_frac, (const SgClient *)(dcl + b * G),
+                          C.d_tabB, C.d_tabBb, status + a0);
+          ROFL_LAUNCH(k_sigma_finish_batch, grid1(d, (u32)gc), dim3(TPB), 0, C.stream, kind, (u32)d, fp_bits, fp_frac, (const SgClient *)(dcl + b * G), init, status + a0); }
+        HIPCHK(hipMemcpyAsync(stg_out[b], gp, gc * d * plen, hipMemcpyDeviceToHost, C.stream));
+        HIPCHK(hipMemcpyAsync(stg_out[b] + G * d * plen, gc_, gc * d * clen, hipMemcpyDeviceToHost, C.stream));
+        HIPCHK(hipMemcpyAsync(h_st + a0, status + a0, 4 * gc, hipMemcpyDeviceToHost, C.stream));
+        HIPCHK(hipEventRecord(C.pool_event(b), C.stream));
+    };
+    enqueue(0);
+    for (size_t g = 0; g < ngroups; g++) {
+        const size_t a0 = g * G, gc = std::min(G, na - a0), b = g & (nbuf - 1);
+        if (g + 1 < ngroups) enqueue(g + 1);      // (its buffers are those of group g - 1, which is finished)
+        C.wait_event(C.pool_event(b));           // the group's one wait: proofs, commitments and status words are on the host
+        std::vector<size_t> good;                // positions in the group
+        for (size_t j = 0; j < gc; j++) {
+            const u32 st = h_st[a0 + j];
+            rcs[act[a0 + j]] = (st & 2u) ? ROFL_NON_FINITE : (st & 4u) ? ROFL_FORMAT_ERROR : ROFL_OK;
+            if (!(st & 6u)) good.push_back(j);
+        }
+        if (good.empty()) continue;
+        const uint8_t *hp = stg_out[b], *hc = stg_out[b] + G * d * plen;
+        const size_t sp = std::max<size_t>(1, (d * plen) >> 18), sc_ = std::max<size_t>(1, (d * clen) >> 18);
+        C.pool->run(good.size() * (sp + sc_), [&](size_t t) {
+            const size_t j = good[t / (sp + sc_)], i = act[a0 + j]; size_t k = t % (sp + sc_);
+            if (k < sp) { const size_t lo = d * plen * k / sp, hi = d * plen * (k + 1) / sp; memcpy(proofs_out[i] + lo, hp + j * d * plen + lo, hi - lo); }
+            else { k -= sp; const size_t lo = d * clen * k / sc_, hi = d * clen * (k + 1) / sc_; memcpy(commits_out[i] + lo, hc + j * d * clen + lo, hi - lo); } });
+    }
+    timing_end(C);
     return ROFL_OK;
 }
 // Verification of the per-element Sigma-proofs of `nc` vectors of d elements (the clients of a round: the reference's server verifies every
@@ -1889,6 +2123,30 @@ int rofl_create_compressed_randproof_batch(size_t n_clients, const float *const 
         for (size_t j = 0; j < k; j++) { v[j] = d ? values[idx[j]] : nullptr; r[j] = d ? r32[idx[j]] : nullptr; if (existing32) e[j] = existing32[idx[j]]; nn[j] = nonces[idx[j]];
                                          po[j] = proofs_out[idx[j]]; co[j] = d ? pairs_out[idx[j]] : nullptr; }
         int rcode = compressed_create_batch(k, v.data(), d, r.data(), e.data(), fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
+        for (size_t j = 0; j < k; j++) rc_out[idx[j]] = rc[j];
+        return rcode; }); });
+}
+int rofl_create_sigmaproof_vec_batch(int kind, size_t n_clients, const float *const *values, size_t d, const uint8_t *const *r1_32, const uint8_t *const *r2_32,
+                                     const uint8_t *const *existing32, unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonces, uint8_t *const *proofs_out,
+                                     uint8_t *const *commits_out, int *rc_out) {
+    // (everything here is decided before a device is touched)
+    if (kind < 0 || kind > 2 || d >= ((size_t)1 << 28) || !valid_fp(fp_bits, fp_frac) || n_clients > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_clients == 0) return ROFL_OK;
+    if (!nonces || !rc_out || (kind != 0 && !r2_32) || (d && (!values || !r1_32 || !proofs_out || !commits_out))) return fail(ROFL_BAD_PARAM, "bad parameter");
+    for (size_t i = 0; i < n_clients; i++)
+        if ((nonces[i].mode == 0 && nonces[i].stream_scalars && !nonces[i].stream) || (d && (!values[i] || !r1_32[i] || (kind != 0 && !r2_32[i]) || !proofs_out[i] || !commits_out[i])))
+            return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
+    if (devs.empty() || n_clients < 2)
+        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
+            return sigma_create_batch(kind, n_clients, values, d, r1_32, r2_32, existing32, fp_bits, fp_frac, nonces, proofs_out, commits_out, rc_out); });
+    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
+        const size_t k = idx.size();
+        std::vector<const float *> v(k, nullptr); std::vector<const uint8_t *> a(k, nullptr), b(k, nullptr), e(k, nullptr); std::vector<rofl_nonce_t> nn(k); std::vector<uint8_t *> po(k, nullptr), co(k, nullptr);
+        std::vector<int> rc(k, ROFL_OK);
+        for (size_t j = 0; j < k; j++) { const size_t i = idx[j]; nn[j] = nonces[i]; if (existing32) e[j] = existing32[i];
+                                         if (d) { v[j] = values[i]; a[j] = r1_32[i]; if (kind != 0) b[j] = r2_32[i]; po[j] = proofs_out[i]; co[j] = commits_out[i]; } }
+        int rcode = sigma_create_batch(kind, k, v.data(), d, a.data(), b.data(), e.data(), fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
         for (size_t j = 0; j < k; j++) rc_out[idx[j]] = rc[j];
         return rcode; }); });
 }

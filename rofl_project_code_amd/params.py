@@ -237,21 +237,17 @@ class EncParamsRange:
     @staticmethod
     def _rand_create_batch(xs, bls, enc_coms, nonces, fp):
         """The randomness leg of encrypt_batch: (thunks, collect) -- the thunks run beside the range proofs (_concurrently), collect(their
-        results) is the list of (rand proofs, pairs) per client.  enc_coms[i]: the commitments to complete, or None.  Here: one
-        create_randproof_vec(_existing) per client on the lanes."""
-        def one(i):
-            if enc_coms[i] is None:
-                return rand_proof_vec.create_randproof_vec(xs[i], bls[i], nonce=nonces[i], fp=fp)
-            return rand_proof_vec.create_randproof_vec_existing(xs[i], enc_coms[i], bls[i], nonce=nonces[i], fp=fp)
-        return [lambda i=i: one(i) for i in range(len(xs))], list
+        results) is the list of (rand proofs, pairs) per client.  enc_coms[i]: the commitments to complete, or None.  Here: ONE
+        rofl_create_sigmaproof_vec_batch (create_randproof_vec(_existing) of every client) for all clients."""
+        return [lambda: rand_proof_vec.create_randproof_vec_batch(xs, bls, nonces=nonces, existing_list=enc_coms, fp=fp)], lambda res: res[0]
 
     @classmethod
     def encrypt_batch(cls, clients, prove_range, n_partition, check_percentage, nonce_seeds=None, fp=None):
         """encrypt() for several clients of one process (rofl_service's client binary hosts its clients as tasks of one process,
         client.rs:265-266): clients = [(plaintext_vec, blinding_vec), ...] of one length.  The L-inf legs of all of them are ONE
         rofl_create_rangeproof_batch call -- over the first k values of every client when check_percentage < 1 -- and the randomness leg
-        (_rand_create_batch: one call per client here, ONE rofl_create_compressed_randproof_batch for EncParamsRangeCompressed) runs beside
-        it.  Every container is byte-identical to what encrypt() returns for that client with the same nonce seed; a client that fails
+        (_rand_create_batch: ONE rofl_create_sigmaproof_vec_batch here, ONE rofl_create_compressed_randproof_batch for EncParamsRangeCompressed)
+        runs beside it.  Every container is byte-identical to what encrypt() returns for that client with the same nonce seed; a client that fails
         raises."""
         fp = api._fp(fp)
         n = len(clients)
@@ -486,8 +482,10 @@ class EncParamsL2:
     def encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None):
         """encrypt() for several clients of one process (rofl_service's client binary hosts its clients as tasks of one process,
         client.rs:265-266): clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one length.  The L-inf legs of all of
-        them are ONE rofl_create_rangeproof_batch call (one launch sequence, one set of host hops); their square proofs and sum proofs run
-        beside it on other lanes.  Every container is byte-identical to what encrypt() returns for that client with the same nonce seed."""
+        them are ONE rofl_create_rangeproof_batch call (one launch sequence, one set of host hops), their sum proofs ONE
+        rofl_create_rangeproof_l2_batch and their square proofs ONE rofl_create_sigmaproof_vec_batch: three calls side by side on three
+        lanes.  Every container is byte-identical to what encrypt() returns for that client with the same nonce seed; a client that fails
+        raises."""
         fp = api._fp(fp)
         n = len(clients)
         if n == 0:
@@ -506,19 +504,19 @@ class EncParamsL2:
         # the range proofs' commitments, computed first (one call for all clients) so that the square proofs can complete them while the range proofs run
         enc_all = pedersen_ops.commit_vec(np.concatenate([conversion32.f32_to_scalar_vec(c, fp=fp) for c in clipped]), np.concatenate(bls))
         enc_com = [enc_all[i * d:(i + 1) * d] for i in range(n)]
-        thunks = [lambda: range_proof_vec.create_rangeproof_batch(clipped, bls, prove_range, n_partition, nonces=[_sub_nonce(sd, b"range", wd) for sd, wd in zip(seeds, wds)], fp=fp)]
-        for i in range(n):
-            thunks.append(lambda i=i: l2_range_proof_vec.create_rangeproof_l2(clipped[i], r2s[i], l2_range, n_partition, nonce=_sub_nonce(seeds[i], b"l2", wds[i]), fp=fp))
-            thunks.append(lambda i=i: square_rand_proof_vec.create_l2rangeproof_vec_existing(clipped[i], enc_com[i], bls[i], r2s[i], nonce=_sub_nonce(seeds[i], b"sq", wds[i]), fp=fp))
-        res = _concurrently(*thunks)
+        def nonces(tag):
+            return [_sub_nonce(sd, tag, wd) for sd, wd in zip(seeds, wds)]
+        res = _concurrently(
+            lambda: range_proof_vec.create_rangeproof_batch(clipped, bls, prove_range, n_partition, nonces=nonces(b"range"), fp=fp),
+            lambda: l2_range_proof_vec.create_rangeproof_l2_batch(clipped, r2s, l2_range, n_partition, nonces=nonces(b"l2"), fp=fp),
+            lambda: square_rand_proof_vec.create_l2rangeproof_vec_batch(clipped, bls, r2s, nonces=nonces(b"sq"), existing_list=enc_com, fp=fp))
         out = []
         for i in range(n):
-            r = res[0][i]
-            if isinstance(r, Exception):
-                raise r
-            rp, rp_com = r
+            for r in (res[0][i], res[1][i], res[2][i]):
+                if isinstance(r, Exception):
+                    raise r
+            (rp, rp_com), (sum_proof, _), (proofs, commits) = res[0][i], res[1][i], res[2][i]
             assert (rp_com == enc_com[i]).all()
-            (sum_proof, _), (proofs, commits) = res[1 + 2 * i], res[2 + 2 * i]
             out.append(cls(commits, proofs, rp, sum_proof, prove_range, l2_range))
         return out
 
@@ -651,8 +649,8 @@ class EncParamsL2Compressed(EncParamsL2):
     def encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None):
         """encrypt() for several clients of one process: clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one
         length.  The 8-bit legs of all of them are ONE rofl_create_rangeproof_batch call, their compressed randomness proofs ONE
-        rofl_create_compressed_randproof_batch over the range proofs' commitments; the sum proofs and the SquareProofs run per client
-        beside them on other lanes.  Every container is byte-identical to what encrypt() returns for that client with the same nonce
+        rofl_create_compressed_randproof_batch over the range proofs' commitments, their sum proofs ONE rofl_create_rangeproof_l2_batch and
+        their SquareProofs ONE rofl_create_sigmaproof_vec_batch: four calls side by side on the lanes.  Every container is byte-identical to what encrypt() returns for that client with the same nonce
         seed; a client that fails raises."""
         fp = api._fp(fp)
         n = len(clients)
@@ -671,20 +669,20 @@ class EncParamsL2Compressed(EncParamsL2):
         wds = [witness_digest(x, bl, r2) if sd is not None else b"" for x, bl, r2, sd in zip(xs, bls, r2s, seeds)]
         enc_all = pedersen_ops.commit_vec(np.concatenate([conversion32.f32_to_scalar_vec(c, fp=fp) for c in clipped]), np.concatenate(bls))
         enc_com = [enc_all[i * d:(i + 1) * d] for i in range(n)]
-        thunks = [lambda: range_proof_vec.create_rangeproof_batch(clipped, bls, prove_range, n_partition, nonces=[_sub_nonce(sd, b"range", wd) for sd, wd in zip(seeds, wds)], fp=fp),
-                  lambda: compressed_rand_proof.helper_prove_batch(clipped, bls, nonces=[_sub_nonce(sd, b"rand", wd) for sd, wd in zip(seeds, wds)], existing_list=enc_com, fp=fp)]
-        for i in range(n):
-            thunks.append(lambda i=i: l2_range_proof_vec.create_rangeproof_l2(clipped[i], r2s[i], l2_range, n_partition, nonce=_sub_nonce(seeds[i], b"l2", wds[i]), fp=fp))
-            thunks.append(lambda i=i: square_proof_vec.create_l2rangeproof_vec_existing(clipped[i], enc_com[i], bls[i], r2s[i], nonce=_sub_nonce(seeds[i], b"sq", wds[i]), fp=fp))
-        res = _concurrently(*thunks)
+        def nonces(tag):
+            return [_sub_nonce(sd, tag, wd) for sd, wd in zip(seeds, wds)]
+        res = _concurrently(
+            lambda: range_proof_vec.create_rangeproof_batch(clipped, bls, prove_range, n_partition, nonces=nonces(b"range"), fp=fp),
+            lambda: compressed_rand_proof.helper_prove_batch(clipped, bls, nonces=nonces(b"rand"), existing_list=enc_com, fp=fp),
+            lambda: l2_range_proof_vec.create_rangeproof_l2_batch(clipped, r2s, l2_range, n_partition, nonces=nonces(b"l2"), fp=fp),
+            lambda: square_proof_vec.create_l2rangeproof_vec_batch(clipped, bls, r2s, nonces=nonces(b"sq"), existing_list=enc_com, fp=fp))
         out = []
         for i in range(n):
-            for r in (res[0][i], res[1][i]):
+            for r in (res[0][i], res[1][i], res[2][i], res[3][i]):
                 if isinstance(r, Exception):
                     raise r
-            (rp, rp_com), (rand_proof, pairs) = res[0][i], res[1][i]
+            (rp, rp_com), (rand_proof, pairs), (sum_proof, _), (sq_proofs, sq_commits) = res[0][i], res[1][i], res[2][i], res[3][i]
             assert (rp_com == enc_com[i]).all()
-            (sum_proof, _), (sq_proofs, sq_commits) = res[2 + 2 * i], res[3 + 2 * i]
             merged = np.concatenate([pairs, sq_commits[:, 32:64]], axis=1)        # merge(), as in encrypt()
             out.append(cls(merged, sq_proofs, rand_proof, rp, sum_proof, prove_range, l2_range))
         return out

@@ -1,0 +1,32 @@
+"""Helper for test_gpu_l2_create_batch.py::test_device_resident_inputs: device pointers in, same bytes out."""
+import os, sys
+import numpy as np
+import torch
+torch.cuda.init()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+import rofl_project_code_amd as R
+R.set_device(0)
+FP, NB = (32, 7), 32
+d, n = 65, 3
+xs, bls = [], []
+for i in range(n):
+    rng = np.random.default_rng(277 + i)
+    xs.append((rng.integers(-20, 20, size=d) / 128.0).astype(np.float32))
+    bl = rng.integers(0, 256, size=(d, 32), dtype=np.uint8); bl[:, 31] &= 0x0F
+    bls.append(bl)
+seeds = [bytes([0x50 + i]) * 32 for i in range(n)]
+want = [R.l2_range_proof_vec.create_rangeproof_l2(xs[i], bls[i], NB, 1, nonce=R.Nonce.seeded(seeds[i]), fp=FP) for i in range(n)]
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+# client 1 lives on the device, its neighbours in host memory; then every client on the device
+for vl, rl in ((list(xs), list(bls)), ([dev(x) for x in xs], [dev(b) for b in bls])):
+    vl[1], rl[1] = dev(xs[1]), dev(bls[1])
+    got = R.l2_range_proof_vec.create_rangeproof_l2_batch(vl, rl, NB, 1, nonces=[R.Nonce.seeded(s) for s in seeds], fp=FP)
+    for i in range(n):
+        assert not isinstance(got[i], Exception), (i, got[i])
+        assert (got[i][0] == want[i][0]).all() and (got[i][1] == want[i][1]).all(), i
+print("DEVICE_INPUTS PASS")

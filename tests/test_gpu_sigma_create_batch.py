@@ -1,0 +1,211 @@
+"""rofl_create_sigmaproof_vec_batch (rand_proof_vec.create_randproof_vec_batch, square_rand_proof_vec / square_proof_vec
+.create_l2rangeproof_vec_batch): the per-element Sigma-proof vectors of several clients of one process in one launch sequence -- groups of
+sixteen clients, k_sigma_points_batch (one thread per point, blocks of 64 elements, the client on a grid dimension of its own),
+k_sigma_point_var_batch (the slow marks of a client whose handed-in commitments are not its values') and k_sigma_finish_batch (blocks of
+256).  Every client's proofs and commitments must be the bytes of its own single call and of the CPU oracle (orc.sigma_create), whatever
+its neighbours in the batch are.
+
+Shapes: d around the points kernel's block (63, 64, 65) and the finish kernel's block (255, 256, 257), 0 and 1; n = 1, 2 and 17 (a second
+group, of one)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import orc
+
+pytestmark = pytest.mark.gpu
+FP = (16, 7)
+GROUP = 16                # clients per launch (kSigmaCreateGroup)
+DS = (0, 1, 63, 64, 65, 255, 256, 257)
+NN = {0: 2, 1: 3, 2: 3}   # nonces per element
+KINDS = (0, 1, 2)
+
+
+@pytest.fixture(scope="module")
+def R():
+    import rofl_project_code_amd as R
+    from rofl_project_code_amd import build
+    build.build()
+    R.set_device(0)
+    return R
+
+
+def _nonce(R, kind, d, i, mode):
+    """client i's prover randomness: (Nonce, the oracle's keyword)"""
+    if mode == "seed":
+        return R.Nonce.seeded(bytes([i + 1]) * 32), dict(seed=bytes([i + 1]) * 32)
+    s = np.random.default_rng(9000 + i).integers(0, 256, size=64 * NN[kind] * d, dtype=np.uint8).tobytes()      # nn wide scalars per element
+    return R.Nonce.stream(s), dict(stream=s)
+
+
+_inputs, _single, _oracle = {}, {}, {}
+
+
+def _client(R, d, i):
+    """(values, r1, r2, commitments of the values, commitments of OTHER values) of client i at length d, made once and never written to"""
+    if (d, i) not in _inputs:
+        rng = np.random.default_rng(6000 + 31 * d + i)
+        x = (rng.integers(-100, 100, size=d) / 128.0).astype(np.float32)
+        r1 = rng.integers(0, 256, size=(d, 32), dtype=np.uint8); r1[:, 31] &= 0x0F
+        r2 = rng.integers(0, 256, size=(d, 32), dtype=np.uint8); r2[:, 31] &= 0x0F
+        if d:
+            com = R.pedersen_ops.commit_vec(R.conversion32.f32_to_scalar_vec(x, fp=FP), r1)
+            other = R.pedersen_ops.commit_vec(R.conversion32.f32_to_scalar_vec((x + np.float32(1 / 128.0)).astype(np.float32), fp=FP), r1)      # valid points, not the values' commitments
+        else:
+            com = other = np.zeros((0, 32), np.uint8)
+        _inputs[(d, i)] = (x, r1, r2, com, other)
+    return _inputs[(d, i)]
+
+
+def _existing(R, d, i, ex):
+    """ex: None (no commitment handed in), "own" (the values' commitments) or "other" (valid points that commit to other values)"""
+    return None if ex is None else _client(R, d, i)[3 if ex == "own" else 4]
+
+
+def _batch(R, kind, xs, r1s, r2s, **kw):
+    if kind == 0:
+        return R.rand_proof_vec.create_randproof_vec_batch(xs, r1s, **kw)
+    cls = R.square_rand_proof_vec if kind == 1 else R.square_proof_vec
+    return cls.create_l2rangeproof_vec_batch(xs, r1s, r2s, **kw)
+
+
+def _call_single(R, kind, x, r1, r2, nonce, existing):
+    if kind == 0:
+        return R.rand_proof_vec.create_randproof_vec(x, r1, nonce=nonce, existing=existing, fp=FP)
+    cls = R.square_rand_proof_vec if kind == 1 else R.square_proof_vec
+    return cls.create_l2rangeproof_vec(x, r1, r2, nonce=nonce, existing=existing, fp=FP)
+
+
+def _one(R, kind, d, i, mode, ex=None):
+    """the single call's (proofs, commitments) for client i, computed once per case"""
+    key = (kind, d, i, mode, ex)
+    if key not in _single:
+        x, r1, r2 = _client(R, d, i)[:3]
+        _single[key] = _call_single(R, kind, x, r1, r2, _nonce(R, kind, d, i, mode)[0], _existing(R, d, i, ex))
+    return _single[key]
+
+
+def _orc(R, kind, d, i, mode, ex=None):
+    key = (kind, d, i, mode, ex)
+    if key not in _oracle:
+        x, r1, r2 = _client(R, d, i)[:3]
+        _oracle[key] = orc.sigma_create(kind, x, r1, r2 if kind else None, FP[0], FP[1], existing=_existing(R, d, i, ex), **_nonce(R, kind, d, i, mode)[1])
+    return _oracle[key]
+
+
+def _same(got, want):
+    return not isinstance(got, Exception) and got[0].shape == want[0].shape and got[1].shape == want[1].shape and (got[0] == want[0]).all() and (got[1] == want[1]).all()
+
+
+def _is_oracle(got, want):
+    """got = (proofs, commitments) against the oracle's (rc, proofs, commitments)"""
+    return want[0] == 0 and _same(got, want[1:])
+
+
+def _verifies(R, kind, proofs, commits):
+    if kind == 0:
+        return R.rand_proof_vec.verify_randproof_vec(proofs, commits)
+    return (R.square_rand_proof_vec if kind == 1 else R.square_proof_vec).verify_l2rangeproof_vec(proofs, commits)
+
+
+@pytest.mark.parametrize("mode", ["seed", "stream"])
+@pytest.mark.parametrize("n,d", [(GROUP + 1, 65), (1, 257)] + [(2, d) for d in DS], ids=lambda v: str(v))
+@pytest.mark.parametrize("kind", KINDS)
+def test_bytes_equal_the_single_call_and_the_oracle(R, kind, n, d, mode):
+    cl = [_client(R, d, i) for i in range(n)]
+    got = _batch(R, kind, [c[0] for c in cl], [c[1] for c in cl], [c[2] for c in cl], nonces=[_nonce(R, kind, d, i, mode)[0] for i in range(n)], fp=FP)
+    assert len(got) == n
+    for i in range(n):
+        assert _same(got[i], _one(R, kind, d, i, mode)), ("single call", i)
+        assert _is_oracle(got[i], _orc(R, kind, d, i, mode)), ("oracle", i)
+        if d:
+            assert _verifies(R, kind, got[i][0], got[i][1]) is True
+            assert orc.sigma_verify(kind, got[i][0], got[i][1]) == (0, True)
+
+
+@pytest.mark.parametrize("pattern", [(None, "own", None), ("own", None, "own")], ids=["middle", "outer"])
+@pytest.mark.parametrize("kind", KINDS)
+def test_mixed_existing(R, kind, pattern):
+    d, n = 65, 3
+    cl = [_client(R, d, i) for i in range(n)]
+    got = _batch(R, kind, [c[0] for c in cl], [c[1] for c in cl], [c[2] for c in cl], nonces=[_nonce(R, kind, d, i, "seed")[0] for i in range(n)],
+                 existing_list=[_existing(R, d, i, e) for i, e in enumerate(pattern)], fp=FP)
+    for i in range(n):
+        assert _same(got[i], _one(R, kind, d, i, "seed", ex=pattern[i])), i
+        assert _is_oracle(got[i], _orc(R, kind, d, i, "seed", ex=pattern[i])), ("oracle", i)
+        assert pattern[i] is None or (got[i][1][:, :32] == cl[i][3]).all()
+
+
+@pytest.mark.parametrize("pattern", [(None, "other", "own"), ("other", None, "own")], ids=["middle", "first"])
+@pytest.mark.parametrize("kind", (1, 2))
+def test_commitments_of_other_values_take_the_slow_path_alone(R, kind, pattern):
+    """One client hands in valid points that are not its values' commitments: SG_LCMP marks every element of that client and
+    k_sigma_point_var_batch redoes its c_sq' as the reference computes it (m' L + r2' B~ over the point handed in); its neighbours -- one
+    without a commitment, one with its own -- keep the fast path.  Bytes as the single call and the oracle give them (the proof does not
+    verify either way: the commitment is not the value's)."""
+    d, n = 65, 3
+    cl = [_client(R, d, i) for i in range(n)]
+    got = _batch(R, kind, [c[0] for c in cl], [c[1] for c in cl], [c[2] for c in cl], nonces=[_nonce(R, kind, d, i, "seed")[0] for i in range(n)],
+                 existing_list=[_existing(R, d, i, e) for i, e in enumerate(pattern)], fp=FP)
+    for i in range(n):
+        assert _same(got[i], _one(R, kind, d, i, "seed", ex=pattern[i])), i
+        assert _is_oracle(got[i], _orc(R, kind, d, i, "seed", ex=pattern[i])), ("oracle", i)
+    slow = pattern.index("other")
+    assert not _same(got[slow], _one(R, kind, d, slow, "seed", ex="own"))      # (the case does drive other bytes)
+    assert _verifies(R, kind, got[slow][0], got[slow][1]) is False
+    assert all(_verifies(R, kind, got[i][0], got[i][1]) for i in range(n) if i != slow)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_a_failing_member_does_not_sink_the_call(R, kind):
+    d, n = 65, 5
+    cl = [_client(R, d, i) for i in range(n)]
+    xs, r1s, r2s = [c[0] for c in cl], [c[1] for c in cl], [c[2] for c in cl]
+    xs[1] = xs[1].copy(); xs[1][40] = np.nan
+    ex = [None] * n
+    ex[2] = cl[2][3].copy(); ex[2][64] = 0xFF      # (not its value's commitment either: kinds 1, 2 reach the decode through the slow mark)
+    nonces = [_nonce(R, kind, d, i, "seed")[0] for i in range(n)]
+    nonces[3] = R.Nonce.stream(bytes(64 * (NN[kind] * d - 1)))      # one scalar short
+    got = _batch(R, kind, xs, r1s, r2s, nonces=nonces, existing_list=ex, fp=FP)      # (returns: the call's own code is 0)
+    assert [g.code if isinstance(g, R.RoflError) else 0 for g in got] == [0, 10, 5, 12, 0]
+    for i in (0, 4):
+        assert _same(got[i], _one(R, kind, d, i, "seed")), i
+    # the single call's order for a client with both faults: the non-finite value first
+    ex[1] = ex[2]
+    both = _batch(R, kind, xs[:2], r1s[:2], r2s[:2], nonces=nonces[:2], existing_list=ex[:2], fp=FP)
+    assert _same(both[0], _one(R, kind, d, 0, "seed")) and isinstance(both[1], R.RoflError) and both[1].code == 10
+    with pytest.raises(R.RoflError) as e:
+        _call_single(R, kind, xs[1], r1s[1], r2s[1], nonces[1], ex[1])
+    assert e.value.code == 10
+    # and the call after it is sound
+    again = _batch(R, kind, [c[0] for c in cl[:2]], r1s[:2], r2s[:2], nonces=nonces[:2], fp=FP)
+    assert _same(again[0], _one(R, kind, d, 0, "seed")) and _same(again[1], _one(R, kind, d, 1, "seed"))
+
+
+def test_device_resident_inputs():
+    """One client's values, r1, r2 and existing as device pointers (torch tensors on the GPU), its neighbours' in host memory: same bytes.
+    (Own process: torch has to bring up its HIP runtime before the library's is loaded.)"""
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "gpu_sigma_create_batch_device_check.py")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "DEVICE_INPUTS PASS" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_devices_option(R, kind):
+    """rofl_set_option("devices", 0b11), both logical devices on the one GPU: five clients dealt round-robin, same bytes"""
+    from rofl_project_code_amd import api
+    api.map_device(1, 0)
+    d, n = 65, 5
+    cl = [_client(R, d, i) for i in range(n)]
+    ex = ["own" if i == 3 else None for i in range(n)]
+    try:
+        R.set_option("devices", 0b11)
+        got = _batch(R, kind, [c[0] for c in cl], [c[1] for c in cl], [c[2] for c in cl], nonces=[_nonce(R, kind, d, i, "seed")[0] for i in range(n)],
+                     existing_list=[_existing(R, d, i, e) for i, e in enumerate(ex)], fp=FP)
+    finally:
+        R.set_option("devices", 0)
+    for i in range(n):
+        assert _same(got[i], _one(R, kind, d, i, "seed", ex=ex[i])), i
+        assert _is_oracle(got[i], _orc(R, kind, d, i, "seed", ex=ex[i])), ("oracle", i)

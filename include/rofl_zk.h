@@ -163,7 +163,9 @@ int rofl_verify_rangeproof_batch_strided(size_t n_clients, const uint8_t *const 
 int rofl_clip_f32(const float *in, size_t d, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *out);
 
 /* ---- l2_range_proof_vec (l2_range_proof_vec/mod.rs) ---- */
-/* create_rangeproof_l2 :15-140 */
+/* create_rangeproof_l2 :15-140.  The batch call below with one client, on the calling thread's device: values and blindings32 are host
+ * or device memory; d != d_blindings is 1, then d = 0 or d >= 2^28 (the kernel counts elements in 32 bits), n_partition = 0,
+ * prove_range = 0, an invalid (fp_bits, fp_frac) or a null nonce is 11; then the client's own outcome as listed below. */
 int rofl_create_rangeproof_l2(const float *values, size_t d, const uint8_t *blindings32, size_t d_blindings,
                               size_t prove_range, size_t n_partition, unsigned fp_bits, unsigned fp_frac,
                               const rofl_nonce_t *nonce, uint8_t *proof_out, size_t *proof_len_out,
@@ -173,7 +175,7 @@ int rofl_create_rangeproof_l2(const float *values, size_t d, const uint8_t *blin
  * one-value Bulletproofs of all surviving clients are ONE prove_multiple launch sequence with one set of host hops.  proofs_out[i]
  * (*proof_len_out = 32 * (9 + 2 lg prove_range) bytes each) and commits_out32 + 32 i are byte for byte what rofl_create_rangeproof_l2
  * returns for (values[i], blindings32[i], nonces[i]); client i's nonces sit at index 0 of its own stream or seed.  values[i] (d floats) and
- * blindings32[i] (d scalars) are host or device memory (the single call reads its values on the host).  rc_out[i] is exactly the code the
+ * blindings32[i] (d scalars) are host or device memory (the single call is this call with one client).  rc_out[i] is exactly the code the
  * single call returns for client i, decided in its order: 2 ValueOutOfRangeError (it wins over a NaN wherever the two sit: the range loop
  * runs to its end first), 10 non-finite, 8 OverflowError, 7 NormOutOfRangeError, 3 InvalidBitsize, 12 nonce stream too short -- a client
  * that fails is left out, its outputs are unspecified, and the others are still proved.  The return value is non-zero only for errors of

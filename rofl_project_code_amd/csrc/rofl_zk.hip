@@ -1093,8 +1093,8 @@ int rofl_clip_f32(const float *in, size_t d, size_t prove_range, unsigned fp_bit
 
 namespace {
 // What create_rangeproof_l2 decides on the host once a client's sums are known (l2_range_proof_vec/mod.rs:62-79, then the upstream errors), in
-// the reference's order: the f32 shadow sum against the scalar sum (OverflowError), the norm bound, the bit size, the nonce stream.  The
-// single call and the batch both ask here.  *v_out: the value the sum proof commits to.
+// the reference's order: the f32 shadow sum against the scalar sum (OverflowError), the norm bound, the bit size, the nonce stream.
+// *v_out: the value the sum proof commits to.
 int l2_sum_outcome(const sc &val, float val_float, size_t prove_range, unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonce, u64 *v_out) {
     float val_f = sc_to_f32(val, fp_bits, fp_frac);
     volatile float diff = val_f - val_float;
@@ -1116,12 +1116,14 @@ const char *l2_outcome_text(int rc) {
     }
     return "";
 }
-// create_rangeproof_l2 for the clients of one process (the one-value sum proofs of a round's L2 updates) as ONE launch sequence.
+// THE creator of L2 sum proofs: create_rangeproof_l2 for the clients of one process (the one-value sum proofs of a round's L2 updates) as
+// ONE launch sequence; rofl_create_rangeproof_l2 is a group of one.  rcs[i] is client i's own outcome in the reference's order (within a
+// client ValueOutOfRange 2 wins over NaN 10 wherever they sit, then 8, 7, 3, 12; l2_outcome_text has the texts).
 // k_l2_sumsq_batch (client = grid row, kL2SumBlocks blocks striding over the d values) leaves per client the status bits, the block
 // partials of sum k^2 (192-bit integers) and of the blinding sum, and per element the f32 term of the reference's shadow sum;
 // k_l2_sumsq_combine adds the partials.  WAIT 1: status words, sums and terms are on the host (4 d bytes per client: the shadow sum is
-// serial left to right by definition, so the pool adds every client's terms in order and decides with l2_sum_outcome what the single call
-// would have returned).  The surviving clients are compacted densely: one k_commit over them (WAIT 2: their V bytes, for the
+// serial left to right by definition, so the pool adds every client's terms in order and decides with l2_sum_outcome what the reference
+// returns).  The surviving clients are compacted densely: one k_commit over them (WAIT 2: their V bytes, for the
 // transcripts) and one prove_chunks over na chunks of one value -- the host hops of the Bulletproof are paid once per batch.
 constexpr u32 kL2SumBlocks = 8;      // per client: 2 048 threads stride over d; 48 clients are 384 blocks on 256 CUs
 int l2_create_batch(size_t nc, const float *const *values, size_t d, const uint8_t *const *blind, size_t prove_range, unsigned fp_bits, unsigned fp_frac,
@@ -1195,45 +1197,13 @@ int l2_create_batch(size_t nc, const float *const *values, size_t d, const uint8
 }  // namespace
 int rofl_create_rangeproof_l2(const float *values, size_t d, const uint8_t *blindings32, size_t d_blindings, size_t prove_range, size_t n_partition,
                               unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonce, uint8_t *proof_out, size_t *proof_len_out, uint8_t commit_out[32]) {
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(false, true); Ctx &C = *lane_lock.c;
+    return guarded([&]() -> int {      // a batch of one on the caller's device (the batch entry would bind the first of the `devices` option)
         if (d != d_blindings) return fail(ROFL_WRONG_NUM_BLINDING, "WrongNumBlindingFactors");
-        if (!valid_fp(fp_bits, fp_frac) || d == 0 || n_partition == 0 || prove_range == 0 || !nonce) return fail(ROFL_BAD_PARAM, "bad parameter (the reference panics here)");
-        float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
-        for (size_t i = 0; i < d; i++) if (mn > values[i] || values[i] > mx) return fail(ROFL_VALUE_OUT_OF_RANGE, "ValueOutOfRangeError");
-        // l2_range_proof_vec/mod.rs:37-79: scalar sum of squares, the f32 shadow sum in the reference's
-        // serial left-to-right order (its result decides the OverflowError branch), and the blinding sum.
-        sc val = sc_zero(), bsum = sc_zero();
-        volatile float val_float = 0.0f; float shift = (float)(1u << fp_frac);
-        for (size_t i = 0; i < d; i++) {
-            sc s; int rc = f32_to_sc(values[i], fp_bits, fp_frac, &s); if (rc) return fail(rc, "non-finite value");
-            val = sc_add(val, h_mul(s, s));
-            volatile float q = sc_to_f32(s, fp_bits, fp_frac); volatile float qq = q * q; volatile float term = qq * shift;
-            val_float = (i == 0) ? term : val_float + term;
-            sc bl = sc_frombytes(blindings32 + 32 * i); if (sc_geq_l(bl.v)) bl = sc_from_mont(sc_to_mont(bl));
-            bsum = sc_add(bsum, bl);
-        }
-        u64 v = 0;
-        if (int rc = l2_sum_outcome(val, val_float, prove_range, fp_bits, fp_frac, nonce, &v)) return fail(rc, l2_outcome_text(rc));
-        C.init();
-        timing_begin(C);
-        u64 *vshift = C.vshift.as<u64>(1); sc *d_bl = C.blind.as<sc>(1);
-        HIPCHK(hipMemcpyAsync(vshift, &v, 8, hipMemcpyHostToDevice, C.stream));
-        HIPCHK(hipMemcpyAsync(d_bl, &bsum, 32, hipMemcpyHostToDevice, C.stream));
-        uint8_t *Vb = C.Vbytes.as<uint8_t>(32);
-        ROFL_LAUNCH(k_commit, grid1(1), dim3(TPB), 0, C.stream, 1u, vshift, (const sc *)nullptr, d_bl, C.d_tabB8, C.d_tabBb8, (const niels *)nullptr, Vb, (uint8_t *)nullptr, 0u, 1u);
-        uint8_t hV[32];
-        HIPCHK(hipMemcpyAsync(hV, Vb, 32, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        // BulletproofGens::new(64, 1), label "L2RangeProof" (l2_range_proof_vec/mod.rs:156-171): the first
-        // prove_range generators of party 0 are the same chain prefix.
-        ChunkNonce cn{}; cn.mode = nonce->mode;
-        if (nonce->mode == 1) memcpy(cn.seed.w, nonce->seed, 32);
-        else { uint8_t *sb = C.stream_buf.as<uint8_t>(nonce->stream_scalars * 64 + 64); C.up(sb, nonce->stream, nonce->stream_scalars * 64, C.stream); cn.d_stream = sb; cn.stream_scalars = nonce->stream_scalars; }
-        uint8_t *pout = proof_out;
-        prove_chunks(C, "L2RangeProof", 1, prove_range, 1, vshift, d_bl, std::vector<ChunkNonce>(1, cn), hV, &pout);
-        timing_end(C);
-        memcpy(commit_out, hV, 32);
+        if (!valid_fp(fp_bits, fp_frac) || d == 0 || d >= ((size_t)1 << 28) || n_partition == 0 || prove_range == 0 || !nonce)      // (2^28: the kernel's u32 d)
+            return fail(ROFL_BAD_PARAM, "bad parameter (the reference panics here)");
+        int rc = ROFL_OK;
+        if (int r = l2_create_batch(1, &values, d, &blindings32, prove_range, fp_bits, fp_frac, nonce, &proof_out, commit_out, &rc)) return r;
+        if (rc) return fail(rc, l2_outcome_text(rc));
         *proof_len_out = 32 * (9 + 2 * (size_t)lg2u(prove_range));
         return ROFL_OK;
     });

@@ -51,4 +51,24 @@ for kind in (0, 1, 2):
     got2 = batch(kind, [dev(x) for x in xs], [dev(a) for a in r1s], [dev(b) for b in r2s], None)
     for i in range(n):
         assert (got2[i][0] == want2[i][0]).all() and (got2[i][1] == want2[i][1]).all(), (kind, i)
+# the single call (the C entry itself: the Python wrappers take host arrays) on device-resident values, r1, r2 and existing: the oracle's bytes
+import ctypes
+import orc
+from rofl_project_code_amd import api
+PLEN, CLEN = {0: 128, 1: 192, 2: 160}, {0: 64, 1: 96, 2: 64}
+vp = lambda t: ctypes.c_void_p(t.data_ptr())
+for kind in (0, 1, 2):
+    for i, with_ex in ((0, True), (2, False)):
+        tv, t1, t2, te = dev(xs[i]), dev(r1s[i]), dev(r2s[i]), dev(coms[i])
+        ns = R.Nonce.seeded(seeds[i])._struct()
+        proofs, commits = np.zeros((d, PLEN[kind]), np.uint8), np.zeros((d, CLEN[kind]), np.uint8)
+        out = (FP[0], FP[1], ctypes.byref(ns), proofs.ctypes.data_as(ctypes.c_void_p), commits.ctypes.data_as(ctypes.c_void_p))
+        ex = vp(te) if with_ex else None
+        if kind == 0:
+            rc = api.lib().rofl_create_randproof_vec(vp(tv), ctypes.c_size_t(d), vp(t1), ctypes.c_size_t(d), ex, *out)
+        else:
+            fn = api.lib().rofl_create_squarerandproof_vec if kind == 1 else api.lib().rofl_create_squareproof_vec
+            rc = fn(vp(tv), ctypes.c_size_t(d), vp(t1), ctypes.c_size_t(d), vp(t2), ex, *out)
+        orc_rc, opr, ocm = orc.sigma_create(kind, xs[i], r1s[i], r2s[i] if kind else None, FP[0], FP[1], seed=seeds[i], existing=coms[i] if with_ex else None)
+        assert rc == 0 and orc_rc == 0 and (proofs == opr).all() and (commits == ocm).all(), ("single call, device inputs", kind, i, rc)
 print("DEVICE_INPUTS PASS")

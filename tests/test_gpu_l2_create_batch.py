@@ -3,6 +3,9 @@ one launch sequence -- k_l2_sumsq_batch (8 blocks of 256 per client, grid-stride
 blinding sum, the per-element f32 terms of the shadow sum), the host's serial shadow sum and decision, one k_commit and one prove_chunks
 over the surviving clients.  Every client's proof and commitment must be the bytes of its own single call (rofl_create_rangeproof_l2) and of
 the CPU oracle (orc.create_rangeproof_l2), and every client's code the code of both, whatever its neighbours in the batch are.
+The single call runs the same code as a group of one: "batch equals single" says that a client's neighbours do not matter, and the oracle
+anchors the bytes and the codes of both.  The single call's own promises are here too: every outcome code with its rofl_last_error text,
+the serial f32 shadow sum, a blinding >= l (every client's first), device-resident inputs.
 
 Shapes: d around the block (255, 256, 257) and the wave (63, 64, 65), 1; d = 8 * 256 + 2, where the grid-stride loop wraps for two
 threads; n = 2 and 17 (seventeen chunks of one value in one prove_chunks)."""
@@ -51,7 +54,7 @@ def _client(d, i):
         k[idx] = rng.integers(-3, 4, size=idx.size)
         k[idx[0]] = 3 if i % 2 else -3      # (never all zero; negative values too)
         bl = rng.integers(0, 256, size=(d, 32), dtype=np.uint8); bl[:, 31] &= 0x0F
-        bl[0] = 0xFF                        # a blinding >= l: reduced first, as the host loop does
+        bl[0] = 0xFF                        # a blinding >= l: reduced first, as the reference does
         _inputs[(d, i)] = ((k / 128.0).astype(np.float32), bl)
     return _inputs[(d, i)]
 
@@ -89,6 +92,51 @@ def test_bytes_equal_the_single_call_and_the_oracle(R, fp, prove_range, n, d, mo
         assert _equal(g, orc.create_rangeproof_l2(cl[i][0], cl[i][1], prove_range, 1, fp[0], fp[1], **_nonce(R, i, mode, prove_range)[1])), ("oracle", i)
         assert orc.verify_rangeproof_l2(g[1], g[2], prove_range, fp[0], fp[1]) == (0, True)
     assert R.l2_range_proof_vec.verify_rangeproof_l2_batch([g[0] for g in got], np.stack([g[1] for g in got]), prove_range, verifier_seed=b"\x05" * 32, fp=fp) == [True] * n
+
+
+@pytest.mark.parametrize("mode", ["seed", "stream"])
+@pytest.mark.parametrize("d", DS)
+@pytest.mark.parametrize("fp,prove_range", CONFIGS, ids=lambda v: str(v))
+def test_the_single_call_equals_the_oracle(R, fp, prove_range, d, mode):
+    """rofl_create_rangeproof_l2 alone against orc.create_rangeproof_l2 (client 0's blindings start with one >= l)"""
+    x, bl = _client(d, 0)
+    got = _single(R, x, bl, prove_range, _nonce(R, 0, mode, prove_range)[0], fp)
+    assert got[0] == 0 and got[1].size == 32 * (9 + 2 * int(np.log2(prove_range)))
+    assert _equal(got, orc.create_rangeproof_l2(x, bl, prove_range, 1, fp[0], fp[1], **_nonce(R, 0, mode, prove_range)[1]))
+    assert orc.verify_rangeproof_l2(got[1], got[2], prove_range, fp[0], fp[1]) == (0, True)
+
+
+TEXTS = {2: "ValueOutOfRangeError", 10: "non-finite value", 8: "OverflowError", 7: "NormOutOfRangeError", 3: "InvalidBitsize", 12: "nonce stream too short"}
+
+
+def test_the_single_calls_outcomes_and_texts(R):
+    """Every outcome of the single call with its rofl_last_error text, in the reference's order within a vector (ValueOutOfRange 2 wins over
+    NaN 10 wherever they sit; then OverflowError 8, NormOutOfRange 7, InvalidBitsize 3): the code is the oracle's.  The short stream (12) is
+    this library's own refusal -- the oracle reads zeros past the end of a stream -- and comes last: after the values' own outcomes."""
+    d = 257
+    cases = [((16, 7), 16, m[1], m[2]) for m in _parity_members(d)]                      # 0, 10, 2, 2, 8, 8 (16 bits cannot hold the sum), 12, 0
+    cases += [((32, 7), 16, m[1], False) for m in _parity_members(d)[4:6]]               # norm 8.0 and [6, 6] where the sum fits: 7, 7
+    cases.append(((16, 7), 24, _client(d, 0)[0], False))                                 # a bit size no proof can have
+    cases.append(((16, 7), 24, _parity_members(d)[4][1], False))                         # ... after the norm
+    cases.append(((32, 7), 32, (np.random.default_rng(4242).integers(200, 300, size=300) / 128.0).astype(np.float32), False))      # sum k^2 > 2^24
+    cases.append(((16, 7), 16, _parity_members(d)[1][1], True))                          # a NaN before the stream's length
+    seen = []
+    for i, (fp, prove_range, x, short) in enumerate(cases):
+        bl = _client(x.size, i % 2)[1]
+        nonce, okw = _nonce(R, i % 7, "stream", prove_range, short=short)
+        want = orc.create_rangeproof_l2(x, bl, prove_range, 1, fp[0], fp[1], **okw)[0]
+        if short and want == 0:
+            want = 12
+        try:
+            R.l2_range_proof_vec.create_rangeproof_l2(x, bl, prove_range, 1, nonce=nonce, fp=fp)
+            code = 0
+        except R.RoflError as e:
+            code = e.code
+            assert str(e) == "%s (%d): %s" % (e.name, code, TEXTS[code]), str(e)
+        print("case", i, "single", code, "oracle", want)
+        assert code == want, i
+        seen.append(code)
+    assert seen[:4] == [0, 10, 2, 2] and seen[6] == 12 and seen[-1] == 10 and set(seen) == {0, 2, 10, 8, 7, 3, 12}
 
 
 def _parity_members(d):
@@ -145,6 +193,7 @@ def test_the_shadow_sums_order(R):
     assert [o[0] for o in oracle] == [0, 8]      # (what the oracle said when this test was written; the assertions below do not depend on it)
     got = R.l2_range_proof_vec.create_rangeproof_l2_batch(xs, bls, prove_range, 1, nonces=[_nonce(R, i, "seed", prove_range)[0] for i in range(2)], fp=fp)
     for i in range(2):
+        assert _equal(_single(R, xs[i], bls[i], prove_range, _nonce(R, i, "seed", prove_range)[0], fp), oracle[i]), ("single call against the oracle", i)
         assert _equal(_outcome(got[i]), oracle[i]), ("oracle", i)
         assert _equal(_outcome(got[i]), _single(R, xs[i], bls[i], prove_range, _nonce(R, i, "seed", prove_range)[0], fp)), ("single call", i)
 
@@ -154,3 +203,10 @@ def test_device_resident_inputs():
     (Own process: torch has to bring up its HIP runtime before the library's is loaded.)"""
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "gpu_l2_create_batch_device_check.py")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "DEVICE_INPUTS PASS" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_the_single_call_takes_device_resident_inputs():
+    """rofl_create_rangeproof_l2 (the C entry itself) on device-resident values and blindings: the oracle's bytes.  (Before the single call
+    became a group of one it read values[i] on the host: this case cannot run there.)"""
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "gpu_l2_create_batch_device_check.py"), "--single"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "SINGLE_DEVICE_INPUTS PASS" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

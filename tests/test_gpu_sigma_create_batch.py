@@ -4,6 +4,11 @@ sixteen clients, k_sigma_points_batch (one thread per point, blocks of 64 elemen
 k_sigma_point_var_batch (the slow marks of a client whose handed-in commitments are not its values') and k_sigma_finish_batch (blocks of
 256).  Every client's proofs and commitments must be the bytes of its own single call and of the CPU oracle (orc.sigma_create), whatever
 its neighbours in the batch are.
+The single calls (rofl_create_randproof_vec / _squarerandproof_vec / _squareproof_vec) are held to the oracle on their own as well, so
+that "batch equals single" never stands alone: every kind, shape and nonce mode, commitments handed in (the values' own, and valid points
+that commit to other values: the slow-mark walk), the order of the call's checks with the rofl_last_error texts, device-resident inputs.
+Whichever code runs behind the single entry points -- an implementation of its own or a group of one -- these hold.  (Runs of elements of
+one vector are test_gpu_chunk_split.py's.)
 
 Shapes: d around the points kernel's block (63, 64, 65) and the finish kernel's block (255, 256, 257), 0 and 1; n = 1, 2 and 17 (a second
 group, of one)."""
@@ -126,6 +131,29 @@ def test_bytes_equal_the_single_call_and_the_oracle(R, kind, n, d, mode):
             assert orc.sigma_verify(kind, got[i][0], got[i][1]) == (0, True)
 
 
+@pytest.mark.parametrize("mode", ["seed", "stream"])
+@pytest.mark.parametrize("d", DS)
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_single_call_equals_the_oracle(R, kind, d, mode):
+    """The single call alone against orc.sigma_create: the oracle is the anchor of the bytes of the single call and of the batch."""
+    got = _one(R, kind, d, 0, mode)
+    assert _is_oracle(got, _orc(R, kind, d, 0, mode))
+    if d:
+        assert _verifies(R, kind, got[0], got[1]) is True
+
+
+@pytest.mark.parametrize("mode", ["seed", "stream"])
+@pytest.mark.parametrize("kind,ex", [(k, "own") for k in KINDS] + [(1, "other"), (2, "other")])
+def test_the_single_call_with_existing_equals_the_oracle(R, kind, ex, mode):
+    """d = 65.  "own": the values' commitments, completed.  "other" (kinds 1, 2): valid points that commit to other values -- SG_LCMP marks
+    every element and the variable-base kernel walks the marks; bytes as the reference computes them, and a proof that does not verify."""
+    d = 65
+    got = _one(R, kind, d, 0, mode, ex=ex)
+    assert _is_oracle(got, _orc(R, kind, d, 0, mode, ex=ex))
+    assert (got[1][:, :32] == _existing(R, d, 0, ex)).all()
+    assert _verifies(R, kind, got[0], got[1]) is (ex == "own")
+
+
 @pytest.mark.parametrize("pattern", [(None, "own", None), ("own", None, "own")], ids=["middle", "outer"])
 @pytest.mark.parametrize("kind", KINDS)
 def test_mixed_existing(R, kind, pattern):
@@ -185,8 +213,41 @@ def test_a_failing_member_does_not_sink_the_call(R, kind):
     assert _same(again[0], _one(R, kind, d, 0, "seed")) and _same(again[1], _one(R, kind, d, 1, "seed"))
 
 
+def _raises(R, kind, code, text, x, r1, r2, **kw):
+    """the single call fails with `code` and rofl_last_error's text `text`"""
+    with pytest.raises(R.RoflError) as e:
+        _call_single(R, kind, x, r1, r2, kw["nonce"], kw.get("existing"))
+    assert e.value.code == code and str(e.value) == "%s (%d): %s" % (e.value.name, code, text), str(e.value)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_single_calls_error_order_and_texts(R, kind):
+    """WrongNumBlindingFactors (ROFL_WRONG_NUM_BLINDING, d != d_r1: the oracle's code too) before everything; a short stream (12) before
+    the device sees the values; then, in one vector, a non-finite value (10) before an undecodable commitment (5), which alone is 5.
+    Codes as rofl_zk.h numbers them, texts as rofl_last_error gives them."""
+    d = 65
+    x, r1, r2, com = _client(R, d, 0)[:4]
+    nonce = _nonce(R, kind, d, 0, "seed")[0]
+    short = R.Nonce.stream(bytes(64 * (NN[kind] * d - 1)))      # one scalar short
+    xnan = x.copy(); xnan[40] = np.nan
+    bad = com.copy(); bad[64] = 0xFF      # (not its value's commitment either: kinds 1, 2 reach the decode through the slow mark)
+    NAN = "non-finite value (the reference panics in fixed::saturating_from_float)"
+    wrong = orc.sigma_create(kind, x, r1[:-1], r2 if kind else None, FP[0], FP[1], seed=b"\x01" * 32)[0]
+    assert wrong == 1
+    _raises(R, kind, wrong, "WrongNumBlindingFactors", x, r1[:-1], r2, nonce=nonce)
+    _raises(R, kind, wrong, "WrongNumBlindingFactors", xnan, r1[:-1], r2, nonce=short, existing=bad)      # before everything else
+    _raises(R, kind, 12, "nonce stream too short", x, r1, r2, nonce=short)
+    _raises(R, kind, 12, "nonce stream too short", xnan, r1, r2, nonce=short, existing=bad)                # before the device sees the values
+    _raises(R, kind, 10, NAN, xnan, r1, r2, nonce=nonce)
+    _raises(R, kind, 10, NAN, xnan, r1, r2, nonce=nonce, existing=bad)                                     # before the commitment
+    _raises(R, kind, 5, "invalid Ristretto encoding", x, r1, r2, nonce=nonce, existing=bad)
+    assert orc.sigma_create(kind, x, r1, r2 if kind else None, FP[0], FP[1], seed=b"\x01" * 32, existing=bad)[0] == 5
+    assert _same(_call_single(R, kind, x, r1, r2, nonce, None), _one(R, kind, d, 0, "seed"))      # (and the next call is sound)
+
+
 def test_device_resident_inputs():
-    """One client's values, r1, r2 and existing as device pointers (torch tensors on the GPU), its neighbours' in host memory: same bytes.
+    """One client's values, r1, r2 and existing as device pointers (torch tensors on the GPU), its neighbours' in host memory: same bytes;
+    then the single call (the C entry itself) on device-resident inputs: the oracle's bytes.
     (Own process: torch has to bring up its HIP runtime before the library's is loaded.)"""
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "gpu_sigma_create_batch_device_check.py")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "DEVICE_INPUTS PASS" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

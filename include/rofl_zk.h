@@ -320,6 +320,23 @@ int rofl_get_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float
 int rofl_fp_square_vec(const uint8_t *in32, size_t d, unsigned fp_bits, unsigned fp_frac, uint8_t *out32);      /* conversion32.rs:66-88 square; 8 = overflow (the reference panics) */
 int rofl_scalar_powers(const uint8_t value32[32], size_t count, uint8_t *out32);                              /* conversion32.rs:101-122 precompute_exponentiate / exponentiate */
 int rofl_scalar_add_vec(const uint8_t *a32, const uint8_t *b32, size_t d, int subtract, uint8_t *out32);      /* pedersen_ops.rs:78-94 add_scalar_vec(_vec) */
+/* Blinding vectors from seeds (pedersen_ops.rs:110-127 rnd_scalar_vec / generate_cancelling_scalar_vec with the randomness an explicit input,
+ * and the dealer-free pairwise masks a deployment uses instead of the reference's dealer).
+ *   stream of a 32-byte seed: scalar k = wide-reduce(SHAKE256("rofl-zk/blind/v1" || seed[32] || u64le(k >> 1))[64 (k & 1) .. 64 (k & 1) + 64]),
+ *   the construction of nonce mode 1 under a label of its own (the nonce stream and the blinding stream of one seed never coincide);
+ *   out32[v][k] = sum_t terms[v][t].sign * stream(terms[v][t].seed)[first + k] mod l for k in [0, d): n_vec vectors in ONE launch.
+ * A vector without terms is the zero vector.  `first` lets ranks, devices or chunks take runs of one vector: the runs concatenate to the bytes of
+ * the unsplit call.  out32[v] holds d * 32 bytes of host memory or of device memory of the library's device (see "Memory spaces"; a device
+ * output must be 16-byte aligned).  Returns 11 before the device is touched for: a null array with n_vec > 0, a null terms[v] with
+ * term_count[v] > 0, a null out32[v] with d > 0, a sign other than +1 / -1, n_vec > 65 535, d >= 2^28, first + d > 2^63, more than 2^22 terms
+ * in all; n_vec = 0 or d = 0 returns 0 and writes nothing.  Seeds are secrets: they never appear in rofl_last_error, and the library's own
+ * copies of the term list are overwritten with zeros before the call returns.  The call runs on the calling thread's device and lane like
+ * the other pedersen_ops calls; the `devices` option does not apply (split a vector with `first` instead). */
+typedef struct { uint8_t seed[32]; int32_t sign; } rofl_blind_term_t;      /* sign: +1 or -1 */
+int rofl_blinding_vecs(size_t n_vec, const size_t *term_count, const rofl_blind_term_t *const *terms,
+                       size_t first, size_t d, uint8_t *const *out32);
+/* pedersen_ops.rs:124-127 with the randomness an explicit input: one vector of one +1 term */
+int rofl_rnd_scalar_vec(const uint8_t seed[32], size_t first, size_t d, uint8_t *out32);
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out);         /* conversion32.rs:49-54 */
 int rofl_uint_to_f32_vec(const uint64_t *in, size_t d, unsigned fp_bits, unsigned fp_frac, float *out);        /* conversion32.rs:41-47 */
 int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float *out);  /* conversion32.rs:62-64 */
@@ -464,7 +481,10 @@ int rofl_comm_destroy(void);
  * (proofs, commitments) and of the per-element Sigma-proof entry points (values, randomness, existing commitments, proofs,
  * commitments) may live in host memory or in device memory of the library's device (HIP unified addressing): a caller that
  * already holds the update on the GPU passes device pointers and nothing crosses PCIe on the way in.  Outputs are written to
- * host memory. */
+ * host memory, with one exception: the out32[v] of rofl_blinding_vecs / out32 of rofl_rnd_scalar_vec may be device memory of the
+ * library's device (16-byte aligned), which the kernel then writes in place -- blindings generated there can be handed to the create
+ * calls as device inputs without ever crossing PCIe.  A host output of those calls goes through the lane's workspace and the pinned
+ * staging path like every other output. */
 
 /* ---- behaviour options ----
  * Switches that change WHAT a call returns or how it waits are part of the ABI, not of the process environment.  `key` is one of the

@@ -89,6 +89,8 @@ int rofl_dbg_host_fd_ops(const uint8_t a[32], const uint8_t b[32], uint8_t out_m
 int rofl_dbg_host_fd_scalarmult(const uint8_t k[32], const uint8_t p[32], uint8_t out[32]);
 int rofl_dbg_host_merlin(const uint8_t *label, size_t label_len, const uint8_t *msg, size_t msg_len, uint8_t out[64]);
 int rofl_dbg_host_nonce(const uint8_t seed[32], uint64_t idx, uint8_t out[32]);
+/* scalar idx of the blinding stream of a seed (rofl_blinding_vecs), computed on the host from the source the kernel is compiled from */
+int rofl_dbg_host_blind(const uint8_t seed[32], uint64_t idx, uint8_t out[32]);
 
 /* host micro-benchmarks of the code the per-round hops run (nanoseconds per operation on the calling core).
  * what: 0 Keccak-f[1600]; 1 point doubling, 2 point addition, 3 Ristretto encoding (51-bit host arithmetic);

@@ -152,6 +152,11 @@ extern "C" {
     pub fn rofl_fp_square_vec(in32: *const u8, d: usize, fp_bits: c_uint, fp_frac: c_uint, out32: *mut u8) -> c_int;
     pub fn rofl_scalar_powers(value32: *const u8, count: usize, out32: *mut u8) -> c_int;
     pub fn rofl_scalar_add_vec(a32: *const u8, b32: *const u8, d: usize, subtract: c_int, out32: *mut u8) -> c_int;
+    /// out32[v][k] = sum_t terms[v][t].sign * stream(terms[v][t].seed)[first + k] mod l for k in [0, d): n_vec blinding vectors in one launch
+    /// (out32[v]: d * 32 bytes of host memory, or 16-byte aligned device memory of the library's device)
+    pub fn rofl_blinding_vecs(n_vec: usize, term_count: *const usize, terms: *const *const RoflBlindTerm, first: usize, d: usize,
+        out32: *const *mut u8) -> c_int;
+    pub fn rofl_rnd_scalar_vec(seed: *const u8, first: usize, d: usize, out32: *mut u8) -> c_int;
     pub fn rofl_f32_to_fp_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut u64) -> c_int;
     pub fn rofl_uint_to_f32_vec(input: *const u64, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
     pub fn rofl_get_l2_clip_bounds(range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
@@ -169,6 +174,13 @@ extern "C" {
 }
 
 /// rofl_wire_msg_t (include/rofl_zk.h): the proto3 messages of flservice.proto:75-100 as spans over `to_bytes` concatenations
+/// rofl_blind_term_t: one term of a blinding vector -- the 32-byte seed of a stream and its sign (+1 or -1)
+#[repr(C)]
+pub struct RoflBlindTerm {
+    pub seed: [u8; 32],
+    pub sign: i32,
+}
+
 #[repr(C)]
 pub struct RoflWireMsg {
     pub kind: c_int,                       // 0 EncRangeData, 1 EncNormData, 2 EncNormDataCompressed

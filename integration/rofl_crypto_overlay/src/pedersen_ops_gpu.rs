@@ -1,5 +1,8 @@
 //! GPU bodies for the vector operations of rofl_crypto/src/pedersen_ops.rs:9-59, 103-108 (same signatures; the scalar-only
-//! helpers of that file -- add_scalar_vec, zero_*_vec, rnd_scalar_vec, generate_cancelling_scalar_vec -- stay as they are).
+//! helpers of that file -- add_scalar_vec, zero_*_vec -- and its rnd_scalar_vec / generate_cancelling_scalar_vec, which draw from
+//! thread_rng, stay as they are).  The *_seeded functions and pairwise_blinding_vec at the end are additions: blinding vectors
+//! expanded on the device from 32-byte seeds (rofl_blinding_vecs), for hosts that want :110-127 reproducible, or cancelling
+//! blindings without the dealer of :110-122.
 use curve25519_dalek_ng::ristretto::RistrettoPoint;
 use curve25519_dalek_ng::scalar::Scalar;
 
@@ -54,3 +57,43 @@ pub fn sum_points_strided(bytes: &[u8], d: usize, stride: usize) -> RistrettoPoi
     bytes_to_points(&out)[0]
 }
 pub fn sum_rp_vec(rp_vec: &Vec<RistrettoPoint>) -> RistrettoPoint { sum_points_strided(&points_to_bytes(rp_vec), rp_vec.len(), 32) }
+
+fn blinding_vecs(term_lists: &[Vec<RoflBlindTerm>], first: usize, d: usize) -> Vec<Vec<Scalar>> {
+    let counts: Vec<usize> = term_lists.iter().map(|t| t.len()).collect();
+    let tp: Vec<*const RoflBlindTerm> = term_lists.iter().map(|t| t.as_ptr()).collect();
+    let mut out: Vec<Vec<u8>> = term_lists.iter().map(|_| vec![0u8; d * 32]).collect();
+    let op: Vec<*mut u8> = out.iter_mut().map(|o| o.as_mut_ptr()).collect();
+    let rc = unsafe { rofl_blinding_vecs(term_lists.len(), counts.as_ptr(), tp.as_ptr(), first, d, op.as_ptr()) };
+    assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
+    out.iter().map(|o| bytes_to_scalars(o)).collect()
+}
+/// rnd_scalar_vec (:124-127) with the randomness an explicit input: scalars [0, length) of the blinding stream of `seed`.
+pub fn rnd_scalar_vec_seeded(length: usize, seed: &[u8; 32]) -> Vec<Scalar> {
+    let mut out = vec![0u8; length * 32];
+    let rc = unsafe { rofl_rnd_scalar_vec(seed.as_ptr(), 0, length, out.as_mut_ptr()) };
+    assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
+    bytes_to_scalars(&out)
+}
+/// generate_cancelling_scalar_vec (:110-122) from one seed, as one device call: vector i < n_vec - 1 is the stream of
+/// seed_i = SHA3-256("rofl-zk/blind/v1/vec" || seed || u32le(i)), the last vector is minus their sum.
+pub fn generate_cancelling_scalar_vec_seeded(n_vec: usize, n_dim: usize, seed: &[u8; 32]) -> Vec<Vec<Scalar>> {
+    use sha3::{Digest, Sha3_256};
+    assert!(n_vec >= 1);
+    let seeds: Vec<[u8; 32]> = (0..n_vec - 1).map(|i| {
+        let mut h = Sha3_256::new();
+        h.update(b"rofl-zk/blind/v1/vec"); h.update(seed); h.update(&(i as u32).to_le_bytes());
+        let mut s = [0u8; 32]; s.copy_from_slice(&h.finalize()); s
+    }).collect();
+    let mut lists: Vec<Vec<RoflBlindTerm>> = seeds.iter().map(|s| vec![RoflBlindTerm { seed: *s, sign: 1 }]).collect();
+    lists.push(seeds.iter().map(|s| RoflBlindTerm { seed: *s, sign: -1 }).collect());
+    blinding_vecs(&lists, 0, n_dim)
+}
+/// Dealer-free cancelling blindings: client `index` holds one shared seed per peer, `peers` = (peer index, seed), and its vector is
+/// the sum over the peers of +stream(seed) where index < peer index, -stream(seed) otherwise.  A seed serves ONE round.
+pub fn pairwise_blinding_vec(index: usize, peers: &[(usize, [u8; 32])], d: usize) -> Vec<Scalar> {
+    let terms: Vec<RoflBlindTerm> = peers.iter().map(|(j, s)| {
+        assert!(*j != index, "a client is not its own peer");
+        RoflBlindTerm { seed: *s, sign: if index < *j { 1 } else { -1 } }
+    }).collect();
+    blinding_vecs(&[terms], 0, d).pop().unwrap()
+}

@@ -9,7 +9,9 @@ Scalars / points are numpy uint8 arrays of shape (d, 32); proofs are (n_proofs, 
 Errors that the reference reports as Err(..) (or panics) raise RoflError(code).
 """
 import ctypes
+import hashlib
 import os
+import struct
 import threading
 
 import numpy as np
@@ -34,6 +36,11 @@ class RoflError(Exception):
 class _NonceStruct(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int), ("stream", ctypes.c_void_p), ("stream_scalars", ctypes.c_size_t),
                 ("seed", ctypes.c_ubyte * 32)]
+
+
+class _BlindTerm(ctypes.Structure):
+    """rofl_blind_term_t"""
+    _fields_ = [("seed", ctypes.c_ubyte * 32), ("sign", ctypes.c_int32)]
 
 
 class _Timing(ctypes.Structure):
@@ -972,6 +979,116 @@ class pedersen_ops:
         vecs = [pedersen_ops.rnd_scalar_vec(n_dim) for _ in range(n_vec)]
         vecs[-1] = pedersen_ops.add_scalar_vec(pedersen_ops.zero_scalar_vec(n_dim), pedersen_ops.add_scalar_vec_vec(vecs[:-1]), subtract=True)
         return vecs
+
+    # ---- blinding vectors from seeds (rofl_blinding_vecs): one kernel launch per call, whatever the number of vectors and terms ----
+    @staticmethod
+    def blinding_vecs(term_lists, d, first=0, out=None):
+        """rofl_blinding_vecs: vector v = sum over term_lists[v] = [(seed32, sign), ...] of sign * stream(seed)[first .. first + d) mod l, where
+        scalar k of a seed's stream is SHAKE256("rofl-zk/blind/v1" || seed || u64le(k >> 1))[64 (k & 1) .. + 64] reduced mod l.  All vectors
+        are ONE launch.  out=None returns one (n_vec, d, 32) uint8 array; otherwise `out` lists one destination per vector, written in
+        place: a contiguous uint8 numpy array of d * 32 bytes, or a torch uint8 tensor / a pointer (int) on the library's GPU (16-byte
+        aligned; nothing crosses PCIe), and the list is returned.  A sign other than +1 / -1 raises ValueError."""
+        n, d, first = len(term_lists), int(d), int(first)
+        if d < 0 or first < 0:
+            raise ValueError("d and first are not negative")
+        counts = (_sz * max(n, 1))()
+        keep, tp = [], (ctypes.c_void_p * max(n, 1))()
+        for v, terms in enumerate(term_lists):
+            arr = (_BlindTerm * max(len(terms), 1))()
+            for t, (seed, sign) in enumerate(terms):
+                seed = bytes(seed)
+                if len(seed) != 32:
+                    raise ValueError("a seed is 32 bytes")
+                if sign not in (1, -1):
+                    raise ValueError("a term's sign is +1 or -1")
+                ctypes.memmove(arr[t].seed, seed, 32)
+                arr[t].sign = int(sign)
+            counts[v] = len(terms)
+            keep.append(arr)
+            tp[v] = ctypes.addressof(arr)
+        if out is None:
+            res = np.empty((n, d, 32), dtype=np.uint8)      # every byte is written by the call (n * d * 32 of them: no zeroing pass in front)
+            dst = [res[v] for v in range(n)]
+        else:
+            res = dst = list(out)
+            if len(dst) != n:
+                raise ValueError("one destination per vector")
+        op = (ctypes.c_void_p * max(n, 1))()
+        for v, o in enumerate(dst):
+            if _is_dev(o):
+                if not o.is_contiguous() or o.element_size() != 1 or o.numel() < d * 32:
+                    raise ValueError("a device destination is a contiguous uint8 tensor of d * 32 bytes")
+                op[v] = o.data_ptr()
+            elif isinstance(o, int):
+                op[v] = o
+            else:
+                if not (isinstance(o, np.ndarray) and o.dtype == np.uint8 and o.flags.c_contiguous and o.flags.writeable and o.size >= d * 32):
+                    raise ValueError("a host destination is a writable contiguous uint8 array of d * 32 bytes")
+                op[v] = o.ctypes.data
+        try:
+            _check(lib().rofl_blinding_vecs(_sz(n), counts, tp, _sz(first), _sz(d), op))
+        finally:
+            for arr in keep:
+                ctypes.memset(arr, 0, ctypes.sizeof(arr))
+        return res
+
+    @staticmethod
+    def rnd_scalar_vec_seeded(length, seed, first=0, out=None):
+        """pedersen_ops.rs:124-127 with the randomness an explicit input: scalars [first, first + length) of the blinding stream of `seed`
+        (blinding_vecs with one +1 term).  -> uint8[length, 32], or `out` (host array / device tensor) written in place."""
+        if out is None:
+            return pedersen_ops.blinding_vecs([[(seed, 1)]], length, first)[0]
+        pedersen_ops.blinding_vecs([[(seed, 1)]], length, first, out=[out])
+        return out
+
+    @staticmethod
+    def cancelling_vec_seed(seed, i):
+        """seed of vector i of generate_cancelling_scalar_vec_seeded: SHA3-256("rofl-zk/blind/v1/vec" || seed || u32le(i))"""
+        return hashlib.sha3_256(b"rofl-zk/blind/v1/vec" + bytes(seed) + struct.pack("<I", int(i))).digest()
+
+    @staticmethod
+    def generate_cancelling_scalar_vec_seeded(n_vec, n_dim, seed):
+        """pedersen_ops.rs:110-122 from one seed, as ONE rofl_blinding_vecs call: vector i < n_vec - 1 is the stream of
+        seed_i = SHA3-256("rofl-zk/blind/v1/vec" || seed || u32le(i)), the last vector is minus their sum (n_vec = 1: the zero vector).
+        -> list of n_vec uint8[n_dim, 32] arrays whose element-wise sum is zero mod l."""
+        n_vec = int(n_vec)
+        if n_vec < 1 or len(bytes(seed)) != 32:
+            raise ValueError("n_vec >= 1 and a 32-byte seed")
+        seeds = [pedersen_ops.cancelling_vec_seed(seed, i) for i in range(n_vec - 1)]
+        res = pedersen_ops.blinding_vecs([[(s, 1)] for s in seeds] + [[(s, -1) for s in seeds]], n_dim)
+        return [res[v] for v in range(n_vec)]
+
+    @staticmethod
+    def _pairwise_terms(index, peers):
+        terms = []
+        for peer_index, shared_seed in peers:
+            if int(peer_index) == int(index):
+                raise ValueError("a client is not its own peer")
+            terms.append((shared_seed, 1 if int(index) < int(peer_index) else -1))
+        return terms
+
+    @staticmethod
+    def pairwise_blinding_vec(index, peers, d, first=0, out=None):
+        """Dealer-free cancelling blindings: client `index` shares a seed with every peer, peers = [(peer_index, shared_seed32), ...], and its
+        vector is sum_j +-stream(s_ij)[first .. first + d) with + where index < peer_index, - otherwise -- the vectors of all clients of a
+        round sum to zero, and the sum of the remaining ones after a dropout is minus the vector of the client that left.  A seed serves ONE
+        round (pairwise_round_seed derives per-round seeds from a long-lived shared secret)."""
+        terms = pedersen_ops._pairwise_terms(index, peers)
+        if out is None:
+            return pedersen_ops.blinding_vecs([terms], d, first)[0]
+        pedersen_ops.blinding_vecs([terms], d, first, out=[out])
+        return out
+
+    @staticmethod
+    def pairwise_blinding_vecs(clients, d):
+        """pairwise_blinding_vec for a process that hosts several clients, clients = [(index, peers), ...]: ONE call -> uint8[n, d, 32]"""
+        return pedersen_ops.blinding_vecs([pedersen_ops._pairwise_terms(i, peers) for i, peers in clients], d)
+
+    @staticmethod
+    def pairwise_round_seed(shared_secret, round_no):
+        """SHA3-256("rofl-zk/blind/v1/round" || shared_secret || u64le(round_no)): the seed two clients use in round `round_no`.  A seed
+        serves ONE round: masks of two rounds under one seed are equal, and the difference of the two masked updates would be in the clear."""
+        return hashlib.sha3_256(b"rofl-zk/blind/v1/round" + bytes(shared_secret) + struct.pack("<Q", int(round_no))).digest()
 
     @staticmethod
     def compute_shifted_values_vec(values, offset):

@@ -101,6 +101,16 @@ HD void shake256_seeded_block(u64 st[25], const u64 dom[2], const u64 seed[4], u
     st[16] ^= 0x8000000000000000ULL;     // final bit of the 136-byte rate
     keccak_f1600(st);
 }
+// Blinding streams (rofl_blinding_vecs): the construction of the nonce DRBG under a label of its own, so that the nonce stream and the
+// blinding stream of one seed never coincide.
+#define ROFL_BLIND_DOM {0x2f6b7a2d6c666f72ULL, 0x31762f646e696c62ULL}      /* "rofl-zk/" "blind/v1" */
+// wide scalar h (0 / 1) of a squeezed block: bytes 64 h .. 64 h + 64, reduced like Scalar::from_bytes_mod_order_wide (canonical)
+HD sc xof_block_scalar(const u64 st[25], int h) {
+    sc lo, hi;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { lo.v[2 * i] = (u32)st[8 * h + i]; lo.v[2 * i + 1] = (u32)(st[8 * h + i] >> 32); hi.v[2 * i] = (u32)st[8 * h + 4 + i]; hi.v[2 * i + 1] = (u32)(st[8 * h + 4 + i] >> 32); }
+    return sc_from_wide(lo, hi);
+}
 
 // ---------------------------------------------------------------- host-only sponge helpers
 // Host-only Keccak-f[1600] for the transcripts: two rounds per iteration with the state in locals (clang keeps the in-place form above,

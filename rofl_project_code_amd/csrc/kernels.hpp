@@ -333,6 +333,42 @@ __global__ void __launch_bounds__(TPB) k_nonce_expand(u32 n, u32 m, const ChunkP
 }
 #endif
 
+// ================================================================ blinding vectors
+// rofl_blinding_vecs: out[v][k] = sum_t sign_t * stream(seed_t)[first + k] mod l.  Scalar idx of a seed's stream = bytes 64 (idx & 1) .. + 64 of
+// SHAKE256("rofl-zk/blind/v1" || seed || u64le(idx >> 1)), wide-reduced: the nonce construction under its own label.
+// blockIdx.y = output vector; thread = one XOF block = scalars 2 blk, 2 blk + 1 of the index space, for every term of its vector.  The term
+// list is indexed by blockIdx.y and the loop counter only, so the seeds and signs come through the scalar data path and the sign is a
+// wave-uniform select.  A thread's two results are 64 contiguous bytes of the vector (a wave writes 4 KB); the first and the last block of
+// a vector own one scalar only when first / first + d is odd.
+struct BlindTerm { u64 seed[4]; u32 neg, pad; };                  // neg: 1 = the term is subtracted
+struct BlindVec { uint8_t *out; u32 term_first, term_count; };    // out: d * 32 bytes of device memory, 16-byte aligned
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(TPB) k_blind_combine(const BlindVec *__restrict__ vecs, const BlindTerm *__restrict__ terms, u64 first, u32 d) {
+    const u32 tf = vecs[blockIdx.y].term_first, nt = vecs[blockIdx.y].term_count;
+    const u64 blk = (first >> 1) + (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (2 * blk >= first + d) return;
+    const u64 dom[2] = ROFL_BLIND_DOM;
+    sc acc[2] = {sc_zero(), sc_zero()};
+    for (u32 t = 0; t < nt; t++) {
+        const BlindTerm *T = &terms[tf + t];
+        const u64 sw[4] = {T->seed[0], T->seed[1], T->seed[2], T->seed[3]};
+        const bool neg = T->neg != 0;
+        u64 st[25];
+        shake256_seeded_block(st, dom, sw, blk);
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            sc v = xof_block_scalar(st, h), nv = sc_neg(v);
+#pragma unroll
+            for (int i = 0; i < 8; i++) v.v[i] = neg ? nv.v[i] : v.v[i];
+            acc[h] = sc_add(acc[h], v);
+        }
+    }
+    sc *o = reinterpret_cast<sc *>(vecs[blockIdx.y].out);
+    if (2 * blk >= first) store_sc(&o[2 * blk - first], acc[0]);                  // (2 blk + 1 >= first always: blk >= first >> 1)
+    if (2 * blk + 1 < first + d) store_sc(&o[2 * blk + 1 - first], acc[1]);
+}
+#endif
+
 // ================================================================ K2: quantize + shift
 // conversion32.rs:11-18 f32_to_scalar, range_proof_vec/mod.rs:27-43.  status bits: 1 out-of-range, 2 NaN.
 #if ROFL_KG(4)

@@ -2282,6 +2282,64 @@ int rofl_scalar_add_vec(const uint8_t *a32, const uint8_t *b32, size_t d, int su
     }
     return ROFL_OK;
 }
+// Blinding vectors from seeds: out32[v][k] = sum_t sign_t * stream(seed_t)[first + k] mod l (k_blind_combine), every vector of the call in ONE
+// launch.  Covers pedersen_ops::rnd_scalar_vec (one +1 term), generate_cancelling_scalar_vec (the last vector = the negated others) and
+// pairwise masks (one term per peer).  Seeds are secrets: they are never put into an error text, and the lane's copies of the term list
+// (pinned host memory and device workspace) are overwritten with zeros before the call returns or unwinds.
+int rofl_blinding_vecs(size_t n_vec, const size_t *term_count, const rofl_blind_term_t *const *terms, size_t first, size_t d, uint8_t *const *out32) {
+    if (n_vec == 0) return ROFL_OK;
+    if (!term_count || !terms || !out32) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
+    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
+    if (first > ((size_t)1 << 63) - d) return fail(ROFL_BAD_PARAM, "first + d exceeds 2^63");
+    size_t total = 0;
+    for (size_t v = 0; v < n_vec; v++) {
+        if (d && !out32[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
+        if (term_count[v] && !terms[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
+        if (term_count[v] > ((size_t)1 << 22) || (total += term_count[v]) > ((size_t)1 << 22)) return fail(ROFL_BAD_PARAM, "more than 2^22 terms in one call");
+        for (size_t t = 0; t < term_count[v]; t++)
+            if (terms[v][t].sign != 1 && terms[v][t].sign != -1) return fail(ROFL_BAD_PARAM, "a term's sign is +1 or -1");
+    }
+    if (d == 0) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        std::vector<char> on_dev(n_vec); size_t n_host = 0;
+        for (size_t v = 0; v < n_vec; v++) {
+            on_dev[v] = is_device_ptr(out32[v]);
+            if (on_dev[v] && ((uintptr_t)out32[v] & 15)) return fail(ROFL_BAD_PARAM, "a device output must be 16-byte aligned");
+            if (!on_dev[v]) n_host++;
+        }
+        // a device output is written in place; a host output goes through the lane's workspace and the staging path
+        uint8_t *ws = n_host ? C.Cbytes.as<uint8_t>(n_host * d * 32) : nullptr;
+        const size_t bytes = n_vec * sizeof(BlindVec) + total * sizeof(BlindTerm);
+        uint8_t *h = C.h_misc.as<uint8_t>(bytes), *dv = C.tmp_in.as<uint8_t>(bytes);
+        struct Wipe { uint8_t *h, *dv; size_t n; hipStream_t s;
+                      ~Wipe() { (void)hipMemsetAsync(dv, 0, n, s); (void)hipStreamSynchronize(s); volatile uint8_t *p = h; for (size_t i = 0; i < n; i++) p[i] = 0; } } wipe{h, dv, bytes, C.stream};
+        BlindVec *hv = reinterpret_cast<BlindVec *>(h); BlindTerm *ht = reinterpret_cast<BlindTerm *>(h + n_vec * sizeof(BlindVec));
+        size_t at = 0, slot = 0;
+        for (size_t v = 0; v < n_vec; v++) {
+            hv[v].out = on_dev[v] ? out32[v] : ws + (slot++) * d * 32; hv[v].term_first = (u32)at; hv[v].term_count = (u32)term_count[v];
+            for (size_t t = 0; t < term_count[v]; t++, at++) { memcpy(ht[at].seed, terms[v][t].seed, 32); ht[at].neg = terms[v][t].sign < 0; ht[at].pad = 0; }
+        }
+        HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, C.stream));
+        const size_t nblk = ((first + d + 1) >> 1) - (first >> 1);
+        ROFL_LAUNCH(k_blind_combine, grid1(nblk, (u32)n_vec), dim3(TPB), 0, C.stream, reinterpret_cast<const BlindVec *>(dv),
+                    reinterpret_cast<const BlindTerm *>(dv + n_vec * sizeof(BlindVec)), (u64)first, (u32)d);
+        for (size_t v = 0; v < n_vec; v++) if (!on_dev[v]) C.down(out32[v], hv[v].out, d * 32, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
+// pedersen_ops::rnd_scalar_vec (pedersen_ops.rs:124-127) with the randomness an explicit input: one vector of one +1 term
+int rofl_rnd_scalar_vec(const uint8_t seed[32], size_t first, size_t d, uint8_t *out32) {
+    if (!seed) return fail(ROFL_BAD_PARAM, "bad parameter");
+    rofl_blind_term_t term; memcpy(term.seed, seed, 32); term.sign = 1;
+    const rofl_blind_term_t *tp = &term; const size_t one = 1; uint8_t *op = out32;
+    int rc = rofl_blinding_vecs(1, &one, &tp, first, d, &op);
+    volatile uint8_t *p = term.seed; for (int i = 0; i < 32; i++) p[i] = 0;
+    return rc;
+}
 // conversion32::f32_to_fp_vec / uint_to_f32_vec (conversion32.rs:41-54): Fix is unsigned, negative inputs saturate to 0
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out) {
     if (!valid_fp(fp_bits, fp_frac)) return fail(ROFL_BAD_PARAM, "bad parameter");
@@ -3200,6 +3258,11 @@ int rofl_dbg_host_nonce(const uint8_t seed[32], uint64_t idx, uint8_t out[32]) {
     const int h = (int)(idx & 1);
     sc lo, hi; for (int i = 0; i < 4; i++) { lo.v[2 * i] = (u32)st[8 * h + i]; lo.v[2 * i + 1] = (u32)(st[8 * h + i] >> 32); hi.v[2 * i] = (u32)st[8 * h + 4 + i]; hi.v[2 * i + 1] = (u32)(st[8 * h + 4 + i] >> 32); }
     sc_tobytes(out, sc_from_wide(lo, hi)); return 0;
+}
+int rofl_dbg_host_blind(const uint8_t seed[32], uint64_t idx, uint8_t out[32]) {
+    const u64 dom[2] = ROFL_BLIND_DOM;
+    u64 sd[4]; memcpy(sd, seed, 32); u64 st[25]; shake256_seeded_block(st, dom, sd, idx >> 1);
+    sc_tobytes(out, xof_block_scalar(st, (int)(idx & 1))); return 0;
 }
 
 }  // extern "C"

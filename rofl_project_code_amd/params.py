@@ -449,6 +449,15 @@ class EncParamsRangeCompressed(EncParamsRange):
         return cls(m["enc_values"], m["rand_proof"], m["range_proofs"], m["range_bits"], m["check_percentage"])
 
 
+def _rand_scalars(d, rand_scalars, rand_seed):
+    """the r2 of one client: handed in, or the blinding stream of `rand_seed` (generated on the GPU), or fresh host randomness"""
+    if rand_scalars is not None and rand_seed is not None:
+        raise ValueError("rand_scalars and rand_seed exclude each other")
+    if rand_scalars is not None:
+        return api._u8(rand_scalars)
+    return pedersen_ops.rnd_scalar_vec(d) if rand_seed is None else pedersen_ops.rnd_scalar_vec_seeded(d, rand_seed)
+
+
 class EncParamsL2:
     """params.rs:544-681: per-element SquareRandProofs, L-inf range proofs, one L2 sum range proof."""
     kind = WIRE_ENC_NORM
@@ -461,11 +470,12 @@ class EncParamsL2:
         self.prove_range, self.l2_prove_range = int(prove_range), int(l2_prove_range)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None):
+        # r2: rand_scalars, or the blinding stream of rand_seed (pedersen_ops.rnd_scalar_vec_seeded, on the GPU), or fresh host randomness
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
-        r2 = pedersen_ops.rnd_scalar_vec(x.size) if rand_scalars is None else api._u8(rand_scalars)
+        r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
         clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         # the square proofs take the range proof's commitments (params.rs:623-637); committing first (same points) lets the
@@ -485,7 +495,8 @@ class EncParamsL2:
         them are ONE rofl_create_rangeproof_batch call (one launch sequence, one set of host hops), their sum proofs ONE
         rofl_create_rangeproof_l2_batch and their square proofs ONE rofl_create_sigmaproof_vec_batch: three calls side by side on three
         lanes.  Every container is byte-identical to what encrypt() returns for that client with the same nonce seed; a client that fails
-        raises."""
+        raises.  (Seeded r2 for a batch: ONE pedersen_ops.blinding_vecs call over the clients' seeds, its rows handed in as rand_scalars --
+        the bytes of encrypt(rand_seed=...).)"""
         fp = api._fp(fp)
         n = len(clients)
         if n == 0:
@@ -628,11 +639,11 @@ class EncParamsL2Compressed(EncParamsL2):
         self.prove_range, self.l2_prove_range = int(prove_range), int(l2_prove_range)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None):
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
-        r2 = pedersen_ops.rnd_scalar_vec(x.size) if rand_scalars is None else api._u8(rand_scalars)
+        r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
         clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         enc_com = pedersen_ops.commit_vec(conversion32.f32_to_scalar_vec(clipped, fp=fp), bl)

@@ -507,16 +507,19 @@ public:
 };
 ShardWorkers &shard_workers() { static ShardWorkers s; return s; }
 
-// The devices a batch entry point spreads its clients over: rofl_set_option("devices", mask).  Empty = the calling thread's device.
+// The devices a call spreads its work over: rofl_set_option("devices", mask).  Empty = the calling thread's device.
 std::vector<int> batch_devices() {
     std::vector<int> v; long m = opts().devices.load();
     for (int i = 0; i < kMaxDevices && m; i++, m >>= 1) if (m & 1) v.push_back(i);
     return v;
 }
-// Clients round-robin over the listed devices, one internal thread per device (bound to it for the duration), each running the ordinary
-// single-device path on its share; verdicts / return codes land in the caller's arrays, in host memory -- in one process there is no
-// collective to run.  run(share, device_slot) is the per-device body; it returns the call-level return code of its share.
+// A call that is not dealt to several devices runs on the listed one: a one-client call when the mask names exactly one device, a batch
+// call (`first_of_many`) on the first of however many it names.  Otherwise the thread stays where it is.
+struct ListedDevice : DeviceBinding {
+    explicit ListedDevice(const std::vector<int> &devs, bool first_of_many = false) : DeviceBinding(devs.size() == 1 || (first_of_many && !devs.empty()) ? devs[0] : t_device) {}
+};
 // run(k) for k < nd, each on the worker of devs[k] (k = 0 on the calling thread), bound to its device; rcs[k] / errs[k] = what it returned.
+// Results land in the caller's arrays, in host memory -- in one process there is no collective to run.
 // The return value is non-zero only when a worker thread could not be started.
 template <class F> int run_on_devices(const std::vector<int> &devs, size_t nd, std::vector<int> &rcs, std::vector<std::string> &errs, F run) {
     rcs.assign(nd, ROFL_OK); errs.assign(nd, std::string());
@@ -534,14 +537,53 @@ template <class F> int run_on_devices(const std::vector<int> &devs, size_t nd, s
     for (auto &t : tickets) sw.wait(t);
     return ROFL_OK;
 }
-template <class F> int shard_over_devices(size_t n_clients, const std::vector<int> &devs, F run) {
-    const size_t nd = std::min(devs.size(), n_clients);
-    std::vector<std::vector<size_t>> share(nd);
-    for (size_t i = 0; i < n_clients; i++) share[i % nd].push_back(i);
-    std::vector<int> rcs; std::vector<std::string> errs;
-    if (int rc = run_on_devices(devs, nd, rcs, errs, [&](size_t k) -> int { return run(share[k]); })) return rc;
-    for (size_t k = 0; k < nd; k++) if (rcs[k]) return fail(rcs[k], errs[k]);
+// the first failing run or share in device order is the call's return code and rofl_last_error text
+int first_failure(const std::vector<int> &rcs, const std::vector<std::string> &errs) {
+    for (size_t k = 0; k < rcs.size(); k++) if (rcs[k]) return fail(rcs[k], errs[k]);
     return ROFL_OK;
+}
+
+// What the body of a batch entry sees of the call's clients: all of them, as the caller passed them (idx == nullptr: every array is handed
+// through and every result is written in place -- nothing is allocated, nothing is copied), or the share of one device.
+struct Share {
+    size_t n; const std::vector<size_t> *idx;      // idx: the members' positions in the caller's arrays
+    size_t size() const { return n; }
+    bool whole() const { return !idx; }
+    const size_t *positions() const { return idx ? idx->data() : nullptr; }
+    // a per-client array of the caller as the implementation reads it: the array itself, or the members' entries gathered (null entries for
+    // an array that is null or, `live` false, not read at this shape)
+    template <class T> struct In { const T *src; std::vector<T> own; const T *data() const { return own.empty() ? src : own.data(); } };
+    template <class T> In<T> view(const T *a, bool live = true) const {
+        In<T> v{a, {}};
+        if (idx) { v.own.resize(n); if (a && live) for (size_t j = 0; j < n; j++) v.own[j] = a[(*idx)[j]]; }
+        return v;
+    }
+    // per-member results, `row` elements each: the caller's array itself, or zeroed rows of the share's own that scatter() copies to the
+    // members' positions (a null array stays null)
+    template <class T> struct Out { T *dst; size_t row; std::vector<T> own; T *data() { return own.empty() ? dst : own.data(); } };
+    template <class T> Out<T> out(T *dst, size_t row = 1) const { return Out<T>{dst, row, std::vector<T>(idx && dst ? n * row : 0)}; }
+    template <class T, class Keep> void scatter(const Out<T> &o, Keep keep) const {
+        if (!o.own.empty()) for (size_t j = 0; j < n; j++) if (keep(j)) memcpy(o.dst + o.row * (*idx)[j], &o.own[o.row * j], o.row * sizeof(T));
+    }
+    template <class T> void scatter(const Out<T> &o) const { scatter(o, [](size_t) { return true; }); }
+};
+// THE policy of rofl_set_option("devices", mask) for a batch entry; body(share) is the entry's implementation call, written once.
+// No listed device, or fewer than two clients: one guarded call of the body on all clients, on the first listed device if there is one.
+// Otherwise the clients are dealt round-robin, client i to share i % nd, one persistent worker per device (share 0 on the calling thread),
+// each running the ordinary single-device path on its share; the first failing share in device order is the call's error.
+// `verdicts` (the verifiers' ok_out; nullptr for the creators, whose rc_out is not touched) is zeroed before the clients are dealt.
+template <class F> int over_devices(size_t n_clients, int *verdicts, F body) {
+    const std::vector<int> devs = batch_devices();
+    if (devs.empty() || n_clients < 2) return guarded([&]() -> int { ListedDevice bind(devs, true); return body(Share{n_clients, nullptr}); });
+    if (verdicts) for (size_t i = 0; i < n_clients; i++) verdicts[i] = 0;
+    return guarded([&]() -> int {
+        const size_t nd = std::min(devs.size(), n_clients);
+        std::vector<std::vector<size_t>> share(nd);
+        for (size_t i = 0; i < n_clients; i++) share[i % nd].push_back(i);
+        std::vector<int> rcs; std::vector<std::string> errs;
+        if (int rc = run_on_devices(devs, nd, rcs, errs, [&](size_t k) -> int { return body(Share{share[k].size(), &share[k]}); })) return rc;
+        return first_failure(rcs, errs);
+    });
 }
 
 // ONE client over several devices ("cfg 2/3 at > 1 GPU -> chunks over ranks").  The reference proves and verifies a client's
@@ -549,18 +591,32 @@ template <class F> int shard_over_devices(size_t n_clients, const std::vector<in
 // here device k takes the k-th contiguous run of the P chunks -- a run's commitments are one span of the caller's array, the cost of a
 // chunk does not depend on its data (padding chunks are proved like any other), so contiguous runs balance exactly like a round-robin deal.
 // No collective: proofs and commitments land in the caller's host arrays.  The bytes are those of the unsplit call (the nonce index space is
-// the client's).  Returns the geometry in *chunk_out / *P_out; 0 runs = the call is not splittable (one chunk, or one device).
-std::vector<std::pair<size_t, size_t>> chunk_runs(size_t P, size_t nd) {
-    std::vector<std::pair<size_t, size_t>> r;
-    nd = std::min(nd, P);
-    for (size_t k = 0; k < nd; k++) { size_t a = k * P / nd, b = (k + 1) * P / nd; if (b > a) r.emplace_back(a, b - a); }
+// the client's).
+// (first, count) of the contiguous runs that n units -- a range proof's chunks, a Sigma vector's elements -- are cut into for nd devices; no
+// run is shorter than min_len (1 for chunks; 2048 for elements: a shorter run is not worth a device)
+typedef std::vector<std::pair<size_t, size_t>> Runs;
+Runs split_runs(size_t n, size_t nd, size_t min_len) {
+    Runs r;
+    nd = std::max<size_t>(1, std::min(nd, n / min_len));
+    for (size_t k = 0; k < nd; k++) { size_t a = k * n / nd, b = (k + 1) * n / nd; if (b > a) r.emplace_back(a, b - a); }
     return r;
+}
+// The runs of ONE client's proofs verified on the listed devices, run(first, count, &ok) each, and the call's one verdict: a failing run is
+// the call's error (a malformed set is the call's FormatError, whichever run met it), otherwise the AND of the runs' verdicts.
+template <class F> int verify_runs(const std::vector<int> &devs, const Runs &runs, int *ok_out, F run) {
+    std::vector<int> rcs, oks(runs.size(), 0); std::vector<std::string> errs;
+    if (int rc = run_on_devices(devs, runs.size(), rcs, errs, [&](size_t k) -> int { return run(runs[k].first, runs[k].second, &oks[k]); })) return rc;
+    *ok_out = 0;
+    if (int rc = first_failure(rcs, errs)) return rc;
+    int ok = 1; for (int o : oks) ok &= o;
+    *ok_out = ok;
+    return ROFL_OK;
 }
 int create_split(const std::vector<int> &devs, const float *values, size_t d, const uint8_t *blind, size_t prove_range, size_t n_partition, unsigned fp_bits,
                  unsigned fp_frac, const rofl_nonce_t *nonce, uint8_t *proofs_out, size_t *plen_out, size_t *np_out, uint8_t *commits_out) {
     const size_t dp = next_pow2(d), nch = std::min(dp, n_partition), chunk = dp / nch, P = (dp + chunk - 1) / chunk;
     const size_t plen = 32 * (9 + 2 * (size_t)lg2u(prove_range * chunk));      // (every run reports the same; needed here to place the runs' proofs)
-    auto runs = chunk_runs(P, devs.size());
+    auto runs = split_runs(P, devs.size(), 1);
     std::vector<int> rcs, rc1(runs.size(), ROFL_OK); std::vector<std::string> errs;
     if (int rc = run_on_devices(devs, runs.size(), rcs, errs, [&](size_t k) -> int {
             LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
@@ -575,7 +631,7 @@ int create_split(const std::vector<int> &devs, const float *values, size_t d, co
     for (size_t k = 0; k < rcs.size(); k++) if (rcs[k] >= ROFL_HIP_ERROR || rcs[k] == ROFL_COMM_ERROR) return fail(rcs[k], errs[k]);
     if (any(rc1, ROFL_VALUE_OUT_OF_RANGE)) return fail(ROFL_VALUE_OUT_OF_RANGE, "ValueOutOfRangeError");
     if (any(rc1, ROFL_NON_FINITE)) return fail(ROFL_NON_FINITE, "non-finite value (the reference panics in fixed::saturating_from_float)");
-    for (size_t k = 0; k < rcs.size(); k++) if (rcs[k]) return fail(rcs[k], errs[k]);
+    if (int rc = first_failure(rcs, errs)) return rc;
     if (any(rc1, ROFL_NONCE_SHORT)) return fail(ROFL_NONCE_SHORT, "nonce stream too short");
     *plen_out = plen; *np_out = P;
     return ROFL_OK;
@@ -583,18 +639,10 @@ int create_split(const std::vector<int> &devs, const float *values, size_t d, co
 int verify_split(const std::vector<int> &devs, const uint8_t *proofs, size_t proof_len, size_t n_proofs, const uint8_t *commits, size_t d, size_t prove_range,
                  unsigned fp_bits, unsigned fp_frac, const uint8_t seed[32], int *ok_out) {
     const size_t chunk = next_pow2(d) / n_proofs;
-    auto runs = chunk_runs(n_proofs, devs.size());
-    std::vector<int> rcs, oks(runs.size(), 0); std::vector<std::string> errs;
-    if (int rc = run_on_devices(devs, runs.size(), rcs, errs, [&](size_t k) -> int {
-            LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-            const uint8_t *pp = proofs + runs[k].first * proof_len, *cc = commits + std::min(runs[k].first * chunk, d) * 32;
-            return verify_impl(C, 1, &pp, proof_len, n_proofs, &cc, d, prove_range, fp_bits, fp_frac, seed, &oks[k], true, nullptr, 32, runs[k].first, runs[k].second); }))
-        return rc;
-    *ok_out = 0;
-    for (size_t k = 0; k < rcs.size(); k++) if (rcs[k]) return fail(rcs[k], errs[k]);      // a malformed set is the call's FormatError, whichever run met it
-    int ok = 1; for (int o : oks) ok &= o;
-    *ok_out = ok;
-    return ROFL_OK;
+    return verify_runs(devs, split_runs(n_proofs, devs.size(), 1), ok_out, [&](size_t first, size_t count, int *ok) -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        const uint8_t *pp = proofs + first * proof_len, *cc = commits + std::min(first * chunk, d) * 32;
+        return verify_impl(C, 1, &pp, proof_len, n_proofs, &cc, d, prove_range, fp_bits, fp_frac, seed, ok, true, nullptr, 32, first, count); });
 }
 // can this (d, n_proofs) set be split?  Only the regular case: the proofs cover the padded vector exactly
 bool verify_splittable(size_t d, size_t n_proofs) { if (!d || n_proofs < 2) return false; size_t dp = next_pow2(d); return n_proofs <= dp && (dp / n_proofs) * n_proofs == dp; }
@@ -1000,7 +1048,7 @@ int rofl_create_rangeproof(const float *values, size_t d, const uint8_t *blindin
         if (devs.size() > 1 && values && blindings32 && nonce && proofs_out && commits_out && proof_len_out && n_proofs_out && d && n_partition && valid_fp(fp_bits, fp_frac) &&
             prove_range && prove_range <= fp_bits && rofl_rangeproof_chunks(d, n_partition) > 1)
             return create_split(devs, values, d, blindings32, prove_range, n_partition, fp_bits, fp_frac, nonce, proofs_out, proof_len_out, n_proofs_out, commits_out);
-        std::unique_ptr<DeviceBinding> bind; if (devs.size() == 1) bind.reset(new DeviceBinding(devs[0]));
+        ListedDevice bind(devs);
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
         int rc1 = ROFL_OK;
         int rc = create_impl(C, 1, &values, d, &blindings32, prove_range, n_partition, fp_bits, fp_frac, nonce, &proofs_out, proof_len_out, n_proofs_out, &commits_out, &rc1, true);
@@ -1025,22 +1073,16 @@ int rofl_create_rangeproof_batch(size_t n_clients, const float *const *values, s
                                  size_t *proof_len_out, size_t *n_proofs_out, uint8_t *const *commits_out, int *rc_out) {
     if (!values || !blindings32 || !proofs_out || !commits_out || !rc_out || !proof_len_out || !n_proofs_out || !nonces) return fail(ROFL_BAD_PARAM, "bad parameter");
     const bool single = false;      // per-client outcomes in rc_out, also for a batch of ONE (the return value is for errors of the whole call)
-    std::vector<int> devs = batch_devices();
-    if (devs.empty() || n_clients < 2)
-        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
-            LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-            return create_impl(C, n_clients, values, d, blindings32, prove_range, n_partition, fp_bits, fp_frac, nonces, proofs_out, proof_len_out, n_proofs_out, commits_out, rc_out, single); });
     std::mutex out_mu;
-    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
-        const size_t k = idx.size();
-        std::vector<const float *> v(k); std::vector<const uint8_t *> b(k); std::vector<rofl_nonce_t> nn(k); std::vector<uint8_t *> po(k), co(k); std::vector<int> rc(k, ROFL_OK);
-        for (size_t j = 0; j < k; j++) { v[j] = values[idx[j]]; b[j] = blindings32[idx[j]]; nn[j] = nonces[idx[j]]; po[j] = proofs_out[idx[j]]; co[j] = commits_out[idx[j]]; }
-        size_t plen = 0, np = 0;
+    return over_devices(n_clients, nullptr, [&](const Share &sh) -> int {
+        auto v = sh.view(values); auto b = sh.view(blindings32); auto nn = sh.view(nonces); auto po = sh.view(proofs_out); auto co = sh.view(commits_out); auto rc = sh.out(rc_out);
+        size_t plen = 0, np = 0;      // a share's own geometry: the caller's proof_len_out / n_proofs_out are written only by a share that succeeded (unlike the L2 creator's, set before dispatch)
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        int r = create_impl(C, k, v.data(), d, b.data(), prove_range, n_partition, fp_bits, fp_frac, nn.data(), po.data(), &plen, &np, co.data(), rc.data(), false);
-        for (size_t j = 0; j < k; j++) rc_out[idx[j]] = rc[j];
-        if (!r) { std::lock_guard<std::mutex> lk(out_mu); *proof_len_out = plen; *n_proofs_out = np; }
-        return r; }); });
+        int r = create_impl(C, sh.size(), v.data(), d, b.data(), prove_range, n_partition, fp_bits, fp_frac, nn.data(), po.data(), sh.whole() ? proof_len_out : &plen,
+                            sh.whole() ? n_proofs_out : &np, co.data(), rc.data(), single);
+        sh.scatter(rc);
+        if (!sh.whole() && !r) { std::lock_guard<std::mutex> lk(out_mu); *proof_len_out = plen; *n_proofs_out = np; }
+        return r; });
 }
 int rofl_verify_rangeproof(const uint8_t *proofs, size_t proof_len, size_t n_proofs, const uint8_t *commits32, size_t d, size_t prove_range,
                            unsigned fp_bits, unsigned fp_frac, const uint8_t verifier_seed[32], int *ok_out) {
@@ -1048,7 +1090,7 @@ int rofl_verify_rangeproof(const uint8_t *proofs, size_t proof_len, size_t n_pro
         std::vector<int> devs = batch_devices();
         if (devs.size() > 1 && proofs && commits32 && ok_out && verifier_seed && verify_splittable(d, n_proofs))      // the client's proofs over the listed devices (verify_split)
             return verify_split(devs, proofs, proof_len, n_proofs, commits32, d, prove_range, fp_bits, fp_frac, verifier_seed, ok_out);
-        std::unique_ptr<DeviceBinding> bind; if (devs.size() == 1) bind.reset(new DeviceBinding(devs[0]));
+        ListedDevice bind(devs);
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
         return verify_impl(C, 1, &proofs, proof_len, n_proofs, &commits32, d, prove_range, fp_bits, fp_frac, verifier_seed, ok_out, true); });
 }
@@ -1069,20 +1111,13 @@ int rofl_verify_rangeproof_batch_strided(size_t n_clients, const uint8_t *const 
                                          size_t d, size_t prove_range, unsigned fp_bits, unsigned fp_frac, const uint8_t verifier_seed[32], int *ok_out) {
     if (!proofs || !commits32 || !ok_out || !verifier_seed || commit_stride < 32) return fail(ROFL_BAD_PARAM, "bad parameter");
     const bool single = false;      // a batch has per-member verdicts, also a batch of ONE: a malformed member gets ok = 0, not the FormatError of rofl_verify_rangeproof (found by the long batch fuzz)
-    std::vector<int> devs = batch_devices();
-    if (devs.empty() || n_clients < 2)
-        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
-            LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-            return verify_impl(C, n_clients, proofs, proof_len, n_proofs, commits32, d, prove_range, fp_bits, fp_frac, verifier_seed, ok_out, single, nullptr, commit_stride); });
-    for (size_t i = 0; i < n_clients; i++) ok_out[i] = 0;
-    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
-        const size_t k = idx.size();
-        std::vector<const uint8_t *> p(k), c(k); std::vector<int> ok(k, 0);
-        for (size_t j = 0; j < k; j++) { p[j] = proofs[idx[j]]; c[j] = commits32[idx[j]]; }
+    return over_devices(n_clients, ok_out, [&](const Share &sh) -> int {
+        auto p = sh.view(proofs); auto c = sh.view(commits32); auto ok = sh.out(ok_out);
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        int r = verify_impl(C, k, p.data(), proof_len, n_proofs, c.data(), d, prove_range, fp_bits, fp_frac, verifier_seed, ok.data(), false, idx.data(), commit_stride);
-        for (size_t j = 0; j < k; j++) ok_out[idx[j]] = ok[j];
-        return r; }); });
+        // (only this verifier is told the members' positions in the whole batch)
+        int r = verify_impl(C, sh.size(), p.data(), proof_len, n_proofs, c.data(), d, prove_range, fp_bits, fp_frac, verifier_seed, ok.data(), single, sh.positions(), commit_stride);
+        sh.scatter(ok);
+        return r; });
 }
 int rofl_clip_f32(const float *in, size_t d, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *out) {
     if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
@@ -1218,17 +1253,12 @@ int rofl_create_rangeproof_l2_batch(size_t n_clients, const float *const *values
         if (!values[i] || !blindings32[i] || !proofs_out[i] || (nonces[i].mode == 0 && nonces[i].stream_scalars && !nonces[i].stream)) return fail(ROFL_BAD_PARAM, "bad parameter");
     *proof_len_out = 32 * (9 + 2 * (size_t)lg2u(prove_range));
     if (n_clients == 0) return ROFL_OK;
-    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
-    if (devs.empty() || n_clients < 2)
-        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
-            return l2_create_batch(n_clients, values, d, blindings32, prove_range, fp_bits, fp_frac, nonces, proofs_out, commits_out32, rc_out); });
-    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
-        const size_t k = idx.size();
-        std::vector<const float *> v(k); std::vector<const uint8_t *> b(k); std::vector<rofl_nonce_t> nn(k); std::vector<uint8_t *> po(k); std::vector<uint8_t> co(32 * k); std::vector<int> rc(k, ROFL_OK);
-        for (size_t j = 0; j < k; j++) { v[j] = values[idx[j]]; b[j] = blindings32[idx[j]]; nn[j] = nonces[idx[j]]; po[j] = proofs_out[idx[j]]; }
-        int rcode = l2_create_batch(k, v.data(), d, b.data(), prove_range, fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
-        for (size_t j = 0; j < k; j++) { rc_out[idx[j]] = rc[j]; if (rc[j] == ROFL_OK && rcode == ROFL_OK) memcpy(commits_out32 + 32 * idx[j], &co[32 * j], 32); }
-        return rcode; }); });
+    return over_devices(n_clients, nullptr, [&](const Share &sh) -> int {
+        auto v = sh.view(values); auto b = sh.view(blindings32); auto nn = sh.view(nonces); auto po = sh.view(proofs_out); auto co = sh.out(commits_out32, 32); auto rc = sh.out(rc_out);
+        int r = l2_create_batch(sh.size(), v.data(), d, b.data(), prove_range, fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
+        sh.scatter(rc);
+        sh.scatter(co, [&](size_t j) { return rc.data()[j] == ROFL_OK && r == ROFL_OK; });      // a commitment only for a member that succeeded in a share that succeeded (unlike the Sigma verifier's sums)
+        return r; });
 }
 int rofl_verify_rangeproof_l2(const uint8_t *proof, size_t proof_len, const uint8_t commit[32], size_t prove_range, unsigned fp_bits, unsigned fp_frac,
                               const uint8_t verifier_seed[32], int *ok_out) {
@@ -1969,19 +1999,14 @@ int round_verify_compressed_impl(Ctx &C, Round &R, const uint8_t *const *proofs,
 
 namespace {
 // ONE vector of per-element Sigma-proofs over several devices: contiguous runs of elements (rofl_set_option("devices", mask)), as the single-client
-// range-proof calls deal chunks.  Runs shorter than a few thousand elements are not worth a device.
-std::vector<std::pair<size_t, size_t>> elem_runs(size_t d, size_t nd) {
-    std::vector<std::pair<size_t, size_t>> r;
-    nd = std::max<size_t>(1, std::min(nd, d / 2048));
-    for (size_t k = 0; k < nd; k++) { size_t a = k * d / nd, b = (k + 1) * d / nd; if (b > a) r.emplace_back(a, b - a); }
-    return r;
-}
+// range-proof calls deal chunks.  Runs shorter than kSigmaRunMin elements are not worth a device.
+constexpr size_t kSigmaRunMin = 2048;
 int sigma_create_any(int kind, const float *values, size_t d, const uint8_t *r1, size_t d_r1, const uint8_t *r2, const uint8_t *existing, unsigned fp_bits, unsigned fp_frac,
                      const rofl_nonce_t *nonce, uint8_t *proofs_out, uint8_t *commits_out) {
     std::vector<int> devs = batch_devices();
-    auto runs = elem_runs(d, devs.size());
+    auto runs = split_runs(d, devs.size(), kSigmaRunMin);
     if (devs.size() < 2 || runs.size() < 2 || d != d_r1 || !values || !r1 || !nonce || !proofs_out || !commits_out || (kind != 0 && !r2)) {
-        std::unique_ptr<DeviceBinding> bind; if (devs.size() == 1) bind.reset(new DeviceBinding(devs[0]));
+        ListedDevice bind(devs);
         return sigma_create(kind, values, d, r1, d_r1, r2, existing, fp_bits, fp_frac, nonce, proofs_out, commits_out);
     }
     const bool has_sq = kind != 0;
@@ -1996,28 +2021,20 @@ int sigma_create_any(int kind, const float *values, size_t d, const uint8_t *r1,
     // elements the call reports NON_FINITE first, sigma_create)
     for (size_t k = 0; k < rcs.size(); k++) if (rcs[k] >= ROFL_HIP_ERROR || rcs[k] == ROFL_BAD_PARAM || rcs[k] == ROFL_NONCE_SHORT) return fail(rcs[k], errs[k]);
     for (size_t k = 0; k < rcs.size(); k++) if (rcs[k] == ROFL_NON_FINITE) return fail(rcs[k], errs[k]);
-    for (size_t k = 0; k < rcs.size(); k++) if (rcs[k]) return fail(rcs[k], errs[k]);
-    return ROFL_OK;
+    return first_failure(rcs, errs);
 }
 int sigma_verify_any(int kind, const uint8_t *proofs, const uint8_t *commits, size_t d, int *ok_out) {
     std::vector<int> devs = batch_devices();
-    auto runs = elem_runs(d, devs.size());
+    auto runs = split_runs(d, devs.size(), kSigmaRunMin);
     if (devs.size() < 2 || runs.size() < 2 || !proofs || !commits || !ok_out) {
-        std::unique_ptr<DeviceBinding> bind; if (devs.size() == 1) bind.reset(new DeviceBinding(devs[0]));
+        ListedDevice bind(devs);
         return sigma_verify_batch(kind, 1, &proofs, &commits, d, ok_out, nullptr, true);
     }
     const bool has_sq = kind != 0;
     const size_t npts = 1 + (kind != 2) + (has_sq ? 1 : 0), nn = has_sq ? 3 : 2, clen = 32 * npts, plen = 32 * (npts + nn);
-    std::vector<int> rcs, oks(runs.size(), 0); std::vector<std::string> errs;
-    if (int rc = run_on_devices(devs, runs.size(), rcs, errs, [&](size_t k) -> int {
-            const uint8_t *pp = proofs + runs[k].first * plen, *cc = commits + runs[k].first * clen;
-            return sigma_verify_batch(kind, 1, &pp, &cc, runs[k].second, &oks[k], nullptr, true); }))      // every run is its own random linear combination
-        return rc;
-    *ok_out = 0;
-    for (size_t k = 0; k < rcs.size(); k++) if (rcs[k]) return fail(rcs[k], errs[k]);      // a malformed vector is the call's FormatError, whichever run met it
-    int ok = 1; for (int o : oks) ok &= o;
-    *ok_out = ok;
-    return ROFL_OK;
+    return verify_runs(devs, runs, ok_out, [&](size_t first, size_t count, int *ok) -> int {      // every run is its own random linear combination
+        const uint8_t *pp = proofs + first * plen, *cc = commits + first * clen;
+        return sigma_verify_batch(kind, 1, &pp, &cc, count, ok, nullptr, true); });
 }
 }  // namespace
 int rofl_create_sigmaproof_vec_range(int kind, const float *values, size_t d, const uint8_t *r1_32, const uint8_t *r2_32, const uint8_t *existing32, unsigned fp_bits, unsigned fp_frac,
@@ -2062,18 +2079,11 @@ int rofl_verify_compressed_randproof_batch_strided(size_t n_clients, const uint8
     if (!ok_out || (n_clients && (!proofs || !pairs)) || d >= 900000 || n_clients > kMaxBatchMembers / 2) return fail(ROFL_BAD_PARAM, "bad parameter");
     for (size_t i = 0; i < n_clients; i++) if (!proofs[i] || (d && !pairs[i])) return fail(ROFL_BAD_PARAM, "bad parameter");
     if (n_clients == 0) return ROFL_OK;
-    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
-    if (devs.empty() || n_clients < 2)
-        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
-            return compressed_verify_batch(n_clients, proofs, pairs, d, ok_out, false, stride); });
-    for (size_t i = 0; i < n_clients; i++) ok_out[i] = 0;
-    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
-        const size_t k = idx.size();
-        std::vector<const uint8_t *> p(k), c(k); std::vector<int> ok(k, 0);
-        for (size_t j = 0; j < k; j++) { p[j] = proofs[idx[j]]; c[j] = pairs[idx[j]]; }
-        int r = compressed_verify_batch(k, p.data(), c.data(), d, ok.data(), false, stride);
-        for (size_t j = 0; j < k; j++) ok_out[idx[j]] = ok[j];
-        return r; }); });
+    return over_devices(n_clients, ok_out, [&](const Share &sh) -> int {
+        auto p = sh.view(proofs); auto c = sh.view(pairs); auto ok = sh.out(ok_out);
+        int r = compressed_verify_batch(sh.size(), p.data(), c.data(), d, ok.data(), false, stride);
+        sh.scatter(ok);
+        return r; });
 }
 int rofl_create_compressed_randproof_batch(size_t n_clients, const float *const *values, size_t d, const uint8_t *const *r32, const uint8_t *const *existing32,
                                            unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonces, uint8_t *const *proofs_out, uint8_t *const *pairs_out, int *rc_out) {
@@ -2083,18 +2093,13 @@ int rofl_create_compressed_randproof_batch(size_t n_clients, const float *const 
     if (!nonces || !proofs_out || !rc_out || (d && (!values || !r32 || !pairs_out))) return fail(ROFL_BAD_PARAM, "bad parameter");
     for (size_t i = 0; i < n_clients; i++)
         if (!proofs_out[i] || (nonces[i].mode == 0 && nonces[i].stream_scalars && !nonces[i].stream) || (d && (!values[i] || !r32[i] || !pairs_out[i]))) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
-    if (devs.empty() || n_clients < 2)
-        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
-            return compressed_create_batch(n_clients, values, d, r32, existing32, fp_bits, fp_frac, nonces, proofs_out, pairs_out, rc_out); });
-    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
-        const size_t k = idx.size();
-        std::vector<const float *> v(k); std::vector<const uint8_t *> r(k), e(k, nullptr); std::vector<rofl_nonce_t> nn(k); std::vector<uint8_t *> po(k), co(k); std::vector<int> rc(k, ROFL_OK);
-        for (size_t j = 0; j < k; j++) { v[j] = d ? values[idx[j]] : nullptr; r[j] = d ? r32[idx[j]] : nullptr; if (existing32) e[j] = existing32[idx[j]]; nn[j] = nonces[idx[j]];
-                                         po[j] = proofs_out[idx[j]]; co[j] = d ? pairs_out[idx[j]] : nullptr; }
-        int rcode = compressed_create_batch(k, v.data(), d, r.data(), e.data(), fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
-        for (size_t j = 0; j < k; j++) rc_out[idx[j]] = rc[j];
-        return rcode; }); });
+    return over_devices(n_clients, nullptr, [&](const Share &sh) -> int {
+        // (at d == 0 the value, blinding and pair arrays may be null: a share hands null entries down)
+        auto v = sh.view(values, d != 0); auto r = sh.view(r32, d != 0); auto e = sh.view(existing32); auto nn = sh.view(nonces); auto po = sh.view(proofs_out); auto co = sh.view(pairs_out, d != 0);
+        auto rc = sh.out(rc_out);
+        int rcode = compressed_create_batch(sh.size(), v.data(), d, r.data(), e.data(), fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
+        sh.scatter(rc);
+        return rcode; });
 }
 int rofl_create_sigmaproof_vec_batch(int kind, size_t n_clients, const float *const *values, size_t d, const uint8_t *const *r1_32, const uint8_t *const *r2_32,
                                      const uint8_t *const *existing32, unsigned fp_bits, unsigned fp_frac, const rofl_nonce_t *nonces, uint8_t *const *proofs_out,
@@ -2106,19 +2111,13 @@ int rofl_create_sigmaproof_vec_batch(int kind, size_t n_clients, const float *co
     for (size_t i = 0; i < n_clients; i++)
         if ((nonces[i].mode == 0 && nonces[i].stream_scalars && !nonces[i].stream) || (d && (!values[i] || !r1_32[i] || (kind != 0 && !r2_32[i]) || !proofs_out[i] || !commits_out[i])))
             return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices
-    if (devs.empty() || n_clients < 2)
-        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
-            return sigma_create_batch(kind, n_clients, values, d, r1_32, r2_32, existing32, fp_bits, fp_frac, nonces, proofs_out, commits_out, rc_out); });
-    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
-        const size_t k = idx.size();
-        std::vector<const float *> v(k, nullptr); std::vector<const uint8_t *> a(k, nullptr), b(k, nullptr), e(k, nullptr); std::vector<rofl_nonce_t> nn(k); std::vector<uint8_t *> po(k, nullptr), co(k, nullptr);
-        std::vector<int> rc(k, ROFL_OK);
-        for (size_t j = 0; j < k; j++) { const size_t i = idx[j]; nn[j] = nonces[i]; if (existing32) e[j] = existing32[i];
-                                         if (d) { v[j] = values[i]; a[j] = r1_32[i]; if (kind != 0) b[j] = r2_32[i]; po[j] = proofs_out[i]; co[j] = commits_out[i]; } }
-        int rcode = sigma_create_batch(kind, k, v.data(), d, a.data(), b.data(), e.data(), fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
-        for (size_t j = 0; j < k; j++) rc_out[idx[j]] = rc[j];
-        return rcode; }); });
+    return over_devices(n_clients, nullptr, [&](const Share &sh) -> int {
+        // (at d == 0 every array but the nonces may be null, and r2 is not read by kind 0: a share hands null entries down)
+        auto v = sh.view(values, d != 0); auto a = sh.view(r1_32, d != 0); auto b = sh.view(r2_32, d != 0 && kind != 0); auto e = sh.view(existing32); auto nn = sh.view(nonces);
+        auto po = sh.view(proofs_out, d != 0); auto co = sh.view(commits_out, d != 0); auto rc = sh.out(rc_out);
+        int rcode = sigma_create_batch(kind, sh.size(), v.data(), d, a.data(), b.data(), e.data(), fp_bits, fp_frac, nn.data(), po.data(), co.data(), rc.data());
+        sh.scatter(rc);
+        return rcode; });
 }
 int rofl_create_randproof_vec(const float *values, size_t d, const uint8_t *r32, size_t d_r, const uint8_t *existing32, unsigned fp_bits, unsigned fp_frac,
                               const rofl_nonce_t *nonce, uint8_t *proofs_out, uint8_t *commits_out) {
@@ -2137,18 +2136,12 @@ int rofl_verify_squarerandproof_vec(const uint8_t *proofs, const uint8_t *commit
 namespace {
 int sigma_batch_entry(int kind, size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *commits, size_t d, int *ok_out, uint8_t *csq_sum_out32) {
     if (!ok_out || (n_clients && (!proofs || !commits))) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::vector<int> devs = batch_devices();      // rofl_set_option("devices", mask): the clients are dealt round-robin to the listed devices, as in the range-proof batch calls
-    if (devs.empty() || n_clients < 2)
-        return guarded([&]() -> int { std::unique_ptr<DeviceBinding> bind; if (!devs.empty()) bind.reset(new DeviceBinding(devs[0]));
-            return sigma_verify_batch(kind, n_clients, proofs, commits, d, ok_out, csq_sum_out32, false); });
-    for (size_t i = 0; i < n_clients; i++) ok_out[i] = 0;
-    return guarded([&]() -> int { return shard_over_devices(n_clients, devs, [&](const std::vector<size_t> &idx) -> int {
-        const size_t k = idx.size();
-        std::vector<const uint8_t *> p(k), c(k); std::vector<int> ok(k, 0); std::vector<uint8_t> sums(csq_sum_out32 ? 32 * k : 0);
-        for (size_t j = 0; j < k; j++) { p[j] = proofs[idx[j]]; c[j] = commits[idx[j]]; }
-        int r = sigma_verify_batch(kind, k, p.data(), c.data(), d, ok.data(), csq_sum_out32 ? sums.data() : nullptr, false);
-        for (size_t j = 0; j < k; j++) { ok_out[idx[j]] = ok[j]; if (csq_sum_out32) memcpy(csq_sum_out32 + 32 * idx[j], &sums[32 * j], 32); }
-        return r; }); });
+    return over_devices(n_clients, ok_out, [&](const Share &sh) -> int {
+        auto p = sh.view(proofs); auto c = sh.view(commits); auto ok = sh.out(ok_out); auto sums = sh.out(csq_sum_out32, 32);
+        int r = sigma_verify_batch(kind, sh.size(), p.data(), c.data(), d, ok.data(), sums.data(), false);
+        sh.scatter(ok);
+        sh.scatter(sums);      // every member's c_sq sum, whatever its verdict and the share's outcome (unlike the L2 creator's commitments)
+        return r; });
 }
 }  // namespace
 int rofl_verify_randproof_vec_batch(size_t n_clients, const uint8_t *const *proofs, const uint8_t *const *commits, size_t d, int *ok_out) {

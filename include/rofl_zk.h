@@ -371,6 +371,33 @@ int rofl_acc_export(uint64_t h, uint8_t *pairs_out);
  * logs are converted to f32 (conversion32.rs:24-39).  The same values and errors as rofl_discrete_log_vec + rofl_scalar_to_f32_vec over the
  * exported L, 11 for a log that is not found included. */
 int rofl_acc_extract(uint64_t h, size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac, float *out, int *ok_out);
+/* Extraction of a round that rejected somebody.  Blindings cancel over the whole round only: the sum over the accepted set A keeps the
+ * residual s[k] = sum_{i in A} r_i[k] mod l in every pair,
+ *   R_sum[k] = R_init + s[k] B        L_sum[k] = L_init + X[k] B + s[k] B~      ((L_init, R_init): identity for init 0, (B, B) for init 1),
+ * and rofl_acc_extract answers *ok_out = 0.  These two entries take the OPENING s of that residual, check it and extract X:
+ *   opening32 (rofl_acc_extract_opened): d x 32 bytes, scalar k at opening32 + 32 k, any 256-bit value (reduced mod l on the device); host
+ *     memory or device memory of the accumulator's device (see "Memory spaces"; a device opening is read in place and must be 16-byte
+ *     aligned, else 11);
+ *   terms (rofl_acc_extract_opened_terms): s = sum_t terms[t].sign * stream(terms[t].seed)[0 .. d) as rofl_blinding_vecs defines it, built in
+ *     the lane's scratch on the device (d < 2^28, else 11) -- the opening never exists on the host.  term_count = 0 is the zero opening.
+ *     The seeds never appear in rofl_last_error, and the library's copies of them are overwritten with zeros before the call returns.
+ * One launch (k_acc_open) checks R_sum[k] == R_init + s[k] B for EVERY k by Ristretto equality -- one exact equation per coordinate, no
+ * random weights, nothing for two errors to cancel against -- and encodes L_sum[k] - s[k] B~.
+ *   every equation holds: *ok_out = 1, *first_bad_out = (size_t)-1, and out[k] is what rofl_acc_extract writes for an accumulator that holds
+ *     (L_sum - s B~, R_init), with the same errors (11 for a log that is not found).  An all-zero opening gives rofl_acc_extract's answer.
+ *   some equation fails: returns 0 with *ok_out = 0 and *first_bad_out = the smallest failing k; out is not written.  A wrong opening is
+ *     detected; it cannot shift the aggregate.
+ * The accumulator is only read, in every outcome: rofl_acc_export before and after returns the same bytes.  first_bad_out may be NULL.
+ * Returns 11 before the device is touched for what rofl_acc_extract refuses, a null opening32, a null terms with term_count > 0, a sign
+ * other than +1 / -1 and more than 2^22 terms.
+ * What the opening costs: s is minus the summed blinding of the clients left out, so whoever holds it can open the sum of THEIR updates
+ * (with one client left out: that client's update).  See DESIGN section 7, "a round that rejects". */
+int rofl_acc_extract_opened(uint64_t h, const uint8_t *opening32 /* d x 32, host or device */,
+                            size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac,
+                            float *out, int *ok_out, size_t *first_bad_out /* may be NULL */);
+int rofl_acc_extract_opened_terms(uint64_t h, size_t term_count, const rofl_blind_term_t *terms,
+                                  size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac,
+                                  float *out, int *ok_out, size_t *first_bad_out);
 int rofl_acc_reset(uint64_t h);      /* back to the initial state of its init */
 int rofl_acc_destroy(uint64_t h);    /* frees the device memory; the handle is invalid afterwards (after a HIP error only destroy accepts it again) */
 
@@ -478,8 +505,8 @@ int rofl_comm_info(int *rank_out, int *world_out, int *rccl_version_out, char *l
 int rofl_comm_destroy(void);
 
 /* Memory spaces.  The per-element INPUT arrays of rofl_create_rangeproof (values, blindings), rofl_verify_rangeproof(_batch)
- * (proofs, commitments) and of the per-element Sigma-proof entry points (values, randomness, existing commitments, proofs,
- * commitments) may live in host memory or in device memory of the library's device (HIP unified addressing): a caller that
+ * (proofs, commitments), of the per-element Sigma-proof entry points (values, randomness, existing commitments, proofs,
+ * commitments) and the opening32 of rofl_acc_extract_opened (16-byte aligned on the device) may live in host memory or in device memory of the library's device (HIP unified addressing): a caller that
  * already holds the update on the GPU passes device pointers and nothing crosses PCIe on the way in.  Outputs are written to
  * host memory, with one exception: the out32[v] of rofl_blinding_vecs / out32 of rofl_rnd_scalar_vec may be device memory of the
  * library's device (16-byte aligned), which the kernel then writes in place -- blindings generated there can be handed to the create

@@ -79,6 +79,12 @@ extern "C" {
     pub fn rofl_acc_export(h: u64, pairs_out: *mut u8) -> c_int;
     pub fn rofl_acc_extract(h: u64, table_size: usize, bsgs_bits: c_uint, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float,
         ok_out: *mut c_int) -> c_int;
+    /// extraction after rejections: the opening s of the accepted set's residual blinding (d x 32 bytes, host or device; or the signed
+    /// seeds it is the sum of) is checked against every R (ok_out = 0, first_bad_out = the smallest failing index) and stripped from L
+    pub fn rofl_acc_extract_opened(h: u64, opening32: *const u8, table_size: usize, bsgs_bits: c_uint, fp_bits: c_uint, fp_frac: c_uint,
+        out: *mut c_float, ok_out: *mut c_int, first_bad_out: *mut usize) -> c_int;
+    pub fn rofl_acc_extract_opened_terms(h: u64, term_count: usize, terms: *const RoflBlindTerm, table_size: usize, bsgs_bits: c_uint,
+        fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float, ok_out: *mut c_int, first_bad_out: *mut usize) -> c_int;
     pub fn rofl_acc_reset(h: u64) -> c_int;
     pub fn rofl_acc_destroy(h: u64) -> c_int;
     /// a round resident on the device (server.rs:474-521, 656-714): records ingested once (one upload, one decode per point), both

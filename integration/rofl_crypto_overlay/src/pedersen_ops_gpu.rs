@@ -2,7 +2,8 @@
 //! helpers of that file -- add_scalar_vec, zero_*_vec -- and its rnd_scalar_vec / generate_cancelling_scalar_vec, which draw from
 //! thread_rng, stay as they are).  The *_seeded functions and pairwise_blinding_vec at the end are additions: blinding vectors
 //! expanded on the device from 32-byte seeds (rofl_blinding_vecs), for hosts that want :110-127 reproducible, or cancelling
-//! blindings without the dealer of :110-122.
+//! blindings without the dealer of :110-122.  acc_extract_opened(_terms) extract the aggregate of a device accumulator (rofl_acc_*) whose
+//! round rejected somebody, from the opening of the accepted clients' residual blinding.
 use curve25519_dalek_ng::ristretto::RistrettoPoint;
 use curve25519_dalek_ng::scalar::Scalar;
 
@@ -96,4 +97,24 @@ pub fn pairwise_blinding_vec(index: usize, peers: &[(usize, [u8; 32])], d: usize
         RoflBlindTerm { seed: *s, sign: if index < *j { 1 } else { -1 } }
     }).collect();
     blinding_vecs(&[terms], 0, d).pop().unwrap()
+}
+
+/// Extraction after rejections (rofl_acc_extract_opened): `opening` = the sum of the accepted clients' blinding vectors, checked against
+/// every R of accumulator `h` and stripped from every L.  Ok(values), or Err(k) with the smallest coordinate whose R equation fails (the
+/// accumulator is unchanged either way).  `d` is the accumulator's length.
+pub fn acc_extract_opened(h: u64, d: usize, opening: &Vec<Scalar>, table_size: usize, fp_bits: u32, fp_frac: u32) -> Result<Vec<f32>, usize> {
+    assert!(opening.len() == d);
+    let s = scalars_to_bytes(opening);
+    let (mut out, mut ok, mut bad) = (vec![0f32; d], 0, usize::MAX);
+    let rc = unsafe { rofl_acc_extract_opened(h, s.as_ptr(), table_size, BSGS_N_BITS as u32, fp_bits, fp_frac, out.as_mut_ptr(), &mut ok, &mut bad) };
+    assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
+    if ok != 0 { Ok(out) } else { Err(bad) }
+}
+/// The same with the opening given as the signed seeds it is the sum of (pairwise masks: one term per accepted-rejected pair; a dealer's
+/// cancelling vectors: the accepted vectors' seeds): it is expanded on the device and never exists on the host.
+pub fn acc_extract_opened_terms(h: u64, d: usize, terms: &[RoflBlindTerm], table_size: usize, fp_bits: u32, fp_frac: u32) -> Result<Vec<f32>, usize> {
+    let (mut out, mut ok, mut bad) = (vec![0f32; d], 0, usize::MAX);
+    let rc = unsafe { rofl_acc_extract_opened_terms(h, terms.len(), terms.as_ptr(), table_size, BSGS_N_BITS as u32, fp_bits, fp_frac, out.as_mut_ptr(), &mut ok, &mut bad) };
+    assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
+    if ok != 0 { Ok(out) } else { Err(bad) }
 }

@@ -1084,6 +1084,38 @@ class pedersen_ops:
         """pairwise_blinding_vec for a process that hosts several clients, clients = [(index, peers), ...]: ONE call -> uint8[n, d, 32]"""
         return pedersen_ops.blinding_vecs([pedersen_ops._pairwise_terms(i, peers) for i, peers in clients], d)
 
+    # ---- a round that rejects: the terms of the accepted set's residual blinding (accumulator.extract_opened_terms) ----
+    @staticmethod
+    def pairwise_residual_terms(accepted, rejected, seeds):
+        """Pairwise masks (pairwise_blinding_vec) after rejections: the masks between two accepted clients cancel in the accepted clients'
+        sum, the masks between an accepted i and a rejected j stay -- one term (seeds[(min(i, j), max(i, j))], +1 if i < j else -1) per
+        such pair, the sign client i gave the stream.  seeds[(i, j)], i < j, is the seed clients i and j share.  A missing seed raises
+        KeyError naming the pair, an index in both sets ValueError."""
+        accepted, rejected = [int(i) for i in accepted], [int(j) for j in rejected]
+        both = set(accepted) & set(rejected)
+        if both:
+            raise ValueError("client %d is both accepted and rejected" % min(both))
+        terms = []
+        for i in accepted:
+            for j in rejected:
+                pair = (i, j) if i < j else (j, i)
+                if pair not in seeds:
+                    raise KeyError("no shared seed of the pair %r" % (pair,))
+                terms.append((seeds[pair], 1 if i < j else -1))
+        return terms
+
+    @staticmethod
+    def cancelling_residual_terms(n_vec, seed, accept):
+        """generate_cancelling_scalar_vec_seeded after rejections, accept[i] = vector i is in the sum: an accepted i < n_vec - 1 is
+        +stream(seed_i), an accepted last vector -stream(seed_i) for every i < n_vec - 1; a stream taken with both signs is gone.  All
+        accepted -> []."""
+        n_vec = int(n_vec)
+        accept = [bool(a) for a in accept]
+        if n_vec < 1 or len(accept) != n_vec:
+            raise ValueError("one verdict per vector")
+        coef = [(1 if accept[i] else 0) - (1 if accept[-1] else 0) for i in range(n_vec - 1)]
+        return [(pedersen_ops.cancelling_vec_seed(seed, i), c) for i, c in enumerate(coef) if c]
+
     @staticmethod
     def pairwise_round_seed(shared_secret, round_no):
         """SHA3-256("rofl-zk/blind/v1/round" || shared_secret || u64le(round_no)): the seed two clients use in round `round_no`.  A seed
@@ -1157,6 +1189,46 @@ class accumulator:
         ok = ctypes.c_int()
         _check(lib().rofl_acc_extract(ctypes.c_uint64(h), _sz(table_size), int(bsgs_bits), *fp, _ptr(out), ctypes.byref(ok)))
         return out if ok.value else None
+
+    @staticmethod
+    def extract_opened(h, d, opening, table_size, bsgs_bits, fp):
+        """rofl_acc_extract_opened: `opening` = the d scalars s of the sum's residual blinding, a uint8[d, 32] numpy array or a contiguous
+        torch uint8 tensor of d * 32 bytes on the accumulator's GPU (read in place).  -> (values, None) when every R equation holds, else
+        (None, first_bad) with the smallest failing index; the accumulator is unchanged either way"""
+        if _is_dev(opening):
+            op, n = _dev_arg(opening, 1, 32)
+        else:
+            opening = _u8(opening)
+            op, n = _ptr(opening), opening.size // 32
+        if n != d:
+            raise ValueError("the opening holds one 32-byte scalar per coordinate")
+        out = np.zeros(d, dtype=np.float32)
+        ok, bad = ctypes.c_int(), _sz()
+        _check(lib().rofl_acc_extract_opened(ctypes.c_uint64(h), op, _sz(table_size), int(bsgs_bits), *fp, _ptr(out), ctypes.byref(ok), ctypes.byref(bad)))
+        return (out, None) if ok.value else (None, bad.value)
+
+    @staticmethod
+    def extract_opened_terms(h, d, terms, table_size, bsgs_bits, fp):
+        """rofl_acc_extract_opened_terms: the opening as its terms [(seed32, sign), ...] (pedersen_ops.pairwise_residual_terms /
+        cancelling_residual_terms), summed on the device as blinding_vecs sums them -- it never exists on the host.  Returns as extract_opened."""
+        terms = list(terms)
+        arr = (_BlindTerm * max(len(terms), 1))()
+        out = np.zeros(d, dtype=np.float32)
+        ok, bad = ctypes.c_int(), _sz()
+        try:
+            for t, (seed, sign) in enumerate(terms):
+                seed = bytes(seed)
+                if len(seed) != 32:
+                    raise ValueError("a seed is 32 bytes")
+                if sign not in (1, -1):
+                    raise ValueError("a term's sign is +1 or -1")
+                ctypes.memmove(arr[t].seed, seed, 32)
+                arr[t].sign = int(sign)
+            _check(lib().rofl_acc_extract_opened_terms(ctypes.c_uint64(h), _sz(len(terms)), arr, _sz(table_size), int(bsgs_bits), *fp, _ptr(out),
+                                                       ctypes.byref(ok), ctypes.byref(bad)))
+        finally:
+            ctypes.memset(arr, 0, ctypes.sizeof(arr))
+        return (out, None) if ok.value else (None, bad.value)
 
     @staticmethod
     def reset(h):

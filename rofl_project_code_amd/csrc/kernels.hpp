@@ -2648,6 +2648,25 @@ __global__ void __launch_bounds__(TPB) k_acc_finish(u32 d, int mode, const ge *s
     gd_ristretto_encode(out + (size_t)32 * t, load_gd(&sum[2 * (size_t)t]));
 }
 #endif
+// Extraction of a sum whose blindings did NOT cancel, with the opening s[k] = sum of the summed clients' r[k] handed in (d raw 32-byte
+// scalars, any 256-bit value: reduced here): R_sum[k] = R_init + s[k] B and L_sum[k] = L_init + X[k] B + s[k] B~.  ONE THREAD PER (pair, L or
+// R), blockIdx.y = which, as k_eg_pairs_batch splits a pair: a block runs one formula and the pair's two 32-addition chains run side by side.
+// R half: Ristretto equality of s[k] B + init with sum[2k + 1] (the two cross products of k_acc_finish: either side may be any representative
+// of its coset); a failure ORs 1 into flag[0] and takes the minimum of k into flag[1] (the host presets it to 0xffffffff).  L half: the
+// encoding of sum[2k] - s[k] B~ into out[k] (d x 32, the input of k_bsgs_solve).  The sum itself is only read.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(TPB) k_acc_open(u32 d, const ge *sum, const sc *opening, ge init, const niels *tabB, const niels *tabBb, uint8_t *out, u32 *flag) {
+    const u32 k = blockIdx.x * blockDim.x + threadIdx.x, which = blockIdx.y;
+    if (k >= d) return;
+    const sc s = load_sc_reduced(&opening[k]);
+    if (which) {
+        gd P = gd_add(sg_fixed_mul8(tabB, s), gd_unpack(init)), R = load_gd(&sum[2 * (size_t)k + 1]);
+        if (!(fd_eq(fd_mul(R.X, P.Y), fd_mul(R.Y, P.X)) || fd_eq(fd_mul(R.Y, P.Y), fd_mul(R.X, P.X)))) { atomicOr(flag, 1u); atomicMin(flag + 1, k); }
+        return;
+    }
+    gd_ristretto_encode(out + (size_t)32 * k, gd_add(load_gd(&sum[2 * (size_t)k]), gd_neg(sg_fixed_mul8(tabBb, s))));
+}
+#endif
 
 // ================================================================ one round, decoded once (rofl_round_*)
 // A round keeps the decoded points of its clients' records in HBM in the layout the batched Sigma-proof check reads:

@@ -957,6 +957,89 @@ template <class T, class M, class F> int destroy_handle(Registry<T> &reg, uint64
 }
 template <class T> void dev_free(T *&p) { if (p) HIPCHK(hipFree(p)); p = nullptr; }
 const auto no_check = [](auto &) { return ROFL_OK; };
+// ---- the driver of k_blind_combine, shared by rofl_blinding_vecs and rofl_acc_extract_opened_terms ----
+// one term list of a call, checked before the device is touched; *total: the terms of the call so far
+int blind_terms_check(size_t term_count, const rofl_blind_term_t *terms, size_t *total) {
+    if (term_count && !terms) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (term_count > ((size_t)1 << 22) || (*total += term_count) > ((size_t)1 << 22)) return fail(ROFL_BAD_PARAM, "more than 2^22 terms in one call");
+    for (size_t t = 0; t < term_count; t++)
+        if (terms[t].sign != 1 && terms[t].sign != -1) return fail(ROFL_BAD_PARAM, "a term's sign is +1 or -1");
+    return ROFL_OK;
+}
+// the lane's copies of a call's term list (pinned host memory, device workspace): overwritten with zeros when the call returns or unwinds
+struct BlindWipe { uint8_t *h = nullptr, *dv = nullptr; size_t n = 0; hipStream_t s = nullptr;
+                   ~BlindWipe() { if (!n) return; (void)hipMemsetAsync(dv, 0, n, s); (void)hipStreamSynchronize(s); volatile uint8_t *p = h; for (size_t i = 0; i < n; i++) p[i] = 0; } };
+// vector v = sum of its terms' streams [first, first + d) into dst[v] (device memory, 16-byte aligned), every vector in ONE launch on the
+// lane's stream; the term list is staged in C.h_misc and in `term_buf`, which the caller leaves alone until `wipe` has run
+void blind_combine_launch(Ctx &C, DevBuf &term_buf, BlindWipe &wipe, size_t n_vec, const size_t *term_count, const rofl_blind_term_t *const *terms, size_t total,
+                          size_t first, size_t d, uint8_t *const *dst) {
+    const size_t bytes = n_vec * sizeof(BlindVec) + total * sizeof(BlindTerm);
+    uint8_t *h = C.h_misc.as<uint8_t>(bytes), *dv = term_buf.as<uint8_t>(bytes);
+    wipe.h = h; wipe.dv = dv; wipe.n = bytes; wipe.s = C.stream;
+    BlindVec *hv = reinterpret_cast<BlindVec *>(h); BlindTerm *ht = reinterpret_cast<BlindTerm *>(h + n_vec * sizeof(BlindVec));
+    size_t at = 0;
+    for (size_t v = 0; v < n_vec; v++) {
+        hv[v].out = dst[v]; hv[v].term_first = (u32)at; hv[v].term_count = (u32)term_count[v];
+        for (size_t t = 0; t < term_count[v]; t++, at++) { memcpy(ht[at].seed, terms[v][t].seed, 32); ht[at].neg = terms[v][t].sign < 0; ht[at].pad = 0; }
+    }
+    HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, C.stream));
+    const size_t nblk = ((first + d + 1) >> 1) - (first >> 1);
+    ROFL_LAUNCH(k_blind_combine, grid1(nblk, (u32)n_vec), dim3(TPB), 0, C.stream, reinterpret_cast<const BlindVec *>(dv),
+                reinterpret_cast<const BlindTerm *>(dv + n_vec * sizeof(BlindVec)), (u64)first, (u32)d);
+}
+// The opening of a sum's residual blinding, for the two rofl_acc_extract_opened entries: d raw scalars in caller memory (host or device),
+// or the term list they are built from on the device.  rofl_acc_extract hands none in.
+struct AccOpening { const uint8_t *bytes; size_t term_count; const rofl_blind_term_t *terms; };
+// What the extraction entries share -- the primary lane, the finishing launch, the verdict, BSGS, the download and the conversion; they
+// differ in the finishing launch only: k_acc_finish (R == the initial R, L encoded as it is) or, with an opening, k_acc_open (R == initial R
+// + s B, L - s B~ encoded).  The sum is read, never written.
+int acc_extract(uint64_t h, const AccOpening *op, size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac, float *out, int *ok_out, size_t *first_bad_out) {
+    if (!out || !ok_out || table_size == 0 || table_size >= (1u << 30) || !(bsgs_bits == 8 || bsgs_bits == 16 || bsgs_bits == 32) || !valid_fp(fp_bits, fp_frac))
+        return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::vector<uint8_t> hv;      // (outlives the lane: its release delivers the staged scalars here)
+    return with_acc(h, no_check, [&](Acc &A) -> int {
+        LaneLock lane_lock = acquire_lane(true); Ctx &C = *lane_lock.c;      // the primary lane: the baby-step tables rofl_discrete_log_vec caches
+        C.init();
+        const size_t d = A.d;
+        if (op && !op->bytes && d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");      // (as rofl_blinding_vecs)
+        uint8_t *enc = C.tmp_in.as<uint8_t>(d * 32), *dout = C.Cbytes.as<uint8_t>(d * 32);
+        u32 *status = C.status.as<u32>(4);      // [0] BSGS, [1] some R equation fails, [2] the smallest index of one
+        HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
+        const ge b = acc_init_point(A.init);
+        BlindWipe wipe;
+        if (!op) ROFL_LAUNCH(k_acc_finish, grid1(d), dim3(TPB), 0, C.stream, (u32)d, 0, (const ge *)A.sum, b.X, b.Y, enc, status + 1);
+        else {
+            const uint8_t *s = op->bytes;
+            if (!s || !is_device_ptr(s)) {      // a device opening is read in place; a host opening is uploaded, a term list expanded, into the lane's scratch
+                uint8_t *ws = C.blind.as<uint8_t>(d * 32);
+                if (s) C.up(ws, s, d * 32, C.stream);
+                else { const size_t one = op->term_count; blind_combine_launch(C, C.tmp_in2, wipe, 1, &one, &op->terms, op->term_count, 0, d, &ws); }
+                s = ws;
+            } else if ((uintptr_t)s & 15) return fail(ROFL_BAD_PARAM, "a device opening must be 16-byte aligned");
+            HIPCHK(hipMemsetAsync(status + 2, 0xff, 4, C.stream));
+            ROFL_LAUNCH(k_acc_open, grid1(d, 2), dim3(TPB), 0, C.stream, (u32)d, (const ge *)A.sum, reinterpret_cast<const sc *>(s), b, C.d_tabB8, C.d_tabBb8, enc, status + 1);
+        }
+        u32 st[3] = {0, 0, 0};
+        HIPCHK(hipMemcpyAsync(st, status, 12, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        if (st[1]) {      // some R is not the initial one (plus the opening's s B): the blindings did not cancel (the reference's None) / the opening is wrong
+            *ok_out = 0;
+            if (op && first_bad_out) *first_bad_out = st[2];
+            return ROFL_OK;
+        }
+        bsgs_solve_launch(C, d, enc, table_size, bsgs_bits, dout, status);
+        hv.resize(d * 32);
+        const uint8_t *hs = (const uint8_t *)C.down(hv.data(), dout, d * 32, C.stream);
+        HIPCHK(hipMemcpyAsync(st, status, 4, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        if (st[0] & 4u) return fail(ROFL_FORMAT_ERROR, "invalid Ristretto encoding");
+        if (st[0] & 8u) return fail(ROFL_BAD_PARAM, "discrete log not found (the reference unwraps None)");
+        for (size_t i = 0; i < d; i++) out[i] = sc_to_f32(sc_frombytes(hs + 32 * i), fp_bits, fp_frac);
+        *ok_out = 1;
+        if (op && first_bad_out) *first_bad_out = (size_t)-1;
+        return ROFL_OK;
+    });
+}
 }  // namespace
 
 // ================================================================ C ABI
@@ -2288,10 +2371,7 @@ int rofl_blinding_vecs(size_t n_vec, const size_t *term_count, const rofl_blind_
     size_t total = 0;
     for (size_t v = 0; v < n_vec; v++) {
         if (d && !out32[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
-        if (term_count[v] && !terms[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
-        if (term_count[v] > ((size_t)1 << 22) || (total += term_count[v]) > ((size_t)1 << 22)) return fail(ROFL_BAD_PARAM, "more than 2^22 terms in one call");
-        for (size_t t = 0; t < term_count[v]; t++)
-            if (terms[v][t].sign != 1 && terms[v][t].sign != -1) return fail(ROFL_BAD_PARAM, "a term's sign is +1 or -1");
+        if (int rc = blind_terms_check(term_count[v], terms[v], &total)) return rc;
     }
     if (d == 0) return ROFL_OK;
     return guarded([&]() -> int {
@@ -2305,21 +2385,11 @@ int rofl_blinding_vecs(size_t n_vec, const size_t *term_count, const rofl_blind_
         }
         // a device output is written in place; a host output goes through the lane's workspace and the staging path
         uint8_t *ws = n_host ? C.Cbytes.as<uint8_t>(n_host * d * 32) : nullptr;
-        const size_t bytes = n_vec * sizeof(BlindVec) + total * sizeof(BlindTerm);
-        uint8_t *h = C.h_misc.as<uint8_t>(bytes), *dv = C.tmp_in.as<uint8_t>(bytes);
-        struct Wipe { uint8_t *h, *dv; size_t n; hipStream_t s;
-                      ~Wipe() { (void)hipMemsetAsync(dv, 0, n, s); (void)hipStreamSynchronize(s); volatile uint8_t *p = h; for (size_t i = 0; i < n; i++) p[i] = 0; } } wipe{h, dv, bytes, C.stream};
-        BlindVec *hv = reinterpret_cast<BlindVec *>(h); BlindTerm *ht = reinterpret_cast<BlindTerm *>(h + n_vec * sizeof(BlindVec));
-        size_t at = 0, slot = 0;
-        for (size_t v = 0; v < n_vec; v++) {
-            hv[v].out = on_dev[v] ? out32[v] : ws + (slot++) * d * 32; hv[v].term_first = (u32)at; hv[v].term_count = (u32)term_count[v];
-            for (size_t t = 0; t < term_count[v]; t++, at++) { memcpy(ht[at].seed, terms[v][t].seed, 32); ht[at].neg = terms[v][t].sign < 0; ht[at].pad = 0; }
-        }
-        HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, C.stream));
-        const size_t nblk = ((first + d + 1) >> 1) - (first >> 1);
-        ROFL_LAUNCH(k_blind_combine, grid1(nblk, (u32)n_vec), dim3(TPB), 0, C.stream, reinterpret_cast<const BlindVec *>(dv),
-                    reinterpret_cast<const BlindTerm *>(dv + n_vec * sizeof(BlindVec)), (u64)first, (u32)d);
-        for (size_t v = 0; v < n_vec; v++) if (!on_dev[v]) C.down(out32[v], hv[v].out, d * 32, C.stream);
+        std::vector<uint8_t *> dst(n_vec); size_t slot = 0;
+        for (size_t v = 0; v < n_vec; v++) dst[v] = on_dev[v] ? out32[v] : ws + (slot++) * d * 32;
+        BlindWipe wipe;
+        blind_combine_launch(C, C.tmp_in, wipe, n_vec, term_count, terms, total, first, d, dst.data());
+        for (size_t v = 0; v < n_vec; v++) if (!on_dev[v]) C.down(out32[v], dst[v], d * 32, C.stream);
         C.sync();
         return ROFL_OK;
     });
@@ -2511,33 +2581,23 @@ int rofl_acc_export(uint64_t h, uint8_t *pairs_out) {
     });
 }
 int rofl_acc_extract(uint64_t h, size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac, float *out, int *ok_out) {
-    if (!out || !ok_out || table_size == 0 || table_size >= (1u << 30) || !(bsgs_bits == 8 || bsgs_bits == 16 || bsgs_bits == 32) || !valid_fp(fp_bits, fp_frac))
-        return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::vector<uint8_t> hv;      // (outlives the lane: its release delivers the staged scalars here)
-    return with_acc(h, no_check, [&](Acc &A) -> int {
-        LaneLock lane_lock = acquire_lane(true); Ctx &C = *lane_lock.c;      // the primary lane: the baby-step tables rofl_discrete_log_vec caches
-        C.init();
-        const size_t d = A.d;
-        uint8_t *enc = C.tmp_in.as<uint8_t>(d * 32), *dout = C.Cbytes.as<uint8_t>(d * 32);
-        u32 *status = C.status.as<u32>(4);
-        HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
-        const ge b = acc_init_point(A.init);
-        ROFL_LAUNCH(k_acc_finish, grid1(d), dim3(TPB), 0, C.stream, (u32)d, 0, (const ge *)A.sum, b.X, b.Y, enc, status + 1);
-        u32 st[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(st, status, 8, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        if (st[1]) { *ok_out = 0; return ROFL_OK; }      // some R is not the initial one: the blindings did not cancel (the reference's None)
-        bsgs_solve_launch(C, d, enc, table_size, bsgs_bits, dout, status);
-        hv.resize(d * 32);
-        const uint8_t *hs = (const uint8_t *)C.down(hv.data(), dout, d * 32, C.stream);
-        HIPCHK(hipMemcpyAsync(st, status, 4, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        if (st[0] & 4u) return fail(ROFL_FORMAT_ERROR, "invalid Ristretto encoding");
-        if (st[0] & 8u) return fail(ROFL_BAD_PARAM, "discrete log not found (the reference unwraps None)");
-        for (size_t i = 0; i < d; i++) out[i] = sc_to_f32(sc_frombytes(hs + 32 * i), fp_bits, fp_frac);
-        *ok_out = 1;
-        return ROFL_OK;
-    });
+    return acc_extract(h, nullptr, table_size, bsgs_bits, fp_bits, fp_frac, out, ok_out, nullptr);
+}
+// Extraction after rejections: the accepted clients' blindings leave a residual s in every pair of the sum, and the caller hands in its
+// opening -- as d scalars (host or device memory) or as the signed seeds it is the sum of.  Every R equation is checked before anything is
+// extracted; see include/rofl_zk.h.
+int rofl_acc_extract_opened(uint64_t h, const uint8_t *opening32, size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac,
+                            float *out, int *ok_out, size_t *first_bad_out) {
+    if (!opening32) return fail(ROFL_BAD_PARAM, "bad parameter");
+    const AccOpening op{opening32, 0, nullptr};
+    return acc_extract(h, &op, table_size, bsgs_bits, fp_bits, fp_frac, out, ok_out, first_bad_out);
+}
+int rofl_acc_extract_opened_terms(uint64_t h, size_t term_count, const rofl_blind_term_t *terms, size_t table_size, unsigned bsgs_bits, unsigned fp_bits,
+                                  unsigned fp_frac, float *out, int *ok_out, size_t *first_bad_out) {
+    size_t total = 0;
+    if (int rc = blind_terms_check(term_count, terms, &total)) return rc;
+    const AccOpening op{nullptr, term_count, terms};
+    return acc_extract(h, &op, table_size, bsgs_bits, fp_bits, fp_frac, out, ok_out, first_bad_out);
 }
 int rofl_acc_reset(uint64_t h) {
     return with_acc(h, no_check, [&](Acc &A) -> int { LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c; C.init(); acc_reset_launch(C, A); C.sync(); return ROFL_OK; });

@@ -778,12 +778,22 @@ class EncModelParamsAccumulator:
         self.acc[:n] = summed.reshape(-1, 64)
         return True
 
-    def extract(self, table_size=None, bsgs_bits=16, fp=None):
-        """None when some R component is not the identity (the blindings did not cancel), else the f32 aggregate."""
+    def extract(self, table_size=None, bsgs_bits=16, fp=None, opening=None):
+        """None when some R component is not the identity (the blindings did not cancel), else the f32 aggregate.
+        opening (uint8[size, 32]): the sum of the summed clients' blinding vectors, for a round that left somebody out -- every R must be
+        opening * B (else None), and opening * B~ is taken off L first.  Composed from commit_vec / add_rp_vec / discrete_log_vec: the
+        host-side counterpart of DeviceAccumulator.extract_opened, three device calls and their transfers instead of one."""
         fp = api._fp(fp)
-        if np.any(self.acc[:, 32:64]):
+        if opening is not None:
+            s = pedersen_ops.add_scalar_vec(api._u8(opening), pedersen_ops.zero_scalar_vec(self.acc.shape[0]))      # canonical
+            if self.acc[:, 32:64].tobytes() != pedersen_ops.commit_no_blinding_vec(s).tobytes():      # (encodings are canonical: byte equality is point equality)
+                return None
+            minus = pedersen_ops.add_scalar_vec(pedersen_ops.zero_scalar_vec(s.shape[0]), s, subtract=True)
+            pts = pedersen_ops.add_rp_vec(np.ascontiguousarray(self.acc[:, :32]), pedersen_ops.commit_vec(pedersen_ops.zero_scalar_vec(s.shape[0]), minus))
+        elif np.any(self.acc[:, 32:64]):
             return None
-        pts = np.ascontiguousarray(self.acc[:, :32])
+        else:
+            pts = np.ascontiguousarray(self.acc[:, :32])
         sc = pedersen_ops.default_discrete_log_vec(pts, fp=fp) if table_size is None else pedersen_ops.discrete_log_vec(pts, table_size, bsgs_bits)
         return conversion32.scalar_to_f32_vec(sc, fp=fp)
 
@@ -801,6 +811,7 @@ class DeviceAccumulator:
     def __init__(self, size, reference_unity=False):
         self.size, self.reference_unity = int(size), bool(reference_unity)
         self._open = False
+        self.last_first_bad = None      # after extract_opened() returned None: the smallest failing coordinate
         self._h = api.accumulator.create(self.size, 1 if self.reference_unity else 0)
         self._open = True
 
@@ -867,6 +878,24 @@ class DeviceAccumulator:
         if table_size is None:
             table_size, bsgs_bits = api.default_bsgs(fp)
         return api.accumulator.extract(self._h, self.size, table_size, bsgs_bits, fp)
+
+    def extract_opened(self, opening=None, opening_terms=None, table_size=None, bsgs_bits=16, fp=None):
+        """extract() for a round that left somebody out: the summed clients' blindings leave a residual in every pair, and the caller hands
+        in its opening -- as `opening` (uint8[size, 32], or a torch uint8 tensor on the GPU: the sum of the summed clients' blinding
+        vectors) or as `opening_terms` ([(seed32, sign), ...] from pedersen_ops.pairwise_residual_terms / cancelling_residual_terms: the
+        opening is then built on the device and never exists on the host).  Exactly one of the two, else ValueError.  The opening is checked
+        against every R before anything is extracted: a wrong one gives None, and last_first_bad holds the smallest coordinate it fails at
+        (None after a success).  The accumulator is not changed.  (A method of its own: extract()'s parameter list is pinned.)"""
+        if (opening is None) == (opening_terms is None):
+            raise ValueError("exactly one of opening and opening_terms")
+        fp = api._fp(fp)
+        if table_size is None:
+            table_size, bsgs_bits = api.default_bsgs(fp)
+        if opening is not None:
+            values, self.last_first_bad = api.accumulator.extract_opened(self._h, self.size, opening, table_size, bsgs_bits, fp)
+        else:
+            values, self.last_first_bad = api.accumulator.extract_opened_terms(self._h, self.size, opening_terms, table_size, bsgs_bits, fp)
+        return values
 
     def reset(self):
         api.accumulator.reset(self._h)

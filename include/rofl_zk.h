@@ -337,6 +337,30 @@ int rofl_blinding_vecs(size_t n_vec, const size_t *term_count, const rofl_blind_
                        size_t first, size_t d, uint8_t *const *out32);
 /* pedersen_ops.rs:124-127 with the randomness an explicit input: one vector of one +1 term */
 int rofl_rnd_scalar_vec(const uint8_t seed[32], size_t first, size_t d, uint8_t *out32);
+/* Key agreement for the pairwise masks: batched Ristretto255 Diffie-Hellman.  This is where the "shared secret" of pairwise_round_seed /
+ * pairwise_blinding_vec comes from.
+ *   secret key: 32 bytes read as a little-endian integer and reduced mod l; a key that is 0 mod l is refused (11);
+ *   public key: the Ristretto encoding of sk * B;
+ *   shared secret of own key a and peer public key P_b: SHAKE256(D || S || lo || hi)[0 .. 32), 112 bytes and one Keccak block, with
+ *     D = "rofl-zk/dh/v1" followed by three zero bytes, S = encode(a * decode(P_b)), lo <= hi the two parties' public keys ordered as byte
+ *     strings -- symmetric: shared(a, P_b) == shared(b, P_a).  The round's mask seed stays pairwise_round_seed(shared, round_no).
+ * rofl_dh_shared: pair i = (pairs[i].own, pairs[i].peer) indexes sk32 (n_own x 32) and peer_pk32 (n_peer x 32); pairs == NULL means all
+ * n_own x n_peer pairs, own-major, and n_pairs must equal the product.  out32 receives n_pairs x 32 bytes, status_out n_pairs bytes,
+ * own_pk_out32 (may be NULL) the n_own public keys.  A peer key is refused per pair, not per call: status 1 = not a canonical Ristretto
+ * encoding, 2 = the identity (32 zero bytes); the 32 output bytes of such a pair are zero, every other pair is unaffected.  Every peer key is
+ * decoded once, whatever the number of pairs it is in.  Host pointers only.  Returns 11 before the device is touched for: a null pointer, a
+ * pair index out of range, an own key that is 0 mod l (the text names the index, never the bytes), n / n_own / n_peer > 2^20,
+ * n_pairs > 2^24, pairs == NULL with n_pairs != n_own * n_peer; n = 0 / n_pairs = 0 returns 0 and touches no device.  One lane: one upload,
+ * three launches, one download.  Secret keys and shared secrets are secrets: the lane's pinned staging copies and device workspace that held
+ * them are overwritten with zeros before the call returns or unwinds.  NOT constant-time (digit-dependent table reads, no addition on a zero
+ * digit), like every other secret-scalar path of this library.  Revealing a secret key reveals every secret it ever agreed on: keys are per
+ * epoch. */
+typedef struct { uint32_t own, peer; } rofl_dh_pair_t;
+int rofl_dh_public_keys(size_t n, const uint8_t *sk32, uint8_t *pk_out32);
+int rofl_dh_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32 /* may be NULL */,
+                   size_t n_peer, const uint8_t *peer_pk32,
+                   size_t n_pairs, const rofl_dh_pair_t *pairs /* NULL: all n_own x n_peer, own-major; n_pairs must equal the product */,
+                   uint8_t *out32 /* n_pairs x 32 */, uint8_t *status_out /* n_pairs */);
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out);         /* conversion32.rs:49-54 */
 int rofl_uint_to_f32_vec(const uint64_t *in, size_t d, unsigned fp_bits, unsigned fp_frac, float *out);        /* conversion32.rs:41-47 */
 int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float *out);  /* conversion32.rs:62-64 */

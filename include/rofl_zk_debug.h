@@ -91,6 +91,9 @@ int rofl_dbg_host_merlin(const uint8_t *label, size_t label_len, const uint8_t *
 int rofl_dbg_host_nonce(const uint8_t seed[32], uint64_t idx, uint8_t out[32]);
 /* scalar idx of the blinding stream of a seed (rofl_blinding_vecs), computed on the host from the source the kernel is compiled from */
 int rofl_dbg_host_blind(const uint8_t seed[32], uint64_t idx, uint8_t out[32]);
+/* one pair of rofl_dh_shared from the host arithmetic (no GPU): out32 and *status as that call gives them; own_pk32 == NULL: computed from sk32.
+ * Returns 11 for a null pointer or a secret key that is 0 mod l. */
+int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status);
 
 /* host micro-benchmarks of the code the per-round hops run (nanoseconds per operation on the calling core).
  * what: 0 Keccak-f[1600]; 1 point doubling, 2 point addition, 3 Ristretto encoding (51-bit host arithmetic);

@@ -163,6 +163,12 @@ extern "C" {
     pub fn rofl_blinding_vecs(n_vec: usize, term_count: *const usize, terms: *const *const RoflBlindTerm, first: usize, d: usize,
         out32: *const *mut u8) -> c_int;
     pub fn rofl_rnd_scalar_vec(seed: *const u8, first: usize, d: usize, out32: *mut u8) -> c_int;
+    /// Ristretto255 key agreement for the pairwise masks: pk = encode(sk * B) for n secret keys (32 bytes each, reduced mod l; 0 is refused)
+    pub fn rofl_dh_public_keys(n: usize, sk32: *const u8, pk_out32: *mut u8) -> c_int;
+    /// shared secrets of (own, peer) pairs, one launch chain: pairs null = all n_own x n_peer pairs, own-major; status 1 / 2 per pair = the
+    /// peer key is not canonical / is the identity (32 zero bytes out); own_pk_out32 may be null
+    pub fn rofl_dh_shared(n_own: usize, sk32: *const u8, own_pk_out32: *mut u8, n_peer: usize, peer_pk32: *const u8,
+        n_pairs: usize, pairs: *const RoflDhPair, out32: *mut u8, status_out: *mut u8) -> c_int;
     pub fn rofl_f32_to_fp_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut u64) -> c_int;
     pub fn rofl_uint_to_f32_vec(input: *const u64, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
     pub fn rofl_get_l2_clip_bounds(range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
@@ -185,6 +191,12 @@ extern "C" {
 pub struct RoflBlindTerm {
     pub seed: [u8; 32],
     pub sign: i32,
+}
+/// rofl_dh_pair_t: one pair of rofl_dh_shared -- indices into its own secret keys and its peer public keys
+#[repr(C)]
+pub struct RoflDhPair {
+    pub own: u32,
+    pub peer: u32,
 }
 
 #[repr(C)]

@@ -4,6 +4,7 @@
 //! expanded on the device from 32-byte seeds (rofl_blinding_vecs), for hosts that want :110-127 reproducible, or cancelling
 //! blindings without the dealer of :110-122.  acc_extract_opened(_terms) extract the aggregate of a device accumulator (rofl_acc_*) whose
 //! round rejected somebody, from the opening of the accepted clients' residual blinding.
+//! dh_public_keys / dh_shared_secrets are the key agreement the pairwise masks' shared secrets come from (rofl_dh_*).
 use curve25519_dalek_ng::ristretto::RistrettoPoint;
 use curve25519_dalek_ng::scalar::Scalar;
 
@@ -117,4 +118,23 @@ pub fn acc_extract_opened_terms(h: u64, d: usize, terms: &[RoflBlindTerm], table
     let rc = unsafe { rofl_acc_extract_opened_terms(h, terms.len(), terms.as_ptr(), table_size, BSGS_N_BITS as u32, fp_bits, fp_frac, out.as_mut_ptr(), &mut ok, &mut bad) };
     assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
     if ok != 0 { Ok(out) } else { Err(bad) }
+}
+
+/// Public keys of `sk` (32 bytes each, reduced mod l; a key that is 0 mod l panics with the library's text): encode(sk * B).
+pub fn dh_public_keys(sk: &[[u8; 32]]) -> Vec<[u8; 32]> {
+    let mut out = vec![[0u8; 32]; sk.len()];
+    let rc = unsafe { rofl_dh_public_keys(sk.len(), sk.as_ptr() as *const u8, out.as_mut_ptr() as *mut u8) };
+    assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
+    out
+}
+/// Shared secrets of own keys `sk` and peer public keys `peer_pks` for the listed (own, peer) pairs (None: all pairs, own-major), one device
+/// call: Ok(32 bytes) per pair, or Err(status) -- 1 the peer key is not a canonical Ristretto encoding, 2 it is the identity.  The secret of
+/// a pair is the same on both sides; pairwise_blinding_vec takes the round's seed derived from it.
+pub fn dh_shared_secrets(sk: &[[u8; 32]], peer_pks: &[[u8; 32]], pairs: Option<&[RoflDhPair]>) -> Vec<Result<[u8; 32], u8>> {
+    let n_pairs = pairs.map_or(sk.len() * peer_pks.len(), |p| p.len());
+    let (mut out, mut status) = (vec![[0u8; 32]; n_pairs], vec![0u8; n_pairs]);
+    let rc = unsafe { rofl_dh_shared(sk.len(), sk.as_ptr() as *const u8, std::ptr::null_mut(), peer_pks.len(), peer_pks.as_ptr() as *const u8,
+        n_pairs, pairs.map_or(std::ptr::null(), |p| p.as_ptr()), out.as_mut_ptr() as *mut u8, status.as_mut_ptr()) };
+    assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
+    out.iter().zip(status.iter()).map(|(o, s)| if *s == 0 { Ok(*o) } else { Err(*s) }).collect()
 }

@@ -43,6 +43,11 @@ class _BlindTerm(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_ubyte * 32), ("sign", ctypes.c_int32)]
 
 
+class _DhPair(ctypes.Structure):
+    """rofl_dh_pair_t"""
+    _fields_ = [("own", ctypes.c_uint32), ("peer", ctypes.c_uint32)]
+
+
 class _Timing(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("msm_accumulate_ms", ctypes.c_double),
                 ("msm_accumulate_launches", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64),
@@ -907,6 +912,73 @@ class compressed_rand_proof:
         return res
 
 
+def _keys32(a, what):
+    """keys as uint8[n, 32]: an (n, 32) / flat array, or a list of 32-byte strings"""
+    if isinstance(a, (list, tuple)):
+        a = [np.frombuffer(bytes(k), dtype=np.uint8) if isinstance(k, (bytes, bytearray, memoryview)) else np.asarray(k, dtype=np.uint8).reshape(-1) for k in a]
+        if any(k.size != 32 for k in a):
+            raise ValueError("%s is 32 bytes" % what)
+        a = np.stack(a) if a else np.zeros((0, 32), dtype=np.uint8)
+    elif isinstance(a, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(bytes(a), dtype=np.uint8)
+    a = np.asarray(a, dtype=np.uint8)
+    if a.size % 32 or (a.ndim > 1 and a.shape[-1] != 32):
+        raise ValueError("%s is 32 bytes" % what)
+    return np.ascontiguousarray(a).reshape(-1, 32)
+
+
+class key_agreement:
+    """Batched Ristretto255 Diffie-Hellman (rofl_dh_public_keys / rofl_dh_shared): where the shared secrets of the pairwise masks come from.
+    A secret key is 32 bytes, reduced mod l (0 mod l is refused); the public key is encode(sk * B); the shared secret of own key a and peer key
+    P_b is SHAKE256("rofl-zk/dh/v1" || 000000 || encode(a * P_b) || lo || hi)[0 .. 32), lo <= hi the two public keys as byte strings -- the
+    same 32 bytes on both sides.  Not constant-time.  A key serves one epoch: revealing it (a round that rejects its owner) reveals every
+    secret it agreed on."""
+
+    @staticmethod
+    def public_keys(sk):
+        """-> uint8[n, 32]"""
+        sk = _keys32(sk, "a secret key")
+        n = sk.shape[0]
+        out = np.zeros((n, 32), dtype=np.uint8)
+        buf = (ctypes.c_ubyte * max(n * 32, 1))()
+        try:
+            ctypes.memmove(buf, sk.ctypes.data, n * 32)
+            _check(lib().rofl_dh_public_keys(_sz(n), buf, _ptr(out)))
+        finally:
+            ctypes.memset(buf, 0, ctypes.sizeof(buf))
+        return out
+
+    @staticmethod
+    def shared_secrets(sk, peer_pks, pairs=None, with_public=False):
+        """Shared secrets of own keys sk (n_own) and peer public keys peer_pks (n_peer), ONE call: pairs = [(own, peer), ...] indexes the two
+        arrays, None = all n_own x n_peer pairs, own-major.  -> (uint8[n_pairs, 32], uint8[n_pairs]); status 1 = the peer key is not a
+        canonical Ristretto encoding, 2 = it is the identity, and the 32 bytes of such a pair are zero.  with_public=True appends the own
+        public keys uint8[n_own, 32]."""
+        sk, pk = _keys32(sk, "a secret key"), _keys32(peer_pks, "a public key")
+        n_own, n_peer = sk.shape[0], pk.shape[0]
+        if pairs is None:
+            n_pairs, parr = n_own * n_peer, None
+        else:
+            pl = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            n_pairs = pl.shape[0]
+            if n_pairs and (pl.min() < 0 or pl[:, 0].max() >= n_own or pl[:, 1].max() >= n_peer):
+                raise ValueError("a pair names a key that is not in the call")
+            parr = (_DhPair * max(n_pairs, 1))()
+            np.frombuffer(parr, dtype=np.uint32)[:2 * n_pairs] = pl.astype(np.uint32).reshape(-1)
+        out, status = np.zeros((n_pairs, 32), dtype=np.uint8), np.zeros(n_pairs, dtype=np.uint8)
+        own_pk = np.zeros((n_own, 32), dtype=np.uint8) if with_public else None
+        buf = (ctypes.c_ubyte * max(n_own * 32, 1))()
+        try:
+            ctypes.memmove(buf, sk.ctypes.data, n_own * 32)
+            _check(lib().rofl_dh_shared(_sz(n_own), buf, _ptr(own_pk) if with_public else None, _sz(n_peer), _ptr(pk), _sz(n_pairs), parr,
+                                        _ptr(out), _ptr(status)))
+        finally:
+            ctypes.memset(buf, 0, ctypes.sizeof(buf))
+        if with_public and n_pairs == 0 and n_own:      # (an empty call computes nothing: the keys come from their own entry)
+            own_pk = key_agreement.public_keys(sk)
+        return (out, status, own_pk) if with_public else (out, status)
+
+
 class pedersen_ops:
     @staticmethod
     def commit_vec(scalars, blindings):
@@ -1083,6 +1155,84 @@ class pedersen_ops:
     def pairwise_blinding_vecs(clients, d):
         """pairwise_blinding_vec for a process that hosts several clients, clients = [(index, peers), ...]: ONE call -> uint8[n, d, 32]"""
         return pedersen_ops.blinding_vecs([pedersen_ops._pairwise_terms(i, peers) for i, peers in clients], d)
+
+    # ---- the seeds from key agreement (key_agreement.shared_secrets): one Diffie-Hellman call for every hosted client ----
+    @staticmethod
+    def pairwise_peers_from_keys(index=None, sk=None, public_keys=None, round_no=None, clients=None):
+        """The `peers` list [(j, seed_ij), ...] pairwise_blinding_vec takes, for every j != index of the round, from client `index`'s secret key
+        and the round's public keys (uint8[n, 32], row j = client j): seed_ij = pairwise_round_seed(shared secret of the pair, round_no).
+        A process that hosts several clients passes clients=[(index, sk), ...] instead of index and sk and gets one peers list per client,
+        all from ONE rofl_dh_shared call (the form pairwise_blinding_vecs takes once zipped with the indices).  A refused public key raises
+        ValueError naming j and the status."""
+        several = clients is not None
+        if several == (index is not None or sk is not None) or (not several and (index is None or sk is None)):
+            raise ValueError("either index and sk, or clients=[(index, sk), ...]")
+        if public_keys is None or round_no is None:
+            raise ValueError("the round's public keys and its number are needed")
+        clients = [(int(i), k) for i, k in clients] if several else [(int(index), sk)]
+        pks = _keys32(public_keys, "a public key")
+        n = pks.shape[0]
+        pairs = []
+        for c, (i, _) in enumerate(clients):
+            if not 0 <= i < n:
+                raise ValueError("client %d has no public key in the round" % i)
+            pairs += [(c, j) for j in range(n) if j != i]
+        sks = _keys32([k for _, k in clients], "a secret key")
+        try:
+            secrets, status = key_agreement.shared_secrets(sks, pks, pairs)
+        finally:
+            sks[...] = 0
+        res, at = [], 0
+        for i, _ in clients:
+            peers = []
+            for j in range(n):
+                if j == i:
+                    continue
+                if status[at]:
+                    secrets[...] = 0
+                    raise ValueError("the public key of client %d is refused (status %d)" % (j, int(status[at])))
+                peers.append((j, pedersen_ops.pairwise_round_seed(secrets[at].tobytes(), round_no)))
+                at += 1
+            res.append(peers)
+        secrets[...] = 0
+        return res if several else res[0]
+
+    @staticmethod
+    def pairwise_residual_terms_from_keys(accepted, revealed, public_keys, round_no):
+        """pairwise_residual_terms from ONE revealed secret key per rejected client instead of one seed per (accepted, rejected) pair:
+        revealed = {j: sk_j}.  Each key is first checked against the round's public keys -- public_keys([sk_j]) != public_keys[j] raises
+        ValueError naming j -- then every (rejected, accepted) secret comes from one rofl_dh_shared call, and the list returned is exactly
+        pairwise_residual_terms(accepted, rejected, seeds) for the seeds those keys imply: same order, same signs.  A revealed key gives away
+        every mask its owner ever shared under it: keys are per epoch."""
+        accepted, rejected = [int(i) for i in accepted], sorted(int(j) for j in revealed)
+        both = set(accepted) & set(rejected)
+        if both:
+            raise ValueError("client %d is both accepted and rejected" % min(both))
+        pks = _keys32(public_keys, "a public key")
+        for i in accepted + rejected:
+            if not 0 <= i < pks.shape[0]:
+                raise ValueError("client %d has no public key in the round" % i)
+        if not accepted or not rejected:
+            return []
+        sks = _keys32([revealed[j] for j in rejected], "a secret key")
+        try:
+            own = key_agreement.public_keys(sks)
+            for r, j in enumerate(rejected):
+                if own[r].tobytes() != pks[j].tobytes():
+                    raise ValueError("the revealed key of client %d does not belong to its public key" % j)
+            secrets, status = key_agreement.shared_secrets(sks, pks[accepted], None)
+        finally:
+            sks[...] = 0
+        seeds = {}
+        for r, j in enumerate(rejected):
+            for a, i in enumerate(accepted):
+                at = r * len(accepted) + a
+                if status[at]:
+                    secrets[...] = 0
+                    raise ValueError("the public key of client %d is refused (status %d)" % (i, int(status[at])))
+                seeds[(i, j) if i < j else (j, i)] = pedersen_ops.pairwise_round_seed(secrets[at].tobytes(), round_no)
+        secrets[...] = 0
+        return pedersen_ops.pairwise_residual_terms(accepted, rejected, seeds)
 
     # ---- a round that rejects: the terms of the accepted set's residual blinding (accumulator.extract_opened_terms) ----
     @staticmethod

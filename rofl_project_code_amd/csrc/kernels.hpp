@@ -2377,6 +2377,77 @@ __global__ void __launch_bounds__(64) k_sigma_point_var_batch(int kind, u32 d, u
                            c.slow_mark);
 }
 #endif
+// ================================================================ key agreement (rofl_dh_public_keys / rofl_dh_shared)
+// Ristretto255 Diffie-Hellman for the pairwise masks: sk = 32 bytes reduced mod l, pk = encode(sk B),
+// shared(a, P_b) = SHAKE256("rofl-zk/dh/v1\0\0\0" || encode(a decode(P_b)) || lo || hi)[0..32) with lo <= hi the two public keys as byte strings
+// (112 bytes, one Keccak block).  Three launches: own public keys (one thread per key), one decoding per PEER into a workspace point with its
+// status word (1 not a canonical encoding, 2 the identity), and one thread per pair for the variable-base multiplication, the encoding, the
+// hash and the store.  Not constant-time, like every secret-scalar path here: digit-dependent table reads, no addition on a zero digit.
+// One-block SHAKE256 of fourteen little-endian words (112 bytes): the absorb of shake256_seeded_block for a longer message
+__device__ __forceinline__ void shake256_block14(u64 st[25], const u64 m[14]) {
+#pragma unroll
+    for (int i = 0; i < 25; i++) st[i] = i < 14 ? m[i] : 0;
+    st[14] ^= 0x1FULL;                   // SHAKE domain suffix right after 112 bytes
+    st[16] ^= 0x8000000000000000ULL;     // final bit of the 136-byte rate
+    keccak_f1600(st);
+}
+#define ROFL_DH_DOM {0x2f6b7a2d6c666f72ULL, 0x00000031762f6864ULL}      /* "rofl-zk/" "dh/v1\0\0\0" */
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(64) k_dh_public(u32 n, const sc *__restrict__ sk, const niels *tabB8, uint8_t *__restrict__ pk) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    sg_encode(pk + (size_t)32 * i, sg_fixed_mul8(tabB8, load_sc_reduced(&sk[i])));      // (sk != 0 mod l: checked by the host before the launch)
+}
+__global__ void __launch_bounds__(64) k_dh_decode(u32 n, const uint8_t *__restrict__ pk, ge *__restrict__ pts, u32 *__restrict__ status) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    gd P;
+    const bool ok = sg_decode(P, pk + (size_t)32 * i);      // (a refused encoding leaves the identity)
+    store_gd(&pts[i], P);
+    status[i] = !ok ? 1u : sg_is_identity(P) ? 2u : 0u;
+}
+#endif
+#if ROFL_KG(3)
+// pairs == nullptr: all n_own x n_peer pairs, own-major.  out: n_pairs x 32 bytes, 16-byte aligned; a refused peer key gives 32 zero bytes.
+__global__ void __launch_bounds__(64) k_dh_shared(u32 n_pairs, u32 n_peer, const uint2 *__restrict__ pairs, const sc *__restrict__ sk, const uint8_t *__restrict__ own_pk,
+                                                  const uint8_t *__restrict__ peer_pk, const ge *__restrict__ peer_pts, const u32 *__restrict__ peer_status,
+                                                  uint8_t *__restrict__ out, uint8_t *__restrict__ status) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pairs) return;
+    u32 a, b;
+    if (pairs) { const uint2 p = pairs[i]; a = p.x; b = p.y; } else { a = i / n_peer; b = i - a * n_peer; }
+    const u32 st = peer_status[b];
+    status[i] = (uint8_t)st;
+    uint4 *o = reinterpret_cast<uint4 *>(out + (size_t)32 * i);
+    if (st) { o[0] = make_uint4(0, 0, 0, 0); o[1] = make_uint4(0, 0, 0, 0); return; }
+    uint8_t S[32];
+    sg_encode(S, sg_var_mul(load_sc_reduced(&sk[a]), load_gd(&peer_pts[b])));
+    const u64 dom[2] = ROFL_DH_DOM;
+    u64 m[14], st25[25];
+    m[0] = dom[0]; m[1] = dom[1];
+#pragma unroll
+    for (int w = 0; w < 4; w++) { u64 v = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) v |= (u64)S[8 * w + q] << (8 * q);
+        m[2 + w] = v; }
+    const u64 *pa = reinterpret_cast<const u64 *>(own_pk + (size_t)32 * a), *pb = reinterpret_cast<const u64 *>(peer_pk + (size_t)32 * b);
+    u64 ka[4], kb[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) { ka[w] = pa[w]; kb[w] = pb[w]; }
+    // byte-string order: the first differing byte decides, so compare the words from the front with their bytes swapped
+    bool a_first = true, decided = false;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        const u64 x = __builtin_bswap64(ka[w]), y = __builtin_bswap64(kb[w]);
+        if (!decided && x != y) { a_first = x < y; decided = true; }
+    }
+#pragma unroll
+    for (int w = 0; w < 4; w++) { m[6 + w] = a_first ? ka[w] : kb[w]; m[10 + w] = a_first ? kb[w] : ka[w]; }
+    shake256_block14(st25, m);
+    o[0] = make_uint4((u32)st25[0], (u32)(st25[0] >> 32), (u32)st25[1], (u32)(st25[1] >> 32));
+    o[1] = make_uint4((u32)st25[2], (u32)(st25[2] >> 32), (u32)st25[3], (u32)(st25[3] >> 32));
+}
+#endif
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(TPB) k_sigma_finish_batch(int kind, u32 d, u32 fp_bits, u32 fp_frac, const SgClient *cl, DMerlin init, u32 *status /* [gridDim.y] */) {
     const SgClient &c = cl[blockIdx.y];

@@ -2403,6 +2403,122 @@ int rofl_rnd_scalar_vec(const uint8_t seed[32], size_t first, size_t d, uint8_t 
     volatile uint8_t *p = term.seed; for (int i = 0; i < 32; i++) p[i] = 0;
     return rc;
 }
+// ---- key agreement: where the pairwise masks' shared secrets come from (k_dh_public, k_dh_decode, k_dh_shared) ----
+}  // extern "C"
+namespace {
+// a secret key as the kernels read it (load_sc_reduced): 32 little-endian bytes reduced mod l
+sc dh_key_scalar(const uint8_t *sk32) { sc r = sc_frombytes(sk32); if (sc_geq_l(r.v)) r = sc_from_mont(sc_to_mont(r)); return r; }
+void dh_wipe(void *p, size_t n) { volatile uint8_t *q = (volatile uint8_t *)p; for (size_t i = 0; i < n; i++) q[i] = 0; }
+// own keys that are 0 mod l are refused before the device is touched; the text names the index, never the bytes
+int dh_check_keys(size_t n, const uint8_t *sk32) {
+    for (size_t i = 0; i < n; i++) {
+        sc k = dh_key_scalar(sk32 + 32 * i); const bool zero = sc_iszero(k); dh_wipe(&k, sizeof k);
+        if (zero) { char buf[96]; snprintf(buf, sizeof buf, "secret key %zu is zero mod l", i); return fail(ROFL_BAD_PARAM, buf); }
+    }
+    return ROFL_OK;
+}
+// k P on the host's 51-bit arithmetic, signed radix-16 windows like sg_var_mul (k canonical)
+h51::ge5 dh_host_mul(const sc &k, const h51::ge5 &P) {
+    h51::ge5 tab[8]; tab[0] = P;
+    for (int e = 1; e < 8; e++) tab[e] = h51::gadd(tab[e - 1], P);
+    int8_t dg[65]; int carry = 0;
+    for (int i = 0; i < 64; i++) { int v = (int)((k.v[i >> 3] >> ((i & 7) * 4)) & 15) + carry; carry = (v + 8) >> 4; dg[i] = (int8_t)(v - (carry << 4)); }
+    dg[64] = (int8_t)carry;
+    h51::ge5 acc = h51::identity();
+    for (int i = 64; i >= 0; i--) {
+        if (i != 64) for (int q = 0; q < 4; q++) acc = h51::gdouble(acc);
+        const int d = dg[i], ad = d < 0 ? -d : d;
+        if (ad) { h51::ge5 q = tab[ad - 1]; if (d < 0) { q.X = h51::neg(q.X); q.T = h51::neg(q.T); } acc = h51::gadd(acc, q); }
+    }
+    dh_wipe(dg, sizeof dg);
+    return acc;
+}
+const uint8_t kDhBase[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
+                             0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};
+}  // namespace
+extern "C" {
+int rofl_dh_public_keys(size_t n, const uint8_t *sk32, uint8_t *pk_out32) {
+    if (n == 0) return ROFL_OK;
+    if (!sk32 || !pk_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
+    if (int rc = dh_check_keys(n, sk32)) return rc;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        uint8_t *h = C.h_misc.as<uint8_t>(n * 64), *dv = C.tmp_in.as<uint8_t>(n * 64);      // [secret keys | public keys]
+        BlindWipe wipe; wipe.h = h; wipe.dv = dv; wipe.n = n * 32; wipe.s = C.stream;
+        memcpy(h, sk32, n * 32);
+        HIPCHK(hipMemcpyAsync(dv, h, n * 32, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_dh_public, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, reinterpret_cast<const sc *>(dv), C.d_tabB8, dv + n * 32);
+        HIPCHK(hipMemcpyAsync(h + n * 32, dv + n * 32, n * 32, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(pk_out32, h + n * 32, n * 32);
+        return ROFL_OK;
+    });
+}
+// The lane's copies of the secret keys and of the shared secrets -- pinned staging and device workspace -- are overwritten with zeros before the
+// call returns or unwinds (the product encodings never leave the threads' registers and scratch).
+int rofl_dh_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32,
+                   size_t n_pairs, const rofl_dh_pair_t *pairs, uint8_t *out32, uint8_t *status_out) {
+    if (n_pairs == 0) return ROFL_OK;
+    if (!sk32 || !peer_pk32 || !out32 || !status_out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_own == 0 || n_peer == 0) return fail(ROFL_BAD_PARAM, "pairs without keys");
+    if (n_own > ((size_t)1 << 20) || n_peer > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
+    if (n_pairs > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 pairs in one call");
+    if (!pairs && n_pairs != n_own * n_peer) return fail(ROFL_BAD_PARAM, "without a pair list n_pairs is n_own x n_peer");
+    if (pairs) for (size_t i = 0; i < n_pairs; i++)
+        if (pairs[i].own >= n_own || pairs[i].peer >= n_peer) { char buf[96]; snprintf(buf, sizeof buf, "pair %zu names a key that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
+    if (int rc = dh_check_keys(n_own, sk32)) return rc;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: [secret keys | peer keys | pair list]; download: [shared secrets | own public keys | status bytes]
+        const size_t up_pairs = (n_own + n_peer) * 32, up_bytes = up_pairs + (pairs ? n_pairs * sizeof(rofl_dh_pair_t) : 0);
+        const size_t dn_pk = n_pairs * 32, dn_st = dn_pk + n_own * 32, dn_bytes = dn_st + n_pairs;
+        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        ge *pts = C.aux_pts.as<ge>(n_peer); u32 *pst = C.status.as<u32>(n_peer);
+        BlindWipe wipe_keys, wipe_out;
+        wipe_keys.h = hu; wipe_keys.dv = du; wipe_keys.n = n_own * 32; wipe_keys.s = C.stream;
+        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = n_pairs * 32; wipe_out.s = C.stream;
+        memcpy(hu, sk32, n_own * 32); memcpy(hu + n_own * 32, peer_pk32, n_peer * 32);
+        if (pairs) memcpy(hu + up_pairs, pairs, n_pairs * sizeof(rofl_dh_pair_t));
+        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_dh_public, dim3((unsigned)((n_own + 63) / 64)), dim3(64), 0, C.stream, (u32)n_own, reinterpret_cast<const sc *>(du), C.d_tabB8, dd + dn_pk);
+        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_peer + 63) / 64)), dim3(64), 0, C.stream, (u32)n_peer, (const uint8_t *)(du + n_own * 32), pts, pst);
+        ROFL_LAUNCH(k_dh_shared, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_pairs, (u32)n_peer,
+                    pairs ? reinterpret_cast<const uint2 *>(du + up_pairs) : (const uint2 *)nullptr, reinterpret_cast<const sc *>(du), (const uint8_t *)(dd + dn_pk),
+                    (const uint8_t *)(du + n_own * 32), (const ge *)pts, (const u32 *)pst, dd, dd + dn_st);
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(out32, hd, n_pairs * 32); memcpy(status_out, hd + dn_st, n_pairs);
+        if (own_pk_out32) memcpy(own_pk_out32, hd + dn_pk, n_own * 32);
+        return ROFL_OK;
+    });
+}
+// one pair of rofl_dh_shared from the host arithmetic (no GPU): status 0 / 1 / 2 as there, 11 for a zero own key
+int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status) {
+    if (!sk32 || !peer_pk32 || !out32 || !status) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (int rc = dh_check_keys(1, sk32)) return rc;
+    memset(out32, 0, 32);
+    ge P;
+    if (!ristretto_decode(P, peer_pk32)) { *status = 1; return ROFL_OK; }
+    if (ge_is_identity_ristretto(P)) { *status = 2; return ROFL_OK; }
+    *status = 0;
+    sc k = dh_key_scalar(sk32);
+    uint8_t own[32], m[112] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 'd', 'h', '/', 'v', '1', 0, 0, 0};
+    if (own_pk32) memcpy(own, own_pk32, 32);
+    else { ge B; ristretto_decode(B, kDhBase); h51::encode(own, dh_host_mul(k, h51::from_ge(B))); }
+    h51::encode(m + 16, dh_host_mul(k, h51::from_ge(P)));
+    const bool own_first = memcmp(own, peer_pk32, 32) <= 0;
+    memcpy(m + 48, own_first ? own : peer_pk32, 32); memcpy(m + 80, own_first ? peer_pk32 : own, 32);
+    u64 st[25]; memset(st, 0, sizeof st); memcpy(st, m, 112);
+    st[14] ^= 0x1FULL; st[16] ^= 0x8000000000000000ULL;
+    keccak_f1600_host(st);
+    memcpy(out32, st, 32);
+    dh_wipe(&k, sizeof k); dh_wipe(m, sizeof m); dh_wipe(st, sizeof st);
+    return ROFL_OK;
+}
 // conversion32::f32_to_fp_vec / uint_to_f32_vec (conversion32.rs:41-54): Fix is unsigned, negative inputs saturate to 0
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out) {
     if (!valid_fp(fp_bits, fp_frac)) return fail(ROFL_BAD_PARAM, "bad parameter");

@@ -67,8 +67,32 @@ int rofl_dbg_point_decodes(uint64_t *count_out);
 int rofl_bench_femul(unsigned iters, double *fe_mul_per_sec_out);
 /* self-test of the quad-parallel point arithmetic (csrc/quad26.hpp): pair i = (P, Q) -> 2^doublings P + Q, one thread per pair and one quad of lanes per pair */
 int rofl_dbg_quad_ops(const uint8_t *pairs64, size_t pairs, unsigned doublings, uint8_t *out_serial32, uint8_t *out_quad32);
+/* The kernels' field and point arithmetic (csrc/fe26.hpp, csrc/quad26.hpp) on RAW limbs: op table csrc/fd_dbg.hpp, kernel k_dbg_fd, one
+ * launch, one thread per case.  Case i reads in[80 i .. 80 i + 79] and writes out[80 i ..]; a field element is 10 limbs of radix 2^25.5
+ * (limb k at bit ceil(25.5 k)) taken as they are -- not carried, not reduced -- so the caller picks the representation and must stay inside
+ * the bounds the header of fe26.hpp states.  Output words an op does not write come back as the caller sent them.  a, b, c, d = elements
+ * 0 .. 3 of the input; p = elements 0 .. 3 (X, Y, Z, T), q = elements 4 .. 7 (or ypx, ymx, t2d in 4 .. 6).
+ *    0 fd_unpack(in[0..7] as 8 words, bit 255 kept)  -> 10 limbs        1 fd_carry(a)        2 fd_pack(a) -> 8 words, then fe_tobytes of them as 8 words
+ *    3 fd_add(a, b)   4 fd_sub(a, b)   5 fd_neg(a)   6 fd_mul(a, b)   7 fd_sq(a)   8 fd_mul(fd_sub(a, b), fd_add(c, d))   9 fd_sq(fd_add(a, b))
+ *   10 fd_invert(a)  11 fd_pow22523(a)  12 fd_sqrt_ratio_i(u = a, v = b) -> root in 0 .. 9, was_square in word 10   13 fd_abs(a)
+ *   14 -> word 0 fd_isneg(a), word 1 fd_iszero(a), word 2 fd_eq(a, b)
+ *   15 gd_madd(p, q, false)  16 gd_madd(p, q, true)  17 gd_add(p, q)  18 gd_double(p)  19 gd_double_not(p)      -> X, Y, Z, T in words 0 .. 39
+ *   20 gd_to_niels(p)  21 gd_to_niels_zinv(p, element 4)                                      -> ypx, ymx, t2d as 3 x 8 packed words
+ *   22 gq_double(p)  23 gq_add(p, q): one quad of lanes per case -> the quad's X, Y, Z, T in words 0 .. 39 and the one-thread gd_double /
+ *      gd_add of the same case in words 40 .. 79 (device only).
+ * 11 = bad parameter (op out of range, n == 0 or n > 2^20). */
+int rofl_dbg_fd_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out);
+/* The scalar field mod l as the kernels compile it (csrc/fe32.hpp sc_*, kernels.hpp load_sc_reduced): kernel k_dbg_sc, one thread per case.
+ * Case i reads in[264 i ..]: scalars of 8 little-endian words, a = words 0 .. 7, b = 8 .. 15; writes the 8 words out[8 i ..].
+ *    0 sc_montmul(a, b)  1 sc_to_mont(a)  2 sc_from_mont(a)  3 sc_mul_plain(a, b)  4 sc_add(a, b)  5 sc_neg(a)  6 sc_sub(a, b)  7 load_sc_reduced(a)
+ *    8 sc_from_wide(lo = a, hi = b)  9 sc_from_wide_mont(lo = a, hi = b)
+ *   10 sc_mac_wide over the in[264 i + 256] <= 16 pairs (scalar 2k, scalar 2k + 1), then ONE sc_redc_wide     11 sc_invert_mont(a) */
+int rofl_dbg_sc_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out);
 
 /* ---- host-side self-test hooks (same source as the device math, compiled for the CPU) ---- */
+/* rofl_dbg_fd_ops (ops 0 .. 21) and rofl_dbg_sc_ops through the host build, where fd_mul / fd_sq assert their operand bounds */
+int rofl_dbg_host_fd_ops_raw(unsigned op, size_t n, const uint32_t *in, uint32_t *out);
+int rofl_dbg_host_sc_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out);
 int rofl_dbg_host_pool_stress(unsigned threads, unsigned jobs);   /* host thread pool: every index of every job runs exactly once */
 int rofl_dbg_host_fe_mul(const uint8_t a[32], const uint8_t b[32], uint8_t out[32]);
 int rofl_dbg_host_fe_ops(const uint8_t a[32], const uint8_t b[32], uint8_t out_add[32], uint8_t out_sub[32], uint8_t out_sq[32], uint8_t out_inv[32]);
@@ -86,7 +110,7 @@ int rofl_dbg_host_fd_codec(const uint8_t in[32], uint8_t out[32]);
 int rofl_dbg_host_decode_encode(const uint8_t in[32], uint8_t out[32]);   /* returns 5 if invalid */
 /* radix-2^25.5 kernel arithmetic (fe26.hpp) compiled for the host with bound assertions enabled */
 int rofl_dbg_host_fd_ops(const uint8_t a[32], const uint8_t b[32], uint8_t out_mul[32], uint8_t out_sq[32], uint8_t out_add[32], uint8_t out_sub[32], uint8_t out_inv[32]);
-int rofl_dbg_host_fd_scalarmult(const uint8_t k[32], const uint8_t p[32], uint8_t out[32]);
+int rofl_dbg_host_fd_scalarmult(const uint8_t k[32], const uint8_t p[32], uint8_t out[32]);   /* k P on the kernel point formulas; k is reduced mod l first */
 int rofl_dbg_host_merlin(const uint8_t *label, size_t label_len, const uint8_t *msg, size_t msg_len, uint8_t out[64]);
 int rofl_dbg_host_nonce(const uint8_t seed[32], uint64_t idx, uint8_t out[32]);
 /* scalar idx of the blinding stream of a seed (rofl_blinding_vecs), computed on the host from the source the kernel is compiled from */

@@ -7,7 +7,10 @@
 // Limb bounds ("tight": even limbs < 2^26 + 2^19, odd limbs < 2^25 + 2^19):
 //   fd_mul / fd_sq / fd_carry / fd_unpack outputs are tight;
 //   fd_add: no carry;  fd_sub(a, b) = a + 2p - b needs b tight;
-//   fd_mul(f, g) needs f < 2^28 and g < 2^27.75 limb-wise (accumulators stay below 2^64: see DESIGN.md section 3, item 8).
+//   fd_mul(f, g) needs f < 2^28 + 2^20 and 19 g < 2^32 (g < 2^27.75) limb-wise, fd_sq(f) needs 19 f < 2^32 in the even and 38 f < 2^32 in
+//   the odd limbs (accumulators stay below 2^64: see DESIGN.md section 3, item 8).
+// Enforced by tests/test_fd_arith_host.py (this header compiled for the host, assertions on) and tests/test_gpu_fd_arith.py (device):
+// every function below at the extremes of these bounds, through the op table of fd_dbg.hpp, against the integer model tests/fd_model.py.
 #pragma once
 #include "fe32.hpp"
 #if defined(ROFL_FD_CHECK_HOST) && !defined(__HIP_DEVICE_COMPILE__)

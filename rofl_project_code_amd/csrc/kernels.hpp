@@ -7,6 +7,7 @@
 #include "fe32.hpp"
 #include "fe26.hpp"
 #include "quad26.hpp"
+#include "fd_dbg.hpp"
 #include "keccak.hpp"
 
 namespace rofl {
@@ -1923,6 +1924,34 @@ __global__ void __launch_bounds__(TPB) k_dbg_quad(u32 pairs, u32 doublings, cons
         S = gd_add(S, Q);
         gd_ristretto_encode(out_serial + (size_t)i * 32, S);
     }
+}
+// the op table of fd_dbg.hpp on raw limbs: one thread per case; for the two quad ops one quad of lanes per case (gq_*: words 0 .. 39 of the
+// case's output) beside the one-thread gd_* result of the same case (words 40 .. 79, written by lane 0)
+__global__ void __launch_bounds__(TPB) k_dbg_fd(u32 op, u32 n, const u32 *in /* [n][FD_DBG_IN] */, u32 *out /* [n][FD_DBG_OUT] */) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (op < FD_DBG_THREAD_OPS) {
+        if (t < n) fd_dbg_apply(op, in + (size_t)t * FD_DBG_IN, out + (size_t)t * FD_DBG_OUT);
+        return;
+    }
+    const u32 i = t >> 2, q = t & 3;
+    if (i >= n) return;                                 // whole quads
+    const u32 *ci = in + (size_t)i * FD_DBG_IN; u32 *co = out + (size_t)i * FD_DBG_OUT;
+    const gd P = gd_dbg_load(ci, 0), Q = gd_dbg_load(ci, 4);
+    const gq a = gq_from_gd(P, q);
+    const gq r = op == FD_DBG_GQ_DOUBLE ? gq_double(a, q) : gq_add(a, gq_from_gd(Q, q), q);
+    const gd R = gq_to_gd(r);                           // DPP: all four lanes are still here
+    if (q == 0) {
+        gd_dbg_store(co, 0, R);
+        gd_dbg_store(co, 4, op == FD_DBG_GQ_DOUBLE ? gd_double(P) : gd_add(P, Q));
+    }
+}
+// the scalar-field op table of fd_dbg.hpp, one thread per case
+__global__ void __launch_bounds__(TPB) k_dbg_sc(u32 op, u32 n, const u32 *in /* [n][SC_DBG_IN] */, u32 *out /* [n][SC_DBG_OUT] */) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const u32 *ci = in + (size_t)t * SC_DBG_IN;
+    const sc r = op == SC_DBG_LOAD_REDUCED ? load_sc_reduced(reinterpret_cast<const sc *>(ci)) : sc_dbg_apply(op, ci);
+    store_sc(reinterpret_cast<sc *>(out + (size_t)t * SC_DBG_OUT), r);
 }
 #endif
 

@@ -9,7 +9,8 @@
 // no LDS).  ~510 instead of ~1100 dependent instructions per doubling, ~680 instead of ~1500 per addition.
 //
 // Bounds: the operands handed to fd_sq / fd_mul are exactly those of gd_double / gd_add in fe26.hpp (same sums and differences
-// of tight values in the same operand positions), so the limb bounds proved there carry over.
+// of tight values in the same operand positions), so the limb bounds proved there carry over; tests/test_gpu_fd_arith.py
+// (test_device_quad_ops) holds gq_double / gq_add to the one-thread gd_* limbs and to the integer model at those bounds.
 #pragma once
 #include "fe26.hpp"
 

@@ -2624,6 +2624,26 @@ int rofl_dbg_quad_ops(const uint8_t *pairs64, size_t pairs, unsigned doublings, 
         return ROFL_OK;
     });
 }
+// the op tables of fd_dbg.hpp on the device: n cases of `in_words` words in, `out_words` words out, one launch
+static int dbg_ops_device(bool scalar_field, unsigned op, size_t n, const uint32_t *in, uint32_t *out) {
+    const size_t in_words = scalar_field ? SC_DBG_IN : FD_DBG_IN, out_words = scalar_field ? SC_DBG_OUT : FD_DBG_OUT;
+    if (op >= (unsigned)(scalar_field ? SC_DBG_OPS : FD_DBG_OPS)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        if (n == 0 || n > (1u << 20) || !in || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
+        C.init();
+        u32 *din = C.tmp_in.as<u32>(n * in_words), *dout = C.tmp_out.as<u32>(n * out_words);
+        C.up(din, in, n * in_words * 4, C.stream);
+        C.up(dout, out, n * out_words * 4, C.stream);      // words an op does not write come back as the caller sent them
+        if (scalar_field) ROFL_LAUNCH(k_dbg_sc, grid1(n), dim3(TPB), 0, C.stream, (u32)op, (u32)n, (const u32 *)din, dout);
+        else ROFL_LAUNCH(k_dbg_fd, grid1(op < FD_DBG_THREAD_OPS ? n : n * 4), dim3(TPB), 0, C.stream, (u32)op, (u32)n, (const u32 *)din, dout);
+        C.down(out, dout, n * out_words * 4, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
+int rofl_dbg_fd_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out) { return dbg_ops_device(false, op, n, in, out); }
+int rofl_dbg_sc_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out) { return dbg_ops_device(true, op, n, in, out); }
 int rofl_discrete_log_vec(const uint8_t *points32, size_t d, size_t table_size, unsigned bsgs_bits, uint8_t *scalars_out32) {
     return guarded([&]() -> int {
         LaneLock lane_lock = acquire_lane(true); Ctx &C = *lane_lock.c;
@@ -3403,6 +3423,7 @@ int rofl_dbg_host_fd_scalarmult(const uint8_t k[32], const uint8_t p[32], uint8_
     ge P; if (!ristretto_decode(P, p)) return ROFL_FORMAT_ERROR;
     nd q = nd_unpack(ge_to_niels(P));
     sc s = sc_frombytes(k);
+    if (sc_geq_l(s.v)) s = sc_from_mont(sc_to_mont(s));      // as load_sc_reduced: sc_naf's 256 digits hold a canonical scalar, not 2^256 - 1
     int8_t naf[256]; int top = sc_naf(naf, s);
     gd acc = gd_identity();
     for (int i = top; i >= 0; i--) { acc = gd_double(acc); if (naf[i]) acc = gd_madd(acc, q, naf[i] < 0); }
@@ -3416,6 +3437,17 @@ int rofl_dbg_host_fd_codec(const uint8_t in[32], uint8_t out[32]) {
     gd p; if (!gd_ristretto_decode(p, in)) return ROFL_FORMAT_ERROR;
     gd q = gd_add(gd_double(p), gd_madd(gd_identity(), nd_unpack(gd_to_niels(p)), true));     // 2P - P through the kernel formulas
     gd_ristretto_encode(out, q); return 0;
+}
+// the op tables of fd_dbg.hpp through the host build (bound assertions on); the two quad ops exist on the device only
+int rofl_dbg_host_fd_ops_raw(unsigned op, size_t n, const uint32_t *in, uint32_t *out) {
+    if (op >= FD_DBG_THREAD_OPS || !in || !out) return ROFL_BAD_PARAM;
+    for (size_t i = 0; i < n; i++) fd_dbg_apply(op, in + i * FD_DBG_IN, out + i * FD_DBG_OUT);
+    return 0;
+}
+int rofl_dbg_host_sc_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out) {
+    if (op >= SC_DBG_OPS || !in || !out) return ROFL_BAD_PARAM;
+    for (size_t i = 0; i < n; i++) { const sc r = sc_dbg_apply(op, in + i * SC_DBG_IN); for (int k = 0; k < 8; k++) out[i * SC_DBG_OUT + k] = r.v[k]; }
+    return 0;
 }
 int rofl_dbg_host_decode_encode(const uint8_t in[32], uint8_t out[32]) { ge p; if (!ristretto_decode(p, in)) return ROFL_FORMAT_ERROR; ristretto_encode(out, ge_add(p, ge_identity())); return 0; }
 int rofl_dbg_host_merlin(const uint8_t *label, size_t label_len, const uint8_t *msg, size_t msg_len, uint8_t out[64]) {

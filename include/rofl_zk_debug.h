@@ -88,6 +88,21 @@ int rofl_dbg_fd_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out);
  *    8 sc_from_wide(lo = a, hi = b)  9 sc_from_wide_mont(lo = a, hi = b)
  *   10 sc_mac_wide over the in[264 i + 256] <= 16 pairs (scalar 2k, scalar 2k + 1), then ONE sc_redc_wide     11 sc_invert_mont(a) */
 int rofl_dbg_sc_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out);
+/* The float-to-fixed rule (conversion32.rs:11-18: |v| 2^fp_frac rounded to nearest, ties to even, saturated at 2^fp_bits - 1, negated mod l
+ * for v < 0) at each of its device sites, on RAW values -- un-clipped, ties, infinities, NaN: nothing is checked on the way in.  `values` is
+ * [rows][d] floats.  The production kernels are launched unchanged, with the clip bounds (get_clip_bounds(prove_range)), the grid and the
+ * block count per client of their launch sites; a row is what a client is there.
+ *   site 0  k_quantize_shift (range-proof create): out = uint64 [rows][dpad], dpad >= d: word i < d of a row is the shifted value
+ *           ((+-k + 2^(prove_range-1)) mod l, low fp_bits bits), 0 where the value is flagged, and the padding words i >= d are 0;
+ *           status_out[row] = OR over the row of 1 (outside the closed clip range) and 2 (NaN).  1 <= prove_range <= fp_bits.
+ *   site 1  k_l2_sumsq_batch + k_l2_sumsq_combine (L2 sum proof): blindings32 = [rows][d][32] (any 256-bit value: reduced mod l);
+ *           terms_out = float [rows][d], the element's term q q 2^fp_frac of the reference's f32 shadow sum (k taken as 0 for NaN);
+ *           out = [rows][2][32]: the integer sum of k^2 (below 2^192) and the blinding sum mod l; status_out[row] as at site 0.
+ *   site 2  sg_f32_to_sc (every Sigma-proof kernel, the ElGamal pairs, the compressed proof's dot product) through k_dbg_quant, one thread
+ *           per value: out = [rows d][32] scalars.  prove_range, dpad, blindings32, terms_out and status_out are not read.
+ * 11 = bad parameter: site > 2, (fp_bits, fp_frac) not a supported format, rows or d == 0, rows dpad > 2^20, a missing array. */
+int rofl_dbg_quantize(unsigned site, size_t rows, size_t d, size_t dpad, size_t prove_range, unsigned fp_bits, unsigned fp_frac,
+                      const float *values, const uint8_t *blindings32, void *out, float *terms_out, uint32_t *status_out);
 
 /* ---- host-side self-test hooks (same source as the device math, compiled for the CPU) ---- */
 /* rofl_dbg_fd_ops (ops 0 .. 21) and rofl_dbg_sc_ops through the host build, where fd_mul / fd_sq assert their operand bounds */

@@ -2246,6 +2246,14 @@ __device__ inline sc sg_f32_to_sc(float v, u32 fp_bits, u32 fp_frac) {     // co
     sc m = sc_from_u64(kq); if (v < 0.0f) m = sc_neg(m);
     return m;
 }
+// rofl_dbg_quantize site 2: sg_f32_to_sc as the Sigma-proof kernels compile it, on raw values (NaN included: what they get is recorded too), one thread per case
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(TPB) k_dbg_quant(u32 n, u32 fp_bits, u32 fp_frac, const float *vals /* [n] */, sc *out /* [n] */) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    store_sc(&out[t], sg_f32_to_sc(vals[t], fp_bits, fp_frac));
+}
+#endif
 // nonce idx of a Sigma-proof call (same sources as k_nonce_expand).  `cache` keeps the last XOF block: consecutive indices share one Keccak-f.
 struct SgNonceCache { u64 blk; u64 w[16]; };
 __device__ inline sc sg_nonce(int mode, const NonceSeed &seed, const uint8_t *stream, u64 stream_scalars, u64 idx, SgNonceCache &cache) {

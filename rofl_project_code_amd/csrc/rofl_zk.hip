@@ -1244,6 +1244,7 @@ const char *l2_outcome_text(int rc) {
 // returns).  The surviving clients are compacted densely: one k_commit over them (WAIT 2: their V bytes, for the
 // transcripts) and one prove_chunks over na chunks of one value -- the host hops of the Bulletproof are paid once per batch.
 constexpr u32 kL2SumBlocks = 8;      // per client: 2 048 threads stride over d; 48 clients are 384 blocks on 256 CUs
+u32 l2_sum_blocks(size_t d) { return (u32)std::min<size_t>(kL2SumBlocks, (d + TPB - 1) / TPB); }
 int l2_create_batch(size_t nc, const float *const *values, size_t d, const uint8_t *const *blind, size_t prove_range, unsigned fp_bits, unsigned fp_frac,
                     const rofl_nonce_t *nonces, uint8_t *const *proofs_out, uint8_t *commits_out32, int *rcs) {
     LaneLock lane_lock = acquire_lane(false, nc == 1); Ctx &C = *lane_lock.c;
@@ -1254,7 +1255,7 @@ int l2_create_batch(size_t nc, const float *const *values, size_t d, const uint8
     float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
     std::vector<char> dev_v(nc), dev_b(nc); bool any_host = false;
     for (size_t i = 0; i < nc; i++) { dev_v[i] = is_device_ptr(values[i]); dev_b[i] = is_device_ptr(blind[i]); any_host |= !dev_v[i] || !dev_b[i]; }
-    const u32 nblk = (u32)std::min<size_t>(kL2SumBlocks, (d + TPB - 1) / TPB);
+    const u32 nblk = l2_sum_blocks(d);
     float *dv = C.vals.as<float>(nc * d), *dterms = C.tmp_out.as<float>(nc * d);
     sc *dbl = C.blind.as<sc>(std::max<size_t>(nc * d, nc)), *part_bl = C.tmp_in2.as<sc>(nc * nblk), *dsums = C.aux_scal.as<sc>(2 * nc);
     u64 *part_sq = C.tmp_in.as<u64>(nc * nblk * 3);
@@ -2644,6 +2645,49 @@ static int dbg_ops_device(bool scalar_field, unsigned op, size_t n, const uint32
 }
 int rofl_dbg_fd_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out) { return dbg_ops_device(false, op, n, in, out); }
 int rofl_dbg_sc_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out) { return dbg_ops_device(true, op, n, in, out); }
+// The float-to-fixed rule (conversion32.rs:11-18) as each device site compiles it, on the caller's raw values: the production kernels with the
+// launch geometry, clip bounds and block count of their launch sites (create_batch_impl, l2_create_batch), and k_dbg_quant for sg_f32_to_sc.
+int rofl_dbg_quantize(unsigned site, size_t rows, size_t d, size_t dpad, size_t prove_range, unsigned fp_bits, unsigned fp_frac,
+                      const float *values, const uint8_t *blindings32, void *out, float *terms_out, uint32_t *status_out) {
+    if (site > 2 || !valid_fp(fp_bits, fp_frac) || rows == 0 || d == 0 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (site != 0) dpad = d;
+    if (dpad < d || rows > (1u << 20) || dpad > (1u << 20) || rows * dpad > (1u << 20)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (site == 0 && (prove_range == 0 || prove_range > fp_bits || !status_out)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (site == 1 && (prove_range == 0 || prove_range > 128 || !blindings32 || !terms_out || !status_out)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        const size_t n = rows * d;
+        float *dv = C.vals.as<float>(n + 1);
+        u32 *status = C.status.as<u32>(rows + 4);
+        HIPCHK(hipMemsetAsync(status, 0, 4 * (rows + 4), C.stream));
+        C.up(dv, values, 4 * n, C.stream);
+        float mn = 0, mx = 0; if (site != 2) clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+        if (site == 0) {
+            u64 *vshift = C.vshift.as<u64>(rows * dpad);
+            HIPCHK(hipMemsetAsync(vshift, 0xff, 8 * rows * dpad, C.stream));      // (padding words come back 0 because the kernel writes them)
+            ROFL_LAUNCH(k_quantize_shift, grid1(dpad, (u32)rows), dim3(TPB), 0, C.stream, dv, (u32)d, (u32)dpad, (u32)prove_range, fp_bits, fp_frac, mn, mx, vshift, status);
+            C.down(out, vshift, 8 * rows * dpad, C.stream);
+        } else if (site == 1) {
+            const u32 nblk = l2_sum_blocks(d);
+            float *dterms = C.tmp_out.as<float>(n);
+            sc *dbl = C.blind.as<sc>(n), *part_bl = C.tmp_in2.as<sc>(rows * nblk), *dsums = C.aux_scal.as<sc>(2 * rows);
+            u64 *part_sq = C.tmp_in.as<u64>(rows * nblk * 3);
+            C.up(dbl, blindings32, 32 * n, C.stream);
+            ROFL_LAUNCH(k_l2_sumsq_batch, dim3(nblk, (unsigned)rows), dim3(TPB), 0, C.stream, (u32)d, fp_bits, fp_frac, mn, mx, (const float *)dv, (const sc *)dbl, dterms, part_sq, part_bl, status);
+            ROFL_LAUNCH(k_l2_sumsq_combine, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, C.stream, (u32)rows, nblk, (const u64 *)part_sq, (const sc *)part_bl, dsums);
+            C.down(terms_out, dterms, 4 * n, C.stream);
+            C.down(out, dsums, sizeof(sc) * 2 * rows, C.stream);
+        } else {
+            sc *ds = C.aux_scal.as<sc>(n);
+            ROFL_LAUNCH(k_dbg_quant, grid1(n), dim3(TPB), 0, C.stream, (u32)n, fp_bits, fp_frac, (const float *)dv, ds);
+            C.down(out, ds, sizeof(sc) * n, C.stream);
+        }
+        if (site != 2) C.down(status_out, status, 4 * rows, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
 int rofl_discrete_log_vec(const uint8_t *points32, size_t d, size_t table_size, unsigned bsgs_bits, uint8_t *scalars_out32) {
     return guarded([&]() -> int {
         LaneLock lane_lock = acquire_lane(true); Ctx &C = *lane_lock.c;

@@ -106,6 +106,17 @@ def _timed(thunk):
     return run
 
 
+def _range_commitments(clipped, bl, prove_range, fp):
+    """The commitments create_rangeproof returns for these (clipped) values and blindings, computed ahead of it so that the legs which complete
+    them can run beside the range proof: commit(read_from_bytes(f32_to_scalar(v) + 2^(n-1)) - 2^(n-1), r) (range_proof_vec/mod.rs:36-43, 96-99).
+    That is commit(f32_to_scalar(v), r) except where the shift leaves the fp_bits bits that read_from_bytes keeps: at a 32- or 64-bit range
+    get_clip_bounds rounds up to a power of two in f32, so the closed upper bound quantizes to 2^(n-1) and commits as the lower bound."""
+    off = np.frombuffer((1 << (prove_range - 1)).to_bytes(32, "little"), np.uint8)
+    s = pedersen_ops.compute_shifted_values_vec(conversion32.f32_to_scalar_vec(clipped, fp=fp), off)
+    s[:, fp[0] // 8:] = 0
+    return pedersen_ops.commit_vec(pedersen_ops.add_scalar_vec(s, np.ascontiguousarray(np.broadcast_to(off, s.shape)), subtract=True), bl)
+
+
 def _concurrently(*thunks):
     """Run independent proof calls on separate library lanes (each call takes a free lane: HIP stream + workspace).  The
     reference runs them one after the other, each spread over the rayon pool; on the GPU the latency-bound tails of one proof
@@ -221,7 +232,7 @@ class EncParamsRange:
         wd = witness_digest(x, bl) if nonce_seed is not None else b""
         clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         if check_percentage >= 1.0:
-            enc_com = pedersen_ops.commit_vec(conversion32.f32_to_scalar_vec(clipped, fp=fp), bl)      # == the range proof's commitments
+            enc_com = _range_commitments(clipped, bl, prove_range, fp)      # == the range proof's commitments
             # NB the reference passes the un-clipped plaintext here (params.rs:499)
             (rp, rp_com), (proofs, pairs) = _concurrently(
                 lambda: range_proof_vec.create_rangeproof(clipped, bl, prove_range, n_partition, nonce=_sub_nonce(nonce_seed, b"range", wd), fp=fp),
@@ -267,7 +278,7 @@ class EncParamsRange:
         rand_nonces = [_sub_nonce(sd, b"rand", wd) for sd, wd in zip(seeds, wds)]
         if check_percentage >= 1.0:
             # the range proofs' commitments, computed first (one call for all clients) so that the randomness proofs can complete them while the range proofs run
-            enc_all = pedersen_ops.commit_vec(np.concatenate([conversion32.f32_to_scalar_vec(c, fp=fp) for c in clipped]), np.concatenate(bls))
+            enc_all = _range_commitments(np.concatenate(clipped), np.concatenate(bls), prove_range, fp)
             enc_coms = [enc_all[i * d:(i + 1) * d] for i in range(n)]
             rv, rb = clipped, bls
         else:
@@ -395,7 +406,7 @@ class EncParamsRangeCompressed(EncParamsRange):
         wd = witness_digest(x, bl) if nonce_seed is not None else b""
         clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         if check_percentage >= 1.0:
-            enc_com = pedersen_ops.commit_vec(conversion32.f32_to_scalar_vec(clipped, fp=fp), bl)
+            enc_com = _range_commitments(clipped, bl, prove_range, fp)
             (rp, rp_com), (proof, pairs) = _concurrently(
                 lambda: range_proof_vec.create_rangeproof(clipped, bl, prove_range, n_partition, nonce=_sub_nonce(nonce_seed, b"range", wd), fp=fp),
                 lambda: compressed_rand_proof.helper_prove_existing(x, enc_com, bl, nonce=_sub_nonce(nonce_seed, b"rand", wd), fp=fp))
@@ -480,7 +491,7 @@ class EncParamsL2:
         clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         # the square proofs take the range proof's commitments (params.rs:623-637); committing first (same points) lets the
         # three proofs run side by side
-        enc_com = pedersen_ops.commit_vec(conversion32.f32_to_scalar_vec(clipped, fp=fp), bl)
+        enc_com = _range_commitments(clipped, bl, prove_range, fp)
         (rp, rp_com), (sum_proof, _), (proofs, commits) = _concurrently(
             lambda: range_proof_vec.create_rangeproof(clipped, bl, prove_range, n_partition, nonce=_sub_nonce(nonce_seed, b"range", wd), fp=fp),
             lambda: l2_range_proof_vec.create_rangeproof_l2(clipped, r2, l2_range, n_partition, nonce=_sub_nonce(nonce_seed, b"l2", wd), fp=fp),
@@ -513,7 +524,7 @@ class EncParamsL2:
             raise ValueError("the clients of a batch have one vector length")
         wds = [witness_digest(x, bl, r2) if sd is not None else b"" for x, bl, r2, sd in zip(xs, bls, r2s, seeds)]
         # the range proofs' commitments, computed first (one call for all clients) so that the square proofs can complete them while the range proofs run
-        enc_all = pedersen_ops.commit_vec(np.concatenate([conversion32.f32_to_scalar_vec(c, fp=fp) for c in clipped]), np.concatenate(bls))
+        enc_all = _range_commitments(np.concatenate(clipped), np.concatenate(bls), prove_range, fp)
         enc_com = [enc_all[i * d:(i + 1) * d] for i in range(n)]
         def nonces(tag):
             return [_sub_nonce(sd, tag, wd) for sd, wd in zip(seeds, wds)]
@@ -646,7 +657,7 @@ class EncParamsL2Compressed(EncParamsL2):
         r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
         clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
-        enc_com = pedersen_ops.commit_vec(conversion32.f32_to_scalar_vec(clipped, fp=fp), bl)
+        enc_com = _range_commitments(clipped, bl, prove_range, fp)
         (rp, rp_com), (sum_proof, _), (rand_proof, pairs) = _concurrently(
             lambda: range_proof_vec.create_rangeproof(clipped, bl, prove_range, n_partition, nonce=_sub_nonce(nonce_seed, b"range", wd), fp=fp),
             lambda: l2_range_proof_vec.create_rangeproof_l2(clipped, r2, l2_range, n_partition, nonce=_sub_nonce(nonce_seed, b"l2", wd), fp=fp),
@@ -678,7 +689,7 @@ class EncParamsL2Compressed(EncParamsL2):
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")
         wds = [witness_digest(x, bl, r2) if sd is not None else b"" for x, bl, r2, sd in zip(xs, bls, r2s, seeds)]
-        enc_all = pedersen_ops.commit_vec(np.concatenate([conversion32.f32_to_scalar_vec(c, fp=fp) for c in clipped]), np.concatenate(bls))
+        enc_all = _range_commitments(np.concatenate(clipped), np.concatenate(bls), prove_range, fp)
         enc_com = [enc_all[i * d:(i + 1) * d] for i in range(n)]
         def nonces(tag):
             return [_sub_nonce(sd, tag, wd) for sd, wd in zip(seeds, wds)]

@@ -361,6 +361,44 @@ int rofl_dh_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32 /* m
                    size_t n_peer, const uint8_t *peer_pk32,
                    size_t n_pairs, const rofl_dh_pair_t *pairs /* NULL: all n_own x n_peer, own-major; n_pairs must equal the product */,
                    uint8_t *out32 /* n_pairs x 32 */, uint8_t *status_out /* n_pairs */);
+/* Secret sharing of the mask secrets (Shamir, over the scalar field mod l), so that a round survives an HONEST dropout without opening the
+ * update of the client that left.
+ *   secret: 32 bytes read as a little-endian integer and reduced mod l, as keys and openings are; zero is allowed here (only rofl_dh_*
+ *     refuses a zero key);
+ *   coefficients: secret s with the 32-byte coefficient seed c and threshold t >= 1 defines f(X) = s + sum_{k=1..t-1} a_k X^k mod l, with
+ *     a_k = scalar k - 1 of the stream of c under the 16-byte label "rofl-zk/share/v1" -- the construction of the blinding stream under a
+ *     label of its own: a_k = int_le(SHAKE256(label || c || u64le((k - 1) >> 1))[64 ((k - 1) & 1) .. + 64]) mod l.  A coefficient seed is
+ *     as secret as the secret it shares;
+ *   share: the share for the evaluation point x is the canonical 32-byte encoding of f(x); x is a uint32, nonzero, all points of a call
+ *     distinct; client i of a round holds x = i + 1.  Any t shares determine s, t - 1 determine nothing;
+ *   reconstruction: from n shares at distinct nonzero points, s = sum_j lambda_j share_j with lambda_j = prod_{m != j} x_m (x_m - x_j)^-1
+ *     mod l.  Shares that are not canonical are reduced.  The interpolation uses ALL shares handed in: more than t consistent shares give the
+ *     same secret, fewer than t or one wrong share give another scalar and NO error -- the sharing is not verifiable (no Feldman
+ *     commitments); what catches a wrong share is the check the reconstructed secret goes into (below);
+ *   self-mask (double masking): client i draws a fresh self-mask secret b_i every round; its seed is SHA3-256("rofl-zk/blind/v1/self" ||
+ *     canonical32(b_i mod l) || u64le(round_no)) and its blinding vector is the pairwise vector plus +stream(self seed).  b_i is revealed
+ *     for every survivor of a round, so it serves ONE round whatever round_no says;
+ *   recovery: the sum over the survivor set A keeps the residual sum_{i in A} stream(self_i) + sum_{i in A, j not in A} +-stream(seed_ij).
+ *     The server collects, from at least t survivors, their shares of sk_j for every dropped j and of b_i for every survivor i,
+ *     reconstructs both groups, builds the term list and hands it to rofl_acc_extract_opened_terms, which checks the opening against every
+ *     R.  A wrong key is caught by comparing its public key, a wrong self secret by the failing R equations; neither names the survivor who
+ *     lied.  The server must never reconstruct BOTH secrets of one client: sk_j opens the pairwise masks, b_j the self-mask, and together
+ *     they open the client's update.
+ * rofl_shamir_share: shares_out32[s][i] = f_s(xs[i]), secret-major; xs == NULL means the points 1 .. n_shares.  A call with a subset of the
+ * points returns exactly the columns the whole call would: that is how ranks or chunks split a sharing.
+ * rofl_shamir_reconstruct: one set of points for all secrets; secrets_out32 receives n_secrets x 32 canonical bytes.  O(n_shares^2) for the
+ * weights, hence the lower cap.
+ * Host pointers only.  Both return 11 before the device is touched for: a null pointer (except xs of share), threshold = 0 or > n_shares,
+ * threshold > 65536, an x of 0, two equal x (the text names the two positions), n_secrets > 65535, n_shares > 2^20 (share) / > 65536
+ * (reconstruct), n_secrets x n_shares > 2^24, n_secrets x (threshold - 1) > 2^24, n_shares = 0 with secrets; n_secrets = 0 returns 0 and
+ * touches no device.  Error texts never contain secret, seed or share bytes.  One lane: one upload, two launches, one download; the pinned
+ * staging copies and the device workspace that held secrets, seeds, coefficients or shares are overwritten with zeros before the call
+ * returns or unwinds.  NOT constant-time.  The `devices` option does not apply. */
+int rofl_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32 /* n_secrets x 32 */,
+                      size_t threshold, size_t n_shares, const uint32_t *xs /* NULL: 1 .. n_shares */,
+                      uint8_t *shares_out32 /* n_secrets x n_shares x 32, secret-major */);
+int rofl_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *xs /* n_shares, one set for all secrets */,
+                            const uint8_t *shares32 /* n_secrets x n_shares x 32, secret-major */, uint8_t *secrets_out32);
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out);         /* conversion32.rs:49-54 */
 int rofl_uint_to_f32_vec(const uint64_t *in, size_t d, unsigned fp_bits, unsigned fp_frac, float *out);        /* conversion32.rs:41-47 */
 int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float *out);  /* conversion32.rs:62-64 */

@@ -133,6 +133,11 @@ int rofl_dbg_host_blind(const uint8_t seed[32], uint64_t idx, uint8_t out[32]);
 /* one pair of rofl_dh_shared from the host arithmetic (no GPU): out32 and *status as that call gives them; own_pk32 == NULL: computed from sk32.
  * Returns 11 for a null pointer or a secret key that is 0 mod l. */
 int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status);
+/* rofl_shamir_share / rofl_shamir_reconstruct on the host's scalar arithmetic and host Keccak, one thread, no GPU: the same parameters, the
+ * same checks (11) and the same bytes.  What the host tests pin the definition with, and the baseline of profiles/shamir_sharing.json. */
+int rofl_dbg_host_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares,
+                               const uint32_t *xs, uint8_t *shares_out32);
+int rofl_dbg_host_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *xs, const uint8_t *shares32, uint8_t *secrets_out32);
 
 /* host micro-benchmarks of the code the per-round hops run (nanoseconds per operation on the calling core).
  * what: 0 Keccak-f[1600]; 1 point doubling, 2 point addition, 3 Ristretto encoding (51-bit host arithmetic);

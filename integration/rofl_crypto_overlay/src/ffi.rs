@@ -169,6 +169,16 @@ extern "C" {
     /// peer key is not canonical / is the identity (32 zero bytes out); own_pk_out32 may be null
     pub fn rofl_dh_shared(n_own: usize, sk32: *const u8, own_pk_out32: *mut u8, n_peer: usize, peer_pk32: *const u8,
         n_pairs: usize, pairs: *const RoflDhPair, out32: *mut u8, status_out: *mut u8) -> c_int;
+    /// Shamir shares of n_secrets scalars (32 bytes each, reduced mod l) at threshold `threshold`: shares_out32[s][i] = f_s(xs[i]), secret-major;
+    /// the coefficients of f_s come from coef_seeds32[s]; xs null = the points 1 .. n_shares, otherwise nonzero and distinct
+    pub fn rofl_shamir_share(n_secrets: usize, secrets32: *const u8, coef_seeds32: *const u8, threshold: usize, n_shares: usize, xs: *const u32,
+        shares_out32: *mut u8) -> c_int;
+    /// the secrets from n_shares shares each at the points xs (one set for all secrets): Lagrange interpolation at 0 over ALL shares handed in
+    pub fn rofl_shamir_reconstruct(n_secrets: usize, n_shares: usize, xs: *const u32, shares32: *const u8, secrets_out32: *mut u8) -> c_int;
+    /// include/rofl_zk_debug.h: the two calls above on the host's arithmetic, one thread, no GPU -- same parameters, same bytes
+    pub fn rofl_dbg_host_shamir_share(n_secrets: usize, secrets32: *const u8, coef_seeds32: *const u8, threshold: usize, n_shares: usize,
+        xs: *const u32, shares_out32: *mut u8) -> c_int;
+    pub fn rofl_dbg_host_shamir_reconstruct(n_secrets: usize, n_shares: usize, xs: *const u32, shares32: *const u8, secrets_out32: *mut u8) -> c_int;
     pub fn rofl_f32_to_fp_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut u64) -> c_int;
     pub fn rofl_uint_to_f32_vec(input: *const u64, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
     pub fn rofl_get_l2_clip_bounds(range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;

@@ -138,3 +138,24 @@ pub fn dh_shared_secrets(sk: &[[u8; 32]], peer_pks: &[[u8; 32]], pairs: Option<&
     assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
     out.iter().zip(status.iter()).map(|(o, s)| if *s == 0 { Ok(*o) } else { Err(*s) }).collect()
 }
+/// Shamir shares of `secrets` (32 bytes each, reduced mod l) at threshold `threshold`, one device call: row s holds the shares of secret s
+/// at the points `xs` (None: 1 ..= n_shares; otherwise nonzero and distinct, client i holds i + 1).  The coefficients of secret s come
+/// from coef_seeds[s], which is as secret as the secret.  A bad parameter panics with the library's text.
+pub fn shamir_share(secrets: &[[u8; 32]], coef_seeds: &[[u8; 32]], threshold: usize, n_shares: usize, xs: Option<&[u32]>) -> Vec<Vec<[u8; 32]>> {
+    assert!(coef_seeds.len() == secrets.len() && xs.map_or(true, |x| x.len() == n_shares), "one seed per secret, one point per share");
+    let mut out = vec![[0u8; 32]; secrets.len() * n_shares];
+    let rc = unsafe { rofl_shamir_share(secrets.len(), secrets.as_ptr() as *const u8, coef_seeds.as_ptr() as *const u8, threshold, n_shares,
+        xs.map_or(std::ptr::null(), |x| x.as_ptr()), out.as_mut_ptr() as *mut u8) };
+    assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
+    out.chunks(n_shares.max(1)).map(|r| r.to_vec()).collect()
+}
+/// The secrets from `shares` (row s: the shares of secret s at the points `xs`, one set of points for all rows): interpolation at 0 over
+/// ALL shares handed in.  Not verifiable: a wrong share gives another secret, not an error.
+pub fn shamir_reconstruct(xs: &[u32], shares: &[Vec<[u8; 32]>]) -> Vec<[u8; 32]> {
+    assert!(shares.iter().all(|r| r.len() == xs.len()), "one share per point");
+    let flat: Vec<[u8; 32]> = shares.iter().flat_map(|r| r.iter().copied()).collect();
+    let mut out = vec![[0u8; 32]; shares.len()];
+    let rc = unsafe { rofl_shamir_reconstruct(shares.len(), xs.len(), xs.as_ptr(), flat.as_ptr() as *const u8, out.as_mut_ptr() as *mut u8) };
+    assert!(rc == ROFL_OK, "rofl_zk: {}", last_error());
+    out
+}

@@ -979,6 +979,71 @@ class key_agreement:
         return (out, status, own_pk) if with_public else (out, status)
 
 
+def _xs32(xs, n_shares):
+    """evaluation points as uint32[n_shares]: nonzero, distinct, each below 2^32"""
+    x = np.asarray(xs)
+    if x.ndim != 1 or x.shape[0] != n_shares or x.dtype.kind not in "iu":
+        raise ValueError("xs is one integer point per share")
+    if n_shares and (int(x.min()) < 1 or int(x.max()) >= 2 ** 32):
+        raise ValueError("an evaluation point is in [1, 2^32)")
+    x = np.ascontiguousarray(x.astype(np.uint32))
+    if np.unique(x).size != n_shares:
+        raise ValueError("the evaluation points are distinct")
+    return x
+
+
+class secret_sharing:
+    """Shamir sharing over the scalar field mod l (rofl_shamir_share / rofl_shamir_reconstruct), for the secrets behind a client's masks: its
+    key-agreement key and its per-round self-mask secret.  A secret is 32 bytes, reduced mod l (zero is allowed); with the 32-byte coefficient
+    seed c and threshold t it defines f(X) = s + sum_{k=1..t-1} a_k X^k, a_k = scalar k - 1 of the stream of c under the label
+    "rofl-zk/share/v1"; the share for the point x (a nonzero uint32; client i holds x = i + 1) is f(x), canonical.  Any t shares determine
+    the secret, t - 1 determine nothing.  A coefficient seed is as secret as the secret it shares.  The sharing is not verifiable: a wrong
+    share reconstructs another scalar without an error.  Not constant-time."""
+
+    @staticmethod
+    def share(secrets, coef_seeds, threshold, n_shares, xs=None):
+        """-> uint8[n_secrets, n_shares, 32], share [s, i] = f_s(xs[i]); xs=None means the points 1 .. n_shares.  A call with a subset of the
+        points returns exactly those columns of the whole call."""
+        sec, seeds = _keys32(secrets, "a secret"), _keys32(coef_seeds, "a coefficient seed")
+        n, threshold, n_shares = sec.shape[0], int(threshold), int(n_shares)
+        if seeds.shape[0] != n:
+            raise ValueError("one coefficient seed per secret")
+        if n_shares < 0 or (n and not 1 <= threshold <= n_shares):
+            raise ValueError("the threshold is in [1, n_shares]")
+        x = None if xs is None else _xs32(xs, n_shares)
+        out = np.zeros((n, n_shares, 32), dtype=np.uint8)
+        bs, bc = (ctypes.c_ubyte * max(n * 32, 1))(), (ctypes.c_ubyte * max(n * 32, 1))()
+        try:
+            ctypes.memmove(bs, sec.ctypes.data, n * 32)
+            ctypes.memmove(bc, seeds.ctypes.data, n * 32)
+            _check(lib().rofl_shamir_share(_sz(n), bs, bc, _sz(threshold), _sz(n_shares), None if x is None else _ptr(x), _ptr(out)))
+        finally:
+            ctypes.memset(bs, 0, ctypes.sizeof(bs))
+            ctypes.memset(bc, 0, ctypes.sizeof(bc))
+        return out
+
+    @staticmethod
+    def reconstruct(xs, shares):
+        """The secrets from shares uint8[n_secrets, len(xs), 32] at the points xs (one set for all secrets) -> uint8[n_secrets, 32].  ALL
+        shares handed in are interpolated; shares that are not canonical are reduced."""
+        n_shares = int(np.asarray(xs).shape[0]) if np.asarray(xs).ndim == 1 else -1
+        x = _xs32(xs, n_shares)
+        sh = np.asarray(shares, dtype=np.uint8)
+        if sh.ndim != 3 or sh.shape[1:] != (n_shares, 32):
+            raise ValueError("shares are uint8[n_secrets, len(xs), 32]")
+        n = sh.shape[0]
+        if n and n_shares == 0:
+            raise ValueError("secrets without shares")
+        out = np.zeros((n, 32), dtype=np.uint8)
+        buf = (ctypes.c_ubyte * max(n * n_shares * 32, 1))()
+        try:
+            ctypes.memmove(buf, np.ascontiguousarray(sh).ctypes.data, n * n_shares * 32)
+            _check(lib().rofl_shamir_reconstruct(_sz(n), _sz(n_shares), _ptr(x), buf, _ptr(out)))
+        finally:
+            ctypes.memset(buf, 0, ctypes.sizeof(buf))
+        return out
+
+
 class pedersen_ops:
     @staticmethod
     def commit_vec(scalars, blindings):
@@ -1156,6 +1221,35 @@ class pedersen_ops:
         """pairwise_blinding_vec for a process that hosts several clients, clients = [(index, peers), ...]: ONE call -> uint8[n, d, 32]"""
         return pedersen_ops.blinding_vecs([pedersen_ops._pairwise_terms(i, peers) for i, peers in clients], d)
 
+    # ---- double masking: the pairwise vector plus the stream of a per-round self-mask, so that a revealed key does not open a late update ----
+    @staticmethod
+    def self_mask_seed(b, round_no):
+        """SHA3-256("rofl-zk/blind/v1/self" || canonical32(b mod l) || u64le(round_no)): the seed of a client's self-mask from its self-mask
+        secret b (32 bytes, read little-endian and reduced mod l as the sharing reduces it).  b is revealed for every SURVIVOR of a round
+        (dropout_residual_terms), so a secret serves ONE round whatever round_no says: draw a fresh one each round."""
+        b = bytes(b)
+        if len(b) != 32:
+            raise ValueError("a self-mask secret is 32 bytes")
+        canon = (int.from_bytes(b, "little") % (2 ** 252 + 27742317777372353535851937790883648493)).to_bytes(32, "little")
+        return hashlib.sha3_256(b"rofl-zk/blind/v1/self" + canon + struct.pack("<Q", int(round_no))).digest()
+
+    @staticmethod
+    def double_masked_blinding_vec(index, peers, self_secret, round_no, d, first=0, out=None):
+        """pairwise_blinding_vec plus +stream(self_mask_seed(self_secret, round_no)): the pairwise masks still cancel over a whole round, the
+        self-masks never do -- every round ends with dropout_residual_terms, which needs the self secrets of the clients in the sum."""
+        terms = pedersen_ops._pairwise_terms(index, peers) + [(pedersen_ops.self_mask_seed(self_secret, round_no), 1)]
+        if out is None:
+            return pedersen_ops.blinding_vecs([terms], d, first)[0]
+        pedersen_ops.blinding_vecs([terms], d, first, out=[out])
+        return out
+
+    @staticmethod
+    def double_masked_blinding_vecs(clients, round_no, d):
+        """double_masked_blinding_vec for a process that hosts several clients, clients = [(index, peers, self_secret), ...]: ONE call
+        -> uint8[n, d, 32]"""
+        return pedersen_ops.blinding_vecs([pedersen_ops._pairwise_terms(i, peers) + [(pedersen_ops.self_mask_seed(b, round_no), 1)]
+                                           for i, peers, b in clients], d)
+
     # ---- the seeds from key agreement (key_agreement.shared_secrets): one Diffie-Hellman call for every hosted client ----
     @staticmethod
     def pairwise_peers_from_keys(index=None, sk=None, public_keys=None, round_no=None, clients=None):
@@ -1233,6 +1327,66 @@ class pedersen_ops:
                 seeds[(i, j) if i < j else (j, i)] = pedersen_ops.pairwise_round_seed(secrets[at].tobytes(), round_no)
         secrets[...] = 0
         return pedersen_ops.pairwise_residual_terms(accepted, rejected, seeds)
+
+    # ---- a round that loses an honest client: double masks, the secrets from the survivors' shares (secret_sharing) ----
+    @staticmethod
+    def dropout_residual_terms(survivors, dropped_keys, self_secrets, public_keys, round_no):
+        """The terms of the residual blinding of the survivors' sum in a double-masked round (double_masked_blinding_vec):
+        pairwise_residual_terms_from_keys(survivors, dropped_keys, public_keys, round_no) -- with its check of every key against the round's
+        public keys -- followed by (self_mask_seed(self_secrets[i], round_no), +1) for i in sorted survivors.  dropped_keys = {j: sk_j} for
+        the clients that left, self_secrets = {i: b_i} for the survivors.  The server must never hold BOTH secrets of one client (the key
+        opens its pairwise masks, the self secret its self-mask: together they open its update), so an index in both dicts raises
+        ValueError naming the client; so do a survivor without a self secret and a survivor in dropped_keys."""
+        surv = [int(i) for i in survivors]
+        dropped = {int(j): k for j, k in dropped_keys.items()}
+        selfs = {int(i): b for i, b in self_secrets.items()}
+        both = set(dropped) & set(selfs)
+        if both:
+            raise ValueError("client %d: its key and its self-mask secret are never opened together" % min(both))
+        for i in surv:
+            if i in dropped:
+                raise ValueError("client %d is a survivor and has a revealed key" % i)
+            if i not in selfs:
+                raise ValueError("survivor %d has no self-mask secret" % i)
+        terms = pedersen_ops.pairwise_residual_terms_from_keys(surv, dropped, public_keys, round_no)
+        return terms + [(pedersen_ops.self_mask_seed(selfs[i], round_no), 1) for i in sorted(surv)]
+
+    @staticmethod
+    def dropout_residual_terms_from_shares(survivors, dropped, xs, key_shares, self_shares, public_keys, round_no):
+        """dropout_residual_terms with the secrets reconstructed from the shares the answering survivors hold: xs = their evaluation points
+        (client i holds i + 1), key_shares = {j: uint8[len(xs), 32]} the shares of sk_j for every dropped j, self_shares = {i: ...} the
+        shares of b_i for every survivor i.  ALL secrets come from ONE rofl_shamir_reconstruct call (dropped keys first, then the survivors'
+        self secrets, the same xs).  A wrong key share raises ValueError naming the dropped client (the public-key check); a wrong self share
+        gives terms whose opening extract_opened refuses (ok = 0).  Neither names the survivor who lied."""
+        surv, drop = [int(i) for i in survivors], sorted(int(j) for j in dropped)
+        key_shares = {int(j): v for j, v in key_shares.items()}
+        self_shares = {int(i): v for i, v in self_shares.items()}
+        both = (set(key_shares) & set(self_shares)) | (set(surv) & set(drop))
+        if both:
+            raise ValueError("client %d: its key and its self-mask secret are never opened together" % min(both))
+        for j in drop:
+            if j not in key_shares:
+                raise ValueError("dropped client %d has no key shares" % j)
+        for i in surv:
+            if i not in self_shares:
+                raise ValueError("survivor %d has no self-mask shares" % i)
+        order = [(key_shares, j) for j in drop] + [(self_shares, i) for i in sorted(surv)]
+        n_sh = int(np.asarray(xs).shape[0])
+        stack = np.zeros((len(order), n_sh, 32), dtype=np.uint8)
+        for r, (src, c) in enumerate(order):
+            a = np.asarray(src[c], dtype=np.uint8)
+            if a.shape != (n_sh, 32):
+                raise ValueError("the shares of client %d are uint8[len(xs), 32]" % c)
+            stack[r] = a
+        try:
+            sec = secret_sharing.reconstruct(xs, stack) if len(order) else np.zeros((0, 32), dtype=np.uint8)
+        finally:
+            stack[...] = 0
+        try:
+            return pedersen_ops.dropout_residual_terms(surv, {j: sec[r].tobytes() for r, j in enumerate(drop)},
+                                                       {i: sec[len(drop) + r].tobytes() for r, i in enumerate(sorted(surv))}, public_keys, round_no)
+        finally:
+            sec[...] = 0
 
     # ---- a round that rejects: the terms of the accepted set's residual blinding (accumulator.extract_opened_terms) ----
     @staticmethod

@@ -2485,6 +2485,98 @@ __global__ void __launch_bounds__(64) k_dh_shared(u32 n_pairs, u32 n_peer, const
     o[1] = make_uint4((u32)st25[2], (u32)(st25[2] >> 32), (u32)st25[3], (u32)(st25[3] >> 32));
 }
 #endif
+// ================================================================ secret sharing (rofl_shamir_share / rofl_shamir_reconstruct)
+// Shamir sharing over the scalar field: secret s (32 bytes reduced mod l), coefficient seed c and threshold t define
+// f(X) = s + sum_{k=1..t-1} a_k X^k mod l with a_k = scalar k - 1 of the stream of c under the label "rofl-zk/share/v1" (the blinding stream's
+// construction); the share for the point x (a nonzero u32) is f(x), canonical.  Reconstruction from n shares at distinct points:
+// s = sum_j lambda_j share_j, lambda_j = prod_{m != j} x_m / (x_m - x_j).  blockIdx.y = secret wherever there is one.
+// Not constant-time (load_sc_reduced branches on its input), like every secret-scalar path here.
+#define SHAMIR_TILE 256      /* coefficients (k_shamir_eval) or points (k_shamir_weights) staged in LDS at a time: one per thread of a block */
+#if ROFL_KG(4)
+// coef[s][k - 1] = a_k of secret s, canonical; m = t - 1 >= 1 coefficients.  thread = one XOF block = coefficients 2 blk + 1, 2 blk + 2
+__global__ void __launch_bounds__(TPB) k_shamir_coeffs(u32 m, const u64 *__restrict__ seeds /* [gridDim.y][4] */, sc *__restrict__ coef /* [gridDim.y][m] */) {
+    const u32 blk = blockIdx.x * blockDim.x + threadIdx.x;
+    if (2 * (u64)blk >= m) return;
+    const u64 *sd = seeds + 4 * (size_t)blockIdx.y;
+    const u64 dom[2] = ROFL_SHARE_DOM, sw[4] = {sd[0], sd[1], sd[2], sd[3]};
+    u64 st[25];
+    shake256_seeded_block(st, dom, sw, blk);
+    sc *o = coef + (size_t)blockIdx.y * m;
+    store_sc(&o[2 * blk], xof_block_scalar(st, 0));
+    if (2 * blk + 1 < m) store_sc(&o[2 * blk + 1], xof_block_scalar(st, 1));
+}
+// share[s][i] = f_s(x_i) by Horner's rule from the top coefficient down, one share per thread; xs == nullptr: x_i = i + 1.
+// A block serves one secret, so at every step all its threads need the same coefficient: the block stages SHAMIR_TILE = 256 coefficients in LDS
+// (one 32-byte load per thread, kept as two planes of 16-byte halves so that the staging stores fall on consecutive banks), and every lane then
+// reads the same address -- a broadcast, no bank conflict.  The accumulator stays canonical and x is in Montgomery form, so
+// sc_montmul(acc, xR) = acc * x canonical and coefficients and the secret are added as they are.  t = 1 (m = 0) runs no step: the reduced secret.
+__global__ void __launch_bounds__(TPB) k_shamir_eval(u32 m, u32 n_shares, const sc *__restrict__ secrets, const sc *__restrict__ coef, const u32 *__restrict__ xs,
+                                                     sc *__restrict__ shares /* [gridDim.y][n_shares] */) {
+    static_assert(SHAMIR_TILE == TPB, "one staged coefficient per thread");
+    __shared__ uint4 tile[2][SHAMIR_TILE];
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n_shares;                       // (a thread past the end keeps staging and keeps the barriers; it stores nothing)
+    const u32 x = !live ? 1u : xs ? xs[i] : i + 1;
+    const sc xR = sc_to_mont(sc_from_u64(x));
+    const sc *cf = coef + (size_t)blockIdx.y * m;
+    sc acc = sc_zero();
+    for (u32 q = (m + SHAMIR_TILE - 1) / SHAMIR_TILE; q-- > 0;) {
+        const u32 base = q * SHAMIR_TILE, len = min((u32)SHAMIR_TILE, m - base);
+        if (threadIdx.x < len) {
+            const uint4 *s = reinterpret_cast<const uint4 *>(&cf[base + threadIdx.x]);
+            tile[0][threadIdx.x] = s[0]; tile[1][threadIdx.x] = s[1];
+        }
+        __syncthreads();
+        for (u32 k = len; k-- > 0;) {
+            sc a;
+            uint4 *d = reinterpret_cast<uint4 *>(&a);
+            d[0] = tile[0][k]; d[1] = tile[1][k];
+            acc = sc_add(sc_montmul(acc, xR), a);
+        }
+        __syncthreads();
+    }
+    acc = sc_add(sc_montmul(acc, xR), load_sc_reduced(&secrets[blockIdx.y]));
+    if (live) store_sc(&shares[(size_t)blockIdx.y * n_shares + i], acc);
+}
+// w[j] = lambda_j in Montgomery form, one per thread: the running products N = prod x_m and D = prod (x_m - x_j) over m != j, then N / D.
+// The factors go in as plain values, so each product carries the factor R^-(n-1) -- the same in N and D, gone from the quotient; the step
+// m == j multiplies both by 1 for the same reason, and no lane leaves the loop's path.  The points are staged SHAMIR_TILE at a time and read
+// by every lane at the same address.  O(n) steps per thread, O(n^2) per call.  Distinct nonzero points (checked by the host): D != 0.
+__global__ void __launch_bounds__(TPB) k_shamir_weights(u32 n, const u32 *__restrict__ xs, sc *__restrict__ w) {
+    __shared__ u32 tile[SHAMIR_TILE];
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = j < n;
+    const u32 xj = live ? xs[j] : 0u;
+    sc N = sc_one_plain(), D = sc_one_plain();
+    for (u32 base = 0; base < n; base += SHAMIR_TILE) {
+        const u32 len = min((u32)SHAMIR_TILE, n - base);
+        if (threadIdx.x < len) tile[threadIdx.x] = xs[base + threadIdx.x];
+        __syncthreads();
+        for (u32 k = 0; k < len; k++) {
+            const u32 xm = tile[k];
+            const bool self = base + k == j;
+            sc fn = sc_from_u64(self ? 1u : xm), fd = sc_from_u64(self ? 1u : xm > xj ? xm - xj : xj - xm), nfd = sc_neg(fd);
+            const bool neg = !self && xm < xj;
+#pragma unroll
+            for (int q = 0; q < 8; q++) fd.v[q] = neg ? nfd.v[q] : fd.v[q];
+            N = sc_montmul(N, fn);
+            D = sc_montmul(D, fd);
+        }
+        __syncthreads();
+    }
+    if (live) store_sc(&w[j], sc_montmul(N, sc_invert_mont(D)));
+}
+// out[s] = sum_j lambda_j * share[s][j], canonical: one block per secret, a thread takes shares j = t, t + TPB, ...  (w is in Montgomery form,
+// so w * share comes out canonical).  A share that is not canonical is reduced.
+__global__ void __launch_bounds__(TPB) k_shamir_combine(u32 n, const sc *__restrict__ w, const sc *__restrict__ shares /* [gridDim.x][n] */, sc *__restrict__ out) {
+    __shared__ sc lds[TPB];
+    const sc *sh = shares + (size_t)blockIdx.x * n;
+    sc v[1] = {sc_zero()};
+    for (u32 j = threadIdx.x; j < n; j += TPB) v[0] = sc_add(v[0], sc_montmul(load_sc(&w[j]), load_sc_reduced(&sh[j])));
+    block_sum_sc<1>(v, lds);
+    if (threadIdx.x == 0) store_sc(&out[blockIdx.x], v[0]);
+}
+#endif
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(TPB) k_sigma_finish_batch(int kind, u32 d, u32 fp_bits, u32 fp_frac, const SgClient *cl, DMerlin init, u32 *status /* [gridDim.y] */) {
     const SgClient &c = cl[blockIdx.y];

@@ -967,8 +967,9 @@ int blind_terms_check(size_t term_count, const rofl_blind_term_t *terms, size_t 
     return ROFL_OK;
 }
 // the lane's copies of a call's term list (pinned host memory, device workspace): overwritten with zeros when the call returns or unwinds
+// (h == nullptr: a device workspace that has no host copy)
 struct BlindWipe { uint8_t *h = nullptr, *dv = nullptr; size_t n = 0; hipStream_t s = nullptr;
-                   ~BlindWipe() { if (!n) return; (void)hipMemsetAsync(dv, 0, n, s); (void)hipStreamSynchronize(s); volatile uint8_t *p = h; for (size_t i = 0; i < n; i++) p[i] = 0; } };
+                   ~BlindWipe() { if (!n) return; (void)hipMemsetAsync(dv, 0, n, s); (void)hipStreamSynchronize(s); volatile uint8_t *p = h; for (size_t i = 0; p && i < n; i++) p[i] = 0; } };
 // vector v = sum of its terms' streams [first, first + d) into dst[v] (device memory, 16-byte aligned), every vector in ONE launch on the
 // lane's stream; the term list is staged in C.h_misc and in `term_buf`, which the caller leaves alone until `wipe` has run
 void blind_combine_launch(Ctx &C, DevBuf &term_buf, BlindWipe &wipe, size_t n_vec, const size_t *term_count, const rofl_blind_term_t *const *terms, size_t total,
@@ -2518,6 +2519,156 @@ int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint
     keccak_f1600_host(st);
     memcpy(out32, st, 32);
     dh_wipe(&k, sizeof k); dh_wipe(m, sizeof m); dh_wipe(st, sizeof st);
+    return ROFL_OK;
+}
+// ---- secret sharing: Shamir shares of mask secrets over the scalar field (k_shamir_coeffs, k_shamir_eval, k_shamir_weights, k_shamir_combine) ----
+}  // extern "C"
+namespace {
+// the evaluation points of a call: nonzero and distinct; the text names positions, never values of anything secret
+int shamir_check_xs(size_t n, const uint32_t *xs) {
+    std::vector<std::pair<uint32_t, uint32_t>> v(n);
+    for (size_t i = 0; i < n; i++) {
+        if (xs[i] == 0) { char buf[96]; snprintf(buf, sizeof buf, "evaluation point %zu is zero", i); return fail(ROFL_BAD_PARAM, buf); }
+        v[i] = {xs[i], (uint32_t)i};
+    }
+    std::sort(v.begin(), v.end());
+    for (size_t i = 1; i < n; i++)
+        if (v[i].first == v[i - 1].first) { char buf[96]; snprintf(buf, sizeof buf, "evaluation points %u and %u are equal", v[i - 1].second, v[i].second); return fail(ROFL_BAD_PARAM, buf); }
+    return ROFL_OK;
+}
+// every check of rofl_shamir_share, shared with its host route; *done: the call is empty and returns 0
+int shamir_share_check(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares, const uint32_t *xs,
+                       const uint8_t *shares_out32, bool *done) {
+    *done = n_secrets == 0;
+    if (*done) return ROFL_OK;
+    if (!secrets32 || !coef_seeds32 || !shares_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_shares == 0) return fail(ROFL_BAD_PARAM, "secrets without shares");
+    if (threshold == 0 || threshold > n_shares) return fail(ROFL_BAD_PARAM, "the threshold is in [1, n_shares]");
+    if (threshold > 65536) return fail(ROFL_BAD_PARAM, "a threshold above 65536");
+    if (n_secrets > 65535) return fail(ROFL_BAD_PARAM, "more than 65535 secrets in one call");
+    if (n_shares > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 shares of a secret in one call");
+    if (n_secrets * n_shares > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 shares in one call");
+    if (n_secrets * (threshold - 1) > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 coefficients in one call");
+    return xs ? shamir_check_xs(n_shares, xs) : ROFL_OK;
+}
+int shamir_reconstruct_check(size_t n_secrets, size_t n_shares, const uint32_t *xs, const uint8_t *shares32, const uint8_t *secrets_out32, bool *done) {
+    *done = n_secrets == 0;
+    if (*done) return ROFL_OK;
+    if (!xs || !shares32 || !secrets_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_shares == 0) return fail(ROFL_BAD_PARAM, "secrets without shares");
+    if (n_secrets > 65535) return fail(ROFL_BAD_PARAM, "more than 65535 secrets in one call");
+    if (n_shares > 65536) return fail(ROFL_BAD_PARAM, "more than 65536 shares of a secret in one call");
+    if (n_secrets * n_shares > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 shares in one call");
+    return shamir_check_xs(n_shares, xs);
+}
+}  // namespace
+extern "C" {
+// The lane's copies of the secrets, the coefficient seeds, the coefficients and the shares -- pinned staging and device workspace -- are
+// overwritten with zeros before the call returns or unwinds.
+int rofl_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares, const uint32_t *xs,
+                      uint8_t *shares_out32) {
+    bool done;
+    if (int rc = shamir_share_check(n_secrets, secrets32, coef_seeds32, threshold, n_shares, xs, shares_out32, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: [secrets | coefficient seeds | points]; workspace: the coefficients; download: the shares, secret-major
+        const size_t m = threshold - 1, up_xs = n_secrets * 64, up_bytes = up_xs + (xs ? n_shares * 4 : 0), dn_bytes = n_secrets * n_shares * 32;
+        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        sc *coef = C.tmp_in2.as<sc>(std::max<size_t>(n_secrets * m, 1));
+        BlindWipe wipe_in, wipe_coef, wipe_out;
+        wipe_in.h = hu; wipe_in.dv = du; wipe_in.n = up_xs; wipe_in.s = C.stream;
+        wipe_coef.dv = reinterpret_cast<uint8_t *>(coef); wipe_coef.n = n_secrets * m * 32; wipe_coef.s = C.stream;
+        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = dn_bytes; wipe_out.s = C.stream;
+        memcpy(hu, secrets32, n_secrets * 32); memcpy(hu + n_secrets * 32, coef_seeds32, n_secrets * 32);
+        if (xs) memcpy(hu + up_xs, xs, n_shares * 4);
+        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
+        if (m) ROFL_LAUNCH(k_shamir_coeffs, grid1((m + 1) / 2, (u32)n_secrets), dim3(TPB), 0, C.stream, (u32)m, reinterpret_cast<const u64 *>(du + n_secrets * 32), coef);
+        ROFL_LAUNCH(k_shamir_eval, grid1(n_shares, (u32)n_secrets), dim3(TPB), 0, C.stream, (u32)m, (u32)n_shares, reinterpret_cast<const sc *>(du), (const sc *)coef,
+                    xs ? reinterpret_cast<const u32 *>(du + up_xs) : (const u32 *)nullptr, reinterpret_cast<sc *>(dd));
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(shares_out32, hd, dn_bytes);
+        return ROFL_OK;
+    });
+}
+int rofl_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *xs, const uint8_t *shares32, uint8_t *secrets_out32) {
+    bool done;
+    if (int rc = shamir_reconstruct_check(n_secrets, n_shares, xs, shares32, secrets_out32, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: [shares, secret-major | points]; workspace: the weights (a function of the points alone); download: the secrets
+        const size_t up_xs = n_secrets * n_shares * 32, up_bytes = up_xs + n_shares * 4, dn_bytes = n_secrets * 32;
+        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        sc *w = C.tmp_in2.as<sc>(n_shares);
+        BlindWipe wipe_in, wipe_out;
+        wipe_in.h = hu; wipe_in.dv = du; wipe_in.n = up_xs; wipe_in.s = C.stream;
+        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = dn_bytes; wipe_out.s = C.stream;
+        memcpy(hu, shares32, up_xs); memcpy(hu + up_xs, xs, n_shares * 4);
+        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_shamir_weights, grid1(n_shares), dim3(TPB), 0, C.stream, (u32)n_shares, reinterpret_cast<const u32 *>(du + up_xs), w);
+        ROFL_LAUNCH(k_shamir_combine, dim3((unsigned)n_secrets), dim3(TPB), 0, C.stream, (u32)n_shares, (const sc *)w, reinterpret_cast<const sc *>(du), reinterpret_cast<sc *>(dd));
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(secrets_out32, hd, dn_bytes);
+        return ROFL_OK;
+    });
+}
+// the two calls on the host's scalar arithmetic and host Keccak, one thread, no GPU: same parameters, same checks, same bytes
+int rofl_dbg_host_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares, const uint32_t *xs,
+                               uint8_t *shares_out32) {
+    bool done;
+    if (int rc = shamir_share_check(n_secrets, secrets32, coef_seeds32, threshold, n_shares, xs, shares_out32, &done)) return rc;
+    if (done) return ROFL_OK;
+    const size_t m = threshold - 1;
+    const u64 dom[2] = ROFL_SHARE_DOM;
+    std::vector<sc> coef(m + 1);
+    for (size_t s = 0; s < n_secrets; s++) {
+        u64 sd[4], st[25]; memcpy(sd, coef_seeds32 + 32 * s, 32);
+        for (size_t blk = 0; 2 * blk < m; blk++) {
+            shake256_seeded_block(st, dom, sd, blk);
+            coef[2 * blk] = xof_block_scalar(st, 0); coef[2 * blk + 1] = xof_block_scalar(st, 1);      // (coef has room for one past m)
+        }
+        sc sec = dh_key_scalar(secrets32 + 32 * s);
+        for (size_t i = 0; i < n_shares; i++) {
+            const sc xR = sc_to_mont(sc_from_u64(xs ? xs[i] : (u64)i + 1));
+            sc acc = sc_zero();
+            for (size_t k = m; k-- > 0;) acc = sc_add(sc_montmul(acc, xR), coef[k]);
+            acc = sc_add(sc_montmul(acc, xR), sec);
+            sc_tobytes(shares_out32 + (s * n_shares + i) * 32, acc);
+            dh_wipe(&acc, sizeof acc);
+        }
+        dh_wipe(&sec, sizeof sec); dh_wipe(sd, sizeof sd); dh_wipe(st, sizeof st);
+    }
+    dh_wipe(coef.data(), coef.size() * sizeof(sc));
+    return ROFL_OK;
+}
+int rofl_dbg_host_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *xs, const uint8_t *shares32, uint8_t *secrets_out32) {
+    bool done;
+    if (int rc = shamir_reconstruct_check(n_secrets, n_shares, xs, shares32, secrets_out32, &done)) return rc;
+    if (done) return ROFL_OK;
+    std::vector<sc> w(n_shares);      // lambda_j in Montgomery form; N and D carry the same power of R (k_shamir_weights)
+    for (size_t j = 0; j < n_shares; j++) {
+        sc N = sc_one_plain(), D = sc_one_plain();
+        for (size_t k = 0; k < n_shares; k++) {
+            if (k == j) continue;
+            const u32 xm = xs[k], xj = xs[j];
+            sc fd = sc_from_u64(xm > xj ? xm - xj : xj - xm); if (xm < xj) fd = sc_neg(fd);
+            N = sc_montmul(N, sc_from_u64(xm)); D = sc_montmul(D, fd);
+        }
+        w[j] = sc_montmul(N, h51::sc_invert_mont_fast(D));
+    }
+    for (size_t s = 0; s < n_secrets; s++) {
+        sc acc = sc_zero();
+        for (size_t j = 0; j < n_shares; j++) acc = sc_add(acc, sc_montmul(w[j], dh_key_scalar(shares32 + (s * n_shares + j) * 32)));
+        sc_tobytes(secrets_out32 + 32 * s, acc);
+        dh_wipe(&acc, sizeof acc);
+    }
     return ROFL_OK;
 }
 // conversion32::f32_to_fp_vec / uint_to_f32_vec (conversion32.rs:41-54): Fix is unsigned, negative inputs saturate to 0

@@ -373,8 +373,8 @@ int rofl_dh_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32 /* m
  *     distinct; client i of a round holds x = i + 1.  Any t shares determine s, t - 1 determine nothing;
  *   reconstruction: from n shares at distinct nonzero points, s = sum_j lambda_j share_j with lambda_j = prod_{m != j} x_m (x_m - x_j)^-1
  *     mod l.  Shares that are not canonical are reduced.  The interpolation uses ALL shares handed in: more than t consistent shares give the
- *     same secret, fewer than t or one wrong share give another scalar and NO error -- the sharing is not verifiable (no Feldman
- *     commitments); what catches a wrong share is the check the reconstructed secret goes into (below);
+ *     same secret, fewer than t or one wrong share give another scalar and NO error -- reconstruction itself checks nothing; a wrong
+ *     share is found, and its holder named, by rofl_feldman_verify BEFORE the shares are interpolated (further below);
  *   self-mask (double masking): client i draws a fresh self-mask secret b_i every round; its seed is SHA3-256("rofl-zk/blind/v1/self" ||
  *     canonical32(b_i mod l) || u64le(round_no)) and its blinding vector is the pairwise vector plus +stream(self seed).  b_i is revealed
  *     for every survivor of a round, so it serves ONE round whatever round_no says;
@@ -382,7 +382,8 @@ int rofl_dh_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32 /* m
  *     The server collects, from at least t survivors, their shares of sk_j for every dropped j and of b_i for every survivor i,
  *     reconstructs both groups, builds the term list and hands it to rofl_acc_extract_opened_terms, which checks the opening against every
  *     R.  A wrong key is caught by comparing its public key, a wrong self secret by the failing R equations; neither names the survivor who
- *     lied.  The server must never reconstruct BOTH secrets of one client: sk_j opens the pairwise masks, b_j the self-mask, and together
+ *     lied -- checking every share against the dealers' commitments first (rofl_feldman_verify) does.  The server must never reconstruct
+ *     BOTH secrets of one client: sk_j opens the pairwise masks, b_j the self-mask, and together
  *     they open the client's update.
  * rofl_shamir_share: shares_out32[s][i] = f_s(xs[i]), secret-major; xs == NULL means the points 1 .. n_shares.  A call with a subset of the
  * points returns exactly the columns the whole call would: that is how ranks or chunks split a sharing.
@@ -399,6 +400,38 @@ int rofl_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t 
                       uint8_t *shares_out32 /* n_secrets x n_shares x 32, secret-major */);
 int rofl_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *xs /* n_shares, one set for all secrets */,
                             const uint8_t *shares32 /* n_secrets x n_shares x 32, secret-major */, uint8_t *secrets_out32);
+/* Verifiable secret sharing: Feldman commitments to the polynomial of a sharing, and one exact check per share against them.  With
+ * f(X) = s + sum_{k=1..t-1} a_k X^k mod l exactly as rofl_shamir_share defines it (the same reduction of the secret, the same
+ * "rofl-zk/share/v1" coefficient stream of the coefficient seed):
+ *   commitments of a secret: t Ristretto encodings, C_0 = encode((s mod l) B) and C_k = encode(a_k B) for k = 1 .. t - 1, B the base
+ *     rofl_dh_public_keys uses.  For a secret that is a DH key, C_0 is byte for byte its rofl_dh_public_keys output.  s = 0 mod l gives the
+ *     identity encoding (32 zero bytes), which is allowed, as Shamir allows a zero secret;
+ *   a share y at the point x (a nonzero uint32) is consistent iff (y mod l) B and sum_{k<t} x^k decode(C_k) are equal as Ristretto
+ *     elements.  Shares that are not canonical are reduced, as rofl_shamir_reconstruct reduces them;
+ *   verdict byte per (secret, share): 0 = consistent, 1 = not consistent, 2 = some commitment of that secret is not a canonical Ristretto
+ *     encoding -- the whole row of that secret gets 2 and nothing of it is compared.  The identity is a valid commitment here.
+ *   The equations are exact, one per share, without random weights (the choice of rofl_acc_extract_opened_terms): that is what lets the
+ *     call name the share that is wrong, and with it the survivor who handed it in or the dealer who dealt it.
+ * Feldman commitments reveal s B.  For a key that is its public key, public already.  For a self-mask secret b_i it is safe only because b_i
+ * is a fresh uniform 32-byte secret whose mask seed is a hash of it: nothing but b_i itself opens the mask, and s B does not give b_i.  Do not
+ * commit to a secret of low entropy.  How the commitments reach every client (they must come over an AUTHENTICATED broadcast: a dealer that
+ * shows different commitments to different clients defeats the check), how the shares travel, and what happens after a complaint stay the
+ * deployment's business.
+ * rofl_feldman_commit: commitments_out32[s][k] = C_k of secret s, secret-major.  rofl_feldman_verify: one set of points for all secrets
+ * (xs == NULL means 1 .. n_shares), verdict_out[s][i] for shares32[s][i] at xs[i]; threshold <= n_shares is NOT required -- a client checks
+ * the one share it received against t commitments.  Every commitment is decoded once, whatever the number of shares.  A call on a subset of
+ * the secrets, or of the points, returns exactly those rows or columns of the whole call.
+ * Host pointers only.  Both return 11 before the device is touched for: a null pointer (except xs), threshold = 0 or > 65536, an x of 0, two
+ * equal x (the text names the two positions), n_secrets > 65535, n_shares > 2^20, n_secrets x n_shares > 2^24, n_secrets x threshold > 2^22
+ * (the workspace of decoded commitments: split a larger round by secrets), n_shares = 0 with secrets; n_secrets = 0 returns 0 and touches no
+ * device.  Error texts never contain secret, seed or share bytes.  One lane: one upload, two launches, one download; commit overwrites its
+ * pinned staging copies and device workspace of secrets, seeds and coefficients with zeros before it returns or unwinds, verify those of
+ * the shares.  NOT constant-time.  The `devices` option does not apply. */
+int rofl_feldman_commit(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32 /* n_secrets x 32 */, size_t threshold,
+                        uint8_t *commitments_out32 /* n_secrets x threshold x 32, secret-major */);
+int rofl_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commitments32 /* n_secrets x threshold x 32, secret-major */,
+                        size_t n_shares, const uint32_t *xs /* NULL: 1 .. n_shares; one set for all secrets */,
+                        const uint8_t *shares32 /* n_secrets x n_shares x 32, secret-major */, uint8_t *verdict_out /* n_secrets x n_shares */);
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out);         /* conversion32.rs:49-54 */
 int rofl_uint_to_f32_vec(const uint64_t *in, size_t d, unsigned fp_bits, unsigned fp_frac, float *out);        /* conversion32.rs:41-47 */
 int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float *out);  /* conversion32.rs:62-64 */

@@ -138,6 +138,13 @@ int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint
 int rofl_dbg_host_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares,
                                const uint32_t *xs, uint8_t *shares_out32);
 int rofl_dbg_host_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *xs, const uint8_t *shares32, uint8_t *secrets_out32);
+/* rofl_feldman_commit / rofl_feldman_verify on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: the
+ * same parameters, the same checks (11) and the same bytes.  What the host tests pin the definition with, and the baseline of
+ * profiles/feldman_vss.json. */
+int rofl_dbg_host_feldman_commit(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold,
+                                 uint8_t *commitments_out32);
+int rofl_dbg_host_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commitments32, size_t n_shares, const uint32_t *xs,
+                                 const uint8_t *shares32, uint8_t *verdict_out);
 
 /* host micro-benchmarks of the code the per-round hops run (nanoseconds per operation on the calling core).
  * what: 0 Keccak-f[1600]; 1 point doubling, 2 point addition, 3 Ristretto encoding (51-bit host arithmetic);

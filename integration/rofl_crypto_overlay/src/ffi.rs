@@ -179,6 +179,18 @@ extern "C" {
     pub fn rofl_dbg_host_shamir_share(n_secrets: usize, secrets32: *const u8, coef_seeds32: *const u8, threshold: usize, n_shares: usize,
         xs: *const u32, shares_out32: *mut u8) -> c_int;
     pub fn rofl_dbg_host_shamir_reconstruct(n_secrets: usize, n_shares: usize, xs: *const u32, shares32: *const u8, secrets_out32: *mut u8) -> c_int;
+    /// Feldman commitments of the sharing polynomials of rofl_shamir_share: commitments_out32[s][k] = encode(a_k B), a_0 = the secret mod l,
+    /// secret-major, `threshold` per secret; C_0 of a DH key is its public key
+    pub fn rofl_feldman_commit(n_secrets: usize, secrets32: *const u8, coef_seeds32: *const u8, threshold: usize, commitments_out32: *mut u8) -> c_int;
+    /// verdict_out[s][i] for shares32[s][i] at xs[i] (null = 1 .. n_shares) against the commitments of secret s: 0 consistent, 1 not, 2 = a
+    /// commitment of that secret is not a canonical encoding (the whole row)
+    pub fn rofl_feldman_verify(n_secrets: usize, threshold: usize, commitments32: *const u8, n_shares: usize, xs: *const u32, shares32: *const u8,
+        verdict_out: *mut u8) -> c_int;
+    /// include/rofl_zk_debug.h: the two calls above on the host's arithmetic, one thread, no GPU -- same parameters, same bytes
+    pub fn rofl_dbg_host_feldman_commit(n_secrets: usize, secrets32: *const u8, coef_seeds32: *const u8, threshold: usize,
+        commitments_out32: *mut u8) -> c_int;
+    pub fn rofl_dbg_host_feldman_verify(n_secrets: usize, threshold: usize, commitments32: *const u8, n_shares: usize, xs: *const u32,
+        shares32: *const u8, verdict_out: *mut u8) -> c_int;
     pub fn rofl_f32_to_fp_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut u64) -> c_int;
     pub fn rofl_uint_to_f32_vec(input: *const u64, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
     pub fn rofl_get_l2_clip_bounds(range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;

@@ -150,7 +150,7 @@ pub fn shamir_share(secrets: &[[u8; 32]], coef_seeds: &[[u8; 32]], threshold: us
     out.chunks(n_shares.max(1)).map(|r| r.to_vec()).collect()
 }
 /// The secrets from `shares` (row s: the shares of secret s at the points `xs`, one set of points for all rows): interpolation at 0 over
-/// ALL shares handed in.  Not verifiable: a wrong share gives another secret, not an error.
+/// ALL shares handed in.  Checks nothing: a wrong share gives another secret, not an error -- check the shares with rofl_feldman_verify first.
 pub fn shamir_reconstruct(xs: &[u32], shares: &[Vec<[u8; 32]>]) -> Vec<[u8; 32]> {
     assert!(shares.iter().all(|r| r.len() == xs.len()), "one share per point");
     let flat: Vec<[u8; 32]> = shares.iter().flat_map(|r| r.iter().copied()).collect();

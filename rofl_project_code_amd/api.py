@@ -997,8 +997,11 @@ class secret_sharing:
     key-agreement key and its per-round self-mask secret.  A secret is 32 bytes, reduced mod l (zero is allowed); with the 32-byte coefficient
     seed c and threshold t it defines f(X) = s + sum_{k=1..t-1} a_k X^k, a_k = scalar k - 1 of the stream of c under the label
     "rofl-zk/share/v1"; the share for the point x (a nonzero uint32; client i holds x = i + 1) is f(x), canonical.  Any t shares determine
-    the secret, t - 1 determine nothing.  A coefficient seed is as secret as the secret it shares.  The sharing is not verifiable: a wrong
-    share reconstructs another scalar without an error.  Not constant-time."""
+    the secret, t - 1 determine nothing.  A coefficient seed is as secret as the secret it shares.  reconstruct() checks nothing: a wrong
+    share reconstructs another scalar without an error.  commit() publishes Feldman commitments of the polynomial and verify_shares() checks
+    every share against them, one exact equation per share, so a wrong share is named before it is interpolated
+    (rofl_feldman_commit / rofl_feldman_verify).  The authenticated broadcast of the commitments, the transport of the shares and any
+    complaint protocol are the deployment's.  Not constant-time."""
 
     @staticmethod
     def share(secrets, coef_seeds, threshold, n_shares, xs=None):
@@ -1041,6 +1044,58 @@ class secret_sharing:
             _check(lib().rofl_shamir_reconstruct(_sz(n), _sz(n_shares), _ptr(x), buf, _ptr(out)))
         finally:
             ctypes.memset(buf, 0, ctypes.sizeof(buf))
+        return out
+
+    @staticmethod
+    def commit(secrets, coef_seeds, threshold):
+        """Feldman commitments of the polynomials share() evaluates (rofl_feldman_commit) -> uint8[n_secrets, threshold, 32]:
+        [s, 0] = encode((secret mod l) B), [s, k] = encode(a_k B).  For a DH key, [s, 0] is its key_agreement.public_keys output.  The
+        commitments reveal secret * B: commit only to keys and to fresh uniform secrets."""
+        sec, seeds = _keys32(secrets, "a secret"), _keys32(coef_seeds, "a coefficient seed")
+        n, threshold = sec.shape[0], int(threshold)
+        if seeds.shape[0] != n:
+            raise ValueError("one coefficient seed per secret")
+        if n and threshold < 1:
+            raise ValueError("the threshold is at least 1")
+        out = np.zeros((n, max(threshold, 0), 32), dtype=np.uint8)
+        bs, bc = (ctypes.c_ubyte * max(n * 32, 1))(), (ctypes.c_ubyte * max(n * 32, 1))()
+        try:
+            ctypes.memmove(bs, sec.ctypes.data, n * 32)
+            ctypes.memmove(bc, seeds.ctypes.data, n * 32)
+            _check(lib().rofl_feldman_commit(_sz(n), bs, bc, _sz(threshold), _ptr(out)))
+        finally:
+            ctypes.memset(bs, 0, ctypes.sizeof(bs))
+            ctypes.memset(bc, 0, ctypes.sizeof(bc))
+        return out
+
+    @staticmethod
+    def verify_shares(commitments, xs, shares):
+        """Every share uint8[n_secrets, len(xs), 32] at the points xs (one set for all secrets) against the commitments
+        uint8[n_secrets, t, 32] of its secret (rofl_feldman_verify) -> uint8[n_secrets, len(xs)] verdicts: 0 = consistent, 1 = not, 2 = a
+        commitment of that secret is not a canonical Ristretto encoding (the whole row).  len(xs) may be below t: a client checks the one
+        share it received.  A call on a subset of the secrets or of the points returns those rows or columns of the whole call."""
+        n_shares = int(np.asarray(xs).shape[0]) if np.asarray(xs).ndim == 1 else -1
+        x = _xs32(xs, n_shares)
+        cm, sh = np.asarray(commitments, dtype=np.uint8), np.asarray(shares, dtype=np.uint8)
+        if cm.ndim != 3 or cm.shape[2] != 32:
+            raise ValueError("commitments are uint8[n_secrets, threshold, 32]")
+        n, t = cm.shape[0], cm.shape[1]
+        if sh.ndim != 3 or sh.shape != (n, n_shares, 32):
+            raise ValueError("shares are uint8[n_secrets, len(xs), 32]")
+        if n and n_shares == 0:
+            raise ValueError("secrets without shares")
+        if n and t < 1:
+            raise ValueError("the threshold is at least 1")
+        out = np.zeros((n, n_shares), dtype=np.uint8)
+        cm, src = np.ascontiguousarray(cm), np.ascontiguousarray(sh)      # (held by name: a temporary copy would be gone before it is read)
+        buf = (ctypes.c_ubyte * max(n * n_shares * 32, 1))()
+        try:
+            ctypes.memmove(buf, src.ctypes.data, n * n_shares * 32)
+            _check(lib().rofl_feldman_verify(_sz(n), _sz(t), _ptr(cm), _sz(n_shares), _ptr(x), buf, _ptr(out)))
+        finally:
+            ctypes.memset(buf, 0, ctypes.sizeof(buf))
+            if src is not sh:
+                src[...] = 0
         return out
 
 
@@ -1357,7 +1412,8 @@ class pedersen_ops:
         (client i holds i + 1), key_shares = {j: uint8[len(xs), 32]} the shares of sk_j for every dropped j, self_shares = {i: ...} the
         shares of b_i for every survivor i.  ALL secrets come from ONE rofl_shamir_reconstruct call (dropped keys first, then the survivors'
         self secrets, the same xs).  A wrong key share raises ValueError naming the dropped client (the public-key check); a wrong self share
-        gives terms whose opening extract_opened refuses (ok = 0).  Neither names the survivor who lied."""
+        gives terms whose opening extract_opened refuses (ok = 0).  Neither names the survivor who lied:
+        dropout_residual_terms_from_verified_shares does, and goes on without that survivor."""
         surv, drop = [int(i) for i in survivors], sorted(int(j) for j in dropped)
         key_shares = {int(j): v for j, v in key_shares.items()}
         self_shares = {int(i): v for i, v in self_shares.items()}
@@ -1387,6 +1443,72 @@ class pedersen_ops:
                                                        {i: sec[len(drop) + r].tobytes() for r, i in enumerate(sorted(surv))}, public_keys, round_no)
         finally:
             sec[...] = 0
+
+    @staticmethod
+    def dropout_residual_terms_from_verified_shares(survivors, dropped, xs, key_shares, self_shares, key_commitments, self_commitments, public_keys,
+                                                    round_no):
+        """dropout_residual_terms_from_shares behind a check of every share against its dealer's Feldman commitments
+        (secret_sharing.commit): key_commitments = {j: uint8[t, 32]} for every dropped j, self_commitments = {i: uint8[t, 32]} for every
+        survivor i, the rest as there.  -> (terms, liars).  First key_commitments[j][0] must BE public_keys[j] (the constant-term commitment
+        of a key is its public key; ValueError naming j otherwise).  Then ALL shares of all secrets go through ONE verify_shares call, in
+        the order ..._from_shares stacks them (dropped keys first, then the survivors' self secrets).  An answering survivor with any
+        verdict other than 0 in its column is a liar: its column is removed for every secret, and the remaining columns go to
+        dropout_residual_terms_from_shares; liars = the sorted client indices (x - 1) of the removed columns.  Fewer than t columns left
+        raises ValueError naming the liars; commitments that are no canonical encodings (verdict 2) raise ValueError naming the dealer."""
+        surv, drop = [int(i) for i in survivors], sorted(int(j) for j in dropped)
+        key_shares = {int(j): v for j, v in key_shares.items()}
+        self_shares = {int(i): v for i, v in self_shares.items()}
+        key_commitments = {int(j): np.asarray(v, dtype=np.uint8) for j, v in key_commitments.items()}
+        self_commitments = {int(i): np.asarray(v, dtype=np.uint8) for i, v in self_commitments.items()}
+        both = (set(key_shares) & set(self_shares)) | (set(surv) & set(drop))
+        if both:
+            raise ValueError("client %d: its key and its self-mask secret are never opened together" % min(both))
+        for j in drop:
+            if j not in key_shares:
+                raise ValueError("dropped client %d has no key shares" % j)
+            if j not in key_commitments:
+                raise ValueError("dropped client %d has no key commitments" % j)
+        for i in surv:
+            if i not in self_shares:
+                raise ValueError("survivor %d has no self-mask shares" % i)
+            if i not in self_commitments:
+                raise ValueError("survivor %d has no self-mask commitments" % i)
+        order = [(key_shares, key_commitments, j) for j in drop] + [(self_shares, self_commitments, i) for i in sorted(surv)]
+        x = np.asarray(xs)
+        n_sh = int(x.shape[0])
+        if not order:
+            return pedersen_ops.dropout_residual_terms_from_shares(surv, drop, xs, key_shares, self_shares, public_keys, round_no), []
+        t = int(order[0][1][order[0][2]].shape[0])
+        pk = _keys32(public_keys, "a public key")
+        for _, com, c in order:
+            if com[c].ndim != 2 or com[c].shape != (t, 32) or t < 1:
+                raise ValueError("the commitments of client %d are uint8[t, 32], one t for the round" % c)
+        for j in drop:
+            if not 0 <= j < pk.shape[0] or key_commitments[j][0].tobytes() != pk[j].tobytes():
+                raise ValueError("client %d: the constant-term commitment of its key is not its public key" % j)
+        stack = np.zeros((len(order), n_sh, 32), dtype=np.uint8)
+        try:
+            for r, (src, _, c) in enumerate(order):
+                a = np.asarray(src[c], dtype=np.uint8)
+                if a.shape != (n_sh, 32):
+                    raise ValueError("the shares of client %d are uint8[len(xs), 32]" % c)
+                stack[r] = a
+            verdict = secret_sharing.verify_shares(np.stack([com[c] for _, com, c in order]), xs, stack)
+        finally:
+            stack[...] = 0
+        for r, (_, _, c) in enumerate(order):
+            if (verdict[r] == 2).any():
+                raise ValueError("client %d: a commitment of its dealing is not a canonical Ristretto encoding" % c)
+        bad = (verdict != 0).any(axis=0)
+        liars = sorted(int(x[c]) - 1 for c in np.flatnonzero(bad))
+        keep = np.flatnonzero(~bad)
+        if keep.size < t:
+            raise ValueError("survivors %r handed in shares that fail their commitments: %d consistent columns left, the threshold is %d"
+                             % (liars, keep.size, t))
+        terms = pedersen_ops.dropout_residual_terms_from_shares(
+            surv, drop, x[keep], {j: np.asarray(key_shares[j], dtype=np.uint8)[keep] for j in drop},
+            {i: np.asarray(self_shares[i], dtype=np.uint8)[keep] for i in surv}, public_keys, round_no)
+        return terms, liars
 
     # ---- a round that rejects: the terms of the accepted set's residual blinding (accumulator.extract_opened_terms) ----
     @staticmethod

@@ -2577,6 +2577,62 @@ __global__ void __launch_bounds__(TPB) k_shamir_combine(u32 n, const sc *__restr
     if (threadIdx.x == 0) store_sc(&out[blockIdx.x], v[0]);
 }
 #endif
+// ================================================================ verifiable sharing (rofl_feldman_commit / rofl_feldman_verify)
+// Feldman commitments to the polynomial of a Shamir sharing: C_0 = encode((s mod l) B), C_k = encode(a_k B), B the base of tabB8 (the base of
+// k_dh_public: C_0 of a key is its public key).  The share y at the point x is consistent iff (y mod l) B == sum_k x^k decode(C_k) as
+// Ristretto elements.  Not constant-time, like every secret-scalar path here.
+#if ROFL_KG(4)
+// out[s][k] = C_k of secret s, one thread per (secret, k), flat index with k fastest: k_dh_public with the scalar taken from the secrets
+// (k = 0, reduced) or from the workspace k_shamir_coeffs filled (coef[s][k - 1], canonical).  A zero scalar gives the identity encoding.
+__global__ void __launch_bounds__(64) k_feldman_commit(u32 n_secrets, u32 t, const sc *__restrict__ secrets, const sc *__restrict__ coef /* [n_secrets][t - 1] */,
+                                                       const niels *tabB8, uint8_t *__restrict__ out /* [n_secrets][t][32] */) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_secrets * t) return;
+    const u32 s = i / t, k = i - s * t;
+    const sc v = k == 0 ? load_sc_reduced(&secrets[s]) : load_sc(&coef[(size_t)s * (t - 1) + (k - 1)]);
+    sg_encode(out + (size_t)32 * i, sg_fixed_mul8(tabB8, v));
+}
+#endif
+#if ROFL_KG(3)
+// verdict[s][i] for the share y = shares[s][i] at the point x_i (xs == nullptr: i + 1): one thread per (secret, share), flat index with the
+// share fastest, so a wave of a secret with >= 64 shares reads each decoded commitment (cpts[s][k], k_dh_decode's workspace) at one address
+// and with few shares per secret the lanes of a wave span secrets.  A row with a commitment of status 1 (not a canonical encoding; 2, the
+// identity, is a valid commitment here) stores 2 and compares nothing.  Otherwise Horner's rule on points from the top: acc = C_{t-1}, then
+// acc = [x] acc + C_k for k = t - 2 .. 0, where [x] acc is an MSB-first double-and-add over xbits = the bit length of the call's LARGEST point
+// (computed by the host): every lane runs the same xbits - 1 doublings, the addition on a set bit runs under the lane's mask, and a lane whose
+// leading bits are zero doubles the identity (the unified formulas are complete).  The top bit selects the start, acc or the identity, so a
+// step is xbits - 1 doublings, up to xbits - 1 additions and the addition of C_k.  Then (y mod l) B from the radix-256 table and the two cross
+// products of Ristretto equality (k_acc_open): 0 consistent, 1 not.  t = 1 runs no step.  The decoded commitments are read straight from
+// global memory, one packed point (128 bytes) per step against 8 (xbits - 1) + 9 (set bits + 1) field multiplications: the kernel is
+// arithmetic-bound ("Create side, verifiable sharing"), so nothing is staged through LDS.
+__global__ void __launch_bounds__(64) k_feldman_check(u32 n_secrets, u32 n_shares, u32 t, u32 xbits, const u32 *__restrict__ xs, const ge *__restrict__ cpts /* [n_secrets][t] */,
+                                                      const u32 *__restrict__ cstatus /* [n_secrets][t] */, const sc *__restrict__ shares /* [n_secrets][n_shares] */,
+                                                      const niels *tabB8, uint8_t *__restrict__ verdict /* [n_secrets][n_shares] */) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_secrets * n_shares) return;
+    const u32 s = i / n_shares, j = i - s * n_shares;
+    const ge *cp = cpts + (size_t)s * t;
+    const u32 *st = cstatus + (size_t)s * t;
+    bool refused = false;
+    for (u32 k = 0; k < t; k++) refused |= st[k] == 1u;
+    if (refused) { verdict[i] = 2; return; }
+    const u32 x = xs ? xs[j] : j + 1;
+    const bool top = (x >> (xbits - 1)) & 1u;
+    gd acc = load_gd(&cp[t - 1]);
+    for (u32 k = t - 1; k-- > 0;) {
+        gd r = gd_identity();
+        if (top) r = acc;
+        for (u32 b = xbits - 1; b-- > 0;) {
+            r = gd_double(r);
+            if ((x >> b) & 1u) r = gd_add(r, acc);
+        }
+        acc = gd_add(r, load_gd(&cp[k]));
+    }
+    const gd P = sg_fixed_mul8(tabB8, load_sc_reduced(&shares[i]));
+    const bool same = fd_eq(fd_mul(acc.X, P.Y), fd_mul(acc.Y, P.X)) || fd_eq(fd_mul(acc.Y, P.Y), fd_mul(acc.X, P.X));
+    verdict[i] = same ? 0 : 1;
+}
+#endif
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(TPB) k_sigma_finish_batch(int kind, u32 d, u32 fp_bits, u32 fp_frac, const SgClient *cl, DMerlin init, u32 *status /* [gridDim.y] */) {
     const SgClient &c = cl[blockIdx.y];

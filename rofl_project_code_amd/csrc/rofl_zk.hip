@@ -2671,6 +2671,162 @@ int rofl_dbg_host_shamir_reconstruct(size_t n_secrets, size_t n_shares, const ui
     }
     return ROFL_OK;
 }
+// ---- verifiable sharing: Feldman commitments to the polynomials above, one exact equation per share (k_feldman_commit, k_dh_decode, k_feldman_check) ----
+}  // extern "C"
+namespace {
+// every check of rofl_feldman_commit / rofl_feldman_verify, shared with their host routes; *done: the call is empty and returns 0
+int feldman_commit_check(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, const uint8_t *commitments_out32, bool *done) {
+    *done = n_secrets == 0;
+    if (*done) return ROFL_OK;
+    if (!secrets32 || !coef_seeds32 || !commitments_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (threshold == 0) return fail(ROFL_BAD_PARAM, "the threshold is at least 1");
+    if (threshold > 65536) return fail(ROFL_BAD_PARAM, "a threshold above 65536");
+    if (n_secrets > 65535) return fail(ROFL_BAD_PARAM, "more than 65535 secrets in one call");
+    if (n_secrets * threshold > ((size_t)1 << 22)) return fail(ROFL_BAD_PARAM, "more than 2^22 commitments in one call");
+    return ROFL_OK;
+}
+int feldman_verify_check(size_t n_secrets, size_t threshold, const uint8_t *commitments32, size_t n_shares, const uint32_t *xs, const uint8_t *shares32,
+                         const uint8_t *verdict_out, bool *done) {
+    *done = n_secrets == 0;
+    if (*done) return ROFL_OK;
+    if (!commitments32 || !shares32 || !verdict_out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_shares == 0) return fail(ROFL_BAD_PARAM, "secrets without shares");
+    if (threshold == 0) return fail(ROFL_BAD_PARAM, "the threshold is at least 1");
+    if (threshold > 65536) return fail(ROFL_BAD_PARAM, "a threshold above 65536");
+    if (n_secrets > 65535) return fail(ROFL_BAD_PARAM, "more than 65535 secrets in one call");
+    if (n_shares > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 shares of a secret in one call");
+    if (n_secrets * n_shares > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 shares in one call");
+    if (n_secrets * threshold > ((size_t)1 << 22)) return fail(ROFL_BAD_PARAM, "more than 2^22 commitments in one call");
+    return xs ? shamir_check_xs(n_shares, xs) : ROFL_OK;
+}
+// bit length of the largest evaluation point of a call (>= 1: the points are nonzero)
+u32 feldman_xbits(size_t n_shares, const uint32_t *xs) {
+    uint32_t mx = xs ? 0 : (uint32_t)n_shares;
+    for (size_t i = 0; xs && i < n_shares; i++) mx = std::max(mx, xs[i]);
+    u32 b = 0; while (b < 32 && mx >> b) b++;
+    return b;
+}
+}  // namespace
+extern "C" {
+// The lane's copies of the secrets, the coefficient seeds and the coefficients -- pinned staging and device workspace -- are overwritten with
+// zeros before the call returns or unwinds; the commitments are public.
+int rofl_feldman_commit(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, uint8_t *commitments_out32) {
+    bool done;
+    if (int rc = feldman_commit_check(n_secrets, secrets32, coef_seeds32, threshold, commitments_out32, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: [secrets | coefficient seeds]; workspace: the coefficients; download: the commitments, secret-major
+        const size_t m = threshold - 1, up_bytes = n_secrets * 64, n_com = n_secrets * threshold, dn_bytes = n_com * 32;
+        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        sc *coef = C.tmp_in2.as<sc>(std::max<size_t>(n_secrets * m, 1));
+        BlindWipe wipe_in, wipe_coef;
+        wipe_in.h = hu; wipe_in.dv = du; wipe_in.n = up_bytes; wipe_in.s = C.stream;
+        wipe_coef.dv = reinterpret_cast<uint8_t *>(coef); wipe_coef.n = n_secrets * m * 32; wipe_coef.s = C.stream;
+        memcpy(hu, secrets32, n_secrets * 32); memcpy(hu + n_secrets * 32, coef_seeds32, n_secrets * 32);
+        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
+        if (m) ROFL_LAUNCH(k_shamir_coeffs, grid1((m + 1) / 2, (u32)n_secrets), dim3(TPB), 0, C.stream, (u32)m, reinterpret_cast<const u64 *>(du + n_secrets * 32), coef);
+        ROFL_LAUNCH(k_feldman_commit, dim3((unsigned)((n_com + 63) / 64)), dim3(64), 0, C.stream, (u32)n_secrets, (u32)threshold, reinterpret_cast<const sc *>(du), (const sc *)coef,
+                    C.d_tabB8, dd);
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(commitments_out32, hd, dn_bytes);
+        return ROFL_OK;
+    });
+}
+// The lane's copies of the shares are overwritten with zeros before the call returns or unwinds; commitments, points and verdicts are public.
+int rofl_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commitments32, size_t n_shares, const uint32_t *xs, const uint8_t *shares32,
+                        uint8_t *verdict_out) {
+    bool done;
+    if (int rc = feldman_verify_check(n_secrets, threshold, commitments32, n_shares, xs, shares32, verdict_out, &done)) return rc;
+    if (done) return ROFL_OK;
+    const u32 xbits = feldman_xbits(n_shares, xs);
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: [shares, secret-major | commitments, secret-major | points]; workspace: the decoded commitments and their status words;
+        // download: the verdict bytes
+        const size_t n_pairs = n_secrets * n_shares, n_com = n_secrets * threshold, up_com = n_pairs * 32, up_xs = up_com + n_com * 32;
+        const size_t up_bytes = up_xs + (xs ? n_shares * 4 : 0);
+        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(n_pairs), *dd = C.tmp_out.as<uint8_t>(n_pairs);
+        ge *pts = C.aux_pts.as<ge>(n_com); u32 *pst = C.status.as<u32>(n_com);
+        BlindWipe wipe_in;
+        wipe_in.h = hu; wipe_in.dv = du; wipe_in.n = up_com; wipe_in.s = C.stream;
+        memcpy(hu, shares32, up_com); memcpy(hu + up_com, commitments32, n_com * 32);
+        if (xs) memcpy(hu + up_xs, xs, n_shares * 4);
+        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_com + 63) / 64)), dim3(64), 0, C.stream, (u32)n_com, (const uint8_t *)(du + up_com), pts, pst);
+        ROFL_LAUNCH(k_feldman_check, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_secrets, (u32)n_shares, (u32)threshold, xbits,
+                    xs ? reinterpret_cast<const u32 *>(du + up_xs) : (const u32 *)nullptr, (const ge *)pts, (const u32 *)pst, reinterpret_cast<const sc *>(du), C.d_tabB8, dd);
+        HIPCHK(hipMemcpyAsync(hd, dd, n_pairs, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(verdict_out, hd, n_pairs);
+        return ROFL_OK;
+    });
+}
+// the two calls on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: same parameters, same checks, same bytes
+int rofl_dbg_host_feldman_commit(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, uint8_t *commitments_out32) {
+    bool done;
+    if (int rc = feldman_commit_check(n_secrets, secrets32, coef_seeds32, threshold, commitments_out32, &done)) return rc;
+    if (done) return ROFL_OK;
+    const size_t m = threshold - 1;
+    const u64 dom[2] = ROFL_SHARE_DOM;
+    ge Bg; ristretto_decode(Bg, kDhBase);
+    const h51::ge5 B = h51::from_ge(Bg);
+    std::vector<sc> coef(m + 2);      // [s mod l | a_1 .. a_{t-1}] and room for one past the end
+    for (size_t s = 0; s < n_secrets; s++) {
+        u64 sd[4], st[25]; memcpy(sd, coef_seeds32 + 32 * s, 32);
+        coef[0] = dh_key_scalar(secrets32 + 32 * s);
+        for (size_t blk = 0; 2 * blk < m; blk++) {
+            shake256_seeded_block(st, dom, sd, blk);
+            coef[1 + 2 * blk] = xof_block_scalar(st, 0); coef[2 + 2 * blk] = xof_block_scalar(st, 1);
+        }
+        for (size_t k = 0; k < threshold; k++) h51::encode(commitments_out32 + (s * threshold + k) * 32, dh_host_mul(coef[k], B));
+        dh_wipe(sd, sizeof sd); dh_wipe(st, sizeof st);
+    }
+    dh_wipe(coef.data(), coef.size() * sizeof(sc));
+    return ROFL_OK;
+}
+int rofl_dbg_host_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commitments32, size_t n_shares, const uint32_t *xs, const uint8_t *shares32,
+                                 uint8_t *verdict_out) {
+    bool done;
+    if (int rc = feldman_verify_check(n_secrets, threshold, commitments32, n_shares, xs, shares32, verdict_out, &done)) return rc;
+    if (done) return ROFL_OK;
+    ge Bg; ristretto_decode(Bg, kDhBase);
+    const h51::ge5 B = h51::from_ge(Bg);
+    std::vector<h51::ge5> cp(threshold);
+    for (size_t s = 0; s < n_secrets; s++) {
+        bool refused = false;
+        for (size_t k = 0; k < threshold; k++) {
+            ge P;
+            if (!ristretto_decode(P, commitments32 + (s * threshold + k) * 32)) { refused = true; break; }
+            cp[k] = h51::from_ge(P);
+        }
+        uint8_t *vd = verdict_out + s * n_shares;
+        if (refused) { memset(vd, 2, n_shares); continue; }
+        for (size_t i = 0; i < n_shares; i++) {
+            const u32 x = xs ? xs[i] : (u32)(i + 1);
+            h51::ge5 acc = cp[threshold - 1];
+            for (size_t k = threshold - 1; k-- > 0;) {      // acc = [x] acc + C_k, MSB-first over the bits of x
+                h51::ge5 r = h51::identity();
+                for (int b = 32; b-- > 0;) {
+                    if (x >> b >> 1) r = h51::gdouble(r);      // (nothing to double above the top bit)
+                    if ((x >> b) & 1u) r = h51::gadd(r, acc);
+                }
+                acc = h51::gadd(r, cp[k]);
+            }
+            sc y = dh_key_scalar(shares32 + (s * n_shares + i) * 32);
+            const h51::ge5 P = dh_host_mul(y, B);
+            dh_wipe(&y, sizeof y);
+            const bool same = h51::eq(h51::mul(acc.X, P.Y), h51::mul(acc.Y, P.X)) || h51::eq(h51::mul(acc.Y, P.Y), h51::mul(acc.X, P.X));
+            vd[i] = same ? 0 : 1;
+        }
+    }
+    return ROFL_OK;
+}
 // conversion32::f32_to_fp_vec / uint_to_f32_vec (conversion32.rs:41-54): Fix is unsigned, negative inputs saturate to 0
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out) {
     if (!valid_fp(fp_bits, fp_frac)) return fail(ROFL_BAD_PARAM, "bad parameter");

@@ -414,9 +414,10 @@ int rofl_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *x
  *     call name the share that is wrong, and with it the survivor who handed it in or the dealer who dealt it.
  * Feldman commitments reveal s B.  For a key that is its public key, public already.  For a self-mask secret b_i it is safe only because b_i
  * is a fresh uniform 32-byte secret whose mask seed is a hash of it: nothing but b_i itself opens the mask, and s B does not give b_i.  Do not
- * commit to a secret of low entropy.  How the commitments reach every client (they must come over an AUTHENTICATED broadcast: a dealer that
- * shows different commitments to different clients defeats the check), how the shares travel, and what happens after a complaint stay the
- * deployment's business.
+ * commit to a secret of low entropy.  The commitments must come over an AUTHENTICATED broadcast: a dealer that shows different commitments
+ * to different clients defeats the check.  rofl_sig_sign / rofl_sig_verify (further below) are that authentication: every dealer signs its
+ * commitments, every client signs its view of everybody's, and a dealer that equivocated is named by the view round.  How the bytes travel,
+ * how the shares travel, and what happens after a complaint stay the deployment's business.
  * rofl_feldman_commit: commitments_out32[s][k] = C_k of secret s, secret-major.  rofl_feldman_verify: one set of points for all secrets
  * (xs == NULL means 1 .. n_shares), verdict_out[s][i] for shares32[s][i] at xs[i]; threshold <= n_shares is NOT required -- a client checks
  * the one share it received against t commitments.  Every commitment is decoded once, whatever the number of shares.  A call on a subset of
@@ -432,6 +433,45 @@ int rofl_feldman_commit(size_t n_secrets, const uint8_t *secrets32, const uint8_
 int rofl_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commitments32 /* n_secrets x threshold x 32, secret-major */,
                         size_t n_shares, const uint32_t *xs /* NULL: 1 .. n_shares; one set for all secrets */,
                         const uint8_t *shares32 /* n_secrets x n_shares x 32, secret-major */, uint8_t *verdict_out /* n_secrets x n_shares */);
+/* Signatures: deterministic Schnorr signatures over Ristretto255, created and verified in batches, one exact verdict per signature.  They
+ * are what makes the broadcast of public keys and Feldman commitments authenticated in a round that a server relays.  Every label below is
+ * exactly 16 bytes; || is concatenation; B is the base rofl_dh_public_keys uses.
+ *   message digest: h(m) = SHAKE256("rofl-zk/sig/v1/m" || u64le(len(m)) || m)[0 .. 32), for any length, 0 included;
+ *   key: 32 bytes read as a little-endian integer and reduced mod l: a.  a = 0 mod l is refused (11; the text names the index, never the
+ *     bytes).  The public key is A = encode(a B), the bytes rofl_dh_public_keys gives for the same input;
+ *   nonce: k = int_le(SHAKE256("rofl-zk/sig/v1/k" || canonical32(a) || h)[0 .. 64)) mod l (80 bytes, one Keccak block); k = 0 is not
+ *     special-cased;
+ *   signature: R = encode(k B), c = int_le(SHAKE256("rofl-zk/sig/v1/c" || R || A || h)[0 .. 64)) mod l (112 bytes, one block),
+ *     s = k + c a mod l; the signature is R || canonical32(s), 64 bytes.  It is deterministic: the same key and message give the same bytes;
+ *   verdict byte per signature, a malformed input before a failing equation:
+ *     2 = the key is not a canonical Ristretto encoding or is the identity, or s >= l;
+ *     0 = encode(s B - c decode(A)) equals the 32 bytes R, with c recomputed from R, A and h;
+ *     1 = anything else (an R that is no canonical encoding therefore simply gives 1).
+ *   A refused key condemns its signatures, not the call: every other signature is unaffected, as with rofl_dh_shared.  The check is exact,
+ *   one equation per signature and no random weights (the choice of rofl_feldman_verify, for the same reason): the verdict names the signer.
+ * Messages are packed back to back: message j is msg_bytes[msg_off[j] .. msg_off[j + 1]).  Signature i uses key refs[i].key and message
+ * refs[i].msg; refs == NULL means key i and message i and requires n_keys == n_msgs == n.  Every message is hashed once and every key
+ * multiplied out or decoded once, whatever the number of signatures that refer to it.  pk_out32 (may be NULL) receives the n_keys public
+ * keys.  Host pointers only.  Both return 11 before the device is touched for: a null pointer (except refs, pk_out32, and msg_bytes when the
+ * total length is 0), msg_off[0] != 0 or offsets that decrease, a total message length above 2^30, n_keys or n_msgs above 2^20 (or 0 with
+ * n > 0), n above 2^24, a ref index out of range, refs == NULL with unequal counts, and for sign a key that is 0 mod l; n = 0 returns 0 and
+ * touches no device.  Error texts never contain key bytes.  One lane: one upload, three launches (digests; public keys or key decoding; sign
+ * or verify), one download.  rofl_sig_sign overwrites its pinned staging copies and the device workspace that held the keys with zeros before
+ * it returns or unwinds; the nonces live in registers only.  The `devices` option does not apply.
+ * What is NOT promised: the paths are NOT constant-time, like every other secret-scalar path of this library.  The nonce is deterministic: no
+ * randomness is needed and none is mixed in, so a fault injected into one of two runs on the same input can leak the key -- sign on hardware
+ * you trust.  A deployment uses a signing key of ITS OWN, never its DH key: the DH key is revealed when its owner drops out, and whoever
+ * holds it then signs in its owner's name.  What signatures give a round: the sender of a key or of commitments is authenticated, and the
+ * view round (every client signs the digest of all dealers' signatures it saw; secret_sharing.view_message in the Python binding) makes
+ * equivocation DETECTABLE and names the client that was shown something else.  What they do not give: who of dealer and relay equivocated
+ * (both signatures on two different commitment sets convict the dealer, one does not convict the relay), what happens after (the complaint
+ * protocol), the transport and the round's state machine -- those stay the deployment's. */
+typedef struct { uint32_t key, msg; } rofl_sig_ref_t;
+int rofl_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32 /* may be NULL */,
+                  size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off /* n_msgs + 1 */,
+                  size_t n, const rofl_sig_ref_t *refs /* NULL: (i, i) */, uint8_t *sig_out64 /* n x 64 */);
+int rofl_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off /* n_msgs + 1 */,
+                    size_t n, const rofl_sig_ref_t *refs /* NULL: (i, i) */, const uint8_t *sig64 /* n x 64 */, uint8_t *verdict_out /* n */);
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out);         /* conversion32.rs:49-54 */
 int rofl_uint_to_f32_vec(const uint64_t *in, size_t d, unsigned fp_bits, unsigned fp_frac, float *out);        /* conversion32.rs:41-47 */
 int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float *out);  /* conversion32.rs:62-64 */

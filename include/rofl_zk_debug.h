@@ -145,6 +145,13 @@ int rofl_dbg_host_feldman_commit(size_t n_secrets, const uint8_t *secrets32, con
                                  uint8_t *commitments_out32);
 int rofl_dbg_host_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commitments32, size_t n_shares, const uint32_t *xs,
                                  const uint8_t *shares32, uint8_t *verdict_out);
+/* rofl_sig_sign / rofl_sig_verify on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: the same
+ * parameters, the same checks (11) and the same bytes.  What the host tests pin the definition with, and the baseline of
+ * profiles/signatures.json. */
+int rofl_dbg_host_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32, size_t n_msgs, const uint8_t *msg_bytes,
+                           const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs, uint8_t *sig_out64);
+int rofl_dbg_host_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,
+                             size_t n, const rofl_sig_ref_t *refs, const uint8_t *sig64, uint8_t *verdict_out);
 
 /* host micro-benchmarks of the code the per-round hops run (nanoseconds per operation on the calling core).
  * what: 0 Keccak-f[1600]; 1 point doubling, 2 point addition, 3 Ristretto encoding (51-bit host arithmetic);

@@ -191,6 +191,13 @@ extern "C" {
         commitments_out32: *mut u8) -> c_int;
     pub fn rofl_dbg_host_feldman_verify(n_secrets: usize, threshold: usize, commitments32: *const u8, n_shares: usize, xs: *const u32,
         shares32: *const u8, verdict_out: *mut u8) -> c_int;
+    /// Deterministic Schnorr signatures over Ristretto255 (the authenticated broadcast of keys and commitments): signature i = key refs[i].key
+    /// on message refs[i].msg, message j = msg_bytes[msg_off[j] .. msg_off[j + 1]); refs null = (i, i); sig_out64 n x 64; pk_out32 may be null
+    pub fn rofl_sig_sign(n_keys: usize, sk32: *const u8, pk_out32: *mut u8, n_msgs: usize, msg_bytes: *const u8, msg_off: *const u64,
+        n: usize, refs: *const RoflSigRef, sig_out64: *mut u8) -> c_int;
+    /// verdict_out[i]: 0 valid, 1 not, 2 = the key is not a canonical encoding or is the identity, or s >= l
+    pub fn rofl_sig_verify(n_keys: usize, pk32: *const u8, n_msgs: usize, msg_bytes: *const u8, msg_off: *const u64,
+        n: usize, refs: *const RoflSigRef, sig64: *const u8, verdict_out: *mut u8) -> c_int;
     pub fn rofl_f32_to_fp_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut u64) -> c_int;
     pub fn rofl_uint_to_f32_vec(input: *const u64, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
     pub fn rofl_get_l2_clip_bounds(range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
@@ -219,6 +226,14 @@ pub struct RoflBlindTerm {
 pub struct RoflDhPair {
     pub own: u32,
     pub peer: u32,
+}
+
+/// rofl_sig_ref_t: one signature of rofl_sig_sign / rofl_sig_verify -- indices into the call's keys and its messages
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RoflSigRef {
+    pub key: u32,
+    pub msg: u32,
 }
 
 #[repr(C)]
@@ -318,4 +333,39 @@ pub fn sigma_create_batch_bytes(kind: c_int, proof_len: usize, commit_len: usize
 pub fn last_error() -> String {
     let mut buf = vec![0 as c_char; 512];
     unsafe { rofl_last_error(buf.as_mut_ptr(), buf.len()); std::ffi::CStr::from_ptr(buf.as_ptr()).to_string_lossy().into_owned() }
+}
+
+/// Batched signatures over the library (rofl_sig_sign / rofl_sig_verify).  A signing key is NOT the key-agreement key: that one is revealed
+/// when its owner drops out.  Not constant-time; deterministic nonces.
+pub mod signatures {
+    use super::{last_error, rofl_sig_sign, rofl_sig_verify, RoflSigRef, ROFL_OK};
+
+    fn pack(messages: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
+        let mut bytes = Vec::with_capacity(messages.iter().map(|m| m.len()).sum());
+        let mut off = Vec::with_capacity(messages.len() + 1);
+        off.push(0u64);
+        for m in messages { bytes.extend_from_slice(m); off.push(bytes.len() as u64); }
+        (bytes, off)
+    }
+    /// signature i = key refs[i].key on message refs[i].msg; refs None = key i on message i.  Panics on a refused parameter (a zero key).
+    pub fn sign(sks: &[[u8; 32]], messages: &[&[u8]], refs: Option<&[RoflSigRef]>) -> Vec<[u8; 64]> {
+        let n = refs.map_or(sks.len(), |r| r.len());
+        let (bytes, off) = pack(messages);
+        let mut out = vec![[0u8; 64]; n];
+        let rc = unsafe { rofl_sig_sign(sks.len(), sks.as_ptr() as *const u8, std::ptr::null_mut(), messages.len(), bytes.as_ptr(), off.as_ptr(),
+                                        n, refs.map_or(std::ptr::null(), |r| r.as_ptr()), out.as_mut_ptr() as *mut u8) };
+        if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+        out
+    }
+    /// one verdict per signature: 0 valid, 1 not, 2 = a refused key or s >= l
+    pub fn verify(pks: &[[u8; 32]], messages: &[&[u8]], sigs: &[[u8; 64]], refs: Option<&[RoflSigRef]>) -> Vec<u8> {
+        let n = sigs.len();
+        assert_eq!(n, refs.map_or(pks.len(), |r| r.len()), "one signature per ref");
+        let (bytes, off) = pack(messages);
+        let mut out = vec![0u8; n];
+        let rc = unsafe { rofl_sig_verify(pks.len(), pks.as_ptr() as *const u8, messages.len(), bytes.as_ptr(), off.as_ptr(),
+                                          n, refs.map_or(std::ptr::null(), |r| r.as_ptr()), sigs.as_ptr() as *const u8, out.as_mut_ptr()) };
+        if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+        out
+    }
 }

@@ -48,6 +48,11 @@ class _DhPair(ctypes.Structure):
     _fields_ = [("own", ctypes.c_uint32), ("peer", ctypes.c_uint32)]
 
 
+class _SigRef(ctypes.Structure):
+    """rofl_sig_ref_t"""
+    _fields_ = [("key", ctypes.c_uint32), ("msg", ctypes.c_uint32)]
+
+
 class _Timing(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("msm_accumulate_ms", ctypes.c_double),
                 ("msm_accumulate_launches", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64),
@@ -979,6 +984,80 @@ class key_agreement:
         return (out, status, own_pk) if with_public else (out, status)
 
 
+def _pack_messages(messages):
+    """a list of bytes-likes as the C ABI takes it: (uint8[total] packed back to back, uint64[n + 1] offsets)"""
+    msgs = [bytes(m) for m in messages]
+    off = np.zeros(len(msgs) + 1, dtype=np.uint64)
+    if msgs:
+        off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+    return np.frombuffer(b"".join(msgs), dtype=np.uint8), off
+
+
+def _sig_refs(refs, n_keys, n_msgs):
+    """(n, ctypes array or None) of a ref list [(key, msg), ...]; None = signature i uses key i and message i"""
+    if refs is None:
+        if n_keys != n_msgs:
+            raise ValueError("without refs there is one message per key")
+        return n_keys, None
+    rl = np.asarray(refs, dtype=np.int64).reshape(-1, 2)
+    n = rl.shape[0]
+    if n and (rl.min() < 0 or rl[:, 0].max() >= n_keys or rl[:, 1].max() >= n_msgs):
+        raise ValueError("a ref names a key or a message that is not in the call")
+    arr = (_SigRef * max(n, 1))()
+    np.frombuffer(arr, dtype=np.uint32)[:2 * n] = rl.astype(np.uint32).reshape(-1)
+    return n, arr
+
+
+class signatures:
+    """Batched deterministic Schnorr signatures over Ristretto255 (rofl_sig_sign / rofl_sig_verify): what authenticates the public keys and
+    the Feldman commitments of a round.  A key is 32 bytes, reduced mod l (0 mod l is refused); its public key is encode(key * B), the bytes
+    of key_agreement.public_keys.  With h = SHAKE256("rofl-zk/sig/v1/m" || u64le(len m) || m)[0 .. 32): nonce k from
+    SHAKE256("rofl-zk/sig/v1/k" || canonical32(key) || h), R = encode(k B), c from SHAKE256("rofl-zk/sig/v1/c" || R || A || h), s = k + c key;
+    the signature is R || s, 64 bytes, the same for the same key and message.  Not constant-time; deterministic nonces.  Use a signing key of
+    its own, NEVER the key-agreement key: that one is revealed when its owner drops out."""
+
+    @staticmethod
+    def public_keys(sk):
+        """-> uint8[n, 32], the bytes of key_agreement.public_keys"""
+        return key_agreement.public_keys(sk)
+
+    @staticmethod
+    def sign(sks, messages, refs=None, with_public=False):
+        """Signatures of the keys sks on the messages (a list of bytes-likes), ONE call: refs = [(key, message), ...] indexes the two, None =
+        key i signs message i.  -> uint8[n, 64]; with_public=True appends the public keys uint8[n_keys, 32]."""
+        sk = _keys32(sks, "a secret key")
+        data, off = _pack_messages(messages)
+        n_keys, n_msgs = sk.shape[0], off.shape[0] - 1
+        n, rarr = _sig_refs(refs, n_keys, n_msgs)
+        out = np.zeros((n, 64), dtype=np.uint8)
+        pk = np.zeros((n_keys, 32), dtype=np.uint8) if with_public else None
+        buf = (ctypes.c_ubyte * max(n_keys * 32, 1))()
+        try:
+            ctypes.memmove(buf, sk.ctypes.data, n_keys * 32)
+            _check(lib().rofl_sig_sign(_sz(n_keys), buf, _ptr(pk) if with_public else None, _sz(n_msgs), _ptr(data) if data.size else None, _ptr(off),
+                                       _sz(n), rarr, _ptr(out)))
+        finally:
+            ctypes.memset(buf, 0, ctypes.sizeof(buf))
+        if with_public and n == 0 and n_keys:      # (an empty call computes nothing: the keys come from their own entry)
+            pk = key_agreement.public_keys(sk)
+        return (out, pk) if with_public else out
+
+    @staticmethod
+    def verify(pks, messages, sigs, refs=None):
+        """-> uint8[n] verdicts of the signatures sigs uint8[n, 64], ONE call: 0 = valid, 1 = not, 2 = the key is not a canonical Ristretto
+        encoding or is the identity, or s >= l.  refs as in sign()."""
+        pk = _keys32(pks, "a public key")
+        data, off = _pack_messages(messages)
+        n_keys, n_msgs = pk.shape[0], off.shape[0] - 1
+        n, rarr = _sig_refs(refs, n_keys, n_msgs)
+        sg = np.ascontiguousarray(np.asarray(sigs, dtype=np.uint8))
+        if sg.size != n * 64 or (sg.ndim > 1 and sg.shape[-1] != 64):
+            raise ValueError("sigs are uint8[n, 64], one per ref")
+        out = np.zeros(n, dtype=np.uint8)
+        _check(lib().rofl_sig_verify(_sz(n_keys), _ptr(pk), _sz(n_msgs), _ptr(data) if data.size else None, _ptr(off), _sz(n), rarr, _ptr(sg), _ptr(out)))
+        return out
+
+
 def _xs32(xs, n_shares):
     """evaluation points as uint32[n_shares]: nonzero, distinct, each below 2^32"""
     x = np.asarray(xs)
@@ -1097,6 +1176,71 @@ class secret_sharing:
             if src is not sh:
                 src[...] = 0
         return out
+
+    # ---- the authenticated broadcast of the commitments: what a round signs (signatures.sign / verify) ----
+    @staticmethod
+    def commitment_message(round_no, dealer, kind, commitments):
+        """The bytes a dealer signs for one of its two commitment rows (kind 0 = its key's, 1 = its self-mask secret's):
+        b"rofl-zk/vss/v1\\0\\0" || u64le(round_no) || u32le(dealer) || u8(kind) || u32le(t) || commitments (t x 32)."""
+        cm = np.ascontiguousarray(np.asarray(commitments, dtype=np.uint8))
+        if cm.ndim != 2 or cm.shape[1] != 32 or cm.shape[0] < 1:
+            raise ValueError("the commitments of dealer %d are uint8[t, 32]" % int(dealer))
+        if int(kind) not in (0, 1):
+            raise ValueError("kind is 0 (key) or 1 (self)")
+        return b"rofl-zk/vss/v1\0\0" + struct.pack("<QIBI", int(round_no), int(dealer), int(kind), cm.shape[0]) + cm.tobytes()
+
+    @staticmethod
+    def view_message(round_no, sigs_by_dealer):
+        """The bytes a client signs for everything it was shown: sigs_by_dealer = {dealer: uint8[2, 64]}, the dealer's key and self signatures.
+        b"rofl-zk/view/v1\\0" || u64le(round_no) || u32le(count), then for each dealer ascending u32le(dealer) || key sig || self sig.
+        Signatures are deterministic and bind their message: two clients who saw the same commitments build the same bytes."""
+        parts = [b"rofl-zk/view/v1\0" + struct.pack("<QI", int(round_no), len(sigs_by_dealer))]
+        for d in sorted(int(k) for k in sigs_by_dealer):
+            s = np.asarray(sigs_by_dealer[d], dtype=np.uint8)
+            if s.shape != (2, 64):
+                raise ValueError("the signatures of dealer %d are uint8[2, 64]" % d)
+            parts.append(struct.pack("<I", d) + s.tobytes())
+        return b"".join(parts)
+
+    @staticmethod
+    def _commitment_messages(round_no, dealers, key_commitments, self_commitments):
+        dealers = [int(d) for d in dealers]
+        if len(key_commitments) != len(dealers) or len(self_commitments) != len(dealers):
+            raise ValueError("one row of key commitments and one of self commitments per dealer")
+        msgs = []
+        for r, d in enumerate(dealers):
+            msgs.append(secret_sharing.commitment_message(round_no, d, 0, key_commitments[r]))
+            msgs.append(secret_sharing.commitment_message(round_no, d, 1, self_commitments[r]))
+        return msgs, [(r, 2 * r + k) for r in range(len(dealers)) for k in (0, 1)]
+
+    @staticmethod
+    def sign_commitments(sig_sks, round_no, dealers, key_commitments, self_commitments):
+        """Every hosted dealer signs its two commitment messages, ONE signatures.sign call: sig_sks[r] is the signing key of dealers[r],
+        key_commitments[r] / self_commitments[r] its rows uint8[t, 32].  -> uint8[n, 2, 64], [r, 0] on the key row, [r, 1] on the self row."""
+        msgs, refs = secret_sharing._commitment_messages(round_no, dealers, key_commitments, self_commitments)
+        if _keys32(sig_sks, "a secret key").shape[0] != len(msgs) // 2:
+            raise ValueError("one signing key per dealer")
+        return signatures.sign(sig_sks, msgs, refs).reshape(-1, 2, 64)
+
+    @staticmethod
+    def verify_commitment_signatures(sig_pks, round_no, dealers, key_commitments, self_commitments, sigs):
+        """The signatures sigs uint8[n, 2, 64] of sign_commitments under the dealers' public signing keys sig_pks[r], ONE signatures.verify
+        call -> uint8[n, 2] verdicts."""
+        msgs, refs = secret_sharing._commitment_messages(round_no, dealers, key_commitments, self_commitments)
+        if _keys32(sig_pks, "a public key").shape[0] != len(msgs) // 2:
+            raise ValueError("one public signing key per dealer")
+        sg = np.asarray(sigs, dtype=np.uint8)
+        if sg.shape != (len(msgs) // 2, 2, 64):
+            raise ValueError("sigs are uint8[n, 2, 64]")
+        return signatures.verify(sig_pks, msgs, sg.reshape(-1, 64), refs).reshape(-1, 2)
+
+    @staticmethod
+    def verify_views(sig_pks, view, view_sigs):
+        """n clients' signatures view_sigs uint8[n, 64] on ONE view message (view_message) under their public signing keys, ONE
+        signatures.verify call with refs (i, 0) -> uint8[n].  A client whose verdict is nonzero saw something else than `view`, or its
+        dealer equivocated: the verdict names it."""
+        n = _keys32(sig_pks, "a public key").shape[0]
+        return signatures.verify(sig_pks, [bytes(view)], view_sigs, [(i, 0) for i in range(n)])
 
 
 class pedersen_ops:
@@ -1509,6 +1653,39 @@ class pedersen_ops:
             surv, drop, x[keep], {j: np.asarray(key_shares[j], dtype=np.uint8)[keep] for j in drop},
             {i: np.asarray(self_shares[i], dtype=np.uint8)[keep] for i in surv}, public_keys, round_no)
         return terms, liars
+
+    @staticmethod
+    def dropout_residual_terms_from_signed_shares(survivors, dropped, xs, key_shares, self_shares, key_commitments, self_commitments, public_keys,
+                                                  round_no, sig_public_keys, commitment_sigs):
+        """dropout_residual_terms_from_verified_shares behind a check of the dealers' signatures on the commitments it uses:
+        sig_public_keys = the clients' public SIGNING keys, indexed like public_keys; commitment_sigs = {client: uint8[64]}, the signature
+        on secret_sharing.commitment_message(round_no, client, kind, commitments) of the row actually used -- kind 0 (key) for every dropped
+        j, kind 1 (self) for every survivor i.  All of them go through ONE signatures.verify call, dropped first, then the survivors
+        ascending.  A missing signature or a verdict other than 0 raises ValueError naming the dealer; then the call is
+        dropout_residual_terms_from_verified_shares, unchanged.  -> (terms, liars)."""
+        surv, drop = sorted(int(i) for i in survivors), sorted(int(j) for j in dropped)
+        key_commitments = {int(j): v for j, v in key_commitments.items()}
+        self_commitments = {int(i): v for i, v in self_commitments.items()}
+        commitment_sigs = {int(c): np.asarray(v, dtype=np.uint8) for c, v in commitment_sigs.items()}
+        spk = _keys32(sig_public_keys, "a public key")
+        used = [(j, 0, key_commitments) for j in drop] + [(i, 1, self_commitments) for i in surv]
+        msgs, sigs = [], []
+        for c, kind, com in used:
+            if c not in com:
+                raise ValueError("%s %d has no %s commitments" % ("survivor" if kind else "dropped client", c, "self-mask" if kind else "key"))
+            if c not in commitment_sigs or commitment_sigs[c].shape != (64,):
+                raise ValueError("client %d: no signature on its %s commitments" % (c, "self-mask" if kind else "key"))
+            if not 0 <= c < spk.shape[0]:
+                raise ValueError("client %d has no public signing key" % c)
+            msgs.append(secret_sharing.commitment_message(round_no, c, kind, com[c]))
+            sigs.append(commitment_sigs[c])
+        if used:
+            verdict = signatures.verify(spk[[c for c, _, _ in used]], msgs, np.stack(sigs))
+            for (c, kind, _), v in zip(used, verdict):
+                if v != 0:
+                    raise ValueError("client %d: the signature on its %s commitments does not verify (verdict %d)" % (c, "self-mask" if kind else "key", int(v)))
+        return pedersen_ops.dropout_residual_terms_from_verified_shares(survivors, dropped, xs, key_shares, self_shares, key_commitments, self_commitments,
+                                                                        public_keys, round_no)
 
     # ---- a round that rejects: the terms of the accepted set's residual blinding (accumulator.extract_opened_terms) ----
     @staticmethod

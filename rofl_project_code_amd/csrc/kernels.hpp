@@ -2421,13 +2421,16 @@ __global__ void __launch_bounds__(64) k_sigma_point_var_batch(int kind, u32 d, u
 // status word (1 not a canonical encoding, 2 the identity), and one thread per pair for the variable-base multiplication, the encoding, the
 // hash and the store.  Not constant-time, like every secret-scalar path here: digit-dependent table reads, no addition on a zero digit.
 // One-block SHAKE256 of fourteen little-endian words (112 bytes): the absorb of shake256_seeded_block for a longer message
-__device__ __forceinline__ void shake256_block14(u64 st[25], const u64 m[14]) {
+// (shake256_block_words<W>: the same for W <= 16 words, the suffix right after 8 W bytes; the signatures' nonce block is W = 10)
+template <int W> __device__ __forceinline__ void shake256_block_words(u64 st[25], const u64 m[W]) {
+    static_assert(W >= 1 && W <= 16, "one block, the suffix in a word of its own");
 #pragma unroll
-    for (int i = 0; i < 25; i++) st[i] = i < 14 ? m[i] : 0;
-    st[14] ^= 0x1FULL;                   // SHAKE domain suffix right after 112 bytes
+    for (int i = 0; i < 25; i++) st[i] = i < W ? m[i] : 0;
+    st[W] ^= 0x1FULL;                    // SHAKE domain suffix right after 8 W bytes (W = 14: 112)
     st[16] ^= 0x8000000000000000ULL;     // final bit of the 136-byte rate
     keccak_f1600(st);
 }
+__device__ __forceinline__ void shake256_block14(u64 st[25], const u64 m[14]) { shake256_block_words<14>(st, m); }
 #define ROFL_DH_DOM {0x2f6b7a2d6c666f72ULL, 0x00000031762f6864ULL}      /* "rofl-zk/" "dh/v1\0\0\0" */
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(64) k_dh_public(u32 n, const sc *__restrict__ sk, const niels *tabB8, uint8_t *__restrict__ pk) {
@@ -2630,6 +2633,144 @@ __global__ void __launch_bounds__(64) k_feldman_check(u32 n_secrets, u32 n_share
     }
     const gd P = sg_fixed_mul8(tabB8, load_sc_reduced(&shares[i]));
     const bool same = fd_eq(fd_mul(acc.X, P.Y), fd_mul(acc.Y, P.X)) || fd_eq(fd_mul(acc.Y, P.Y), fd_mul(acc.X, P.X));
+    verdict[i] = same ? 0 : 1;
+}
+#endif
+// ================================================================ signatures (rofl_sig_sign / rofl_sig_verify)
+// Deterministic Schnorr signatures over Ristretto255, what authenticates the public keys and the Feldman commitments of a round.  Every label
+// is 16 bytes ("rofl-zk/" and eight more), two words like ROFL_DH_DOM:
+//   h(m) = SHAKE256("rofl-zk/sig/v1/m" || u64le(len m) || m)[0 .. 32)                                      (k_sig_digest, once per message)
+//   a = key mod l (!= 0, checked by the host), A = encode(a B)                                             (k_dh_public, once per key)
+//   k = int_le(SHAKE256("rofl-zk/sig/v1/k" || canonical32(a) || h)[0 .. 64)) mod l                         (80 bytes, one block)
+//   R = encode(k B), c = int_le(SHAKE256("rofl-zk/sig/v1/c" || R || A || h)[0 .. 64)) mod l                (112 bytes: shake256_block14)
+//   s = k + c a mod l; the signature is R || canonical32(s).
+// Verdict: 2 = the key is refused by k_dh_decode (status != 0) or s >= l; 0 = encode(s B - c decode(A)) is the 32 bytes R; 1 otherwise (an R
+// that is no canonical encoding is never the output of an encoding).  One exact equation per signature, no random weights: the verdict names
+// the signer.  Not constant-time, like every secret-scalar path here.
+#define ROFL_SIG_DOM_M {0x2f6b7a2d6c666f72ULL, 0x6d2f31762f676973ULL}      /* "rofl-zk/" "sig/v1/m" */
+#define ROFL_SIG_DOM_K {0x2f6b7a2d6c666f72ULL, 0x6b2f31762f676973ULL}      /* "rofl-zk/" "sig/v1/k" */
+#define ROFL_SIG_DOM_C {0x2f6b7a2d6c666f72ULL, 0x632f31762f676973ULL}      /* "rofl-zk/" "sig/v1/c" */
+// the challenge of a signature from the words of R, A and h
+__device__ __forceinline__ sc sig_challenge(const u64 R[4], const u64 A[4], const u64 h[4]) {
+    const u64 dom[2] = ROFL_SIG_DOM_C;
+    u64 m[14], st[25];
+    m[0] = dom[0]; m[1] = dom[1];
+#pragma unroll
+    for (int w = 0; w < 4; w++) { m[2 + w] = R[w]; m[6 + w] = A[w]; m[10 + w] = h[w]; }
+    shake256_block14(st, m);
+    return xof_block_scalar(st, 0);
+}
+#if ROFL_KG(4)
+// dig[j] = h(message j), one thread per message; message j is bytes[off[j] .. off[j + 1]).  The sponge's stream is three words of prefix
+// (label, length) and then the message, so stream word g >= 3 is the message's bytes 8 (g - 3) .. + 8: a message starts at ANY byte, so a
+// word is put together from the two 8-byte aligned words that hold it (`bytes` is 8-byte aligned; only aligned words that hold a byte of
+// the message are read).  The word after the last whole one carries the remaining 0 .. 7 bytes and the SHAKE suffix 0x1F above them; the
+// last block gets 0x80 into byte 135.  The four endings fall out of the XORs: inside a block; on the last byte of the rate (0x1F and 0x80 in
+// one byte: 0x9F); exactly on the rate (the suffix word is word 0 of a block of its own); the empty message (the suffix is word 3).
+// The lanes of a wave run as many blocks as their longest message has: a long message is one serial chain of permutations on one lane.
+__global__ void __launch_bounds__(64) k_sig_digest(u32 n_msgs, const uint8_t *__restrict__ bytes, const u64 *__restrict__ off /* [n_msgs + 1] */, u64 *__restrict__ dig /* [n_msgs][4] */) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_msgs) return;
+    const u64 o = off[j], len = off[j + 1] - o, nw = len >> 3;
+    const u32 rem = (u32)len & 7u, mis = (u32)o & 7u, sh = 8 * mis;
+    const u64 *a = reinterpret_cast<const u64 *>(bytes + (o - mis));
+    const u64 lastw = len ? (mis + len - 1) >> 3 : 0;      // the last aligned word that holds a byte of the message
+    const u64 dom[2] = ROFL_SIG_DOM_M;
+    u64 st[25];
+#pragma unroll
+    for (int i = 0; i < 25; i++) st[i] = 0;
+    st[0] = dom[0]; st[1] = dom[1]; st[2] = len;
+    const u64 gpad = 3 + nw, nblk = gpad / 17 + 1;
+    for (u64 b = 0; b < nblk; b++) {
+#pragma unroll
+        for (int i = 0; i < 17; i++) {
+            const u64 g = 17 * b + i;
+            if (g < 3 || g > gpad) continue;
+            const u64 k = g - 3;
+            u64 v = 0;
+            if (k < nw || rem) {
+                const u64 lo = a[k], hi = (sh && k + 1 <= lastw) ? a[k + 1] : 0;
+                v = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+            }
+            if (k == nw) v = (v & ((1ULL << (8 * rem)) - 1)) | (0x1FULL << (8 * rem));
+            st[i] ^= v;
+        }
+        if (b + 1 == nblk) st[16] ^= 0x8000000000000000ULL;
+        keccak_f1600(st);
+    }
+    uint4 *d = reinterpret_cast<uint4 *>(dig + 4 * (size_t)j);
+    d[0] = make_uint4((u32)st[0], (u32)(st[0] >> 32), (u32)st[1], (u32)(st[1] >> 32));
+    d[1] = make_uint4((u32)st[2], (u32)(st[2] >> 32), (u32)st[3], (u32)(st[3] >> 32));
+}
+// sig[i] = the signature of key refs[i].x on message refs[i].y (refs == nullptr: key i on message i), one thread per signature: the nonce
+// block, k B from the radix-256 table, its encoding, the challenge block, s, two 32-byte stores.  pk: the output of a k_dh_public launch over
+// the keys; dig: k_sig_digest's.  k = 0 is not special: R is then the identity encoding and s = c a.
+__global__ void __launch_bounds__(64) k_sig_sign(u32 n, const uint2 *__restrict__ refs, const sc *__restrict__ sk, const uint8_t *__restrict__ pk, const u64 *__restrict__ dig,
+                                                 const niels *tabB8, uint8_t *__restrict__ sig /* [n][64], 16-byte aligned */) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 ka = i, mb = i;
+    if (refs) { const uint2 r = refs[i]; ka = r.x; mb = r.y; }
+    const sc a = load_sc_reduced(&sk[ka]);
+    const u64 *hp = dig + 4 * (size_t)mb, *ap = reinterpret_cast<const u64 *>(pk + (size_t)32 * ka);
+    u64 h[4], A[4], R[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) { h[w] = hp[w]; A[w] = ap[w]; }
+    sc k;
+    {   const u64 dom[2] = ROFL_SIG_DOM_K;
+        u64 m[10], st[25];
+        m[0] = dom[0]; m[1] = dom[1];
+#pragma unroll
+        for (int w = 0; w < 4; w++) { m[2 + w] = (u64)a.v[2 * w] | ((u64)a.v[2 * w + 1] << 32); m[6 + w] = h[w]; }
+        shake256_block_words<10>(st, m);
+        k = xof_block_scalar(st, 0); }
+    uint8_t Rb[32];
+    sg_encode(Rb, sg_fixed_mul8(tabB8, k));
+#pragma unroll
+    for (int w = 0; w < 4; w++) { u64 v = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) v |= (u64)Rb[8 * w + q] << (8 * q);
+        R[w] = v; }
+    const sc c = sig_challenge(R, A, h);
+    const sc s = sc_add(k, sc_montmul(sc_to_mont(c), a));      // (c R) a R^-1 = c a, canonical
+    uint4 *o = reinterpret_cast<uint4 *>(sig + (size_t)64 * i);
+    o[0] = make_uint4((u32)R[0], (u32)(R[0] >> 32), (u32)R[1], (u32)(R[1] >> 32));
+    o[1] = make_uint4((u32)R[2], (u32)(R[2] >> 32), (u32)R[3], (u32)(R[3] >> 32));
+    store_sc(reinterpret_cast<sc *>(o + 2), s);
+}
+#endif
+#if ROFL_KG(3)
+// verdict[i] of signature i = sig[i] under key refs[i].x on message refs[i].y (refs == nullptr: key i, message i), one thread per signature.
+// kpts / kstatus: k_dh_decode's workspace over the keys (status 1 not a canonical encoding, 2 the identity: both refuse the key); dig:
+// k_sig_digest's.  A refused key or s >= l stores 2 and computes nothing.  Otherwise c from R (the 32 bytes as they came), the key's bytes and
+// h; s B from the radix-256 table plus (l - c) decode(A) by the variable-base windows; the encoding of the sum against R's bytes: 0 equal, 1
+// not.  Nothing is staged through LDS: per signature two 32-byte reads and one packed point against ~3 000 field multiplications.
+__global__ void __launch_bounds__(64) k_sig_verify(u32 n, const uint2 *__restrict__ refs, const uint8_t *__restrict__ pk, const ge *__restrict__ kpts, const u32 *__restrict__ kstatus,
+                                                   const u64 *__restrict__ dig, const uint8_t *__restrict__ sig /* [n][64], 16-byte aligned */, const niels *tabB8,
+                                                   uint8_t *__restrict__ verdict) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 ka = i, mb = i;
+    if (refs) { const uint2 r = refs[i]; ka = r.x; mb = r.y; }
+    const uint4 *sp = reinterpret_cast<const uint4 *>(sig + (size_t)64 * i);
+    const uint4 r0 = sp[0], r1 = sp[1];
+    const sc s = load_sc(reinterpret_cast<const sc *>(sp + 2));
+    if (kstatus[ka] != 0u || sc_geq_l(s.v)) { verdict[i] = 2; return; }
+    const u64 *hp = dig + 4 * (size_t)mb, *ap = reinterpret_cast<const u64 *>(pk + (size_t)32 * ka);
+    u64 h[4], A[4];
+    const u64 R[4] = {(u64)r0.x | ((u64)r0.y << 32), (u64)r0.z | ((u64)r0.w << 32), (u64)r1.x | ((u64)r1.y << 32), (u64)r1.z | ((u64)r1.w << 32)};
+#pragma unroll
+    for (int w = 0; w < 4; w++) { h[w] = hp[w]; A[w] = ap[w]; }
+    const sc c = sig_challenge(R, A, h);
+    const gd P = gd_add(sg_fixed_mul8(tabB8, s), sg_var_mul(sc_neg(c), load_gd(&kpts[ka])));
+    uint8_t E[32];
+    sg_encode(E, P);
+    bool same = true;
+#pragma unroll
+    for (int w = 0; w < 4; w++) { u64 v = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) v |= (u64)E[8 * w + q] << (8 * q);
+        same &= v == R[w]; }
     verdict[i] = same ? 0 : 1;
 }
 #endif

@@ -2827,6 +2827,179 @@ int rofl_dbg_host_feldman_verify(size_t n_secrets, size_t threshold, const uint8
     }
     return ROFL_OK;
 }
+// ---- signatures: deterministic Schnorr over Ristretto255 on the commitments and views of a round (k_sig_digest, k_dh_public / k_dh_decode, k_sig_sign / k_sig_verify) ----
+}  // extern "C"
+namespace {
+// every check of rofl_sig_sign / rofl_sig_verify, shared with their host routes; keys32: secret keys (sign) or public keys (verify), sig: the
+// signatures read or written, verdict: verify's output; *done: the call is empty and returns 0.  *total: the messages' bytes
+int sig_check(bool sign, size_t n_keys, const uint8_t *keys32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs,
+              const uint8_t *sig, const uint8_t *verdict, size_t *total, bool *done) {
+    *done = n == 0; *total = 0;
+    if (*done) return ROFL_OK;
+    if (!keys32 || !msg_off || !sig || (!sign && !verdict)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_keys == 0 || n_msgs == 0) return fail(ROFL_BAD_PARAM, "signatures without keys or without messages");
+    if (n_keys > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
+    if (n_msgs > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 messages in one call");
+    if (n > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 signatures in one call");
+    if (msg_off[0] != 0) return fail(ROFL_BAD_PARAM, "the first message offset is 0");
+    for (size_t j = 0; j < n_msgs; j++) {
+        if (msg_off[j + 1] < msg_off[j]) { char buf[96]; snprintf(buf, sizeof buf, "message offset %zu is below the one before it", j + 1); return fail(ROFL_BAD_PARAM, buf); }
+        if (msg_off[j + 1] > ((uint64_t)1 << 30)) return fail(ROFL_BAD_PARAM, "more than 2^30 message bytes in one call");
+    }
+    *total = (size_t)msg_off[n_msgs];
+    if (*total && !msg_bytes) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (!refs && !(n_keys == n && n_msgs == n)) return fail(ROFL_BAD_PARAM, "without a ref list n_keys, n_msgs and n are equal");
+    if (refs) for (size_t i = 0; i < n; i++)
+        if (refs[i].key >= n_keys || refs[i].msg >= n_msgs) { char buf[96]; snprintf(buf, sizeof buf, "ref %zu names a key or a message that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
+    return sign ? dh_check_keys(n_keys, keys32) : ROFL_OK;
+}
+// h(m) = SHAKE256("rofl-zk/sig/v1/m" || u64le(len) || m)[0 .. 32) on the host's sponge
+void sig_host_digest(uint8_t out[32], const uint8_t *m, uint64_t len) {
+    uint8_t pre[24] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 's', 'i', 'g', '/', 'v', '1', '/', 'm'};
+    memcpy(pre + 16, &len, 8);
+    Sponge sp(136, 0x1F); sp.absorb(pre, 24); if (len) sp.absorb(m, (size_t)len); sp.squeeze(out, 32);
+}
+// int_le(SHAKE256(label || x || y [|| z])[0 .. 64)) mod l for the labels "rofl-zk/sig/v1/k" (which = 'k', two parts) and ".../c" ('c', three)
+sc sig_host_wide(char which, const uint8_t *x, const uint8_t *y, const uint8_t *z) {
+    uint8_t m[112] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 's', 'i', 'g', '/', 'v', '1', '/', (uint8_t)which}, w[64];
+    memcpy(m + 16, x, 32); memcpy(m + 48, y, 32); if (z) memcpy(m + 80, z, 32);
+    Sponge sp(136, 0x1F); sp.absorb(m, z ? 112 : 80); sp.squeeze(w, 64);
+    sc r = sc_from_wide(sc_frombytes(w), sc_frombytes(w + 32));
+    dh_wipe(m, sizeof m); dh_wipe(w, sizeof w); dh_wipe(&sp, sizeof sp);
+    return r;
+}
+// layout of the lane's upload for the two calls: [keys | signatures (verify) | offsets | refs | message bytes], every part 8-byte aligned, the
+// signatures 16; the message bytes are followed by 8 spare bytes (k_sig_digest reads whole aligned words)
+struct SigLayout { size_t sig, off, refs, msg, bytes; };
+SigLayout sig_layout(bool sign, size_t n_keys, size_t n_msgs, size_t n, bool has_refs, size_t total) {
+    SigLayout l;
+    l.sig = n_keys * 32; l.off = l.sig + (sign ? 0 : n * 64); l.refs = l.off + (n_msgs + 1) * 8; l.msg = l.refs + (has_refs ? n * sizeof(rofl_sig_ref_t) : 0);
+    l.bytes = l.msg + ((total + 7) & ~(size_t)7) + 8;
+    return l;
+}
+}  // namespace
+extern "C" {
+// The lane's copies of the secret keys -- pinned staging and device workspace -- are overwritten with zeros before the call returns or
+// unwinds; the nonces never leave their threads' registers; digests, public keys and signatures are public.
+int rofl_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,
+                  size_t n, const rofl_sig_ref_t *refs, uint8_t *sig_out64) {
+    bool done; size_t total;
+    if (int rc = sig_check(true, n_keys, sk32, n_msgs, msg_bytes, msg_off, n, refs, sig_out64, nullptr, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: sig_layout; workspace: the digests; download: [signatures | public keys]
+        const SigLayout l = sig_layout(true, n_keys, n_msgs, n, refs != nullptr, total);
+        const size_t dn_pk = n * 64, dn_bytes = dn_pk + n_keys * 32;
+        uint8_t *hu = C.h_misc.as<uint8_t>(l.bytes), *du = C.tmp_in.as<uint8_t>(l.bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        u64 *dig = C.tmp_in2.as<u64>(n_msgs * 4);
+        BlindWipe wipe_keys;
+        wipe_keys.h = hu; wipe_keys.dv = du; wipe_keys.n = n_keys * 32; wipe_keys.s = C.stream;
+        memcpy(hu, sk32, n_keys * 32); memcpy(hu + l.off, msg_off, (n_msgs + 1) * 8);
+        if (refs) memcpy(hu + l.refs, refs, n * sizeof(rofl_sig_ref_t));
+        if (total) memcpy(hu + l.msg, msg_bytes, total);
+        memset(hu + l.msg + total, 0, l.bytes - l.msg - total);
+        HIPCHK(hipMemcpyAsync(du, hu, l.bytes, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_sig_digest, dim3((unsigned)((n_msgs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_msgs, (const uint8_t *)(du + l.msg), reinterpret_cast<const u64 *>(du + l.off), dig);
+        ROFL_LAUNCH(k_dh_public, dim3((unsigned)((n_keys + 63) / 64)), dim3(64), 0, C.stream, (u32)n_keys, reinterpret_cast<const sc *>(du), C.d_tabB8, dd + dn_pk);
+        ROFL_LAUNCH(k_sig_sign, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, refs ? reinterpret_cast<const uint2 *>(du + l.refs) : (const uint2 *)nullptr,
+                    reinterpret_cast<const sc *>(du), (const uint8_t *)(dd + dn_pk), (const u64 *)dig, C.d_tabB8, dd);
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(sig_out64, hd, n * 64);
+        if (pk_out32) memcpy(pk_out32, hd + dn_pk, n_keys * 32);
+        return ROFL_OK;
+    });
+}
+// nothing here is secret: public keys, messages, signatures, verdicts
+int rofl_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs,
+                    const uint8_t *sig64, uint8_t *verdict_out) {
+    bool done; size_t total;
+    if (int rc = sig_check(false, n_keys, pk32, n_msgs, msg_bytes, msg_off, n, refs, sig64, verdict_out, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: sig_layout; workspace: the digests, the decoded keys and their status words; download: the verdict bytes
+        const SigLayout l = sig_layout(false, n_keys, n_msgs, n, refs != nullptr, total);
+        uint8_t *hu = C.h_misc.as<uint8_t>(l.bytes), *du = C.tmp_in.as<uint8_t>(l.bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(n), *dd = C.tmp_out.as<uint8_t>(n);
+        u64 *dig = C.tmp_in2.as<u64>(n_msgs * 4);
+        ge *pts = C.aux_pts.as<ge>(n_keys); u32 *pst = C.status.as<u32>(n_keys);
+        memcpy(hu, pk32, n_keys * 32); memcpy(hu + l.sig, sig64, n * 64); memcpy(hu + l.off, msg_off, (n_msgs + 1) * 8);
+        if (refs) memcpy(hu + l.refs, refs, n * sizeof(rofl_sig_ref_t));
+        if (total) memcpy(hu + l.msg, msg_bytes, total);
+        memset(hu + l.msg + total, 0, l.bytes - l.msg - total);
+        HIPCHK(hipMemcpyAsync(du, hu, l.bytes, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_sig_digest, dim3((unsigned)((n_msgs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_msgs, (const uint8_t *)(du + l.msg), reinterpret_cast<const u64 *>(du + l.off), dig);
+        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_keys + 63) / 64)), dim3(64), 0, C.stream, (u32)n_keys, (const uint8_t *)du, pts, pst);
+        ROFL_LAUNCH(k_sig_verify, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, refs ? reinterpret_cast<const uint2 *>(du + l.refs) : (const uint2 *)nullptr,
+                    (const uint8_t *)du, (const ge *)pts, (const u32 *)pst, (const u64 *)dig, (const uint8_t *)(du + l.sig), C.d_tabB8, dd);
+        HIPCHK(hipMemcpyAsync(hd, dd, n, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(verdict_out, hd, n);
+        return ROFL_OK;
+    });
+}
+// the two calls on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: same parameters, same checks, same bytes
+int rofl_dbg_host_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,
+                           size_t n, const rofl_sig_ref_t *refs, uint8_t *sig_out64) {
+    bool done; size_t total;
+    if (int rc = sig_check(true, n_keys, sk32, n_msgs, msg_bytes, msg_off, n, refs, sig_out64, nullptr, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    ge Bg; ristretto_decode(Bg, kDhBase);
+    const h51::ge5 B = h51::from_ge(Bg);
+    std::vector<uint8_t> dig(n_msgs * 32), pk(n_keys * 32), can(n_keys * 32);
+    std::vector<sc> keys(n_keys);
+    for (size_t j = 0; j < n_msgs; j++) sig_host_digest(dig.data() + 32 * j, msg_bytes + msg_off[j], msg_off[j + 1] - msg_off[j]);
+    for (size_t a = 0; a < n_keys; a++) {
+        keys[a] = dh_key_scalar(sk32 + 32 * a);
+        sc_tobytes(can.data() + 32 * a, keys[a]);
+        h51::encode(pk.data() + 32 * a, dh_host_mul(keys[a], B));
+    }
+    for (size_t i = 0; i < n; i++) {
+        const size_t a = refs ? refs[i].key : i, b = refs ? refs[i].msg : i;
+        uint8_t *o = sig_out64 + 64 * i;
+        sc k = sig_host_wide('k', can.data() + 32 * a, dig.data() + 32 * b, nullptr);
+        h51::encode(o, dh_host_mul(k, B));
+        sc c = sig_host_wide('c', o, pk.data() + 32 * a, dig.data() + 32 * b);
+        sc s = sc_add(k, sc_montmul(sc_to_mont(c), keys[a]));
+        sc_tobytes(o + 32, s);
+        dh_wipe(&k, sizeof k); dh_wipe(&c, sizeof c); dh_wipe(&s, sizeof s);
+    }
+    if (pk_out32) memcpy(pk_out32, pk.data(), n_keys * 32);
+    dh_wipe(keys.data(), keys.size() * sizeof(sc)); dh_wipe(can.data(), can.size());
+    return ROFL_OK;
+}
+int rofl_dbg_host_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs,
+                             const uint8_t *sig64, uint8_t *verdict_out) {
+    bool done; size_t total;
+    if (int rc = sig_check(false, n_keys, pk32, n_msgs, msg_bytes, msg_off, n, refs, sig64, verdict_out, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    ge Bg; ristretto_decode(Bg, kDhBase);
+    const h51::ge5 B = h51::from_ge(Bg);
+    std::vector<uint8_t> dig(n_msgs * 32), refused(n_keys);
+    std::vector<h51::ge5> kp(n_keys);
+    for (size_t j = 0; j < n_msgs; j++) sig_host_digest(dig.data() + 32 * j, msg_bytes + msg_off[j], msg_off[j + 1] - msg_off[j]);
+    for (size_t a = 0; a < n_keys; a++) {
+        ge P;
+        refused[a] = !ristretto_decode(P, pk32 + 32 * a) || ge_is_identity_ristretto(P);
+        if (!refused[a]) kp[a] = h51::from_ge(P);
+    }
+    for (size_t i = 0; i < n; i++) {
+        const size_t a = refs ? refs[i].key : i, b = refs ? refs[i].msg : i;
+        const uint8_t *sg = sig64 + 64 * i;
+        const sc s = sc_frombytes(sg + 32);
+        if (refused[a] || sc_geq_l(s.v)) { verdict_out[i] = 2; continue; }
+        const sc c = sig_host_wide('c', sg, pk32 + 32 * a, dig.data() + 32 * b);
+        uint8_t enc[32];
+        h51::encode(enc, h51::gadd(dh_host_mul(s, B), dh_host_mul(sc_neg(c), kp[a])));
+        verdict_out[i] = memcmp(enc, sg, 32) == 0 ? 0 : 1;
+    }
+    return ROFL_OK;
+}
 // conversion32::f32_to_fp_vec / uint_to_f32_vec (conversion32.rs:41-54): Fix is unsigned, negative inputs saturate to 0
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out) {
     if (!valid_fp(fp_bits, fp_frac)) return fail(ROFL_BAD_PARAM, "bad parameter");

@@ -417,7 +417,8 @@ int rofl_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *x
  * commit to a secret of low entropy.  The commitments must come over an AUTHENTICATED broadcast: a dealer that shows different commitments
  * to different clients defeats the check.  rofl_sig_sign / rofl_sig_verify (further below) are that authentication: every dealer signs its
  * commitments, every client signs its view of everybody's, and a dealer that equivocated is named by the view round.  How the bytes travel,
- * how the shares travel, and what happens after a complaint stay the deployment's business.
+ * how the shares travel (their encryption on the way is rofl_aead_seal / rofl_aead_open, further below), and what happens after a complaint
+ * stay the deployment's business.
  * rofl_feldman_commit: commitments_out32[s][k] = C_k of secret s, secret-major.  rofl_feldman_verify: one set of points for all secrets
  * (xs == NULL means 1 .. n_shares), verdict_out[s][i] for shares32[s][i] at xs[i]; threshold <= n_shares is NOT required -- a client checks
  * the one share it received against t commitments.  Every commitment is decoded once, whatever the number of shares.  A call on a subset of
@@ -472,6 +473,49 @@ int rofl_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32 /* may b
                   size_t n, const rofl_sig_ref_t *refs /* NULL: (i, i) */, uint8_t *sig_out64 /* n x 64 */);
 int rofl_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off /* n_msgs + 1 */,
                     size_t n, const rofl_sig_ref_t *refs /* NULL: (i, i) */, const uint8_t *sig64 /* n x 64 */, uint8_t *verdict_out /* n */);
+/* Sealed shares: RFC 8439 ChaCha20-Poly1305 in batches, one record per pairwise key and one exact verdict per record.  It is the ENCRYPTION
+ * of the share bundles that a relaying server carries between clients; how the bytes travel stays the deployment's business.
+ *   record: exactly RFC 8439 section 2.8 -- a 256-bit key, a 96-bit nonce, a 32-bit block counter.  The one-time Poly1305 key is the first
+ *     32 bytes of ChaCha20 block 0, the data is encrypted from block 1, the tag runs over
+ *     AD || pad16 || CT || pad16 || u64le(len AD) || u64le(len CT), and the output is CT || tag, len + 16 bytes: libsodium's combined form
+ *     (crypto_aead_chacha20poly1305_ietf_*), which any standard library opens;
+ *   key: with derive_round == NULL a row of key32 IS the RFC 8439 key.  With derive_round non-NULL a row is a rofl_dh_shared output and the key
+ *     is K = SHAKE256("rofl-zk/seal/v1\0" || row || u64le(*derive_round))[0 .. 32) (a 16-byte label, 56 bytes, one Keccak block, on the
+ *     device), derived once per key, however many records use it.  A fresh key per round is what lets a round use a structured nonce;
+ *   record i uses key key_idx[i] (key_idx == NULL: key i, and n_keys == n), nonce nonce12[12 i ..), AD ad_bytes[ad_off[i] .. ad_off[i + 1])
+ *     and payload pt_bytes[pt_off[i] .. pt_off[i + 1]); seal writes it at sealed_out[pt_off[i] + 16 i ..), so the records are packed back to
+ *     back with offsets pt_off[i] + 16 i;
+ *   verdict byte per record of open, the tag checked over the ciphertext BEFORE anything is decrypted:
+ *     0 = the tag matches; the plaintext is written at pt_out[sealed_off[i] ..), len_i - 16 bytes;
+ *     1 = the tag does not match; those len_i - 16 bytes are written as zeros;
+ *     2 = the record is shorter than 16 bytes; nothing is written for it.
+ *   A bad record condemns itself, not the call, as with rofl_dh_shared and rofl_sig_verify.
+ * Host pointers only.  Both return 11 before the device is touched, with a text that names the index and never a key or plaintext byte,
+ * for: a null pointer (allowed: derive_round, key_idx, and ad_bytes / pt_bytes / sealed_bytes -- and pt_out of open -- when their total
+ * length is 0), an offset array that does not start at 0 or that decreases, a key_idx out of range, key_idx == NULL with n_keys != n, n or
+ * n_keys above 2^24 (or n_keys = 0 with n > 0), a total AD or a total payload above 2^30 bytes, one payload above 2^24 bytes (open counts
+ * the records without their tags); n = 0 returns 0 and touches no device.  One lane: one upload, at most two launches (the key
+ * derivation where asked for; seal or open), one download.  The `devices` option does not apply.  Keys, derived keys and plaintexts are
+ * secrets: the pinned staging copies and the device workspace that held them are overwritten with zeros before the call returns or
+ * unwinds; keystream and authenticator keys live in registers only.
+ * What is NOT promised: nothing is constant-time.  A (key, nonce) pair that seals two different payloads gives away the XOR of both and the
+ * authenticator: the CALLER owns nonce uniqueness (secret_sharing.seal_shares in the Python binding: a key per pair and round, the nonce
+ * from sender and recipient).  One record is one thread: one long record is one serial chain on one lane, as with k_sig_digest, and a
+ * call that consists of it is slower than one host core.  A deployment uses a CHANNEL key pair of its own for this, a third key beside its
+ * mask key and its signing key: the mask key of a client that drops out is RECONSTRUCTED by the server, and a sealing key derived from it
+ * would open every bundle ever sealed to or from that client. */
+int rofl_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round /* may be NULL */,
+                   size_t n, const uint32_t *key_idx /* NULL: record i uses key i; needs n_keys == n */,
+                   const uint8_t *nonce12 /* n x 12 */,
+                   const uint8_t *ad_bytes, const uint64_t *ad_off /* n + 1 */,
+                   const uint8_t *pt_bytes, const uint64_t *pt_off /* n + 1 */,
+                   uint8_t *sealed_out /* pt_off[n] + 16 n bytes: record i at pt_off[i] + 16 i, len_i + 16 bytes */);
+int rofl_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round,
+                   size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                   const uint8_t *ad_bytes, const uint64_t *ad_off,
+                   const uint8_t *sealed_bytes, const uint64_t *sealed_off /* n + 1 */,
+                   uint8_t *pt_out /* sealed_off[n] bytes: plaintext i at sealed_off[i], len_i - 16 bytes */,
+                   uint8_t *verdict_out /* n */);
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out);         /* conversion32.rs:49-54 */
 int rofl_uint_to_f32_vec(const uint64_t *in, size_t d, unsigned fp_bits, unsigned fp_frac, float *out);        /* conversion32.rs:41-47 */
 int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float *out);  /* conversion32.rs:62-64 */

@@ -152,6 +152,20 @@ int rofl_dbg_host_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32
                            const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs, uint8_t *sig_out64);
 int rofl_dbg_host_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,
                              size_t n, const rofl_sig_ref_t *refs, const uint8_t *sig64, uint8_t *verdict_out);
+/* rofl_aead_seal / rofl_aead_open in plain C++ on one thread, no GPU: the same parameters, the same checks (11) and the same bytes.  What the
+ * host tests pin the definition with, and the baseline of profiles/share_seal.json on a box without libsodium. */
+int rofl_dbg_host_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx,
+                            const uint8_t *nonce12, const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes,
+                            const uint64_t *pt_off, uint8_t *sealed_out);
+int rofl_dbg_host_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx,
+                            const uint8_t *nonce12, const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes,
+                            const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out);
+/* Poly1305 alone, because an AEAD call cannot choose (r, s): tag_out16[j] = the tag of message j = msg_bytes[msg_off[j] .. msg_off[j + 1])
+ * under key32[j] = r || s (r is clamped inside).  rofl_dbg_poly1305 runs the AEAD kernels' own device function, one thread per message, one
+ * launch; rofl_dbg_host_poly1305 the host route's.  11 for a null pointer, n above 2^20, bad offsets, a message above 2^24 bytes. */
+int rofl_dbg_poly1305(size_t n, const uint8_t *key32 /* n x 32 */, const uint8_t *msg_bytes, const uint64_t *msg_off /* n + 1 */,
+                      uint8_t *tag_out16 /* n x 16 */);
+int rofl_dbg_host_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16);
 
 /* host micro-benchmarks of the code the per-round hops run (nanoseconds per operation on the calling core).
  * what: 0 Keccak-f[1600]; 1 point doubling, 2 point addition, 3 Ristretto encoding (51-bit host arithmetic);

@@ -198,6 +198,14 @@ extern "C" {
     /// verdict_out[i]: 0 valid, 1 not, 2 = the key is not a canonical encoding or is the identity, or s >= l
     pub fn rofl_sig_verify(n_keys: usize, pk32: *const u8, n_msgs: usize, msg_bytes: *const u8, msg_off: *const u64,
         n: usize, refs: *const RoflSigRef, sig64: *const u8, verdict_out: *mut u8) -> c_int;
+    /// RFC 8439 ChaCha20-Poly1305 on the share bundles a server relays: record i under key key_idx[i] (null = key i), nonce12 n x 12, AD and
+    /// payload packed with n + 1 offsets; sealed_out holds CT || tag of record i at pt_off[i] + 16 i.  derive_round non-null: a row of key32 is
+    /// a rofl_dh_shared output and the key is SHAKE256("rofl-zk/seal/v1\0" || row || u64le(round))[0 .. 32)
+    pub fn rofl_aead_seal(n_keys: usize, key32: *const u8, derive_round: *const u64, n: usize, key_idx: *const u32, nonce12: *const u8,
+        ad_bytes: *const u8, ad_off: *const u64, pt_bytes: *const u8, pt_off: *const u64, sealed_out: *mut u8) -> c_int;
+    /// verdict_out[i]: 0 opened (plaintext at pt_out[sealed_off[i] ..)), 1 the tag does not match (zeros there), 2 shorter than 16 bytes
+    pub fn rofl_aead_open(n_keys: usize, key32: *const u8, derive_round: *const u64, n: usize, key_idx: *const u32, nonce12: *const u8,
+        ad_bytes: *const u8, ad_off: *const u64, sealed_bytes: *const u8, sealed_off: *const u64, pt_out: *mut u8, verdict_out: *mut u8) -> c_int;
     pub fn rofl_f32_to_fp_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut u64) -> c_int;
     pub fn rofl_uint_to_f32_vec(input: *const u64, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
     pub fn rofl_get_l2_clip_bounds(range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
@@ -367,5 +375,43 @@ pub mod signatures {
                                           n, refs.map_or(std::ptr::null(), |r| r.as_ptr()), sigs.as_ptr() as *const u8, out.as_mut_ptr()) };
         if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
         out
+    }
+}
+
+/// Batched RFC 8439 ChaCha20-Poly1305 over the library (rofl_aead_seal / rofl_aead_open): the share bundles a server relays.  The keys come
+/// from a CHANNEL key pair of its own (never the mask key, which is reconstructed when its owner drops out) through rofl_dh_shared and
+/// derive_round.  Not constant-time; the caller owns nonce uniqueness.
+pub mod sealed {
+    use super::{last_error, rofl_aead_open, rofl_aead_seal, ROFL_OK};
+
+    fn pack(items: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
+        let mut bytes = Vec::with_capacity(items.iter().map(|m| m.len()).sum());
+        let mut off = Vec::with_capacity(items.len() + 1);
+        off.push(0u64);
+        for m in items { bytes.extend_from_slice(m); off.push(bytes.len() as u64); }
+        (bytes, off)
+    }
+    /// record i = payload i under key i, nonce i and AD i -> CT || tag.  Panics on a refused parameter.
+    pub fn seal(keys: &[[u8; 32]], derive_round: Option<u64>, nonces: &[[u8; 12]], ads: &[&[u8]], payloads: &[&[u8]]) -> Vec<Vec<u8>> {
+        let n = payloads.len();
+        assert!(keys.len() == n && nonces.len() == n && ads.len() == n, "one key, nonce and AD per payload");
+        let ((ad, ad_off), (pt, pt_off)) = (pack(ads), pack(payloads));
+        let mut out = vec![0u8; pt.len() + 16 * n];
+        let rc = unsafe { rofl_aead_seal(n, keys.as_ptr() as *const u8, derive_round.as_ref().map_or(std::ptr::null(), |r| r as *const u64), n, std::ptr::null(),
+                                         nonces.as_ptr() as *const u8, ad.as_ptr(), ad_off.as_ptr(), pt.as_ptr(), pt_off.as_ptr(), out.as_mut_ptr()) };
+        if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+        (0..n).map(|i| out[pt_off[i] as usize + 16 * i..pt_off[i + 1] as usize + 16 * (i + 1)].to_vec()).collect()
+    }
+    /// (plaintexts, verdicts): verdict 0 opened, 1 the tag does not match (a zero plaintext), 2 shorter than 16 bytes (an empty plaintext)
+    pub fn open(keys: &[[u8; 32]], derive_round: Option<u64>, nonces: &[[u8; 12]], ads: &[&[u8]], records: &[&[u8]]) -> (Vec<Vec<u8>>, Vec<u8>) {
+        let n = records.len();
+        assert!(keys.len() == n && nonces.len() == n && ads.len() == n, "one key, nonce and AD per record");
+        let ((ad, ad_off), (ct, ct_off)) = (pack(ads), pack(records));
+        let (mut pt, mut verdict) = (vec![0u8; ct.len().max(1)], vec![0u8; n]);
+        let rc = unsafe { rofl_aead_open(n, keys.as_ptr() as *const u8, derive_round.as_ref().map_or(std::ptr::null(), |r| r as *const u64), n, std::ptr::null(),
+                                         nonces.as_ptr() as *const u8, ad.as_ptr(), ad_off.as_ptr(), ct.as_ptr(), ct_off.as_ptr(), pt.as_mut_ptr(), verdict.as_mut_ptr()) };
+        if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+        let out = (0..n).map(|i| { let (a, b) = (ct_off[i] as usize, ct_off[i + 1] as usize); pt[a..a + (b - a).saturating_sub(16)].to_vec() }).collect();
+        (out, verdict)
     }
 }

@@ -1058,6 +1058,111 @@ class signatures:
         return out
 
 
+def _packed(x, what):
+    """Byte strings as the C ABI takes them -> (uint8[total], uint64[n + 1], form).  Three forms are accepted: a pre-packed
+    (uint8[total], uint64[n + 1]) pair (form "packed"); a 2-D uint8 array of equal-length rows (form = the row length; no Python-level
+    join); a list of bytes-likes (form None)."""
+    if isinstance(x, tuple) and len(x) == 2 and isinstance(x[1], np.ndarray) and x[1].dtype == np.uint64:
+        data, off = np.ascontiguousarray(np.asarray(x[0], dtype=np.uint8)).reshape(-1), np.ascontiguousarray(x[1]).reshape(-1)
+        if off.size < 1 or off[0] != 0 or (off[1:] < off[:-1]).any() or int(off[-1]) > data.size:
+            raise ValueError("%s: offsets start at 0, do not decrease and end inside the bytes" % what)
+        return data, off, "packed"
+    if isinstance(x, np.ndarray) and x.ndim == 2:
+        if x.dtype != np.uint8:
+            raise ValueError("%s: a 2-D array is uint8[n, length]" % what)
+        return np.ascontiguousarray(x).reshape(-1), np.arange(x.shape[0] + 1, dtype=np.uint64) * np.uint64(x.shape[1]), int(x.shape[1])
+    data, off = _pack_messages(x)
+    return data, off, None
+
+
+class aead:
+    """Batched RFC 8439 ChaCha20-Poly1305 (rofl_aead_seal / rofl_aead_open): what encrypts the share bundles a server relays between
+    clients.  A record is CT || tag, 16 bytes longer than its payload: libsodium's crypto_aead_chacha20poly1305_ietf combined form, which any
+    standard library opens.  keys: uint8[n_keys, 32]; record i uses keys[key_idx[i]] (key_idx None: keys[i]).  With derive_round=None a key
+    is the RFC 8439 key itself; with derive_round=r a row is a key_agreement.shared_secrets output and the key is
+    SHAKE256("rofl-zk/seal/v1\\0" || row || u64le(r))[0 .. 32), derived once per key on the device.  nonces: uint8[n, 12].  ads, plaintexts and
+    sealed each come as a list of bytes-likes, as a 2-D uint8 array of equal-length rows, or as a pre-packed (uint8[total], uint64[n + 1])
+    pair; the array forms do not go through a Python-level join.  Not constant-time.  A (key, nonce) pair that seals two different payloads
+    gives away both and the authenticator: the caller owns nonce uniqueness."""
+
+    @staticmethod
+    def _args(keys, nonces, ads, key_idx, derive_round):
+        k = _keys32(keys, "a key")
+        nc = np.ascontiguousarray(np.asarray(nonces, dtype=np.uint8) if not isinstance(nonces, (list, tuple))
+                                  else np.array([np.frombuffer(bytes(v), dtype=np.uint8) for v in nonces], dtype=np.uint8).reshape(-1, 12))
+        if nc.size % 12 or (nc.ndim > 1 and nc.shape[-1] != 12):
+            raise ValueError("nonces are uint8[n, 12]")
+        nc = nc.reshape(-1, 12)
+        n = nc.shape[0]
+        ad, ad_off, _ = _packed(ads, "ads")
+        if ad_off.size != n + 1:
+            raise ValueError("one AD per nonce")
+        idx = None
+        if key_idx is None:
+            if k.shape[0] != n:
+                raise ValueError("without key_idx there is one key per record")
+        else:
+            ki = np.asarray(key_idx, dtype=np.int64).reshape(-1)
+            if ki.size != n or (n and (ki.min() < 0 or ki.max() >= k.shape[0])):
+                raise ValueError("key_idx names one key of the call per record")
+            idx = np.ascontiguousarray(ki.astype(np.uint32))
+        rnd = None if derive_round is None else np.array([int(derive_round)], dtype=np.uint64)
+        return k, nc, n, ad, ad_off, idx, rnd
+
+    @staticmethod
+    def seal(keys, nonces, ads, plaintexts, key_idx=None, derive_round=None):
+        """-> the sealed records in the form of `plaintexts`: a list of bytes, uint8[n, length + 16], or the packed pair
+        (uint8[total + 16 n], uint64[n + 1]).  ONE call."""
+        k, nc, n, ad, ad_off, idx, rnd = aead._args(keys, nonces, ads, key_idx, derive_round)
+        pt, pt_off, form = _packed(plaintexts, "plaintexts")
+        if pt_off.size != n + 1:
+            raise ValueError("one plaintext per nonce")
+        total = int(pt_off[-1])
+        out = np.zeros(total + 16 * n, dtype=np.uint8)
+        out_off = pt_off + np.arange(n + 1, dtype=np.uint64) * np.uint64(16)
+        bk, bp = (ctypes.c_ubyte * max(k.size, 1))(), (ctypes.c_ubyte * max(total, 1))()
+        try:
+            ctypes.memmove(bk, k.ctypes.data, k.size)
+            ctypes.memmove(bp, pt.ctypes.data, total)
+            _check(lib().rofl_aead_seal(_sz(k.shape[0]), bk, None if rnd is None else _ptr(rnd), _sz(n), None if idx is None else _ptr(idx), _ptr(nc),
+                                        _ptr(ad) if ad.size else None, _ptr(ad_off), bp if total else None, _ptr(pt_off), _ptr(out)))
+        finally:
+            ctypes.memset(bk, 0, ctypes.sizeof(bk))
+            ctypes.memset(bp, 0, ctypes.sizeof(bp))
+        if form == "packed":
+            return out, out_off
+        if form is None:
+            raw = out.tobytes()
+            return [raw[int(out_off[i]):int(out_off[i + 1])] for i in range(n)]
+        return out.reshape(n, form + 16)
+
+    @staticmethod
+    def open(keys, nonces, ads, sealed, key_idx=None, derive_round=None):
+        """-> (plaintexts, verdicts uint8[n]), ONE call.  Verdict 0: the tag matches; 1: it does not, and the plaintext is zeros; 2: the record
+        is shorter than 16 bytes, and its plaintext is empty.  The tag is checked before anything is decrypted.  The plaintexts come in the
+        form of `sealed`: a list of bytes; uint8[n, length - 16]; or, for a packed pair, (uint8[total], the same offsets) with plaintext i at
+        offset[i], 16 bytes shorter than its record (the layout of the C ABI)."""
+        k, nc, n, ad, ad_off, idx, rnd = aead._args(keys, nonces, ads, key_idx, derive_round)
+        ct, ct_off, form = _packed(sealed, "sealed")
+        if ct_off.size != n + 1:
+            raise ValueError("one sealed record per nonce")
+        total = int(ct_off[-1])
+        pt, verdict = np.zeros(max(total, 1), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        bk = (ctypes.c_ubyte * max(k.size, 1))()
+        try:
+            ctypes.memmove(bk, k.ctypes.data, k.size)
+            _check(lib().rofl_aead_open(_sz(k.shape[0]), bk, None if rnd is None else _ptr(rnd), _sz(n), None if idx is None else _ptr(idx), _ptr(nc),
+                                        _ptr(ad) if ad.size else None, _ptr(ad_off), _ptr(ct) if total else None, _ptr(ct_off), _ptr(pt), _ptr(verdict)))
+        finally:
+            ctypes.memset(bk, 0, ctypes.sizeof(bk))
+        if form == "packed":
+            return (pt[:total], ct_off), verdict
+        if form is None:
+            raw = pt.tobytes()
+            return [raw[int(ct_off[i]):max(int(ct_off[i + 1]) - 16, int(ct_off[i]))] for i in range(n)], verdict
+        return np.ascontiguousarray(pt[:total].reshape(n, form)[:, :max(form - 16, 0)]), verdict
+
+
 def _xs32(xs, n_shares):
     """evaluation points as uint32[n_shares]: nonzero, distinct, each below 2^32"""
     x = np.asarray(xs)
@@ -1079,7 +1184,8 @@ class secret_sharing:
     the secret, t - 1 determine nothing.  A coefficient seed is as secret as the secret it shares.  reconstruct() checks nothing: a wrong
     share reconstructs another scalar without an error.  commit() publishes Feldman commitments of the polynomial and verify_shares() checks
     every share against them, one exact equation per share, so a wrong share is named before it is interpolated
-    (rofl_feldman_commit / rofl_feldman_verify).  The authenticated broadcast of the commitments, the transport of the shares and any
+    (rofl_feldman_commit / rofl_feldman_verify).  sign_commitments / verify_views authenticate the broadcast of the commitments, and
+    seal_shares / open_shares encrypt the shares on their way under a CHANNEL key pair of their own (aead); the transport itself and any
     complaint protocol are the deployment's.  Not constant-time."""
 
     @staticmethod
@@ -1241,6 +1347,93 @@ class secret_sharing:
         dealer equivocated: the verdict names it."""
         n = _keys32(sig_pks, "a public key").shape[0]
         return signatures.verify(sig_pks, [bytes(view)], view_sigs, [(i, 0) for i in range(n)])
+
+    # ---- the shares on their way: every bundle sealed under the pair's channel key of the round (aead.seal / open) ----
+    # A client has THREE key pairs: the mask key (key_agreement; Shamir-shared, and RECONSTRUCTED by the server when its owner drops out), the
+    # signing key (signatures) and the CHANNEL key used here, which is never shared and never revealed.  Were the bundles sealed under a key
+    # derived from the mask keys' shared secret, reconstructing a dropped client's mask key would open every bundle ever sealed to or from it.
+    @staticmethod
+    def bundle_nonce(sender, recipient):
+        """u32le(sender) || u32le(recipient) || u32le(0), 12 bytes: unique per direction under a pair's key of ONE round (the key is derived
+        per round, aead's derive_round), and one bundle goes each way per round."""
+        return struct.pack("<III", int(sender), int(recipient), 0)
+
+    @staticmethod
+    def bundle_ad(round_no, sender, recipient):
+        """b"rofl-zk/shares/1" || u64le(round_no) || u32le(sender) || u32le(recipient), 32 bytes: what a bundle is bound to"""
+        return b"rofl-zk/shares/1" + struct.pack("<QII", int(round_no), int(sender), int(recipient))
+
+    @staticmethod
+    def _bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, own_sends):
+        """The pairs of a seal_shares / open_shares call, own-major: (shared secrets uint8[n, 32], nonces uint8[n, 12], ADs uint8[n, 32], the
+        flat indices of the pairs with own id != peer id, n_own, n_peer); ONE rofl_dh_shared call.  own_sends: the own client is the sender."""
+        own, peer = np.asarray(own_ids, dtype=np.uint32).reshape(-1), np.asarray(peer_ids, dtype=np.uint32).reshape(-1)
+        sk, pk = _keys32(channel_sks, "a channel secret key"), _keys32(peer_channel_pks, "a channel public key")
+        if sk.shape[0] != own.size or pk.shape[0] != peer.size:
+            raise ValueError("one channel secret key per own id and one channel public key per peer id")
+        n_own, n_peer = own.size, peer.size
+        o, p = np.repeat(own, n_peer), np.tile(peer, n_own)
+        keep = np.flatnonzero(o != p)
+        secrets, status = key_agreement.shared_secrets(sk, pk)
+        bad = keep[status[keep] != 0]
+        if bad.size:
+            secrets[...] = 0
+            raise ValueError("peer %d: its channel public key is refused (status %d): no key is derived from it" % (int(p[bad[0]]), int(status[bad[0]])))
+        snd, rcp = (o, p) if own_sends else (p, o)
+        nonces = np.zeros((o.size, 3), dtype="<u4")
+        nonces[:, 0], nonces[:, 1] = snd, rcp
+        ads = np.zeros((o.size, 32), dtype=np.uint8)
+        ads[:, :16] = np.frombuffer(b"rofl-zk/shares/1", dtype=np.uint8)
+        ads[:, 16:24] = np.frombuffer(struct.pack("<Q", int(round_no)), dtype=np.uint8)
+        ads[:, 24:28], ads[:, 28:32] = snd.astype("<u4").view(np.uint8).reshape(-1, 4), rcp.astype("<u4").view(np.uint8).reshape(-1, 4)
+        return secrets, nonces.view(np.uint8).reshape(-1, 12), ads, keep, n_own, n_peer
+
+    @staticmethod
+    def seal_shares(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, key_shares, self_shares):
+        """Every hosted dealer seals its share bundles for all peers: ONE key_agreement.shared_secrets call and ONE aead.seal call.
+        channel_sks[a] is the CHANNEL secret key of dealer own_ids[a] (not its mask key, not its signing key), peer_channel_pks[b] the channel
+        public key of peer_ids[b]; key_shares / self_shares are uint8[n_own, n_peer, 32], [a, b] dealer own_ids[a]'s share for peer_ids[b].
+        The payload is key share || self share (64 bytes), the key the pair's shared secret under derive_round = round_no, the nonce
+        bundle_nonce(sender, recipient), the AD bundle_ad(round_no, sender, recipient).  -> uint8[n_own, n_peer, 80]; the record of a pair
+        with own id == peer id is zeros.  A peer whose channel key is not a canonical encoding or is the identity raises ValueError naming
+        it.  The shared secrets held here are zeroed before the call returns."""
+        secrets, nonces, ads, keep, n_own, n_peer = secret_sharing._bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, True)
+        ks, payload = secrets[keep], None
+        try:
+            k, s = np.asarray(key_shares, dtype=np.uint8), np.asarray(self_shares, dtype=np.uint8)
+            if k.shape != (n_own, n_peer, 32) or s.shape != (n_own, n_peer, 32):
+                raise ValueError("key_shares and self_shares are uint8[n_own, n_peer, 32]")
+            payload = np.concatenate([k, s], axis=2).reshape(-1, 64)[keep]
+            out = np.zeros((n_own * n_peer, 80), dtype=np.uint8)
+            out[keep] = aead.seal(ks, nonces[keep], ads[keep], payload, derive_round=round_no)
+        finally:
+            secrets[...] = 0
+            ks[...] = 0
+            if payload is not None:
+                payload[...] = 0
+        return out.reshape(n_own, n_peer, 80)
+
+    @staticmethod
+    def open_shares(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, records):
+        """Every hosted client opens what it was sent: records uint8[n_own, n_peer, 80], [a, b] what peer_ids[b] sealed for own_ids[a]; ONE
+        key_agreement.shared_secrets call and ONE aead.open call.  -> (key_shares, self_shares uint8[n_own, n_peer, 32], verdicts
+        uint8[n_own, n_peer]): verdict 1 names a bundle that was changed on the way, sealed for somebody else, by somebody else or for another
+        round; its shares are zeros.  The pair with own id == peer id is skipped: verdict 0 and zero shares.  A refused channel key raises
+        ValueError naming the peer.  The shared secrets held here are zeroed before the call returns."""
+        secrets, nonces, ads, keep, n_own, n_peer = secret_sharing._bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, False)
+        ks = secrets[keep]
+        try:
+            rec = np.asarray(records, dtype=np.uint8)
+            if rec.shape != (n_own, n_peer, 80):
+                raise ValueError("records are uint8[n_own, n_peer, 80]")
+            pt, v = aead.open(ks, nonces[keep], ads[keep], np.ascontiguousarray(rec.reshape(-1, 80)[keep]), derive_round=round_no)
+        finally:
+            secrets[...] = 0
+            ks[...] = 0
+        shares, verdict = np.zeros((n_own * n_peer, 64), dtype=np.uint8), np.zeros(n_own * n_peer, dtype=np.uint8)
+        shares[keep], verdict[keep] = pt, v
+        shares = shares.reshape(n_own, n_peer, 64)
+        return np.ascontiguousarray(shares[:, :, :32]), np.ascontiguousarray(shares[:, :, 32:]), verdict.reshape(n_own, n_peer)
 
 
 class pedersen_ops:

@@ -2774,6 +2774,249 @@ __global__ void __launch_bounds__(64) k_sig_verify(u32 n, const uint2 *__restric
     verdict[i] = same ? 0 : 1;
 }
 #endif
+// ================================================================ sealed shares (rofl_aead_seal / rofl_aead_open)
+// RFC 8439 ChaCha20-Poly1305, one record per thread: what encrypts the share bundles that a server relays between clients.
+//   key: a row of the call's keys as it is, or K = SHAKE256("rofl-zk/seal/v1\0" || row || u64le(round))[0 .. 32)    (k_aead_derive, once per key)
+//   block 0 of ChaCha20(key, nonce): its first 32 bytes are the one-time Poly1305 key r || s; the data is encrypted from block 1;
+//   tag = Poly1305(AD || pad16 || CT || pad16 || u64le(len AD) || u64le(len CT)); the record is CT || tag.
+// Padded to 16 bytes, every block the AEAD authenticates is a FULL Poly1305 block (the 2^128 bit set); only rofl_dbg_poly1305 sees the raw
+// ragged tail (a 0x01 byte after the message, no 2^128 bit).  Not constant-time in any promised sense; the nonce is the caller's.
+#define ROFL_SEAL_DOM {0x2f6b7a2d6c666f72ULL, 0x0031762f6c616573ULL}      /* "rofl-zk/" "seal/v1\0" */
+HD u32 rotl32(u32 x, int n) { return (x << n) | (x >> (32 - n)); }
+#define ROFL_CHACHA_QR(a, b, c, d) \
+    x[a] += x[b]; x[d] = rotl32(x[d] ^ x[a], 16); x[c] += x[d]; x[b] = rotl32(x[b] ^ x[c], 12); \
+    x[a] += x[b]; x[d] = rotl32(x[d] ^ x[a], 8);  x[c] += x[d]; x[b] = rotl32(x[b] ^ x[c], 7);
+// one ChaCha20 block (RFC 8439 section 2.3): the sixteen state words stay in registers, the twenty rounds are unrolled
+HD void chacha20_block(u32 out[16], const u32 key[8], u32 counter, const u32 nonce[3]) {
+    const u32 in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7],
+                        counter, nonce[0], nonce[1], nonce[2]};
+    u32 x[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) x[i] = in[i];
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        ROFL_CHACHA_QR(0, 4, 8, 12) ROFL_CHACHA_QR(1, 5, 9, 13) ROFL_CHACHA_QR(2, 6, 10, 14) ROFL_CHACHA_QR(3, 7, 11, 15)
+        ROFL_CHACHA_QR(0, 5, 10, 15) ROFL_CHACHA_QR(1, 6, 11, 12) ROFL_CHACHA_QR(2, 7, 8, 13) ROFL_CHACHA_QR(3, 4, 9, 14)
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) out[i] = x[i] + in[i];
+}
+// Poly1305 on five 26-bit limbs: 25 products of 32 x 32 -> 64 bits per block (v_mad_u64_u32), each column summed in one 64-bit accumulator.
+// Three 44-bit limbs would need 64 x 64 -> 128 products, four 32-bit multiplies and their carries each on this chip, and 64-bit limbs for
+// r, 5 r and h; 5 x 26 keeps r, 5 r and h in fifteen 32-bit registers.
+// Limb bounds: r_i < 2^26 (r_4 < 2^20 after the clamp), 5 r_i < 2^29, h_i < 2^27 once a block is added: a column is below 5 2^56 < 2^59.
+struct poly1305 { u32 r[5], h[5]; };
+// k: the sixteen bytes of r as four little-endian words; the clamp of RFC 8439 section 2.5 is applied here
+HD void poly1305_init(poly1305 &p, const u32 k[4]) {
+    const u32 t0 = k[0] & 0x0fffffffu, t1 = k[1] & 0x0ffffffcu, t2 = k[2] & 0x0ffffffcu, t3 = k[3] & 0x0ffffffcu;
+    p.r[0] = t0 & 0x3ffffffu; p.r[1] = ((t0 >> 26) | (t1 << 6)) & 0x3ffffffu; p.r[2] = ((t1 >> 20) | (t2 << 12)) & 0x3ffffffu;
+    p.r[3] = ((t2 >> 14) | (t3 << 18)) & 0x3ffffffu; p.r[4] = t3 >> 8;
+#pragma unroll
+    for (int i = 0; i < 5; i++) p.h[i] = 0;
+}
+// h = (h + m + hibit 2^128) r mod 2^130 - 5, partially reduced (h_1 may keep one carry); m: sixteen bytes as four little-endian words
+HD void poly1305_block(poly1305 &p, const u32 m[4], u32 hibit) {
+    const u32 r0 = p.r[0], r1 = p.r[1], r2 = p.r[2], r3 = p.r[3], r4 = p.r[4], s1 = r1 * 5, s2 = r2 * 5, s3 = r3 * 5, s4 = r4 * 5;
+    const u32 h0 = p.h[0] + (m[0] & 0x3ffffffu), h1 = p.h[1] + (((m[0] >> 26) | (m[1] << 6)) & 0x3ffffffu),
+              h2 = p.h[2] + (((m[1] >> 20) | (m[2] << 12)) & 0x3ffffffu), h3 = p.h[3] + (((m[2] >> 14) | (m[3] << 18)) & 0x3ffffffu),
+              h4 = p.h[4] + ((m[3] >> 8) | (hibit << 24));
+    u64 d0 = (u64)h0 * r0 + (u64)h1 * s4 + (u64)h2 * s3 + (u64)h3 * s2 + (u64)h4 * s1;
+    u64 d1 = (u64)h0 * r1 + (u64)h1 * r0 + (u64)h2 * s4 + (u64)h3 * s3 + (u64)h4 * s2;
+    u64 d2 = (u64)h0 * r2 + (u64)h1 * r1 + (u64)h2 * r0 + (u64)h3 * s4 + (u64)h4 * s3;
+    u64 d3 = (u64)h0 * r3 + (u64)h1 * r2 + (u64)h2 * r1 + (u64)h3 * r0 + (u64)h4 * s4;
+    u64 d4 = (u64)h0 * r4 + (u64)h1 * r3 + (u64)h2 * r2 + (u64)h3 * r1 + (u64)h4 * r0;
+    d1 += d0 >> 26; d2 += d1 >> 26; d3 += d2 >> 26; d4 += d3 >> 26;
+    const u64 e = (d0 & 0x3ffffffu) + (d4 >> 26) * 5;      // below 2^26 + 5 2^33; 64 bits, no bound on d4 needed
+    p.h[0] = (u32)e & 0x3ffffffu; p.h[1] = ((u32)d1 & 0x3ffffffu) + (u32)(e >> 26);
+    p.h[2] = (u32)d2 & 0x3ffffffu; p.h[3] = (u32)d3 & 0x3ffffffu; p.h[4] = (u32)d4 & 0x3ffffffu;
+}
+// tag = ((h mod 2^130 - 5) + s) mod 2^128 as four little-endian words
+HD void poly1305_finish(u32 tag[4], const poly1305 &p, const u32 s[4]) {
+    u32 h0 = p.h[0], h1 = p.h[1], h2 = p.h[2], h3 = p.h[3], h4 = p.h[4], c;
+    c = h1 >> 26; h1 &= 0x3ffffffu; h2 += c; c = h2 >> 26; h2 &= 0x3ffffffu; h3 += c; c = h3 >> 26; h3 &= 0x3ffffffu; h4 += c;
+    c = h4 >> 26; h4 &= 0x3ffffffu; h0 += c * 5; c = h0 >> 26; h0 &= 0x3ffffffu; h1 += c;      // h < 2^130 + 2^26; h_1 <= 2^26
+    u32 g0 = h0 + 5, g1, g2, g3, g4;                                                          // g = h + 5 - 2^130 = h - p
+    c = g0 >> 26; g0 &= 0x3ffffffu; g1 = h1 + c; c = g1 >> 26; g1 &= 0x3ffffffu; g2 = h2 + c; c = g2 >> 26; g2 &= 0x3ffffffu;
+    g3 = h3 + c; c = g3 >> 26; g3 &= 0x3ffffffu; g4 = h4 + c - (1u << 26);
+    const u32 take_g = (g4 >> 31) - 1u;      // all ones when g did not go below zero: h >= p
+    h0 = (h0 & ~take_g) | (g0 & take_g); h1 = (h1 & ~take_g) | (g1 & take_g); h2 = (h2 & ~take_g) | (g2 & take_g);
+    h3 = (h3 & ~take_g) | (g3 & take_g); h4 = (h4 & ~take_g) | (g4 & take_g);
+    // limbs at bits 0, 26, 52, 78, 104 added up (h_1 may be 2^26: additions, not ORs), then s, carries through 128 bits and no further
+    u64 v = (u64)h0 + ((u64)h1 << 26) + s[0]; tag[0] = (u32)v;
+    v = (v >> 32) + ((u64)h2 << 20) + s[1]; tag[1] = (u32)v;
+    v = (v >> 32) + ((u64)h3 << 14) + s[2]; tag[2] = (u32)v;
+    v = (v >> 32) + ((u64)h4 << 8) + s[3]; tag[3] = (u32)v;
+}
+// the bytes of a sixteen-byte block past its first `valid` set to zero
+HD void block16_keep(u32 m[4], u32 valid /* 0 .. 16 */) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int left = (int)valid - 4 * k;
+        m[k] = left >= 4 ? m[k] : left <= 0 ? 0u : m[k] & ((1u << (8 * left)) - 1u);
+    }
+}
+// Bytes [p, p + valid) of a packed byte string as four little-endian words, the rest zero.  A record starts at ANY byte, so a word is put
+// together from the two aligned words that hold it, as k_sig_digest does (`base` is 4-byte aligned); only aligned words that hold one of the
+// bytes asked for are read.
+__device__ __forceinline__ void load_block16(u32 m[4], const uint8_t *__restrict__ base, u64 p, u32 valid /* 1 .. 16 */) {
+    const u32 mis = (u32)p & 3u, sh = 8 * mis, end = mis + valid;
+    const u32 *a = reinterpret_cast<const u32 *>(base + (p - mis));
+    u32 w[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) w[k] = 4u * k < end ? a[k] : 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) m[k] = sh ? (w[k] >> sh) | (w[k + 1] << (32 - sh)) : w[k];
+    block16_keep(m, valid);
+}
+// the first `valid` bytes of a block to dst: whole words where dst is word-aligned and the block is full, single bytes otherwise (records are
+// packed back to back, so a word at a ragged edge is shared with the neighbour's thread)
+__device__ __forceinline__ void store_block16(uint8_t *__restrict__ dst, const u32 m[4], u32 valid /* 1 .. 16 */) {
+    if (valid == 16 && ((uintptr_t)dst & 3u) == 0) {
+        u32 *d = reinterpret_cast<u32 *>(dst);
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = m[k];
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k++) if ((u32)k < valid) dst[k] = (uint8_t)(m[k >> 2] >> (8 * (k & 3)));
+}
+// bytes [o, o + len) of a packed string into the authenticator, the last block padded with zeros to sixteen bytes
+__device__ __forceinline__ void aead_absorb(poly1305 &P, const uint8_t *__restrict__ base, u64 o, u64 len) {
+    for (u64 pos = 0; pos < len; pos += 16) {
+        u32 m[4];
+        load_block16(m, base, o + pos, (u32)(len - pos < 16 ? len - pos : 16));
+        poly1305_block(P, m, 1);
+    }
+}
+// what seal and open share: key and nonce of record i, block 0, the authenticator keyed with its first half; s: its second half
+__device__ __forceinline__ void aead_begin(u32 i, const u32 *__restrict__ key_idx, const u32 *__restrict__ keys, const u32 *__restrict__ nonce, u32 key[8], u32 nc[3],
+                                           poly1305 &P, u32 s[4]) {
+    const u32 *kp = keys + 8 * (size_t)(key_idx ? key_idx[i] : i), *np = nonce + 3 * (size_t)i;
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = kp[w];
+#pragma unroll
+    for (int w = 0; w < 3; w++) nc[w] = np[w];
+    u32 ks[16];
+    chacha20_block(ks, key, 0, nc);
+    poly1305_init(P, ks);
+#pragma unroll
+    for (int w = 0; w < 4; w++) s[w] = ks[4 + w];
+}
+__device__ __forceinline__ void aead_tag(u32 tag[4], poly1305 &P, const u32 s[4], u64 ad_len, u64 ct_len) {
+    const u32 m[4] = {(u32)ad_len, (u32)(ad_len >> 32), (u32)ct_len, (u32)(ct_len >> 32)};
+    poly1305_block(P, m, 1);
+    poly1305_finish(tag, P, s);
+}
+#if ROFL_KG(2)
+// keys[a] = SHAKE256("rofl-zk/seal/v1\0" || keys[a] || u64le(round))[0 .. 32), in place, one thread per key: 56 bytes, one Keccak block
+__global__ void __launch_bounds__(64) k_aead_derive(u32 n_keys, u64 round, u64 *__restrict__ keys /* [n_keys][4] */) {
+    const u32 a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_keys) return;
+    const u64 dom[2] = ROFL_SEAL_DOM;
+    u64 *row = keys + 4 * (size_t)a, m[7], st[25];
+    m[0] = dom[0]; m[1] = dom[1]; m[6] = round;
+#pragma unroll
+    for (int w = 0; w < 4; w++) m[2 + w] = row[w];
+    shake256_block_words<7>(st, m);
+#pragma unroll
+    for (int w = 0; w < 4; w++) row[w] = st[w];
+}
+// out[pt_off[i] + 16 i ..) = CT_i || tag_i, one thread per record; record i's key is keys[key_idx[i]] (key_idx == nullptr: keys[i]), its
+// nonce nonce[i], its AD ad[ad_off[i] .. ad_off[i + 1]), its payload pt[pt_off[i] .. pt_off[i + 1]).  The lanes of a wave run as many blocks
+// as their own record has; the ragged last ChaCha block and the ragged last Poly1305 blocks of AD and CT are per lane.  A long record is one
+// serial chain on one lane (Poly1305 is a Horner chain, and the blocks of ChaCha are taken in order here).
+__global__ void __launch_bounds__(64) k_aead_seal(u32 n, const u32 *__restrict__ key_idx, const u32 *__restrict__ keys /* [n_keys][8] */, const u32 *__restrict__ nonce /* [n][3] */,
+                                                  const uint8_t *__restrict__ ad, const u64 *__restrict__ ad_off, const uint8_t *__restrict__ pt, const u64 *__restrict__ pt_off,
+                                                  uint8_t *__restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 key[8], nc[3], s[4], ks[16], tag[4];
+    poly1305 P;
+    aead_begin(i, key_idx, keys, nonce, key, nc, P, s);
+    const u64 ao = ad_off[i], alen = ad_off[i + 1] - ao, po = pt_off[i], len = pt_off[i + 1] - po;
+    aead_absorb(P, ad, ao, alen);
+    uint8_t *o = out + po + 16 * (u64)i;
+    for (u64 b = 0; b < len; b += 64) {
+        chacha20_block(ks, key, 1u + (u32)(b >> 6), nc);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const u64 pos = b + 16 * q;
+            if (pos >= len) continue;
+            const u32 valid = (u32)(len - pos < 16 ? len - pos : 16);
+            u32 m[4];
+            load_block16(m, pt, po + pos, valid);
+#pragma unroll
+            for (int w = 0; w < 4; w++) m[w] ^= ks[4 * q + w];
+            block16_keep(m, valid);
+            poly1305_block(P, m, 1);
+            store_block16(o + pos, m, valid);
+        }
+    }
+    aead_tag(tag, P, s, alen, len);
+    store_block16(o + len, tag, 16);
+}
+// Record i = sealed[s_off[i] .. s_off[i + 1]).  Shorter than 16 bytes: verdict 2, nothing written.  Otherwise the tag is computed over the
+// ciphertext FIRST; only a record whose tag matches is decrypted (verdict 0, plaintext at pt_out[s_off[i] ..)), any other gets zeros there
+// (verdict 1).  One thread per record, two passes over the ciphertext.
+__global__ void __launch_bounds__(64) k_aead_open(u32 n, const u32 *__restrict__ key_idx, const u32 *__restrict__ keys /* [n_keys][8] */, const u32 *__restrict__ nonce /* [n][3] */,
+                                                  const uint8_t *__restrict__ ad, const u64 *__restrict__ ad_off, const uint8_t *__restrict__ sealed, const u64 *__restrict__ s_off,
+                                                  uint8_t *__restrict__ pt_out, uint8_t *__restrict__ verdict) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u64 so = s_off[i], rlen = s_off[i + 1] - so;
+    if (rlen < 16) { verdict[i] = 2; return; }
+    const u64 len = rlen - 16, ao = ad_off[i], alen = ad_off[i + 1] - ao;
+    u32 key[8], nc[3], s[4], ks[16], tag[4], got[4];
+    poly1305 P;
+    aead_begin(i, key_idx, keys, nonce, key, nc, P, s);
+    aead_absorb(P, ad, ao, alen);
+    aead_absorb(P, sealed, so, len);
+    aead_tag(tag, P, s, alen, len);
+    load_block16(got, sealed, so + len, 16);
+    const bool bad = ((tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3])) != 0;
+    uint8_t *o = pt_out + so;
+    for (u64 b = 0; b < len; b += 64) {
+        if (!bad) chacha20_block(ks, key, 1u + (u32)(b >> 6), nc);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const u64 pos = b + 16 * q;
+            if (pos >= len) continue;
+            const u32 valid = (u32)(len - pos < 16 ? len - pos : 16);
+            u32 m[4] = {0, 0, 0, 0};
+            if (!bad) {
+                load_block16(m, sealed, so + pos, valid);
+#pragma unroll
+                for (int w = 0; w < 4; w++) m[w] ^= ks[4 * q + w];
+            }
+            store_block16(o + pos, m, valid);
+        }
+    }
+    verdict[i] = bad ? 1 : 0;
+}
+// tag[j] = Poly1305 of message j = msg[off[j] .. off[j + 1]) under key[j] = r || s, one thread per message: the authenticator of the two
+// kernels above on inputs that an AEAD call cannot choose (r, s and a raw ragged tail)
+__global__ void __launch_bounds__(64) k_dbg_poly1305(u32 n, const u32 *__restrict__ key /* [n][8] */, const uint8_t *__restrict__ msg, const u64 *__restrict__ off, u32 *__restrict__ tag_out /* [n][4] */) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    u32 k[8], m[4], tag[4];
+#pragma unroll
+    for (int w = 0; w < 8; w++) k[w] = key[8 * (size_t)j + w];
+    poly1305 P;
+    poly1305_init(P, k);
+    const u64 o = off[j], len = off[j + 1] - o, full = len & ~(u64)15;
+    const u32 rem = (u32)len & 15u;
+    for (u64 pos = 0; pos < full; pos += 16) { load_block16(m, msg, o + pos, 16); poly1305_block(P, m, 1); }
+    if (rem) {
+        load_block16(m, msg, o + full, rem);
+#pragma unroll
+        for (int w = 0; w < 4; w++) if ((rem >> 2) == (u32)w) m[w] |= 1u << (8 * (rem & 3u));
+        poly1305_block(P, m, 0);
+    }
+    poly1305_finish(tag, P, k + 4);
+#pragma unroll
+    for (int w = 0; w < 4; w++) tag_out[4 * (size_t)j + w] = tag[w];
+}
+#endif
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(TPB) k_sigma_finish_batch(int kind, u32 d, u32 fp_bits, u32 fp_frac, const SgClient *cl, DMerlin init, u32 *status /* [gridDim.y] */) {
     const SgClient &c = cl[blockIdx.y];

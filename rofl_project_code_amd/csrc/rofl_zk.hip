@@ -3000,6 +3000,259 @@ int rofl_dbg_host_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, 
     }
     return ROFL_OK;
 }
+// ---- sealed shares: RFC 8439 ChaCha20-Poly1305 under pairwise keys on the share bundles a server relays (k_aead_derive, k_aead_seal / k_aead_open) ----
+}  // extern "C"
+namespace {
+// one packed byte string of a call: offsets that start at 0 and do not decrease, a total within `max_total`; what: "AD" / "payload" / "record"
+int aead_check_off(const char *what, size_t n, const uint64_t *off, const uint8_t *bytes, uint64_t max_one, uint64_t max_total, size_t *total) {
+    char buf[128];
+    if (off[0] != 0) { snprintf(buf, sizeof buf, "the first %s offset is 0", what); return fail(ROFL_BAD_PARAM, buf); }
+    for (size_t i = 0; i < n; i++) {
+        if (off[i + 1] < off[i]) { snprintf(buf, sizeof buf, "%s offset %zu is below the one before it", what, i + 1); return fail(ROFL_BAD_PARAM, buf); }
+        if (off[i + 1] - off[i] > max_one) { snprintf(buf, sizeof buf, "%s %zu is longer than 2^24 bytes", what, i); return fail(ROFL_BAD_PARAM, buf); }
+        if (off[i + 1] > max_total) { snprintf(buf, sizeof buf, "more than 2^30 %s bytes in one call (at %s %zu)", what, what, i); return fail(ROFL_BAD_PARAM, buf); }
+    }
+    *total = (size_t)off[n];
+    if (*total && !bytes) { snprintf(buf, sizeof buf, "a null pointer: the %s bytes", what); return fail(ROFL_BAD_PARAM, buf); }
+    return ROFL_OK;
+}
+// every check of rofl_aead_seal / rofl_aead_open, shared with their host routes.  data / data_off: the payloads (seal) or the sealed records
+// (open), whose lengths are 16 more; out: what the call writes; *done: the call is empty and returns 0.  Texts name indices, never bytes.
+int aead_check(bool seal, size_t n_keys, const uint8_t *key32, size_t n, const uint32_t *key_idx, const uint8_t *nonce12, const uint8_t *ad_bytes, const uint64_t *ad_off,
+               const uint8_t *data, const uint64_t *data_off, const uint8_t *out, const uint8_t *verdict, size_t *ad_total, size_t *data_total, bool *done) {
+    *done = n == 0; *ad_total = *data_total = 0;
+    if (*done) return ROFL_OK;
+    if (n > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 records in one call");
+    if (n_keys > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 keys in one call");
+    if (n_keys == 0) return fail(ROFL_BAD_PARAM, "records without keys");
+    if (!key32) return fail(ROFL_BAD_PARAM, "a null pointer: the keys");
+    if (!nonce12) return fail(ROFL_BAD_PARAM, "a null pointer: the nonces");
+    if (!ad_off) return fail(ROFL_BAD_PARAM, "a null pointer: the AD offsets");
+    if (!data_off) return fail(ROFL_BAD_PARAM, seal ? "a null pointer: the payload offsets" : "a null pointer: the record offsets");
+    if (!seal && !verdict) return fail(ROFL_BAD_PARAM, "a null pointer: the verdicts");
+    if (!key_idx && n_keys != n) return fail(ROFL_BAD_PARAM, "without a key index list n_keys is n");
+    if (key_idx) for (size_t i = 0; i < n; i++)
+        if (key_idx[i] >= n_keys) { char buf[96]; snprintf(buf, sizeof buf, "record %zu names a key that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
+    const uint64_t tagged = seal ? 0 : 16;      // a sealed record carries its tag
+    if (int rc = aead_check_off("AD", n, ad_off, ad_bytes, ~(uint64_t)0, (uint64_t)1 << 30, ad_total)) return rc;
+    if (int rc = aead_check_off(seal ? "payload" : "record", n, data_off, data, ((uint64_t)1 << 24) + tagged, ((uint64_t)1 << 30) + tagged * n, data_total)) return rc;
+    if (!out && (seal || *data_total)) return fail(ROFL_BAD_PARAM, "a null pointer: the output");
+    return ROFL_OK;
+}
+// the key of a call's row: the row itself, or SHAKE256("rofl-zk/seal/v1\0" || row || u64le(round))[0 .. 32) on the host's sponge
+void aead_host_key(uint32_t key[8], const uint8_t *row, const uint64_t *derive_round) {
+    if (!derive_round) { memcpy(key, row, 32); return; }
+    uint8_t m[56] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 's', 'e', 'a', 'l', '/', 'v', '1', 0};
+    memcpy(m + 16, row, 32); memcpy(m + 48, derive_round, 8);
+    Sponge sp(136, 0x1F); sp.absorb(m, sizeof m); sp.squeeze(reinterpret_cast<uint8_t *>(key), 32);
+    dh_wipe(m, sizeof m); dh_wipe(&sp, sizeof sp);
+}
+// `len` bytes into the authenticator, the last block padded with zeros to sixteen bytes (every block full: the AEAD's framing)
+void aead_host_absorb(poly1305 &P, const uint8_t *p, uint64_t len) {
+    for (uint64_t pos = 0; pos < len; pos += 16) {
+        uint32_t m[4] = {0, 0, 0, 0};
+        memcpy(m, p + pos, (size_t)std::min<uint64_t>(16, len - pos));
+        poly1305_block(P, m, 1);
+    }
+}
+// block 0 -> the authenticator's key; then the tag over AD and CT
+void aead_host_tag(uint32_t tag[4], const uint32_t key[8], const uint32_t nc[3], const uint8_t *ad, uint64_t alen, const uint8_t *ct, uint64_t len) {
+    uint32_t ks[16];
+    chacha20_block(ks, key, 0, nc);
+    poly1305 P; poly1305_init(P, ks);
+    aead_host_absorb(P, ad, alen); aead_host_absorb(P, ct, len);
+    const uint32_t m[4] = {(uint32_t)alen, (uint32_t)(alen >> 32), (uint32_t)len, (uint32_t)(len >> 32)};
+    poly1305_block(P, m, 1);
+    poly1305_finish(tag, P, ks + 4);
+    dh_wipe(ks, sizeof ks); dh_wipe(&P, sizeof P);
+}
+// dst = src ^ ChaCha20 keystream from block 1
+void aead_host_xor(uint8_t *dst, const uint8_t *src, uint64_t len, const uint32_t key[8], const uint32_t nc[3]) {
+    uint32_t ks[16];
+    for (uint64_t b = 0; b < len; b += 64) {
+        chacha20_block(ks, key, 1u + (uint32_t)(b >> 6), nc);
+        const uint8_t *k = reinterpret_cast<const uint8_t *>(ks);
+        for (uint64_t q = 0; q < 64 && b + q < len; q++) dst[b + q] = src[b + q] ^ k[q];
+    }
+    dh_wipe(ks, sizeof ks);
+}
+// layout of the lane's upload for the two calls: [keys | payloads or records | ADs | nonces | AD offsets | data offsets | key indices]; every
+// part 8-byte aligned, each byte string followed by 8 spare bytes (the kernels read whole aligned words)
+struct AeadLayout { size_t data, ad, nonce, ad_off, data_off, idx, bytes; };
+AeadLayout aead_layout(size_t n_keys, size_t n, bool has_idx, size_t ad_total, size_t data_total) {
+    auto pad = [](size_t b) { return ((b + 7) & ~(size_t)7) + 8; };
+    AeadLayout l;
+    l.data = n_keys * 32; l.ad = l.data + pad(data_total); l.nonce = l.ad + pad(ad_total); l.ad_off = l.nonce + ((n * 12 + 7) & ~(size_t)7);
+    l.data_off = l.ad_off + (n + 1) * 8; l.idx = l.data_off + (n + 1) * 8; l.bytes = l.idx + (has_idx ? n * 4 : 0);
+    return l;
+}
+// the upload both calls make, and the key derivation where asked for; `secret`: the leading bytes of the upload that are wiped afterwards
+uint8_t *aead_upload(Ctx &C, BlindWipe &wipe, const AeadLayout &l, size_t secret, size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n,
+                     const uint32_t *key_idx, const uint8_t *nonce12, const uint8_t *ad_bytes, const uint64_t *ad_off, size_t ad_total,
+                     const uint8_t *data, const uint64_t *data_off, size_t data_total) {
+    uint8_t *hu = C.h_misc.as<uint8_t>(l.bytes), *du = C.tmp_in.as<uint8_t>(l.bytes);
+    wipe.h = hu; wipe.dv = du; wipe.n = secret; wipe.s = C.stream;
+    memcpy(hu, key32, n_keys * 32);
+    if (data_total) memcpy(hu + l.data, data, data_total);
+    memset(hu + l.data + data_total, 0, l.ad - l.data - data_total);
+    if (ad_total) memcpy(hu + l.ad, ad_bytes, ad_total);
+    memset(hu + l.ad + ad_total, 0, l.nonce - l.ad - ad_total);
+    memcpy(hu + l.nonce, nonce12, n * 12); memset(hu + l.nonce + n * 12, 0, l.ad_off - l.nonce - n * 12);
+    memcpy(hu + l.ad_off, ad_off, (n + 1) * 8); memcpy(hu + l.data_off, data_off, (n + 1) * 8);
+    if (key_idx) memcpy(hu + l.idx, key_idx, n * 4);
+    HIPCHK(hipMemcpyAsync(du, hu, l.bytes, hipMemcpyHostToDevice, C.stream));
+    if (derive_round) ROFL_LAUNCH(k_aead_derive, dim3((unsigned)((n_keys + 63) / 64)), dim3(64), 0, C.stream, (u32)n_keys, (u64)*derive_round, reinterpret_cast<u64 *>(du));
+    return du;
+}
+// a packed list of messages for the Poly1305 hooks
+int poly_check(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, const uint8_t *tag_out16, size_t *total, bool *done) {
+    *done = n == 0; *total = 0;
+    if (*done) return ROFL_OK;
+    if (!key32 || !msg_off || !tag_out16) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 messages in one call");
+    return aead_check_off("message", n, msg_off, msg_bytes, (uint64_t)1 << 24, (uint64_t)1 << 30, total);
+}
+}  // namespace
+extern "C" {
+// The lane's copies of the keys (as given and derived) and of the plaintexts -- pinned staging and device workspace -- are overwritten with
+// zeros before the call returns or unwinds; keystream and authenticator keys live in registers only.  The sealed records are public.
+int rofl_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                   const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes, const uint64_t *pt_off, uint8_t *sealed_out) {
+    bool done; size_t ad_total, pt_total;
+    if (int rc = aead_check(true, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, pt_bytes, pt_off, sealed_out, nullptr, &ad_total, &pt_total, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        const AeadLayout l = aead_layout(n_keys, n, key_idx != nullptr, ad_total, pt_total);
+        const size_t dn_bytes = pt_total + 16 * n;
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        BlindWipe wipe_secrets;
+        const uint8_t *du = aead_upload(C, wipe_secrets, l, l.ad, n_keys, key32, derive_round, n, key_idx, nonce12, ad_bytes, ad_off, ad_total, pt_bytes, pt_off, pt_total);
+        ROFL_LAUNCH(k_aead_seal, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, key_idx ? reinterpret_cast<const u32 *>(du + l.idx) : (const u32 *)nullptr,
+                    reinterpret_cast<const u32 *>(du), reinterpret_cast<const u32 *>(du + l.nonce), du + l.ad, reinterpret_cast<const u64 *>(du + l.ad_off),
+                    du + l.data, reinterpret_cast<const u64 *>(du + l.data_off), dd);
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(sealed_out, hd, dn_bytes);
+        return ROFL_OK;
+    });
+}
+// the keys in the upload and the plaintexts in the download are wiped the same way; records, ADs, nonces and verdicts are public
+int rofl_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                   const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes, const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out) {
+    bool done; size_t ad_total, s_total;
+    if (int rc = aead_check(false, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, sealed_bytes, sealed_off, pt_out, verdict_out, &ad_total, &s_total, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // download: [plaintexts, laid out like the records | verdict bytes]
+        const AeadLayout l = aead_layout(n_keys, n, key_idx != nullptr, ad_total, s_total);
+        const size_t dn_bytes = s_total + n;
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        BlindWipe wipe_keys, wipe_out;
+        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = s_total; wipe_out.s = C.stream;
+        const uint8_t *du = aead_upload(C, wipe_keys, l, n_keys * 32, n_keys, key32, derive_round, n, key_idx, nonce12, ad_bytes, ad_off, ad_total, sealed_bytes, sealed_off, s_total);
+        ROFL_LAUNCH(k_aead_open, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, key_idx ? reinterpret_cast<const u32 *>(du + l.idx) : (const u32 *)nullptr,
+                    reinterpret_cast<const u32 *>(du), reinterpret_cast<const u32 *>(du + l.nonce), du + l.ad, reinterpret_cast<const u64 *>(du + l.ad_off),
+                    du + l.data, reinterpret_cast<const u64 *>(du + l.data_off), dd, dd + s_total);
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(verdict_out, hd + s_total, n);
+        for (size_t i = 0; i < n; i++)      // a record shorter than its tag writes nothing; the 16 bytes after a plaintext are not the library's
+            if (verdict_out[i] != 2 && sealed_off[i + 1] - sealed_off[i] > 16) memcpy(pt_out + sealed_off[i], hd + sealed_off[i], (size_t)(sealed_off[i + 1] - sealed_off[i] - 16));
+        return ROFL_OK;
+    });
+}
+// the two calls in plain C++ on one thread, no GPU: same parameters, same checks, same bytes
+int rofl_dbg_host_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                            const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes, const uint64_t *pt_off, uint8_t *sealed_out) {
+    bool done; size_t ad_total, pt_total;
+    if (int rc = aead_check(true, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, pt_bytes, pt_off, sealed_out, nullptr, &ad_total, &pt_total, &done)) return rc;
+    if (done) return ROFL_OK;
+    std::vector<uint32_t> keys(n_keys * 8);
+    for (size_t a = 0; a < n_keys; a++) aead_host_key(keys.data() + 8 * a, key32 + 32 * a, derive_round);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t *key = keys.data() + 8 * (key_idx ? key_idx[i] : i);
+        const uint64_t len = pt_off[i + 1] - pt_off[i], alen = ad_off[i + 1] - ad_off[i];
+        uint32_t nc[3], tag[4];
+        memcpy(nc, nonce12 + 12 * i, 12);
+        uint8_t *o = sealed_out + pt_off[i] + 16 * i;
+        aead_host_xor(o, pt_bytes + pt_off[i], len, key, nc);
+        aead_host_tag(tag, key, nc, ad_bytes + ad_off[i], alen, o, len);
+        memcpy(o + len, tag, 16);
+    }
+    dh_wipe(keys.data(), keys.size() * 4);
+    return ROFL_OK;
+}
+int rofl_dbg_host_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                            const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes, const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out) {
+    bool done; size_t ad_total, s_total;
+    if (int rc = aead_check(false, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, sealed_bytes, sealed_off, pt_out, verdict_out, &ad_total, &s_total, &done)) return rc;
+    if (done) return ROFL_OK;
+    std::vector<uint32_t> keys(n_keys * 8);
+    for (size_t a = 0; a < n_keys; a++) aead_host_key(keys.data() + 8 * a, key32 + 32 * a, derive_round);
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t rlen = sealed_off[i + 1] - sealed_off[i], alen = ad_off[i + 1] - ad_off[i];
+        if (rlen < 16) { verdict_out[i] = 2; continue; }
+        const uint32_t *key = keys.data() + 8 * (key_idx ? key_idx[i] : i);
+        const uint8_t *ct = sealed_bytes + sealed_off[i];
+        uint32_t nc[3], tag[4];
+        memcpy(nc, nonce12 + 12 * i, 12);
+        aead_host_tag(tag, key, nc, ad_bytes + ad_off[i], alen, ct, rlen - 16);      // the tag over the ciphertext first
+        verdict_out[i] = memcmp(tag, ct + rlen - 16, 16) == 0 ? 0 : 1;
+        if (verdict_out[i]) { if (rlen > 16) memset(pt_out + sealed_off[i], 0, (size_t)(rlen - 16)); }
+        else aead_host_xor(pt_out + sealed_off[i], ct, rlen - 16, key, nc);
+    }
+    dh_wipe(keys.data(), keys.size() * 4);
+    return ROFL_OK;
+}
+// Poly1305 of n messages under n keys r || s through the kernels' own device functions (k_dbg_poly1305, one thread per message)
+int rofl_dbg_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16) {
+    bool done; size_t total;
+    if (int rc = poly_check(n, key32, msg_bytes, msg_off, tag_out16, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: [keys | offsets | message bytes and 8 spare]; download: the tags
+        const size_t up_off = n * 32, up_msg = up_off + (n + 1) * 8, up_bytes = up_msg + ((total + 7) & ~(size_t)7) + 8;
+        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(n * 16), *dd = C.tmp_out.as<uint8_t>(n * 16);
+        memcpy(hu, key32, n * 32); memcpy(hu + up_off, msg_off, (n + 1) * 8);
+        if (total) memcpy(hu + up_msg, msg_bytes, total);
+        memset(hu + up_msg + total, 0, up_bytes - up_msg - total);
+        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_dbg_poly1305, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, reinterpret_cast<const u32 *>(du), (const uint8_t *)(du + up_msg),
+                    reinterpret_cast<const u64 *>(du + up_off), reinterpret_cast<u32 *>(dd));
+        HIPCHK(hipMemcpyAsync(hd, dd, n * 16, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(tag_out16, hd, n * 16);
+        return ROFL_OK;
+    });
+}
+int rofl_dbg_host_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16) {
+    bool done; size_t total;
+    if (int rc = poly_check(n, key32, msg_bytes, msg_off, tag_out16, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    for (size_t j = 0; j < n; j++) {
+        uint32_t k[8], m[4], tag[4];
+        memcpy(k, key32 + 32 * j, 32);
+        poly1305 P; poly1305_init(P, k);
+        const uint8_t *p = msg_bytes + msg_off[j];
+        const uint64_t len = msg_off[j + 1] - msg_off[j], full = len & ~(uint64_t)15;
+        for (uint64_t pos = 0; pos < full; pos += 16) { memcpy(m, p + pos, 16); poly1305_block(P, m, 1); }
+        if (len & 15) {
+            uint8_t last[16] = {0};
+            memcpy(last, p + full, (size_t)(len & 15)); last[len & 15] = 1;
+            memcpy(m, last, 16); poly1305_block(P, m, 0);
+        }
+        poly1305_finish(tag, P, k + 4);
+        memcpy(tag_out16 + 16 * j, tag, 16);
+    }
+    return ROFL_OK;
+}
 // conversion32::f32_to_fp_vec / uint_to_f32_vec (conversion32.rs:41-54): Fix is unsigned, negative inputs saturate to 0
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out) {
     if (!valid_fp(fp_bits, fp_frac)) return fail(ROFL_BAD_PARAM, "bad parameter");

@@ -417,8 +417,9 @@ int rofl_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *x
  * commit to a secret of low entropy.  The commitments must come over an AUTHENTICATED broadcast: a dealer that shows different commitments
  * to different clients defeats the check.  rofl_sig_sign / rofl_sig_verify (further below) are that authentication: every dealer signs its
  * commitments, every client signs its view of everybody's, and a dealer that equivocated is named by the view round.  How the bytes travel,
- * how the shares travel (their encryption on the way is rofl_aead_seal / rofl_aead_open, further below), and what happens after a complaint
- * stay the deployment's business.
+ * how the shares travel (their encryption on the way is rofl_aead_seal / rofl_aead_open, further below) stay the deployment's business.  A
+ * complaint against a dealer is JUDGED by rofl_dleq_prove / rofl_dleq_verify (further below); what a round does with the party the ruling
+ * names, and a dealer that sends nothing, stay the deployment's as well.
  * rofl_feldman_commit: commitments_out32[s][k] = C_k of secret s, secret-major.  rofl_feldman_verify: one set of points for all secrets
  * (xs == NULL means 1 .. n_shares), verdict_out[s][i] for shares32[s][i] at xs[i]; threshold <= n_shares is NOT required -- a client checks
  * the one share it received against t commitments.  Every commitment is decoded once, whatever the number of shares.  A call on a subset of
@@ -465,8 +466,9 @@ int rofl_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commi
  * holds it then signs in its owner's name.  What signatures give a round: the sender of a key or of commitments is authenticated, and the
  * view round (every client signs the digest of all dealers' signatures it saw; secret_sharing.view_message in the Python binding) makes
  * equivocation DETECTABLE and names the client that was shown something else.  What they do not give: who of dealer and relay equivocated
- * (both signatures on two different commitment sets convict the dealer, one does not convict the relay), what happens after (the complaint
- * protocol), the transport and the round's state machine -- those stay the deployment's. */
+ * (both signatures on two different commitment sets convict the dealer, one does not convict the relay), the transport, the round's state
+ * machine and what a round does with a convicted party -- those stay the deployment's.  A complaint about a SHARE is judged with
+ * rofl_dleq_prove / rofl_dleq_verify (below). */
 typedef struct { uint32_t key, msg; } rofl_sig_ref_t;
 int rofl_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32 /* may be NULL */,
                   size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off /* n_msgs + 1 */,
@@ -516,6 +518,51 @@ int rofl_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t *derive_r
                    const uint8_t *sealed_bytes, const uint64_t *sealed_off /* n + 1 */,
                    uint8_t *pt_out /* sealed_off[n] bytes: plaintext i at sealed_off[i], len_i - 16 bytes */,
                    uint8_t *verdict_out /* n */);
+/* Complaints: batched Chaum-Pedersen proofs of discrete-log equality (DLEQ), what lets a third party JUDGE a complaint against a dealer.  A
+ * client that opened its bundle and found a share that fails rofl_feldman_verify cannot show that to anybody: the bundle is sealed under a
+ * key only the pair holds.  The complainant therefore reveals the pair's raw DH point S and proves that S was made with the secret behind
+ * its public channel key; anyone can then derive the pair's key, open the record the dealer SIGNED, and run the Feldman check.  Every label
+ * is exactly 16 bytes; B, the reduction of a key, encode and decode are those of rofl_dh_public_keys / rofl_dh_shared.
+ *   statement: A = encode(x B) the prover's public key, P the peer's public key, S = encode(x decode(P)) the reveal, ctx 32 bytes of the
+ *     caller's that bind the proof to its use;
+ *   nonce: k = int_le(SHAKE256("rofl-zk/dleq/v1k" || canonical32(x) || P || ctx)[0 .. 64)) mod l (112 bytes, one Keccak block); k = 0 is not
+ *     special-cased;
+ *   commitments: T1 = encode(k B), T2 = encode(k decode(P));
+ *   challenge: c = int_le(SHAKE256("rofl-zk/dleq/v1c" || A || P || S || T1 || T2 || ctx)[0 .. 64)) mod l (208 bytes, two blocks);
+ *   response: s = k + c x mod l; the proof is canonical32(c) || canonical32(s), 64 bytes, deterministic like the signatures;
+ *   verdict byte per proof, a malformed input before a failing equation:
+ *     2 = A or P is not a canonical Ristretto encoding or is the identity, S is not a canonical encoding or is the identity, c >= l or
+ *         s >= l (so no non-canonical alias of a valid proof verifies);
+ *     0 = c equals the challenge recomputed from A, P, S, T1' = encode(s B - c decode(A)), T2' = encode(s decode(P) - c decode(S)), ctx;
+ *     1 = anything else.
+ *   A bad proof condemns itself, not the call, as with rofl_dh_shared and rofl_sig_verify.
+ *   shared secret: for verdict 0 shared_out32 (may be NULL) receives exactly the 32 bytes rofl_dh_shared gives for the pair,
+ *     SHAKE256("rofl-zk/dh/v1\0\0\0" || S || lo || hi)[0 .. 32); every other proof gets 32 zero bytes.  They go to
+ *     rofl_aead_open(derive_round = ...) unchanged.
+ * Pair i uses own key pairs[i].own and peer key pairs[i].peer; pairs == NULL means all n_own x n_peer pairs, own-major; ctx, reveal, proof,
+ * status and verdict are per pair.  In rofl_dleq_prove a refused peer key gives status 1 (not canonical) or 2 (the identity) and a zero
+ * reveal and proof for that pair only.  Host pointers only.  The limits and checks are those of rofl_dh_shared: both return 11 before the
+ * device is touched for a null pointer (except pairs, own_pk_out32, shared_out32), n_own or n_peer = 0 with n_pairs > 0, n_own or
+ * n_peer above 2^20, n_pairs above 2^24, pairs == NULL with n_pairs != n_own x n_peer, a pair index out of range (the text names the pair),
+ * and for prove an own key that is 0 mod l (the text names the index, never a key byte); n_pairs = 0 returns 0 and touches no device.  One
+ * lane, one upload, one download; prove launches k_dh_public, k_dh_decode and k_dleq_prove, verify k_dh_decode over both key tables and
+ * k_dleq_verify: every key is multiplied out or decoded once, whatever the number of pairs it is in.  rofl_dleq_prove overwrites its pinned
+ * staging copies and the device workspace that held the keys with zeros before it returns or unwinds; the nonces live in registers only.
+ * rofl_dleq_verify does the same for the shared secrets it hands back.  The `devices` option does not apply.
+ * What is NOT promised: the paths are NOT constant-time, like every other secret-scalar path of this library, and the nonce is
+ * deterministic (prove on hardware you trust).  What a reveal COSTS: S opens that pair's channel in BOTH directions for every round of the
+ * channel keys' epoch (the per-round keys are hashes of it), so whoever judges learns one share of each of the two clients' secrets per
+ * round -- those shares count against the threshold -- and the pair re-keys afterwards.  What stays the deployment's: the transport, the
+ * state machine, what the round does with a convicted party, and a dealer that sends nothing (silence proves nothing to a third party). */
+int rofl_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32 /* may be NULL */,
+                    size_t n_peer, const uint8_t *peer_pk32,
+                    size_t n_pairs, const rofl_dh_pair_t *pairs /* NULL: all, own-major */,
+                    const uint8_t *ctx32 /* n_pairs x 32 */,
+                    uint8_t *reveal_out32 /* n_pairs x 32 */, uint8_t *proof_out64 /* n_pairs x 64 */, uint8_t *status_out /* n_pairs */);
+int rofl_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const uint8_t *peer_pk32,
+                     size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
+                     const uint8_t *reveal32, const uint8_t *proof64,
+                     uint8_t *shared_out32 /* may be NULL */, uint8_t *verdict_out /* n_pairs */);
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out);         /* conversion32.rs:49-54 */
 int rofl_uint_to_f32_vec(const uint64_t *in, size_t d, unsigned fp_bits, unsigned fp_frac, float *out);        /* conversion32.rs:41-47 */
 int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float *out);  /* conversion32.rs:62-64 */

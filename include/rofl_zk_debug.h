@@ -166,6 +166,19 @@ int rofl_dbg_host_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t 
 int rofl_dbg_poly1305(size_t n, const uint8_t *key32 /* n x 32 */, const uint8_t *msg_bytes, const uint64_t *msg_off /* n + 1 */,
                       uint8_t *tag_out16 /* n x 16 */);
 int rofl_dbg_host_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16);
+/* rofl_dleq_prove / rofl_dleq_verify on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: the same
+ * parameters, the same checks (11) and the same bytes.  What the host tests pin the definition with, and the baseline of profiles/dleq.json. */
+int rofl_dbg_host_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs,
+                             const rofl_dh_pair_t *pairs, const uint8_t *ctx32, uint8_t *reveal_out32, uint8_t *proof_out64, uint8_t *status_out);
+int rofl_dbg_host_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs,
+                              const rofl_dh_pair_t *pairs, const uint8_t *ctx32, const uint8_t *reveal32, const uint8_t *proof64,
+                              uint8_t *shared_out32, uint8_t *verdict_out);
+/* out32[i] = encode(k1[i] decode(p1[i]) + k2[i] decode(p2[i])) through the kernels' own device functions, one thread per item, n <= 2^24:
+ * rofl_dbg_var_mul2 on the joint chain sg_var_mul2 (two tables, one chain of doublings), rofl_dbg_var_mul_sum as the sum of two sg_var_mul
+ * products.  Scalars are reduced mod l; a point that does not decode counts as the identity.  *kernel_ms (may be NULL): the launch alone,
+ * between two events on the lane's stream -- the A/B of profiles/dleq.json. */
+int rofl_dbg_var_mul2(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms);
+int rofl_dbg_var_mul_sum(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms);
 
 /* host micro-benchmarks of the code the per-round hops run (nanoseconds per operation on the calling core).
  * what: 0 Keccak-f[1600]; 1 point doubling, 2 point addition, 3 Ristretto encoding (51-bit host arithmetic);

@@ -206,6 +206,16 @@ extern "C" {
     /// verdict_out[i]: 0 opened (plaintext at pt_out[sealed_off[i] ..)), 1 the tag does not match (zeros there), 2 shorter than 16 bytes
     pub fn rofl_aead_open(n_keys: usize, key32: *const u8, derive_round: *const u64, n: usize, key_idx: *const u32, nonce12: *const u8,
         ad_bytes: *const u8, ad_off: *const u64, sealed_bytes: *const u8, sealed_off: *const u64, pt_out: *mut u8, verdict_out: *mut u8) -> c_int;
+    /// A complaint against a dealer: pair i = (own key pairs[i].own, peer key pairs[i].peer), null = all pairs own-major; reveal i is the pair's
+    /// raw DH point, proof i the 64-byte DLEQ proof that it was made with the own key, bound to ctx32[i]; a refused peer key gives status 1 / 2
+    /// and zeros; own_pk_out32 may be null
+    pub fn rofl_dleq_prove(n_own: usize, sk32: *const u8, own_pk_out32: *mut u8, n_peer: usize, peer_pk32: *const u8,
+        n_pairs: usize, pairs: *const RoflDhPair, ctx32: *const u8, reveal_out32: *mut u8, proof_out64: *mut u8, status_out: *mut u8) -> c_int;
+    /// verdict_out[i]: 0 the proof holds (shared_out32[i], may be null, is then the pair's rofl_dh_shared secret), 1 it does not, 2 a key or
+    /// the reveal is not a canonical encoding or is the identity, or c or s >= l
+    pub fn rofl_dleq_verify(n_own: usize, own_pk32: *const u8, n_peer: usize, peer_pk32: *const u8,
+        n_pairs: usize, pairs: *const RoflDhPair, ctx32: *const u8, reveal32: *const u8, proof64: *const u8,
+        shared_out32: *mut u8, verdict_out: *mut u8) -> c_int;
     pub fn rofl_f32_to_fp_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut u64) -> c_int;
     pub fn rofl_uint_to_f32_vec(input: *const u64, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
     pub fn rofl_get_l2_clip_bounds(range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;

@@ -1058,6 +1058,70 @@ class signatures:
         return out
 
 
+def _dh_pairs(pairs, n_own, n_peer):
+    """(n_pairs, ctypes array or None) of a pair list [(own, peer), ...]; None = all n_own x n_peer pairs, own-major"""
+    if pairs is None:
+        return n_own * n_peer, None
+    pl = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n_pairs = pl.shape[0]
+    if n_pairs and (pl.min() < 0 or pl[:, 0].max() >= n_own or pl[:, 1].max() >= n_peer):
+        raise ValueError("a pair names a key that is not in the call")
+    parr = (_DhPair * max(n_pairs, 1))()
+    np.frombuffer(parr, dtype=np.uint32)[:2 * n_pairs] = pl.astype(np.uint32).reshape(-1)
+    return n_pairs, parr
+
+
+class dleq:
+    """Batched Chaum-Pedersen proofs of discrete-log equality over Ristretto255 (rofl_dleq_prove / rofl_dleq_verify): what lets a third
+    party judge a complaint about a sealed share.  The holder of x behind A = encode(x B) reveals S = encode(x decode(P)), the raw DH point
+    of its pair with the peer key P, and proves that S was made with that x: k from SHAKE256("rofl-zk/dleq/v1k" || canonical32(x) || P ||
+    ctx), T1 = encode(k B), T2 = encode(k decode(P)), c from SHAKE256("rofl-zk/dleq/v1c" || A || P || S || T1 || T2 || ctx), s = k + c x;
+    the proof is c || s, 64 bytes, the same for the same inputs.  ctx is 32 bytes that bind a proof to its use.  Not constant-time;
+    deterministic nonces.  A reveal opens the pair's channel in both directions for the whole epoch of the two keys: re-key afterwards."""
+
+    @staticmethod
+    def prove(sks, peer_pks, ctxs, pairs=None, with_public=False):
+        """Reveals and proofs of own keys sks (n_own) against peer public keys peer_pks (n_peer), ONE call: pairs as in
+        key_agreement.shared_secrets, ctxs uint8[n_pairs, 32].  -> (reveals uint8[n_pairs, 32], proofs uint8[n_pairs, 64], status
+        uint8[n_pairs]); status 1 = the peer key is not a canonical Ristretto encoding, 2 = it is the identity, and reveal and proof of such a
+        pair are zero.  with_public=True appends the own public keys uint8[n_own, 32]."""
+        sk, pk, cx = _keys32(sks, "a secret key"), _keys32(peer_pks, "a public key"), _keys32(ctxs, "a context")
+        n_own, n_peer = sk.shape[0], pk.shape[0]
+        n_pairs, parr = _dh_pairs(pairs, n_own, n_peer)
+        if cx.shape[0] != n_pairs:
+            raise ValueError("one context per pair")
+        reveal, proof, status = np.zeros((n_pairs, 32), dtype=np.uint8), np.zeros((n_pairs, 64), dtype=np.uint8), np.zeros(n_pairs, dtype=np.uint8)
+        own_pk = np.zeros((n_own, 32), dtype=np.uint8) if with_public else None
+        buf = (ctypes.c_ubyte * max(n_own * 32, 1))()
+        try:
+            ctypes.memmove(buf, sk.ctypes.data, n_own * 32)
+            _check(lib().rofl_dleq_prove(_sz(n_own), buf, _ptr(own_pk) if with_public else None, _sz(n_peer), _ptr(pk), _sz(n_pairs), parr, _ptr(cx),
+                                         _ptr(reveal), _ptr(proof), _ptr(status)))
+        finally:
+            ctypes.memset(buf, 0, ctypes.sizeof(buf))
+        if with_public and n_pairs == 0 and n_own:      # (an empty call computes nothing: the keys come from their own entry)
+            own_pk = key_agreement.public_keys(sk)
+        return (reveal, proof, status, own_pk) if with_public else (reveal, proof, status)
+
+    @staticmethod
+    def verify(own_pks, peer_pks, ctxs, reveals, proofs, pairs=None):
+        """-> (verdicts uint8[n_pairs], shared uint8[n_pairs, 32]), ONE call: verdict 0 = the proof holds, 1 = it does not, 2 = a key or the
+        reveal is not a canonical Ristretto encoding or is the identity, or c or s >= l.  shared is the key_agreement.shared_secrets output of
+        the pair for verdict 0 and zeros otherwise: it opens what the pair sealed, so zero it when done."""
+        a, pk, cx = _keys32(own_pks, "a public key"), _keys32(peer_pks, "a public key"), _keys32(ctxs, "a context")
+        n_own, n_peer = a.shape[0], pk.shape[0]
+        n_pairs, parr = _dh_pairs(pairs, n_own, n_peer)
+        rv = _keys32(reveals, "a reveal")
+        pf = np.ascontiguousarray(np.asarray(proofs, dtype=np.uint8))
+        if pf.size != n_pairs * 64 or (pf.ndim > 1 and pf.shape[-1] != 64):
+            raise ValueError("proofs are uint8[n_pairs, 64]")
+        if cx.shape[0] != n_pairs or rv.shape[0] != n_pairs:
+            raise ValueError("one context and one reveal per pair")
+        verdict, shared = np.zeros(n_pairs, dtype=np.uint8), np.zeros((n_pairs, 32), dtype=np.uint8)
+        _check(lib().rofl_dleq_verify(_sz(n_own), _ptr(a), _sz(n_peer), _ptr(pk), _sz(n_pairs), parr, _ptr(cx), _ptr(rv), _ptr(pf), _ptr(shared), _ptr(verdict)))
+        return verdict, shared
+
+
 def _packed(x, what):
     """Byte strings as the C ABI takes them -> (uint8[total], uint64[n + 1], form).  Three forms are accepted: a pre-packed
     (uint8[total], uint64[n + 1]) pair (form "packed"); a 2-D uint8 array of equal-length rows (form = the row length; no Python-level
@@ -1185,8 +1249,10 @@ class secret_sharing:
     share reconstructs another scalar without an error.  commit() publishes Feldman commitments of the polynomial and verify_shares() checks
     every share against them, one exact equation per share, so a wrong share is named before it is interpolated
     (rofl_feldman_commit / rofl_feldman_verify).  sign_commitments / verify_views authenticate the broadcast of the commitments, and
-    seal_shares / open_shares encrypt the shares on their way under a CHANNEL key pair of their own (aead); the transport itself and any
-    complaint protocol are the deployment's.  Not constant-time."""
+    seal_shares / open_shares encrypt the shares on their way under a CHANNEL key pair of their own (aead).  sign_bundles makes every
+    sealed record attributable, file_complaints opens one pair's channel to a judge with a DLEQ proof (dleq), and judge_complaints rules
+    who of complainant and dealer is at fault.  The transport, the round's state machine, what a round does with a convicted party and a
+    dealer that sends nothing are the deployment's.  Not constant-time."""
 
     @staticmethod
     def share(secrets, coef_seeds, threshold, n_shares, xs=None):
@@ -1434,6 +1500,143 @@ class secret_sharing:
         shares[keep], verdict[keep] = pt, v
         shares = shares.reshape(n_own, n_peer, 64)
         return np.ascontiguousarray(shares[:, :, :32]), np.ascontiguousarray(shares[:, :, 32:]), verdict.reshape(n_own, n_peer)
+
+    # ---- a complaint against a dealer: the dealer SIGNS every sealed record, the complainant opens the pair's channel to a judge (dleq) ----
+    # A client whose opened share fails verify_shares can name the dealer, but nobody else can check the claim: the record is sealed under a
+    # key only the two hold.  With the dealer's signature on the record the complainant can reveal the pair's DH point with a proof that it
+    # is the right one (file_complaints), and anyone re-derives the key, opens the signed record and runs the Feldman check
+    # (judge_complaints).  The reveal opens that pair's channel in BOTH directions for the whole epoch of the channel keys: the judge learns
+    # one share of each of the two clients' secrets per round, and the pair re-keys afterwards.
+    @staticmethod
+    def bundle_message(round_no, sender, recipient, record):
+        """The bytes a dealer signs for one sealed record: b"rofl-zk/sealed/1" || u64le(round_no) || u32le(sender) || u32le(recipient) ||
+        record (80 bytes), 112 bytes"""
+        rec = np.ascontiguousarray(np.asarray(record, dtype=np.uint8)).reshape(-1)
+        if rec.size != 80:
+            raise ValueError("a sealed record is 80 bytes")
+        return b"rofl-zk/sealed/1" + struct.pack("<QII", int(round_no), int(sender), int(recipient)) + rec.tobytes()
+
+    @staticmethod
+    def _bundle_messages(round_no, own_ids, peer_ids, records):
+        own, peer = [int(i) for i in own_ids], [int(i) for i in peer_ids]
+        rec = np.asarray(records, dtype=np.uint8)
+        if rec.shape != (len(own), len(peer), 80):
+            raise ValueError("records are uint8[n_own, n_peer, 80]")
+        msgs = [secret_sharing.bundle_message(round_no, o, p, rec[a, b]) for a, o in enumerate(own) for b, p in enumerate(peer)]
+        return msgs, [(a, a * len(peer) + b) for a in range(len(own)) for b in range(len(peer))]
+
+    @staticmethod
+    def sign_bundles(sig_sks, round_no, own_ids, peer_ids, records):
+        """Every hosted dealer signs the records it sealed (seal_shares' output uint8[n_own, n_peer, 80]), ONE signatures.sign call:
+        sig_sks[a] is the SIGNING key of dealer own_ids[a].  -> uint8[n_own, n_peer, 64].  The signature is what makes a record
+        attributable: a record without a valid one is a missing record, not grounds for a complaint."""
+        msgs, refs = secret_sharing._bundle_messages(round_no, own_ids, peer_ids, records)
+        if _keys32(sig_sks, "a secret key").shape[0] != len(own_ids):
+            raise ValueError("one signing key per own id")
+        return signatures.sign(sig_sks, msgs, refs).reshape(len(own_ids), len(peer_ids), 64)
+
+    @staticmethod
+    def verify_bundle_signatures(sig_pks, round_no, own_ids, peer_ids, records, sigs):
+        """The signatures sigs uint8[n_own, n_peer, 64] of sign_bundles under the senders' public signing keys sig_pks[a] (sender own_ids[a],
+        recipient peer_ids[b]), ONE signatures.verify call -> uint8[n_own, n_peer] verdicts.  A recipient checks these on receipt."""
+        msgs, refs = secret_sharing._bundle_messages(round_no, own_ids, peer_ids, records)
+        if _keys32(sig_pks, "a public key").shape[0] != len(own_ids):
+            raise ValueError("one public signing key per own id")
+        sg = np.asarray(sigs, dtype=np.uint8)
+        if sg.shape != (len(own_ids), len(peer_ids), 64):
+            raise ValueError("sigs are uint8[n_own, n_peer, 64]")
+        return signatures.verify(sig_pks, msgs, sg.reshape(-1, 64), refs).reshape(len(own_ids), len(peer_ids))
+
+    @staticmethod
+    def complaint_context(round_no, complainant, dealer):
+        """SHA3-256(b"rofl-zk/complain" || u64le(round_no) || u32le(complainant) || u32le(dealer)), 32 bytes: what binds a complaint's proof
+        to its round and its two parties (computed on the host, like the self-mask seed)"""
+        return hashlib.sha3_256(b"rofl-zk/complain" + struct.pack("<QII", int(round_no), int(complainant), int(dealer))).digest()
+
+    @staticmethod
+    def file_complaints(channel_sks, own_ids, dealer_ids, dealer_channel_pks, round_no, which):
+        """The hosted clients' complaints which = [(own id, dealer id), ...], ONE dleq.prove call: channel_sks[a] is the CHANNEL secret key of
+        own_ids[a], dealer_channel_pks[b] the channel public key of dealer_ids[b].  -> (reveals uint8[n, 32], proofs uint8[n, 64]), one per
+        entry of `which`, bound to complaint_context(round_no, own id, dealer id).  A refused dealer key raises ValueError naming the dealer."""
+        own, dealers = [int(i) for i in own_ids], [int(i) for i in dealer_ids]
+        which = [(int(o), int(d)) for o, d in which]
+        for o, d in which:
+            if o not in own or d not in dealers:
+                raise ValueError("complaint (%d, %d) names a client that is not in the call" % (o, d))
+        pairs = [(own.index(o), dealers.index(d)) for o, d in which]
+        ctxs = np.frombuffer(b"".join(secret_sharing.complaint_context(round_no, o, d) for o, d in which), dtype=np.uint8).reshape(-1, 32)
+        reveals, proofs, status = dleq.prove(channel_sks, dealer_channel_pks, ctxs, pairs)
+        if status.any():
+            i = int(np.flatnonzero(status)[0])
+            raise ValueError("dealer %d: its channel public key is refused (status %d): nothing is revealed against it" % (which[i][1], int(status[i])))
+        return reveals, proofs
+
+    @staticmethod
+    def judge_complaints(round_no, complaints, channel_pks, sig_pks, key_commitments, self_commitments):
+        """Rule on complaints = [(complainant, dealer, record, record_sig, reveal, proof), ...]: the 80-byte record the dealer sent, the
+        dealer's signature on it (sign_bundles), and the complainant's reveal and proof (file_complaints).  channel_pks, sig_pks,
+        key_commitments and self_commitments are indexed by client id (arrays or dicts); the commitments were signature-checked earlier.
+        Exactly ONE call each of signatures.verify, dleq.verify, aead.open (on the shared secrets that came back, derive_round = round_no)
+        and verify_shares (the dealers and the points complainant + 1 that occur; grid entries no complaint names are ignored).
+        -> [(at_fault, reason), ...] per complaint, the first that applies:
+          4  the record's signature does not verify under the dealer's signing key        -> the complainant
+          3  the DLEQ verdict is 1 or 2                                                   -> the complainant
+          1  the record does not open under the proven key                                -> the dealer
+          0  a share of the opened bundle is inconsistent with the dealer's commitments   -> the dealer
+          2  the record opens and both shares are consistent                              -> the complainant
+        A commitment row with verdict 2 raises ValueError naming the dealer.  The shared secrets and opened shares held here are zeroed
+        before the call returns."""
+        cs = [(int(c[0]), int(c[1])) for c in complaints]
+        n = len(cs)
+        if n == 0:
+            return []
+        if len(set(cs)) != n:
+            raise ValueError("two complaints name the same (complainant, dealer): one record per pair and round")
+        rec = np.stack([np.asarray(c[2], dtype=np.uint8).reshape(-1) for c in complaints])
+        if rec.shape != (n, 80):
+            raise ValueError("a sealed record is 80 bytes")
+        row = lambda table, i: np.asarray(table[i], dtype=np.uint8)      # noqa: E731
+        sig_v = signatures.verify(np.stack([row(sig_pks, d) for _, d in cs]), [secret_sharing.bundle_message(round_no, d, c, rec[i]) for i, (c, d) in enumerate(cs)],
+                                  np.stack([np.asarray(c[3], dtype=np.uint8).reshape(-1) for c in complaints]))
+        ctxs = np.frombuffer(b"".join(secret_sharing.complaint_context(round_no, c, d) for c, d in cs), dtype=np.uint8).reshape(-1, 32)
+        proof_v, shared = dleq.verify(np.stack([row(channel_pks, c) for c, _ in cs]), np.stack([row(channel_pks, d) for _, d in cs]), ctxs,
+                                      np.stack([np.asarray(c[4], dtype=np.uint8).reshape(-1) for c in complaints]),
+                                      np.stack([np.asarray(c[5], dtype=np.uint8).reshape(-1) for c in complaints]), [(i, i) for i in range(n)])
+        opened = shares = None
+        try:
+            nonces = np.frombuffer(b"".join(secret_sharing.bundle_nonce(d, c) for c, d in cs), dtype=np.uint8).reshape(-1, 12)
+            ads = np.frombuffer(b"".join(secret_sharing.bundle_ad(round_no, d, c) for c, d in cs), dtype=np.uint8).reshape(-1, 32)
+            opened, open_v = aead.open(shared, nonces, ads, rec, derive_round=round_no)
+            dealers, points = sorted({d for _, d in cs}), sorted({c + 1 for c, _ in cs})
+            com = np.stack([row(key_commitments, d) for d in dealers] + [row(self_commitments, d) for d in dealers])
+            shares = np.zeros((2 * len(dealers), len(points), 32), dtype=np.uint8)
+            at = [(dealers.index(d), points.index(c + 1)) for c, d in cs]
+            for i, (r, x) in enumerate(at):
+                shares[r, x], shares[len(dealers) + r, x] = opened[i, :32], opened[i, 32:]
+            share_v = secret_sharing.verify_shares(com, points, shares)
+            refused = np.flatnonzero((share_v == 2).any(axis=1))
+            if refused.size:
+                raise ValueError("dealer %d: a commitment of its %s row is not a canonical encoding" % (dealers[int(refused[0]) % len(dealers)],
+                                                                                                      "key" if refused[0] < len(dealers) else "self"))
+            out = []
+            for i, (c, d) in enumerate(cs):
+                r, x = at[i]
+                if sig_v[i]:
+                    out.append((c, 4))
+                elif proof_v[i]:
+                    out.append((c, 3))
+                elif open_v[i]:
+                    out.append((d, 1))
+                elif share_v[r, x] or share_v[len(dealers) + r, x]:
+                    out.append((d, 0))
+                else:
+                    out.append((c, 2))
+            return out
+        finally:
+            shared[...] = 0
+            for a in (opened, shares):
+                if a is not None:
+                    a[...] = 0
 
 
 class pedersen_ops:

@@ -2211,19 +2211,48 @@ __global__ void __launch_bounds__(64) k_fixed_tab8(const niels *tab4, niels *tab
 }
 #endif
 __device__ inline gd gd_neg(const gd &p) { gd r; r.X = fd_neg(p.X); r.Y = p.Y; r.Z = p.Z; r.T = fd_neg(p.T); return r; }
-// k * P, signed radix-16 windows, k canonical (< 2^253)
-__device__ inline gd sg_var_mul(const sc &k, const gd &P) {
-    ge tab[8];                                          // packed 1P..8P (local memory)
+// the parts of a variable-base product on signed radix-16 windows: the packed table 1P..8P (local memory), the 65 digits of a canonical
+// scalar (< 2^253; no digit for a zero window), and the addition of one window's table entry
+__device__ inline void sg_var_tab(ge tab[8], const gd &P) {
     gd cur = P; tab[0] = gd_pack(cur);
     for (int e = 1; e < 8; e++) { cur = gd_add(cur, P); tab[e] = gd_pack(cur); }
-    int8_t dg[65]; int carry = 0;
+}
+__device__ inline void sg_var_digits(int8_t dg[65], const sc &k) {
+    int carry = 0;
     for (int i = 0; i < 64; i++) { int v = (int)((k.v[i >> 3] >> ((i & 7) * 4)) & 15) + carry; carry = (v + 8) >> 4; dg[i] = (int8_t)(v - (carry << 4)); }
     dg[64] = (int8_t)carry;
+}
+__device__ inline gd sg_var_window(const gd &acc, const ge tab[8], int d) {
+    const int ad = d < 0 ? -d : d;
+    if (!ad) return acc;
+    gd q = gd_unpack(tab[ad - 1]); if (d < 0) q = gd_neg(q);
+    return gd_add(acc, q);
+}
+// k * P, signed radix-16 windows, k canonical (< 2^253)
+__device__ inline gd sg_var_mul(const sc &k, const gd &P) {
+    ge tab[8];
+    sg_var_tab(tab, P);
+    int8_t dg[65];
+    sg_var_digits(dg, k);
     gd acc = gd_identity();
     for (int i = 64; i >= 0; i--) {
         if (i != 64) { acc = gd_double(acc); acc = gd_double(acc); acc = gd_double(acc); acc = gd_double(acc); }
-        int d = dg[i], ad = d < 0 ? -d : d;
-        if (ad) { gd q = gd_unpack(tab[ad - 1]); if (d < 0) q = gd_neg(q); acc = gd_add(acc, q); }
+        acc = sg_var_window(acc, tab, dg[i]);
+    }
+    return acc;
+}
+// k1 * P1 + k2 * P2 on ONE chain of doublings: two packed tables, the signed radix-16 digits of both scalars (k1, k2 canonical) -- 256
+// doublings instead of the 512 of two sg_var_mul calls, for a second table in local memory
+__device__ inline gd sg_var_mul2(const sc &k1, const gd &P1, const sc &k2, const gd &P2) {
+    ge tab1[8], tab2[8];
+    sg_var_tab(tab1, P1); sg_var_tab(tab2, P2);
+    int8_t d1[65], d2[65];
+    sg_var_digits(d1, k1); sg_var_digits(d2, k2);
+    gd acc = gd_identity();
+    for (int i = 64; i >= 0; i--) {
+        if (i != 64) { acc = gd_double(acc); acc = gd_double(acc); acc = gd_double(acc); acc = gd_double(acc); }
+        acc = sg_var_window(acc, tab1, d1[i]);
+        acc = sg_var_window(acc, tab2, d2[i]);
     }
     return acc;
 }
@@ -2431,7 +2460,47 @@ template <int W> __device__ __forceinline__ void shake256_block_words(u64 st[25]
     keccak_f1600(st);
 }
 __device__ __forceinline__ void shake256_block14(u64 st[25], const u64 m[14]) { shake256_block_words<14>(st, m); }
+// Two-block SHAKE256 of W little-endian words, 17 < W <= 33 (up to 264 bytes): the first 17 words fill the 136-byte rate
+template <int W> __device__ __forceinline__ void shake256_two_block_words(u64 st[25], const u64 m[W]) {
+    static_assert(W > 17 && W <= 33, "two blocks, the suffix in a word of its own");
+#pragma unroll
+    for (int i = 0; i < 25; i++) st[i] = i < 17 ? m[i] : 0;
+    keccak_f1600(st);
+#pragma unroll
+    for (int i = 0; i < W - 17; i++) st[i] ^= m[17 + i];
+    st[W - 17] ^= 0x1FULL;               // SHAKE domain suffix right after 8 W bytes
+    st[16] ^= 0x8000000000000000ULL;
+    keccak_f1600(st);
+}
 #define ROFL_DH_DOM {0x2f6b7a2d6c666f72ULL, 0x00000031762f6864ULL}      /* "rofl-zk/" "dh/v1\0\0\0" */
+// the encoding of a point as four little-endian words, the form the one-block hashes take it in
+__device__ __forceinline__ void sg_encode_words(u64 w4[4], const gd &p) {
+    uint8_t E[32];
+    sg_encode(E, p);
+#pragma unroll
+    for (int w = 0; w < 4; w++) { u64 v = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) v |= (u64)E[8 * w + q] << (8 * q);
+        w4[w] = v; }
+}
+// o[0 .. 32) = the shared secret of a pair from the words of S = encode(a decode(P_b)) and of the two public keys, in either order
+__device__ __forceinline__ void dh_secret_store(uint4 *o, const u64 S[4], const u64 ka[4], const u64 kb[4]) {
+    const u64 dom[2] = ROFL_DH_DOM;
+    u64 m[14], st25[25];
+    m[0] = dom[0]; m[1] = dom[1];
+    // byte-string order: the first differing byte decides, so compare the words from the front with their bytes swapped
+    bool a_first = true, decided = false;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        const u64 x = __builtin_bswap64(ka[w]), y = __builtin_bswap64(kb[w]);
+        if (!decided && x != y) { a_first = x < y; decided = true; }
+    }
+#pragma unroll
+    for (int w = 0; w < 4; w++) { m[2 + w] = S[w]; m[6 + w] = a_first ? ka[w] : kb[w]; m[10 + w] = a_first ? kb[w] : ka[w]; }
+    shake256_block14(st25, m);
+    o[0] = make_uint4((u32)st25[0], (u32)(st25[0] >> 32), (u32)st25[1], (u32)(st25[1] >> 32));
+    o[1] = make_uint4((u32)st25[2], (u32)(st25[2] >> 32), (u32)st25[3], (u32)(st25[3] >> 32));
+}
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(64) k_dh_public(u32 n, const sc *__restrict__ sk, const niels *tabB8, uint8_t *__restrict__ pk) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2460,32 +2529,13 @@ __global__ void __launch_bounds__(64) k_dh_shared(u32 n_pairs, u32 n_peer, const
     status[i] = (uint8_t)st;
     uint4 *o = reinterpret_cast<uint4 *>(out + (size_t)32 * i);
     if (st) { o[0] = make_uint4(0, 0, 0, 0); o[1] = make_uint4(0, 0, 0, 0); return; }
-    uint8_t S[32];
-    sg_encode(S, sg_var_mul(load_sc_reduced(&sk[a]), load_gd(&peer_pts[b])));
-    const u64 dom[2] = ROFL_DH_DOM;
-    u64 m[14], st25[25];
-    m[0] = dom[0]; m[1] = dom[1];
-#pragma unroll
-    for (int w = 0; w < 4; w++) { u64 v = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) v |= (u64)S[8 * w + q] << (8 * q);
-        m[2 + w] = v; }
+    u64 S[4];
+    sg_encode_words(S, sg_var_mul(load_sc_reduced(&sk[a]), load_gd(&peer_pts[b])));
     const u64 *pa = reinterpret_cast<const u64 *>(own_pk + (size_t)32 * a), *pb = reinterpret_cast<const u64 *>(peer_pk + (size_t)32 * b);
     u64 ka[4], kb[4];
 #pragma unroll
     for (int w = 0; w < 4; w++) { ka[w] = pa[w]; kb[w] = pb[w]; }
-    // byte-string order: the first differing byte decides, so compare the words from the front with their bytes swapped
-    bool a_first = true, decided = false;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const u64 x = __builtin_bswap64(ka[w]), y = __builtin_bswap64(kb[w]);
-        if (!decided && x != y) { a_first = x < y; decided = true; }
-    }
-#pragma unroll
-    for (int w = 0; w < 4; w++) { m[6 + w] = a_first ? ka[w] : kb[w]; m[10 + w] = a_first ? kb[w] : ka[w]; }
-    shake256_block14(st25, m);
-    o[0] = make_uint4((u32)st25[0], (u32)(st25[0] >> 32), (u32)st25[1], (u32)(st25[1] >> 32));
-    o[1] = make_uint4((u32)st25[2], (u32)(st25[2] >> 32), (u32)st25[3], (u32)(st25[3] >> 32));
+    dh_secret_store(o, S, ka, kb);
 }
 #endif
 // ================================================================ secret sharing (rofl_shamir_share / rofl_shamir_reconstruct)
@@ -3015,6 +3065,132 @@ __global__ void __launch_bounds__(64) k_dbg_poly1305(u32 n, const u32 *__restric
     poly1305_finish(tag, P, k + 4);
 #pragma unroll
     for (int w = 0; w < 4; w++) tag_out[4 * (size_t)j + w] = tag[w];
+}
+#endif
+// ================================================================ complaints (rofl_dleq_prove / rofl_dleq_verify)
+// A Chaum-Pedersen proof of discrete-log equality: the holder of x behind A = encode(x B) reveals S = encode(x decode(P)), the raw DH point
+// it shares with the peer key P, and proves that S was made with that x.  Whoever checks the proof can derive the pair's shared secret and
+// open what the two sealed for each other.  Labels are 16 bytes, two words like ROFL_DH_DOM; ctx is 32 bytes of the caller's:
+//   k = int_le(SHAKE256("rofl-zk/dleq/v1k" || canonical32(x) || P || ctx)[0 .. 64)) mod l                  (112 bytes: shake256_block14)
+//   T1 = encode(k B), T2 = encode(k decode(P))
+//   c = int_le(SHAKE256("rofl-zk/dleq/v1c" || A || P || S || T1 || T2 || ctx)[0 .. 64)) mod l              (208 bytes: two blocks)
+//   s = k + c x mod l; the proof is canonical32(c) || canonical32(s).
+// Verdict: 2 = A or P is refused by k_dh_decode, S is no canonical encoding or is the identity, c >= l or s >= l; 0 = c equals the challenge
+// recomputed from T1' = encode(s B - c decode(A)) and T2' = encode(s decode(P) - c decode(S)); 1 otherwise.  Not constant-time.
+#define ROFL_DLEQ_DOM_K {0x2f6b7a2d6c666f72ULL, 0x6b31762f71656c64ULL}      /* "rofl-zk/" "dleq/v1k" */
+#define ROFL_DLEQ_DOM_C {0x2f6b7a2d6c666f72ULL, 0x6331762f71656c64ULL}      /* "rofl-zk/" "dleq/v1c" */
+__device__ __forceinline__ sc dleq_challenge(const u64 A[4], const u64 P[4], const u64 S[4], const u64 T1[4], const u64 T2[4], const u64 ctx[4]) {
+    const u64 dom[2] = ROFL_DLEQ_DOM_C;
+    u64 m[26], st[25];
+    m[0] = dom[0]; m[1] = dom[1];
+#pragma unroll
+    for (int w = 0; w < 4; w++) { m[2 + w] = A[w]; m[6 + w] = P[w]; m[10 + w] = S[w]; m[14 + w] = T1[w]; m[18 + w] = T2[w]; m[22 + w] = ctx[w]; }
+    shake256_two_block_words<26>(st, m);
+    return xof_block_scalar(st, 0);
+}
+__device__ __forceinline__ void dleq_load_words(u64 w4[4], const uint8_t *p /* 8-byte aligned */) {
+    const u64 *q = reinterpret_cast<const u64 *>(p);
+#pragma unroll
+    for (int w = 0; w < 4; w++) w4[w] = q[w];
+}
+__device__ __forceinline__ void dleq_store_words(uint4 *o, const u64 w4[4]) {
+    o[0] = make_uint4((u32)w4[0], (u32)(w4[0] >> 32), (u32)w4[1], (u32)(w4[1] >> 32));
+    o[1] = make_uint4((u32)w4[2], (u32)(w4[2] >> 32), (u32)w4[3], (u32)(w4[3] >> 32));
+}
+#if ROFL_KG(4)
+// reveal[i], proof[i] of pair i = (own key a, peer key b); pairs == nullptr: all n_own x n_peer pairs, own-major.  One thread per pair: the
+// nonce block, x P and k P by the variable-base windows, k B from the radix-256 table, three encodings, the two-block challenge, s.  own_pk:
+// the output of a k_dh_public launch; peer_pts / peer_status: k_dh_decode's workspace.  A refused peer key stores its status and zeros.
+// k = 0 is not special: T1 and T2 are then the identity encoding and s = c x.  reveal, proof, ctx: 16-byte aligned.
+__global__ void __launch_bounds__(64) k_dleq_prove(u32 n_pairs, u32 n_peer, const uint2 *__restrict__ pairs, const sc *__restrict__ sk, const uint8_t *__restrict__ own_pk,
+                                                   const uint8_t *__restrict__ peer_pk, const ge *__restrict__ peer_pts, const u32 *__restrict__ peer_status,
+                                                   const uint8_t *__restrict__ ctx /* [n_pairs][32] */, const niels *tabB8,
+                                                   uint8_t *__restrict__ reveal /* [n_pairs][32] */, uint8_t *__restrict__ proof /* [n_pairs][64] */, uint8_t *__restrict__ status) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pairs) return;
+    u32 a, b;
+    if (pairs) { const uint2 p = pairs[i]; a = p.x; b = p.y; } else { a = i / n_peer; b = i - a * n_peer; }
+    const u32 st = peer_status[b];
+    status[i] = (uint8_t)st;
+    uint4 *ro = reinterpret_cast<uint4 *>(reveal + (size_t)32 * i), *po = reinterpret_cast<uint4 *>(proof + (size_t)64 * i);
+    if (st) {
+        const uint4 z = make_uint4(0, 0, 0, 0);
+        ro[0] = z; ro[1] = z; po[0] = z; po[1] = z; po[2] = z; po[3] = z;
+        return;
+    }
+    const sc x = load_sc_reduced(&sk[a]);
+    u64 A[4], P[4], C[4], S[4], T1[4], T2[4];
+    dleq_load_words(A, own_pk + (size_t)32 * a); dleq_load_words(P, peer_pk + (size_t)32 * b); dleq_load_words(C, ctx + (size_t)32 * i);
+    sc k;
+    {   const u64 dom[2] = ROFL_DLEQ_DOM_K;
+        u64 m[14], st25[25];
+        m[0] = dom[0]; m[1] = dom[1];
+#pragma unroll
+        for (int w = 0; w < 4; w++) { m[2 + w] = (u64)x.v[2 * w] | ((u64)x.v[2 * w + 1] << 32); m[6 + w] = P[w]; m[10 + w] = C[w]; }
+        shake256_block14(st25, m);
+        k = xof_block_scalar(st25, 0); }
+    const gd Pg = load_gd(&peer_pts[b]);
+    sg_encode_words(S, sg_var_mul(x, Pg));
+    sg_encode_words(T1, sg_fixed_mul8(tabB8, k));
+    sg_encode_words(T2, sg_var_mul(k, Pg));
+    const sc c = dleq_challenge(A, P, S, T1, T2, C);
+    const sc s = sc_add(k, sc_montmul(sc_to_mont(c), x));      // (c R) x R^-1 = c x, canonical
+    dleq_store_words(ro, S);
+    store_sc(reinterpret_cast<sc *>(po), c);
+    store_sc(reinterpret_cast<sc *>(po + 2), s);
+}
+#endif
+#if ROFL_KG(3)
+// verdict[i] of pair i = (prover key a, peer key b), one thread per pair.  own_pts / own_status, peer_pts / peer_status: k_dh_decode's
+// workspace over the two key tables; S is decoded here (one per pair).  A malformed input stores 2 and computes nothing.  Otherwise
+// T1' = s B + (l - c) decode(A) as k_sig_verify has it, T2' = s decode(P) + (l - c) decode(S), the challenge from their encodings against c.
+// shared (may be nullptr): the pair's rofl_dh_shared secret from S and the two keys for verdict 0, 32 zero bytes otherwise.
+__global__ void __launch_bounds__(64) k_dleq_verify(u32 n_pairs, u32 n_peer, const uint2 *__restrict__ pairs, const uint8_t *__restrict__ own_pk, const ge *__restrict__ own_pts,
+                                                    const u32 *__restrict__ own_status, const uint8_t *__restrict__ peer_pk, const ge *__restrict__ peer_pts,
+                                                    const u32 *__restrict__ peer_status, const uint8_t *__restrict__ ctx /* [n_pairs][32] */,
+                                                    const uint8_t *__restrict__ reveal /* [n_pairs][32] */, const uint8_t *__restrict__ proof /* [n_pairs][64] */, const niels *tabB8,
+                                                    uint8_t *__restrict__ shared /* [n_pairs][32] */, uint8_t *__restrict__ verdict) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pairs) return;
+    u32 a, b;
+    if (pairs) { const uint2 p = pairs[i]; a = p.x; b = p.y; } else { a = i / n_peer; b = i - a * n_peer; }
+    uint4 *so = shared ? reinterpret_cast<uint4 *>(shared + (size_t)32 * i) : nullptr;
+    if (so) { so[0] = make_uint4(0, 0, 0, 0); so[1] = make_uint4(0, 0, 0, 0); }
+    const sc *pp = reinterpret_cast<const sc *>(proof + (size_t)64 * i);
+    const sc c = load_sc(pp), s = load_sc(pp + 1);
+    gd Sg;
+    if (own_status[a] != 0u || peer_status[b] != 0u || sc_geq_l(c.v) || sc_geq_l(s.v) || !sg_decode(Sg, reveal + (size_t)32 * i) || sg_is_identity(Sg)) { verdict[i] = 2; return; }
+    u64 A[4], P[4], C[4], S[4], T1[4], T2[4];
+    dleq_load_words(A, own_pk + (size_t)32 * a); dleq_load_words(P, peer_pk + (size_t)32 * b); dleq_load_words(C, ctx + (size_t)32 * i);
+    dleq_load_words(S, reveal + (size_t)32 * i);
+    const sc nc = sc_neg(c);
+    sg_encode_words(T1, gd_add(sg_fixed_mul8(tabB8, s), sg_var_mul(nc, load_gd(&own_pts[a]))));
+    sg_encode_words(T2, sg_var_mul2(s, load_gd(&peer_pts[b]), nc, Sg));
+    const sc c2 = dleq_challenge(A, P, S, T1, T2, C);
+    bool same = true;
+#pragma unroll
+    for (int w = 0; w < 8; w++) same &= c2.v[w] == c.v[w];
+    verdict[i] = same ? 0 : 1;
+    if (same && so) dh_secret_store(so, S, A, P);
+}
+// out[i] = encode(k1[i] decode(p1[i]) + k2[i] decode(p2[i])), one thread per item, on the joint chain sg_var_mul2 (k_dbg_var_mul2) and as the
+// sum of two sg_var_mul products (k_dbg_var_mul_sum): two kernels, so that each is compiled with the registers and scratch of its own path.
+// Scalars are reduced as keys are; a point that does not decode counts as the identity.
+template <bool JOINT> __device__ __forceinline__ void dbg_var_mul_item(u32 i, const sc *k1, const uint8_t *p1, const sc *k2, const uint8_t *p2, uint8_t *out) {
+    gd P1, P2;
+    sg_decode(P1, p1 + (size_t)32 * i); sg_decode(P2, p2 + (size_t)32 * i);
+    const sc a = load_sc_reduced(&k1[i]), b = load_sc_reduced(&k2[i]);
+    sg_encode(out + (size_t)32 * i, JOINT ? sg_var_mul2(a, P1, b, P2) : gd_add(sg_var_mul(a, P1), sg_var_mul(b, P2)));
+}
+__global__ void __launch_bounds__(64) k_dbg_var_mul2(u32 n, const sc *__restrict__ k1, const uint8_t *__restrict__ p1, const sc *__restrict__ k2, const uint8_t *__restrict__ p2,
+                                                     uint8_t *__restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dbg_var_mul_item<true>(i, k1, p1, k2, p2, out);
+}
+__global__ void __launch_bounds__(64) k_dbg_var_mul_sum(u32 n, const sc *__restrict__ k1, const uint8_t *__restrict__ p1, const sc *__restrict__ k2, const uint8_t *__restrict__ p2,
+                                                        uint8_t *__restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dbg_var_mul_item<false>(i, k1, p1, k2, p2, out);
 }
 #endif
 #if ROFL_KG(4)

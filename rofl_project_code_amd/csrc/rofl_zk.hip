@@ -2435,6 +2435,18 @@ h51::ge5 dh_host_mul(const sc &k, const h51::ge5 &P) {
     dh_wipe(dg, sizeof dg);
     return acc;
 }
+// the shared secret of rofl_dh_shared from S = encode(a decode(P_b)) and the two public keys, in either order
+void dh_host_secret(uint8_t out32[32], const uint8_t S[32], const uint8_t own[32], const uint8_t peer[32]) {
+    uint8_t m[112] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 'd', 'h', '/', 'v', '1', 0, 0, 0};
+    memcpy(m + 16, S, 32);
+    const bool own_first = memcmp(own, peer, 32) <= 0;
+    memcpy(m + 48, own_first ? own : peer, 32); memcpy(m + 80, own_first ? peer : own, 32);
+    u64 st[25]; memset(st, 0, sizeof st); memcpy(st, m, 112);
+    st[14] ^= 0x1FULL; st[16] ^= 0x8000000000000000ULL;
+    keccak_f1600_host(st);
+    memcpy(out32, st, 32);
+    dh_wipe(m, sizeof m); dh_wipe(st, sizeof st);
+}
 const uint8_t kDhBase[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
                              0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};
 }  // namespace
@@ -2508,17 +2520,12 @@ int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint
     if (ge_is_identity_ristretto(P)) { *status = 2; return ROFL_OK; }
     *status = 0;
     sc k = dh_key_scalar(sk32);
-    uint8_t own[32], m[112] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 'd', 'h', '/', 'v', '1', 0, 0, 0};
+    uint8_t own[32], S[32];
     if (own_pk32) memcpy(own, own_pk32, 32);
     else { ge B; ristretto_decode(B, kDhBase); h51::encode(own, dh_host_mul(k, h51::from_ge(B))); }
-    h51::encode(m + 16, dh_host_mul(k, h51::from_ge(P)));
-    const bool own_first = memcmp(own, peer_pk32, 32) <= 0;
-    memcpy(m + 48, own_first ? own : peer_pk32, 32); memcpy(m + 80, own_first ? peer_pk32 : own, 32);
-    u64 st[25]; memset(st, 0, sizeof st); memcpy(st, m, 112);
-    st[14] ^= 0x1FULL; st[16] ^= 0x8000000000000000ULL;
-    keccak_f1600_host(st);
-    memcpy(out32, st, 32);
-    dh_wipe(&k, sizeof k); dh_wipe(m, sizeof m); dh_wipe(st, sizeof st);
+    h51::encode(S, dh_host_mul(k, h51::from_ge(P)));
+    dh_host_secret(out32, S, own, peer_pk32);
+    dh_wipe(&k, sizeof k); dh_wipe(S, sizeof S);
     return ROFL_OK;
 }
 // ---- secret sharing: Shamir shares of mask secrets over the scalar field (k_shamir_coeffs, k_shamir_eval, k_shamir_weights, k_shamir_combine) ----
@@ -3252,6 +3259,214 @@ int rofl_dbg_host_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_by
         memcpy(tag_out16 + 16 * j, tag, 16);
     }
     return ROFL_OK;
+}
+// ---- complaints: a DLEQ proof opens one pair's sealed channel to a judge (k_dh_public / k_dh_decode, k_dleq_prove / k_dleq_verify) ----
+}  // extern "C"
+namespace {
+// every check of rofl_dleq_prove / rofl_dleq_verify, shared with their host routes: those of rofl_dh_shared.  own32: secret keys (prove) or
+// public keys (verify); out: status or verdict bytes; *done: the call is empty and returns 0
+int dleq_check(bool prove, size_t n_own, const uint8_t *own32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
+               const uint8_t *reveal32, const uint8_t *proof64, const uint8_t *out, bool *done) {
+    *done = n_pairs == 0;
+    if (*done) return ROFL_OK;
+    if (!own32 || !peer_pk32 || !ctx32 || !reveal32 || !proof64 || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_own == 0 || n_peer == 0) return fail(ROFL_BAD_PARAM, "pairs without keys");
+    if (n_own > ((size_t)1 << 20) || n_peer > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
+    if (n_pairs > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 pairs in one call");
+    if (!pairs && n_pairs != n_own * n_peer) return fail(ROFL_BAD_PARAM, "without a pair list n_pairs is n_own x n_peer");
+    if (pairs) for (size_t i = 0; i < n_pairs; i++)
+        if (pairs[i].own >= n_own || pairs[i].peer >= n_peer) { char buf[96]; snprintf(buf, sizeof buf, "pair %zu names a key that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
+    return prove ? dh_check_keys(n_own, own32) : ROFL_OK;
+}
+// int_le(SHAKE256("rofl-zk/dleq/v1" || which || the parts, 32 bytes each)[0 .. 64)) mod l: which = 'k' takes three parts, 'c' six
+sc dleq_host_wide(char which, const uint8_t *const *parts, int n_parts) {
+    uint8_t m[208] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 'd', 'l', 'e', 'q', '/', 'v', '1', (uint8_t)which}, w[64];
+    for (int p = 0; p < n_parts; p++) memcpy(m + 16 + 32 * p, parts[p], 32);
+    Sponge sp(136, 0x1F); sp.absorb(m, 16 + 32 * (size_t)n_parts); sp.squeeze(w, 64);
+    sc r = sc_from_wide(sc_frombytes(w), sc_frombytes(w + 32));
+    dh_wipe(m, sizeof m); dh_wipe(w, sizeof w); dh_wipe(&sp, sizeof sp);
+    return r;
+}
+// the keys of a host route decoded once: refused[j] as k_dh_decode's status word (1 not canonical, 2 the identity)
+void dleq_host_decode(size_t n, const uint8_t *pk32, std::vector<uint8_t> &refused, std::vector<h51::ge5> &pts) {
+    refused.assign(n, 0); pts.resize(n);
+    for (size_t j = 0; j < n; j++) {
+        ge P;
+        refused[j] = !ristretto_decode(P, pk32 + 32 * j) ? 1 : ge_is_identity_ristretto(P) ? 2 : 0;
+        if (!refused[j]) pts[j] = h51::from_ge(P);
+    }
+}
+// the driver of the two debug hooks below: one upload, one launch, one download; *kernel_ms (may be NULL) is the launch between two events
+int dbg_var_mul_device(bool joint, size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms) {
+    if (n == 0) return ROFL_OK;
+    if (!k1_32 || !p1_32 || !k2_32 || !p2_32 || !out32) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 items in one call");
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        uint8_t *hu = C.h_misc.as<uint8_t>(n * 128), *du = C.tmp_in.as<uint8_t>(n * 128);      // [k1 | p1 | k2 | p2]
+        uint8_t *hd = C.h_misc2.as<uint8_t>(n * 32), *dd = C.tmp_out.as<uint8_t>(n * 32);
+        memcpy(hu, k1_32, n * 32); memcpy(hu + n * 32, p1_32, n * 32); memcpy(hu + n * 64, k2_32, n * 32); memcpy(hu + n * 96, p2_32, n * 32);
+        HIPCHK(hipMemcpyAsync(du, hu, n * 128, hipMemcpyHostToDevice, C.stream));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (kernel_ms) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, C.stream)); }
+        const dim3 grid((unsigned)((n + 63) / 64));
+        const sc *k1 = reinterpret_cast<const sc *>(du), *k2 = reinterpret_cast<const sc *>(du + n * 64);
+        if (joint) ROFL_LAUNCH(k_dbg_var_mul2, grid, dim3(64), 0, C.stream, (u32)n, k1, (const uint8_t *)(du + n * 32), k2, (const uint8_t *)(du + n * 96), dd);
+        else ROFL_LAUNCH(k_dbg_var_mul_sum, grid, dim3(64), 0, C.stream, (u32)n, k1, (const uint8_t *)(du + n * 32), k2, (const uint8_t *)(du + n * 96), dd);
+        if (kernel_ms) HIPCHK(hipEventRecord(e1, C.stream));
+        HIPCHK(hipMemcpyAsync(hd, dd, n * 32, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        if (kernel_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1)); *kernel_ms = ms; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+        memcpy(out32, hd, n * 32);
+        return ROFL_OK;
+    });
+}
+}  // namespace
+extern "C" {
+// The lane's copies of the secret keys -- pinned staging and device workspace -- are overwritten with zeros before the call returns or
+// unwinds; the nonces never leave their threads' registers; reveals and proofs are what the caller publishes.
+int rofl_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs,
+                    const uint8_t *ctx32, uint8_t *reveal_out32, uint8_t *proof_out64, uint8_t *status_out) {
+    bool done;
+    if (int rc = dleq_check(true, n_own, sk32, n_peer, peer_pk32, n_pairs, pairs, ctx32, reveal_out32, proof_out64, status_out, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: [secret keys | peer keys | contexts | pair list]; download: [reveals | proofs | own public keys | status bytes]
+        const size_t up_ctx = (n_own + n_peer) * 32, up_pairs = up_ctx + n_pairs * 32, up_bytes = up_pairs + (pairs ? n_pairs * sizeof(rofl_dh_pair_t) : 0);
+        const size_t dn_proof = n_pairs * 32, dn_pk = dn_proof + n_pairs * 64, dn_st = dn_pk + n_own * 32, dn_bytes = dn_st + n_pairs;
+        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        ge *pts = C.aux_pts.as<ge>(n_peer); u32 *pst = C.status.as<u32>(n_peer);
+        BlindWipe wipe_keys;
+        wipe_keys.h = hu; wipe_keys.dv = du; wipe_keys.n = n_own * 32; wipe_keys.s = C.stream;
+        memcpy(hu, sk32, n_own * 32); memcpy(hu + n_own * 32, peer_pk32, n_peer * 32); memcpy(hu + up_ctx, ctx32, n_pairs * 32);
+        if (pairs) memcpy(hu + up_pairs, pairs, n_pairs * sizeof(rofl_dh_pair_t));
+        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_dh_public, dim3((unsigned)((n_own + 63) / 64)), dim3(64), 0, C.stream, (u32)n_own, reinterpret_cast<const sc *>(du), C.d_tabB8, dd + dn_pk);
+        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_peer + 63) / 64)), dim3(64), 0, C.stream, (u32)n_peer, (const uint8_t *)(du + n_own * 32), pts, pst);
+        ROFL_LAUNCH(k_dleq_prove, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_pairs, (u32)n_peer,
+                    pairs ? reinterpret_cast<const uint2 *>(du + up_pairs) : (const uint2 *)nullptr, reinterpret_cast<const sc *>(du), (const uint8_t *)(dd + dn_pk),
+                    (const uint8_t *)(du + n_own * 32), (const ge *)pts, (const u32 *)pst, (const uint8_t *)(du + up_ctx), C.d_tabB8, dd, dd + dn_proof, dd + dn_st);
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        memcpy(reveal_out32, hd, n_pairs * 32); memcpy(proof_out64, hd + dn_proof, n_pairs * 64); memcpy(status_out, hd + dn_st, n_pairs);
+        if (own_pk_out32) memcpy(own_pk_out32, hd + dn_pk, n_own * 32);
+        return ROFL_OK;
+    });
+}
+// The inputs are public; the shared secrets that come back open the pair's channel, so the lane's copies of them are overwritten with zeros.
+int rofl_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
+                     const uint8_t *reveal32, const uint8_t *proof64, uint8_t *shared_out32, uint8_t *verdict_out) {
+    bool done;
+    if (int rc = dleq_check(false, n_own, own_pk32, n_peer, peer_pk32, n_pairs, pairs, ctx32, reveal32, proof64, verdict_out, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // upload: [prover keys | peer keys | contexts | reveals | proofs | pair list]; workspace: both key tables decoded by ONE k_dh_decode
+        // launch, with their status words; download: [shared secrets | verdict bytes]
+        const size_t n_keys = n_own + n_peer;
+        const size_t up_ctx = n_keys * 32, up_rev = up_ctx + n_pairs * 32, up_proof = up_rev + n_pairs * 32, up_pairs = up_proof + n_pairs * 64;
+        const size_t up_bytes = up_pairs + (pairs ? n_pairs * sizeof(rofl_dh_pair_t) : 0);
+        const size_t dn_v = shared_out32 ? n_pairs * 32 : 0, dn_bytes = dn_v + n_pairs;
+        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
+        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
+        ge *pts = C.aux_pts.as<ge>(n_keys); u32 *pst = C.status.as<u32>(n_keys);
+        BlindWipe wipe_out;
+        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = dn_v; wipe_out.s = C.stream;
+        memcpy(hu, own_pk32, n_own * 32); memcpy(hu + n_own * 32, peer_pk32, n_peer * 32); memcpy(hu + up_ctx, ctx32, n_pairs * 32);
+        memcpy(hu + up_rev, reveal32, n_pairs * 32); memcpy(hu + up_proof, proof64, n_pairs * 64);
+        if (pairs) memcpy(hu + up_pairs, pairs, n_pairs * sizeof(rofl_dh_pair_t));
+        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
+        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_keys + 63) / 64)), dim3(64), 0, C.stream, (u32)n_keys, (const uint8_t *)du, pts, pst);
+        ROFL_LAUNCH(k_dleq_verify, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_pairs, (u32)n_peer,
+                    pairs ? reinterpret_cast<const uint2 *>(du + up_pairs) : (const uint2 *)nullptr, (const uint8_t *)du, (const ge *)pts, (const u32 *)pst,
+                    (const uint8_t *)(du + n_own * 32), (const ge *)(pts + n_own), (const u32 *)(pst + n_own), (const uint8_t *)(du + up_ctx), (const uint8_t *)(du + up_rev),
+                    (const uint8_t *)(du + up_proof), C.d_tabB8, shared_out32 ? dd : (uint8_t *)nullptr, dd + dn_v);
+        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        if (shared_out32) memcpy(shared_out32, hd, n_pairs * 32);
+        memcpy(verdict_out, hd + dn_v, n_pairs);
+        return ROFL_OK;
+    });
+}
+// the two calls on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: same parameters, same checks, same bytes
+int rofl_dbg_host_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs,
+                             const uint8_t *ctx32, uint8_t *reveal_out32, uint8_t *proof_out64, uint8_t *status_out) {
+    bool done;
+    if (int rc = dleq_check(true, n_own, sk32, n_peer, peer_pk32, n_pairs, pairs, ctx32, reveal_out32, proof_out64, status_out, &done)) return rc;
+    if (done) return ROFL_OK;
+    ge Bg; ristretto_decode(Bg, kDhBase);
+    const h51::ge5 B = h51::from_ge(Bg);
+    std::vector<uint8_t> pk(n_own * 32), can(n_own * 32), refused;
+    std::vector<sc> keys(n_own);
+    std::vector<h51::ge5> pp;
+    for (size_t a = 0; a < n_own; a++) {
+        keys[a] = dh_key_scalar(sk32 + 32 * a);
+        sc_tobytes(can.data() + 32 * a, keys[a]);
+        h51::encode(pk.data() + 32 * a, dh_host_mul(keys[a], B));
+    }
+    dleq_host_decode(n_peer, peer_pk32, refused, pp);
+    for (size_t i = 0; i < n_pairs; i++) {
+        const size_t a = pairs ? pairs[i].own : i / n_peer, b = pairs ? pairs[i].peer : i % n_peer;
+        uint8_t *S = reveal_out32 + 32 * i, *pf = proof_out64 + 64 * i, T1[32], T2[32];
+        status_out[i] = refused[b];
+        if (refused[b]) { memset(S, 0, 32); memset(pf, 0, 64); continue; }
+        const uint8_t *P = peer_pk32 + 32 * b, *cx = ctx32 + 32 * i;
+        const uint8_t *kparts[3] = {can.data() + 32 * a, P, cx};
+        sc k = dleq_host_wide('k', kparts, 3);
+        h51::encode(S, dh_host_mul(keys[a], pp[b]));
+        h51::encode(T1, dh_host_mul(k, B));
+        h51::encode(T2, dh_host_mul(k, pp[b]));
+        const uint8_t *cparts[6] = {pk.data() + 32 * a, P, S, T1, T2, cx};
+        sc c = dleq_host_wide('c', cparts, 6);
+        sc s = sc_add(k, sc_montmul(sc_to_mont(c), keys[a]));
+        sc_tobytes(pf, c); sc_tobytes(pf + 32, s);
+        dh_wipe(&k, sizeof k); dh_wipe(&c, sizeof c); dh_wipe(&s, sizeof s);
+    }
+    if (own_pk_out32) memcpy(own_pk_out32, pk.data(), n_own * 32);
+    dh_wipe(keys.data(), keys.size() * sizeof(sc)); dh_wipe(can.data(), can.size());
+    return ROFL_OK;
+}
+int rofl_dbg_host_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
+                              const uint8_t *reveal32, const uint8_t *proof64, uint8_t *shared_out32, uint8_t *verdict_out) {
+    bool done;
+    if (int rc = dleq_check(false, n_own, own_pk32, n_peer, peer_pk32, n_pairs, pairs, ctx32, reveal32, proof64, verdict_out, &done)) return rc;
+    if (done) return ROFL_OK;
+    ge Bg; ristretto_decode(Bg, kDhBase);
+    const h51::ge5 B = h51::from_ge(Bg);
+    std::vector<uint8_t> own_refused, peer_refused;
+    std::vector<h51::ge5> op, pp;
+    dleq_host_decode(n_own, own_pk32, own_refused, op);
+    dleq_host_decode(n_peer, peer_pk32, peer_refused, pp);
+    for (size_t i = 0; i < n_pairs; i++) {
+        const size_t a = pairs ? pairs[i].own : i / n_peer, b = pairs ? pairs[i].peer : i % n_peer;
+        const uint8_t *S = reveal32 + 32 * i, *pf = proof64 + 64 * i, *A = own_pk32 + 32 * a, *P = peer_pk32 + 32 * b, *cx = ctx32 + 32 * i;
+        if (shared_out32) memset(shared_out32 + 32 * i, 0, 32);
+        const sc c = sc_frombytes(pf), s = sc_frombytes(pf + 32);
+        ge Sg;
+        if (own_refused[a] || peer_refused[b] || sc_geq_l(c.v) || sc_geq_l(s.v) || !ristretto_decode(Sg, S) || ge_is_identity_ristretto(Sg)) { verdict_out[i] = 2; continue; }
+        const sc nc = sc_neg(c);
+        uint8_t T1[32], T2[32], c2[32];
+        h51::encode(T1, h51::gadd(dh_host_mul(s, B), dh_host_mul(nc, op[a])));
+        h51::encode(T2, h51::gadd(dh_host_mul(s, pp[b]), dh_host_mul(nc, h51::from_ge(Sg))));
+        const uint8_t *cparts[6] = {A, P, S, T1, T2, cx};
+        sc_tobytes(c2, dleq_host_wide('c', cparts, 6));
+        verdict_out[i] = memcmp(c2, pf, 32) == 0 ? 0 : 1;
+        if (verdict_out[i] == 0 && shared_out32) dh_host_secret(shared_out32 + 32 * i, S, A, P);
+    }
+    return ROFL_OK;
+}
+// out32[i] = encode(k1[i] decode(p1[i]) + k2[i] decode(p2[i])) through the kernels' own device functions, one thread per item: on the joint
+// chain sg_var_mul2 (rofl_dbg_var_mul2) and as gd_add(sg_var_mul, sg_var_mul) (rofl_dbg_var_mul_sum)
+int rofl_dbg_var_mul2(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms) {
+    return dbg_var_mul_device(true, n, k1_32, p1_32, k2_32, p2_32, out32, kernel_ms);
+}
+int rofl_dbg_var_mul_sum(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms) {
+    return dbg_var_mul_device(false, n, k1_32, p1_32, k2_32, p2_32, out32, kernel_ms);
 }
 // conversion32::f32_to_fp_vec / uint_to_f32_vec (conversion32.rs:41-54): Fix is unsigned, negative inputs saturate to 0
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out) {

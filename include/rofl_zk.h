@@ -161,6 +161,32 @@ int rofl_verify_rangeproof_batch_strided(size_t n_clients, const uint8_t *const 
                                          const uint8_t verifier_seed[32], int *ok_out);
 /* clip_f32_to_range_vec :104-111 */
 int rofl_clip_f32(const float *in, size_t d, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *out);
+/* Probabilistic quantization (bindings32.rs quantize_probabilistic, whose body only clips; prob_quant.rs is a stub): seeded stochastic
+ * rounding of f32 values to f32 values that lie EXACTLY on the fixed-point grid, so that every deterministic float-to-fixed site converts
+ * them without rounding and proofs, commitments, wire bytes, verifiers and the server stay as they are.
+ *   stream of a 32-byte seed: block b = the first 128 bytes of SHAKE256("rofl-zk/quant/v1" || seed[32] || u64le(b)), read as 32
+ *   little-endian u32 words; element index e uses word e & 31 of block e >> 5 (the construction of nonce mode 1 and of the blinding
+ *   streams under a label of its own).
+ *   out[v][k], element index e = first + k, value x = values[v][k]:
+ *     1. c = what rofl_clip_f32 returns for x under (prove_range, fp_bits, fp_frac) -- NaN and +-inf included, there is no other rule for them;
+ *     2. X = |c| * 2^fp_frac, f = floor(X), r = X - f, t = floor(r * 2^32): all exact in double, r has at most 24 significant bits;
+ *     3. k' = f + (word(e) < t ? 1 : 0); the output is k' * 2^-fp_frac with the sign bit of c (a negative value that rounds to zero gives -0.0).
+ *   Consequences: r > 0 implies X < 2^23, so the output is always an exact f32; a value on the grid (t = 0) comes back unchanged for
+ *   every seed (so does +-0.0; a value below 2^-32 of a grid step, subnormals among them, goes to a zero of its sign); P(up) = t / 2^32,
+ *   within 2^-32 of r, so the expectation of the output is within 2^-32 grid steps of c; the clip bound is itself on the grid, so rounding
+ *   up never leaves [min, max]; the wrap of a value AT the closed bound is neither made worse nor fixed.
+ * n_vec vectors in ONE launch, each with its own seed (seeds32 + 32 v), input and output; values[v] and out[v] each hold d floats of host
+ * memory or of device memory of the library's device ("Memory spaces"), and out[v] may be the pointer values[v].  `first` lets ranks,
+ * devices or chunks take runs of one vector: the runs concatenate to the bytes of the unsplit call.  Returns 11 before the device is
+ * touched for: a null seeds32, values or out with n_vec > 0, a null values[v] or out[v] with d > 0, an invalid (fp_bits, fp_frac),
+ * prove_range = 0, n_vec > 65 535, d >= 2^28, first + d > 2^63; n_vec = 0 or d = 0 returns 0 and writes nothing.  When every pointer is
+ * host memory and n_vec * d is below a fixed, measured threshold the rule runs on the host, compiled from the kernel's
+ * source: same bytes, no device needed.  The seed is a per-round secret of the client (who knows it knows which way each coordinate was
+ * rounded): seeds never appear in rofl_last_error, and the library's own copies are overwritten with zeros before the call returns.
+ * The call runs on the calling thread's device and lane; the `devices` option does not apply (split a vector with `first` instead).
+ * Not constant time. */
+int rofl_quantize_prob(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, const float *const *values, size_t first, size_t d,
+                       size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
 
 /* ---- l2_range_proof_vec (l2_range_proof_vec/mod.rs) ---- */
 /* create_rangeproof_l2 :15-140.  The batch call below with one client, on the calling thread's device: values and blindings32 are host
@@ -737,7 +763,9 @@ int rofl_comm_destroy(void);
  * host memory, with one exception: the out32[v] of rofl_blinding_vecs / out32 of rofl_rnd_scalar_vec may be device memory of the
  * library's device (16-byte aligned), which the kernel then writes in place -- blindings generated there can be handed to the create
  * calls as device inputs without ever crossing PCIe.  A host output of those calls goes through the lane's workspace and the pinned
- * staging path like every other output. */
+ * staging path like every other output.  rofl_quantize_prob is the second exception: each values[v] and each out[v] is host memory or
+ * device memory of the library's device, in any combination (4-byte aligned, as a float array is); a device input is read and a device
+ * output written in place -- also the same array -- so an update quantized there goes to the create calls as a device input. */
 
 /* ---- behaviour options ----
  * Switches that change WHAT a call returns or how it waits are part of the ABI, not of the process environment.  `key` is one of the

@@ -130,6 +130,17 @@ int rofl_dbg_host_merlin(const uint8_t *label, size_t label_len, const uint8_t *
 int rofl_dbg_host_nonce(const uint8_t seed[32], uint64_t idx, uint8_t out[32]);
 /* scalar idx of the blinding stream of a seed (rofl_blinding_vecs), computed on the host from the source the kernel is compiled from */
 int rofl_dbg_host_blind(const uint8_t seed[32], uint64_t idx, uint8_t out[32]);
+/* word idx of the rounding stream of a seed (rofl_quantize_prob): word idx & 31 of block idx >> 5, on the host from the kernel's source */
+int rofl_dbg_host_quant(const uint8_t seed[32], uint64_t idx, uint32_t *word_out);
+/* The rounding rule of rofl_quantize_prob on caller-supplied words instead of a seed's stream: out[i] = the rule applied to values[i] with
+ * words[i], so that a test can sit exactly on word = t - 1, t, 0 and 2^32 - 1.  site 0: the host copy (no GPU); site 1: the device copy
+ * (k_dbg_quant_round, one thread per case).  11: site > 1, an invalid format, prove_range = 0, a null array with n > 0, n > 2^20. */
+int rofl_dbg_quant_round(unsigned site, size_t n, const float *values, const uint32_t *words, size_t prove_range, unsigned fp_bits,
+                         unsigned fp_frac, float *out);
+/* rofl_quantize_prob with the route chosen by the caller instead of by the pointers and the size: route 0 = the host copy of the rule (host
+ * pointers only, else 11), 1 = the kernel.  Same checks, same bytes; what scripts/gpu_prob_quant.py finds the crossover with. */
+int rofl_dbg_quantize_prob_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
+                                 size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
 /* one pair of rofl_dh_shared from the host arithmetic (no GPU): out32 and *status as that call gives them; own_pk32 == NULL: computed from sk32.
  * Returns 11 for a null pointer or a secret key that is 0 mod l. */
 int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status);

@@ -37,6 +37,18 @@ pub fn create_rangeproof(
     }
 }
 
+/// reference: bindings32.rs:661-672 `quantize_probabilistic(values, len, range)`, whose body only clips (prob_quant.rs is a stub).
+/// Here the clipped values are also rounded onto the grid of 2^-frac, up with the probability of the fractional part, by the rounding
+/// stream of `seed` -- a per-round secret of the client.  The result is exact in f32, so `create_rangeproof` and the Sigma-proof
+/// creators convert it without rounding.  Panics on a bad parameter, as the reference's binding does on a null pointer.
+pub fn quantize_probabilistic(value_vec: &Vec<f32>, prove_range: usize, seed: &[u8; 32]) -> Vec<f32> {
+    let mut out = vec![0f32; value_vec.len()];
+    let (vp, op) = (value_vec.as_ptr(), out.as_mut_ptr());
+    let rc = unsafe { rofl_quantize_prob(1, seed.as_ptr(), &vp, 0, value_vec.len(), prove_range, fp_bits(), fp_frac(), &op) };
+    if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+    out
+}
+
 /// reference: range_proof_vec/mod.rs:149-191.  `Ok(false)` for a proof that does not verify, `Err` for malformed input.
 pub fn verify_rangeproof(
     range_proof_vec: &Vec<RangeProof>,

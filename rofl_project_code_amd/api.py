@@ -326,6 +326,68 @@ class range_proof_vec:
         _check(lib().rofl_clip_f32(_ptr(v), _sz(v.size), _sz(prove_range), *_fp(fp), _ptr(out)))
         return out
 
+    # ---- probabilistic quantization (rofl_quantize_prob): seeded stochastic rounding onto the fixed-point grid, one launch per call ----
+    @staticmethod
+    def quantize_probabilistic_vecs(list_of_values, prove_range, seeds, first=0, fp=None, out=None):
+        """rofl_quantize_prob for several vectors of one length (the clients a process hosts) in ONE call: vector v is clipped like
+        clip_f32_to_range_vec and each element is rounded to one of its two neighbours on the grid of 2^-fp_frac, up with the probability of
+        its fractional part, by word `first + k` of the rounding stream of seeds[v] (include/rofl_zk.h has the definition).  The results are
+        f32 values ON the grid: the create calls convert them exactly, and a round aggregates to exactly their sum.
+        A vector is a float32 numpy array (anything np.asarray takes) or a contiguous float32 torch tensor on the library's GPU.  out=None
+        returns one float32 (n, d) numpy array; otherwise `out` lists one destination per vector -- a writable contiguous float32 numpy array
+        or a float32 tensor on the GPU of d elements, which may be the input itself -- and the list is returned.
+        A seed is a per-round SECRET of its client (pedersen_ops.quant_round_seed): whoever knows it knows which way every coordinate went."""
+        n, first = len(list_of_values), int(first)
+        seeds = [bytes(s) for s in seeds]
+        if len(seeds) != n:
+            raise ValueError("one seed per vector")
+        if any(len(s) != 32 for s in seeds):
+            raise ValueError("a seed is 32 bytes")
+        if first < 0 or int(prove_range) < 1:
+            raise ValueError("first is not negative and prove_range is at least 1")
+        keep, vp, d = [], (ctypes.c_void_p * max(n, 1))(), None
+        for v, x in enumerate(list_of_values):
+            if _is_dev(x):
+                p, dv = _dev_arg(x, 4)
+                p = p.value
+            else:
+                x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+                p, dv = x.ctypes.data, x.size
+            keep.append(x)
+            if d is not None and dv != d:
+                raise ValueError("the vectors of one call have one length")
+            d, vp[v] = dv, p
+        d = d or 0
+        if out is None:
+            res = np.empty((n, d), dtype=np.float32)
+            dst = [res[v] for v in range(n)]
+        else:
+            res = dst = list(out)
+            if len(dst) != n:
+                raise ValueError("one destination per vector")
+        op = (ctypes.c_void_p * max(n, 1))()
+        for v, o in enumerate(dst):
+            if _is_dev(o):
+                if not o.is_contiguous() or o.element_size() != 4 or o.numel() != d:
+                    raise ValueError("a device destination is a contiguous float32 tensor of d elements")
+                op[v] = o.data_ptr()
+            else:
+                if not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous and o.flags.writeable and o.size == d):
+                    raise ValueError("a host destination is a writable contiguous float32 array of d elements")
+                op[v] = o.ctypes.data
+        sb = ctypes.create_string_buffer(b"".join(seeds), max(32 * n, 1))
+        try:
+            _check(lib().rofl_quantize_prob(_sz(n), sb, vp, _sz(first), _sz(d), _sz(prove_range), *_fp(fp), op))
+        finally:
+            ctypes.memset(sb, 0, ctypes.sizeof(sb))
+        return res
+
+    @staticmethod
+    def quantize_probabilistic(values, prove_range, seed, first=0, fp=None):
+        """bindings32.rs quantize_probabilistic(values, len, range) with the rounding the reference's stub leaves out, the randomness an
+        explicit 32-byte seed: quantize_probabilistic_vecs for one vector.  -> float32[d] on the fixed-point grid, within the clip range."""
+        return range_proof_vec.quantize_probabilistic_vecs([values], prove_range, [seed], first, fp)[0]
+
     @staticmethod
     def create_rangeproof(values, blindings, prove_range, n_partition, nonce=None, fp=None):
         """-> (proofs uint8[n_proofs, proof_len], commitments uint8[d, 32]).  `values` (f32[d]) and `blindings` (u8[d,32]) may be
@@ -2120,6 +2182,14 @@ class pedersen_ops:
         """SHA3-256("rofl-zk/blind/v1/round" || shared_secret || u64le(round_no)): the seed two clients use in round `round_no`.  A seed
         serves ONE round: masks of two rounds under one seed are equal, and the difference of the two masked updates would be in the clear."""
         return hashlib.sha3_256(b"rofl-zk/blind/v1/round" + bytes(shared_secret) + struct.pack("<Q", int(round_no))).digest()
+
+    @staticmethod
+    def quant_round_seed(secret, round_no):
+        """SHA3-256("rofl-zk/quant/v1/round" || secret || u64le(round_no)): the seed a client rounds its update with in round `round_no`
+        (range_proof_vec.quantize_probabilistic, the quant_seed of the containers' encrypt), from a long-lived secret of ITS OWN.  The seed is
+        a per-round secret of the client: it decides which way every coordinate is rounded, so whoever learns it learns the update's
+        fractional parts from its rounded values, and a seed used in two rounds rounds equal fractions the same way in both."""
+        return hashlib.sha3_256(b"rofl-zk/quant/v1/round" + bytes(secret) + struct.pack("<Q", int(round_no))).digest()
 
     @staticmethod
     def compute_shifted_values_vec(values, offset):

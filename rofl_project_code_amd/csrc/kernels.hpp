@@ -404,6 +404,63 @@ __global__ void __launch_bounds__(TPB) k_quantize_shift(const float *vals, u32 d
 }
 #endif
 
+// ================================================================ probabilistic quantization
+// rofl_quantize_prob (the definition is in include/rofl_zk.h): seeded stochastic rounding of f32 values onto the fixed-point grid; the
+// outputs are f32 grid values, which every deterministic site above converts exactly.
+// The rounding rule, compiled for the host and the device from this one source.  clip_min / clip_max: the bounds rofl_clip_f32 uses; the
+// comparisons restate its fmaxf / fminf (NaN -> clip_min, the order of the two steps) without leaning on either library's treatment of +-0.
+HD float quant_prob_round(float v, u32 word, float clip_min, float clip_max, u32 fp_frac) {
+    float c = (clip_min >= v || v != v) ? clip_min : v;
+    c = (clip_max <= c) ? clip_max : c;
+    const double x = fabs((double)c) * (double)(1u << fp_frac), f = floor(x), r = x - f;      // exact: x has the 24 significant bits of c
+    if (r == 0.0) return c;                                                                   // on the grid (every |c| 2^frac >= 2^23 is)
+    const u32 t = (u32)(r * 4294967296.0);                                                    // floor(r 2^32), exact; 0 below 2^-32 (subnormals)
+    const double k = f + (word < t ? 1.0 : 0.0);                                              // <= 2^23: k 2^-frac is an exact f32
+    return copysignf((float)(k / (double)(1u << fp_frac)), c);
+}
+// word e & 31 of block e >> 5 of a seed's stream: the first 128 bytes of SHAKE256("rofl-zk/quant/v1" || seed || u64le(block)) as 32
+// little-endian u32 words
+HD u32 quant_block_word(const u64 st[25], u32 j) { return (u32)(st[j >> 1] >> (32 * (j & 1))); }
+// blockIdx.y = vector (its own seed, input and output: a descriptor read through the scalar data path, as BlindVec); thread = one XOF
+// block = elements 32 blk .. 32 blk + 31 of the index space, one Keccak-f for 32 elements.  A block is ONE wave: its 64 XOF blocks cover
+// 2048 consecutive elements, and the words go through LDS (row = XOF block, 33 words apart: the 32 lanes of a half write 32 banks, and
+// read one row) so that in each of the 32 passes the wave loads and stores 64 consecutive floats -- 256 contiguous bytes per instruction
+// -- instead of 64 separate 128-byte runs.  first and first + d need not be multiples of 32: the first and the last XOF block of a vector
+// own fewer elements, and a lane whose block lies outside [first, first + d) skips its permutation.  in == out is allowed (an element is
+// read and written by one lane).
+struct QuantVec { const float *in; float *out; u64 seed[4]; };
+#define QP_TPB 64
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(QP_TPB) k_quantize_prob(const QuantVec *__restrict__ vecs, u64 first, u32 d, float clip_min, float clip_max, u32 fp_frac) {
+    __shared__ u32 s_w[QP_TPB * 33];
+    const QuantVec *V = &vecs[blockIdx.y];
+    const u64 blk0 = (first >> 5) + (u64)blockIdx.x * QP_TPB, blk = blk0 + threadIdx.x, end = first + d;      // (end <= 2^63: 32 blk does not wrap)
+    if (32 * blk < end) {
+        const u64 dom[2] = ROFL_QUANT_DOM;
+        const u64 sw[4] = {V->seed[0], V->seed[1], V->seed[2], V->seed[3]};
+        u64 st[25];
+        shake256_seeded_block(st, dom, sw, blk);
+#pragma unroll
+        for (u32 j = 0; j < 32; j++) s_w[threadIdx.x * 33 + j] = quant_block_word(st, j);
+    }
+    __syncthreads();
+    const float *in = V->in; float *out = V->out;
+    for (u32 i = 0; i < 32; i++) {
+        const u32 q = i * QP_TPB + threadIdx.x;      // element q of the wave's 2048: XOF block q >> 5, word q & 31
+        const u64 e = 32 * blk0 + q;
+        if (e < first || e >= end) continue;
+        const u32 k = (u32)(e - first);
+        out[k] = quant_prob_round(in[k], s_w[(q >> 5) * 33 + (q & 31)], clip_min, clip_max, fp_frac);
+    }
+}
+// rofl_dbg_quant_round site 1: the rule as the device compiles it, on the caller's words, one thread per case
+__global__ void __launch_bounds__(TPB) k_dbg_quant_round(u32 n, const float *vals, const u32 *words, float clip_min, float clip_max, u32 fp_frac, float *out) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    out[t] = quant_prob_round(vals[t], words[t], clip_min, clip_max, fp_frac);
+}
+#endif
+
 // The sums of the L2 sum proof (l2_range_proof_vec/mod.rs:37-79) for the clients of a batch, one client per grid row, a fixed number of
 // blocks per client striding over its d values.  Per client: the status bits (1 = a value outside the clip range, 2 = NaN, as
 // k_quantize_shift has them); sum_i s_i^2 -- s_i is k_i or l - k_i with k_i < 2^64, so s_i^2 = k_i^2 mod l and the sum is the plain integer

@@ -2405,6 +2405,73 @@ int rofl_rnd_scalar_vec(const uint8_t seed[32], size_t first, size_t d, uint8_t 
     volatile uint8_t *p = term.seed; for (int i = 0; i < 32; i++) p[i] = 0;
     return rc;
 }
+// ---- probabilistic quantization (rofl_quantize_prob: the definition is in the header, the rule and the kernel in kernels.hpp) ----
+// Below this many elements in all, a call whose pointers are all host memory runs the rule on the host: one Keccak-f per 32 elements on one
+// core against the fixed cost of two staged copies, a launch and a synchronisation.  The measured crossover (profiles/prob_quant.json,
+// DESIGN section 7); a constant, not a knob: both routes give the same bytes.
+constexpr size_t kQuantProbHostBelow = 8192;
+static void quant_prob_host(const uint8_t *seed32, const float *in, u64 first, size_t d, float mn, float mx, unsigned fp_frac, float *out) {
+    const u64 dom[2] = ROFL_QUANT_DOM;
+    u64 sd[4], st[25], cur = ~0ULL; memcpy(sd, seed32, 32);
+    for (size_t k = 0; k < d; k++) {
+        const u64 e = first + k;
+        if ((e >> 5) != cur) { cur = e >> 5; shake256_seeded_block(st, dom, sd, cur); }
+        out[k] = quant_prob_round(in[k], quant_block_word(st, (u32)(e & 31)), mn, mx, fp_frac);
+    }
+    volatile u64 *p = sd; for (int i = 0; i < 4; i++) p[i] = 0;
+    p = st; for (int i = 0; i < 25; i++) p[i] = 0;
+}
+// route: -1 = by the pointers and the size, 0 = the host copy, 1 = the kernel (rofl_dbg_quantize_prob_route)
+static int quantize_prob_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
+                              size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec == 0) return ROFL_OK;
+    if (!seeds32 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
+    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
+    if (first > ((size_t)1 << 63) - d) return fail(ROFL_BAD_PARAM, "first + d exceeds 2^63");
+    if (d == 0) return ROFL_OK;
+    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
+    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+    return guarded([&]() -> int {
+        std::vector<char> dev_in(n_vec, 0), dev_out(n_vec, 0); bool all_host = true;
+        for (size_t v = 0; v < n_vec; v++) { dev_in[v] = is_device_ptr(values[v]); dev_out[v] = is_device_ptr(out[v]); all_host &= !dev_in[v] && !dev_out[v]; }
+        if (route == 0 && !all_host) return fail(ROFL_BAD_PARAM, "the host route takes host pointers only");
+        if (route == 0 || (route == -1 && all_host && n_vec * d < kQuantProbHostBelow)) {
+            for (size_t v = 0; v < n_vec; v++) quant_prob_host(seeds32 + 32 * v, values[v], first, d, mn, mx, fp_frac, out[v]);
+            return ROFL_OK;
+        }
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        // a device input is read and a device output written in place; a vector with a host pointer gets ONE slot of the lane's workspace:
+        // a host input is uploaded into it, the kernel writes a host output into it (in place when both are host memory)
+        size_t n_slot = 0;
+        for (size_t v = 0; v < n_vec; v++) if (!dev_in[v] || !dev_out[v]) n_slot++;
+        float *ws = n_slot ? C.vals.as<float>(n_slot * d) : nullptr;
+        const size_t bytes = n_vec * sizeof(QuantVec);
+        uint8_t *h = C.h_misc.as<uint8_t>(bytes), *dv = C.tmp_in.as<uint8_t>(bytes);
+        BlindWipe wipe; wipe.h = h; wipe.dv = dv; wipe.n = bytes; wipe.s = C.stream;      // (the seeds: zeroed when the call returns or unwinds)
+        QuantVec *hv = reinterpret_cast<QuantVec *>(h);
+        size_t slot = 0;
+        for (size_t v = 0; v < n_vec; v++) {
+            float *s = (!dev_in[v] || !dev_out[v]) ? ws + (slot++) * d : nullptr;
+            hv[v].in = dev_in[v] ? values[v] : s; hv[v].out = dev_out[v] ? out[v] : s;
+            memcpy(hv[v].seed, seeds32 + 32 * v, 32);
+            if (!dev_in[v]) C.up(s, values[v], 4 * d, C.stream);
+        }
+        HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, C.stream));
+        const size_t nblk = ((first + d + 31) >> 5) - (first >> 5);      // XOF blocks that hold an element of [first, first + d): <= 2^23 + 1
+        ROFL_LAUNCH(k_quantize_prob, dim3((unsigned)((nblk + QP_TPB - 1) / QP_TPB), (unsigned)n_vec), dim3(QP_TPB), 0, C.stream,
+                    reinterpret_cast<const QuantVec *>(dv), (u64)first, (u32)d, mn, mx, (u32)fp_frac);
+        for (size_t v = 0; v < n_vec; v++) if (!dev_out[v]) C.down(out[v], hv[v].out, 4 * d, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
+int rofl_quantize_prob(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, size_t prove_range,
+                       unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    return quantize_prob_impl(-1, n_vec, seeds32, values, first, d, prove_range, fp_bits, fp_frac, out);
+}
 // ---- key agreement: where the pairwise masks' shared secrets come from (k_dh_public, k_dh_decode, k_dh_shared) ----
 }  // extern "C"
 namespace {
@@ -4456,6 +4523,34 @@ int rofl_dbg_host_blind(const uint8_t seed[32], uint64_t idx, uint8_t out[32]) {
     const u64 dom[2] = ROFL_BLIND_DOM;
     u64 sd[4]; memcpy(sd, seed, 32); u64 st[25]; shake256_seeded_block(st, dom, sd, idx >> 1);
     sc_tobytes(out, xof_block_scalar(st, (int)(idx & 1))); return 0;
+}
+int rofl_dbg_host_quant(const uint8_t seed[32], uint64_t idx, uint32_t *word_out) {
+    if (!seed || !word_out) return ROFL_BAD_PARAM;
+    const u64 dom[2] = ROFL_QUANT_DOM;
+    u64 sd[4]; memcpy(sd, seed, 32); u64 st[25]; shake256_seeded_block(st, dom, sd, idx >> 5);
+    *word_out = quant_block_word(st, (u32)(idx & 31)); return 0;
+}
+int rofl_dbg_quant_round(unsigned site, size_t n, const float *values, const uint32_t *words, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *out) {
+    if (site > 1 || !valid_fp(fp_bits, fp_frac) || prove_range == 0 || n > (1u << 20) || (n && (!values || !words || !out))) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n == 0) return ROFL_OK;
+    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+    if (site == 0) { for (size_t i = 0; i < n; i++) out[i] = quant_prob_round(values[i], words[i], mn, mx, fp_frac); return ROFL_OK; }
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        float *dv = C.vals.as<float>(n), *dout = C.tmp_out.as<float>(n);
+        u32 *dw = C.tmp_in.as<u32>(n);
+        C.up(dv, values, 4 * n, C.stream); C.up(dw, words, 4 * n, C.stream);
+        ROFL_LAUNCH(k_dbg_quant_round, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (const float *)dv, (const u32 *)dw, mn, mx, (u32)fp_frac, dout);
+        C.down(out, dout, 4 * n, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
+int rofl_dbg_quantize_prob_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
+                                 size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return quantize_prob_impl((int)route, n_vec, seeds32, values, first, d, prove_range, fp_bits, fp_frac, out);
 }
 
 }  // extern "C"

@@ -196,6 +196,41 @@ def _num_checked(d, check_percentage):
     return min(int(d), int(np.floor(np.float64(x) + 0.5)))
 
 
+# The containers' quant_seed / quant_seeds (probabilistic quantization, range_proof_vec.quantize_probabilistic): with a seed the quantize
+# call stands where clip_f32_to_range_vec stands, and its output -- on the fixed-point grid, inside the clip range -- is the plaintext of
+# EVERY leg from there on, the witness digest included: the legs that take the un-clipped plaintext (params.rs:499) would otherwise round
+# the raw values deterministically and prove something else than the range proof commits to.  Without a seed nothing changes.
+# The seed is a per-round SECRET of the client (pedersen_ops.quant_round_seed).  For the L2 containers rounding up can push an update that
+# sat just under the norm bound over it; the sum proof then reports NormOutOfRangeError (7) as for any other update over the bound.
+def _clip_or_quantize(x, prove_range, quant_seed, fp):
+    """-> (plaintext, clipped) of one client"""
+    if quant_seed is None:
+        return x, range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
+    q = range_proof_vec.quantize_probabilistic(x, prove_range, quant_seed, fp=fp).reshape(x.shape)
+    return q, q
+
+
+def _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp):
+    """-> (plaintexts, clipped) of the clients of encrypt_batch: ONE quantize call for all clients that have a seed"""
+    if quant_seeds is None:
+        return xs, [range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp) for x in xs]
+    quant_seeds = list(quant_seeds)
+    if len(quant_seeds) != len(xs):
+        raise ValueError("one quant seed (or None) per client")
+    if any(x.size != xs[0].size for x in xs):
+        raise ValueError("the clients of a batch have one vector length")
+    xs, clipped = list(xs), [None] * len(xs)
+    with_seed = [i for i, s in enumerate(quant_seeds) if s is not None]
+    if with_seed:
+        q = range_proof_vec.quantize_probabilistic_vecs([xs[i] for i in with_seed], prove_range, [quant_seeds[i] for i in with_seed], fp=fp)
+        for row, i in enumerate(with_seed):
+            xs[i] = clipped[i] = q[row].reshape(xs[i].shape)
+    for i, s in enumerate(quant_seeds):
+        if s is None:
+            clipped[i] = range_proof_vec.clip_f32_to_range_vec(xs[i], prove_range, fp=fp)
+    return xs, clipped
+
+
 class _HostLegs:
     """Where verify_batch takes the batched legs of the majority-shape members from: caller memory, through the existing batch entry points.
     DeviceRound supplies the same three legs over the commitments it holds on the device (us = the members, idx = their positions in the
@@ -225,12 +260,12 @@ class EncParamsRange:
         self.prove_range, self.check_percentage = int(prove_range), float(check_percentage)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, check_percentage, nonce_seed=None, fp=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, check_percentage, nonce_seed=None, fp=None, quant_seed=None):
         fp = api._fp(fp)                       # resolved in the caller's thread; the proof calls below run on pool threads
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp)
         wd = witness_digest(x, bl) if nonce_seed is not None else b""
-        clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         if check_percentage >= 1.0:
             enc_com = _range_commitments(clipped, bl, prove_range, fp)      # == the range proof's commitments
             # NB the reference passes the un-clipped plaintext here (params.rs:499)
@@ -254,6 +289,18 @@ class EncParamsRange:
 
     @classmethod
     def encrypt_batch(cls, clients, prove_range, n_partition, check_percentage, nonce_seeds=None, fp=None):
+        """_encrypt_batch (below) without probabilistic quantization: the clients' values are clipped, as encrypt() without a quant_seed does."""
+        return cls._encrypt_batch(clients, prove_range, n_partition, check_percentage, nonce_seeds, fp, None)
+
+    @classmethod
+    def encrypt_batch_quantized(cls, clients, prove_range, n_partition, check_percentage, quant_seeds, nonce_seeds=None, fp=None):
+        """encrypt_batch with quant_seeds = one 32-byte seed (or None: clip only) per client: ONE rofl_quantize_prob call rounds the values of
+        all hosted clients, then the legs run as in encrypt_batch.  Byte-identical to encrypt(quant_seed=...) per client.  (A method of
+        its own: the parameter list of encrypt_batch is pinned.)"""
+        return cls._encrypt_batch(clients, prove_range, n_partition, check_percentage, nonce_seeds, fp, quant_seeds)
+
+    @classmethod
+    def _encrypt_batch(cls, clients, prove_range, n_partition, check_percentage, nonce_seeds, fp, quant_seeds):
         """encrypt() for several clients of one process (rofl_service's client binary hosts its clients as tasks of one process,
         client.rs:265-266): clients = [(plaintext_vec, blinding_vec), ...] of one length.  The L-inf legs of all of them are ONE
         rofl_create_rangeproof_batch call -- over the first k values of every client when check_percentage < 1 -- and the randomness leg
@@ -269,7 +316,7 @@ class EncParamsRange:
         for (x, bl) in clients:
             x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
             xs.append(x); bls.append(bl)
-            clipped.append(range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp))
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)      # (quant_seeds: ONE quantize call for all hosted clients)
         d = xs[0].size
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")
@@ -399,12 +446,12 @@ class EncParamsRangeCompressed(EncParamsRange):
         self.prove_range, self.check_percentage = int(prove_range), float(check_percentage)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, check_percentage, nonce_seed=None, fp=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, check_percentage, nonce_seed=None, fp=None, quant_seed=None):
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp)
         wd = witness_digest(x, bl) if nonce_seed is not None else b""
-        clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         if check_percentage >= 1.0:
             enc_com = _range_commitments(clipped, bl, prove_range, fp)
             (rp, rp_com), (proof, pairs) = _concurrently(
@@ -481,14 +528,14 @@ class EncParamsL2:
         self.prove_range, self.l2_prove_range = int(prove_range), int(l2_prove_range)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None):
         # r2: rand_scalars, or the blinding stream of rand_seed (pedersen_ops.rnd_scalar_vec_seeded, on the GPU), or fresh host randomness
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
         r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
-        clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         # the square proofs take the range proof's commitments (params.rs:623-637); committing first (same points) lets the
         # three proofs run side by side
         enc_com = _range_commitments(clipped, bl, prove_range, fp)
@@ -501,6 +548,18 @@ class EncParamsL2:
 
     @classmethod
     def encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None):
+        """_encrypt_batch (below) without probabilistic quantization: the clients' values are clipped, as encrypt() without a quant_seed does."""
+        return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, None)
+
+    @classmethod
+    def encrypt_batch_quantized(cls, clients, prove_range, n_partition, l2_range, quant_seeds, nonce_seeds=None, fp=None):
+        """encrypt_batch with quant_seeds = one 32-byte seed (or None: clip only) per client: ONE rofl_quantize_prob call rounds the values of
+        all hosted clients, then the legs run as in encrypt_batch.  Byte-identical to encrypt(quant_seed=...) per client.  (A method of
+        its own: the parameter list of encrypt_batch is pinned.)"""
+        return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds)
+
+    @classmethod
+    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds):
         """encrypt() for several clients of one process (rofl_service's client binary hosts its clients as tasks of one process,
         client.rs:265-266): clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one length.  The L-inf legs of all of
         them are ONE rofl_create_rangeproof_batch call (one launch sequence, one set of host hops), their sum proofs ONE
@@ -518,7 +577,7 @@ class EncParamsL2:
             x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
             r2 = pedersen_ops.rnd_scalar_vec(x.size) if r2 is None else api._u8(r2)
             xs.append(x); bls.append(bl); r2s.append(r2)
-            clipped.append(range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp))
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)      # (quant_seeds: ONE quantize call for all hosted clients)
         d = xs[0].size
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")
@@ -650,13 +709,13 @@ class EncParamsL2Compressed(EncParamsL2):
         self.prove_range, self.l2_prove_range = int(prove_range), int(l2_prove_range)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None):
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
         r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
-        clipped = range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
         enc_com = _range_commitments(clipped, bl, prove_range, fp)
         (rp, rp_com), (sum_proof, _), (rand_proof, pairs) = _concurrently(
             lambda: range_proof_vec.create_rangeproof(clipped, bl, prove_range, n_partition, nonce=_sub_nonce(nonce_seed, b"range", wd), fp=fp),
@@ -669,6 +728,18 @@ class EncParamsL2Compressed(EncParamsL2):
 
     @classmethod
     def encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None):
+        """_encrypt_batch (below) without probabilistic quantization: the clients' values are clipped, as encrypt() without a quant_seed does."""
+        return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, None)
+
+    @classmethod
+    def encrypt_batch_quantized(cls, clients, prove_range, n_partition, l2_range, quant_seeds, nonce_seeds=None, fp=None):
+        """encrypt_batch with quant_seeds = one 32-byte seed (or None: clip only) per client: ONE rofl_quantize_prob call rounds the values of
+        all hosted clients, then the legs run as in encrypt_batch.  Byte-identical to encrypt(quant_seed=...) per client.  (A method of
+        its own: the parameter list of encrypt_batch is pinned.)"""
+        return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds)
+
+    @classmethod
+    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds):
         """encrypt() for several clients of one process: clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one
         length.  The 8-bit legs of all of them are ONE rofl_create_rangeproof_batch call, their compressed randomness proofs ONE
         rofl_create_compressed_randproof_batch over the range proofs' commitments, their sum proofs ONE rofl_create_rangeproof_l2_batch and
@@ -684,7 +755,7 @@ class EncParamsL2Compressed(EncParamsL2):
             x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
             r2 = pedersen_ops.rnd_scalar_vec(x.size) if r2 is None else api._u8(r2)
             xs.append(x); bls.append(bl); r2s.append(r2)
-            clipped.append(range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp))
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)      # (quant_seeds: ONE quantize call for all hosted clients)
         d = xs[0].size
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")

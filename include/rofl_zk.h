@@ -187,6 +187,39 @@ int rofl_clip_f32(const float *in, size_t d, size_t prove_range, unsigned fp_bit
  * Not constant time. */
 int rofl_quantize_prob(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, const float *const *values, size_t first, size_t d,
                        size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
+/* Distributed noise: seeded centered-binomial noise (cpSGD, Agarwal et al. 2018) added to f32 values ON the fixed-point grid, the step a
+ * client takes after rounding and before it commits, so that the noise of n clients adds up to the noise a differentially private release
+ * of the sum needs.  Outputs are f32 grid values, as after rofl_quantize_prob: proofs, commitments, wire bytes, verifiers and the server
+ * stay as they are.
+ *   stream of a 32-byte seed: the construction of the rounding stream under a label of its own: block b = the first 128 bytes of
+ *   SHAKE256("rofl-zk/noise/v1" || seed[32] || u64le(b)), read as 32 little-endian u32 words; stream word w is word w & 31 of block w >> 5.
+ *   noise of element index e = first + i: k is a multiple of 16 with 16 <= k <= 2^20, W = k / 16, and
+ *     n_e = popcount(stream words e W .. e W + W - 1) - k,
+ *   2k fair bits minus k: n_e lies in [-k, k], its mean is 0 and its variance exactly k / 2 grid steps^2.  For a W that does not divide 32
+ *   an element's words straddle XOF blocks: the stream is one run of words.
+ *   out[v][i], value x = values[v][i] -- every step is one IEEE operation, so host and device agree:
+ *     1. c = what rofl_clip_f32 returns for x under (prove_range, fp_bits, fp_frac) -- NaN and +-inf included;
+ *     2. q = nearbyint((double)c * 2^fp_frac): the library's float-to-fixed rule, exact, and the identity for a c already on the grid;
+ *     3. y = q + (double)n_e, one double addition: exact whenever |q| < 2^52 (every value of the 8-, 16- and 32-bit formats, and every
+ *        value below 2^40 of the 64-bit formats; above, the sum is rounded to nearest even like any double addition);
+ *     4. out = rofl_clip_f32((float)(y * 2^-fp_frac)), the double -> float conversion rounding to nearest even.
+ *   Consequences: the output is always an integer multiple of the grid step -- exactly q + n_e steps below 2^24 steps, above that a float
+ *   has no finer values -- so every deterministic float-to-fixed site converts it without rounding; a zero result is +0.0.  Saturation
+ *   at the clip bound truncates the noise: a caller who needs the exact distribution clips the raw update to [min + k steps, max - k steps]
+ *   first.  The wrap of a value AT the closed bound is neither made worse nor fixed.  The sum of the noise of n vectors
+ *   under independent seeds is Binomial(2nk, 1/2) - nk.  The library gives the distribution; turning (n, k, sensitivity) into an
+ *   (epsilon, delta) is the deployment's job.
+ * Everything else is as rofl_quantize_prob: n_vec vectors in ONE launch, each with its own seed (seeds32 + 32 v), input and output;
+ * values[v] and out[v] each hold d floats of host memory or of device memory of the library's device, in any combination, and out[v] may
+ * be the pointer values[v]; the runs of a vector taken with `first` concatenate to the bytes of the unsplit call.  Returns 11 before the
+ * device is touched for the bad-parameter cases of that call, for a k that is not a multiple of 16 or lies outside [16, 2^20], and for
+ * (first + d) W > 2^63; n_vec = 0 or d = 0 returns 0 and writes nothing.  When every pointer is host memory and the call needs fewer
+ * Keccak permutations (n_vec d W / 32) than a fixed, measured threshold the rule runs on the host, compiled from the
+ * kernel's source: same bytes, no device needed.  The seed is a per-round secret of the client (who knows it removes the client's noise):
+ * seeds never appear in rofl_last_error, and the library's own copies are overwritten with zeros before the call returns.  The call runs
+ * on the calling thread's device and lane; the `devices` option does not apply.  Not constant time. */
+int rofl_noise_binomial(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, const float *const *values, size_t first, size_t d, uint32_t k,
+                        size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
 
 /* ---- l2_range_proof_vec (l2_range_proof_vec/mod.rs) ---- */
 /* create_rangeproof_l2 :15-140.  The batch call below with one client, on the calling thread's device: values and blindings32 are host
@@ -765,7 +798,8 @@ int rofl_comm_destroy(void);
  * calls as device inputs without ever crossing PCIe.  A host output of those calls goes through the lane's workspace and the pinned
  * staging path like every other output.  rofl_quantize_prob is the second exception: each values[v] and each out[v] is host memory or
  * device memory of the library's device, in any combination (4-byte aligned, as a float array is); a device input is read and a device
- * output written in place -- also the same array -- so an update quantized there goes to the create calls as a device input. */
+ * output written in place -- also the same array -- so an update quantized there goes to the create calls as a device input.
+ * rofl_noise_binomial takes its values[v] and out[v] in the same way. */
 
 /* ---- behaviour options ----
  * Switches that change WHAT a call returns or how it waits are part of the ABI, not of the process environment.  `key` is one of the

@@ -141,6 +141,18 @@ int rofl_dbg_quant_round(unsigned site, size_t n, const float *values, const uin
  * pointers only, else 11), 1 = the kernel.  Same checks, same bytes; what scripts/gpu_prob_quant.py finds the crossover with. */
 int rofl_dbg_quantize_prob_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
                                  size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
+/* noise integer n_e of element index e of a seed's noise stream (rofl_noise_binomial), on the host from the kernel's source.  11: a null
+ * pointer, a k the call rejects, (e + 1) k / 16 > 2^63. */
+int rofl_dbg_host_noise(const uint8_t seed[32], uint64_t e, uint32_t k, int32_t *n_out);
+/* The value rule of rofl_noise_binomial on caller-supplied noise instead of a seed's stream: out[i] = the rule applied to values[i] with
+ * noise_i32[i], so that a test can sit exactly on the clip bounds.  site 0: the host copy (no GPU); site 1: the device copy
+ * (k_dbg_noise_apply, one thread per case).  11: site > 1, an invalid format, prove_range = 0, a null array with n > 0, n > 2^20. */
+int rofl_dbg_noise_apply(unsigned site, size_t n, const float *values, const int32_t *noise_i32, size_t prove_range, unsigned fp_bits,
+                         unsigned fp_frac, float *out);
+/* rofl_noise_binomial with the route chosen by the caller instead of by the pointers and the size: route 0 = the host copy of the rule (host
+ * pointers only, else 11), 1 = the kernel.  Same checks, same bytes; what scripts/gpu_binomial_noise.py finds the crossover with. */
+int rofl_dbg_noise_binomial_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
+                                  uint32_t k, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
 /* one pair of rofl_dh_shared from the host arithmetic (no GPU): out32 and *status as that call gives them; own_pk32 == NULL: computed from sk32.
  * Returns 11 for a null pointer or a secret key that is 0 mod l. */
 int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status);

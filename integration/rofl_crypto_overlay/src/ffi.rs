@@ -118,6 +118,11 @@ extern "C" {
     /// memory or device memory of the library's device, and may be the same array
     pub fn rofl_quantize_prob(n_vec: usize, seeds32: *const u8, values: *const *const c_float, first: usize, d: usize, prove_range: usize,
         fp_bits: c_uint, fp_frac: c_uint, out: *const *mut c_float) -> c_int;
+    /// seeded centered-binomial noise on the fixed-point grid, n_vec vectors (own seed, input, output each) in one launch: out[v][i] = the
+    /// clipped, rounded values[v][i] plus popcount(2k bits of the noise stream of seeds32[32 v ..] for element first + i) - k grid steps,
+    /// clipped again; values[v] / out[v] are host memory or device memory of the library's device, and may be the same array
+    pub fn rofl_noise_binomial(n_vec: usize, seeds32: *const u8, values: *const *const c_float, first: usize, d: usize, k: u32,
+        prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *const *mut c_float) -> c_int;
     pub fn rofl_verify_rangeproof_l2_batch(n_clients: usize, proofs: *const *const u8, proof_len: usize, commits32: *const u8,
         prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, verifier_seed: *const u8, ok_out: *mut c_int) -> c_int;
     pub fn rofl_verify_randproof_vec_batch(n_clients: usize, proofs: *const *const u8, commits: *const *const u8, d: usize, ok_out: *mut c_int) -> c_int;

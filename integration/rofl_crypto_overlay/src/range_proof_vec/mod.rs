@@ -49,6 +49,18 @@ pub fn quantize_probabilistic(value_vec: &Vec<f32>, prove_range: usize, seed: &[
     out
 }
 
+/// No counterpart in the reference: distributed noise for a differentially private release of the round's sum.  Every value is clipped,
+/// rounded onto the grid of 2^-frac (the identity after `quantize_probabilistic`) and gets popcount(2k bits) - k grid steps of the noise
+/// stream of `seed` added -- a per-round secret of the client: who knows it removes the noise.  `k` is a multiple of 16 from 16 to 2^20;
+/// the variance is k / 2 steps^2 and the noise of n clients adds up to Binomial(2nk, 1/2) - nk.  Panics on a bad parameter.
+pub fn add_binomial_noise(value_vec: &Vec<f32>, prove_range: usize, seed: &[u8; 32], k: u32) -> Vec<f32> {
+    let mut out = vec![0f32; value_vec.len()];
+    let (vp, op) = (value_vec.as_ptr(), out.as_mut_ptr());
+    let rc = unsafe { rofl_noise_binomial(1, seed.as_ptr(), &vp, 0, value_vec.len(), k, prove_range, fp_bits(), fp_frac(), &op) };
+    if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+    out
+}
+
 /// reference: range_proof_vec/mod.rs:149-191.  `Ok(false)` for a proof that does not verify, `Err` for malformed input.
 pub fn verify_rangeproof(
     range_proof_vec: &Vec<RangeProof>,

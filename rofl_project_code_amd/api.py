@@ -10,9 +10,11 @@ Errors that the reference reports as Err(..) (or panics) raise RoflError(code).
 """
 import ctypes
 import hashlib
+import math
 import os
 import struct
 import threading
+from fractions import Fraction
 
 import numpy as np
 
@@ -337,6 +339,14 @@ class range_proof_vec:
         returns one float32 (n, d) numpy array; otherwise `out` lists one destination per vector -- a writable contiguous float32 numpy array
         or a float32 tensor on the GPU of d elements, which may be the input itself -- and the list is returned.
         A seed is a per-round SECRET of its client (pedersen_ops.quant_round_seed): whoever knows it knows which way every coordinate went."""
+        fp = _fp(fp)
+        return range_proof_vec._seeded_vecs(list_of_values, prove_range, seeds, first, out, lambda n, sb, vp, first, d, op:
+                                            lib().rofl_quantize_prob(n, sb, vp, first, d, _sz(prove_range), *fp, op))
+
+    @staticmethod
+    def _seeded_vecs(list_of_values, prove_range, seeds, first, out, call):
+        """the arguments of rofl_quantize_prob and rofl_noise_binomial -- one seed, one input and one destination per vector, host or device
+        memory -- checked and marshalled; call(n, seeds, values, first, d, out) -> return code"""
         n, first = len(list_of_values), int(first)
         seeds = [bytes(s) for s in seeds]
         if len(seeds) != n:
@@ -377,7 +387,7 @@ class range_proof_vec:
                 op[v] = o.ctypes.data
         sb = ctypes.create_string_buffer(b"".join(seeds), max(32 * n, 1))
         try:
-            _check(lib().rofl_quantize_prob(_sz(n), sb, vp, _sz(first), _sz(d), _sz(prove_range), *_fp(fp), op))
+            _check(call(_sz(n), sb, vp, _sz(first), _sz(d), op))
         finally:
             ctypes.memset(sb, 0, ctypes.sizeof(sb))
         return res
@@ -387,6 +397,56 @@ class range_proof_vec:
         """bindings32.rs quantize_probabilistic(values, len, range) with the rounding the reference's stub leaves out, the randomness an
         explicit 32-byte seed: quantize_probabilistic_vecs for one vector.  -> float32[d] on the fixed-point grid, within the clip range."""
         return range_proof_vec.quantize_probabilistic_vecs([values], prove_range, [seed], first, fp)[0]
+
+    # ---- distributed noise (rofl_noise_binomial): seeded centered-binomial noise on the fixed-point grid, one launch per call ----
+    @staticmethod
+    def add_binomial_noise_vecs(list_of_values, prove_range, seeds, k, first=0, fp=None, out=None):
+        """rofl_noise_binomial for several vectors of one length (the clients a process hosts) in ONE call: vector v is clipped like
+        clip_f32_to_range_vec, rounded onto the grid of 2^-fp_frac (the identity after quantize_probabilistic), and element `first + i` gets
+        popcount(2k bits of the noise stream of seeds[v]) - k grid steps added: mean 0, variance k / 2 steps^2, and the noise of n clients
+        adds up to Binomial(2nk, 1/2) - nk (include/rofl_zk.h has the definition).  k is a multiple of 16 from 16 to 2^20
+        (binomial_noise_k).  The results are f32 values ON the grid, inside the clip range: a value within k steps of a bound can saturate
+        there, which truncates its noise -- clip_f32_for_noise first where the exact distribution matters.
+        Vectors, `out` and the return value are as in quantize_probabilistic_vecs: numpy arrays or float32 tensors on the library's GPU.
+        A seed is a per-round SECRET of its client (pedersen_ops.noise_round_seed): whoever knows it removes the client's noise."""
+        k, fp = int(k), _fp(fp)
+        if k < 16 or k > 1 << 20 or k % 16:
+            raise ValueError("k is a multiple of 16 from 16 to 2^20")
+        return range_proof_vec._seeded_vecs(list_of_values, prove_range, seeds, first, out, lambda n, sb, vp, first, d, op:
+                                            lib().rofl_noise_binomial(n, sb, vp, first, d, ctypes.c_uint32(k), _sz(prove_range), *fp, op))
+
+    @staticmethod
+    def add_binomial_noise(values, prove_range, seed, k, first=0, fp=None):
+        """add_binomial_noise_vecs for one vector -> float32[d] on the fixed-point grid, within the clip range."""
+        return range_proof_vec.add_binomial_noise_vecs([values], prove_range, [seed], k, first, fp)[0]
+
+    @staticmethod
+    def binomial_noise_k(sigma_steps):
+        """the smallest k add_binomial_noise accepts whose noise has a standard deviation of at least `sigma_steps` grid steps
+        (variance k / 2 >= sigma^2).  What (n clients, k, sensitivity) mean as an (epsilon, delta) is the deployment's accounting."""
+        s = Fraction(sigma_steps)
+        if s < 0:
+            raise ValueError("sigma is not negative")
+        k = max(16, 16 * int(math.ceil(2 * s * s / 16)))
+        if k > 1 << 20:
+            raise ValueError("sigma^2 above 2^19 grid steps^2 needs a k above 2^20")
+        return k
+
+    @staticmethod
+    def clip_f32_for_noise(values, prove_range, k, fp=None):
+        """clip into [min + k steps, max - k steps] of the clip range of (prove_range, fp): after it, add_binomial_noise with this k never
+        saturates, so the added noise has exactly the binomial distribution.  NaN goes to the lower bound, as in clip_f32_to_range_vec.
+        Raises ValueError when that interval is empty (k steps reach past the middle of the range)."""
+        fp, k = _fp(fp), int(k)
+        mx = Fraction(conversion32.get_clip_bounds(prove_range, fp=fp)[1])      # (the lower bound is its negative)
+        top = mx - Fraction(k, 1 << fp[1])
+        if k < 0 or top < 0:
+            raise ValueError("no room for k steps of noise inside the clip range")
+        hi = np.float32(float(top))                                             # the largest f32 <= max - k steps: on the grid, as every
+        if Fraction(float(hi)) > top:                                           # f32 of 2^24 steps or more is
+            hi = np.nextafter(hi, np.float32(0))
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        return np.minimum(hi, np.maximum(-hi, np.where(np.isnan(v), -hi, v))).astype(np.float32)
 
     @staticmethod
     def create_rangeproof(values, blindings, prove_range, n_partition, nonce=None, fp=None):
@@ -2190,6 +2250,14 @@ class pedersen_ops:
         a per-round secret of the client: it decides which way every coordinate is rounded, so whoever learns it learns the update's
         fractional parts from its rounded values, and a seed used in two rounds rounds equal fractions the same way in both."""
         return hashlib.sha3_256(b"rofl-zk/quant/v1/round" + bytes(secret) + struct.pack("<Q", int(round_no))).digest()
+
+    @staticmethod
+    def noise_round_seed(secret, round_no):
+        """SHA3-256("rofl-zk/noise/v1/round" || secret || u64le(round_no)): the seed a client draws its distributed noise from in round
+        `round_no` (range_proof_vec.add_binomial_noise, the noise_seed of the containers' encrypt), from a long-lived secret of ITS OWN.
+        The seed is a per-round secret of the client: whoever learns it computes the client's noise and removes it from the client's share
+        of the released sum, and a seed used in two rounds adds the same noise in both, which their difference cancels."""
+        return hashlib.sha3_256(b"rofl-zk/noise/v1/round" + bytes(secret) + struct.pack("<Q", int(round_no))).digest()
 
     @staticmethod
     def compute_shifted_values_vec(values, offset):

@@ -461,6 +461,84 @@ __global__ void __launch_bounds__(TPB) k_dbg_quant_round(u32 n, const float *val
 }
 #endif
 
+// ================================================================ distributed noise
+// rofl_noise_binomial (the definition is in include/rofl_zk.h): seeded centered-binomial noise added ON the fixed-point grid; like the
+// rounding above, the outputs are f32 grid values.
+// The value rule, compiled for the host and the device from this one source: clip as rofl_clip_f32, the library's float-to-fixed rounding
+// (the identity for a value already on the grid), ONE double addition of the noise, back to f32 (round to nearest even), clip again.
+// A zero result is +0.0: (double)n is +0.0 for n = 0, and x + (-x) is +0.0.
+HD float noise_apply(float x, int n, float clip_min, float clip_max, u32 fp_frac) {
+    float c = (clip_min >= x || x != x) ? clip_min : x;
+    c = (clip_max <= c) ? clip_max : c;
+    const double s = (double)(1u << fp_frac);
+    const double y = rint((double)c * s) + (double)n;      // exact for |c| 2^frac < 2^52
+    const float o = (float)(y / s);
+    const float p = (clip_min >= o) ? clip_min : o;
+    return (clip_max <= p) ? clip_max : p;
+}
+// The popcounts of words [jlo, jhi) of one squeezed block, summed into the counters of the elements they belong to: word jlo is word
+// `rem0` from the end of element el0 (W words per element).  `add(el, count)` is called once per element that ends inside the block and
+// once for the part of the element the block ends in -- between 1 and 33 calls.
+template <typename Add>
+HD void noise_block_counts(const u64 st[25], u32 jlo, u32 jhi, u32 el0, u32 rem0, u32 W, Add add) {
+    u32 el = el0, rem = rem0, acc = 0;
+#pragma unroll
+    for (u32 j = 0; j < 32; j++) {
+        if (j < jlo || j >= jhi) continue;
+        acc += (u32)__builtin_popcount(quant_block_word(st, j));
+        if (--rem == 0) { add(el, acc); acc = 0; el++; rem = W; }
+    }
+    if (acc) add(el, acc);
+}
+// blockIdx.y = vector (QuantVec: its seed, input and output); a workgroup is ONE wave and takes groups of `epw` consecutive elements,
+// group g = elements g epw .. of the call (a grid-stride loop: gridDim.x is capped, the number of groups is not).  The words of a group
+// are one run of the stream, [lo, lo + n_el W) with lo = (first + g epw) W, which lies in the XOF blocks lo >> 5 .. : lane t permutes
+// block (lo >> 5) + t, + 64 per pass, so inside a group no block is permuted twice and none lies outside the run; the block a run starts
+// or ends in the middle of is permuted by both neighbours -- one permutation in `passes x 64`, the price of groups that own whole
+// elements and need no sum across workgroups.  The host picks epw so that a group fills whole passes (noise_epw in rofl_zk.hip): 2048
+// words (one pass) for W <= 32, up to 32 passes for wide elements, a single element of any width above that.
+// Each lane adds the popcounts of its block to LDS counters, one per element of the group (integers: the order does not matter); counter
+// i lies at i + (i >> 5), so that at W = 1 the 32 lanes of a half, whose elements are 32 apart, hit 32 banks.  Then the wave reads the
+// counters in order: loads and stores of the floats are contiguous, up to 64 per instruction.  in == out is allowed (an element is read
+// and written by one lane).  All indices inside a group are 32-bit: n_el W <= max(65 536, W).
+#define NB_TPB 64
+#define NB_EPW_MAX 2048
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(NB_TPB) k_noise_binomial(const QuantVec *__restrict__ vecs, u64 first, u32 d, u32 W, u32 epw, u32 n_grp,
+                                                           float clip_min, float clip_max, u32 fp_frac) {
+    __shared__ u32 s_cnt[NB_EPW_MAX + NB_EPW_MAX / 32 + 1];
+    const QuantVec *V = &vecs[blockIdx.y];
+    const u64 dom[2] = ROFL_NOISE_DOM;
+    const u64 sw[4] = {V->seed[0], V->seed[1], V->seed[2], V->seed[3]};
+    const float *in = V->in; float *out = V->out;
+    const int k = (int)(16 * W);
+    for (u32 g = blockIdx.x; g < n_grp; g += gridDim.x) {
+        const u32 k0 = g * epw, n_el = min(epw, d - k0);                 // (k0 < d < 2^28)
+        const u64 lo = (first + k0) * (u64)W;                            // (<= 2^63: checked by the host)
+        const u32 off = (u32)lo & 31, total = n_el * W, nblk = (off + total + 31) >> 5;
+        for (u32 i = threadIdx.x; i < n_el + (n_el >> 5) + 1; i += NB_TPB) s_cnt[i] = 0;
+        __syncthreads();
+        for (u32 t = threadIdx.x; t < nblk; t += NB_TPB) {
+            u64 st[25];
+            shake256_seeded_block(st, dom, sw, (lo >> 5) + t);
+            const u32 jlo = t ? 0 : off, jhi = min(32u, off + total - 32 * t);
+            const u32 s = 32 * t + jlo - off, el = s / W;                // word s of the run is the block's first owned word
+            noise_block_counts(st, jlo, jhi, el, W - (s - el * W), W, [&](u32 e, u32 c) { atomicAdd(&s_cnt[e + (e >> 5)], c); });
+        }
+        __syncthreads();
+        for (u32 i = threadIdx.x; i < n_el; i += NB_TPB)
+            out[k0 + i] = noise_apply(in[k0 + i], (int)s_cnt[i + (i >> 5)] - k, clip_min, clip_max, fp_frac);
+        __syncthreads();      // (the next group zeroes the counters)
+    }
+}
+// rofl_dbg_noise_apply site 1: the value rule as the device compiles it, on the caller's noise, one thread per case
+__global__ void __launch_bounds__(TPB) k_dbg_noise_apply(u32 n, const float *vals, const int *noise, float clip_min, float clip_max, u32 fp_frac, float *out) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    out[t] = noise_apply(vals[t], noise[t], clip_min, clip_max, fp_frac);
+}
+#endif
+
 // The sums of the L2 sum proof (l2_range_proof_vec/mod.rs:37-79) for the clients of a batch, one client per grid row, a fixed number of
 // blocks per client striding over its d values.  Per client: the status bits (1 = a value outside the clip range, 2 = NaN, as
 // k_quantize_shift has them); sum_i s_i^2 -- s_i is k_i or l - k_i with k_i < 2^64, so s_i^2 = k_i^2 mod l and the sum is the plain integer

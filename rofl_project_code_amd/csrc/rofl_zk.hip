@@ -2421,24 +2421,17 @@ static void quant_prob_host(const uint8_t *seed32, const float *in, u64 first, s
     volatile u64 *p = sd; for (int i = 0; i < 4; i++) p[i] = 0;
     p = st; for (int i = 0; i < 25; i++) p[i] = 0;
 }
-// route: -1 = by the pointers and the size, 0 = the host copy, 1 = the kernel (rofl_dbg_quantize_prob_route)
-static int quantize_prob_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
-                              size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
-    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec == 0) return ROFL_OK;
-    if (!seeds32 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
-    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
-    if (first > ((size_t)1 << 63) - d) return fail(ROFL_BAD_PARAM, "first + d exceeds 2^63");
-    if (d == 0) return ROFL_OK;
-    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
-    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+// What rofl_quantize_prob and rofl_noise_binomial share once their parameters are checked.  route: -1 = by the pointers and the size
+// (`small`: an all-host call runs on the host), 0 = the host copy, 1 = the kernel.  host(v) runs the rule of vector v on the host;
+// launch(C, vecs) enqueues the kernel over the device copy of the descriptors on C.stream.
+static int seeded_vecs_run(int route, bool small, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, float *const *out,
+                           const std::function<void(size_t)> &host, const std::function<void(Ctx &, const QuantVec *)> &launch) {
     return guarded([&]() -> int {
         std::vector<char> dev_in(n_vec, 0), dev_out(n_vec, 0); bool all_host = true;
         for (size_t v = 0; v < n_vec; v++) { dev_in[v] = is_device_ptr(values[v]); dev_out[v] = is_device_ptr(out[v]); all_host &= !dev_in[v] && !dev_out[v]; }
         if (route == 0 && !all_host) return fail(ROFL_BAD_PARAM, "the host route takes host pointers only");
-        if (route == 0 || (route == -1 && all_host && n_vec * d < kQuantProbHostBelow)) {
-            for (size_t v = 0; v < n_vec; v++) quant_prob_host(seeds32 + 32 * v, values[v], first, d, mn, mx, fp_frac, out[v]);
+        if (route == 0 || (route == -1 && all_host && small)) {
+            for (size_t v = 0; v < n_vec; v++) host(v);
             return ROFL_OK;
         }
         LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
@@ -2460,17 +2453,90 @@ static int quantize_prob_impl(int route, size_t n_vec, const uint8_t *seeds32, c
             if (!dev_in[v]) C.up(s, values[v], 4 * d, C.stream);
         }
         HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, C.stream));
-        const size_t nblk = ((first + d + 31) >> 5) - (first >> 5);      // XOF blocks that hold an element of [first, first + d): <= 2^23 + 1
-        ROFL_LAUNCH(k_quantize_prob, dim3((unsigned)((nblk + QP_TPB - 1) / QP_TPB), (unsigned)n_vec), dim3(QP_TPB), 0, C.stream,
-                    reinterpret_cast<const QuantVec *>(dv), (u64)first, (u32)d, mn, mx, (u32)fp_frac);
+        launch(C, reinterpret_cast<const QuantVec *>(dv));
         for (size_t v = 0; v < n_vec; v++) if (!dev_out[v]) C.down(out[v], hv[v].out, 4 * d, C.stream);
         C.sync();
         return ROFL_OK;
     });
 }
+// route: as seeded_vecs_run (rofl_dbg_quantize_prob_route)
+static int quantize_prob_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
+                              size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec == 0) return ROFL_OK;
+    if (!seeds32 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
+    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
+    if (first > ((size_t)1 << 63) - d) return fail(ROFL_BAD_PARAM, "first + d exceeds 2^63");
+    if (d == 0) return ROFL_OK;
+    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
+    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+    return seeded_vecs_run(route, n_vec * d < kQuantProbHostBelow, n_vec, seeds32, values, d, out,
+        [&](size_t v) { quant_prob_host(seeds32 + 32 * v, values[v], first, d, mn, mx, fp_frac, out[v]); },
+        [&](Ctx &C, const QuantVec *vecs) {
+            const size_t nblk = ((first + d + 31) >> 5) - (first >> 5);      // XOF blocks that hold an element of [first, first + d): <= 2^23 + 1
+            ROFL_LAUNCH(k_quantize_prob, dim3((unsigned)((nblk + QP_TPB - 1) / QP_TPB), (unsigned)n_vec), dim3(QP_TPB), 0, C.stream,
+                        vecs, (u64)first, (u32)d, mn, mx, (u32)fp_frac);
+        });
+}
 int rofl_quantize_prob(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, size_t prove_range,
                        unsigned fp_bits, unsigned fp_frac, float *const *out) {
     return quantize_prob_impl(-1, n_vec, seeds32, values, first, d, prove_range, fp_bits, fp_frac, out);
+}
+// ---- distributed noise (rofl_noise_binomial: the definition is in the header, the value rule and the kernel in kernels.hpp) ----
+// Below this many Keccak permutations in all (n_vec d W / 32), a call whose pointers are all host memory runs on the host: one core's
+// permutations against the fixed cost of two staged copies, a launch and a synchronisation.  The measured crossover
+// (profiles/binomial_noise.json); a constant, not a knob: both routes give the same bytes.
+constexpr u64 kNoiseHostBelowPerms = 256;
+// elements of a workgroup's group in k_noise_binomial: the words of a group, plus the 31 its first block can hold of a neighbour, fill
+// `passes` x 64 blocks -- one pass for W <= 32, W / 32 passes up to 32 (a wide element then wastes at most a few per cent of the lanes of
+// its group's last pass), and a single element whatever its width beyond that
+static u32 noise_epw(u32 W) {
+    const u32 passes = std::min(std::max(W / 32, 1u), 32u);
+    return std::min(std::max((2048 * passes - 31) / W, 1u), (u32)NB_EPW_MAX);
+}
+// noise integer of element index e: popcount of stream words e W .. e W + W - 1, minus k.  *cur / st: the block the caller holds squeezed.
+static int noise_host_element(const u64 sd[4], u64 e, u32 W, u64 *cur, u64 st[25]) {
+    const u64 dom[2] = ROFL_NOISE_DOM;
+    u32 cnt = 0;
+    for (u64 w = e * W; w < e * W + W; w++) {
+        if ((w >> 5) != *cur) { *cur = w >> 5; shake256_seeded_block(st, dom, sd, *cur); }
+        cnt += (u32)__builtin_popcount(quant_block_word(st, (u32)(w & 31)));
+    }
+    return (int)cnt - (int)(16 * W);
+}
+static void noise_host(const uint8_t *seed32, const float *in, u64 first, size_t d, u32 W, float mn, float mx, unsigned fp_frac, float *out) {
+    u64 sd[4], st[25], cur = ~0ULL; memcpy(sd, seed32, 32);
+    for (size_t i = 0; i < d; i++) out[i] = noise_apply(in[i], noise_host_element(sd, first + i, W, &cur, st), mn, mx, fp_frac);
+    volatile u64 *p = sd; for (int i = 0; i < 4; i++) p[i] = 0;
+    p = st; for (int i = 0; i < 25; i++) p[i] = 0;
+}
+static bool noise_k_ok(uint32_t k) { return k >= 16 && k <= (1u << 20) && k % 16 == 0; }
+// route: as seeded_vecs_run (rofl_dbg_noise_binomial_route)
+static int noise_binomial_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, uint32_t k,
+                               size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (!noise_k_ok(k)) return fail(ROFL_BAD_PARAM, "k is a multiple of 16 from 16 to 2^20");
+    if (n_vec == 0) return ROFL_OK;
+    if (!seeds32 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
+    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
+    const u32 W = k / 16;
+    if (first > ((size_t)1 << 63) - d || first + d > ((u64)1 << 63) / W) return fail(ROFL_BAD_PARAM, "(first + d) k / 16 exceeds 2^63");
+    if (d == 0) return ROFL_OK;
+    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
+    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+    return seeded_vecs_run(route, (u64)n_vec * d * W < 32 * kNoiseHostBelowPerms, n_vec, seeds32, values, d, out,
+        [&](size_t v) { noise_host(seeds32 + 32 * v, values[v], first, d, W, mn, mx, fp_frac, out[v]); },
+        [&](Ctx &C, const QuantVec *vecs) {
+            const u32 epw = noise_epw(W), n_grp = (u32)((d + epw - 1) / epw);
+            ROFL_LAUNCH(k_noise_binomial, dim3(std::min(n_grp, 1u << 22), (unsigned)n_vec), dim3(NB_TPB), 0, C.stream,
+                        vecs, (u64)first, (u32)d, W, epw, n_grp, mn, mx, (u32)fp_frac);
+        });
+}
+int rofl_noise_binomial(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, uint32_t k, size_t prove_range,
+                        unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    return noise_binomial_impl(-1, n_vec, seeds32, values, first, d, k, prove_range, fp_bits, fp_frac, out);
 }
 // ---- key agreement: where the pairwise masks' shared secrets come from (k_dh_public, k_dh_decode, k_dh_shared) ----
 }  // extern "C"
@@ -4551,6 +4617,33 @@ int rofl_dbg_quantize_prob_route(unsigned route, size_t n_vec, const uint8_t *se
                                  size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
     if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
     return quantize_prob_impl((int)route, n_vec, seeds32, values, first, d, prove_range, fp_bits, fp_frac, out);
+}
+int rofl_dbg_host_noise(const uint8_t seed[32], uint64_t e, uint32_t k, int32_t *n_out) {
+    if (!seed || !n_out || !noise_k_ok(k) || e >= ((u64)1 << 63) / (k / 16)) return ROFL_BAD_PARAM;
+    u64 sd[4], st[25], cur = ~0ULL; memcpy(sd, seed, 32);
+    *n_out = noise_host_element(sd, e, k / 16, &cur, st); return 0;
+}
+int rofl_dbg_noise_apply(unsigned site, size_t n, const float *values, const int32_t *noise_i32, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *out) {
+    if (site > 1 || !valid_fp(fp_bits, fp_frac) || prove_range == 0 || n > (1u << 20) || (n && (!values || !noise_i32 || !out))) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n == 0) return ROFL_OK;
+    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+    if (site == 0) { for (size_t i = 0; i < n; i++) out[i] = noise_apply(values[i], noise_i32[i], mn, mx, fp_frac); return ROFL_OK; }
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        float *dv = C.vals.as<float>(n), *dout = C.tmp_out.as<float>(n);
+        int *dn = C.tmp_in.as<int>(n);
+        C.up(dv, values, 4 * n, C.stream); C.up(dn, noise_i32, 4 * n, C.stream);
+        ROFL_LAUNCH(k_dbg_noise_apply, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (const float *)dv, (const int *)dn, mn, mx, (u32)fp_frac, dout);
+        C.down(out, dout, 4 * n, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
+int rofl_dbg_noise_binomial_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
+                                  uint32_t k, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return noise_binomial_impl((int)route, n_vec, seeds32, values, first, d, k, prove_range, fp_bits, fp_frac, out);
 }
 
 }  // extern "C"

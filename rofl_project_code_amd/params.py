@@ -202,16 +202,48 @@ def _num_checked(d, check_percentage):
 # the raw values deterministically and prove something else than the range proof commits to.  Without a seed nothing changes.
 # The seed is a per-round SECRET of the client (pedersen_ops.quant_round_seed).  For the L2 containers rounding up can push an update that
 # sat just under the norm bound over it; the sum proof then reports NormOutOfRangeError (7) as for any other update over the bound.
-def _clip_or_quantize(x, prove_range, quant_seed, fp):
+#
+# The containers' noise_seed + noise_k / noise_seeds + noise_k (distributed noise, range_proof_vec.add_binomial_noise): both or neither.
+# The noise is added after the rounding of a quant_seed, where one is given (without one the noise call rounds to nearest itself), and
+# before everything else; its output -- again on the grid and inside the clip range -- is the plaintext of every leg and of the witness
+# digest in the same way.  The seed is a per-round SECRET of the client (pedersen_ops.noise_round_seed).  A value within noise_k steps of
+# a clip bound can saturate there (range_proof_vec.clip_f32_for_noise avoids it), and for the L2 containers the noise raises the norm --
+# by about sqrt(d noise_k / 2) steps: an update that then exceeds the bound fails with NormOutOfRangeError (7) like any other.
+def _noise_args(noise_seed, noise_k):
+    if (noise_seed is None) != (noise_k is None):
+        raise ValueError("noise_seed(s) and noise_k are given together or not at all")
+    return noise_seed is not None
+
+
+def _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed=None, noise_k=None):
     """-> (plaintext, clipped) of one client"""
-    if quant_seed is None:
+    noisy = _noise_args(noise_seed, noise_k)
+    if quant_seed is None and not noisy:
         return x, range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
-    q = range_proof_vec.quantize_probabilistic(x, prove_range, quant_seed, fp=fp).reshape(x.shape)
+    q = x if quant_seed is None else range_proof_vec.quantize_probabilistic(x, prove_range, quant_seed, fp=fp).reshape(x.shape)
+    if noisy:
+        q = range_proof_vec.add_binomial_noise(q, prove_range, noise_seed, noise_k, fp=fp).reshape(x.shape)
     return q, q
 
 
-def _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp):
-    """-> (plaintexts, clipped) of the clients of encrypt_batch: ONE quantize call for all clients that have a seed"""
+def _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds=None, noise_k=None):
+    """-> (plaintexts, clipped) of the clients of encrypt_batch: ONE quantize call for all clients that have a quant seed, then ONE noise
+    call for all clients that have a noise seed"""
+    if _noise_args(noise_seeds, noise_k):
+        noise_seeds = list(noise_seeds)
+        if len(noise_seeds) != len(xs):
+            raise ValueError("one noise seed (or None) per client")
+        if any(x.size != xs[0].size for x in xs):
+            raise ValueError("the clients of a batch have one vector length")
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)
+        xs, clipped = list(xs), list(clipped)
+        with_seed = [i for i, s in enumerate(noise_seeds) if s is not None]
+        if with_seed:
+            # (the input is the rounded vector where there is one, else the raw one: the noise call clips and rounds to nearest itself)
+            q = range_proof_vec.add_binomial_noise_vecs([xs[i] for i in with_seed], prove_range, [noise_seeds[i] for i in with_seed], noise_k, fp=fp)
+            for row, i in enumerate(with_seed):
+                xs[i] = clipped[i] = q[row].reshape(xs[i].shape)
+        return xs, clipped
     if quant_seeds is None:
         return xs, [range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp) for x in xs]
     quant_seeds = list(quant_seeds)
@@ -260,11 +292,11 @@ class EncParamsRange:
         self.prove_range, self.check_percentage = int(prove_range), float(check_percentage)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, check_percentage, nonce_seed=None, fp=None, quant_seed=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, check_percentage, nonce_seed=None, fp=None, quant_seed=None, noise_seed=None, noise_k=None):
         fp = api._fp(fp)                       # resolved in the caller's thread; the proof calls below run on pool threads
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
-        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed, noise_k)
         wd = witness_digest(x, bl) if nonce_seed is not None else b""
         if check_percentage >= 1.0:
             enc_com = _range_commitments(clipped, bl, prove_range, fp)      # == the range proof's commitments
@@ -300,7 +332,17 @@ class EncParamsRange:
         return cls._encrypt_batch(clients, prove_range, n_partition, check_percentage, nonce_seeds, fp, quant_seeds)
 
     @classmethod
-    def _encrypt_batch(cls, clients, prove_range, n_partition, check_percentage, nonce_seeds, fp, quant_seeds):
+    def encrypt_batch_private(cls, clients, prove_range, n_partition, check_percentage, nonce_seeds=None, fp=None, quant_seeds=None, noise_seeds=None, noise_k=None):
+        """encrypt_batch_quantized with distributed noise: noise_seeds = one 32-byte seed (or None: no noise) per client and noise_k, both or
+        neither.  After the ONE rofl_quantize_prob call of the quant_seeds, ONE rofl_noise_binomial call adds the noise of all hosted clients,
+        then the legs run as in encrypt_batch.  Byte-identical to encrypt(quant_seed=..., noise_seed=..., noise_k=...) per client, and
+        without noise seeds to encrypt_batch_quantized.  (A method of its own: the parameter lists of encrypt_batch and
+        encrypt_batch_quantized are pinned.)"""
+        _noise_args(noise_seeds, noise_k)
+        return cls._encrypt_batch(clients, prove_range, n_partition, check_percentage, nonce_seeds, fp, quant_seeds, noise_seeds, noise_k)
+
+    @classmethod
+    def _encrypt_batch(cls, clients, prove_range, n_partition, check_percentage, nonce_seeds, fp, quant_seeds, noise_seeds=None, noise_k=None):
         """encrypt() for several clients of one process (rofl_service's client binary hosts its clients as tasks of one process,
         client.rs:265-266): clients = [(plaintext_vec, blinding_vec), ...] of one length.  The L-inf legs of all of them are ONE
         rofl_create_rangeproof_batch call -- over the first k values of every client when check_percentage < 1 -- and the randomness leg
@@ -316,7 +358,7 @@ class EncParamsRange:
         for (x, bl) in clients:
             x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
             xs.append(x); bls.append(bl)
-        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)      # (quant_seeds: ONE quantize call for all hosted clients)
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds, noise_k)      # (ONE quantize and ONE noise call for all hosted clients)
         d = xs[0].size
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")
@@ -446,11 +488,11 @@ class EncParamsRangeCompressed(EncParamsRange):
         self.prove_range, self.check_percentage = int(prove_range), float(check_percentage)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, check_percentage, nonce_seed=None, fp=None, quant_seed=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, check_percentage, nonce_seed=None, fp=None, quant_seed=None, noise_seed=None, noise_k=None):
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
-        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed, noise_k)
         wd = witness_digest(x, bl) if nonce_seed is not None else b""
         if check_percentage >= 1.0:
             enc_com = _range_commitments(clipped, bl, prove_range, fp)
@@ -528,13 +570,13 @@ class EncParamsL2:
         self.prove_range, self.l2_prove_range = int(prove_range), int(l2_prove_range)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None, noise_seed=None, noise_k=None):
         # r2: rand_scalars, or the blinding stream of rand_seed (pedersen_ops.rnd_scalar_vec_seeded, on the GPU), or fresh host randomness
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
         r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
-        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed, noise_k)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
         # the square proofs take the range proof's commitments (params.rs:623-637); committing first (same points) lets the
         # three proofs run side by side
@@ -559,7 +601,17 @@ class EncParamsL2:
         return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds)
 
     @classmethod
-    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds):
+    def encrypt_batch_private(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None, quant_seeds=None, noise_seeds=None, noise_k=None):
+        """encrypt_batch_quantized with distributed noise: noise_seeds = one 32-byte seed (or None: no noise) per client and noise_k, both or
+        neither.  After the ONE rofl_quantize_prob call of the quant_seeds, ONE rofl_noise_binomial call adds the noise of all hosted clients,
+        then the legs run as in encrypt_batch.  Byte-identical to encrypt(quant_seed=..., noise_seed=..., noise_k=...) per client, and
+        without noise seeds to encrypt_batch_quantized.  The noise raises the norm: an update it pushes over the L2 bound fails with
+        NormOutOfRangeError (7).  (A method of its own: the parameter lists of encrypt_batch and encrypt_batch_quantized are pinned.)"""
+        _noise_args(noise_seeds, noise_k)
+        return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds, noise_k)
+
+    @classmethod
+    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds=None, noise_k=None):
         """encrypt() for several clients of one process (rofl_service's client binary hosts its clients as tasks of one process,
         client.rs:265-266): clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one length.  The L-inf legs of all of
         them are ONE rofl_create_rangeproof_batch call (one launch sequence, one set of host hops), their sum proofs ONE
@@ -577,7 +629,7 @@ class EncParamsL2:
             x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
             r2 = pedersen_ops.rnd_scalar_vec(x.size) if r2 is None else api._u8(r2)
             xs.append(x); bls.append(bl); r2s.append(r2)
-        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)      # (quant_seeds: ONE quantize call for all hosted clients)
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds, noise_k)      # (ONE quantize and ONE noise call for all hosted clients)
         d = xs[0].size
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")
@@ -709,12 +761,12 @@ class EncParamsL2Compressed(EncParamsL2):
         self.prove_range, self.l2_prove_range = int(prove_range), int(l2_prove_range)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None, noise_seed=None, noise_k=None):
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
         r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
-        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed, noise_k)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
         enc_com = _range_commitments(clipped, bl, prove_range, fp)
         (rp, rp_com), (sum_proof, _), (rand_proof, pairs) = _concurrently(
@@ -739,7 +791,17 @@ class EncParamsL2Compressed(EncParamsL2):
         return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds)
 
     @classmethod
-    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds):
+    def encrypt_batch_private(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None, quant_seeds=None, noise_seeds=None, noise_k=None):
+        """encrypt_batch_quantized with distributed noise: noise_seeds = one 32-byte seed (or None: no noise) per client and noise_k, both or
+        neither.  After the ONE rofl_quantize_prob call of the quant_seeds, ONE rofl_noise_binomial call adds the noise of all hosted clients,
+        then the legs run as in encrypt_batch.  Byte-identical to encrypt(quant_seed=..., noise_seed=..., noise_k=...) per client, and
+        without noise seeds to encrypt_batch_quantized.  The noise raises the norm: an update it pushes over the L2 bound fails with
+        NormOutOfRangeError (7).  (A method of its own: the parameter lists of encrypt_batch and encrypt_batch_quantized are pinned.)"""
+        _noise_args(noise_seeds, noise_k)
+        return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds, noise_k)
+
+    @classmethod
+    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds=None, noise_k=None):
         """encrypt() for several clients of one process: clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one
         length.  The 8-bit legs of all of them are ONE rofl_create_rangeproof_batch call, their compressed randomness proofs ONE
         rofl_create_compressed_randproof_batch over the range proofs' commitments, their sum proofs ONE rofl_create_rangeproof_l2_batch and
@@ -755,7 +817,7 @@ class EncParamsL2Compressed(EncParamsL2):
             x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
             r2 = pedersen_ops.rnd_scalar_vec(x.size) if r2 is None else api._u8(r2)
             xs.append(x); bls.append(bl); r2s.append(r2)
-        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)      # (quant_seeds: ONE quantize call for all hosted clients)
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds, noise_k)      # (ONE quantize and ONE noise call for all hosted clients)
         d = xs[0].size
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")

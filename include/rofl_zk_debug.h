@@ -48,6 +48,33 @@ int rofl_dbg_bind_device(int device);
 /* GPU multi-scalar multiplication sum_i k_i * P_i through the production Pippenger pipeline (dalek
  * vartime_multiscalar_mul as used by upstream verify_multiple); test hook for skewed / extreme scalars. */
 int rofl_dbg_msm(const uint8_t *scalars32, const uint8_t *points32, size_t n, uint8_t out32[32]);
+/* The same driver with the shape and the scalars chosen by the caller, for the tests that push its fixed-size structures (bucket lists,
+ * slots, the overflow list, coarse bins) to their capacity and over it.  Both run ONE msm_run; scalars are reduced mod l as rofl_dbg_msm
+ * does.  The L/R-merged mode of the inner-product rounds (MsmOpt::lr_nh != 0) needs scalar arrays in which every term belongs to one side
+ * by construction (k_lr_first, k_ipp_round) and is NOT reachable through these entries.
+ *   rofl_dbg_msm_many:  out32[p] = sum_i scalars32[p][i] * points32[i]: np generic problems of n terms over one shared point array
+ *                       (decoded as rofl_dbg_msm decodes it; 5 = a point that is no Ristretto encoding).
+ *   rofl_dbg_msm_fixed: out32[p] = sum_k s[p][k] G_k + sum_k s[p][N + k] H_k over the generators of BulletproofGens::new(n_bits, m), N = n_bits m,
+ *                       in the order [G | H], party-major; scalars32 is [np][2N].  The MsmOpt carries the shape's window table the way the
+ *                       verifier sets it (the table chosen for np problems, slice stride 2N).  11 when the shape has no window table
+ *                       (2N < ROFL_MSM_FB_MIN), np == 0 or a null pointer. */
+int rofl_dbg_msm_many(size_t np, size_t n, const uint8_t *scalars32, const uint8_t *points32, uint8_t *out32);
+int rofl_dbg_msm_fixed(size_t n_bits, size_t m, size_t np, const uint8_t *scalars32, uint8_t *out32);
+/* The attempts of the calling thread's last msm_run, first to last: an MSM whose attempt overflowed one of its fixed-size structures is
+ * repeated on the next variant (csrc/host_msm.hpp).  At most `max` records are written, *count_out is the number of attempts made.
+ *   kind         the variant that ran (ROFL_MSM_*); two = 1: fixed-base through the two-level sort, 0: through the slot sort
+ *   c, W         window width and window count of the attempt's layout
+ *   cap          slots per bucket of the slot sort, as the plan sized them (the other variants do not use it)
+ *   cap_bin      entries of a coarse bin (two-level sort), else 0;  sets: bucket sets per problem (fixed-base), else 0
+ *   small_group  windows per block of the fused small launch, else 0
+ *   finisher     who combines the windows (ROFL_MSM_FIN_*): host chains, k_msm_horner, or k_msm_wsum + the host's eight-lane chains
+ *   overflow     the overflow word the host read back: small launch / two-level sort: non-zero = a list / a bin overflowed; slot sort: the
+ *                number of entries that found their bucket's slots full (up to 4096 of them are added from the overflow list)
+ *   repeated     1: the MSM was run again on the next variant */
+enum { ROFL_MSM_FIXED_BASE = 0, ROFL_MSM_SMALL = 1, ROFL_MSM_SLOTS = 2, ROFL_MSM_COUNT_SORT = 3 };
+enum { ROFL_MSM_FIN_HOST = 0, ROFL_MSM_FIN_DEVICE = 1, ROFL_MSM_FIN_HOST8 = 2 };
+typedef struct { uint32_t kind, two, c, W, cap, cap_bin, sets, small_group, finisher, overflow, repeated; } rofl_msm_attempt_t;
+int rofl_dbg_msm_trace(rofl_msm_attempt_t *attempts_out, size_t max, size_t *count_out);
 /* RangeProof::verify_multiple(&BulletproofGens::new(gens_capacity, m), &PedersenGens::default(), &mut Transcript::new(label), commits, n_bits)
  * on one aggregated proof, called the way upstream's own tests call it: any transcript label, the m (a power of two) commitments as they
  * are -- no shift by 2^(n-1) B, no padding.  The operator API fixes the labels ("RangeProof", "L2RangeProof") and the shift as the reference

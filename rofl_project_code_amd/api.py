@@ -257,6 +257,50 @@ def msm_retries():
     return dict(zip(("done", "small_overflow", "bin_overflow_to_slots", "slot_overflow"), (int(x) for x in out)))
 
 
+class _MsmAttempt(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("kind", "two", "c", "W", "cap", "cap_bin", "sets", "small_group", "finisher", "overflow", "repeated")]
+
+
+MSM_KINDS = ("fixed_base", "small", "slots", "count_sort")
+MSM_FINISHERS = ("host", "device", "host8")
+
+
+def msm_trace():
+    """test hook (include/rofl_zk_debug.h): the attempts of the calling thread's last MSM, first to last, one dict per attempt --
+    kind (MSM_KINDS), two, c, W, cap, cap_bin, sets, small_group, finisher (MSM_FINISHERS), overflow (the raw word), repeated"""
+    buf = (_MsmAttempt * 8)()
+    cnt = ctypes.c_size_t()
+    _check(lib().rofl_dbg_msm_trace(buf, _sz(8), ctypes.byref(cnt)))
+    out = []
+    for a in buf[:min(cnt.value, 8)]:
+        d = {f[0]: int(getattr(a, f[0])) for f in _MsmAttempt._fields_}
+        d["kind"], d["finisher"], d["two"], d["repeated"] = MSM_KINDS[d["kind"]], MSM_FINISHERS[d["finisher"]], bool(d["two"]), bool(d["repeated"])
+        out.append(d)
+    return out
+
+
+def dbg_msm_many(scalars32, points32):
+    """test hook: out[p] = sum_i scalars32[p][i] * points32[i] for the np problems of scalars32 [np][n][32], in ONE launch chain"""
+    k = np.ascontiguousarray(scalars32, dtype=np.uint8)
+    p = np.ascontiguousarray(points32, dtype=np.uint8).reshape(-1, 32)
+    if k.ndim != 3 or k.shape[2] != 32 or k.shape[1] != p.shape[0]:
+        raise ValueError("scalars32 must be [np][n][32] over n points")
+    out = np.zeros((k.shape[0], 32), dtype=np.uint8)
+    _check(lib().rofl_dbg_msm_many(_sz(k.shape[0]), _sz(k.shape[1]), _ptr(k), _ptr(p), _ptr(out)))
+    return out
+
+
+def dbg_msm_fixed(n_bits, m, scalars32):
+    """test hook: out[p] = sum_k s[p][k] G_k + sum_k s[p][N + k] H_k over the Bulletproofs generators of (n_bits, m), scalars32 [np][2 N][32],
+    through the fixed-base variants of the MSM driver (the shape's window table)"""
+    k = np.ascontiguousarray(scalars32, dtype=np.uint8)
+    if k.ndim != 3 or k.shape[2] != 32 or k.shape[1] != 2 * n_bits * m:
+        raise ValueError("scalars32 must be [np][2 n_bits m][32]")
+    out = np.zeros((k.shape[0], 32), dtype=np.uint8)
+    _check(lib().rofl_dbg_msm_fixed(_sz(n_bits), _sz(m), _sz(k.shape[0]), _ptr(k), _ptr(out)))
+    return out
+
+
 def set_timing(on):
     """0 / False = off, 1 / True = every instrumented launch, 2 = only the fixed-base accumulation (cheap enough for timed steps)"""
     _check(lib().rofl_set_timing(int(on)))

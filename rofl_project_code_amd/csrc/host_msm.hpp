@@ -358,11 +358,22 @@ MsmJob msm_enqueue(Ctx &C, MsmWs &W, const std::vector<MsmProb> &probs, size_t n
 // sort (-> slot path) / after an overflow of the slot path's overflow list (-> the next slower variant).  Process-wide; the tests of the server
 // path use them to show that a scenario really took the path it was built for.
 std::atomic<uint64_t> g_msm_stat[4];
+// rofl_dbg_msm_trace: the attempts of the calling thread's last msm_run, in order (the fields of the ROFL_TRACE line below).  msm_run empties
+// the list, msm_retry appends to it: a few stores per attempt on the host, nothing that a launch depends on.  The chain of variants is at most
+// five attempts long; a longer list (msm_run2's two interleaved MSMs are not reset) keeps its first kMsmTraceMax.
+constexpr u32 kMsmTraceMax = 8;
+thread_local rofl_msm_attempt_t t_msm_trace[kMsmTraceMax];
+thread_local u32 t_msm_trace_n = 0;
 bool msm_retry_inner(const MsmJob &J, MsmAllow &al);
 bool msm_retry(const MsmJob &J, MsmAllow &al) {
     const bool small = J.kind == MsmKind::Small, two = J.two;
     const bool again = msm_retry_inner(J, al);
     g_msm_stat[again ? (small ? 1 : two ? 2 : 3) : 0].fetch_add(1, std::memory_order_relaxed);
+    if (t_msm_trace_n < kMsmTraceMax)
+        t_msm_trace[t_msm_trace_n++] = rofl_msm_attempt_t{
+            J.fb() ? (uint32_t)ROFL_MSM_FIXED_BASE : small ? (uint32_t)ROFL_MSM_SMALL : J.kind == MsmKind::Slots ? (uint32_t)ROFL_MSM_SLOTS : (uint32_t)ROFL_MSM_COUNT_SORT,
+            two ? 1u : 0u, J.P.c, J.P.W, J.cap, J.cap_bin, J.fb() ? J.sets : 0u, small ? J.small_group : 0u,
+            J.host8 ? (uint32_t)ROFL_MSM_FIN_HOST8 : J.dev_horner ? (uint32_t)ROFL_MSM_FIN_DEVICE : (uint32_t)ROFL_MSM_FIN_HOST, *J.ws->h_ovf.as<u32>(4), again ? 1u : 0u};
     return again;
 }
 bool msm_retry_inner(const MsmJob &J, MsmAllow &al) {
@@ -500,6 +511,7 @@ void msm_finish(Ctx &C, const MsmJob &J, std::vector<ge5> &results, const MsmOpt
 // one MSM, start to finish: enqueue, wait, repeat through the next variant if a fixed-size structure overflowed, combine.
 void msm_run(Ctx &C, const std::vector<MsmProb> &probs, size_t n, std::vector<ge5> &results, const MsmOpt &opt = MsmOpt()) {
     MsmAllow al; bool overlap_done = false;
+    t_msm_trace_n = 0;
     for (;;) {
         double t_enter = now_ms();
         MsmJob J = msm_enqueue(C, C.mws[0], probs, n, opt, al);

@@ -3650,6 +3650,61 @@ int rofl_dbg_msm(const uint8_t *scalars32, const uint8_t *points32, size_t n, ui
         return ROFL_OK;
     });
 }
+// np generic problems over one shared point array in one msm_run (test hook: the many-problem finishers under chosen scalars)
+int rofl_dbg_msm_many(size_t np, size_t n, const uint8_t *scalars32, const uint8_t *points32, uint8_t *out32) {
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        if (np == 0 || n == 0 || !scalars32 || !points32 || !out32 || np * n > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "bad parameter");
+        C.init();
+        std::vector<sc> hs(np * n);
+        for (size_t i = 0; i < np * n; i++) { hs[i] = sc_frombytes(scalars32 + 32 * i); if (sc_geq_l(hs[i].v)) hs[i] = sc_from_mont(sc_to_mont(hs[i])); }
+        uint8_t *dp = C.tmp_in.as<uint8_t>(n * 32); niels *dn = C.aux_pts.as<niels>(n); sc *ds = C.aux_scal.as<sc>(np * n);
+        u32 *status = C.status.as<u32>(4);
+        HIPCHK(hipMemsetAsync(status, 0, 16, C.stream));
+        C.up(dp, points32, n * 32, C.stream);
+        C.up(ds, hs.data(), np * n * 32, C.stream);
+        count_decodes(n);
+        ROFL_LAUNCH(k_decode, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (u32)n, dp, (const niels *)nullptr, dn, (uint8_t *)nullptr, status);
+        u32 st = 0;
+        HIPCHK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, C.stream));
+        C.sync();
+        if (st & 4u) return fail(ROFL_FORMAT_ERROR, "invalid Ristretto encoding");
+        std::vector<MsmProb> pr(np); std::vector<ge5> res;
+        for (size_t p = 0; p < np; p++) pr[p] = MsmProb{dn, ds + p * n};
+        msm_run(C, pr, n, res);
+        for (size_t p = 0; p < np; p++) h51::encode(out32 + 32 * p, res[p]);
+        return ROFL_OK;
+    });
+}
+// np problems over the generators of (n_bits, m) in one msm_run, with the shape's window table in the MsmOpt as verify_chunks sets it
+// (test hook: the fixed-base variants under chosen scalars)
+int rofl_dbg_msm_fixed(size_t n_bits, size_t m, size_t np, const uint8_t *scalars32, uint8_t *out32) {
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        if (n_bits == 0 || m == 0 || np == 0 || !scalars32 || !out32 || n_bits * m > ((size_t)1 << 22) || np * 2 * n_bits * m > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "bad parameter");
+        C.init();
+        const size_t N = n_bits * m;
+        GensPin gens = get_gens(C, n_bits, m, GENS_VERIFY);
+        if (!gens.wtab()) return fail(ROFL_BAD_PARAM, "the shape has no window table");
+        std::vector<sc> hs(np * 2 * N);
+        for (size_t i = 0; i < hs.size(); i++) { hs[i] = sc_frombytes(scalars32 + 32 * i); if (sc_geq_l(hs[i].v)) hs[i] = sc_from_mont(sc_to_mont(hs[i])); }
+        sc *ds = C.SL.as<sc>(np * 2 * N);
+        C.up(ds, hs.data(), hs.size() * 32, C.stream);
+        C.sync();
+        std::vector<MsmProb> pr(np); std::vector<ge5> res;
+        for (size_t p = 0; p < np; p++) pr[p] = MsmProb{gens.tbl(), ds + p * 2 * N};
+        MsmOpt mo; gens.fb_for(np, &mo.fb_wtab, &mo.fb_c); mo.fb_stride = 2 * N;
+        msm_run(C, pr, 2 * N, res, mo);
+        for (size_t p = 0; p < np; p++) h51::encode(out32 + 32 * p, res[p]);
+        return ROFL_OK;
+    });
+}
+int rofl_dbg_msm_trace(rofl_msm_attempt_t *attempts_out, size_t max, size_t *count_out) {
+    if (!count_out || (max && !attempts_out)) return ROFL_BAD_PARAM;
+    *count_out = t_msm_trace_n;
+    for (size_t i = 0; i < max && i < t_msm_trace_n; i++) attempts_out[i] = t_msm_trace[i];
+    return ROFL_OK;
+}
 // bulletproofs' RangeProof::verify_multiple(&bp_gens, &pc_gens, &mut Transcript::new(label), &value_commitments, n) on ONE aggregated proof
 // exactly as upstream's own tests call it: any transcript label (upstream's serialized-proof vectors use b"Deserialize-And-Verify Test"),
 // the commitments as they are (no shift, no padding: m must be a power of two), generators of capacity >= n.  If byte vectors of

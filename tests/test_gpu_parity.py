@@ -336,14 +336,22 @@ def _gpu_msm(R, k, p):
 
 @pytest.mark.parametrize("n", [1, 5, 63, 64, 300, 513, 2000, 6000, 8192, 9000])
 def test_msm_extreme_scalars(R, n):
-    """The Pippenger pipeline on inputs the proof path never produces: heavy bucket skew (slot overflow list /
-    two-pass fallback), scalars in [2^252, l) (split top-window digit), zeros, small and all-ones scalars."""
+    """The Pippenger pipeline on inputs the proof path never produces: heavy bucket skew, scalars in [2^252, l) (top-window digit exactly B),
+    zeros, small and all-ones scalars.  Which variants a family went through is in the trace (test_gpu_msm_paths.py pins the paths case by
+    case); here: n equal scalars put n entries into one bucket per window, so above 64 terms the first attempt cannot hold them
+    (the fused small launch, up to 8192 terms, has lists of 64 or 72; the slot sort of n = 9000 has 16 slots a bucket and 4096 overflow
+    entries for twenty windows) and the MSM is repeated at least once."""
     rng = np.random.default_rng(n)
     pts = orc.commit_vec(orc.rand_scalars(rng, n), None)            # n random valid points
     cases = orc.extreme_scalar_cases(rng, n)
     for name, k in cases.items():
         k = np.ascontiguousarray(k)
-        assert (_gpu_msm(R, k, pts) == orc.msm(k, pts)).all(), name
+        got = _gpu_msm(R, k, pts)
+        trace = R.api.msm_trace()
+        assert (got == orc.msm(k, pts)).all(), (name, trace)
+        if name in ("all_equal", "minus_one"):
+            # (64 terms are the one size >= 64 without a repeat: they fill a small-launch list of 64 exactly)
+            assert (len(trace) > 1 and trace[0]["repeated"]) == (n > 64), (name, trace)
 
 
 def test_cfg4_shape_batch_verify(R):

@@ -220,6 +220,39 @@ int rofl_quantize_prob(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, co
  * on the calling thread's device and lane; the `devices` option does not apply.  Not constant time. */
 int rofl_noise_binomial(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, const float *const *values, size_t first, size_t d, uint32_t k,
                         size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
+/* Norm clipping: an update is projected onto the L2 ball of max_sq grid steps^2 ON the fixed-point grid, the step a client takes after
+ * rounding and before noise, so that the sum of squares the L2 sum proof computes for it is at most max_sq by construction instead of
+ * being found too large (NormOutOfRangeError, 7) after the commitments.  The rule is integer arithmetic on step counts: host, device and
+ * any reduction order give the same bytes.  Outputs are f32 grid values: proofs, commitments, wire bytes and verifiers stay as they are.
+ * Per vector v, with T = max_sq[v], x_i = values[v][i]:
+ *   1. c_i = what rofl_clip_f32 returns for x_i under (prove_range, fp_bits, fp_frac) -- NaN and +-inf included; q_i = the library's
+ *      saturating float-to-fixed rule of |c_i| (nearbyint(|c_i| 2^fp_frac), at most 2^fp_bits - 1): for a value on the grid, its step count.
+ *   2. S = sum_i q_i^2, an exact integer (below d 2^128: accumulated on 192 bits).
+ *   3. S <= T: out_i = the value rule of rofl_noise_binomial with zero noise (clip, round to nearest onto the grid; a grid value comes
+ *      back unchanged, a zero is +0.0); scale_out[v] = 2^32.
+ *   4. S > T: Te = T without seeds; with seeds Te = r^2, r = isqrt(T) - ceil(sqrt(d)).  m = the largest integer below 2^32 with
+ *      m^2 S <= 2^64 Te (m may be 0); scale_out[v] = m.  y_i = q_i m (up to 96 bits), f_i = y_i >> 32, t_i = y_i mod 2^32;
+ *      k_i = f_i without seeds, k_i = f_i + (word(i) < t_i ? 1 : 0) with them, word(i) = word i & 31 of block i >> 5 of the seed's stream:
+ *      the first 128 bytes of SHAKE256("rofl-zk/clip2/v1" || seed[32] || u64le(block)) as 32 little-endian u32 words.
+ *      k'_i = trunc24(k_i): k_i below 2^24, otherwise k_i with all bits below its top 24 cleared, so that k'_i 2^-fp_frac is an exact f32.
+ *      out_i = k'_i 2^-fp_frac with the sign of c_i, +0.0 for k'_i = 0.
+ *   Consequences.  k'_i <= k_i <= q_i for EVERY scaled vector (m <= 2^32 - 1 gives y_i / 2^32 <= q_i - q_i / 2^32, so f_i <= q_i - 1 for
+ *   q_i >= 1, and q_i = 0 gives t_i = 0): the output lies inside the clip range and no magnitude grows.  Without seeds
+ *   sum k'^2 <= (m / 2^32)^2 S <= T.  With seeds, for EVERY stream: ||k'|| <= ||k|| <= ||y / 2^32|| + ||e|| with |e_i| < 1 and
+ *   ||y / 2^32|| = (m / 2^32) sqrt(S) <= r, so ||k'|| <= r + sqrt(d) <= isqrt(T) and sum k'^2 <= T.  Given the scale the seeded rounding is unbiased below 2^24 steps:
+ *   E[k_i] = y_i / 2^32.  A vector that fits is never scaled, so the call is the identity on an honest grid update inside the ball.
+ *   There is no `first`: a norm belongs to the whole vector.
+ * seeds32 = NULL: no seeds (every vector truncates); otherwise one seed per vector (seeds32 + 32 v).  n_vec vectors of one length in ONE
+ * call, each with its own input, output and max_sq; values[v] and out[v] are host or device memory in any combination and out[v] may be
+ * values[v], as for rofl_quantize_prob.  scale_out (n_vec u64, host memory) may be NULL.  Returns 11 before the device is touched for:
+ * an invalid format, prove_range = 0, a null values / out / max_sq array or entry, more than 65 535 vectors, d >= 2^28, and a seeded
+ * vector with isqrt(max_sq) < ceil(sqrt(d)).  n_vec = 0 or d = 0 returns 0 and writes nothing.  An all-host call below a fixed, measured
+ * number of elements runs the rule on the host, compiled from the kernels' source: same bytes, no device needed.
+ * Otherwise two launches (the sum of squares; the scale search and the scaling) with no host round trip between them.  A clip seed is a
+ * per-round secret of the client: seeds never appear in rofl_last_error, and the library's own copies are overwritten with zeros
+ * before the call returns.  Runs on the calling thread's device and lane; the `devices` option does not apply.  Not constant time. */
+int rofl_clip_l2(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 or NULL */, const float *const *values, size_t d, const uint64_t *max_sq /* n_vec */,
+                 size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out, uint64_t *scale_out /* n_vec or NULL */);
 
 /* ---- l2_range_proof_vec (l2_range_proof_vec/mod.rs) ---- */
 /* create_rangeproof_l2 :15-140.  The batch call below with one client, on the calling thread's device: values and blindings32 are host
@@ -799,7 +832,7 @@ int rofl_comm_destroy(void);
  * staging path like every other output.  rofl_quantize_prob is the second exception: each values[v] and each out[v] is host memory or
  * device memory of the library's device, in any combination (4-byte aligned, as a float array is); a device input is read and a device
  * output written in place -- also the same array -- so an update quantized there goes to the create calls as a device input.
- * rofl_noise_binomial takes its values[v] and out[v] in the same way. */
+ * rofl_noise_binomial and rofl_clip_l2 take their values[v] and out[v] in the same way. */
 
 /* ---- behaviour options ----
  * Switches that change WHAT a call returns or how it waits are part of the ABI, not of the process environment.  `key` is one of the

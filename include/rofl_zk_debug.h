@@ -180,6 +180,15 @@ int rofl_dbg_noise_apply(unsigned site, size_t n, const float *values, const int
  * pointers only, else 11), 1 = the kernel.  Same checks, same bytes; what scripts/gpu_binomial_noise.py finds the crossover with. */
 int rofl_dbg_noise_binomial_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
                                   uint32_t k, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
+/* Step 4 of rofl_clip_l2 on caller-supplied step counts, scale and words instead of a vector's sum and a seed's stream: out[i] =
+ * trunc24((q[i] m >> 32) + (words[i] < q[i] m mod 2^32 ? 1 : 0)) 2^-fp_frac, positive; words == NULL: the unseeded rule (no + 1).
+ * site 0: the host copy (no GPU); site 1: the device copy (k_dbg_clip_l2_round, one thread per case).  11: site > 1, fp_frac > 12, a null
+ * q or out with n > 0, n > 2^20. */
+int rofl_dbg_clip_l2_round(unsigned site, size_t n, const uint64_t *q, uint32_t m, const uint32_t *words, unsigned fp_frac, float *out);
+/* rofl_clip_l2 with the route chosen by the caller instead of by the pointers and the size: route 0 = the host copy of the rule (host
+ * pointers only, else 11), 1 = the kernels.  Same checks, same bytes; what scripts/gpu_l2_clip.py finds the crossover with. */
+int rofl_dbg_clip_l2_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq,
+                           size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out, uint64_t *scale_out);
 /* one pair of rofl_dh_shared from the host arithmetic (no GPU): out32 and *status as that call gives them; own_pk32 == NULL: computed from sk32.
  * Returns 11 for a null pointer or a secret key that is 0 mod l. */
 int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status);

@@ -123,6 +123,11 @@ extern "C" {
     /// clipped again; values[v] / out[v] are host memory or device memory of the library's device, and may be the same array
     pub fn rofl_noise_binomial(n_vec: usize, seeds32: *const u8, values: *const *const c_float, first: usize, d: usize, k: u32,
         prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *const *mut c_float) -> c_int;
+    /// projection onto the L2 ball on the fixed-point grid, n_vec vectors (own input, output, max_sq and optional seed each) in one call:
+    /// out[v] = values[v] on the grid when its sum of squared steps is at most max_sq[v], else scaled by m / 2^32 so that the sum of
+    /// squares of the result is; seeds32 null: truncation, else seeded rounding of the scaled steps; scale_out (n_vec u64) may be null
+    pub fn rofl_clip_l2(n_vec: usize, seeds32: *const u8, values: *const *const c_float, d: usize, max_sq: *const u64, prove_range: usize,
+        fp_bits: c_uint, fp_frac: c_uint, out: *const *mut c_float, scale_out: *mut u64) -> c_int;
     pub fn rofl_verify_rangeproof_l2_batch(n_clients: usize, proofs: *const *const u8, proof_len: usize, commits32: *const u8,
         prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, verifier_seed: *const u8, ok_out: *mut c_int) -> c_int;
     pub fn rofl_verify_randproof_vec_batch(n_clients: usize, proofs: *const *const u8, commits: *const *const u8, d: usize, ok_out: *mut c_int) -> c_int;

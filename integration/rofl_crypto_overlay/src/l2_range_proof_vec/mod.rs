@@ -50,6 +50,21 @@ pub fn verify_rangeproof_l2(range_proof: &RangeProof, commit: &RistrettoPoint, p
     }
 }
 
+/// No counterpart in the reference (its trainer clips in float): projection of an update onto the L2 ball of `max_sq` grid steps^2 ON the
+/// fixed-point grid, so that the sum of squares `create_rangeproof_l2` computes for the result is at most `max_sq` by construction.  A
+/// vector inside the ball comes back on the grid unchanged; otherwise its steps are scaled by m / 2^32 and truncated (`seed` None) or
+/// rounded by the words of the seed's stream -- a per-round secret of the client.  Returns (values, scale): scale is 2^32 for a vector
+/// that fitted, else m.  Panics on a bad parameter (a seeded call needs isqrt(max_sq) >= ceil(sqrt(d))).
+pub fn clip_l2(value_vec: &Vec<f32>, prove_range: usize, max_sq: u64, seed: Option<&[u8; 32]>) -> (Vec<f32>, u64) {
+    let mut out = vec![0f32; value_vec.len()];
+    let mut scale: u64 = 0;
+    let (vp, op) = (value_vec.as_ptr(), out.as_mut_ptr());
+    let sp = seed.map_or(std::ptr::null(), |s| s.as_ptr());
+    let rc = unsafe { rofl_clip_l2(1, sp, &vp, value_vec.len(), &max_sq, prove_range, fp_bits(), fp_frac(), &op, &mut scale) };
+    if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+    (out, scale)
+}
+
 /// `create_rangeproof_l2` for the clients of one process (client.rs:265-266 runs them as tasks of one process): ONE
 /// rofl_create_rangeproof_l2_batch call -- one kernel for every client's sums, one Bulletproof launch sequence for all sum proofs.  Entry i
 /// is what `create_rangeproof_l2` returns for client i, its error included.

@@ -653,6 +653,80 @@ class range_proof_vec:
 
 
 class l2_range_proof_vec:
+    # ---- norm clipping (rofl_clip_l2): projection onto the L2 ball on the fixed-point grid, two launches per call ----
+    @staticmethod
+    def clip_l2_vecs(list_of_values, prove_range, max_sq, seeds=None, fp=None, out=None, with_scale=False):
+        """rofl_clip_l2 for several vectors of one length (the clients a process hosts) in ONE call: vector v is clipped like
+        clip_f32_to_range_vec and converted to grid steps q; if sum q^2 <= max_sq[v] it comes back on the grid unchanged, otherwise it is
+        scaled by m / 2^32, m the largest integer with m^2 sum q^2 <= 2^64 Te, so that the exact integer sum of squares of the RESULT -- what
+        the L2 sum proof computes -- is at most max_sq[v] (include/rofl_zk.h has the definition and the proof).  max_sq is an int (steps^2,
+        norm_budget) or one int per vector.  seeds=None: the scaled steps are truncated (Te = max_sq); seeds = one 32-byte seed per
+        vector: they are rounded up or down by the words of the seed's stream, unbiased given the scale, inside the smaller budget
+        Te = (isqrt(max_sq) - ceil(sqrt(d)))^2 that holds the bound for every stream; a seeds list with None entries makes one seeded and
+        one unseeded call.  Vectors, `out` and the return value are as in range_proof_vec.quantize_probabilistic_vecs: numpy arrays or
+        float32 tensors on the library's GPU, also in place.  with_scale=True: -> (vectors, [scale per vector]), 2^32 for a vector that
+        fitted, else m.  A seed is a per-round SECRET of its client (pedersen_ops.clip_round_seed)."""
+        n, fp = len(list_of_values), _fp(fp)
+        ts = [int(max_sq)] * n if isinstance(max_sq, (int, np.integer)) else [int(t) for t in max_sq]
+        if len(ts) != n:
+            raise ValueError("one max_sq per vector")
+        if any(t < 0 or t >> 64 for t in ts):
+            raise ValueError("max_sq is an unsigned 64-bit number of steps^2")
+        if seeds is not None:
+            seeds = list(seeds)
+            if len(seeds) != n:
+                raise ValueError("one seed (or None) per vector")
+            if all(s is None for s in seeds):
+                seeds = None
+
+        def call(idx, dst):      # ONE rofl_clip_l2 call over the vectors `idx`, all seeded or none
+            tb = (ctypes.c_uint64 * max(len(idx), 1))(*[ts[i] for i in idx])
+            sc = (ctypes.c_uint64 * max(len(idx), 1))()
+            sub = [seeds[i] for i in idx] if seeds is not None and idx and seeds[idx[0]] is not None else None
+            res = range_proof_vec._seeded_vecs([list_of_values[i] for i in idx], prove_range, sub if sub is not None else [bytes(32)] * len(idx), 0, dst,
+                                               lambda n_, sb, vp, first, d, op: lib().rofl_clip_l2(n_, sb if sub is not None else None, vp, d, tb, _sz(prove_range),
+                                                                                                    *fp, op, sc))
+            return res, [int(s) for s in sc[:len(idx)]]
+        if seeds is None or all(s is not None for s in seeds):
+            res, scales = call(list(range(n)), out)
+            return (res, scales) if with_scale else res
+        # a seeded and an unseeded call, each into the destinations of its own vectors
+        dst = list(out) if out is not None else None
+        if dst is not None and len(dst) != n:
+            raise ValueError("one destination per vector")
+        res, scales = [None] * n, [None] * n
+        for idx in ([i for i, s in enumerate(seeds) if s is not None], [i for i, s in enumerate(seeds) if s is None]):
+            r, sc = call(idx, None if dst is None else [dst[i] for i in idx])
+            for row, i in enumerate(idx):
+                res[i], scales[i] = r[row], sc[row]
+        if dst is None:
+            res = np.stack(res)
+        return (res, scales) if with_scale else res
+
+    @staticmethod
+    def clip_l2(values, prove_range, max_sq, seed=None, fp=None, with_scale=False):
+        """clip_l2_vecs for one vector -> float32[d] on the fixed-point grid with sum of squared steps <= max_sq (with_scale: and its scale)."""
+        r = l2_range_proof_vec.clip_l2_vecs([values], prove_range, [int(max_sq)], None if seed is None else [seed], fp, None, with_scale)
+        return (r[0][0], r[1][0]) if with_scale else r[0]
+
+    @staticmethod
+    def norm_budget(l2_range, fp=None, reserve_steps=0):
+        """(isqrt(B) - reserve_steps)^2 with B = (2^l2_range - 1) & (2^fp_bits - 1): the max_sq of clip_l2 for an update that is proved with
+        `l2_range`.  B is the integer behind the bound of the norm check (conversion32.get_l2_clip_bounds): every sum of squares S <= B
+        passes it.  reserve_steps keeps room for what is added AFTER the clip: the noise of noise_k (range_proof_vec.add_binomial_noise) adds
+        an L2 length of about sqrt(d noise_k / 2) steps, and since the length of a sum is at most the sum of the lengths, an update clipped
+        to isqrt(B) - reserve stays inside B as long as the noise is no longer than the reserve.  How many steps to reserve is the
+        deployment's choice: no tail bound is built in, and a draw longer than the reserve fails with NormOutOfRangeError (7) as before.
+        S must also stay where the f32 shadow sum of the sum proof is exact (the OverflowError rule, 5); this call does not change that.
+        Raises ValueError when the reserve exceeds isqrt(B)."""
+        fp, l2_range, reserve_steps = _fp(fp), int(l2_range), int(reserve_steps)
+        if l2_range < 1 or reserve_steps < 0:
+            raise ValueError("l2_range is at least 1 and the reserve is not negative")
+        r = math.isqrt(((1 << l2_range) - 1) & ((1 << fp[0]) - 1)) - reserve_steps
+        if r < 0:
+            raise ValueError("the reserve exceeds the whole budget of isqrt(B) steps")
+        return r * r
+
     @staticmethod
     def create_rangeproof_l2(values, blindings, prove_range, n_partition, nonce=None, fp=None):
         v = np.ascontiguousarray(values, dtype=np.float32)
@@ -2302,6 +2376,13 @@ class pedersen_ops:
         The seed is a per-round secret of the client: whoever learns it computes the client's noise and removes it from the client's share
         of the released sum, and a seed used in two rounds adds the same noise in both, which their difference cancels."""
         return hashlib.sha3_256(b"rofl-zk/noise/v1/round" + bytes(secret) + struct.pack("<Q", int(round_no))).digest()
+
+    @staticmethod
+    def clip_round_seed(secret, round_no):
+        """SHA3-256("rofl-zk/clip2/v1/round" || secret || u64le(round_no)): the seed a client rounds its norm-clipped update with in round
+        `round_no` (l2_range_proof_vec.clip_l2, the clip_seed of the L2 containers' encrypt), from a long-lived secret of ITS OWN.  The
+        seed is a per-round secret of the client: whoever learns it learns which way every scaled coordinate was rounded."""
+        return hashlib.sha3_256(b"rofl-zk/clip2/v1/round" + bytes(secret) + struct.pack("<Q", int(round_no))).digest()
 
     @staticmethod
     def compute_shifted_values_vec(values, offset):

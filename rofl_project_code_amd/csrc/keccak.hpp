@@ -113,6 +113,9 @@ HD void shake256_seeded_block(u64 st[25], const u64 dom[2], const u64 seed[4], u
 // Fair bits of the distributed noise (rofl_noise_binomial): a fifth label, so that the noise of a client that reuses its rounding seed is
 // still unrelated to the words that rounded its update.
 #define ROFL_NOISE_DOM {0x2f6b7a2d6c666f72ULL, 0x31762f6573696f6eULL}      /* "rofl-zk/" "noise/v1" */
+// Rounding words of the norm clipping (rofl_clip_l2): a sixth label, so that the words that round the scaled update are unrelated to the
+// words that rounded it onto the grid and to its noise, also under a reused seed.
+#define ROFL_CLIP_DOM {0x2f6b7a2d6c666f72ULL, 0x31762f3270696c63ULL}       /* "rofl-zk/" "clip2/v1" */
 // wide scalar h (0 / 1) of a squeezed block: bytes 64 h .. 64 h + 64, reduced like Scalar::from_bytes_mod_order_wide (canonical)
 HD sc xof_block_scalar(const u64 st[25], int h) {
     sc lo, hi;

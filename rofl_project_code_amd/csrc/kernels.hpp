@@ -545,7 +545,7 @@ __global__ void __launch_bounds__(TPB) k_dbg_noise_apply(u32 n, const float *val
 // sum of k_i^2 < d 2^128 < l: a 192-bit accumulator, exact in any order, never reduced; the blinding sum mod l (inputs >= l reduced first,
 // exact in any order); and, per ELEMENT, the term q q 2^frac of the reference's f32 shadow sum, q = (float)k / 2^frac -- the shadow sum
 // itself is serial by definition and stays on the host.  Block partials go to memory; k_l2_sumsq_combine adds them.
-__device__ __forceinline__ void u192_add(u64 *a, u64 b0, u64 b1, u64 b2) {
+HD void u192_add(u64 *a, u64 b0, u64 b1, u64 b2) {
     u64 t = a[0] + b0, c = t < b0; a[0] = t;
     t = a[1] + b1; u64 c1 = t < b1; t += c; c1 += t < c; a[1] = t;
     a[2] += b2 + c1;
@@ -592,6 +592,147 @@ __global__ void __launch_bounds__(64) k_l2_sumsq_combine(u32 n_clients, u32 nblk
     sc v = sc_zero();
     for (int q = 0; q < 3; q++) { v.v[2 * q] = (u32)a[q]; v.v[2 * q + 1] = (u32)(a[q] >> 32); }
     out[2 * c] = v; out[2 * c + 1] = bl;
+}
+#endif
+
+// ================================================================ norm clipping
+// rofl_clip_l2 (the definition is in include/rofl_zk.h): an update is projected onto the L2 ball of max_sq steps^2 ON the fixed-point grid,
+// in integers, so that the sum of squares the kernel above computes for the result is at most max_sq whatever the order of any reduction.
+// The per-element rule and the search for the scale are compiled for the host and the device from this one source.
+HD void mul64_wide(u64 a, u64 b, u64 *lo, u64 *hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *lo = a * b; *hi = __umul64hi(a, b);
+#else
+    const unsigned __int128 p = (unsigned __int128)a * b; *lo = (u64)p; *hi = (u64)(p >> 64);
+#endif
+}
+// step 1: c = what rofl_clip_f32 returns for x (the comparisons of quant_prob_round), q = the k of k_l2_sumsq_batch for c
+HD u64 clip_l2_steps(float x, float clip_min, float clip_max, u32 fp_bits, u32 fp_frac, float *c_out) {
+    float c = (clip_min >= x || x != x) ? clip_min : x;
+    c = (clip_max <= c) ? clip_max : c;
+    *c_out = c;
+    const u64 maxbits = fp_bits >= 64 ? ~0ULL : ((1ULL << fp_bits) - 1);
+    const double lim = fp_bits >= 64 ? 18446744073709551616.0 : (double)(1ULL << fp_bits);
+    const double xs = fabs((double)c) * (double)(1ULL << fp_frac);
+    if (xs >= lim) return maxbits;
+    const double r = rint(xs);
+    return (r >= lim) ? maxbits : (u64)r;
+}
+// m^2 S <= 2^64 Te, on 256 bits (m < 2^32, S < 2^192)
+HD bool clip_l2_scale_ok(u64 m, const u64 S[3], u64 te) {
+    const u64 mm = m * m;
+    u64 p0, p1, p2, p3, lo, hi;
+    mul64_wide(mm, S[0], &p0, &p1);
+    mul64_wide(mm, S[1], &lo, &hi); p1 += lo; p2 = hi + (p1 < lo);      // (hi <= 2^64 - 2: the carry fits)
+    mul64_wide(mm, S[2], &lo, &hi); p2 += lo; p3 = hi + (p2 < lo);
+    return p3 == 0 && p2 == 0 && (p1 < te || (p1 == te && p0 == 0));
+}
+// step 4: the largest m below 2^32 with m^2 S <= 2^64 Te, bit by bit from the top (the test is monotone in m): 32 steps
+HD u32 clip_l2_scale(const u64 S[3], u64 te) {
+    u32 m = 0;
+    for (int b = 31; b >= 0; b--) { const u32 c = m | (1u << b); if (clip_l2_scale_ok(c, S, te)) m = c; }
+    return m;
+}
+HD bool clip_l2_fits(const u64 S[3], u64 max_sq) { return S[2] == 0 && S[1] == 0 && S[0] <= max_sq; }
+// step 4 for one element: y = q m on 96 bits, k = y >> 32 (+ 1 when the word lies below y mod 2^32), trunc24, the sign of c.  k <= q for
+// every m below 2^32, so the result lies inside the clip range; k' has at most 24 significant bits, so every conversion below is exact.
+HD float clip_l2_round(u64 q, u32 m, bool seeded, u32 word, float c, u32 fp_frac) {
+    const u64 lo = (q & 0xffffffffULL) * m, hi = (q >> 32) * m;
+    u64 k = hi + (lo >> 32);
+    if (seeded && word < (u32)lo) k++;
+    if (k >> 24) k &= ~((1ULL << (40 - __builtin_clzll(k))) - 1);
+    if (k == 0) return 0.0f;
+    return copysignf((float)((double)k / (double)(1u << fp_frac)), c);
+}
+// One descriptor per vector, as QuantVec (its first three members): max_sq = T, te = the budget the scale is computed for (T without
+// seeds, (isqrt(T) - ceil(sqrt(d)))^2 with them: computed by the host).
+struct ClipVec { const float *in; float *out; u64 seed[4]; u64 max_sq, te; };
+#define CL_TPB 256
+#if ROFL_KG(4)
+// blockIdx.y = vector; gridDim.x blocks (a fixed number, at most what d needs) stride over its d values with coalesced loads, each lane
+// summing q^2 on 192 bits; the wave's sums are added by shuffles, the block's four waves through LDS, and the block writes ONE partial.
+__global__ void __launch_bounds__(CL_TPB) k_clip_l2_sumsq(const ClipVec *__restrict__ vecs, u32 d, float clip_min, float clip_max, u32 fp_bits, u32 fp_frac,
+                                                          u64 *part /* [vector][gridDim.x][3] */) {
+    __shared__ u64 s_p[CL_TPB / 64][3];
+    const float *in = vecs[blockIdx.y].in;
+    u64 acc[3] = {0, 0, 0};
+    for (u32 i = blockIdx.x * CL_TPB + threadIdx.x; i < d; i += gridDim.x * CL_TPB) {      // (d < 2^28: i does not wrap)
+        float c; const u64 q = clip_l2_steps(in[i], clip_min, clip_max, fp_bits, fp_frac, &c);
+        u64 lo, hi; mul64_wide(q, q, &lo, &hi);
+        u192_add(acc, lo, hi, 0);
+    }
+    for (int o = 32; o; o >>= 1) {
+        const u64 b0 = __shfl_down((unsigned long long)acc[0], o), b1 = __shfl_down((unsigned long long)acc[1], o), b2 = __shfl_down((unsigned long long)acc[2], o);
+        u192_add(acc, b0, b1, b2);
+    }
+    if ((threadIdx.x & 63) == 0) { s_p[threadIdx.x >> 6][0] = acc[0]; s_p[threadIdx.x >> 6][1] = acc[1]; s_p[threadIdx.x >> 6][2] = acc[2]; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (u32 w = 1; w < CL_TPB / 64; w++) u192_add(acc, s_p[w][0], s_p[w][1], s_p[w][2]);
+        u64 *p = part + 3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+        p[0] = acc[0]; p[1] = acc[1]; p[2] = acc[2];
+    }
+}
+// blockIdx.y = vector; a block is ONE wave and owns elements 2048 blockIdx.x .. + 2047, the layout of k_quantize_prob.  Prologue: lane 0
+// adds the vector's n_part partials (the launch-boundary combine: no launch of its own) and, when the sum exceeds max_sq, runs the 32-step
+// search; scale and branch reach the wave through LDS, and block 0 writes scale_out.  A vector that fits takes the value rule with zero
+// noise and permutes nothing.  Otherwise, with seeds, lane t permutes XOF block 64 blockIdx.x + t and the words pass through LDS rows 33
+// words apart (32 lanes of a half write 32 banks and read one row), so that every pass loads and stores 64 consecutive floats.  in == out
+// is allowed: an element is read and written by one lane, and k_clip_l2_sumsq has finished with the input.
+template <bool SEEDED>
+__device__ __forceinline__ void clip_l2_apply_body(const ClipVec *__restrict__ vecs, u32 d, u32 n_part, const u64 *__restrict__ part, float clip_min,
+                                                   float clip_max, u32 fp_bits, u32 fp_frac, u64 *scale_out) {
+    __shared__ u32 s_w[SEEDED ? QP_TPB * 33 : 1];
+    __shared__ u32 s_m[2];
+    const ClipVec *V = &vecs[blockIdx.y];
+    if (threadIdx.x == 0) {
+        u64 S[3] = {0, 0, 0};
+        const u64 *p = part + 3 * (size_t)blockIdx.y * n_part;
+        for (u32 b = 0; b < n_part; b++) u192_add(S, p[3 * b], p[3 * b + 1], p[3 * b + 2]);
+        const bool fits = clip_l2_fits(S, V->max_sq);
+        const u32 m = fits ? 0 : clip_l2_scale(S, V->te);
+        s_m[0] = m; s_m[1] = fits;
+        if (blockIdx.x == 0) scale_out[blockIdx.y] = fits ? (1ULL << 32) : (u64)m;
+    }
+    __syncthreads();
+    const u32 m = s_m[0]; const bool fits = s_m[1] != 0;
+    const u32 e0 = blockIdx.x * (32 * QP_TPB);      // (< d < 2^28)
+    if (SEEDED && !fits) {      // (uniform in the block)
+        const u32 blk = blockIdx.x * QP_TPB + threadIdx.x;
+        if (32 * (u64)blk < d) {
+            const u64 dom[2] = ROFL_CLIP_DOM;
+            const u64 sw[4] = {V->seed[0], V->seed[1], V->seed[2], V->seed[3]};
+            u64 st[25];
+            shake256_seeded_block(st, dom, sw, blk);
+#pragma unroll
+            for (u32 j = 0; j < 32; j++) s_w[threadIdx.x * 33 + j] = quant_block_word(st, j);
+        }
+        __syncthreads();
+    }
+    const float *in = V->in; float *out = V->out;
+    for (u32 i = 0; i < 32; i++) {
+        const u32 q = i * QP_TPB + threadIdx.x, e = e0 + q;
+        if (e >= d) break;
+        const float x = in[e];
+        if (fits) { out[e] = noise_apply(x, 0, clip_min, clip_max, fp_frac); continue; }
+        float c; const u64 k = clip_l2_steps(x, clip_min, clip_max, fp_bits, fp_frac, &c);
+        out[e] = clip_l2_round(k, m, SEEDED, SEEDED ? s_w[(q >> 5) * 33 + (q & 31)] : 0u, c, fp_frac);
+    }
+}
+// (two kernels, not a template: the host sees the kernels through generated prototypes)
+__global__ void __launch_bounds__(QP_TPB) k_clip_l2_apply(const ClipVec *__restrict__ vecs, u32 d, u32 n_part, const u64 *__restrict__ part, float clip_min,
+                                                          float clip_max, u32 fp_bits, u32 fp_frac, u64 *scale_out /* [vector] */) {
+    clip_l2_apply_body<false>(vecs, d, n_part, part, clip_min, clip_max, fp_bits, fp_frac, scale_out);
+}
+__global__ void __launch_bounds__(QP_TPB) k_clip_l2_apply_seeded(const ClipVec *__restrict__ vecs, u32 d, u32 n_part, const u64 *__restrict__ part, float clip_min,
+                                                                 float clip_max, u32 fp_bits, u32 fp_frac, u64 *scale_out /* [vector] */) {
+    clip_l2_apply_body<true>(vecs, d, n_part, part, clip_min, clip_max, fp_bits, fp_frac, scale_out);
+}
+// rofl_dbg_clip_l2_round site 1: step 4 as the device compiles it, on the caller's q, m and words, one thread per case
+__global__ void __launch_bounds__(TPB) k_dbg_clip_l2_round(u32 n, const u64 *q, u32 m, const u32 *words, u32 fp_frac, float *out) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    out[t] = clip_l2_round(q[t], m, words != nullptr, words ? words[t] : 0u, 1.0f, fp_frac);
 }
 #endif
 

@@ -2423,9 +2423,12 @@ static void quant_prob_host(const uint8_t *seed32, const float *in, u64 first, s
 }
 // What rofl_quantize_prob and rofl_noise_binomial share once their parameters are checked.  route: -1 = by the pointers and the size
 // (`small`: an all-host call runs on the host), 0 = the host copy, 1 = the kernel.  host(v) runs the rule of vector v on the host;
-// launch(C, vecs) enqueues the kernel over the device copy of the descriptors on C.stream.
+// launch(C, vecs) enqueues the kernel over the device copy of the descriptors on C.stream.  rofl_clip_l2 comes here too: its descriptors
+// (ClipVec) begin with a QuantVec and are `stride` bytes apart, fill(v, desc) writes what follows, its seeds32 may be null (no seeds:
+// zeros), and its launch also enqueues the copy of what the kernels leave besides the vectors.
 static int seeded_vecs_run(int route, bool small, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, float *const *out,
-                           const std::function<void(size_t)> &host, const std::function<void(Ctx &, const QuantVec *)> &launch) {
+                           const std::function<void(size_t)> &host, const std::function<void(Ctx &, const QuantVec *)> &launch,
+                           size_t stride = sizeof(QuantVec), const std::function<void(size_t, QuantVec *)> &fill = {}) {
     return guarded([&]() -> int {
         std::vector<char> dev_in(n_vec, 0), dev_out(n_vec, 0); bool all_host = true;
         for (size_t v = 0; v < n_vec; v++) { dev_in[v] = is_device_ptr(values[v]); dev_out[v] = is_device_ptr(out[v]); all_host &= !dev_in[v] && !dev_out[v]; }
@@ -2441,20 +2444,21 @@ static int seeded_vecs_run(int route, bool small, size_t n_vec, const uint8_t *s
         size_t n_slot = 0;
         for (size_t v = 0; v < n_vec; v++) if (!dev_in[v] || !dev_out[v]) n_slot++;
         float *ws = n_slot ? C.vals.as<float>(n_slot * d) : nullptr;
-        const size_t bytes = n_vec * sizeof(QuantVec);
+        const size_t bytes = n_vec * stride;
         uint8_t *h = C.h_misc.as<uint8_t>(bytes), *dv = C.tmp_in.as<uint8_t>(bytes);
-        BlindWipe wipe; wipe.h = h; wipe.dv = dv; wipe.n = bytes; wipe.s = C.stream;      // (the seeds: zeroed when the call returns or unwinds)
-        QuantVec *hv = reinterpret_cast<QuantVec *>(h);
+        BlindWipe wipe; wipe.h = h; wipe.dv = dv; wipe.n = seeds32 ? bytes : 0; wipe.s = C.stream;      // (the seeds: zeroed when the call returns or unwinds)
+        auto hv = [&](size_t v) { return reinterpret_cast<QuantVec *>(h + v * stride); };
         size_t slot = 0;
         for (size_t v = 0; v < n_vec; v++) {
             float *s = (!dev_in[v] || !dev_out[v]) ? ws + (slot++) * d : nullptr;
-            hv[v].in = dev_in[v] ? values[v] : s; hv[v].out = dev_out[v] ? out[v] : s;
-            memcpy(hv[v].seed, seeds32 + 32 * v, 32);
+            hv(v)->in = dev_in[v] ? values[v] : s; hv(v)->out = dev_out[v] ? out[v] : s;
+            if (seeds32) memcpy(hv(v)->seed, seeds32 + 32 * v, 32); else memset(hv(v)->seed, 0, 32);
+            if (fill) fill(v, hv(v));
             if (!dev_in[v]) C.up(s, values[v], 4 * d, C.stream);
         }
         HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, C.stream));
         launch(C, reinterpret_cast<const QuantVec *>(dv));
-        for (size_t v = 0; v < n_vec; v++) if (!dev_out[v]) C.down(out[v], hv[v].out, 4 * d, C.stream);
+        for (size_t v = 0; v < n_vec; v++) if (!dev_out[v]) C.down(out[v], hv(v)->out, 4 * d, C.stream);
         C.sync();
         return ROFL_OK;
     });
@@ -2537,6 +2541,82 @@ static int noise_binomial_impl(int route, size_t n_vec, const uint8_t *seeds32, 
 int rofl_noise_binomial(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, uint32_t k, size_t prove_range,
                         unsigned fp_bits, unsigned fp_frac, float *const *out) {
     return noise_binomial_impl(-1, n_vec, seeds32, values, first, d, k, prove_range, fp_bits, fp_frac, out);
+}
+// ---- norm clipping (rofl_clip_l2: the definition is in the header, the rule, the search and the kernels in kernels.hpp) ----
+// Below this many elements in all, a call whose pointers are all host memory runs the rule on the host: two passes of one core over the
+// values (and one Keccak-f per 32 elements with seeds) against the fixed cost of two staged copies, two launches and a synchronisation.
+// The measured crossovers, the first size of the sweep at which the kernels win (profiles/l2_clip.json); constants,
+// not knobs: both routes give the same bytes.
+constexpr size_t kClipL2HostBelow = 16384, kClipL2HostBelowSeeded = 8192;
+constexpr u32 kClipL2Blocks = 8;      // k_clip_l2_sumsq, per vector: 2 048 threads stride over d, as the sums of the L2 proof (kL2SumBlocks)
+static u64 isqrt_u64(u64 x) {
+    u64 r = (u64)std::sqrt((long double)x);
+    while ((unsigned __int128)r * r > x) r--;
+    while ((unsigned __int128)(r + 1) * (r + 1) <= x) r++;
+    return r;
+}
+// Te of a seeded vector: (isqrt(T) - ceil(sqrt(d)))^2; false when the difference is negative
+static bool clip_l2_seeded_budget(u64 T, size_t d, u64 *te) {
+    const u64 rt = isqrt_u64(T), rd = d ? isqrt_u64(d - 1) + 1 : 0;
+    if (rt < rd) return false;
+    *te = (rt - rd) * (rt - rd); return true;
+}
+static void clip_l2_host(const uint8_t *seed32 /* or null */, const float *in, size_t d, u64 T, u64 te, float mn, float mx, unsigned fp_bits, unsigned fp_frac,
+                         float *out, uint64_t *scale) {
+    u64 S[3] = {0, 0, 0};
+    for (size_t i = 0; i < d; i++) {
+        float c; const u64 q = clip_l2_steps(in[i], mn, mx, fp_bits, fp_frac, &c);
+        u64 lo, hi; mul64_wide(q, q, &lo, &hi); u192_add(S, lo, hi, 0);
+    }
+    if (clip_l2_fits(S, T)) {
+        for (size_t i = 0; i < d; i++) out[i] = noise_apply(in[i], 0, mn, mx, fp_frac);
+        if (scale) *scale = 1ULL << 32;
+        return;
+    }
+    const u32 m = clip_l2_scale(S, te);
+    const u64 dom[2] = ROFL_CLIP_DOM;
+    u64 sd[4] = {0, 0, 0, 0}, st[25], cur = ~0ULL;
+    if (seed32) memcpy(sd, seed32, 32);
+    for (size_t i = 0; i < d; i++) {
+        if (seed32 && (i >> 5) != cur) { cur = i >> 5; shake256_seeded_block(st, dom, sd, cur); }
+        float c; const u64 q = clip_l2_steps(in[i], mn, mx, fp_bits, fp_frac, &c);
+        out[i] = clip_l2_round(q, m, seed32 != nullptr, seed32 ? quant_block_word(st, (u32)(i & 31)) : 0u, c, fp_frac);
+    }
+    if (scale) *scale = m;
+    volatile u64 *p = sd; for (int i = 0; i < 4; i++) p[i] = 0;
+    if (seed32) { p = st; for (int i = 0; i < 25; i++) p[i] = 0; }
+}
+// route: as seeded_vecs_run (rofl_dbg_clip_l2_route)
+static int clip_l2_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq, size_t prove_range,
+                        unsigned fp_bits, unsigned fp_frac, float *const *out, uint64_t *scale_out) {
+    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec == 0) return ROFL_OK;
+    if (!values || !out || !max_sq) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
+    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
+    if (d == 0) return ROFL_OK;
+    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::vector<u64> te(max_sq, max_sq + n_vec);
+    if (seeds32) for (size_t v = 0; v < n_vec; v++)
+        if (!clip_l2_seeded_budget(max_sq[v], d, &te[v])) return fail(ROFL_BAD_PARAM, "max_sq leaves no room for the rounding of d elements: isqrt(max_sq) < ceil(sqrt(d))");
+    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+    return seeded_vecs_run(route, n_vec * d < (seeds32 ? kClipL2HostBelowSeeded : kClipL2HostBelow), n_vec, seeds32, values, d, out,
+        [&](size_t v) { clip_l2_host(seeds32 ? seeds32 + 32 * v : nullptr, values[v], d, max_sq[v], te[v], mn, mx, fp_bits, fp_frac, out[v], scale_out ? scale_out + v : nullptr); },
+        [&](Ctx &C, const QuantVec *qv) {
+            const ClipVec *vecs = reinterpret_cast<const ClipVec *>(qv);
+            const u32 n_part = (u32)std::min<size_t>(kClipL2Blocks, (d + CL_TPB - 1) / CL_TPB);
+            u64 *part = C.tmp_out.as<u64>(n_vec * (3 * (size_t)n_part + 1)), *dscale = part + 3 * (size_t)n_part * n_vec;
+            ROFL_LAUNCH(k_clip_l2_sumsq, dim3(n_part, (unsigned)n_vec), dim3(CL_TPB), 0, C.stream, vecs, (u32)d, mn, mx, (u32)fp_bits, (u32)fp_frac, part);
+            const dim3 grid((unsigned)((d + 32 * QP_TPB - 1) / (32 * QP_TPB)), (unsigned)n_vec);
+            if (seeds32) ROFL_LAUNCH(k_clip_l2_apply_seeded, grid, dim3(QP_TPB), 0, C.stream, vecs, (u32)d, n_part, (const u64 *)part, mn, mx, (u32)fp_bits, (u32)fp_frac, dscale);
+            else ROFL_LAUNCH(k_clip_l2_apply, grid, dim3(QP_TPB), 0, C.stream, vecs, (u32)d, n_part, (const u64 *)part, mn, mx, (u32)fp_bits, (u32)fp_frac, dscale);
+            if (scale_out) C.down(scale_out, dscale, 8 * n_vec, C.stream);
+        },
+        sizeof(ClipVec), [&](size_t v, QuantVec *qv) { ClipVec *cv = reinterpret_cast<ClipVec *>(qv); cv->max_sq = max_sq[v]; cv->te = te[v]; });
+}
+int rofl_clip_l2(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq, size_t prove_range, unsigned fp_bits,
+                 unsigned fp_frac, float *const *out, uint64_t *scale_out) {
+    return clip_l2_impl(-1, n_vec, seeds32, values, d, max_sq, prove_range, fp_bits, fp_frac, out, scale_out);
 }
 // ---- key agreement: where the pairwise masks' shared secrets come from (k_dh_public, k_dh_decode, k_dh_shared) ----
 }  // extern "C"
@@ -4699,6 +4779,27 @@ int rofl_dbg_noise_binomial_route(unsigned route, size_t n_vec, const uint8_t *s
                                   uint32_t k, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
     if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
     return noise_binomial_impl((int)route, n_vec, seeds32, values, first, d, k, prove_range, fp_bits, fp_frac, out);
+}
+int rofl_dbg_clip_l2_round(unsigned site, size_t n, const uint64_t *q, uint32_t m, const uint32_t *words, unsigned fp_frac, float *out) {
+    if (site > 1 || fp_frac > 12 || n > (1u << 20) || (n && (!q || !out))) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n == 0) return ROFL_OK;
+    if (site == 0) { for (size_t i = 0; i < n; i++) out[i] = clip_l2_round(q[i], m, words != nullptr, words ? words[i] : 0u, 1.0f, fp_frac); return ROFL_OK; }
+    return guarded([&]() -> int {
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        u64 *dq = C.vals.as<u64>(n); float *dout = C.tmp_out.as<float>(n);
+        u32 *dw = words ? C.tmp_in.as<u32>(n) : nullptr;
+        C.up(dq, q, 8 * n, C.stream); if (words) C.up(dw, words, 4 * n, C.stream);
+        ROFL_LAUNCH(k_dbg_clip_l2_round, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (const u64 *)dq, (u32)m, (const u32 *)dw, (u32)fp_frac, dout);
+        C.down(out, dout, 4 * n, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
+int rofl_dbg_clip_l2_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq,
+                           size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out, uint64_t *scale_out) {
+    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return clip_l2_impl((int)route, n_vec, seeds32, values, d, max_sq, prove_range, fp_bits, fp_frac, out, scale_out);
 }
 
 }  // extern "C"

@@ -215,28 +215,49 @@ def _noise_args(noise_seed, noise_k):
     return noise_seed is not None
 
 
-def _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed=None, noise_k=None):
+#
+# The L2 containers' l2_clip + clip_seed / clip_seeds (norm clipping, l2_range_proof_vec.clip_l2): l2_clip is the budget max_sq in grid
+# steps^2 (l2_range_proof_vec.norm_budget(l2_range) for the whole bound of the norm check), clip_seed an optional 32-byte seed that rounds
+# the scaled steps instead of truncating them (pedersen_ops.clip_round_seed, a per-round SECRET of the client).  The clip stands between
+# the rounding and the noise: after it the exact integer sum of squares the sum proof computes is at most l2_clip, so a quant_seed can no
+# longer push an update over the bound, and the noise can only by more than the steps norm_budget reserved for it.  Its output is the
+# plaintext of every leg and of the witness digest.  Without l2_clip nothing changes.
+def _clip_args(l2_clip, clip_seed):
+    if l2_clip is None and clip_seed is not None:
+        raise ValueError("clip_seed(s) without l2_clip")
+    return l2_clip is not None
+
+
+def _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed=None, noise_k=None, l2_clip=None, clip_seed=None):
     """-> (plaintext, clipped) of one client"""
-    noisy = _noise_args(noise_seed, noise_k)
-    if quant_seed is None and not noisy:
+    noisy, clipping = _noise_args(noise_seed, noise_k), _clip_args(l2_clip, clip_seed)
+    if quant_seed is None and not noisy and not clipping:
         return x, range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
     q = x if quant_seed is None else range_proof_vec.quantize_probabilistic(x, prove_range, quant_seed, fp=fp).reshape(x.shape)
+    if clipping:
+        q = l2_range_proof_vec.clip_l2(q, prove_range, l2_clip, clip_seed, fp=fp).reshape(x.shape)
     if noisy:
         q = range_proof_vec.add_binomial_noise(q, prove_range, noise_seed, noise_k, fp=fp).reshape(x.shape)
     return q, q
 
 
-def _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds=None, noise_k=None):
-    """-> (plaintexts, clipped) of the clients of encrypt_batch: ONE quantize call for all clients that have a quant seed, then ONE noise
-    call for all clients that have a noise seed"""
-    if _noise_args(noise_seeds, noise_k):
-        noise_seeds = list(noise_seeds)
+def _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds=None, noise_k=None, l2_clip=None, clip_seeds=None):
+    """-> (plaintexts, clipped) of the clients of encrypt_batch: ONE quantize call for all clients that have a quant seed, then ONE clip
+    call for all clients where there is an l2_clip, then ONE noise call for all clients that have a noise seed"""
+    noisy, clipping = _noise_args(noise_seeds, noise_k), _clip_args(l2_clip, clip_seeds)
+    if noisy or clipping:
+        noise_seeds = list(noise_seeds) if noisy else [None] * len(xs)
         if len(noise_seeds) != len(xs):
             raise ValueError("one noise seed (or None) per client")
         if any(x.size != xs[0].size for x in xs):
             raise ValueError("the clients of a batch have one vector length")
         xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)
         xs, clipped = list(xs), list(clipped)
+        if clipping and xs:
+            # (the input is the rounded vector where there is one, else the raw one: the clip call clips and rounds to nearest itself)
+            q = l2_range_proof_vec.clip_l2_vecs(xs, prove_range, l2_clip, clip_seeds, fp=fp)
+            for i in range(len(xs)):
+                xs[i] = clipped[i] = q[i].reshape(xs[i].shape)
         with_seed = [i for i, s in enumerate(noise_seeds) if s is not None]
         if with_seed:
             # (the input is the rounded vector where there is one, else the raw one: the noise call clips and rounds to nearest itself)
@@ -570,13 +591,14 @@ class EncParamsL2:
         self.prove_range, self.l2_prove_range = int(prove_range), int(l2_prove_range)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None, noise_seed=None, noise_k=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None, noise_seed=None, noise_k=None,
+                l2_clip=None, clip_seed=None):
         # r2: rand_scalars, or the blinding stream of rand_seed (pedersen_ops.rnd_scalar_vec_seeded, on the GPU), or fresh host randomness
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
         r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
-        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed, noise_k)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed, noise_k, l2_clip, clip_seed)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
         # the square proofs take the range proof's commitments (params.rs:623-637); committing first (same points) lets the
         # three proofs run side by side
@@ -611,7 +633,18 @@ class EncParamsL2:
         return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds, noise_k)
 
     @classmethod
-    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds=None, noise_k=None):
+    def encrypt_batch_clipped(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None, quant_seeds=None, noise_seeds=None, noise_k=None, l2_clip=None, clip_seeds=None):
+        """encrypt_batch_private with norm clipping: l2_clip = the budget in grid steps^2 (an int, or one per client;
+        l2_range_proof_vec.norm_budget) and clip_seeds = None or one 32-byte seed (or None: truncate) per client.  Between the ONE
+        rofl_quantize_prob call and the ONE rofl_noise_binomial call, ONE rofl_clip_l2 call projects the updates of all hosted clients
+        onto the ball, so that none of them fails the norm check of its sum proof.  Byte-identical to encrypt(..., l2_clip=, clip_seed=)
+        per client, and with l2_clip=None to encrypt_batch_private.  (A method of its own: the parameter lists of the other
+        encrypt_batch* methods are pinned.)"""
+        _noise_args(noise_seeds, noise_k); _clip_args(l2_clip, clip_seeds)
+        return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds, noise_k, l2_clip, clip_seeds)
+
+    @classmethod
+    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds=None, noise_k=None, l2_clip=None, clip_seeds=None):
         """encrypt() for several clients of one process (rofl_service's client binary hosts its clients as tasks of one process,
         client.rs:265-266): clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one length.  The L-inf legs of all of
         them are ONE rofl_create_rangeproof_batch call (one launch sequence, one set of host hops), their sum proofs ONE
@@ -629,7 +662,7 @@ class EncParamsL2:
             x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
             r2 = pedersen_ops.rnd_scalar_vec(x.size) if r2 is None else api._u8(r2)
             xs.append(x); bls.append(bl); r2s.append(r2)
-        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds, noise_k)      # (ONE quantize and ONE noise call for all hosted clients)
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds, noise_k, l2_clip, clip_seeds)      # (ONE quantize, ONE clip and ONE noise call for all hosted clients)
         d = xs[0].size
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")
@@ -761,12 +794,13 @@ class EncParamsL2Compressed(EncParamsL2):
         self.prove_range, self.l2_prove_range = int(prove_range), int(l2_prove_range)
 
     @classmethod
-    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None, noise_seed=None, noise_k=None):
+    def encrypt(cls, plaintext_vec, blinding_vec, prove_range, n_partition, l2_range, nonce_seed=None, rand_scalars=None, fp=None, rand_seed=None, quant_seed=None, noise_seed=None, noise_k=None,
+                l2_clip=None, clip_seed=None):
         fp = api._fp(fp)
         x = np.ascontiguousarray(plaintext_vec, dtype=np.float32)
         bl = api._u8(blinding_vec)
         r2 = _rand_scalars(x.size, rand_scalars, rand_seed)
-        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed, noise_k)
+        x, clipped = _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed, noise_k, l2_clip, clip_seed)
         wd = witness_digest(x, bl, r2) if nonce_seed is not None else b""
         enc_com = _range_commitments(clipped, bl, prove_range, fp)
         (rp, rp_com), (sum_proof, _), (rand_proof, pairs) = _concurrently(
@@ -801,7 +835,18 @@ class EncParamsL2Compressed(EncParamsL2):
         return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds, noise_k)
 
     @classmethod
-    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds=None, noise_k=None):
+    def encrypt_batch_clipped(cls, clients, prove_range, n_partition, l2_range, nonce_seeds=None, fp=None, quant_seeds=None, noise_seeds=None, noise_k=None, l2_clip=None, clip_seeds=None):
+        """encrypt_batch_private with norm clipping: l2_clip = the budget in grid steps^2 (an int, or one per client;
+        l2_range_proof_vec.norm_budget) and clip_seeds = None or one 32-byte seed (or None: truncate) per client.  Between the ONE
+        rofl_quantize_prob call and the ONE rofl_noise_binomial call, ONE rofl_clip_l2 call projects the updates of all hosted clients
+        onto the ball, so that none of them fails the norm check of its sum proof.  Byte-identical to encrypt(..., l2_clip=, clip_seed=)
+        per client, and with l2_clip=None to encrypt_batch_private.  (A method of its own: the parameter lists of the other
+        encrypt_batch* methods are pinned.)"""
+        _noise_args(noise_seeds, noise_k); _clip_args(l2_clip, clip_seeds)
+        return cls._encrypt_batch(clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds, noise_k, l2_clip, clip_seeds)
+
+    @classmethod
+    def _encrypt_batch(cls, clients, prove_range, n_partition, l2_range, nonce_seeds, fp, quant_seeds, noise_seeds=None, noise_k=None, l2_clip=None, clip_seeds=None):
         """encrypt() for several clients of one process: clients = [(plaintext_vec, blinding_vec, rand_scalars or None), ...] of one
         length.  The 8-bit legs of all of them are ONE rofl_create_rangeproof_batch call, their compressed randomness proofs ONE
         rofl_create_compressed_randproof_batch over the range proofs' commitments, their sum proofs ONE rofl_create_rangeproof_l2_batch and
@@ -817,7 +862,7 @@ class EncParamsL2Compressed(EncParamsL2):
             x = np.ascontiguousarray(x, dtype=np.float32); bl = api._u8(bl)
             r2 = pedersen_ops.rnd_scalar_vec(x.size) if r2 is None else api._u8(r2)
             xs.append(x); bls.append(bl); r2s.append(r2)
-        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds, noise_k)      # (ONE quantize and ONE noise call for all hosted clients)
+        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds, noise_k, l2_clip, clip_seeds)      # (ONE quantize, ONE clip and ONE noise call for all hosted clients)
         d = xs[0].size
         if any(x.size != d for x in xs):
             raise ValueError("the clients of a batch have one vector length")

@@ -744,6 +744,7 @@ LaneLock acquire_lane(bool primary_only = false, bool side = false) {
 }
 
 inline dim3 grid1(size_t n, u32 y = 1) { return dim3((unsigned)((n + TPB - 1) / TPB), y, 1); }
+inline dim3 per_item(size_t n) { return dim3((unsigned)((n + 63) / 64)); }      // one thread per item in blocks of one wave (launched with dim3(64))
 unsigned lg2u(size_t x) { unsigned r = 0; while (((size_t)1 << r) < x) r++; return r; }
 bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 size_t next_pow2(size_t val) { if (val == 1) return 1; size_t n = val - 1; while ((n & (n - 1)) != 0) n &= n - 1; return n << 1; }

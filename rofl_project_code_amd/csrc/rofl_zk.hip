@@ -27,6 +27,7 @@
 #include <functional>
 #include <mutex>
 #include <shared_mutex>
+#include <stdexcept>
 #include <thread>
 #include <string>
 #include <vector>
@@ -2618,1068 +2619,33 @@ int rofl_clip_l2(size_t n_vec, const uint8_t *seeds32, const float *const *value
                  unsigned fp_frac, float *const *out, uint64_t *scale_out) {
     return clip_l2_impl(-1, n_vec, seeds32, values, d, max_sq, prove_range, fp_bits, fp_frac, out, scale_out);
 }
-// ---- key agreement: where the pairwise masks' shared secrets come from (k_dh_public, k_dh_decode, k_dh_shared) ----
-}  // extern "C"
-namespace {
-// a secret key as the kernels read it (load_sc_reduced): 32 little-endian bytes reduced mod l
-sc dh_key_scalar(const uint8_t *sk32) { sc r = sc_frombytes(sk32); if (sc_geq_l(r.v)) r = sc_from_mont(sc_to_mont(r)); return r; }
-void dh_wipe(void *p, size_t n) { volatile uint8_t *q = (volatile uint8_t *)p; for (size_t i = 0; i < n; i++) q[i] = 0; }
-// own keys that are 0 mod l are refused before the device is touched; the text names the index, never the bytes
-int dh_check_keys(size_t n, const uint8_t *sk32) {
-    for (size_t i = 0; i < n; i++) {
-        sc k = dh_key_scalar(sk32 + 32 * i); const bool zero = sc_iszero(k); dh_wipe(&k, sizeof k);
-        if (zero) { char buf[96]; snprintf(buf, sizeof buf, "secret key %zu is zero mod l", i); return fail(ROFL_BAD_PARAM, buf); }
-    }
-    return ROFL_OK;
-}
-// k P on the host's 51-bit arithmetic, signed radix-16 windows like sg_var_mul (k canonical)
-h51::ge5 dh_host_mul(const sc &k, const h51::ge5 &P) {
-    h51::ge5 tab[8]; tab[0] = P;
-    for (int e = 1; e < 8; e++) tab[e] = h51::gadd(tab[e - 1], P);
-    int8_t dg[65]; int carry = 0;
-    for (int i = 0; i < 64; i++) { int v = (int)((k.v[i >> 3] >> ((i & 7) * 4)) & 15) + carry; carry = (v + 8) >> 4; dg[i] = (int8_t)(v - (carry << 4)); }
-    dg[64] = (int8_t)carry;
-    h51::ge5 acc = h51::identity();
-    for (int i = 64; i >= 0; i--) {
-        if (i != 64) for (int q = 0; q < 4; q++) acc = h51::gdouble(acc);
-        const int d = dg[i], ad = d < 0 ? -d : d;
-        if (ad) { h51::ge5 q = tab[ad - 1]; if (d < 0) { q.X = h51::neg(q.X); q.T = h51::neg(q.T); } acc = h51::gadd(acc, q); }
-    }
-    dh_wipe(dg, sizeof dg);
-    return acc;
-}
-// the shared secret of rofl_dh_shared from S = encode(a decode(P_b)) and the two public keys, in either order
-void dh_host_secret(uint8_t out32[32], const uint8_t S[32], const uint8_t own[32], const uint8_t peer[32]) {
-    uint8_t m[112] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 'd', 'h', '/', 'v', '1', 0, 0, 0};
-    memcpy(m + 16, S, 32);
-    const bool own_first = memcmp(own, peer, 32) <= 0;
-    memcpy(m + 48, own_first ? own : peer, 32); memcpy(m + 80, own_first ? peer : own, 32);
-    u64 st[25]; memset(st, 0, sizeof st); memcpy(st, m, 112);
-    st[14] ^= 0x1FULL; st[16] ^= 0x8000000000000000ULL;
-    keccak_f1600_host(st);
-    memcpy(out32, st, 32);
-    dh_wipe(m, sizeof m); dh_wipe(st, sizeof st);
-}
-const uint8_t kDhBase[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
-                             0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};
-}  // namespace
-extern "C" {
-int rofl_dh_public_keys(size_t n, const uint8_t *sk32, uint8_t *pk_out32) {
-    if (n == 0) return ROFL_OK;
-    if (!sk32 || !pk_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
-    if (int rc = dh_check_keys(n, sk32)) return rc;
+#include "protocol_calls.hpp"
+// what the calls above left in the lanes' staging buffers (described in the debug header): reads only; every device buffer is copied whole
+int rofl_dbg_lane_scan(const uint8_t *needle, size_t n, int *found) {
+    if (!needle || !found || n < 16) return fail(ROFL_BAD_PARAM, "bad parameter");
+    *found = 0;
     return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        uint8_t *h = C.h_misc.as<uint8_t>(n * 64), *dv = C.tmp_in.as<uint8_t>(n * 64);      // [secret keys | public keys]
-        BlindWipe wipe; wipe.h = h; wipe.dv = dv; wipe.n = n * 32; wipe.s = C.stream;
-        memcpy(h, sk32, n * 32);
-        HIPCHK(hipMemcpyAsync(dv, h, n * 32, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_dh_public, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, reinterpret_cast<const sc *>(dv), C.d_tabB8, dv + n * 32);
-        HIPCHK(hipMemcpyAsync(h + n * 32, dv + n * 32, n * 32, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(pk_out32, h + n * 32, n * 32);
-        return ROFL_OK;
-    });
-}
-// The lane's copies of the secret keys and of the shared secrets -- pinned staging and device workspace -- are overwritten with zeros before the
-// call returns or unwinds (the product encodings never leave the threads' registers and scratch).
-int rofl_dh_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32,
-                   size_t n_pairs, const rofl_dh_pair_t *pairs, uint8_t *out32, uint8_t *status_out) {
-    if (n_pairs == 0) return ROFL_OK;
-    if (!sk32 || !peer_pk32 || !out32 || !status_out) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_own == 0 || n_peer == 0) return fail(ROFL_BAD_PARAM, "pairs without keys");
-    if (n_own > ((size_t)1 << 20) || n_peer > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
-    if (n_pairs > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 pairs in one call");
-    if (!pairs && n_pairs != n_own * n_peer) return fail(ROFL_BAD_PARAM, "without a pair list n_pairs is n_own x n_peer");
-    if (pairs) for (size_t i = 0; i < n_pairs; i++)
-        if (pairs[i].own >= n_own || pairs[i].peer >= n_peer) { char buf[96]; snprintf(buf, sizeof buf, "pair %zu names a key that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
-    if (int rc = dh_check_keys(n_own, sk32)) return rc;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: [secret keys | peer keys | pair list]; download: [shared secrets | own public keys | status bytes]
-        const size_t up_pairs = (n_own + n_peer) * 32, up_bytes = up_pairs + (pairs ? n_pairs * sizeof(rofl_dh_pair_t) : 0);
-        const size_t dn_pk = n_pairs * 32, dn_st = dn_pk + n_own * 32, dn_bytes = dn_st + n_pairs;
-        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        ge *pts = C.aux_pts.as<ge>(n_peer); u32 *pst = C.status.as<u32>(n_peer);
-        BlindWipe wipe_keys, wipe_out;
-        wipe_keys.h = hu; wipe_keys.dv = du; wipe_keys.n = n_own * 32; wipe_keys.s = C.stream;
-        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = n_pairs * 32; wipe_out.s = C.stream;
-        memcpy(hu, sk32, n_own * 32); memcpy(hu + n_own * 32, peer_pk32, n_peer * 32);
-        if (pairs) memcpy(hu + up_pairs, pairs, n_pairs * sizeof(rofl_dh_pair_t));
-        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_dh_public, dim3((unsigned)((n_own + 63) / 64)), dim3(64), 0, C.stream, (u32)n_own, reinterpret_cast<const sc *>(du), C.d_tabB8, dd + dn_pk);
-        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_peer + 63) / 64)), dim3(64), 0, C.stream, (u32)n_peer, (const uint8_t *)(du + n_own * 32), pts, pst);
-        ROFL_LAUNCH(k_dh_shared, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_pairs, (u32)n_peer,
-                    pairs ? reinterpret_cast<const uint2 *>(du + up_pairs) : (const uint2 *)nullptr, reinterpret_cast<const sc *>(du), (const uint8_t *)(dd + dn_pk),
-                    (const uint8_t *)(du + n_own * 32), (const ge *)pts, (const u32 *)pst, dd, dd + dn_st);
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(out32, hd, n_pairs * 32); memcpy(status_out, hd + dn_st, n_pairs);
-        if (own_pk_out32) memcpy(own_pk_out32, hd + dn_pk, n_own * 32);
-        return ROFL_OK;
-    });
-}
-// one pair of rofl_dh_shared from the host arithmetic (no GPU): status 0 / 1 / 2 as there, 11 for a zero own key
-int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status) {
-    if (!sk32 || !peer_pk32 || !out32 || !status) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (int rc = dh_check_keys(1, sk32)) return rc;
-    memset(out32, 0, 32);
-    ge P;
-    if (!ristretto_decode(P, peer_pk32)) { *status = 1; return ROFL_OK; }
-    if (ge_is_identity_ristretto(P)) { *status = 2; return ROFL_OK; }
-    *status = 0;
-    sc k = dh_key_scalar(sk32);
-    uint8_t own[32], S[32];
-    if (own_pk32) memcpy(own, own_pk32, 32);
-    else { ge B; ristretto_decode(B, kDhBase); h51::encode(own, dh_host_mul(k, h51::from_ge(B))); }
-    h51::encode(S, dh_host_mul(k, h51::from_ge(P)));
-    dh_host_secret(out32, S, own, peer_pk32);
-    dh_wipe(&k, sizeof k); dh_wipe(S, sizeof S);
-    return ROFL_OK;
-}
-// ---- secret sharing: Shamir shares of mask secrets over the scalar field (k_shamir_coeffs, k_shamir_eval, k_shamir_weights, k_shamir_combine) ----
-}  // extern "C"
-namespace {
-// the evaluation points of a call: nonzero and distinct; the text names positions, never values of anything secret
-int shamir_check_xs(size_t n, const uint32_t *xs) {
-    std::vector<std::pair<uint32_t, uint32_t>> v(n);
-    for (size_t i = 0; i < n; i++) {
-        if (xs[i] == 0) { char buf[96]; snprintf(buf, sizeof buf, "evaluation point %zu is zero", i); return fail(ROFL_BAD_PARAM, buf); }
-        v[i] = {xs[i], (uint32_t)i};
-    }
-    std::sort(v.begin(), v.end());
-    for (size_t i = 1; i < n; i++)
-        if (v[i].first == v[i - 1].first) { char buf[96]; snprintf(buf, sizeof buf, "evaluation points %u and %u are equal", v[i - 1].second, v[i].second); return fail(ROFL_BAD_PARAM, buf); }
-    return ROFL_OK;
-}
-// every check of rofl_shamir_share, shared with its host route; *done: the call is empty and returns 0
-int shamir_share_check(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares, const uint32_t *xs,
-                       const uint8_t *shares_out32, bool *done) {
-    *done = n_secrets == 0;
-    if (*done) return ROFL_OK;
-    if (!secrets32 || !coef_seeds32 || !shares_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_shares == 0) return fail(ROFL_BAD_PARAM, "secrets without shares");
-    if (threshold == 0 || threshold > n_shares) return fail(ROFL_BAD_PARAM, "the threshold is in [1, n_shares]");
-    if (threshold > 65536) return fail(ROFL_BAD_PARAM, "a threshold above 65536");
-    if (n_secrets > 65535) return fail(ROFL_BAD_PARAM, "more than 65535 secrets in one call");
-    if (n_shares > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 shares of a secret in one call");
-    if (n_secrets * n_shares > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 shares in one call");
-    if (n_secrets * (threshold - 1) > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 coefficients in one call");
-    return xs ? shamir_check_xs(n_shares, xs) : ROFL_OK;
-}
-int shamir_reconstruct_check(size_t n_secrets, size_t n_shares, const uint32_t *xs, const uint8_t *shares32, const uint8_t *secrets_out32, bool *done) {
-    *done = n_secrets == 0;
-    if (*done) return ROFL_OK;
-    if (!xs || !shares32 || !secrets_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_shares == 0) return fail(ROFL_BAD_PARAM, "secrets without shares");
-    if (n_secrets > 65535) return fail(ROFL_BAD_PARAM, "more than 65535 secrets in one call");
-    if (n_shares > 65536) return fail(ROFL_BAD_PARAM, "more than 65536 shares of a secret in one call");
-    if (n_secrets * n_shares > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 shares in one call");
-    return shamir_check_xs(n_shares, xs);
-}
-}  // namespace
-extern "C" {
-// The lane's copies of the secrets, the coefficient seeds, the coefficients and the shares -- pinned staging and device workspace -- are
-// overwritten with zeros before the call returns or unwinds.
-int rofl_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares, const uint32_t *xs,
-                      uint8_t *shares_out32) {
-    bool done;
-    if (int rc = shamir_share_check(n_secrets, secrets32, coef_seeds32, threshold, n_shares, xs, shares_out32, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: [secrets | coefficient seeds | points]; workspace: the coefficients; download: the shares, secret-major
-        const size_t m = threshold - 1, up_xs = n_secrets * 64, up_bytes = up_xs + (xs ? n_shares * 4 : 0), dn_bytes = n_secrets * n_shares * 32;
-        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        sc *coef = C.tmp_in2.as<sc>(std::max<size_t>(n_secrets * m, 1));
-        BlindWipe wipe_in, wipe_coef, wipe_out;
-        wipe_in.h = hu; wipe_in.dv = du; wipe_in.n = up_xs; wipe_in.s = C.stream;
-        wipe_coef.dv = reinterpret_cast<uint8_t *>(coef); wipe_coef.n = n_secrets * m * 32; wipe_coef.s = C.stream;
-        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = dn_bytes; wipe_out.s = C.stream;
-        memcpy(hu, secrets32, n_secrets * 32); memcpy(hu + n_secrets * 32, coef_seeds32, n_secrets * 32);
-        if (xs) memcpy(hu + up_xs, xs, n_shares * 4);
-        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
-        if (m) ROFL_LAUNCH(k_shamir_coeffs, grid1((m + 1) / 2, (u32)n_secrets), dim3(TPB), 0, C.stream, (u32)m, reinterpret_cast<const u64 *>(du + n_secrets * 32), coef);
-        ROFL_LAUNCH(k_shamir_eval, grid1(n_shares, (u32)n_secrets), dim3(TPB), 0, C.stream, (u32)m, (u32)n_shares, reinterpret_cast<const sc *>(du), (const sc *)coef,
-                    xs ? reinterpret_cast<const u32 *>(du + up_xs) : (const u32 *)nullptr, reinterpret_cast<sc *>(dd));
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(shares_out32, hd, dn_bytes);
-        return ROFL_OK;
-    });
-}
-int rofl_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *xs, const uint8_t *shares32, uint8_t *secrets_out32) {
-    bool done;
-    if (int rc = shamir_reconstruct_check(n_secrets, n_shares, xs, shares32, secrets_out32, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: [shares, secret-major | points]; workspace: the weights (a function of the points alone); download: the secrets
-        const size_t up_xs = n_secrets * n_shares * 32, up_bytes = up_xs + n_shares * 4, dn_bytes = n_secrets * 32;
-        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        sc *w = C.tmp_in2.as<sc>(n_shares);
-        BlindWipe wipe_in, wipe_out;
-        wipe_in.h = hu; wipe_in.dv = du; wipe_in.n = up_xs; wipe_in.s = C.stream;
-        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = dn_bytes; wipe_out.s = C.stream;
-        memcpy(hu, shares32, up_xs); memcpy(hu + up_xs, xs, n_shares * 4);
-        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_shamir_weights, grid1(n_shares), dim3(TPB), 0, C.stream, (u32)n_shares, reinterpret_cast<const u32 *>(du + up_xs), w);
-        ROFL_LAUNCH(k_shamir_combine, dim3((unsigned)n_secrets), dim3(TPB), 0, C.stream, (u32)n_shares, (const sc *)w, reinterpret_cast<const sc *>(du), reinterpret_cast<sc *>(dd));
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(secrets_out32, hd, dn_bytes);
-        return ROFL_OK;
-    });
-}
-// the two calls on the host's scalar arithmetic and host Keccak, one thread, no GPU: same parameters, same checks, same bytes
-int rofl_dbg_host_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares, const uint32_t *xs,
-                               uint8_t *shares_out32) {
-    bool done;
-    if (int rc = shamir_share_check(n_secrets, secrets32, coef_seeds32, threshold, n_shares, xs, shares_out32, &done)) return rc;
-    if (done) return ROFL_OK;
-    const size_t m = threshold - 1;
-    const u64 dom[2] = ROFL_SHARE_DOM;
-    std::vector<sc> coef(m + 1);
-    for (size_t s = 0; s < n_secrets; s++) {
-        u64 sd[4], st[25]; memcpy(sd, coef_seeds32 + 32 * s, 32);
-        for (size_t blk = 0; 2 * blk < m; blk++) {
-            shake256_seeded_block(st, dom, sd, blk);
-            coef[2 * blk] = xof_block_scalar(st, 0); coef[2 * blk + 1] = xof_block_scalar(st, 1);      // (coef has room for one past m)
-        }
-        sc sec = dh_key_scalar(secrets32 + 32 * s);
-        for (size_t i = 0; i < n_shares; i++) {
-            const sc xR = sc_to_mont(sc_from_u64(xs ? xs[i] : (u64)i + 1));
-            sc acc = sc_zero();
-            for (size_t k = m; k-- > 0;) acc = sc_add(sc_montmul(acc, xR), coef[k]);
-            acc = sc_add(sc_montmul(acc, xR), sec);
-            sc_tobytes(shares_out32 + (s * n_shares + i) * 32, acc);
-            dh_wipe(&acc, sizeof acc);
-        }
-        dh_wipe(&sec, sizeof sec); dh_wipe(sd, sizeof sd); dh_wipe(st, sizeof st);
-    }
-    dh_wipe(coef.data(), coef.size() * sizeof(sc));
-    return ROFL_OK;
-}
-int rofl_dbg_host_shamir_reconstruct(size_t n_secrets, size_t n_shares, const uint32_t *xs, const uint8_t *shares32, uint8_t *secrets_out32) {
-    bool done;
-    if (int rc = shamir_reconstruct_check(n_secrets, n_shares, xs, shares32, secrets_out32, &done)) return rc;
-    if (done) return ROFL_OK;
-    std::vector<sc> w(n_shares);      // lambda_j in Montgomery form; N and D carry the same power of R (k_shamir_weights)
-    for (size_t j = 0; j < n_shares; j++) {
-        sc N = sc_one_plain(), D = sc_one_plain();
-        for (size_t k = 0; k < n_shares; k++) {
-            if (k == j) continue;
-            const u32 xm = xs[k], xj = xs[j];
-            sc fd = sc_from_u64(xm > xj ? xm - xj : xj - xm); if (xm < xj) fd = sc_neg(fd);
-            N = sc_montmul(N, sc_from_u64(xm)); D = sc_montmul(D, fd);
-        }
-        w[j] = sc_montmul(N, h51::sc_invert_mont_fast(D));
-    }
-    for (size_t s = 0; s < n_secrets; s++) {
-        sc acc = sc_zero();
-        for (size_t j = 0; j < n_shares; j++) acc = sc_add(acc, sc_montmul(w[j], dh_key_scalar(shares32 + (s * n_shares + j) * 32)));
-        sc_tobytes(secrets_out32 + 32 * s, acc);
-        dh_wipe(&acc, sizeof acc);
-    }
-    return ROFL_OK;
-}
-// ---- verifiable sharing: Feldman commitments to the polynomials above, one exact equation per share (k_feldman_commit, k_dh_decode, k_feldman_check) ----
-}  // extern "C"
-namespace {
-// every check of rofl_feldman_commit / rofl_feldman_verify, shared with their host routes; *done: the call is empty and returns 0
-int feldman_commit_check(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, const uint8_t *commitments_out32, bool *done) {
-    *done = n_secrets == 0;
-    if (*done) return ROFL_OK;
-    if (!secrets32 || !coef_seeds32 || !commitments_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (threshold == 0) return fail(ROFL_BAD_PARAM, "the threshold is at least 1");
-    if (threshold > 65536) return fail(ROFL_BAD_PARAM, "a threshold above 65536");
-    if (n_secrets > 65535) return fail(ROFL_BAD_PARAM, "more than 65535 secrets in one call");
-    if (n_secrets * threshold > ((size_t)1 << 22)) return fail(ROFL_BAD_PARAM, "more than 2^22 commitments in one call");
-    return ROFL_OK;
-}
-int feldman_verify_check(size_t n_secrets, size_t threshold, const uint8_t *commitments32, size_t n_shares, const uint32_t *xs, const uint8_t *shares32,
-                         const uint8_t *verdict_out, bool *done) {
-    *done = n_secrets == 0;
-    if (*done) return ROFL_OK;
-    if (!commitments32 || !shares32 || !verdict_out) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_shares == 0) return fail(ROFL_BAD_PARAM, "secrets without shares");
-    if (threshold == 0) return fail(ROFL_BAD_PARAM, "the threshold is at least 1");
-    if (threshold > 65536) return fail(ROFL_BAD_PARAM, "a threshold above 65536");
-    if (n_secrets > 65535) return fail(ROFL_BAD_PARAM, "more than 65535 secrets in one call");
-    if (n_shares > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 shares of a secret in one call");
-    if (n_secrets * n_shares > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 shares in one call");
-    if (n_secrets * threshold > ((size_t)1 << 22)) return fail(ROFL_BAD_PARAM, "more than 2^22 commitments in one call");
-    return xs ? shamir_check_xs(n_shares, xs) : ROFL_OK;
-}
-// bit length of the largest evaluation point of a call (>= 1: the points are nonzero)
-u32 feldman_xbits(size_t n_shares, const uint32_t *xs) {
-    uint32_t mx = xs ? 0 : (uint32_t)n_shares;
-    for (size_t i = 0; xs && i < n_shares; i++) mx = std::max(mx, xs[i]);
-    u32 b = 0; while (b < 32 && mx >> b) b++;
-    return b;
-}
-}  // namespace
-extern "C" {
-// The lane's copies of the secrets, the coefficient seeds and the coefficients -- pinned staging and device workspace -- are overwritten with
-// zeros before the call returns or unwinds; the commitments are public.
-int rofl_feldman_commit(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, uint8_t *commitments_out32) {
-    bool done;
-    if (int rc = feldman_commit_check(n_secrets, secrets32, coef_seeds32, threshold, commitments_out32, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: [secrets | coefficient seeds]; workspace: the coefficients; download: the commitments, secret-major
-        const size_t m = threshold - 1, up_bytes = n_secrets * 64, n_com = n_secrets * threshold, dn_bytes = n_com * 32;
-        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        sc *coef = C.tmp_in2.as<sc>(std::max<size_t>(n_secrets * m, 1));
-        BlindWipe wipe_in, wipe_coef;
-        wipe_in.h = hu; wipe_in.dv = du; wipe_in.n = up_bytes; wipe_in.s = C.stream;
-        wipe_coef.dv = reinterpret_cast<uint8_t *>(coef); wipe_coef.n = n_secrets * m * 32; wipe_coef.s = C.stream;
-        memcpy(hu, secrets32, n_secrets * 32); memcpy(hu + n_secrets * 32, coef_seeds32, n_secrets * 32);
-        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
-        if (m) ROFL_LAUNCH(k_shamir_coeffs, grid1((m + 1) / 2, (u32)n_secrets), dim3(TPB), 0, C.stream, (u32)m, reinterpret_cast<const u64 *>(du + n_secrets * 32), coef);
-        ROFL_LAUNCH(k_feldman_commit, dim3((unsigned)((n_com + 63) / 64)), dim3(64), 0, C.stream, (u32)n_secrets, (u32)threshold, reinterpret_cast<const sc *>(du), (const sc *)coef,
-                    C.d_tabB8, dd);
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(commitments_out32, hd, dn_bytes);
-        return ROFL_OK;
-    });
-}
-// The lane's copies of the shares are overwritten with zeros before the call returns or unwinds; commitments, points and verdicts are public.
-int rofl_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commitments32, size_t n_shares, const uint32_t *xs, const uint8_t *shares32,
-                        uint8_t *verdict_out) {
-    bool done;
-    if (int rc = feldman_verify_check(n_secrets, threshold, commitments32, n_shares, xs, shares32, verdict_out, &done)) return rc;
-    if (done) return ROFL_OK;
-    const u32 xbits = feldman_xbits(n_shares, xs);
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: [shares, secret-major | commitments, secret-major | points]; workspace: the decoded commitments and their status words;
-        // download: the verdict bytes
-        const size_t n_pairs = n_secrets * n_shares, n_com = n_secrets * threshold, up_com = n_pairs * 32, up_xs = up_com + n_com * 32;
-        const size_t up_bytes = up_xs + (xs ? n_shares * 4 : 0);
-        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(n_pairs), *dd = C.tmp_out.as<uint8_t>(n_pairs);
-        ge *pts = C.aux_pts.as<ge>(n_com); u32 *pst = C.status.as<u32>(n_com);
-        BlindWipe wipe_in;
-        wipe_in.h = hu; wipe_in.dv = du; wipe_in.n = up_com; wipe_in.s = C.stream;
-        memcpy(hu, shares32, up_com); memcpy(hu + up_com, commitments32, n_com * 32);
-        if (xs) memcpy(hu + up_xs, xs, n_shares * 4);
-        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_com + 63) / 64)), dim3(64), 0, C.stream, (u32)n_com, (const uint8_t *)(du + up_com), pts, pst);
-        ROFL_LAUNCH(k_feldman_check, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_secrets, (u32)n_shares, (u32)threshold, xbits,
-                    xs ? reinterpret_cast<const u32 *>(du + up_xs) : (const u32 *)nullptr, (const ge *)pts, (const u32 *)pst, reinterpret_cast<const sc *>(du), C.d_tabB8, dd);
-        HIPCHK(hipMemcpyAsync(hd, dd, n_pairs, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(verdict_out, hd, n_pairs);
-        return ROFL_OK;
-    });
-}
-// the two calls on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: same parameters, same checks, same bytes
-int rofl_dbg_host_feldman_commit(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, uint8_t *commitments_out32) {
-    bool done;
-    if (int rc = feldman_commit_check(n_secrets, secrets32, coef_seeds32, threshold, commitments_out32, &done)) return rc;
-    if (done) return ROFL_OK;
-    const size_t m = threshold - 1;
-    const u64 dom[2] = ROFL_SHARE_DOM;
-    ge Bg; ristretto_decode(Bg, kDhBase);
-    const h51::ge5 B = h51::from_ge(Bg);
-    std::vector<sc> coef(m + 2);      // [s mod l | a_1 .. a_{t-1}] and room for one past the end
-    for (size_t s = 0; s < n_secrets; s++) {
-        u64 sd[4], st[25]; memcpy(sd, coef_seeds32 + 32 * s, 32);
-        coef[0] = dh_key_scalar(secrets32 + 32 * s);
-        for (size_t blk = 0; 2 * blk < m; blk++) {
-            shake256_seeded_block(st, dom, sd, blk);
-            coef[1 + 2 * blk] = xof_block_scalar(st, 0); coef[2 + 2 * blk] = xof_block_scalar(st, 1);
-        }
-        for (size_t k = 0; k < threshold; k++) h51::encode(commitments_out32 + (s * threshold + k) * 32, dh_host_mul(coef[k], B));
-        dh_wipe(sd, sizeof sd); dh_wipe(st, sizeof st);
-    }
-    dh_wipe(coef.data(), coef.size() * sizeof(sc));
-    return ROFL_OK;
-}
-int rofl_dbg_host_feldman_verify(size_t n_secrets, size_t threshold, const uint8_t *commitments32, size_t n_shares, const uint32_t *xs, const uint8_t *shares32,
-                                 uint8_t *verdict_out) {
-    bool done;
-    if (int rc = feldman_verify_check(n_secrets, threshold, commitments32, n_shares, xs, shares32, verdict_out, &done)) return rc;
-    if (done) return ROFL_OK;
-    ge Bg; ristretto_decode(Bg, kDhBase);
-    const h51::ge5 B = h51::from_ge(Bg);
-    std::vector<h51::ge5> cp(threshold);
-    for (size_t s = 0; s < n_secrets; s++) {
-        bool refused = false;
-        for (size_t k = 0; k < threshold; k++) {
-            ge P;
-            if (!ristretto_decode(P, commitments32 + (s * threshold + k) * 32)) { refused = true; break; }
-            cp[k] = h51::from_ge(P);
-        }
-        uint8_t *vd = verdict_out + s * n_shares;
-        if (refused) { memset(vd, 2, n_shares); continue; }
-        for (size_t i = 0; i < n_shares; i++) {
-            const u32 x = xs ? xs[i] : (u32)(i + 1);
-            h51::ge5 acc = cp[threshold - 1];
-            for (size_t k = threshold - 1; k-- > 0;) {      // acc = [x] acc + C_k, MSB-first over the bits of x
-                h51::ge5 r = h51::identity();
-                for (int b = 32; b-- > 0;) {
-                    if (x >> b >> 1) r = h51::gdouble(r);      // (nothing to double above the top bit)
-                    if ((x >> b) & 1u) r = h51::gadd(r, acc);
-                }
-                acc = h51::gadd(r, cp[k]);
+        Ctx *P = nullptr;
+        { std::lock_guard<std::mutex> lk(g_ctx_mu); auto it = g_ctxs.find(current_device()); if (it != g_ctxs.end()) P = it->second; }
+        if (!P) return ROFL_OK;
+        std::vector<Ctx *> lanes;
+        { std::lock_guard<std::mutex> g(P->init_mu); if (P->inited) { lanes.push_back(P); lanes.insert(lanes.end(), P->sibs.begin(), P->sibs.end()); } }
+        std::vector<uint8_t> copy;
+        const auto holds = [&](const uint8_t *p, size_t cap) { return p && std::search(p, p + cap, needle, needle + n) != p + cap; };
+        for (Ctx *c : lanes) {
+            std::lock_guard<std::mutex> lk(c->mu);
+            HIPCHK(hipSetDevice(P->phys));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            for (const PinBuf *b : {&c->h_misc, &c->h_misc2}) *found += holds((const uint8_t *)b->p, b->cap);
+            for (const DevBuf *b : {&c->tmp_in, &c->tmp_in2, &c->tmp_out}) {
+                if (!b->p) continue;
+                copy.resize(b->cap);
+                HIPCHK(hipMemcpy(copy.data(), b->p, b->cap, hipMemcpyDeviceToHost));
+                *found += holds(copy.data(), b->cap);
             }
-            sc y = dh_key_scalar(shares32 + (s * n_shares + i) * 32);
-            const h51::ge5 P = dh_host_mul(y, B);
-            dh_wipe(&y, sizeof y);
-            const bool same = h51::eq(h51::mul(acc.X, P.Y), h51::mul(acc.Y, P.X)) || h51::eq(h51::mul(acc.Y, P.Y), h51::mul(acc.X, P.X));
-            vd[i] = same ? 0 : 1;
         }
-    }
-    return ROFL_OK;
-}
-// ---- signatures: deterministic Schnorr over Ristretto255 on the commitments and views of a round (k_sig_digest, k_dh_public / k_dh_decode, k_sig_sign / k_sig_verify) ----
-}  // extern "C"
-namespace {
-// every check of rofl_sig_sign / rofl_sig_verify, shared with their host routes; keys32: secret keys (sign) or public keys (verify), sig: the
-// signatures read or written, verdict: verify's output; *done: the call is empty and returns 0.  *total: the messages' bytes
-int sig_check(bool sign, size_t n_keys, const uint8_t *keys32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs,
-              const uint8_t *sig, const uint8_t *verdict, size_t *total, bool *done) {
-    *done = n == 0; *total = 0;
-    if (*done) return ROFL_OK;
-    if (!keys32 || !msg_off || !sig || (!sign && !verdict)) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_keys == 0 || n_msgs == 0) return fail(ROFL_BAD_PARAM, "signatures without keys or without messages");
-    if (n_keys > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
-    if (n_msgs > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 messages in one call");
-    if (n > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 signatures in one call");
-    if (msg_off[0] != 0) return fail(ROFL_BAD_PARAM, "the first message offset is 0");
-    for (size_t j = 0; j < n_msgs; j++) {
-        if (msg_off[j + 1] < msg_off[j]) { char buf[96]; snprintf(buf, sizeof buf, "message offset %zu is below the one before it", j + 1); return fail(ROFL_BAD_PARAM, buf); }
-        if (msg_off[j + 1] > ((uint64_t)1 << 30)) return fail(ROFL_BAD_PARAM, "more than 2^30 message bytes in one call");
-    }
-    *total = (size_t)msg_off[n_msgs];
-    if (*total && !msg_bytes) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (!refs && !(n_keys == n && n_msgs == n)) return fail(ROFL_BAD_PARAM, "without a ref list n_keys, n_msgs and n are equal");
-    if (refs) for (size_t i = 0; i < n; i++)
-        if (refs[i].key >= n_keys || refs[i].msg >= n_msgs) { char buf[96]; snprintf(buf, sizeof buf, "ref %zu names a key or a message that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
-    return sign ? dh_check_keys(n_keys, keys32) : ROFL_OK;
-}
-// h(m) = SHAKE256("rofl-zk/sig/v1/m" || u64le(len) || m)[0 .. 32) on the host's sponge
-void sig_host_digest(uint8_t out[32], const uint8_t *m, uint64_t len) {
-    uint8_t pre[24] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 's', 'i', 'g', '/', 'v', '1', '/', 'm'};
-    memcpy(pre + 16, &len, 8);
-    Sponge sp(136, 0x1F); sp.absorb(pre, 24); if (len) sp.absorb(m, (size_t)len); sp.squeeze(out, 32);
-}
-// int_le(SHAKE256(label || x || y [|| z])[0 .. 64)) mod l for the labels "rofl-zk/sig/v1/k" (which = 'k', two parts) and ".../c" ('c', three)
-sc sig_host_wide(char which, const uint8_t *x, const uint8_t *y, const uint8_t *z) {
-    uint8_t m[112] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 's', 'i', 'g', '/', 'v', '1', '/', (uint8_t)which}, w[64];
-    memcpy(m + 16, x, 32); memcpy(m + 48, y, 32); if (z) memcpy(m + 80, z, 32);
-    Sponge sp(136, 0x1F); sp.absorb(m, z ? 112 : 80); sp.squeeze(w, 64);
-    sc r = sc_from_wide(sc_frombytes(w), sc_frombytes(w + 32));
-    dh_wipe(m, sizeof m); dh_wipe(w, sizeof w); dh_wipe(&sp, sizeof sp);
-    return r;
-}
-// layout of the lane's upload for the two calls: [keys | signatures (verify) | offsets | refs | message bytes], every part 8-byte aligned, the
-// signatures 16; the message bytes are followed by 8 spare bytes (k_sig_digest reads whole aligned words)
-struct SigLayout { size_t sig, off, refs, msg, bytes; };
-SigLayout sig_layout(bool sign, size_t n_keys, size_t n_msgs, size_t n, bool has_refs, size_t total) {
-    SigLayout l;
-    l.sig = n_keys * 32; l.off = l.sig + (sign ? 0 : n * 64); l.refs = l.off + (n_msgs + 1) * 8; l.msg = l.refs + (has_refs ? n * sizeof(rofl_sig_ref_t) : 0);
-    l.bytes = l.msg + ((total + 7) & ~(size_t)7) + 8;
-    return l;
-}
-}  // namespace
-extern "C" {
-// The lane's copies of the secret keys -- pinned staging and device workspace -- are overwritten with zeros before the call returns or
-// unwinds; the nonces never leave their threads' registers; digests, public keys and signatures are public.
-int rofl_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,
-                  size_t n, const rofl_sig_ref_t *refs, uint8_t *sig_out64) {
-    bool done; size_t total;
-    if (int rc = sig_check(true, n_keys, sk32, n_msgs, msg_bytes, msg_off, n, refs, sig_out64, nullptr, &total, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: sig_layout; workspace: the digests; download: [signatures | public keys]
-        const SigLayout l = sig_layout(true, n_keys, n_msgs, n, refs != nullptr, total);
-        const size_t dn_pk = n * 64, dn_bytes = dn_pk + n_keys * 32;
-        uint8_t *hu = C.h_misc.as<uint8_t>(l.bytes), *du = C.tmp_in.as<uint8_t>(l.bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        u64 *dig = C.tmp_in2.as<u64>(n_msgs * 4);
-        BlindWipe wipe_keys;
-        wipe_keys.h = hu; wipe_keys.dv = du; wipe_keys.n = n_keys * 32; wipe_keys.s = C.stream;
-        memcpy(hu, sk32, n_keys * 32); memcpy(hu + l.off, msg_off, (n_msgs + 1) * 8);
-        if (refs) memcpy(hu + l.refs, refs, n * sizeof(rofl_sig_ref_t));
-        if (total) memcpy(hu + l.msg, msg_bytes, total);
-        memset(hu + l.msg + total, 0, l.bytes - l.msg - total);
-        HIPCHK(hipMemcpyAsync(du, hu, l.bytes, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_sig_digest, dim3((unsigned)((n_msgs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_msgs, (const uint8_t *)(du + l.msg), reinterpret_cast<const u64 *>(du + l.off), dig);
-        ROFL_LAUNCH(k_dh_public, dim3((unsigned)((n_keys + 63) / 64)), dim3(64), 0, C.stream, (u32)n_keys, reinterpret_cast<const sc *>(du), C.d_tabB8, dd + dn_pk);
-        ROFL_LAUNCH(k_sig_sign, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, refs ? reinterpret_cast<const uint2 *>(du + l.refs) : (const uint2 *)nullptr,
-                    reinterpret_cast<const sc *>(du), (const uint8_t *)(dd + dn_pk), (const u64 *)dig, C.d_tabB8, dd);
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(sig_out64, hd, n * 64);
-        if (pk_out32) memcpy(pk_out32, hd + dn_pk, n_keys * 32);
         return ROFL_OK;
     });
-}
-// nothing here is secret: public keys, messages, signatures, verdicts
-int rofl_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs,
-                    const uint8_t *sig64, uint8_t *verdict_out) {
-    bool done; size_t total;
-    if (int rc = sig_check(false, n_keys, pk32, n_msgs, msg_bytes, msg_off, n, refs, sig64, verdict_out, &total, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: sig_layout; workspace: the digests, the decoded keys and their status words; download: the verdict bytes
-        const SigLayout l = sig_layout(false, n_keys, n_msgs, n, refs != nullptr, total);
-        uint8_t *hu = C.h_misc.as<uint8_t>(l.bytes), *du = C.tmp_in.as<uint8_t>(l.bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(n), *dd = C.tmp_out.as<uint8_t>(n);
-        u64 *dig = C.tmp_in2.as<u64>(n_msgs * 4);
-        ge *pts = C.aux_pts.as<ge>(n_keys); u32 *pst = C.status.as<u32>(n_keys);
-        memcpy(hu, pk32, n_keys * 32); memcpy(hu + l.sig, sig64, n * 64); memcpy(hu + l.off, msg_off, (n_msgs + 1) * 8);
-        if (refs) memcpy(hu + l.refs, refs, n * sizeof(rofl_sig_ref_t));
-        if (total) memcpy(hu + l.msg, msg_bytes, total);
-        memset(hu + l.msg + total, 0, l.bytes - l.msg - total);
-        HIPCHK(hipMemcpyAsync(du, hu, l.bytes, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_sig_digest, dim3((unsigned)((n_msgs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_msgs, (const uint8_t *)(du + l.msg), reinterpret_cast<const u64 *>(du + l.off), dig);
-        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_keys + 63) / 64)), dim3(64), 0, C.stream, (u32)n_keys, (const uint8_t *)du, pts, pst);
-        ROFL_LAUNCH(k_sig_verify, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, refs ? reinterpret_cast<const uint2 *>(du + l.refs) : (const uint2 *)nullptr,
-                    (const uint8_t *)du, (const ge *)pts, (const u32 *)pst, (const u64 *)dig, (const uint8_t *)(du + l.sig), C.d_tabB8, dd);
-        HIPCHK(hipMemcpyAsync(hd, dd, n, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(verdict_out, hd, n);
-        return ROFL_OK;
-    });
-}
-// the two calls on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: same parameters, same checks, same bytes
-int rofl_dbg_host_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,
-                           size_t n, const rofl_sig_ref_t *refs, uint8_t *sig_out64) {
-    bool done; size_t total;
-    if (int rc = sig_check(true, n_keys, sk32, n_msgs, msg_bytes, msg_off, n, refs, sig_out64, nullptr, &total, &done)) return rc;
-    if (done) return ROFL_OK;
-    ge Bg; ristretto_decode(Bg, kDhBase);
-    const h51::ge5 B = h51::from_ge(Bg);
-    std::vector<uint8_t> dig(n_msgs * 32), pk(n_keys * 32), can(n_keys * 32);
-    std::vector<sc> keys(n_keys);
-    for (size_t j = 0; j < n_msgs; j++) sig_host_digest(dig.data() + 32 * j, msg_bytes + msg_off[j], msg_off[j + 1] - msg_off[j]);
-    for (size_t a = 0; a < n_keys; a++) {
-        keys[a] = dh_key_scalar(sk32 + 32 * a);
-        sc_tobytes(can.data() + 32 * a, keys[a]);
-        h51::encode(pk.data() + 32 * a, dh_host_mul(keys[a], B));
-    }
-    for (size_t i = 0; i < n; i++) {
-        const size_t a = refs ? refs[i].key : i, b = refs ? refs[i].msg : i;
-        uint8_t *o = sig_out64 + 64 * i;
-        sc k = sig_host_wide('k', can.data() + 32 * a, dig.data() + 32 * b, nullptr);
-        h51::encode(o, dh_host_mul(k, B));
-        sc c = sig_host_wide('c', o, pk.data() + 32 * a, dig.data() + 32 * b);
-        sc s = sc_add(k, sc_montmul(sc_to_mont(c), keys[a]));
-        sc_tobytes(o + 32, s);
-        dh_wipe(&k, sizeof k); dh_wipe(&c, sizeof c); dh_wipe(&s, sizeof s);
-    }
-    if (pk_out32) memcpy(pk_out32, pk.data(), n_keys * 32);
-    dh_wipe(keys.data(), keys.size() * sizeof(sc)); dh_wipe(can.data(), can.size());
-    return ROFL_OK;
-}
-int rofl_dbg_host_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs,
-                             const uint8_t *sig64, uint8_t *verdict_out) {
-    bool done; size_t total;
-    if (int rc = sig_check(false, n_keys, pk32, n_msgs, msg_bytes, msg_off, n, refs, sig64, verdict_out, &total, &done)) return rc;
-    if (done) return ROFL_OK;
-    ge Bg; ristretto_decode(Bg, kDhBase);
-    const h51::ge5 B = h51::from_ge(Bg);
-    std::vector<uint8_t> dig(n_msgs * 32), refused(n_keys);
-    std::vector<h51::ge5> kp(n_keys);
-    for (size_t j = 0; j < n_msgs; j++) sig_host_digest(dig.data() + 32 * j, msg_bytes + msg_off[j], msg_off[j + 1] - msg_off[j]);
-    for (size_t a = 0; a < n_keys; a++) {
-        ge P;
-        refused[a] = !ristretto_decode(P, pk32 + 32 * a) || ge_is_identity_ristretto(P);
-        if (!refused[a]) kp[a] = h51::from_ge(P);
-    }
-    for (size_t i = 0; i < n; i++) {
-        const size_t a = refs ? refs[i].key : i, b = refs ? refs[i].msg : i;
-        const uint8_t *sg = sig64 + 64 * i;
-        const sc s = sc_frombytes(sg + 32);
-        if (refused[a] || sc_geq_l(s.v)) { verdict_out[i] = 2; continue; }
-        const sc c = sig_host_wide('c', sg, pk32 + 32 * a, dig.data() + 32 * b);
-        uint8_t enc[32];
-        h51::encode(enc, h51::gadd(dh_host_mul(s, B), dh_host_mul(sc_neg(c), kp[a])));
-        verdict_out[i] = memcmp(enc, sg, 32) == 0 ? 0 : 1;
-    }
-    return ROFL_OK;
-}
-// ---- sealed shares: RFC 8439 ChaCha20-Poly1305 under pairwise keys on the share bundles a server relays (k_aead_derive, k_aead_seal / k_aead_open) ----
-}  // extern "C"
-namespace {
-// one packed byte string of a call: offsets that start at 0 and do not decrease, a total within `max_total`; what: "AD" / "payload" / "record"
-int aead_check_off(const char *what, size_t n, const uint64_t *off, const uint8_t *bytes, uint64_t max_one, uint64_t max_total, size_t *total) {
-    char buf[128];
-    if (off[0] != 0) { snprintf(buf, sizeof buf, "the first %s offset is 0", what); return fail(ROFL_BAD_PARAM, buf); }
-    for (size_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) { snprintf(buf, sizeof buf, "%s offset %zu is below the one before it", what, i + 1); return fail(ROFL_BAD_PARAM, buf); }
-        if (off[i + 1] - off[i] > max_one) { snprintf(buf, sizeof buf, "%s %zu is longer than 2^24 bytes", what, i); return fail(ROFL_BAD_PARAM, buf); }
-        if (off[i + 1] > max_total) { snprintf(buf, sizeof buf, "more than 2^30 %s bytes in one call (at %s %zu)", what, what, i); return fail(ROFL_BAD_PARAM, buf); }
-    }
-    *total = (size_t)off[n];
-    if (*total && !bytes) { snprintf(buf, sizeof buf, "a null pointer: the %s bytes", what); return fail(ROFL_BAD_PARAM, buf); }
-    return ROFL_OK;
-}
-// every check of rofl_aead_seal / rofl_aead_open, shared with their host routes.  data / data_off: the payloads (seal) or the sealed records
-// (open), whose lengths are 16 more; out: what the call writes; *done: the call is empty and returns 0.  Texts name indices, never bytes.
-int aead_check(bool seal, size_t n_keys, const uint8_t *key32, size_t n, const uint32_t *key_idx, const uint8_t *nonce12, const uint8_t *ad_bytes, const uint64_t *ad_off,
-               const uint8_t *data, const uint64_t *data_off, const uint8_t *out, const uint8_t *verdict, size_t *ad_total, size_t *data_total, bool *done) {
-    *done = n == 0; *ad_total = *data_total = 0;
-    if (*done) return ROFL_OK;
-    if (n > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 records in one call");
-    if (n_keys > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 keys in one call");
-    if (n_keys == 0) return fail(ROFL_BAD_PARAM, "records without keys");
-    if (!key32) return fail(ROFL_BAD_PARAM, "a null pointer: the keys");
-    if (!nonce12) return fail(ROFL_BAD_PARAM, "a null pointer: the nonces");
-    if (!ad_off) return fail(ROFL_BAD_PARAM, "a null pointer: the AD offsets");
-    if (!data_off) return fail(ROFL_BAD_PARAM, seal ? "a null pointer: the payload offsets" : "a null pointer: the record offsets");
-    if (!seal && !verdict) return fail(ROFL_BAD_PARAM, "a null pointer: the verdicts");
-    if (!key_idx && n_keys != n) return fail(ROFL_BAD_PARAM, "without a key index list n_keys is n");
-    if (key_idx) for (size_t i = 0; i < n; i++)
-        if (key_idx[i] >= n_keys) { char buf[96]; snprintf(buf, sizeof buf, "record %zu names a key that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
-    const uint64_t tagged = seal ? 0 : 16;      // a sealed record carries its tag
-    if (int rc = aead_check_off("AD", n, ad_off, ad_bytes, ~(uint64_t)0, (uint64_t)1 << 30, ad_total)) return rc;
-    if (int rc = aead_check_off(seal ? "payload" : "record", n, data_off, data, ((uint64_t)1 << 24) + tagged, ((uint64_t)1 << 30) + tagged * n, data_total)) return rc;
-    if (!out && (seal || *data_total)) return fail(ROFL_BAD_PARAM, "a null pointer: the output");
-    return ROFL_OK;
-}
-// the key of a call's row: the row itself, or SHAKE256("rofl-zk/seal/v1\0" || row || u64le(round))[0 .. 32) on the host's sponge
-void aead_host_key(uint32_t key[8], const uint8_t *row, const uint64_t *derive_round) {
-    if (!derive_round) { memcpy(key, row, 32); return; }
-    uint8_t m[56] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 's', 'e', 'a', 'l', '/', 'v', '1', 0};
-    memcpy(m + 16, row, 32); memcpy(m + 48, derive_round, 8);
-    Sponge sp(136, 0x1F); sp.absorb(m, sizeof m); sp.squeeze(reinterpret_cast<uint8_t *>(key), 32);
-    dh_wipe(m, sizeof m); dh_wipe(&sp, sizeof sp);
-}
-// `len` bytes into the authenticator, the last block padded with zeros to sixteen bytes (every block full: the AEAD's framing)
-void aead_host_absorb(poly1305 &P, const uint8_t *p, uint64_t len) {
-    for (uint64_t pos = 0; pos < len; pos += 16) {
-        uint32_t m[4] = {0, 0, 0, 0};
-        memcpy(m, p + pos, (size_t)std::min<uint64_t>(16, len - pos));
-        poly1305_block(P, m, 1);
-    }
-}
-// block 0 -> the authenticator's key; then the tag over AD and CT
-void aead_host_tag(uint32_t tag[4], const uint32_t key[8], const uint32_t nc[3], const uint8_t *ad, uint64_t alen, const uint8_t *ct, uint64_t len) {
-    uint32_t ks[16];
-    chacha20_block(ks, key, 0, nc);
-    poly1305 P; poly1305_init(P, ks);
-    aead_host_absorb(P, ad, alen); aead_host_absorb(P, ct, len);
-    const uint32_t m[4] = {(uint32_t)alen, (uint32_t)(alen >> 32), (uint32_t)len, (uint32_t)(len >> 32)};
-    poly1305_block(P, m, 1);
-    poly1305_finish(tag, P, ks + 4);
-    dh_wipe(ks, sizeof ks); dh_wipe(&P, sizeof P);
-}
-// dst = src ^ ChaCha20 keystream from block 1
-void aead_host_xor(uint8_t *dst, const uint8_t *src, uint64_t len, const uint32_t key[8], const uint32_t nc[3]) {
-    uint32_t ks[16];
-    for (uint64_t b = 0; b < len; b += 64) {
-        chacha20_block(ks, key, 1u + (uint32_t)(b >> 6), nc);
-        const uint8_t *k = reinterpret_cast<const uint8_t *>(ks);
-        for (uint64_t q = 0; q < 64 && b + q < len; q++) dst[b + q] = src[b + q] ^ k[q];
-    }
-    dh_wipe(ks, sizeof ks);
-}
-// layout of the lane's upload for the two calls: [keys | payloads or records | ADs | nonces | AD offsets | data offsets | key indices]; every
-// part 8-byte aligned, each byte string followed by 8 spare bytes (the kernels read whole aligned words)
-struct AeadLayout { size_t data, ad, nonce, ad_off, data_off, idx, bytes; };
-AeadLayout aead_layout(size_t n_keys, size_t n, bool has_idx, size_t ad_total, size_t data_total) {
-    auto pad = [](size_t b) { return ((b + 7) & ~(size_t)7) + 8; };
-    AeadLayout l;
-    l.data = n_keys * 32; l.ad = l.data + pad(data_total); l.nonce = l.ad + pad(ad_total); l.ad_off = l.nonce + ((n * 12 + 7) & ~(size_t)7);
-    l.data_off = l.ad_off + (n + 1) * 8; l.idx = l.data_off + (n + 1) * 8; l.bytes = l.idx + (has_idx ? n * 4 : 0);
-    return l;
-}
-// the upload both calls make, and the key derivation where asked for; `secret`: the leading bytes of the upload that are wiped afterwards
-uint8_t *aead_upload(Ctx &C, BlindWipe &wipe, const AeadLayout &l, size_t secret, size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n,
-                     const uint32_t *key_idx, const uint8_t *nonce12, const uint8_t *ad_bytes, const uint64_t *ad_off, size_t ad_total,
-                     const uint8_t *data, const uint64_t *data_off, size_t data_total) {
-    uint8_t *hu = C.h_misc.as<uint8_t>(l.bytes), *du = C.tmp_in.as<uint8_t>(l.bytes);
-    wipe.h = hu; wipe.dv = du; wipe.n = secret; wipe.s = C.stream;
-    memcpy(hu, key32, n_keys * 32);
-    if (data_total) memcpy(hu + l.data, data, data_total);
-    memset(hu + l.data + data_total, 0, l.ad - l.data - data_total);
-    if (ad_total) memcpy(hu + l.ad, ad_bytes, ad_total);
-    memset(hu + l.ad + ad_total, 0, l.nonce - l.ad - ad_total);
-    memcpy(hu + l.nonce, nonce12, n * 12); memset(hu + l.nonce + n * 12, 0, l.ad_off - l.nonce - n * 12);
-    memcpy(hu + l.ad_off, ad_off, (n + 1) * 8); memcpy(hu + l.data_off, data_off, (n + 1) * 8);
-    if (key_idx) memcpy(hu + l.idx, key_idx, n * 4);
-    HIPCHK(hipMemcpyAsync(du, hu, l.bytes, hipMemcpyHostToDevice, C.stream));
-    if (derive_round) ROFL_LAUNCH(k_aead_derive, dim3((unsigned)((n_keys + 63) / 64)), dim3(64), 0, C.stream, (u32)n_keys, (u64)*derive_round, reinterpret_cast<u64 *>(du));
-    return du;
-}
-// a packed list of messages for the Poly1305 hooks
-int poly_check(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, const uint8_t *tag_out16, size_t *total, bool *done) {
-    *done = n == 0; *total = 0;
-    if (*done) return ROFL_OK;
-    if (!key32 || !msg_off || !tag_out16) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 messages in one call");
-    return aead_check_off("message", n, msg_off, msg_bytes, (uint64_t)1 << 24, (uint64_t)1 << 30, total);
-}
-}  // namespace
-extern "C" {
-// The lane's copies of the keys (as given and derived) and of the plaintexts -- pinned staging and device workspace -- are overwritten with
-// zeros before the call returns or unwinds; keystream and authenticator keys live in registers only.  The sealed records are public.
-int rofl_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
-                   const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes, const uint64_t *pt_off, uint8_t *sealed_out) {
-    bool done; size_t ad_total, pt_total;
-    if (int rc = aead_check(true, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, pt_bytes, pt_off, sealed_out, nullptr, &ad_total, &pt_total, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        const AeadLayout l = aead_layout(n_keys, n, key_idx != nullptr, ad_total, pt_total);
-        const size_t dn_bytes = pt_total + 16 * n;
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        BlindWipe wipe_secrets;
-        const uint8_t *du = aead_upload(C, wipe_secrets, l, l.ad, n_keys, key32, derive_round, n, key_idx, nonce12, ad_bytes, ad_off, ad_total, pt_bytes, pt_off, pt_total);
-        ROFL_LAUNCH(k_aead_seal, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, key_idx ? reinterpret_cast<const u32 *>(du + l.idx) : (const u32 *)nullptr,
-                    reinterpret_cast<const u32 *>(du), reinterpret_cast<const u32 *>(du + l.nonce), du + l.ad, reinterpret_cast<const u64 *>(du + l.ad_off),
-                    du + l.data, reinterpret_cast<const u64 *>(du + l.data_off), dd);
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(sealed_out, hd, dn_bytes);
-        return ROFL_OK;
-    });
-}
-// the keys in the upload and the plaintexts in the download are wiped the same way; records, ADs, nonces and verdicts are public
-int rofl_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
-                   const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes, const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out) {
-    bool done; size_t ad_total, s_total;
-    if (int rc = aead_check(false, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, sealed_bytes, sealed_off, pt_out, verdict_out, &ad_total, &s_total, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // download: [plaintexts, laid out like the records | verdict bytes]
-        const AeadLayout l = aead_layout(n_keys, n, key_idx != nullptr, ad_total, s_total);
-        const size_t dn_bytes = s_total + n;
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        BlindWipe wipe_keys, wipe_out;
-        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = s_total; wipe_out.s = C.stream;
-        const uint8_t *du = aead_upload(C, wipe_keys, l, n_keys * 32, n_keys, key32, derive_round, n, key_idx, nonce12, ad_bytes, ad_off, ad_total, sealed_bytes, sealed_off, s_total);
-        ROFL_LAUNCH(k_aead_open, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, key_idx ? reinterpret_cast<const u32 *>(du + l.idx) : (const u32 *)nullptr,
-                    reinterpret_cast<const u32 *>(du), reinterpret_cast<const u32 *>(du + l.nonce), du + l.ad, reinterpret_cast<const u64 *>(du + l.ad_off),
-                    du + l.data, reinterpret_cast<const u64 *>(du + l.data_off), dd, dd + s_total);
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(verdict_out, hd + s_total, n);
-        for (size_t i = 0; i < n; i++)      // a record shorter than its tag writes nothing; the 16 bytes after a plaintext are not the library's
-            if (verdict_out[i] != 2 && sealed_off[i + 1] - sealed_off[i] > 16) memcpy(pt_out + sealed_off[i], hd + sealed_off[i], (size_t)(sealed_off[i + 1] - sealed_off[i] - 16));
-        return ROFL_OK;
-    });
-}
-// the two calls in plain C++ on one thread, no GPU: same parameters, same checks, same bytes
-int rofl_dbg_host_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
-                            const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes, const uint64_t *pt_off, uint8_t *sealed_out) {
-    bool done; size_t ad_total, pt_total;
-    if (int rc = aead_check(true, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, pt_bytes, pt_off, sealed_out, nullptr, &ad_total, &pt_total, &done)) return rc;
-    if (done) return ROFL_OK;
-    std::vector<uint32_t> keys(n_keys * 8);
-    for (size_t a = 0; a < n_keys; a++) aead_host_key(keys.data() + 8 * a, key32 + 32 * a, derive_round);
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t *key = keys.data() + 8 * (key_idx ? key_idx[i] : i);
-        const uint64_t len = pt_off[i + 1] - pt_off[i], alen = ad_off[i + 1] - ad_off[i];
-        uint32_t nc[3], tag[4];
-        memcpy(nc, nonce12 + 12 * i, 12);
-        uint8_t *o = sealed_out + pt_off[i] + 16 * i;
-        aead_host_xor(o, pt_bytes + pt_off[i], len, key, nc);
-        aead_host_tag(tag, key, nc, ad_bytes + ad_off[i], alen, o, len);
-        memcpy(o + len, tag, 16);
-    }
-    dh_wipe(keys.data(), keys.size() * 4);
-    return ROFL_OK;
-}
-int rofl_dbg_host_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
-                            const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes, const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out) {
-    bool done; size_t ad_total, s_total;
-    if (int rc = aead_check(false, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, sealed_bytes, sealed_off, pt_out, verdict_out, &ad_total, &s_total, &done)) return rc;
-    if (done) return ROFL_OK;
-    std::vector<uint32_t> keys(n_keys * 8);
-    for (size_t a = 0; a < n_keys; a++) aead_host_key(keys.data() + 8 * a, key32 + 32 * a, derive_round);
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t rlen = sealed_off[i + 1] - sealed_off[i], alen = ad_off[i + 1] - ad_off[i];
-        if (rlen < 16) { verdict_out[i] = 2; continue; }
-        const uint32_t *key = keys.data() + 8 * (key_idx ? key_idx[i] : i);
-        const uint8_t *ct = sealed_bytes + sealed_off[i];
-        uint32_t nc[3], tag[4];
-        memcpy(nc, nonce12 + 12 * i, 12);
-        aead_host_tag(tag, key, nc, ad_bytes + ad_off[i], alen, ct, rlen - 16);      // the tag over the ciphertext first
-        verdict_out[i] = memcmp(tag, ct + rlen - 16, 16) == 0 ? 0 : 1;
-        if (verdict_out[i]) { if (rlen > 16) memset(pt_out + sealed_off[i], 0, (size_t)(rlen - 16)); }
-        else aead_host_xor(pt_out + sealed_off[i], ct, rlen - 16, key, nc);
-    }
-    dh_wipe(keys.data(), keys.size() * 4);
-    return ROFL_OK;
-}
-// Poly1305 of n messages under n keys r || s through the kernels' own device functions (k_dbg_poly1305, one thread per message)
-int rofl_dbg_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16) {
-    bool done; size_t total;
-    if (int rc = poly_check(n, key32, msg_bytes, msg_off, tag_out16, &total, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: [keys | offsets | message bytes and 8 spare]; download: the tags
-        const size_t up_off = n * 32, up_msg = up_off + (n + 1) * 8, up_bytes = up_msg + ((total + 7) & ~(size_t)7) + 8;
-        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(n * 16), *dd = C.tmp_out.as<uint8_t>(n * 16);
-        memcpy(hu, key32, n * 32); memcpy(hu + up_off, msg_off, (n + 1) * 8);
-        if (total) memcpy(hu + up_msg, msg_bytes, total);
-        memset(hu + up_msg + total, 0, up_bytes - up_msg - total);
-        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_dbg_poly1305, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C.stream, (u32)n, reinterpret_cast<const u32 *>(du), (const uint8_t *)(du + up_msg),
-                    reinterpret_cast<const u64 *>(du + up_off), reinterpret_cast<u32 *>(dd));
-        HIPCHK(hipMemcpyAsync(hd, dd, n * 16, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(tag_out16, hd, n * 16);
-        return ROFL_OK;
-    });
-}
-int rofl_dbg_host_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16) {
-    bool done; size_t total;
-    if (int rc = poly_check(n, key32, msg_bytes, msg_off, tag_out16, &total, &done)) return rc;
-    if (done) return ROFL_OK;
-    for (size_t j = 0; j < n; j++) {
-        uint32_t k[8], m[4], tag[4];
-        memcpy(k, key32 + 32 * j, 32);
-        poly1305 P; poly1305_init(P, k);
-        const uint8_t *p = msg_bytes + msg_off[j];
-        const uint64_t len = msg_off[j + 1] - msg_off[j], full = len & ~(uint64_t)15;
-        for (uint64_t pos = 0; pos < full; pos += 16) { memcpy(m, p + pos, 16); poly1305_block(P, m, 1); }
-        if (len & 15) {
-            uint8_t last[16] = {0};
-            memcpy(last, p + full, (size_t)(len & 15)); last[len & 15] = 1;
-            memcpy(m, last, 16); poly1305_block(P, m, 0);
-        }
-        poly1305_finish(tag, P, k + 4);
-        memcpy(tag_out16 + 16 * j, tag, 16);
-    }
-    return ROFL_OK;
-}
-// ---- complaints: a DLEQ proof opens one pair's sealed channel to a judge (k_dh_public / k_dh_decode, k_dleq_prove / k_dleq_verify) ----
-}  // extern "C"
-namespace {
-// every check of rofl_dleq_prove / rofl_dleq_verify, shared with their host routes: those of rofl_dh_shared.  own32: secret keys (prove) or
-// public keys (verify); out: status or verdict bytes; *done: the call is empty and returns 0
-int dleq_check(bool prove, size_t n_own, const uint8_t *own32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
-               const uint8_t *reveal32, const uint8_t *proof64, const uint8_t *out, bool *done) {
-    *done = n_pairs == 0;
-    if (*done) return ROFL_OK;
-    if (!own32 || !peer_pk32 || !ctx32 || !reveal32 || !proof64 || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_own == 0 || n_peer == 0) return fail(ROFL_BAD_PARAM, "pairs without keys");
-    if (n_own > ((size_t)1 << 20) || n_peer > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
-    if (n_pairs > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 pairs in one call");
-    if (!pairs && n_pairs != n_own * n_peer) return fail(ROFL_BAD_PARAM, "without a pair list n_pairs is n_own x n_peer");
-    if (pairs) for (size_t i = 0; i < n_pairs; i++)
-        if (pairs[i].own >= n_own || pairs[i].peer >= n_peer) { char buf[96]; snprintf(buf, sizeof buf, "pair %zu names a key that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
-    return prove ? dh_check_keys(n_own, own32) : ROFL_OK;
-}
-// int_le(SHAKE256("rofl-zk/dleq/v1" || which || the parts, 32 bytes each)[0 .. 64)) mod l: which = 'k' takes three parts, 'c' six
-sc dleq_host_wide(char which, const uint8_t *const *parts, int n_parts) {
-    uint8_t m[208] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 'd', 'l', 'e', 'q', '/', 'v', '1', (uint8_t)which}, w[64];
-    for (int p = 0; p < n_parts; p++) memcpy(m + 16 + 32 * p, parts[p], 32);
-    Sponge sp(136, 0x1F); sp.absorb(m, 16 + 32 * (size_t)n_parts); sp.squeeze(w, 64);
-    sc r = sc_from_wide(sc_frombytes(w), sc_frombytes(w + 32));
-    dh_wipe(m, sizeof m); dh_wipe(w, sizeof w); dh_wipe(&sp, sizeof sp);
-    return r;
-}
-// the keys of a host route decoded once: refused[j] as k_dh_decode's status word (1 not canonical, 2 the identity)
-void dleq_host_decode(size_t n, const uint8_t *pk32, std::vector<uint8_t> &refused, std::vector<h51::ge5> &pts) {
-    refused.assign(n, 0); pts.resize(n);
-    for (size_t j = 0; j < n; j++) {
-        ge P;
-        refused[j] = !ristretto_decode(P, pk32 + 32 * j) ? 1 : ge_is_identity_ristretto(P) ? 2 : 0;
-        if (!refused[j]) pts[j] = h51::from_ge(P);
-    }
-}
-// the driver of the two debug hooks below: one upload, one launch, one download; *kernel_ms (may be NULL) is the launch between two events
-int dbg_var_mul_device(bool joint, size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms) {
-    if (n == 0) return ROFL_OK;
-    if (!k1_32 || !p1_32 || !k2_32 || !p2_32 || !out32) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 items in one call");
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        uint8_t *hu = C.h_misc.as<uint8_t>(n * 128), *du = C.tmp_in.as<uint8_t>(n * 128);      // [k1 | p1 | k2 | p2]
-        uint8_t *hd = C.h_misc2.as<uint8_t>(n * 32), *dd = C.tmp_out.as<uint8_t>(n * 32);
-        memcpy(hu, k1_32, n * 32); memcpy(hu + n * 32, p1_32, n * 32); memcpy(hu + n * 64, k2_32, n * 32); memcpy(hu + n * 96, p2_32, n * 32);
-        HIPCHK(hipMemcpyAsync(du, hu, n * 128, hipMemcpyHostToDevice, C.stream));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (kernel_ms) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, C.stream)); }
-        const dim3 grid((unsigned)((n + 63) / 64));
-        const sc *k1 = reinterpret_cast<const sc *>(du), *k2 = reinterpret_cast<const sc *>(du + n * 64);
-        if (joint) ROFL_LAUNCH(k_dbg_var_mul2, grid, dim3(64), 0, C.stream, (u32)n, k1, (const uint8_t *)(du + n * 32), k2, (const uint8_t *)(du + n * 96), dd);
-        else ROFL_LAUNCH(k_dbg_var_mul_sum, grid, dim3(64), 0, C.stream, (u32)n, k1, (const uint8_t *)(du + n * 32), k2, (const uint8_t *)(du + n * 96), dd);
-        if (kernel_ms) HIPCHK(hipEventRecord(e1, C.stream));
-        HIPCHK(hipMemcpyAsync(hd, dd, n * 32, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        if (kernel_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1)); *kernel_ms = ms; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-        memcpy(out32, hd, n * 32);
-        return ROFL_OK;
-    });
-}
-}  // namespace
-extern "C" {
-// The lane's copies of the secret keys -- pinned staging and device workspace -- are overwritten with zeros before the call returns or
-// unwinds; the nonces never leave their threads' registers; reveals and proofs are what the caller publishes.
-int rofl_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs,
-                    const uint8_t *ctx32, uint8_t *reveal_out32, uint8_t *proof_out64, uint8_t *status_out) {
-    bool done;
-    if (int rc = dleq_check(true, n_own, sk32, n_peer, peer_pk32, n_pairs, pairs, ctx32, reveal_out32, proof_out64, status_out, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: [secret keys | peer keys | contexts | pair list]; download: [reveals | proofs | own public keys | status bytes]
-        const size_t up_ctx = (n_own + n_peer) * 32, up_pairs = up_ctx + n_pairs * 32, up_bytes = up_pairs + (pairs ? n_pairs * sizeof(rofl_dh_pair_t) : 0);
-        const size_t dn_proof = n_pairs * 32, dn_pk = dn_proof + n_pairs * 64, dn_st = dn_pk + n_own * 32, dn_bytes = dn_st + n_pairs;
-        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        ge *pts = C.aux_pts.as<ge>(n_peer); u32 *pst = C.status.as<u32>(n_peer);
-        BlindWipe wipe_keys;
-        wipe_keys.h = hu; wipe_keys.dv = du; wipe_keys.n = n_own * 32; wipe_keys.s = C.stream;
-        memcpy(hu, sk32, n_own * 32); memcpy(hu + n_own * 32, peer_pk32, n_peer * 32); memcpy(hu + up_ctx, ctx32, n_pairs * 32);
-        if (pairs) memcpy(hu + up_pairs, pairs, n_pairs * sizeof(rofl_dh_pair_t));
-        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_dh_public, dim3((unsigned)((n_own + 63) / 64)), dim3(64), 0, C.stream, (u32)n_own, reinterpret_cast<const sc *>(du), C.d_tabB8, dd + dn_pk);
-        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_peer + 63) / 64)), dim3(64), 0, C.stream, (u32)n_peer, (const uint8_t *)(du + n_own * 32), pts, pst);
-        ROFL_LAUNCH(k_dleq_prove, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_pairs, (u32)n_peer,
-                    pairs ? reinterpret_cast<const uint2 *>(du + up_pairs) : (const uint2 *)nullptr, reinterpret_cast<const sc *>(du), (const uint8_t *)(dd + dn_pk),
-                    (const uint8_t *)(du + n_own * 32), (const ge *)pts, (const u32 *)pst, (const uint8_t *)(du + up_ctx), C.d_tabB8, dd, dd + dn_proof, dd + dn_st);
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        memcpy(reveal_out32, hd, n_pairs * 32); memcpy(proof_out64, hd + dn_proof, n_pairs * 64); memcpy(status_out, hd + dn_st, n_pairs);
-        if (own_pk_out32) memcpy(own_pk_out32, hd + dn_pk, n_own * 32);
-        return ROFL_OK;
-    });
-}
-// The inputs are public; the shared secrets that come back open the pair's channel, so the lane's copies of them are overwritten with zeros.
-int rofl_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
-                     const uint8_t *reveal32, const uint8_t *proof64, uint8_t *shared_out32, uint8_t *verdict_out) {
-    bool done;
-    if (int rc = dleq_check(false, n_own, own_pk32, n_peer, peer_pk32, n_pairs, pairs, ctx32, reveal32, proof64, verdict_out, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // upload: [prover keys | peer keys | contexts | reveals | proofs | pair list]; workspace: both key tables decoded by ONE k_dh_decode
-        // launch, with their status words; download: [shared secrets | verdict bytes]
-        const size_t n_keys = n_own + n_peer;
-        const size_t up_ctx = n_keys * 32, up_rev = up_ctx + n_pairs * 32, up_proof = up_rev + n_pairs * 32, up_pairs = up_proof + n_pairs * 64;
-        const size_t up_bytes = up_pairs + (pairs ? n_pairs * sizeof(rofl_dh_pair_t) : 0);
-        const size_t dn_v = shared_out32 ? n_pairs * 32 : 0, dn_bytes = dn_v + n_pairs;
-        uint8_t *hu = C.h_misc.as<uint8_t>(up_bytes), *du = C.tmp_in.as<uint8_t>(up_bytes);
-        uint8_t *hd = C.h_misc2.as<uint8_t>(dn_bytes), *dd = C.tmp_out.as<uint8_t>(dn_bytes);
-        ge *pts = C.aux_pts.as<ge>(n_keys); u32 *pst = C.status.as<u32>(n_keys);
-        BlindWipe wipe_out;
-        wipe_out.h = hd; wipe_out.dv = dd; wipe_out.n = dn_v; wipe_out.s = C.stream;
-        memcpy(hu, own_pk32, n_own * 32); memcpy(hu + n_own * 32, peer_pk32, n_peer * 32); memcpy(hu + up_ctx, ctx32, n_pairs * 32);
-        memcpy(hu + up_rev, reveal32, n_pairs * 32); memcpy(hu + up_proof, proof64, n_pairs * 64);
-        if (pairs) memcpy(hu + up_pairs, pairs, n_pairs * sizeof(rofl_dh_pair_t));
-        HIPCHK(hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, C.stream));
-        ROFL_LAUNCH(k_dh_decode, dim3((unsigned)((n_keys + 63) / 64)), dim3(64), 0, C.stream, (u32)n_keys, (const uint8_t *)du, pts, pst);
-        ROFL_LAUNCH(k_dleq_verify, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, C.stream, (u32)n_pairs, (u32)n_peer,
-                    pairs ? reinterpret_cast<const uint2 *>(du + up_pairs) : (const uint2 *)nullptr, (const uint8_t *)du, (const ge *)pts, (const u32 *)pst,
-                    (const uint8_t *)(du + n_own * 32), (const ge *)(pts + n_own), (const u32 *)(pst + n_own), (const uint8_t *)(du + up_ctx), (const uint8_t *)(du + up_rev),
-                    (const uint8_t *)(du + up_proof), C.d_tabB8, shared_out32 ? dd : (uint8_t *)nullptr, dd + dn_v);
-        HIPCHK(hipMemcpyAsync(hd, dd, dn_bytes, hipMemcpyDeviceToHost, C.stream));
-        C.sync();
-        if (shared_out32) memcpy(shared_out32, hd, n_pairs * 32);
-        memcpy(verdict_out, hd + dn_v, n_pairs);
-        return ROFL_OK;
-    });
-}
-// the two calls on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: same parameters, same checks, same bytes
-int rofl_dbg_host_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs,
-                             const uint8_t *ctx32, uint8_t *reveal_out32, uint8_t *proof_out64, uint8_t *status_out) {
-    bool done;
-    if (int rc = dleq_check(true, n_own, sk32, n_peer, peer_pk32, n_pairs, pairs, ctx32, reveal_out32, proof_out64, status_out, &done)) return rc;
-    if (done) return ROFL_OK;
-    ge Bg; ristretto_decode(Bg, kDhBase);
-    const h51::ge5 B = h51::from_ge(Bg);
-    std::vector<uint8_t> pk(n_own * 32), can(n_own * 32), refused;
-    std::vector<sc> keys(n_own);
-    std::vector<h51::ge5> pp;
-    for (size_t a = 0; a < n_own; a++) {
-        keys[a] = dh_key_scalar(sk32 + 32 * a);
-        sc_tobytes(can.data() + 32 * a, keys[a]);
-        h51::encode(pk.data() + 32 * a, dh_host_mul(keys[a], B));
-    }
-    dleq_host_decode(n_peer, peer_pk32, refused, pp);
-    for (size_t i = 0; i < n_pairs; i++) {
-        const size_t a = pairs ? pairs[i].own : i / n_peer, b = pairs ? pairs[i].peer : i % n_peer;
-        uint8_t *S = reveal_out32 + 32 * i, *pf = proof_out64 + 64 * i, T1[32], T2[32];
-        status_out[i] = refused[b];
-        if (refused[b]) { memset(S, 0, 32); memset(pf, 0, 64); continue; }
-        const uint8_t *P = peer_pk32 + 32 * b, *cx = ctx32 + 32 * i;
-        const uint8_t *kparts[3] = {can.data() + 32 * a, P, cx};
-        sc k = dleq_host_wide('k', kparts, 3);
-        h51::encode(S, dh_host_mul(keys[a], pp[b]));
-        h51::encode(T1, dh_host_mul(k, B));
-        h51::encode(T2, dh_host_mul(k, pp[b]));
-        const uint8_t *cparts[6] = {pk.data() + 32 * a, P, S, T1, T2, cx};
-        sc c = dleq_host_wide('c', cparts, 6);
-        sc s = sc_add(k, sc_montmul(sc_to_mont(c), keys[a]));
-        sc_tobytes(pf, c); sc_tobytes(pf + 32, s);
-        dh_wipe(&k, sizeof k); dh_wipe(&c, sizeof c); dh_wipe(&s, sizeof s);
-    }
-    if (own_pk_out32) memcpy(own_pk_out32, pk.data(), n_own * 32);
-    dh_wipe(keys.data(), keys.size() * sizeof(sc)); dh_wipe(can.data(), can.size());
-    return ROFL_OK;
-}
-int rofl_dbg_host_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
-                              const uint8_t *reveal32, const uint8_t *proof64, uint8_t *shared_out32, uint8_t *verdict_out) {
-    bool done;
-    if (int rc = dleq_check(false, n_own, own_pk32, n_peer, peer_pk32, n_pairs, pairs, ctx32, reveal32, proof64, verdict_out, &done)) return rc;
-    if (done) return ROFL_OK;
-    ge Bg; ristretto_decode(Bg, kDhBase);
-    const h51::ge5 B = h51::from_ge(Bg);
-    std::vector<uint8_t> own_refused, peer_refused;
-    std::vector<h51::ge5> op, pp;
-    dleq_host_decode(n_own, own_pk32, own_refused, op);
-    dleq_host_decode(n_peer, peer_pk32, peer_refused, pp);
-    for (size_t i = 0; i < n_pairs; i++) {
-        const size_t a = pairs ? pairs[i].own : i / n_peer, b = pairs ? pairs[i].peer : i % n_peer;
-        const uint8_t *S = reveal32 + 32 * i, *pf = proof64 + 64 * i, *A = own_pk32 + 32 * a, *P = peer_pk32 + 32 * b, *cx = ctx32 + 32 * i;
-        if (shared_out32) memset(shared_out32 + 32 * i, 0, 32);
-        const sc c = sc_frombytes(pf), s = sc_frombytes(pf + 32);
-        ge Sg;
-        if (own_refused[a] || peer_refused[b] || sc_geq_l(c.v) || sc_geq_l(s.v) || !ristretto_decode(Sg, S) || ge_is_identity_ristretto(Sg)) { verdict_out[i] = 2; continue; }
-        const sc nc = sc_neg(c);
-        uint8_t T1[32], T2[32], c2[32];
-        h51::encode(T1, h51::gadd(dh_host_mul(s, B), dh_host_mul(nc, op[a])));
-        h51::encode(T2, h51::gadd(dh_host_mul(s, pp[b]), dh_host_mul(nc, h51::from_ge(Sg))));
-        const uint8_t *cparts[6] = {A, P, S, T1, T2, cx};
-        sc_tobytes(c2, dleq_host_wide('c', cparts, 6));
-        verdict_out[i] = memcmp(c2, pf, 32) == 0 ? 0 : 1;
-        if (verdict_out[i] == 0 && shared_out32) dh_host_secret(shared_out32 + 32 * i, S, A, P);
-    }
-    return ROFL_OK;
-}
-// out32[i] = encode(k1[i] decode(p1[i]) + k2[i] decode(p2[i])) through the kernels' own device functions, one thread per item: on the joint
-// chain sg_var_mul2 (rofl_dbg_var_mul2) and as gd_add(sg_var_mul, sg_var_mul) (rofl_dbg_var_mul_sum)
-int rofl_dbg_var_mul2(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms) {
-    return dbg_var_mul_device(true, n, k1_32, p1_32, k2_32, p2_32, out32, kernel_ms);
-}
-int rofl_dbg_var_mul_sum(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms) {
-    return dbg_var_mul_device(false, n, k1_32, p1_32, k2_32, p2_32, out32, kernel_ms);
 }
 // conversion32::f32_to_fp_vec / uint_to_f32_vec (conversion32.rs:41-54): Fix is unsigned, negative inputs saturate to 0
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out) {

@@ -253,6 +253,40 @@ int rofl_noise_binomial(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, c
  * before the call returns.  Runs on the calling thread's device and lane; the `devices` option does not apply.  Not constant time. */
 int rofl_clip_l2(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 or NULL */, const float *const *values, size_t d, const uint64_t *max_sq /* n_vec */,
                  size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out, uint64_t *scale_out /* n_vec or NULL */);
+/* Randomized Hadamard rotation: y = (1 / sqrt(B)) H_B D x per block of B elements, D a diagonal of seeded signs: the step the papers of
+ * the chain above (cpSGD, the distributed discrete Gaussian, Skellam) put in FRONT of the rounding.  An update of L2 norm rho may hold all
+ * of rho in one coordinate, which the per-coordinate range of the L-inf leg then clips; after the rotation every coordinate is about
+ * rho / sqrt(B).  The rotation is orthonormal, so an L2 bound means the same before and after it, and the sum commutes with it: the
+ * server undoes it once, on the extracted aggregate.  The output is longer than the input (whole blocks): the rotation stands in front of
+ * the containers, which take the rotated vector and blindings of its length.
+ * B = 2^k, k = block_log2, 0 <= k <= 22; n_blk = ceil(d / B); dp = n_blk B.  Forward (inverse = 0): values[v] holds d floats, out[v]
+ * receives dp floats, elements d .. dp - 1 of the input count as +0.0.  Inverse (inverse = 1): d is a multiple of B, d floats go in and d
+ * floats come out.  Per block, every step is ONE IEEE binary32 operation, round to nearest even, subnormals kept, so that host, device
+ * and any schedule of the butterflies give the same bytes:
+ *   0. clamp: z_i = fminf(2^100, fmaxf(-2^100, x_i)); a NaN goes to -2^100, the way rofl_clip_f32 sends it to its minimum.  With
+ *      |z| <= 2^100 and B <= 2^22 nothing below overflows or produces a NaN, which is why the rule can promise bytes.
+ *   1. signs (forward: here; inverse: LAST): the sign bit of z_i flips when s_e = 1, e = block B + i the index in the padded vector,
+ *      s_e = bit e & 31 of little-endian u32 word (e >> 5) & 31 of stream block e >> 10: the first 128 bytes of
+ *      SHAKE256("rofl-zk/rotate/v1" || seed[32] || u64le(block)), the construction of the other streams under a label of its own.
+ *   2. butterflies: k stages, h = 1, 2, 4, .., B / 2; for every i with i & h == 0: (z_i, z_{i+h}) <- (z_i + z_{i+h}, z_i - z_{i+h}).
+ *      Register butterflies of any radix, shuffles and passes through shared memory are this network evaluated in another order.
+ *   3. scale: one multiplication by c_B as the LAST arithmetic operation on every element: c_B = 2^(-k/2) for even k,
+ *      2^(-(k-1)/2) f32(0x3F3504F3) for odd k.  It is not folded into the last butterfly and no contraction does so.
+ *   The inverse is steps 0, 2, 3, then 1 (H is symmetric).
+ *   Consequences.  ||out - exact||_2 <= (k + 2) 2^-24 ||x||_2 for finite inputs whose butterflies stay normal; a round trip stays within
+ *   (2k + 4) 2^-24 ||x||_2.  Dyadic inputs whose butterflies fit 24 bits are transformed exactly, and with an even k so is the way back.
+ *   k = 0 is the sign flip alone.  The signs are the inverse's last step, so an exact zero comes back as +0.0 or -0.0: compare by value.
+ * The seed is PUBLIC: every client and the server of a round use the same one (it still goes through the wiping path of the secret
+ * seeds, which is harmless).  n_vec vectors of one length in ONE call, each with its own seed (seeds32 + 32 v), input and output;
+ * values[v] and out[v] are host or device memory in any combination, and out[v] may be values[v] when that buffer holds the output
+ * length.  Returns 11 before the device is touched for: k > 22, inverse not 0 or 1, a null seeds32 / values / out array or entry, more
+ * than 65 535 vectors, dp >= 2^28 (the kernels count elements in 32 bits), and an inverse whose d is not a multiple of B.  n_vec = 0 or
+ * d = 0 returns 0 and writes nothing.  There is no `first`: a block is indivisible.  An all-host call below a fixed, measured number of
+ * elements runs the network on the host, compiled from the kernels' source: same bytes, no device needed.  Otherwise
+ * one launch for B <= 8 192 and two for longer blocks, with no host round trip between them.  Runs on the calling thread's device and
+ * lane; the `devices` option does not apply. */
+int rofl_rotate(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, const float *const *values, size_t d, unsigned block_log2, int inverse,
+                float *const *out);
 
 /* ---- l2_range_proof_vec (l2_range_proof_vec/mod.rs) ---- */
 /* create_rangeproof_l2 :15-140.  The batch call below with one client, on the calling thread's device: values and blindings32 are host

@@ -189,6 +189,12 @@ int rofl_dbg_clip_l2_round(unsigned site, size_t n, const uint64_t *q, uint32_t 
  * pointers only, else 11), 1 = the kernels.  Same checks, same bytes; what scripts/gpu_l2_clip.py finds the crossover with. */
 int rofl_dbg_clip_l2_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq,
                            size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out, uint64_t *scale_out);
+/* rofl_rotate with the route chosen by the caller instead of by the pointers and the size: route 0 = the host copy of the network (host
+ * pointers only, else 11), 1 = the kernels.  Same checks, same bytes; what scripts/gpu_rotate.py finds the crossover with. */
+int rofl_dbg_rotate_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, unsigned block_log2, int inverse,
+                          float *const *out);
+/* log2 of the elements a workgroup of k_rotate_tile owns: blocks up to this size take one launch, longer ones also k_rotate_cols.  No GPU. */
+int rofl_dbg_rotate_tile_log2(void);
 /* one pair of rofl_dh_shared from the host arithmetic (no GPU): out32 and *status as that call gives them; own_pk32 == NULL: computed from sk32.
  * Returns 11 for a null pointer or a secret key that is 0 mod l. */
 int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status);

@@ -128,6 +128,11 @@ extern "C" {
     /// squares of the result is; seeds32 null: truncation, else seeded rounding of the scaled steps; scale_out (n_vec u64) may be null
     pub fn rofl_clip_l2(n_vec: usize, seeds32: *const u8, values: *const *const c_float, d: usize, max_sq: *const u64, prove_range: usize,
         fp_bits: c_uint, fp_frac: c_uint, out: *const *mut c_float, scale_out: *mut u64) -> c_int;
+    /// randomized Hadamard rotation, n_vec vectors (own PUBLIC seed, input, output each) in one call: per block of 2^block_log2 elements
+    /// out = (1 / sqrt(B)) H D values (inverse = 1: D H), bit-defined; forward reads d floats and writes ceil(d / B) B, the inverse takes
+    /// and returns whole blocks; values[v] / out[v] are host memory or device memory of the library's device
+    pub fn rofl_rotate(n_vec: usize, seeds32: *const u8, values: *const *const c_float, d: usize, block_log2: c_uint, inverse: c_int,
+        out: *const *mut c_float) -> c_int;
     pub fn rofl_verify_rangeproof_l2_batch(n_clients: usize, proofs: *const *const u8, proof_len: usize, commits32: *const u8,
         prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, verifier_seed: *const u8, ok_out: *mut c_int) -> c_int;
     pub fn rofl_verify_randproof_vec_batch(n_clients: usize, proofs: *const *const u8, commits: *const *const u8, d: usize, ok_out: *mut c_int) -> c_int;

@@ -61,6 +61,24 @@ pub fn add_binomial_noise(value_vec: &Vec<f32>, prove_range: usize, seed: &[u8; 
     out
 }
 
+/// ceil(d / B) B with B = 2^block_log2: the length of a rotated vector, which the blinding vectors of a rotated round have as well.
+pub fn rotated_len(d: usize, block_log2: u32) -> usize {
+    ((d + (1usize << block_log2) - 1) >> block_log2) << block_log2
+}
+
+/// No counterpart in the reference: the randomized Hadamard rotation y = (1 / sqrt(B)) H_B D x per block of B = 2^block_log2 elements,
+/// the step in FRONT of the rounding that spreads an update over its coordinates, so that none of them meets the per-coordinate range.
+/// `seed` is PUBLIC: every client and the server of a round use the same one.  Returns `rotated_len` elements, the padding counting as
+/// zeros; `inverse` takes and returns whole blocks -- the server calls it once on the extracted aggregate and truncates to d.  Bit-defined
+/// (include/rofl_zk.h).  Panics on a bad parameter (block_log2 above 22, an inverse of a length that is not whole blocks).
+pub fn rotate(value_vec: &Vec<f32>, seed: &[u8; 32], block_log2: u32, inverse: bool) -> Vec<f32> {
+    let mut out = vec![0f32; if block_log2 <= 22 { rotated_len(value_vec.len(), block_log2) } else { 0 }];
+    let (vp, op) = (value_vec.as_ptr(), out.as_mut_ptr());
+    let rc = unsafe { rofl_rotate(1, seed.as_ptr(), &vp, value_vec.len(), block_log2, inverse as i32, &op) };
+    if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+    out
+}
+
 /// reference: range_proof_vec/mod.rs:149-191.  `Ok(false)` for a proof that does not verify, `Err` for malformed input.
 pub fn verify_rangeproof(
     range_proof_vec: &Vec<RangeProof>,

@@ -388,9 +388,10 @@ class range_proof_vec:
                                             lib().rofl_quantize_prob(n, sb, vp, first, d, _sz(prove_range), *fp, op))
 
     @staticmethod
-    def _seeded_vecs(list_of_values, prove_range, seeds, first, out, call):
+    def _seeded_vecs(list_of_values, prove_range, seeds, first, out, call, out_len=None):
         """the arguments of rofl_quantize_prob and rofl_noise_binomial -- one seed, one input and one destination per vector, host or device
-        memory -- checked and marshalled; call(n, seeds, values, first, d, out) -> return code"""
+        memory -- checked and marshalled; call(n, seeds, values, first, d, out) -> return code.  out_len(d) -> the length of a
+        destination where it is not d (rofl_rotate)."""
         n, first = len(list_of_values), int(first)
         seeds = [bytes(s) for s in seeds]
         if len(seeds) != n:
@@ -412,8 +413,9 @@ class range_proof_vec:
                 raise ValueError("the vectors of one call have one length")
             d, vp[v] = dv, p
         d = d or 0
+        do = d if out_len is None else out_len(d)
         if out is None:
-            res = np.empty((n, d), dtype=np.float32)
+            res = np.empty((n, do), dtype=np.float32)
             dst = [res[v] for v in range(n)]
         else:
             res = dst = list(out)
@@ -422,12 +424,12 @@ class range_proof_vec:
         op = (ctypes.c_void_p * max(n, 1))()
         for v, o in enumerate(dst):
             if _is_dev(o):
-                if not o.is_contiguous() or o.element_size() != 4 or o.numel() != d:
-                    raise ValueError("a device destination is a contiguous float32 tensor of d elements")
+                if not o.is_contiguous() or o.element_size() != 4 or o.numel() != do:
+                    raise ValueError("a device destination is a contiguous float32 tensor of %d elements" % do)
                 op[v] = o.data_ptr()
             else:
-                if not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous and o.flags.writeable and o.size == d):
-                    raise ValueError("a host destination is a writable contiguous float32 array of d elements")
+                if not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous and o.flags.writeable and o.size == do):
+                    raise ValueError("a host destination is a writable contiguous float32 array of %d elements" % do)
                 op[v] = o.ctypes.data
         sb = ctypes.create_string_buffer(b"".join(seeds), max(32 * n, 1))
         try:
@@ -491,6 +493,50 @@ class range_proof_vec:
             hi = np.nextafter(hi, np.float32(0))
         v = np.ascontiguousarray(values, dtype=np.float32)
         return np.minimum(hi, np.maximum(-hi, np.where(np.isnan(v), -hi, v))).astype(np.float32)
+
+    # ---- Hadamard rotation (rofl_rotate): y = (1 / sqrt(B)) H_B D x per block of B = 2^block_log2 elements, seeded signs ----
+    @staticmethod
+    def rotated_len(d, block_log2):
+        """ceil(d / B) B with B = 2^block_log2: the length of a rotated vector of d elements -- what the containers and the blinding
+        vectors of a rotated round are sized by."""
+        d, k = int(d), int(block_log2)
+        if d < 0 or not 0 <= k <= 22:
+            raise ValueError("d is not negative and block_log2 is 0 .. 22")
+        return -(-d >> k) << k
+
+    @staticmethod
+    def rotate_vecs(list_of_values, seed_or_seeds, block_log2, inverse=False, out=None):
+        """rofl_rotate for several vectors of one length (the clients a process hosts) in ONE call: every block of B = 2^block_log2
+        elements of vector v is clamped to +-2^100, multiplied by the signs of the stream of its seed, sent through the Walsh-Hadamard
+        butterflies and scaled by 1 / sqrt(B) (include/rofl_zk.h has the definition: bit-defined, the same bytes on the host and on the
+        GPU).  A single 32-byte seed is repeated for every vector; it is PUBLIC, every client and the server of a round use the same one
+        (pedersen_ops.rotate_round_seed).  A vector of d elements comes back with rotated_len(d, block_log2) elements, the padding
+        counting as zeros; inverse=True takes whole blocks and returns as many elements.  Vectors, `out` and the return value are as in
+        quantize_probabilistic_vecs: numpy arrays or float32 tensors on the library's GPU, also in place where the buffer holds the
+        output length.  The rotation stands in FRONT of the containers: they take the rotated vector and blindings of its length."""
+        n, k = len(list_of_values), int(block_log2)
+        if not 0 <= k <= 22:
+            raise ValueError("block_log2 is 0 .. 22")
+        seeds = [bytes(seed_or_seeds)] * n if isinstance(seed_or_seeds, (bytes, bytearray, memoryview)) else list(seed_or_seeds)
+        return range_proof_vec._seeded_vecs(list_of_values, 1, seeds, 0, out, lambda n_, sb, vp, first, d, op:
+                                            lib().rofl_rotate(n_, sb, vp, d, ctypes.c_uint(k), ctypes.c_int(1 if inverse else 0), op),
+                                            out_len=lambda d: range_proof_vec.rotated_len(d, k))
+
+    @staticmethod
+    def rotate(x, seed, block_log2):
+        """rotate_vecs for one vector -> float32[rotated_len(d, block_log2)] (a GPU tensor in: pass out= to rotate_vecs to keep it there)."""
+        return range_proof_vec.rotate_vecs([x], seed, block_log2)[0]
+
+    @staticmethod
+    def unrotate(y, seed, block_log2, d=None):
+        """the inverse of rotate on a vector of whole blocks -- what the server applies ONCE to the aggregate DeviceAccumulator.extract
+        returns -- truncated to its first d elements (d=None: all of them).  -> float32[d]"""
+        x = range_proof_vec.rotate_vecs([y], seed, block_log2, inverse=True)[0]
+        if d is not None:
+            if not 0 <= int(d) <= x.size:
+                raise ValueError("d is 0 .. len(y)")
+            x = x[:int(d)]
+        return x
 
     @staticmethod
     def create_rangeproof(values, blindings, prove_range, n_partition, nonce=None, fp=None):
@@ -2383,6 +2429,13 @@ class pedersen_ops:
         `round_no` (l2_range_proof_vec.clip_l2, the clip_seed of the L2 containers' encrypt), from a long-lived secret of ITS OWN.  The
         seed is a per-round secret of the client: whoever learns it learns which way every scaled coordinate was rounded."""
         return hashlib.sha3_256(b"rofl-zk/clip2/v1/round" + bytes(secret) + struct.pack("<Q", int(round_no))).digest()
+
+    @staticmethod
+    def rotate_round_seed(public, round_no):
+        """SHA3-256("rofl-zk/rotate/v1/round" || public || u64le(round_no)): the seed of the Hadamard rotation of round `round_no`
+        (range_proof_vec.rotate / unrotate), from a value every participant knows, for instance the round's model hash.  Unlike
+        quant_round_seed this seed is PUBLIC: every client and the server of a round use the same one, and nothing is hidden by it."""
+        return hashlib.sha3_256(b"rofl-zk/rotate/v1/round" + bytes(public) + struct.pack("<Q", int(round_no))).digest()
 
     @staticmethod
     def compute_shifted_values_vec(values, offset):

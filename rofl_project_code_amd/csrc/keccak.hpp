@@ -116,6 +116,19 @@ HD void shake256_seeded_block(u64 st[25], const u64 dom[2], const u64 seed[4], u
 // Rounding words of the norm clipping (rofl_clip_l2): a sixth label, so that the words that round the scaled update are unrelated to the
 // words that rounded it onto the grid and to its noise, also under a reused seed.
 #define ROFL_CLIP_DOM {0x2f6b7a2d6c666f72ULL, 0x31762f3270696c63ULL}       /* "rofl-zk/" "clip2/v1" */
+// Sign bits of the Hadamard rotation (rofl_rotate): the same construction under "rofl-zk/rotate/v1", a label of 17 bytes, so the seed and
+// the index lie one byte off the words: SHAKE256(label17 || seed32 || u64le(index)), 57 bytes, one squeezed block.  The seed is PUBLIC.
+HD void shake256_rotate_block(u64 st[25], const u64 seed[4], u64 index) {
+#pragma unroll
+    for (int i = 0; i < 25; i++) st[i] = 0;
+    st[0] = 0x2f6b7a2d6c666f72ULL; st[1] = 0x762f657461746f72ULL;      /* "rofl-zk/" "rotate/v" */
+    st[2] = 0x31ULL | (seed[0] << 8);                                   /* "1" */
+    st[3] = (seed[0] >> 56) | (seed[1] << 8); st[4] = (seed[1] >> 56) | (seed[2] << 8); st[5] = (seed[2] >> 56) | (seed[3] << 8);
+    st[6] = (seed[3] >> 56) | (index << 8);
+    st[7] = (index >> 56) | (0x1FULL << 8);      // SHAKE domain suffix right after 57 bytes
+    st[16] ^= 0x8000000000000000ULL;             // final bit of the 136-byte rate
+    keccak_f1600(st);
+}
 // wide scalar h (0 / 1) of a squeezed block: bytes 64 h .. 64 h + 64, reduced like Scalar::from_bytes_mod_order_wide (canonical)
 HD sc xof_block_scalar(const u64 st[25], int h) {
     sc lo, hi;

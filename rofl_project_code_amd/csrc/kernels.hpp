@@ -736,6 +736,217 @@ __global__ void __launch_bounds__(TPB) k_dbg_clip_l2_round(u32 n, const u64 *q, 
 }
 #endif
 
+// ================================================================ Hadamard rotation
+// rofl_rotate (the definition is in include/rofl_zk.h): y = c_B H_B D x per block of B = 2^k elements, every step one IEEE binary32
+// operation in a fixed network, so that the host copy below, the kernels and any schedule of the butterflies give the same bytes.  The
+// element rules are compiled for the host and the device from this one source.
+#define ROT_T_LOG2 13                    /* a workgroup of k_rotate_tile owns T = 8 192 contiguous elements: 32 KB of LDS */
+#define ROT_T (1u << ROT_T_LOG2)
+#define ROT_TPB 512                      /* 16 consecutive elements per thread */
+#define ROT_COL_TPB 256
+#define ROT_MAX_LOG2 22
+// step 0: |z| <= 2^100, a NaN goes to -2^100 (the comparisons of rofl_clip_f32); -0.0 and subnormals pass
+HD float rot_clamp(float x) {
+    const float L = 1.2676506002282294e30f;      // 2^100
+    float c = (-L >= x || x != x) ? -L : x;
+    return (L <= c) ? L : c;
+}
+// step 1: the sign bit flips where the stream's bit is set
+HD float rot_flip(float z, u32 bit) {
+    u32 u; __builtin_memcpy(&u, &z, 4); u ^= bit << 31; __builtin_memcpy(&z, &u, 4);
+    return z;
+}
+// step 3: c_B = 2^(-k/2), or 2^(-(k-1)/2) f32(0x3F3504F3) for odd k -- a power of two times one float, exact
+HD float rot_scale(u32 k) {
+    const u32 u = ((127u - (k >> 1) - (k & 1)) << 23) | ((k & 1) ? 0x3504F3u : 0u);      // (odd k: the exponent and the mantissa of 0x3F3504F3)
+    float c; __builtin_memcpy(&c, &u, 4);
+    return c;
+}
+// sign bit of element e of the padded vector from the words of its XOF block (e >> 10)
+HD u32 rot_sign_bit(const u64 st[25], u32 e) { return (quant_block_word(st, (e >> 5) & 31) >> (e & 31)) & 1; }
+#if ROFL_KG(4)
+// LDS image of a tile, element idx at rot_swz(idx): a thread's 16 consecutive elements stay in its own 64 bytes, and its four 16-byte
+// pieces are rotated by (idx >> 5) & 3, so that the eight lanes of a ds_write_b128 group (stride 64 bytes: two 128-byte bank rows between
+// them without the rotation) cover all 32 banks once.  A run of 32 (or, read as pairs, 64) consecutive idx is a permutation of one bank
+// row, so the reads of the LDS stages below are conflict-free as well.  No padding: the tile takes exactly 4 T bytes.
+__device__ __forceinline__ u32 rot_swz(u32 idx) { return (idx & ~15u) | (((((idx >> 2) & 3) + (idx >> 5)) & 3) << 2) | (idx & 3); }
+// blockIdx.y = vector, blockIdx.x = tile: elements T blockIdx.x .. + T - 1 of the padded vector, whole blocks of it when B <= T and a
+// part of one block otherwise.  Thread t holds elements 16 t .. 16 t + 15 of the tile.
+//   in:      16-byte loads where the input is aligned, elements from d on read as +0.0 and never from memory; step 0; threads 0 .. 7
+//            each squeeze one XOF block of the tile's 8 192 sign bits into LDS; step 1 (forward)
+//   h < 16:  register butterflies                               (index bits 0 .. 3)
+//   h < 1024: __shfl_xor between the lanes of a wave            (index bits 4 .. 9)
+//   h < 8192: ONE pass through LDS (rot_swz): written as held, read back with a thread holding elements p, p + 1 of every 1 024-element
+//            eighth, p = 2 t, a radix-8 register butterfly     (index bits 10 .. 12); k <= 10 does not touch the LDS image
+//   out:     step 3 when B <= T, then step 1 (inverse), one store; for B > T the scale and the inverse's signs belong to k_rotate_cols,
+//            and the inverse leaves the tile's sign words in `signs` for it.
+// Only stages h < min(B, T) run (k is uniform).  in == out is allowed: a workgroup reads and writes its own T elements only.
+__global__ void __launch_bounds__(ROT_TPB) k_rotate_tile(const QuantVec *__restrict__ vecs, u32 d, u32 dp, u32 k, u32 inverse, u32 *signs /* [vector][dp / 32] */) {
+    __shared__ __attribute__((aligned(16))) float s_x[ROT_T];
+    __shared__ u32 s_sign[ROT_T / 32];
+    const QuantVec *V = &vecs[blockIdx.y];
+    const float *in = V->in; float *out = V->out;
+    const u32 tid = threadIdx.x, t0 = blockIdx.x * ROT_T, e0 = t0 + 16 * tid;      // (dp < 2^28: no index wraps)
+    float v[16];
+    const bool al_in = ((size_t)in & 15) == 0, al_out = ((size_t)out & 15) == 0;
+#pragma unroll
+    for (u32 j = 0; j < 4; j++) {
+        const u32 e = e0 + 4 * j;
+        if (al_in && e + 4 <= d) {
+            const float4 q = *reinterpret_cast<const float4 *>(in + e);
+            v[4 * j] = q.x; v[4 * j + 1] = q.y; v[4 * j + 2] = q.z; v[4 * j + 3] = q.w;
+        } else {
+#pragma unroll
+            for (u32 i = 0; i < 4; i++) v[4 * j + i] = (e + i < d) ? in[e + i] : 0.0f;
+        }
+    }
+#pragma unroll
+    for (u32 i = 0; i < 16; i++) v[i] = rot_clamp(v[i]);
+    const u32 blk = blockIdx.x * (ROT_T / 1024) + tid;
+    if (tid < ROT_T / 1024 && (blk << 10) < dp) {      // (sign words past dp are never read for an element that is stored)
+        u64 st[25];
+        const u64 sw[4] = {V->seed[0], V->seed[1], V->seed[2], V->seed[3]};
+        shake256_rotate_block(st, sw, blk);
+#pragma unroll
+        for (u32 j = 0; j < 32; j++) s_sign[32 * tid + j] = quant_block_word(st, j);
+    }
+    __syncthreads();
+    if (!inverse) {
+        const u32 w = s_sign[tid >> 1] >> (16 * (tid & 1));
+#pragma unroll
+        for (u32 i = 0; i < 16; i++) v[i] = rot_flip(v[i], (w >> i) & 1);
+    } else if (k > ROT_T_LOG2 && tid < ROT_T / 32 && t0 + 32 * tid < dp) {
+        signs[(size_t)blockIdx.y * (dp >> 5) + (t0 >> 5) + tid] = s_sign[tid];
+    }
+    // index bits 0 .. 3: registers
+#pragma unroll
+    for (u32 s = 0; s < 4; s++) {
+        if (k > s) {
+#pragma unroll
+            for (u32 i = 0; i < 16; i++) if (!(i & (1u << s))) { const float a = v[i], b = v[i | (1u << s)]; v[i] = a + b; v[i | (1u << s)] = a - b; }
+        }
+    }
+    // index bits 4 .. 9: the lanes of a wave.  The lane whose bit is clear holds z_i and takes z_i + z_{i+h}; the other one z_i - z_{i+h}
+#pragma unroll
+    for (u32 s = 0; s < 6; s++) {
+        if (k > 4 + s) {
+            const bool hi = (tid >> s) & 1;
+#pragma unroll
+            for (u32 i = 0; i < 16; i++) { const float o = __shfl_xor(v[i], 1 << s); v[i] = hi ? o - v[i] : v[i] + o; }
+        }
+    }
+    const float c = rot_scale(k);
+    if (k <= 10) {
+        const u32 w = s_sign[tid >> 1] >> (16 * (tid & 1));
+#pragma unroll
+        for (u32 i = 0; i < 16; i++) { v[i] = v[i] * c; if (inverse) v[i] = rot_flip(v[i], (w >> i) & 1); }
+#pragma unroll
+        for (u32 j = 0; j < 4; j++) {
+            const u32 e = e0 + 4 * j;
+            if (al_out && e + 4 <= dp) {
+                *reinterpret_cast<float4 *>(out + e) = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+            } else {
+#pragma unroll
+                for (u32 i = 0; i < 4; i++) if (e + i < dp) out[e + i] = v[4 * j + i];
+            }
+        }
+        return;
+    }
+    // index bits 10 .. 12: through LDS
+#pragma unroll
+    for (u32 j = 0; j < 4; j++)
+        *reinterpret_cast<float4 *>(&s_x[16 * tid + 4 * ((j + (tid >> 1)) & 3)]) = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+    __syncthreads();
+    const u32 p = 2 * tid;
+    float x0[8], x1[8];
+#pragma unroll
+    for (u32 m = 0; m < 8; m++) {
+        const float2 q = *reinterpret_cast<const float2 *>(&s_x[rot_swz(1024 * m + p)]);
+        x0[m] = q.x; x1[m] = q.y;
+    }
+#pragma unroll
+    for (u32 s = 0; s < 3; s++) {
+        if (k > 10 + s) {
+#pragma unroll
+            for (u32 m = 0; m < 8; m++) if (!(m & (1u << s))) {
+                const float a0 = x0[m], b0 = x0[m | (1u << s)]; x0[m] = a0 + b0; x0[m | (1u << s)] = a0 - b0;
+                const float a1 = x1[m], b1 = x1[m | (1u << s)]; x1[m] = a1 + b1; x1[m | (1u << s)] = a1 - b1;
+            }
+        }
+    }
+    const bool last = k <= ROT_T_LOG2;      // (otherwise k_rotate_cols scales and signs)
+#pragma unroll
+    for (u32 m = 0; m < 8; m++) {
+        const u32 q = 1024 * m + p, e = t0 + q;
+        if (last) {
+            x0[m] = x0[m] * c; x1[m] = x1[m] * c;
+            if (inverse) { const u32 w = s_sign[q >> 5] >> (q & 31); x0[m] = rot_flip(x0[m], w & 1); x1[m] = rot_flip(x1[m], (w >> 1) & 1); }
+        }
+        if (e + 2 <= dp) {      // (dp is a multiple of B >= 2 048 here: a pair is inside or outside)
+            if (al_out) *reinterpret_cast<float2 *>(out + e) = make_float2(x0[m], x1[m]);
+            else { out[e] = x0[m]; out[e + 1] = x1[m]; }
+        }
+    }
+}
+// The stages h = T .. B / 2 of a block with B > T, in place on `out`: the block is a matrix of R = B / T rows of T elements and the
+// stages run along its columns.  A workgroup takes a strip of W = max(32, 8 192 / R) consecutive columns of all R rows (at most 512 x 32
+// floats = 64 KB of dynamic LDS at k = 22), so every row segment is a coalesced access of at least 128 bytes, and the lanes of a wave
+// run along the columns: 32 consecutive words of one row in every LDS access, no bank conflict at any stride of the rows.  The stages go
+// three at a time (a radix-8 register butterfly per thread and pass, the last pass what is left): the first pass reads `out`, the passes
+// in between go through LDS (s_rot, one barrier per pass; R <= 8 needs none), and the last one multiplies by c_B (step 3), flips the
+// signs of the inverse (step 1, from the words k_rotate_tile left in `signs`) and stores.  blockIdx.y = vector, blockIdx.x = block x strip.
+template <int NB>
+__device__ __forceinline__ void rot_col_pass(float *g, float *s_rot, u32 rl, u32 wl, u32 b, bool first, bool last, float c, const u32 *sg, u32 e_base) {
+    const u32 items = 1u << (rl + wl - NB);
+    for (u32 q = threadIdx.x; q < items; q += ROT_COL_TPB) {
+        const u32 col = q & ((1u << wl) - 1), grp = q >> wl;
+        const u32 r0 = ((grp >> b) << (b + NB)) | (grp & ((1u << b) - 1));
+        float x[1 << NB];
+#pragma unroll
+        for (u32 m = 0; m < (1u << NB); m++) {
+            const u32 r = r0 + (m << b);
+            x[m] = first ? g[((size_t)r << ROT_T_LOG2) + col] : s_rot[(r << wl) + col];
+        }
+#pragma unroll
+        for (u32 s = 0; s < (u32)NB; s++) {
+#pragma unroll
+            for (u32 m = 0; m < (1u << NB); m++) if (!(m & (1u << s))) { const float a0 = x[m], b0 = x[m | (1u << s)]; x[m] = a0 + b0; x[m | (1u << s)] = a0 - b0; }
+        }
+#pragma unroll
+        for (u32 m = 0; m < (1u << NB); m++) {
+            const u32 r = r0 + (m << b);
+            if (last) {
+                float y = x[m] * c;
+                if (sg) { const u32 e = e_base + (r << ROT_T_LOG2) + col; y = rot_flip(y, (sg[e >> 5] >> (e & 31)) & 1); }
+                g[((size_t)r << ROT_T_LOG2) + col] = y;
+            } else {
+                s_rot[(r << wl) + col] = x[m];
+            }
+        }
+    }
+}
+__global__ void __launch_bounds__(ROT_COL_TPB) k_rotate_cols(const QuantVec *__restrict__ vecs, u32 dp, u32 k, u32 inverse, const u32 *signs /* [vector][dp / 32] */) {
+    extern __shared__ float s_rot[];
+    const u32 rl = k - ROT_T_LOG2;                                   // log2 R: 1 .. 9
+    const u32 wl = rl <= 8 ? ROT_T_LOG2 - rl : 5;                    // log2 W
+    const u32 strips_l = ROT_T_LOG2 - wl;                            // log2 of the strips of a block
+    const u32 blk = blockIdx.x >> strips_l, strip = blockIdx.x & ((1u << strips_l) - 1);
+    const u32 e_base = (blk << k) + (strip << wl);                   // (< dp < 2^28)
+    if (e_base >= dp) return;                                        // (never: the grid is exact)
+    float *g = vecs[blockIdx.y].out + e_base;
+    const u32 *sg = inverse ? signs + (size_t)blockIdx.y * (dp >> 5) : nullptr;
+    const float c = rot_scale(k);
+    for (u32 b = 0; b < rl; b += 3) {
+        const u32 nb = rl - b < 3 ? rl - b : 3;
+        const bool first = b == 0, last = b + nb == rl;
+        if (nb == 3) rot_col_pass<3>(g, s_rot, rl, wl, b, first, last, c, sg, e_base);
+        else if (nb == 2) rot_col_pass<2>(g, s_rot, rl, wl, b, first, last, c, sg, e_base);
+        else rot_col_pass<1>(g, s_rot, rl, wl, b, first, last, c, sg, e_base);
+        if (!last) __syncthreads();
+    }
+}
+#endif
+
 // ================================================================ K3: Pedersen commit (fixed-base)
 // tables: radix-256 signed digits, tab[w][e] = (e+1) * 256^w * P, w < 32, e < 128  (affine niels; built by k_fixed_tab8 from the radix-16
 // table the per-element chains started with: half the mixed additions, the 393 KB of a base stay in L2)

@@ -2429,7 +2429,8 @@ static void quant_prob_host(const uint8_t *seed32, const float *in, u64 first, s
 // zeros), and its launch also enqueues the copy of what the kernels leave besides the vectors.
 static int seeded_vecs_run(int route, bool small, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, float *const *out,
                            const std::function<void(size_t)> &host, const std::function<void(Ctx &, const QuantVec *)> &launch,
-                           size_t stride = sizeof(QuantVec), const std::function<void(size_t, QuantVec *)> &fill = {}) {
+                           size_t stride = sizeof(QuantVec), const std::function<void(size_t, QuantVec *)> &fill = {}, size_t d_out = 0) {
+    if (d_out == 0) d_out = d;      // (rofl_rotate: an output of d_out >= d elements; a workspace slot holds the longer one, its padding zeroed)
     return guarded([&]() -> int {
         std::vector<char> dev_in(n_vec, 0), dev_out(n_vec, 0); bool all_host = true;
         for (size_t v = 0; v < n_vec; v++) { dev_in[v] = is_device_ptr(values[v]); dev_out[v] = is_device_ptr(out[v]); all_host &= !dev_in[v] && !dev_out[v]; }
@@ -2444,22 +2445,25 @@ static int seeded_vecs_run(int route, bool small, size_t n_vec, const uint8_t *s
         // a host input is uploaded into it, the kernel writes a host output into it (in place when both are host memory)
         size_t n_slot = 0;
         for (size_t v = 0; v < n_vec; v++) if (!dev_in[v] || !dev_out[v]) n_slot++;
-        float *ws = n_slot ? C.vals.as<float>(n_slot * d) : nullptr;
+        float *ws = n_slot ? C.vals.as<float>(n_slot * d_out) : nullptr;
         const size_t bytes = n_vec * stride;
         uint8_t *h = C.h_misc.as<uint8_t>(bytes), *dv = C.tmp_in.as<uint8_t>(bytes);
         BlindWipe wipe; wipe.h = h; wipe.dv = dv; wipe.n = seeds32 ? bytes : 0; wipe.s = C.stream;      // (the seeds: zeroed when the call returns or unwinds)
         auto hv = [&](size_t v) { return reinterpret_cast<QuantVec *>(h + v * stride); };
         size_t slot = 0;
         for (size_t v = 0; v < n_vec; v++) {
-            float *s = (!dev_in[v] || !dev_out[v]) ? ws + (slot++) * d : nullptr;
+            float *s = (!dev_in[v] || !dev_out[v]) ? ws + (slot++) * d_out : nullptr;
             hv(v)->in = dev_in[v] ? values[v] : s; hv(v)->out = dev_out[v] ? out[v] : s;
             if (seeds32) memcpy(hv(v)->seed, seeds32 + 32 * v, 32); else memset(hv(v)->seed, 0, 32);
             if (fill) fill(v, hv(v));
-            if (!dev_in[v]) C.up(s, values[v], 4 * d, C.stream);
+            if (!dev_in[v]) {
+                C.up(s, values[v], 4 * d, C.stream);
+                if (d_out > d) HIPCHK(hipMemsetAsync(s + d, 0, 4 * (d_out - d), C.stream));
+            }
         }
         HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, C.stream));
         launch(C, reinterpret_cast<const QuantVec *>(dv));
-        for (size_t v = 0; v < n_vec; v++) if (!dev_out[v]) C.down(out[v], hv(v)->out, 4 * d, C.stream);
+        for (size_t v = 0; v < n_vec; v++) if (!dev_out[v]) C.down(out[v], hv(v)->out, 4 * d_out, C.stream);
         C.sync();
         return ROFL_OK;
     });
@@ -2618,6 +2622,69 @@ static int clip_l2_impl(int route, size_t n_vec, const uint8_t *seeds32, const f
 int rofl_clip_l2(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq, size_t prove_range, unsigned fp_bits,
                  unsigned fp_frac, float *const *out, uint64_t *scale_out) {
     return clip_l2_impl(-1, n_vec, seeds32, values, d, max_sq, prove_range, fp_bits, fp_frac, out, scale_out);
+}
+// ---- Hadamard rotation (rofl_rotate: the definition is in the header, the element rules and the kernels in kernels.hpp) ----
+// Below this many padded elements in all, a call whose pointers are all host memory runs the network on the host: k passes of one core
+// over a block against the fixed cost of two staged copies, one or two launches and a synchronisation.  The measured crossover
+// (profiles/rotate.json); a constant, not a knob: both routes give the same bytes.
+constexpr size_t kRotateHostBelow = 32768;
+// one vector on the host: block by block through `buf` (B floats), so that out may be in
+static void rotate_host(const uint8_t *seed32, const float *in, size_t d, size_t dp, unsigned k, bool inverse, float *out, std::vector<float> &buf) {
+    const size_t B = (size_t)1 << k;
+    buf.resize(B);
+    float *z = buf.data();
+    const float c = rot_scale(k);
+    u64 sd[4], st[25], cur = ~0ULL; memcpy(sd, seed32, 32);
+    auto signs = [&](size_t e0) {      // step 1 over the block that starts at element e0
+        for (size_t i = 0; i < B; i++) {
+            const u64 e = e0 + i;
+            if ((e >> 10) != cur) { cur = e >> 10; shake256_rotate_block(st, sd, cur); }
+            z[i] = rot_flip(z[i], rot_sign_bit(st, (u32)e));
+        }
+    };
+    for (size_t e0 = 0; e0 < dp; e0 += B) {
+        for (size_t i = 0; i < B; i++) z[i] = rot_clamp(e0 + i < d ? in[e0 + i] : 0.0f);
+        if (!inverse) signs(e0);
+        for (size_t h = 1; h < B; h <<= 1)
+            for (size_t j = 0; j < B; j += 2 * h)
+                for (size_t i = j; i < j + h; i++) { const float a = z[i], b = z[i + h]; z[i] = a + b; z[i + h] = a - b; }
+        for (size_t i = 0; i < B; i++) z[i] = z[i] * c;
+        if (inverse) signs(e0);
+        memcpy(out + e0, z, 4 * B);
+    }
+}
+// route: as seeded_vecs_run (rofl_dbg_rotate_route)
+static int rotate_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, unsigned k, int inverse, float *const *out) {
+    if (k > ROT_MAX_LOG2 || (inverse != 0 && inverse != 1)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec == 0) return ROFL_OK;
+    if (!seeds32 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
+    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "padded vector length of 2^28 or more");
+    const size_t B = (size_t)1 << k, dp = (d + B - 1) / B * B;
+    if (dp >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "padded vector length of 2^28 or more");
+    if (inverse && dp != d) return fail(ROFL_BAD_PARAM, "the inverse takes whole blocks: d is not a multiple of 2^block_log2");
+    if (d == 0) return ROFL_OK;
+    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::vector<float> buf;
+    return seeded_vecs_run(route, n_vec * dp < kRotateHostBelow, n_vec, seeds32, values, d, out,
+        [&](size_t v) { rotate_host(seeds32 + 32 * v, values[v], d, dp, k, inverse != 0, out[v], buf); },
+        [&](Ctx &C, const QuantVec *vecs) {
+            const bool cols = k > ROT_T_LOG2;
+            // (the inverse of a block longer than a tile: the tile kernel leaves the sign words where the column kernel finds them)
+            u32 *signs = (cols && inverse) ? C.tmp_out.as<u32>(n_vec * (dp >> 5)) : nullptr;
+            ROFL_LAUNCH(k_rotate_tile, dim3((unsigned)((dp + ROT_T - 1) >> ROT_T_LOG2), (unsigned)n_vec), dim3(ROT_TPB), 0, C.stream,
+                        vecs, (u32)d, (u32)dp, (u32)k, (u32)inverse, signs);
+            if (cols) {
+                const unsigned rl = k - ROT_T_LOG2, wl = rl <= 8 ? ROT_T_LOG2 - rl : 5;      // as k_rotate_cols: R = 2^rl rows, strips of W = 2^wl columns
+                const size_t lds = rl > 3 ? ((size_t)4 << (rl + wl)) : 0;                    // (at most 64 KB)
+                ROFL_LAUNCH(k_rotate_cols, dim3((unsigned)((dp >> k) << (ROT_T_LOG2 - wl)), (unsigned)n_vec), dim3(ROT_COL_TPB), lds, C.stream,
+                            vecs, (u32)dp, (u32)k, (u32)inverse, (const u32 *)signs);
+            }
+        },
+        sizeof(QuantVec), {}, dp);
+}
+int rofl_rotate(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, unsigned block_log2, int inverse, float *const *out) {
+    return rotate_impl(-1, n_vec, seeds32, values, d, block_log2, inverse, out);
 }
 #include "protocol_calls.hpp"
 // what the calls above left in the lanes' staging buffers (described in the debug header): reads only; every device buffer is copied whole
@@ -3767,5 +3834,11 @@ int rofl_dbg_clip_l2_route(unsigned route, size_t n_vec, const uint8_t *seeds32,
     if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
     return clip_l2_impl((int)route, n_vec, seeds32, values, d, max_sq, prove_range, fp_bits, fp_frac, out, scale_out);
 }
+int rofl_dbg_rotate_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, unsigned block_log2, int inverse,
+                          float *const *out) {
+    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return rotate_impl((int)route, n_vec, seeds32, values, d, block_log2, inverse, out);
+}
+int rofl_dbg_rotate_tile_log2(void) { return ROT_T_LOG2; }
 
 }  // extern "C"

@@ -196,6 +196,14 @@ def _num_checked(d, check_percentage):
     return min(int(d), int(np.floor(np.float64(x) + 0.5)))
 
 
+# The order of a client's steps: rotate -> round -> clip -> noise -> legs.  The first one, the randomized Hadamard rotation
+# (range_proof_vec.rotate / rotate_vecs, rofl_rotate), changes the vector's LENGTH -- d elements become rotated_len(d, block_log2) -- so it
+# stands IN FRONT of the containers, not inside them: encrypt / encrypt_batch* take the rotated vector and a blinding vector of
+# rotated_len entries, and their parameter lists stay as they are.  Its seed is PUBLIC, one per round for every client and the server
+# (pedersen_ops.rotate_round_seed).  The rotation is orthonormal, so l2_range and l2_clip mean the same before and after it, and the sum
+# commutes with it: the server undoes it ONCE, range_proof_vec.unrotate(acc.extract(...), seed, block_log2, d).  The steps below are the
+# keywords of the containers and act on the rotated vector.
+#
 # The containers' quant_seed / quant_seeds (probabilistic quantization, range_proof_vec.quantize_probabilistic): with a seed the quantize
 # call stands where clip_f32_to_range_vec stands, and its output -- on the fixed-point grid, inside the clip range -- is the plaintext of
 # EVERY leg from there on, the witness digest included: the legs that take the un-clipped plaintext (params.rs:499) would otherwise round

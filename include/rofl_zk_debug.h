@@ -244,7 +244,8 @@ int rofl_dbg_host_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_pe
  * between two events on the lane's stream -- the A/B of profiles/dleq.json. */
 int rofl_dbg_var_mul2(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms);
 int rofl_dbg_var_mul_sum(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms);
-/* What the protocol calls above leave behind: the n >= 16 bytes at `needle` are searched for in the staging buffers of every initialised lane
+/* What the protocol calls above, the seeded update-preparation calls (rofl_quantize_prob, rofl_noise_binomial, rofl_clip_l2) and the term
+ * lists of rofl_blinding_vecs / rofl_acc_extract_opened_terms leave behind: the n >= 16 bytes at `needle` are searched for in the staging buffers of every initialised lane
  * of the calling thread's device -- the pinned buffers h_misc and h_misc2 and host copies of the device workspaces tmp_in, tmp_in2 and
  * tmp_out, each up to its capacity, under the lane's mutex and after a synchronisation of its stream.  *found = the number of buffers that
  * hold the needle (0 on a device no call has used yet).  Nothing is written to any of them: tests/test_gpu_lane_residue.py scans for

@@ -8,6 +8,7 @@ Reference signatures mirrored here (rofl_crypto/src/...):
 Scalars / points are numpy uint8 arrays of shape (d, 32); proofs are (n_proofs, proof_len).
 Errors that the reference reports as Err(..) (or panics) raise RoflError(code).
 """
+import contextlib
 import ctypes
 import hashlib
 import math
@@ -360,6 +361,69 @@ def _fp(fp):
     return int(b), int(f)
 
 
+def _float_vecs(list_of_values, out, call, out_len=None):
+    """what rofl_quantize_prob, rofl_noise_binomial, rofl_clip_l2 and rofl_rotate share: n float32 vectors of one length d in, n float32
+    destinations out, each in host or device memory, checked and marshalled; call(n, values, d, out) -> return code.  out_len(d) -> the
+    length of a destination where it is not d (rofl_rotate).  -> one (n, out_len) array for out=None, else the list of the destinations."""
+    n = len(list_of_values)
+    keep, vp, d = [], (ctypes.c_void_p * max(n, 1))(), None
+    for v, x in enumerate(list_of_values):
+        if _is_dev(x):
+            p, dv = _dev_arg(x, 4)
+            p = p.value
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+            p, dv = x.ctypes.data, x.size
+        keep.append(x)
+        if d is not None and dv != d:
+            raise ValueError("the vectors of one call have one length")
+        d, vp[v] = dv, p
+    d = d or 0
+    do = d if out_len is None else out_len(d)
+    if out is None:
+        res = np.empty((n, do), dtype=np.float32)
+        dst = [res[v] for v in range(n)]
+    else:
+        res = dst = list(out)
+        if len(dst) != n:
+            raise ValueError("one destination per vector")
+    op = (ctypes.c_void_p * max(n, 1))()
+    for v, o in enumerate(dst):
+        if _is_dev(o):
+            if not o.is_contiguous() or o.element_size() != 4 or o.numel() != do:
+                raise ValueError("a device destination is a contiguous float32 tensor of %d elements" % do)
+            op[v] = o.data_ptr()
+        else:
+            if not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous and o.flags.writeable and o.size == do):
+                raise ValueError("a host destination is a writable contiguous float32 array of %d elements" % do)
+            op[v] = o.ctypes.data
+    _check(call(_sz(n), vp, _sz(d), op))
+    return res
+
+
+@contextlib.contextmanager
+def _seed_buffer(seeds, n):
+    """one 32-byte seed per vector as the buffer a call reads them from, zeroed when the block is left; seeds=None -> None (a null pointer)"""
+    if seeds is None:
+        yield None
+        return
+    seeds = [bytes(s) for s in seeds]
+    if len(seeds) != n:
+        raise ValueError("one seed per vector")
+    if any(len(s) != 32 for s in seeds):
+        raise ValueError("a seed is 32 bytes")
+    sb = ctypes.create_string_buffer(b"".join(seeds), max(32 * n, 1))
+    try:
+        yield sb
+    finally:
+        ctypes.memset(sb, 0, ctypes.sizeof(sb))
+
+
+def _check_range_args(first, prove_range):
+    if int(first) < 0 or int(prove_range) < 1:
+        raise ValueError("first is not negative and prove_range is at least 1")
+
+
 class range_proof_vec:
     @staticmethod
     def next_pow2(v):
@@ -384,59 +448,10 @@ class range_proof_vec:
         or a float32 tensor on the GPU of d elements, which may be the input itself -- and the list is returned.
         A seed is a per-round SECRET of its client (pedersen_ops.quant_round_seed): whoever knows it knows which way every coordinate went."""
         fp = _fp(fp)
-        return range_proof_vec._seeded_vecs(list_of_values, prove_range, seeds, first, out, lambda n, sb, vp, first, d, op:
-                                            lib().rofl_quantize_prob(n, sb, vp, first, d, _sz(prove_range), *fp, op))
-
-    @staticmethod
-    def _seeded_vecs(list_of_values, prove_range, seeds, first, out, call, out_len=None):
-        """the arguments of rofl_quantize_prob and rofl_noise_binomial -- one seed, one input and one destination per vector, host or device
-        memory -- checked and marshalled; call(n, seeds, values, first, d, out) -> return code.  out_len(d) -> the length of a
-        destination where it is not d (rofl_rotate)."""
-        n, first = len(list_of_values), int(first)
-        seeds = [bytes(s) for s in seeds]
-        if len(seeds) != n:
-            raise ValueError("one seed per vector")
-        if any(len(s) != 32 for s in seeds):
-            raise ValueError("a seed is 32 bytes")
-        if first < 0 or int(prove_range) < 1:
-            raise ValueError("first is not negative and prove_range is at least 1")
-        keep, vp, d = [], (ctypes.c_void_p * max(n, 1))(), None
-        for v, x in enumerate(list_of_values):
-            if _is_dev(x):
-                p, dv = _dev_arg(x, 4)
-                p = p.value
-            else:
-                x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
-                p, dv = x.ctypes.data, x.size
-            keep.append(x)
-            if d is not None and dv != d:
-                raise ValueError("the vectors of one call have one length")
-            d, vp[v] = dv, p
-        d = d or 0
-        do = d if out_len is None else out_len(d)
-        if out is None:
-            res = np.empty((n, do), dtype=np.float32)
-            dst = [res[v] for v in range(n)]
-        else:
-            res = dst = list(out)
-            if len(dst) != n:
-                raise ValueError("one destination per vector")
-        op = (ctypes.c_void_p * max(n, 1))()
-        for v, o in enumerate(dst):
-            if _is_dev(o):
-                if not o.is_contiguous() or o.element_size() != 4 or o.numel() != do:
-                    raise ValueError("a device destination is a contiguous float32 tensor of %d elements" % do)
-                op[v] = o.data_ptr()
-            else:
-                if not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous and o.flags.writeable and o.size == do):
-                    raise ValueError("a host destination is a writable contiguous float32 array of %d elements" % do)
-                op[v] = o.ctypes.data
-        sb = ctypes.create_string_buffer(b"".join(seeds), max(32 * n, 1))
-        try:
-            _check(call(_sz(n), sb, vp, _sz(first), _sz(d), op))
-        finally:
-            ctypes.memset(sb, 0, ctypes.sizeof(sb))
-        return res
+        _check_range_args(first, prove_range)
+        with _seed_buffer(seeds, len(list_of_values)) as sb:
+            return _float_vecs(list_of_values, out, lambda n, vp, d, op:
+                               lib().rofl_quantize_prob(n, sb, vp, _sz(int(first)), d, _sz(prove_range), *fp, op))
 
     @staticmethod
     def quantize_probabilistic(values, prove_range, seed, first=0, fp=None):
@@ -458,8 +473,10 @@ class range_proof_vec:
         k, fp = int(k), _fp(fp)
         if k < 16 or k > 1 << 20 or k % 16:
             raise ValueError("k is a multiple of 16 from 16 to 2^20")
-        return range_proof_vec._seeded_vecs(list_of_values, prove_range, seeds, first, out, lambda n, sb, vp, first, d, op:
-                                            lib().rofl_noise_binomial(n, sb, vp, first, d, ctypes.c_uint32(k), _sz(prove_range), *fp, op))
+        _check_range_args(first, prove_range)
+        with _seed_buffer(seeds, len(list_of_values)) as sb:
+            return _float_vecs(list_of_values, out, lambda n, vp, d, op:
+                               lib().rofl_noise_binomial(n, sb, vp, _sz(int(first)), d, ctypes.c_uint32(k), _sz(prove_range), *fp, op))
 
     @staticmethod
     def add_binomial_noise(values, prove_range, seed, k, first=0, fp=None):
@@ -518,9 +535,10 @@ class range_proof_vec:
         if not 0 <= k <= 22:
             raise ValueError("block_log2 is 0 .. 22")
         seeds = [bytes(seed_or_seeds)] * n if isinstance(seed_or_seeds, (bytes, bytearray, memoryview)) else list(seed_or_seeds)
-        return range_proof_vec._seeded_vecs(list_of_values, 1, seeds, 0, out, lambda n_, sb, vp, first, d, op:
-                                            lib().rofl_rotate(n_, sb, vp, d, ctypes.c_uint(k), ctypes.c_int(1 if inverse else 0), op),
-                                            out_len=lambda d: range_proof_vec.rotated_len(d, k))
+        with _seed_buffer(seeds, n) as sb:
+            return _float_vecs(list_of_values, out, lambda n_, vp, d, op:
+                               lib().rofl_rotate(n_, sb, vp, d, ctypes.c_uint(k), ctypes.c_int(1 if inverse else 0), op),
+                               out_len=lambda d: range_proof_vec.rotated_len(d, k))
 
     @staticmethod
     def rotate(x, seed, block_log2):
@@ -718,35 +736,27 @@ class l2_range_proof_vec:
             raise ValueError("one max_sq per vector")
         if any(t < 0 or t >> 64 for t in ts):
             raise ValueError("max_sq is an unsigned 64-bit number of steps^2")
-        if seeds is not None:
-            seeds = list(seeds)
-            if len(seeds) != n:
-                raise ValueError("one seed (or None) per vector")
-            if all(s is None for s in seeds):
-                seeds = None
-
-        def call(idx, dst):      # ONE rofl_clip_l2 call over the vectors `idx`, all seeded or none
-            tb = (ctypes.c_uint64 * max(len(idx), 1))(*[ts[i] for i in idx])
-            sc = (ctypes.c_uint64 * max(len(idx), 1))()
-            sub = [seeds[i] for i in idx] if seeds is not None and idx and seeds[idx[0]] is not None else None
-            res = range_proof_vec._seeded_vecs([list_of_values[i] for i in idx], prove_range, sub if sub is not None else [bytes(32)] * len(idx), 0, dst,
-                                               lambda n_, sb, vp, first, d, op: lib().rofl_clip_l2(n_, sb if sub is not None else None, vp, d, tb, _sz(prove_range),
-                                                                                                    *fp, op, sc))
-            return res, [int(s) for s in sc[:len(idx)]]
-        if seeds is None or all(s is not None for s in seeds):
-            res, scales = call(list(range(n)), out)
-            return (res, scales) if with_scale else res
-        # a seeded and an unseeded call, each into the destinations of its own vectors
-        dst = list(out) if out is not None else None
+        seeds = [None] * n if seeds is None else list(seeds)
+        if len(seeds) != n:
+            raise ValueError("one seed (or None) per vector")
+        dst = None if out is None else list(out)
         if dst is not None and len(dst) != n:
             raise ValueError("one destination per vector")
-        res, scales = [None] * n, [None] * n
-        for idx in ([i for i, s in enumerate(seeds) if s is not None], [i for i, s in enumerate(seeds) if s is None]):
-            r, sc = call(idx, None if dst is None else [dst[i] for i in idx])
+        _check_range_args(0, prove_range)
+        has = [s is not None for s in seeds]
+        # all seeded or none: ONE call; else a seeded and an unseeded call, each into the destinations of its own vectors
+        groups = [[i for i in range(n) if has[i]], [i for i in range(n) if not has[i]]] if any(has) and not all(has) else [list(range(n))]
+        rows, scales = [None] * n, [None] * n
+        for idx in groups:
+            tb = (ctypes.c_uint64 * max(len(idx), 1))(*[ts[i] for i in idx])
+            sc = (ctypes.c_uint64 * max(len(idx), 1))()
+            with _seed_buffer([seeds[i] for i in idx] if idx and has[idx[0]] else None, len(idx)) as sb:
+                res = _float_vecs([list_of_values[i] for i in idx], None if dst is None else [dst[i] for i in idx], lambda n_, vp, d, op:
+                                  lib().rofl_clip_l2(n_, sb, vp, d, tb, _sz(prove_range), *fp, op, sc))
             for row, i in enumerate(idx):
-                res[i], scales[i] = r[row], sc[row]
-        if dst is None:
-            res = np.stack(res)
+                rows[i], scales[i] = res[row], int(sc[row])
+        if len(groups) > 1:
+            res = rows if dst is not None else np.stack(rows)
         return (res, scales) if with_scale else res
 
     @staticmethod

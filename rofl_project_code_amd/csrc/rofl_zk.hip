@@ -2406,286 +2406,7 @@ int rofl_rnd_scalar_vec(const uint8_t seed[32], size_t first, size_t d, uint8_t 
     volatile uint8_t *p = term.seed; for (int i = 0; i < 32; i++) p[i] = 0;
     return rc;
 }
-// ---- probabilistic quantization (rofl_quantize_prob: the definition is in the header, the rule and the kernel in kernels.hpp) ----
-// Below this many elements in all, a call whose pointers are all host memory runs the rule on the host: one Keccak-f per 32 elements on one
-// core against the fixed cost of two staged copies, a launch and a synchronisation.  The measured crossover (profiles/prob_quant.json,
-// DESIGN section 7); a constant, not a knob: both routes give the same bytes.
-constexpr size_t kQuantProbHostBelow = 8192;
-static void quant_prob_host(const uint8_t *seed32, const float *in, u64 first, size_t d, float mn, float mx, unsigned fp_frac, float *out) {
-    const u64 dom[2] = ROFL_QUANT_DOM;
-    u64 sd[4], st[25], cur = ~0ULL; memcpy(sd, seed32, 32);
-    for (size_t k = 0; k < d; k++) {
-        const u64 e = first + k;
-        if ((e >> 5) != cur) { cur = e >> 5; shake256_seeded_block(st, dom, sd, cur); }
-        out[k] = quant_prob_round(in[k], quant_block_word(st, (u32)(e & 31)), mn, mx, fp_frac);
-    }
-    volatile u64 *p = sd; for (int i = 0; i < 4; i++) p[i] = 0;
-    p = st; for (int i = 0; i < 25; i++) p[i] = 0;
-}
-// What rofl_quantize_prob and rofl_noise_binomial share once their parameters are checked.  route: -1 = by the pointers and the size
-// (`small`: an all-host call runs on the host), 0 = the host copy, 1 = the kernel.  host(v) runs the rule of vector v on the host;
-// launch(C, vecs) enqueues the kernel over the device copy of the descriptors on C.stream.  rofl_clip_l2 comes here too: its descriptors
-// (ClipVec) begin with a QuantVec and are `stride` bytes apart, fill(v, desc) writes what follows, its seeds32 may be null (no seeds:
-// zeros), and its launch also enqueues the copy of what the kernels leave besides the vectors.
-static int seeded_vecs_run(int route, bool small, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, float *const *out,
-                           const std::function<void(size_t)> &host, const std::function<void(Ctx &, const QuantVec *)> &launch,
-                           size_t stride = sizeof(QuantVec), const std::function<void(size_t, QuantVec *)> &fill = {}, size_t d_out = 0) {
-    if (d_out == 0) d_out = d;      // (rofl_rotate: an output of d_out >= d elements; a workspace slot holds the longer one, its padding zeroed)
-    return guarded([&]() -> int {
-        std::vector<char> dev_in(n_vec, 0), dev_out(n_vec, 0); bool all_host = true;
-        for (size_t v = 0; v < n_vec; v++) { dev_in[v] = is_device_ptr(values[v]); dev_out[v] = is_device_ptr(out[v]); all_host &= !dev_in[v] && !dev_out[v]; }
-        if (route == 0 && !all_host) return fail(ROFL_BAD_PARAM, "the host route takes host pointers only");
-        if (route == 0 || (route == -1 && all_host && small)) {
-            for (size_t v = 0; v < n_vec; v++) host(v);
-            return ROFL_OK;
-        }
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        // a device input is read and a device output written in place; a vector with a host pointer gets ONE slot of the lane's workspace:
-        // a host input is uploaded into it, the kernel writes a host output into it (in place when both are host memory)
-        size_t n_slot = 0;
-        for (size_t v = 0; v < n_vec; v++) if (!dev_in[v] || !dev_out[v]) n_slot++;
-        float *ws = n_slot ? C.vals.as<float>(n_slot * d_out) : nullptr;
-        const size_t bytes = n_vec * stride;
-        uint8_t *h = C.h_misc.as<uint8_t>(bytes), *dv = C.tmp_in.as<uint8_t>(bytes);
-        BlindWipe wipe; wipe.h = h; wipe.dv = dv; wipe.n = seeds32 ? bytes : 0; wipe.s = C.stream;      // (the seeds: zeroed when the call returns or unwinds)
-        auto hv = [&](size_t v) { return reinterpret_cast<QuantVec *>(h + v * stride); };
-        size_t slot = 0;
-        for (size_t v = 0; v < n_vec; v++) {
-            float *s = (!dev_in[v] || !dev_out[v]) ? ws + (slot++) * d_out : nullptr;
-            hv(v)->in = dev_in[v] ? values[v] : s; hv(v)->out = dev_out[v] ? out[v] : s;
-            if (seeds32) memcpy(hv(v)->seed, seeds32 + 32 * v, 32); else memset(hv(v)->seed, 0, 32);
-            if (fill) fill(v, hv(v));
-            if (!dev_in[v]) {
-                C.up(s, values[v], 4 * d, C.stream);
-                if (d_out > d) HIPCHK(hipMemsetAsync(s + d, 0, 4 * (d_out - d), C.stream));
-            }
-        }
-        HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, C.stream));
-        launch(C, reinterpret_cast<const QuantVec *>(dv));
-        for (size_t v = 0; v < n_vec; v++) if (!dev_out[v]) C.down(out[v], hv(v)->out, 4 * d_out, C.stream);
-        C.sync();
-        return ROFL_OK;
-    });
-}
-// route: as seeded_vecs_run (rofl_dbg_quantize_prob_route)
-static int quantize_prob_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
-                              size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
-    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec == 0) return ROFL_OK;
-    if (!seeds32 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
-    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
-    if (first > ((size_t)1 << 63) - d) return fail(ROFL_BAD_PARAM, "first + d exceeds 2^63");
-    if (d == 0) return ROFL_OK;
-    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
-    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
-    return seeded_vecs_run(route, n_vec * d < kQuantProbHostBelow, n_vec, seeds32, values, d, out,
-        [&](size_t v) { quant_prob_host(seeds32 + 32 * v, values[v], first, d, mn, mx, fp_frac, out[v]); },
-        [&](Ctx &C, const QuantVec *vecs) {
-            const size_t nblk = ((first + d + 31) >> 5) - (first >> 5);      // XOF blocks that hold an element of [first, first + d): <= 2^23 + 1
-            ROFL_LAUNCH(k_quantize_prob, dim3((unsigned)((nblk + QP_TPB - 1) / QP_TPB), (unsigned)n_vec), dim3(QP_TPB), 0, C.stream,
-                        vecs, (u64)first, (u32)d, mn, mx, (u32)fp_frac);
-        });
-}
-int rofl_quantize_prob(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, size_t prove_range,
-                       unsigned fp_bits, unsigned fp_frac, float *const *out) {
-    return quantize_prob_impl(-1, n_vec, seeds32, values, first, d, prove_range, fp_bits, fp_frac, out);
-}
-// ---- distributed noise (rofl_noise_binomial: the definition is in the header, the value rule and the kernel in kernels.hpp) ----
-// Below this many Keccak permutations in all (n_vec d W / 32), a call whose pointers are all host memory runs on the host: one core's
-// permutations against the fixed cost of two staged copies, a launch and a synchronisation.  The measured crossover
-// (profiles/binomial_noise.json); a constant, not a knob: both routes give the same bytes.
-constexpr u64 kNoiseHostBelowPerms = 256;
-// elements of a workgroup's group in k_noise_binomial: the words of a group, plus the 31 its first block can hold of a neighbour, fill
-// `passes` x 64 blocks -- one pass for W <= 32, W / 32 passes up to 32 (a wide element then wastes at most a few per cent of the lanes of
-// its group's last pass), and a single element whatever its width beyond that
-static u32 noise_epw(u32 W) {
-    const u32 passes = std::min(std::max(W / 32, 1u), 32u);
-    return std::min(std::max((2048 * passes - 31) / W, 1u), (u32)NB_EPW_MAX);
-}
-// noise integer of element index e: popcount of stream words e W .. e W + W - 1, minus k.  *cur / st: the block the caller holds squeezed.
-static int noise_host_element(const u64 sd[4], u64 e, u32 W, u64 *cur, u64 st[25]) {
-    const u64 dom[2] = ROFL_NOISE_DOM;
-    u32 cnt = 0;
-    for (u64 w = e * W; w < e * W + W; w++) {
-        if ((w >> 5) != *cur) { *cur = w >> 5; shake256_seeded_block(st, dom, sd, *cur); }
-        cnt += (u32)__builtin_popcount(quant_block_word(st, (u32)(w & 31)));
-    }
-    return (int)cnt - (int)(16 * W);
-}
-static void noise_host(const uint8_t *seed32, const float *in, u64 first, size_t d, u32 W, float mn, float mx, unsigned fp_frac, float *out) {
-    u64 sd[4], st[25], cur = ~0ULL; memcpy(sd, seed32, 32);
-    for (size_t i = 0; i < d; i++) out[i] = noise_apply(in[i], noise_host_element(sd, first + i, W, &cur, st), mn, mx, fp_frac);
-    volatile u64 *p = sd; for (int i = 0; i < 4; i++) p[i] = 0;
-    p = st; for (int i = 0; i < 25; i++) p[i] = 0;
-}
-static bool noise_k_ok(uint32_t k) { return k >= 16 && k <= (1u << 20) && k % 16 == 0; }
-// route: as seeded_vecs_run (rofl_dbg_noise_binomial_route)
-static int noise_binomial_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, uint32_t k,
-                               size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
-    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (!noise_k_ok(k)) return fail(ROFL_BAD_PARAM, "k is a multiple of 16 from 16 to 2^20");
-    if (n_vec == 0) return ROFL_OK;
-    if (!seeds32 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
-    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
-    const u32 W = k / 16;
-    if (first > ((size_t)1 << 63) - d || first + d > ((u64)1 << 63) / W) return fail(ROFL_BAD_PARAM, "(first + d) k / 16 exceeds 2^63");
-    if (d == 0) return ROFL_OK;
-    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
-    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
-    return seeded_vecs_run(route, (u64)n_vec * d * W < 32 * kNoiseHostBelowPerms, n_vec, seeds32, values, d, out,
-        [&](size_t v) { noise_host(seeds32 + 32 * v, values[v], first, d, W, mn, mx, fp_frac, out[v]); },
-        [&](Ctx &C, const QuantVec *vecs) {
-            const u32 epw = noise_epw(W), n_grp = (u32)((d + epw - 1) / epw);
-            ROFL_LAUNCH(k_noise_binomial, dim3(std::min(n_grp, 1u << 22), (unsigned)n_vec), dim3(NB_TPB), 0, C.stream,
-                        vecs, (u64)first, (u32)d, W, epw, n_grp, mn, mx, (u32)fp_frac);
-        });
-}
-int rofl_noise_binomial(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, uint32_t k, size_t prove_range,
-                        unsigned fp_bits, unsigned fp_frac, float *const *out) {
-    return noise_binomial_impl(-1, n_vec, seeds32, values, first, d, k, prove_range, fp_bits, fp_frac, out);
-}
-// ---- norm clipping (rofl_clip_l2: the definition is in the header, the rule, the search and the kernels in kernels.hpp) ----
-// Below this many elements in all, a call whose pointers are all host memory runs the rule on the host: two passes of one core over the
-// values (and one Keccak-f per 32 elements with seeds) against the fixed cost of two staged copies, two launches and a synchronisation.
-// The measured crossovers, the first size of the sweep at which the kernels win (profiles/l2_clip.json); constants,
-// not knobs: both routes give the same bytes.
-constexpr size_t kClipL2HostBelow = 16384, kClipL2HostBelowSeeded = 8192;
-constexpr u32 kClipL2Blocks = 8;      // k_clip_l2_sumsq, per vector: 2 048 threads stride over d, as the sums of the L2 proof (kL2SumBlocks)
-static u64 isqrt_u64(u64 x) {
-    u64 r = (u64)std::sqrt((long double)x);
-    while ((unsigned __int128)r * r > x) r--;
-    while ((unsigned __int128)(r + 1) * (r + 1) <= x) r++;
-    return r;
-}
-// Te of a seeded vector: (isqrt(T) - ceil(sqrt(d)))^2; false when the difference is negative
-static bool clip_l2_seeded_budget(u64 T, size_t d, u64 *te) {
-    const u64 rt = isqrt_u64(T), rd = d ? isqrt_u64(d - 1) + 1 : 0;
-    if (rt < rd) return false;
-    *te = (rt - rd) * (rt - rd); return true;
-}
-static void clip_l2_host(const uint8_t *seed32 /* or null */, const float *in, size_t d, u64 T, u64 te, float mn, float mx, unsigned fp_bits, unsigned fp_frac,
-                         float *out, uint64_t *scale) {
-    u64 S[3] = {0, 0, 0};
-    for (size_t i = 0; i < d; i++) {
-        float c; const u64 q = clip_l2_steps(in[i], mn, mx, fp_bits, fp_frac, &c);
-        u64 lo, hi; mul64_wide(q, q, &lo, &hi); u192_add(S, lo, hi, 0);
-    }
-    if (clip_l2_fits(S, T)) {
-        for (size_t i = 0; i < d; i++) out[i] = noise_apply(in[i], 0, mn, mx, fp_frac);
-        if (scale) *scale = 1ULL << 32;
-        return;
-    }
-    const u32 m = clip_l2_scale(S, te);
-    const u64 dom[2] = ROFL_CLIP_DOM;
-    u64 sd[4] = {0, 0, 0, 0}, st[25], cur = ~0ULL;
-    if (seed32) memcpy(sd, seed32, 32);
-    for (size_t i = 0; i < d; i++) {
-        if (seed32 && (i >> 5) != cur) { cur = i >> 5; shake256_seeded_block(st, dom, sd, cur); }
-        float c; const u64 q = clip_l2_steps(in[i], mn, mx, fp_bits, fp_frac, &c);
-        out[i] = clip_l2_round(q, m, seed32 != nullptr, seed32 ? quant_block_word(st, (u32)(i & 31)) : 0u, c, fp_frac);
-    }
-    if (scale) *scale = m;
-    volatile u64 *p = sd; for (int i = 0; i < 4; i++) p[i] = 0;
-    if (seed32) { p = st; for (int i = 0; i < 25; i++) p[i] = 0; }
-}
-// route: as seeded_vecs_run (rofl_dbg_clip_l2_route)
-static int clip_l2_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq, size_t prove_range,
-                        unsigned fp_bits, unsigned fp_frac, float *const *out, uint64_t *scale_out) {
-    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec == 0) return ROFL_OK;
-    if (!values || !out || !max_sq) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
-    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "vector length of 2^28 or more");
-    if (d == 0) return ROFL_OK;
-    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::vector<u64> te(max_sq, max_sq + n_vec);
-    if (seeds32) for (size_t v = 0; v < n_vec; v++)
-        if (!clip_l2_seeded_budget(max_sq[v], d, &te[v])) return fail(ROFL_BAD_PARAM, "max_sq leaves no room for the rounding of d elements: isqrt(max_sq) < ceil(sqrt(d))");
-    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
-    return seeded_vecs_run(route, n_vec * d < (seeds32 ? kClipL2HostBelowSeeded : kClipL2HostBelow), n_vec, seeds32, values, d, out,
-        [&](size_t v) { clip_l2_host(seeds32 ? seeds32 + 32 * v : nullptr, values[v], d, max_sq[v], te[v], mn, mx, fp_bits, fp_frac, out[v], scale_out ? scale_out + v : nullptr); },
-        [&](Ctx &C, const QuantVec *qv) {
-            const ClipVec *vecs = reinterpret_cast<const ClipVec *>(qv);
-            const u32 n_part = (u32)std::min<size_t>(kClipL2Blocks, (d + CL_TPB - 1) / CL_TPB);
-            u64 *part = C.tmp_out.as<u64>(n_vec * (3 * (size_t)n_part + 1)), *dscale = part + 3 * (size_t)n_part * n_vec;
-            ROFL_LAUNCH(k_clip_l2_sumsq, dim3(n_part, (unsigned)n_vec), dim3(CL_TPB), 0, C.stream, vecs, (u32)d, mn, mx, (u32)fp_bits, (u32)fp_frac, part);
-            const dim3 grid((unsigned)((d + 32 * QP_TPB - 1) / (32 * QP_TPB)), (unsigned)n_vec);
-            if (seeds32) ROFL_LAUNCH(k_clip_l2_apply_seeded, grid, dim3(QP_TPB), 0, C.stream, vecs, (u32)d, n_part, (const u64 *)part, mn, mx, (u32)fp_bits, (u32)fp_frac, dscale);
-            else ROFL_LAUNCH(k_clip_l2_apply, grid, dim3(QP_TPB), 0, C.stream, vecs, (u32)d, n_part, (const u64 *)part, mn, mx, (u32)fp_bits, (u32)fp_frac, dscale);
-            if (scale_out) C.down(scale_out, dscale, 8 * n_vec, C.stream);
-        },
-        sizeof(ClipVec), [&](size_t v, QuantVec *qv) { ClipVec *cv = reinterpret_cast<ClipVec *>(qv); cv->max_sq = max_sq[v]; cv->te = te[v]; });
-}
-int rofl_clip_l2(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq, size_t prove_range, unsigned fp_bits,
-                 unsigned fp_frac, float *const *out, uint64_t *scale_out) {
-    return clip_l2_impl(-1, n_vec, seeds32, values, d, max_sq, prove_range, fp_bits, fp_frac, out, scale_out);
-}
-// ---- Hadamard rotation (rofl_rotate: the definition is in the header, the element rules and the kernels in kernels.hpp) ----
-// Below this many padded elements in all, a call whose pointers are all host memory runs the network on the host: k passes of one core
-// over a block against the fixed cost of two staged copies, one or two launches and a synchronisation.  The measured crossover
-// (profiles/rotate.json); a constant, not a knob: both routes give the same bytes.
-constexpr size_t kRotateHostBelow = 32768;
-// one vector on the host: block by block through `buf` (B floats), so that out may be in
-static void rotate_host(const uint8_t *seed32, const float *in, size_t d, size_t dp, unsigned k, bool inverse, float *out, std::vector<float> &buf) {
-    const size_t B = (size_t)1 << k;
-    buf.resize(B);
-    float *z = buf.data();
-    const float c = rot_scale(k);
-    u64 sd[4], st[25], cur = ~0ULL; memcpy(sd, seed32, 32);
-    auto signs = [&](size_t e0) {      // step 1 over the block that starts at element e0
-        for (size_t i = 0; i < B; i++) {
-            const u64 e = e0 + i;
-            if ((e >> 10) != cur) { cur = e >> 10; shake256_rotate_block(st, sd, cur); }
-            z[i] = rot_flip(z[i], rot_sign_bit(st, (u32)e));
-        }
-    };
-    for (size_t e0 = 0; e0 < dp; e0 += B) {
-        for (size_t i = 0; i < B; i++) z[i] = rot_clamp(e0 + i < d ? in[e0 + i] : 0.0f);
-        if (!inverse) signs(e0);
-        for (size_t h = 1; h < B; h <<= 1)
-            for (size_t j = 0; j < B; j += 2 * h)
-                for (size_t i = j; i < j + h; i++) { const float a = z[i], b = z[i + h]; z[i] = a + b; z[i + h] = a - b; }
-        for (size_t i = 0; i < B; i++) z[i] = z[i] * c;
-        if (inverse) signs(e0);
-        memcpy(out + e0, z, 4 * B);
-    }
-}
-// route: as seeded_vecs_run (rofl_dbg_rotate_route)
-static int rotate_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, unsigned k, int inverse, float *const *out) {
-    if (k > ROT_MAX_LOG2 || (inverse != 0 && inverse != 1)) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec == 0) return ROFL_OK;
-    if (!seeds32 || !values || !out) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n_vec > kMaxBatchMembers) return fail(ROFL_BAD_PARAM, "more than 65 535 vectors in one call");
-    if (d >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "padded vector length of 2^28 or more");
-    const size_t B = (size_t)1 << k, dp = (d + B - 1) / B * B;
-    if (dp >= ((size_t)1 << 28)) return fail(ROFL_BAD_PARAM, "padded vector length of 2^28 or more");
-    if (inverse && dp != d) return fail(ROFL_BAD_PARAM, "the inverse takes whole blocks: d is not a multiple of 2^block_log2");
-    if (d == 0) return ROFL_OK;
-    for (size_t v = 0; v < n_vec; v++) if (!values[v] || !out[v]) return fail(ROFL_BAD_PARAM, "bad parameter");
-    std::vector<float> buf;
-    return seeded_vecs_run(route, n_vec * dp < kRotateHostBelow, n_vec, seeds32, values, d, out,
-        [&](size_t v) { rotate_host(seeds32 + 32 * v, values[v], d, dp, k, inverse != 0, out[v], buf); },
-        [&](Ctx &C, const QuantVec *vecs) {
-            const bool cols = k > ROT_T_LOG2;
-            // (the inverse of a block longer than a tile: the tile kernel leaves the sign words where the column kernel finds them)
-            u32 *signs = (cols && inverse) ? C.tmp_out.as<u32>(n_vec * (dp >> 5)) : nullptr;
-            ROFL_LAUNCH(k_rotate_tile, dim3((unsigned)((dp + ROT_T - 1) >> ROT_T_LOG2), (unsigned)n_vec), dim3(ROT_TPB), 0, C.stream,
-                        vecs, (u32)d, (u32)dp, (u32)k, (u32)inverse, signs);
-            if (cols) {
-                const unsigned rl = k - ROT_T_LOG2, wl = rl <= 8 ? ROT_T_LOG2 - rl : 5;      // as k_rotate_cols: R = 2^rl rows, strips of W = 2^wl columns
-                const size_t lds = rl > 3 ? ((size_t)4 << (rl + wl)) : 0;                    // (at most 64 KB)
-                ROFL_LAUNCH(k_rotate_cols, dim3((unsigned)((dp >> k) << (ROT_T_LOG2 - wl)), (unsigned)n_vec), dim3(ROT_COL_TPB), lds, C.stream,
-                            vecs, (u32)dp, (u32)k, (u32)inverse, (const u32 *)signs);
-            }
-        },
-        sizeof(QuantVec), {}, dp);
-}
-int rofl_rotate(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, unsigned block_log2, int inverse, float *const *out) {
-    return rotate_impl(-1, n_vec, seeds32, values, d, block_log2, inverse, out);
-}
+#include "prepare_calls.hpp"
 #include "protocol_calls.hpp"
 // what the calls above left in the lanes' staging buffers (described in the debug header): reads only; every device buffer is copied whole
 int rofl_dbg_lane_scan(const uint8_t *needle, size_t n, int *found) {
@@ -3758,87 +3479,5 @@ int rofl_dbg_host_blind(const uint8_t seed[32], uint64_t idx, uint8_t out[32]) {
     u64 sd[4]; memcpy(sd, seed, 32); u64 st[25]; shake256_seeded_block(st, dom, sd, idx >> 1);
     sc_tobytes(out, xof_block_scalar(st, (int)(idx & 1))); return 0;
 }
-int rofl_dbg_host_quant(const uint8_t seed[32], uint64_t idx, uint32_t *word_out) {
-    if (!seed || !word_out) return ROFL_BAD_PARAM;
-    const u64 dom[2] = ROFL_QUANT_DOM;
-    u64 sd[4]; memcpy(sd, seed, 32); u64 st[25]; shake256_seeded_block(st, dom, sd, idx >> 5);
-    *word_out = quant_block_word(st, (u32)(idx & 31)); return 0;
-}
-int rofl_dbg_quant_round(unsigned site, size_t n, const float *values, const uint32_t *words, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *out) {
-    if (site > 1 || !valid_fp(fp_bits, fp_frac) || prove_range == 0 || n > (1u << 20) || (n && (!values || !words || !out))) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n == 0) return ROFL_OK;
-    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
-    if (site == 0) { for (size_t i = 0; i < n; i++) out[i] = quant_prob_round(values[i], words[i], mn, mx, fp_frac); return ROFL_OK; }
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        float *dv = C.vals.as<float>(n), *dout = C.tmp_out.as<float>(n);
-        u32 *dw = C.tmp_in.as<u32>(n);
-        C.up(dv, values, 4 * n, C.stream); C.up(dw, words, 4 * n, C.stream);
-        ROFL_LAUNCH(k_dbg_quant_round, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (const float *)dv, (const u32 *)dw, mn, mx, (u32)fp_frac, dout);
-        C.down(out, dout, 4 * n, C.stream);
-        C.sync();
-        return ROFL_OK;
-    });
-}
-int rofl_dbg_quantize_prob_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
-                                 size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
-    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
-    return quantize_prob_impl((int)route, n_vec, seeds32, values, first, d, prove_range, fp_bits, fp_frac, out);
-}
-int rofl_dbg_host_noise(const uint8_t seed[32], uint64_t e, uint32_t k, int32_t *n_out) {
-    if (!seed || !n_out || !noise_k_ok(k) || e >= ((u64)1 << 63) / (k / 16)) return ROFL_BAD_PARAM;
-    u64 sd[4], st[25], cur = ~0ULL; memcpy(sd, seed, 32);
-    *n_out = noise_host_element(sd, e, k / 16, &cur, st); return 0;
-}
-int rofl_dbg_noise_apply(unsigned site, size_t n, const float *values, const int32_t *noise_i32, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *out) {
-    if (site > 1 || !valid_fp(fp_bits, fp_frac) || prove_range == 0 || n > (1u << 20) || (n && (!values || !noise_i32 || !out))) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n == 0) return ROFL_OK;
-    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
-    if (site == 0) { for (size_t i = 0; i < n; i++) out[i] = noise_apply(values[i], noise_i32[i], mn, mx, fp_frac); return ROFL_OK; }
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        float *dv = C.vals.as<float>(n), *dout = C.tmp_out.as<float>(n);
-        int *dn = C.tmp_in.as<int>(n);
-        C.up(dv, values, 4 * n, C.stream); C.up(dn, noise_i32, 4 * n, C.stream);
-        ROFL_LAUNCH(k_dbg_noise_apply, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (const float *)dv, (const int *)dn, mn, mx, (u32)fp_frac, dout);
-        C.down(out, dout, 4 * n, C.stream);
-        C.sync();
-        return ROFL_OK;
-    });
-}
-int rofl_dbg_noise_binomial_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
-                                  uint32_t k, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
-    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
-    return noise_binomial_impl((int)route, n_vec, seeds32, values, first, d, k, prove_range, fp_bits, fp_frac, out);
-}
-int rofl_dbg_clip_l2_round(unsigned site, size_t n, const uint64_t *q, uint32_t m, const uint32_t *words, unsigned fp_frac, float *out) {
-    if (site > 1 || fp_frac > 12 || n > (1u << 20) || (n && (!q || !out))) return fail(ROFL_BAD_PARAM, "bad parameter");
-    if (n == 0) return ROFL_OK;
-    if (site == 0) { for (size_t i = 0; i < n; i++) out[i] = clip_l2_round(q[i], m, words != nullptr, words ? words[i] : 0u, 1.0f, fp_frac); return ROFL_OK; }
-    return guarded([&]() -> int {
-        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
-        C.init();
-        u64 *dq = C.vals.as<u64>(n); float *dout = C.tmp_out.as<float>(n);
-        u32 *dw = words ? C.tmp_in.as<u32>(n) : nullptr;
-        C.up(dq, q, 8 * n, C.stream); if (words) C.up(dw, words, 4 * n, C.stream);
-        ROFL_LAUNCH(k_dbg_clip_l2_round, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (const u64 *)dq, (u32)m, (const u32 *)dw, (u32)fp_frac, dout);
-        C.down(out, dout, 4 * n, C.stream);
-        C.sync();
-        return ROFL_OK;
-    });
-}
-int rofl_dbg_clip_l2_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq,
-                           size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out, uint64_t *scale_out) {
-    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
-    return clip_l2_impl((int)route, n_vec, seeds32, values, d, max_sq, prove_range, fp_bits, fp_frac, out, scale_out);
-}
-int rofl_dbg_rotate_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, unsigned block_log2, int inverse,
-                          float *const *out) {
-    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
-    return rotate_impl((int)route, n_vec, seeds32, values, d, block_log2, inverse, out);
-}
-int rofl_dbg_rotate_tile_log2(void) { return ROT_T_LOG2; }
 
 }  // extern "C"

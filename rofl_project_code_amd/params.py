@@ -236,60 +236,47 @@ def _clip_args(l2_clip, clip_seed):
     return l2_clip is not None
 
 
-def _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed=None, noise_k=None, l2_clip=None, clip_seed=None):
-    """-> (plaintext, clipped) of one client"""
-    noisy, clipping = _noise_args(noise_seed, noise_k), _clip_args(l2_clip, clip_seed)
-    if quant_seed is None and not noisy and not clipping:
-        return x, range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp)
-    q = x if quant_seed is None else range_proof_vec.quantize_probabilistic(x, prove_range, quant_seed, fp=fp).reshape(x.shape)
-    if clipping:
-        q = l2_range_proof_vec.clip_l2(q, prove_range, l2_clip, clip_seed, fp=fp).reshape(x.shape)
-    if noisy:
-        q = range_proof_vec.add_binomial_noise(q, prove_range, noise_seed, noise_k, fp=fp).reshape(x.shape)
-    return q, q
+def _apply_where(xs, clipped, marks, call):
+    """ONE call(vectors, marks) -> rows over the clients whose mark is not None; a row becomes its client's plaintext and clipped vector"""
+    idx = [i for i, m in enumerate(marks) if m is not None]
+    if idx:
+        rows = call([xs[i] for i in idx], [marks[i] for i in idx])
+        for row, i in zip(rows, idx):
+            xs[i] = clipped[i] = row.reshape(xs[i].shape)
 
 
 def _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds=None, noise_k=None, l2_clip=None, clip_seeds=None):
     """-> (plaintexts, clipped) of the clients of encrypt_batch: ONE quantize call for all clients that have a quant seed, then ONE clip
-    call for all clients where there is an l2_clip, then ONE noise call for all clients that have a noise seed"""
+    call for all clients where there is an l2_clip, then ONE noise call for all clients that have a noise seed.  Every step takes the
+    vector the step before it left -- the rounded one where there is one, else the raw one: the clip and the noise call clip and round to
+    nearest themselves -- and a client that no step touched keeps its raw vector, clipped like clip_f32_to_range_vec."""
     noisy, clipping = _noise_args(noise_seeds, noise_k), _clip_args(l2_clip, clip_seeds)
-    if noisy or clipping:
-        noise_seeds = list(noise_seeds) if noisy else [None] * len(xs)
-        if len(noise_seeds) != len(xs):
-            raise ValueError("one noise seed (or None) per client")
-        if any(x.size != xs[0].size for x in xs):
-            raise ValueError("the clients of a batch have one vector length")
-        xs, clipped = _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp)
-        xs, clipped = list(xs), list(clipped)
-        if clipping and xs:
-            # (the input is the rounded vector where there is one, else the raw one: the clip call clips and rounds to nearest itself)
-            q = l2_range_proof_vec.clip_l2_vecs(xs, prove_range, l2_clip, clip_seeds, fp=fp)
-            for i in range(len(xs)):
-                xs[i] = clipped[i] = q[i].reshape(xs[i].shape)
-        with_seed = [i for i, s in enumerate(noise_seeds) if s is not None]
-        if with_seed:
-            # (the input is the rounded vector where there is one, else the raw one: the noise call clips and rounds to nearest itself)
-            q = range_proof_vec.add_binomial_noise_vecs([xs[i] for i in with_seed], prove_range, [noise_seeds[i] for i in with_seed], noise_k, fp=fp)
-            for row, i in enumerate(with_seed):
-                xs[i] = clipped[i] = q[row].reshape(xs[i].shape)
-        return xs, clipped
-    if quant_seeds is None:
+    if quant_seeds is None and not noisy and not clipping:
         return xs, [range_proof_vec.clip_f32_to_range_vec(x, prove_range, fp=fp) for x in xs]
-    quant_seeds = list(quant_seeds)
-    if len(quant_seeds) != len(xs):
-        raise ValueError("one quant seed (or None) per client")
+    n = len(xs)
+    noise_seeds, quant_seeds = [None] * n if noise_seeds is None else list(noise_seeds), [None] * n if quant_seeds is None else list(quant_seeds)
+    for what, seeds in (("noise", noise_seeds), ("quant", quant_seeds)):
+        if len(seeds) != n:
+            raise ValueError("one %s seed (or None) per client" % what)
     if any(x.size != xs[0].size for x in xs):
         raise ValueError("the clients of a batch have one vector length")
-    xs, clipped = list(xs), [None] * len(xs)
-    with_seed = [i for i, s in enumerate(quant_seeds) if s is not None]
-    if with_seed:
-        q = range_proof_vec.quantize_probabilistic_vecs([xs[i] for i in with_seed], prove_range, [quant_seeds[i] for i in with_seed], fp=fp)
-        for row, i in enumerate(with_seed):
-            xs[i] = clipped[i] = q[row].reshape(xs[i].shape)
-    for i, s in enumerate(quant_seeds):
-        if s is None:
+    xs, clipped = list(xs), [None] * n
+    _apply_where(xs, clipped, quant_seeds, lambda vs, seeds: range_proof_vec.quantize_probabilistic_vecs(vs, prove_range, seeds, fp=fp))
+    if clipping and xs:      # (every client: the clip call tells the seeded from the unseeded itself)
+        for i, row in enumerate(l2_range_proof_vec.clip_l2_vecs(xs, prove_range, l2_clip, clip_seeds, fp=fp)):
+            xs[i] = clipped[i] = row.reshape(xs[i].shape)
+    _apply_where(xs, clipped, noise_seeds, lambda vs, seeds: range_proof_vec.add_binomial_noise_vecs(vs, prove_range, seeds, noise_k, fp=fp))
+    for i in range(n):
+        if clipped[i] is None:
             clipped[i] = range_proof_vec.clip_f32_to_range_vec(xs[i], prove_range, fp=fp)
     return xs, clipped
+
+
+def _clip_or_quantize(x, prove_range, quant_seed, fp, noise_seed=None, noise_k=None, l2_clip=None, clip_seed=None):
+    """-> (plaintext, clipped) of one client: a batch of one"""
+    one = lambda a: None if a is None else [a]
+    xs, clipped = _clip_or_quantize_batch([x], prove_range, one(quant_seed), fp, one(noise_seed), noise_k, one(l2_clip), one(clip_seed))
+    return xs[0], clipped[0]
 
 
 class _HostLegs:

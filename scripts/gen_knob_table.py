@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rofl_project_code_amd", "csrc")
 SRC = os.path.join(CSRC, "host_rt.hpp")                                               # the KNOBS registry
-HOST_SOURCES = ["rofl_zk.hip", "protocol_calls.hpp", "host_rt.hpp", "host_msm.hpp", "host_prover.hpp", "host_verifier.hpp"]      # everything that may call knob()
+HOST_SOURCES = ["rofl_zk.hip", "prepare_calls.hpp", "protocol_calls.hpp", "host_rt.hpp", "host_msm.hpp", "host_prover.hpp", "host_verifier.hpp"]      # everything that may call knob()
 
 
 def knobs():

@@ -1,17 +1,27 @@
-"""What a protocol call leaves in its lane's staging buffers (rofl_dbg_lane_scan: pinned h_misc / h_misc2, device tmp_in / tmp_in2 /
-tmp_out, on every lane of the device).  Each case makes ONE call and then scans: no secret of the call may be found in any buffer, and one
-public by-product of the same call must be -- the positive control, which shows that the scan finds what is there.  Keys and payloads come
-from a seeded generator, every needle is at least 16 random bytes: a chance match has probability 2^-128.  The inputs a case needs from
-another primitive come from the Python models, so that nothing but the call under test has put them into a lane."""
+"""What a protocol call or an update-preparation call leaves in its lane's staging buffers (rofl_dbg_lane_scan: pinned h_misc / h_misc2,
+device tmp_in / tmp_in2 / tmp_out, on every lane of the device).  Each case makes ONE call and then scans: no secret of the call may be
+found in any buffer, and one public by-product of the same call must be -- the positive control, which shows that the scan finds what is
+there.  Keys and payloads come from a seeded generator, every needle is at least 16 random bytes: a chance match has probability 2^-128.
+The inputs a case needs from another primitive come from the Python models, so that nothing but the call under test has put them into a
+lane.
+
+The last five cases hold the two drivers that wipe with BlindWipe to the same promise: the preparation calls' driver (prepare_calls.hpp:
+quantization, noise and clipping seeds) and blind_combine_launch (the term seeds of rofl_blinding_vecs and of an opening given as terms).
+The quantization, noise and blinding calls leave no public by-product of 16 bytes in a scanned buffer (their vectors go through the
+lane's value and byte workspaces, which the scan does not read): for them the first test of this module is the control that the scan
+finds what is there.  The clipping call has one, its two scales, adjacent 64-bit words in tmp_out (8 of the 16 bytes are the scales' zero
+high halves: a chance match still needs both 32-bit scales side by side)."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import aead_model as A
+import blind_model as B
 import dh_model as D
 import dleq_model as Q
 import feldman_model as F
+import orc
 import shamir_model as S
 
 pytestmark = pytest.mark.gpu
@@ -169,3 +179,76 @@ def test_dleq_verify_with_shared_out(R):
     verdicts, shared = R.dleq.verify(_pk(sk), peers, ctxs, reveals, proofs)      # (the wrapper always asks for shared_out32)
     assert not verdicts.any() and shared.any(axis=1).all()
     _check(R, [("shared %d" % i, shared[i]) for i in range(2)])
+
+
+# ---- the calls that wipe with BlindWipe: the preparation calls' driver and blind_combine_launch ----
+PREP_FP, PREP_RANGE, PREP_D = (16, 7), 8, 33      # d = 33: two XOF blocks of 32 rounding words
+
+
+def _prep_case(salt):
+    """2 vectors of 33 values inside the clip range of (8, fp16.7), with their seeds: (seeds, values, outs, the leading arguments of a route-1 call)"""
+    rng = np.random.default_rng(20270350 + salt)
+    seeds = _rows(rng, 2)
+    vals = [rng.uniform(-0.9, 0.9, PREP_D).astype(np.float32) for _ in range(2)]
+    outs = [np.full(PREP_D, np.nan, np.float32) for _ in range(2)]
+    arr = lambda xs: (ctypes.c_void_p * 2)(*[x.ctypes.data for x in xs])
+    return seeds, vals, outs, [ctypes.c_uint(1), ctypes.c_size_t(2), seeds.tobytes(), arr(vals)], arr(outs)
+
+
+def _prep_tail(outs_arr):
+    return [ctypes.c_size_t(PREP_RANGE), ctypes.c_uint(PREP_FP[0]), ctypes.c_uint(PREP_FP[1]), outs_arr]
+
+
+def _seed_secrets(seeds):
+    return [("seed %d" % i, seeds[i]) for i in range(len(seeds))]
+
+
+def test_quantize_prob_kernel_route(R):
+    seeds, vals, outs, head, oa = _prep_case(0)
+    assert R.lib().rofl_dbg_quantize_prob_route(*head, ctypes.c_size_t(0), ctypes.c_size_t(PREP_D), *_prep_tail(oa)) == 0
+    assert not np.isnan(np.stack(outs)).any()
+    _check(R, _seed_secrets(seeds))
+
+
+def test_noise_binomial_kernel_route(R):
+    seeds, vals, outs, head, oa = _prep_case(1)
+    assert R.lib().rofl_dbg_noise_binomial_route(*head, ctypes.c_size_t(0), ctypes.c_size_t(PREP_D), ctypes.c_uint32(16), *_prep_tail(oa)) == 0
+    assert not np.isnan(np.stack(outs)).any()
+    _check(R, _seed_secrets(seeds))
+
+
+def test_clip_l2_seeded_kernel_route(R):
+    """max_sq = 100 steps^2: isqrt = 10 >= ceil(sqrt(33)) = 6, and far below the sum of squares of either vector, so both are scaled"""
+    seeds, vals, outs, head, oa = _prep_case(2)
+    max_sq, scale = (ctypes.c_uint64 * 2)(100, 100), (ctypes.c_uint64 * 2)()
+    assert R.lib().rofl_dbg_clip_l2_route(*head, ctypes.c_size_t(PREP_D), max_sq, *_prep_tail(oa), scale) == 0
+    assert not np.isnan(np.stack(outs)).any() and all(0 < m < 1 << 32 for m in scale)
+    _check(R, _seed_secrets(seeds), public=bytes(scale))
+
+
+def test_blinding_vecs(R):
+    rng = np.random.default_rng(20270360)
+    seeds = _rows(rng, 4)
+    terms = [[(seeds[0], 1), (seeds[1], -1)], [(seeds[2], -1), (seeds[3], 1)]]
+    got = R.pedersen_ops.blinding_vecs(terms, 3)
+    assert got.tobytes() == b"".join(B.combine(t, 3).tobytes() for t in terms)
+    _check(R, _seed_secrets(seeds))
+
+
+def test_extract_opened_terms(R):
+    """one client's record of the oracle under the blinding the two terms expand to: the extraction expands them on the device"""
+    rng = np.random.default_rng(20270361)
+    seeds = _rows(rng, 2)
+    terms = [(seeds[0], 1), (seeds[1], -1)]
+    ks = (5, -3, 0)
+    x = np.stack([orc.f32_to_scalar(k / 128.0, *FP)[1] for k in ks])
+    r = B.combine(terms, 3)
+    rec = np.ascontiguousarray(np.concatenate([orc.commit_vec(x, r), orc.commit_vec(r, None)], axis=1))
+    h = R.api.accumulator.create(3)
+    try:
+        R.api.accumulator.add(h, [rec.ctypes.data], [3], 64)
+        got, bad = R.api.accumulator.extract_opened_terms(h, 3, terms, 1 << 15, 16, FP)
+    finally:
+        R.api.accumulator.destroy(h)
+    assert bad is None and got.tobytes() == np.array([k / 128.0 for k in ks], np.float32).tobytes()
+    _check(R, _seed_secrets(seeds))

@@ -202,7 +202,7 @@ def test_knob_registry_is_complete_and_documented():
     names = [k[0] for k in g.knobs()]
     assert len(names) == len(set(names)) >= 40
     assert set(g.reads()) == set(names)
-    for f in ("rofl_zk.hip", "protocol_calls.hpp", "host_rt.hpp", "host_msm.hpp", "host_prover.hpp", "host_verifier.hpp", "kernels.hpp", "host51.hpp", "host51x8.hpp",
+    for f in ("rofl_zk.hip", "prepare_calls.hpp", "protocol_calls.hpp", "host_rt.hpp", "host_msm.hpp", "host_prover.hpp", "host_verifier.hpp", "kernels.hpp", "host51.hpp", "host51x8.hpp",
               "keccak.hpp", "fe32.hpp", "fe26.hpp", "quad26.hpp", "wire.hpp"):
         src = open(os.path.join(ROOT, "rofl_project_code_amd", "csrc", f)).read()
         assert len(re.findall(r"\bgetenv\(", src)) == (1 if f == "host_rt.hpp" else 0), f      # the one inside knob()

@@ -115,6 +115,22 @@ int rofl_dbg_fd_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out);
  *    8 sc_from_wide(lo = a, hi = b)  9 sc_from_wide_mont(lo = a, hi = b)
  *   10 sc_mac_wide over the in[264 i + 256] <= 16 pairs (scalar 2k, scalar 2k + 1), then ONE sc_redc_wide     11 sc_invert_mont(a) */
 int rofl_dbg_sc_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out);
+/* Every Ristretto encoder and identity predicate of the library on the CALLER'S representatives.  A point the library holds stands for a
+ * Ristretto class, and each of K + T, T in E[4] = {(0, 1), (0, -1), (i, 0), (-i, 0)}, is a legal stand-in for the class K; which one a sum of
+ * decoded points lands on is decided by the summands.  Case i is the projective point (X, Y, Z, T) of xyzt[128 i .. 128 i + 127]: four
+ * canonical 32-byte field elements, any Z, loaded as they are into the site's own point type; out32[32 i ..] is the site's encoding of it
+ * and is_identity_out[i] what the site's predicate says (1 / 0).  The caller answers for X Y = Z T and for the point being on the curve.
+ *   site 0  gd_ristretto_encode and sg_is_identity on the device (csrc/fe26.hpp, csrc/kernels.hpp): kernel k_dbg_encode_reps, one launch,
+ *           one thread per case
+ *   site 1  the host build of the same fe26.hpp functions (the predicate as sg_is_identity's body: gd_pack, then ge_is_identity_ristretto)
+ *   site 2  ristretto_encode and ge_is_identity_ristretto (csrc/fe32.hpp), on the host
+ *   site 3  h51::encode and h51::is_identity_ristretto (csrc/host51.hpp)
+ *   site 4  h8::encode8 (csrc/host51x8.hpp), eight lanes a batch in the order given -- the caller mixes the lanes; a short last batch is
+ *           filled with (0, 1, 1, 0).  There is no eight-lane predicate: is_identity_out is h51's on the lanes as loaded.  Returns -1 where
+ *           the CPU has no AVX-512 IFMA (nothing written).
+ * Sites 1 .. 4 need no GPU.  11 = bad parameter: a null pointer, site > 4, n > 2^20, a coordinate that is not a canonical field element. */
+int rofl_dbg_encode_reps(unsigned site, size_t n, const uint8_t *xyzt /* n x 4 x 32 */, uint8_t *out32 /* n x 32 */,
+                         uint8_t *is_identity_out /* n */);
 /* The float-to-fixed rule (conversion32.rs:11-18: |v| 2^fp_frac rounded to nearest, ties to even, saturated at 2^fp_bits - 1, negated mod l
  * for v < 0) at each of its device sites, on RAW values -- un-clipped, ties, infinities, NaN: nothing is checked on the way in.  `values` is
  * [rows][d] floats.  The production kernels are launched unchanged, with the clip bounds (get_clip_bounds(prove_range)), the grid and the

@@ -302,6 +302,20 @@ def dbg_msm_fixed(n_bits, m, scalars32):
     return out
 
 
+def dbg_encode_reps(site, xyzt):
+    """test hook (include/rofl_zk_debug.h): the encoder and the identity predicate of `site` (0 device, 1 fe26 on the host, 2 fe32, 3 h51,
+    4 h8::encode8 in batches of eight) on the n representatives xyzt [n][4][32] (X, Y, Z, T canonical) -> (encodings u8[n, 32],
+    is_identity u8[n]), or None where site 4 has no AVX-512 IFMA to run on"""
+    p = np.ascontiguousarray(xyzt, dtype=np.uint8).reshape(-1, 128)
+    out = np.zeros((p.shape[0], 32), dtype=np.uint8)
+    ident = np.full(p.shape[0], 0xFF, dtype=np.uint8)
+    rc = lib().rofl_dbg_encode_reps(ctypes.c_uint(int(site)), _sz(p.shape[0]), _ptr(p), _ptr(out), _ptr(ident))
+    if rc == -1:
+        return None
+    _check(rc)
+    return out, ident
+
+
 def set_timing(on):
     """0 / False = off, 1 / True = every instrumented launch, 2 = only the fixed-base accumulation (cheap enough for timed steps)"""
     _check(lib().rofl_set_timing(int(on)))

@@ -2748,6 +2748,17 @@ __device__ inline bool sg_decode(gd &p, const uint8_t *in) { bool ok = gd_ristre
 // niels form of a freshly decoded point (gd_ristretto_decode leaves Z = 1: no inversion)
 __device__ inline niels sg_affine_niels(const gd &p) { niels r; r.ypx = fd_pack(fd_add(p.Y, p.X)); r.ymx = fd_pack(fd_sub(p.Y, p.X)); r.t2d = fd_pack(fd_mul(p.T, fd_d2())); return r; }
 __device__ inline bool sg_is_identity(const gd &p) { ge t = gd_pack(p); return ge_is_identity_ristretto(t); }
+// rofl_dbg_encode_reps site 0: the device encoder and the device identity predicate on caller-supplied representatives (X, Y, Z, T canonical,
+// any Z), one thread per case
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(TPB) k_dbg_encode_reps(u32 n, const ge *pts /* [n] */, uint8_t *out /* [n][32] */, uint8_t *is_identity /* [n] */) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const gd p = load_gd(&pts[t]);
+    gd_ristretto_encode(out + (size_t)32 * t, p);
+    is_identity[t] = sg_is_identity(p) ? 1 : 0;
+}
+#endif
 
 // kind 0 RandProof (L|R ; L'|R'|Zm|Zr), 1 SquareRandProof (L|R|c_sq ; L'|R'|c_sq'|Zm|Zr1|Zr2), 2 SquareProof (c_l|c_sq ; c_l'|c_sq'|Zm|Zr1|Zr2)
 __device__ inline void sg_transcript(int kind, DMerlin &t, const uint8_t *cm, const uint8_t *pf, bool has_R) {

@@ -2615,6 +2615,51 @@ static int dbg_ops_device(bool scalar_field, unsigned op, size_t n, const uint32
 }
 int rofl_dbg_fd_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out) { return dbg_ops_device(false, op, n, in, out); }
 int rofl_dbg_sc_ops(unsigned op, size_t n, const uint32_t *in, uint32_t *out) { return dbg_ops_device(true, op, n, in, out); }
+// Every Ristretto encoder and identity predicate of the library on the caller's own representatives: case i is the projective point
+// (X, Y, Z, T) of xyzt[128 i ..], four canonical field elements, loaded into the site's point type as it is -- any Z, any of the four
+// representatives K + E[4] of a class.  Nothing here encodes or tests by itself: each site calls the production function.
+int rofl_dbg_encode_reps(unsigned site, size_t n, const uint8_t *xyzt, uint8_t *out32, uint8_t *is_identity_out) {
+    if (site > 4 || n > (1u << 20) || !xyzt || !out32 || !is_identity_out) return fail(ROFL_BAD_PARAM, "bad parameter");
+    std::vector<ge> pts(n);
+    for (size_t i = 0; i < n; i++) {
+        fe *const c[4] = {&pts[i].X, &pts[i].Y, &pts[i].Z, &pts[i].T};
+        for (int k = 0; k < 4; k++) {
+            const uint8_t *b = xyzt + 128 * i + 32 * k;
+            *c[k] = fe_frombytes(b);
+            uint8_t chk[32]; fe_tobytes(chk, *c[k]);
+            if (memcmp(chk, b, 32) != 0) return fail(ROFL_BAD_PARAM, "a coordinate is not a canonical field element");
+        }
+    }
+    if (site == 0) {
+        if (n == 0) return ROFL_OK;
+        return guarded([&]() -> int {
+            LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+            C.init();
+            ge *din = C.tmp_in.as<ge>(n);
+            uint8_t *dout = C.tmp_out.as<uint8_t>(n * 33);
+            C.up(din, pts.data(), n * sizeof(ge), C.stream);
+            ROFL_LAUNCH(k_dbg_encode_reps, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (const ge *)din, dout, dout + n * 32);
+            C.down(out32, dout, n * 32, C.stream);
+            C.down(is_identity_out, dout + n * 32, n, C.stream);
+            C.sync();
+            return ROFL_OK;
+        });
+    }
+    if (site == 4 && !h8::available()) return -1;
+    for (size_t i = 0; i < n; i++) {
+        if (site == 1) { const gd p = gd_unpack(pts[i]); gd_ristretto_encode(out32 + 32 * i, p); is_identity_out[i] = ge_is_identity_ristretto(gd_pack(p)) ? 1 : 0; }      // (sg_is_identity's body: that wrapper is device-only)
+        else if (site == 2) { ristretto_encode(out32 + 32 * i, pts[i]); is_identity_out[i] = ge_is_identity_ristretto(pts[i]) ? 1 : 0; }
+        else if (site == 3) { const ge5 p = h51::from_ge(pts[i]); h51::encode(out32 + 32 * i, p); is_identity_out[i] = h51::is_identity_ristretto(p) ? 1 : 0; }
+    }
+    for (size_t first = 0; site == 4 && first < n; first += 8) {      // eight lanes a batch, in the caller's order; a short last batch is filled with (0, 1, 1, 0)
+        ge5 lanes[8]; uint8_t enc[8][32];
+        const size_t cnt = n - first < 8 ? n - first : 8;
+        for (size_t l = 0; l < 8; l++) lanes[l] = l < cnt ? h51::from_ge(pts[first + l]) : h51::identity();
+        h8::encode8(enc, lanes);
+        for (size_t l = 0; l < cnt; l++) { memcpy(out32 + 32 * (first + l), enc[l], 32); is_identity_out[first + l] = h51::is_identity_ristretto(lanes[l]) ? 1 : 0; }
+    }
+    return ROFL_OK;
+}
 // The float-to-fixed rule (conversion32.rs:11-18) as each device site compiles it, on the caller's raw values: the production kernels with the
 // launch geometry, clip bounds and block count of their launch sites (create_batch_impl, l2_create_batch), and k_dbg_quant for sg_f32_to_sc.
 int rofl_dbg_quantize(unsigned site, size_t rows, size_t d, size_t dpad, size_t prove_range, unsigned fp_bits, unsigned fp_frac,

@@ -689,6 +689,49 @@ int rofl_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const
                      size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
                      const uint8_t *reveal32, const uint8_t *proof64,
                      uint8_t *shared_out32 /* may be NULL */, uint8_t *verdict_out /* n_pairs */);
+/* Merkle trees: a commitment to a list of n byte strings -- a round's broadcast -- behind one 32-byte root, with single entries proved and
+ * checked by a path of depth(n) <= 20 hashes.  A client signs the root instead of the whole list, checks the entries it holds against what
+ * everybody signed, and hands a judge one entry and its path instead of the list.  Every label is exactly 16 bytes:
+ *   leaf:   leaf(m) = SHAKE256("rofl-zk/mtr/v1/l" || u64le(len m) || m)[0 .. 32), any length, 0 included (the stream of the signature
+ *     digest under another label);
+ *   node:   node(a, b) = SHAKE256("rofl-zk/mtr/v1/n" || a || b)[0 .. 32) (80 bytes, one Keccak block);
+ *   levels: level 0 is the n leaf digests, w_0 = n; level l + 1 has w_{l+1} = ceil(w_l / 2) nodes, node i = node(level_l[2i], level_l[2i + 1]);
+ *     when w_l is odd the last node of level l moves up UNCHANGED (nothing is duplicated): the tree shape of RFC 6962;
+ *     depth(n) = bit_length(n - 1), depth(1) = 0; top is the one node of the last level;
+ *   root:   root = SHAKE256("rofl-zk/mtr/v1/r" || u64le(n) || top)[0 .. 32) (56 bytes, one block): the leaf count is bound, so a path cannot
+ *     be replayed under another n; the three labels keep a leaf digest, an inner node and a root from standing in for one another;
+ *   path of leaf j: depth(n) slots of 32 bytes, bottom up; slot l holds the sibling level_l[(j >> l) ^ 1] if that index is < w_l, and 32 zero
+ *     bytes otherwise (the node moved up alone; only on the right edge);
+ *   check:  climb from leaf(m); at level l with x = j >> l and a sibling in the slot take node(cur, slot) for even x, node(slot, cur) for odd
+ *     x, else keep cur; then the root block and the compare;
+ *   verdict byte per path, a malformed input before a failing climb:
+ *     2 = j >= n of its root, or a nonzero byte in a slot the shape leaves empty, slots depth(n) .. stride - 1 of the row included;
+ *     0 = the climb gives the root;  1 = anything else.
+ * rofl_merkle_build: message j is msg_bytes[msg_off[j] .. msg_off[j + 1]); msg_off == NULL means msg_bytes holds n x 32 leaf DIGESTS.  It
+ * writes the root, the leaf digests (leaves_out32, may be NULL) and the paths of the n_paths leaves path_idx names (any order, repeats
+ * allowed), n_paths x depth(n) x 32 bytes.  rofl_merkle_verify: path i is leaf refs[i].index under root refs[i].root with n_leaves[root]
+ * leaves; refs == NULL means every path under root 0 with index i (n_roots is then 1); row i of paths32 has `stride` slots, of which the
+ * first depth(n) are the path; message i (or digest i) is path i's leaf.  A bad path condemns itself, not the call.
+ * Host pointers only.  Both return 11 before the device is touched for a null pointer (except msg_off, refs, leaves_out32, msg_bytes of
+ * messages that are all empty, and the paths of trees of one leaf), offsets that do not start at 0 or decrease (the text names the
+ * position), more than 2^30 message bytes, n_paths above 2^24, more than 2^30 path bytes; build for n = 0 with paths asked for, n above
+ * 2^20, a path_idx >= n (the text names the path); verify for n_roots = 0 or above 2^20, a leaf count outside [1, 2^20] (the text names
+ * the root), stride above 20 or below the depth of a root that a ref names, refs == NULL with n_roots != 1, a ref whose root is >= n_roots.
+ * An index >= its root's leaf count is NOT a parameter error: it is a peer's data, verdict 2.  n = 0 with n_paths = 0 (build) and
+ * n_paths = 0 (verify) return 0 and touch no device.  One lane, one upload, one download.  build launches k_mt_leaves (one thread per
+ * message; skipped for digests), k_mt_tile ceil(depth / 9) times (a workgroup reduces 512 consecutive nodes nine levels in LDS; every
+ * level is kept in a device workspace of fewer than 2 n nodes) and k_mt_paths; verify k_mt_leaves and k_mt_climb (one thread per path).
+ * Nothing here is secret and nothing is wiped.  The `devices` option does not apply.
+ * What the tree does NOT give: no consistency or append proofs between two trees, no proof that an entry is absent (the leaves are not
+ * sorted by the tree), and one tree per call. */
+typedef struct { uint32_t root, index; } rofl_merkle_ref_t;
+int rofl_merkle_build(size_t n, const uint8_t *msg_bytes, const uint64_t *msg_off /* n + 1; NULL: msg_bytes is n x 32 leaf digests */,
+                      uint8_t *root_out32, uint8_t *leaves_out32 /* may be NULL; n x 32 */,
+                      size_t n_paths, const uint32_t *path_idx /* n_paths leaf indices */, uint8_t *paths_out32 /* n_paths x depth(n) x 32 */);
+int rofl_merkle_verify(size_t n_roots, const uint8_t *root32, const uint32_t *n_leaves /* per root */,
+                       size_t n_paths, const rofl_merkle_ref_t *refs /* NULL: root 0, index i */,
+                       const uint8_t *msg_bytes, const uint64_t *msg_off /* n_paths + 1; NULL: n_paths x 32 leaf digests */,
+                       const uint8_t *paths32 /* n_paths x stride x 32 */, size_t stride, uint8_t *verdict_out /* n_paths */);
 int rofl_f32_to_fp_vec(const float *in, size_t d, unsigned fp_bits, unsigned fp_frac, uint64_t *out);         /* conversion32.rs:49-54 */
 int rofl_uint_to_f32_vec(const uint64_t *in, size_t d, unsigned fp_bits, unsigned fp_frac, float *out);        /* conversion32.rs:41-47 */
 int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, float *out);  /* conversion32.rs:62-64 */

@@ -254,6 +254,15 @@ int rofl_dbg_host_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_
 int rofl_dbg_host_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs,
                               const rofl_dh_pair_t *pairs, const uint8_t *ctx32, const uint8_t *reveal32, const uint8_t *proof64,
                               uint8_t *shared_out32, uint8_t *verdict_out);
+/* rofl_merkle_build / rofl_merkle_verify on the host's sponge, one thread, no GPU: the same parameters, the same checks (11) and the same
+ * bytes and verdicts.  What the host tests pin the definition with, and the baseline of profiles/merkle.json.
+ * rofl_dbg_merkle_tile_leaves: the number of nodes a workgroup of k_mt_tile owns, so that tests can place n around it; no output byte
+ * depends on it. */
+int rofl_dbg_host_merkle_build(size_t n, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *root_out32, uint8_t *leaves_out32,
+                               size_t n_paths, const uint32_t *path_idx, uint8_t *paths_out32);
+int rofl_dbg_host_merkle_verify(size_t n_roots, const uint8_t *root32, const uint32_t *n_leaves, size_t n_paths, const rofl_merkle_ref_t *refs,
+                                const uint8_t *msg_bytes, const uint64_t *msg_off, const uint8_t *paths32, size_t stride, uint8_t *verdict_out);
+size_t rofl_dbg_merkle_tile_leaves(void);
 /* out32[i] = encode(k1[i] decode(p1[i]) + k2[i] decode(p2[i])) through the kernels' own device functions, one thread per item, n <= 2^24:
  * rofl_dbg_var_mul2 on the joint chain sg_var_mul2 (two tables, one chain of doublings), rofl_dbg_var_mul_sum as the sum of two sg_var_mul
  * products.  Scalars are reduced mod l; a point that does not decode counts as the identity.  *kernel_ms (may be NULL): the launch alone,

@@ -236,6 +236,14 @@ extern "C" {
     pub fn rofl_dleq_verify(n_own: usize, own_pk32: *const u8, n_peer: usize, peer_pk32: *const u8,
         n_pairs: usize, pairs: *const RoflDhPair, ctx32: *const u8, reveal32: *const u8, proof64: *const u8,
         shared_out32: *mut u8, verdict_out: *mut u8) -> c_int;
+    /// a Merkle tree over n messages (msg_off null: msg_bytes is n x 32 leaf digests): the root, the leaf digests (leaves_out32 may be null)
+    /// and the paths of the leaves path_idx names, n_paths x depth(n) x 32 bytes, depth(n) = bit_length(n - 1)
+    pub fn rofl_merkle_build(n: usize, msg_bytes: *const u8, msg_off: *const u64, root_out32: *mut u8, leaves_out32: *mut u8,
+        n_paths: usize, path_idx: *const u32, paths_out32: *mut u8) -> c_int;
+    /// verdict_out[i]: 0 the path of leaf refs[i].index climbs to root refs[i].root (refs null: root 0, index i), 1 it does not, 2 the index is
+    /// not below the root's leaf count or a slot the shape leaves empty (up to `stride`) has a nonzero byte
+    pub fn rofl_merkle_verify(n_roots: usize, root32: *const u8, n_leaves: *const u32, n_paths: usize, refs: *const RoflMerkleRef,
+        msg_bytes: *const u8, msg_off: *const u64, paths32: *const u8, stride: usize, verdict_out: *mut u8) -> c_int;
     pub fn rofl_f32_to_fp_vec(input: *const c_float, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut u64) -> c_int;
     pub fn rofl_uint_to_f32_vec(input: *const u64, d: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
     pub fn rofl_get_l2_clip_bounds(range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *mut c_float) -> c_int;
@@ -272,6 +280,14 @@ pub struct RoflDhPair {
 pub struct RoflSigRef {
     pub key: u32,
     pub msg: u32,
+}
+
+/// rofl_merkle_ref_t: one path of rofl_merkle_verify -- the root it is checked under and the index of its leaf
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RoflMerkleRef {
+    pub root: u32,
+    pub index: u32,
 }
 
 #[repr(C)]

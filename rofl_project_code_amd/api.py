@@ -56,6 +56,11 @@ class _SigRef(ctypes.Structure):
     _fields_ = [("key", ctypes.c_uint32), ("msg", ctypes.c_uint32)]
 
 
+class _MerkleRef(ctypes.Structure):
+    """rofl_merkle_ref_t"""
+    _fields_ = [("root", ctypes.c_uint32), ("index", ctypes.c_uint32)]
+
+
 class _Timing(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("msm_accumulate_ms", ctypes.c_double),
                 ("msm_accumulate_launches", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64),
@@ -110,7 +115,7 @@ def lib():
             raise RuntimeError(f"{_LIB_PATH} not found: build it with `python -m rofl_project_code_amd.build` "
                                "(hipcc --offload-arch=gfx950); there is no CPU fallback")
         _lib = ctypes.CDLL(_LIB_PATH)
-        for name in ("rofl_next_pow2", "rofl_rangeproof_chunks", "rofl_rangeproof_size", "rofl_nonces_per_chunk", "rofl_wire_encoded_size"):
+        for name in ("rofl_next_pow2", "rofl_rangeproof_chunks", "rofl_rangeproof_size", "rofl_nonces_per_chunk", "rofl_wire_encoded_size", "rofl_dbg_merkle_tile_leaves"):
             getattr(_lib, name).restype = ctypes.c_size_t
     return _lib
 
@@ -1368,6 +1373,96 @@ class signatures:
         return out
 
 
+def _leaf_input(messages, digests):
+    """(n, bytes pointer or None, offsets pointer or None, the arrays kept alive) of a call's leaves: messages packed, or digests uint8[n, 32]"""
+    if (messages is None) == (digests is None):
+        raise ValueError("either messages or digests")
+    if digests is not None:
+        dg = _keys32(digests, "a leaf digest")
+        return dg.shape[0], _ptr(dg), None, (dg,)
+    data, off = _pack_messages(messages)
+    return off.shape[0] - 1, _ptr(data) if data.size else None, _ptr(off), (data, off)
+
+
+class merkle:
+    """Batched Merkle trees (rofl_merkle_build / rofl_merkle_verify): a list of byte strings behind one 32-byte root, single entries proved and
+    checked by a path of depth(n) hashes.  leaf(m) = SHAKE256("rofl-zk/mtr/v1/l" || u64le(len m) || m)[0 .. 32), node(a, b) =
+    SHAKE256("rofl-zk/mtr/v1/n" || a || b)[0 .. 32); a level of odd width moves its last node up unchanged (the shape of RFC 6962);
+    root = SHAKE256("rofl-zk/mtr/v1/r" || u64le(n) || top)[0 .. 32).  The path of leaf j has depth(n) slots bottom up: the sibling
+    level_l[(j >> l) ^ 1], or 32 zero bytes where the node moved up alone.  Nothing is secret.  No consistency or append proofs, no proof
+    of absence, one tree per call."""
+    MAX_STRIDE = 20
+
+    @staticmethod
+    def depth(n):
+        """slots in a path of a tree of n >= 1 leaves: bit_length(n - 1)"""
+        n = int(n)
+        if n < 1:
+            raise ValueError("a tree has at least one leaf")
+        return (n - 1).bit_length()
+
+    @staticmethod
+    def _build(fn, messages, digests, paths_for, with_leaves):
+        n, bytes_p, off_p, keep = _leaf_input(messages, digests)
+        if n == 0:
+            raise ValueError("a tree has at least one leaf")
+        idx = np.ascontiguousarray(np.asarray([] if paths_for is None else paths_for, dtype=np.int64).reshape(-1))
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            raise ValueError("a path names a leaf that is not in the tree")
+        idx = idx.astype(np.uint32)
+        d = merkle.depth(n)
+        root = np.zeros(32, dtype=np.uint8)
+        leaves = np.zeros((n, 32), dtype=np.uint8) if with_leaves else None
+        paths = np.zeros((idx.size, d, 32), dtype=np.uint8)
+        _check(fn(_sz(n), bytes_p, off_p, _ptr(root), _ptr(leaves) if with_leaves else None, _sz(idx.size), _ptr(idx) if idx.size else None,
+                  _ptr(paths) if paths.size else None))
+        del keep
+        out = (root,) + ((paths,) if paths_for is not None else ()) + ((leaves,) if with_leaves else ())
+        return out if len(out) > 1 else root
+
+    @staticmethod
+    def build(messages=None, digests=None, paths_for=None, with_leaves=False):
+        """The tree over the messages (a list of bytes-likes) or over leaf digests uint8[n, 32], ONE call -> root uint8[32]; with paths_for
+        (leaf indices, any order, repeats allowed) also paths uint8[k, depth(n), 32]; with_leaves=True appends the leaf digests uint8[n, 32]."""
+        return merkle._build(lib().rofl_merkle_build, messages, digests, paths_for, with_leaves)
+
+    @staticmethod
+    def _verify(fn, roots, counts, paths, messages, digests, refs):
+        rt = _keys32(roots, "a root")
+        cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int64).reshape(-1))
+        if cnt.size != rt.shape[0]:
+            raise ValueError("one leaf count per root")
+        if cnt.size and (cnt.min() < 1 or cnt.max() > 1 << 20):
+            raise ValueError("a leaf count is in [1, 2^20]")
+        cnt = cnt.astype(np.uint32)
+        n, bytes_p, off_p, keep = _leaf_input(messages, digests)
+        pt = np.ascontiguousarray(np.asarray(paths, dtype=np.uint8))
+        if pt.ndim != 3 or pt.shape[0] != n or pt.shape[2] != 32:
+            raise ValueError("paths are uint8[n, stride, 32], one row per leaf")
+        stride = pt.shape[1]
+        rarr = None
+        if refs is not None:
+            rl = np.asarray(refs, dtype=np.int64).reshape(-1, 2)
+            if rl.shape[0] != n:
+                raise ValueError("one ref per path")
+            if n and (rl.min() < 0 or rl[:, 0].max() >= rt.shape[0] or rl[:, 1].max() >= 1 << 32):
+                raise ValueError("a ref names a root that is not in the call")
+            rarr = (_MerkleRef * max(n, 1))()
+            np.frombuffer(rarr, dtype=np.uint32)[:2 * n] = rl.astype(np.uint32).reshape(-1)
+        out = np.zeros(n, dtype=np.uint8)
+        _check(fn(_sz(rt.shape[0]), _ptr(rt), _ptr(cnt), _sz(n), rarr, bytes_p, off_p, _ptr(pt) if pt.size else None, _sz(stride), _ptr(out)))
+        del keep
+        return out
+
+    @staticmethod
+    def verify(roots, counts, paths, messages=None, digests=None, refs=None):
+        """-> uint8[n] verdicts of the paths uint8[n, stride, 32] (the rows of build(), or wider rows whose further slots are zero), ONE call:
+        path i is the leaf messages[i] (or digests[i]) at index refs[i][1] under root refs[i][0] of roots uint8[n_roots, 32] with counts[root]
+        leaves; refs=None: one root, leaf i at index i.  0 = the climb gives the root, 1 = it does not, 2 = the index is not below the leaf
+        count or a slot the shape leaves empty holds a nonzero byte."""
+        return merkle._verify(lib().rofl_merkle_verify, roots, counts, paths, messages, digests, refs)
+
+
 def _dh_pairs(pairs, n_own, n_peer):
     """(n_pairs, ctypes array or None) of a pair list [(own, peer), ...]; None = all n_own x n_peer pairs, own-major"""
     if pairs is None:
@@ -1723,6 +1818,79 @@ class secret_sharing:
         dealer equivocated: the verdict names it."""
         n = _keys32(sig_pks, "a public key").shape[0]
         return signatures.verify(sig_pks, [bytes(view)], view_sigs, [(i, 0) for i in range(n)])
+
+    # ---- the second view round: the same broadcast behind a Merkle root (merkle.build / verify), so that 60 bytes are signed whatever the number
+    # of dealers, a client that holds only some dealers' entries checks them against what everybody signed, and two views that differ are
+    # settled with one entry and its path ----
+    @staticmethod
+    def view_leaf(round_no, dealer, sigs2x64):
+        """The leaf of one dealer in the view tree, 156 bytes: b"rofl-zk/view/v2\\0" || u64le(round_no) || u32le(dealer) || key sig || self sig."""
+        s = np.asarray(sigs2x64, dtype=np.uint8)
+        if s.shape != (2, 64):
+            raise ValueError("the signatures of dealer %d are uint8[2, 64]" % int(dealer))
+        return b"rofl-zk/view/v2\0" + struct.pack("<QI", int(round_no), int(dealer)) + s.tobytes()
+
+    @staticmethod
+    def view_tree(round_no, sigs_by_dealer, paths_for=None):
+        """The view of sigs_by_dealer = {dealer: uint8[2, 64]} as a tree, ONE merkle.build call: the leaves are the dealers' view_leaf in
+        ascending dealer order.  -> (root uint8[32], dealers_sorted); with paths_for (a list of DEALERS) also their paths
+        uint8[k, depth(count), 32].  The leaf index of a dealer is its position in dealers_sorted."""
+        dealers = sorted(int(k) for k in sigs_by_dealer)
+        leaves = [secret_sharing.view_leaf(round_no, d, sigs_by_dealer[d]) for d in dealers]
+        if paths_for is None:
+            return merkle.build(leaves), dealers
+        pos = {d: i for i, d in enumerate(dealers)}
+        if any(int(d) not in pos for d in paths_for):
+            raise ValueError("a path is asked for a dealer that is not in the view")
+        root, paths = merkle.build(leaves, paths_for=[pos[int(d)] for d in paths_for])
+        return root, dealers, paths
+
+    @staticmethod
+    def view_root_message(round_no, count, root):
+        """The bytes a client signs for the tree of everything it was shown, 60 bytes:
+        b"rofl-zk/view/v2r" || u64le(round_no) || u32le(count) || root."""
+        r = bytes(root) if isinstance(root, (bytes, bytearray, memoryview)) else np.asarray(root, dtype=np.uint8).tobytes()
+        if len(r) != 32:
+            raise ValueError("a root is 32 bytes")
+        return b"rofl-zk/view/v2r" + struct.pack("<QI", int(round_no), int(count)) + r
+
+    @staticmethod
+    def sign_view_root(sig_sks, round_no, count, roots):
+        """Every hosted client signs the view_root_message of ITS root (roots uint8[n, 32]; clients may have been shown different things), ONE
+        signatures.sign call -> uint8[n, 64]."""
+        rt = _keys32(roots, "a root")
+        if _keys32(sig_sks, "a secret key").shape[0] != rt.shape[0]:
+            raise ValueError("one root per signing key")
+        return signatures.sign(sig_sks, [secret_sharing.view_root_message(round_no, count, r) for r in rt])
+
+    @staticmethod
+    def verify_view_roots(sig_pks, round_no, count, root, view_sigs):
+        """n clients' signatures view_sigs uint8[n, 64] on the view_root_message of ONE root under their public signing keys, ONE
+        signatures.verify call with refs (i, 0) -> uint8[n].  A client whose verdict is nonzero signed another root: it was shown something
+        else, or its dealer equivocated; the verdict names it, as verify_views does."""
+        n = _keys32(sig_pks, "a public key").shape[0]
+        return signatures.verify(sig_pks, [secret_sharing.view_root_message(round_no, count, root)], view_sigs, [(i, 0) for i in range(n)])
+
+    @staticmethod
+    def verify_view_entries(round_no, root, count, positions, entries, paths):
+        """What a client that holds only some dealers' signature pairs checks against the root everybody signed, ONE merkle.verify call:
+        entries = [(dealer, uint8[2, 64]), ...], positions[i] the leaf index of entry i (the dealer's position among the round's dealers in
+        ascending order), paths uint8[k, stride, 32] -> uint8[k] verdicts, 0 = the entry is in the tree of `root` with `count` leaves."""
+        leaves = [secret_sharing.view_leaf(round_no, d, s) for d, s in entries]
+        pos = [int(p) for p in positions]
+        if len(pos) != len(leaves):
+            raise ValueError("one position per entry")
+        return merkle.verify([root], [int(count)], paths, messages=leaves, refs=[(0, p) for p in pos])
+
+    @staticmethod
+    def differing_view_entries(round_no, sigs_a, sigs_b):
+        """The dealers whose leaves differ between two views {dealer: uint8[2, 64]}, ascending: a dealer in only one of them, or with other
+        signatures -- what to ask paths for when two signed roots differ.  Plain Python."""
+        out = []
+        for d in sorted(set(int(k) for k in sigs_a) | set(int(k) for k in sigs_b)):
+            if d not in sigs_a or d not in sigs_b or secret_sharing.view_leaf(round_no, d, sigs_a[d]) != secret_sharing.view_leaf(round_no, d, sigs_b[d]):
+                out.append(d)
+        return out
 
     # ---- the shares on their way: every bundle sealed under the pair's channel key of the round (aead.seal / open) ----
     # A client has THREE key pairs: the mask key (key_agreement; Shamir-shared, and RECONSTRUCTED by the server when its owner drops out), the

@@ -3208,26 +3208,22 @@ __device__ __forceinline__ sc sig_challenge(const u64 R[4], const u64 A[4], cons
     shake256_block14(st, m);
     return xof_block_scalar(st, 0);
 }
-#if ROFL_KG(4)
-// dig[j] = h(message j), one thread per message; message j is bytes[off[j] .. off[j + 1]).  The sponge's stream is three words of prefix
-// (label, length) and then the message, so stream word g >= 3 is the message's bytes 8 (g - 3) .. + 8: a message starts at ANY byte, so a
+// st[0 .. 4) = SHAKE256(label16 || u64le(len) || m)[0 .. 32) for the label words dom0, dom1 and the message m = bytes[o .. o + len): the
+// digest of the signatures (k_sig_digest) and, under a label of its own, the leaf digest of the Merkle trees (k_mt_leaves), one thread per
+// message.  The sponge's stream is three words of prefix (label, length) and then the message, so stream word g >= 3 is the message's bytes 8 (g - 3) .. + 8: a message starts at ANY byte, so a
 // word is put together from the two 8-byte aligned words that hold it (`bytes` is 8-byte aligned; only aligned words that hold a byte of
 // the message are read).  The word after the last whole one carries the remaining 0 .. 7 bytes and the SHAKE suffix 0x1F above them; the
 // last block gets 0x80 into byte 135.  The four endings fall out of the XORs: inside a block; on the last byte of the rate (0x1F and 0x80 in
 // one byte: 0x9F); exactly on the rate (the suffix word is word 0 of a block of its own); the empty message (the suffix is word 3).
 // The lanes of a wave run as many blocks as their longest message has: a long message is one serial chain of permutations on one lane.
-__global__ void __launch_bounds__(64) k_sig_digest(u32 n_msgs, const uint8_t *__restrict__ bytes, const u64 *__restrict__ off /* [n_msgs + 1] */, u64 *__restrict__ dig /* [n_msgs][4] */) {
-    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_msgs) return;
-    const u64 o = off[j], len = off[j + 1] - o, nw = len >> 3;
+__device__ __forceinline__ void labelled_digest(u64 st[25], u64 dom0, u64 dom1, const uint8_t *__restrict__ bytes, u64 o, u64 len) {
+    const u64 nw = len >> 3;
     const u32 rem = (u32)len & 7u, mis = (u32)o & 7u, sh = 8 * mis;
     const u64 *a = reinterpret_cast<const u64 *>(bytes + (o - mis));
     const u64 lastw = len ? (mis + len - 1) >> 3 : 0;      // the last aligned word that holds a byte of the message
-    const u64 dom[2] = ROFL_SIG_DOM_M;
-    u64 st[25];
 #pragma unroll
     for (int i = 0; i < 25; i++) st[i] = 0;
-    st[0] = dom[0]; st[1] = dom[1]; st[2] = len;
+    st[0] = dom0; st[1] = dom1; st[2] = len;
     const u64 gpad = 3 + nw, nblk = gpad / 17 + 1;
     for (u64 b = 0; b < nblk; b++) {
 #pragma unroll
@@ -3246,9 +3242,28 @@ __global__ void __launch_bounds__(64) k_sig_digest(u32 n_msgs, const uint8_t *__
         if (b + 1 == nblk) st[16] ^= 0x8000000000000000ULL;
         keccak_f1600(st);
     }
-    uint4 *d = reinterpret_cast<uint4 *>(dig + 4 * (size_t)j);
-    d[0] = make_uint4((u32)st[0], (u32)(st[0] >> 32), (u32)st[1], (u32)(st[1] >> 32));
-    d[1] = make_uint4((u32)st[2], (u32)(st[2] >> 32), (u32)st[3], (u32)(st[3] >> 32));
+}
+// four words as two 16-byte stores / from two 16-byte loads (p is 16-byte aligned)
+__device__ __forceinline__ void store_words4(u64 *p, const u64 v[4]) {
+    uint4 *d = reinterpret_cast<uint4 *>(p);
+    d[0] = make_uint4((u32)v[0], (u32)(v[0] >> 32), (u32)v[1], (u32)(v[1] >> 32));
+    d[1] = make_uint4((u32)v[2], (u32)(v[2] >> 32), (u32)v[3], (u32)(v[3] >> 32));
+}
+__device__ __forceinline__ void load_words4(u64 v[4], const u64 *p) {
+    const uint4 *s = reinterpret_cast<const uint4 *>(p);
+    const uint4 a = s[0], b = s[1];
+    v[0] = (u64)a.x | ((u64)a.y << 32); v[1] = (u64)a.z | ((u64)a.w << 32); v[2] = (u64)b.x | ((u64)b.y << 32); v[3] = (u64)b.z | ((u64)b.w << 32);
+}
+#if ROFL_KG(4)
+// dig[j] = h(message j), one thread per message; message j is bytes[off[j] .. off[j + 1])
+__global__ void __launch_bounds__(64) k_sig_digest(u32 n_msgs, const uint8_t *__restrict__ bytes, const u64 *__restrict__ off /* [n_msgs + 1] */, u64 *__restrict__ dig /* [n_msgs][4] */) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_msgs) return;
+    const u64 dom[2] = ROFL_SIG_DOM_M;
+    const u64 o = off[j];
+    u64 st[25];
+    labelled_digest(st, dom[0], dom[1], bytes, o, off[j + 1] - o);
+    store_words4(dig + 4 * (size_t)j, st);
 }
 // sig[i] = the signature of key refs[i].x on message refs[i].y (refs == nullptr: key i on message i), one thread per signature: the nonce
 // block, k B from the radix-256 table, its encoding, the challenge block, s, two 32-byte stores.  pk: the output of a k_dh_public launch over
@@ -3909,6 +3924,149 @@ __global__ void __launch_bounds__(TPB) k_cpow_rows(u32 d, const sc *sq, sc *out_
         store_sc(&o[k], sc_from_mont(p));
         if (k + 1 < cnt) p = sc_montmul(p, c);
     }
+}
+#endif
+
+// ================================================================ Merkle trees (rofl_merkle_build / rofl_merkle_verify)
+// A commitment to a list of n byte strings, what a round's broadcast is signed through: one root, and per entry a path of depth(n) hashes.
+//   leaf(m)    = SHAKE256("rofl-zk/mtr/v1/l" || u64le(len m) || m)[0 .. 32)                               (k_mt_leaves: labelled_digest)
+//   node(a, b) = SHAKE256("rofl-zk/mtr/v1/n" || a || b)[0 .. 32)                                          (80 bytes, one block)
+//   level 0 is the n leaf digests, w_0 = n; level l + 1 has w_{l+1} = ceil(w_l / 2) nodes, node i = node(level_l[2i], level_l[2i + 1]);
+//   the last node of a level of odd width moves up UNCHANGED; top = the one node of level depth(n) = bit_length(n - 1);
+//   root       = SHAKE256("rofl-zk/mtr/v1/r" || u64le(n) || top)[0 .. 32)                                 (56 bytes, one block)
+//   path of leaf j: depth(n) slots, slot l = level_l[(j >> l) ^ 1] if that index is < w_l, 32 zero bytes otherwise.
+// Verdict of a path: 2 = j >= n or a nonzero byte in a slot the shape leaves empty (slots depth(n) .. stride - 1 included); 0 = the climb from
+// the leaf digest gives the root; 1 otherwise.  Nothing here is secret.
+#define ROFL_MT_DOM_L {0x2f6b7a2d6c666f72ULL, 0x6c2f31762f72746dULL}      /* "rofl-zk/" "mtr/v1/l" */
+#define ROFL_MT_DOM_N {0x2f6b7a2d6c666f72ULL, 0x6e2f31762f72746dULL}      /* "rofl-zk/" "mtr/v1/n" */
+#define ROFL_MT_DOM_R {0x2f6b7a2d6c666f72ULL, 0x722f31762f72746dULL}      /* "rofl-zk/" "mtr/v1/r" */
+// k_mt_tile: a workgroup of ROFL_MT_TILE / 2 threads owns ROFL_MT_TILE consecutive nodes of a level.  No output byte depends on it.
+#define ROFL_MT_TILE_LOG2 9
+#define ROFL_MT_TILE (1u << ROFL_MT_TILE_LOG2)
+__device__ __forceinline__ void mt_node(u64 out[4], const u64 a[4], const u64 b[4]) {
+    const u64 dom[2] = ROFL_MT_DOM_N;
+    u64 m[10], st[25];
+    m[0] = dom[0]; m[1] = dom[1];
+#pragma unroll
+    for (int w = 0; w < 4; w++) { m[2 + w] = a[w]; m[6 + w] = b[w]; }
+    shake256_block_words<10>(st, m);
+#pragma unroll
+    for (int w = 0; w < 4; w++) out[w] = st[w];
+}
+__device__ __forceinline__ void mt_root(u64 out[4], u64 n, const u64 top[4]) {
+    const u64 dom[2] = ROFL_MT_DOM_R;
+    u64 m[7], st[25];
+    m[0] = dom[0]; m[1] = dom[1]; m[2] = n;
+#pragma unroll
+    for (int w = 0; w < 4; w++) m[3 + w] = top[w];
+    shake256_block_words<7>(st, m);
+#pragma unroll
+    for (int w = 0; w < 4; w++) out[w] = st[w];
+}
+#if ROFL_KG(4)
+// dig[j] = leaf(message j), one thread per message: k_sig_digest under the leaf label
+__global__ void __launch_bounds__(64) k_mt_leaves(u32 n_msgs, const uint8_t *__restrict__ bytes, const u64 *__restrict__ off /* [n_msgs + 1] */, u64 *__restrict__ dig /* [n_msgs][4] */) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_msgs) return;
+    const u64 dom[2] = ROFL_MT_DOM_L;
+    const u64 o = off[j];
+    u64 st[25];
+    labelled_digest(st, dom[0], dom[1], bytes, o, off[j + 1] - o);
+    store_words4(dig + 4 * (size_t)j, st);
+}
+// Up to ROFL_MT_TILE_LOG2 levels of the tree in one launch.  Workgroup b takes the nodes [b T, min((b + 1) T, w_in)) of the level `in`
+// (T = ROFL_MT_TILE) into LDS and halves them level by level: thread i of a level reads its two children from LDS as uint4s, runs the node
+// block and, after a barrier, stores the parent to LDS slot i and to that level's place in `out`; a last node without a sibling moves up as it
+// is.  Pairs never cross an aligned T-boundary, so the tiles of a level reduce independently and level k above `in` is filled by workgroup b
+// at [b T >> k, ...).  out: the levels above `in` back to back, widths ceil(w_in / 2), ceil(w_in / 4), ...; the loop ends after
+// ROFL_MT_TILE_LOG2 levels (the host launches again on the tile roots, the last level written) or at the level of width 1, the top: then
+// -- the call's last launch, one workgroup -- thread 0 also stores the root block over (n_leaves, top).  w_in = 1 (a tree of one leaf) runs no
+// level and stores the root.  16 KB of LDS; the barriers are reached by every thread (w, cnt and k are the same for the whole workgroup).
+__global__ void __launch_bounds__(ROFL_MT_TILE / 2) k_mt_tile(u32 w_in, const u64 *__restrict__ in /* [w_in][4], 16-byte aligned */, u64 *__restrict__ out, u64 n_leaves,
+                                                             u64 *__restrict__ root_out /* [4] */) {
+    __shared__ uint4 s[2 * ROFL_MT_TILE];
+    const u32 tid = threadIdx.x, base = blockIdx.x * ROFL_MT_TILE;      // (the grid is ceil(w_in / T): base < w_in)
+    u32 cnt = w_in - base < ROFL_MT_TILE ? w_in - base : ROFL_MT_TILE, w = w_in;
+    const uint4 *src = reinterpret_cast<const uint4 *>(in) + 2 * (size_t)base;
+    for (u32 i = tid; i < 2 * cnt; i += ROFL_MT_TILE / 2) s[i] = src[i];
+    __syncthreads();
+    u64 *lvl = out;
+    for (u32 k = 1; k <= ROFL_MT_TILE_LOG2 && w > 1; k++) {
+        const u32 half = (cnt + 1) >> 1;
+        const bool act = tid < half;
+        u64 p[4];
+        if (act) {
+            u64 a[4];
+            load_words4(a, reinterpret_cast<const u64 *>(&s[4 * tid]));
+            if (2 * tid + 1 < cnt) { u64 b[4]; load_words4(b, reinterpret_cast<const u64 *>(&s[4 * tid + 2])); mt_node(p, a, b); }
+            else { p[0] = a[0]; p[1] = a[1]; p[2] = a[2]; p[3] = a[3]; }
+        }
+        __syncthreads();      // every child is read before a parent overwrites it
+        if (act) {
+            store_words4(reinterpret_cast<u64 *>(&s[2 * tid]), p);
+            store_words4(lvl + 4 * ((size_t)(base >> k) + tid), p);
+        }
+        __syncthreads();
+        w = (w + 1) >> 1; cnt = half;
+        lvl += 4 * (size_t)w;
+    }
+    if (w == 1 && tid == 0) {
+        u64 top[4], r[4];
+        load_words4(top, reinterpret_cast<const u64 *>(&s[0]));
+        mt_root(r, n_leaves, top);
+        store_words4(root_out, r);
+    }
+}
+// paths[p][l] = slot l of the path of leaf idx[p], one thread per (path, slot): the sibling level_l[(j >> l) ^ 1] from the leaf digests
+// (l = 0) or from k_mt_tile's node buffer (levels 1 .. depth back to back), or 32 zero bytes where the shape has none
+__global__ void __launch_bounds__(TPB) k_mt_paths(u32 n_slots /* n_paths x depth */, u32 depth, u32 n, const u32 *__restrict__ idx, const u64 *__restrict__ leaves,
+                                                   const u64 *__restrict__ nodes, u64 *__restrict__ paths /* [n_paths][depth][4], 16-byte aligned */) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_slots) return;
+    const u32 l = t % depth, j = idx[t / depth];
+    u32 w = n; size_t at = 0;      // the width of level l and where it starts in `nodes`
+    for (u32 i = 1; i <= l; i++) { if (i > 1) at += w; w = (w + 1) >> 1; }
+    const u32 sib = (j >> l) ^ 1u;
+    u64 v[4] = {0, 0, 0, 0};
+    if (sib < w) load_words4(v, l == 0 ? leaves + 4 * (size_t)sib : nodes + 4 * (at + sib));
+    store_words4(paths + 4 * (size_t)t, v);
+}
+// verdict[i] of path i: leaf refs[i].y under root refs[i].x (refs == nullptr: leaf i under root 0), one thread per path.  dig: the leaf
+// digests, k_mt_leaves' over the paths' messages or the caller's.  First the malformed checks -- the index against its root's leaf count,
+// every slot the shape leaves empty against zero -- which store 2 and compute nothing; then up to `stride` node blocks, the root block and the
+// compare: 0 equal, 1 not.
+__global__ void __launch_bounds__(64) k_mt_climb(u32 n_paths, const u64 *__restrict__ roots /* [n_roots][4] */, const u32 *__restrict__ n_leaves, const uint2 *__restrict__ refs,
+                                                 const u64 *__restrict__ dig /* [n_paths][4] */, const u64 *__restrict__ paths /* [n_paths][stride][4] */, u32 stride,
+                                                 uint8_t *__restrict__ verdict) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_paths) return;
+    u32 r = 0, j = i;
+    if (refs) { const uint2 q = refs[i]; r = q.x; j = q.y; }
+    const u32 n = n_leaves[r];
+    if (j >= n) { verdict[i] = 2; return; }
+    const u64 *row = paths + 4 * (size_t)i * stride;
+    u32 has = 0, w = n;      // bit l: slot l holds a sibling
+    for (u32 l = 0; l < stride; l++) {
+        if (w > 1 && ((j >> l) ^ 1u) < w) has |= 1u << l;
+        else if (row[4 * l] | row[4 * l + 1] | row[4 * l + 2] | row[4 * l + 3]) { verdict[i] = 2; return; }
+        w = (w + 1) >> 1;
+    }
+    u64 cur[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) cur[q] = dig[4 * (size_t)i + q];
+    for (u32 l = 0; l < stride; l++) {
+        if (!(has >> l & 1u)) continue;
+        u64 sib[4], up[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) sib[q] = row[4 * l + q];
+        if ((j >> l) & 1u) mt_node(up, sib, cur); else mt_node(up, cur, sib);
+#pragma unroll
+        for (int q = 0; q < 4; q++) cur[q] = up[q];
+    }
+    u64 got[4];
+    mt_root(got, n, cur);
+    const u64 *want = roots + 4 * (size_t)r;
+    verdict[i] = (got[0] == want[0]) & (got[1] == want[1]) & (got[2] == want[2]) & (got[3] == want[3]) ? 0 : 1;
 }
 #endif
 

@@ -484,6 +484,17 @@ int rofl_dbg_host_feldman_verify(size_t n_secrets, size_t threshold, const uint8
 // ---- signatures: deterministic Schnorr over Ristretto255 on the commitments and views of a round (k_sig_digest, k_dh_public / k_dh_decode, k_sig_sign / k_sig_verify) ----
 }  // extern "C"
 namespace {
+// the packed messages of a call (signatures, Merkle leaves): offsets that start at 0 and do not decrease, at most 2^30 bytes; *total: the bytes
+int msg_off_check(size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off, size_t *total) {
+    if (msg_off[0] != 0) return fail(ROFL_BAD_PARAM, "the first message offset is 0");
+    for (size_t j = 0; j < n_msgs; j++) {
+        if (msg_off[j + 1] < msg_off[j]) { char buf[96]; snprintf(buf, sizeof buf, "message offset %zu is below the one before it", j + 1); return fail(ROFL_BAD_PARAM, buf); }
+        if (msg_off[j + 1] > ((uint64_t)1 << 30)) return fail(ROFL_BAD_PARAM, "more than 2^30 message bytes in one call");
+    }
+    *total = (size_t)msg_off[n_msgs];
+    if (*total && !msg_bytes) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return ROFL_OK;
+}
 // every check of rofl_sig_sign / rofl_sig_verify, shared with their host routes; keys32: secret keys (sign) or public keys (verify), sig: the
 // signatures read or written, verdict: verify's output; *done: the call is empty and returns 0.  *total: the messages' bytes
 int sig_check(bool sign, size_t n_keys, const uint8_t *keys32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs,
@@ -495,24 +506,20 @@ int sig_check(bool sign, size_t n_keys, const uint8_t *keys32, size_t n_msgs, co
     if (n_keys > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
     if (n_msgs > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 messages in one call");
     if (n > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 signatures in one call");
-    if (msg_off[0] != 0) return fail(ROFL_BAD_PARAM, "the first message offset is 0");
-    for (size_t j = 0; j < n_msgs; j++) {
-        if (msg_off[j + 1] < msg_off[j]) { char buf[96]; snprintf(buf, sizeof buf, "message offset %zu is below the one before it", j + 1); return fail(ROFL_BAD_PARAM, buf); }
-        if (msg_off[j + 1] > ((uint64_t)1 << 30)) return fail(ROFL_BAD_PARAM, "more than 2^30 message bytes in one call");
-    }
-    *total = (size_t)msg_off[n_msgs];
-    if (*total && !msg_bytes) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (int rc = msg_off_check(n_msgs, msg_bytes, msg_off, total)) return rc;
     if (!refs && !(n_keys == n && n_msgs == n)) return fail(ROFL_BAD_PARAM, "without a ref list n_keys, n_msgs and n are equal");
     if (refs) for (size_t i = 0; i < n; i++)
         if (refs[i].key >= n_keys || refs[i].msg >= n_msgs) { char buf[96]; snprintf(buf, sizeof buf, "ref %zu names a key or a message that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
     return sign ? dh_check_keys(n_keys, keys32) : ROFL_OK;
 }
-// h(m) = SHAKE256("rofl-zk/sig/v1/m" || u64le(len) || m)[0 .. 32) on the host's sponge
-void sig_host_digest(uint8_t out[32], const uint8_t *m, uint64_t len) {
-    uint8_t pre[24] = {'r', 'o', 'f', 'l', '-', 'z', 'k', '/', 's', 'i', 'g', '/', 'v', '1', '/', 'm'};
-    memcpy(pre + 16, &len, 8);
+// SHAKE256(label16 || u64le(len) || m)[0 .. 32) on the host's sponge: labelled_digest's bytes
+void host_labelled_digest(uint8_t out[32], const char *label16, const uint8_t *m, uint64_t len) {
+    uint8_t pre[24];
+    memcpy(pre, label16, 16); memcpy(pre + 16, &len, 8);
     Sponge sp(136, 0x1F); sp.absorb(pre, 24); if (len) sp.absorb(m, (size_t)len); sp.squeeze(out, 32);
 }
+// h(m) = SHAKE256("rofl-zk/sig/v1/m" || u64le(len) || m)[0 .. 32)
+void sig_host_digest(uint8_t out[32], const uint8_t *m, uint64_t len) { host_labelled_digest(out, "rofl-zk/sig/v1/m", m, len); }
 }  // namespace
 extern "C" {
 // The lane's copies of the secret keys -- pinned staging and device workspace -- are overwritten with zeros before the call returns or
@@ -969,4 +976,177 @@ int rofl_dbg_var_mul2(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, cons
 }
 int rofl_dbg_var_mul_sum(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms) {
     return dbg_var_mul_device(false, n, k1_32, p1_32, k2_32, p2_32, out32, kernel_ms);
+}
+// ---- Merkle trees: a round's broadcast behind one root, single entries proved by a path (k_mt_leaves, k_mt_tile, k_mt_paths / k_mt_climb) ----
+}  // extern "C"
+namespace {
+u32 mt_depth(size_t n) { u32 d = 0; while (((size_t)1 << d) < n) d++; return d; }      // bit_length(n - 1)
+// every check of rofl_merkle_build, shared with its host route; *done: the call is empty and returns 0.  *total: the bytes behind msg_bytes
+int merkle_build_check(size_t n, const uint8_t *msg_bytes, const uint64_t *msg_off, const uint8_t *root_out32, size_t n_paths, const uint32_t *path_idx,
+                       const uint8_t *paths_out32, size_t *total, bool *done) {
+    *done = n == 0 && n_paths == 0; *total = 0;
+    if (*done) return ROFL_OK;
+    if (n == 0) return fail(ROFL_BAD_PARAM, "paths of a tree without leaves");
+    if (!root_out32 || (!msg_off && !msg_bytes)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 leaves in one call");
+    if (msg_off) { if (int rc = msg_off_check(n, msg_bytes, msg_off, total)) return rc; }
+    else *total = n * 32;
+    const size_t depth = mt_depth(n);
+    if (n_paths > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 paths in one call");
+    if (n_paths * depth * 32 > ((size_t)1 << 30)) return fail(ROFL_BAD_PARAM, "more than 2^30 path bytes in one call");
+    if (n_paths && (!path_idx || (depth && !paths_out32))) return fail(ROFL_BAD_PARAM, "bad parameter");
+    for (size_t i = 0; i < n_paths; i++)
+        if (path_idx[i] >= n) { char buf[96]; snprintf(buf, sizeof buf, "path %zu names a leaf that is not in the tree", i); return fail(ROFL_BAD_PARAM, buf); }
+    return ROFL_OK;
+}
+// every check of rofl_merkle_verify, shared with its host route.  An index >= its root's leaf count is no parameter error: it is verdict 2
+int merkle_verify_check(size_t n_roots, const uint8_t *root32, const uint32_t *n_leaves, size_t n_paths, const rofl_merkle_ref_t *refs, const uint8_t *msg_bytes,
+                        const uint64_t *msg_off, const uint8_t *paths32, size_t stride, const uint8_t *verdict_out, size_t *total, bool *done) {
+    *done = n_paths == 0; *total = 0;
+    if (*done) return ROFL_OK;
+    if (!root32 || !n_leaves || !verdict_out || (!msg_off && !msg_bytes) || (stride && !paths32)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_roots == 0) return fail(ROFL_BAD_PARAM, "paths without roots");
+    if (n_roots > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 roots in one call");
+    if (n_paths > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 paths in one call");
+    if (stride > 20) return fail(ROFL_BAD_PARAM, "a stride above 20");
+    if (n_paths * stride * 32 > ((size_t)1 << 30)) return fail(ROFL_BAD_PARAM, "more than 2^30 path bytes in one call");
+    for (size_t r = 0; r < n_roots; r++)
+        if (n_leaves[r] == 0 || n_leaves[r] > (1u << 20)) { char buf[96]; snprintf(buf, sizeof buf, "the leaf count of root %zu is not in [1, 2^20]", r); return fail(ROFL_BAD_PARAM, buf); }
+    if (!refs && n_roots != 1) return fail(ROFL_BAD_PARAM, "without a ref list there is one root");
+    for (size_t i = 0; i < (refs ? n_paths : 1); i++) {
+        const size_t r = refs ? refs[i].root : 0;
+        char buf[96];
+        if (r >= n_roots) { snprintf(buf, sizeof buf, "ref %zu names a root that is not in the call", i); return fail(ROFL_BAD_PARAM, buf); }
+        if (stride < mt_depth(n_leaves[r])) { snprintf(buf, sizeof buf, "the stride is below the depth of root %zu", r); return fail(ROFL_BAD_PARAM, buf); }
+    }
+    if (msg_off) return msg_off_check(n_paths, msg_bytes, msg_off, total);
+    *total = n_paths * 32;
+    return ROFL_OK;
+}
+void mt_host_node(uint8_t out[32], const uint8_t a[32], const uint8_t b[32]) {
+    uint8_t m[80];
+    memcpy(m, "rofl-zk/mtr/v1/n", 16); memcpy(m + 16, a, 32); memcpy(m + 48, b, 32);
+    Sponge sp(136, 0x1F); sp.absorb(m, sizeof m); sp.squeeze(out, 32);
+}
+void mt_host_root(uint8_t out[32], uint64_t n, const uint8_t top[32]) {
+    uint8_t m[56];
+    memcpy(m, "rofl-zk/mtr/v1/r", 16); memcpy(m + 16, &n, 8); memcpy(m + 24, top, 32);
+    Sponge sp(136, 0x1F); sp.absorb(m, sizeof m); sp.squeeze(out, 32);
+}
+}  // namespace
+extern "C" {
+size_t rofl_dbg_merkle_tile_leaves(void) { return ROFL_MT_TILE; }
+// nothing here is secret: messages, digests, roots, paths, verdicts
+int rofl_merkle_build(size_t n, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *root_out32, uint8_t *leaves_out32, size_t n_paths, const uint32_t *path_idx,
+                      uint8_t *paths_out32) {
+    bool done; size_t total;
+    if (int rc = merkle_build_check(n, msg_bytes, msg_off, root_out32, n_paths, path_idx, paths_out32, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    const u32 depth = mt_depth(n);
+    const bool hashed = !msg_off;      // msg_bytes holds the leaf digests
+    int rc = guarded([&]() -> int {
+        StagedCall st; Ctx &C = st.C;
+        const InPart off = st.in(msg_off, (n + 1) * 8), idx = st.in(path_idx, n_paths * 4), msg = hashed ? st.in(msg_bytes, total, kAlign16) : st.in(msg_bytes, total, kPadded);
+        const OutPart root = st.out(root_out32, 32, kAlign16), paths = st.out(paths_out32, n_paths * depth * 32, kAlign16);
+        const bool own_leaves = !hashed && !leaves_out32;      // the leaf digests stay in the workspace: nobody asked for them
+        OutPart leaves{0};
+        if (!hashed && leaves_out32) leaves = st.out(leaves_out32, n * 32, kAlign16);
+        size_t n_nodes = 0;      // levels 1 .. depth back to back
+        for (size_t w = n; w > 1;) { w = (w + 1) / 2; n_nodes += w; }
+        u64 *nodes = st.work<u64>(4 * (n_nodes + (own_leaves ? n : 0)));
+        st.upload();
+        const u64 *lf = hashed ? st.dev<u64>(msg) : own_leaves ? nodes + 4 * n_nodes : st.dev<u64>(leaves);
+        if (!hashed) ROFL_LAUNCH(k_mt_leaves, per_item(n), dim3(64), 0, C.stream, (u32)n, st.dev<uint8_t>(msg), st.dev<u64>(off), const_cast<u64 *>(lf));
+        // ceil(depth / log2 T) launches (one for a single leaf): each takes the level `in` up log2 T levels, and the next starts on its tile roots
+        const u64 *in = lf; u64 *out = nodes; size_t w = n;
+        do {
+            ROFL_LAUNCH(k_mt_tile, dim3((unsigned)((w + ROFL_MT_TILE - 1) / ROFL_MT_TILE)), dim3(ROFL_MT_TILE / 2), 0, C.stream, (u32)w, in, out, (u64)n, st.dev<u64>(root));
+            for (u32 k = 0; k < ROFL_MT_TILE_LOG2 && w > 1; k++) { w = (w + 1) / 2; in = out; out += 4 * w; }
+        } while (w > 1);
+        if (n_paths && depth)
+            ROFL_LAUNCH(k_mt_paths, grid1(n_paths * depth), dim3(TPB), 0, C.stream, (u32)(n_paths * depth), depth, (u32)n, st.dev<u32>(idx), lf, (const u64 *)nodes, st.dev<u64>(paths));
+        st.finish();
+        return ROFL_OK;
+    });
+    if (rc == ROFL_OK && hashed && leaves_out32) memcpy(leaves_out32, msg_bytes, n * 32);
+    return rc;
+}
+int rofl_merkle_verify(size_t n_roots, const uint8_t *root32, const uint32_t *n_leaves, size_t n_paths, const rofl_merkle_ref_t *refs, const uint8_t *msg_bytes,
+                       const uint64_t *msg_off, const uint8_t *paths32, size_t stride, uint8_t *verdict_out) {
+    bool done; size_t total;
+    if (int rc = merkle_verify_check(n_roots, root32, n_leaves, n_paths, refs, msg_bytes, msg_off, paths32, stride, verdict_out, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    const bool hashed = !msg_off;
+    return guarded([&]() -> int {
+        StagedCall st; Ctx &C = st.C;
+        const InPart roots = st.in(root32, n_roots * 32), cnt = st.in(n_leaves, n_roots * 4), rf = st.in(refs, n_paths * sizeof(rofl_merkle_ref_t)), off = st.in(msg_off, (n_paths + 1) * 8),
+                     pt = st.in(paths32, n_paths * stride * 32), msg = hashed ? st.in(msg_bytes, total) : st.in(msg_bytes, total, kPadded);
+        const OutPart verdict = st.out(verdict_out, n_paths);
+        u64 *ws = st.work<u64>(hashed ? 0 : n_paths * 4);
+        st.upload();
+        const u64 *dig = hashed ? st.dev<u64>(msg) : ws;
+        if (!hashed) ROFL_LAUNCH(k_mt_leaves, per_item(n_paths), dim3(64), 0, C.stream, (u32)n_paths, st.dev<uint8_t>(msg), st.dev<u64>(off), ws);
+        ROFL_LAUNCH(k_mt_climb, per_item(n_paths), dim3(64), 0, C.stream, (u32)n_paths, st.dev<u64>(roots), st.dev<u32>(cnt), st.dev<uint2>(rf), dig, st.dev<u64>(pt), (u32)stride,
+                    st.dev<uint8_t>(verdict));
+        st.finish();
+        return ROFL_OK;
+    });
+}
+// the two calls on the host's sponge, one thread, no GPU: same parameters, same checks, same bytes and verdicts
+int rofl_dbg_host_merkle_build(size_t n, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *root_out32, uint8_t *leaves_out32, size_t n_paths, const uint32_t *path_idx,
+                               uint8_t *paths_out32) {
+    bool done; size_t total;
+    if (int rc = merkle_build_check(n, msg_bytes, msg_off, root_out32, n_paths, path_idx, paths_out32, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    const u32 depth = mt_depth(n);
+    std::vector<std::vector<uint8_t>> lv(depth + 1);
+    lv[0].resize(n * 32);
+    if (!msg_off) memcpy(lv[0].data(), msg_bytes, n * 32);
+    else for (size_t j = 0; j < n; j++) host_labelled_digest(lv[0].data() + 32 * j, "rofl-zk/mtr/v1/l", msg_bytes + msg_off[j], msg_off[j + 1] - msg_off[j]);
+    for (u32 l = 0; l < depth; l++) {
+        const size_t w = lv[l].size() / 32, up = (w + 1) / 2;
+        lv[l + 1].resize(up * 32);
+        for (size_t i = 0; i < w / 2; i++) mt_host_node(lv[l + 1].data() + 32 * i, lv[l].data() + 64 * i, lv[l].data() + 64 * i + 32);
+        if (w & 1) memcpy(lv[l + 1].data() + 32 * (up - 1), lv[l].data() + 32 * (w - 1), 32);
+    }
+    mt_host_root(root_out32, n, lv[depth].data());
+    if (leaves_out32) memcpy(leaves_out32, lv[0].data(), n * 32);
+    for (size_t p = 0; p < n_paths; p++)
+        for (u32 l = 0; l < depth; l++) {
+            const size_t sib = ((size_t)path_idx[p] >> l) ^ 1;
+            uint8_t *slot = paths_out32 + (p * depth + l) * 32;
+            if (sib < lv[l].size() / 32) memcpy(slot, lv[l].data() + 32 * sib, 32); else memset(slot, 0, 32);
+        }
+    return ROFL_OK;
+}
+int rofl_dbg_host_merkle_verify(size_t n_roots, const uint8_t *root32, const uint32_t *n_leaves, size_t n_paths, const rofl_merkle_ref_t *refs, const uint8_t *msg_bytes,
+                                const uint64_t *msg_off, const uint8_t *paths32, size_t stride, uint8_t *verdict_out) {
+    bool done; size_t total;
+    if (int rc = merkle_verify_check(n_roots, root32, n_leaves, n_paths, refs, msg_bytes, msg_off, paths32, stride, verdict_out, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    const uint8_t zero[32] = {0};
+    for (size_t i = 0; i < n_paths; i++) {
+        const size_t r = refs ? refs[i].root : 0, j = refs ? refs[i].index : i, n = n_leaves[r];
+        const uint8_t *row = paths32 + i * stride * 32;
+        uint8_t &v = verdict_out[i];
+        v = j >= n ? 2 : 0;
+        bool has[20]; size_t w = n;
+        for (size_t l = 0; l < stride && v == 0; l++) {
+            has[l] = w > 1 && ((j >> l) ^ 1) < w;
+            if (!has[l] && memcmp(row + 32 * l, zero, 32) != 0) v = 2;
+            w = (w + 1) / 2;
+        }
+        if (v) continue;
+        uint8_t cur[32], up[32];
+        if (!msg_off) memcpy(cur, msg_bytes + 32 * i, 32);
+        else host_labelled_digest(cur, "rofl-zk/mtr/v1/l", msg_bytes + msg_off[i], msg_off[i + 1] - msg_off[i]);
+        for (size_t l = 0; l < stride; l++) {
+            if (!has[l]) continue;
+            if ((j >> l) & 1) mt_host_node(up, row + 32 * l, cur); else mt_host_node(up, cur, row + 32 * l);
+            memcpy(cur, up, 32);
+        }
+        mt_host_root(up, n, cur);
+        v = memcmp(up, root32 + 32 * r, 32) == 0 ? 0 : 1;
+    }
+    return ROFL_OK;
 }

@@ -51,7 +51,9 @@ int rofl_dbg_msm(const uint8_t *scalars32, const uint8_t *points32, size_t n, ui
 /* The same driver with the shape and the scalars chosen by the caller, for the tests that push its fixed-size structures (bucket lists,
  * slots, the overflow list, coarse bins) to their capacity and over it.  Both run ONE msm_run; scalars are reduced mod l as rofl_dbg_msm
  * does.  The L/R-merged mode of the inner-product rounds (MsmOpt::lr_nh != 0) needs scalar arrays in which every term belongs to one side
- * by construction (k_lr_first, k_ipp_round) and is NOT reachable through these entries.
+ * by construction (k_lr_first, k_ipp_round) and is NOT reachable through these entries: tests/test_gpu_nonce_collide.py drives it to the
+ * same capacities through the prover itself, with nonce streams (Nonce.stream) that make the rounds' scalars collide, and reads every
+ * round's attempts with rofl_dbg_msm_trace_all.
  *   rofl_dbg_msm_many:  out32[p] = sum_i scalars32[p][i] * points32[i]: np generic problems of n terms over one shared point array
  *                       (decoded as rofl_dbg_msm decodes it; 5 = a point that is no Ristretto encoding).
  *   rofl_dbg_msm_fixed: out32[p] = sum_k s[p][k] G_k + sum_k s[p][N + k] H_k over the generators of BulletproofGens::new(n_bits, m), N = n_bits m,
@@ -75,6 +77,16 @@ enum { ROFL_MSM_FIXED_BASE = 0, ROFL_MSM_SMALL = 1, ROFL_MSM_SLOTS = 2, ROFL_MSM
 enum { ROFL_MSM_FIN_HOST = 0, ROFL_MSM_FIN_DEVICE = 1, ROFL_MSM_FIN_HOST8 = 2 };
 typedef struct { uint32_t kind, two, c, W, cap, cap_bin, sets, small_group, finisher, overflow, repeated; } rofl_msm_attempt_t;
 int rofl_dbg_msm_trace(rofl_msm_attempt_t *attempts_out, size_t max, size_t *count_out);
+/* Every msm_run of the calling thread, not only the last: a prover call makes one per inner-product round.  rofl_dbg_msm_trace_begin empties
+ * the calling thread's store and switches it on (it is off until then, and stays on for that thread); from then on each msm_run appends one
+ * record when it returns: tag (which hop of its caller: 99 = the S commitment, 100 + r = inner-product round r, 0 = unknown), np problems of
+ * n terms, lr = 1 for the L/R-merged mode (np = 2 x chunks, n = 2 n_g: one scalar array over [Gc | Hc] serves problems 2q and 2q + 1), and
+ * its n_attempts attempts as above.  rofl_dbg_msm_trace_all copies at most `max` records, oldest first; *count_out is the number of msm_runs
+ * since begin (the store keeps the first 1024).  The verifier's paired MSMs (msm_run2) are not recorded.  A few stores per attempt on the
+ * host, nothing that a launch depends on.  tests/test_gpu_nonce_collide.py reads the repeats of every round of a proof with it. */
+typedef struct { uint32_t tag, np, n, lr, n_attempts; rofl_msm_attempt_t attempts[8]; } rofl_msm_run_t;
+int rofl_dbg_msm_trace_begin(void);
+int rofl_dbg_msm_trace_all(rofl_msm_run_t *out, size_t max, size_t *count_out);
 /* RangeProof::verify_multiple(&BulletproofGens::new(gens_capacity, m), &PedersenGens::default(), &mut Transcript::new(label), commits, n_bits)
  * on one aggregated proof, called the way upstream's own tests call it: any transcript label, the m (a power of two) commitments as they
  * are -- no shift by 2^(n-1) B, no padding.  The operator API fixes the labels ("RangeProof", "L2RangeProof") and the shift as the reference

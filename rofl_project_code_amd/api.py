@@ -72,7 +72,8 @@ class Nonce:
     """Prover randomness (the reference uses rand::thread_rng inside bulletproofs).
 
     Nonce.seeded(seed32): deterministic SHAKE256 stream; Nonce.stream(bytes): explicit 64-byte wide scalars
-    in the reference draw order; Nonce.random(): fresh OS randomness (what a deployment uses)."""
+    in the reference draw order; Nonce.random(): fresh OS randomness (what a deployment uses).  A stream with repeated blocks
+    (equal nonces) is accepted and proved bit for bit like any other, only slower: the rounds' MSMs are repeated on slower variants."""
 
     def __init__(self, mode, seed=None, stream=None):
         self.mode, self.seed, self._stream = mode, seed, stream
@@ -271,18 +272,39 @@ MSM_KINDS = ("fixed_base", "small", "slots", "count_sort")
 MSM_FINISHERS = ("host", "device", "host8")
 
 
+def _attempt_dict(a):
+    d = {f[0]: int(getattr(a, f[0])) for f in _MsmAttempt._fields_}
+    d["kind"], d["finisher"], d["two"], d["repeated"] = MSM_KINDS[d["kind"]], MSM_FINISHERS[d["finisher"]], bool(d["two"]), bool(d["repeated"])
+    return d
+
+
 def msm_trace():
     """test hook (include/rofl_zk_debug.h): the attempts of the calling thread's last MSM, first to last, one dict per attempt --
     kind (MSM_KINDS), two, c, W, cap, cap_bin, sets, small_group, finisher (MSM_FINISHERS), overflow (the raw word), repeated"""
     buf = (_MsmAttempt * 8)()
     cnt = ctypes.c_size_t()
     _check(lib().rofl_dbg_msm_trace(buf, _sz(8), ctypes.byref(cnt)))
-    out = []
-    for a in buf[:min(cnt.value, 8)]:
-        d = {f[0]: int(getattr(a, f[0])) for f in _MsmAttempt._fields_}
-        d["kind"], d["finisher"], d["two"], d["repeated"] = MSM_KINDS[d["kind"]], MSM_FINISHERS[d["finisher"]], bool(d["two"]), bool(d["repeated"])
-        out.append(d)
-    return out
+    return [_attempt_dict(a) for a in buf[:min(cnt.value, 8)]]
+
+
+class _MsmRun(ctypes.Structure):
+    """rofl_msm_run_t"""
+    _fields_ = [(f, ctypes.c_uint32) for f in ("tag", "np", "n", "lr", "n_attempts")] + [("attempts", _MsmAttempt * 8)]
+
+
+def msm_trace_begin():
+    """test hook (include/rofl_zk_debug.h): empty the calling thread's store of MSM runs and switch it on"""
+    _check(lib().rofl_dbg_msm_trace_begin())
+
+
+def msm_trace_all(max_runs=1024):
+    """test hook (include/rofl_zk_debug.h): every msm_run of the calling thread since msm_trace_begin(), oldest first, one dict per run --
+    tag (99 = the S commitment, 100 + r = inner-product round r), np, n, lr (the L/R-merged mode), attempts (as msm_trace gives them)"""
+    buf = (_MsmRun * max_runs)()
+    cnt = ctypes.c_size_t()
+    _check(lib().rofl_dbg_msm_trace_all(buf, _sz(max_runs), ctypes.byref(cnt)))
+    return [{"tag": int(r.tag), "np": int(r.np), "n": int(r.n), "lr": bool(r.lr), "attempts": [_attempt_dict(a) for a in r.attempts[:min(int(r.n_attempts), 8)]]}
+            for r in buf[:min(cnt.value, max_runs, 1024)]]
 
 
 def dbg_msm_many(scalars32, points32):

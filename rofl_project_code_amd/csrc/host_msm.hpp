@@ -364,6 +364,24 @@ std::atomic<uint64_t> g_msm_stat[4];
 constexpr u32 kMsmTraceMax = 8;
 thread_local rofl_msm_attempt_t t_msm_trace[kMsmTraceMax];
 thread_local u32 t_msm_trace_n = 0;
+// rofl_dbg_msm_trace_all: a prover call makes one msm_run per round and the list above keeps the last one only.  After
+// rofl_dbg_msm_trace_begin every msm_run of the calling thread appends its shape and its attempts here when it returns (msm_run2's
+// interleaved pair is not recorded).  Off until begin is called: one thread-local flag read per msm_run; at most kMsmRunsMax records are
+// kept, later ones are counted only.
+constexpr size_t kMsmRunsMax = 1024;
+static_assert(sizeof(((rofl_msm_run_t *)nullptr)->attempts) == kMsmTraceMax * sizeof(rofl_msm_attempt_t), "rofl_msm_run_t holds a whole attempt list");
+thread_local bool t_msm_runs_on = false;
+thread_local size_t t_msm_runs_n = 0;
+thread_local std::vector<rofl_msm_run_t> t_msm_runs;
+static void msm_runs_record(u32 tag, size_t np, size_t n, bool lr) {
+    if (!t_msm_runs_on) return;
+    if (t_msm_runs_n++ >= kMsmRunsMax) return;
+    rofl_msm_run_t rec{};
+    rec.tag = tag; rec.np = (uint32_t)np; rec.n = (uint32_t)n; rec.lr = lr ? 1u : 0u;
+    rec.n_attempts = std::min(t_msm_trace_n, kMsmTraceMax);
+    for (u32 i = 0; i < rec.n_attempts; i++) rec.attempts[i] = t_msm_trace[i];
+    t_msm_runs.push_back(rec);
+}
 bool msm_retry_inner(const MsmJob &J, MsmAllow &al);
 bool msm_retry(const MsmJob &J, MsmAllow &al) {
     const bool small = J.kind == MsmKind::Small, two = J.two;
@@ -524,6 +542,7 @@ void msm_run(Ctx &C, const std::vector<MsmProb> &probs, size_t n, std::vector<ge
           if (opt.tag) { double &e = C.wait_ms[wkey]; e = e == 0 ? w : std::min(w, 0.5 * (e + w)); } }
         if (msm_retry(J, al)) continue;
         msm_finish(C, J, results, opt);
+        msm_runs_record(opt.tag, probs.size(), n, opt.lr_nh != 0);
         return;
     }
 }

@@ -2539,6 +2539,13 @@ int rofl_dbg_msm_trace(rofl_msm_attempt_t *attempts_out, size_t max, size_t *cou
     for (size_t i = 0; i < max && i < t_msm_trace_n; i++) attempts_out[i] = t_msm_trace[i];
     return ROFL_OK;
 }
+int rofl_dbg_msm_trace_begin(void) { t_msm_runs.clear(); t_msm_runs_n = 0; t_msm_runs_on = true; return ROFL_OK; }
+int rofl_dbg_msm_trace_all(rofl_msm_run_t *out, size_t max, size_t *count_out) {
+    if (!count_out || (max && !out)) return ROFL_BAD_PARAM;
+    *count_out = t_msm_runs_n;
+    for (size_t i = 0; i < max && i < t_msm_runs.size(); i++) out[i] = t_msm_runs[i];
+    return ROFL_OK;
+}
 // bulletproofs' RangeProof::verify_multiple(&bp_gens, &pc_gens, &mut Transcript::new(label), &value_commitments, n) on ONE aggregated proof
 // exactly as upstream's own tests call it: any transcript label (upstream's serialized-proof vectors use b"Deserialize-And-Verify Test"),
 // the commitments as they are (no shift, no padding: m must be a power of two), generators of capacity >= n.  If byte vectors of

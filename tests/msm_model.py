@@ -283,6 +283,130 @@ def predict_generic(problems):
     return out
 
 
+# ---- the same policy for the L/R-merged launches of the inner-product rounds (MsmOpt::lr_nh != 0): ONE scalar array of n = 2 n_g terms over
+# [Gc | Hc] per chunk serves problems 2q (L) and 2q + 1 (R); every term belongs to one side, so a problem has per_side = n / 2 terms
+BIN_TAIL = 2048           # MSM_BIN_TAIL: entries of a coarse bin's tail region
+FB_THREADS = 1 << 19      # Ctx::msm_fb_threads: accumulate threads a fixed-base launch asks for when it is alone on the device
+
+
+def bin_cap(avg):
+    """msm_bin_cap at the default ROFL_MSM_BIN_SIGMA = 8: twice the mean load of a bin, eight standard deviations, 64, rounded up to 64"""
+    hot, dev = 2 * avg, 1
+    while dev * dev < hot:
+        dev += 1
+    return (hot + 8 * dev + 64 + 63) // 64 * 64
+
+
+def _slot_cap(B, n):
+    cap = 16
+    while cap < 256 and cap * B < 4 * n:
+        cap *= 2
+    return cap
+
+
+def merged_generic_plan(n, nq):
+    """msm_plan_job for a generic merged launch of nq chunks (np = 2 nq problems) with n = 2 n_g merged terms: the window width follows n and
+    np, everything that is sized per problem follows per_side = n / 2; `cap` from 4 n / B for the layout of each variant"""
+    np_, per_side = 2 * nq, n // 2
+    t10 = 2048 if np_ >= 32 else 512
+    c = 16 if n >= 1 << 17 else 13 if n >= 8192 else 10 if n >= t10 else 7 if n >= 64 else 4
+    c_small = 10 if (per_side <= 8192 and c > 10 and np_ * 26 <= 512) else c
+    Ps = plan(c_small)
+    Bs = Ps["B"]
+    small_cap = 64 if per_side <= 8 * Bs else 72
+    small_lds = max(Bs * 4 * (1 + small_cap), ((Bs // 8) * 4 + (Bs // 16) * 5 + 1) * SIZEOF_GE, (Bs + Bs * 3 // 4 + 1) * SIZEOF_GE)
+    small = per_side <= 8192 and c_small <= 10 and per_side <= 16 * Bs and (np_ * Ps["W"] <= 512 or small_lds <= 24 * 1024)
+    return {"c": c, "per_side": per_side, "small": small, "c_small": c_small, "small_cap": small_cap, "cap_small": _slot_cap(Bs, n),
+            "small_group": 4 if (small and Bs == 64 and np_ * Ps["W"] > 512) else 1, "cap": _slot_cap(plan(c)["B"], n)}
+
+
+def merged_fixed_plan(n_g, nq, stride, c=16, want=FB_THREADS):
+    """the fixed-base branch of msm_plan_job for a merged launch over the window table of a shape with `stride` = 2 N generators: bucket sets
+    per problem, windows per set, slots per bucket, and -- from 8192 terms a side on, at 2^14 or 2^15 buckets -- the two-level sort with the
+    capacity of its coarse bins.  per_side = n_g."""
+    P = plan(c)
+    W, B, per_side = P["W"], P["B"], n_g
+    sets = W
+    for sdiv in range(1, W + 1):
+        if W % sdiv == 0 and nq * 2 * sdiv * B >= want:
+            sets = sdiv
+            break
+    wide_b = B in (32768, 16384)
+    if wide_b and per_side >= 8192:
+        while sets < W and bin_cap(per_side * (W // sets) // 512) * 4 + 1024 > 96 * 1024:
+            sets += 1
+            while sets < W and W % sets:
+                sets += 1
+    wps = W // sets
+    cap = 16
+    while cap < 2048 and cap * B < 3 * per_side * (wps + 1):
+        cap *= 2
+    if wps == 1:
+        cap *= 2
+    two = wide_b and W * stride <= 1 << 24
+    nbins, fbits, cap_bin = 256, 7 if B == 32768 else 6, 0
+    if two:
+        cap_bin = bin_cap(per_side * wps // nbins)
+        if cap_bin * 4 + 1024 > 96 * 1024:
+            nbins, fbits = 512, fbits - 1
+            cap_bin = bin_cap(per_side * wps // nbins)
+        if cap_bin * 4 + 1024 > 96 * 1024 or per_side < 8192:
+            two = False
+    return {"c": c, "W": W, "B": B, "per_side": per_side, "sets": sets, "wps": wps, "cap": cap, "two": two, "cap_bin": cap_bin if two else 0,
+            "nbins": nbins, "fbits": fbits}
+
+
+def bin_loads(set_loads, fbits):
+    """[sets][B] bucket loads -> [sets][bins]: the entries of each coarse bin (bucket >> fbits) of the two-level sort"""
+    ld = np.asarray(set_loads)
+    return ld.reshape(ld.shape[0], -1, 1 << fbits).sum(axis=2)
+
+
+def bin_verdict(max_bin_load, cap_bin):
+    """Does a coarse bin with this many entries overflow?  True above cap_bin + BIN_TAIL (a bin's main region and its tail are all the room
+    it has), False up to cap_bin - 64 (what msm_bin_cap sizes the main region for; the 64 on top are its allowance for the left-overs),
+    None in between: level 1 reserves main-region space in multiples of 32 per tile, so the exact capacity is not a function of the loads."""
+    if max_bin_load > cap_bin + BIN_TAIL:
+        return True
+    return False if max_bin_load <= cap_bin - 64 else None
+
+
+def predict_merged(sides, n_g, stride, fixed_base):
+    """The attempts msm_run makes for ONE merged launch.  sides: [np][per_side][32], problem 2q = the L terms of chunk q, 2q + 1 its R terms.
+    -> list of dicts kind, two, c, W, cap, cap_bin, overflow, repeated; overflow is None where the word is only a flag (small launch, two-level
+    sort: non-zero exactly when repeated) and repeated is None where bin_verdict cannot tell (the list then goes on as if it were repeated)."""
+    sides = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 32) for s in sides]
+    nq, n = len(sides) // 2, 2 * n_g
+    out = []
+
+    def att(kind, two, c, cap, cap_bin, overflow, repeated):
+        out.append({"kind": kind, "two": two, "c": c, "W": plan(c)["W"], "cap": cap, "cap_bin": cap_bin, "overflow": overflow, "repeated": repeated})
+
+    if fixed_base:
+        f = merged_fixed_plan(n_g, nq, stride)
+        set_loads = [merge_sets(loads(s, f["c"]), f["sets"]) for s in sides]
+        if f["two"]:
+            verdict = bin_verdict(max(int(bin_loads(sl, f["fbits"]).max()) for sl in set_loads), f["cap_bin"])
+            att("fixed_base", True, f["c"], f["cap"], f["cap_bin"], None, verdict)
+            if verdict is False:
+                return out
+        word = sum(overflow(sl, f["cap"]) for sl in set_loads)
+        att("fixed_base", False, f["c"], f["cap"], 0, word, word > OVF_MAX)
+        if word <= OVF_MAX:
+            return out
+    g = merged_generic_plan(n, nq)
+    if g["small"]:
+        over = any(int(loads(s, g["c_small"]).max()) > g["small_cap"] for s in sides)
+        att("small", False, g["c_small"], g["cap_small"], 0, None, over)
+        if not over:
+            return out
+    word = sum(overflow(loads(s, g["c"]), g["cap"]) for s in sides)
+    att("slots", False, g["c"], g["cap"], 0, word, word > OVF_MAX)
+    if word > OVF_MAX:
+        att("count_sort", False, g["c"], g["cap"], 0, 0, False)
+    return out
+
+
 def finisher(np_, fixed_base, host8):
     """who combines the windows: the host's chains; from eight generic problems on the eight-lane host chains where the CPU has them, else
     from 32 problems on the device"""

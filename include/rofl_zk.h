@@ -222,6 +222,41 @@ int rofl_quantize_prob(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, co
  * on the calling thread's device and lane; the `devices` option does not apply.  Not constant time. */
 int rofl_noise_binomial(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, const float *const *values, size_t first, size_t d, uint32_t k,
                         size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
+/* Discrete Gaussian noise: the second noise mechanism, for the analyses of secure aggregation that are written for it (Canonne, Kamath,
+ * Steinke 2020; Kairouz et al. 2021).  The exact, integer-only rejection sampler of Canonne-Kamath-Steinke on a seeded stream: its cost
+ * does not grow with sigma, sigma2 is any integer from 1 to 2^24 (sigma up to 4096 grid steps), and host and device give the same bytes.
+ * Outputs are f32 grid values through the value rule of rofl_noise_binomial: proofs, commitments, wire bytes, verifiers and the server
+ * stay as they are.
+ *   stream: every ELEMENT has one of its own, 256 blocks = 8 192 little-endian u32 words: block j of element index e = first + i is the
+ *   first 128 bytes of SHAKE256("rofl-zk/dgaus/v1" || seed[32] || u64le((e << 8) | j)); word w of the stream is word w & 31 of block
+ *   w >> 5, and words are consumed in order.  A draw past word 8 191 ends the element: its noise is 0.
+ *   draws: below(D) for 1 <= D < 2^64, with b = bit_length(D - 1): b = 0 returns 0 and consumes nothing; otherwise repeat: take one word
+ *   if b <= 32, else two (lo first, then hi; the value is lo | hi << 32), mask to the low b bits, return the value if it is < D.
+ *   bit() = next word & 1.
+ *   sampler for s2 = sigma2, t = isqrt(s2) + 1, all in unsigned 64-bit integers; "restart" = back to step 1, the stream goes on:
+ *     frac(n, D), Bernoulli(exp(-n / D)) for 0 <= n <= D:  K = 1; while below(D K) < n: K += 1; return K & 1.
+ *     expo(n, D), Bernoulli(exp(-n / D)) for any n:  f = n / D; f times: if frac(1, 1) == 0 return 0; then return frac(n - f D, D).
+ *     1. U = below(t); if frac(U, t) == 0 restart.
+ *     2. V = 0; while V < 64 and frac(1, 1) == 1: V += 1; if V == 64 restart.
+ *     3. X = U + t V; B = bit(); if B == 1 and X == 0 restart.
+ *     4. a = X t - s2 (signed); if expo(a^2, 2 s2 t^2) == 0 restart.
+ *     5. the noise n_e is -X if B else X.
+ *   Bounds: X <= 64 t - 1 <= 262 207; |a| <= 64 t^2 < 2^31; 2 s2 t^2 < 2^50; K <= 8 192, since every below(D) with D > 1 consumes a
+ *   word, so D K < 2^63.  The two truncations (V < 64, 8 192 words) have probability below e^-64; they make the rule total.
+ *   n_e has the discrete Gaussian distribution P(x) ~ exp(-x^2 / (2 sigma2)): mean 0, variance within 10^-3 of sigma2 from sigma2 = 1
+ *   up.  The sum of n independent ones is close to, and not exactly, a discrete Gaussian of n sigma2 (Kairouz et al. 2021).
+ *   out[v][i] = steps 1 - 4 of the value rule of rofl_noise_binomial with this n_e, saturation at the clip bound included.
+ * Everything else is as rofl_noise_binomial: n_vec vectors in ONE launch, each with its own seed, input and output in host or device
+ * memory in any combination, out[v] may be values[v]; a stream per element makes the runs of a vector taken with `first` concatenate to
+ * the bytes of the unsplit call.  Returns 11 before the device is touched for the bad-parameter cases of rofl_quantize_prob, for
+ * sigma2 = 0 or sigma2 > 2^24, and for first + d > 2^55; n_vec = 0 or d = 0 returns 0 and writes nothing.  When every pointer is host
+ * memory and n_vec * d is below a fixed, measured threshold the rule runs on the host, compiled from the kernel's
+ * source: same bytes, no device needed.  The seed is a per-round secret of the client: seeds never appear in rofl_last_error, and the
+ * library's own copies are overwritten with zeros before the call returns.  The call runs on the calling thread's device and lane; the
+ * `devices` option does not apply.  NOT constant time: a rejection sampler takes as long as its draws make it, so the time an element
+ * takes depends on its noise. */
+int rofl_noise_dgauss(size_t n_vec, const uint8_t *seeds32 /* n_vec x 32 */, const float *const *values, size_t first, size_t d, uint32_t sigma2,
+                      size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
 /* Norm clipping: an update is projected onto the L2 ball of max_sq grid steps^2 ON the fixed-point grid, the step a client takes after
  * rounding and before noise, so that the sum of squares the L2 sum proof computes for it is at most max_sq by construction instead of
  * being found too large (NormOutOfRangeError, 7) after the commitments.  The rule is integer arithmetic on step counts: host, device and

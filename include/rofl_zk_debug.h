@@ -208,6 +208,22 @@ int rofl_dbg_noise_apply(unsigned site, size_t n, const float *values, const int
  * pointers only, else 11), 1 = the kernel.  Same checks, same bytes; what scripts/gpu_binomial_noise.py finds the crossover with. */
 int rofl_dbg_noise_binomial_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
                                   uint32_t k, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
+/* noise integer of element index e of a seed under rofl_noise_dgauss and the stream words it consumed (words_used_out may be null), on the
+ * host from the kernel's source.  11: a null seed or noise_out, a sigma2 the call rejects, e >= 2^55. */
+int rofl_dbg_host_dgauss(const uint8_t seed[32], uint64_t e, uint32_t sigma2, int32_t *noise_out, uint32_t *words_used_out);
+/* The sampler of rofl_noise_dgauss on caller-supplied words instead of a seed's stream: case i runs over words[i stride .. i stride +
+ * lens[i]) with sigma2s[i] and leaves its noise, the words it read and whether it finished (0: it asked for a word past lens[i] or past
+ * word 8 191; the noise is then 0).  site 0: the host copy (no GPU); site 1: the device copy (k_dbg_dgauss_words, one thread per case).
+ * 11: site > 1, n_cases > 2^20, stride > 8 192, n_cases stride > 2^26, lens[i] > stride, a sigma2 the call rejects, a null array. */
+int rofl_dbg_dgauss_words(unsigned site, size_t n_cases, const uint32_t *words, size_t stride, const uint32_t *lens, const uint32_t *sigma2s,
+                          int32_t *noise_out, uint32_t *used_out, uint32_t *finished_out);
+/* rofl_noise_dgauss with the route chosen by the caller instead of by the pointers and the size: route 0 = the host copy of the rule (host
+ * pointers only, else 11), 1 = the kernel.  Same checks, same bytes; what scripts/gpu_dgauss_noise.py finds the crossover with. */
+int rofl_dbg_noise_dgauss_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
+                                uint32_t sigma2, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out);
+/* How k_noise_dgauss lays out a call of ONE vector of d elements (more vectors only raise the first figure): the elements a lane owns,
+ * and the XOF blocks a lane's LDS ring holds -- an element that needs more than those wraps the ring.  No GPU.  11: a null pointer, d >= 2^28. */
+int rofl_dbg_dgauss_geometry(size_t d, uint32_t *elements_per_lane, uint32_t *lds_blocks);
 /* Step 4 of rofl_clip_l2 on caller-supplied step counts, scale and words instead of a vector's sum and a seed's stream: out[i] =
  * trunc24((q[i] m >> 32) + (words[i] < q[i] m mod 2^32 ? 1 : 0)) 2^-fp_frac, positive; words == NULL: the unseeded rule (no + 1).
  * site 0: the host copy (no GPU); site 1: the device copy (k_dbg_clip_l2_round, one thread per case).  11: site > 1, fp_frac > 12, a null

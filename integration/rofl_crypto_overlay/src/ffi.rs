@@ -123,6 +123,12 @@ extern "C" {
     /// clipped again; values[v] / out[v] are host memory or device memory of the library's device, and may be the same array
     pub fn rofl_noise_binomial(n_vec: usize, seeds32: *const u8, values: *const *const c_float, first: usize, d: usize, k: u32,
         prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *const *mut c_float) -> c_int;
+    /// seeded discrete Gaussian noise on the fixed-point grid (the exact integer sampler of Canonne, Kamath and Steinke on a stream per
+    /// element), n_vec vectors (own seed, input, output each) in one launch: out[v][i] = the clipped, rounded values[v][i] plus the noise
+    /// of element first + i under seeds32[32 v ..] and sigma2 (an integer from 1 to 2^24) in grid steps, clipped again; values[v] / out[v]
+    /// are host memory or device memory of the library's device, and may be the same array
+    pub fn rofl_noise_dgauss(n_vec: usize, seeds32: *const u8, values: *const *const c_float, first: usize, d: usize, sigma2: u32,
+        prove_range: usize, fp_bits: c_uint, fp_frac: c_uint, out: *const *mut c_float) -> c_int;
     /// projection onto the L2 ball on the fixed-point grid, n_vec vectors (own input, output, max_sq and optional seed each) in one call:
     /// out[v] = values[v] on the grid when its sum of squared steps is at most max_sq[v], else scaled by m / 2^32 so that the sum of
     /// squares of the result is; seeds32 null: truncation, else seeded rounding of the scaled steps; scale_out (n_vec u64) may be null

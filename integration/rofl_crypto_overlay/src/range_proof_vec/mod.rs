@@ -61,6 +61,18 @@ pub fn add_binomial_noise(value_vec: &Vec<f32>, prove_range: usize, seed: &[u8; 
     out
 }
 
+/// No counterpart in the reference: discrete Gaussian noise, the mechanism the analyses of secure aggregation are written for.  Every
+/// value is clipped, rounded onto the grid of 2^-frac and gets a discrete Gaussian number of grid steps added, P(x) ~ exp(-x^2 / (2 sigma2)),
+/// drawn by the exact integer sampler from the element's own stream under `seed` -- a per-round secret of the client: who knows it
+/// removes the noise.  `sigma2` is an integer from 1 to 2^24; the cost does not depend on it.  Panics on a bad parameter.
+pub fn add_dgauss_noise(value_vec: &Vec<f32>, prove_range: usize, seed: &[u8; 32], sigma2: u32) -> Vec<f32> {
+    let mut out = vec![0f32; value_vec.len()];
+    let (vp, op) = (value_vec.as_ptr(), out.as_mut_ptr());
+    let rc = unsafe { rofl_noise_dgauss(1, seed.as_ptr(), &vp, 0, value_vec.len(), sigma2, prove_range, fp_bits(), fp_frac(), &op) };
+    if rc != ROFL_OK { panic!("rofl_zk: {}", last_error()); }
+    out
+}
+
 /// ceil(d / B) B with B = 2^block_log2: the length of a rotated vector, which the blinding vectors of a rotated round have as well.
 pub fn rotated_len(d: usize, block_log2: u32) -> usize {
     ((d + (1usize << block_log2) - 1) >> block_log2) << block_log2

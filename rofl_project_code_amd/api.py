@@ -460,6 +460,37 @@ def _seed_buffer(seeds, n):
         ctypes.memset(sb, 0, ctypes.sizeof(sb))
 
 
+class DiscreteGaussian:
+    """noise_k=DiscreteGaussian(sigma2) of the containers' encrypt calls: discrete Gaussian noise of variance parameter sigma2 (an integer
+    from 1 to 2^24, range_proof_vec.dgauss_sigma2) in place of the binomial noise an int noise_k asks for.  Immutable."""
+    __slots__ = ("_sigma2",)
+
+    def __init__(self, sigma2):
+        object.__setattr__(self, "_sigma2", _dgauss_sigma2_arg(sigma2))
+
+    sigma2 = property(lambda self: self._sigma2)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("DiscreteGaussian is immutable")
+
+    def __eq__(self, other):
+        return isinstance(other, DiscreteGaussian) and other._sigma2 == self._sigma2
+
+    def __hash__(self):
+        return hash(("DiscreteGaussian", self._sigma2))
+
+    def __repr__(self):
+        return "DiscreteGaussian(%d)" % self._sigma2
+
+
+def _dgauss_sigma2_arg(sigma2):
+    if isinstance(sigma2, DiscreteGaussian):
+        return sigma2.sigma2
+    if isinstance(sigma2, bool) or int(sigma2) != sigma2 or not 1 <= int(sigma2) <= 1 << 24:
+        raise ValueError("sigma2 is an integer from 1 to 2^24")
+    return int(sigma2)
+
+
 def _check_range_args(first, prove_range):
     if int(first) < 0 or int(prove_range) < 1:
         raise ValueError("first is not negative and prove_range is at least 1")
@@ -551,6 +582,41 @@ class range_proof_vec:
             hi = np.nextafter(hi, np.float32(0))
         v = np.ascontiguousarray(values, dtype=np.float32)
         return np.minimum(hi, np.maximum(-hi, np.where(np.isnan(v), -hi, v))).astype(np.float32)
+
+    # ---- discrete Gaussian noise (rofl_noise_dgauss): the exact seeded sampler, any integer sigma^2 up to 2^24, one launch per call ----
+    @staticmethod
+    def add_dgauss_noise_vecs(list_of_values, prove_range, seeds, sigma2, first=0, fp=None, out=None):
+        """rofl_noise_dgauss for several vectors of one length (the clients a process hosts) in ONE call: vector v is clipped like
+        clip_f32_to_range_vec, rounded onto the grid of 2^-fp_frac (the identity after quantize_probabilistic), and element `first + i` gets
+        a discrete Gaussian number of grid steps added, P(x) ~ exp(-x^2 / (2 sigma2)), drawn by the exact integer sampler of Canonne,
+        Kamath and Steinke from that element's own stream under seeds[v] (include/rofl_zk.h has the definition).  sigma2 is an integer
+        from 1 to 2^24 (dgauss_sigma2); the cost does not depend on it.  The results are f32 values ON the grid, inside the clip range: a
+        value near a bound can saturate there, which truncates its noise.
+        Vectors, `out` and the return value are as in quantize_probabilistic_vecs: numpy arrays or float32 tensors on the library's GPU.
+        A seed is a per-round SECRET of its client (pedersen_ops.noise_round_seed): whoever knows it removes the client's noise.  The
+        call is not constant time: how long an element takes depends on its noise."""
+        sigma2, fp = _dgauss_sigma2_arg(sigma2), _fp(fp)
+        _check_range_args(first, prove_range)
+        with _seed_buffer(seeds, len(list_of_values)) as sb:
+            return _float_vecs(list_of_values, out, lambda n, vp, d, op:
+                               lib().rofl_noise_dgauss(n, sb, vp, _sz(int(first)), d, ctypes.c_uint32(sigma2), _sz(prove_range), *fp, op))
+
+    @staticmethod
+    def add_dgauss_noise(values, prove_range, seed, sigma2, first=0, fp=None):
+        """add_dgauss_noise_vecs for one vector -> float32[d] on the fixed-point grid, within the clip range."""
+        return range_proof_vec.add_dgauss_noise_vecs([values], prove_range, [seed], sigma2, first, fp)[0]
+
+    @staticmethod
+    def dgauss_sigma2(sigma_steps):
+        """the smallest sigma2 add_dgauss_noise accepts that is at least `sigma_steps`^2: an integer from 1 to 2^24.  What (n clients,
+        sigma2, sensitivity) mean as an (epsilon, delta) is the deployment's accounting."""
+        s = Fraction(sigma_steps)
+        if s < 0:
+            raise ValueError("sigma is not negative")
+        s2 = max(1, int(math.ceil(s * s)))
+        if s2 > 1 << 24:
+            raise ValueError("sigma above 4096 grid steps needs a sigma2 above 2^24")
+        return s2
 
     # ---- Hadamard rotation (rofl_rotate): y = (1 / sqrt(B)) H_B D x per block of B = 2^block_log2 elements, seeded signs ----
     @staticmethod

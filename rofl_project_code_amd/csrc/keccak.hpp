@@ -116,6 +116,8 @@ HD void shake256_seeded_block(u64 st[25], const u64 dom[2], const u64 seed[4], u
 // Rounding words of the norm clipping (rofl_clip_l2): a sixth label, so that the words that round the scaled update are unrelated to the
 // words that rounded it onto the grid and to its noise, also under a reused seed.
 #define ROFL_CLIP_DOM {0x2f6b7a2d6c666f72ULL, 0x31762f3270696c63ULL}       /* "rofl-zk/" "clip2/v1" */
+// Words of the discrete Gaussian noise (rofl_noise_dgauss): a seventh label; here the index is (element << 8) | block, a stream per element.
+#define ROFL_DGAUSS_DOM {0x2f6b7a2d6c666f72ULL, 0x31762f7375616764ULL}     /* "rofl-zk/" "dgaus/v1" */
 // Sign bits of the Hadamard rotation (rofl_rotate): the same construction under "rofl-zk/rotate/v1", a label of 17 bytes, so the seed and
 // the index lie one byte off the words: SHAKE256(label17 || seed32 || u64le(index)), 57 bytes, one squeezed block.  The seed is PUBLIC.
 HD void shake256_rotate_block(u64 st[25], const u64 seed[4], u64 index) {

@@ -539,6 +539,158 @@ __global__ void __launch_bounds__(TPB) k_dbg_noise_apply(u32 n, const float *val
 }
 #endif
 
+// ================================================================ discrete Gaussian noise
+// rofl_noise_dgauss (the definition is in include/rofl_zk.h): the exact integer sampler of Canonne, Kamath and Steinke (2020) on a seeded
+// stream of u32 words that every ELEMENT has to itself; the noise goes through noise_apply like the binomial's.
+// The sampler, compiled for the host and the device from this one source, over a word source `Src`: next(x) hands out the next word, or
+// returns false when the source is dry, and pos is the number of words handed out.  A dry source ends the run wherever it stands: the
+// result is "not finished", and `ckpt` is the word at which the attempt that ran dry began -- a restart leaves nothing behind but the
+// position in the stream, so a caller who has more words by then runs again from ckpt instead of from word 0.
+#define DG_STREAM_WORDS 8192u      // 256 blocks; a draw past them ends the element with noise 0
+struct DgaussOut { u32 finished; int noise; u32 used, ckpt; };
+// words [0, n) of a buffer; word w lies at w & mask (~0: a plain array; 2^r - 1: a ring that holds the last 2^r words squeezed)
+struct DgBuf {
+    const u32 *w; u32 n, mask, pos;
+    HD bool next(u32 &x) { if (pos >= n) return false; x = w[pos & mask]; pos++; return true; }
+};
+HD u32 dg_isqrt(u32 x) {      // x <= 2^24
+    u32 r = 0;
+    for (u32 b = 1u << 12; b; b >>= 1) { const u32 c = r | b; if (c * c <= x) r = c; }
+    return r;
+}
+// uniform in [0, D), 1 <= D < 2^63: one word per draw up to 32 bits, two (lo, hi) above; D = 1 consumes nothing
+template <class Src> HD bool dg_below(Src &s, u64 D, u64 &v) {
+    v = 0;
+    if (D <= 1) return true;
+    const u32 b = 64u - (u32)__builtin_clzll(D - 1);
+    const u64 mask = (1ULL << b) - 1;      // (b <= 63)
+    for (;;) {
+        u32 lo, hi = 0;
+        if (!s.next(lo)) return false;
+        if (b > 32 && !s.next(hi)) return false;
+        v = (lo | (u64)hi << 32) & mask;
+        if (v < D) return true;
+    }
+}
+// Bernoulli(exp(-n / D)), 0 <= n <= D -> 0 / 1, or -1: dry.  Every round with D K > 1 takes a word, so K <= 8 192 and D K < 2^63.
+template <class Src> HD int dg_frac(Src &s, u64 n, u64 D) {
+    for (u64 K = 1;; K++) {
+        u64 v;
+        if (!dg_below(s, D * K, v)) return -1;
+        if (!(v < n)) return (int)(K & 1);
+    }
+}
+// Bernoulli(exp(-n / D)), any n: floor(n / D) times frac(1, 1), then frac(n mod D, D) -- the quotient by subtraction, one step per
+// draw of frac(1, 1), which the first 0 ends: the same draws in the same order as with f = n / D, and no 64-bit division on the device
+template <class Src> HD int dg_expo(Src &s, u64 n, u64 D) {
+    while (n >= D) { n -= D; const int r = dg_frac(s, 1, 1); if (r <= 0) return r; }
+    return dg_frac(s, n, D);
+}
+template <class Src> HD DgaussOut dgauss_run(Src &s, u32 s2) {
+    const u64 t = dg_isqrt(s2) + 1, den = 2 * (u64)s2 * t * t;      // (den < 2^50)
+    u32 ckpt;
+    for (;;) {
+        ckpt = s.pos;
+        u64 U;
+        if (!dg_below(s, t, U)) break;                              // 1. U, accepted with exp(-U / t)
+        int r = dg_frac(s, U, t);
+        if (r < 0) break;
+        if (!r) continue;
+        u32 V = 0;                                                  // 2. V geometric: exp(-1) per step, cut at 64
+        while (V < 64 && (r = dg_frac(s, 1, 1)) == 1) V++;
+        if (r < 0) break;
+        if (V == 64) continue;
+        const u64 X = U + t * V;                                    // 3. X <= 64 t - 1, the sign, no second zero
+        u32 w;
+        if (!s.next(w)) break;
+        const u32 B = w & 1;
+        if (B && X == 0) continue;
+        const long long a = (long long)(X * t) - (long long)s2;     // 4. |a| <= 64 t^2 < 2^31
+        r = dg_expo(s, (u64)(a * a), den);
+        if (r < 0) break;
+        if (!r) continue;
+        return DgaussOut{1u, B ? -(int)X : (int)X, s.pos, ckpt};
+    }
+    return DgaussOut{0u, 0, s.pos, ckpt};
+}
+// the sampler over a buffer of words: not finished = it asked for a word past n_words
+HD DgaussOut dgauss_sample(const u32 *words, u32 n_words, u32 s2) {
+    DgBuf b{words, n_words < DG_STREAM_WORDS ? n_words : DG_STREAM_WORDS, ~0u, 0};
+    return dgauss_run(b, s2);
+}
+// block j of element index e into dst[0 .. 32): the first 128 bytes of SHAKE256("rofl-zk/dgaus/v1" || seed || u64le(e << 8 | j)).  The
+// words leave the state by literal index: a state indexed by a run-time word number would live in scratch.
+HD void dg_squeeze(u32 *dst, u64 s0, u64 s1, u64 s2_, u64 s3, u64 e, u32 j) {
+    const u64 dom[2] = ROFL_DGAUSS_DOM;
+    u64 sw[4] = {s0, s1, s2_, s3}, st[25];
+    shake256_seeded_block(st, dom, sw, (e << 8) | j);
+#pragma unroll
+    for (u32 k = 0; k < 16; k++) { dst[2 * k] = (u32)st[k]; dst[2 * k + 1] = (u32)(st[k] >> 32); }
+#if !defined(__HIP_DEVICE_COMPILE__)
+    // on the host the state and the seed words are memory of the caller's thread: the permuted state gives the seed back (Keccak-f is
+    // invertible), so neither outlives the squeeze (on the device both are registers of the lane)
+    { volatile u64 *p = st; for (int i = 0; i < 25; i++) p[i] = 0; p = sw; for (int i = 0; i < 4; i++) p[i] = 0; }
+#endif
+}
+// the same out of line: the on-demand source below is read at every draw site of the sampler, and a permutation inlined at each of them
+// would be a dozen copies of Keccak-f
+HDN __attribute__((noinline)) inline void dg_squeeze_call(u32 *dst, u64 s0, u64 s1, u64 s2_, u64 s3, u64 e, u32 j) { dg_squeeze(dst, s0, s1, s2_, s3, e, j); }
+// the stream of element index e of a seed, squeezed block by block as the sampler asks, through a buffer of one block (32 words): the
+// host twin's source, and the kernel's for an attempt that outgrows its ring
+struct DgSeeded {
+    u64 s0, s1, s2_, s3, e; u32 *blk; u32 cur, pos;
+    HD bool next(u32 &x) {
+        if (pos >= DG_STREAM_WORDS) return false;
+        if ((pos >> 5) != cur) { cur = pos >> 5; dg_squeeze_call(blk, s0, s1, s2_, s3, e, cur); }
+        x = blk[pos & 31]; pos++; return true;
+    }
+};
+// blockIdx.y = vector (QuantVec: its seed, input and output); a workgroup is ONE wave; lane t of workgroup b owns elements b 64 + t,
+// + gridDim.x 64, ... of the vector (the host sizes the grid so that a lane owns several: how many blocks an element needs varies, and
+// a wave waits for its slowest lane).  Each trip of the lane loop has ONE permutation, which all lanes reach together: a lane squeezes
+// the next block of its current element into its own LDS row, a ring of DG_R blocks (rows DG_ROW = 32 DG_R + 1 words apart: equal word
+// numbers of the 64 lanes fall on different banks), and runs the sampler over the words it has, from the word where the attempt that ran
+// dry last time began.  A lane that finishes applies the value rule, stores and moves on to its next element; one that does not keeps
+// its row.  The ring holds an attempt of up to 32 (DG_R - 1) + 1 words wherever it starts; an attempt whose first block the next squeeze
+// would overwrite (by the model 3 in 20 000 elements at sigma2 = 2^24, none below) is finished on the spot by the on-demand source, whose
+// permutations the lanes do not share.  in == out is allowed (an element is read and written by one lane).
+#define DG_TPB 64
+#define DG_R 2
+#define DG_ROW (32 * DG_R + 1)
+#if ROFL_KG(4)
+__global__ void __launch_bounds__(DG_TPB) k_noise_dgauss(const QuantVec *__restrict__ vecs, u64 first, u32 d, u32 s2, float clip_min, float clip_max, u32 fp_frac) {
+    __shared__ u32 s_row[DG_TPB * DG_ROW];
+    const QuantVec *V = &vecs[blockIdx.y];
+    const u64 s0 = V->seed[0], s1 = V->seed[1], s2_ = V->seed[2], s3 = V->seed[3];
+    const float *in = V->in; float *out = V->out;
+    u32 *row = s_row + threadIdx.x * DG_ROW;
+    const u32 stride = gridDim.x * DG_TPB;      // (<= 2^17; d < 2^28: i + stride does not wrap)
+    u32 i = blockIdx.x * DG_TPB + threadIdx.x, have = 0, ckpt = 0;
+    while (i < d) {
+        dg_squeeze(row + 32 * (have & (DG_R - 1)), s0, s1, s2_, s3, first + i, have);
+        have++;
+        DgBuf ring{row, 32 * have, 32 * DG_R - 1, ckpt};
+        DgaussOut r = dgauss_run(ring, s2);
+        if (!r.finished && have < DG_STREAM_WORDS / 32 && (r.ckpt >> 5) + DG_R <= have) {
+            DgSeeded src{s0, s1, s2_, s3, first + i, row, ~0u, r.ckpt};
+            r = dgauss_run(src, s2);
+            r.finished = 1;      // (or dry at word 8 192: noise 0)
+        }
+        if (r.finished || have == DG_STREAM_WORDS / 32) {
+            out[i] = noise_apply(in[i], r.noise, clip_min, clip_max, fp_frac);
+            i += stride; have = 0; ckpt = 0;
+        } else ckpt = r.ckpt;
+    }
+}
+// rofl_dbg_dgauss_words site 1: the sampler as the device compiles it, on the caller's words, one thread per case
+__global__ void __launch_bounds__(TPB) k_dbg_dgauss_words(u32 n, const u32 *words, u32 stride, const u32 *lens, const u32 *s2s, int *res /* 3 n: noise, used, finished */) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const DgaussOut r = dgauss_sample(words + (size_t)t * stride, lens[t], s2s[t]);
+    res[t] = r.noise; res[n + t] = (int)r.used; res[2 * n + t] = (int)r.finished;
+}
+#endif
+
 // The sums of the L2 sum proof (l2_range_proof_vec/mod.rs:37-79) for the clients of a batch, one client per grid row, a fixed number of
 // blocks per client striding over its d values.  Per client: the status bits (1 = a value outside the clip range, 2 = NaN, as
 // k_quantize_shift has them); sum_i s_i^2 -- s_i is k_i or l - k_i with k_i < 2^64, so s_i^2 = k_i^2 mod l and the sum is the plain integer

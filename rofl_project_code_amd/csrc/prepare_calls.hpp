@@ -169,6 +169,61 @@ int noise_binomial_impl(int route, size_t n_vec, const uint8_t *seeds32, const f
         });
 }
 
+// ---- discrete Gaussian noise (rofl_noise_dgauss: the definition is in the header, the sampler and the kernel in kernels.hpp) ----
+// Below this many elements in all, a call whose pointers are all host memory runs on the host: about 1.2 permutations and one run of the
+// sampler per element on one core against the fixed cost of two staged copies, a launch and a synchronisation.  The measured crossover
+// (profiles/dgauss_noise.json); a constant, not a knob: both routes give the same bytes.
+constexpr size_t kDgaussHostBelow = 768;
+// The grid of k_noise_dgauss for one vector of d elements.  No more waves in all than the chip holds at once at two per SIMD (256 CUs x
+// 8): beyond that a lane owns more elements instead -- the blocks an element needs vary, a wave waits for its slowest lane, and the sum
+// over a lane's elements varies less.  Below that a small call is a matter of latency, a lane's elements run one after the other, and
+// waves are free: two elements per lane, so that a lane's second element fills some of the trips its wave waits for the slowest first.
+constexpr u32 kDgaussLaneElems = 2, kDgaussWaves = 2048;
+u32 dgauss_grid(size_t n_vec, size_t d) {
+    const u32 want = (u32)((d + (size_t)DG_TPB * kDgaussLaneElems - 1) / ((size_t)DG_TPB * kDgaussLaneElems));
+    return std::max(1u, std::min(want, kDgaussWaves / (u32)std::min<size_t>(n_vec, kDgaussWaves)));
+}
+// The per-element streams of one seed, read on the host: the on-demand source of kernels.hpp with its seed words and its block of 32 stream
+// words.  Both are the caller's secrets, as the seed and block of a HostStream: zeroed when the owner goes out of scope (the state of
+// each squeeze zeroes itself, dg_squeeze).
+struct DgaussHostStream {
+    DgSeeded src; u32 blk[32];
+    explicit DgaussHostStream(const uint8_t *seed32) : src{0, 0, 0, 0, 0, blk, ~0u, 0} { memcpy(&src.s0, seed32, 8); memcpy(&src.s1, seed32 + 8, 8); memcpy(&src.s2_, seed32 + 16, 8); memcpy(&src.s3, seed32 + 24, 8); }
+    DgaussHostStream(const DgaussHostStream &) = delete;
+    // noise integer of element index e, and the words it consumed (not finished: dry at word 8 192, noise 0)
+    int element(u64 e, u32 s2, u32 *used) {
+        src.e = e; src.cur = ~0u; src.pos = 0;
+        const DgaussOut r = dgauss_run(src, s2);
+        if (used) *used = r.used;
+        return r.noise;
+    }
+    ~DgaussHostStream() {
+        volatile u64 *p = &src.s0; p[0] = 0; p = &src.s1; p[0] = 0; p = &src.s2_; p[0] = 0; p = &src.s3; p[0] = 0;
+        volatile u32 *q = blk; for (int i = 0; i < 32; i++) q[i] = 0;
+    }
+};
+void noise_dgauss_host(const uint8_t *seed32, const float *in, u64 first, size_t d, u32 s2, float mn, float mx, unsigned fp_frac, float *out) {
+    DgaussHostStream xs(seed32);
+    for (size_t i = 0; i < d; i++) out[i] = noise_apply(in[i], xs.element(first + i, s2, nullptr), mn, mx, fp_frac);
+}
+bool dgauss_sigma2_ok(uint32_t s2) { return s2 >= 1 && s2 <= (1u << 24); }
+// route: as PrepCall (rofl_dbg_noise_dgauss_route)
+int noise_dgauss_impl(int route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, uint32_t sigma2,
+                      size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    if (!valid_fp(fp_bits, fp_frac) || prove_range == 0) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (!dgauss_sigma2_ok(sigma2)) return fail(ROFL_BAD_PARAM, "sigma2 is an integer from 1 to 2^24");
+    if (int rc = prep_check(n_vec, seeds32, true, values, out, d, [&]() -> int {
+        return first > ((size_t)1 << 55) || first + d > ((size_t)1 << 55) ? fail(ROFL_BAD_PARAM, "first + d exceeds 2^55") : ROFL_OK; }); rc != kPrepGo) return rc;
+    float mn, mx; clip_bounds(prove_range, fp_bits, fp_frac, &mn, &mx);
+    return prep_run<QuantVec>(PrepCall{route, n_vec * d < kDgaussHostBelow, n_vec, seeds32, values, d, d, out},
+        [&](size_t v) { noise_dgauss_host(seeds32 + 32 * v, values[v], first, d, sigma2, mn, mx, fp_frac, out[v]); }, no_fill,
+        [&](Ctx &C, const QuantVec *vecs) -> const void * {
+            ROFL_LAUNCH(k_noise_dgauss, dim3(dgauss_grid(n_vec, d), (unsigned)n_vec), dim3(DG_TPB), 0, C.stream,
+                        vecs, (u64)first, (u32)d, (u32)sigma2, mn, mx, (u32)fp_frac);
+            return nullptr;
+        });
+}
+
 // ---- norm clipping (rofl_clip_l2: the definition is in the header, the rule, the search and the kernels in kernels.hpp) ----
 // Below this many elements in all, a call whose pointers are all host memory runs the rule on the host: two passes of one core over the
 // values (and one Keccak-f per 32 elements with seeds) against the fixed cost of two staged copies, two launches and a synchronisation.
@@ -300,6 +355,10 @@ int rofl_noise_binomial(size_t n_vec, const uint8_t *seeds32, const float *const
                         unsigned fp_bits, unsigned fp_frac, float *const *out) {
     return noise_binomial_impl(-1, n_vec, seeds32, values, first, d, k, prove_range, fp_bits, fp_frac, out);
 }
+int rofl_noise_dgauss(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d, uint32_t sigma2, size_t prove_range,
+                      unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    return noise_dgauss_impl(-1, n_vec, seeds32, values, first, d, sigma2, prove_range, fp_bits, fp_frac, out);
+}
 int rofl_clip_l2(size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t d, const uint64_t *max_sq, size_t prove_range, unsigned fp_bits,
                  unsigned fp_frac, float *const *out, uint64_t *scale_out) {
     return clip_l2_impl(-1, n_vec, seeds32, values, d, max_sq, prove_range, fp_bits, fp_frac, out, scale_out);
@@ -342,6 +401,50 @@ int rofl_dbg_noise_binomial_route(unsigned route, size_t n_vec, const uint8_t *s
                                   uint32_t k, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
     if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
     return noise_binomial_impl((int)route, n_vec, seeds32, values, first, d, k, prove_range, fp_bits, fp_frac, out);
+}
+int rofl_dbg_host_dgauss(const uint8_t seed[32], uint64_t e, uint32_t sigma2, int32_t *noise_out, uint32_t *words_used_out) {
+    if (!seed || !noise_out || !dgauss_sigma2_ok(sigma2) || e >= ((u64)1 << 55)) return ROFL_BAD_PARAM;
+    u32 used;
+    *noise_out = DgaussHostStream(seed).element(e, sigma2, &used);
+    if (words_used_out) *words_used_out = used;
+    return 0;
+}
+int rofl_dbg_dgauss_words(unsigned site, size_t n_cases, const uint32_t *words, size_t stride, const uint32_t *lens, const uint32_t *sigma2s,
+                          int32_t *noise_out, uint32_t *used_out, uint32_t *finished_out) {
+    if (site > 1 || n_cases > (1u << 20) || stride > DG_STREAM_WORDS || n_cases * stride > ((size_t)1 << 26) ||
+        (n_cases && (!lens || !sigma2s || !noise_out || !used_out || !finished_out || (stride && !words)))) return fail(ROFL_BAD_PARAM, "bad parameter");
+    for (size_t i = 0; i < n_cases; i++) if (lens[i] > stride || !dgauss_sigma2_ok(sigma2s[i])) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n_cases == 0) return ROFL_OK;
+    if (site == 0) {
+        for (size_t i = 0; i < n_cases; i++) {
+            const DgaussOut r = dgauss_sample(words + i * stride, lens[i], sigma2s[i]);
+            noise_out[i] = r.noise; used_out[i] = r.used; finished_out[i] = r.finished;
+        }
+        return ROFL_OK;
+    }
+    return guarded([&]() -> int {      // (as probe_run, with three arrays in and three out)
+        LaneLock lane_lock = acquire_lane(); Ctx &C = *lane_lock.c;
+        C.init();
+        const size_t n = n_cases;
+        u32 *dw = C.vals.as<u32>(std::max<size_t>(n * stride, 1)), *dl = C.tmp_in.as<u32>(2 * n); int *dres = C.tmp_out.as<int>(3 * n);
+        if (stride) C.up(dw, words, 4 * n * stride, C.stream);
+        C.up(dl, lens, 4 * n, C.stream); C.up(dl + n, sigma2s, 4 * n, C.stream);
+        ROFL_LAUNCH(k_dbg_dgauss_words, grid1(n), dim3(TPB), 0, C.stream, (u32)n, (const u32 *)dw, (u32)stride, (const u32 *)dl, (const u32 *)(dl + n), dres);
+        C.down(noise_out, dres, 4 * n, C.stream); C.down(used_out, dres + n, 4 * n, C.stream); C.down(finished_out, dres + 2 * n, 4 * n, C.stream);
+        C.sync();
+        return ROFL_OK;
+    });
+}
+int rofl_dbg_noise_dgauss_route(unsigned route, size_t n_vec, const uint8_t *seeds32, const float *const *values, size_t first, size_t d,
+                                uint32_t sigma2, size_t prove_range, unsigned fp_bits, unsigned fp_frac, float *const *out) {
+    if (route > 1) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return noise_dgauss_impl((int)route, n_vec, seeds32, values, first, d, sigma2, prove_range, fp_bits, fp_frac, out);
+}
+int rofl_dbg_dgauss_geometry(size_t d, uint32_t *elements_per_lane, uint32_t *lds_blocks) {
+    if (!elements_per_lane || !lds_blocks || d >= ((size_t)1 << 28)) return ROFL_BAD_PARAM;
+    const size_t lanes = (size_t)dgauss_grid(1, d) * DG_TPB;
+    *elements_per_lane = (uint32_t)((d + lanes - 1) / lanes); *lds_blocks = DG_R;
+    return 0;
 }
 int rofl_dbg_clip_l2_round(unsigned site, size_t n, const uint64_t *q, uint32_t m, const uint32_t *words, unsigned fp_frac, float *out) {
     if (site > 1 || fp_frac > 12 || n > (1u << 20) || (n && (!q || !out))) return fail(ROFL_BAD_PARAM, "bad parameter");

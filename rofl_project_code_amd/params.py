@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import api
-from .api import (RoflError, Nonce, lib, _check, _ptr, _sz, range_proof_vec, l2_range_proof_vec, rand_proof_vec,
+from .api import (RoflError, Nonce, DiscreteGaussian, lib, _check, _ptr, _sz, range_proof_vec, l2_range_proof_vec, rand_proof_vec,
                   square_rand_proof_vec, square_proof_vec, compressed_rand_proof, pedersen_ops, conversion32)
 
 WIRE_ENC_RANGE, WIRE_ENC_NORM, WIRE_ENC_NORM_COMPRESSED = 0, 1, 2
@@ -217,6 +217,8 @@ def _num_checked(d, check_percentage):
 # digest in the same way.  The seed is a per-round SECRET of the client (pedersen_ops.noise_round_seed).  A value within noise_k steps of
 # a clip bound can saturate there (range_proof_vec.clip_f32_for_noise avoids it), and for the L2 containers the noise raises the norm --
 # by about sqrt(d noise_k / 2) steps: an update that then exceeds the bound fails with NormOutOfRangeError (7) like any other.
+# noise_k is an int for the binomial noise, or a DiscreteGaussian(sigma2) for the discrete Gaussian noise (range_proof_vec.add_dgauss_noise:
+# any integer sigma2 from 1 to 2^24, a cost that does not grow with it); the seed serves either, their stream labels differ.
 def _noise_args(noise_seed, noise_k):
     if (noise_seed is None) != (noise_k is None):
         raise ValueError("noise_seed(s) and noise_k are given together or not at all")
@@ -265,7 +267,10 @@ def _clip_or_quantize_batch(xs, prove_range, quant_seeds, fp, noise_seeds=None, 
     if clipping and xs:      # (every client: the clip call tells the seeded from the unseeded itself)
         for i, row in enumerate(l2_range_proof_vec.clip_l2_vecs(xs, prove_range, l2_clip, clip_seeds, fp=fp)):
             xs[i] = clipped[i] = row.reshape(xs[i].shape)
-    _apply_where(xs, clipped, noise_seeds, lambda vs, seeds: range_proof_vec.add_binomial_noise_vecs(vs, prove_range, seeds, noise_k, fp=fp))
+    if isinstance(noise_k, DiscreteGaussian):      # the mechanism is the type of noise_k: an int is the binomial's k
+        _apply_where(xs, clipped, noise_seeds, lambda vs, seeds: range_proof_vec.add_dgauss_noise_vecs(vs, prove_range, seeds, noise_k.sigma2, fp=fp))
+    else:
+        _apply_where(xs, clipped, noise_seeds, lambda vs, seeds: range_proof_vec.add_binomial_noise_vecs(vs, prove_range, seeds, noise_k, fp=fp))
     for i in range(n):
         if clipped[i] is None:
             clipped[i] = range_proof_vec.clip_f32_to_range_vec(xs[i], prove_range, fp=fp)

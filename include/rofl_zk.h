@@ -660,13 +660,13 @@ int rofl_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uin
  * length is 0), an offset array that does not start at 0 or that decreases, a key_idx out of range, key_idx == NULL with n_keys != n, n or
  * n_keys above 2^24 (or n_keys = 0 with n > 0), a total AD or a total payload above 2^30 bytes, one payload above 2^24 bytes (open counts
  * the records without their tags); n = 0 returns 0 and touches no device.  One lane: one upload, at most two launches (the key
- * derivation where asked for; seal or open), one download.  The `devices` option does not apply.  Keys, derived keys and plaintexts are
+ * derivation where asked for; seal or open) and, when a payload has 16 384 bytes or more, two (seal) or three (open) for those, one download.  The `devices` option does not apply.  Keys, derived keys and plaintexts are
  * secrets: the pinned staging copies and the device workspace that held them are overwritten with zeros before the call returns or
  * unwinds; keystream and authenticator keys live in registers only.
  * What is NOT promised: nothing is constant-time.  A (key, nonce) pair that seals two different payloads gives away the XOR of both and the
  * authenticator: the CALLER owns nonce uniqueness (secret_sharing.seal_shares in the Python binding: a key per pair and round, the nonce
- * from sender and recipient).  One record is one thread: one long record is one serial chain on one lane, as with k_sig_digest, and a
- * call that consists of it is slower than one host core.  A deployment uses a CHANNEL key pair of its own for this, a third key beside its
+ * from sender and recipient).  A record below 16 384 bytes is one thread; a longer one is cut into segments of 16 KB, one workgroup
+ * each, and only its AD and the join of its segments are serial chains.  A deployment uses a CHANNEL key pair of its own for this, a third key beside its
  * mask key and its signing key: the mask key of a client that drops out is RECONSTRUCTED by the server, and a sealing key derived from it
  * would open every bundle ever sealed to or from that client. */
 int rofl_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round /* may be NULL */,

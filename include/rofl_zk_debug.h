@@ -275,6 +275,22 @@ int rofl_dbg_host_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t 
 int rofl_dbg_poly1305(size_t n, const uint8_t *key32 /* n x 32 */, const uint8_t *msg_bytes, const uint64_t *msg_off /* n + 1 */,
                       uint8_t *tag_out16 /* n x 16 */);
 int rofl_dbg_host_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16);
+/* The long route of rofl_aead_seal / rofl_aead_open (records cut into segments, one workgroup per segment, a finishing lane per record) for
+ * EVERY record of the call, whatever its length -- the empty one included, which has no segment and only the finishing step.  The
+ * parameters, checks and bytes are those of the public calls; seg_blocks is the segment length in 16-byte blocks, 0 for the built one.
+ * Any other value is a multiple of the pass tile (11: "seg_blocks is a multiple of the pass tile"), which lets a test reach segment
+ * boundaries with kilobytes.  rofl_dbg_poly1305_long: rofl_dbg_poly1305 through the same segment and finish kernels, messages of whole
+ * 16-byte blocks only (11 otherwise).  rofl_dbg_aead_long_geometry: out3 = {blocks of a pass tile, blocks of a built segment, the payload
+ * length in bytes from which the public calls take the long route}. */
+int rofl_dbg_aead_seal_long(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx,
+                            const uint8_t *nonce12, const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes,
+                            const uint64_t *pt_off, uint8_t *sealed_out, uint32_t seg_blocks);
+int rofl_dbg_aead_open_long(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx,
+                            const uint8_t *nonce12, const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes,
+                            const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out, uint32_t seg_blocks);
+int rofl_dbg_poly1305_long(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16,
+                           uint32_t seg_blocks);
+int rofl_dbg_aead_long_geometry(uint32_t *out3);
 /* rofl_dleq_prove / rofl_dleq_verify on the host's 51-bit point arithmetic, scalar arithmetic and host Keccak, one thread, no GPU: the same
  * parameters, the same checks (11) and the same bytes.  What the host tests pin the definition with, and the baseline of profiles/dleq.json. */
 int rofl_dbg_host_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs,

@@ -1667,9 +1667,24 @@ class aead:
         return k, nc, n, ad, ad_off, idx, rnd
 
     @staticmethod
-    def seal(keys, nonces, ads, plaintexts, key_idx=None, derive_round=None):
+    def long_geometry():
+        """(blocks of a pass tile, blocks of a built segment, LONG_MIN): a record whose payload has LONG_MIN bytes or more is cut into
+        segments of 16-byte blocks and sealed or opened by one workgroup per segment (rofl_dbg_aead_long_geometry)."""
+        out = (ctypes.c_uint32 * 3)()
+        _check(lib().rofl_dbg_aead_long_geometry(out))
+        return tuple(int(v) for v in out)
+
+    @staticmethod
+    def _entry(name, seg_blocks):
+        """the public entry, or with seg_blocks (0: the built segment) the debug entry that sends EVERY record down the long route"""
+        if seg_blocks is None:
+            return getattr(lib(), name), ()
+        return getattr(lib(), name.replace("rofl_", "rofl_dbg_") + "_long"), (ctypes.c_uint32(int(seg_blocks)),)
+
+    @staticmethod
+    def seal(keys, nonces, ads, plaintexts, key_idx=None, derive_round=None, long_seg_blocks=None):
         """-> the sealed records in the form of `plaintexts`: a list of bytes, uint8[n, length + 16], or the packed pair
-        (uint8[total + 16 n], uint64[n + 1]).  ONE call."""
+        (uint8[total + 16 n], uint64[n + 1]).  ONE call.  long_seg_blocks: see _entry (tests and measurements)."""
         k, nc, n, ad, ad_off, idx, rnd = aead._args(keys, nonces, ads, key_idx, derive_round)
         pt, pt_off, form = _packed(plaintexts, "plaintexts")
         if pt_off.size != n + 1:
@@ -1681,8 +1696,9 @@ class aead:
         try:
             ctypes.memmove(bk, k.ctypes.data, k.size)
             ctypes.memmove(bp, pt.ctypes.data, total)
-            _check(lib().rofl_aead_seal(_sz(k.shape[0]), bk, None if rnd is None else _ptr(rnd), _sz(n), None if idx is None else _ptr(idx), _ptr(nc),
-                                        _ptr(ad) if ad.size else None, _ptr(ad_off), bp if total else None, _ptr(pt_off), _ptr(out)))
+            fn, more = aead._entry("rofl_aead_seal", long_seg_blocks)
+            _check(fn(_sz(k.shape[0]), bk, None if rnd is None else _ptr(rnd), _sz(n), None if idx is None else _ptr(idx), _ptr(nc),
+                      _ptr(ad) if ad.size else None, _ptr(ad_off), bp if total else None, _ptr(pt_off), _ptr(out), *more))
         finally:
             ctypes.memset(bk, 0, ctypes.sizeof(bk))
             ctypes.memset(bp, 0, ctypes.sizeof(bp))
@@ -1694,7 +1710,7 @@ class aead:
         return out.reshape(n, form + 16)
 
     @staticmethod
-    def open(keys, nonces, ads, sealed, key_idx=None, derive_round=None):
+    def open(keys, nonces, ads, sealed, key_idx=None, derive_round=None, long_seg_blocks=None):
         """-> (plaintexts, verdicts uint8[n]), ONE call.  Verdict 0: the tag matches; 1: it does not, and the plaintext is zeros; 2: the record
         is shorter than 16 bytes, and its plaintext is empty.  The tag is checked before anything is decrypted.  The plaintexts come in the
         form of `sealed`: a list of bytes; uint8[n, length - 16]; or, for a packed pair, (uint8[total], the same offsets) with plaintext i at
@@ -1708,8 +1724,9 @@ class aead:
         bk = (ctypes.c_ubyte * max(k.size, 1))()
         try:
             ctypes.memmove(bk, k.ctypes.data, k.size)
-            _check(lib().rofl_aead_open(_sz(k.shape[0]), bk, None if rnd is None else _ptr(rnd), _sz(n), None if idx is None else _ptr(idx), _ptr(nc),
-                                        _ptr(ad) if ad.size else None, _ptr(ad_off), _ptr(ct) if total else None, _ptr(ct_off), _ptr(pt), _ptr(verdict)))
+            fn, more = aead._entry("rofl_aead_open", long_seg_blocks)
+            _check(fn(_sz(k.shape[0]), bk, None if rnd is None else _ptr(rnd), _sz(n), None if idx is None else _ptr(idx), _ptr(nc),
+                      _ptr(ad) if ad.size else None, _ptr(ad_off), _ptr(ct) if total else None, _ptr(ct_off), _ptr(pt), _ptr(verdict), *more))
         finally:
             ctypes.memset(bk, 0, ctypes.sizeof(bk))
         if form == "packed":

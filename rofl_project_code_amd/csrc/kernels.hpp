@@ -3497,6 +3497,9 @@ __global__ void __launch_bounds__(64) k_sig_verify(u32 n, const uint2 *__restric
 // Padded to 16 bytes, every block the AEAD authenticates is a FULL Poly1305 block (the 2^128 bit set); only rofl_dbg_poly1305 sees the raw
 // ragged tail (a 0x01 byte after the message, no 2^128 bit).  Not constant-time in any promised sense; the nonce is the caller's.
 #define ROFL_SEAL_DOM {0x2f6b7a2d6c666f72ULL, 0x0031762f6c616573ULL}      /* "rofl-zk/" "seal/v1\0" */
+// the long route (further below): lanes of a workgroup = 16-byte blocks of one pass, the pass tile (4 KB); blocks of a segment (16 KB)
+#define AEAD_LONG_T 256u
+#define AEAD_LONG_S 1024u
 HD u32 rotl32(u32 x, int n) { return (x << n) | (x >> (32 - n)); }
 #define ROFL_CHACHA_QR(a, b, c, d) \
     x[a] += x[b]; x[d] = rotl32(x[d] ^ x[a], 16); x[c] += x[d]; x[b] = rotl32(x[b] ^ x[c], 12); \
@@ -3642,13 +3645,14 @@ __global__ void __launch_bounds__(64) k_aead_derive(u32 n_keys, u64 round, u64 *
 // serial chain on one lane (Poly1305 is a Horner chain, and the blocks of ChaCha are taken in order here).
 __global__ void __launch_bounds__(64) k_aead_seal(u32 n, const u32 *__restrict__ key_idx, const u32 *__restrict__ keys /* [n_keys][8] */, const u32 *__restrict__ nonce /* [n][3] */,
                                                   const uint8_t *__restrict__ ad, const u64 *__restrict__ ad_off, const uint8_t *__restrict__ pt, const u64 *__restrict__ pt_off,
-                                                  uint8_t *__restrict__ out) {
+                                                  uint8_t *__restrict__ out, u64 long_min) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const u64 ao = ad_off[i], alen = ad_off[i + 1] - ao, po = pt_off[i], len = pt_off[i + 1] - po;
+    if (len >= long_min) return;      // the long route's (k_aead_long_seal)
     u32 key[8], nc[3], s[4], ks[16], tag[4];
     poly1305 P;
     aead_begin(i, key_idx, keys, nonce, key, nc, P, s);
-    const u64 ao = ad_off[i], alen = ad_off[i + 1] - ao, po = pt_off[i], len = pt_off[i + 1] - po;
     aead_absorb(P, ad, ao, alen);
     uint8_t *o = out + po + 16 * (u64)i;
     for (u64 b = 0; b < len; b += 64) {
@@ -3675,12 +3679,13 @@ __global__ void __launch_bounds__(64) k_aead_seal(u32 n, const u32 *__restrict__
 // (verdict 1).  One thread per record, two passes over the ciphertext.
 __global__ void __launch_bounds__(64) k_aead_open(u32 n, const u32 *__restrict__ key_idx, const u32 *__restrict__ keys /* [n_keys][8] */, const u32 *__restrict__ nonce /* [n][3] */,
                                                   const uint8_t *__restrict__ ad, const u64 *__restrict__ ad_off, const uint8_t *__restrict__ sealed, const u64 *__restrict__ s_off,
-                                                  uint8_t *__restrict__ pt_out, uint8_t *__restrict__ verdict) {
+                                                  uint8_t *__restrict__ pt_out, uint8_t *__restrict__ verdict, u64 long_min) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const u64 so = s_off[i], rlen = s_off[i + 1] - so;
     if (rlen < 16) { verdict[i] = 2; return; }
     const u64 len = rlen - 16, ao = ad_off[i], alen = ad_off[i + 1] - ao;
+    if (len >= long_min) return;      // the long route's (k_aead_long_mac, k_aead_long_open_finish, k_aead_long_decrypt)
     u32 key[8], nc[3], s[4], ks[16], tag[4], got[4];
     poly1305 P;
     aead_begin(i, key_idx, keys, nonce, key, nc, P, s);
@@ -3730,6 +3735,290 @@ __global__ void __launch_bounds__(64) k_dbg_poly1305(u32 n, const u32 *__restric
     poly1305_finish(tag, P, k + 4);
 #pragma unroll
     for (int w = 0; w < 4; w++) tag_out[4 * (size_t)j + w] = tag[w];
+}
+// ---------------------------------------------------------------- long records: one record over lanes and workgroups
+// A record of AEAD_LONG_MIN bytes or more (protocol_calls.hpp) leaves the one-lane kernels.  With a = ceil(alen / 16) AD blocks A_i,
+// c = ceil(len / 16) ciphertext blocks C_j and the length block L, every block padded with zeros and its 2^128 bit set, the tag before + s is
+//   h = sum A_i r^(a + c + 2 - i) + sum C_j r^(c + 2 - j) + L r   (mod 2^130 - 5).
+// The ciphertext is cut into segments of S blocks (AEAD_LONG_S; S is a multiple of the pass tile AEAD_LONG_T); one workgroup of AEAD_LONG_T
+// lanes takes one (record, segment) g of n_g blocks and leaves P_g = sum_{j in g} C_j r^(last_g + 1 - j) -- Horner inside the segment -- in the
+// call's workspace; one lane per record then absorbs the AD (serially: ADs are short, and a long one stays a serial chain), folds
+// H = H r^(n_g) + P_g segment by segment, H = (H + L) r, and finishes.  r^S is computed once per record, r^(n_last) by square-and-multiply.
+// Inside a workgroup lane t takes the blocks t, t + T, ... of the segment (a wave's load of a pass is one contiguous 1 KB run), runs Horner
+// with R = r^T and no trailing multiplication, scales its sum by r^(n_g - l_t) (l_t its last block: one of r^1 .. r^T), and the lane sums are
+// added in 64 bits across the wave and through LDS across the waves, then carried.  r^1 .. r^T are built per workgroup in LDS in log steps.
+// ChaCha20: the four lanes of a quad hold the four 16-byte quarters of one 64-byte keystream block, and they compute it TOGETHER: lane q keeps
+// column q of the 4 x 4 state, the column rounds are local, the diagonal rounds move rows b, c, d by one, two, three lanes (DPP quad_perm: no
+// LDS, no redundant rounds), and a 4 x 4 transpose in registers hands lane q row q, the keystream of its quarter.  Block 0 (r, s) is computed
+// by ONE quad of a workgroup and r handed to the rest through LDS.
+#define AEAD_LONG_QR(a, b, c, d) \
+    a += b; d = rotl32(d ^ a, 16); c += d; b = rotl32(b ^ c, 12); a += b; d = rotl32(d ^ a, 8); c += d; b = rotl32(b ^ c, 7);
+// lane q of a quad reads the value of lane (q + K) & 3 of its quad; every lane of the quad must be active
+template <int K> __device__ __forceinline__ u32 quad_rot(u32 v) {
+    constexpr int ctrl = ((0 + K) & 3) | (((1 + K) & 3) << 2) | (((2 + K) & 3) << 4) | (((3 + K) & 3) << 6);      // quad_perm
+    return (u32)__builtin_amdgcn_mov_dpp((int)v, ctrl, 0xf, 0xf, true);
+}
+// (v0, v1, v2, v3) rotated left by q places: v_k = v_(k + q) & 3
+__device__ __forceinline__ void rot4_by(u32 &v0, u32 &v1, u32 &v2, u32 &v3, u32 q) {
+    u32 t0 = q & 1 ? v1 : v0, t1 = q & 1 ? v2 : v1, t2 = q & 1 ? v3 : v2, t3 = q & 1 ? v0 : v3;
+    v0 = q & 2 ? t2 : t0; v1 = q & 2 ? t3 : t1; v2 = q & 2 ? t0 : t2; v3 = q & 2 ? t1 : t3;
+}
+// ks = words 4 q .. 4 q + 3 of the ChaCha20 block whose input column q is (a0, b0, c0, d0) = (constant q, key q, key 4 + q, counter or nonce
+// q - 1), in lane q of a quad whose four lanes all call this together
+__device__ __forceinline__ void chacha20_quad(u32 ks[4], u32 a0, u32 b0, u32 c0, u32 d0, u32 q) {
+    u32 a = a0, b = b0, c = c0, d = d0;
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        AEAD_LONG_QR(a, b, c, d)                                                  // columns
+        b = quad_rot<1>(b); c = quad_rot<2>(c); d = quad_rot<3>(d);               // lane q: x[q], x[4 + (q + 1) & 3], x[8 + (q + 2) & 3], x[12 + (q + 3) & 3]
+        AEAD_LONG_QR(a, b, c, d)                                                  // diagonals
+        b = quad_rot<3>(b); c = quad_rot<2>(c); d = quad_rot<1>(d);
+    }
+    a += a0; b += b0; c += c0; d += d0;
+    // the transpose: lane q holds v[row][q] for the four rows and wants v[q][column] for the four columns
+    rot4_by(a, b, c, d, q);                                                       // register k: v[(k + q) & 3][q]
+    b = quad_rot<3>(b); c = quad_rot<2>(c); d = quad_rot<1>(d);                   // register k from lane q - k: v[q][(q - k) & 3]
+    u32 u0 = a, u1 = d, u2 = c, u3 = b;                                           // u_k = v[q][(q + k) & 3]
+    rot4_by(u0, u1, u2, u3, (4u - q) & 3u);                                       // u_k = v[q][k]
+    ks[0] = u0; ks[1] = u1; ks[2] = u2; ks[3] = u3;
+}
+// the input column of lane q for the record's key and nonce; d0 is the counter in lane 0
+__device__ __forceinline__ void chacha20_quad_column(u32 &a0, u32 &b0, u32 &c0, u32 &d0, const u32 *__restrict__ kp, const u32 *__restrict__ np, u32 q) {
+    a0 = q == 0 ? 0x61707865u : q == 1 ? 0x3320646eu : q == 2 ? 0x79622d32u : 0x6b206574u;
+    b0 = kp[q]; c0 = kp[4 + q]; d0 = q ? np[q - 1] : 0u;
+}
+// out = a b mod 2^130 - 5 on 26-bit limbs, left as poly1305_block leaves h.  a: limbs below 2^28 (a sum of at most three values this function
+// or p5_carry left, or one of them and a block).  b: a MULTIPLIER -- a general element, not a clamped one: a clamped r or a power that p5_carry
+// has carried, limbs at most 2^26, so 5 b_i < 2^29 fits 32 bits and a column is below 5 2^28 5 2^26 < 2^59.  Out: limbs below 2^26, but
+// out_1 < 2^26 + 2^11 (d_4 >> 26 < 2^33, times 5, carried once).  out may be a or b.
+__device__ __forceinline__ void p5_mul(u32 out[5], const u32 a[5], const u32 b[5]) {
+    const u32 h0 = a[0], h1 = a[1], h2 = a[2], h3 = a[3], h4 = a[4];
+    const u32 r0 = b[0], r1 = b[1], r2 = b[2], r3 = b[3], r4 = b[4], s1 = r1 * 5, s2 = r2 * 5, s3 = r3 * 5, s4 = r4 * 5;
+    u64 d0 = (u64)h0 * r0 + (u64)h1 * s4 + (u64)h2 * s3 + (u64)h3 * s2 + (u64)h4 * s1;
+    u64 d1 = (u64)h0 * r1 + (u64)h1 * r0 + (u64)h2 * s4 + (u64)h3 * s3 + (u64)h4 * s2;
+    u64 d2 = (u64)h0 * r2 + (u64)h1 * r1 + (u64)h2 * r0 + (u64)h3 * s4 + (u64)h4 * s3;
+    u64 d3 = (u64)h0 * r3 + (u64)h1 * r2 + (u64)h2 * r1 + (u64)h3 * r0 + (u64)h4 * s4;
+    u64 d4 = (u64)h0 * r4 + (u64)h1 * r3 + (u64)h2 * r2 + (u64)h3 * r1 + (u64)h4 * r0;
+    d1 += d0 >> 26; d2 += d1 >> 26; d3 += d2 >> 26; d4 += d3 >> 26;
+    const u64 e = (d0 & 0x3ffffffu) + (d4 >> 26) * 5;
+    out[0] = (u32)e & 0x3ffffffu; out[1] = ((u32)d1 & 0x3ffffffu) + (u32)(e >> 26);
+    out[2] = (u32)d2 & 0x3ffffffu; out[3] = (u32)d3 & 0x3ffffffu; out[4] = (u32)d4 & 0x3ffffffu;
+}
+// what p5_mul left, carried until it can be a multiplier: limbs below 2^26, h_1 at most 2^26 (the two passes of poly1305_finish)
+__device__ __forceinline__ void p5_carry(u32 h[5]) {
+    u32 c;
+    c = h[1] >> 26; h[1] &= 0x3ffffffu; h[2] += c; c = h[2] >> 26; h[2] &= 0x3ffffffu; h[3] += c; c = h[3] >> 26; h[3] &= 0x3ffffffu; h[4] += c;
+    c = h[4] >> 26; h[4] &= 0x3ffffffu; h[0] += c * 5; c = h[0] >> 26; h[0] &= 0x3ffffffu; h[1] += c;
+}
+// out = r^e, e >= 1, square-and-multiply from the top bit; r and every intermediate are carried multipliers
+__device__ __forceinline__ void p5_pow(u32 out[5], const u32 r[5], u32 e) {
+    u32 acc[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) acc[k] = r[k];
+    for (int b = 30 - __clz((int)e); b >= 0; b--) {
+        p5_mul(acc, acc, acc); p5_carry(acc);
+        if ((e >> b) & 1u) { p5_mul(acc, acc, r); p5_carry(acc); }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; k++) out[k] = acc[k];
+}
+// h += the sixteen bytes m as a full block (the 2^128 bit set)
+__device__ __forceinline__ void p5_add_block(u32 h[5], const u32 m[4]) {
+    h[0] += m[0] & 0x3ffffffu; h[1] += ((m[0] >> 26) | (m[1] << 6)) & 0x3ffffffu; h[2] += ((m[1] >> 20) | (m[2] << 12)) & 0x3ffffffu;
+    h[3] += ((m[2] >> 14) | (m[3] << 18)) & 0x3ffffffu; h[4] += (m[3] >> 8) | (1u << 24);
+}
+// the table of a call's long records: seg_first[j], j <= n_long, the first workgroup of long record j; long_rec[j] its index in the call;
+// seg_owner[g] the long record of workgroup g.  A record of c blocks has ceil(c / S) segments, none when it is empty.
+// MODE 0: authenticate the ciphertext that is there (open; `tagged` = 16).  MODE 1: encrypt, write and authenticate (seal).  MODE 2: the
+// authenticator alone under keys[i] = r || s on a message of whole blocks (rofl_dbg_poly1305_long).
+template <int MODE>
+__device__ __forceinline__ void aead_long_segment(const u32 *__restrict__ key_idx, const u32 *__restrict__ keys, const u32 *__restrict__ nonce, const uint8_t *__restrict__ data,
+                                                  const u64 *__restrict__ data_off, u32 tagged, uint8_t *__restrict__ out, const u32 *__restrict__ seg_first,
+                                                  const u32 *__restrict__ long_rec, const u32 *__restrict__ seg_owner, u32 S, u32 *__restrict__ part /* [segments][8] */) {
+    __shared__ u32 pw[AEAD_LONG_T][5];                 // pw[k] = r^(k + 1), carried
+    __shared__ u64 wsum[AEAD_LONG_T / 64][5];
+    const u32 t = threadIdx.x, q = t & 3u, g = blockIdx.x, j = seg_owner[g], i = long_rec[j], b_first = (g - seg_first[j]) * S;
+    const u64 o = data_off[i], len = data_off[i + 1] - o - tagged;
+    const u32 nblk = (u32)((len + 15) >> 4), n_g = nblk - b_first < S ? nblk - b_first : S;
+    const u32 *kp = keys + 8 * (size_t)(MODE == 2 ? i : key_idx ? key_idx[i] : i), *np = nonce + 3 * (size_t)i;
+    u32 a0 = 0, b0 = 0, c0 = 0, d0 = 0, ks[4];
+    if (MODE != 2) chacha20_quad_column(a0, b0, c0, d0, kp, np, q);
+    if (MODE == 2) {
+        if (t == 0) { poly1305 P; poly1305_init(P, kp);
+#pragma unroll
+            for (int k = 0; k < 5; k++) pw[0][k] = P.r[k]; }
+    } else if (t < 4) {                                // block 0 in one quad; lane 0 holds its words 0 .. 3, r
+        chacha20_quad(ks, a0, b0, c0, d0, q);
+        if (t == 0) { poly1305 P; poly1305_init(P, ks);
+#pragma unroll
+            for (int k = 0; k < 5; k++) pw[0][k] = P.r[k]; }
+    }
+    __syncthreads();
+    for (u32 h = 1; h < AEAD_LONG_T; h <<= 1) {        // r^(h + t + 1) = r^h r^(t + 1) for t < h: the table doubles
+        if (t < h) { u32 x[5]; p5_mul(x, pw[h - 1], pw[t]); p5_carry(x);
+#pragma unroll
+            for (int k = 0; k < 5; k++) pw[h + t][k] = x[k]; }
+        __syncthreads();
+    }
+    u32 R[5], acc[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 5; k++) R[k] = pw[AEAD_LONG_T - 1][k];
+    uint8_t *dst = MODE == 1 ? out + o + 16 * (u64)i : nullptr;
+    for (u32 lb = t; lb - t < n_g; lb += AEAD_LONG_T) {      // whole passes: the lanes of a quad stay together for the keystream
+        const u32 blk = b_first + lb;
+        if (MODE == 1) chacha20_quad(ks, a0, b0, c0, q ? d0 : 1u + (blk >> 2), q);      // lane 0's d is the counter, the others' a nonce word
+        if (lb < n_g) {
+            const u64 pos = 16 * (u64)blk;
+            const u32 valid = (u32)(len - pos < 16 ? len - pos : 16);
+            u32 m[4];
+            load_block16(m, data, o + pos, valid);
+            if (MODE == 1) {
+#pragma unroll
+                for (int w = 0; w < 4; w++) m[w] ^= ks[w];
+                block16_keep(m, valid);
+                store_block16(dst + pos, m, valid);
+            }
+            p5_mul(acc, acc, R);                       // acc: a product plus a block, limbs below 2^27 + 2^11
+            p5_add_block(acc, m);
+        }
+    }
+    u64 v[5] = {0, 0, 0, 0, 0};
+    if (t < n_g) {                                     // the lane's last block is l_t = t + (K - 1) T: scale by r^(n_g - l_t), one of r^1 .. r^T
+        const u32 e = n_g - (t + ((n_g - 1 - t) / AEAD_LONG_T) * AEAD_LONG_T);
+        u32 x[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) x[k] = pw[e - 1][k];
+        p5_mul(acc, acc, x);
+#pragma unroll
+        for (int k = 0; k < 5; k++) v[k] = acc[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 5; k++)                        // 256 limbs below 2^26 + 2^11: below 2^35 in 64 bits
+        for (int d = 32; d; d >>= 1) v[k] += __shfl_xor(v[k], d);
+    if ((t & 63u) == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) wsum[t >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (t == 0) {
+        u64 d[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) { d[k] = 0; for (u32 w = 0; w < AEAD_LONG_T / 64; w++) d[k] += wsum[w][k]; }
+        d[1] += d[0] >> 26; d[2] += d[1] >> 26; d[3] += d[2] >> 26; d[4] += d[3] >> 26;
+        const u64 e = (d[0] & 0x3ffffffu) + (d[4] >> 26) * 5;                   // P_g as p5_mul leaves a product: limbs below 2^26, limb 1 below 2^26 + 2^11
+        u32 *pg = part + 8 * (size_t)g;
+        pg[0] = (u32)e & 0x3ffffffu; pg[1] = ((u32)d[1] & 0x3ffffffu) + (u32)(e >> 26);
+        pg[2] = (u32)d[2] & 0x3ffffffu; pg[3] = (u32)d[3] & 0x3ffffffu; pg[4] = (u32)d[4] & 0x3ffffffu;
+    }
+}
+// one lane per long record: the AD, the segments' partial sums in order, the length block, the tag -- written (MODE 1), compared with the
+// record's and turned into the verdict (MODE 0; a record shorter than its tag: verdict 2), or Poly1305's own finish (MODE 2)
+template <int MODE>
+__device__ __forceinline__ void aead_long_finish(u32 n_long, const u32 *__restrict__ key_idx, const u32 *__restrict__ keys, const u32 *__restrict__ nonce, const uint8_t *__restrict__ ad,
+                                                 const u64 *__restrict__ ad_off, const uint8_t *__restrict__ data, const u64 *__restrict__ data_off, const u32 *__restrict__ seg_first,
+                                                 const u32 *__restrict__ long_rec, u32 S, const u32 *__restrict__ part, uint8_t *__restrict__ out, uint8_t *__restrict__ verdict) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_long) return;
+    const u32 i = long_rec[j];
+    const u64 o = data_off[i], rlen = data_off[i + 1] - o;
+    if (MODE == 0 && rlen < 16) { verdict[i] = 2; return; }
+    const u64 len = rlen - (MODE == 0 ? 16 : 0);
+    u64 alen = 0;
+    u32 key[8], nc[3], s[4], tag[4];
+    poly1305 P;
+    if (MODE == 2) {
+#pragma unroll
+        for (int w = 0; w < 8; w++) key[w] = keys[8 * (size_t)i + w];
+        poly1305_init(P, key);
+#pragma unroll
+        for (int w = 0; w < 4; w++) s[w] = key[4 + w];
+    } else {
+        aead_begin(i, key_idx, keys, nonce, key, nc, P, s);
+        const u64 ao = ad_off[i];
+        alen = ad_off[i + 1] - ao;
+        aead_absorb(P, ad, ao, alen);
+    }
+    const u32 first = seg_first[j], ns = seg_first[j + 1] - first;
+    if (ns) {                                          // H = H r^(n_g) + P_g: a product plus a P_g, limbs below 2^27 + 2^12
+        u32 pwr[5];
+        if (ns > 1) p5_pow(pwr, P.r, S);
+        for (u32 g = 0; g + 1 < ns; g++) {
+            p5_mul(P.h, P.h, pwr);
+#pragma unroll
+            for (int k = 0; k < 5; k++) P.h[k] += part[8 * (size_t)(first + g) + k];
+        }
+        p5_pow(pwr, P.r, (u32)((len + 15) >> 4) - (ns - 1) * S);
+        p5_mul(P.h, P.h, pwr);
+#pragma unroll
+        for (int k = 0; k < 5; k++) P.h[k] += part[8 * (size_t)(first + ns - 1) + k];
+    }
+    if (MODE == 2) {
+        poly1305_finish(tag, P, s);
+#pragma unroll
+        for (int w = 0; w < 4; w++) reinterpret_cast<u32 *>(out)[4 * (size_t)i + w] = tag[w];
+        return;
+    }
+    aead_tag(tag, P, s, alen, len);
+    if (MODE == 1) { store_block16(out + o + 16 * (u64)i + len, tag, 16); return; }
+    u32 got[4];
+    load_block16(got, data, o + len, 16);
+    verdict[i] = ((tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3])) != 0 ? 1 : 0;
+}
+__global__ void __launch_bounds__(AEAD_LONG_T) k_aead_long_seal(const u32 *__restrict__ key_idx, const u32 *__restrict__ keys, const u32 *__restrict__ nonce, const uint8_t *__restrict__ pt,
+                                                                const u64 *__restrict__ pt_off, uint8_t *__restrict__ out, const u32 *__restrict__ seg_first,
+                                                                const u32 *__restrict__ long_rec, const u32 *__restrict__ seg_owner, u32 S, u32 *__restrict__ part) {
+    aead_long_segment<1>(key_idx, keys, nonce, pt, pt_off, 0, out, seg_first, long_rec, seg_owner, S, part);
+}
+__global__ void __launch_bounds__(AEAD_LONG_T) k_aead_long_mac(const u32 *__restrict__ key_idx, const u32 *__restrict__ keys, const u32 *__restrict__ nonce, const uint8_t *__restrict__ sealed,
+                                                               const u64 *__restrict__ s_off, const u32 *__restrict__ seg_first, const u32 *__restrict__ long_rec,
+                                                               const u32 *__restrict__ seg_owner, u32 S, u32 *__restrict__ part) {
+    aead_long_segment<0>(key_idx, keys, nonce, sealed, s_off, 16, nullptr, seg_first, long_rec, seg_owner, S, part);
+}
+__global__ void __launch_bounds__(64) k_aead_long_seal_finish(u32 n_long, const u32 *__restrict__ key_idx, const u32 *__restrict__ keys, const u32 *__restrict__ nonce,
+                                                              const uint8_t *__restrict__ ad, const u64 *__restrict__ ad_off, const u64 *__restrict__ pt_off, const u32 *__restrict__ seg_first,
+                                                              const u32 *__restrict__ long_rec, u32 S, const u32 *__restrict__ part, uint8_t *__restrict__ out) {
+    aead_long_finish<1>(n_long, key_idx, keys, nonce, ad, ad_off, nullptr, pt_off, seg_first, long_rec, S, part, out, nullptr);
+}
+__global__ void __launch_bounds__(64) k_aead_long_open_finish(u32 n_long, const u32 *__restrict__ key_idx, const u32 *__restrict__ keys, const u32 *__restrict__ nonce,
+                                                              const uint8_t *__restrict__ ad, const u64 *__restrict__ ad_off, const uint8_t *__restrict__ sealed, const u64 *__restrict__ s_off,
+                                                              const u32 *__restrict__ seg_first, const u32 *__restrict__ long_rec, u32 S, const u32 *__restrict__ part,
+                                                              uint8_t *__restrict__ verdict) {
+    aead_long_finish<0>(n_long, key_idx, keys, nonce, ad, ad_off, sealed, s_off, seg_first, long_rec, S, part, nullptr, verdict);
+}
+// after the verdicts: the plaintext of a record whose verdict is 0, zeros for any other; one workgroup per (record, segment) as above
+__global__ void __launch_bounds__(AEAD_LONG_T) k_aead_long_decrypt(const u32 *__restrict__ key_idx, const u32 *__restrict__ keys, const u32 *__restrict__ nonce, const uint8_t *__restrict__ sealed,
+                                                                   const u64 *__restrict__ s_off, const uint8_t *__restrict__ verdict, uint8_t *__restrict__ pt_out,
+                                                                   const u32 *__restrict__ seg_first, const u32 *__restrict__ long_rec, const u32 *__restrict__ seg_owner, u32 S) {
+    const u32 t = threadIdx.x, q = t & 3u, g = blockIdx.x, j = seg_owner[g], i = long_rec[j], b_first = (g - seg_first[j]) * S;
+    const u64 o = s_off[i], len = s_off[i + 1] - o - 16;
+    const u32 nblk = (u32)((len + 15) >> 4), n_g = nblk - b_first < S ? nblk - b_first : S;
+    const bool ok = verdict[i] == 0;                   // one record: the same in every lane of the workgroup
+    u32 a0, b0, c0, d0, ks[4] = {0, 0, 0, 0};
+    chacha20_quad_column(a0, b0, c0, d0, keys + 8 * (size_t)(key_idx ? key_idx[i] : i), nonce + 3 * (size_t)i, q);
+    for (u32 lb = t; lb - t < n_g; lb += AEAD_LONG_T) {
+        const u32 blk = b_first + lb;
+        if (ok) chacha20_quad(ks, a0, b0, c0, q ? d0 : 1u + (blk >> 2), q);
+        if (lb < n_g) {
+            const u64 pos = 16 * (u64)blk;
+            const u32 valid = (u32)(len - pos < 16 ? len - pos : 16);
+            u32 m[4] = {0, 0, 0, 0};
+            if (ok) {
+                load_block16(m, sealed, o + pos, valid);
+#pragma unroll
+                for (int w = 0; w < 4; w++) m[w] ^= ks[w];
+            }
+            store_block16(pt_out + o + pos, m, valid);
+        }
+    }
+}
+// Poly1305 of whole-block messages under keys r || s through the long route's segment and finish steps (rofl_dbg_poly1305_long)
+__global__ void __launch_bounds__(AEAD_LONG_T) k_dbg_poly1305_long_seg(const u32 *__restrict__ key, const uint8_t *__restrict__ msg, const u64 *__restrict__ off, const u32 *__restrict__ seg_first,
+                                                                       const u32 *__restrict__ long_rec, const u32 *__restrict__ seg_owner, u32 S, u32 *__restrict__ part) {
+    aead_long_segment<2>(nullptr, key, nullptr, msg, off, 0, nullptr, seg_first, long_rec, seg_owner, S, part);
+}
+__global__ void __launch_bounds__(64) k_dbg_poly1305_long_finish(u32 n, const u32 *__restrict__ key, const u64 *__restrict__ off, const u32 *__restrict__ seg_first,
+                                                                 const u32 *__restrict__ long_rec, u32 S, const u32 *__restrict__ part, uint8_t *__restrict__ tag_out) {
+    aead_long_finish<2>(n, nullptr, key, nullptr, nullptr, nullptr, nullptr, off, seg_first, long_rec, S, part, tag_out, nullptr);
 }
 #endif
 // ================================================================ complaints (rofl_dleq_prove / rofl_dleq_verify)

@@ -704,6 +704,101 @@ void aead_upload(StagedCall &st, const AeadParts &p, size_t n_keys, const uint64
     st.upload();
     if (derive_round) ROFL_LAUNCH(k_aead_derive, per_item(n_keys), dim3(64), 0, st.C.stream, (u32)n_keys, (u64)*derive_round, const_cast<u64 *>(st.dev<u64>(p.keys)));
 }
+// ---- the long route: a record of AEAD_LONG_MIN bytes or more is cut into segments, one workgroup each (k_aead_long_*) ----
+// The smallest power of two from which the long route's median beat the one-lane kernels' by more than the two spreads at every batch size
+// measured, seal and open (profiles/aead_long.json, scripts/gpu_seal_long.py: 16 KB; at n = 1 and n = 64 it wins from 1 KB, in the
+// largest batches the call is its copies and the two are level below 16 KB); not a knob.
+// (ROFL_AEAD_LONG_MIN: a second build for the measurement alone -- 0xffffffff keeps every record on the one-lane kernels, the parent's route)
+#ifndef ROFL_AEAD_LONG_MIN
+#define ROFL_AEAD_LONG_MIN 16384
+#endif
+constexpr uint32_t AEAD_LONG_MIN = ROFL_AEAD_LONG_MIN;
+// the long records of a call and their workgroups as the kernels read them: [seg_first (n_long + 1) | long_rec (n_long) | seg_owner (n_seg)].
+// `forced`: every record (the debug entries); a record shorter than its tag has no segments.
+struct AeadLong {
+    std::vector<uint32_t> tab; size_t nl = 0, nseg = 0;
+    const u32 *first(const u32 *dev) const { return dev; }
+    const u32 *rec(const u32 *dev) const { return dev + nl + 1; }
+    const u32 *owner(const u32 *dev) const { return dev + 2 * nl + 1; }
+};
+AeadLong aead_long_table(size_t n, const uint64_t *off, uint64_t tagged, uint32_t S, bool forced) {
+    AeadLong L;
+    std::vector<uint32_t> first{0}, rec, owner;
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t rlen = off[i + 1] - off[i], len = rlen >= tagged ? rlen - tagged : 0;
+        if (!forced && (rlen < tagged || len < AEAD_LONG_MIN)) continue;
+        const uint64_t blocks = (len + 15) / 16;
+        owner.insert(owner.end(), (size_t)((blocks + S - 1) / S), (uint32_t)rec.size());
+        rec.push_back((uint32_t)i); first.push_back((uint32_t)owner.size());
+    }
+    L.nl = rec.size(); L.nseg = owner.size();
+    if (L.nl) { L.tab = first; L.tab.insert(L.tab.end(), rec.begin(), rec.end()); L.tab.insert(L.tab.end(), owner.begin(), owner.end()); }
+    return L;
+}
+int aead_long_seg_check(uint32_t *seg_blocks) {
+    if (*seg_blocks == 0) *seg_blocks = AEAD_LONG_S;
+    if (*seg_blocks % AEAD_LONG_T) return fail(ROFL_BAD_PARAM, "seg_blocks is a multiple of the pass tile");
+    return ROFL_OK;
+}
+int aead_seal_call(bool forced, uint32_t S, size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                   const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes, const uint64_t *pt_off, uint8_t *sealed_out) {
+    bool done; size_t ad_total, pt_total;
+    if (int rc = aead_check(true, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, pt_bytes, pt_off, sealed_out, nullptr, &ad_total, &pt_total, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        const AeadLong L = aead_long_table(n, pt_off, 0, S, forced);
+        StagedCall st; Ctx &C = st.C;
+        const AeadParts p = aead_parts(st, true, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, ad_total, pt_bytes, pt_off, pt_total);
+        const InPart tab = st.in(L.nl ? L.tab.data() : nullptr, L.tab.size() * 4);
+        const OutPart sealed = st.out(sealed_out, pt_total + 16 * n);
+        u32 *part = L.nl ? st.work<u32>(std::max<size_t>(L.nseg, 1) * 8, kSecret) : nullptr;
+        aead_upload(st, p, n_keys, derive_round);
+        if (L.nl < n) ROFL_LAUNCH(k_aead_seal, per_item(n), dim3(64), 0, C.stream, (u32)n, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce), st.dev<uint8_t>(p.ad),
+                                  st.dev<u64>(p.ad_off), st.dev<uint8_t>(p.data), st.dev<u64>(p.data_off), st.dev<uint8_t>(sealed), (u64)AEAD_LONG_MIN);
+        if (L.nl) {
+            const u32 *t = st.dev<u32>(tab);
+            if (L.nseg) ROFL_LAUNCH(k_aead_long_seal, dim3((unsigned)L.nseg), dim3(AEAD_LONG_T), 0, C.stream, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce),
+                                    st.dev<uint8_t>(p.data), st.dev<u64>(p.data_off), st.dev<uint8_t>(sealed), L.first(t), L.rec(t), L.owner(t), (u32)S, part);
+            ROFL_LAUNCH(k_aead_long_seal_finish, per_item(L.nl), dim3(64), 0, C.stream, (u32)L.nl, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce), st.dev<uint8_t>(p.ad),
+                        st.dev<u64>(p.ad_off), st.dev<u64>(p.data_off), L.first(t), L.rec(t), (u32)S, (const u32 *)part, st.dev<uint8_t>(sealed));
+        }
+        st.finish();
+        return ROFL_OK;
+    });
+}
+// open: the partial sums over the ciphertext, then the verdicts, then the plaintexts of the records whose verdict is 0 -- no plaintext byte of
+// a record exists before its verdict does
+int aead_open_call(bool forced, uint32_t S, size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                   const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes, const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out) {
+    bool done; size_t ad_total, s_total;
+    if (int rc = aead_check(false, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, sealed_bytes, sealed_off, pt_out, verdict_out, &ad_total, &s_total, &done)) return rc;
+    if (done) return ROFL_OK;
+    return guarded([&]() -> int {
+        const AeadLong L = aead_long_table(n, sealed_off, 16, S, forced);
+        StagedCall st; Ctx &C = st.C;
+        const AeadParts p = aead_parts(st, false, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, ad_total, sealed_bytes, sealed_off, s_total);
+        const InPart tab = st.in(L.nl ? L.tab.data() : nullptr, L.tab.size() * 4);
+        const OutPart pt = st.out(nullptr, s_total, kSecret), verdict = st.out(verdict_out, n);      // the plaintexts laid out like the records: delivered below
+        u32 *part = L.nl ? st.work<u32>(std::max<size_t>(L.nseg, 1) * 8, kSecret) : nullptr;
+        aead_upload(st, p, n_keys, derive_round);
+        if (L.nl < n) ROFL_LAUNCH(k_aead_open, per_item(n), dim3(64), 0, C.stream, (u32)n, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce), st.dev<uint8_t>(p.ad),
+                                  st.dev<u64>(p.ad_off), st.dev<uint8_t>(p.data), st.dev<u64>(p.data_off), st.dev<uint8_t>(pt), st.dev<uint8_t>(verdict), (u64)AEAD_LONG_MIN);
+        if (L.nl) {
+            const u32 *t = st.dev<u32>(tab);
+            if (L.nseg) ROFL_LAUNCH(k_aead_long_mac, dim3((unsigned)L.nseg), dim3(AEAD_LONG_T), 0, C.stream, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce),
+                                    st.dev<uint8_t>(p.data), st.dev<u64>(p.data_off), L.first(t), L.rec(t), L.owner(t), (u32)S, part);
+            ROFL_LAUNCH(k_aead_long_open_finish, per_item(L.nl), dim3(64), 0, C.stream, (u32)L.nl, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce), st.dev<uint8_t>(p.ad),
+                        st.dev<u64>(p.ad_off), st.dev<uint8_t>(p.data), st.dev<u64>(p.data_off), L.first(t), L.rec(t), (u32)S, (const u32 *)part, st.dev<uint8_t>(verdict));
+            if (L.nseg) ROFL_LAUNCH(k_aead_long_decrypt, dim3((unsigned)L.nseg), dim3(AEAD_LONG_T), 0, C.stream, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce),
+                                    st.dev<uint8_t>(p.data), st.dev<u64>(p.data_off), (const uint8_t *)st.dev<uint8_t>(verdict), st.dev<uint8_t>(pt), L.first(t), L.rec(t), L.owner(t), (u32)S);
+        }
+        st.finish();
+        const uint8_t *hp = st.host(pt);
+        for (size_t i = 0; i < n; i++)      // a record shorter than its tag writes nothing; the 16 bytes after a plaintext are not the library's
+            if (verdict_out[i] != 2 && sealed_off[i + 1] - sealed_off[i] > 16) memcpy(pt_out + sealed_off[i], hp + sealed_off[i], (size_t)(sealed_off[i + 1] - sealed_off[i] - 16));
+        return ROFL_OK;
+    });
+}
 // a packed list of messages for the Poly1305 hooks
 int poly_check(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, const uint8_t *tag_out16, size_t *total, bool *done) {
     *done = n == 0; *total = 0;
@@ -715,42 +810,34 @@ int poly_check(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const u
 }  // namespace
 extern "C" {
 // The lane's copies of the keys (as given and derived) and of the plaintexts -- pinned staging and device workspace -- are overwritten with
-// zeros before the call returns or unwinds; keystream and authenticator keys live in registers only.  The sealed records are public.
+// zeros before the call returns or unwinds; keystream and authenticator keys live in registers and LDS only, and the long route's partial
+// sums, functions of the one-time key r, in a workspace that is wiped with the keys.  The sealed records are public.
 int rofl_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
                    const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes, const uint64_t *pt_off, uint8_t *sealed_out) {
-    bool done; size_t ad_total, pt_total;
-    if (int rc = aead_check(true, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, pt_bytes, pt_off, sealed_out, nullptr, &ad_total, &pt_total, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        StagedCall st; Ctx &C = st.C;
-        const AeadParts p = aead_parts(st, true, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, ad_total, pt_bytes, pt_off, pt_total);
-        const OutPart sealed = st.out(sealed_out, pt_total + 16 * n);
-        aead_upload(st, p, n_keys, derive_round);
-        ROFL_LAUNCH(k_aead_seal, per_item(n), dim3(64), 0, C.stream, (u32)n, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce), st.dev<uint8_t>(p.ad), st.dev<u64>(p.ad_off),
-                    st.dev<uint8_t>(p.data), st.dev<u64>(p.data_off), st.dev<uint8_t>(sealed));
-        st.finish();
-        return ROFL_OK;
-    });
+    return aead_seal_call(false, AEAD_LONG_S, n_keys, key32, derive_round, n, key_idx, nonce12, ad_bytes, ad_off, pt_bytes, pt_off, sealed_out);
 }
 // the keys in the upload and the plaintexts in the download are wiped the same way; records, ADs, nonces and verdicts are public
 int rofl_aead_open(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
                    const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes, const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out) {
-    bool done; size_t ad_total, s_total;
-    if (int rc = aead_check(false, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, sealed_bytes, sealed_off, pt_out, verdict_out, &ad_total, &s_total, &done)) return rc;
-    if (done) return ROFL_OK;
-    return guarded([&]() -> int {
-        StagedCall st; Ctx &C = st.C;
-        const AeadParts p = aead_parts(st, false, n_keys, key32, n, key_idx, nonce12, ad_bytes, ad_off, ad_total, sealed_bytes, sealed_off, s_total);
-        const OutPart pt = st.out(nullptr, s_total, kSecret), verdict = st.out(verdict_out, n);      // the plaintexts laid out like the records: delivered below
-        aead_upload(st, p, n_keys, derive_round);
-        ROFL_LAUNCH(k_aead_open, per_item(n), dim3(64), 0, C.stream, (u32)n, st.dev<u32>(p.idx), st.dev<u32>(p.keys), st.dev<u32>(p.nonce), st.dev<uint8_t>(p.ad), st.dev<u64>(p.ad_off),
-                    st.dev<uint8_t>(p.data), st.dev<u64>(p.data_off), st.dev<uint8_t>(pt), st.dev<uint8_t>(verdict));
-        st.finish();
-        const uint8_t *hp = st.host(pt);
-        for (size_t i = 0; i < n; i++)      // a record shorter than its tag writes nothing; the 16 bytes after a plaintext are not the library's
-            if (verdict_out[i] != 2 && sealed_off[i + 1] - sealed_off[i] > 16) memcpy(pt_out + sealed_off[i], hp + sealed_off[i], (size_t)(sealed_off[i + 1] - sealed_off[i] - 16));
-        return ROFL_OK;
-    });
+    return aead_open_call(false, AEAD_LONG_S, n_keys, key32, derive_round, n, key_idx, nonce12, ad_bytes, ad_off, sealed_bytes, sealed_off, pt_out, verdict_out);
+}
+// every record of the call down the long route, whatever its length, in segments of seg_blocks blocks (0: AEAD_LONG_S)
+int rofl_dbg_aead_seal_long(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                            const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *pt_bytes, const uint64_t *pt_off, uint8_t *sealed_out, uint32_t seg_blocks) {
+    if (int rc = aead_long_seg_check(&seg_blocks)) return rc;
+    return aead_seal_call(true, seg_blocks, n_keys, key32, derive_round, n, key_idx, nonce12, ad_bytes, ad_off, pt_bytes, pt_off, sealed_out);
+}
+int rofl_dbg_aead_open_long(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
+                            const uint8_t *ad_bytes, const uint64_t *ad_off, const uint8_t *sealed_bytes, const uint64_t *sealed_off, uint8_t *pt_out, uint8_t *verdict_out,
+                            uint32_t seg_blocks) {
+    if (int rc = aead_long_seg_check(&seg_blocks)) return rc;
+    return aead_open_call(true, seg_blocks, n_keys, key32, derive_round, n, key_idx, nonce12, ad_bytes, ad_off, sealed_bytes, sealed_off, pt_out, verdict_out);
+}
+// out3 = {blocks of a pass tile, blocks of a built segment, AEAD_LONG_MIN in bytes}
+int rofl_dbg_aead_long_geometry(uint32_t *out3) {
+    if (!out3) return fail(ROFL_BAD_PARAM, "bad parameter");
+    out3[0] = AEAD_LONG_T; out3[1] = AEAD_LONG_S; out3[2] = AEAD_LONG_MIN;
+    return ROFL_OK;
 }
 // the two calls in plain C++ on one thread, no GPU: same parameters, same checks, same bytes
 int rofl_dbg_host_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx, const uint8_t *nonce12,
@@ -806,6 +893,29 @@ int rofl_dbg_poly1305(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, 
         const OutPart tags = st.out(tag_out16, n * 16);
         st.upload();
         ROFL_LAUNCH(k_dbg_poly1305, per_item(n), dim3(64), 0, C.stream, (u32)n, st.dev<u32>(keys), st.dev<uint8_t>(msg), st.dev<u64>(off), st.dev<u32>(tags));
+        st.finish();
+        return ROFL_OK;
+    });
+}
+// ... and through the long route's segment and finish kernels (k_dbg_poly1305_long_seg, k_dbg_poly1305_long_finish): whole-block messages only
+int rofl_dbg_poly1305_long(size_t n, const uint8_t *key32, const uint8_t *msg_bytes, const uint64_t *msg_off, uint8_t *tag_out16, uint32_t seg_blocks) {
+    bool done; size_t total;
+    if (int rc = aead_long_seg_check(&seg_blocks)) return rc;
+    if (int rc = poly_check(n, key32, msg_bytes, msg_off, tag_out16, &total, &done)) return rc;
+    if (done) return ROFL_OK;
+    for (size_t j = 0; j < n; j++) if ((msg_off[j + 1] - msg_off[j]) % 16) return fail(ROFL_BAD_PARAM, "a message of the long route's hook is whole 16-byte blocks");
+    return guarded([&]() -> int {
+        const AeadLong L = aead_long_table(n, msg_off, 0, seg_blocks, true);
+        StagedCall st; Ctx &C = st.C;
+        const InPart keys = st.in(key32, n * 32), off = st.in(msg_off, (n + 1) * 8), msg = st.in(msg_bytes, total, kPadded), tab = st.in(L.tab.data(), L.tab.size() * 4);
+        const OutPart tags = st.out(tag_out16, n * 16);
+        u32 *part = st.work<u32>(std::max<size_t>(L.nseg, 1) * 8);
+        st.upload();
+        const u32 *t = st.dev<u32>(tab);
+        if (L.nseg) ROFL_LAUNCH(k_dbg_poly1305_long_seg, dim3((unsigned)L.nseg), dim3(AEAD_LONG_T), 0, C.stream, st.dev<u32>(keys), st.dev<uint8_t>(msg), st.dev<u64>(off), L.first(t), L.rec(t),
+                                L.owner(t), (u32)seg_blocks, part);
+        ROFL_LAUNCH(k_dbg_poly1305_long_finish, per_item(n), dim3(64), 0, C.stream, (u32)n, st.dev<u32>(keys), st.dev<u64>(off), L.first(t), L.rec(t), (u32)seg_blocks, (const u32 *)part,
+                    st.dev<uint8_t>(tags));
         st.finish();
         return ROFL_OK;
     });

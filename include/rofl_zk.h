@@ -726,6 +726,43 @@ int rofl_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const
                      size_t n_pairs, const rofl_dh_pair_t *pairs, const uint8_t *ctx32,
                      const uint8_t *reveal32, const uint8_t *proof64,
                      uint8_t *shared_out32 /* may be NULL */, uint8_t *verdict_out /* n_pairs */);
+/* Threshold decryption by a committee: points combined under ONE set of scalars shared by every item of the batch.  A small decryptor
+ * committee holds a Shamir-shared ElGamal key sk (rofl_shamir_share / rofl_feldman_commit deal it), clients encapsulate per-round secrets to
+ * PK = sk B (rofl_dh_public_keys / rofl_dh_shared under an ephemeral key: the ciphertext point C is the ephemeral public key), a member
+ * answers with the partial decryption D_j = s_j C and its proof (rofl_dleq_prove with the share key as own key; rofl_dleq_verify checks it
+ * against the member's public share key), and the server interpolates in the exponent: sk C = sum_j lambda_j D_j.
+ *   rofl_combine_points: out32[i] = encode(sum_j a_j decode(P[i][j])), n_terms scalars a_j for ALL n_items items; a scalar is 32 bytes,
+ *     reduced mod l if it is not canonical; the points are item-major.  The identity is a valid term.
+ *   rofl_threshold_combine: the same with a_j = lambda_j = prod_{m != j} x_m / (x_m - x_j), the weights of rofl_shamir_reconstruct at the
+ *     points xs.  With committee_pk32 and ct32 (the ciphertext point of every item) shared_out32[i] receives
+ *     SHAKE256("rofl-zk/dh/v1\0\0\0" || out32[i] || lo || hi)[0 .. 32), lo <= hi the pair (ct32[i], committee_pk32) as byte strings: exactly
+ *     the bytes rofl_dh_shared gave the encrypting client.  out32 may be NULL when shared_out32 is given.
+ *   status byte per item: 0 = combined (a sum that is the identity gives the identity encoding, 32 zero bytes; all-zero scalars give it for
+ *     every item); 2 = a term of the item is not a canonical Ristretto encoding: 32 zero bytes in both outputs, its neighbours unaffected.
+ *   A wrong partial decryption gives ANOTHER point and no error, as a wrong share does in rofl_shamir_reconstruct: rofl_dleq_verify names
+ *   it first.
+ * Host pointers only.  Both return 11 before the device is touched for a null pointer (except committee_pk32, ct32 and one of out32 /
+ * shared_out32), n_terms = 0 with items, n_terms above 65536, n_items above 2^20, n_items x n_terms above 2^24, an evaluation point that is
+ * zero or repeated (the text names the positions), and, when shared_out32 is asked for, a committee key or a ciphertext point that is not a
+ * canonical encoding or is the identity (the text names the index).  n_items = 0 returns 0 and touches no device.
+ * The items are walked in groups of at most 2^21 points (64 MiB staged, 192 MiB decoded), one lane, one upload and one download per
+ * group; a group launches k_shamir_weights (threshold), k_comb_schedule, k_comb_decode, k_comb_accumulate and, with more than 8 slices,
+ * k_comb_finish: the shared scalars are recoded and every window sorted once, every encoding is decoded once, and a lane per (item, slice)
+ * runs a bucket-method MSM that holds no buckets.  Window width and slice count are functions of the shape alone and no
+ * output byte depends on them.  A call below 160 points runs on the host twin (the same bytes).  The scalars, the combined points, the
+ * shared secrets and the partial sums -- pinned staging and device workspace -- are overwritten with zeros before the call returns or
+ * unwinds.  The `devices` option does not apply.
+ * What is NOT given: key generation without a dealer, proactive resharing, the transport, and constant time. */
+int rofl_combine_points(size_t n_items, size_t n_terms,
+                        const uint8_t *scalars32 /* n_terms x 32, ONE set for all items */,
+                        const uint8_t *points32 /* n_items x n_terms x 32, item-major */,
+                        uint8_t *out32 /* n_items x 32 */, uint8_t *status_out /* n_items */);
+int rofl_threshold_combine(size_t n_items, size_t n_shares, const uint32_t *xs /* n_shares, one set for all items */,
+                           const uint8_t *partials32 /* n_items x n_shares x 32, item-major */,
+                           const uint8_t *committee_pk32 /* 32 bytes, may be NULL */,
+                           const uint8_t *ct32 /* n_items x 32, needed with committee_pk32 */,
+                           uint8_t *out32 /* n_items x 32, may be NULL when shared_out32 is given */,
+                           uint8_t *shared_out32 /* n_items x 32, may be NULL */, uint8_t *status_out /* n_items */);
 /* Merkle trees: a commitment to a list of n byte strings -- a round's broadcast -- behind one 32-byte root, with single entries proved and
  * checked by a path of depth(n) <= 20 hashes.  A client signs the root instead of the whole list, checks the entries it holds against what
  * everybody signed, and hands a judge one entry and its path instead of the list.  Every label is exactly 16 bytes:

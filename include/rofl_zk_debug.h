@@ -298,6 +298,23 @@ int rofl_dbg_host_dleq_prove(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_
 int rofl_dbg_host_dleq_verify(size_t n_own, const uint8_t *own_pk32, size_t n_peer, const uint8_t *peer_pk32, size_t n_pairs,
                               const rofl_dh_pair_t *pairs, const uint8_t *ctx32, const uint8_t *reveal32, const uint8_t *proof64,
                               uint8_t *shared_out32, uint8_t *verdict_out);
+/* rofl_combine_points / rofl_threshold_combine on the host's 51-bit point arithmetic, one thread, no GPU, whatever their size: the same
+ * parameters, the same checks (11) and the same bytes.  What the host tests pin the definition with, and a baseline of
+ * profiles/threshold_combine.json.
+ * rofl_dbg_*_split: the two calls forced onto the device with window width c = window_bits (0 or 2 .. 10) and S = slices (0 or more; clamped
+ * to the terms and to 1024), 0 = chosen from the shape as the public calls choose; no output byte depends on either.  chosen2 (may be NULL)
+ * receives c and S as used (of the last group of items), kernel_ms3 (may be NULL) the time between events on the lane's stream of
+ * schedule (with the weights) | decode | accumulate and finish, summed over the groups. */
+int rofl_dbg_host_combine_points(size_t n_items, size_t n_terms, const uint8_t *scalars32, const uint8_t *points32, uint8_t *out32,
+                                 uint8_t *status_out);
+int rofl_dbg_host_threshold_combine(size_t n_items, size_t n_shares, const uint32_t *xs, const uint8_t *partials32,
+                                    const uint8_t *committee_pk32, const uint8_t *ct32, uint8_t *out32, uint8_t *shared_out32,
+                                    uint8_t *status_out);
+int rofl_dbg_combine_points_split(size_t n_items, size_t n_terms, const uint8_t *scalars32, const uint8_t *points32, uint8_t *out32,
+                                  uint8_t *status_out, uint32_t window_bits, uint32_t slices, uint32_t *chosen2, double *kernel_ms3);
+int rofl_dbg_threshold_combine_split(size_t n_items, size_t n_shares, const uint32_t *xs, const uint8_t *partials32,
+                                     const uint8_t *committee_pk32, const uint8_t *ct32, uint8_t *out32, uint8_t *shared_out32,
+                                     uint8_t *status_out, uint32_t window_bits, uint32_t slices);
 /* rofl_merkle_build / rofl_merkle_verify on the host's sponge, one thread, no GPU: the same parameters, the same checks (11) and the same
  * bytes and verdicts.  What the host tests pin the definition with, and the baseline of profiles/merkle.json.
  * rofl_dbg_merkle_tile_leaves: the number of nodes a workgroup of k_mt_tile owns, so that tests can place n around it; no output byte

@@ -242,6 +242,14 @@ extern "C" {
     pub fn rofl_dleq_verify(n_own: usize, own_pk32: *const u8, n_peer: usize, peer_pk32: *const u8,
         n_pairs: usize, pairs: *const RoflDhPair, ctx32: *const u8, reveal32: *const u8, proof64: *const u8,
         shared_out32: *mut u8, verdict_out: *mut u8) -> c_int;
+    /// out32[i] = encode(sum_j a_j decode(P[i][j])): n_terms scalars shared by ALL n_items items, the points item-major; status 2 = a term
+    /// of the item is not a canonical encoding (32 zero bytes, the neighbours unaffected)
+    pub fn rofl_combine_points(n_items: usize, n_terms: usize, scalars32: *const u8, points32: *const u8, out32: *mut u8,
+        status_out: *mut u8) -> c_int;
+    /// the same with the Lagrange weights of the points xs as scalars: the committee's partial decryptions of every ciphertext combined;
+    /// with committee_pk32 and ct32, shared_out32[i] is the rofl_dh_shared secret of the encrypting client (out32 may then be null)
+    pub fn rofl_threshold_combine(n_items: usize, n_shares: usize, xs: *const u32, partials32: *const u8, committee_pk32: *const u8,
+        ct32: *const u8, out32: *mut u8, shared_out32: *mut u8, status_out: *mut u8) -> c_int;
     /// a Merkle tree over n messages (msg_off null: msg_bytes is n x 32 leaf digests): the root, the leaf digests (leaves_out32 may be null)
     /// and the paths of the leaves path_idx names, n_paths x depth(n) x 32 bytes, depth(n) = bit_length(n - 1)
     pub fn rofl_merkle_build(n: usize, msg_bytes: *const u8, msg_off: *const u64, root_out32: *mut u8, leaves_out32: *mut u8,

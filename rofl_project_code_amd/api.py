@@ -1859,6 +1859,37 @@ class secret_sharing:
                 src[...] = 0
         return out
 
+    @staticmethod
+    def _combine(fn, xs, points, committee_pk=None, ct=None, want_point=True):
+        """rofl_threshold_combine (or an entry of its shape) -> (points or None, shared secrets or None, status)"""
+        n_shares = int(np.asarray(xs).shape[0]) if np.asarray(xs).ndim == 1 else -1
+        x = _xs32(xs, n_shares)
+        pt = np.ascontiguousarray(np.asarray(points, dtype=np.uint8))
+        if pt.ndim != 3 or pt.shape[1:] != (n_shares, 32):
+            raise ValueError("points are uint8[n_items, len(xs), 32]")
+        n = pt.shape[0]
+        if n and n_shares == 0:
+            raise ValueError("items without shares")
+        pk = c = shared = None
+        if committee_pk is not None:
+            pk, c = _keys32(committee_pk, "the committee key"), _keys32(ct, "a ciphertext point")
+            if pk.shape[0] != 1 or c.shape[0] != n:
+                raise ValueError("one committee key and one ciphertext point per item")
+            shared = np.zeros((n, 32), dtype=np.uint8)
+        out, status = np.zeros((n, 32), dtype=np.uint8) if want_point else None, np.zeros(n, dtype=np.uint8)
+        _check(fn(_sz(n), _sz(n_shares), _ptr(x), _ptr(pt), None if pk is None else _ptr(pk), None if c is None else _ptr(c),
+                  None if out is None else _ptr(out), None if shared is None else _ptr(shared), _ptr(status)))
+        return out, shared, status
+
+    @staticmethod
+    def reconstruct_points(xs, points):
+        """Interpolation in the exponent (rofl_threshold_combine): points uint8[n_items, len(xs), 32] hold [i, j] = f_i(xs[j]) * Q_i for
+        polynomials f_i and any points Q_i; -> (uint8[n_items, 32], uint8[n_items]) with [i] = f_i(0) * Q_i under the weights of
+        reconstruct(), one set for all items.  status 2 = a point of the item is not a canonical Ristretto encoding (32 zero bytes).  ALL
+        points handed in are interpolated and nothing is checked: a wrong point gives another result without an error."""
+        out, _, status = secret_sharing._combine(lib().rofl_threshold_combine, xs, points)
+        return out, status
+
     # ---- the authenticated broadcast of the commitments: what a round signs (signatures.sign / verify) ----
     @staticmethod
     def commitment_message(round_no, dealer, kind, commitments):
@@ -2222,6 +2253,81 @@ class secret_sharing:
                     a[...] = 0
 
 
+def _ctx_rows(ctx, n):
+    """contexts as uint8[n, 32]: one 32-byte context for all n, or one per row"""
+    cx = _keys32(ctx, "a context")
+    if cx.shape[0] == 1 and n != 1:
+        cx = np.ascontiguousarray(np.broadcast_to(cx, (n, 32)))
+    if cx.shape[0] != n:
+        raise ValueError("one context, or one per ciphertext")
+    return cx
+
+
+class threshold:
+    """Threshold decryption by a committee (rofl_threshold_combine), for protocols that share per-round secrets with a small decryptor
+    committee once instead of with every client every round.  The committee holds a Shamir-shared key: secret_sharing.share deals sk,
+    secret_sharing.commit publishes PK = sk * B as commitment 0, and member j's public share key is s_j * B.  A client encapsulates to PK
+    with an ephemeral key (the ciphertext point is its public key); a member answers with the partial decryption s_j * C and a DLEQ proof;
+    the server combines t of them in the exponent, sk * C = sum_j lambda_j * (s_j * C), and derives the very bytes the client derived.
+    Every method but combine() and check_member_keys() is a composition of key_agreement and dleq calls.  A wrong partial decryption gives
+    ANOTHER key and no error from combine(): verify_partials() names it first.  What this does NOT give: key generation without a dealer,
+    proactive resharing, the transport, and constant time."""
+
+    @staticmethod
+    def encapsulate(committee_pk, eph_keys):
+        """-> (ct uint8[n, 32], shared uint8[n, 32]): ciphertext point i is the public key of the ephemeral secret key eph_keys[i], shared[i]
+        its key_agreement secret with the committee key.  An ephemeral key serves one ciphertext."""
+        pk = _keys32(committee_pk, "the committee key")
+        if pk.shape[0] != 1:
+            raise ValueError("one committee key")
+        shared, status, ct = key_agreement.shared_secrets(eph_keys, pk, with_public=True)
+        if status.any():
+            raise ValueError("the committee key is not a canonical Ristretto encoding or is the identity")
+        return ct, shared
+
+    @staticmethod
+    def partial_decrypt(share_key, ct, ctx):
+        """A member's answers for the ciphertext points ct uint8[n, 32] under its share key -> (partials uint8[n, 32], proofs uint8[n, 64],
+        status uint8[n]) as dleq.prove gives them: partial i = share_key * ct[i] with the proof that it was made with the key behind the
+        member's public share key, bound to ctx (32 bytes for all, or one per ciphertext)."""
+        c = _keys32(ct, "a ciphertext point")
+        return dleq.prove(_keys32(share_key, "a share key"), c, _ctx_rows(ctx, c.shape[0]))
+
+    @staticmethod
+    def verify_partials(member_pk, ct, ctx, partials, proofs):
+        """-> verdicts uint8[n] of dleq.verify for one member's answers: 0 = partial i is member_key * ct[i], 1 = it is not, 2 = malformed."""
+        c = _keys32(ct, "a ciphertext point")
+        verdicts, shared = dleq.verify(_keys32(member_pk, "a public share key"), c, _ctx_rows(ctx, c.shape[0]), partials, proofs)
+        shared[...] = 0
+        return verdicts
+
+    @staticmethod
+    def combine(committee_pk, xs, ct, partials, _fn=None):
+        """The shared secrets of the ciphertext points ct uint8[n, 32] from partials uint8[n, len(xs), 32], [i, j] the answer of the member
+        at the point xs[j] for ciphertext i -> (shared uint8[n, 32], status uint8[n]): shared[i] is what encapsulate() returned for
+        ciphertext i.  status 2 = a partial of the item is not a canonical Ristretto encoding (32 zero bytes).  Nothing is verified here: a
+        wrong partial gives a different key and no error -- run verify_partials() first.  The secrets open what the clients sealed: zero
+        them when done."""
+        _, shared, status = secret_sharing._combine(_fn or lib().rofl_threshold_combine, xs, partials, committee_pk, ct, want_point=False)
+        return shared, status
+
+    @staticmethod
+    def check_member_keys(committee_pk, xs, member_pks, threshold):
+        """True iff the public share keys member_pks[j] = s_j * B at the points xs lie on ONE polynomial of degree threshold - 1 whose
+        value at 0 is the committee key: the first `threshold` keys must combine to it, and so must every further key together with the
+        first threshold - 1 (one rofl_threshold_combine of one item each)."""
+        pk, keys = _keys32(committee_pk, "the committee key"), _keys32(member_pks, "a public share key")
+        x, t = np.asarray(xs), int(threshold)
+        if pk.shape[0] != 1 or x.ndim != 1 or keys.shape[0] != x.shape[0] or not 1 <= t <= x.shape[0]:
+            raise ValueError("one committee key, one point per member key, and a threshold in [1, members]")
+        for k in range(t - 1, x.shape[0]):
+            sel = list(range(t - 1)) + [k]
+            out, status = secret_sharing.reconstruct_points(x[sel], keys[sel][None])
+            if status[0] or out[0].tobytes() != pk[0].tobytes():
+                return False
+        return True
+
+
 class pedersen_ops:
     @staticmethod
     def commit_vec(scalars, blindings):
@@ -2260,6 +2366,20 @@ class pedersen_ops:
         out = np.zeros(32, dtype=np.uint8)
         _check(lib().rofl_sum_points(_ptr(p), _sz(p.shape[0]), _sz(32), _ptr(out)))
         return out
+
+    @staticmethod
+    def combine_points(scalars, points, _fn=None):
+        """out[i] = sum_j scalars[j] * points[i, j] (rofl_combine_points): ONE set of scalars uint8[n_terms, 32] (reduced mod l) for all
+        items, points uint8[n_items, n_terms, 32].  -> (uint8[n_items, 32], uint8[n_items]); status 2 = a term of the item is not a
+        canonical Ristretto encoding, and its 32 bytes are zero; the identity is a valid term and a valid sum.  Not constant-time."""
+        sc, pt = _keys32(scalars, "a scalar"), np.ascontiguousarray(np.asarray(points, dtype=np.uint8))
+        n_terms = sc.shape[0]
+        if pt.ndim != 3 or pt.shape[1:] != (n_terms, 32):
+            raise ValueError("points are uint8[n_items, len(scalars), 32]")
+        n = pt.shape[0]
+        out, status = np.zeros((n, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        _check((_fn or lib().rofl_combine_points)(_sz(n), _sz(n_terms), _ptr(sc), _ptr(pt), _ptr(out), _ptr(status)))
+        return out, status
 
     @staticmethod
     def rnd_scalar_vec(length):

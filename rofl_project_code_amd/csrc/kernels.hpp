@@ -4147,6 +4147,179 @@ __global__ void __launch_bounds__(64) k_dbg_var_mul_sum(u32 n, const sc *__restr
     if (i < n) dbg_var_mul_item<false>(i, k1, p1, k2, p2, out);
 }
 #endif
+// ================================================================ threshold decryption (rofl_combine_points / rofl_threshold_combine)
+// out[i] = encode(sum_j a_j decode(P[i][j])): a batched multi-scalar multiplication whose n_terms scalars are THE SAME for every item (the
+// Lagrange weights of a decryptor committee, or any other shared set).  Because the scalars are shared, so is everything a bucket method
+// derives from them: the signed radix-2^c digits and, per window, the order of the terms by |digit|.  k_comb_schedule builds that order
+// once; every lane of k_comb_accumulate then walks the same list, so every branch it takes -- the sign included -- is uniform across the
+// wave, and the bucket array of the classic method collapses into two register-resident points:
+//   for a window, from the largest digit value down:  run += +-P[i][j] for every term j of that value;  total += run after every value
+// (the running-sum bucket reduction, sum_v v * bucket_v, with no bucket ever stored).  Windows are joined by Horner's rule, c doublings of
+// `total` between them from the top window down.
+// Digits: with the bias K = sum_w 2^(c-1) 2^(c w) added to the scalar once (comb_k), digit w is ((k + K) >> c w & (2^c - 1)) - 2^(c-1),
+// in [-2^(c-1), 2^(c-1)): no carry runs from window to window, so a (term, window) digit is read off on its own.  W = ceil(253 / c) + 1
+// windows; the last one holds the carry out of the top (k < l < 2^253).
+// The op list of a (slice, window), `stride` words each: [0] = length, then from the largest occupied digit value down the terms of a value
+// (index within the slice | COMB_NEG for a negative digit) followed by ONE mark COMB_MARK | r, r = the distance to the next occupied value
+// below (or to 0): `total += run` r times.  Terms with a zero digit do not appear, digit values above the largest occupied one cost
+// nothing, and a window without terms has length 0.
+// Slices: the term list is cut into S contiguous slices (comb_slice), each with op lists of its own; a lane serves one (item, slice), a WAVE
+// one slice of 64 items (threadIdx.y, at most COMB_MAX_SB slices in a block).  The partial sums of an item meet in LDS and are added by a
+// tree of complete point additions; wave 0 finishes.  If S > COMB_MAX_SB, gridDim.y > 1 and every block stores its partial sum instead:
+// k_comb_finish, a second small launch, adds them and finishes.
+// Nothing here is constant-time.  Vector stores only.
+#define COMB_MARK 0x40000000u
+#define COMB_NEG 0x80000000u
+#define COMB_IDX 0x00ffffffu
+#define COMB_MAX_SB 8
+struct comb_k { u32 v[9]; };      // a scalar plus the bias, below 2^(c W) <= 2^273
+HD u32 comb_windows(u32 c) { return (253 + c - 1) / c + 1; }
+HD void comb_slice(u32 n_terms, u32 S, u32 s, u32 &lo, u32 &len) {      // the first n_terms % S slices hold one term more
+    const u32 base = n_terms / S, rem = n_terms % S;
+    lo = s * base + (s < rem ? s : rem); len = base + (s < rem ? 1u : 0u);
+}
+HD comb_k comb_add_bias(const sc &k, const comb_k &K) {
+    comb_k r; u64 carry = 0;
+    for (int q = 0; q < 9; q++) { const u64 t = (u64)(q < 8 ? k.v[q] : 0u) + K.v[q] + carry; r.v[q] = (u32)t; carry = t >> 32; }
+    return r;
+}
+HD int comb_digit(const comb_k &b, u32 c, u32 w) {
+    const u32 pos = c * w, q = pos >> 5, sh = pos & 31;
+    u32 v = b.v[q] >> sh;
+    if (sh && q + 1 < 9) v |= b.v[q + 1] << (32 - sh);
+    return (int)(v & ((1u << c) - 1)) - (int)(1u << (c - 1));
+}
+#if ROFL_KG(3)
+// One block per (window blockIdx.x, slice blockIdx.y): a counting sort of the slice's terms by |digit| in LDS (at most 2^9 + 1 values), two
+// passes over the scalars with the marks placed by thread 0 in between.  mont: the scalars are k_shamir_weights' output, in Montgomery form
+// (sc_from_mont gives lambda_j canonical); otherwise 32 raw bytes each, reduced if not canonical.  The order of the terms WITHIN a digit
+// value is whatever the atomics give: the sum does not depend on it.
+__global__ void __launch_bounds__(TPB) k_comb_schedule(u32 n_terms, u32 S, u32 c, u32 stride, comb_k K, u32 mont, const sc *__restrict__ scalars, u32 *__restrict__ sched) {
+    __shared__ u32 hist[513], cur[513];
+    const u32 w = blockIdx.x, s = blockIdx.y, W = gridDim.x, half = 1u << (c - 1);
+    u32 lo, len;
+    comb_slice(n_terms, S, s, lo, len);
+    u32 *ops = sched + ((size_t)s * W + w) * stride;
+    for (u32 v = threadIdx.x; v <= half; v += TPB) hist[v] = 0;
+    __syncthreads();
+    for (u32 t = threadIdx.x; t < len; t += TPB) {
+        const sc k = mont ? sc_from_mont(load_sc(&scalars[lo + t])) : load_sc_reduced(&scalars[lo + t]);
+        const int d = comb_digit(comb_add_bias(k, K), c, w);
+        if (d) atomicAdd(&hist[d < 0 ? -d : d], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 pos = 0, prev = 0;
+        for (u32 v = half; v >= 1; v--) {
+            if (!hist[v]) continue;
+            if (prev) ops[1 + pos++] = COMB_MARK | (prev - v);
+            cur[v] = pos; pos += hist[v]; prev = v;
+        }
+        if (prev) ops[1 + pos++] = COMB_MARK | prev;
+        ops[0] = pos;      // <= 2 * (terms with a nonzero digit) <= stride - 1
+    }
+    __syncthreads();
+    for (u32 t = threadIdx.x; t < len; t += TPB) {
+        const sc k = mont ? sc_from_mont(load_sc(&scalars[lo + t])) : load_sc_reduced(&scalars[lo + t]);
+        const int d = comb_digit(comb_add_bias(k, K), c, w);
+        if (d) ops[1 + atomicAdd(&cur[d < 0 ? -d : d], 1u)] = t | (d < 0 ? COMB_NEG : 0u);
+    }
+}
+// Every encoding decoded ONCE into the workspace, as the affine niels triple gd_madd wants (a decoded Ristretto point has Z = 1: y + x,
+// y - x, 2 d x y straight from X, Y, T).  Layout: six planes of uint4 per term with the ITEM index fastest, pts[(j * 6 + q) * ld + i], so
+// with one lane per item a wave's load of term j is six contiguous kilobytes.  ld: the items rounded up to whole waves; the lanes past the
+// end store the identity, as does an encoding that is not canonical, which also raises bad[i] (zeroed before the launch; every writer
+// stores the same 1).  The identity is a valid term.  Thread = (term j, item i), blockIdx.x = j * (ld / 64) + i / 64.
+__global__ void __launch_bounds__(64) k_comb_decode(u32 n_items, u32 n_terms, u32 ld, const uint8_t *__restrict__ enc /* [n_items][n_terms][32] */, uint4 *__restrict__ pts,
+                                                    u32 *__restrict__ bad) {
+    const u32 bpt = ld / 64, j = blockIdx.x / bpt, i = (blockIdx.x - j * bpt) * 64 + threadIdx.x;
+    gd P = gd_identity();
+    if (i < n_items && !sg_decode(P, enc + ((size_t)i * n_terms + j) * 32)) bad[i] = 1u;
+    niels q;
+    q.ypx = fd_pack(fd_add(P.Y, P.X)); q.ymx = fd_pack(fd_sub(P.Y, P.X)); q.t2d = fd_pack(fd_mul(P.T, fd_d2()));
+    const uint4 *src = reinterpret_cast<const uint4 *>(&q);
+#pragma unroll
+    for (int p = 0; p < 6; p++) pts[((size_t)j * 6 + p) * ld + i] = src[p];
+}
+__device__ __forceinline__ nd comb_load_point(const uint4 *__restrict__ pts, size_t j, u32 ld, u32 i) {
+    niels q;
+    uint4 *d = reinterpret_cast<uint4 *>(&q);
+#pragma unroll
+    for (int p = 0; p < 6; p++) d[p] = pts[(j * 6 + p) * ld + i];
+    return nd_unpack(q);
+}
+// what the finishing lane of item i stores: status 2 and zeros for an item with a refused term; otherwise status 0, the 32-byte encoding
+// (out may be nullptr) and, where asked (shared != nullptr), the rofl_dh_shared secret of the pair (ciphertext point ct[i], committee key pk)
+__device__ __forceinline__ void comb_finish(u32 i, const gd &P, const u32 *__restrict__ bad, const uint8_t *__restrict__ pk, const uint8_t *__restrict__ ct,
+                                            uint8_t *__restrict__ out, uint8_t *__restrict__ shared, uint8_t *__restrict__ status) {
+    const bool refused = bad[i] != 0u;
+    status[i] = refused ? 2 : 0;
+    u64 E[4] = {0, 0, 0, 0};
+    if (!refused) sg_encode_words(E, P);
+    if (out) dleq_store_words(reinterpret_cast<uint4 *>(out + (size_t)32 * i), E);
+    if (!shared) return;
+    uint4 *so = reinterpret_cast<uint4 *>(shared + (size_t)32 * i);
+    if (refused) { so[0] = make_uint4(0, 0, 0, 0); so[1] = make_uint4(0, 0, 0, 0); return; }
+    u64 A[4], C[4];
+    dleq_load_words(A, pk); dleq_load_words(C, ct + (size_t)32 * i);
+    dh_secret_store(so, E, C, A);
+}
+// blockDim = (64 items, SB slices), SB a power of two <= COMB_MAX_SB; grid = (ld / 64, ceil(S / SB)).  The op lists are read through
+// UNIFORM loads, not staged in LDS: a wave's slice index comes through readfirstlane, so list address, length and every op sit in scalar
+// registers -- the list costs no vector load and no barrier per window, a few hundred words shared by every block stay in the scalar
+// cache, and LDS is left to the tree below (SB / 2 x 64 packed points, 32 KiB at SB = 8).  The points come through coalesced 16-byte loads
+// (k_comb_decode's layout).  While no window has had a term, `total` is the identity and its doublings are skipped; inside a window there
+// is no `total += run` before the first term, because the list starts at the largest occupied digit value.  Both skips are uniform.
+// A refused term was decoded as the identity, so its lane walks like the others and the finishing lane reports it.
+__global__ void __launch_bounds__(64 * COMB_MAX_SB) k_comb_accumulate(u32 n_items, u32 n_terms, u32 S, u32 c, u32 W, u32 stride, const u32 *__restrict__ sched,
+                                                                      const uint4 *__restrict__ pts, u32 ld, const u32 *__restrict__ bad, ge *__restrict__ part /* [gridDim.y][ld] */,
+                                                                      const uint8_t *__restrict__ pk, const uint8_t *__restrict__ ct, uint8_t *__restrict__ out,
+                                                                      uint8_t *__restrict__ shared, uint8_t *__restrict__ status) {
+    __shared__ ge lds[COMB_MAX_SB / 2 * 64];
+    const u32 i = blockIdx.x * 64 + threadIdx.x;      // (< ld: the workspace is padded to whole waves)
+    const u32 sl = (u32)__builtin_amdgcn_readfirstlane((int)threadIdx.y), s = blockIdx.y * blockDim.y + sl;
+    gd total = gd_identity();
+    if (s < S) {
+        u32 lo, len;
+        comb_slice(n_terms, S, s, lo, len);
+        bool started = false;
+        for (u32 w = W; w-- > 0;) {
+            const u32 *ops = sched + ((size_t)s * W + w) * stride;
+            const u32 n_ops = (u32)__builtin_amdgcn_readfirstlane((int)ops[0]);
+            if (started) {
+                for (u32 q = 1; q < c; q++) total = gd_double_not(total);
+                total = gd_double(total);
+            }
+            if (!n_ops) continue;
+            started = true;
+            gd run = gd_identity();
+            for (u32 k = 0; k < n_ops; k++) {
+                const u32 op = (u32)__builtin_amdgcn_readfirstlane((int)ops[1 + k]);
+                if (op & COMB_MARK) { for (u32 r = op & COMB_IDX; r; r--) total = gd_add(total, run); }
+                else run = gd_madd(run, comb_load_point(pts, (size_t)lo + (op & COMB_IDX), ld, i), (op & COMB_NEG) != 0);
+            }
+        }
+    }
+    for (u32 h = blockDim.y >> 1; h; h >>= 1) {      // (every wave takes every barrier)
+        if (sl >= h && sl < 2 * h) lds[(sl - h) * 64 + threadIdx.x] = gd_pack(total);
+        __syncthreads();
+        if (sl < h) total = gd_add(total, gd_unpack(lds[sl * 64 + threadIdx.x]));
+        __syncthreads();
+    }
+    if (sl != 0) return;
+    if (gridDim.y > 1) store_gd(&part[(size_t)blockIdx.y * ld + i], total);
+    else if (i < n_items) comb_finish(i, total, bad, pk, ct, out, shared, status);
+}
+// the second launch of a call with more than COMB_MAX_SB slices: one thread per item adds the n_part partial sums and finishes
+__global__ void __launch_bounds__(64) k_comb_finish(u32 n_items, u32 n_part, u32 ld, const ge *__restrict__ part, const u32 *__restrict__ bad, const uint8_t *__restrict__ pk,
+                                                    const uint8_t *__restrict__ ct, uint8_t *__restrict__ out, uint8_t *__restrict__ shared, uint8_t *__restrict__ status) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    gd total = load_gd(&part[i]);
+    for (u32 g = 1; g < n_part; g++) total = gd_add(total, load_gd(&part[(size_t)g * ld + i]));
+    comb_finish(i, total, bad, pk, ct, out, shared, status);
+}
+#endif
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(TPB) k_sigma_finish_batch(int kind, u32 d, u32 fp_bits, u32 fp_frac, const SgClient *cl, DMerlin init, u32 *status /* [gridDim.y] */) {
     const SgClient &c = cl[blockIdx.y];

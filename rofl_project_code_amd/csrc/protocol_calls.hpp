@@ -256,6 +256,20 @@ int shamir_reconstruct_check(size_t n_secrets, size_t n_shares, const uint32_t *
     if (n_secrets * n_shares > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 shares in one call");
     return shamir_check_xs(n_shares, xs);
 }
+// lambda_j of the points xs in Montgomery form; N and D carry the same power of R (k_shamir_weights)
+void host_shamir_weights(size_t n_shares, const uint32_t *xs, std::vector<sc> &w) {
+    w.resize(n_shares);
+    for (size_t j = 0; j < n_shares; j++) {
+        sc N = sc_one_plain(), D = sc_one_plain();
+        for (size_t k = 0; k < n_shares; k++) {
+            if (k == j) continue;
+            const u32 xm = xs[k], xj = xs[j];
+            sc fd = sc_from_u64(xm > xj ? xm - xj : xj - xm); if (xm < xj) fd = sc_neg(fd);
+            N = sc_montmul(N, sc_from_u64(xm)); D = sc_montmul(D, fd);
+        }
+        w[j] = sc_montmul(N, h51::sc_invert_mont_fast(D));
+    }
+}
 }  // namespace
 extern "C" {
 // The lane's copies of the secrets, the coefficient seeds, the coefficients and the shares -- pinned staging and device workspace -- are
@@ -327,17 +341,8 @@ int rofl_dbg_host_shamir_reconstruct(size_t n_secrets, size_t n_shares, const ui
     bool done;
     if (int rc = shamir_reconstruct_check(n_secrets, n_shares, xs, shares32, secrets_out32, &done)) return rc;
     if (done) return ROFL_OK;
-    std::vector<sc> w(n_shares);      // lambda_j in Montgomery form; N and D carry the same power of R (k_shamir_weights)
-    for (size_t j = 0; j < n_shares; j++) {
-        sc N = sc_one_plain(), D = sc_one_plain();
-        for (size_t k = 0; k < n_shares; k++) {
-            if (k == j) continue;
-            const u32 xm = xs[k], xj = xs[j];
-            sc fd = sc_from_u64(xm > xj ? xm - xj : xj - xm); if (xm < xj) fd = sc_neg(fd);
-            N = sc_montmul(N, sc_from_u64(xm)); D = sc_montmul(D, fd);
-        }
-        w[j] = sc_montmul(N, h51::sc_invert_mont_fast(D));
-    }
+    std::vector<sc> w;
+    host_shamir_weights(n_shares, xs, w);
     for (size_t s = 0; s < n_secrets; s++) {
         sc acc = sc_zero();
         for (size_t j = 0; j < n_shares; j++) acc = sc_add(acc, sc_montmul(w[j], dh_key_scalar(shares32 + (s * n_shares + j) * 32)));
@@ -1086,6 +1091,234 @@ int rofl_dbg_var_mul2(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, cons
 }
 int rofl_dbg_var_mul_sum(size_t n, const uint8_t *k1_32, const uint8_t *p1_32, const uint8_t *k2_32, const uint8_t *p2_32, uint8_t *out32, double *kernel_ms) {
     return dbg_var_mul_device(false, n, k1_32, p1_32, k2_32, p2_32, out32, kernel_ms);
+}
+// ---- threshold decryption: points combined under ONE shared set of scalars (k_shamir_weights, k_comb_schedule, k_comb_decode, k_comb_accumulate / k_comb_finish) ----
+}  // extern "C"
+namespace {
+// The items of a call are walked in groups of at most kCombGroupPoints points: 64 MiB of encodings staged and 192 MiB of decoded workspace
+// at a time, whatever the call's size.
+constexpr size_t kCombGroupPoints = (size_t)1 << 21;
+constexpr size_t kCombSimds = 1024;      // 256 compute units x 4: what a call of few items is sliced to fill, one wave each
+constexpr size_t kCombSliceMin = 4;      // a slice keeps at least this many terms: below it the 253 doublings every slice repeats dominate
+constexpr u32 kCombForcedSlicesMax = 1024;
+// Below this many points (n_items x n_terms) a call runs on the host twin: one core walks the same op lists in less time than two staged
+// copies, three launches and a synchronisation take.  The first size of the 5-share sweep at which the device route wins: 32 items, 160
+// points, 1.24 ms against 2.36 ms (profiles/threshold_combine.json, "crossover_sweep").  The 40-share sweep crosses at
+// 320 points (2.2 ms against 3.1 ms; at 160 the host is 0.6 ms ahead): one constant in points serves both within that.  Not a knob.
+constexpr size_t kCombHostBelow = 160;
+// c in 2..10 minimising windows x (terms + digit values), the additions of one lane; a pure function of the slice length
+u32 comb_pick_window(size_t slice_len) {
+    u32 best = 2; size_t best_cost = ~(size_t)0;
+    for (u32 c = 2; c <= 10; c++) {
+        const size_t cost = (size_t)(comb_windows(c) - 1) * (slice_len + ((size_t)1 << (c - 1)));
+        if (cost < best_cost) { best_cost = cost; best = c; }
+    }
+    return best;
+}
+// S from the items of one launch: whole waves of items times S slices fill the chip once; clamped to slices of kCombSliceMin terms
+u32 comb_pick_slices(size_t n_items, size_t n_terms) {
+    const size_t waves = (n_items + 63) / 64;
+    return (u32)std::max<size_t>(1, std::min(kCombSimds / std::min(waves, kCombSimds), n_terms / kCombSliceMin));
+}
+comb_k comb_bias(u32 c) {
+    comb_k K; memset(&K, 0, sizeof K);
+    for (u32 w = 0; w < comb_windows(c); w++) { const u32 pos = c * w + c - 1; K.v[pos >> 5] |= 1u << (pos & 31); }
+    return K;
+}
+struct CombCall {
+    size_t n_items, n_terms;
+    const uint8_t *scalars32; const uint32_t *xs;      // one of the two: raw scalars, or evaluation points whose Lagrange weights are the scalars
+    const uint8_t *points32, *pk32, *ct32;
+    uint8_t *out32, *shared32, *status;
+    u32 force_c = 0, force_s = 0;                      // the debug entries: 0 = chosen from the shape
+    uint32_t *chosen = nullptr; double *kernel_ms = nullptr;      // (c, S) of the last group; schedule | decode | accumulate and finish, summed over the groups
+};
+// a key that keys a shared secret: canonical and not the identity
+bool comb_key_ok(const uint8_t *p32) { ge P; return ristretto_decode(P, p32) && !ge_is_identity_ristretto(P); }
+// every check of the two calls, shared with their host routes; *done: the call is empty and returns 0
+int comb_check(const CombCall &a, bool *done) {
+    *done = a.n_items == 0;
+    if (*done) return ROFL_OK;
+    if ((!a.scalars32 && !a.xs) || !a.points32 || !a.status || (!a.out32 && !a.shared32)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (a.shared32 && (!a.pk32 || !a.ct32)) return fail(ROFL_BAD_PARAM, "shared secrets need the committee key and the ciphertext points");
+    if (a.n_terms == 0) return fail(ROFL_BAD_PARAM, "items without terms");
+    if (a.n_terms > 65536) return fail(ROFL_BAD_PARAM, "more than 65536 terms of an item in one call");
+    if (a.n_items > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 items in one call");
+    if (a.n_items * a.n_terms > ((size_t)1 << 24)) return fail(ROFL_BAD_PARAM, "more than 2^24 points in one call");
+    if (a.force_c && (a.force_c < 2 || a.force_c > 10)) return fail(ROFL_BAD_PARAM, "window_bits is 0 or in [2, 10]");
+    if (a.xs) if (int rc = shamir_check_xs(a.n_terms, a.xs)) return rc;
+    if (a.shared32) {
+        if (!comb_key_ok(a.pk32)) return fail(ROFL_BAD_PARAM, "the committee key is not a canonical encoding or is the identity");
+        for (size_t i = 0; i < a.n_items; i++)
+            if (!comb_key_ok(a.ct32 + 32 * i)) { char buf[112]; snprintf(buf, sizeof buf, "ciphertext point %zu is not a canonical encoding or is the identity", i); return fail(ROFL_BAD_PARAM, buf); }
+    }
+    return ROFL_OK;
+}
+int comb_device(const CombCall &a) {
+    return guarded([&]() -> int {
+        size_t G = std::max<size_t>(1, kCombGroupPoints / a.n_terms);
+        if (G >= 64) G &= ~(size_t)63;
+        double ms_sum[3] = {0, 0, 0};
+        for (size_t i0 = 0; i0 < a.n_items; i0 += G) {
+            const size_t n = std::min(G, a.n_items - i0), ld = (n + 63) & ~(size_t)63, n_terms = a.n_terms;
+            const u32 S = a.force_s ? std::min<u32>({a.force_s, (u32)n_terms, kCombForcedSlicesMax}) : comb_pick_slices(n, n_terms);
+            const u32 c = a.force_c ? a.force_c : comb_pick_window((n_terms + S - 1) / S), W = comb_windows(c);
+            const u32 stride = 2 * (u32)((n_terms + S - 1) / S) + 2;
+            u32 SB = 1; while (SB < S && SB < COMB_MAX_SB) SB <<= 1;
+            const u32 NG = (S + SB - 1) / SB;
+            if (a.chosen) { a.chosen[0] = c; a.chosen[1] = S; }
+            StagedCall st; Ctx &C = st.C;
+            const InPart scal = st.in(a.scalars32, n_terms * 32, kSecret), xp = st.in(a.xs, n_terms * 4), pts_in = st.in(a.points32 + i0 * n_terms * 32, n * n_terms * 32),
+                         ct = st.in(a.shared32 ? a.ct32 + i0 * 32 : nullptr, n * 32), pk = st.in(a.shared32 ? a.pk32 : nullptr, 32);
+            const OutPart shared = st.out(a.shared32 ? a.shared32 + i0 * 32 : nullptr, a.shared32 ? n * 32 : 0, kSecret), out = st.out(a.out32 ? a.out32 + i0 * 32 : nullptr, n * 32, kSecret),
+                          status = st.out(a.status + i0, n);
+            // the workspace: [partial sums (secret) | weights | op lists | refusal flags | decoded points], each part 256-byte aligned
+            auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+            const size_t part_b = up(NG > 1 ? (size_t)NG * ld * sizeof(ge) : 0), w_b = up(a.xs ? n_terms * sizeof(sc) : 0), sched_b = up((size_t)S * W * stride * 4), bad_b = up(ld * 4);
+            uint8_t *ws = st.work<uint8_t>(part_b + w_b + sched_b + bad_b + n_terms * 6 * ld * sizeof(uint4));
+            st.ws_secret = part_b;
+            ge *part = reinterpret_cast<ge *>(ws); sc *wts = reinterpret_cast<sc *>(ws + part_b); u32 *sched = reinterpret_cast<u32 *>(ws + part_b + w_b);
+            u32 *bad = reinterpret_cast<u32 *>(ws + part_b + w_b + sched_b); uint4 *dpts = reinterpret_cast<uint4 *>(ws + part_b + w_b + sched_b + bad_b);
+            st.upload();
+            hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+            auto mark = [&](int k) { if (a.kernel_ms) { HIPCHK(hipEventCreate(&ev[k])); HIPCHK(hipEventRecord(ev[k], C.stream)); } };
+            const uint8_t *d_pk = a.shared32 ? st.dev<uint8_t>(pk) : nullptr, *d_ct = a.shared32 ? st.dev<uint8_t>(ct) : nullptr;
+            uint8_t *d_shared = a.shared32 ? st.dev<uint8_t>(shared) : nullptr;
+            mark(0);
+            if (a.xs) ROFL_LAUNCH(k_shamir_weights, grid1(n_terms), dim3(TPB), 0, C.stream, (u32)n_terms, st.dev<u32>(xp), wts);
+            ROFL_LAUNCH(k_comb_schedule, dim3(W, S), dim3(TPB), 0, C.stream, (u32)n_terms, S, c, stride, comb_bias(c), a.xs ? 1u : 0u, a.xs ? (const sc *)wts : st.dev<sc>(scal), sched);
+            mark(1);
+            HIPCHK(hipMemsetAsync(bad, 0, ld * 4, C.stream));
+            ROFL_LAUNCH(k_comb_decode, dim3((unsigned)(n_terms * (ld / 64))), dim3(64), 0, C.stream, (u32)n, (u32)n_terms, (u32)ld, st.dev<uint8_t>(pts_in), dpts, bad);
+            mark(2);
+            ROFL_LAUNCH(k_comb_accumulate, dim3((unsigned)(ld / 64), NG), dim3(64, SB), 0, C.stream, (u32)n, (u32)n_terms, S, c, W, stride, (const u32 *)sched, (const uint4 *)dpts, (u32)ld,
+                        (const u32 *)bad, part, d_pk, d_ct, st.dev<uint8_t>(out), d_shared, st.dev<uint8_t>(status));
+            if (NG > 1) ROFL_LAUNCH(k_comb_finish, per_item(n), dim3(64), 0, C.stream, (u32)n, NG, (u32)ld, (const ge *)part, (const u32 *)bad, d_pk, d_ct, st.dev<uint8_t>(out), d_shared,
+                                    st.dev<uint8_t>(status));
+            mark(3);
+            st.finish();
+            if (a.kernel_ms) for (int k = 0; k < 3; k++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1])); ms_sum[k] += ms; }
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        }
+        if (a.kernel_ms) for (int k = 0; k < 3; k++) a.kernel_ms[k] = ms_sum[k];
+        return ROFL_OK;
+    });
+}
+// the calls on the host's 51-bit point arithmetic, one thread, no GPU: the op lists of ONE slice built as k_comb_schedule builds them, then
+// walked per item as a lane of k_comb_accumulate walks them
+int comb_host(const CombCall &a) {
+    const size_t n_terms = a.n_terms;
+    const u32 c = a.force_c ? a.force_c : comb_pick_window(n_terms), W = comb_windows(c), half = 1u << (c - 1);
+    if (a.chosen) { a.chosen[0] = c; a.chosen[1] = 1; }
+    const comb_k K = comb_bias(c);
+    std::vector<sc> k(n_terms);
+    if (a.xs) { host_shamir_weights(n_terms, a.xs, k); for (sc &v : k) v = sc_from_mont(v); }
+    else for (size_t j = 0; j < n_terms; j++) k[j] = dh_key_scalar(a.scalars32 + 32 * j);
+    std::vector<std::vector<u32>> ops(W);
+    std::vector<std::vector<u32>> by_value(half + 1);
+    for (u32 w = 0; w < W; w++) {
+        for (auto &v : by_value) v.clear();
+        for (size_t j = 0; j < n_terms; j++) { const int d = comb_digit(comb_add_bias(k[j], K), c, w); if (d) by_value[d < 0 ? -d : d].push_back((u32)j | (d < 0 ? COMB_NEG : 0u)); }
+        u32 prev = 0;
+        for (u32 v = half; v >= 1; v--) {
+            if (by_value[v].empty()) continue;
+            if (prev) ops[w].push_back(COMB_MARK | (prev - v));
+            ops[w].insert(ops[w].end(), by_value[v].begin(), by_value[v].end()); prev = v;
+        }
+        if (prev) ops[w].push_back(COMB_MARK | prev);
+    }
+    dh_wipe(k.data(), k.size() * sizeof(sc));
+    std::vector<h51::ge5> P(n_terms);
+    for (size_t i = 0; i < a.n_items; i++) {
+        bool refused = false;
+        for (size_t j = 0; j < n_terms && !refused; j++) { ge Q; refused = !ristretto_decode(Q, a.points32 + (i * n_terms + j) * 32); if (!refused) P[j] = h51::from_ge(Q); }
+        a.status[i] = refused ? 2 : 0;
+        uint8_t E[32]; memset(E, 0, 32);
+        if (!refused) {
+            h51::ge5 total = h51::identity(); bool started = false;
+            for (u32 w = W; w-- > 0;) {
+                if (started) for (u32 q = 0; q < c; q++) total = h51::gdouble(total);
+                if (ops[w].empty()) continue;
+                started = true;
+                h51::ge5 run = h51::identity();
+                for (u32 op : ops[w]) {
+                    if (op & COMB_MARK) { for (u32 r = op & COMB_IDX; r; r--) total = h51::gadd(total, run); continue; }
+                    h51::ge5 q = P[op & COMB_IDX];
+                    if (op & COMB_NEG) { q.X = h51::neg(q.X); q.T = h51::neg(q.T); }
+                    run = h51::gadd(run, q);
+                }
+            }
+            h51::encode(E, total);
+            dh_wipe(&total, sizeof total);
+        }
+        if (a.out32) memcpy(a.out32 + 32 * i, E, 32);
+        if (a.shared32) { if (refused) memset(a.shared32 + 32 * i, 0, 32); else dh_host_secret(a.shared32 + 32 * i, E, a.ct32 + 32 * i, a.pk32); }
+        dh_wipe(E, sizeof E);
+    }
+    for (auto &o : ops) dh_wipe(o.data(), o.size() * 4);
+    return ROFL_OK;
+}
+// the public calls: the host twin below the crossover when every pointer is host memory, the device otherwise
+int comb_route(const CombCall &a) {
+    bool done;
+    if (int rc = comb_check(a, &done)) return rc;
+    if (done) return ROFL_OK;
+    if (a.n_items * a.n_terms < kCombHostBelow) {
+        const void *ptrs[] = {a.scalars32, a.xs, a.points32, a.pk32, a.ct32, a.out32, a.shared32, a.status};
+        bool all_host = true;
+        for (const void *p : ptrs) all_host &= !p || !is_device_ptr(p);
+        if (all_host) return comb_host(a);
+    }
+    return comb_device(a);
+}
+}  // namespace
+extern "C" {
+// The lane's copies of the scalars, the combined points, the shared secrets and the partial sums -- pinned staging and device workspace --
+// are overwritten with zeros before the call returns or unwinds; the decoded terms and the op lists are functions of public inputs.
+int rofl_combine_points(size_t n_items, size_t n_terms, const uint8_t *scalars32, const uint8_t *points32, uint8_t *out32, uint8_t *status_out) {
+    CombCall a{n_items, n_terms, scalars32, nullptr, points32, nullptr, nullptr, out32, nullptr, status_out};
+    if (n_items && (!scalars32 || !out32)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return comb_route(a);
+}
+int rofl_threshold_combine(size_t n_items, size_t n_shares, const uint32_t *xs, const uint8_t *partials32, const uint8_t *committee_pk32, const uint8_t *ct32, uint8_t *out32,
+                           uint8_t *shared_out32, uint8_t *status_out) {
+    CombCall a{n_items, n_shares, nullptr, xs, partials32, committee_pk32, ct32, out32, shared_out32, status_out};
+    if (n_items && !xs) return fail(ROFL_BAD_PARAM, "bad parameter");
+    return comb_route(a);
+}
+// the two calls forced onto the device with c = window_bits and S = slices (0 = chosen from the shape; slices is clamped to the terms and to
+// 1024).  chosen2 (may be NULL): c and S as used; kernel_ms3 (may be NULL): schedule | decode | accumulate and finish between events
+int rofl_dbg_combine_points_split(size_t n_items, size_t n_terms, const uint8_t *scalars32, const uint8_t *points32, uint8_t *out32, uint8_t *status_out, uint32_t window_bits,
+                                  uint32_t slices, uint32_t *chosen2, double *kernel_ms3) {
+    CombCall a{n_items, n_terms, scalars32, nullptr, points32, nullptr, nullptr, out32, nullptr, status_out, window_bits, slices, chosen2, kernel_ms3};
+    if (n_items && (!scalars32 || !out32)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    bool done;
+    if (int rc = comb_check(a, &done)) return rc;
+    return done ? ROFL_OK : comb_device(a);
+}
+int rofl_dbg_threshold_combine_split(size_t n_items, size_t n_shares, const uint32_t *xs, const uint8_t *partials32, const uint8_t *committee_pk32, const uint8_t *ct32, uint8_t *out32,
+                                     uint8_t *shared_out32, uint8_t *status_out, uint32_t window_bits, uint32_t slices) {
+    CombCall a{n_items, n_shares, nullptr, xs, partials32, committee_pk32, ct32, out32, shared_out32, status_out, window_bits, slices};
+    if (n_items && !xs) return fail(ROFL_BAD_PARAM, "bad parameter");
+    bool done;
+    if (int rc = comb_check(a, &done)) return rc;
+    return done ? ROFL_OK : comb_device(a);
+}
+// the two calls on the host twin, whatever their size: the same parameters, the same checks, the same bytes
+int rofl_dbg_host_combine_points(size_t n_items, size_t n_terms, const uint8_t *scalars32, const uint8_t *points32, uint8_t *out32, uint8_t *status_out) {
+    CombCall a{n_items, n_terms, scalars32, nullptr, points32, nullptr, nullptr, out32, nullptr, status_out};
+    if (n_items && (!scalars32 || !out32)) return fail(ROFL_BAD_PARAM, "bad parameter");
+    bool done;
+    if (int rc = comb_check(a, &done)) return rc;
+    return done ? ROFL_OK : comb_host(a);
+}
+int rofl_dbg_host_threshold_combine(size_t n_items, size_t n_shares, const uint32_t *xs, const uint8_t *partials32, const uint8_t *committee_pk32, const uint8_t *ct32, uint8_t *out32,
+                                    uint8_t *shared_out32, uint8_t *status_out) {
+    CombCall a{n_items, n_shares, nullptr, xs, partials32, committee_pk32, ct32, out32, shared_out32, status_out};
+    if (n_items && !xs) return fail(ROFL_BAD_PARAM, "bad parameter");
+    bool done;
+    if (int rc = comb_check(a, &done)) return rc;
+    return done ? ROFL_OK : comb_host(a);
 }
 // ---- Merkle trees: a round's broadcast behind one root, single entries proved by a path (k_mt_leaves, k_mt_tile, k_mt_paths / k_mt_climb) ----
 }  // extern "C"

@@ -638,6 +638,39 @@ int rofl_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32 /* may b
                   size_t n, const rofl_sig_ref_t *refs /* NULL: (i, i) */, uint8_t *sig_out64 /* n x 64 */);
 int rofl_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off /* n_msgs + 1 */,
                     size_t n, const rofl_sig_ref_t *refs /* NULL: (i, i) */, const uint8_t *sig64 /* n x 64 */, uint8_t *verdict_out /* n */);
+/* Standard signatures: Ed25519 bit for bit as RFC 8032 section 5.1 defines it (no context, no prehash), a second scheme beside rofl_sig_*.
+ * It is what Android Keystore, CryptoKit, a YubiKey, a TPM or libsodium's crypto_sign produce and check, so a client's signing key -- the
+ * one key that never needs to leave its hardware -- can stay there.  Same curve, same base point, another point encoding and SHA-512.
+ *   key: a 32-byte seed.  h = SHA-512(seed); a = int_le(h[0 .. 32)) with bits 0, 1, 2 and 255 cleared and bit 254 set; prefix = h[32 .. 64);
+ *     the public key is A = enc(a B).  Every seed is a valid key: none is refused at sign;
+ *   signature: r = int_le(SHA-512(prefix || M)) mod l, R = enc(r B), k = int_le(SHA-512(R || A || M)) mod l, S = r + k a mod l; the
+ *     signature is R || le32(S), 64 bytes, deterministic;
+ *   enc / decoding: RFC 8032 5.1.2 / 5.1.3 -- y in 255 little-endian bits, the sign of x in bit 255.  Decoding refuses y >= p, a y with no
+ *     square root, and x = 0 with the sign bit set;
+ *   verdict byte per signature, a malformed input before a failing equation:
+ *     2 = the key does not decode by these rules, or has small order (8 A is the identity), or S >= l;
+ *     0 = enc(S B - k A) equals the 32 bytes R as they came, with k recomputed from those bytes, the key's bytes and M;
+ *     1 = anything else (an R that is no canonical encoding therefore simply gives 1).
+ *   This is the cofactorless equation compared by encoding, as ref10 and libsodium have it.  A refused key condemns its signatures, not the
+ *   call; one exact equation per signature and no random weights: the verdict names the signer.
+ * Messages, refs, pk_out32, host pointers and the argument checks (11 before the device is touched; n = 0 returns 0 and touches no device)
+ * are those of rofl_sig_sign / rofl_sig_verify, with two differences.  No key is refused at sign.  And a cap of its own: unlike the Schnorr
+ * scheme, which digests every message once, Ed25519 hashes the message once per SIGNATURE (the prefix differs per key, R || A per
+ * signature), so the sum over the signatures of their messages' lengths is at most 2^30 (11 otherwise).  A call that lets 10 000 keys sign
+ * one 1.3 MB view would hash 13 GB: sign the view round's root form (secret_sharing.sign_view_root, 60 bytes) instead.
+ * One lane: one upload, one download.  Launches: sign 4 (key expansion; nonce hash; R; challenge hash with S), verify 3 (key decoding;
+ * challenge hash; check), public keys 1.  Every key is expanded or decoded once, whatever the number of signatures under it.  Seeds,
+ * expanded keys, prefixes and nonces are secrets: the staging copies and the device workspace that held them are overwritten with zeros
+ * before the call returns or unwinds, and error texts never contain them.  The `devices` option does not apply.
+ * What this is NOT: an R of small order is not refused on its own (libsodium refuses it), it is judged by the equation.  There is no
+ * Ed25519ph and no Ed25519ctx.  Nothing is constant-time.  The nonce is deterministic: no randomness is needed and none is mixed in, so a
+ * fault injected into one of two runs on the same input can leak the key -- sign on hardware you trust. */
+int rofl_ed25519_public_keys(size_t n, const uint8_t *seed32, uint8_t *pk_out32);
+int rofl_ed25519_sign(size_t n_keys, const uint8_t *seed32, uint8_t *pk_out32 /* may be NULL */,
+                      size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off /* n_msgs + 1 */,
+                      size_t n, const rofl_sig_ref_t *refs /* NULL: (i, i) */, uint8_t *sig_out64 /* n x 64 */);
+int rofl_ed25519_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off /* n_msgs + 1 */,
+                        size_t n, const rofl_sig_ref_t *refs /* NULL: (i, i) */, const uint8_t *sig64 /* n x 64 */, uint8_t *verdict_out /* n */);
 /* Sealed shares: RFC 8439 ChaCha20-Poly1305 in batches, one record per pairwise key and one exact verdict per record.  It is the ENCRYPTION
  * of the share bundles that a relaying server carries between clients; how the bytes travel stays the deployment's business.
  *   record: exactly RFC 8439 section 2.8 -- a 256-bit key, a 96-bit nonce, a 32-bit block counter.  The one-time Poly1305 key is the first

@@ -261,6 +261,13 @@ int rofl_dbg_host_sig_sign(size_t n_keys, const uint8_t *sk32, uint8_t *pk_out32
                            const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs, uint8_t *sig_out64);
 int rofl_dbg_host_sig_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,
                              size_t n, const rofl_sig_ref_t *refs, const uint8_t *sig64, uint8_t *verdict_out);
+/* rofl_ed25519_public_keys / _sign / _verify on the host's 51-bit point arithmetic and the SHA-512 text the kernels compile, one thread, no
+ * GPU: the same parameters, the same checks (11) and the same bytes and verdicts.  What the host tests pin the definition with. */
+int rofl_dbg_host_ed25519_public_keys(size_t n, const uint8_t *seed32, uint8_t *pk_out32);
+int rofl_dbg_host_ed25519_sign(size_t n_keys, const uint8_t *seed32, uint8_t *pk_out32, size_t n_msgs, const uint8_t *msg_bytes,
+                               const uint64_t *msg_off, size_t n, const rofl_sig_ref_t *refs, uint8_t *sig_out64);
+int rofl_dbg_host_ed25519_verify(size_t n_keys, const uint8_t *pk32, size_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,
+                                 size_t n, const rofl_sig_ref_t *refs, const uint8_t *sig64, uint8_t *verdict_out);
 /* rofl_aead_seal / rofl_aead_open in plain C++ on one thread, no GPU: the same parameters, the same checks (11) and the same bytes.  What the
  * host tests pin the definition with, and the baseline of profiles/share_seal.json on a box without libsodium. */
 int rofl_dbg_host_aead_seal(size_t n_keys, const uint8_t *key32, const uint64_t *derive_round, size_t n, const uint32_t *key_idx,

@@ -224,6 +224,14 @@ extern "C" {
     /// verdict_out[i]: 0 valid, 1 not, 2 = the key is not a canonical encoding or is the identity, or s >= l
     pub fn rofl_sig_verify(n_keys: usize, pk32: *const u8, n_msgs: usize, msg_bytes: *const u8, msg_off: *const u64,
         n: usize, refs: *const RoflSigRef, sig64: *const u8, verdict_out: *mut u8) -> c_int;
+    /// RFC 8032 Ed25519 (no context, no prehash), the standard scheme beside rofl_sig_*: 32-byte seeds, the public keys a stock client has
+    pub fn rofl_ed25519_public_keys(n: usize, seed32: *const u8, pk_out32: *mut u8) -> c_int;
+    /// same shape as rofl_sig_sign; no seed is refused; the signatures' message lengths sum to at most 2^30
+    pub fn rofl_ed25519_sign(n_keys: usize, seed32: *const u8, pk_out32: *mut u8, n_msgs: usize, msg_bytes: *const u8, msg_off: *const u64,
+        n: usize, refs: *const RoflSigRef, sig_out64: *mut u8) -> c_int;
+    /// verdict_out[i]: 0 valid, 1 not, 2 = the key does not decode or has small order, or S >= l
+    pub fn rofl_ed25519_verify(n_keys: usize, pk32: *const u8, n_msgs: usize, msg_bytes: *const u8, msg_off: *const u64,
+        n: usize, refs: *const RoflSigRef, sig64: *const u8, verdict_out: *mut u8) -> c_int;
     /// RFC 8439 ChaCha20-Poly1305 on the share bundles a server relays: record i under key key_idx[i] (null = key i), nonce12 n x 12, AD and
     /// payload packed with n + 1 offsets; sealed_out holds CT || tag of record i at pt_off[i] + 16 i.  derive_round non-null: a row of key32 is
     /// a rofl_dh_shared output and the key is SHAKE256("rofl-zk/seal/v1\0" || row || u64le(round))[0 .. 32)

@@ -1461,6 +1461,62 @@ class signatures:
         return out
 
 
+class ed25519:
+    """Batched Ed25519 signatures bit for bit as RFC 8032 section 5.1 defines them, no context, no prehash (rofl_ed25519_public_keys / _sign /
+    _verify): the scheme a phone's key store, an HSM or libsodium's crypto_sign speaks, beside `signatures` and with its conventions.  A key
+    is a 32-byte seed, and every seed is valid: h = SHA-512(seed), a = clamp(h[0 .. 32)), prefix = h[32 .. 64), A = enc(a B);
+    r = SHA-512(prefix || M) mod l, R = enc(r B), k = SHA-512(R || A || M) mod l, S = r + k a mod l; the signature is R || S, 64 bytes.
+    The message is hashed once per SIGNATURE: the signatures' message lengths sum to at most 2^30 in one call.  Not constant-time;
+    deterministic nonces; an R of small order is not refused on its own; no Ed25519ph / Ed25519ctx."""
+
+    @staticmethod
+    def _with_seeds(seeds, call):
+        sk = _keys32(seeds, "a seed")
+        buf = (ctypes.c_ubyte * max(sk.shape[0] * 32, 1))()
+        try:
+            ctypes.memmove(buf, sk.ctypes.data, sk.shape[0] * 32)
+            _check(call(sk.shape[0], buf))
+        finally:
+            ctypes.memset(buf, 0, ctypes.sizeof(buf))
+
+    @staticmethod
+    def public_keys(seeds):
+        """-> uint8[n, 32], A = enc(a B) of every seed"""
+        pk = np.zeros((_keys32(seeds, "a seed").shape[0], 32), dtype=np.uint8)
+        ed25519._with_seeds(seeds, lambda n, buf: lib().rofl_ed25519_public_keys(_sz(n), buf, _ptr(pk)))
+        return pk
+
+    @staticmethod
+    def sign(seeds, messages, refs=None, with_public=False):
+        """Signatures of the seeds' keys on the messages (a list of bytes-likes), ONE call: refs = [(key, message), ...] indexes the two,
+        None = key i signs message i.  -> uint8[n, 64]; with_public=True appends the public keys uint8[n_keys, 32]."""
+        data, off = _pack_messages(messages)
+        n_keys, n_msgs = _keys32(seeds, "a seed").shape[0], off.shape[0] - 1
+        n, rarr = _sig_refs(refs, n_keys, n_msgs)
+        out = np.zeros((n, 64), dtype=np.uint8)
+        pk = np.zeros((n_keys, 32), dtype=np.uint8) if with_public else None
+        ed25519._with_seeds(seeds, lambda nk, buf: lib().rofl_ed25519_sign(_sz(nk), buf, _ptr(pk) if with_public else None, _sz(n_msgs), _ptr(data) if data.size else None,
+                                                                          _ptr(off), _sz(n), rarr, _ptr(out)))
+        if with_public and n == 0 and n_keys:      # (an empty call computes nothing: the keys come from their own entry)
+            pk = ed25519.public_keys(seeds)
+        return (out, pk) if with_public else out
+
+    @staticmethod
+    def verify(pks, messages, sigs, refs=None):
+        """-> uint8[n] verdicts of the signatures sigs uint8[n, 64], ONE call: 0 = valid, 1 = not, 2 = the key does not decode (RFC 8032
+        5.1.3) or has small order, or S >= l.  refs as in sign()."""
+        pk = _keys32(pks, "a public key")
+        data, off = _pack_messages(messages)
+        n_keys, n_msgs = pk.shape[0], off.shape[0] - 1
+        n, rarr = _sig_refs(refs, n_keys, n_msgs)
+        sg = np.ascontiguousarray(np.asarray(sigs, dtype=np.uint8))
+        if sg.size != n * 64 or (sg.ndim > 1 and sg.shape[-1] != 64):
+            raise ValueError("sigs are uint8[n, 64], one per ref")
+        out = np.zeros(n, dtype=np.uint8)
+        _check(lib().rofl_ed25519_verify(_sz(n_keys), _ptr(pk), _sz(n_msgs), _ptr(data) if data.size else None, _ptr(off), _sz(n), rarr, _ptr(sg), _ptr(out)))
+        return out
+
+
 def _leaf_input(messages, digests):
     """(n, bytes pointer or None, offsets pointer or None, the arrays kept alive) of a call's leaves: messages packed, or digests uint8[n, 32]"""
     if (messages is None) == (digests is None):
@@ -1891,6 +1947,8 @@ class secret_sharing:
         return out, status
 
     # ---- the authenticated broadcast of the commitments: what a round signs (signatures.sign / verify) ----
+    # Every helper below that signs or checks takes scheme=signatures: the class whose sign / verify it calls.  scheme=ed25519 runs the same
+    # round on RFC 8032 signatures (keys are then 32-byte seeds); the messages, the layouts and the verdict bytes are the same.
     @staticmethod
     def commitment_message(round_no, dealer, kind, commitments):
         """The bytes a dealer signs for one of its two commitment rows (kind 0 = its key's, 1 = its self-mask secret's):
@@ -1927,16 +1985,16 @@ class secret_sharing:
         return msgs, [(r, 2 * r + k) for r in range(len(dealers)) for k in (0, 1)]
 
     @staticmethod
-    def sign_commitments(sig_sks, round_no, dealers, key_commitments, self_commitments):
+    def sign_commitments(sig_sks, round_no, dealers, key_commitments, self_commitments, scheme=signatures):
         """Every hosted dealer signs its two commitment messages, ONE signatures.sign call: sig_sks[r] is the signing key of dealers[r],
         key_commitments[r] / self_commitments[r] its rows uint8[t, 32].  -> uint8[n, 2, 64], [r, 0] on the key row, [r, 1] on the self row."""
         msgs, refs = secret_sharing._commitment_messages(round_no, dealers, key_commitments, self_commitments)
         if _keys32(sig_sks, "a secret key").shape[0] != len(msgs) // 2:
             raise ValueError("one signing key per dealer")
-        return signatures.sign(sig_sks, msgs, refs).reshape(-1, 2, 64)
+        return scheme.sign(sig_sks, msgs, refs).reshape(-1, 2, 64)
 
     @staticmethod
-    def verify_commitment_signatures(sig_pks, round_no, dealers, key_commitments, self_commitments, sigs):
+    def verify_commitment_signatures(sig_pks, round_no, dealers, key_commitments, self_commitments, sigs, scheme=signatures):
         """The signatures sigs uint8[n, 2, 64] of sign_commitments under the dealers' public signing keys sig_pks[r], ONE signatures.verify
         call -> uint8[n, 2] verdicts."""
         msgs, refs = secret_sharing._commitment_messages(round_no, dealers, key_commitments, self_commitments)
@@ -1945,15 +2003,15 @@ class secret_sharing:
         sg = np.asarray(sigs, dtype=np.uint8)
         if sg.shape != (len(msgs) // 2, 2, 64):
             raise ValueError("sigs are uint8[n, 2, 64]")
-        return signatures.verify(sig_pks, msgs, sg.reshape(-1, 64), refs).reshape(-1, 2)
+        return scheme.verify(sig_pks, msgs, sg.reshape(-1, 64), refs).reshape(-1, 2)
 
     @staticmethod
-    def verify_views(sig_pks, view, view_sigs):
+    def verify_views(sig_pks, view, view_sigs, scheme=signatures):
         """n clients' signatures view_sigs uint8[n, 64] on ONE view message (view_message) under their public signing keys, ONE
         signatures.verify call with refs (i, 0) -> uint8[n].  A client whose verdict is nonzero saw something else than `view`, or its
         dealer equivocated: the verdict names it."""
         n = _keys32(sig_pks, "a public key").shape[0]
-        return signatures.verify(sig_pks, [bytes(view)], view_sigs, [(i, 0) for i in range(n)])
+        return scheme.verify(sig_pks, [bytes(view)], view_sigs, [(i, 0) for i in range(n)])
 
     # ---- the second view round: the same broadcast behind a Merkle root (merkle.build / verify), so that 60 bytes are signed whatever the number
     # of dealers, a client that holds only some dealers' entries checks them against what everybody signed, and two views that differ are
@@ -1991,21 +2049,21 @@ class secret_sharing:
         return b"rofl-zk/view/v2r" + struct.pack("<QI", int(round_no), int(count)) + r
 
     @staticmethod
-    def sign_view_root(sig_sks, round_no, count, roots):
+    def sign_view_root(sig_sks, round_no, count, roots, scheme=signatures):
         """Every hosted client signs the view_root_message of ITS root (roots uint8[n, 32]; clients may have been shown different things), ONE
         signatures.sign call -> uint8[n, 64]."""
         rt = _keys32(roots, "a root")
         if _keys32(sig_sks, "a secret key").shape[0] != rt.shape[0]:
             raise ValueError("one root per signing key")
-        return signatures.sign(sig_sks, [secret_sharing.view_root_message(round_no, count, r) for r in rt])
+        return scheme.sign(sig_sks, [secret_sharing.view_root_message(round_no, count, r) for r in rt])
 
     @staticmethod
-    def verify_view_roots(sig_pks, round_no, count, root, view_sigs):
+    def verify_view_roots(sig_pks, round_no, count, root, view_sigs, scheme=signatures):
         """n clients' signatures view_sigs uint8[n, 64] on the view_root_message of ONE root under their public signing keys, ONE
         signatures.verify call with refs (i, 0) -> uint8[n].  A client whose verdict is nonzero signed another root: it was shown something
         else, or its dealer equivocated; the verdict names it, as verify_views does."""
         n = _keys32(sig_pks, "a public key").shape[0]
-        return signatures.verify(sig_pks, [secret_sharing.view_root_message(round_no, count, root)], view_sigs, [(i, 0) for i in range(n)])
+        return scheme.verify(sig_pks, [secret_sharing.view_root_message(round_no, count, root)], view_sigs, [(i, 0) for i in range(n)])
 
     @staticmethod
     def verify_view_entries(round_no, root, count, positions, entries, paths):
@@ -2140,17 +2198,17 @@ class secret_sharing:
         return msgs, [(a, a * len(peer) + b) for a in range(len(own)) for b in range(len(peer))]
 
     @staticmethod
-    def sign_bundles(sig_sks, round_no, own_ids, peer_ids, records):
+    def sign_bundles(sig_sks, round_no, own_ids, peer_ids, records, scheme=signatures):
         """Every hosted dealer signs the records it sealed (seal_shares' output uint8[n_own, n_peer, 80]), ONE signatures.sign call:
         sig_sks[a] is the SIGNING key of dealer own_ids[a].  -> uint8[n_own, n_peer, 64].  The signature is what makes a record
         attributable: a record without a valid one is a missing record, not grounds for a complaint."""
         msgs, refs = secret_sharing._bundle_messages(round_no, own_ids, peer_ids, records)
         if _keys32(sig_sks, "a secret key").shape[0] != len(own_ids):
             raise ValueError("one signing key per own id")
-        return signatures.sign(sig_sks, msgs, refs).reshape(len(own_ids), len(peer_ids), 64)
+        return scheme.sign(sig_sks, msgs, refs).reshape(len(own_ids), len(peer_ids), 64)
 
     @staticmethod
-    def verify_bundle_signatures(sig_pks, round_no, own_ids, peer_ids, records, sigs):
+    def verify_bundle_signatures(sig_pks, round_no, own_ids, peer_ids, records, sigs, scheme=signatures):
         """The signatures sigs uint8[n_own, n_peer, 64] of sign_bundles under the senders' public signing keys sig_pks[a] (sender own_ids[a],
         recipient peer_ids[b]), ONE signatures.verify call -> uint8[n_own, n_peer] verdicts.  A recipient checks these on receipt."""
         msgs, refs = secret_sharing._bundle_messages(round_no, own_ids, peer_ids, records)
@@ -2159,7 +2217,7 @@ class secret_sharing:
         sg = np.asarray(sigs, dtype=np.uint8)
         if sg.shape != (len(own_ids), len(peer_ids), 64):
             raise ValueError("sigs are uint8[n_own, n_peer, 64]")
-        return signatures.verify(sig_pks, msgs, sg.reshape(-1, 64), refs).reshape(len(own_ids), len(peer_ids))
+        return scheme.verify(sig_pks, msgs, sg.reshape(-1, 64), refs).reshape(len(own_ids), len(peer_ids))
 
     @staticmethod
     def complaint_context(round_no, complainant, dealer):
@@ -2186,7 +2244,7 @@ class secret_sharing:
         return reveals, proofs
 
     @staticmethod
-    def judge_complaints(round_no, complaints, channel_pks, sig_pks, key_commitments, self_commitments):
+    def judge_complaints(round_no, complaints, channel_pks, sig_pks, key_commitments, self_commitments, scheme=signatures):
         """Rule on complaints = [(complainant, dealer, record, record_sig, reveal, proof), ...]: the 80-byte record the dealer sent, the
         dealer's signature on it (sign_bundles), and the complainant's reveal and proof (file_complaints).  channel_pks, sig_pks,
         key_commitments and self_commitments are indexed by client id (arrays or dicts); the commitments were signature-checked earlier.
@@ -2210,8 +2268,8 @@ class secret_sharing:
         if rec.shape != (n, 80):
             raise ValueError("a sealed record is 80 bytes")
         row = lambda table, i: np.asarray(table[i], dtype=np.uint8)      # noqa: E731
-        sig_v = signatures.verify(np.stack([row(sig_pks, d) for _, d in cs]), [secret_sharing.bundle_message(round_no, d, c, rec[i]) for i, (c, d) in enumerate(cs)],
-                                  np.stack([np.asarray(c[3], dtype=np.uint8).reshape(-1) for c in complaints]))
+        sig_v = scheme.verify(np.stack([row(sig_pks, d) for _, d in cs]), [secret_sharing.bundle_message(round_no, d, c, rec[i]) for i, (c, d) in enumerate(cs)],
+                              np.stack([np.asarray(c[3], dtype=np.uint8).reshape(-1) for c in complaints]))
         ctxs = np.frombuffer(b"".join(secret_sharing.complaint_context(round_no, c, d) for c, d in cs), dtype=np.uint8).reshape(-1, 32)
         proof_v, shared = dleq.verify(np.stack([row(channel_pks, c) for c, _ in cs]), np.stack([row(channel_pks, d) for _, d in cs]), ctxs,
                                       np.stack([np.asarray(c[4], dtype=np.uint8).reshape(-1) for c in complaints]),
@@ -2755,7 +2813,7 @@ class pedersen_ops:
 
     @staticmethod
     def dropout_residual_terms_from_signed_shares(survivors, dropped, xs, key_shares, self_shares, key_commitments, self_commitments, public_keys,
-                                                  round_no, sig_public_keys, commitment_sigs):
+                                                  round_no, sig_public_keys, commitment_sigs, scheme=signatures):
         """dropout_residual_terms_from_verified_shares behind a check of the dealers' signatures on the commitments it uses:
         sig_public_keys = the clients' public SIGNING keys, indexed like public_keys; commitment_sigs = {client: uint8[64]}, the signature
         on secret_sharing.commitment_message(round_no, client, kind, commitments) of the row actually used -- kind 0 (key) for every dropped
@@ -2779,7 +2837,7 @@ class pedersen_ops:
             msgs.append(secret_sharing.commitment_message(round_no, c, kind, com[c]))
             sigs.append(commitment_sigs[c])
         if used:
-            verdict = signatures.verify(spk[[c for c, _, _ in used]], msgs, np.stack(sigs))
+            verdict = scheme.verify(spk[[c for c, _, _ in used]], msgs, np.stack(sigs))
             for (c, kind, _), v in zip(used, verdict):
                 if v != 0:
                     raise ValueError("client %d: the signature on its %s commitments does not verify (verdict %d)" % (c, "self-mask" if kind else "key", int(v)))

@@ -9,6 +9,7 @@
 #include "quad26.hpp"
 #include "fd_dbg.hpp"
 #include "keccak.hpp"
+#include "sha512.hpp"
 
 namespace rofl {
 
@@ -3486,6 +3487,181 @@ __global__ void __launch_bounds__(64) k_sig_verify(u32 n, const uint2 *__restric
 #pragma unroll
         for (int q = 0; q < 8; q++) v |= (u64)E[8 * w + q] << (8 * q);
         same &= v == R[w]; }
+    verdict[i] = same ? 0 : 1;
+}
+#endif
+// ================================================================ standard signatures (rofl_ed25519_public_keys / _sign / _verify)
+// Ed25519 as RFC 8032 section 5.1 defines it (no context, no prehash), on the curve, the tables and the scalar field of everything above:
+//   h = SHA-512(seed); a = int_le(h[0 .. 32)) with bits 0, 1, 2, 255 cleared and bit 254 set; prefix = h[32 .. 64); A = enc(a B)   (k_ed_expand, once per key)
+//   r = int_le(SHA-512(prefix || M)) mod l                                                        (k_ed_hash mode 0, once per signature)
+//   R = enc(r B)                                                                                  (k_ed_commit)
+//   k = int_le(SHA-512(R || A || M)) mod l; S = r + k a mod l; the signature is R || le32(S)      (k_ed_hash mode 2; mode 1 stops at k: verify)
+// enc: y in 255 little-endian bits, the parity of x in bit 255.  Decoding (k_ed_decode, once per key) refuses y >= p, a y with no x, and
+// x = 0 under a set sign bit (status 1), and marks the keys of small order, 8 A = identity (status 2).
+// Verdict (k_ed_check): 2 = the key's status is not 0 or S >= l; 0 = enc(S B - k A) is the 32 bytes R as they came; 1 otherwise.  The
+// cofactorless equation, compared by encoding as ref10 does; one exact equation per signature, no random weights.
+// Launches: sign 4 (expand, hash, commit, hash), verify 3 (decode, hash, check), public keys 1.  The hash is a kernel of its own because
+// the chains (k_ed_commit, k_ed_check) fill the register file as k_sig_sign / k_sig_verify do; the 64-byte digests live and die in registers.
+// Lanes of a wave run as many SHA-512 blocks as their longest message has: a lone long message is one serial chain on one lane.
+// Not constant-time, like every secret-scalar path here; a is kept reduced mod l (B has order l, and S is a residue mod l).
+#define ROFL_SC_QUARTER_MONT {{0xe91e8439u, 0xf7c8d6b0u, 0x1719297cu, 0xc1631264u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x0fffffffu}}      /* 2^256 / 4 mod l */
+// k B for the Ed25519 base point B (k canonical).  The radix-256 table's base is the representative B' the Ristretto decoder picks in B's
+// coset: B' = B + T with 4 T = 0, the same Ristretto element and another Edwards point.  4 (q B') = 4 q B for every q, so with q = k / 4 mod l
+// the table's product, doubled twice, is k B exactly -- whichever of the four representatives the table was built from.
+__device__ inline gd ed_base_mul(const niels *tabB8, const sc &k) {
+    const sc quarter = ROFL_SC_QUARTER_MONT;
+    return gd_double(gd_double_not(sg_fixed_mul8(tabB8, sc_montmul(k, quarter))));
+}
+// enc(p) as four little-endian words (RFC 8032 5.1.2)
+__device__ inline void ed_encode_words(u64 w4[4], const gd &p) {
+    const fd zi = fd_invert(p.Z);
+    const fd x = fd_mul(p.X, zi), y = fd_mul(p.Y, zi);
+    fe c = fe_canon(fd_pack(y));
+    c.v[7] |= (u32)fd_isneg(x) << 31;
+#pragma unroll
+    for (int w = 0; w < 4; w++) w4[w] = (u64)c.v[2 * w] | ((u64)c.v[2 * w + 1] << 32);
+}
+// RFC 8032 5.1.3 on the eight words of an encoding: x = |sqrt((y^2 - 1) / (d y^2 + 1))| (the even root), negated under the sign bit.  False:
+// y >= p, no root, or x = 0 with the sign bit set.  P has Z = 1 and tight coordinates.  (d y^2 + 1 is never 0: -1 / d is no square.)
+__device__ inline bool ed_decode(gd &P, const u32 w[8]) {
+    fe y8;
+#pragma unroll
+    for (int i = 0; i < 8; i++) y8.v[i] = w[i];
+    const bool sign = w[7] >> 31;
+    y8.v[7] &= 0x7fffffffu;
+    const fe c = fe_canon(y8);
+    bool canon = true;
+#pragma unroll
+    for (int i = 0; i < 8; i++) canon &= c.v[i] == y8.v[i];
+    const fd y = fd_unpack(y8), yy = fd_sq(y);
+    const fd u = fd_carry(fd_sub(yy, fd_one())), v = fd_carry(fd_add(fd_mul(fd_unpack(fe_d()), yy), fd_one()));
+    fd x;
+    const bool square = fd_sqrt_ratio_i(x, u, v);
+    if (!canon || !square || (sign && fd_iszero(x))) return false;
+    if (sign) x = fd_carry(fd_neg(x));
+    P.X = x; P.Y = y; P.Z = fd_one(); P.T = fd_mul(x, y);
+    return true;
+}
+// the message words of sha512_pre_msg on the device: M starts at ANY byte of `bytes` (8-byte aligned, zero-padded to a whole word and
+// one more: StagedCall's kPadded), so a word is put together from the two aligned words that hold it, as labelled_digest does; only
+// aligned words that hold a byte of M are read
+struct EdMsgWords {
+    const u64 *a; u64 lastw; u32 sh;
+    __device__ __forceinline__ EdMsgWords(const uint8_t *bytes, u64 o, u64 len) {
+        const u32 mis = (u32)o & 7u;
+        a = reinterpret_cast<const u64 *>(bytes + (o - mis)); sh = 8 * mis; lastw = len ? (mis + len - 1) >> 3 : 0;
+    }
+    __device__ __forceinline__ u64 operator()(u64 k) const {
+        const u64 lo = a[k], hi = (sh && k + 1 <= lastw) ? a[k + 1] : 0;
+        return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+    }
+};
+#if ROFL_KG(4)
+// ek[j] = a (reduced mod l) | prefix, pk[j] = A of seed j, one thread per key: one SHA-512 block, the clamp, a B from the radix-256 table
+__global__ void __launch_bounds__(64) k_ed_expand(u32 n_keys, const u64 *__restrict__ seeds /* [n_keys][4] */, const niels *tabB8, u64 *__restrict__ ek /* [n_keys][8] */,
+                                                  u64 *__restrict__ pk /* [n_keys][4] */) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_keys) return;
+    u64 H[8], w[16];
+    sha512_init(H);
+#pragma unroll
+    for (int i = 0; i < 16; i++) w[i] = i < 4 ? __builtin_bswap64(seeds[4 * (size_t)j + i]) : 0;
+    w[4] = 0x8000000000000000ULL; w[15] = 256;
+    sha512_block(H, w);
+    u64 d[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) d[i] = __builtin_bswap64(H[i]);
+    d[0] &= ~7ULL; d[3] = (d[3] & 0x3fffffffffffffffULL) | 0x4000000000000000ULL;
+    sc a;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { a.v[2 * i] = (u32)d[i]; a.v[2 * i + 1] = (u32)(d[i] >> 32); }
+    a = sc_from_mont(sc_to_mont(a));
+    u64 *e = ek + 8 * (size_t)j;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { e[i] = (u64)a.v[2 * i] | ((u64)a.v[2 * i + 1] << 32); e[4 + i] = d[4 + i]; }
+    u64 A[4];
+    ed_encode_words(A, ed_base_mul(tabB8, a));
+#pragma unroll
+    for (int i = 0; i < 4; i++) pk[4 * (size_t)j + i] = A[i];
+}
+// One SHA-512 chain per signature i of key refs[i].x on message refs[i].y (refs == nullptr: key i, message i), then the wide reduction:
+//   mode 0: rbuf[i] = int_le(SHA-512(prefix || M)) mod l, the prefix from ek
+//   mode 1: kbuf[i] = int_le(SHA-512(R || A || M)) mod l, R = sig[i][0 .. 32) as it came, A = pk's bytes; skipped under a refused key (kstatus)
+//   mode 2: the same k, and sig[i][32 .. 64) = rbuf[i] + k a mod l with a from ek (kbuf, kstatus unused)
+__global__ void __launch_bounds__(64) k_ed_hash(u32 n, u32 mode, const uint2 *__restrict__ refs, const u64 *__restrict__ ek /* [n_keys][8] */, const u64 *__restrict__ pk /* [n_keys][4] */,
+                                                const u32 *__restrict__ kstatus, const uint8_t *__restrict__ bytes, const u64 *__restrict__ off /* [n_msgs + 1] */,
+                                                uint8_t *sig /* [n][64], 16-byte aligned */, sc *rbuf /* [n] */, sc *__restrict__ kbuf /* [n] */) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 ka = i, mb = i;
+    if (refs) { const uint2 r = refs[i]; ka = r.x; mb = r.y; }
+    if (mode == 1u && kstatus[ka] != 0u) return;
+    u64 pre[8];
+    if (mode == 0u) {
+#pragma unroll
+        for (int w = 0; w < 4; w++) { pre[w] = ek[8 * (size_t)ka + 4 + w]; pre[4 + w] = 0; }
+    } else {
+        const u64 *rp = reinterpret_cast<const u64 *>(sig + (size_t)64 * i);
+#pragma unroll
+        for (int w = 0; w < 4; w++) { pre[w] = rp[w]; pre[4 + w] = pk[4 * (size_t)ka + w]; }
+    }
+    const u64 o = off[mb], len = off[mb + 1] - o;
+    u64 H[8];
+    sha512_pre_msg(H, pre, mode == 0u ? 4u : 8u, EdMsgWords(bytes, o, len), len);
+    const sc h = sha512_scalar(H);
+    if (mode == 0u) { store_sc(&rbuf[i], h); return; }
+    if (mode == 1u) { store_sc(&kbuf[i], h); return; }
+    sc a;
+#pragma unroll
+    for (int w = 0; w < 4; w++) { const u64 v = ek[8 * (size_t)ka + w]; a.v[2 * w] = (u32)v; a.v[2 * w + 1] = (u32)(v >> 32); }
+    store_sc(reinterpret_cast<sc *>(sig + (size_t)64 * i + 32), sc_add(load_sc(&rbuf[i]), sc_montmul(sc_to_mont(h), a)));      // (k R) a R^-1 = k a, canonical
+}
+// sig[i][0 .. 32) = R = enc(rbuf[i] B), one thread per signature
+__global__ void __launch_bounds__(64) k_ed_commit(u32 n, const sc *__restrict__ rbuf, const niels *tabB8, uint8_t *__restrict__ sig /* [n][64], 16-byte aligned */) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u64 R[4];
+    ed_encode_words(R, ed_base_mul(tabB8, load_sc(&rbuf[i])));
+    uint4 *o = reinterpret_cast<uint4 *>(sig + (size_t)64 * i);
+    o[0] = make_uint4((u32)R[0], (u32)(R[0] >> 32), (u32)R[1], (u32)(R[1] >> 32));
+    o[1] = make_uint4((u32)R[2], (u32)(R[2] >> 32), (u32)R[3], (u32)(R[3] >> 32));
+}
+#endif
+#if ROFL_KG(3)
+// pts[j] = -A_j (what the check multiplies by k), status[j] = 1 refused by the decoding, 2 of small order (three doublings reach the
+// identity), 0 fine; a refused key leaves the identity.  One thread per key: every key is decoded once, whatever signs under it.
+__global__ void __launch_bounds__(64) k_ed_decode(u32 n_keys, const u32 *__restrict__ pk /* [n_keys][8] */, ge *__restrict__ pts, u32 *__restrict__ status) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_keys) return;
+    u32 w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = pk[8 * (size_t)j + i];
+    gd P;
+    const bool ok = ed_decode(P, w);
+    if (!ok) P = gd_identity();
+    const gd Q = gd_double(gd_double_not(gd_double_not(P)));
+    const bool small = fd_iszero(Q.X) && fd_eq(Q.Y, Q.Z);
+    store_gd(&pts[j], gd_neg(P));
+    status[j] = !ok ? 1u : small ? 2u : 0u;
+}
+// verdict[i] of signature i, one thread per signature: the body of k_sig_verify with the challenge handed in (kbuf: k_ed_hash mode 1) and
+// the Edwards encoder.  S B from the radix-256 table plus k (-A) by the variable-base windows -- the exact -k A also for a key with a
+// torsion part, where (l - k) A would differ from it -- encoded and compared with R's bytes.
+__global__ void __launch_bounds__(64) k_ed_check(u32 n, const uint2 *__restrict__ refs, const ge *__restrict__ kpts, const u32 *__restrict__ kstatus, const sc *__restrict__ kbuf,
+                                                 const uint8_t *__restrict__ sig /* [n][64], 16-byte aligned */, const niels *tabB8, uint8_t *__restrict__ verdict) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 ka = refs ? refs[i].x : i;
+    const uint4 *sp = reinterpret_cast<const uint4 *>(sig + (size_t)64 * i);
+    const uint4 r0 = sp[0], r1 = sp[1];
+    const sc s = load_sc(reinterpret_cast<const sc *>(sp + 2));
+    if (kstatus[ka] != 0u || sc_geq_l(s.v)) { verdict[i] = 2; return; }
+    const u64 R[4] = {(u64)r0.x | ((u64)r0.y << 32), (u64)r0.z | ((u64)r0.w << 32), (u64)r1.x | ((u64)r1.y << 32), (u64)r1.z | ((u64)r1.w << 32)};
+    u64 E[4];
+    ed_encode_words(E, gd_add(ed_base_mul(tabB8, s), sg_var_mul(load_sc(&kbuf[i]), load_gd(&kpts[ka]))));
+    bool same = true;
+#pragma unroll
+    for (int w = 0; w < 4; w++) same &= E[w] == R[w];
     verdict[i] = same ? 0 : 1;
 }
 #endif

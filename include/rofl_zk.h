@@ -846,8 +846,12 @@ int rofl_get_l2_clip_bounds(size_t range, unsigned fp_bits, unsigned fp_frac, fl
 /* ---- server-side extraction of the aggregate (bsgs32.rs:14-73, pedersen_ops.rs:27-53 discrete_log_vec_table) ----
  * BSGSTable::new(table_size) is built once per (table_size) on the device and cached; every point goes through
  * solve_discrete_log_with_neg with max_it = 2^bsgs_bits / table_size giant steps; values wrap to bsgs_bits bits like
- * BSGS_URawFix.  bsgs_bits = 8 (fp8) or 16 (fp16/fp32/fp64 builds, fp.rs:42-108).  A point whose log is not found in
- * either direction returns 11 (the reference unwraps None). */
+ * BSGS_URawFix.  bsgs_bits = 8 (fp8) or 16 (fp16/fp32/fp64 builds, fp.rs:42-108); 32 runs the same walk.  bsgs_bits = 24 and 40
+ * read sums that do not fit 16 bits (48 clients of 16-bit updates: 22 bits; a round of 32-bit updates: 38): same semantics, same
+ * scalars, on a solver built for many giant steps; they require table_size < 2^bsgs_bits.  Any other width,
+ * table_size 0 or >= 2^30 is 11, decided before the device is touched.  A point whose log is not found in either direction
+ * returns 11 (the reference unwraps None).  The float outputs of rofl_acc_extract* convert the scalar with (fp_bits, fp_frac) as
+ * before: a caller whose sum exceeds its fp_bits passes fp = (64, frac); the exact scalars come from rofl_discrete_log_vec. */
 int rofl_discrete_log_vec(const uint8_t *points32, size_t d, size_t table_size, unsigned bsgs_bits, uint8_t *scalars_out32);
 
 /* ---- server-side aggregation on the device (params.rs:74-147 EncModelParamsAccumulator, server.rs:504-507, 696-714) ----

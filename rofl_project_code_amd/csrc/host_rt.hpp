@@ -560,6 +560,9 @@ struct Ctx {
     }
     struct Bsgs { uint8_t *keys; u32 *slots; u32 mask; };
     std::map<size_t, Bsgs> bsgs;                          // table_size -> baby-step table
+    struct Wdlog { unsigned long long *slots; u64 mask; };
+    std::map<size_t, Wdlog> wdlog;                        // table_size -> the wide solver's table (bsgs_bits 24 / 40), keyed by (x y)^2
+    DevBuf wd_flag;                                       // one word per point of a wide solve: open / found / undecodable
     std::unique_ptr<HostPool> pool;
     size_t fold_min = 1024;
     size_t msm_small_max = 8192;      // ROFL_MSM_SMALL_MAX: generic MSMs with at most this many terms per problem side run as one fused launch (0 = off)

@@ -5070,6 +5070,143 @@ __global__ void __launch_bounds__(64) k_bsgs_solve(u32 d, const uint8_t *points,
 }
 #endif
 
+// ================================================================ wide discrete log: bsgs_bits 24 and 40
+// The walk above pays a Ristretto encoding (an inverse square root) per giant step.  Here a step's hash key is k(P) = (T/Z)^2 = (x y)^2 of
+// whatever Edwards representative the walk holds: adding a 4-torsion point maps (x, y) to (-x, -y) or (+-i y, +-i x) and negation maps x to
+// -x, so k is constant on a Ristretto class AND on its negative.  That costs one inversion, which a lane shares over WD_K consecutive steps
+// of its own walk (Montgomery's trick); the per-step values wait in LDS, one 64-lane column per limb (no bank conflicts, no barrier: a lane
+// reads only what it wrote).  Per step: 9 multiplications forward (T c, c Z, the mixed addition), 2 + a squaring on the way back, and 1/WD_K
+// of an inversion (254 squarings + 11 multiplications).
+//
+// k(x B) = k(-x B): the table of x = 0 .. m answers for -m .. m, so the giant stride is 2 m and ONE pass finds both signs.  The integer v
+// with M = v B and |v| <= max_it m is unique (it is far below l / 2), and bsgs_model.solve returns sign(v) (|v| mod 2^bits) exactly when
+// |v| <= max_it m: its first hit of the + walk, or of the - walk, is that v.  So any confirmed hit is the answer, the earliest hit is agreed
+// by one compare-and-swap on the point's flag word, and walkers of a point stop when it is set.  A key match is a candidate only: it is
+// confirmed by multiplying out v B and comparing the classes (X1 Y2 == Y1 X2 or Y1 Y2 == X1 X2), and a false one walks on.
+//
+// Table in HBM: one u64 per slot, (33 fingerprint bits << 31) | (x + 1), 0 = empty, open addressing at a load of at most 1/3; a probe is one
+// 8-byte load and the WD_K probes of a batch are in flight together.  Nothing else is stored: a confirmation recomputes x B.
+#define WD_K 7                // steps per inversion: 7 x 20 limbs x 64 lanes x 4 B = 35 KB of LDS per wave, four waves per CU
+#define WD_MIN_RUN (8 * WD_K) // a walker's start (decode + fixed-base product) costs about ten steps: no run is shorter than this
+__device__ __forceinline__ u64 wd_mix(u64 h) {
+    h ^= h >> 33; h *= 0xff51afd7ed558ccdULL; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ULL; h ^= h >> 33;
+    return h;
+}
+// The hashed keys of P, P +- S, .., P +- (WD_K - 1) S into lds[j][0..1][lane]; P leaves as P +- WD_K S.  P tight, Z != 0 (complete curve).
+__device__ __forceinline__ void wd_batch(gd &P, const nd &S, bool neg, u32 (*lds)[20][64], u32 lane) {
+    fd c = fd_one();
+#pragma unroll 1
+    for (int j = 0; j < WD_K; j++) {
+        fd u = fd_mul(P.T, c);                       // T_j Z_0 .. Z_{j-1}
+#pragma unroll
+        for (int q = 0; q < 10; q++) { lds[j][q][lane] = u.v[q]; lds[j][10 + q][lane] = P.Z.v[q]; }
+        c = fd_mul(c, P.Z);
+        P = gd_madd(P, S, neg);
+    }
+    fd inv = fd_invert(c);                           // 1 / (Z_0 .. Z_{WD_K-1})
+#pragma unroll 1
+    for (int j = WD_K - 1; j >= 0; j--) {
+        fd u, z;
+#pragma unroll
+        for (int q = 0; q < 10; q++) { u.v[q] = lds[j][q][lane]; z.v[q] = lds[j][10 + q][lane]; }
+        fd k = fd_sq(fd_mul(u, inv));                // (T_j / Z_j)^2
+        inv = fd_mul(inv, z);
+        fe kc = fe_canon(fd_pack(k));
+        u64 h = wd_mix((u64)kc.v[0] | ((u64)kc.v[1] << 32));
+        lds[j][0][lane] = (u32)h; lds[j][1][lane] = (u32)(h >> 32);
+    }
+}
+#if ROFL_KG(3)
+// Thread t inserts x = t run .. t run + run - 1 (<= m): one fixed-base product for the start, then steps of B under shared inversions.
+__global__ void __launch_bounds__(64) k_wdlog_build(u64 m, u32 run /* a multiple of WD_K */, niels B1, const niels *tabB, unsigned long long *slots, u64 slot_mask) {
+    __shared__ u32 lds[WD_K][20][64];
+    const u32 lane = threadIdx.x;
+    const u64 x0 = ((u64)blockIdx.x * 64 + lane) * run;
+    if (x0 > m) return;
+    gd P = sg_fixed_mul(tabB, sc_from_u64(x0));
+    const nd S = nd_unpack(B1);
+    for (u32 s = 0; s < run && x0 + s <= m; s += WD_K) {
+        wd_batch(P, S, false, lds, lane);
+#pragma unroll 1
+        for (int j = 0; j < WD_K; j++) {
+            const u64 x = x0 + s + j;
+            if (x > m) break;
+            const u64 h = (u64)lds[j][0][lane] | ((u64)lds[j][1][lane] << 32);
+            const unsigned long long word = ((h >> 31) << 31) | (x + 1);
+            u64 sl = h & slot_mask;
+            while (atomicCAS(&slots[sl], 0ULL, word) != 0ULL) sl = (sl + 1) & slot_mask;
+        }
+    }
+}
+#endif
+// A candidate: the walk point M -+ base B has the key of x B, so M = v B for v = +-base +- x if it is a true one.  Both signs of x are
+// multiplied out and compared with M as Ristretto classes; a confirmed v within reach claims the point's flag and writes the scalar the
+// model returns.  -> true when this point is settled (by this lane or another).
+__device__ __noinline__ bool wd_confirm(const uint8_t *pt, const niels *tabB, u64 base, bool back, u64 x, u64 reach, u32 bits, u32 *flag, uint8_t *out) {
+    gd M;
+    if (!sg_decode(M, pt)) return false;
+    for (int sgn = 0; sgn < (x ? 2 : 1); sgn++) {
+        const long long v = (back ? -(long long)base : (long long)base) + (sgn ? -(long long)x : (long long)x);
+        const bool negv = v < 0;
+        const u64 mag = (u64)(negv ? -v : v);
+        if (mag > reach) continue;
+        const gd G = sg_fixed_mul(tabB, sc_from_u64(mag));
+        const fd xy = fd_mul(M.X, G.Y), yx = fd_mul(M.Y, G.X), yy = fd_mul(M.Y, G.Y), xx = fd_mul(M.X, G.X);
+        // -M is (-X, Y): the two equalities with the sign of X1 turned
+        const bool eq = negv ? (fd_iszero(fd_add(xy, yx)) || fd_iszero(fd_add(yy, xx))) : (fd_eq(xy, yx) || fd_eq(yy, xx));
+        if (!eq) continue;
+        if (atomicCAS(flag, 0u, 1u) == 0u) {
+            sc r = sc_from_u64(mag & ((1ULL << bits) - 1));
+            if (negv) r = sc_neg(r);
+            sc_tobytes(out, r);
+        }
+        return true;
+    }
+    return false;
+}
+#if ROFL_KG(3)
+// wp walkers per point (even): walker w of point i takes the steps a = (w / 2) run .. + run - 1 of the walk M - a G (w even) or M + a G
+// (w odd), G = 2 m B.  flag[i]: 0 open, 1 found (out[i] written), 2 undecodable.
+__global__ void __launch_bounds__(64) k_wdlog_solve(u32 d, const uint8_t *points, u32 wp, u64 run /* a multiple of WD_K */, u64 m, u32 bits, u64 reach /* max_it m */,
+                                                    niels G2m, const niels *tabB, const unsigned long long *slots, u64 slot_mask, u32 *flag, uint8_t *out, u32 *status) {
+    __shared__ u32 lds[WD_K][20][64];
+    const u32 lane = threadIdx.x;
+    const u64 t = (u64)blockIdx.x * 64 + lane;
+    if (t >= (u64)d * wp) return;
+    const u32 i = (u32)(t / wp), w = (u32)(t % wp);
+    const bool back = w & 1;
+    const uint8_t *pt = points + (size_t)32 * i;
+    gd P;
+    if (!sg_decode(P, pt)) { if (w == 0) { atomicOr(status, 4u); flag[i] = 2u; } return; }
+    u64 a = (u64)(w >> 1) * run;
+    if (a) {
+        gd G = sg_fixed_mul(tabB, sc_from_u64(2 * m * a));      // < 2^42
+        if (!back) { G.X = fd_carry(fd_neg(G.X)); G.T = fd_carry(fd_neg(G.T)); }
+        P = gd_add(P, G);
+    }
+    const nd S = nd_unpack(G2m);
+    for (u64 s = 0; s < run; s += WD_K, a += WD_K) {
+        if (((const volatile u32 *)flag)[i]) return;
+        wd_batch(P, S, !back, lds, lane);
+        u64 h[WD_K]; unsigned long long e[WD_K];
+#pragma unroll
+        for (int j = 0; j < WD_K; j++) { h[j] = (u64)lds[j][0][lane] | ((u64)lds[j][1][lane] << 32); e[j] = slots[h[j] & slot_mask]; }
+#pragma unroll
+        for (int j = 0; j < WD_K; j++) {
+            u64 sl = h[j] & slot_mask; unsigned long long ej = e[j];
+            while (ej) {
+                if ((ej >> 31) == (h[j] >> 31) && wd_confirm(pt, tabB, 2 * m * (a + j), back, (ej & 0x7fffffffu) - 1, reach, bits, flag + i, out + (size_t)32 * i)) return;
+                sl = (sl + 1) & slot_mask; ej = slots[sl];
+            }
+        }
+    }
+}
+__global__ void __launch_bounds__(TPB) k_wdlog_finish(u32 d, const u32 *flag, u32 *status) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < d && flag[i] == 0u) atomicOr(status, 8u);
+}
+#endif
+
 // ================================================================ micro-benchmark: field multiply rate
 #if ROFL_KG(4)
 __global__ void __launch_bounds__(TPB) k_bench_femul(u32 iters, const fe *in, fe *out) {

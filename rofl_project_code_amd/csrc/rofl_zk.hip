@@ -118,9 +118,45 @@ void timing_end(Ctx &C) {
 }
 
 
+// the (table_size, bsgs_bits) pairs the extraction entries accept
+bool valid_bsgs(size_t table_size, unsigned bsgs_bits) {
+    if (table_size == 0 || table_size >= (1u << 30)) return false;
+    if (bsgs_bits == 24 || bsgs_bits == 40) return table_size < ((u64)1 << bsgs_bits);      // the wide solver: no step of 0
+    return bsgs_bits == 8 || bsgs_bits == 16 || bsgs_bits == 32;
+}
+// bsgs_bits 24 and 40: the solver for many giant steps (kernels.hpp, "wide discrete log").  Its table is cached per table_size like C.bsgs.
+// The split: a point's 2 (J + 1) steps, J = ceil(max_it / 2) in each direction, go to wp walkers so that d * wp fills the chip -- 256 CUs
+// hold four 64-lane waves of k_wdlog_solve each (its LDS), 65 536 lanes -- but no walker gets fewer than WD_MIN_RUN steps.
+void wdlog_solve_launch(Ctx &C, size_t d, const uint8_t *dp, size_t table_size, unsigned bsgs_bits, uint8_t *dout, u32 *status) {
+    const u64 m = table_size;
+    auto it = C.wdlog.find(table_size);
+    if (it == C.wdlog.end()) {
+        Ctx::Wdlog b; u64 nslots = 1; while (nslots < 3 * (m + 1)) nslots <<= 1;
+        b.mask = nslots - 1;
+        HIPCHK(hipMalloc(&b.slots, 8 * nslots));
+        HIPCHK(hipMemsetAsync(b.slots, 0, 8 * nslots, C.stream));
+        const niels B1 = h51::to_niels32(h_fixed_mul(C.ht.B5, sc_from_u64(1)));
+        const u64 threads = (m + WD_MIN_RUN) / WD_MIN_RUN;      // ceil((m + 1) / run)
+        ROFL_LAUNCH(k_wdlog_build, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, C.stream, m, (u32)WD_MIN_RUN, B1, C.d_tabB, b.slots, b.mask);
+        it = C.wdlog.emplace(table_size, b).first;
+    }
+    const Ctx::Wdlog &T = it->second;
+    const u64 max_it = ((u64)1 << bsgs_bits) / m, per_dir = (max_it + 1) / 2 + 1;
+    u64 half = 65536 / (2 * (u64)d);
+    half = std::max<u64>(1, std::min<u64>(half, (per_dir + WD_MIN_RUN - 1) / WD_MIN_RUN));
+    const u64 run = ((per_dir + half - 1) / half + WD_K - 1) / WD_K * WD_K;
+    const u32 wp = (u32)(2 * half);
+    const niels G2m = h51::to_niels32(h_fixed_mul(C.ht.B5, sc_from_u64(2 * m)));
+    u32 *flag = C.wd_flag.as<u32>(d);
+    HIPCHK(hipMemsetAsync(flag, 0, 4 * d, C.stream));
+    ROFL_LAUNCH(k_wdlog_solve, dim3((unsigned)(((u64)d * wp + 63) / 64)), dim3(64), 0, C.stream, (u32)d, dp, wp, run, m, bsgs_bits, max_it * m, G2m, C.d_tabB,
+                (const unsigned long long *)T.slots, T.mask, flag, dout, status);
+    ROFL_LAUNCH(k_wdlog_finish, grid1(d), dim3(TPB), 0, C.stream, (u32)d, (const u32 *)flag, status);
+}
 // BSGSTable::new(table_size) on the device, built once per table_size and cached on the device's primary lane (callers hold it: acquire_lane(true)),
 // then one k_bsgs_solve over the d compressed points at dp (device) -> canonical scalars at dout; status bit 8: a log that was not found
 void bsgs_solve_launch(Ctx &C, size_t d, const uint8_t *dp, size_t table_size, unsigned bsgs_bits, uint8_t *dout, u32 *status) {
+    if (bsgs_bits == 24 || bsgs_bits == 40) return wdlog_solve_launch(C, d, dp, table_size, bsgs_bits, dout, status);
     auto it = C.bsgs.find(table_size);
     if (it == C.bsgs.end()) {
         Ctx::Bsgs b; u32 nslots = 1; while (nslots < 2 * (table_size + 1)) nslots <<= 1;
@@ -996,7 +1032,7 @@ struct AccOpening { const uint8_t *bytes; size_t term_count; const rofl_blind_te
 // differ in the finishing launch only: k_acc_finish (R == the initial R, L encoded as it is) or, with an opening, k_acc_open (R == initial R
 // + s B, L - s B~ encoded).  The sum is read, never written.
 int acc_extract(uint64_t h, const AccOpening *op, size_t table_size, unsigned bsgs_bits, unsigned fp_bits, unsigned fp_frac, float *out, int *ok_out, size_t *first_bad_out) {
-    if (!out || !ok_out || table_size == 0 || table_size >= (1u << 30) || !(bsgs_bits == 8 || bsgs_bits == 16 || bsgs_bits == 32) || !valid_fp(fp_bits, fp_frac))
+    if (!out || !ok_out || !valid_bsgs(table_size, bsgs_bits) || !valid_fp(fp_bits, fp_frac))
         return fail(ROFL_BAD_PARAM, "bad parameter");
     std::vector<uint8_t> hv;      // (outlives the lane: its release delivers the staged scalars here)
     return with_acc(h, no_check, [&](Acc &A) -> int {
@@ -2711,9 +2747,9 @@ int rofl_dbg_quantize(unsigned site, size_t rows, size_t d, size_t dpad, size_t 
     });
 }
 int rofl_discrete_log_vec(const uint8_t *points32, size_t d, size_t table_size, unsigned bsgs_bits, uint8_t *scalars_out32) {
+    if (!valid_bsgs(table_size, bsgs_bits)) return fail(ROFL_BAD_PARAM, "bad parameter");      // (before the device is touched)
     return guarded([&]() -> int {
         LaneLock lane_lock = acquire_lane(true); Ctx &C = *lane_lock.c;
-        if (table_size == 0 || table_size >= (1u << 30) || !(bsgs_bits == 8 || bsgs_bits == 16 || bsgs_bits == 32)) return fail(ROFL_BAD_PARAM, "bad parameter");
         if (d == 0) return ROFL_OK;
         C.init();
         timing_begin(C);

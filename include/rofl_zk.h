@@ -524,6 +524,26 @@ int rofl_dh_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32 /* m
                    size_t n_peer, const uint8_t *peer_pk32,
                    size_t n_pairs, const rofl_dh_pair_t *pairs /* NULL: all n_own x n_peer, own-major; n_pairs must equal the product */,
                    uint8_t *out32 /* n_pairs x 32 */, uint8_t *status_out /* n_pairs */);
+/* Standard key agreement: batched X25519, bit for bit the function X25519 of RFC 7748 section 5 -- what a key store, an HSM, libsodium's
+ * crypto_scalarmult_curve25519 and TLS compute -- beside the Ristretto agreement above and with its calling conventions.
+ *   secret key: 32 bytes, clamped as the RFC says (k[0] &= 248; k[31] &= 127; k[31] |= 64), never reduced mod l; no key is refused;
+ *   public key: X25519(sk, 9);
+ *   shared secret of own key a and peer public key u_b: the 32 bytes X25519(a, u_b), raw, with NO post-hash (rofl_aead_* with derive_round
+ *     and pairwise_round_seed hash it themselves) -- symmetric: shared(a, pk_b) == shared(b, pk_a);
+ *   peer u: bit 255 is masked off and the non-canonical values p .. 2^255 - 1 are accepted and reduced, so status 1 never occurs;
+ *   status 2: the result is 32 zero bytes (the peer key is one of the small-order values, RFC 7748 section 6.1: the check libsodium makes);
+ *     every other pair is unaffected.  The output is the canonical little-endian encoding of x2 / z2 (z2 = 0 gives 0).
+ * Pairs, limits, the 11 cases (but none for a key's value), empty calls and "host pointers only" are those of rofl_dh_shared.  One lane:
+ * one upload, one or two launches of one kernel (the own public keys are the same ladder on u = 9), one download.  Secret keys and shared
+ * secrets are secrets: the lane's pinned staging copies and device workspace that held them are overwritten with zeros before the call
+ * returns or unwinds.  NOT promised constant-time, like every other secret-scalar path of this library (the ladder itself has no
+ * key-dependent branch or address).  A shared secret of X25519 and one of rofl_dh_shared have nothing in common: both sides of a channel
+ * use the same agreement. */
+int rofl_x25519_public_keys(size_t n, const uint8_t *sk32, uint8_t *pk_out32);
+int rofl_x25519_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32 /* may be NULL */,
+                       size_t n_peer, const uint8_t *peer_pk32,
+                       size_t n_pairs, const rofl_dh_pair_t *pairs /* NULL: all, own-major */,
+                       uint8_t *out32, uint8_t *status_out);
 /* Secret sharing of the mask secrets (Shamir, over the scalar field mod l), so that a round survives an HONEST dropout without opening the
  * update of the client that left.
  *   secret: 32 bytes read as a little-endian integer and reduced mod l, as keys and openings are; zero is allowed here (only rofl_dh_*

@@ -242,6 +242,14 @@ int rofl_dbg_rotate_tile_log2(void);
 /* one pair of rofl_dh_shared from the host arithmetic (no GPU): out32 and *status as that call gives them; own_pk32 == NULL: computed from sk32.
  * Returns 11 for a null pointer or a secret key that is 0 mod l. */
 int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint8_t peer_pk32[32], uint8_t out32[32], uint8_t *status);
+/* n items of X25519 on the host, one thread, no GPU, from the ladder text the kernel compiles: out32[i] = X25519(sk32[i], u_in32[i]) and
+ * status[i] as rofl_x25519_shared gives them; u_in32 == NULL: u = 9 (the public keys).  Returns 11 for a null pointer; n = 0 returns 0. */
+int rofl_dbg_host_x25519(size_t n, const uint8_t *sk32, const uint8_t *u_in32, uint8_t *out32, uint8_t *status);
+/* rofl_x25519_shared with the layout chosen by the caller: route 0 = the library's choice (one ladder per lane quad while 4 n_pairs <=
+ * 65 536, else one per lane), 1 = one ladder per lane, 2 = one ladder per lane quad; any other route is 11.  Same checks, same bytes; what
+ * scripts/gpu_x25519.py finds the crossover with.  The public entry is this with route 0. */
+int rofl_dbg_x25519_shared(unsigned route, size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32,
+                           size_t n_pairs, const rofl_dh_pair_t *pairs, uint8_t *out32, uint8_t *status_out);
 /* rofl_shamir_share / rofl_shamir_reconstruct on the host's scalar arithmetic and host Keccak, one thread, no GPU: the same parameters, the
  * same checks (11) and the same bytes.  What the host tests pin the definition with, and the baseline of profiles/shamir_sharing.json. */
 int rofl_dbg_host_shamir_share(size_t n_secrets, const uint8_t *secrets32, const uint8_t *coef_seeds32, size_t threshold, size_t n_shares,

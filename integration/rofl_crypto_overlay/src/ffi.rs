@@ -195,6 +195,12 @@ extern "C" {
     /// peer key is not canonical / is the identity (32 zero bytes out); own_pk_out32 may be null
     pub fn rofl_dh_shared(n_own: usize, sk32: *const u8, own_pk_out32: *mut u8, n_peer: usize, peer_pk32: *const u8,
         n_pairs: usize, pairs: *const RoflDhPair, out32: *mut u8, status_out: *mut u8) -> c_int;
+    /// RFC 7748 X25519, the standard agreement beside rofl_dh_*: pk = X25519(clamp(sk), 9) for n secret keys; no key is refused
+    pub fn rofl_x25519_public_keys(n: usize, sk32: *const u8, pk_out32: *mut u8) -> c_int;
+    /// same shape as rofl_dh_shared; out32 is the raw X25519(a, u_b) with no post-hash; status 2 per pair = the result is all zero (a
+    /// small-order peer key), status 1 never occurs
+    pub fn rofl_x25519_shared(n_own: usize, sk32: *const u8, own_pk_out32: *mut u8, n_peer: usize, peer_pk32: *const u8,
+        n_pairs: usize, pairs: *const RoflDhPair, out32: *mut u8, status_out: *mut u8) -> c_int;
     /// Shamir shares of n_secrets scalars (32 bytes each, reduced mod l) at threshold `threshold`: shares_out32[s][i] = f_s(xs[i]), secret-major;
     /// the coefficients of f_s come from coef_seeds32[s]; xs null = the points 1 .. n_shares, otherwise nonzero and distinct
     pub fn rofl_shamir_share(n_secrets: usize, secrets32: *const u8, coef_seeds32: *const u8, threshold: usize, n_shares: usize, xs: *const u32,

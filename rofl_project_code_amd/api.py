@@ -1335,6 +1335,46 @@ def _keys32(a, what):
     return np.ascontiguousarray(a).reshape(-1, 32)
 
 
+def _agree_public(entry, sk):
+    """public_keys of key_agreement / x25519: entry(n, sk32, pk_out32) on a staging copy of the keys that is zeroed afterwards"""
+    sk = _keys32(sk, "a secret key")
+    n = sk.shape[0]
+    out = np.zeros((n, 32), dtype=np.uint8)
+    buf = (ctypes.c_ubyte * max(n * 32, 1))()
+    try:
+        ctypes.memmove(buf, sk.ctypes.data, n * 32)
+        _check(entry(_sz(n), buf, _ptr(out)))
+    finally:
+        ctypes.memset(buf, 0, ctypes.sizeof(buf))
+    return out
+
+
+def _agree_shared(entry, public_keys, sk, peer_pks, pairs, with_public):
+    """shared_secrets of key_agreement / x25519: entry is rofl_dh_shared or a call of its shape"""
+    sk, pk = _keys32(sk, "a secret key"), _keys32(peer_pks, "a public key")
+    n_own, n_peer = sk.shape[0], pk.shape[0]
+    if pairs is None:
+        n_pairs, parr = n_own * n_peer, None
+    else:
+        pl = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n_pairs = pl.shape[0]
+        if n_pairs and (pl.min() < 0 or pl[:, 0].max() >= n_own or pl[:, 1].max() >= n_peer):
+            raise ValueError("a pair names a key that is not in the call")
+        parr = (_DhPair * max(n_pairs, 1))()
+        np.frombuffer(parr, dtype=np.uint32)[:2 * n_pairs] = pl.astype(np.uint32).reshape(-1)
+    out, status = np.zeros((n_pairs, 32), dtype=np.uint8), np.zeros(n_pairs, dtype=np.uint8)
+    own_pk = np.zeros((n_own, 32), dtype=np.uint8) if with_public else None
+    buf = (ctypes.c_ubyte * max(n_own * 32, 1))()
+    try:
+        ctypes.memmove(buf, sk.ctypes.data, n_own * 32)
+        _check(entry(_sz(n_own), buf, _ptr(own_pk) if with_public else None, _sz(n_peer), _ptr(pk), _sz(n_pairs), parr, _ptr(out), _ptr(status)))
+    finally:
+        ctypes.memset(buf, 0, ctypes.sizeof(buf))
+    if with_public and n_pairs == 0 and n_own:      # (an empty call computes nothing: the keys come from their own entry)
+        own_pk = public_keys(sk)
+    return (out, status, own_pk) if with_public else (out, status)
+
+
 class key_agreement:
     """Batched Ristretto255 Diffie-Hellman (rofl_dh_public_keys / rofl_dh_shared): where the shared secrets of the pairwise masks come from.
     A secret key is 32 bytes, reduced mod l (0 mod l is refused); the public key is encode(sk * B); the shared secret of own key a and peer key
@@ -1345,16 +1385,7 @@ class key_agreement:
     @staticmethod
     def public_keys(sk):
         """-> uint8[n, 32]"""
-        sk = _keys32(sk, "a secret key")
-        n = sk.shape[0]
-        out = np.zeros((n, 32), dtype=np.uint8)
-        buf = (ctypes.c_ubyte * max(n * 32, 1))()
-        try:
-            ctypes.memmove(buf, sk.ctypes.data, n * 32)
-            _check(lib().rofl_dh_public_keys(_sz(n), buf, _ptr(out)))
-        finally:
-            ctypes.memset(buf, 0, ctypes.sizeof(buf))
-        return out
+        return _agree_public(lib().rofl_dh_public_keys, sk)
 
     @staticmethod
     def shared_secrets(sk, peer_pks, pairs=None, with_public=False):
@@ -1362,29 +1393,27 @@ class key_agreement:
         arrays, None = all n_own x n_peer pairs, own-major.  -> (uint8[n_pairs, 32], uint8[n_pairs]); status 1 = the peer key is not a
         canonical Ristretto encoding, 2 = it is the identity, and the 32 bytes of such a pair are zero.  with_public=True appends the own
         public keys uint8[n_own, 32]."""
-        sk, pk = _keys32(sk, "a secret key"), _keys32(peer_pks, "a public key")
-        n_own, n_peer = sk.shape[0], pk.shape[0]
-        if pairs is None:
-            n_pairs, parr = n_own * n_peer, None
-        else:
-            pl = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-            n_pairs = pl.shape[0]
-            if n_pairs and (pl.min() < 0 or pl[:, 0].max() >= n_own or pl[:, 1].max() >= n_peer):
-                raise ValueError("a pair names a key that is not in the call")
-            parr = (_DhPair * max(n_pairs, 1))()
-            np.frombuffer(parr, dtype=np.uint32)[:2 * n_pairs] = pl.astype(np.uint32).reshape(-1)
-        out, status = np.zeros((n_pairs, 32), dtype=np.uint8), np.zeros(n_pairs, dtype=np.uint8)
-        own_pk = np.zeros((n_own, 32), dtype=np.uint8) if with_public else None
-        buf = (ctypes.c_ubyte * max(n_own * 32, 1))()
-        try:
-            ctypes.memmove(buf, sk.ctypes.data, n_own * 32)
-            _check(lib().rofl_dh_shared(_sz(n_own), buf, _ptr(own_pk) if with_public else None, _sz(n_peer), _ptr(pk), _sz(n_pairs), parr,
-                                        _ptr(out), _ptr(status)))
-        finally:
-            ctypes.memset(buf, 0, ctypes.sizeof(buf))
-        if with_public and n_pairs == 0 and n_own:      # (an empty call computes nothing: the keys come from their own entry)
-            own_pk = key_agreement.public_keys(sk)
-        return (out, status, own_pk) if with_public else (out, status)
+        return _agree_shared(lib().rofl_dh_shared, key_agreement.public_keys, sk, peer_pks, pairs, with_public)
+
+
+class x25519:
+    """Batched X25519 bit for bit as RFC 7748 section 5 defines it (rofl_x25519_public_keys / rofl_x25519_shared): the agreement a key store,
+    an HSM, libsodium's crypto_scalarmult_curve25519 / crypto_kx and TLS speak, beside key_agreement and interchangeable with it as an
+    object (the agreement= option of the helpers that do nothing with a key but agree).  A secret key is any 32 bytes, clamped, never
+    refused; the public key is X25519(sk, 9); the shared secret is the raw X25519(a, u_b), no post-hash -- the same 32 bytes on both sides.
+    Not constant-time as a promise.  Its keys are no group elements of this library: DLEQ complaints, threshold decryption and the Feldman
+    C_0 stay on key_agreement."""
+
+    @staticmethod
+    def public_keys(sk):
+        """-> uint8[n, 32]"""
+        return _agree_public(lib().rofl_x25519_public_keys, sk)
+
+    @staticmethod
+    def shared_secrets(sk, peer_pks, pairs=None, with_public=False):
+        """key_agreement.shared_secrets on X25519: same arguments, same shapes.  A peer u is read with bit 255 masked and p .. 2^255 - 1
+        accepted, so status 1 never occurs; status 2 = the result is all zero (a small-order peer key), and the pair's 32 bytes are zero."""
+        return _agree_shared(lib().rofl_x25519_shared, x25519.public_keys, sk, peer_pks, pairs, with_public)
 
 
 def _pack_messages(messages):
@@ -1867,7 +1896,7 @@ class secret_sharing:
     def commit(secrets, coef_seeds, threshold):
         """Feldman commitments of the polynomials share() evaluates (rofl_feldman_commit) -> uint8[n_secrets, threshold, 32]:
         [s, 0] = encode((secret mod l) B), [s, k] = encode(a_k B).  For a DH key, [s, 0] is its key_agreement.public_keys output.  The
-        commitments reveal secret * B: commit only to keys and to fresh uniform secrets."""
+        commitments reveal secret * B: commit only to keys and to fresh uniform secrets.  Ristretto only: C_0 is never an x25519 public key."""
         sec, seeds = _keys32(secrets, "a secret"), _keys32(coef_seeds, "a coefficient seed")
         n, threshold = sec.shape[0], int(threshold)
         if seeds.shape[0] != n:
@@ -2102,9 +2131,10 @@ class secret_sharing:
         return b"rofl-zk/shares/1" + struct.pack("<QII", int(round_no), int(sender), int(recipient))
 
     @staticmethod
-    def _bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, own_sends):
+    def _bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, own_sends, agreement=key_agreement):
         """The pairs of a seal_shares / open_shares call, own-major: (shared secrets uint8[n, 32], nonces uint8[n, 12], ADs uint8[n, 32], the
-        flat indices of the pairs with own id != peer id, n_own, n_peer); ONE rofl_dh_shared call.  own_sends: the own client is the sender."""
+        flat indices of the pairs with own id != peer id, n_own, n_peer); ONE agreement.shared_secrets call.  own_sends: the own client is the
+        sender."""
         own, peer = np.asarray(own_ids, dtype=np.uint32).reshape(-1), np.asarray(peer_ids, dtype=np.uint32).reshape(-1)
         sk, pk = _keys32(channel_sks, "a channel secret key"), _keys32(peer_channel_pks, "a channel public key")
         if sk.shape[0] != own.size or pk.shape[0] != peer.size:
@@ -2112,7 +2142,7 @@ class secret_sharing:
         n_own, n_peer = own.size, peer.size
         o, p = np.repeat(own, n_peer), np.tile(peer, n_own)
         keep = np.flatnonzero(o != p)
-        secrets, status = key_agreement.shared_secrets(sk, pk)
+        secrets, status = agreement.shared_secrets(sk, pk)
         bad = keep[status[keep] != 0]
         if bad.size:
             secrets[...] = 0
@@ -2127,15 +2157,16 @@ class secret_sharing:
         return secrets, nonces.view(np.uint8).reshape(-1, 12), ads, keep, n_own, n_peer
 
     @staticmethod
-    def seal_shares(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, key_shares, self_shares):
+    def seal_shares(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, key_shares, self_shares, agreement=key_agreement):
         """Every hosted dealer seals its share bundles for all peers: ONE key_agreement.shared_secrets call and ONE aead.seal call.
         channel_sks[a] is the CHANNEL secret key of dealer own_ids[a] (not its mask key, not its signing key), peer_channel_pks[b] the channel
         public key of peer_ids[b]; key_shares / self_shares are uint8[n_own, n_peer, 32], [a, b] dealer own_ids[a]'s share for peer_ids[b].
         The payload is key share || self share (64 bytes), the key the pair's shared secret under derive_round = round_no, the nonce
         bundle_nonce(sender, recipient), the AD bundle_ad(round_no, sender, recipient).  -> uint8[n_own, n_peer, 80]; the record of a pair
         with own id == peer id is zeros.  A peer whose channel key is not a canonical encoding or is the identity raises ValueError naming
-        it.  The shared secrets held here are zeroed before the call returns."""
-        secrets, nonces, ads, keep, n_own, n_peer = secret_sharing._bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, True)
+        it.  The shared secrets held here are zeroed before the call returns.  agreement=x25519: the channel keys are X25519 keys and the
+        pair's secret is the raw X25519 output, what a stock client derives; both sides of a channel use the same agreement."""
+        secrets, nonces, ads, keep, n_own, n_peer = secret_sharing._bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, True, agreement)
         ks, payload = secrets[keep], None
         try:
             k, s = np.asarray(key_shares, dtype=np.uint8), np.asarray(self_shares, dtype=np.uint8)
@@ -2152,13 +2183,14 @@ class secret_sharing:
         return out.reshape(n_own, n_peer, 80)
 
     @staticmethod
-    def open_shares(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, records):
+    def open_shares(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, records, agreement=key_agreement):
         """Every hosted client opens what it was sent: records uint8[n_own, n_peer, 80], [a, b] what peer_ids[b] sealed for own_ids[a]; ONE
         key_agreement.shared_secrets call and ONE aead.open call.  -> (key_shares, self_shares uint8[n_own, n_peer, 32], verdicts
         uint8[n_own, n_peer]): verdict 1 names a bundle that was changed on the way, sealed for somebody else, by somebody else or for another
         round; its shares are zeros.  The pair with own id == peer id is skipped: verdict 0 and zero shares.  A refused channel key raises
-        ValueError naming the peer.  The shared secrets held here are zeroed before the call returns."""
-        secrets, nonces, ads, keep, n_own, n_peer = secret_sharing._bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, False)
+        ValueError naming the peer.  The shared secrets held here are zeroed before the call returns.  agreement: as in seal_shares; a
+        record sealed under the other agreement does not open (verdict 1)."""
+        secrets, nonces, ads, keep, n_own, n_peer = secret_sharing._bundle_keys(channel_sks, own_ids, peer_ids, peer_channel_pks, round_no, False, agreement)
         ks = secrets[keep]
         try:
             rec = np.asarray(records, dtype=np.uint8)
@@ -2229,7 +2261,8 @@ class secret_sharing:
     def file_complaints(channel_sks, own_ids, dealer_ids, dealer_channel_pks, round_no, which):
         """The hosted clients' complaints which = [(own id, dealer id), ...], ONE dleq.prove call: channel_sks[a] is the CHANNEL secret key of
         own_ids[a], dealer_channel_pks[b] the channel public key of dealer_ids[b].  -> (reveals uint8[n, 32], proofs uint8[n, 64]), one per
-        entry of `which`, bound to complaint_context(round_no, own id, dealer id).  A refused dealer key raises ValueError naming the dealer."""
+        entry of `which`, bound to complaint_context(round_no, own id, dealer id).  A refused dealer key raises ValueError naming the dealer.
+        Ristretto channel keys only: a DLEQ proof needs group elements, not X25519 u coordinates."""
         own, dealers = [int(i) for i in own_ids], [int(i) for i in dealer_ids]
         which = [(int(o), int(d)) for o, d in which]
         for o, d in which:
@@ -2257,7 +2290,7 @@ class secret_sharing:
           0  a share of the opened bundle is inconsistent with the dealer's commitments   -> the dealer
           2  the record opens and both shares are consistent                              -> the complainant
         A commitment row with verdict 2 raises ValueError naming the dealer.  The shared secrets and opened shares held here are zeroed
-        before the call returns."""
+        before the call returns.  Ristretto channel keys only, as file_complaints."""
         cs = [(int(c[0]), int(c[1])) for c in complaints]
         n = len(cs)
         if n == 0:
@@ -2329,7 +2362,7 @@ class threshold:
     the server combines t of them in the exponent, sk * C = sum_j lambda_j * (s_j * C), and derives the very bytes the client derived.
     Every method but combine() and check_member_keys() is a composition of key_agreement and dleq calls.  A wrong partial decryption gives
     ANOTHER key and no error from combine(): verify_partials() names it first.  What this does NOT give: key generation without a dealer,
-    proactive resharing, the transport, and constant time."""
+    proactive resharing, the transport, and constant time.  Ristretto only: combining in the exponent needs group elements, so x25519 has no part here."""
 
     @staticmethod
     def encapsulate(committee_pk, eph_keys):
@@ -2608,12 +2641,12 @@ class pedersen_ops:
 
     # ---- the seeds from key agreement (key_agreement.shared_secrets): one Diffie-Hellman call for every hosted client ----
     @staticmethod
-    def pairwise_peers_from_keys(index=None, sk=None, public_keys=None, round_no=None, clients=None):
+    def pairwise_peers_from_keys(index=None, sk=None, public_keys=None, round_no=None, clients=None, agreement=key_agreement):
         """The `peers` list [(j, seed_ij), ...] pairwise_blinding_vec takes, for every j != index of the round, from client `index`'s secret key
         and the round's public keys (uint8[n, 32], row j = client j): seed_ij = pairwise_round_seed(shared secret of the pair, round_no).
         A process that hosts several clients passes clients=[(index, sk), ...] instead of index and sk and gets one peers list per client,
         all from ONE rofl_dh_shared call (the form pairwise_blinding_vecs takes once zipped with the indices).  A refused public key raises
-        ValueError naming j and the status."""
+        ValueError naming j and the status.  agreement=x25519: the keys are X25519 keys and the secret the raw X25519 output."""
         several = clients is not None
         if several == (index is not None or sk is not None) or (not several and (index is None or sk is None)):
             raise ValueError("either index and sk, or clients=[(index, sk), ...]")
@@ -2629,7 +2662,7 @@ class pedersen_ops:
             pairs += [(c, j) for j in range(n) if j != i]
         sks = _keys32([k for _, k in clients], "a secret key")
         try:
-            secrets, status = key_agreement.shared_secrets(sks, pks, pairs)
+            secrets, status = agreement.shared_secrets(sks, pks, pairs)
         finally:
             sks[...] = 0
         res, at = [], 0
@@ -2648,12 +2681,12 @@ class pedersen_ops:
         return res if several else res[0]
 
     @staticmethod
-    def pairwise_residual_terms_from_keys(accepted, revealed, public_keys, round_no):
+    def pairwise_residual_terms_from_keys(accepted, revealed, public_keys, round_no, agreement=key_agreement):
         """pairwise_residual_terms from ONE revealed secret key per rejected client instead of one seed per (accepted, rejected) pair:
         revealed = {j: sk_j}.  Each key is first checked against the round's public keys -- public_keys([sk_j]) != public_keys[j] raises
         ValueError naming j -- then every (rejected, accepted) secret comes from one rofl_dh_shared call, and the list returned is exactly
         pairwise_residual_terms(accepted, rejected, seeds) for the seeds those keys imply: same order, same signs.  A revealed key gives away
-        every mask its owner ever shared under it: keys are per epoch."""
+        every mask its owner ever shared under it: keys are per epoch.  agreement: as in pairwise_peers_from_keys."""
         accepted, rejected = [int(i) for i in accepted], sorted(int(j) for j in revealed)
         both = set(accepted) & set(rejected)
         if both:
@@ -2666,11 +2699,11 @@ class pedersen_ops:
             return []
         sks = _keys32([revealed[j] for j in rejected], "a secret key")
         try:
-            own = key_agreement.public_keys(sks)
+            own = agreement.public_keys(sks)
             for r, j in enumerate(rejected):
                 if own[r].tobytes() != pks[j].tobytes():
                     raise ValueError("the revealed key of client %d does not belong to its public key" % j)
-            secrets, status = key_agreement.shared_secrets(sks, pks[accepted], None)
+            secrets, status = agreement.shared_secrets(sks, pks[accepted], None)
         finally:
             sks[...] = 0
         seeds = {}

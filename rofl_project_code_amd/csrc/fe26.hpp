@@ -186,6 +186,71 @@ HDN inline fd fd_invert(const fd &z) {
     return fd_mul(fd_sqn(z_250_0, 5), z11);
 }
 
+// k a for a small constant k < 2^17: ten products and one carry chain instead of the hundred of fd_mul.  Any limbs < 2^32 -> tight
+// (columns < 2^49; the carry into limb 0 is 19 (h9 >> 25) < 2^29).
+HD fd fd_mul_small(const fd &a, u32 k) {
+#if defined(ROFL_FD_CHECK)
+    assert(k < (1u << 17));
+#endif
+    return fd_reduce_cols((u64)a.v[0] * k, (u64)a.v[1] * k, (u64)a.v[2] * k, (u64)a.v[3] * k, (u64)a.v[4] * k, (u64)a.v[5] * k, (u64)a.v[6] * k, (u64)a.v[7] * k,
+                          (u64)a.v[8] * k, (u64)a.v[9] * k);
+}
+
+// ---------------------------------------------------------------- the Montgomery ladder of RFC 7748 (X25519), x-only, one thread
+// One step on (x2 : z2), (x3 : z3) with z1 = 1:
+//   A = x2 + z2, B = x2 - z2, C = x3 + z3, D = x3 - z3;   DA, CB, AA, BB;   E = AA - BB
+//   x3' = (DA + CB)^2, z3' = x1 (DA - CB)^2, x2' = AA BB, z2' = E (AA + a24 E), a24 = 121665
+// Bounds.  x1 (fd_unpack of 255 bits: limbs <= 2^26 - 1 / 2^25 - 1) and every x, z (a product or a square) are tight.  A SUM of two tight
+// values is < 2^27 + 2^20 in the even and < 2^26 + 2^20 in the odd limbs; a DIFFERENCE a + 2p - b is < 1.5 2^27 + 2^19 (even) and
+// < 1.5 2^26 + 2^19 (odd).  Both satisfy fd_sq (19 (1.5 2^27 + 2^19) < 2^32, 38 (1.5 2^26 + 2^19) < 2^32) and both operand positions of
+// fd_mul (< 2^28 + 2^20; 19 (1.5 2^27 + 2^19) < 2^32).  Every operand below is tight, a sum or a difference of tight values: A, C, DA + CB,
+// AA + a24 E (fd_mul_small's output is tight) are sums; B, D, DA - CB, E are differences.
+#define X25519_A24 121665u
+// the next key bit from the top: the key is a 256-bit shift register in eight words, so no step indexes a register array
+HD u32 x25519_next_bit(u32 k[8]) {
+    const u32 b = k[7] >> 31;
+#pragma unroll
+    for (int i = 7; i > 0; i--) k[i] = (k[i] << 1) | (k[i - 1] >> 31);
+    k[0] <<= 1;
+    return b;
+}
+HD void x25519_clamp(u32 k[8]) { k[0] &= ~7u; k[7] = (k[7] & 0x7fffffffu) | 0x40000000u; }
+HD void x25519_step(fd &x2, fd &z2, fd &x3, fd &z3, const fd &x1) {
+    const fd A = fd_add(x2, z2), B = fd_sub(x2, z2), C = fd_add(x3, z3), D = fd_sub(x3, z3);
+    const fd DA = fd_mul(D, A), CB = fd_mul(B, C), AA = fd_sq(A), BB = fd_sq(B);
+    const fd E = fd_sub(AA, BB);
+    x3 = fd_sq(fd_add(DA, CB));
+    z3 = fd_mul(x1, fd_sq(fd_sub(DA, CB)));
+    x2 = fd_mul(AA, BB);
+    z2 = fd_mul(E, fd_add(AA, fd_mul_small(E, X25519_A24)));
+}
+// X25519(k, u) as eight words, not yet canonical (fe_canon / fe_tobytes finish it): k clamped here, u with bit 255 ignored and any value
+// below 2^255 accepted.  The lanes of a wave hold different keys: the conditional swap is a select on the XOR of consecutive bits, never
+// a branch.  z2 = 0 gives 0 (fd_invert(0) = 0).  Not constant-time as a promise, like every secret-scalar path here.
+HDN inline fe x25519_ladder(const u32 key[8], const fe &u) {
+    u32 k[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) k[i] = key[i];
+    x25519_clamp(k);
+    fe um = u; um.v[7] &= 0x7fffffffu;
+    const fd x1 = fd_unpack(um);
+    fd x2 = fd_one(), z2 = fd_zero(), x3 = x1, z3 = fd_one();
+    u32 prev = x25519_next_bit(k);      // bit 255 of a clamped key: 0
+#pragma unroll 1
+    for (int t = 254; t >= 0; t--) {
+        const u32 bit = x25519_next_bit(k);
+        const bool swap = (bit ^ prev) != 0;
+        prev = bit;
+        const fd a = fd_select(x2, x3, swap), b = fd_select(x3, x2, swap), c = fd_select(z2, z3, swap), d = fd_select(z3, z2, swap);
+        x2 = a; x3 = b; z2 = c; z3 = d;
+        x25519_step(x2, z2, x3, z3, x1);
+    }
+    x2 = fd_select(x2, x3, prev != 0); z2 = fd_select(z2, z3, prev != 0);
+#pragma unroll
+    for (int i = 0; i < 8; i++) k[i] = 0;
+    return fd_pack(fd_mul(x2, fd_invert(z2)));
+}
+
 // 2d in this radix
 HD fd fd_d2() {
     fd r = {{0x2b2f159u, 0x1a6e509u, 0x22add7au, 0x0d4141du, 0x0038052u, 0x0f3d130u, 0x3407977u, 0x19ce331u, 0x1c56dffu, 0x0901b67u}};

@@ -3189,6 +3189,54 @@ __global__ void __launch_bounds__(64) k_dh_shared(u32 n_pairs, u32 n_peer, const
     dh_secret_store(o, S, ka, kb);
 }
 #endif
+// ================================================================ standard key agreement (rofl_x25519_public_keys / rofl_x25519_shared)
+// X25519 of RFC 7748 section 5 beside the Ristretto agreement above, for a peer whose key lives in a key store that speaks nothing else:
+// sk = 32 bytes clamped (never reduced mod l, none refused), pk = X25519(sk, 9), shared(a, u_b) = X25519(a, u_b), the 32 raw bytes, no
+// post-hash.  u_b is read with bit 255 masked and p .. 2^255 - 1 accepted; an all-zero result (u_b of small order) stores status 2.
+// No decoding, no square root, no table: an x-only ladder of 255 steps (x25519_step, fe26.hpp), one inversion, one canonical store.
+// ONE kernel, two layouts of the same step, the same bytes:
+//   quad == 0  one ladder per lane, blocks of 64: the throughput shape.  x1, x2, z2, x3, z3 and the step's temporaries live in registers.
+//   quad != 0  one ladder per lane quad (xq_step, quad26.hpp), 16 ladders per block: three dependent products a step instead of ten, the
+//              shape of a client with one key and a round of peers.  The inversion runs on all four lanes; lane 0 stores.
+// peer == nullptr: u = 9 for every item (the public keys).  pairs == nullptr: item i = (i / n_peer, i % n_peer).  No LDS in either layout.
+// Not constant-time as a promise, like every secret-scalar path here; there is no key-dependent branch or address on this route.
+#if ROFL_KG(3)
+__global__ void __launch_bounds__(64) k_x25519(u32 n_pairs, u32 n_peer, u32 quad, const uint2 *__restrict__ pairs, const u32 *__restrict__ sk /* [n_own][8] */,
+                                               const u32 *__restrict__ peer /* [n_peer][8] */, uint8_t *__restrict__ out /* [n_pairs][32], 16-byte aligned */,
+                                               uint8_t *__restrict__ status /* may be nullptr */) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x, i = quad ? t >> 2 : t, q = t & 3;
+    if (i >= n_pairs) return;      // (a quad leaves or stays as a whole)
+    u32 a, b;
+    if (pairs) { const uint2 p = pairs[i]; a = p.x; b = p.y; } else { a = i / n_peer; b = i - a * n_peer; }
+    u32 k[8]; fe u = fe_zero();
+    u.v[0] = 9;
+#pragma unroll
+    for (int w = 0; w < 8; w++) { k[w] = sk[8 * (size_t)a + w]; if (peer) u.v[w] = peer[8 * (size_t)b + w]; }
+    fe r;
+    if (!quad) r = x25519_ladder(k, u);
+    else {
+        x25519_clamp(k);
+        u.v[7] &= 0x7fffffffu;
+        const fd x1 = fd_unpack(u);
+        fd s = fd_select(fd_select(x1, fd_one(), q != 0), fd_zero(), q == 3);      // (x3, z3, x2, z2) = (x1, 1, 1, 0)
+        u32 prev = x25519_next_bit(k);
+#pragma unroll 1
+        for (int step = 254; step >= 0; step--) {
+            const u32 bit = x25519_next_bit(k);
+            s = xq_step(s, x1, q, (bit ^ prev) != 0);
+            prev = bit;
+        }
+        s = fd_select(s, fq_perm<2, 3, 0, 1>(s), prev != 0);
+        r = fd_pack(fd_mul(fq_bcast<2>(s), fd_invert(fq_bcast<3>(s))));
+        if (q) return;
+    }
+    r = fe_canon(r);
+    uint4 *o = reinterpret_cast<uint4 *>(out + (size_t)32 * i);
+    o[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    o[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
+    if (status) status[i] = (r.v[0] | r.v[1] | r.v[2] | r.v[3] | r.v[4] | r.v[5] | r.v[6] | r.v[7]) ? 0 : 2;
+}
+#endif
 // ================================================================ secret sharing (rofl_shamir_share / rofl_shamir_reconstruct)
 // Shamir sharing over the scalar field: secret s (32 bytes reduced mod l), coefficient seed c and threshold t define
 // f(X) = s + sum_{k=1..t-1} a_k X^k mod l with a_k = scalar k - 1 of the stream of c under the label "rofl-zk/share/v1" (the blinding stream's

@@ -216,6 +216,69 @@ int rofl_dbg_host_dh(const uint8_t sk32[32], const uint8_t *own_pk32, const uint
     dh_wipe(&k, sizeof k); dh_wipe(S, sizeof S);
     return ROFL_OK;
 }
+// ---- standard key agreement: RFC 7748 X25519 beside the Ristretto agreement above (k_x25519) ----
+}  // extern "C"
+namespace {
+// One k_x25519 launch over n items.  route 1: one ladder per lane; 2: one per lane quad; 0: the quad layout while its 4 n lanes fit the
+// 65 536 the chip holds at one wave per SIMD (the bound of wdlog_solve_launch) -- a derived rule: below it every ladder gets the short chain
+// and the chip is not yet full, beyond it the lane layout's smaller total work decides.
+void x25519_launch(Ctx &C, unsigned route, size_t n, size_t n_peer, const uint2 *pairs, const u32 *sk, const u32 *peer, uint8_t *out, uint8_t *status) {
+    const bool quad = route == 2 || (route == 0 && 4 * n <= 65536);
+    ROFL_LAUNCH(k_x25519, per_item(quad ? 4 * n : n), dim3(64), 0, C.stream, (u32)n, (u32)n_peer, quad ? 1u : 0u, pairs, sk, peer, out, status);
+}
+}  // namespace
+extern "C" {
+// The lane's copies of the secret keys and of the shared secrets -- pinned staging and device -- are overwritten with zeros before the call
+// returns or unwinds.  No key is refused: there is no zero key after clamping.
+int rofl_x25519_public_keys(size_t n, const uint8_t *sk32, uint8_t *pk_out32) {
+    if (n == 0) return ROFL_OK;
+    if (!sk32 || !pk_out32) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (n > ((size_t)1 << 20)) return fail(ROFL_BAD_PARAM, "more than 2^20 keys in one call");
+    return guarded([&]() -> int {
+        StagedCall st; Ctx &C = st.C;
+        const InPart keys = st.in(sk32, n * 32, kSecret);
+        const OutPart pk = st.out(pk_out32, n * 32);
+        st.upload();
+        x25519_launch(C, 0, n, 1, nullptr, st.dev<u32>(keys), nullptr, st.dev<uint8_t>(pk), nullptr);
+        st.finish();
+        return ROFL_OK;
+    });
+}
+int rofl_dbg_x25519_shared(unsigned route, size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32,
+                           size_t n_pairs, const rofl_dh_pair_t *pairs, uint8_t *out32, uint8_t *status_out) {
+    if (n_pairs == 0) return ROFL_OK;
+    if (!sk32 || !peer_pk32 || !out32 || !status_out || route > 2) return fail(ROFL_BAD_PARAM, "bad parameter");
+    if (int rc = dh_check_pairs(n_own, n_peer, n_pairs, pairs)) return rc;
+    return guarded([&]() -> int {
+        StagedCall st; Ctx &C = st.C;
+        const InPart keys = st.in(sk32, n_own * 32, kSecret), peer = st.in(peer_pk32, n_peer * 32), pl = st.in(pairs, n_pairs * sizeof(rofl_dh_pair_t));
+        const OutPart shared = st.out(out32, n_pairs * 32, kSecret), pk = st.out(own_pk_out32, n_own * 32), status = st.out(status_out, n_pairs);
+        st.upload();
+        if (own_pk_out32) x25519_launch(C, route, n_own, 1, nullptr, st.dev<u32>(keys), nullptr, st.dev<uint8_t>(pk), nullptr);
+        x25519_launch(C, route, n_pairs, n_peer, st.dev<uint2>(pl), st.dev<u32>(keys), st.dev<u32>(peer), st.dev<uint8_t>(shared), st.dev<uint8_t>(status));
+        st.finish();
+        return ROFL_OK;
+    });
+}
+int rofl_x25519_shared(size_t n_own, const uint8_t *sk32, uint8_t *own_pk_out32, size_t n_peer, const uint8_t *peer_pk32,
+                       size_t n_pairs, const rofl_dh_pair_t *pairs, uint8_t *out32, uint8_t *status_out) {
+    return rofl_dbg_x25519_shared(0, n_own, sk32, own_pk_out32, n_peer, peer_pk32, n_pairs, pairs, out32, status_out);
+}
+// item i = X25519(sk32[i], u32[i]) on the host from the ladder text the kernel compiles (fe26.hpp), one thread, no GPU; u32 == NULL: u = 9
+int rofl_dbg_host_x25519(size_t n, const uint8_t *sk32, const uint8_t *u_in32, uint8_t *out32, uint8_t *status) {
+    if (n == 0) return ROFL_OK;
+    if (!sk32 || !out32 || !status) return fail(ROFL_BAD_PARAM, "bad parameter");
+    for (size_t i = 0; i < n; i++) {
+        u32 k[8]; memcpy(k, sk32 + 32 * i, 32);
+        fe u = fe_zero(); u.v[0] = 9;
+        if (u_in32) memcpy(u.v, u_in32 + 32 * i, 32);
+        fe r = x25519_ladder(k, u);
+        fe_tobytes(out32 + 32 * i, r);
+        status[i] = fe_iszero(r) ? 2 : 0;
+        dh_wipe(k, sizeof k); dh_wipe(&r, sizeof r);
+    }
+    return ROFL_OK;
+}
 // ---- secret sharing: Shamir shares of mask secrets over the scalar field (k_shamir_coeffs, k_shamir_eval, k_shamir_weights, k_shamir_combine) ----
 }  // extern "C"
 namespace {

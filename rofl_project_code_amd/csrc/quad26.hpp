@@ -24,6 +24,39 @@ template <int K> __device__ __forceinline__ fd fq_bcast(const fd &a) {
     return r;
 }
 
+// lane q of the caller's quad gets the value held by lane Pq: any quad_perm, still one DPP move per limb (fq_bcast<K> is fq_perm<K, K, K, K>)
+template <int P0, int P1, int P2, int P3> __device__ __forceinline__ fd fq_perm(const fd &a) {
+    fd r;
+#pragma unroll
+    for (int i = 0; i < 10; i++) r.v[i] = (u32)__builtin_amdgcn_update_dpp(0, (int)a.v[i], P0 | (P1 << 2) | (P2 << 4) | (P3 << 6), 0xf, 0xf, false);
+    return r;
+}
+
+// ---------------------------------------------------------------- the ladder step of x25519_step (fe26.hpp) on a quad
+// A single ladder on one lane is 255 steps of ten dependent products.  Here lane q of a quad holds coordinate q of (x3, z3, x2, z2) and the
+// step is THREE dependent fd_mul deep, the operands moved by quad_perm (five moves of ten limbs a step, no LDS):
+//   sums       s = (x3, z3, x2, z2), p = its pair partner:  v = (C, D, A, B) = even lanes own + partner, odd lanes partner - own
+//   layer 1    m = (D A | C B | A A | B B)                  f = perm<1,3,2,3>(v), g = perm<2,0,2,3>(v)
+//   layer 2    r = ((DA+CB)^2 | (DA-CB)^2 | AA BB | E (AA + a24 E)), from w = (DA+CB, DA-CB, -, E) = the same sum / difference of m and its partner
+//   layer 3    lane 1 alone: x1 (DA-CB)^2                   -> (x3', z3', x2', z2')
+// The conditional swap (x2, z2) <-> (x3, z3) is perm<2,3,0,1> under a select: the lanes of a wave hold different keys.
+// Bounds: as argued at x25519_step.  Every fd_mul operand here is tight (m, r, x1, the partner of m), a sum of two tight values (C, A,
+// DA+CB, AA + a24 E) or a difference of two (D, B, DA-CB, E), and both kinds fit both operand positions of fd_mul; fd_mul_small takes any limbs.
+// The squarings run as fd_mul: the four lanes share one instruction stream.
+__device__ __forceinline__ fd xq_pair(const fd &a, const fd &p, u32 q) {      // even lanes: own + partner; odd lanes: partner - own (own must be tight)
+    return fd_select(fd_add(a, p), fd_sub(p, a), q & 1);
+}
+__device__ __forceinline__ fd xq_step(const fd &s, const fd &x1, u32 q, bool swap) {
+    const fd t = fd_select(s, fq_perm<2, 3, 0, 1>(s), swap);
+    const fd v = xq_pair(t, fq_perm<1, 0, 3, 2>(t), q);
+    const fd m = fd_mul(fq_perm<1, 3, 2, 3>(v), fq_perm<2, 0, 2, 3>(v));
+    const fd p = fq_perm<1, 0, 3, 2>(m), w = xq_pair(m, p, q);
+    const fd f = fd_select(w, m, q == 2);
+    const fd g = fd_select(fd_select(w, p, q == 2), fd_add(p, fd_mul_small(w, X25519_A24)), q == 3);
+    const fd r = fd_mul(f, g);
+    return fd_select(r, fd_mul(x1, r), q == 1);
+}
+
 // coordinate q = lane & 3 of a point: 0 X, 1 Y, 2 Z, 3 T
 struct gq { fd v; };
 

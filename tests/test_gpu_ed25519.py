@@ -2,7 +2,8 @@
 
 Every kernel runs one thread per key or per signature in blocks of 64, so n in {1, 63, 64, 65, 257} is one lane, a wave short of one, a full
 one, a crossing, and several blocks with a ragged tail.  The block-end lengths of ed25519_model.LENS go into ONE call at packed starts, so the
-lanes of a wave run different numbers of SHA-512 blocks; good signatures, every class of 1 and every class of 2 share a wave; one key signs
+lanes of a wave run different numbers of SHA-512 blocks; good signatures, every class of 1 and every class of 2 share a wave; the torsion corpus
+(ed25519_model.torsion_cases: keys and R with a small-order part) in one call, through refs, alone and past a block end; one key signs
 65 messages and 65 keys sign one; the host twin gives the device's bytes.  Then the signed round of test_gpu_signatures.py under
 scheme=ed25519, and the same helper under the default scheme with the bytes it always gave."""
 import numpy as np
@@ -12,7 +13,7 @@ import ed25519_model as E
 import sig_model as S
 import test_ed25519_host as H
 import test_gpu_signatures as T
-from test_ed25519_host import padding_batch  # noqa: F401
+from test_ed25519_host import padding_batch, torsion  # noqa: F401
 from test_gpu_signatures import R, signed_round  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +72,38 @@ def test_every_verdict_class_in_one_wave(R, padding_batch):  # noqa: F811
     # the refused key shared through refs: it condemns its signatures, not the call
     refs = [(i, i) for i in range(len(want))] + [(19, 0), (0, 0)]
     assert want[19] == 2 and R.ed25519.verify(H.rows(keys), ms, H.rows(sg + [sg[0], sg[0]], 64), refs).tolist() == want + [2, 0]
+
+
+def test_the_torsion_corpus_in_one_call(R, padding_batch, torsion):  # noqa: F811
+    seeds, msgs, pks, sigs = padding_batch
+    keys, ms, sg = H.interleaved(torsion, (pks[7].tobytes(), msgs[7], sigs[7].tobytes()))      # 163 signatures: every wave of three blocks mixes 0, 1 and 2
+    want = [0] + [v for c in torsion for v in (c[3], 0)]
+    assert want[1::2] == [c[3] for c in torsion] and 128 < len(want) <= 200
+    got = R.ed25519.verify(H.rows(keys), ms, H.rows(sg, 64)).tolist()
+    assert got == want, [c[4] for c, g in zip(torsion, got[1::2]) if c[3] != g]
+    assert got == H.host_verify(R.api.lib(), keys, ms, sg).tolist()
+
+
+def test_mixed_order_keys_shared_through_refs(R, torsion):  # noqa: F811
+    a = [c for c in torsion if c[4][0] == "a"]
+    keys = [a[4 * i][0] for i in range(7)]      # each key once: decoded once, its torsion part intact, status 0 -- no verdict below is 2
+    refs = [(j // 4, j) for j in range(28)]
+    assert all(keys[k] == a[j][0] for k, j in refs) and {c[3] for c in a} == {0, 1}
+    assert R.ed25519.verify(H.rows(keys), [c[1] for c in a], H.rows([c[2] for c in a], 64), refs).tolist() == [c[3] for c in a]
+    # the same signatures backwards, so that neighbouring lanes that share a key change places
+    back = refs[::-1]
+    assert R.ed25519.verify(H.rows(keys), [c[1] for c in a], H.rows([a[j][2] for _, j in back], 64), back).tolist() == [a[j][3] for _, j in back]
+
+
+def test_a_torsion_verdict_does_not_depend_on_its_lane(R, padding_batch, torsion):  # noqa: F811
+    seeds, msgs, pks, sigs = padding_batch
+    a = [c for c in torsion if c[4][0] == "a"]
+    assert a[0][4] == "a1" and a[0][3] == 0 and a[1][3] == 1      # the order-8 key at k = 0 mod 8, accepted, and at 4 mod 8, not
+    for c in a[:2]:
+        assert R.ed25519.verify(H.rows([c[0]]), [c[1]], H.rows([c[2]], 64)).tolist() == [c[3]]      # n = 1
+    keys, ms, sg = [pks[7].tobytes()] * 64, [msgs[7]] * 64, [sigs[7].tobytes()] * 64      # a full block of good ones, then family (a) from lane 64 on
+    got = R.ed25519.verify(H.rows(keys + [c[0] for c in a]), ms + [c[1] for c in a], H.rows(sg + [c[2] for c in a], 64)).tolist()
+    assert got == [0] * 64 + [c[3] for c in a]
 
 
 def test_one_key_many_messages_and_many_keys_one_message(R, batch257):  # noqa: F811

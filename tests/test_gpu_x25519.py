@@ -2,7 +2,8 @@
 
 k_x25519 runs one ladder per lane (route 1, 64 a block) or per lane quad (route 2, 16 a block), so n in {1, 15, 16, 17, 63, 64, 65, 257} is
 one item, a wave short of one, a full wave, a crossing and a ragged tail for both layouts.  The edge corpus goes into ONE call per route, so
-zero results, non-canonical u and ordinary pairs share a wave; route 0 is run on both sides of its rule; then a sealed round under
+zero results, non-canonical u and ordinary pairs share a wave, and so does every non-canonical u, p .. 2^255 - 1 under both values of bit 255;
+route 0 is run on both sides of its rule; then a sealed round under
 agreement=x25519."""
 import numpy as np
 import pytest
@@ -10,7 +11,7 @@ import pytest
 import x25519_model as X
 from test_ed25519_host import call, rows
 from test_gpu_signatures import R  # noqa: F401
-from test_x25519_host import host
+from test_x25519_host import host, noncanonical_want
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +50,14 @@ def test_the_edge_corpus_in_one_call_and_the_host_twin_agrees(R, route):  # noqa
     out, st, _ = device(R, route, X.CORPUS_K, X.CORPUS_U, None, len(want), with_public=False)
     assert [o.tobytes() for o in out] == [w for w, _ in want] and st == [s for _, s in want] and st.count(2) == 8 * len(X.SMALL_ORDER)
     assert host(R.api.lib(), [k for k in X.CORPUS_K for _ in X.CORPUS_U], X.CORPUS_U * len(X.CORPUS_K)) == ([o.tobytes() for o in out], st)
+
+
+@pytest.mark.parametrize("route", [1, 2])
+def test_every_noncanonical_u_in_one_call_and_the_host_twin_agrees(R, route):  # noqa: F811
+    want = noncanonical_want()
+    out, st, _ = device(R, route, X.CORPUS_K, X.NONCANONICAL_U, None, len(want), with_public=False)
+    assert [o.tobytes() for o in out] == [w for w, _ in want] and st == [s for _, s in want] and st.count(2) == 4 * len(X.CORPUS_K)
+    assert host(R.api.lib(), [k for k in X.CORPUS_K for _ in X.NONCANONICAL_U], X.NONCANONICAL_U * len(X.CORPUS_K)) == ([o.tobytes() for o in out], st)
 
 
 @pytest.mark.parametrize("n", [16384, 16385])

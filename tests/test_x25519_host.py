@@ -60,6 +60,22 @@ def test_the_host_twin_on_the_edge_corpus(hiplib, k):
     assert host(hiplib, [key], None) == ([X.public_key(key)], [0])
 
 
+def noncanonical_want():
+    """[(32 bytes, status)] of CORPUS_K x NONCANONICAL_U, key-major, from the model -- held to what reduction says: u = p + i is u = i, so zeros
+    and status 2 for i in {0, 1} and x25519(k, i) for the rest, whatever bit 255 holds"""
+    want = [X.shared(k, u) for k in X.CORPUS_K for u in X.NONCANONICAL_U]
+    assert len(X.NONCANONICAL_U) == 38 and len(set(X.NONCANONICAL_U)) == 38
+    assert all(X.P <= int.from_bytes(u, "little") % 2**255 < 2**255 and (int.from_bytes(u, "little") >> 255) == j // 19 for j, u in enumerate(X.NONCANONICAL_U))
+    assert want == [(bytes(32), 2) if j % 19 < 2 else (X.x25519(k, (j % 19).to_bytes(32, "little")), 0) for k in X.CORPUS_K for j in range(38)]
+    return want
+
+
+def test_the_host_twin_on_every_noncanonical_u(hiplib):
+    want = noncanonical_want()
+    got, st = host(hiplib, [k for k in X.CORPUS_K for _ in X.NONCANONICAL_U], X.NONCANONICAL_U * len(X.CORPUS_K))
+    assert got == [w for w, _ in want] and st == [s for _, s in want] and st.count(2) == 4 * len(X.CORPUS_K)
+
+
 @pytest.mark.parametrize("mask", [(0, 0x07), (31, 0x40), (31, 0x80), (31, 0xc0)])
 def test_keys_that_differ_only_in_the_clamped_bits(hiplib, mask):
     rng = np.random.default_rng(20261202)

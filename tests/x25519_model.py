@@ -1,6 +1,6 @@
 """X25519 of RFC 7748 section 5 on Python integers, independent of the library: what rofl_x25519_* and rofl_dbg_host_x25519 are held to.
 shared(k, u) -> (32 bytes, status): status 2 and zeros for an all-zero result (section 6.1), else 0; CORPUS_U / CORPUS_K are the edge inputs
-the host and the device tests share."""
+the host and the device tests share, NONCANONICAL_U every u in p .. 2^255 - 1 with and without bit 255."""
 import numpy as np
 
 P = 2**255 - 19
@@ -45,4 +45,6 @@ SMALL_ORDER = [_le(0), _le(1), _le(P - 1), _le(P), _le(P + 1)] + ORDER8      # e
 _rng = np.random.default_rng(20261201)
 CORPUS_U = (SMALL_ORDER + [bytes(s[:31]) + bytes([s[31] | 0x80]) for s in SMALL_ORDER]
             + [_le(2**255 - 1), _le(9 + 2**255), _le(P - 2), _le(2)] + [_rng.bytes(32) for _ in range(64)])
+# every non-canonical u: p + i, i = 0 .. 18, then the same 19 under bit 255.  Entry j is u = j % 19 once masked and reduced: zeros for 0 and 1 only
+NONCANONICAL_U = [_le(P + i) for i in range(19)] + [_le(P + i + 2**255) for i in range(19)]
 CORPUS_K = [bytes(32), b"\xff" * 32, b"\x55" * 32, b"\xaa" * 32]
